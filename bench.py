@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — GraphSLAM Gauss-Newton iterations/s on a synthetic cone track (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--workload cfg4]
+  python bench.py --gpus N --steps K --warmup W [--workload cfg4] [--dump-outputs DIR] [--full]
 
 A "step" is ONE full Gauss-Newton iteration (linearise A5-A7, factorise + solve A8, update A9) of the hot path
 over the resident graph; inputs are in HBM before the timed region.
@@ -17,8 +17,13 @@ iterations per second, the same unit as the N = 1 line.
 `--workload cfg5 --shard` (N > 1) instead shards THE NAMED WORKLOAD: `--gpus 8 --workload cfg5 --shard` is BASELINE config 5
 itself, 1M poses / 50k cones by pose window across 8 GPUs (strong scaling: value = iterations/s of that one graph).
 
-One JSON line on stdout from rank 0, with `roofline` (edge-linearisation kernel, HIP events in this process)
-and, at N = 1, `cpu_baseline` (the CPU oracle + the reference's vendored Eigen solver on this host).
+One JSON line on stdout from rank 0.  A plain run sets up, warms up, times the K steps and prints the headline
+(`value`, `ms_per_step`).  `--full` adds every other measurement and check: `roofline` (edge-linearisation kernel, HIP
+events in this process), per-phase and solver figures, and, at N = 1, `cpu_baseline` (the CPU oracle + the reference's
+vendored Eigen solver on this host), the parity of the timed handle against the oracle, association, frame latency,
+growth, roofline_by_config and wide_view_tracks (`--no-cpu` / `--no-extra-configs` leave parts of it out).
+`--dump-outputs DIR` writes the estimates the timed handle holds after the last timed step as DIR/poses.npy
+[N, 3] (x, y, heading) and DIR/landmarks.npy [M, 2], float64: the inputs are the same seeded track on every run.
 """
 import argparse
 import importlib
@@ -31,6 +36,23 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0        # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, np, arrays):
+    """Writes each array as <out_dir>/<name>.npy in float64.  Over DUMP_LIMIT_BYTES in all, every array keeps a fixed, seeded
+    sample of its rows, and the row numbers it kept go to <name>_rows.npy (float64, exact below 2^53)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(a, dtype=np.float64) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            row_bytes = a.nbytes // max(len(a), 1) + 8
+            keep = min(len(a), int((DUMP_LIMIT_BYTES - 4096) / len(arrays) // row_bytes))
+            rows = np.sort(np.random.default_rng(1234).choice(len(a), keep, replace=False))
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline(pkg, g, iters, budget_s=22.0):
@@ -187,6 +209,11 @@ def main():
                     help="N > 1: shard the NAMED workload itself over the ranks (strong scaling; `--workload cfg5 --shard --gpus 8` is "
                          "BASELINE config 5: 1M poses / 50k cones by pose window across 8 GPUs) instead of N x the workload")
     ap.add_argument("--no-extra-configs", action="store_true", help="skip roofline_by_config (cfg3 / cfg5 beside the timed workload)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other measurement and check: roofline, phases, solver, CPU baseline and parity vs the "
+                         "oracle, association, frame latency, growth, other configurations (a plain run times the steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the timed handle's estimates after the last timed step to DIR/poses.npy and DIR/landmarks.npy (float64)")
     args = ap.parse_args()
 
     import torch                                   # first: its HIP runtime is the one the process uses
@@ -326,32 +353,35 @@ def main():
     timed_poses, timed_lms = G.poses(), G.landmarks()
     if not (np.isfinite(timed_poses).all() and np.isfinite(timed_lms).all()):
         raise SystemExit("bench: the timed handle holds non-finite estimates")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, np, dict(poses=timed_poses, landmarks=timed_lms))
 
     # ---- roofline of the edge-linearisation kernel (HIP events on the library's stream, this process)
-    lin_ms = G.time_linearize(50)                  # this rank's window when sharded
-    alg_bytes = G.linearize_bytes() // world       # E_pp*152 + E_pl*96 + N*120 + M*64  (SURVEY §8d), per window
-    achieved = alg_bytes / (lin_ms * 1e-3) / 1e9
-    # HBM traffic per launch from the PMC counters (FETCH_SIZE x2 + WRITE_SIZE): rocprofv3 collects them in separate
-    # passes around the process (scripts/pmc_iter.sh), so this run cannot measure them itself.  The committed measurement
-    # of the same kernel on the same workload is reported — and only while the kernel source still hashes to what the
-    # counters were taken on (scripts/make_pmc_json.py); otherwise null.
-    traffic, traffic_src = None, None
-    try:
-        sys.path.insert(0, os.path.join(ROOT, "scripts"))
-        from make_pmc_json import kernel_hash
-        for fn in sorted(os.listdir(os.path.join(ROOT, "profiles")), reverse=True):
-            if fn.endswith("_linearize_pmc.json"):
-                pm = json.load(open(os.path.join(ROOT, "profiles", fn)))
-                w = pm.get("workloads", {}).get(args.workload)
-                if w and pm.get("kernel_source_sha256") == kernel_hash() and world == 1:
-                    traffic = w["traffic_bytes_per_launch"]
-                    traffic_src = "committed_measurement profiles/%s (kernel source sha256 %s...)" % (fn, pm["kernel_source_sha256"][:12])
-                break
-    except Exception:
-        traffic = None
-    roofline = dict(bound="hbm", achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS,
-                    traffic=traffic, traffic_source=traffic_src, kernel="k_linearize_ell: edge linearisation + assembly (A5-A7)", ms_per_launch=lin_ms,
-                    algorithmic_bytes=alg_bytes, note="back-to-back launches of this rank's window (N > 1: no per-phase events inside the sharded step)")
+    if args.full:
+        lin_ms = G.time_linearize(50)                  # this rank's window when sharded
+        alg_bytes = G.linearize_bytes() // world       # E_pp*152 + E_pl*96 + N*120 + M*64  (SURVEY §8d), per window
+        achieved = alg_bytes / (lin_ms * 1e-3) / 1e9
+        # HBM traffic per launch from the PMC counters (FETCH_SIZE x2 + WRITE_SIZE): rocprofv3 collects them in separate
+        # passes around the process (scripts/pmc_iter.sh), so this run cannot measure them itself.  The committed measurement
+        # of the same kernel on the same workload is reported — and only while the kernel source still hashes to what the
+        # counters were taken on (scripts/make_pmc_json.py); otherwise null.
+        traffic, traffic_src = None, None
+        try:
+            sys.path.insert(0, os.path.join(ROOT, "scripts"))
+            from make_pmc_json import kernel_hash
+            for fn in sorted(os.listdir(os.path.join(ROOT, "profiles")), reverse=True):
+                if fn.endswith("_linearize_pmc.json"):
+                    pm = json.load(open(os.path.join(ROOT, "profiles", fn)))
+                    w = pm.get("workloads", {}).get(args.workload)
+                    if w and pm.get("kernel_source_sha256") == kernel_hash() and world == 1:
+                        traffic = w["traffic_bytes_per_launch"]
+                        traffic_src = "committed_measurement profiles/%s (kernel source sha256 %s...)" % (fn, pm["kernel_source_sha256"][:12])
+                    break
+        except Exception:
+            traffic = None
+        roofline = dict(bound="hbm", achieved=achieved, peak=HBM_PEAK_GBS, unit="GB/s", frac=achieved / HBM_PEAK_GBS,
+                        traffic=traffic, traffic_source=traffic_src, kernel="k_linearize_ell: edge linearisation + assembly (A5-A7)", ms_per_launch=lin_ms,
+                        algorithmic_bytes=alg_bytes, note="back-to-back launches of this rank's window (N > 1: no per-phase events inside the sharded step)")
     out = dict(metric="GraphSLAM Gauss-Newton iters/sec at N poses x M cones; pose RMSE vs ref",
                value=value, unit="GN iterations/s (whole %d-pose graph)" % N if strong else "GN iterations/s (%dk-pose windows)" % (Nw // 1000),
                n_gpus=world, steps=args.steps, warmup=args.warmup,
@@ -365,28 +395,30 @@ def main():
                            unknowns=3 * plan.n_free_poses + 2 * plan.n_free_landmarks,
                            parallelism=("%d pose windows, one per GPU; one RCCL all-reduce (sum, fp64) of %d doubles (%d bytes) per iteration, enqueued by the library (gs_dist_iterate)"
                                         % (world, G.dist_exchange_doubles(), 8 * G.dist_exchange_doubles())) if world > 1 else "single GPU",
-                           fronts=plan.n_fronts, levels=plan.n_levels, max_front=plan.max_front),
-               roofline=roofline)
+                           fronts=plan.n_fronts, levels=plan.n_levels, max_front=plan.max_front))
+    if args.full:
+        out["roofline"] = roofline
     if dist_mode and backend != "gloo" and not lib_rccl:
         out["exchange"] = dict(doubles=int(G.dist_exchange_doubles()), bytes=int(8 * G.dist_exchange_doubles()), ms_exchange=None,
                                note="the library's own RCCL communicator could not be created: torch.distributed.all_reduce on a torch side stream (rounds 2-3's path)")
-    if dist_mode and backend != "gloo" and lib_rccl:
+    if args.full and dist_mode and backend != "gloo" and lib_rccl:
         # the collective alone: `reps` all-reduces of the exchange buffer back to back on the library's stream (every rank calls it)
         out["exchange"] = dict(doubles=int(G.dist_exchange_doubles()), bytes=int(8 * G.dist_exchange_doubles()), ms_exchange=G.time_exchange(50),
                                shared_fronts=int(plan.n_shared_fronts), own_fronts=int(plan.n_own_fronts),
                                note="ms_exchange = one ncclAllReduce(sum, fp64) of the exchange buffer, mean of 50 back to back (HIP events on the library's stream); inside the iteration it sits between the local half and the shared top")
-    if dist_mode:
+    if args.full and dist_mode:
         # the structure phase of the sharded graph (once per graph change, outside the timed region): a rank plans its own window and the shared
         # top from per-landmark window masks; the slowest rank's time
         ts = torch.tensor([plan.ms_structure], dtype=torch.float64, device="cpu" if backend == "gloo" else "cuda")
         dist.all_reduce(ts, op=dist.ReduceOp.MAX)
         out["structure_ms_slowest_rank"] = float(ts.item())
+    if dist_mode:
         out["ingestion"] = ("rank-local: %.3f of the observation edges per rank (own window + the windows' first poses + fixed poses), landmark windows handed over" % ingest_frac
                             if local_ingest else "every rank holds the whole graph")
     if dist_mode and world == 1:
         out["config"]["parallelism"] = ("single GPU through the multi-GPU code path (GS_BENCH_FORCE_DIST): RCCL group of 1 created inside the library, top 3 levels forced shared "
                                         "(%d doubles all-reduced per iteration), gs_dist_iterate" % G.dist_exchange_doubles())
-    if world == 1 and not dist_mode:
+    if args.full and world == 1 and not dist_mode:
         warm_clocks(G)                             # (untimed; the timed region above is over)
         phases = G.time_iterations(20)
         out["phases_ms"] = dict(linearize=phases.ms_linearize, factor=phases.ms_factor, backsolve=phases.ms_backsolve,
@@ -432,7 +464,7 @@ def main():
                                achieved_back_to_back=achieved, ms_per_launch_back_to_back=lin_ms,
                                note="HIP start/stop events attached to the kernel's dispatch inside full iterations (cold inputs), mean of 20 launches; ms_event_to_event = events recorded around the phase (holds the hand-over from the previous kernel too); "
                                     "achieved_back_to_back = the same kernel launched 50x in a row (inputs cached)")
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         og, cb = cpu_baseline(pkg, g, args.cpu_iters)
         out["cpu_baseline"] = cb
         out["speedup_vs_cpu_baseline"] = value / cb["value"]
@@ -474,14 +506,14 @@ def main():
         G2.close()
     else:
         out["cpu_baseline"] = None
-    if rank == 0 and world == 1 and not dist_mode and not args.no_extra_configs:
+    if args.full and rank == 0 and world == 1 and not dist_mode and not args.no_extra_configs:
         try:
             out["association"] = association_roofline(pkg, np, track, g, local)
         except Exception as e:                                  # an extra: never costs the bench line
             out["association"] = dict(error=str(e))
-    if rank == 0 and world == 1 and not dist_mode and not args.no_cpu and args.workload == "cfg4":
+    if args.full and rank == 0 and world == 1 and not dist_mode and not args.no_cpu and args.workload == "cfg4":
         out["frame_latency"] = frame_latency(pkg, np)
-    if rank == 0 and world == 1 and not dist_mode and not args.no_extra_configs and args.workload == "cfg4":
+    if args.full and rank == 0 and world == 1 and not dist_mode and not args.no_extra_configs and args.workload == "cfg4":
         # the roofline kernel where it is launch-bound (cfg3), at the headline size (cfg4 = the entry above) and where it is
         # HBM-bound (cfg5, 1.05 GB per pass): same kernel, same measurement (HIP events inside full iterations)
         rb = {"cfg4": dict(algorithmic_bytes=alg_bytes, ms_per_launch=out["roofline"]["ms_per_launch"], achieved=out["roofline"]["achieved"],

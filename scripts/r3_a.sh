@@ -10,7 +10,7 @@ GS_LIB=$OLD timeout -k 10 300 python scripts/parity_spread.py cfg4 diff_first > 
 timeout -k 10 400 python scripts/parity_spread.py cfg5 g2o_order > $O/spread_cfg5_new.log 2>&1; echo "spread cfg5 new exit=$?"
 GS_LIB=$OLD timeout -k 10 400 python scripts/parity_spread.py cfg5 diff_first > $O/spread_cfg5_old.log 2>&1; echo "spread cfg5 old exit=$?"
 grep -h "vs\|b_pose" $O/spread_*.log | cut -c1-230
-timeout -k 10 600 python bench.py > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "bench exit=$?"
+timeout -k 10 600 python bench.py --full > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "bench exit=$?"
 python - <<PY
 import json
 d = json.load(open("$O/bench_cfg4.json"))

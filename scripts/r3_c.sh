@@ -3,7 +3,7 @@ set -o pipefail
 O=gpurun_out/r3c; mkdir -p $O
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "pytest exit=$?" | tee -a $O/pytest_gpu.log
 tail -4 $O/pytest_gpu.log
-timeout -k 10 900 python bench.py > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "bench exit=$?"; tail -3 $O/bench_cfg4.err
+timeout -k 10 900 python bench.py --full > $O/bench_cfg4.json 2> $O/bench_cfg4.err; echo "bench exit=$?"; tail -3 $O/bench_cfg4.err
 python - <<PY
 import json
 d = json.load(open("$O/bench_cfg4.json"))

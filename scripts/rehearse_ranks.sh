@@ -3,7 +3,7 @@
 # does on the host side — rank-local ingestion, shard plans, the failure report across ranks — without the hardware.  Flags DO arrive late here (the
 # processes are time-sliced): the runs exercise the timeout report / fallback / re-measure path as a matter of course.
 O=gpurun_out/rehearse; mkdir -p $O
-run() { name=$1; shift; n=$1; shift; GS_BENCH_BACKEND=gloo timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29600 + RANDOM % 300)) bench.py --gpus $n "$@" > $O/$name.json 2> $O/$name.err; rc=$?
+run() { name=$1; shift; n=$1; shift; GS_BENCH_BACKEND=gloo timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29600 + RANDOM % 300)) bench.py --gpus $n "$@" --full > $O/$name.json 2> $O/$name.err; rc=$?
   python - <<PY
 import json
 try:

@@ -1165,12 +1165,37 @@ def test_bench_nccl_branch_runs_for_real_at_world_size_one(pkg):
                MASTER_PORT="29541", HSA_ENABLE_IPC_MODE_LEGACY="0")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2",
-                        "--workload", "cfg3", "--cpu-iters", "4"], env=env, capture_output=True, text=True, timeout=600)
+                        "--workload", "cfg3", "--cpu-iters", "4", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert out["n_gpus"] == 1 and "RCCL group of 1" in out["config"]["parallelism"]
     assert out["timed_handle_bitwise_equals_optimize"] is True and out["timed_handle_iterations"] == 8
     assert out["pose_rmse_vs_oracle_rel"] < 1e-6 and out["value"] > 0
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_timed_estimates(pkg, tmp_path):
+    """bench.py without --full: one JSON line with the headline, --steps timed steps, and --dump-outputs writes the timed handle's
+    estimates after its last step — bit for bit what gs_optimize(warmup + steps) gives on a fresh handle of the same graph."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--workload", "cfg3",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["steps"] == 5 and out["warmup"] == 2 and out["ms_per_step"] > 0 and out["dtype"] == "f64" and out["higher_is_better"] is True
+    assert abs(out["value"] * out["ms_per_step"] - 1e3) < 1e-6 * 1e3
+    assert "roofline" not in out and out["cpu_baseline"] is None
+    P, L = np.load(str(tmp_path / "poses.npy")), np.load(str(tmp_path / "landmarks.npy"))
+    N, M = pkg.track.CONFIGS["cfg3"]
+    assert P.dtype == np.float64 and P.shape == (N, 3) and L.dtype == np.float64 and L.shape == (M, 2)
+    t = pkg.track.generate(N, M)
+    fe = pkg.Graph(device=0); g = pkg.track.bench_graph(t, fe); fe.close()          # the bench's own front end (A0 on the device)
+    H = pkg.Graph(device=0); H.load_bench_graph(g)
+    done, _ = H.optimize(7)
+    assert done == 7
+    assert np.array_equal(H.poses(), P) and np.array_equal(H.landmarks(), L)
+    H.close()
 
 
 def test_device_exchange_buffers_on_a_shared_torch_stream(pkg):
