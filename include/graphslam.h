@@ -47,6 +47,7 @@ extern "C" {
 #define GS_ERR_NUMERIC          -8  /* zero pivot: H singular (see gs_optimize) */
 #define GS_ERR_CAPACITY         -9  /* output buffer too small                  */
 #define GS_ERR_TIMEOUT         -10  /* a whole-tree solver launch gave up waiting for a front (see gs_stream_synchronize) */
+#define GS_ERR_OUT_OF_PATTERN  -11  /* covariance block of a pair outside the factor's pattern (see gs_get_covariance_block) */
 
 typedef struct gs_graph gs_graph;   /* replaces g2o::SparseOptimizer (src/slam.hpp:98) */
 typedef struct gs_slam  gs_slam;    /* replaces the graph-side state of class Slam     */
@@ -225,7 +226,8 @@ int  gs_get_stats(gs_graph *g, gs_stats *stats);      /* plan statistics after i
  *      stream; returns the mean milliseconds per pass in *out_ms_per_pass.
  * gs_linearize_bytes: algorithmic bytes of one pass, SURVEY §8(d):
  *      E_pp*152 + E_pl*96 + N*120 + M*64.
- * gs_export_system: copy the block-sparse H and b of the last linearisation to the host
+ * gs_export_system: copy the block-sparse H and b of the last linearisation to the host (gs_compute_marginals
+ *      counts as one: after it, these are H and b at the estimates of that call)
  *      (vertex arrays in insertion order, edge arrays in the order reported by *_edge_order):
  *      Hpp_diag [N*9], Hll_diag [M*4], Hpp_off [Epp*9] (= A^T Omega B), Hpl [Epl*6] (= A^T Omega B,
  *      3x2 row-major), b_pose [N*3], b_lm [M*2].  Any pointer may be NULL.
@@ -271,6 +273,47 @@ const char *gs_growth_refusal(gs_graph *g);
 /* flat int32 dump of the plan, see csrc/gs_plan.hpp for the layout; call with out==NULL
  * to get the required length in *out_len. */
 int  gs_plan_export(gs_graph *g, int32_t *out, int64_t *out_len);
+
+/* ---- marginal covariances --------------------------------------------------
+ * gs_compute_marginals       <- g2o SparseOptimizer::computeMarginals (g2o/core/sparse_optimizer.h): the
+ *      counterpart of what g2o offers; the reference itself never calls it.  Linearises H at the CURRENT
+ *      estimates (the ones gs_get_* returns), factorises it with the iteration's kernels and launch sequence
+ *      (no backward solve, no update) and runs a selected inversion of the factor (Takahashi recursion):
+ *      Sigma = H^-1 on the pattern of L, kept on the device by the handle.  g2o's computeMarginals reuses the
+ *      last iteration's factor instead, taken at the estimates BEFORE that iteration's update.
+ *      Nothing else moves: no estimate, no chi2 history, no stop / failure / fallback state of gs_optimize_until
+ *      and gs_iterate; runs on the handle's stream.  It is a linearisation, though: gs_export_system afterwards
+ *      returns the H and b of this call.  H must have a gauge (fixed vertices): without one it is singular in exact
+ *      arithmetic, and only an exactly-zero pivot is reported.  Fixed vertices (the gauge) are not in H: their blocks, and
+ *      every cross block that involves one, are zeros.  A zero pivot returns GS_ERR_NUMERIC (no results), a
+ *      front-flag timeout GS_ERR_TIMEOUT (the handle falls back to one launch per level, as gs_optimize does);
+ *      a host-only handle GS_ERR_NO_DEVICE; a sharded handle GS_ERR_INVALID.
+ * getters: the results of the last gs_compute_marginals, which belong to the estimates and the graph of that
+ *      call: after an iteration, a gs_set_*_estimate, any gs_add_*, a fixed flag or gs_clear they return
+ *      GS_ERR_NOT_INITIALIZED until the next gs_compute_marginals.  Full blocks, row-major; each returns the
+ *      number of blocks written (GS_ERR_CAPACITY when capacity is below it).
+ * gs_get_pose_covariances         3x3 per pose, the order of gs_get_poses (out_ids may be NULL)
+ * gs_get_landmark_covariances     2x2 per landmark, the order of gs_get_landmarks (out_ids may be NULL)
+ * gs_get_odometry_edge_covariances    Sigma(x_i, x_j), 3x3 per odometry edge, insertion order
+ * gs_get_observation_edge_covariances Sigma(x_p, l), 3x2 per observation edge, insertion order
+ * gs_get_covariance_block         Sigma(a, b) of any two vertices (kind 0 pose, 1 landmark) whose block lies in
+ *      the pattern of L — every pair joined by an edge does, and every vertex with itself; other pairs return
+ *      GS_ERR_OUT_OF_PATTERN (no extra solves).  out: 3 or 2 rows (a) x 3 or 2 columns (b), row-major.
+ * gs_slam_get_map_covariances     (below) the 2x2 block of every cone of the Slam mirror's map, map order: computes
+ *      the marginals of gs_slam_graph on demand; what gs_slam_perform does or publishes does not change. */
+typedef struct gs_marginals_info {
+    int32_t struct_size;         /* sizeof(gs_marginals_info), for ABI evolution                         */
+    int32_t numeric_failure;     /* as gs_stats: 0 ok, 1 zero pivot, 2 front-flag timeout                 */
+    int32_t n_fronts, n_levels;
+    int64_t sigma_bytes;         /* device bytes of the selected inverse kept by the handle              */
+    double  ms_linearize_factor, ms_selinv, ms_extract, ms_total;   /* HIP events on the handle's stream */
+} gs_marginals_info;
+int  gs_compute_marginals(gs_graph *g, gs_marginals_info *info /* may be NULL */);
+int  gs_get_pose_covariances(gs_graph *g, int32_t capacity, int32_t *out_ids, double *out_3x3);
+int  gs_get_landmark_covariances(gs_graph *g, int32_t capacity, int32_t *out_ids, double *out_2x2);
+int  gs_get_odometry_edge_covariances(gs_graph *g, int32_t capacity, double *out_3x3);
+int  gs_get_observation_edge_covariances(gs_graph *g, int32_t capacity, double *out_3x2);
+int  gs_get_covariance_block(gs_graph *g, int32_t kind_a, int32_t id_a, int32_t kind_b, int32_t id_b, double *out);
 
 /* ---- front end (A0, A1) ----------------------------------------------------
  * gs_polar_to_xy_batch  <- Slam::Spherical2Cartesian + transformConeToCoG    (src/slam.cpp:637-654, 513-523)
@@ -376,6 +419,8 @@ int  gs_slam_destroy(gs_slam *s);
 int  gs_slam_perform(gs_slam *s, const double odometry_xytheta[3], const double *cones_4xk, int32_t k);
 int  gs_slam_map_size(gs_slam *s);
 int  gs_slam_get_map(gs_slam *s, int32_t capacity, double *out_xy, int32_t *out_type);
+int  gs_slam_get_map_covariances(gs_slam *s, int32_t capacity, double *out_2x2);   /* see gs_compute_marginals; a map cone that is not in the graph: zeros;
+                                                                                      GS_ERR_NOT_INITIALIZED until the mirror has fixed its gauge (first optimizeGraph) */
 int  gs_slam_loop_closed(gs_slam *s);
 int  gs_slam_current_cone_index(gs_slam *s);
 int  gs_slam_get_send_pose(gs_slam *s, double out_xytheta[3]);

@@ -22,7 +22,7 @@ _ip = C.POINTER(C.c_int32)
 GS_OK = 0
 ERRORS = {-1: "GS_ERR_INVALID", -2: "GS_ERR_DUPLICATE_ID", -3: "GS_ERR_UNKNOWN_ID", -4: "GS_ERR_NO_DEVICE",
           -5: "GS_ERR_HIP", -6: "GS_ERR_NOT_INITIALIZED", -7: "GS_ERR_EMPTY", -8: "GS_ERR_NUMERIC",
-          -9: "GS_ERR_CAPACITY", -10: "GS_ERR_TIMEOUT"}
+          -9: "GS_ERR_CAPACITY", -10: "GS_ERR_TIMEOUT", -11: "GS_ERR_OUT_OF_PATTERN"}
 
 
 class GsError(RuntimeError):
@@ -80,6 +80,15 @@ class PlanInfo(C.Structure):
     _fields_ = [("n_scalar", C.c_int32), ("n_fronts", C.c_int32), ("n_levels", C.c_int32),
                 ("max_front", C.c_int32), ("l_doubles", C.c_int64), ("u_doubles", C.c_int64),
                 ("n_asm_blocks", C.c_int64), ("n_child_map", C.c_int64)]
+
+
+class MarginalsInfo(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("numeric_failure", C.c_int32), ("n_fronts", C.c_int32), ("n_levels", C.c_int32),
+                ("sigma_bytes", C.c_int64), ("ms_linearize_factor", C.c_double), ("ms_selinv", C.c_double),
+                ("ms_extract", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 def declared_symbols(debug=True):
@@ -203,6 +212,14 @@ def lib():
     L.gs_shell_slam.argtypes = [vp]; L.gs_shell_slam.restype = vp
     L.gs_slam_perform.argtypes = [vp, _dp, _dp, C.c_int32]
     L.gs_slam_get_map.argtypes = [vp, C.c_int32, _dp, _ip]
+    if hasattr(L, "gs_compute_marginals"):                 # (a tuning build of an older tree loaded through GS_LIB may predate the marginals)
+        L.gs_slam_get_map_covariances.argtypes = [vp, C.c_int32, _dp]
+        L.gs_compute_marginals.argtypes = [vp, C.POINTER(MarginalsInfo)]
+        L.gs_get_pose_covariances.argtypes = [vp, C.c_int32, _ip, _dp]
+        L.gs_get_landmark_covariances.argtypes = [vp, C.c_int32, _ip, _dp]
+        L.gs_get_odometry_edge_covariances.argtypes = [vp, C.c_int32, _dp]
+        L.gs_get_observation_edge_covariances.argtypes = [vp, C.c_int32, _dp]
+        L.gs_get_covariance_block.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp]
     L.gs_slam_get_send_pose.argtypes = [vp, _dp]
     L.gs_slam_collect_direction.argtypes = [vp, C.c_uint32, C.c_double, C.c_double]
     L.gs_slam_collect_distance.argtypes = [vp, C.c_uint32, C.c_double]
@@ -500,6 +517,33 @@ class Graph:
         dp = np.zeros((self.n_poses, 3)); dl = np.zeros((self.n_landmarks, 2))
         self._check(self.L.gs_export_delta(self.h, _d(dp), _d(dl))); return dp, dl
 
+    # ---- marginal covariances (gs_compute_marginals: selected inversion of the factor at the current estimates)
+    def compute_marginals(self):
+        """Sigma = H^-1 on the pattern of the factor at the current estimates; returns the gs_marginals_info as a dict"""
+        info = MarginalsInfo(); self._check(self.L.gs_compute_marginals(self.h, C.byref(info))); return info.as_dict()
+
+    def pose_covariances(self):
+        """[N,3,3] in the order of poses() (zeros for fixed poses)"""
+        n = self.n_poses; out = np.zeros((n, 3, 3)); self._check(self.L.gs_get_pose_covariances(self.h, n, None, _d(out))); return out
+
+    def landmark_covariances(self):
+        """[M,2,2] in the order of landmarks()"""
+        n = self.n_landmarks; out = np.zeros((n, 2, 2)); self._check(self.L.gs_get_landmark_covariances(self.h, n, None, _d(out))); return out
+
+    def odometry_edge_covariances(self):
+        """[E,3,3] Sigma(x_i, x_j) per odometry edge, insertion order"""
+        n = self.n_pp; out = np.zeros((n, 3, 3)); self._check(self.L.gs_get_odometry_edge_covariances(self.h, n, _d(out))); return out
+
+    def observation_edge_covariances(self):
+        """[E,3,2] Sigma(x_p, l) per observation edge, insertion order"""
+        n = self.n_pl; out = np.zeros((n, 3, 2)); self._check(self.L.gs_get_observation_edge_covariances(self.h, n, _d(out))); return out
+
+    def covariance_block(self, kind_a, id_a, kind_b, id_b):
+        """Sigma(a, b), kind 0 pose / 1 landmark (or "pose" / "landmark"); GsError GS_ERR_OUT_OF_PATTERN outside the factor's pattern"""
+        ka = {"pose": 0, "landmark": 1}.get(kind_a, kind_a); kb = {"pose": 0, "landmark": 1}.get(kind_b, kind_b)
+        out = np.zeros((3 if ka == 0 else 2, 3 if kb == 0 else 2))
+        self._check(self.L.gs_get_covariance_block(self.h, int(ka), int(id_a), int(kb), int(id_b), _d(out))); return out
+
     # ---- host-only plan (no device work)
     def plan_build_host(self):
         info = PlanInfo(); self._check(self.L.gs_plan_build_host(self.h, C.byref(info))); return info
@@ -748,6 +792,11 @@ class Slam:
     def map(self):
         n = self.map_size; xy = np.zeros((n, 2)); ty = np.zeros(n, dtype=np.int32)
         self._check(self.L.gs_slam_get_map(self.h, n, _d(xy), _i(ty))); return xy, ty
+
+    def map_covariances(self):
+        """[n,2,2] covariance of every map cone, map order (computes the marginals of the mirror's graph)"""
+        n = self.map_size; out = np.zeros((n, 2, 2))
+        self._check(self.L.gs_slam_get_map_covariances(self.h, n, _d(out))); return out
 
     def send_pose(self):
         o = np.zeros(3); self._check(self.L.gs_slam_get_send_pose(self.h, _d(o))); return o

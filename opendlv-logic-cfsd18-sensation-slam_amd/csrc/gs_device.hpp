@@ -97,6 +97,8 @@ struct DevGraph {
     uint8_t *pose_known = nullptr, *lm_known = nullptr;         // vertex estimates tracked by this rank
     int64_t *x_off = nullptr;                                   // front -> slot offset in the exchange buffer
     double *exchange = nullptr;                                 // dense slots of the shared fronts (all-reduced)
+    double *dpiv = nullptr;                                     // gs_compute_marginals: the LDL^T factor kernels write the pivots D here, at piv0 + k
+                                                                // (non-null: the launchers pick the kernels' CAP instances; null in iterations)
 };
 
 // launchers (gs_kernels.hip); all asynchronous on `st`
@@ -149,5 +151,12 @@ size_t factor_tab_lds_bytes(int kind);                                       // 
 size_t backsolve_tab_lds_bytes(int kind, int f_or_slot_f, int npiv_small);
 void launch_patch_asm3(int64_t n, int32_t *asm3, const int32_t *lm_grp_start, hipStream_t st);
 int  factor_lds_limit_f();      // largest front dimension that fits the LDS variant
+// marginals (gs_compute_marginals): selected inversion of the factor, one launch per level and form from the root.  list[0 .. count) = the fronts
+// of the launch, all of one form by max_f: <= 63 a wave each, 64 .. 159 a workgroup each (panels of 16 pivots on the matrix cores), larger (variant 4)
+// a workgroup each in HBM.  sig = the Sigma arena, sig_off[front] = offset of the front's image (packed lower triangle of its f x f rows,
+// row-major: (r, c) at r (r + 1) / 2 + c)
+void launch_selinv(const DevGraph &d, const int64_t *sig_off, double *sig, const int32_t *list, int count, int max_f, hipStream_t st);
+// out[i] = tab[i] >= 0 ? sig[tab[i]] : 0 (covariance blocks out of the Sigma images)
+void launch_sigma_gather(int64_t n, const int64_t *tab, const double *sig, double *out, hipStream_t st);
 
 }  // namespace gs

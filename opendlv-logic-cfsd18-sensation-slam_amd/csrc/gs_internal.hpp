@@ -82,6 +82,21 @@ struct gs_graph {
     std::vector<int32_t> bf_host, u3_off_host, u3_size_host, pos_of_front;                  // host mirrors the patch is computed from
     gs::Sc3Args sc3_args{};
     std::string no_growth_reason;           // why the last structure change was not absorbed by growing (empty: it was, or nothing tried)
+    // gs_compute_marginals: tables built on the first call after a structure phase (plan_version), device buffers from the pool (reused while they fit)
+    struct Marginals {
+        uint64_t plan_version = ~0ull;      // the plan the tables below were built for
+        std::vector<int64_t> sig_off;       // front -> its Sigma image in the arena (packed lower triangle of f x f)
+        std::vector<int32_t> front_of;      // scalar -> the front that has it as a pivot
+        std::vector<int32_t> sel_list;      // the selinv launches' fronts: per level (root first) and form (<= 63, 64 .. 159, larger), consecutive
+        struct Launch { int first, count, max_f; };
+        std::vector<Launch> sel_launch;     // in launch order
+        int64_t sig_doubles = 0, n_out = 0; // arena size; entries of the dense output (poses 9 N | landmarks 4 M | odometry 9 E | observation 6 E)
+        int64_t cap_sig = 0, cap_out = 0, cap_dout = 0, cap_fronts = 0, cap_piv = 0, cap_list = 0;
+        double *sig = nullptr, *dpiv = nullptr, *d_out = nullptr; int64_t *d_sig_off = nullptr, *d_tab = nullptr; int32_t *d_list = nullptr;
+        // results: valid for the graph / estimates / iteration count below
+        bool valid = false; uint64_t structure_version = 0, estimate_version = 0; int32_t iter = 0;
+        std::vector<double> out;
+    } marg;
 };
 
 namespace gs {

@@ -1337,8 +1337,15 @@ __device__ __forceinline__ void f3_panel_pivots(int k0, bool &bad, double (&p)[4
     }
 }
 
+// gs_compute_marginals: the panel's pivots d (uniform in every lane) to Dp[k0 .. k0 + 3], by lane 0.  Dp is a compile-time null in the
+// iteration's instances (template flag CAP of the factor kernels): their code is the same as without the capture
+__device__ __forceinline__ void f3_store_pivots(double *Dp, int k0, const double (&dd)[4], int npiv, int lane) {
+    if (Dp != nullptr && lane == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) if (k0 + j < npiv) Dp[k0 + j] = dd[j]; }
+}
 template <int B, int NT = 4>      // panel B: pivots 4B .. 4B+3 (tile column J0 = B / 4), LDL^T; NT = tile rows of the front (3: fronts of <= 47 scalars)
-__device__ __forceinline__ bool f3_panel_step(bool &bad, v4d (&acc)[NT * (NT + 1) / 2], double *Pn, double *L, int npiv, int f, int lane) {
+__device__ __forceinline__ bool f3_panel_step(bool &bad, v4d (&acc)[NT * (NT + 1) / 2], double *Pn, double *L, int npiv, int f, int lane, double *Dp) {
     constexpr int k0 = 4 * B, J0 = B / 4, jc = (B % 4) * 4;
     static_assert(J0 < NT, "panel beyond the front's tile rows");
     if (k0 >= npiv) return false;                                   // uniform
@@ -1362,6 +1369,7 @@ __device__ __forceinline__ bool f3_panel_step(bool &bad, v4d (&acc)[NT * (NT + 1
 #pragma unroll
     for (int j = 0; j < 4; ++j) p[j] = Pn[lane * 4 + j];
     f3_panel_pivots(k0, bad, p, dd, npiv, lane);
+    f3_store_pivots(Dp, k0, dd, npiv, lane);
     // the panel's columns of L (the diagonal is 1), one masked region.  Rows above the panel are zero and nobody reads them (the
     // backward solve uses a column from its diagonal down): not stored — whole 64-byte groups of them, a fifth of a leaf's L bytes
     if (lane >= (k0 & ~7) && lane <= f) {
@@ -1469,7 +1477,7 @@ __device__ __forceinline__ bool f3_gather_pair(double *img, const int (&rc)[F3_K
 // so a panel costs one workgroup barrier.  Element by element the arithmetic and its order are the wave-per-front
 // kernel's: the results are bit-identical.
 __device__ __forceinline__ int f3_tile_row(int t) { return t >= 6 ? 3 : (t >= 3 ? 2 : (t >= 1 ? 1 : 0)); }
-__device__ __forceinline__ bool f3_block_panel(int B, bool &bad, v4d (&acc)[3], double *Pn, double *Pw, double *L, int npiv, int f, int wave, int lane) {
+__device__ __forceinline__ bool f3_block_panel(int B, bool &bad, v4d (&acc)[3], double *Pn, double *Pw, double *L, int npiv, int f, int wave, int lane, double *Dp) {
     const int k0 = 4 * B, J0 = B >> 2, jc = (B & 3) * 4;             // uniform
     if (k0 >= npiv) return false;                                   // uniform over the workgroup
     const int lc = lane & 15, lr = lane >> 4;
@@ -1486,6 +1494,7 @@ __device__ __forceinline__ bool f3_block_panel(int B, bool &bad, v4d (&acc)[3], 
 #pragma unroll
     for (int j = 0; j < 4; ++j) p[j] = Pb[lane * 4 + j];
     f3_panel_pivots(k0, bad, p, dd, npiv, lane);
+    if (wave == 0) f3_store_pivots(Dp, k0, dd, npiv, lane);
     if (wave == 0 && lane >= (k0 & ~7) && lane <= f) {             // (rows above the panel: zero, never read, not stored)
         double *Lc = L + (int64_t)k0 * (f + 1) + lane;
 #pragma unroll
@@ -1555,12 +1564,12 @@ __device__ __forceinline__ void f3_sub_add(double *img, const v4d (&acc)[NT * (N
 #pragma unroll
             for (int q = 0; q < 4; ++q) img[pl[q]] = o[q]; }
 }
-template <bool TREE, bool LEAF, int NT, bool MERGED = false>
+template <bool TREE, bool LEAF, int NT, bool MERGED = false, bool CAP = false>      // CAP: gs_compute_marginals' instance (pivots to d.dpiv)
 __device__ __forceinline__ void f3_wave_front(const DevGraph &d, int pos, int mode, int leaf_slot, double *smem, int wave, int lane, bool ts_on, bool first,
                                               v4d (*acc_out)[NT * (NT + 1) / 2] = nullptr, int *npiv_out = nullptr, int *f_out = nullptr);
 // SUB: the front's children are LEAVES (level 0, <= 47 scalars) factorised by this workgroup's own waves, four at a time, their Schur
 // complements added into the image in list order — nothing of them goes to HBM but their L panels (k_factor3_sub)
-template <bool SUB = false, int NTL = 3>      // NTL: tile rows of the leaves (SUB)
+template <bool SUB = false, int NTL = 3, bool CAP = false>      // NTL: tile rows of the leaves (SUB); CAP: pivots to d.dpiv (marginals)
 __device__ __forceinline__ void f3_block_front(const DevGraph &d, int pos, int mode, int leaf_slot, double *smem, bool ts_on, int sub_leaf_slot = 0) {
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
 #define F3B_TS(i) do { if (ts_on) { __builtin_amdgcn_s_waitcnt(0); if (tid == 0) d.dbg_ts[i] = wall_clock64(); } } while (0)
@@ -1641,7 +1650,7 @@ __device__ __forceinline__ void f3_block_front(const DevGraph &d, int pos, int m
             const int e = e0 + wave; const bool has = e < fr.nchild;  // uniform per wave
             v4d cacc[NTL * (NTL + 1) / 2]; int ctab = 0, cnp = 0, cf = 0;
             if (has) { ctab = xt[e * XS + lane]; const int hd = xt[e * XS + XH + (lane & 7)];
-                f3_wave_front<true, true, NTL, true>(d, __builtin_amdgcn_readlane(hd, 4), FRONT_OWN, sub_leaf_slot, smem + MF_IMG, wave, lane, false, false, &cacc, &cnp, &cf); }
+                f3_wave_front<true, true, NTL, true, CAP>(d, __builtin_amdgcn_readlane(hd, 4), FRONT_OWN, sub_leaf_slot, smem + MF_IMG, wave, lane, false, false, &cacc, &cnp, &cf); }
             __syncthreads();
 #pragma unroll 1
             for (int k = 0; k < 4; ++k) { if (wave == k && has) f3_sub_add<NTL>(img, cacc, ctab, cnp, cf, lane); __syncthreads(); }
@@ -1686,9 +1695,10 @@ __device__ __forceinline__ void f3_block_front(const DevGraph &d, int pos, int m
         for (int q = 0; q < 4; ++q) acc[s][q] = t < 10 ? img[t * 256 + q * 64 + lane] : 0.0; }
     F3B_TS(6);
     double *L = d.Lbuf + fr.L_off;
+    double *Dp = CAP ? d.dpiv + fr.piv0 : nullptr;
     bool go = true, bad = false;
 #pragma clang loop unroll(disable)
-    for (int B = 0; B < 16 && go; ++B) go = f3_block_panel(B, bad, acc, Pn, Pw, L, npiv, f, wave, lane);
+    for (int B = 0; B < 16 && go; ++B) go = f3_block_panel(B, bad, acc, Pn, Pw, L, npiv, f, wave, lane, Dp);
     if (d.inject_iter != 0 && d.iter == d.inject_iter && pos == 0 && tid == 0) atomicMax(d.fail, d.inject_code);   // gs_debug_fail_at_iteration (fault injection for tests)
     if (bad && tid == 0) atomicMax(d.fail, 1);
     F3B_TS(7);
@@ -1730,7 +1740,7 @@ __device__ __forceinline__ void f3_block_front(const DevGraph &d, int pos, int m
 // descriptor), smem = the workgroup's dynamic LDS (the wave takes slot `wave`), first = the launch's first position
 // MERGED (leaf instance only): the leaf runs INSIDE its parent's workgroup (k_factor3_sub): its Schur complement is not stored — the
 // accumulators are handed back (acc_out, with the front's npiv and f) and the caller adds them into the parent's LDS image.
-template <bool TREE, bool LEAF, int NT, bool MERGED>
+template <bool TREE, bool LEAF, int NT, bool MERGED, bool CAP>
 __device__ __forceinline__ void f3_wave_front(const DevGraph &d, int pos, int mode, int leaf_slot, double *smem, int wave, int lane, bool ts_on, bool first,
                                               v4d (*acc_out)[NT * (NT + 1) / 2], int *npiv_out, int *f_out) {
     static_assert(LEAF || NT == 4, "only the leaf instance has a three-tile-row form");
@@ -1900,16 +1910,17 @@ __device__ __forceinline__ void f3_wave_front(const DevGraph &d, int pos, int mo
     // ---- panels of 4 pivots; the LDS image is free now, its first 256 doubles serve as the panel buffer
     double *Pn = P.F;
     double *L = d.Lbuf + fr.L_off;
+    double *Dp = CAP ? d.dpiv + fr.piv0 : nullptr;
     bool go = true, bad = false;
-    go = go && f3_panel_step<0, NT>(bad, acc, Pn, L, npiv, f, lane);   go = go && f3_panel_step<1, NT>(bad, acc, Pn, L, npiv, f, lane);
-    go = go && f3_panel_step<2, NT>(bad, acc, Pn, L, npiv, f, lane);   go = go && f3_panel_step<3, NT>(bad, acc, Pn, L, npiv, f, lane);
-    go = go && f3_panel_step<4, NT>(bad, acc, Pn, L, npiv, f, lane);   go = go && f3_panel_step<5, NT>(bad, acc, Pn, L, npiv, f, lane);
-    go = go && f3_panel_step<6, NT>(bad, acc, Pn, L, npiv, f, lane);   go = go && f3_panel_step<7, NT>(bad, acc, Pn, L, npiv, f, lane);
-    go = go && f3_panel_step<8, NT>(bad, acc, Pn, L, npiv, f, lane);   go = go && f3_panel_step<9, NT>(bad, acc, Pn, L, npiv, f, lane);
-    go = go && f3_panel_step<10, NT>(bad, acc, Pn, L, npiv, f, lane);  go = go && f3_panel_step<11, NT>(bad, acc, Pn, L, npiv, f, lane);
+    go = go && f3_panel_step<0, NT>(bad, acc, Pn, L, npiv, f, lane, Dp);   go = go && f3_panel_step<1, NT>(bad, acc, Pn, L, npiv, f, lane, Dp);
+    go = go && f3_panel_step<2, NT>(bad, acc, Pn, L, npiv, f, lane, Dp);   go = go && f3_panel_step<3, NT>(bad, acc, Pn, L, npiv, f, lane, Dp);
+    go = go && f3_panel_step<4, NT>(bad, acc, Pn, L, npiv, f, lane, Dp);   go = go && f3_panel_step<5, NT>(bad, acc, Pn, L, npiv, f, lane, Dp);
+    go = go && f3_panel_step<6, NT>(bad, acc, Pn, L, npiv, f, lane, Dp);   go = go && f3_panel_step<7, NT>(bad, acc, Pn, L, npiv, f, lane, Dp);
+    go = go && f3_panel_step<8, NT>(bad, acc, Pn, L, npiv, f, lane, Dp);   go = go && f3_panel_step<9, NT>(bad, acc, Pn, L, npiv, f, lane, Dp);
+    go = go && f3_panel_step<10, NT>(bad, acc, Pn, L, npiv, f, lane, Dp);  go = go && f3_panel_step<11, NT>(bad, acc, Pn, L, npiv, f, lane, Dp);
     if constexpr (NT == 4) {
-    go = go && f3_panel_step<12, NT>(bad, acc, Pn, L, npiv, f, lane);  go = go && f3_panel_step<13, NT>(bad, acc, Pn, L, npiv, f, lane);
-    go = go && f3_panel_step<14, NT>(bad, acc, Pn, L, npiv, f, lane);  go = go && f3_panel_step<15, NT>(bad, acc, Pn, L, npiv, f, lane); }
+    go = go && f3_panel_step<12, NT>(bad, acc, Pn, L, npiv, f, lane, Dp);  go = go && f3_panel_step<13, NT>(bad, acc, Pn, L, npiv, f, lane, Dp);
+    go = go && f3_panel_step<14, NT>(bad, acc, Pn, L, npiv, f, lane, Dp);  go = go && f3_panel_step<15, NT>(bad, acc, Pn, L, npiv, f, lane, Dp); }
     if (d.inject_iter != 0 && d.iter == d.inject_iter && pos == 0 && lane == 0) atomicMax(d.fail, d.inject_code);   // gs_debug_fail_at_iteration (fault injection for tests)
     if (bad && lane == 0) atomicMax(d.fail, 1);
     F3_TS(7);
@@ -1995,17 +2006,17 @@ __device__ __forceinline__ void f3_wave_front(const DevGraph &d, int pos, int mo
 // six at a time — 20 us of the 168 us factor phase at cfg4, 205 of 990 at cfg5.  Now workgroup b takes level-1 front b: its waves
 // factorise the leaves (the leaf instance's code), add their Schur complements into the front's LDS image in list order, and the four
 // waves factorise the front itself (the block form).  Same arithmetic, same order: bit-identical to the two-launch path.
-template <int NTL>      // tile rows of the leaves: 3 when every leaf has <= 47 scalars, else 4
+template <int NTL, bool CAP = false>      // tile rows of the leaves: 3 when every leaf has <= 47 scalars, else 4; CAP: marginals instance
 __global__ void __launch_bounds__(256, NTL == 3 ? 3 : 2) k_factor3_sub(DevGraph d, int first_pos, int count, int leaf_slot) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     if ((int)blockIdx.x >= count) return;
-    f3_block_front<true, NTL>(d, first_pos + (int)blockIdx.x, FRONT_OWN, 0, smem, false, leaf_slot);
+    f3_block_front<true, NTL, CAP>(d, first_pos + (int)blockIdx.x, FRONT_OWN, 0, smem, false, leaf_slot);
 }
 
 #ifndef F3_LEAF4_WPS
 #define F3_LEAF4_WPS 3      // waves per SIMD the four-tile-row leaf instance is compiled for
 #endif
-template <bool TREE, bool LEAF, int NT = 4>
+template <bool TREE, bool LEAF, int NT = 4, bool CAP = false>      // CAP: gs_compute_marginals' instance (pivots to d.dpiv)
 __global__ void __launch_bounds__(256, LEAF ? (NT == 3 ? 5 : F3_LEAF4_WPS) : 2) k_factor3(DevGraph d, int level_off, int count, int mode, int leaf_slot, int n_wave_fronts) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -2016,12 +2027,12 @@ __global__ void __launch_bounds__(256, LEAF ? (NT == 3 ? 5 : F3_LEAF4_WPS) : 2) 
         bid = wg_ticket(d, smem);                                    // (the flagged launch: its fronts wait for each other)
         const int wave_blocks = (n_wave_fronts + 3) >> 2;
         if (bid >= wave_blocks) { const int pos = level_off + n_wave_fronts + (bid - wave_blocks);
-            f3_block_front(d, pos, mode, leaf_slot, smem, (d.dbg & 16) && pos == (d.dbg >> 8)); return; }
+            f3_block_front<false, 3, CAP>(d, pos, mode, leaf_slot, smem, (d.dbg & 16) && pos == (d.dbg >> 8)); return; }
     }
     const int fi = bid * 4 + wave;
     if (fi >= (TREE && !LEAF ? n_wave_fronts : count)) return;      // whole wave leaves; no block barrier below
     const bool ts_on = ((d.dbg & 8) && count == (d.dbg >> 8) && fi == 0) || ((d.dbg & 16) && level_off + fi == (d.dbg >> 8));   // 16: probe the front at a level POSITION
-    f3_wave_front<TREE, LEAF, NT>(d, level_off + fi, mode, leaf_slot, smem, wave, lane, ts_on, fi == 0);
+    f3_wave_front<TREE, LEAF, NT, false, CAP>(d, level_off + fi, mode, leaf_slot, smem, wave, lane, ts_on, fi == 0);
 }
 
 // backward solve of variant 3's LDL^T panels (unit diagonal): x_piv = L11^-T (y - L21^T x_bnd), one wave per front
@@ -2145,7 +2156,7 @@ template <int NT> struct BigDims {
     static constexpr int LDS_DOUBLES = IMG + 2 * PANEL + 4 * PANEL + BIG_TAB / 2;      // image, two spill buffers, a private buffer per wave, one child table
 };
 template <int NT>
-__device__ __forceinline__ bool f3_big_panel(int B, bool &bad, v4d (&acc)[BigDims<NT>::TPW], double *Pn, double *Pw, double *L, int npiv, int f, int wave, int lane) {
+__device__ __forceinline__ bool f3_big_panel(int B, bool &bad, v4d (&acc)[BigDims<NT>::TPW], double *Pn, double *Pw, double *L, int npiv, int f, int wave, int lane, double *Dp) {
     using D = BigDims<NT>;
     const int k0 = 4 * B, J0 = B >> 2, jc = (B & 3) * 4;             // uniform
     if (k0 >= npiv) return false;
@@ -2193,6 +2204,7 @@ __device__ __forceinline__ bool f3_big_panel(int B, bool &bad, v4d (&acc)[BigDim
 #pragma unroll
             for (int m = 0; m < D::NR; ++m) p[m][j] = 0.0; }
     }
+    if (wave == 0) f3_store_pivots(Dp, k0, dd, npiv, lane);
     if (wave == 0) {
 #pragma unroll
         for (int m = 0; m < D::NR; ++m) if (lane + 64 * m >= (k0 & ~7) && lane + 64 * m <= f) {      // (rows above the panel: zero, never read, not stored)
@@ -2223,7 +2235,7 @@ __device__ __forceinline__ bool f3_big_panel(int B, bool &bad, v4d (&acc)[BigDim
 // mode (pose-window shards, as for the small fronts): FRONT_OWN a front of this rank's own subtree; FRONT_CONTRIB this rank's share of a
 // shared front — the originals it evaluated + the update matrices of the children it owns — written to the front's exchange slot, no
 // factorisation; FRONT_TOP a shared front after the all-reduce: the image starts from the summed slot, only the shared children are added
-template <int NT>
+template <int NT, bool CAP = false>
 __device__ __forceinline__ void f3_big_front(const DevGraph &d, int pos, double *smem, int mode = FRONT_OWN) {
     using D = BigDims<NT>;
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
@@ -2311,10 +2323,11 @@ __device__ __forceinline__ void f3_big_front(const DevGraph &d, int pos, double 
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[s][q] = 4 * s + wave < D::NTILE ? img[(4 * s + wave) * 256 + q * 64 + lane] : 0.0;
     double *L = d.Lbuf + fr.L_off;
+    double *Dp = CAP ? d.dpiv + fr.piv0 : nullptr;
     bool go = true, bad = false;
 #pragma clang loop unroll(disable)
     BIG_TS(3);
-    for (int B = 0; B < 4 * NT && go; ++B) { go = f3_big_panel<NT>(B, bad, acc, Pn, Pw, L, npiv, f, wave, lane); if (B < 16) BIG_TS(4 + B); }
+    for (int B = 0; B < 4 * NT && go; ++B) { go = f3_big_panel<NT>(B, bad, acc, Pn, Pw, L, npiv, f, wave, lane, Dp); if (B < 16) BIG_TS(4 + B); }
     BIG_TS(20);
     if (d.inject_iter != 0 && d.iter == d.inject_iter && pos == 0 && tid == 0) atomicMax(d.fail, d.inject_code);   // gs_debug_fail_at_iteration
     if (bad && tid == 0) atomicMax(d.fail, 1);
@@ -2414,20 +2427,20 @@ __device__ __forceinline__ void bs3_big_front(const DevGraph &d, int pos, double
 // CLASS: the launches are cut by LDS need, and each class is its own kernel so that the many fronts just beyond a wave do not
 // inherit the registers (and with them the occupancy) of the others: 0 = fronts of 64-79 scalars (three workgroups per CU),
 // 1 = small fronts (a wave or four each) and fronts of 80-111 (two per CU), 2 = fronts of 112-159 (one per CU)
-template <int CLASS>
+template <int CLASS, bool CAP = false>
 __global__ void __launch_bounds__(256, CLASS == 0 ? 3 : (CLASS == 1 ? 2 : 1)) k_factor3_tab(DevGraph d, const int2 *__restrict__ wgt, int leaf_launch_preceded, int mode) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     const int bid = wg_ticket(d, smem);
     const int2 e = wgt[bid];
     const int pos = __builtin_amdgcn_readfirstlane(e.x), kind = __builtin_amdgcn_readfirstlane(e.y) & 0xff, cnt = __builtin_amdgcn_readfirstlane(e.y) >> 8;
-    if constexpr (CLASS == 0) { f3_big_front<5>(d, pos, smem, mode); }
-    else if constexpr (CLASS == 2) { f3_big_front<10>(d, pos, smem, mode); }
+    if constexpr (CLASS == 0) { f3_big_front<5, CAP>(d, pos, smem, mode); }
+    else if constexpr (CLASS == 2) { f3_big_front<10, CAP>(d, pos, smem, mode); }
     else {
         // (the host never puts a four-wave entry into a CONTRIB table: that form has the modes OWN and TOP)
-        if (kind == WG_WAVES) { if (wave < cnt) f3_wave_front<true, false, 4>(d, pos + wave, mode, leaf_launch_preceded, smem, wave, lane, false, bid == 0 && wave == 0); }
-        else if (kind == WG_BLOCK4) f3_block_front(d, pos, mode, leaf_launch_preceded, smem, false);
-        else f3_big_front<7>(d, pos, smem, mode);
+        if (kind == WG_WAVES) { if (wave < cnt) f3_wave_front<true, false, 4, false, CAP>(d, pos + wave, mode, leaf_launch_preceded, smem, wave, lane, false, bid == 0 && wave == 0); }
+        else if (kind == WG_BLOCK4) f3_block_front<false, 3, CAP>(d, pos, mode, leaf_launch_preceded, smem, false);
+        else f3_big_front<7, CAP>(d, pos, smem, mode);
     }
 }
 template <bool BIG>      // BIG: a launch of big fronts only (few registers: as many workgroups per CU as the LDS allows); else small fronts, a wave each
@@ -2455,14 +2468,19 @@ size_t backsolve_tab_lds_bytes(int kind, int f_or_slot_f, int npiv_small) {     
     if (kind == WG_WAVES || kind == WG_BLOCK4) { const int slot = ((((f_or_slot_f + 1) | 1) * std::max(npiv_small, 1)) + 1) & ~1; return (size_t)slot * 4 * sizeof(double); }
     return (size_t)bs3_big_lds_doubles(f_or_slot_f) * sizeof(double);
 }
-void launch_factor_tab(const DevGraph &d, const int2 *wgt, int n_wg, int leaf_launch_preceded, size_t lds_bytes, int cls, hipStream_t st, int mode) {
+template <bool CAP>      // CAP: gs_compute_marginals (d.dpiv set), the instances that write the pivots
+static void launch_factor_tab_t(const DevGraph &d, const int2 *wgt, int n_wg, int leaf_launch_preceded, size_t lds_bytes, int cls, hipStream_t st, int mode) {
     if (n_wg <= 0) return;                                           // (a launch holds workgroups of ONE class: the host cut the table that way)
-    if (cls == 0) { allow_max_lds((const void *)k_factor3_tab<0>);
-        hipLaunchKernelGGL(k_factor3_tab<0>, dim3(n_wg), dim3(256), lds_bytes, st, ticketed(d, (unsigned)n_wg), wgt, leaf_launch_preceded, mode); }
-    else if (cls == 2) { allow_max_lds((const void *)k_factor3_tab<2>);
-        hipLaunchKernelGGL(k_factor3_tab<2>, dim3(n_wg), dim3(256), lds_bytes, st, ticketed(d, (unsigned)n_wg), wgt, leaf_launch_preceded, mode); }
-    else { allow_max_lds((const void *)k_factor3_tab<1>);
-        hipLaunchKernelGGL(k_factor3_tab<1>, dim3(n_wg), dim3(256), lds_bytes, st, ticketed(d, (unsigned)n_wg), wgt, leaf_launch_preceded, mode); }
+    if (cls == 0) { allow_max_lds((const void *)k_factor3_tab<0, CAP>);
+        hipLaunchKernelGGL((k_factor3_tab<0, CAP>), dim3(n_wg), dim3(256), lds_bytes, st, ticketed(d, (unsigned)n_wg), wgt, leaf_launch_preceded, mode); }
+    else if (cls == 2) { allow_max_lds((const void *)k_factor3_tab<2, CAP>);
+        hipLaunchKernelGGL((k_factor3_tab<2, CAP>), dim3(n_wg), dim3(256), lds_bytes, st, ticketed(d, (unsigned)n_wg), wgt, leaf_launch_preceded, mode); }
+    else { allow_max_lds((const void *)k_factor3_tab<1, CAP>);
+        hipLaunchKernelGGL((k_factor3_tab<1, CAP>), dim3(n_wg), dim3(256), lds_bytes, st, ticketed(d, (unsigned)n_wg), wgt, leaf_launch_preceded, mode); }
+}
+void launch_factor_tab(const DevGraph &d, const int2 *wgt, int n_wg, int leaf_launch_preceded, size_t lds_bytes, int cls, hipStream_t st, int mode) {
+    if (d.dpiv) launch_factor_tab_t<true>(d, wgt, n_wg, leaf_launch_preceded, lds_bytes, cls, st, mode);
+    else launch_factor_tab_t<false>(d, wgt, n_wg, leaf_launch_preceded, lds_bytes, cls, st, mode);
 }
 void launch_backsolve_tab(const DevGraph &d, const int2 *wgt, int n_wg, int max_npiv_small, int max_f_small, size_t lds_bytes, int cls, hipStream_t st) {
     if (n_wg <= 0) return;
@@ -2650,22 +2668,27 @@ void launch_build_sc3(const int32_t *bf, const int32_t *asm3, int32_t *sc3, int3
 // whole-tree launches of variant 3 (own fronts of a single-GPU graph): the leaf instance (positions [0, n_leaf)), then — n_sub > 0 —
 // the bottom subtrees (level-1 fronts at positions [sub_first, sub_first + n_sub), each with the leaves below it, which are the
 // positions [n_leaf, sub_first) and get no launch of their own), then every level above in one flagged launch
-void launch_factor_tree(const DevGraph &d, int n_leaf, int leaf_slot, int leaf_max_f, int count, int n_block, int sub_first, int n_sub, hipStream_t st) {
+template <bool CAP>
+static void launch_factor_tree_t(const DevGraph &d, int n_leaf, int leaf_slot, int leaf_max_f, int count, int n_block, int sub_first, int n_sub, hipStream_t st) {
     if (count <= 0) return;
-    allow_max_lds((const void *)k_factor3<true, false>); allow_max_lds((const void *)k_factor3<true, true>); allow_max_lds((const void *)k_factor3<true, true, 3>);
+    allow_max_lds((const void *)k_factor3<true, false, 4, CAP>); allow_max_lds((const void *)k_factor3<true, true, 4, CAP>); allow_max_lds((const void *)k_factor3<true, true, 3, CAP>);
     // level 0 (no children) through the high-occupancy leaf instance (three tile rows when every leaf has <= 47 scalars),
     // everything above in one launch whose fronts wait on flags
     const int nt3 = d.leaf_nt3;                                      // gs_debug_options.leaf_nt3
-    if (n_leaf > 0 && leaf_max_f <= 47 && nt3) hipLaunchKernelGGL((k_factor3<true, true, 3>), dim3((n_leaf + 3) / 4), dim3(256), (size_t)leaf_slot * 4 * sizeof(double), st, d, 0, n_leaf, FRONT_OWN, leaf_slot, 0);
-    else if (n_leaf > 0) hipLaunchKernelGGL((k_factor3<true, true>), dim3((n_leaf + 3) / 4), dim3(256), (size_t)leaf_slot * 4 * sizeof(double), st, d, 0, n_leaf, FRONT_OWN, leaf_slot, 0);
+    if (n_leaf > 0 && leaf_max_f <= 47 && nt3) hipLaunchKernelGGL((k_factor3<true, true, 3, CAP>), dim3((n_leaf + 3) / 4), dim3(256), (size_t)leaf_slot * 4 * sizeof(double), st, d, 0, n_leaf, FRONT_OWN, leaf_slot, 0);
+    else if (n_leaf > 0) hipLaunchKernelGGL((k_factor3<true, true, 4, CAP>), dim3((n_leaf + 3) / 4), dim3(256), (size_t)leaf_slot * 4 * sizeof(double), st, d, 0, n_leaf, FRONT_OWN, leaf_slot, 0);
     int first = n_leaf, plain_level = n_leaf > 0 ? 1 : 0;
-    if (n_sub > 0) { allow_max_lds((const void *)k_factor3_sub<3>); allow_max_lds((const void *)k_factor3_sub<4>);
-        if (leaf_max_f <= 47 && nt3) hipLaunchKernelGGL(k_factor3_sub<3>, dim3(n_sub), dim3(256), factor_sub_lds_bytes(leaf_slot), st, d, sub_first, n_sub, leaf_slot);
-        else hipLaunchKernelGGL(k_factor3_sub<4>, dim3(n_sub), dim3(256), factor_sub_lds_bytes(leaf_slot), st, d, sub_first, n_sub, leaf_slot);
+    if (n_sub > 0) { allow_max_lds((const void *)k_factor3_sub<3, CAP>); allow_max_lds((const void *)k_factor3_sub<4, CAP>);
+        if (leaf_max_f <= 47 && nt3) hipLaunchKernelGGL((k_factor3_sub<3, CAP>), dim3(n_sub), dim3(256), factor_sub_lds_bytes(leaf_slot), st, d, sub_first, n_sub, leaf_slot);
+        else hipLaunchKernelGGL((k_factor3_sub<4, CAP>), dim3(n_sub), dim3(256), factor_sub_lds_bytes(leaf_slot), st, d, sub_first, n_sub, leaf_slot);
         first = sub_first + n_sub; plain_level = 2; }
     // the last n_block level positions (whole upper levels) get a workgroup each, the others a wave each
     if (count > first) { const int nw = count - first - n_block; const unsigned grid = (unsigned)((nw + 3) / 4 + n_block);
-        hipLaunchKernelGGL((k_factor3<true, false>), dim3(grid), dim3(256), (size_t)MF_IMG * 4 * sizeof(double), st, ticketed(d, grid), first, count - first, FRONT_OWN, plain_level, nw); }   // leaf_slot argument: the highest level whose fronts have all their children in earlier launches
+        hipLaunchKernelGGL((k_factor3<true, false, 4, CAP>), dim3(grid), dim3(256), (size_t)MF_IMG * 4 * sizeof(double), st, ticketed(d, grid), first, count - first, FRONT_OWN, plain_level, nw); }   // leaf_slot argument: the highest level whose fronts have all their children in earlier launches
+}
+void launch_factor_tree(const DevGraph &d, int n_leaf, int leaf_slot, int leaf_max_f, int count, int n_block, int sub_first, int n_sub, hipStream_t st) {
+    if (d.dpiv) launch_factor_tree_t<true>(d, n_leaf, leaf_slot, leaf_max_f, count, n_block, sub_first, n_sub, st);
+    else launch_factor_tree_t<false>(d, n_leaf, leaf_slot, leaf_max_f, count, n_block, sub_first, n_sub, st);
 }
 size_t factor_sub_lds_bytes(int leaf_slot) { return (size_t)(MF_IMG + std::max(1536, 4 * leaf_slot)) * sizeof(double); }
 // the shared top of a sharded graph (mode TOP: fronts start from the all-reduced exchange slots and gather their shared
@@ -2686,8 +2709,10 @@ void launch_backsolve_tree(const DevGraph &d, int first, int count, int max_npiv
 void launch_factor_level(const DevGraph &d, int level_off, int count, int max_f, int mode, hipStream_t st) {
     if (count <= 0) return;
     if (max_f <= 63 && d.factor_variant == 3) {
-        allow_max_lds((const void *)k_factor3<false, false>);
         const size_t lds3 = std::max((size_t)MF_IMG * 4 * sizeof(double), (size_t)d.f3_lds_kb * 1024);   // gs_debug_options.f3_lds_kb: occupancy experiments (more LDS per block = fewer resident blocks)
+        if (d.dpiv) { allow_max_lds((const void *)k_factor3<false, false, 4, true>);        // gs_compute_marginals: the instance that writes the pivots
+            hipLaunchKernelGGL((k_factor3<false, false, 4, true>), dim3((count + 3) / 4), dim3(256), lds3, st, d, level_off, count, mode, 0, count); return; }
+        allow_max_lds((const void *)k_factor3<false, false>);
         hipLaunchKernelGGL((k_factor3<false, false>), dim3((count + 3) / 4), dim3(256), lds3, st, d, level_off, count, mode, 0, count);
         return;
     }
@@ -2875,6 +2900,186 @@ __global__ void __launch_bounds__(256) k_update(DevGraph d) {
 void launch_update(const DevGraph &d, hipStream_t st) {
     int n = 3 * (d.N + d.tN) + 2 * (d.M + d.tM);
     if (n > 0) hipLaunchKernelGGL(k_update, dim3((n + 255) / 256), dim3(256), 0, st, d);
+}
+
+// ---- marginals: selected inversion of the multifrontal factor (Takahashi recursion), gs_compute_marginals.  H = L D L^T (variant 3: unit L,
+// D captured by the factor into d.dpiv; variant 4: L L^T, so a column is divided by its diagonal and 1 / d = 1 / L_kk^2).  Sigma = H^-1 on the
+// rows of every front, one launch per level (and form) from the root: the front's boundary block Sigma_BB is the parent's, gathered through the
+// same row map the extend-add uses; then, from the last pivot back to the first (rows r, c of the front below k):
+//      Sigma[r, k] = -sum_c Sigma[r, c] l[c, k],     Sigma[k, k] = 1 / d_k - sum_r l[r, k] Sigma[r, k]
+// The image — packed lower triangle, row-major, (r, c) at r (r + 1) / 2 + c — is the format of the Sigma arena.  Every front takes the same
+// form whatever the launch mode of the factor, and its sums run in a fixed order: the same L and D give the same Sigma bit for bit.
+__host__ __device__ __forceinline__ int64_t tri_of(int r) { return ((int64_t)r * (r + 1)) >> 1; }
+__device__ __forceinline__ double selinv_l(const double *L, int64_t ldl, int r, int k, bool unit) {     // l[r, k] of the unit-diagonal form
+    const double *Lk = L + (int64_t)k * ldl;
+    return unit ? Lk[r] : Lk[r] / Lk[k];
+}
+__device__ __forceinline__ double selinv_dinv(const DevGraph &d, const double *L, int64_t ldl, int piv0, int k, bool unit) {
+    if (unit) return 1.0 / d.dpiv[piv0 + k];
+    const double lkk = L[(int64_t)k * ldl + k]; return 1.0 / (lkk * lkk);
+}
+// Sigma_BB of front fr into its image S (packed) out of the parent's image in the arena
+__device__ __forceinline__ void selinv_gather_bb(const DevGraph &d, const DevFront &fr, const int64_t *sig_off, const double *sig, double *S, int tid, int nthreads) {
+    const int npiv = fr.npiv, nb = fr.nbnd;
+    if (nb == 0) return;
+    const double *Sp = sig + sig_off[fr.parent];
+    const int32_t *map = d.child_map + fr.map_off;
+    const int64_t nt = tri_of(nb);
+    for (int64_t idx = tid; idx < nt; idx += nthreads) {
+        int i = (int)((sqrt(8.0 * (double)idx + 1.0) - 1.0) * 0.5);
+        if (tri_of(i) > idx) --i;
+        if (tri_of(i + 1) <= idx) ++i;
+        const int j = (int)(idx - tri_of(i));
+        S[tri_of(npiv + i) + npiv + j] = Sp[tri_of(map[i]) + map[j]];
+    }
+}
+// Fronts of at most 159 scalars: panels of 16 pivots.  NW = 1: a wave per front (f <= 63); NW = 4: a workgroup (f of 64 .. 159).  For the panel
+// K = [k0, k1) and the rows below it R = [k1, f) (Sigma[R, R] known):
+//   1. W = -Sigma[R, R] l[R, K]            one GEMM on v_mfma_f64_16x16x4_f64 (row tiles of 16 over the waves)
+//   2. Sigma[R, k] = W[R, k] - sum_{c in K, c > k} Sigma[R, c] l[c, k],   k = k1-1 .. k0: a thread per row of R, a chain of 16 steps in registers
+//   3. V = Sigma[R, K]^T l[R, K]           a 16 x 16 GEMM on the matrix cores
+//   4. Sigma[r, k] = -V[r, k] - sum_{c in K, c > k} Sigma[r, c] l[c, k] (r in K, r > k),  Sigma[k, k] = 1 / d_k - V[k, k] - sum_{r in K, r > k} l[r, k] Sigma[r, k]:
+//      the 16-step chain of the panel itself, 16 lanes of wave 0
+// LDS: the image (tri(fcap) doubles), l of the panel (16 x 16), l[R, K] and W / Sigma[R, K] (fcap16 x 16 each), V, the panel block, 1 / d.
+static constexpr int SEL_PANEL = 16;
+__host__ __device__ __forceinline__ int64_t selinv_panel_lds_doubles(int fcap) {
+    const int f16 = (fcap + 15) & ~15;
+    return tri_of(fcap) + 256 + 2 * 16 * (int64_t)f16 + 256 + 256 + 16;
+}
+template <int NW>
+__global__ void __launch_bounds__(64 * NW) k_selinv_panel(DevGraph d, const int64_t *__restrict__ sig_off, double *__restrict__ sig,
+                                                           const int32_t *__restrict__ list, int fcap) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int T = 64 * NW;
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lc = lane & 15, lr = lane >> 4;
+    const int s = list[blockIdx.x];
+    const DevFront fr = d.fronts[s];
+    const int npiv = fr.npiv, f = npiv + fr.nbnd;
+    const int f16 = (fcap + 15) & ~15;
+    double *S = smem, *Lk = S + tri_of(fcap), *LR = Lk + 256, *Wb = LR + 16 * f16, *Vb = Wb + 16 * f16, *Pb = Vb + 256, *dv = Pb + 256;
+    selinv_gather_bb(d, fr, sig_off, sig, S, tid, T);
+    const bool unit = d.factor_variant == 3;                        // uniform
+    const double *L = d.Lbuf + fr.L_off;
+    const int64_t ldl = f + 1;
+    auto sym = [&](int r, int c) -> double { return (r < f && c < f) ? (r >= c ? S[tri_of(r) + c] : S[tri_of(c) + r]) : 0.0; };
+    for (int k1 = npiv; k1 > 0; ) {
+        const int k0 = max(k1 - SEL_PANEL, 0), w = k1 - k0, nR = f - k1, nRp = (nR + 15) & ~15;
+        __syncthreads();                                            // the image of the previous panel (or the gather) is complete
+        // the panel's l (strictly lower, zero elsewhere), l[R, K] (zero beyond the front and the panel), 1 / d
+        for (int idx = tid; idx < 256; idx += T) { const int a = idx >> 4, j = idx & 15;
+            Lk[idx] = (a < w && j < a) ? selinv_l(L, ldl, k0 + a, k0 + j, unit) : 0.0; }
+        for (int idx = tid; idx < 16 * nRp; idx += T) { const int i = idx >> 4, j = idx & 15;
+            LR[idx] = (i < nR && j < w) ? selinv_l(L, ldl, k1 + i, k0 + j, unit) : 0.0; }
+        if (tid < 16) dv[tid] = tid < w ? selinv_dinv(d, L, ldl, fr.piv0, k0 + tid, unit) : 0.0;
+        __syncthreads();
+        // 1. W = -Sigma[R, R] l[R, K]: row tile I by wave I mod NW; A[i][k] = Sigma[k1 + 16 I + i, k1 + c0 + k], B[k][j] = l[k1 + c0 + k, k0 + j]
+        for (int I = wave; I < nRp / 16; I += NW) {
+            v4d acc = {0.0, 0.0, 0.0, 0.0};
+            for (int c0 = 0; c0 < nRp; c0 += 4)
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(sym(k1 + 16 * I + lc, k1 + c0 + lr), LR[(c0 + lr) * 16 + lc], acc, 0, 0, 0);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) Wb[(16 * I + lr + 4 * q) * 16 + lc] = -acc[q];
+        }
+        __syncthreads();
+        // 2. Sigma[R, K]: a thread per row of R, the chain through the panel's pivots in registers
+        for (int t = tid; t < nR; t += T) {
+            double sv[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) sv[j] = Wb[t * 16 + j];
+#pragma unroll
+            for (int k = 15; k >= 0; --k) {
+                double x = sv[k];
+#pragma unroll
+                for (int c = k + 1; c < 16; ++c) x -= sv[c] * Lk[c * 16 + k];
+                sv[k] = x; }
+#pragma unroll
+            for (int j = 0; j < 16; ++j) { Wb[t * 16 + j] = sv[j]; if (j < w) S[tri_of(k1 + t) + k0 + j] = sv[j]; }
+        }
+        __syncthreads();
+        if (wave == 0) {
+            // 3. V = Sigma[R, K]^T l[R, K]: A[a][k] = Sigma[k1 + c0 + k, k0 + a], B[k][b] = l[k1 + c0 + k, k0 + b]
+            v4d acc = {0.0, 0.0, 0.0, 0.0};
+            for (int c0 = 0; c0 < nRp; c0 += 4)
+                acc = __builtin_amdgcn_mfma_f64_16x16x4f64(Wb[(c0 + lr) * 16 + lc], LR[(c0 + lr) * 16 + lc], acc, 0, 0, 0);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) Vb[(lr + 4 * q) * 16 + lc] = acc[q];
+            wave_lds_sync();
+            // 4. the panel's own block (Pb: both halves), lane r = row r
+            for (int k = w - 1; k >= 0; --k) {
+                if (lane > k && lane < w) {
+                    double x = -Vb[lane * 16 + k];
+                    for (int c = k + 1; c < w; ++c) x -= Pb[lane * 16 + c] * Lk[c * 16 + k];
+                    Pb[lane * 16 + k] = x; Pb[k * 16 + lane] = x; }
+                wave_lds_sync();
+                if (lane == 0) {
+                    double x = dv[k] - Vb[k * 16 + k];
+                    for (int r = k + 1; r < w; ++r) x -= Lk[r * 16 + k] * Pb[r * 16 + k];
+                    Pb[k * 16 + k] = x; }
+                wave_lds_sync();
+            }
+            for (int idx = lane; idx < 256; idx += 64) { const int r = idx >> 4, c = idx & 15;
+                if (r < w && c <= r) S[tri_of(k0 + r) + k0 + c] = Pb[idx]; }
+        }
+        k1 = k0;
+    }
+    __syncthreads();
+    double *out = sig + sig_off[s];
+    const int64_t nt = tri_of(f);
+    for (int64_t idx = tid; idx < nt; idx += T) out[idx] = S[idx];
+}
+// Fronts of more than 159 scalars (variant-4 plans only): a workgroup per front, a pivot at a time, the image in its arena slot.
+__global__ void __launch_bounds__(256) k_selinv_big(DevGraph d, const int64_t *__restrict__ sig_off, double *__restrict__ sig, const int32_t *__restrict__ list) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int s = list[blockIdx.x];
+    const DevFront fr = d.fronts[s];
+    const int npiv = fr.npiv, f = npiv + fr.nbnd, tid = threadIdx.x;
+    double *S = sig + sig_off[s];
+    double *lv = smem;                                              // l[c, k] of the current pivot (c > k)
+    double *red = lv + f;                                           // the four waves' partial sums
+    selinv_gather_bb(d, fr, sig_off, sig, S, tid, 256);
+    __syncthreads();
+    const bool unit = d.factor_variant == 3;
+    const double *L = d.Lbuf + fr.L_off;
+    const int64_t ldl = f + 1;
+    for (int k = npiv - 1; k >= 0; --k) {
+        const double dinv = selinv_dinv(d, L, ldl, fr.piv0, k, unit);
+        for (int c = k + 1 + tid; c < f; c += 256) lv[c] = selinv_l(L, ldl, c, k, unit);
+        __syncthreads();
+        double part = 0.0;
+        for (int r = k + 1 + tid; r < f; r += 256) {
+            double *Sr = S + tri_of(r);
+            double t = 0.0;
+            for (int c = k + 1; c <= r; ++c) t += Sr[c] * lv[c];                 // row r of the image
+            for (int c = r + 1; c < f; ++c) t += S[tri_of(c) + r] * lv[c];      // its upper part: column r
+            Sr[k] = -t;
+            part += lv[r] * t;
+        }
+        for (int o = 32; o > 0; o >>= 1) part += __shfl_down(part, o, WAVE);
+        if ((tid & 63) == 0) red[tid >> 6] = part;
+        __syncthreads();
+        if (tid == 0) S[tri_of(k) + k] = dinv + ((red[0] + red[1]) + (red[2] + red[3]));
+        __syncthreads();
+    }
+}
+__global__ void __launch_bounds__(256) k_sigma_gather(int64_t n, const int64_t *__restrict__ tab, const double *__restrict__ sig, double *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) { const int64_t o = tab[i]; out[i] = o >= 0 ? sig[o] : 0.0; }
+}
+void launch_selinv(const DevGraph &d, const int64_t *sig_off, double *sig, const int32_t *list, int count, int max_f, hipStream_t st) {
+    if (count <= 0) return;
+    if (max_f <= 63) {
+        const size_t lds = (size_t)selinv_panel_lds_doubles(max_f) * sizeof(double);
+        allow_max_lds(reinterpret_cast<const void *>(&k_selinv_panel<1>));
+        hipLaunchKernelGGL(k_selinv_panel<1>, dim3(count), dim3(64), lds, st, d, sig_off, sig, list, max_f);
+    } else if (max_f <= 159) {
+        const size_t lds = (size_t)selinv_panel_lds_doubles(max_f) * sizeof(double);
+        allow_max_lds(reinterpret_cast<const void *>(&k_selinv_panel<4>));
+        hipLaunchKernelGGL(k_selinv_panel<4>, dim3(count), dim3(256), lds, st, d, sig_off, sig, list, max_f);
+    } else hipLaunchKernelGGL(k_selinv_big, dim3(count), dim3(256), ((size_t)max_f + 4) * sizeof(double), st, d, sig_off, sig, list);
+}
+void launch_sigma_gather(int64_t n, const int64_t *tab, const double *sig, double *out, hipStream_t st) {
+    if (n > 0) hipLaunchKernelGGL(k_sigma_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n, tab, sig, out);
 }
 
 void launch_polar_to_xy(int n, const double *az, const double *zen, const double *dist, double lidar, double *out, hipStream_t st) {

@@ -72,6 +72,27 @@ extern "C" int gs_slam_get_map(gs_slam *s, int32_t cap, double *xy, int32_t *typ
     return (int)s->map.size();
 }
 
+extern "C" int gs_slam_get_map_covariances(gs_slam *s, int32_t cap, double *out) {
+    if (!s || !out) return fail(GS_ERR_INVALID, "null argument");
+    if (cap < (int)s->map.size()) return fail(GS_ERR_CAPACITY, "buffer too small");
+    // the mirror fixes its gauge (poses 1000 / 1001, cones 0 / 1) at its first optimizeGraph (loop closure); before that H is singular in exact
+    // arithmetic and a factorisation may still find no exactly-zero pivot: no covariances until the gauge is there
+    if (s->g->host_only) return fail(GS_ERR_NO_DEVICE, "host-only handle (device = -2): no compute without a gfx950 device");
+    const gs::HostGraph &hg = s->g->h;
+    bool gauge = false;
+    for (uint8_t f : hg.pose_fixed) gauge = gauge || f;
+    for (uint8_t f : hg.lm_fixed) gauge = gauge || f;
+    if (!gauge) return fail(GS_ERR_NOT_INITIALIZED, "the Slam mirror has not fixed its gauge yet (it does at the first optimizeGraph, the loop closure): no covariances before that");
+    int rc = gs_compute_marginals(s->g, nullptr); if (rc != GS_OK) return rc;
+    const gs::HostGraph &h = s->g->h;
+    std::vector<double> cov(4 * (size_t)h.n_lms());
+    rc = gs_get_landmark_covariances(s->g, h.n_lms(), nullptr, cov.data()); if (rc < 0) return rc;
+    for (size_t j = 0; j < s->map.size(); ++j) {
+        auto it = h.lm_index.find(s->map[j].id);
+        for (int k = 0; k < 4; ++k) out[4 * j + k] = it == h.lm_index.end() ? 0.0 : cov[4 * (size_t)it->second + k]; }
+    return (int)s->map.size();
+}
+
 static double normalize_theta(double th) {
     if (th >= -M_PI && th < M_PI) return th;
     double m = std::floor(th / (2 * M_PI)); th -= m * 2 * M_PI;
