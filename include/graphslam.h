@@ -226,8 +226,9 @@ int  gs_get_stats(gs_graph *g, gs_stats *stats);      /* plan statistics after i
  *      stream; returns the mean milliseconds per pass in *out_ms_per_pass.
  * gs_linearize_bytes: algorithmic bytes of one pass, SURVEY §8(d):
  *      E_pp*152 + E_pl*96 + N*120 + M*64.
- * gs_export_system: copy the block-sparse H and b of the last linearisation to the host (gs_compute_marginals
- *      counts as one: after it, these are H and b at the estimates of that call)
+ * gs_export_system: copy the block-sparse H and b of the last linearisation to the host (gs_linearize, the last
+ *      iteration of gs_optimize / gs_iterate: H and b at the estimates before its update, or gs_compute_marginals:
+ *      H and b at the estimates of that call)
  *      (vertex arrays in insertion order, edge arrays in the order reported by *_edge_order):
  *      Hpp_diag [N*9], Hll_diag [M*4], Hpp_off [Epp*9] (= A^T Omega B), Hpl [Epl*6] (= A^T Omega B,
  *      3x2 row-major), b_pose [N*3], b_lm [M*2].  Any pointer may be NULL.

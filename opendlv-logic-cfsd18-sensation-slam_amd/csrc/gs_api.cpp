@@ -1452,6 +1452,10 @@ extern "C" int gs_export_system(gs_graph *g, double *Hpp_diag, double *Hll_diag,
     if (g->d.tN > 0) return fail(GS_ERR_INVALID, "the plan has grown by appended poses: their blocks live in the tail arenas, which this export does not read (gs_initialize_optimization with GS_GROW=0 rebuilds)");
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
     const DevGraph &d = g->d;
+    // an iteration and gs_compute_marginals leave the landmark blocks as per-edge partials (the fronts sum them): sum them here, so
+    // that H_ll and b_l are those of the last linearisation whichever call ran it
+    launch_linearize_finalize(d, g->stream, false);
+    { const hipError_t e = hipGetLastError(); if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("export: ") + hipGetErrorString(e)); }
     // the device keeps these arrays structure-of-arrays (and the diagonal blocks packed symmetric); the
     // export format is array-of-blocks, full and row-major
     const size_t N = (size_t)d.N, M = (size_t)d.M, Epp = (size_t)d.Epp, Epl = (size_t)d.Epl;

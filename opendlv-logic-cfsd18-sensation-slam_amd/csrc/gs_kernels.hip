@@ -728,7 +728,7 @@ __global__ void __launch_bounds__(256, LIN_WAVES_PER_SIMD) k_linearize_ell(DevGr
 }
 
 // landmark diagonal blocks from the per-(wave tile, landmark) partials (slots ordered by landmark, then tile)
-// + the chi2 total (fixed order)
+// + the chi2 total (fixed order; n_partial < 0: the landmark blocks only)
 __global__ void __launch_bounds__(256) k_linearize_finalize(DevGraph d, int n_partial) {
     __shared__ double red[8];
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
@@ -742,7 +742,7 @@ __global__ void __launch_bounds__(256) k_linearize_finalize(DevGraph d, int n_pa
         d.Hll_diag[l] = a[0]; d.Hll_diag[(int64_t)d.M + l] = a[1]; d.Hll_diag[2 * (int64_t)d.M + l] = a[2];
         d.b_lm[l] = a[3]; d.b_lm[(int64_t)d.M + l] = a[4];
     }
-    if (blockIdx.x == gridDim.x - 1) {
+    if (n_partial >= 0 && blockIdx.x == gridDim.x - 1) {           // (uniform over the block: block_sum's barriers are safe)
         double s = 0.0;
         for (int k = threadIdx.x; k < n_partial; k += 256) s += d.chi2_partial[k];
         const double tot = block_sum(s, red);
@@ -765,10 +765,12 @@ void launch_linearize_gather(const DevGraph &d, hipStream_t st) {
     hipLaunchKernelGGL(k_reduce_chi2, dim3(1), dim3(256), 0, st, d, gp);
 }
 // materialise H_ll, b_l and the chi2 total from the fused kernel's partials (export / chi2 queries only: inside an
-// iteration the front assembly sums the landmark slots itself and k_update totals chi2)
-void launch_linearize_finalize(const DevGraph &d, hipStream_t st) {
+// iteration the front assembly sums the landmark slots itself and k_update totals chi2).  with_chi2 = false: the landmark blocks
+// alone, from the partials of whichever linearisation ran last (gs_export_system: an iteration's, or gs_compute_marginals')
+void launch_linearize_finalize(const DevGraph &d, hipStream_t st, bool with_chi2) {
     if (d.n_wtiles > 0)
-        hipLaunchKernelGGL(k_linearize_finalize, dim3(max(1, (d.M + 255) / 256)), dim3(256), 0, st, d, d.n_wtiles + (d.tN > 0 ? 1 : 0));     // (+ the tail's partial)
+        hipLaunchKernelGGL(k_linearize_finalize, dim3(max(1, (d.M + 255) / 256)), dim3(256), 0, st, d,
+                           with_chi2 ? d.n_wtiles + (d.tN > 0 ? 1 : 0) : -1);     // (+ the tail's partial)
 }
 // start / stop (optional): HIP events attached to THIS dispatch (hipExtLaunchKernelGGL) — the kernel's own begin and end as the
 // command processor stamps them, what a kernel trace reports; an event recorded before / after the launch also holds the
