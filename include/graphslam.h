@@ -87,6 +87,11 @@ typedef struct gs_config {
                                         rewritten after loop closure, which restoring the reference's comments would not do.  One more
                                         keyframe does not rebuild the structure here (append-only growth), so the call costs about a
                                         millisecond at lap size; in localizer mode the published pose is then the optimised one. */
+    /* robust kernels, applied by gs_create (see gs_set_robust_kernel); the defaults, none on both kinds, are the reference's behaviour */
+    int32_t odometry_robust_kernel;     /* GS_ROBUST_*, 0 = none                                */
+    double  odometry_robust_delta;      /* 1.0                                                  */
+    int32_t observation_robust_kernel;  /* GS_ROBUST_*, 0 = none                                */
+    double  observation_robust_delta;   /* 1.0                                                  */
 } gs_config;
 
 /* per-call statistics of gs_optimize / gs_iterate (all times from HIP events on
@@ -209,16 +214,50 @@ int  gs_get_landmarks(gs_graph *g, int32_t capacity, int32_t *out_ids, double *o
  *      stop rule, this is the build-defined one.  Iterates until the chi2 at two
  *      consecutive linearisation points differs by <= rel_chi2_tol * chi2 (checked on the device
  *      value every iteration), at most max_iterations; returns the iterations whose update
- *      was applied, 0 on failure as gs_optimize. */
+ *      was applied, 0 on failure as gs_optimize.
+ * With a robust kernel set (gs_set_robust_kernel) every chi2 these calls report (gs_chi2, gs_stats.chi2_initial / chi2_final, the
+ *      verbose line) is the sum of rho(s) over the edges (g2o activeRobustChi2), and the stop rule of gs_optimize_until compares
+ *      that sum. */
 int  gs_initialize_optimization(gs_graph *g);
 int  gs_optimize(gs_graph *g, int32_t iterations, gs_stats *stats /* may be NULL */);
 int  gs_optimize_until(gs_graph *g, int32_t max_iterations, double rel_chi2_tol, gs_stats *stats /* may be NULL */);
 int  gs_iterate(gs_graph *g);
 int  gs_sync_estimates(gs_graph *g);      /* device -> host estimates, waits for the stream   */
 int  gs_stream_synchronize(gs_graph *g);
-/* computeActiveErrors + activeChi2 at the current estimates (device) */
+/* computeActiveErrors + activeChi2 at the current estimates (device); with a robust kernel set: activeRobustChi2, the sum of rho(s) */
 int  gs_chi2(gs_graph *g, double *out_chi2);
 int  gs_get_stats(gs_graph *g, gs_stats *stats);      /* plan statistics after initialize */
+
+/* ---- robust kernels ---------------------------------------------------------
+ * <- g2o OptimizableGraph::Edge::setRobustKernel with RobustKernelHuber / RobustKernelCauchy (the reference never sets one; the
+ * formulas are restated from g2o's published text, not pinned against a g2o build).  For an edge with squared error
+ * s = e^T Omega e (g2o's e->chi2()) and parameter delta, d2 = delta^2:
+ *      none     rho(s) = s                                          w = rho'(s) = 1
+ *      Huber    rho(s) = s if s <= d2, else 2 sqrt(s) delta - d2    w = 1 if s <= d2, else delta / sqrt(s)
+ *      Cauchy   rho(s) = d2 log(1 + s / d2)                         w = 1 / (1 + s / d2)
+ * The edge contributes w A^T Omega A, w A^T Omega B, w B^T Omega B to H, -w A^T Omega e, -w B^T Omega e to b (the second-order
+ * term 2 rho'' (Omega e)(Omega e)^T is dropped, as g2o drops it) and rho(s) to chi2: one iteration is the plain Gauss-Newton
+ * iteration of the same graph with every information matrix scaled by its edge's weight at the current estimates.
+ * delta is in units of sqrt(s), i.e. it INCLUDES Omega: with the reference's cone_information = 0.01 a cone matched 3 m off has
+ * sqrt(s) = 0.3, and the residuals at a clean optimum are near 0.01.  delta = 1, g2o's default, does nothing on this graph.
+ * The kernel is set per edge KIND on the handle (all odometry edges / all observation edges), not per edge.  The setting belongs
+ * to the handle: it survives gs_clear, growth and structure phases, costs no structure phase, may change between two gs_iterate
+ * calls, and makes the marginals stale like any other change.  It can be set and read on a host-only handle.
+ * Unknown kind or kernel, or (kernel other than none) a delta that is not finite and > 0: GS_ERR_INVALID.
+ * NOT DONE: pose-window shards.  gs_set_robust_kernel(other than none) on a handle configured with gs_dist_configure(world > 1),
+ * and gs_dist_configure(world > 1) on a handle with a kernel set, return GS_ERR_INVALID.
+ * gs_get_edge_chi2: per edge of that kind, insertion order, at the CURRENT estimates: s = e^T Omega e and the weight rho'(s) of the
+ *      kind's kernel (1 with GS_ROBUST_NONE).  Edges between two fixed vertices are reported too (they stay out of chi2).  Either
+ *      pointer may be NULL; returns the number of edges (GS_ERR_CAPACITY when capacity is below it and a pointer is given);
+ *      a host-only handle GS_ERR_NO_DEVICE, a sharded handle GS_ERR_INVALID. */
+#define GS_ROBUST_NONE      0
+#define GS_ROBUST_HUBER     1
+#define GS_ROBUST_CAUCHY    2
+#define GS_EDGE_ODOMETRY    0
+#define GS_EDGE_OBSERVATION 1
+int  gs_set_robust_kernel(gs_graph *g, int32_t edge_kind, int32_t kernel, double delta);
+int  gs_get_robust_kernel(gs_graph *g, int32_t edge_kind, int32_t *out_kernel, double *out_delta);
+int  gs_get_edge_chi2(gs_graph *g, int32_t edge_kind, int32_t capacity, double *out_chi2, double *out_weight);
 
 /* ---- measurement / parity hooks (tuning, fault injection and timestamps: include/graphslam_debug.h) ----------
  * gs_linearize: one A5+A6+A7 pass (the roofline kernel) on the stream, nothing else.
@@ -228,7 +267,7 @@ int  gs_get_stats(gs_graph *g, gs_stats *stats);      /* plan statistics after i
  *      E_pp*152 + E_pl*96 + N*120 + M*64.
  * gs_export_system: copy the block-sparse H and b of the last linearisation to the host (gs_linearize, the last
  *      iteration of gs_optimize / gs_iterate: H and b at the estimates before its update, or gs_compute_marginals:
- *      H and b at the estimates of that call)
+ *      H and b at the estimates of that call); with a robust kernel set: the WEIGHTED H and b (every edge's blocks scaled by rho'(s))
  *      (vertex arrays in insertion order, edge arrays in the order reported by *_edge_order):
  *      Hpp_diag [N*9], Hll_diag [M*4], Hpp_off [Epp*9] (= A^T Omega B), Hpl [Epl*6] (= A^T Omega B,
  *      3x2 row-major), b_pose [N*3], b_lm [M*2].  Any pointer may be NULL.
@@ -280,7 +319,8 @@ int  gs_plan_export(gs_graph *g, int32_t *out, int64_t *out_len);
  *      counterpart of what g2o offers; the reference itself never calls it.  Linearises H at the CURRENT
  *      estimates (the ones gs_get_* returns), factorises it with the iteration's kernels and launch sequence
  *      (no backward solve, no update) and runs a selected inversion of the factor (Takahashi recursion):
- *      Sigma = H^-1 on the pattern of L, kept on the device by the handle.  g2o's computeMarginals reuses the
+ *      Sigma = H^-1 on the pattern of L, kept on the device by the handle.  With a robust kernel set H is the weighted H
+ *      (gs_set_robust_kernel), and a change of the setting makes the results stale like an iteration does.  g2o's computeMarginals reuses the
  *      last iteration's factor instead, taken at the estimates BEFORE that iteration's update.
  *      Nothing else moves: no estimate, no chi2 history, no stop / failure / fallback state of gs_optimize_until
  *      and gs_iterate; runs on the handle's stream.  It is a linearisation, though: gs_export_system afterwards

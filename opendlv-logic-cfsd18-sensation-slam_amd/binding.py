@@ -38,7 +38,14 @@ class Config(C.Structure):
                 ("same_cone_threshold", C.c_double), ("cone_mapping_threshold", C.c_double),
                 ("lidar_to_cog", C.c_double), ("loop_closing_radius", C.c_double),
                 ("loop_closing_min_index", C.c_int32), ("optimize_iterations", C.c_int32),
-                ("reference_quirks", C.c_int32), ("optimize_every_keyframe", C.c_int32)]
+                ("reference_quirks", C.c_int32), ("optimize_every_keyframe", C.c_int32),
+                ("odometry_robust_kernel", C.c_int32), ("odometry_robust_delta", C.c_double),
+                ("observation_robust_kernel", C.c_int32), ("observation_robust_delta", C.c_double)]
+
+
+# gs_set_robust_kernel: GS_ROBUST_* / GS_EDGE_* of include/graphslam.h by name
+ROBUST_KERNELS = {"none": 0, "huber": 1, "cauchy": 2}
+EDGE_KINDS = {"odometry": 0, "observation": 1}
 
 
 class Stats(C.Structure):
@@ -220,6 +227,10 @@ def lib():
         L.gs_get_odometry_edge_covariances.argtypes = [vp, C.c_int32, _dp]
         L.gs_get_observation_edge_covariances.argtypes = [vp, C.c_int32, _dp]
         L.gs_get_covariance_block.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp]
+    if hasattr(L, "gs_set_robust_kernel"):                 # (a tuning build of an older tree loaded through GS_LIB may predate the robust kernels)
+        L.gs_set_robust_kernel.argtypes = [vp, C.c_int32, C.c_int32, C.c_double]
+        L.gs_get_robust_kernel.argtypes = [vp, C.c_int32, _ip, _dp]
+        L.gs_get_edge_chi2.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp]
     L.gs_slam_get_send_pose.argtypes = [vp, _dp]
     L.gs_slam_collect_direction.argtypes = [vp, C.c_uint32, C.c_double, C.c_double]
     L.gs_slam_collect_distance.argtypes = [vp, C.c_uint32, C.c_double]
@@ -262,6 +273,8 @@ def default_config(**kw):
     cfg = Config()
     lib().gs_config_default(C.byref(cfg))
     for k, v in kw.items():
+        if k.endswith("_robust_kernel"):
+            v = ROBUST_KERNELS.get(v, v)
         setattr(cfg, k, v)
     return cfg
 
@@ -543,6 +556,24 @@ class Graph:
         ka = {"pose": 0, "landmark": 1}.get(kind_a, kind_a); kb = {"pose": 0, "landmark": 1}.get(kind_b, kind_b)
         out = np.zeros((3 if ka == 0 else 2, 3 if kb == 0 else 2))
         self._check(self.L.gs_get_covariance_block(self.h, int(ka), int(id_a), int(kb), int(id_b), _d(out))); return out
+
+    # ---- robust kernels (gs_set_robust_kernel: per edge kind on the handle)
+    def set_robust_kernel(self, kind, kernel, delta=1.0):
+        """kind "odometry" / "observation", kernel "none" / "huber" / "cauchy" (or the GS_EDGE_* / GS_ROBUST_* numbers); delta in units of sqrt(e^T Omega e)"""
+        self._check(self.L.gs_set_robust_kernel(self.h, int(EDGE_KINDS.get(kind, kind)), int(ROBUST_KERNELS.get(kernel, kernel)), float(delta)))
+
+    def robust_kernel(self, kind):
+        """(kernel name, delta) of the edge kind"""
+        k = C.c_int32(); d = C.c_double()
+        self._check(self.L.gs_get_robust_kernel(self.h, int(EDGE_KINDS.get(kind, kind)), C.byref(k), C.byref(d)))
+        return {v: n for n, v in ROBUST_KERNELS.items()}.get(k.value, k.value), d.value
+
+    def edge_chi2(self, kind):
+        """(chi2, weight): s = e^T Omega e and rho'(s) of every edge of the kind at the current estimates, insertion order"""
+        kd = int(EDGE_KINDS.get(kind, kind))
+        n = self.n_pp if kd == 0 else self.n_pl
+        s = np.zeros(n); w = np.zeros(n)
+        self._check(self.L.gs_get_edge_chi2(self.h, kd, n, _d(s), _d(w))); return s, w
 
     # ---- host-only plan (no device work)
     def plan_build_host(self):

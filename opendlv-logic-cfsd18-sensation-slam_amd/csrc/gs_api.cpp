@@ -81,12 +81,22 @@ template <class T, class A> static int dev_upload(gs_graph *g, T **ptr, const st
     if (!v.empty()) HIP_TRY(hipMemcpyAsync(*ptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, g->stream));
     return GS_OK;
 }
+// the handle's robust kernels (cfg.*_robust_*) travel to the kernels by value in DevGraph
+static void apply_robust(gs_graph *g) {
+    g->d.rk_pp = g->cfg.odometry_robust_kernel; g->d.rd_pp = g->cfg.odometry_robust_delta;
+    g->d.rk_pl = g->cfg.observation_robust_kernel; g->d.rd_pl = g->cfg.observation_robust_delta;
+}
+static int robust_check(int32_t kernel, double delta) {
+    if (kernel != GS_ROBUST_NONE && kernel != GS_ROBUST_HUBER && kernel != GS_ROBUST_CAUCHY) return fail(GS_ERR_INVALID, "unknown robust kernel (GS_ROBUST_NONE / HUBER / CAUCHY)");
+    if (kernel != GS_ROBUST_NONE && !(std::isfinite(delta) && delta > 0.0)) return fail(GS_ERR_INVALID, "robust kernel: delta must be finite and > 0");
+    return GS_OK;
+}
 // the device side of a plan goes away; keep = the memory stays with the handle for the next plan
 static void dev_release(gs_graph *g, bool keep) {
     if (!keep) { for (auto &c : g->allocs) hipFree(c.p); g->allocs.clear(); }
     else for (auto &c : g->allocs) { c.in_use = false; if (pool_poison(g) && g->stream) hipMemsetAsync(c.p, 0xFF, c.size, g->stream); }
     g->pool_base = nullptr; g->pool_size = g->pool_off = 0; g->pool_next = 0; g->pool_total = 0;
-    g->d = DevGraph();
+    g->d = DevGraph(); apply_robust(g);
     g->dev_valid = false;
     g->room = gs_graph::GrowRoom(); g->d_bf = g->d_xrow = g->d_patch = g->d_list = nullptr;
     g->marg = gs_graph::Marginals();                                // its buffers were pool memory of the plan
@@ -127,6 +137,8 @@ extern "C" int gs_config_default(gs_config *c) {
     c->loop_closing_min_index = 20;      // reference src/slam.cpp:702
     c->optimize_iterations = 10;         // reference src/slam.cpp:481
     c->reference_quirks = 0;
+    c->odometry_robust_kernel = GS_ROBUST_NONE; c->odometry_robust_delta = 1.0;       // the reference sets no robust kernel
+    c->observation_robust_kernel = GS_ROBUST_NONE; c->observation_robust_delta = 1.0;
     return GS_OK;
 }
 
@@ -183,6 +195,10 @@ extern "C" int gs_create(const gs_config *cfg, gs_graph **out) {
     gs_config c;
     gs_config_default(&c);
     if (cfg) { size_t n = std::min<size_t>(sizeof(c), (size_t)std::max(cfg->struct_size, 0)); std::memcpy(&c, cfg, n); c.struct_size = (int32_t)sizeof(c); }
+    { int rc = robust_check(c.odometry_robust_kernel, c.odometry_robust_delta); if (rc != GS_OK) return rc;
+      rc = robust_check(c.observation_robust_kernel, c.observation_robust_delta); if (rc != GS_OK) return rc;
+      if (c.odometry_robust_kernel == GS_ROBUST_NONE) c.odometry_robust_delta = 1.0;           // (unused; kept valid)
+      if (c.observation_robust_kernel == GS_ROBUST_NONE) c.observation_robust_delta = 1.0; }
     if (c.device == -2) {   // host-only handle: graph container + plan inspection, never any arithmetic
         gs_graph *g = new gs_graph(); g->cfg = c; g->device = -2; g->host_only = true; options_from_environment(g->opt); *out = g; return GS_OK; }
     int ndev = usable_devices();
@@ -196,6 +212,7 @@ extern "C" int gs_create(const gs_config *cfg, gs_graph **out) {
         return fail(GS_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
     gs_graph *g = new gs_graph();
     g->cfg = c; g->device = dev; g->force_gather = c.linearize_gather != 0; g->default_factor_variant = c.factor_variant;
+    apply_robust(g);
     options_from_environment(g->opt);
     HIP_TRY(hipSetDevice(dev));
     if (hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking) != hipSuccess) { delete g; return fail(GS_ERR_HIP, "hipStreamCreate failed"); }
@@ -223,6 +240,28 @@ extern "C" int gs_clear(gs_graph *g) {
     if (!g) return fail(GS_ERR_INVALID, "null graph");
     if (!g->host_only) { hipSetDevice(g->device); hipStreamSynchronize(g->stream); dev_free_all(g); }
     g->h.clear(); g->plan = Plan(); g->plan_version = ~0ull;
+    return GS_OK;
+}
+
+// ------------------------------------------------------------------ robust kernels
+extern "C" int gs_set_robust_kernel(gs_graph *g, int32_t edge_kind, int32_t kernel, double delta) {
+    if (!g) return fail(GS_ERR_INVALID, "null graph");
+    if (edge_kind != GS_EDGE_ODOMETRY && edge_kind != GS_EDGE_OBSERVATION) return fail(GS_ERR_INVALID, "edge kind must be GS_EDGE_ODOMETRY or GS_EDGE_OBSERVATION");
+    int rc = robust_check(kernel, delta); if (rc != GS_OK) return rc;
+    if (kernel != GS_ROBUST_NONE && g->world > 1) return fail(GS_ERR_INVALID, "robust kernels are not supported on sharded handles (gs_dist_configure with world > 1)");
+    if (kernel == GS_ROBUST_NONE) delta = 1.0;
+    if (edge_kind == GS_EDGE_ODOMETRY) { g->cfg.odometry_robust_kernel = kernel; g->cfg.odometry_robust_delta = delta; }
+    else { g->cfg.observation_robust_kernel = kernel; g->cfg.observation_robust_delta = delta; }
+    apply_robust(g);                        // the kernels take the setting by value at their next launch: no structure phase, no wait
+    g->marg.valid = false;                  // H changes with the weights
+    return GS_OK;
+}
+extern "C" int gs_get_robust_kernel(gs_graph *g, int32_t edge_kind, int32_t *out_kernel, double *out_delta) {
+    if (!g) return fail(GS_ERR_INVALID, "null graph");
+    if (edge_kind != GS_EDGE_ODOMETRY && edge_kind != GS_EDGE_OBSERVATION) return fail(GS_ERR_INVALID, "edge kind must be GS_EDGE_ODOMETRY or GS_EDGE_OBSERVATION");
+    const bool pp = edge_kind == GS_EDGE_ODOMETRY;
+    if (out_kernel) *out_kernel = pp ? g->cfg.odometry_robust_kernel : g->cfg.observation_robust_kernel;
+    if (out_delta) *out_delta = pp ? g->cfg.odometry_robust_delta : g->cfg.observation_robust_delta;
     return GS_OK;
 }
 
@@ -1478,6 +1517,44 @@ extern "C" int gs_export_system(gs_graph *g, double *Hpp_diag, double *Hll_diag,
     if (pl_order) for (size_t k = 0; k < Epl; ++k) pl_order[k] = (int32_t)k;                 // exported in insertion order
     return GS_OK;
 }
+// per-edge s = e^T W e and weight at the current estimates (k_edge_chi2).  The index table of the kind's edges goes up with the call
+// (a query, not part of an iteration): endpoints from the host graph, an observation edge's place from the plan — its ELL index,
+// or its tail slot when a growth step appended it
+extern "C" int gs_get_edge_chi2(gs_graph *g, int32_t edge_kind, int32_t capacity, double *out_chi2, double *out_weight) {
+    if (!g) return fail(GS_ERR_INVALID, "null graph");
+    if (edge_kind != GS_EDGE_ODOMETRY && edge_kind != GS_EDGE_OBSERVATION) return fail(GS_ERR_INVALID, "edge kind must be GS_EDGE_ODOMETRY or GS_EDGE_OBSERVATION");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: per-edge chi2 is not supported on sharded handles");
+    rc = ensure_ready(g); if (rc != GS_OK) return rc;
+    if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: per-edge chi2 is not supported on sharded handles");
+    const HostGraph &h = g->h; const Plan &P = g->plan;
+    const bool pp = edge_kind == GS_EDGE_ODOMETRY;
+    const int n = pp ? h.n_pp() : h.n_pl();
+    if ((out_chi2 || out_weight) && capacity < n) return fail(GS_ERR_CAPACITY, "buffer too small");
+    if (n == 0 || (!out_chi2 && !out_weight)) return n;
+    const int per = pp ? 2 : 3;
+    std::vector<int32_t> tab((size_t)n * per);
+    if (pp) for (int k = 0; k < n; ++k) { tab[2 * (size_t)k] = h.pp_i[k]; tab[2 * (size_t)k + 1] = h.pp_j[k]; }
+    else for (int k = 0; k < n; ++k) {
+        int32_t src;
+        if (k < P.base_Epl) { src = P.ell_of_ins[k]; if (src < 0) return fail(GS_ERR_INVALID, "observation edge outside the linearisation layout"); }
+        else { if (k - P.base_Epl >= g->d.tEpl) return fail(GS_ERR_INVALID, "observation edge not on the device"); src = -(k - P.base_Epl) - 1; }
+        tab[3 * (size_t)k] = h.pl_p[k]; tab[3 * (size_t)k + 1] = h.pl_l[k]; tab[3 * (size_t)k + 2] = src; }
+    if (pp && n > g->d.Epp + g->d.tEpp) return fail(GS_ERR_INVALID, "odometry edge not on the device");
+    int32_t *dtab = nullptr; double *dout = nullptr;
+    HIP_TRY(hipMalloc((void **)&dtab, tab.size() * sizeof(int32_t)));
+    if (hipMalloc((void **)&dout, (size_t)n * 2 * sizeof(double)) != hipSuccess) { hipFree(dtab); return fail(GS_ERR_HIP, "hipMalloc failed"); }
+    std::vector<double> out((size_t)n * 2);
+    hipError_t e = hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) { launch_edge_chi2(g->d, edge_kind, n, dtab, dout, g->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(out.data(), dout, out.size() * sizeof(double), hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->stream); else hipStreamSynchronize(g->stream);
+    hipFree(dtab); hipFree(dout);
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("edge chi2: ") + hipGetErrorString(e));
+    if (out_chi2) std::memcpy(out_chi2, out.data(), (size_t)n * sizeof(double));
+    if (out_weight) std::memcpy(out_weight, out.data() + n, (size_t)n * sizeof(double));
+    return n;
+}
 extern "C" int gs_export_delta(gs_graph *g, double *dpose, double *dlm) {
     if (!g) return fail(GS_ERR_INVALID, "null graph");
     if (!g->dev_valid) return fail(GS_ERR_NOT_INITIALIZED, "no iteration run yet");
@@ -1798,6 +1875,8 @@ extern "C" int gs_frame_frontend(gs_graph *g, const double pose[3], const double
 // ------------------------------------------------------------------ multi-GPU
 extern "C" int gs_dist_configure(gs_graph *g, int32_t rank, int32_t world) {
     if (!g || world < 1 || rank < 0 || rank >= world) return fail(GS_ERR_INVALID, "bad rank/world");
+    if (world > 1 && (g->cfg.odometry_robust_kernel != GS_ROBUST_NONE || g->cfg.observation_robust_kernel != GS_ROBUST_NONE))
+        return fail(GS_ERR_INVALID, "robust kernels are not supported on sharded handles: set GS_ROBUST_NONE on both edge kinds first");
     g->rank = rank; g->world = world; ++g->h.structure_version; ++g->h.reshape_version;
     return GS_OK;
 }

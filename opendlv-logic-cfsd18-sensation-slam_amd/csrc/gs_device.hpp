@@ -99,6 +99,9 @@ struct DevGraph {
     double *exchange = nullptr;                                 // dense slots of the shared fronts (all-reduced)
     double *dpiv = nullptr;                                     // gs_compute_marginals: the LDL^T factor kernels write the pivots D here, at piv0 + k
                                                                 // (non-null: the launchers pick the kernels' CAP instances; null in iterations)
+    // robust kernels (gs_set_robust_kernel): type (GS_ROBUST_*) and delta per edge kind, by value.  Either type != 0: the launchers
+    // pick the edge kernels' ROBUST instances; both 0: the plain instances, which never read these fields
+    int32_t rk_pp = 0, rk_pl = 0; double rd_pp = 1.0, rd_pl = 1.0;
 };
 
 // launchers (gs_kernels.hip); all asynchronous on `st`
@@ -106,6 +109,10 @@ void launch_linearize(const DevGraph &d, hipStream_t st, hipEvent_t start = null
 void launch_linearize_gather(const DevGraph &d, hipStream_t st);
 void launch_linearize_finalize(const DevGraph &d, hipStream_t st, bool with_chi2 = true);   // H_ll, b_l (and the chi2 total) from the fused kernel's partials
 void launch_chi2_only(const DevGraph &d, hipStream_t st);
+// gs_get_edge_chi2: a thread per edge of one kind, insertion order.  kind 0 (odometry): tab [n][2] {i, j}, edge k reads record k of
+// pp_zinv / pp_info; kind 1 (observation): tab [n][3] {pose, landmark, src}, src >= 0 the edge's ELL index, src < 0 tail slot -(src + 1).
+// out [2][n]: s = e^T W e, then the weight rho'(s) of the kind's kernel
+void launch_edge_chi2(const DevGraph &d, int kind, int n, const int32_t *tab, double *out, hipStream_t st);
 // mode: 0 own front, 1 contribution of this rank to a shared front (-> exchange), 2 shared front from the exchange
 void launch_factor_level(const DevGraph &d, int level_off, int count, int max_f, int mode, hipStream_t st);
 void launch_factor_tree(const DevGraph &d, int n_leaf, int leaf_slot, int leaf_max_f, int count, int n_block, int sub_first, int n_sub, hipStream_t st);   // variant 3: leaf level (+ the bottom subtrees: a level-1 front with its leaves per workgroup) + every level above

@@ -299,12 +299,35 @@ __device__ __forceinline__ void edge_pl(double px, double py, double c, double s
 //   Hp[6] = A^T W A (xx xy xt yy yt tt), bp[3] = -A^T W e, W6 = A^T W B (3x2 row-major),
 //   Hl[3] = B^T W B (00 01 11), bl[2] = -B^T W e, chi = e^T W e
 struct PlQuad { double Hp[6], bp[3], W6[6], Hl[3], bl[2], chi; };
+// Robust kernels (g2o RobustKernelHuber / RobustKernelCauchy, restated): for the squared error s = e^T W e of an edge returns rho(s)
+// and sets w = rho'(s).  kernel: GS_ROBUST_* of include/graphslam.h (0 none, 1 Huber, 2 Cauchy).  IEEE sqrt / log / division, every
+// product rounded on its own, so that a weight is a function of s alone wherever it is computed.  w is EXACTLY 1.0 where the kernel
+// does not act (none; Huber with s <= delta^2): scaling by it changes no bit.
+__device__ __forceinline__ double robust_rho(int kernel, double delta, double s, double &w) {
+#pragma clang fp contract(off)
+    w = 1.0;
+    if (kernel == 1) { const double d2 = delta * delta;
+        if (s > d2) { const double r = sqrt(s); w = delta / r; return 2.0 * r * delta - d2; }
+        return s; }
+    if (kernel == 2) { const double d2 = delta * delta, aux = 1.0 + s / d2; w = 1.0 / aux; return d2 * log(aux); }
+    return s;
+}
+// The scaled information enters the products below as an opaque value, like the loaded one it replaces: the compiler then forms the
+// same multiply-adds in the ROBUST instance as in the plain one, and a weight of exactly 1.0 gives the plain instance's bits
+// (tests: Huber with delta = 1e150 against none).  Without it the contraction of a * (w * wr) + ... is free to differ.
+__device__ __forceinline__ double opaque(double v) { asm volatile("" : "+v"(v)); return v; }
+// ROBUST: chi becomes rho(s) and the information matrix is scaled by rho'(s) before the products (g2o: constructQuadraticForm with a
+// robust kernel, without the second-order term) — the PLAIN linearisation of the edge with W <- w W.  rk / rd: kernel type and delta
+// of the observation edges (DevGraph::rk_pl, rd_pl); the plain instance ignores them.
+template <bool ROBUST = false>
 __device__ __forceinline__ void quad_pl(double px, double py, double c, double s, double lx, double ly, double zx, double zy,
-                                        double w00, double w01, double w11, PlQuad &q) {
+                                        double w00, double w01, double w11, PlQuad &q, int rk = 0, double rd = 1.0) {
     double ex, ey, A0[3], A1[3];
     edge_pl(px, py, c, s, lx, ly, zx, zy, ex, ey, A0, A1);
     double We0 = w00 * ex + w01 * ey, We1 = w01 * ex + w11 * ey;
     q.chi = ex * We0 + ey * We1;
+    if (ROBUST) { double wr; q.chi = robust_rho(rk, rd, q.chi, wr);
+        w00 = opaque(w00 * wr); w01 = opaque(w01 * wr); w11 = opaque(w11 * wr); We0 = opaque(We0 * wr); We1 = opaque(We1 * wr); }
     double WA0[3], WA1[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) { WA0[k] = w00 * A0[k] + w01 * A1[k]; WA1[k] = w01 * A0[k] + w11 * A1[k]; }
@@ -333,7 +356,9 @@ template <class Tp> __device__ __forceinline__ void st_wt(Tp *ptr, Tp v) { __hip
 #else
 #define ST_O(ptr, v) (*(ptr) = (v))
 #endif
-template <bool WRITE_H>
+// ROBUST: as in quad_pl — s is computed for BOTH endpoints of an edge by the same expression from the same operands, so the two
+// evaluations of an odometry edge scale by the same weight
+template <bool WRITE_H, bool ROBUST = false>
 __device__ __forceinline__ double pp_incidence(const DevGraph &d, int k, int role, const double xi[3], const double xj[3],
                                                double ci, double si, const double zinv5[5], const double w[6],
                                                bool fi, bool fj, double H[6], double b[3], double *hoff = nullptr, int64_t hoff_stride = 0) {
@@ -362,9 +387,13 @@ __device__ __forceinline__ double pp_incidence(const DevGraph &d, int k, int rol
 #else
     const double e0 = zinv5[0] + (cz * rx - sz * ry), e1 = zinv5[1] + (sz * rx + cz * ry), e2 = normalize_theta(zinv5[2] + rth);
 #endif
-    const double w00 = w[0], w01 = w[1], w02 = w[2], w11 = w[3], w12 = w[4], w22 = w[5];
-    const double We0 = w00 * e0 + w01 * e1 + w02 * e2, We1 = w01 * e0 + w11 * e1 + w12 * e2, We2 = w02 * e0 + w12 * e1 + w22 * e2;
-    if (role == 0 && !(fi && fj)) chi = e0 * We0 + e1 * We1 + e2 * We2;
+    double w00 = w[0], w01 = w[1], w02 = w[2], w11 = w[3], w12 = w[4], w22 = w[5];
+    double We0 = w00 * e0 + w01 * e1 + w02 * e2, We1 = w01 * e0 + w11 * e1 + w12 * e2, We2 = w02 * e0 + w12 * e1 + w22 * e2;
+    if (ROBUST) { double wr; const double rho = robust_rho(d.rk_pp, d.rd_pp, e0 * We0 + e1 * We1 + e2 * We2, wr);
+        if (role == 0 && !(fi && fj)) chi = rho;
+        w00 = opaque(w00 * wr); w01 = opaque(w01 * wr); w02 = opaque(w02 * wr); w11 = opaque(w11 * wr); w12 = opaque(w12 * wr); w22 = opaque(w22 * wr);
+        We0 = opaque(We0 * wr); We1 = opaque(We1 * wr); We2 = opaque(We2 * wr); }
+    else if (role == 0 && !(fi && fj)) chi = e0 * We0 + e1 * We1 + e2 * We2;
     if (WRITE_H) {
         const double m0 = cz * ci + sz * si, m1 = cz * si - sz * ci;
         const double bw0 = m0 * We0 - m1 * We1, bw1 = m1 * We0 + m0 * We1;      // b0.We, b1.We
@@ -395,7 +424,7 @@ __device__ __forceinline__ double pp_incidence(const DevGraph &d, int k, int rol
 // the same with the operands fetched here.  An incidence record is 8 bytes: {edge (-1: another shard evaluates it), other endpoint | role << 31}
 // (role 0: the pose that holds the record is the edge's i endpoint, 1: its j endpoint) — the pose itself is known to whoever walks its
 // records (16-byte {edge, role, i, j} records until round 3: 32 of the pass's ~150 excess bytes per pose)
-template <bool WRITE_H>
+template <bool WRITE_H, bool ROBUST = false>
 __device__ __forceinline__ double pp_incidence_rec(const DevGraph &d, const int2 inc, int p, double H[6], double b[3], bool have_cs = false, double own_c = 1.0, double own_s = 0.0) {
     const int k = inc.x, role = (int)((uint32_t)inc.y >> 31), other = inc.y & 0x7fffffff;
     if (k < 0) return 0.0;                                                       // evaluated by another shard
@@ -411,11 +440,11 @@ __device__ __forceinline__ double pp_incidence_rec(const DevGraph &d, const int2
     if (have_cs && i == p) { si = own_s; ci = own_c; }
     else if (have_cs) { const double2 t2 = reinterpret_cast<const double2 *>(d.pose_cs)[i]; ci = t2.x; si = t2.y; }   // fused kernel: cached
     else sincos(xi[2], &si, &ci);
-    return pp_incidence<WRITE_H>(d, k, role, xi, xj, ci, si, z5, w, d.pose_fixed[i], d.pose_fixed[j], H, b);
+    return pp_incidence<WRITE_H, ROBUST>(d, k, role, xi, xj, ci, si, z5, w, d.pose_fixed[i], d.pose_fixed[j], H, b);
 }
-template <bool WRITE_H>
+template <bool WRITE_H, bool ROBUST = false>
 __device__ __forceinline__ double pp_incidence_q(const DevGraph &d, int q, int p, double H[6], double b[3], bool have_cs = false, double own_c = 1.0, double own_s = 0.0) {
-    return pp_incidence_rec<WRITE_H>(d, reinterpret_cast<const int2 *>(d.ppinc)[q], p, H, b, have_cs, own_c, own_s);
+    return pp_incidence_rec<WRITE_H, ROBUST>(d, reinterpret_cast<const int2 *>(d.ppinc)[q], p, H, b, have_cs, own_c, own_s);
 }
 
 // one partial-sum record (64-byte aligned line): two 16-byte loads and one 8-byte load instead of five scattered 8-byte ones
@@ -446,7 +475,7 @@ __device__ __forceinline__ double block_sum(double v, double *red) {
 
 // ---- general fallback: gather kernels on the same ELL arrays (any slot count R; also the chi2-only pass).
 //      thread per pose / thread per landmark, every sum in fixed order.
-template <bool WRITE_H>
+template <bool WRITE_H, bool ROBUST = false>
 __global__ void __launch_bounds__(256) k_linearize_pose_gather(DevGraph d) {
     __shared__ double red[8];
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -463,8 +492,8 @@ __global__ void __launch_bounds__(256) k_linearize_pose_gather(DevGraph d) {
             const int l = d.ell_l[e];
             if (l < 0) continue;
             PlQuad q;
-            quad_pl(px, py, c, s, d.lm_est[2 * l], d.lm_est[2 * l + 1], d.ell_z[e], d.ell_z[L + e],
-                    d.ell_w[e], d.ell_w[L + e], d.ell_w[2 * L + e], q);
+            quad_pl<ROBUST>(px, py, c, s, d.lm_est[2 * l], d.lm_est[2 * l + 1], d.ell_z[e], d.ell_z[L + e],
+                            d.ell_w[e], d.ell_w[L + e], d.ell_w[2 * L + e], q, d.rk_pl, d.rd_pl);
             const bool fl = d.lm_fixed[l];
             if (!(fp && fl)) chi += q.chi;
             if (WRITE_H) {
@@ -477,7 +506,7 @@ __global__ void __launch_bounds__(256) k_linearize_pose_gather(DevGraph d) {
                 for (int k = 0; k < 6; ++k) d.Hpl[k * L + e] = both ? q.W6[k] : 0.0;
             }
         }
-        for (int q = d.ppadj_start[p]; q < d.ppadj_start[p + 1]; ++q) chi += pp_incidence_q<WRITE_H>(d, q, p, H, b);
+        for (int q = d.ppadj_start[p]; q < d.ppadj_start[p + 1]; ++q) chi += pp_incidence_q<WRITE_H, ROBUST>(d, q, p, H, b);
         if (WRITE_H) {
 #pragma unroll
             for (int k = 0; k < 6; ++k) d.Hpp_diag[(int64_t)k * d.N + p] = fp ? 0.0 : H[k];
@@ -489,6 +518,7 @@ __global__ void __launch_bounds__(256) k_linearize_pose_gather(DevGraph d) {
     if (threadIdx.x == 0) d.chi2_partial[blockIdx.x] = tot;
 }
 
+template <bool ROBUST = false>
 __global__ void __launch_bounds__(256) k_linearize_lm_gather(DevGraph d) {
     const int l = blockIdx.x * blockDim.x + threadIdx.x;
     if (l >= d.M) return;
@@ -501,8 +531,8 @@ __global__ void __launch_bounds__(256) k_linearize_lm_gather(DevGraph d) {
             const int p = d.ell_p0 + (int)((e % S) / d.ell_T);
             double s, c; sincos(d.pose_est[3 * p + 2], &s, &c);
             PlQuad r;
-            quad_pl(d.pose_est[3 * p], d.pose_est[3 * p + 1], c, s, lx, ly, d.ell_z[e], d.ell_z[L + e],
-                    d.ell_w[e], d.ell_w[L + e], d.ell_w[2 * L + e], r);
+            quad_pl<ROBUST>(d.pose_est[3 * p], d.pose_est[3 * p + 1], c, s, lx, ly, d.ell_z[e], d.ell_z[L + e],
+                            d.ell_w[e], d.ell_w[L + e], d.ell_w[2 * L + e], r, d.rk_pl, d.rd_pl);
             h00 += r.Hl[0]; h01 += r.Hl[1]; h11 += r.Hl[2]; b0 += r.bl[0]; b1 += r.bl[1];
         }
     }
@@ -587,7 +617,10 @@ template <class Tp> __device__ __forceinline__ void st_off_wt(Tp *base, uint32_t
 #else
 #define LTS(i) do { } while (0)
 #endif
-template <int T>
+// ROBUST (launched when either edge kind has a robust kernel): the same pass with every edge's information scaled by rho'(s) and
+// chi2 = sum of rho(s); no extra load, no extra store, the same order of every sum.  The plain instances are the default and are
+// compiled exactly as before (profiles/robust_linearize_resource_usage.txt).
+template <int T, bool ROBUST = false>
 __global__ void __launch_bounds__(256, LIN_WAVES_PER_SIMD) k_linearize_ell(DevGraph d) {
     constexpr int PW = 64 / T;
     __shared__ double s_lc[4][5][LIN_R * 64];       // 40 KB per block = 4 blocks per CU in the 160 KB LDS: 4 waves per SIMD
@@ -655,7 +688,7 @@ __global__ void __launch_bounds__(256, LIN_WAVES_PER_SIMD) k_linearize_ell(DevGr
             if (e.l[j] >= 0) {
                 const uint32_t o = off8 + (uint32_t)i * plane8;
                 PlQuad q;
-                quad_pl(px, py, cs, sn, lx[j], ly[j], e.zx[j], e.zy[j], e.w00[j], e.w01[j], e.w11[j], q);
+                quad_pl<ROBUST>(px, py, cs, sn, lx[j], ly[j], e.zx[j], e.zy[j], e.w00[j], e.w01[j], e.w11[j], q, d.rk_pl, d.rd_pl);
                 if (!(fp && fl[j])) chi += q.chi;
                 const bool both = !fp && !fl[j];
 #if !(LIN_ABL & 4)
@@ -679,8 +712,8 @@ __global__ void __launch_bounds__(256, LIN_WAVES_PER_SIMD) k_linearize_ell(DevGr
     LTS(3);
     // ---- odometry incidences: lane h takes incidences q0+h, q0+h+T, ... of its pose
 #if !(LIN_ABL & 1)
-    if (q0 + h < q1) chi += pp_incidence_rec<true>(d, inc0, p, H, b, true, cs, sn);
-    for (int q = q0 + h + T; q < q1; q += T) chi += pp_incidence_q<true>(d, q, p, H, b, true, cs, sn);
+    if (q0 + h < q1) chi += pp_incidence_rec<true, ROBUST>(d, inc0, p, H, b, true, cs, sn);
+    for (int q = q0 + h + T; q < q1; q += T) chi += pp_incidence_q<true, ROBUST>(d, q, p, H, b, true, cs, sn);
 #endif
     LTS(4);
     // ---- pose sums: xor-shuffle over the T lanes of the pose, then each lane stores its share of the 9 components
@@ -758,10 +791,16 @@ __global__ void __launch_bounds__(256) k_reduce_chi2(DevGraph d, int n_partial) 
     if (threadIdx.x == 0) d.chi2[0] = tot;
 }
 
+static inline bool robust_on(const DevGraph &d) { return d.rk_pp != 0 || d.rk_pl != 0; }
 void launch_linearize_gather(const DevGraph &d, hipStream_t st) {
     const int gp = (d.N + 255) / 256, gl = (d.M + 255) / 256;
+    if (robust_on(d)) {
+        if (gp > 0) hipLaunchKernelGGL((k_linearize_pose_gather<true, true>), dim3(gp), dim3(256), 0, st, d);
+        if (gl > 0) hipLaunchKernelGGL(k_linearize_lm_gather<true>, dim3(gl), dim3(256), 0, st, d);
+    } else {
     if (gp > 0) hipLaunchKernelGGL(k_linearize_pose_gather<true>, dim3(gp), dim3(256), 0, st, d);
-    if (gl > 0) hipLaunchKernelGGL(k_linearize_lm_gather, dim3(gl), dim3(256), 0, st, d);
+    if (gl > 0) hipLaunchKernelGGL(k_linearize_lm_gather<false>, dim3(gl), dim3(256), 0, st, d);
+    }
     hipLaunchKernelGGL(k_reduce_chi2, dim3(1), dim3(256), 0, st, d, gp);
 }
 // materialise H_ll, b_l and the chi2 total from the fused kernel's partials (export / chi2 queries only: inside an
@@ -775,10 +814,20 @@ void launch_linearize_finalize(const DevGraph &d, hipStream_t st, bool with_chi2
 // start / stop (optional): HIP events attached to THIS dispatch (hipExtLaunchKernelGGL) — the kernel's own begin and end as the
 // command processor stamps them, what a kernel trace reports; an event recorded before / after the launch also holds the
 // hand-over from the previous kernel of the stream
+template <int T> static void launch_ell_robust(const DevGraph &d, dim3 grid, dim3 block, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
+    if (!start && !stop) hipLaunchKernelGGL((k_linearize_ell<T, true>), grid, block, 0, st, d);
+    else hipExtLaunchKernelGGL((k_linearize_ell<T, true>), grid, block, 0, st, start, stop, 0, d);
+}
 void launch_linearize(const DevGraph &d, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
     if (d.n_wtiles <= 0) { launch_linearize_gather(d, st); return; }
     if (d.wt_hi <= d.wt_lo) return;
     const dim3 grid((d.wt_hi - d.wt_lo + 3) / 4), block(256);
+    if (robust_on(d)) { switch (d.ell_T) {
+        case 1: launch_ell_robust<1>(d, grid, block, st, start, stop); break;
+        case 2: launch_ell_robust<2>(d, grid, block, st, start, stop); break;
+        case 4: launch_ell_robust<4>(d, grid, block, st, start, stop); break;
+        default: launch_ell_robust<8>(d, grid, block, st, start, stop); break; }
+        return; }
     // (without events: the plain launch — the kernel trace of a lap-sized optimize(10) shows 3 us between k_update and a linearisation
     // dispatched through hipExtLaunchKernelGGL and none in front of the plainly launched kernels, scripts/r4_g.sh)
     if (!start && !stop) { switch (d.ell_T) {
@@ -805,6 +854,7 @@ void launch_linearize(const DevGraph &d, hipStream_t st, hipEvent_t start, hipEv
 //   3. thread 0 walks the tail odometry edges in order: the new pose's share into the LDS accumulators, the older end's share into
 //      its accumulator (a tail pose) or, read-modify-write, into the old pose's H_pp / b entries; off-diagonal blocks to the tail arena;
 //   4. the tail poses' diagonal blocks and rhs out; chi2 of the tail (edges in order) as one more partial for k_update.
+template <bool ROBUST = false>
 __global__ void __launch_bounds__(256) k_linearize_tail(DevGraph d) {
     constexpr int EC = 512, PC = 16;                                 // == gs::TAIL_PL, gs::TAIL_POSES (launch_linearize_tail checks)
     __shared__ double s_p[9][EC], s_l[5][EC], s_chi[EC], s_acc[PC][9];
@@ -813,8 +863,8 @@ __global__ void __launch_bounds__(256) k_linearize_tail(DevGraph d) {
         const int p = d.t_pl[2 * e], l = d.t_pl[2 * e + 1];
         const double2 cs = reinterpret_cast<const double2 *>(d.pose_cs)[p];
         PlQuad q;
-        quad_pl(d.pose_est[3 * p], d.pose_est[3 * p + 1], cs.x, cs.y, d.lm_est[2 * l], d.lm_est[2 * l + 1], d.t_pl_z[2 * e], d.t_pl_z[2 * e + 1],
-                d.t_pl_w[3 * e], d.t_pl_w[3 * e + 1], d.t_pl_w[3 * e + 2], q);
+        quad_pl<ROBUST>(d.pose_est[3 * p], d.pose_est[3 * p + 1], cs.x, cs.y, d.lm_est[2 * l], d.lm_est[2 * l + 1], d.t_pl_z[2 * e], d.t_pl_z[2 * e + 1],
+                        d.t_pl_w[3 * e], d.t_pl_w[3 * e + 1], d.t_pl_w[3 * e + 2], q, d.rk_pl, d.rd_pl);
         const bool fl = d.lm_fixed[l];
 #pragma unroll
         for (int k = 0; k < 6; ++k) { s_p[k][e] = q.Hp[k]; d.t_Hpl[(int64_t)k * d.tcapEpl + e] = fl ? 0.0 : q.W6[k]; }
@@ -858,8 +908,8 @@ __global__ void __launch_bounds__(256) k_linearize_tail(DevGraph d) {
             const double2 ci = reinterpret_cast<const double2 *>(d.pose_cs)[i];
             const bool fi = d.pose_fixed[i], fj = d.pose_fixed[j];
             double Hi[6] = {0, 0, 0, 0, 0, 0}, bi[3] = {0, 0, 0}, Hj[6] = {0, 0, 0, 0, 0, 0}, bj[3] = {0, 0, 0};
-            chi += pp_incidence<true>(d, (int)k, 0, xi, xj, ci.x, ci.y, z5, w, fi, fj, Hi, bi, d.t_Hpp_off + kk, d.tcapEpp);
-            pp_incidence<true>(d, (int)k, 1, xi, xj, ci.x, ci.y, z5, w, fi, fj, Hj, bj);
+            chi += pp_incidence<true, ROBUST>(d, (int)k, 0, xi, xj, ci.x, ci.y, z5, w, fi, fj, Hi, bi, d.t_Hpp_off + kk, d.tcapEpp);
+            pp_incidence<true, ROBUST>(d, (int)k, 1, xi, xj, ci.x, ci.y, z5, w, fi, fj, Hj, bj);
             auto share = [&](int v, const double *H, const double *b) {   // endpoint v's share of the edge
                 if (d.pose_fixed[v]) return;
                 if (v >= d.N) {
@@ -886,13 +936,51 @@ __global__ void __launch_bounds__(256) k_linearize_tail(DevGraph d) {
     }
 }
 void launch_linearize_tail(const DevGraph &d, hipStream_t st) {
-    if (d.tN > 0 && d.tcapEpl <= 512 && d.tcapN <= 16) hipLaunchKernelGGL(k_linearize_tail, dim3(1), dim3(256), 0, st, d);
+    if (!(d.tN > 0 && d.tcapEpl <= 512 && d.tcapN <= 16)) return;
+    if (robust_on(d)) hipLaunchKernelGGL(k_linearize_tail<true>, dim3(1), dim3(256), 0, st, d);
+    else hipLaunchKernelGGL(k_linearize_tail<false>, dim3(1), dim3(256), 0, st, d);
 }
 void launch_chi2_only(const DevGraph &d, hipStream_t st) {
     if (d.tN > 0 && d.n_wtiles > 0) { launch_linearize(d, st); launch_linearize_tail(d, st); launch_linearize_finalize(d, st); return; }   // a grown plan: the full pass (the gather kernels do not know the tail)
     const int gp = (d.N + 255) / 256;
-    if (gp > 0) hipLaunchKernelGGL(k_linearize_pose_gather<false>, dim3(gp), dim3(256), 0, st, d);
+    if (gp > 0 && robust_on(d)) hipLaunchKernelGGL((k_linearize_pose_gather<false, true>), dim3(gp), dim3(256), 0, st, d);
+    else if (gp > 0) hipLaunchKernelGGL(k_linearize_pose_gather<false>, dim3(gp), dim3(256), 0, st, d);
     hipLaunchKernelGGL(k_reduce_chi2, dim3(1), dim3(256), 0, st, d, gp);
+}
+// ---- gs_get_edge_chi2: s = e^T W e of every edge of one kind at the current estimates and the weight rho'(s) of the kind's kernel.
+// A thread per edge, insertion order (the host hands the per-edge index table over: gs_device.hpp); s comes out of the SAME
+// quad_pl / pp_incidence expressions the linearisation evaluates, with the poses' cached cos / sin.  Fixed endpoints do not matter here.
+__global__ void __launch_bounds__(256) k_edge_chi2(DevGraph d, int kind, int n, const int32_t *__restrict__ tab, double *__restrict__ out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    double s, w;
+    if (kind == 0) {
+        const int i = tab[2 * k], j = tab[2 * k + 1];
+        double xi[3], xj[3], z5[5], wi[6], H[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { xi[c] = d.pose_est[3 * i + c]; xj[c] = d.pose_est[3 * j + c]; }
+#pragma unroll
+        for (int c = 0; c < 5; ++c) z5[c] = d.pp_zinv[5 * (int64_t)k + c];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) wi[c] = d.pp_info[6 * (int64_t)k + c];
+        const double2 ci = reinterpret_cast<const double2 *>(d.pose_cs)[i];
+        s = pp_incidence<false>(d, k, 0, xi, xj, ci.x, ci.y, z5, wi, false, false, H, b);
+        robust_rho(d.rk_pp, d.rd_pp, s, w);
+    } else {
+        const int p = tab[3 * k], l = tab[3 * k + 1], src = tab[3 * k + 2];
+        double zx, zy, w00, w01, w11;
+        if (src >= 0) { const int64_t L = d.ell_len; zx = d.ell_z[src]; zy = d.ell_z[L + src]; w00 = d.ell_w[src]; w01 = d.ell_w[L + src]; w11 = d.ell_w[2 * L + src]; }
+        else { const int e = -(src + 1); zx = d.t_pl_z[2 * e]; zy = d.t_pl_z[2 * e + 1]; w00 = d.t_pl_w[3 * e]; w01 = d.t_pl_w[3 * e + 1]; w11 = d.t_pl_w[3 * e + 2]; }
+        const double2 cs = reinterpret_cast<const double2 *>(d.pose_cs)[p];
+        PlQuad q;
+        quad_pl(d.pose_est[3 * p], d.pose_est[3 * p + 1], cs.x, cs.y, d.lm_est[2 * l], d.lm_est[2 * l + 1], zx, zy, w00, w01, w11, q);
+        s = q.chi;
+        robust_rho(d.rk_pl, d.rd_pl, s, w);
+    }
+    out[k] = s; out[(int64_t)n + k] = w;
+}
+void launch_edge_chi2(const DevGraph &d, int kind, int n, const int32_t *tab, double *out, hipStream_t st) {
+    if (n > 0) hipLaunchKernelGGL(k_edge_chi2, dim3((n + 255) / 256), dim3(256), 0, st, d, kind, n, tab, out);
 }
 
 // ------------------------------------------------------------------ A8 factorisation
