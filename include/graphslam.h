@@ -197,7 +197,7 @@ int  gs_get_landmarks(gs_graph *g, int32_t capacity, int32_t *out_ids, double *o
  *      + g2o BlockSolver::buildStructure: index maps, ordering, symbolic plan, upload to HBM.
  * gs_optimize                <- m_optimizer.optimize(10)                          (src/slam.cpp:481)
  *      runs `iterations` x (computeActiveErrors, buildSystem, solve, update) on the device,
- *      no damping, no line search, no convergence test; returns iterations done.
+ *      no damping, no line search, no convergence test; returns iterations done (damped: gs_optimize_lm, below).
  *      Failure semantics are g2o's: when the factorisation of an iteration fails, that iteration's
  *      update and all later ones are NOT applied — the estimates stay at the last good iterate —
  *      and the call returns 0 (stats->iterations = updates applied, stats->numeric_failure = code).
@@ -227,6 +227,59 @@ int  gs_stream_synchronize(gs_graph *g);
 /* computeActiveErrors + activeChi2 at the current estimates (device); with a robust kernel set: activeRobustChi2, the sum of rho(s) */
 int  gs_chi2(gs_graph *g, double *out_chi2);
 int  gs_get_stats(gs_graph *g, gs_stats *stats);      /* plan statistics after initialize */
+
+/* ---- Levenberg-Marquardt ------------------------------------------------------
+ * gs_optimize_lm <- g2o OptimizationAlgorithmLevenberg, the one-line swap at the reference's call site (src/slam.cpp:61 constructs
+ * OptimizationAlgorithmGaussNewton).  g2o is not part of this project's checkers: the rule is restated from g2o's published text and is
+ * not pinned against a g2o build.  State lambda, nu (2 at the start).  Per iteration, at the accepted estimates x:
+ *   1. chi_old = chi2(x) (with a robust kernel set: the sum of rho(s), as everywhere else); H and b linearised at x.
+ *   2. first iteration, no lambda given: lambda = tau * max_j |H_jj| over the free scalars.
+ *   3. trials, at most max_trials_after_failure: solve (H + lambda I) D = b — lambda added to EVERY free diagonal scalar (g2o setLambda),
+ *      not Marquardt's scaling —; x_try = x [+] D (the update of gs_iterate, angle normalisation included); chi_new = chi2(x_try);
+ *      scale = sum_j D_j (lambda D_j + b_j) + 1e-3; rho = (chi_old - chi_new) / scale.
+ *      rho > 0 and chi_new finite: ACCEPT, lambda *= max(1/3, min(1 - (2 rho - 1)^3, 2/3)), nu = 2, next iteration.
+ *      otherwise REJECT: x is put back bit for bit, lambda *= nu, nu *= 2, next trial.  A zero pivot in a trial's factorisation is a
+ *      rejected trial (g2o sets rho = -1), not the end of the call.
+ *   4. every trial of an iteration rejected: the call ends ("terminate"), the estimates are the last accepted ones.
+ * The whole call runs on the handle's stream with no host decision inside a trial: a trial is the launch sequence of gs_iterate with
+ * five more launches around it — damp + base copy of the estimates, scale, the chi2 pass (two launches: per-pose sums, total) and step;
+ * a max-diagonal kernel once per call when no lambda is given —; lambda, nu, the counters and the verdict live in a device record the
+ * host reads between chunks of trials.  A retrial linearises again at the restored estimates.
+ * Returns the number of ACCEPTED iterations (like gs_optimize: the updates that stayed); a call that ends by "terminate" returns the
+ * count so far with info->terminated = 1 — not an error.  A flag timeout of a whole-tree launch is repaired by the per-level fallback
+ * as in gs_optimize.  gs_stats: chi2_initial / chi2_final are the values at the first / last accepted point, iterations the accepted
+ * count.  Works with robust kernels, grown plans, factor_variant 3 and 4, workgroup fronts, both linearisation paths; makes the
+ * marginals stale like an iteration; leaves no failure, stop or LM state behind that gates a later gs_iterate / gs_optimize.
+ * gs_export_system afterwards returns the system of the LAST TRIAL AS IT WAS FACTORISED: H at that trial's starting point with its
+ * lambda on the free diagonal scalars (b and the off-diagonal blocks undamped).
+ * Errors: iterations < 0, a tau or initial_lambda that is not finite, tau <= 0, max_trials_after_failure < 1: GS_ERR_INVALID;
+ * a host-only handle GS_ERR_NO_DEVICE.  A solver failure the step control cannot turn into a rejected trial ends the call with an
+ * error code, NOT with gs_optimize's "return 0" (0 is a regular result here: no trial accepted): GS_ERR_TIMEOUT when a front's flag
+ * did not arrive with one launch per level either, GS_ERR_NUMERIC for any other failure code; the estimates are the last accepted
+ * ones, stats and info are filled (stats->numeric_failure = the code), and the handle is clean for the next call.
+ * NOT DONE: pose-window shards (a handle configured with gs_dist_configure(world > 1) returns GS_ERR_INVALID); Marquardt's diagonal
+ * scaling, dogleg; a convergence stop rule other than "terminate"; the Slam mirror keeps calling gs_optimize. */
+typedef struct gs_lm_params {
+    int32_t struct_size;                /* sizeof(gs_lm_params), for ABI evolution                           */
+    int32_t max_trials_after_failure;   /* 10 (g2o's default)                                                */
+    double  initial_lambda;             /* <= 0 (default): tau * max_j |H_jj| at the first linearisation      */
+    double  tau;                        /* 1e-5 (g2o's default)                                              */
+} gs_lm_params;
+typedef struct gs_lm_info {
+    int32_t struct_size;
+    int32_t iterations;                 /* accepted                                                          */
+    int32_t trials, rejected;           /* trials run, trials rejected                                       */
+    int32_t terminated;                 /* 1: an iteration used up its trials without an accepted step       */
+    int32_t reserved;
+    double  lambda_initial, lambda_final;   /* of the first trial; the one a next trial would have used     */
+    /* per ITERATION (the first 64): chi2 at the accepted point the iteration started from, lambda of its accepted (or last) trial,
+       its number of trials.  A call that terminates has one more entry than accepted iterations. */
+    double  chi2[64], lambda[64];
+    int32_t n_trials[64];
+} gs_lm_info;
+int  gs_lm_params_default(gs_lm_params *p);
+int  gs_optimize_lm(gs_graph *g, int32_t iterations, const gs_lm_params *p /* NULL: defaults */,
+                    gs_stats *stats /* may be NULL */, gs_lm_info *info /* may be NULL */);
 
 /* ---- robust kernels ---------------------------------------------------------
  * <- g2o OptimizableGraph::Edge::setRobustKernel with RobustKernelHuber / RobustKernelCauchy (the reference never sets one; the

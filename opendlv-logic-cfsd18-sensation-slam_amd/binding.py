@@ -98,6 +98,25 @@ class MarginalsInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LmParams(C.Structure):
+    """gs_lm_params (include/graphslam.h)"""
+    _fields_ = [("struct_size", C.c_int32), ("max_trials_after_failure", C.c_int32), ("initial_lambda", C.c_double), ("tau", C.c_double)]
+
+
+class LmInfo(C.Structure):
+    """gs_lm_info: counters of a gs_optimize_lm call and its per-iteration history (the first 64 iterations)"""
+    _fields_ = [("struct_size", C.c_int32), ("iterations", C.c_int32), ("trials", C.c_int32), ("rejected", C.c_int32),
+                ("terminated", C.c_int32), ("reserved", C.c_int32), ("lambda_initial", C.c_double), ("lambda_final", C.c_double),
+                ("chi2", C.c_double * 64), ("lambda_", C.c_double * 64), ("n_trials", C.c_int32 * 64)]
+
+    def as_dict(self):
+        """scalars as they are; the histories as arrays cut to the iterations that ran (one more than accepted after a terminate)"""
+        n = min(self.iterations + (1 if self.terminated else 0), 64)
+        o = {k: getattr(self, k) for k in ("iterations", "trials", "rejected", "terminated", "lambda_initial", "lambda_final")}
+        o["chi2"] = np.array(self.chi2[:n]); o["lambda"] = np.array(self.lambda_[:n]); o["n_trials"] = np.array(self.n_trials[:n], dtype=np.int32)
+        return o
+
+
 def declared_symbols(debug=True):
     """Every function name include/graphslam.h (and, debug=True, include/graphslam_debug.h) declares."""
     names = set()
@@ -231,6 +250,9 @@ def lib():
         L.gs_set_robust_kernel.argtypes = [vp, C.c_int32, C.c_int32, C.c_double]
         L.gs_get_robust_kernel.argtypes = [vp, C.c_int32, _ip, _dp]
         L.gs_get_edge_chi2.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp]
+    if hasattr(L, "gs_optimize_lm"):                       # (a tuning build of an older tree loaded through GS_LIB may predate Levenberg-Marquardt)
+        L.gs_lm_params_default.argtypes = [C.POINTER(LmParams)]
+        L.gs_optimize_lm.argtypes = [vp, C.c_int32, C.POINTER(LmParams), C.POINTER(Stats), C.POINTER(LmInfo)]
     L.gs_slam_get_send_pose.argtypes = [vp, _dp]
     L.gs_slam_collect_direction.argtypes = [vp, C.c_uint32, C.c_double, C.c_double]
     L.gs_slam_collect_distance.argtypes = [vp, C.c_uint32, C.c_double]
@@ -334,6 +356,21 @@ def dist_unique_id():
     if rc < 0:
         raise GsError(rc, (lib().gs_last_error() or b"").decode())
     return buf.raw
+
+
+def lm_params(**kw):
+    """gs_lm_params_default with the named fields replaced (max_trials: short for max_trials_after_failure)"""
+    p = LmParams()
+    rc = lib().gs_lm_params_default(C.byref(p))
+    if rc < 0:
+        raise GsError(rc, (lib().gs_last_error() or b"").decode())
+    if "max_trials" in kw:
+        kw["max_trials_after_failure"] = kw.pop("max_trials")
+    for k, v in kw.items():
+        if k not in ("max_trials_after_failure", "initial_lambda", "tau"):
+            raise AttributeError("gs_lm_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
 
 
 def device_count():
@@ -470,6 +507,15 @@ class Graph:
         st = Stats(); st.struct_size = C.sizeof(Stats)
         done = self._check(self.L.gs_optimize_until(self.h, int(max_iterations), float(rel_chi2_tol), C.byref(st)))
         return done, st
+
+    def optimize_lm(self, iterations=10, **params):
+        """gs_optimize_lm (Levenberg-Marquardt, g2o's rule): params = fields of gs_lm_params (max_trials_after_failure or max_trials,
+        initial_lambda, tau); returns (accepted iterations, Stats, gs_lm_info as a dict)"""
+        p = lm_params(**params)
+        st = Stats(); st.struct_size = C.sizeof(Stats)
+        info = LmInfo(); info.struct_size = C.sizeof(LmInfo)
+        done = self._check(self.L.gs_optimize_lm(self.h, int(iterations), C.byref(p), C.byref(st), C.byref(info)))
+        return done, st, info.as_dict()
 
     def debug_fail_at_iteration(self, k, code=1):
         self._check(self.L.gs_debug_fail_at_iteration(self.h, int(k), int(code)))

@@ -228,6 +228,7 @@ extern "C" int gs_destroy(gs_graph *g) {
     hipSetDevice(g->device);
     hipStreamSynchronize(g->stream);
     dev_free_all(g);
+    if (g->lm.mem) hipFree(g->lm.mem);
     gs_dist_comm_release(g);
     gs_frontend_release(g);
     for (auto &e : g->ev) hipEventDestroy(e);
@@ -1430,6 +1431,130 @@ extern "C" int gs_optimize(gs_graph *g, int32_t iterations, gs_stats *stats) { r
 extern "C" int gs_optimize_until(gs_graph *g, int32_t max_iterations, double rel_chi2_tol, gs_stats *stats) {
     if (!(rel_chi2_tol >= 0.0)) return fail(GS_ERR_INVALID, "rel_chi2_tol must be >= 0");
     return optimize_impl(g, max_iterations, rel_chi2_tol, stats);
+}
+
+// ------------------------------------------------------------------ Levenberg-Marquardt (gs_lm.hpp: trial sequence, device record)
+extern "C" int gs_lm_params_default(gs_lm_params *p) {
+    if (!p) return fail(GS_ERR_INVALID, "null params");
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(*p); p->max_trials_after_failure = 10; p->initial_lambda = 0.0; p->tau = 1e-5;
+    return GS_OK;
+}
+// the handle's LM buffers: one allocation of its own (not pool memory: it outlives the plans), grow-only
+static int lm_reserve(gs_graph *g) {
+    auto &W = g->lm; const size_t NP = (size_t)(g->d.N + g->d.tN), ML = (size_t)(g->d.M + g->d.tM);
+    const size_t np = (size_t)lm_grid(g->d);
+    if (!W.mem || NP > W.cap_p || ML > W.cap_l) {
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        if (W.mem) { hipFree(W.mem); W.mem = nullptr; }
+        const size_t cp = NP + 64, cl = ML + 64, cpart = (cp + cl + 255) / 256 + 1;
+        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t o_state = 0, o_hc = al(2 * sizeof(LmState)), o_hl = o_hc + al(64 * 8), o_ht = o_hl + al(64 * 8), o_bp = o_ht + al(64 * 4),
+                     o_bc = o_bp + al(cp * 24), o_bl = o_bc + al(cp * 16), o_part = o_bl + al(cl * 16), total = o_part + al(cpart * 8);
+        HIP_TRY(hipMalloc(&W.mem, total));
+        char *b = (char *)W.mem;
+        W.dev.state = (LmState *)(b + o_state); W.dev.hist_chi2 = (double *)(b + o_hc); W.dev.hist_lambda = (double *)(b + o_hl); W.dev.hist_trials = (int32_t *)(b + o_ht);
+        W.dev.base_pose = (double *)(b + o_bp); W.dev.base_cs = (double *)(b + o_bc); W.dev.base_lm = (double *)(b + o_bl); W.dev.part = (double *)(b + o_part);
+        W.cap_p = cp; W.cap_l = cl; }
+    W.dev.n_part = (int32_t)np;
+    return GS_OK;
+}
+// one trial, asynchronous: today's linearise / factor / back-solve / update launches in today's launch modes, with the LM kernels around them
+static void enqueue_lm_trial(gs_graph *g, int par, bool init) {
+    const LmDev &lm = g->lm.dev;
+    ++g->d.iter;
+    launch_linearize(g->d, g->stream);
+    launch_linearize_tail(g->d, g->stream);
+    if (init) launch_lm_maxdiag(g->d, lm, g->stream);
+    launch_lm_damp(g->d, lm, par, init ? 1 : 0, g->stream);
+    enqueue_factor_levels(g, g->own, 0, 0);
+    enqueue_finish(g, false);                                        // (no shared top on a single device), back-solve, update
+    launch_lm_scale(g->d, lm, par, g->stream);
+    launch_chi2_only(g->d, g->stream);                               // chi2 at x_try -> chi2[0]
+    launch_lm_step(g->d, lm, par, g->stream);
+}
+extern "C" int gs_optimize_lm(gs_graph *g, int32_t iterations, const gs_lm_params *params, gs_stats *stats, gs_lm_info *info) {
+    if (!g) return fail(GS_ERR_INVALID, "null graph");
+    if (iterations < 0) return fail(GS_ERR_INVALID, "negative iteration count");
+    gs_lm_params P; gs_lm_params_default(&P);
+    if (params) { std::memcpy(&P, params, std::min<size_t>(sizeof(P), (size_t)std::max(params->struct_size, 0))); P.struct_size = (int32_t)sizeof(P); }
+    if (!std::isfinite(P.tau) || !(P.tau > 0.0)) return fail(GS_ERR_INVALID, "gs_lm_params.tau must be finite and > 0");
+    if (!std::isfinite(P.initial_lambda)) return fail(GS_ERR_INVALID, "gs_lm_params.initial_lambda must be finite (<= 0: tau * max diag(H))");
+    if (P.max_trials_after_failure < 1) return fail(GS_ERR_INVALID, "gs_lm_params.max_trials_after_failure must be >= 1");
+    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: Levenberg-Marquardt is not supported on sharded handles");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    rc = ensure_ready(g); if (rc != GS_OK) return rc;
+    if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: Levenberg-Marquardt is not supported on sharded handles");
+    rc = lm_reserve(g); if (rc != GS_OK) return rc;
+    if (g->fell_back && iterations > 0 && g->opt.tree != 0 && !g->d.tree && ++g->fallback_calls >= g->fallback_retry_after) {      // as gs_optimize: try the whole-tree launches again
+        g->d.tree = 1; g->tree_proven = false; g->fallback_calls = 0; g->fallback_retrying = true; }
+    { const int ii = g->d.inject_iter, ic = g->d.inject_code;       // an armed fault injection survives the reset
+      HIP_TRY(hipMemsetAsync(g->d.fail, 0, 4 * sizeof(int32_t), g->stream)); g->d.inject_iter = ii; g->d.inject_code = ic; }
+    g->d.conv_tol = -1.0; g->d.hist_slot = -1;
+    LmState *H = g->lm.host; std::memset(H, 0, 2 * sizeof(LmState));
+    LmState &S0 = H[0];
+    S0.lambda = P.initial_lambda > 0.0 ? P.initial_lambda : 0.0; S0.lambda_initial = S0.lambda; S0.nu = 2.0; S0.tau = P.tau;
+    S0.budget = iterations; S0.max_trials = P.max_trials_after_failure; S0.need_lambda = P.initial_lambda > 0.0 ? 0 : 1;
+    HIP_TRY(hipMemcpyAsync(g->lm.dev.state, H, 2 * sizeof(LmState), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemsetAsync(g->lm.dev.hist_chi2, 0, 64 * sizeof(double), g->stream));
+    HIP_TRY(hipMemsetAsync(g->lm.dev.hist_lambda, 0, 64 * sizeof(double), g->stream));
+    HIP_TRY(hipMemsetAsync(g->lm.dev.hist_trials, 0, 64 * sizeof(int32_t), g->stream));
+    hipEventRecord(g->ev[5], g->stream);
+    // Chunks of trials, the device record read in between (one host round trip per chunk).  Never more trials than iterations still
+    // to accept — each needs one at least —, so the only trials that run as no-ops are the ones enqueued behind a "terminate"; the first
+    // trial alone until a whole-tree launch of this plan has come back clean, as in gs_optimize.
+    LmState S = S0; int seq = 0, first_failure = 0; int32_t ff[4] = {0, 0, 0, 0}; bool fell_back = false;
+    while (iterations > 0 && !S.done && S.iterations < iterations) {
+        const bool alone = S.trials == 0 && !(g->tree_proven && g->d.tree);
+        const int n = alone ? 1 : std::min(iterations - S.iterations, 8);
+        for (int k = 0; k < n; ++k, ++seq) enqueue_lm_trial(g, seq & 1, k == 0 && S.trials == 0 && S.need_lambda != 0);
+        if (g->enqueue_rc != GS_OK) { hipStreamSynchronize(g->stream); reset_failure(g); return take_enqueue_error(g); }
+        HIP_TRY(hipMemcpyAsync(ff, g->d.fail, sizeof(ff), hipMemcpyDeviceToHost, g->stream));
+        HIP_TRY(hipMemcpyAsync(&H[1], g->lm.dev.state + (seq & 1), sizeof(LmState), hipMemcpyDeviceToHost, g->stream));
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        S = H[1];
+        if (ff[0] == 0 && g->d.tree) { g->tree_proven = true;
+            if (g->fallback_retrying) { g->fallback_retrying = false; g->fell_back = false; g->fallback_retry_after = 4; } }
+        if (ff[0] != 0 && first_failure == 0) first_failure = ff[0];
+        if (ff[0] == 2 && g->d.tree && !fell_back) {                // the trials behind the timeout were no-ops: run them again, one launch per level
+            fall_back_to_levels(g);
+            fell_back = true; g->d.inject_iter = 0;
+            HIP_TRY(hipMemsetAsync(g->d.fail, 0, sizeof(int32_t), g->stream));
+            ff[0] = 0; continue; }
+        if (ff[0] != 0) break;
+    }
+    HIP_TRY(hipMemsetAsync(g->d.fail + 1, 0, 2 * sizeof(int32_t), g->stream));     // the update count and the stop flag must not gate later gs_iterate calls
+    if (S.trials == 0 && (stats || info || g->cfg.verbose)) launch_chi2_only(g->d, g->stream);     // nothing ran: chi2 at the estimates as they are
+    hipEventRecord(g->ev[6], g->stream);
+    double chi_here = 0.0, hc[64], hl[64]; int32_t ht[64];
+    HIP_TRY(hipMemcpyAsync(&chi_here, g->d.chi2, sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(hc, g->lm.dev.hist_chi2, sizeof(hc), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(hl, g->lm.dev.hist_lambda, sizeof(hl), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(ht, g->lm.dev.hist_trials, sizeof(ht), hipMemcpyDeviceToHost, g->stream));
+    const bool pull = g->dev_valid && g->dev_estimates_newer;
+    if (pull) { const size_t Np = (size_t)(g->d.N + g->d.tN), Mp = (size_t)(g->d.M + g->d.tM);
+        if (Np) HIP_TRY(hipMemcpyAsync(g->h.pose_est.data(), g->d.pose_est, Np * 3 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+        if (Mp) HIP_TRY(hipMemcpyAsync(g->h.lm_est.data(), g->d.lm_est, Mp * 2 * sizeof(double), hipMemcpyDeviceToHost, g->stream)); }
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    if (pull) g->dev_estimates_newer = false;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { reset_failure(g); return fail(GS_ERR_HIP, std::string("LM iteration: ") + hipGetErrorString(e)); }
+    float ms = 0; hipEventElapsedTime(&ms, g->ev[5], g->ev[6]);
+    const double chi_first = S.trials > 0 ? hc[0] : chi_here, chi_last = S.trials > 0 ? S.chi_base : chi_here;
+    if (g->cfg.verbose) for (int it = 0; it < std::min(S.iterations, 64); ++it)
+        std::fprintf(stderr, "iteration= %d\t chi2= %.6f\t edges= %d\t schur= 0\t lambda= %.6g\t levenbergIter= %d\n", it,
+                     it + 1 < S.iterations && it + 1 < 64 ? hc[it + 1] : chi_last, g->h.n_pp() + g->h.n_pl(), hl[it], ht[it]);
+    if (stats) { std::memset(stats, 0, sizeof(*stats)); stats->struct_size = (int32_t)sizeof(*stats);
+        fill_plan_stats(g, stats); stats->iterations = S.iterations; stats->numeric_failure = ff[0]; stats->first_failure = first_failure;
+        stats->chi2_initial = chi_first; stats->chi2_final = chi_last; stats->ms_total = ms; }
+    if (info) { std::memset(info, 0, sizeof(*info)); info->struct_size = (int32_t)sizeof(*info);
+        info->iterations = S.iterations; info->trials = S.trials; info->rejected = S.rejected; info->terminated = S.terminated;
+        info->lambda_initial = S.lambda_initial; info->lambda_final = S.lambda;
+        std::memcpy(info->chi2, hc, sizeof(hc)); std::memcpy(info->lambda, hl, sizeof(hl)); std::memcpy(info->n_trials, ht, sizeof(ht)); }
+    if (ff[0]) { rc = reset_failure(g); if (rc != GS_OK) return rc;
+        if (ff[0] == 2) return fail(GS_ERR_TIMEOUT, "a front's completion flag did not arrive in time, with one launch per level as well (estimates = last accepted point)");
+        return fail(GS_ERR_NUMERIC, "a solver failure the step control could not treat as a rejected trial (estimates = last accepted point)"); }
+    return S.iterations;
 }
 
 extern "C" int gs_chi2(gs_graph *g, double *out) {

@@ -10,6 +10,7 @@
 #include "../../include/graphslam_debug.h"
 #include "gs_device.hpp"
 #include "gs_host.hpp"
+#include "gs_lm.hpp"
 
 struct gs_graph {
     // launch parameters of one list of fronts grouped by level
@@ -97,6 +98,9 @@ struct gs_graph {
         bool valid = false; uint64_t structure_version = 0, estimate_version = 0; int32_t iter = 0;
         std::vector<double> out;
     } marg;
+    // gs_optimize_lm: the device state record, history, base copy of the estimates and reduction partials (gs_lm.hpp) — one allocation of
+    // the handle's own, grow-only, sized for cap_p poses / cap_l landmarks (tail included)
+    struct Lm { gs::LmDev dev{}; void *mem = nullptr; size_t cap_p = 0, cap_l = 0; gs::LmState host[2]{}; } lm;
 };
 
 namespace gs {

@@ -1,0 +1,201 @@
+// gs_lm.hip — the kernels gs_optimize_lm adds around the Gauss-Newton launches (gfx950, wave64).  See gs_lm.hpp for the trial
+// sequence and the double-buffered state record.  A translation unit of its own: the kernels of gs_kernels.hip are not touched,
+// not re-instantiated, and DevGraph is what it was.
+//
+// All four kernels are vertex-parallel with the same geometry: thread v < NP = N + tN is pose v (a grown plan's tail poses follow
+// the base ones in every per-pose array), thread NP + l is landmark l < ML = M + tM; 256 threads per workgroup, lm_grid()
+// workgroups.  Every sum is two-stage in a fixed order — lanes by shuffle, waves in wave order, then the workgroups' partials in
+// index order — so no value depends on the solver's launch mode.  One writer per address, no atomics.
+//
+// Where lambda goes (wherever the front assembly reads the diagonal scalar from):
+//   free pose p < N          Hpp_diag planes xx, yy, tt (0, 3, 5)
+//   free tail pose           t_Hpp_diag, the same planes with stride tcapN
+//   free landmark l < M      gather path: Hll_diag planes 00, 11 (0, 2); fused path: entries 0 and 2 of the landmark's FIRST lm_part
+//                            slot (the fronts sum the landmark's run of slots; k_linearize_tail adds there too)
+//   free tail landmark       t_Hll_diag planes 0, 2 with stride tcapM
+#include "gs_lm.hpp"
+
+#include <algorithm>
+#include <cmath>
+
+namespace gs {
+
+static constexpr int LM_REC = 8;        // doubles per lm_part record (gs_kernels.hip)
+
+__device__ __forceinline__ double lm_wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+__device__ __forceinline__ double lm_wave_max(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
+    return v;
+}
+// fixed-order sum / max over the 256 threads, the result in EVERY thread (red: 5 doubles of LDS)
+__device__ __forceinline__ double lm_block_sum(double v, double *red) {
+    v = lm_wave_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) red[4] = ((red[0] + red[1]) + red[2]) + red[3];
+    __syncthreads();
+    const double r = red[4];
+    __syncthreads();
+    return r;
+}
+__device__ __forceinline__ double lm_block_max(double v, double *red) {
+    v = lm_wave_max(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) red[4] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    __syncthreads();
+    const double r = red[4];
+    __syncthreads();
+    return r;
+}
+
+// the two diagonal scalars of free landmark l (any path), as the fronts see them
+__device__ __forceinline__ void lm_diag_of(const DevGraph &d, int l, double &h00, double &h11) {
+    if (l >= d.M) { const int o = l - d.M; h00 = d.t_Hll_diag[o]; h11 = d.t_Hll_diag[2 * (int64_t)d.tcapM + o]; }
+    else if (d.n_wtiles > 0) { h00 = 0.0; h11 = 0.0;
+        for (int q = d.lm_grp_start[l]; q < d.lm_grp_start[l + 1]; ++q) { h00 += d.lm_part[(int64_t)q * LM_REC]; h11 += d.lm_part[(int64_t)q * LM_REC + 2]; } }
+    else { h00 = d.Hll_diag[l]; h11 = d.Hll_diag[2 * (int64_t)d.M + l]; }
+}
+
+__global__ void __launch_bounds__(256) k_lm_maxdiag(DevGraph d, LmDev lm) {
+    __shared__ double red[5];
+    const int v = blockIdx.x * 256 + threadIdx.x, NP = d.N + d.tN, ML = d.M + d.tM;
+    double m = 0.0;
+    if (v < NP) { const int p = v;
+        if (d.pose_gidx[p] >= 0) {
+            const double *H = p < d.N ? d.Hpp_diag + p : d.t_Hpp_diag + (p - d.N); const int64_t S = p < d.N ? d.N : d.tcapN;
+            m = fmax(fabs(H[0]), fmax(fabs(H[3 * S]), fabs(H[5 * S]))); }
+    } else if (v < NP + ML) { const int l = v - NP;
+        if (d.lm_gidx[l] >= 0) { double a, b; lm_diag_of(d, l, a, b); m = fmax(fabs(a), fabs(b)); } }
+    m = lm_block_max(m, red);
+    if (threadIdx.x == 0) lm.part[blockIdx.x] = m;
+}
+
+// base copy of the estimates (the trial starts at the accepted point) + lambda on the free diagonal scalars.
+// init: the first trial of a call without a lambda — every workgroup reduces the max-diagonal partials itself (a max does not depend
+// on the order), workgroup 0 files the value.  A trial enqueued behind the end of the call (done) re-applies the last trial's lambda:
+// its linearisation ran at the same estimates, so the system in HBM stays the last trial's as it was factorised.
+__global__ void __launch_bounds__(256) k_lm_damp(DevGraph d, LmDev lm, int par, int init) {
+    __shared__ double red[5];
+    LmState &S = lm.state[par];
+    const int v = blockIdx.x * 256 + threadIdx.x, NP = d.N + d.tN, ML = d.M + d.tM;
+    const bool first = init != 0 && S.need_lambda != 0, done = S.done != 0;
+    double lam;
+    if (first) { double m = 0.0;
+        for (int k = threadIdx.x; k < lm.n_part; k += 256) m = fmax(m, lm.part[k]);
+        lam = S.tau * lm_block_max(m, red);
+    } else lam = done ? S.lambda_last : S.lambda;
+    if (v < NP) { const int p = v;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) lm.base_pose[3 * (int64_t)p + c] = d.pose_est[3 * (int64_t)p + c];
+        lm.base_cs[2 * (int64_t)p] = d.pose_cs[2 * (int64_t)p]; lm.base_cs[2 * (int64_t)p + 1] = d.pose_cs[2 * (int64_t)p + 1];
+        if (d.pose_gidx[p] >= 0) {
+            double *H = p < d.N ? d.Hpp_diag + p : d.t_Hpp_diag + (p - d.N); const int64_t St = p < d.N ? d.N : d.tcapN;
+            H[0] += lam; H[3 * St] += lam; H[5 * St] += lam; }
+    } else if (v < NP + ML) { const int l = v - NP;
+        lm.base_lm[2 * (int64_t)l] = d.lm_est[2 * (int64_t)l]; lm.base_lm[2 * (int64_t)l + 1] = d.lm_est[2 * (int64_t)l + 1];
+        if (d.lm_gidx[l] >= 0) {
+            if (l >= d.M) { const int o = l - d.M; d.t_Hll_diag[o] += lam; d.t_Hll_diag[2 * (int64_t)d.tcapM + o] += lam; }
+            // (fused path: a free base landmark always has a slot — the plan gives every landmark with an observation edge in the layout one
+            // per wave tile that sees it, and a growth step that would touch a landmark without one is refused, gs_plan.cpp grow_plan
+            // "landmark without a partial-sum slot".  A free landmark with no observation edge at all has no slot and no place the fronts
+            // would read a lambda from: its diagonal is assembled as 0, H + lambda I stays singular there, and the zero pivot makes every
+            // trial a rejected one — the call terminates instead of moving a vertex no measurement holds.  The guard keeps the store in bounds.)
+            else if (d.n_wtiles > 0) { const int q = d.lm_grp_start[l];
+                if (q < d.lm_grp_start[l + 1]) { d.lm_part[(int64_t)q * LM_REC] += lam; d.lm_part[(int64_t)q * LM_REC + 2] += lam; } }
+            else { d.Hll_diag[l] += lam; d.Hll_diag[2 * (int64_t)d.M + l] += lam; } } }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && !done) {             // (fields no other workgroup of this launch reads)
+        S.lambda_last = lam;
+        if (first) { S.lambda = lam; S.lambda_initial = lam; } }
+}
+
+// scale = sum_j D_j (lambda D_j + b_j) over the free scalars, g2o's computeScale: one partial per workgroup.  Runs BEHIND the update
+// (dpose / dlm are the increment) and BEFORE the chi2 pass (on a grown plan that pass is a full linearisation: it overwrites b).
+__global__ void __launch_bounds__(256) k_lm_scale(DevGraph d, LmDev lm, int par) {
+    __shared__ double red[5];
+    LmState &S = lm.state[par];
+    const int v = blockIdx.x * 256 + threadIdx.x, NP = d.N + d.tN, ML = d.M + d.tM;
+    const double lam = S.lambda_last;
+    double s = 0.0;
+    if (v < NP) { const int p = v;
+        if (d.pose_gidx[p] >= 0) {
+            const double *b = p < d.N ? d.b_pose + p : d.t_b_pose + (p - d.N); const int64_t St = p < d.N ? d.N : d.tcapN;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) { const double dx = d.dpose[3 * (int64_t)p + c]; s += dx * (lam * dx + b[c * St]); } }
+    } else if (v < NP + ML) { const int l = v - NP;
+        if (d.lm_gidx[l] >= 0) {
+            double b0, b1;
+            if (l >= d.M) { const int o = l - d.M; b0 = d.t_b_lm[o]; b1 = d.t_b_lm[(int64_t)d.tcapM + o]; }
+            else if (d.n_wtiles > 0) { b0 = 0.0; b1 = 0.0;
+                for (int q = d.lm_grp_start[l]; q < d.lm_grp_start[l + 1]; ++q) { b0 += d.lm_part[(int64_t)q * LM_REC + 3]; b1 += d.lm_part[(int64_t)q * LM_REC + 4]; } }
+            else { b0 = d.b_lm[l]; b1 = d.b_lm[(int64_t)d.M + l]; }
+            const double d0 = d.dlm[2 * (int64_t)l], d1 = d.dlm[2 * (int64_t)l + 1];
+            s += d0 * (lam * d0 + b0); s += d1 * (lam * d1 + b1); } }
+    s = lm_block_sum(s, red);
+    if (threadIdx.x == 0) lm.part[blockIdx.x] = s;
+    // chi2[0] is still the total at the linearisation point (k_update / k_reduce_chi2 filed it); fail[0] is final for this trial
+    // (only the solver kernels raise it).  Fields no workgroup of this launch reads.
+    if (blockIdx.x == 0 && threadIdx.x == 0) { S.chi_old = d.chi2[0]; S.failcode = d.fail[0]; }
+}
+
+// The verdict.  Every workgroup forms it from the same read-only inputs — state[par], the scale partials in index order, chi2[0] of
+// the chi2 pass — and restores its share of the estimates on a rejection; workgroup 0 writes the next record, the history and the flags.
+//   fail[0] == 1 (zero pivot in this trial's factorisation; k_update applied nothing): a rejected trial, the code is cleared.
+//   fail[0] >= 2 (a whole-tree launch gave up on a flag, ...): nothing moves, the host repairs it and runs the trial again.
+//   done: fail[2] = this trial's iteration number makes k_update skip every later enqueued trial (the rule of gs_optimize_until).
+__global__ void __launch_bounds__(256) k_lm_step(DevGraph d, LmDev lm, int par) {
+    __shared__ double red[5];
+    const LmState S = lm.state[par];
+    const int v = blockIdx.x * 256 + threadIdx.x, NP = d.N + d.tN, ML = d.M + d.tM;
+    double s = 0.0;
+    for (int k = threadIdx.x; k < lm.n_part; k += 256) s += lm.part[k];
+    const double scale = lm_block_sum(s, red) + 1e-3;
+    const double chi_new = d.chi2[0];
+    const bool active = S.done == 0 && (S.failcode == 0 || S.failcode == 1);
+    const double rho = (S.chi_old - chi_new) / scale;
+    const bool accept = active && S.failcode == 0 && rho > 0.0 && isfinite(chi_new);
+    if (active && !accept) {                                        // put x back (bit for bit: copies)
+        if (v < NP) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) d.pose_est[3 * (int64_t)v + c] = lm.base_pose[3 * (int64_t)v + c];
+            d.pose_cs[2 * (int64_t)v] = lm.base_cs[2 * (int64_t)v]; d.pose_cs[2 * (int64_t)v + 1] = lm.base_cs[2 * (int64_t)v + 1];
+        } else if (v < NP + ML) { const int l = v - NP;
+            d.lm_est[2 * (int64_t)l] = lm.base_lm[2 * (int64_t)l]; d.lm_est[2 * (int64_t)l + 1] = lm.base_lm[2 * (int64_t)l + 1]; } }
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    LmState T = S;
+    T.failcode = 0;
+    if (active) {
+        const int it = S.iterations;
+        if (S.trials == 0) T.chi_base = S.chi_old;
+        if (it < 64) { lm.hist_chi2[it] = S.chi_old; lm.hist_lambda[it] = S.lambda_last; lm.hist_trials[it] = S.trials_iter + 1; }
+        T.need_lambda = 0; T.trials = S.trials + 1;
+        if (accept) {
+            const double t = 2.0 * rho - 1.0;
+            double alpha = 1.0 - t * t * t;
+            alpha = fmin(alpha, 2.0 / 3.0);
+            T.lambda = S.lambda_last * fmax(1.0 / 3.0, alpha); T.nu = 2.0;
+            T.iterations = it + 1; T.trials_iter = 0; T.chi_base = chi_new;
+            if (T.iterations >= S.budget) T.done = 1;
+        } else {
+            T.lambda = S.lambda_last * S.nu; T.nu = 2.0 * S.nu;
+            T.rejected = S.rejected + 1; T.trials_iter = S.trials_iter + 1;
+            if (S.failcode == 1) d.fail[0] = 0;
+            if (T.trials_iter >= S.max_trials) { T.terminated = 1; T.done = 1; }
+        }
+        if (T.done) d.fail[2] = d.iter;
+    } else if (S.done != 0 && S.failcode == 1) d.fail[0] = 0;      // a no-op trial behind the end of the call factorised the last trial's system again: its zero pivot is that trial's, already counted
+    lm.state[par ^ 1] = T;
+}
+
+int lm_grid(const DevGraph &d) { return std::max(1, (d.N + d.tN + d.M + d.tM + 255) / 256); }
+void launch_lm_maxdiag(const DevGraph &d, const LmDev &lm, hipStream_t st) { hipLaunchKernelGGL(k_lm_maxdiag, dim3(lm_grid(d)), dim3(256), 0, st, d, lm); }
+void launch_lm_damp(const DevGraph &d, const LmDev &lm, int par, int init, hipStream_t st) { hipLaunchKernelGGL(k_lm_damp, dim3(lm_grid(d)), dim3(256), 0, st, d, lm, par, init); }
+void launch_lm_scale(const DevGraph &d, const LmDev &lm, int par, hipStream_t st) { hipLaunchKernelGGL(k_lm_scale, dim3(lm_grid(d)), dim3(256), 0, st, d, lm, par); }
+void launch_lm_step(const DevGraph &d, const LmDev &lm, int par, hipStream_t st) { hipLaunchKernelGGL(k_lm_step, dim3(lm_grid(d)), dim3(256), 0, st, d, lm, par); }
+
+}  // namespace gs
