@@ -99,6 +99,25 @@ int gs_debug_time_exchange(gs_graph *g, int32_t reps, double *out_ms);
  * <= 63 scalars, a workgroup per front of 64 .. 159; arena < 2^29 doubles), 4 = block-per-front kernel with 64-bit addressing
  * (anything else).  Pure function; what gs_initialize_optimization applies. */
 int gs_debug_select_factor_variant(int32_t requested, int32_t max_front, int64_t arena_doubles);
+/* The solver launches of the current plan, as decided once with the plan (a function of the plan and the options: no call history).
+ * Same calling convention as gs_plan_export (out == NULL: *out_len = the length); works on a host-only handle after gs_plan_build_host.
+ * int32 record, n_levels = L, own / shared level positions n_own / n_shared (a position indexes the device's level list: own fronts,
+ * then the shared top of a sharded plan from shared_base):
+ *   [0..20)  0x47535331, L, n_own, n_shared, shared_base, factor_variant (3, or 0 = the C-ABI's 4), tables (1: the plan holds a front of
+ *            more than 63 scalars, launches are table-driven), leaf_n, leaf_slot, leaf_max_f, n_subtrees, sub_first, sub_free, block_n,
+ *            bs_l0 (first level of the flagged backward-solve launch), small_max_npiv, small_max_f, 0, 0, 0
+ *   own_start[L + 1], shared_start[L + 1], own_fronts[n_own], shared_fronts[n_shared]  (position -> front, positions relative to the list)
+ *   five tables (own factor, own backward solve, shared contributions, shared top, shared backward solve), each: n, then n entries
+ *            {position, kind | count << 8}: kind 0 = `count` small fronts a wave each (factor: position upwards, backward solve: downwards),
+ *            1 = a small front on four waves, 4 / 2 / 3 = a front of 64-79 / 80-111 / 112-159 scalars on a workgroup
+ *   the launches of one iteration in whole-tree mode, then with one launch per level (after a flag timeout), each: n, then n records
+ *            {kind, first, count, LDS bytes (0: chosen inside the launcher), kernel class or mode, table (-1: none)}
+ *            kind 1 whole-tree factor launch over positions [first, first + count) (leaf instance, bottom subtrees and flagged levels as
+ *            the header says), 2 the leaf instance alone, 3 one factor launch over positions of one level (class = mode: 0 own, 1
+ *            contributions, 2 shared top), 4 the shared top's flagged launch, 5 table-driven factor launch: entries [first, first + count)
+ *            of `table` (0 .. 4 in the order above), 6 flagged backward-solve launch, 7 backward-solve launch of one level, 8 table-driven
+ *            backward-solve launch.  A launch over no fronts (an empty level of a list) is none: left out. */
+int gs_debug_schedule_export(gs_graph *g, int32_t *out, int64_t *out_len);
 
 #ifdef __cplusplus
 }

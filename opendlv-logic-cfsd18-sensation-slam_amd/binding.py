@@ -204,6 +204,8 @@ def lib():
     L.gs_time_iterations.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
     L.gs_plan_build_host.argtypes = [vp, C.POINTER(PlanInfo)]
     L.gs_plan_export.argtypes = [vp, _ip, C.POINTER(C.c_int64)]
+    if hasattr(L, "gs_debug_schedule_export"):             # (a tuning build of an older tree loaded through GS_LIB may predate the schedule)
+        L.gs_debug_schedule_export.argtypes = [vp, _ip, C.POINTER(C.c_int64)]
     L.gs_reserve_device.argtypes = [vp, C.c_int64]
     L.gs_plan_growths.argtypes = [vp]; L.gs_growth_refusal.argtypes = [vp]; L.gs_growth_refusal.restype = C.c_char_p
     L.gs_polar_to_xy_batch.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp]
@@ -643,6 +645,29 @@ class Graph:
         out = np.zeros(n.value, dtype=np.int32)
         self._check(self.L.gs_plan_export(self.h, _i(out), C.byref(n)))
         return out
+
+    def debug_schedule(self):
+        """the solver launches of the current plan (gs_debug_schedule_export), parsed: the scalar decisions, level lists, the five
+        workgroup tables as (n, 2) arrays and the launches of an iteration per mode as (n, 6) arrays
+        {kind, first, count, lds, cls, table}"""
+        n = C.c_int64(0)
+        self._check(self.L.gs_debug_schedule_export(self.h, None, C.byref(n)))
+        raw = np.zeros(n.value, dtype=np.int32)
+        self._check(self.L.gs_debug_schedule_export(self.h, _i(raw), C.byref(n)))
+        names = ("magic", "n_levels", "n_own", "n_shared", "shared_base", "factor_variant", "tables", "leaf_n", "leaf_slot", "leaf_max_f",
+                 "n_subtrees", "sub_first", "sub_free", "block_n", "bs_l0", "small_max_npiv", "small_max_f")
+        S = {k: int(raw[i]) for i, k in enumerate(names)}
+        at = [20]
+        def take(cnt, width=1):
+            a = raw[at[0]:at[0] + cnt * width].copy(); at[0] += cnt * width
+            return a.reshape(cnt, width) if width > 1 else a
+        L1 = S["n_levels"] + 1
+        S["own_start"] = take(L1); S["shared_start"] = take(L1); S["own_fronts"] = take(S["n_own"]); S["shared_fronts"] = take(S["n_shared"])
+        S["tab"] = [take(int(take(1)[0]), 2) for _ in range(5)]
+        S["launches_tree"] = take(int(take(1)[0]), 6); S["launches_level"] = take(int(take(1)[0]), 6)
+        assert at[0] == len(raw), (at[0], len(raw))
+        S["raw"] = raw
+        return S
 
     # ---- front end
     def polar_to_xy(self, az, zen, dist):

@@ -3,15 +3,11 @@
 // (reference src/slam.cpp:53-65, 433-484, 525-550, 713-732) lands here.
 #include "../../include/graphslam.h"
 #include "../../include/graphslam_debug.h"
-#include "gs_device.hpp"
-#include "gs_host.hpp"
-#include "gs_internal.hpp"
+#include "gs_private.hpp"
 #include "gs_parallel.hpp"
 
-#include <dlfcn.h>
-#include <rccl/rccl.h>          // types and prototypes only: the library is resolved at run time (rccl_api), never linked
-
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -27,54 +23,13 @@ thread_local std::string g_last_error;
 int fail(int code, const std::string &msg) { g_last_error = msg; return code; }
 }  // namespace gs
 
-#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
-    return fail(GS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
-
 // ------------------------------------------------------------------ helpers
-void gs_frontend_release(gs_graph *g);       // front-end buffers of the handle (defined with the front end below)
-void gs_dist_comm_release(gs_graph *g);      // the handle's own RCCL communicator (defined with the multi-GPU entry points)
 static int usable_devices() {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
 }
 
-// Device memory of a plan comes out of a few large chunks (8 MB, then doubling): the ~70 arrays of one structure phase
-// cost a dozen hipMalloc calls instead of 70 (each is 50-100 us of the structure phase), and dev_free_all returns them together.
-// Arrays of 32 MB and more get an allocation of their own.
-// gs_debug_options.pool_poison (tests): every chunk is filled with 0xFF bytes (NaN doubles, negative indices) when it is allocated and whenever a plan
-// releases it — an array that is read before this code writes it cannot pass for zero-initialised
-static bool pool_poison(const gs_graph *g) { return g->opt.pool_poison > 0; }
-template <class T> static int dev_alloc(gs_graph *g, T **ptr, size_t count) {
-    *ptr = nullptr;
-    const size_t bytes = (std::max<size_t>(count, 1) * sizeof(T) + 255) & ~(size_t)255;
-    if (bytes >= ((size_t)32 << 20)) {                                // a big array: its own allocation, exactly its size (a chunk rounded up to a
-        int best = -1;                                                // power of two for it, or the abandoned rest of the current chunk, were 270 MB of
-        for (size_t i = 0; i < g->allocs.size(); ++i) { const auto &c = g->allocs[i];      // an 800 MB footprint at 100k poses); one kept from the last plan
-            if (c.big && !c.in_use && c.size >= bytes && c.size <= bytes + bytes / 4 && (best < 0 || c.size < g->allocs[best].size)) best = (int)i; }   // serves if it fits within 25 %
-        if (best < 0) { void *p = nullptr;
-            HIP_TRY(hipMalloc(&p, bytes));
-            if (pool_poison(g)) HIP_TRY(hipMemsetAsync(p, 0xFF, bytes, g->stream));
-            gs_graph::DevChunk c; c.p = p; c.size = bytes; c.big = true; g->allocs.push_back(c); best = (int)g->allocs.size() - 1; }
-        g->allocs[best].in_use = true; g->pool_total += g->allocs[best].size; *ptr = (T *)g->allocs[best].p;
-        return GS_OK; }
-    if (g->pool_off + bytes > g->pool_size) {
-        size_t want = std::max<size_t>(g->pool_next, (size_t)8 << 20);
-        while (want < bytes) want <<= 1;
-        int pick = -1;
-        for (size_t i = 0; i < g->allocs.size() && pick < 0; ++i) { const auto &c = g->allocs[i]; if (!c.big && !c.in_use && c.size >= want) pick = (int)i; }   // a chunk of the last plan
-        if (pick < 0) { void *p = nullptr;
-            HIP_TRY(hipMalloc(&p, want));
-            if (pool_poison(g)) HIP_TRY(hipMemsetAsync(p, 0xFF, want, g->stream));
-            gs_graph::DevChunk c; c.p = p; c.size = want; g->allocs.push_back(c); pick = (int)g->allocs.size() - 1; }
-        auto &c = g->allocs[pick]; c.in_use = true; g->pool_total += c.size;
-        g->pool_base = (char *)c.p; g->pool_size = c.size; g->pool_off = 0;
-        g->pool_next = std::min<size_t>(std::max(want, c.size) << 1, (size_t)128 << 20);      // chunks of at most 128 MB: little slack in the footprint
-    }
-    *ptr = (T *)(g->pool_base + g->pool_off);
-    g->pool_off += bytes;
-    return GS_OK;
-}
 template <class T, class A> static int dev_upload(gs_graph *g, T **ptr, const std::vector<T, A> &v) {
     int rc = dev_alloc(g, ptr, v.size());
     if (rc != GS_OK) return rc;
@@ -100,6 +55,7 @@ static void dev_release(gs_graph *g, bool keep) {
     g->dev_valid = false;
     g->room = gs_graph::GrowRoom(); g->d_bf = g->d_xrow = g->d_patch = g->d_list = nullptr;
     g->marg = gs_graph::Marginals();                                // its buffers were pool memory of the plan
+    g->sched = Schedule(); for (auto &t : g->d_wg) t = nullptr;     // ... and so were the schedule's tables
 }
 static void dev_free_all(gs_graph *g) { dev_release(g, false); }
 // after a structure phase: what the new plan did not take again goes back to the device
@@ -112,7 +68,7 @@ static void dev_trim(gs_graph *g) {
     g->allocs.resize(w);
 }
 
-static int ensure_device(gs_graph *g) {
+int ensure_device(gs_graph *g) {
     if (g->host_only) return fail(GS_ERR_NO_DEVICE, "host-only handle (device = -2): no compute without a gfx950 device");
     HIP_TRY(hipSetDevice(g->device));
     return GS_OK;
@@ -292,8 +248,6 @@ extern "C" int gs_set_stream(gs_graph *g, void *s) {
     return GS_OK;
 }
 
-// ------------------------------------------------------------------ construction (A2)
-static int pull_estimates_if_needed(gs_graph *g);
 
 extern "C" int gs_add_pose(gs_graph *g, int32_t id, const double est[3]) {
     if (!g || !est) return fail(GS_ERR_INVALID, "null argument");
@@ -405,12 +359,18 @@ extern "C" int gs_set_landmark_estimate(gs_graph *g, int32_t id, const double es
 }
 
 // ------------------------------------------------------------------ read-back (A11)
-static int pull_estimates_if_needed(gs_graph *g) {
-    if (!g->dev_valid || !g->dev_estimates_newer) return GS_OK;
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+int pull_estimates_enqueue(gs_graph *g, bool &pull) {
+    pull = g->dev_valid && g->dev_estimates_newer;
+    if (!pull) return GS_OK;
     const int N = g->d.N + g->d.tN, M = g->d.M + g->d.tM;          // (tail vertices of a grown plan follow the base ones in the same arrays)
     if (N > 0) HIP_TRY(hipMemcpyAsync(g->h.pose_est.data(), g->d.pose_est, (size_t)N * 3 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
     if (M > 0) HIP_TRY(hipMemcpyAsync(g->h.lm_est.data(), g->d.lm_est, (size_t)M * 2 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    return GS_OK;
+}
+int pull_estimates_if_needed(gs_graph *g) {
+    if (!g->dev_valid || !g->dev_estimates_newer) return GS_OK;
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    bool pull; if ((rc = pull_estimates_enqueue(g, pull)) != GS_OK) return rc;
     HIP_TRY(hipStreamSynchronize(g->stream));
     g->dev_estimates_newer = false;
     return GS_OK;
@@ -425,7 +385,7 @@ static int read_failure(gs_graph *g, int32_t out[2]) {
     HIP_TRY(hipStreamSynchronize(g->stream));
     return GS_OK;
 }
-static int reset_failure(gs_graph *g) {
+int reset_failure(gs_graph *g) {
     g->d.inject_iter = 0; g->d.inject_code = 0;
     HIP_TRY(hipMemsetAsync(g->d.fail, 0, 4 * sizeof(int32_t), g->stream));
     // the ticket counter and its host-side running sum start again together (a launch that failed to ENQUEUE was counted on the host only)
@@ -571,13 +531,20 @@ static int upload_raw_begin(gs_graph *g, RawUpload &R) {
     return GS_OK;
 }
 
+// the workgroup tables of the schedule (plans with a front of more than 63 scalars) go to the device with the plan; the copies read the
+// handle's own vectors
+static int upload_tables(gs_graph *g) {
+    for (int t = 0; t < N_TABS; ++t) { g->d_wg[t] = nullptr;
+        if (g->sched.big) { int rc = dev_upload(g, (int32_t **)&g->d_wg[t], g->sched.tab[t].wg); if (rc != GS_OK) return rc; } }
+    return GS_OK;
+}
+
 static int upload_graph(gs_graph *g, RawUpload &raw) {
     const HostGraph &h = g->h; const Plan &P = g->plan; DevGraph &d = g->d;
     const bool ut_on = g->opt.plan_timing > 0; auto ut_prev = std::chrono::steady_clock::now();
 #define GS_UT(name) do { if (ut_on) { auto n_ = std::chrono::steady_clock::now(); std::fprintf(stderr, "upload %-18s %.2f ms\n", (name), std::chrono::duration<double, std::milli>(n_ - ut_prev).count()); ut_prev = n_; } } while (0)
     const int N = h.n_poses(), M = h.n_lms(), Epp = h.n_pp(), Epl = h.n_pl();
     d.N = N; d.M = M; d.Epp = Epp; d.Epl = Epl; d.n_scalar = P.n_scalar;
-    g->leaf_n = -1; g->block_n = -1;
     int rc;
 #define UP(dst, vec) if ((rc = dev_upload(g, &d.dst, vec)) != GS_OK) return rc
     // estimates, fixed flags, odometry edges and the insertion-order observation arrays are in HBM already (RawUpload)
@@ -698,7 +665,7 @@ static int upload_graph(gs_graph *g, RawUpload &raw) {
           cd[4 * q] = P.children[q]; cd[4 * q + 1] = C.npiv | (C.nbnd << 16); cd[4 * q + 2] = C.owner; cd[4 * q + 3] = (int32_t)C.map_off; }
       UP(child_desc, cd); }
     // level lists on the device: this rank's own fronts, then the shared top (empty when world == 1)
-    { std::vector<int32_t> lf = P.level_fronts_owned; g->shared_base = (int)lf.size();
+    { std::vector<int32_t> lf = P.level_fronts_owned;
       lf.insert(lf.end(), P.level_fronts_shared.begin(), P.level_fronts_shared.end());
       UP(level_fronts, lf); }
     d.xfail_off = -1; d.iter = 0; d.inject_iter = 0; d.inject_code = 0;
@@ -718,7 +685,6 @@ static int upload_graph(gs_graph *g, RawUpload &raw) {
       if (g->opt.factor_variant > 0) v = g->opt.factor_variant;
       v = gs_debug_select_factor_variant(v, P.max_front, arena_doubles);
       if (v == 4) v = 0;                                              // device-side code for the block-per-front kernel
-      g->wg_f.clear(); g->wg_b.clear(); g->d_wg_f = g->d_wg_b = g->d_wgs_c = g->d_wgs_t = g->d_wgs_b = nullptr;
       d.factor_variant = v;
       d.dbg = g->opt.dbg; d.leaf_nt3 = g->opt.leaf_nt3 != 0 ? 1 : 0; d.f3_lds_kb = std::max(g->opt.f3_lds_kb, 0);
       if (v == 3) {
@@ -808,27 +774,12 @@ static int upload_graph(gs_graph *g, RawUpload &raw) {
     HIP_TRY(hipMemsetAsync(d.chi2, 0, 80 * sizeof(double), g->stream));
     HIP_TRY(hipMemsetAsync(d.dpose, 0, ((size_t)N + TAIL_POSES) * 3 * sizeof(double), g->stream));
     HIP_TRY(hipMemsetAsync(d.dlm, 0, ((size_t)M + TAIL_LMS) * 2 * sizeof(double), g->stream));
-    // per-level launch parameters and the global workspace for fronts beyond the LDS limit
-    const int nlev = (int)P.level_start.size() - 1;
-    const int lim = factor_lds_limit_f();
-    int64_t max_blocks_oversize = 0;
-    auto level_params = [&](const std::vector<int32_t> &start, const std::vector<int32_t> &list, gs_graph::LevelSet &ls) {
-        ls.start = start; ls.max_f.assign(nlev, 0); ls.max_npiv.assign(nlev, 0); ls.max_nbnd.assign(nlev, 0);
-        for (int l = 0; l < nlev; ++l) {
-            for (int q = start[l]; q < start[l + 1]; ++q) { const Front &F = P.fronts[list[q]];
-                ls.max_f[l] = std::max(ls.max_f[l], F.npiv + F.nbnd);
-                ls.max_npiv[l] = std::max(ls.max_npiv[l], F.npiv); ls.max_nbnd[l] = std::max(ls.max_nbnd[l], F.nbnd); }
-            if (ls.max_f[l] > lim) { const int64_t f = ls.max_f[l];
-                d.front_ws_stride = std::max(d.front_ws_stride, ((f + 1) | 1) * f);
-                max_blocks_oversize = std::max<int64_t>(max_blocks_oversize, start[l + 1] - start[l]); }
-        }
-    };
-    level_params(P.level_start_owned, P.level_fronts_owned, g->own);
-    level_params(P.level_start_shared, P.level_fronts_shared, g->shared);
-    if (max_blocks_oversize > 0) {      // fronts beyond the LDS limit use a global workspace, one slice per block
-        max_blocks_oversize = std::max<int64_t>(max_blocks_oversize, (int64_t)P.level_fronts_shared.size());
-        AL(front_ws, d.front_ws_stride * max_blocks_oversize);
-    }
+    // the solver launches of this plan, decided here once (gs_schedule.hpp); the global workspace for fronts beyond the LDS limit,
+    // one slice per block; the workgroup tables of a plan with fronts beyond a wave
+    g->sched = build_schedule(P, g->pos_of_front, d.factor_variant, g->opt.tree != 0, g->opt);
+    d.front_ws_stride = g->sched.front_ws_stride;
+    if (g->sched.ws_blocks > 0) AL(front_ws, d.front_ws_stride * g->sched.ws_blocks);
+    if ((rc = upload_tables(g)) != GS_OK) return rc;
 #undef UP
 #undef AL
 #undef ZERO
@@ -947,12 +898,11 @@ static int upload_growth(gs_graph *g, const Growth &gr) {
     for (int i = 0; i < nf; ++i) { const int s = gr.fronts[i]; const int32_t *r = &patch[(size_t)i * 32];
         g->u3_off_host[s] = r[21]; g->u3_size_host[s] = r[22]; for (int c = 0; c < 8; ++c) g->bf_host[8 * (size_t)s + c] = r[23 + c]; }
     g->room.used_U = used_U; g->room.used_sc = used_sc;
-    { gs_graph::LevelSet &ls = g->own; const int nlev = (int)ls.start.size() - 1;
-      for (int l = 0; l < nlev; ++l) { ls.max_f[l] = ls.max_npiv[l] = ls.max_nbnd[l] = 0;
-          for (int q = ls.start[l]; q < ls.start[l + 1]; ++q) { const Front &F = P.fronts[P.level_fronts_owned[q]];
-              ls.max_f[l] = std::max(ls.max_f[l], F.npiv + F.nbnd); ls.max_npiv[l] = std::max(ls.max_npiv[l], F.npiv); ls.max_nbnd[l] = std::max(ls.max_nbnd[l], F.nbnd); } } }
-    g->leaf_n = -1; g->block_n = -1; g->tree_proven = false;        // the leaf instance and its LDS slot are chosen again from the grown fronts
-    g->wg_f.clear(); g->wg_b.clear(); g->d_wg_f = g->d_wg_b = g->d_wgs_c = g->d_wgs_t = g->d_wgs_b = nullptr;   // ... and so are the workgroup tables of a plan with workgroup fronts (a grown front may change its size class)
+    // the launch geometry is chosen again from the grown fronts: level maxima, leaf instance and its LDS slot, the workgroup tables (a
+    // grown front may change its size class).  The old tables stay in the pool until the next full structure phase.
+    g->sched = build_schedule(P, g->pos_of_front, d.factor_variant, g->opt.tree != 0, g->opt);
+    if ((rc = upload_tables(g)) != GS_OK) return rc;
+    g->tree_proven = false;
     g->dev_estimate_version = h.estimate_version;
     return GS_OK;
 }
@@ -1024,6 +974,26 @@ extern "C" int gs_plan_export(gs_graph *g, int32_t *out, int64_t *out_len) {
     return GS_OK;
 }
 
+// the schedule of the current plan: the one the device runs from when the plan is uploaded, else (host-only handle, after gs_plan_build_host)
+// built the way upload_graph builds it — without the arena-size rule of the variant choice, which needs the device layout
+extern "C" int gs_debug_schedule_export(gs_graph *g, int32_t *out, int64_t *out_len) {
+    if (!g || !out_len) return fail(GS_ERR_INVALID, "null argument");
+    if (!g->plan.valid) return fail(GS_ERR_NOT_INITIALIZED, "no plan built");
+    std::vector<int32_t> v;
+    if (g->dev_valid && g->plan_version == g->h.structure_version) export_schedule(g->plan, g->sched, v);
+    else { const Plan &P = g->plan;
+        int fv = gs_debug_select_factor_variant(g->opt.factor_variant > 0 ? g->opt.factor_variant : g->cfg.factor_variant, P.max_front, 0);
+        if (fv == 4) fv = 0;
+        std::vector<int32_t> pos(P.fronts.size(), -1); int32_t q = 0;
+        for (int32_t s : P.level_fronts_owned) pos[s] = q++;
+        for (int32_t s : P.level_fronts_shared) pos[s] = q++;
+        export_schedule(P, build_schedule(P, pos, fv, g->opt.tree != 0, g->opt), v); }
+    if (!out) { *out_len = (int64_t)v.size(); return GS_OK; }
+    if (*out_len < (int64_t)v.size()) return fail(GS_ERR_CAPACITY, "buffer too small");
+    std::memcpy(out, v.data(), v.size() * sizeof(int32_t)); *out_len = (int64_t)v.size();
+    return GS_OK;
+}
+
 extern "C" int gs_initialize_optimization(gs_graph *g) {
     if (!g) return fail(GS_ERR_INVALID, "null graph");
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
@@ -1071,7 +1041,7 @@ extern "C" int gs_initialize_optimization(gs_graph *g) {
     return GS_OK;
 }
 
-static int ensure_ready(gs_graph *g) {
+int ensure_ready(gs_graph *g) {
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (!g->dev_valid || g->plan_version != g->h.structure_version) return gs_initialize_optimization(g);
     if (g->dev_estimate_version != g->h.estimate_version) {      // host-side setEstimate since the upload
@@ -1085,230 +1055,7 @@ static int ensure_ready(gs_graph *g) {
     return GS_OK;
 }
 
-// ------------------------------------------------------------------ one Gauss-Newton iteration (A5-A9)
-// own fronts bottom-up (mode 0), shared top bottom-up from the all-reduced exchange buffer (mode 2)
-// ---- plans that hold a front of more than 63 scalars (single GPU): the workgroup tables of the table-driven launches, built on
-// first use.  Factor: level positions upwards from the end of the leaf launch — a big front a workgroup (NT = 7 or 10 tile
-// rows), a small front of the upper levels (the last block_n positions) four waves, other small fronts a wave each in groups of
-// up to four that do not straddle a level.  Backward solve: every position from the root downwards.
-static int build_big_tables(gs_graph *g, const gs_graph::LevelSet &ls) {
-    const Plan &P = g->plan; const int nlev = (int)ls.start.size() - 1, total = ls.start[nlev];
-    auto f_of = [&](int q) { const Front &F = P.fronts[P.level_fronts_owned[q]]; return F.npiv + F.nbnd; };
-    auto big_kind = [&](int f) { return f <= 79 ? 4 : (f <= 111 ? 2 : 3); };        // 5, 7 or 10 tile rows
-    g->wg_f.clear(); g->wg_b.clear(); g->seg_f.clear(); g->seg_b.clear();
-    g->wgs_c.clear(); g->wgs_t.clear(); g->wgs_b.clear(); g->segs_c.clear(); g->segs_t.clear(); g->segs_b.clear();
-    g->small_max_npiv = 1; g->small_max_f = 1;
-    for (const Front &F : P.fronts) if (!F.opaque && F.npiv + F.nbnd <= 63) { g->small_max_npiv = std::max(g->small_max_npiv, (int)F.npiv); g->small_max_f = std::max(g->small_max_f, F.npiv + F.nbnd); }
-    auto push = [&](std::vector<int32_t> &tab, std::vector<gs_graph::WgSeg> &segs, int pos, int kind_cnt, int level, size_t lds, int cls) {
-        const int e = (int)tab.size() / 2; tab.push_back(pos); tab.push_back(kind_cnt);
-        if (!segs.empty() && segs.back().level == level && segs.back().lds == lds && segs.back().cls == cls) ++segs.back().count; else segs.push_back({e, 1, level, lds, cls}); };
-    auto fcls = [](int kind) { return kind == 4 ? 0 : (kind == 3 ? 2 : 1); };       // factor kernel class: fronts of 64-79 | small fronts and 80-111 | 112-159
-    const int first = std::max(g->leaf_n, 0), first_block = total - std::max(g->block_n, 0);
-    for (int l = 0; l < nlev; ++l)
-        for (int q = std::max(ls.start[l], first); q < ls.start[l + 1]; ) {
-            const int f = f_of(q);
-            if (f > 63) { const int k = big_kind(f); push(g->wg_f, g->seg_f, q, k, l, factor_tab_lds_bytes(k), fcls(k)); ++q; }
-            else if (q >= first_block) { push(g->wg_f, g->seg_f, q, 1 | (1 << 8), l, factor_tab_lds_bytes(1), 1); ++q; }
-            else { int cnt = 1; while (cnt < 4 && q + cnt < ls.start[l + 1] && q + cnt < first_block && f_of(q + cnt) <= 63) ++cnt;
-                push(g->wg_f, g->seg_f, q, 0 | (cnt << 8), l, factor_tab_lds_bytes(0), 1); q += cnt; } }
-    for (int l = nlev - 1; l >= 0; --l)
-        for (int q = ls.start[l + 1] - 1; q >= ls.start[l]; ) {
-            const int f = f_of(q);
-            if (f > 63) { // LDS by the size class of the front (the largest front of the class), so that runs of one class share a launch
-                const int k = big_kind(f), fc = k == 4 ? 79 : (k == 2 ? 111 : 159);
-                push(g->wg_b, g->seg_b, q, k, l, backsolve_tab_lds_bytes(k, fc, 0), 1); --q; }
-            else { int cnt = 1; while (cnt < 4 && q - cnt >= ls.start[l] && f_of(q - cnt) <= 63) ++cnt;
-                push(g->wg_b, g->seg_b, q, 0 | (cnt << 8), l, backsolve_tab_lds_bytes(0, g->small_max_f, g->small_max_npiv), 0); q -= cnt; } }
-    // ---- pose-window shards: the SHARED top of a plan with workgroup fronts (round 4).  Three tables over the shared level positions
-    // (shared_base + q): contributions (mode CONTRIB: no dependencies among them; a small front a wave — the four-wave form has no such
-    // mode —, a big one a workgroup), the top itself (mode TOP, children first: a small front four waves, a big one a workgroup), and
-    // the backward solve (root first).
-    { const gs_graph::LevelSet &sh = g->shared; const int nls = (int)sh.start.size() - 1, B0 = g->shared_base;
-      auto fs = [&](int q) { const Front &F = P.fronts[P.level_fronts_shared[q]]; return F.npiv + F.nbnd; };
-      for (int l = 0; l < nls; ++l)
-          for (int q = sh.start[l]; q < sh.start[l + 1]; ) { const int f = fs(q);
-              if (f > 63) { const int k = big_kind(f);
-                  push(g->wgs_c, g->segs_c, B0 + q, k, l, factor_tab_lds_bytes(k), fcls(k)); push(g->wgs_t, g->segs_t, B0 + q, k, l, factor_tab_lds_bytes(k), fcls(k)); ++q; }
-              else { push(g->wgs_t, g->segs_t, B0 + q, 1 | (1 << 8), l, factor_tab_lds_bytes(1), 1);
-                  int cnt = 1; while (cnt < 4 && q + cnt < sh.start[l + 1] && fs(q + cnt) <= 63) ++cnt;
-                  push(g->wgs_c, g->segs_c, B0 + q, 0 | (cnt << 8), l, factor_tab_lds_bytes(0), 1);
-                  for (int k2 = 1; k2 < cnt; ++k2) push(g->wgs_t, g->segs_t, B0 + q + k2, 1 | (1 << 8), l, factor_tab_lds_bytes(1), 1);
-                  q += cnt; } }
-      for (int l = nls - 1; l >= 0; --l)
-          for (int q = sh.start[l + 1] - 1; q >= sh.start[l]; ) { const int f = fs(q);
-              if (f > 63) { const int k = big_kind(f), fc = k == 4 ? 79 : (k == 2 ? 111 : 159); push(g->wgs_b, g->segs_b, B0 + q, k, l, backsolve_tab_lds_bytes(k, fc, 0), 1); --q; }
-              else { int cnt = 1; while (cnt < 4 && q - cnt >= sh.start[l] && fs(q - cnt) <= 63) ++cnt;
-                  push(g->wgs_b, g->segs_b, B0 + q, 0 | (cnt << 8), l, backsolve_tab_lds_bytes(0, g->small_max_f, g->small_max_npiv), 0); q -= cnt; } } }
-    int rc;
-    auto up = [&](int2 **dst, const std::vector<int32_t> &v) -> int {
-        int r2 = dev_alloc(g, (int32_t **)dst, v.size()); if (r2 != GS_OK) return r2;
-        if (!v.empty()) { hipError_t e = hipMemcpyAsync(*dst, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice, g->stream); if (e != hipSuccess) return fail(GS_ERR_HIP, hipGetErrorString(e)); }   // the host vectors live on the handle
-        return GS_OK; };
-    if ((rc = up(&g->d_wg_f, g->wg_f)) != GS_OK || (rc = up(&g->d_wg_b, g->wg_b)) != GS_OK || (rc = up(&g->d_wgs_c, g->wgs_c)) != GS_OK ||
-        (rc = up(&g->d_wgs_t, g->wgs_t)) != GS_OK || (rc = up(&g->d_wgs_b, g->wgs_b)) != GS_OK) return rc;
-    return GS_OK;
-}
-// launches = maximal runs of table entries with the same LDS need (whole-tree mode: across levels; after a flag timeout: never
-// across a level, so that no workgroup waits for one of its own launch)
-template <class Launch> static void for_each_run(const std::vector<gs_graph::WgSeg> &segs, bool across_levels, Launch &&fn) {
-    for (size_t i = 0; i < segs.size(); ) {
-        size_t j = i + 1; int n = segs[i].count;
-        while (j < segs.size() && segs[j].lds == segs[i].lds && segs[j].cls == segs[i].cls && (across_levels || segs[j].level == segs[i].level)) { n += segs[j].count; ++j; }
-        fn(segs[i].first, n, segs[i].lds, segs[i].cls);
-        i = j; }
-}
-static bool ensure_big_tables(gs_graph *g) {
-    // the workgroup tables of a plan with fronts beyond a wave are built on first use; if that fails (device memory), NO solver launch of
-    // this iteration may run and its update must not be applied: the failure is kept on the handle (enqueue_rc: every entry point that
-    // enqueues iterations returns it) and raised on the device like a failed solve, so that k_update applies nothing
-    if (g->d_wg_f) return true;
-    const int rc = build_big_tables(g, g->own);
-    if (rc == GS_OK) return true;
-    g->enqueue_rc = rc; g->enqueue_err = g_last_error; g->d_wg_f = g->d_wg_b = g->d_wgs_c = g->d_wgs_t = g->d_wgs_b = nullptr;
-    const int32_t one = 1; hipMemcpyAsync(g->d.fail, &one, sizeof(int32_t), hipMemcpyHostToDevice, g->stream); hipStreamSynchronize(g->stream);
-    return false;
-}
-static void enqueue_factor_big(gs_graph *g, const gs_graph::LevelSet &ls, bool tree) {
-    if (!ensure_big_tables(g)) return;
-    if (g->leaf_n > 0) launch_factor_tree(g->d, g->leaf_n, g->leaf_slot, g->leaf_max_f, g->leaf_n, 0, 0, 0, g->stream);       // the leaf instance alone
-    // "no flags to wait for at level 1" holds only if EVERY leaf went through the leaf launch (big leaves share the table launch with their parents)
-    const int leaf_pre = (g->leaf_n > 0 && g->leaf_n == ls.start[1]) ? 1 : 0;
-    for_each_run(g->seg_f, tree, [&](int first, int n, size_t lds, int cls) { launch_factor_tab(g->d, g->d_wg_f + first, n, leaf_pre, lds, cls, g->stream); });
-}
-static void enqueue_backsolve_big(gs_graph *g, const gs_graph::LevelSet &, bool tree) {
-    if (!g->d_wg_b) return;
-    for_each_run(g->seg_b, tree, [&](int first, int n, size_t lds, int cls) { launch_backsolve_tab(g->d, g->d_wg_b + first, n, g->small_max_npiv, g->small_max_f, lds, cls, g->stream); });
-}
-// the shared top of a sharded plan with workgroup fronts: contributions (mode 1), the top from the exchange (mode 2), its backward solve
-static void enqueue_shared_big(gs_graph *g, int what) {
-    if (!ensure_big_tables(g)) return;
-    const bool tree = g->d.tree != 0;
-    if (what == 1) for_each_run(g->segs_c, true, [&](int first, int n, size_t lds, int cls) { launch_factor_tab(g->d, g->d_wgs_c + first, n, 0, lds, cls, g->stream, 1); });
-    else if (what == 2) for_each_run(g->segs_t, tree, [&](int first, int n, size_t lds, int cls) { launch_factor_tab(g->d, g->d_wgs_t + first, n, 0, lds, cls, g->stream, 2); });
-    else for_each_run(g->segs_b, tree, [&](int first, int n, size_t lds, int cls) { launch_backsolve_tab(g->d, g->d_wgs_b + first, n, g->small_max_npiv, g->small_max_f, lds, cls, g->stream); });
-}
-static void enqueue_factor_levels(gs_graph *g, const gs_graph::LevelSet &ls, int base, int mode) {
-    const int nlev = (int)ls.start.size() - 1;
-    if (g->d.factor_variant == 3 && g->d.tree && mode == 0 && base == 0 && nlev > 0) {     // every own level in one launch
-        ++g->d.epoch;
-        // leaf instance: level 0 only if its fronts really have no children (always true for an elimination tree's level 0)
-        if (g->leaf_n < 0) {                                          // once per plan
-            int n_leaf = ls.start[1], F_leaf_all = 0, slot = 256; g->leaf_max_f = 0;
-            // leaves beyond a wave (the fronts of a level are sorted by size class: the small ones first) go to the table-driven launch
-            for (int q = 0; q < n_leaf; ++q) { const Front &F = g->plan.fronts[g->plan.level_fronts_owned[q]]; if (F.npiv + F.nbnd > 63) { n_leaf = q; break; } }
-            for (int q = 0; q < n_leaf; ++q) { const Front &F = g->plan.fronts[g->plan.level_fronts_owned[q]];
-                g->leaf_max_f = std::max(g->leaf_max_f, F.npiv + F.nbnd);
-                if (F.child_cnt != 0) { n_leaf = 0; break; }
-                slot = std::max(slot, (((F.npiv + F.nbnd + 1) | 1) * F.npiv + 1) & ~1); }
-            F_leaf_all = n_leaf;                                        // GS_LEAF_KERNEL=2: leaf launches whatever their number
-            // few leaves (all resident at once anyway: <= GS_LEAF_MIN, default 2048): no separate leaf launches, the whole-tree
-            // launches take level 0 as well — two kernel boundaries less per iteration (cfg1-cfg3: 6-11 % of it)
-            if (n_leaf <= g->opt.leaf_min) n_leaf = 0;
-            if (g->opt.leaf_kernel == 0) n_leaf = 0; else if (g->opt.leaf_kernel == 2) n_leaf = F_leaf_all;
-            g->leaf_n = n_leaf; g->leaf_slot = slot;
-            // the bottom subtrees (k_factor3_sub): every level-1 front of this rank with the leaves below it in one workgroup — their update
-            // matrices never leave the chip.  Taken when the leaf instance is in use, the plan put the leaves under
-            // level-1 fronts behind the others (gs_plan.cpp) and the workgroup's LDS fits; the leaf launch then covers positions [0, sub_free).
-            g->sub_n = 0; g->sub_first = 0; g->sub_free = n_leaf;
-            if (g->opt.subtree != 0 && n_leaf > 0 && n_leaf == ls.start[1] && g->plan.max_front <= 63 && nlev >= 2 &&
-                factor_sub_lds_bytes(slot) <= (size_t)160 * 1024) {
-                const Plan &P = g->plan; const auto &lfo = P.level_fronts_owned;
-                auto under = [&](int s) { const int pa = P.fronts[s].parent; return pa >= 0 && P.fronts[pa].level == 1 && g->pos_of_front[pa] >= ls.start[1] && g->pos_of_front[pa] < ls.start[2]; };
-                int nfree = 0; while (nfree < n_leaf && !under(lfo[nfree])) ++nfree;
-                bool ok = true; int64_t kids = 0;
-                for (int q = nfree; q < n_leaf && ok; ++q) ok = under(lfo[q]);
-                for (int q = ls.start[1]; q < ls.start[2] && ok; ++q) { const Front &F = P.fronts[lfo[q]]; kids += F.child_cnt;
-                    for (int c = 0; c < F.child_cnt && ok; ++c) { const int cp = g->pos_of_front[P.children[F.child_off + c]]; ok = cp >= nfree && cp < n_leaf; } }
-                if (ok && kids == n_leaf - nfree && ls.start[2] > ls.start[1]) { g->sub_first = ls.start[1]; g->sub_n = ls.start[2] - ls.start[1]; g->sub_free = nfree; } } }
-        // the upper levels — few fronts, all of them in the dependent chain — get four waves per front: whole levels from the
-        // top down while a level has at most GS_BLOCK_FRONTS (512) fronts (those workgroups are all resident at once)
-        if (g->block_n < 0) { const int thr = g->opt.block_fronts;
-            int nb = 0;
-            const int lowest = g->sub_n > 0 ? 2 : (g->leaf_n > 0 ? 1 : 0);      // the first level of the flagged launch
-            for (int l = nlev - 1; l >= lowest; --l) { const int nl = ls.start[l + 1] - ls.start[l];
-                if (nl > thr) break;
-                nb += nl; }
-            g->block_n = std::min(nb, ls.start[nlev] - (g->sub_n > 0 ? g->sub_first + g->sub_n : std::max(g->leaf_n, 0))); }
-        if (g->plan.max_front > 63) { enqueue_factor_big(g, ls, true); return; }
-        launch_factor_tree(g->d, g->sub_n > 0 ? g->sub_free : g->leaf_n, g->leaf_slot, g->leaf_max_f, ls.start[nlev], g->block_n, g->sub_first, g->sub_n, g->stream); return; }
-    if (g->d.factor_variant == 3 && !g->d.tree && mode == 0 && base == 0 && nlev > 0 && g->plan.max_front > 63) { ++g->d.epoch; enqueue_factor_big(g, ls, false); return; }
-    if (g->d.factor_variant == 3 && mode == 2 && nlev > 0 && ls.start[nlev] > 0 && g->plan.max_front > 63) { enqueue_shared_big(g, 2); return; }     // ... of a plan with workgroup fronts: table-driven
-    if (g->d.factor_variant == 3 && g->d.tree && mode == 2 && nlev > 0 && ls.start[nlev] > 0) {     // the shared top of a sharded graph, one flagged launch
-        launch_factor_tree_top(g->d, base, ls.start[nlev], g->stream); return; }
-    for (int l = 0; l < nlev; ++l)
-        launch_factor_level(g->d, base + ls.start[l], ls.start[l + 1] - ls.start[l], ls.max_f[l], mode, g->stream);
-}
-static void enqueue_backsolve_levels(gs_graph *g, const gs_graph::LevelSet &ls, int base) {
-    const int nlev = (int)ls.start.size() - 1;
-    if (g->d.factor_variant == 3 && base == 0 && nlev > 0 && g->plan.max_front > 63) { enqueue_backsolve_big(g, ls, g->d.tree != 0); return; }
-    if (g->d.factor_variant == 3 && base != 0 && nlev > 0 && ls.start[nlev] > 0 && g->plan.max_front > 63) { enqueue_shared_big(g, 3); return; }
-    if (g->d.factor_variant == 3 && g->d.tree && base == 0 && nlev > 0) {
-        // levels >= 1 in one launch (fronts wait for their parent's flag), then the leaf level on its own: by then every
-        // parent is done, so it needs no flags, and its LDS slot is sized for the leaves alone (more resident waves)
-        // The flagged launch is register-heavy (each lane preloads its L columns: 2 waves per SIMD) — right for the chain
-        // of the upper levels (2.2 us per level), wrong for the wide levels at the bottom, which are bound by resident
-        // waves x bytes: levels of more than GS_BS_WIDE (2048) fronts run one light launch each, like the leaves
-        // (measured per-level completion times: scripts/level_times.py).
-        const int wide = g->opt.bs_wide;
-        int l0 = 0;
-        if (g->leaf_n != 0) while (l0 + 1 < nlev && ls.start[l0 + 1] - ls.start[l0] > wide) ++l0;
-        if (l0 == 0 && nlev > 1 && g->leaf_n != 0) l0 = 1;
-        int mn = 0, mf = 0; for (int l = l0; l < nlev; ++l) { mn = std::max(mn, ls.max_npiv[l]); mf = std::max(mf, ls.max_f[l]); }
-        launch_backsolve_tree(g->d, ls.start[l0], ls.start[nlev] - ls.start[l0], mn, mf, g->stream);
-        for (int l = l0 - 1; l >= 0; --l) launch_backsolve_level(g->d, ls.start[l], ls.start[l + 1] - ls.start[l], ls.max_npiv[l], ls.max_nbnd[l], g->stream);
-        return; }
-    if (g->d.factor_variant == 3 && g->d.tree && base != 0 && nlev > 0 && ls.start[nlev] > 0) {      // shared top: one flagged launch, root first
-        int mn = 0, mf = 0; for (int l = 0; l < nlev; ++l) { mn = std::max(mn, ls.max_npiv[l]); mf = std::max(mf, ls.max_f[l]); }
-        launch_backsolve_tree(g->d, base, ls.start[nlev], mn, mf, g->stream); return; }
-    for (int l = nlev - 1; l >= 0; --l)
-        launch_backsolve_level(g->d, base + ls.start[l], ls.start[l + 1] - ls.start[l], ls.max_npiv[l], ls.max_nbnd[l], g->stream);
-}
-// pose-window shards, first half: linearise this shard's edges, factorise its own subtrees, write its contribution
-// to every shared front into the exchange buffer (the caller all-reduces that buffer: RCCL sum, fp64)
-static void enqueue_local(gs_graph *g, bool timed) {
-    ++g->d.iter;                                                     // kernels see the iteration they belong to (fault injection, gs_debug_fail_at_iteration)
-    if (timed) hipEventRecord(g->ev[0], g->stream);
-    launch_linearize(g->d, g->stream, g->ev_lin[0], g->ev_lin[1]);   // (null outside gs_time_iterations' second pass)
-    launch_linearize_tail(g->d, g->stream);                          // a grown plan's tail (no launch without one)
-    if (timed) hipEventRecord(g->ev[1], g->stream);
-    enqueue_factor_levels(g, g->own, 0, 0);
-    const int nshared = (int)g->plan.level_fronts_shared.size();
-    if (nshared > 0 && g->d.factor_variant == 3 && g->plan.max_front > 63) enqueue_shared_big(g, 1);      // a plan with workgroup fronts: table-driven
-    else if (nshared > 0) { int mf = 0; for (int v : g->shared.max_f) mf = std::max(mf, v);
-        launch_factor_level(g->d, g->shared_base, nshared, mf, 1, g->stream); }
-}
-// second half: the shared top (redundantly on every rank), backward solve top-down, update
-static void enqueue_finish(gs_graph *g, bool timed) {
-    enqueue_factor_levels(g, g->shared, g->shared_base, 2);
-    if (timed) hipEventRecord(g->ev[2], g->stream);
-    enqueue_backsolve_levels(g, g->shared, g->shared_base);
-    enqueue_backsolve_levels(g, g->own, 0);
-    if (timed) hipEventRecord(g->ev[3], g->stream);
-    launch_update(g->d, g->stream);
-    if (timed) hipEventRecord(g->ev[4], g->stream);
-    g->dev_estimates_newer = true;
-}
-static void enqueue_iteration(gs_graph *g, bool timed) { enqueue_local(g, timed); enqueue_finish(g, timed); }
-// a failure of the enqueue itself (not of the arithmetic): reported once by the entry point that enqueued
-static int take_enqueue_error(gs_graph *g) {
-    if (g->enqueue_rc == GS_OK) return GS_OK;
-    const int rc = g->enqueue_rc; g->enqueue_rc = GS_OK;
-    return fail(rc, "solver launch tables: " + g->enqueue_err + " (no update applied)");
-}
-
-extern "C" int gs_iterate(gs_graph *g) {
-    if (!g) return fail(GS_ERR_INVALID, "null graph");
-    if (!g->dev_valid || g->plan_version != g->h.structure_version) return fail(GS_ERR_NOT_INITIALIZED, "call gs_initialize_optimization first");
-    if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: use gs_dist_iterate (RCCL inside the library) or gs_dist_iterate_local / all-reduce / gs_dist_iterate_finish");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    enqueue_iteration(g, false);
-    if (g->enqueue_rc != GS_OK) return take_enqueue_error(g);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return 1;
-}
-
-static void fill_plan_stats(gs_graph *g, gs_stats *s) {
+void fill_plan_stats(gs_graph *g, gs_stats *s) {
     const Plan &P = g->plan;
     s->n_free_poses = 0; s->n_free_landmarks = 0;
     for (auto v : P.pose_gidx) s->n_free_poses += v >= 0;
@@ -1322,7 +1069,7 @@ static void fill_plan_stats(gs_graph *g, gs_stats *s) {
     for (const Front &F : P.fronts) s->n_big_fronts += (!F.opaque && F.npiv + F.nbnd > 63);
     s->device_bytes = (int64_t)g->pool_total; s->ms_plan_host = P.ms_build; s->n_growths = P.n_growths;
     s->n_own_fronts = (int32_t)P.level_fronts_owned.size(); s->n_shared_fronts = (int32_t)P.level_fronts_shared.size();
-    s->n_subtrees = g->leaf_n >= 0 ? g->sub_n : 0;
+    s->n_subtrees = g->sched.sub_n;
 }
 
 extern "C" int gs_get_stats(gs_graph *g, gs_stats *s) {
@@ -1330,1151 +1077,5 @@ extern "C" int gs_get_stats(gs_graph *g, gs_stats *s) {
     if (!g->plan.valid) return fail(GS_ERR_NOT_INITIALIZED, "no plan built");
     std::memset(s, 0, sizeof(*s)); s->struct_size = (int32_t)sizeof(*s);
     fill_plan_stats(g, s);
-    return GS_OK;
-}
-
-// a whole-tree launch gave up on a front's flag: one launch per level from now on; a retry of the whole-tree launches that ends this way
-// waits four times longer before the next one (gs_optimize, gs_compute_marginals)
-static void fall_back_to_levels(gs_graph *g) {
-    if (g->fallback_retrying) { g->fallback_retrying = false; g->fallback_retry_after = std::min(g->fallback_retry_after * 4, 1024); }
-    g->fallback_calls = 0;
-    g->d.tree = 0; g->fell_back = true;
-}
-// gs_optimize (rel_tol < 0: the reference's fixed iteration count) and gs_optimize_until (rel_tol >= 0: the stop rule)
-static int optimize_impl(gs_graph *g, int32_t iterations, double rel_tol, gs_stats *stats) {
-    if (!g) return fail(GS_ERR_INVALID, "null graph");
-    if (iterations < 0) return fail(GS_ERR_INVALID, "negative iteration count");
-    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: use gs_dist_optimize (RCCL inside the library), or drive gs_dist_iterate_local / all-reduce / gs_dist_iterate_finish");
-    // g2o: optimize() is always preceded by initializeOptimization() (reference src/slam.cpp:480-481);
-    // the plan is rebuilt only when the structure changed since the last call.
-    int rc = ensure_ready(g); if (rc != GS_OK) return rc;
-    // A handle that fell back to one launch per level (a whole-tree launch gave up on a front's flag) does not stay there until the next plan:
-    // what makes a flag late — the chip shared with another process, a debugger, a profiler replaying kernels — passes.  After 4 calls on the
-    // slow path the whole-tree launches are tried again (first iteration on its own, like a new plan's); another timeout quadruples the wait
-    // (16, 64, ... 1024 calls), a clean launch ends the episode.
-    if (g->fell_back && iterations > 0 && g->opt.tree != 0 && !g->d.tree && ++g->fallback_calls >= g->fallback_retry_after) {
-        g->d.tree = 1; g->tree_proven = false; g->fallback_calls = 0; g->fallback_retrying = true; }
-    { const int ii = g->d.inject_iter, ic = g->d.inject_code;       // an armed fault injection survives the reset below
-      HIP_TRY(hipMemsetAsync(g->d.fail, 0, 4 * sizeof(int32_t), g->stream)); g->d.inject_iter = ii; g->d.inject_code = ic; }
-    const bool until = rel_tol >= 0.0;
-    g->d.conv_tol = until ? rel_tol : -1.0;
-    if (until) { const double none = -1.0; HIP_TRY(hipMemcpyAsync(g->d.chi2 + 70, &none, sizeof(double), hipMemcpyHostToDevice, g->stream)); }
-    hipEventRecord(g->ev[5], g->stream);
-    const int nh = std::min(iterations, 64);
-    // All iterations are enqueued up front (no host round trip between them).  g2o leaves its loop at the first failed
-    // solve and keeps the previous iterate: k_update applies nothing once the failure flag is up, and fail[1] says how
-    // many updates went in.  A flag timeout of a whole-tree launch (code 2) is not a property of H: the handle falls
-    // back to one launch per level and runs the remaining iterations again from the last good iterate.
-    // Stop rule (gs_optimize_until): k_update compares the chi2 of consecutive linearisation points on the device and
-    // raises fail[2]; later updates are skipped like after a failure.  The host enqueues chunks of 4 iterations and
-    // looks at the flags in between, so at most 3 enqueued iterations run as no-ops after convergence.
-    // Chunks: the FIRST iteration on its own, then groups of 8 — a remainder of up to 12 in one — (stop rule: 4).  A whole-tree launch whose flag hand-off fails
-    // (its pollers are bounded and leave at once when any front has reported a failure, so such a launch drains in one poll
-    // budget, ~30 ms) would otherwise have every remaining iteration queued up behind it, each paying the same again: with
-    // chunks a timeout costs one chunk before the per-level fallback takes over.  One host round trip per chunk.
-    int applied = 0, enq = 0, first_failure = 0; int32_t ff[4] = {0, 0, 0, 0}; bool fell_back = false;
-    while (enq < iterations) {
-        // (a remainder of up to 12 goes out as one chunk: the reference's optimize(10) is 1 + 9, two host round trips instead of three)
-        // (the FIRST iteration goes out alone only until a whole-tree launch of THIS plan has come back clean once: the flag hand-off
-        // depends on the launch geometry, not on the numbers — a repeated optimize(10), the reference's quirk path, is one host round trip)
-        const bool alone = enq == 0 && !(g->tree_proven && g->d.tree);
-        const int upto = std::min(iterations, alone ? 1 : (until ? enq + 4 : (iterations - enq <= 12 ? iterations : enq + 8)));
-        for (int it = enq; it < upto; ++it) {
-            g->d.hist_slot = it < nh ? it : -1;                      // k_update files the chi2 of this iteration's linearisation point itself
-            enqueue_iteration(g, false);
-        }
-        g->d.hist_slot = -1;
-        if (g->enqueue_rc != GS_OK) { g->d.conv_tol = -1.0; hipStreamSynchronize(g->stream); reset_failure(g); return take_enqueue_error(g); }
-        enq = upto;
-        HIP_TRY(hipMemcpyAsync(ff, g->d.fail, sizeof(ff), hipMemcpyDeviceToHost, g->stream));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        applied = ff[1];
-        if (ff[0] == 0 && g->d.tree) { g->tree_proven = true;
-            if (g->fallback_retrying) { g->fallback_retrying = false; g->fell_back = false; g->fallback_retry_after = 4; } }     // back on the whole-tree launches
-        if (ff[0] != 0 && first_failure == 0) first_failure = ff[0];
-        if (ff[0] == 2 && g->d.tree && !fell_back) {
-            fall_back_to_levels(g);
-            fell_back = true; g->d.inject_iter = 0;
-            HIP_TRY(hipMemsetAsync(g->d.fail, 0, sizeof(int32_t), g->stream));      // the code only: the update count goes on
-            enq = applied; ff[0] = 0; continue; }
-        if (ff[0] != 0 || ff[2] != 0) break;
-    }
-    g->d.conv_tol = -1.0;
-    if (until) HIP_TRY(hipMemsetAsync(g->d.fail + 2, 0, sizeof(int32_t), g->stream));     // the stop flag must not gate later gs_iterate calls
-    const int nshow = std::min(applied, nh);
-    if (g->cfg.verbose || stats) { launch_chi2_only(g->d, g->stream);
-        hipMemcpyAsync(g->d.chi2 + 1 + nh, g->d.chi2, sizeof(double), hipMemcpyDeviceToDevice, g->stream); }
-    hipEventRecord(g->ev[6], g->stream);
-    double hist[80];
-    HIP_TRY(hipMemcpyAsync(hist, g->d.chi2, sizeof(hist), hipMemcpyDeviceToHost, g->stream));
-    // the estimates come back with the same wait (on failure: the last good iterate, what g2o's vertices hold)
-    const bool pull = g->dev_valid && g->dev_estimates_newer;
-    if (pull) { const size_t Np = (size_t)(g->d.N + g->d.tN), Mp = (size_t)(g->d.M + g->d.tM);
-        if (Np) HIP_TRY(hipMemcpyAsync(g->h.pose_est.data(), g->d.pose_est, Np * 3 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-        if (Mp) HIP_TRY(hipMemcpyAsync(g->h.lm_est.data(), g->d.lm_est, Mp * 2 * sizeof(double), hipMemcpyDeviceToHost, g->stream)); }
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    if (pull) g->dev_estimates_newer = false;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { reset_failure(g); return fail(GS_ERR_HIP, std::string("iteration: ") + hipGetErrorString(e)); }      // (a launch that never ran: the ticket counter and its running sum start again)
-    float ms = 0; hipEventElapsedTime(&ms, g->ev[5], g->ev[6]);
-    if (g->cfg.verbose) for (int it = 0; it < nshow; ++it)  // g2o prints the chi2 AFTER the update of iteration it
-        std::fprintf(stderr, "iteration= %d\t chi2= %.6f\t edges= %d\t schur= 0\n", it, it + 1 < applied ? hist[2 + it] : hist[1 + nh], g->h.n_pp() + g->h.n_pl());
-    if (stats) { std::memset(stats, 0, sizeof(*stats)); stats->struct_size = (int32_t)sizeof(*stats);
-        fill_plan_stats(g, stats); stats->iterations = applied; stats->numeric_failure = ff[0]; stats->first_failure = first_failure;
-        stats->chi2_initial = iterations > 0 ? hist[1] : hist[1 + nh]; stats->chi2_final = hist[1 + nh]; stats->ms_total = ms; }
-    if (ff[0]) { rc = reset_failure(g); if (rc != GS_OK) return rc; }
-    if (ff[0] == 2) { g_last_error = "a front's completion flag did not arrive in time, with one launch per level as well"; return 0; }
-    if (ff[0]) { g_last_error = "zero pivot: H is singular (g2o: optimize() returns 0, the vertices keep the last good iterate)"; return 0; }
-    return applied;
-}
-extern "C" int gs_optimize(gs_graph *g, int32_t iterations, gs_stats *stats) { return optimize_impl(g, iterations, -1.0, stats); }
-extern "C" int gs_optimize_until(gs_graph *g, int32_t max_iterations, double rel_chi2_tol, gs_stats *stats) {
-    if (!(rel_chi2_tol >= 0.0)) return fail(GS_ERR_INVALID, "rel_chi2_tol must be >= 0");
-    return optimize_impl(g, max_iterations, rel_chi2_tol, stats);
-}
-
-// ------------------------------------------------------------------ Levenberg-Marquardt (gs_lm.hpp: trial sequence, device record)
-extern "C" int gs_lm_params_default(gs_lm_params *p) {
-    if (!p) return fail(GS_ERR_INVALID, "null params");
-    std::memset(p, 0, sizeof(*p));
-    p->struct_size = (int32_t)sizeof(*p); p->max_trials_after_failure = 10; p->initial_lambda = 0.0; p->tau = 1e-5;
-    return GS_OK;
-}
-// the handle's LM buffers: one allocation of its own (not pool memory: it outlives the plans), grow-only
-static int lm_reserve(gs_graph *g) {
-    auto &W = g->lm; const size_t NP = (size_t)(g->d.N + g->d.tN), ML = (size_t)(g->d.M + g->d.tM);
-    const size_t np = (size_t)lm_grid(g->d);
-    if (!W.mem || NP > W.cap_p || ML > W.cap_l) {
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        if (W.mem) { hipFree(W.mem); W.mem = nullptr; }
-        const size_t cp = NP + 64, cl = ML + 64, cpart = (cp + cl + 255) / 256 + 1;
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t o_state = 0, o_hc = al(2 * sizeof(LmState)), o_hl = o_hc + al(64 * 8), o_ht = o_hl + al(64 * 8), o_bp = o_ht + al(64 * 4),
-                     o_bc = o_bp + al(cp * 24), o_bl = o_bc + al(cp * 16), o_part = o_bl + al(cl * 16), total = o_part + al(cpart * 8);
-        HIP_TRY(hipMalloc(&W.mem, total));
-        char *b = (char *)W.mem;
-        W.dev.state = (LmState *)(b + o_state); W.dev.hist_chi2 = (double *)(b + o_hc); W.dev.hist_lambda = (double *)(b + o_hl); W.dev.hist_trials = (int32_t *)(b + o_ht);
-        W.dev.base_pose = (double *)(b + o_bp); W.dev.base_cs = (double *)(b + o_bc); W.dev.base_lm = (double *)(b + o_bl); W.dev.part = (double *)(b + o_part);
-        W.cap_p = cp; W.cap_l = cl; }
-    W.dev.n_part = (int32_t)np;
-    return GS_OK;
-}
-// one trial, asynchronous: today's linearise / factor / back-solve / update launches in today's launch modes, with the LM kernels around them
-static void enqueue_lm_trial(gs_graph *g, int par, bool init) {
-    const LmDev &lm = g->lm.dev;
-    ++g->d.iter;
-    launch_linearize(g->d, g->stream);
-    launch_linearize_tail(g->d, g->stream);
-    if (init) launch_lm_maxdiag(g->d, lm, g->stream);
-    launch_lm_damp(g->d, lm, par, init ? 1 : 0, g->stream);
-    enqueue_factor_levels(g, g->own, 0, 0);
-    enqueue_finish(g, false);                                        // (no shared top on a single device), back-solve, update
-    launch_lm_scale(g->d, lm, par, g->stream);
-    launch_chi2_only(g->d, g->stream);                               // chi2 at x_try -> chi2[0]
-    launch_lm_step(g->d, lm, par, g->stream);
-}
-extern "C" int gs_optimize_lm(gs_graph *g, int32_t iterations, const gs_lm_params *params, gs_stats *stats, gs_lm_info *info) {
-    if (!g) return fail(GS_ERR_INVALID, "null graph");
-    if (iterations < 0) return fail(GS_ERR_INVALID, "negative iteration count");
-    gs_lm_params P; gs_lm_params_default(&P);
-    if (params) { std::memcpy(&P, params, std::min<size_t>(sizeof(P), (size_t)std::max(params->struct_size, 0))); P.struct_size = (int32_t)sizeof(P); }
-    if (!std::isfinite(P.tau) || !(P.tau > 0.0)) return fail(GS_ERR_INVALID, "gs_lm_params.tau must be finite and > 0");
-    if (!std::isfinite(P.initial_lambda)) return fail(GS_ERR_INVALID, "gs_lm_params.initial_lambda must be finite (<= 0: tau * max diag(H))");
-    if (P.max_trials_after_failure < 1) return fail(GS_ERR_INVALID, "gs_lm_params.max_trials_after_failure must be >= 1");
-    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: Levenberg-Marquardt is not supported on sharded handles");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    rc = ensure_ready(g); if (rc != GS_OK) return rc;
-    if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: Levenberg-Marquardt is not supported on sharded handles");
-    rc = lm_reserve(g); if (rc != GS_OK) return rc;
-    if (g->fell_back && iterations > 0 && g->opt.tree != 0 && !g->d.tree && ++g->fallback_calls >= g->fallback_retry_after) {      // as gs_optimize: try the whole-tree launches again
-        g->d.tree = 1; g->tree_proven = false; g->fallback_calls = 0; g->fallback_retrying = true; }
-    { const int ii = g->d.inject_iter, ic = g->d.inject_code;       // an armed fault injection survives the reset
-      HIP_TRY(hipMemsetAsync(g->d.fail, 0, 4 * sizeof(int32_t), g->stream)); g->d.inject_iter = ii; g->d.inject_code = ic; }
-    g->d.conv_tol = -1.0; g->d.hist_slot = -1;
-    LmState *H = g->lm.host; std::memset(H, 0, 2 * sizeof(LmState));
-    LmState &S0 = H[0];
-    S0.lambda = P.initial_lambda > 0.0 ? P.initial_lambda : 0.0; S0.lambda_initial = S0.lambda; S0.nu = 2.0; S0.tau = P.tau;
-    S0.budget = iterations; S0.max_trials = P.max_trials_after_failure; S0.need_lambda = P.initial_lambda > 0.0 ? 0 : 1;
-    HIP_TRY(hipMemcpyAsync(g->lm.dev.state, H, 2 * sizeof(LmState), hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemsetAsync(g->lm.dev.hist_chi2, 0, 64 * sizeof(double), g->stream));
-    HIP_TRY(hipMemsetAsync(g->lm.dev.hist_lambda, 0, 64 * sizeof(double), g->stream));
-    HIP_TRY(hipMemsetAsync(g->lm.dev.hist_trials, 0, 64 * sizeof(int32_t), g->stream));
-    hipEventRecord(g->ev[5], g->stream);
-    // Chunks of trials, the device record read in between (one host round trip per chunk).  Never more trials than iterations still
-    // to accept — each needs one at least —, so the only trials that run as no-ops are the ones enqueued behind a "terminate"; the first
-    // trial alone until a whole-tree launch of this plan has come back clean, as in gs_optimize.
-    LmState S = S0; int seq = 0, first_failure = 0; int32_t ff[4] = {0, 0, 0, 0}; bool fell_back = false;
-    while (iterations > 0 && !S.done && S.iterations < iterations) {
-        const bool alone = S.trials == 0 && !(g->tree_proven && g->d.tree);
-        const int n = alone ? 1 : std::min(iterations - S.iterations, 8);
-        for (int k = 0; k < n; ++k, ++seq) enqueue_lm_trial(g, seq & 1, k == 0 && S.trials == 0 && S.need_lambda != 0);
-        if (g->enqueue_rc != GS_OK) { hipStreamSynchronize(g->stream); reset_failure(g); return take_enqueue_error(g); }
-        HIP_TRY(hipMemcpyAsync(ff, g->d.fail, sizeof(ff), hipMemcpyDeviceToHost, g->stream));
-        HIP_TRY(hipMemcpyAsync(&H[1], g->lm.dev.state + (seq & 1), sizeof(LmState), hipMemcpyDeviceToHost, g->stream));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        S = H[1];
-        if (ff[0] == 0 && g->d.tree) { g->tree_proven = true;
-            if (g->fallback_retrying) { g->fallback_retrying = false; g->fell_back = false; g->fallback_retry_after = 4; } }
-        if (ff[0] != 0 && first_failure == 0) first_failure = ff[0];
-        if (ff[0] == 2 && g->d.tree && !fell_back) {                // the trials behind the timeout were no-ops: run them again, one launch per level
-            fall_back_to_levels(g);
-            fell_back = true; g->d.inject_iter = 0;
-            HIP_TRY(hipMemsetAsync(g->d.fail, 0, sizeof(int32_t), g->stream));
-            ff[0] = 0; continue; }
-        if (ff[0] != 0) break;
-    }
-    HIP_TRY(hipMemsetAsync(g->d.fail + 1, 0, 2 * sizeof(int32_t), g->stream));     // the update count and the stop flag must not gate later gs_iterate calls
-    if (S.trials == 0 && (stats || info || g->cfg.verbose)) launch_chi2_only(g->d, g->stream);     // nothing ran: chi2 at the estimates as they are
-    hipEventRecord(g->ev[6], g->stream);
-    double chi_here = 0.0, hc[64], hl[64]; int32_t ht[64];
-    HIP_TRY(hipMemcpyAsync(&chi_here, g->d.chi2, sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipMemcpyAsync(hc, g->lm.dev.hist_chi2, sizeof(hc), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipMemcpyAsync(hl, g->lm.dev.hist_lambda, sizeof(hl), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipMemcpyAsync(ht, g->lm.dev.hist_trials, sizeof(ht), hipMemcpyDeviceToHost, g->stream));
-    const bool pull = g->dev_valid && g->dev_estimates_newer;
-    if (pull) { const size_t Np = (size_t)(g->d.N + g->d.tN), Mp = (size_t)(g->d.M + g->d.tM);
-        if (Np) HIP_TRY(hipMemcpyAsync(g->h.pose_est.data(), g->d.pose_est, Np * 3 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-        if (Mp) HIP_TRY(hipMemcpyAsync(g->h.lm_est.data(), g->d.lm_est, Mp * 2 * sizeof(double), hipMemcpyDeviceToHost, g->stream)); }
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    if (pull) g->dev_estimates_newer = false;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { reset_failure(g); return fail(GS_ERR_HIP, std::string("LM iteration: ") + hipGetErrorString(e)); }
-    float ms = 0; hipEventElapsedTime(&ms, g->ev[5], g->ev[6]);
-    const double chi_first = S.trials > 0 ? hc[0] : chi_here, chi_last = S.trials > 0 ? S.chi_base : chi_here;
-    if (g->cfg.verbose) for (int it = 0; it < std::min(S.iterations, 64); ++it)
-        std::fprintf(stderr, "iteration= %d\t chi2= %.6f\t edges= %d\t schur= 0\t lambda= %.6g\t levenbergIter= %d\n", it,
-                     it + 1 < S.iterations && it + 1 < 64 ? hc[it + 1] : chi_last, g->h.n_pp() + g->h.n_pl(), hl[it], ht[it]);
-    if (stats) { std::memset(stats, 0, sizeof(*stats)); stats->struct_size = (int32_t)sizeof(*stats);
-        fill_plan_stats(g, stats); stats->iterations = S.iterations; stats->numeric_failure = ff[0]; stats->first_failure = first_failure;
-        stats->chi2_initial = chi_first; stats->chi2_final = chi_last; stats->ms_total = ms; }
-    if (info) { std::memset(info, 0, sizeof(*info)); info->struct_size = (int32_t)sizeof(*info);
-        info->iterations = S.iterations; info->trials = S.trials; info->rejected = S.rejected; info->terminated = S.terminated;
-        info->lambda_initial = S.lambda_initial; info->lambda_final = S.lambda;
-        std::memcpy(info->chi2, hc, sizeof(hc)); std::memcpy(info->lambda, hl, sizeof(hl)); std::memcpy(info->n_trials, ht, sizeof(ht)); }
-    if (ff[0]) { rc = reset_failure(g); if (rc != GS_OK) return rc;
-        if (ff[0] == 2) return fail(GS_ERR_TIMEOUT, "a front's completion flag did not arrive in time, with one launch per level as well (estimates = last accepted point)");
-        return fail(GS_ERR_NUMERIC, "a solver failure the step control could not treat as a rejected trial (estimates = last accepted point)"); }
-    return S.iterations;
-}
-
-extern "C" int gs_chi2(gs_graph *g, double *out) {
-    if (!g || !out) return fail(GS_ERR_INVALID, "null argument");
-    int rc = ensure_ready(g); if (rc != GS_OK) return rc;
-    launch_chi2_only(g->d, g->stream);
-    HIP_TRY(hipMemcpyAsync(out, g->d.chi2, sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    return GS_OK;
-}
-
-// ------------------------------------------------------------------ measurement / parity hooks
-extern "C" int gs_linearize(gs_graph *g) {
-    if (!g) return fail(GS_ERR_INVALID, "null graph");
-    int rc = ensure_ready(g); if (rc != GS_OK) return rc;
-    launch_linearize(g->d, g->stream);
-    launch_linearize_tail(g->d, g->stream);
-    launch_linearize_finalize(g->d, g->stream);              // stand-alone pass: materialise H_ll, b_l, chi2 for export
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("linearize: ") + hipGetErrorString(e));
-    return GS_OK;
-}
-extern "C" int gs_time_linearize(gs_graph *g, int32_t reps, double *out_ms) {
-    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
-    int rc = ensure_ready(g); if (rc != GS_OK) return rc;
-    launch_linearize(g->d, g->stream);                       // warm
-    hipEventRecord(g->ev[0], g->stream);
-    for (int r = 0; r < reps; ++r) launch_linearize(g->d, g->stream);
-    hipEventRecord(g->ev[1], g->stream);
-    HIP_TRY(hipEventSynchronize(g->ev[1]));
-    float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
-    *out_ms = (double)ms / reps;
-    return GS_OK;
-}
-extern "C" int gs_debug_front_times(gs_graph *g, int64_t *out, int64_t capacity) {
-    if (!g || !out) return fail(GS_ERR_INVALID, "null argument");
-    if (!g->dev_valid) return fail(GS_ERR_NOT_INITIALIZED, "nothing on the device yet");
-    const int64_t n = 2 * (int64_t)g->plan.fronts.size();
-    if (capacity < n) return fail(GS_ERR_CAPACITY, "buffer too small");
-    HIP_TRY(hipMemcpyAsync(out, g->d.done_ts, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    return (int)(n / 2);
-}
-extern "C" int gs_debug_timestamps(gs_graph *g, int64_t *out64) {
-    if (!g || !out64) return fail(GS_ERR_INVALID, "null argument");
-    if (!g->dev_valid) return fail(GS_ERR_NOT_INITIALIZED, "nothing on the device yet");
-    HIP_TRY(hipMemcpyAsync(out64, g->d.dbg_ts, 64 * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    return GS_OK;
-}
-extern "C" int64_t gs_linearize_bytes(gs_graph *g) {
-    if (!g) return 0;
-    return (int64_t)g->h.n_pp() * 152 + (int64_t)g->h.n_pl() * 96 + (int64_t)g->h.n_poses() * 120 + (int64_t)g->h.n_lms() * 64;
-}
-extern "C" int gs_export_system(gs_graph *g, double *Hpp_diag, double *Hll_diag, double *Hpp_off, double *Hpl,
-                                double *b_pose, double *b_lm, int32_t *pp_order, int32_t *pl_order) {
-    if (!g) return fail(GS_ERR_INVALID, "null graph");
-    if (!g->dev_valid) return fail(GS_ERR_NOT_INITIALIZED, "nothing linearised yet");
-    if (g->d.tN > 0) return fail(GS_ERR_INVALID, "the plan has grown by appended poses: their blocks live in the tail arenas, which this export does not read (gs_initialize_optimization with GS_GROW=0 rebuilds)");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    const DevGraph &d = g->d;
-    // an iteration and gs_compute_marginals leave the landmark blocks as per-edge partials (the fronts sum them): sum them here, so
-    // that H_ll and b_l are those of the last linearisation whichever call ran it
-    launch_linearize_finalize(d, g->stream, false);
-    { const hipError_t e = hipGetLastError(); if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("export: ") + hipGetErrorString(e)); }
-    // the device keeps these arrays structure-of-arrays (and the diagonal blocks packed symmetric); the
-    // export format is array-of-blocks, full and row-major
-    const size_t N = (size_t)d.N, M = (size_t)d.M, Epp = (size_t)d.Epp, Epl = (size_t)d.Epl;
-    const size_t L = (size_t)d.ell_len;
-    std::vector<double> t0(N * 6), t1(M * 3), t2(Epp * 9), t3(L * 6), t4(N * 3), t5(M * 2);
-    auto dl = [&](std::vector<double> &dst, const double *src) -> hipError_t {
-        return dst.empty() ? hipSuccess : hipMemcpyAsync(dst.data(), src, dst.size() * sizeof(double), hipMemcpyDeviceToHost, g->stream); };
-    HIP_TRY(dl(t0, d.Hpp_diag)); HIP_TRY(dl(t1, d.Hll_diag)); HIP_TRY(dl(t2, d.Hpp_off)); HIP_TRY(dl(t3, d.Hpl));
-    HIP_TRY(dl(t4, d.b_pose)); HIP_TRY(dl(t5, d.b_lm));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    static const int sym3[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}}, sym2[2][2] = {{0, 1}, {1, 2}};
-    if (Hpp_diag) for (size_t p = 0; p < N; ++p) for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) Hpp_diag[9 * p + 3 * r + c] = t0[sym3[r][c] * N + p];
-    if (Hll_diag) for (size_t l = 0; l < M; ++l) for (int r = 0; r < 2; ++r) for (int c = 0; c < 2; ++c) Hll_diag[4 * l + 2 * r + c] = t1[sym2[r][c] * M + l];
-    if (Hpp_off) for (size_t k = 0; k < Epp; ++k) for (int c = 0; c < 9; ++c) Hpp_off[9 * k + c] = t2[c * Epp + k];
-    if (Hpl) for (size_t k = 0; k < Epl; ++k) { const int32_t e = g->plan.ell_of_ins[k];                 // insertion order; an edge outside this rank's layout: zeros
-        for (int c = 0; c < 6; ++c) Hpl[6 * k + c] = e >= 0 ? t3[c * L + (size_t)e] : 0.0; }
-    if (b_pose) for (size_t p = 0; p < N; ++p) for (int c = 0; c < 3; ++c) b_pose[3 * p + c] = t4[c * N + p];
-    if (b_lm) for (size_t l = 0; l < M; ++l) for (int c = 0; c < 2; ++c) b_lm[2 * l + c] = t5[c * M + l];
-    if (pp_order) std::memcpy(pp_order, g->plan.pp_order.data(), g->plan.pp_order.size() * sizeof(int32_t));
-    if (pl_order) for (size_t k = 0; k < Epl; ++k) pl_order[k] = (int32_t)k;                 // exported in insertion order
-    return GS_OK;
-}
-// per-edge s = e^T W e and weight at the current estimates (k_edge_chi2).  The index table of the kind's edges goes up with the call
-// (a query, not part of an iteration): endpoints from the host graph, an observation edge's place from the plan — its ELL index,
-// or its tail slot when a growth step appended it
-extern "C" int gs_get_edge_chi2(gs_graph *g, int32_t edge_kind, int32_t capacity, double *out_chi2, double *out_weight) {
-    if (!g) return fail(GS_ERR_INVALID, "null graph");
-    if (edge_kind != GS_EDGE_ODOMETRY && edge_kind != GS_EDGE_OBSERVATION) return fail(GS_ERR_INVALID, "edge kind must be GS_EDGE_ODOMETRY or GS_EDGE_OBSERVATION");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: per-edge chi2 is not supported on sharded handles");
-    rc = ensure_ready(g); if (rc != GS_OK) return rc;
-    if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: per-edge chi2 is not supported on sharded handles");
-    const HostGraph &h = g->h; const Plan &P = g->plan;
-    const bool pp = edge_kind == GS_EDGE_ODOMETRY;
-    const int n = pp ? h.n_pp() : h.n_pl();
-    if ((out_chi2 || out_weight) && capacity < n) return fail(GS_ERR_CAPACITY, "buffer too small");
-    if (n == 0 || (!out_chi2 && !out_weight)) return n;
-    const int per = pp ? 2 : 3;
-    std::vector<int32_t> tab((size_t)n * per);
-    if (pp) for (int k = 0; k < n; ++k) { tab[2 * (size_t)k] = h.pp_i[k]; tab[2 * (size_t)k + 1] = h.pp_j[k]; }
-    else for (int k = 0; k < n; ++k) {
-        int32_t src;
-        if (k < P.base_Epl) { src = P.ell_of_ins[k]; if (src < 0) return fail(GS_ERR_INVALID, "observation edge outside the linearisation layout"); }
-        else { if (k - P.base_Epl >= g->d.tEpl) return fail(GS_ERR_INVALID, "observation edge not on the device"); src = -(k - P.base_Epl) - 1; }
-        tab[3 * (size_t)k] = h.pl_p[k]; tab[3 * (size_t)k + 1] = h.pl_l[k]; tab[3 * (size_t)k + 2] = src; }
-    if (pp && n > g->d.Epp + g->d.tEpp) return fail(GS_ERR_INVALID, "odometry edge not on the device");
-    int32_t *dtab = nullptr; double *dout = nullptr;
-    HIP_TRY(hipMalloc((void **)&dtab, tab.size() * sizeof(int32_t)));
-    if (hipMalloc((void **)&dout, (size_t)n * 2 * sizeof(double)) != hipSuccess) { hipFree(dtab); return fail(GS_ERR_HIP, "hipMalloc failed"); }
-    std::vector<double> out((size_t)n * 2);
-    hipError_t e = hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) { launch_edge_chi2(g->d, edge_kind, n, dtab, dout, g->stream); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(out.data(), dout, out.size() * sizeof(double), hipMemcpyDeviceToHost, g->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream); else hipStreamSynchronize(g->stream);
-    hipFree(dtab); hipFree(dout);
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("edge chi2: ") + hipGetErrorString(e));
-    if (out_chi2) std::memcpy(out_chi2, out.data(), (size_t)n * sizeof(double));
-    if (out_weight) std::memcpy(out_weight, out.data() + n, (size_t)n * sizeof(double));
-    return n;
-}
-extern "C" int gs_export_delta(gs_graph *g, double *dpose, double *dlm) {
-    if (!g) return fail(GS_ERR_INVALID, "null graph");
-    if (!g->dev_valid) return fail(GS_ERR_NOT_INITIALIZED, "no iteration run yet");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (dpose && g->d.N) HIP_TRY(hipMemcpyAsync(dpose, g->d.dpose, (size_t)(g->d.N + g->d.tN) * 3 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    if (dlm && g->d.M) HIP_TRY(hipMemcpyAsync(dlm, g->d.dlm, (size_t)(g->d.M + g->d.tM) * 2 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    return GS_OK;
-}
-extern "C" int gs_time_iterations(gs_graph *g, int32_t reps, gs_stats *s) {
-    if (!g || !s || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
-    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: time the two halves from the caller");
-    int rc = ensure_ready(g); if (rc != GS_OK) return rc;
-    const int N = g->d.N + g->d.tN, M = g->d.M + g->d.tM;
-    double *sp = nullptr, *sl = nullptr;                        // save estimates
-    HIP_TRY(hipMalloc((void **)&sp, std::max<size_t>((size_t)N * 3, 1) * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&sl, std::max<size_t>((size_t)M * 2, 1) * sizeof(double)));
-    hipMemcpyAsync(sp, g->d.pose_est, (size_t)N * 3 * sizeof(double), hipMemcpyDeviceToDevice, g->stream);
-    hipMemcpyAsync(sl, g->d.lm_est, (size_t)M * 2 * sizeof(double), hipMemcpyDeviceToDevice, g->stream);
-    const bool newer = g->dev_estimates_newer;
-    std::memset(s, 0, sizeof(*s)); s->struct_size = (int32_t)sizeof(*s); fill_plan_stats(g, s);
-    enqueue_iteration(g, false);                                 // warm
-    // all repetitions are enqueued back to back like the iterations of gs_optimize (no host round trip in between);
-    // every repetition has its own five phase events plus a sixth right behind the fifth: that empty interval is what
-    // one event boundary costs on this stream (ms_event_overhead), i.e. how much of each phase time is the measurement
-    // ... then `reps` more iterations with a start / stop pair attached to the linearisation kernel's own dispatch (hipExtLaunchKernelGGL):
-    // its begin -> end as a kernel trace reports it, without the hand-over from k_update that the event-to-event interval also holds
-    std::vector<hipEvent_t> evs((size_t)reps * 8);
-    for (auto &e : evs) HIP_TRY(hipEventCreate(&e));
-    hipEvent_t saved[5]; for (int k = 0; k < 5; ++k) saved[k] = g->ev[k];
-    for (int r = 0; r < reps; ++r) {
-        for (int k = 0; k < 5; ++k) g->ev[k] = evs[(size_t)r * 8 + k];
-        enqueue_iteration(g, true);
-        hipEventRecord(evs[(size_t)r * 8 + 5], g->stream);
-    }
-    for (int k = 0; k < 5; ++k) g->ev[k] = saved[k];
-    // second pass, nothing recorded between the phases (a dispatch with events attached lengthens the event-to-event interval
-    // around it by ~10 us: the two measurements do not share iterations)
-    for (int r = 0; r < reps; ++r) {
-        g->ev_lin[0] = evs[(size_t)r * 8 + 6]; g->ev_lin[1] = evs[(size_t)r * 8 + 7];
-        enqueue_iteration(g, false);
-    }
-    g->ev_lin[0] = g->ev_lin[1] = nullptr;
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    double ovh = 0.0, link = 0.0; int nlink = 0;
-    for (int r = 0; r < reps; ++r) { const hipEvent_t *e = &evs[(size_t)r * 8];
-        float a = 0, b = 0, c = 0, dd = 0, o = 0, lk = 0;
-        hipEventElapsedTime(&a, e[0], e[1]); hipEventElapsedTime(&b, e[1], e[2]);
-        hipEventElapsedTime(&c, e[2], e[3]); hipEventElapsedTime(&dd, e[3], e[4]); hipEventElapsedTime(&o, e[4], e[5]);
-        if (hipEventElapsedTime(&lk, e[6], e[7]) == hipSuccess && lk > 0) { link += lk; ++nlink; }     // (the gather path launches several kernels: no pair)
-        s->ms_linearize += a; s->ms_factor += b; s->ms_backsolve += c; s->ms_update += dd; ovh += o; }
-    (void)hipGetLastError();
-    for (auto &e : evs) hipEventDestroy(e);
-    s->ms_linearize /= reps; s->ms_factor /= reps; s->ms_backsolve /= reps; s->ms_update /= reps; s->ms_event_overhead = ovh / reps;
-    s->ms_linearize_kernel = nlink > 0 ? link / nlink : 0.0;
-    s->ms_total = s->ms_linearize + s->ms_factor + s->ms_backsolve + s->ms_update; s->iterations = reps;
-    hipMemcpyAsync(g->d.pose_est, sp, (size_t)N * 3 * sizeof(double), hipMemcpyDeviceToDevice, g->stream);
-    launch_pose_trig(g->d, g->stream);
-    hipMemcpyAsync(g->d.lm_est, sl, (size_t)M * 2 * sizeof(double), hipMemcpyDeviceToDevice, g->stream);
-    int32_t failflag = 0;
-    hipMemcpyAsync(&failflag, g->d.fail, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream);
-    hipMemsetAsync(g->d.fail, 0, sizeof(int32_t), g->stream);
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    hipFree(sp); hipFree(sl);
-    g->dev_estimates_newer = newer; s->numeric_failure = failflag;
-    return GS_OK;
-}
-
-// ------------------------------------------------------------------ front end (A0, A1)
-// Device memory of the front end lives on the handle and only ever grows: the batch calls carve a scratch arena, the
-// per-frame path has pinned staging buffers and a device-resident copy of the map.  Nothing is allocated, freed or
-// synchronised beyond the one wait for the results per call.
-namespace {
-struct Carver {   // carves the handle's grow-only arena (256-byte aligned pieces), valid until the next front-end call
-    gs_graph *g; size_t off = 0;
-    template <class T> T *get(size_t n) { T *p = (T *)(g->fe.arena + off); off += (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255; return p; }
-};
-}
-static int arena_reserve(gs_graph *g, size_t bytes) {
-    if (bytes <= g->fe.arena_bytes) return GS_OK;
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    if (g->fe.arena) { hipFree(g->fe.arena); g->fe.arena = nullptr; g->fe.arena_bytes = 0; }
-    const size_t want = bytes + bytes / 2 + 4096;
-    HIP_TRY(hipMalloc((void **)&g->fe.arena, want));
-    g->fe.arena_bytes = want;
-    return GS_OK;
-}
-static size_t padded(size_t n, size_t elem) { return (std::max<size_t>(n, 1) * elem + 255) & ~(size_t)255; }
-void gs_frontend_release(gs_graph *g) {      // gs_destroy
-    if (g->fe.arena) hipFree(g->fe.arena);
-    if (g->fe.pin_in) hipHostFree(g->fe.pin_in);
-    if (g->fe.pin_out) hipHostFree(g->fe.pin_out);
-    if (g->fe.dev_in) hipFree(g->fe.dev_in);
-    if (g->fe.dev_out) hipFree(g->fe.dev_out);
-    if (g->fe.map_xy) hipFree(g->fe.map_xy);
-    if (g->fe.map_type) hipFree(g->fe.map_type);
-    if (g->fe.pin_map) hipHostFree(g->fe.pin_map);
-    if (g->fe.grid_mem) hipFree(g->fe.grid_mem);
-    if (g->fe.pcs) hipFree(g->fe.pcs);
-    g->fe = gs_graph::FrontEnd();
-}
-
-extern "C" int gs_polar_to_xy_batch(gs_graph *g, int32_t n, const double *az, const double *zen, const double *dist, double *out) {
-    if (!g || n < 0 || (n > 0 && (!az || !zen || !dist || !out))) return fail(GS_ERR_INVALID, "bad argument");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (n == 0) return GS_OK;
-    if ((rc = arena_reserve(g, 3 * padded(n, 8) + padded(2 * (size_t)n, 8))) != GS_OK) return rc;
-    Carver c{g}; double *a = c.get<double>(n), *z = c.get<double>(n), *d = c.get<double>(n), *o = c.get<double>(2 * (size_t)n);
-    HIP_TRY(hipMemcpyAsync(a, az, (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(z, zen, (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(d, dist, (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
-    launch_polar_to_xy(n, a, z, d, g->cfg.lidar_to_cog, o, g->stream);
-    HIP_TRY(hipMemcpyAsync(out, o, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    return GS_OK;
-}
-extern "C" int gs_cone_to_global_batch(gs_graph *g, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs,
-                                       const double *obs, double *out) {
-    if (!g || n < 0 || npose < 0 || (n > 0 && (!poses || !pose_of_obs || !obs || !out))) return fail(GS_ERR_INVALID, "bad argument");
-    for (int i = 0; i < n; ++i) if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (n == 0) return GS_OK;
-    if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded(2 * (size_t)n, 8))) != GS_OK) return rc;
-    Carver c{g}; double *p = c.get<double>(3 * (size_t)npose); int32_t *po = c.get<int32_t>(n);
-    double *ob = c.get<double>(4 * (size_t)n), *o = c.get<double>(2 * (size_t)n);
-    HIP_TRY(hipMemcpyAsync(p, poses, 3 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(po, pose_of_obs, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
-    launch_cone_to_global(n, p, po, ob, g->cfg.lidar_to_cog, o, g->stream);
-    HIP_TRY(hipMemcpyAsync(out, o, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    return GS_OK;
-}
-// the hashed grid of a map that is in device memory: built on the device (launch_grid_build), nothing crosses PCIe, nothing waits
-struct GridBufs { int32_t *count, *start, *cursor, *items; long long buckets; };
-static size_t grid_bytes(int n_map, long long &buckets) {
-    buckets = 4096; while (buckets < 4 * (long long)n_map) buckets <<= 1;      // a power of two >= 4 n_map: mostly empty buckets, L2-resident
-    return 3 * padded((size_t)buckets + 1, 4) + padded((size_t)n_map, 4);
-}
-static GridBufs grid_carve(char *base, int n_map, long long buckets) {
-    GridBufs b; size_t off = 0; auto take = [&](size_t bytes) { char *p = base + off; off += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return p; };
-    b.count = (int32_t *)take(((size_t)buckets + 1) * 4); b.start = (int32_t *)take(((size_t)buckets + 1) * 4);
-    b.cursor = (int32_t *)take(((size_t)buckets + 1) * 4); b.items = (int32_t *)take((size_t)n_map * 4); b.buckets = buckets;
-    return b;
-}
-extern "C" int gs_associate_batch(gs_graph *g, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs, const double *obs,
-                                  int32_t n_map, const double *map_xy, const int32_t *map_type, double thr, double type_tol, int32_t *out) {
-    if (!g || n < 0 || npose < 0 || n_map < 0 || (n > 0 && (!poses || !pose_of_obs || !obs || !out)) || (n_map > 0 && (!map_xy || !map_type)))
-        return fail(GS_ERR_INVALID, "bad argument");
-    for (int i = 0; i < n; ++i) if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (n == 0) return GS_OK;
-    // maps beyond a few LDS tiles go through a hashed uniform grid (cell edge a hair above the threshold, so that every cone
-    // within the threshold sits in the 3 x 3 cells around the query) that is BUILT ON THE DEVICE from the uploaded map; the brute-force
-    // kernel stays for small maps and non-positive thresholds.  gs_debug_options.assoc_grid = 0 / 1 forces either (A/B, tests).
-    bool grid = n_map >= 2048 && thr > 0.0;
-    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && n_map > 0 && thr > 0.0;
-    long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
-    if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded(2 * (size_t)n_map, 8) +
-                               padded(n_map, 4) + padded(n, 4) + gbytes + padded(2 * (size_t)npose, 8))) != GS_OK) return rc;
-    Carver c{g}; double *p = c.get<double>(3 * (size_t)npose); int32_t *po = c.get<int32_t>(n); double *pcs = c.get<double>(2 * (size_t)npose);
-    double *ob = c.get<double>(4 * (size_t)n), *mx = c.get<double>(2 * (size_t)n_map);
-    int32_t *mt = c.get<int32_t>(n_map), *o = c.get<int32_t>(n);
-    HIP_TRY(hipMemcpyAsync(p, poses, 3 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(po, pose_of_obs, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
-    if (n_map > 0) { HIP_TRY(hipMemcpyAsync(mx, map_xy, 2 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream));
-                     HIP_TRY(hipMemcpyAsync(mt, map_type, (size_t)n_map * 4, hipMemcpyHostToDevice, g->stream)); }
-    if (grid) { const GridBufs gb = grid_carve(c.get<char>(gbytes), n_map, buckets);
-        launch_grid_build(n_map, mx, thr, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream);
-        launch_associate_grid_dev(n, p, po, ob, g->cfg.lidar_to_cog, mx, mt, thr, type_tol, buckets, gb.start, gb.items, o, npose, pcs, g->stream);
-    } else launch_associate(n, p, po, ob, g->cfg.lidar_to_cog, n_map, mx, mt, thr, type_tol, o, g->stream);
-    HIP_TRY(hipMemcpyAsync(out, o, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));        // the one wait of the call: the result copy
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("association: ") + hipGetErrorString(e));
-    return GS_OK;
-}
-// A1 batched with EVERYTHING resident: the map of gs_map_append (its grid is built on the device, once per map change or threshold),
-// poses / observations / result in device memory, asynchronous on the handle's stream (the caller waits: gs_stream_synchronize).
-static int resident_grid(gs_graph *g, double thr) {
-    auto &fe = g->fe;
-    if (fe.grid_valid && fe.grid_map_n == fe.map_n && fe.grid_thr == thr) return GS_OK;
-    long long buckets = 0; const size_t bytes = grid_bytes(fe.map_n, buckets) + 5 * 256;
-    if (bytes > fe.grid_bytes) { HIP_TRY(hipStreamSynchronize(g->stream));
-        if (fe.grid_mem) hipFree(fe.grid_mem);
-        fe.grid_mem = nullptr; fe.grid_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&fe.grid_mem, bytes + bytes / 2)); fe.grid_bytes = bytes + bytes / 2; }
-    const GridBufs gb = grid_carve(fe.grid_mem, fe.map_n, buckets);
-    launch_grid_build(fe.map_n, fe.map_xy, thr, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream);
-    fe.grid_valid = true; fe.grid_map_n = fe.map_n; fe.grid_thr = thr; fe.grid_max_cells = buckets;
-    return GS_OK;
-}
-extern "C" int gs_associate_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
-                                     double thr, double type_tol, int32_t *dev_out) {
-    if (!g || n < 0 || npose < 0 || (n > 0 && (!dev_poses || !dev_pose_of_obs || !dev_obs || !dev_out))) return fail(GS_ERR_INVALID, "bad argument");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (n == 0) return GS_OK;
-    auto &fe = g->fe;
-    const bool grid = thr > 0.0 && fe.map_n > 0 && g->opt.assoc_grid != 0;
-    if (grid) { if ((rc = resident_grid(g, thr)) != GS_OK) return rc;
-        if ((size_t)npose * 2 * sizeof(double) > fe.pcs_bytes) { HIP_TRY(hipStreamSynchronize(g->stream));      // scratch for the poses' cos / sin, grow-only
-            if (fe.pcs) hipFree(fe.pcs);
-            fe.pcs = nullptr; fe.pcs_bytes = 0;
-            const size_t want = (size_t)npose * 2 * sizeof(double) * 3 / 2 + 4096;
-            HIP_TRY(hipMalloc((void **)&fe.pcs, want)); fe.pcs_bytes = want; }
-        const GridBufs gb = grid_carve(fe.grid_mem, fe.map_n, fe.grid_max_cells);
-        launch_associate_grid_dev(n, dev_poses, dev_pose_of_obs, dev_obs, g->cfg.lidar_to_cog, fe.map_xy, fe.map_type, thr, type_tol, gb.buckets, gb.start, gb.items, dev_out,
-                                  npose, fe.pcs, g->stream, g->ev_lin[0], g->ev_lin[1]);
-    } else launch_associate(n, dev_poses, dev_pose_of_obs, dev_obs, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, thr, type_tol, dev_out, g->stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("association: ") + hipGetErrorString(e));
-    return GS_OK;
-}
-// bench / profiling hook (graphslam_debug.h): `reps` launches of the resident association, each with a start / stop event pair attached to
-// its dispatch (the kernel's own begin -> end, as for the linearisation kernel); mean milliseconds per launch; the grid is built before
-extern "C" int gs_debug_time_associate_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
-                                                const double *dev_obs, double thr, double type_tol, int32_t *dev_out, int32_t reps, double *out_ms) {
-    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
-    int rc = gs_associate_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, thr, type_tol, dev_out); if (rc != GS_OK) return rc;     // warm (and the grid)
-    std::vector<hipEvent_t> ev(2 * (size_t)reps); for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-    for (int r = 0; r < reps && rc == GS_OK; ++r) { g->ev_lin[0] = ev[2 * (size_t)r]; g->ev_lin[1] = ev[2 * (size_t)r + 1];
-        rc = gs_associate_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, thr, type_tol, dev_out); }
-    g->ev_lin[0] = g->ev_lin[1] = nullptr;
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    double tot = 0; int cnt = 0;
-    for (int r = 0; r < reps; ++r) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]) == hipSuccess && ms > 0) { tot += ms; ++cnt; } }
-    (void)hipGetLastError();
-    for (auto &e : ev) hipEventDestroy(e);
-    *out_ms = cnt ? tot / cnt : 0.0;
-    return rc;
-}
-
-// ---- the per-keyframe path: resident map + one fused launch -------------------------------------------------------
-static int map_reserve(gs_graph *g, int want) {
-    if (want <= g->fe.map_cap) return GS_OK;
-    const int cap = std::max(want + want / 2, 1024);
-    double *xy = nullptr; int32_t *ty = nullptr;
-    HIP_TRY(hipMalloc((void **)&xy, (size_t)cap * 2 * sizeof(double)));
-    HIP_TRY(hipMalloc((void **)&ty, (size_t)cap * sizeof(int32_t)));
-    if (g->fe.map_n > 0) { HIP_TRY(hipMemcpyAsync(xy, g->fe.map_xy, (size_t)g->fe.map_n * 2 * sizeof(double), hipMemcpyDeviceToDevice, g->stream));
-                           HIP_TRY(hipMemcpyAsync(ty, g->fe.map_type, (size_t)g->fe.map_n * sizeof(int32_t), hipMemcpyDeviceToDevice, g->stream)); }
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    if (g->fe.map_xy) hipFree(g->fe.map_xy);
-    if (g->fe.map_type) hipFree(g->fe.map_type);
-    g->fe.map_xy = xy; g->fe.map_type = ty; g->fe.map_cap = cap;
-    return GS_OK;
-}
-static int pin_map_reserve(gs_graph *g, size_t bytes) {
-    if (bytes <= g->fe.pin_map_bytes) return GS_OK;
-    HIP_TRY(hipStreamSynchronize(g->stream));                       // a previous staged copy may still be in flight
-    if (g->fe.pin_map) hipHostFree(g->fe.pin_map);
-    g->fe.pin_map = nullptr; g->fe.pin_map_bytes = 0;
-    const size_t want = std::max<size_t>(bytes + bytes / 2, 1 << 16);
-    HIP_TRY(hipHostMalloc((void **)&g->fe.pin_map, want, hipHostMallocDefault));
-    g->fe.pin_map_bytes = want;
-    return GS_OK;
-}
-extern "C" int gs_map_size(gs_graph *g) { return g ? g->fe.map_n : fail(GS_ERR_INVALID, "null graph"); }
-extern "C" int gs_map_clear(gs_graph *g) { if (!g) return fail(GS_ERR_INVALID, "null graph"); g->fe.map_n = 0; g->fe.grid_valid = false; return GS_OK; }
-extern "C" int gs_map_append(gs_graph *g, int32_t n, const double *xy, const int32_t *type) {
-    if (!g || n < 0 || (n > 0 && (!xy || !type))) return fail(GS_ERR_INVALID, "bad argument");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (n == 0) return GS_OK;
-    if ((rc = map_reserve(g, g->fe.map_n + n)) != GS_OK) return rc;
-    // staged through pinned memory so that the copy is asynchronous; the staging buffer is reused once the stream has passed
-    // it — every gs_frame_frontend call waits for the stream, and two appends without one in between wait here
-    const size_t bx = (size_t)n * 2 * sizeof(double), bt = (size_t)n * sizeof(int32_t);
-    if (g->fe.pin_map_busy) { HIP_TRY(hipStreamSynchronize(g->stream)); g->fe.pin_map_busy = false; }
-    if ((rc = pin_map_reserve(g, bx + bt)) != GS_OK) return rc;
-    std::memcpy(g->fe.pin_map, xy, bx); std::memcpy(g->fe.pin_map + bx, type, bt);
-    HIP_TRY(hipMemcpyAsync(g->fe.map_xy + 2 * (size_t)g->fe.map_n, g->fe.pin_map, bx, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(g->fe.map_type + g->fe.map_n, g->fe.pin_map + bx, bt, hipMemcpyHostToDevice, g->stream));
-    g->fe.pin_map_busy = true;                                      // no wait here: the next frame's launch is ordered behind the copies
-    g->fe.map_n += n; g->fe.grid_valid = false;
-    return GS_OK;
-}
-extern "C" int gs_map_set_xy(gs_graph *g, int32_t first, int32_t n, const double *xy) {
-    if (!g || first < 0 || n < 0 || (n > 0 && !xy)) return fail(GS_ERR_INVALID, "bad argument");
-    if (first + n > g->fe.map_n) return fail(GS_ERR_INVALID, "beyond the end of the map");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (n == 0) return GS_OK;
-    HIP_TRY(hipMemcpyAsync(g->fe.map_xy + 2 * (size_t)first, xy, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));                       // pageable source: the caller's buffer is free on return
-    g->fe.pin_map_busy = false; g->fe.grid_valid = false;
-    return GS_OK;
-}
-extern "C" int gs_frame_frontend(gs_graph *g, const double pose[3], const double *obs, int32_t k, double thr, double type_tol,
-                                 int32_t signed_type, double *out_zxy, double *out_gxy, int32_t *out_idx) {
-    if (!g || !pose || k < 0 || (k > 0 && (!obs || !out_zxy || !out_gxy || !out_idx))) return fail(GS_ERR_INVALID, "bad argument");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (k == 0) return GS_OK;
-    if (k > g->fe.cap_obs) {                                        // grow-only: staging and device buffers for k observations
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        if (g->fe.pin_in) hipHostFree(g->fe.pin_in);
-        if (g->fe.pin_out) hipHostFree(g->fe.pin_out);
-        if (g->fe.dev_in) hipFree(g->fe.dev_in);
-        if (g->fe.dev_out) hipFree(g->fe.dev_out);
-        g->fe.pin_in = nullptr; g->fe.pin_out = nullptr; g->fe.dev_in = nullptr; g->fe.dev_out = nullptr; g->fe.cap_obs = 0;
-        const int cap = std::max(64, k + k / 2);
-        const size_t bin = (3 + 4 * (size_t)cap) * sizeof(double), bout = (size_t)cap * (4 * sizeof(double) + sizeof(int32_t));
-        HIP_TRY(hipHostMalloc((void **)&g->fe.pin_in, bin, hipHostMallocDefault)); HIP_TRY(hipHostMalloc((void **)&g->fe.pin_out, bout, hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&g->fe.dev_in, bin)); HIP_TRY(hipMalloc((void **)&g->fe.dev_out, bout));
-        g->fe.cap_obs = cap;
-    }
-    const size_t bin = (3 + 4 * (size_t)k) * sizeof(double), bz = (size_t)k * 2 * sizeof(double), bi = (size_t)k * sizeof(int32_t);
-    std::memcpy(g->fe.pin_in, pose, 3 * sizeof(double)); std::memcpy(g->fe.pin_in + 3, obs, 4 * (size_t)k * sizeof(double));
-    double *dz = (double *)g->fe.dev_out, *dg = dz + 2 * (size_t)k; int32_t *di = (int32_t *)(dg + 2 * (size_t)k);
-    HIP_TRY(hipMemcpyAsync(g->fe.dev_in, g->fe.pin_in, bin, hipMemcpyHostToDevice, g->stream));
-    launch_frame_frontend(k, g->fe.dev_in, g->cfg.lidar_to_cog, g->fe.map_n, g->fe.map_xy, g->fe.map_type, thr, type_tol, signed_type, dz, dg, di, g->stream);
-    HIP_TRY(hipMemcpyAsync(g->fe.pin_out, g->fe.dev_out, 2 * bz + bi, hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    g->fe.pin_map_busy = false;
-    std::memcpy(out_zxy, g->fe.pin_out, bz); std::memcpy(out_gxy, g->fe.pin_out + bz, bz); std::memcpy(out_idx, g->fe.pin_out + 2 * bz, bi);
-    return GS_OK;
-}
-
-// ------------------------------------------------------------------ multi-GPU
-extern "C" int gs_dist_configure(gs_graph *g, int32_t rank, int32_t world) {
-    if (!g || world < 1 || rank < 0 || rank >= world) return fail(GS_ERR_INVALID, "bad rank/world");
-    if (world > 1 && (g->cfg.odometry_robust_kernel != GS_ROBUST_NONE || g->cfg.observation_robust_kernel != GS_ROBUST_NONE))
-        return fail(GS_ERR_INVALID, "robust kernels are not supported on sharded handles: set GS_ROBUST_NONE on both edge kinds first");
-    g->rank = rank; g->world = world; ++g->h.structure_version; ++g->h.reshape_version;
-    return GS_OK;
-}
-// ---- rank-local ingestion (round 4): a rank need not hold the observation edges of the other windows' interiors
-static void window_starts_of(const gs_graph *g, std::vector<int32_t> &first_pose, std::vector<int32_t> *fp_of_pose = nullptr) {
-    const HostGraph &h = g->h; const int N = h.n_poses(), W = std::max(1, g->world);
-    int nfree = 0; for (int p = 0; p < N; ++p) nfree += !h.pose_fixed[p];
-    first_pose.assign((size_t)W + 1, N);
-    if (fp_of_pose) fp_of_pose->assign((size_t)N, -1);
-    int f = 0, w = 0;
-    for (int p = 0; p < N; ++p) if (!h.pose_fixed[p]) {
-        while (w <= W && (int)(((int64_t)w * nfree + W - 1) / W) == f) first_pose[(size_t)w++] = p;     // (empty windows share a start)
-        if (fp_of_pose) (*fp_of_pose)[(size_t)p] = f;
-        ++f; }
-}
-extern "C" int gs_dist_window_starts(gs_graph *g, int32_t *out_first_pose, int32_t capacity) {
-    if (!g || !out_first_pose) return fail(GS_ERR_INVALID, "null argument");
-    if (capacity < g->world + 1) return fail(GS_ERR_CAPACITY, "gs_dist_window_starts: world + 1 entries are written");
-    std::vector<int32_t> fp; window_starts_of(g, fp);
-    std::memcpy(out_first_pose, fp.data(), fp.size() * sizeof(int32_t));
-    return GS_OK;
-}
-extern "C" int gs_dist_local_landmark_windows(gs_graph *g, uint64_t *seen_interior, uint64_t *seen_first, int32_t n_landmarks) {
-    if (!g || !seen_interior || !seen_first) return fail(GS_ERR_INVALID, "null argument");
-    const HostGraph &h = g->h;
-    if (n_landmarks != h.n_lms()) return fail(GS_ERR_INVALID, "gs_dist_local_landmark_windows: one entry per landmark of the graph");
-    if (g->world > 64) return fail(GS_ERR_INVALID, "landmark windows are 64-bit masks: at most 64 ranks");
-    std::vector<int32_t> first; window_starts_of(g, first);
-    const int r = g->rank; const uint64_t bit = 1ull << r;
-    std::fill(seen_interior, seen_interior + n_landmarks, 0ull); std::fill(seen_first, seen_first + n_landmarks, 0ull);
-    for (size_t k = 0; k < h.pl_p.size(); ++k) { const int p = h.pl_p[k], l = h.pl_l[k];
-        if (h.pose_fixed[p] || h.lm_fixed[l] || p < first[(size_t)r] || p >= first[(size_t)r + 1]) continue;      // this rank's own window only: the ranks' bits are disjoint, their sum is the union
-        if (r >= 1 && p == first[(size_t)r]) seen_first[l] |= bit; else seen_interior[l] |= bit; }
-    return GS_OK;
-}
-extern "C" int gs_dist_set_landmark_windows(gs_graph *g, const uint64_t *seen_interior, const uint64_t *seen_first, int32_t n_landmarks) {
-    if (!g || n_landmarks < 0 || (n_landmarks > 0 && (!seen_interior || !seen_first))) return fail(GS_ERR_INVALID, "bad argument");
-    g->lm_seen_interior.assign(seen_interior, seen_interior + n_landmarks); g->lm_seen_first.assign(seen_first, seen_first + n_landmarks);
-    ++g->h.structure_version; ++g->h.reshape_version;
-    return GS_OK;
-}
-extern "C" int64_t gs_dist_exchange_doubles(gs_graph *g) { return (g && g->plan.valid) ? g->plan.exchange_doubles : 0; }
-extern "C" int gs_dist_set_exchange_buffer(gs_graph *g, void *p) {
-    if (!g) return fail(GS_ERR_INVALID, "null graph");
-    g->exchange = (double *)p; g->exchange_external = p != nullptr;
-    if (g->dev_valid && p) g->d.exchange = (double *)p;        // the previous (own) buffer stays allocated until the next upload
-    return GS_OK;
-}
-static int dist_ready(gs_graph *g) {
-    if (!g) return fail(GS_ERR_INVALID, "null graph");
-    if (!g->dev_valid || g->plan_version != g->h.structure_version) return fail(GS_ERR_NOT_INITIALIZED, "call gs_initialize_optimization first");
-    if (g->plan.dist && !g->d.exchange) return fail(GS_ERR_NOT_INITIALIZED, "no exchange buffer");
-    return ensure_device(g);
-}
-extern "C" int gs_dist_iterate_local(gs_graph *g) {
-    int rc = dist_ready(g); if (rc != GS_OK) return rc;
-    enqueue_local(g, false);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return GS_OK;
-}
-extern "C" int gs_dist_iterate_finish(gs_graph *g) {
-    int rc = dist_ready(g); if (rc != GS_OK) return rc;
-    enqueue_finish(g, false);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return 1;
-}
-// host copies of the exchange buffer (tests; all-reduce over a CPU backend when ranks share one GPU)
-extern "C" int gs_dist_read_exchange(gs_graph *g, double *host) {
-    int rc = dist_ready(g); if (rc != GS_OK) return rc;
-    if (!host) return fail(GS_ERR_INVALID, "null buffer");
-    if (g->plan.exchange_doubles > 0) HIP_TRY(hipMemcpyAsync(host, g->d.exchange, (size_t)g->plan.exchange_doubles * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    return GS_OK;
-}
-extern "C" int gs_dist_write_exchange(gs_graph *g, const double *host) {
-    int rc = dist_ready(g); if (rc != GS_OK) return rc;
-    if (!host) return fail(GS_ERR_INVALID, "null buffer");
-    if (g->plan.exchange_doubles > 0) HIP_TRY(hipMemcpyAsync(g->d.exchange, host, (size_t)g->plan.exchange_doubles * sizeof(double), hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    return GS_OK;
-}
-
-// ---- RCCL inside the library: the host side of the sharded iteration stays C++ (north_star: "Host stays C++ ... RCCL all-reduce over
-// xGMI on the shared-landmark rows").  The RCCL library is resolved at run time — first the copy the process has loaded already (under
-// bench.py: torch's), then the system's — so libgraphslam_hip.so has no link-time dependency on it and a single-GPU consumer never loads it.
-namespace {
-struct RcclApi {
-    void *lib = nullptr;
-    decltype(&ncclGetUniqueId) GetUniqueId = nullptr; decltype(&ncclCommInitRank) CommInitRank = nullptr;
-    decltype(&ncclAllReduce) AllReduce = nullptr; decltype(&ncclCommDestroy) CommDestroy = nullptr;
-    decltype(&ncclGetErrorString) GetErrorString = nullptr; decltype(&ncclCommCount) CommCount = nullptr;
-};
-RcclApi *rccl_api(std::string &err) {
-    static RcclApi api; static bool tried = false; static std::string why;
-    if (!tried) { tried = true;
-        const char *names[] = {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1", "/opt/rocm/lib/librccl.so"};
-        for (const char *n : names) if (!api.lib) api.lib = dlopen(n, RTLD_NOW | RTLD_NOLOAD);     // a copy the process has loaded already
-        for (const char *n : names) if (!api.lib) api.lib = dlopen(n, RTLD_NOW | RTLD_LOCAL);
-        if (!api.lib) why = std::string("librccl.so not found: ") + (dlerror() ? dlerror() : "");
-        else {
-            api.GetUniqueId = (decltype(api.GetUniqueId))dlsym(api.lib, "ncclGetUniqueId"); api.CommInitRank = (decltype(api.CommInitRank))dlsym(api.lib, "ncclCommInitRank");
-            api.AllReduce = (decltype(api.AllReduce))dlsym(api.lib, "ncclAllReduce"); api.CommDestroy = (decltype(api.CommDestroy))dlsym(api.lib, "ncclCommDestroy");
-            api.GetErrorString = (decltype(api.GetErrorString))dlsym(api.lib, "ncclGetErrorString"); api.CommCount = (decltype(api.CommCount))dlsym(api.lib, "ncclCommCount");
-            if (!api.GetUniqueId || !api.CommInitRank || !api.AllReduce || !api.CommDestroy) { why = "librccl.so lacks ncclGetUniqueId / ncclCommInitRank / ncclAllReduce / ncclCommDestroy"; api.lib = nullptr; } } }
-    if (!api.lib) { err = why; return nullptr; }
-    return &api;
-}
-int rccl_fail(RcclApi *R, ncclResult_t rc, const char *what) {
-    return fail(GS_ERR_HIP, std::string(what) + ": " + (R && R->GetErrorString ? R->GetErrorString(rc) : "RCCL error") + " (" + std::to_string((int)rc) + ")");
-}
-}  // namespace
-extern "C" int gs_dist_unique_id(void *out128) {
-    if (!out128) return fail(GS_ERR_INVALID, "null buffer");
-    std::string err; RcclApi *R = rccl_api(err); if (!R) return fail(GS_ERR_NO_DEVICE, err);
-    static_assert(sizeof(ncclUniqueId) == 128, "gs_dist_unique_id hands out NCCL_UNIQUE_ID_BYTES = 128 bytes");
-    ncclUniqueId id; ncclResult_t rc = R->GetUniqueId(&id); if (rc != ncclSuccess) return rccl_fail(R, rc, "ncclGetUniqueId");
-    std::memcpy(out128, &id, sizeof(id)); return GS_OK;
-}
-extern "C" int gs_dist_comm_init(gs_graph *g, const void *unique_id_128, int32_t rank, int32_t world) {
-    if (!g || !unique_id_128 || world < 1 || rank < 0 || rank >= world) return fail(GS_ERR_INVALID, "bad argument");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    std::string err; RcclApi *R = rccl_api(err); if (!R) return fail(GS_ERR_NO_DEVICE, err);
-    if (g->comm && g->own_comm) { R->CommDestroy((ncclComm_t)g->comm); g->comm = nullptr; }
-    ncclUniqueId id; std::memcpy(&id, unique_id_128, sizeof(id));
-    ncclComm_t c = nullptr; ncclResult_t nr = R->CommInitRank(&c, world, id, rank);      // (collective: every rank of the group calls it; the current device is the handle's)
-    if (nr != ncclSuccess) return rccl_fail(R, nr, "ncclCommInitRank");
-    g->comm = c; g->own_comm = true; g->comm_world = world;
-    return GS_OK;
-}
-extern "C" int gs_dist_set_communicator(gs_graph *g, void *nccl_comm) {
-    if (!g) return fail(GS_ERR_INVALID, "null graph");
-    std::string err; RcclApi *R = rccl_api(err); if (!R) return fail(GS_ERR_NO_DEVICE, err);
-    if (g->comm && g->own_comm) R->CommDestroy((ncclComm_t)g->comm);
-    g->comm = nccl_comm; g->own_comm = false; g->comm_world = 0;
-    if (nccl_comm && R->CommCount) { int n = 0; if (R->CommCount((ncclComm_t)nccl_comm, &n) == ncclSuccess) g->comm_world = n; }
-    return GS_OK;
-}
-void gs_dist_comm_release(gs_graph *g) {      // gs_destroy
-    if (!g->comm || !g->own_comm) { g->comm = nullptr; return; }
-    std::string err; if (RcclApi *R = rccl_api(err)) R->CommDestroy((ncclComm_t)g->comm);
-    g->comm = nullptr;
-}
-// the all-reduce of the shared fronts' slots (and of the ranks' failure flags at the buffer's tail), enqueued on the handle's stream
-static int enqueue_allreduce(gs_graph *g) {
-    if (!g->comm) return fail(GS_ERR_NOT_INITIALIZED, "no RCCL communicator: gs_dist_comm_init or gs_dist_set_communicator first");
-    if (g->comm_world > 0 && g->comm_world != g->world) return fail(GS_ERR_INVALID, "the communicator's size differs from gs_dist_configure's world");
-    std::string err; RcclApi *R = rccl_api(err); if (!R) return fail(GS_ERR_NO_DEVICE, err);
-    const int64_t n = g->plan.exchange_doubles;
-    if (n <= 0) return GS_OK;
-    ncclResult_t nr = R->AllReduce(g->d.exchange, g->d.exchange, (size_t)n, ncclDouble, ncclSum, (ncclComm_t)g->comm, g->stream);
-    return nr == ncclSuccess ? GS_OK : rccl_fail(R, nr, "ncclAllReduce");
-}
-// rank-local ingestion without any other channel between the replicas than the library's own communicator: this rank's bits of the landmark windows
-// (from the edges it holds), ncclAllReduce(uint64, sum) — the ranks' bits are disjoint, the sum is the union —, the result handed to the handle
-extern "C" int gs_dist_share_landmark_windows(gs_graph *g) {
-    if (!g) return fail(GS_ERR_INVALID, "null graph");
-    if (!g->comm) return fail(GS_ERR_NOT_INITIALIZED, "no RCCL communicator: gs_dist_comm_init or gs_dist_set_communicator first");
-    if (g->comm_world > 0 && g->comm_world != g->world) return fail(GS_ERR_INVALID, "the communicator's size differs from gs_dist_configure's world");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    std::string err; RcclApi *R = rccl_api(err); if (!R) return fail(GS_ERR_NO_DEVICE, err);
-    const int M = g->h.n_lms();
-    std::vector<uint64_t> m(2 * (size_t)M);
-    if ((rc = gs_dist_local_landmark_windows(g, m.data(), m.data() + M, M)) != GS_OK) return rc;
-    if (M == 0) return gs_dist_set_landmark_windows(g, nullptr, nullptr, 0);
-    uint64_t *dev = nullptr;
-    HIP_TRY(hipMalloc(&dev, m.size() * sizeof(uint64_t)));
-    hipError_t e = hipMemcpyAsync(dev, m.data(), m.size() * sizeof(uint64_t), hipMemcpyHostToDevice, g->stream);
-    ncclResult_t nr = e == hipSuccess ? R->AllReduce(dev, dev, m.size(), ncclUint64, ncclSum, (ncclComm_t)g->comm, g->stream) : ncclSuccess;
-    if (e == hipSuccess && nr == ncclSuccess) e = hipMemcpyAsync(m.data(), dev, m.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, g->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream);
-    hipFree(dev);
-    if (nr != ncclSuccess) return rccl_fail(R, nr, "ncclAllReduce (landmark windows)");
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("landmark windows: ") + hipGetErrorString(e));
-    return gs_dist_set_landmark_windows(g, m.data(), m.data() + M, M);
-}
-extern "C" int gs_dist_iterate(gs_graph *g) {
-    int rc = dist_ready(g); if (rc != GS_OK) return rc;
-    if (!g->plan.dist) return fail(GS_ERR_INVALID, "not a sharded graph: gs_iterate");
-    enqueue_local(g, false);
-    if ((rc = enqueue_allreduce(g)) != GS_OK) return rc;
-    enqueue_finish(g, false);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return 1;
-}
-// measurement hook (graphslam_debug.h): `reps` all-reduces of the exchange buffer back to back on the handle's stream, HIP events around
-// them; mean milliseconds per all-reduce.  Collective: every rank of the communicator calls it.
-extern "C" int gs_debug_time_exchange(gs_graph *g, int32_t reps, double *out_ms) {
-    if (!out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
-    int rc = dist_ready(g); if (rc != GS_OK) return rc;
-    if ((rc = enqueue_allreduce(g)) != GS_OK) return rc;           // warm
-    hipEventRecord(g->ev[0], g->stream);
-    for (int r = 0; r < reps && rc == GS_OK; ++r) rc = enqueue_allreduce(g);
-    hipEventRecord(g->ev[1], g->stream);
-    HIP_TRY(hipEventSynchronize(g->ev[1]));
-    float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
-    *out_ms = (double)ms / reps;
-    return rc;
-}
-// Slam's optimize(10) (reference src/slam.cpp:481) on a sharded graph: every rank makes the same call; g2o's failure rule holds across
-// ranks (a rank's failure flag rides through the all-reduce: no rank applies the update of that iteration or any later one).  Returns the
-// iterations whose update was applied, 0 when any rank's factorisation failed.  The estimates this rank tracks (gs_dist_known) come back.
-extern "C" int gs_dist_optimize(gs_graph *g, int32_t iterations, gs_stats *stats) {
-    if (!g) return fail(GS_ERR_INVALID, "null graph");
-    if (iterations < 0) return fail(GS_ERR_INVALID, "negative iteration count");
-    int rc = ensure_ready(g); if (rc != GS_OK) return rc;
-    if (!g->plan.dist) return fail(GS_ERR_INVALID, "not a sharded graph: gs_optimize");
-    if ((rc = dist_ready(g)) != GS_OK) return rc;
-    HIP_TRY(hipMemsetAsync(g->d.fail, 0, 4 * sizeof(int32_t), g->stream));
-    g->d.conv_tol = -1.0;
-    hipEventRecord(g->ev[5], g->stream);
-    const int nh = std::min(iterations, 64);
-    // A flag timeout on ANY rank (code 2 where it happened, 4 on the others: the same all-reduce tells everybody) is not a property of H: the rank it
-    // happened on switches to one launch per level, every rank runs the iterations that were not applied again — the repair gs_optimize makes on one GPU,
-    // decided identically on every rank (the count of applied updates is the same everywhere).  At most twice per call.
-    int32_t ff[4] = {0, 0, 0, 0}; double hist[80]; int from = 0, first_failure = 0;
-    for (int repair = 0; ; ++repair) {
-        for (int it = from; it < iterations; ++it) {
-            g->d.hist_slot = it < nh ? it : -1;
-            enqueue_local(g, false);
-            if ((rc = enqueue_allreduce(g)) != GS_OK) { g->d.hist_slot = -1; return rc; }
-            enqueue_finish(g, false);
-        }
-        g->d.hist_slot = -1;
-        hipEventRecord(g->ev[6], g->stream);
-        HIP_TRY(hipMemcpyAsync(ff, g->d.fail, sizeof(ff), hipMemcpyDeviceToHost, g->stream));
-        HIP_TRY(hipMemcpyAsync(hist, g->d.chi2, sizeof(hist), hipMemcpyDeviceToHost, g->stream));
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        if (ff[0] != 0 && first_failure == 0) first_failure = ff[0];
-        if ((ff[0] != 2 && ff[0] != 4) || repair >= 2) break;
-        if (ff[0] == 2) { g->d.tree = 0; g->fell_back = true; g->fallback_calls = 0; }
-        // Every rank is here (the code came with the same all-reduce).  A launch that gave up BEHIND the exchange — the shared top, a backward solve — is only
-        // heard of with the NEXT contribution: by then the other ranks have applied an update the rank it happened on has not.  The ranks compare their counts
-        // (one more all-reduce, only in this branch); if they differ the estimates have parted and no re-run can mend that: every rank says so, nobody goes on.
-        { std::string err; RcclApi *R = rccl_api(err); if (!R) return fail(GS_ERR_NO_DEVICE, err);
-          double v[2] = {(double)ff[1], -(double)ff[1]}, *dv = nullptr;
-          HIP_TRY(hipMalloc(&dv, sizeof(v)));
-          hipError_t e2 = hipMemcpyAsync(dv, v, sizeof(v), hipMemcpyHostToDevice, g->stream);
-          ncclResult_t nr = e2 == hipSuccess ? R->AllReduce(dv, dv, 2, ncclDouble, ncclMax, (ncclComm_t)g->comm, g->stream) : ncclSuccess;
-          if (e2 == hipSuccess && nr == ncclSuccess) e2 = hipMemcpyAsync(v, dv, sizeof(v), hipMemcpyDeviceToHost, g->stream);
-          if (e2 == hipSuccess) e2 = hipStreamSynchronize(g->stream);
-          hipFree(dv);
-          if (nr != ncclSuccess) return rccl_fail(R, nr, "ncclAllReduce (applied updates)");
-          if (e2 != hipSuccess) return fail(GS_ERR_HIP, std::string("applied updates: ") + hipGetErrorString(e2));
-          if (v[0] != -v[1]) { reset_failure(g);
-              return fail(GS_ERR_TIMEOUT, "a launch behind the exchange gave up on one rank after the others had applied that iteration's update: the ranks' estimates have parted "
-                                          "(updates applied: " + std::to_string((long long)-v[1]) + " .. " + std::to_string((long long)v[0]) + "); set the estimates again on every rank"); } }
-        g->d.inject_iter = 0;
-        HIP_TRY(hipMemsetAsync(g->d.fail, 0, sizeof(int32_t), g->stream));      // the code only: the update count goes on
-        if (g->d.tickets) { HIP_TRY(hipMemsetAsync(g->d.tickets, 0, 2 * sizeof(uint32_t), g->stream)); g->d.ticket_base = 0; }
-        from = ff[1]; ff[0] = 0;
-    }
-    rc = pull_estimates_if_needed(g); if (rc != GS_OK) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { reset_failure(g); return fail(GS_ERR_HIP, std::string("iteration: ") + hipGetErrorString(e)); }      // (a launch that never ran: the ticket counter and its running sum start again)
-    float ms = 0; hipEventElapsedTime(&ms, g->ev[5], g->ev[6]);
-    if (stats) { std::memset(stats, 0, sizeof(*stats)); stats->struct_size = (int32_t)sizeof(*stats);
-        fill_plan_stats(g, stats); stats->iterations = ff[1]; stats->numeric_failure = ff[0]; stats->first_failure = first_failure;
-        stats->chi2_initial = iterations > 0 ? hist[1] : 0.0; stats->chi2_final = iterations > 0 ? hist[std::min(iterations, nh)] : 0.0;     // THIS rank's edges only (the ranks' sums add up to the graph's)
-        stats->ms_total = ms; }
-    if (ff[0]) { rc = reset_failure(g); if (rc != GS_OK) return rc;
-        if (ff[0] == 2) { g->d.tree = 0; g->fell_back = true; g_last_error = "a front's completion flag did not arrive in time: the handle now uses one launch per level"; }
-        else if (ff[0] == 4) g_last_error = "another rank's whole-tree launch gave up on a front's flag, twice in this call";
-        else g_last_error = ff[0] == 3 ? "another rank met a zero pivot (g2o: optimize() returns 0, the vertices keep the last good iterate)" : "zero pivot: H is singular (g2o: optimize() returns 0, the vertices keep the last good iterate)";
-        return 0; }
-    return ff[1];
-}
-// which vertex estimates this rank tracks (its own subtrees + the shared top), insertion order; a vertex is
-// `primary` on exactly one rank (shared vertices: rank 0), so summing primary-masked estimates over ranks merges them
-extern "C" int gs_dist_known(gs_graph *g, uint8_t *pose_known, uint8_t *lm_known, uint8_t *pose_primary, uint8_t *lm_primary) {
-    if (!g) return fail(GS_ERR_INVALID, "null graph");
-    if (!g->plan.valid) return fail(GS_ERR_NOT_INITIALIZED, "no plan built");
-    const Plan &P = g->plan;
-    auto primary = [&](int gidx, uint8_t known, uint8_t fixed) -> uint8_t {
-        if (fixed || gidx < 0) return P.rank == 0;                      // fixed vertices never move: take them from rank 0
-        if (!known) return 0;
-        // shared <=> known on every rank
-        return 1; };
-    // a shared vertex is known everywhere; make rank 0 its primary holder
-    std::vector<int32_t> front_of_scalar;                              // scalar -> front owner lookup via pivots
-    front_of_scalar.assign(P.n_scalar, 0);
-    for (size_t s = 0; s < P.fronts.size(); ++s) for (int k = 0; k < P.fronts[s].npiv; ++k) front_of_scalar[P.fronts[s].piv0 + k] = P.fronts[s].owner;
-    for (int p = 0; p < g->h.n_poses(); ++p) { const int gi = P.pose_gidx[p]; uint8_t kn = P.pose_known[p], pr = primary(gi, kn, g->h.pose_fixed[p]);
-        if (gi >= 0 && kn && front_of_scalar[gi] < 0) pr = P.rank == 0;
-        if (pose_known) pose_known[p] = kn; if (pose_primary) pose_primary[p] = pr; }
-    for (int l = 0; l < g->h.n_lms(); ++l) { const int gi = P.lm_gidx[l]; uint8_t kn = P.lm_known[l], pr = primary(gi, kn, g->h.lm_fixed[l]);
-        if (gi >= 0 && kn && front_of_scalar[gi] < 0) pr = P.rank == 0;
-        if (lm_known) lm_known[l] = kn; if (lm_primary) lm_primary[l] = pr; }
-    return GS_OK;
-}
-
-// ------------------------------------------------------------------ marginal covariances (gs_compute_marginals)
-// Sigma = H^-1 on the pattern of L by a selected inversion of the multifrontal factor (gs_kernels.hip, k_selinv_panel / k_selinv_big).  The tables
-// (front -> Sigma image, level sizes, output entry -> arena offset) are built on the first call after a structure phase, not in it.
-static int64_t marg_tri(int64_t r) { return r * (r + 1) / 2; }
-// arena offset of Sigma(u, v), u / v scalars in elimination order; -1 when the pair is outside the pattern of L
-static int64_t marg_offset(const gs_graph *g, int u, int v) {
-    const Plan &P = g->plan; const auto &M = g->marg;
-    const int lo = std::min(u, v), hi = std::max(u, v), s = M.front_of[lo];
-    const Front &F = P.fronts[s];
-    int rh;
-    if (hi < F.piv0 + F.npiv) rh = hi - F.piv0;
-    else { const int32_t *b = P.bnd_rows.data() + F.bnd_off, *e = b + F.nbnd, *it = std::lower_bound(b, e, hi);
-        if (it == e || *it != hi) return -1;
-        rh = F.npiv + (int)(it - b); }
-    return M.sig_off[s] + marg_tri(rh) + (lo - F.piv0);
-}
-// offsets of the block Sigma(a, b), a / b = first scalar (-1: fixed vertex -> zeros, offset -1) and size; false: outside the pattern
-static bool marg_block(const gs_graph *g, int ga, int na, int gb, int nb, int64_t *out) {
-    for (int r = 0; r < na; ++r)
-        for (int c = 0; c < nb; ++c) {
-            int64_t o = -1;
-            if (ga >= 0 && gb >= 0) { o = marg_offset(g, ga + r, gb + c); if (o < 0) return false; }
-            out[r * nb + c] = o; }
-    return true;
-}
-template <class T> static int marg_buffer(gs_graph *g, T **ptr, int64_t &cap, int64_t want) {
-    if (*ptr && cap >= want) return GS_OK;
-    const int64_t n = std::max<int64_t>(want + want / 4, 1);        // room for a few growth steps before the next allocation
-    int rc = dev_alloc(g, ptr, (size_t)n); if (rc != GS_OK) return rc;
-    cap = n; return GS_OK;
-}
-static int marg_tables(gs_graph *g) {
-    auto &M = g->marg; const Plan &P = g->plan; const HostGraph &h = g->h;
-    if (M.plan_version == g->plan_version && M.sig) return GS_OK;
-    const int S = (int)P.fronts.size();
-    M.sig_off.assign(S, 0); M.front_of.assign(P.n_scalar, 0);
-    int64_t off = 0;
-    for (int s = 0; s < S; ++s) { const Front &F = P.fronts[s];
-        M.sig_off[s] = off; off += marg_tri(F.npiv + F.nbnd);
-        for (int k = 0; k < F.npiv; ++k) M.front_of[F.piv0 + k] = s; }
-    M.sig_doubles = off;
-    // launch lists: every level from the root down, its fronts split by form (a wave: <= 63 scalars, a workgroup: 64 .. 159, HBM: larger)
-    const int nlev = (int)g->own.start.size() - 1;
-    M.sel_list.clear(); M.sel_launch.clear();
-    for (int l = nlev - 1; l >= 0; --l)
-        for (int form = 0; form < 3; ++form) {
-            const int first = (int)M.sel_list.size(); int max_f = 0;
-            for (int q = g->own.start[l]; q < g->own.start[l + 1]; ++q) {
-                const int s = P.level_fronts_owned[q], fs = P.fronts[s].npiv + P.fronts[s].nbnd;
-                if ((fs <= 63 ? 0 : (fs <= 159 ? 1 : 2)) != form) continue;
-                M.sel_list.push_back(s); max_f = std::max(max_f, fs); }
-            if ((int)M.sel_list.size() > first) M.sel_launch.push_back({first, (int)M.sel_list.size() - first, max_f}); }
-    const int N = h.n_poses(), Ml = h.n_lms(), Epp = h.n_pp(), Epl = h.n_pl();
-    if ((int)P.pose_gidx.size() < N || (int)P.lm_gidx.size() < Ml) return fail(GS_ERR_INVALID, "marginals: the plan does not cover the graph");
-    M.n_out = 9 * (int64_t)N + 4 * (int64_t)Ml + 9 * (int64_t)Epp + 6 * (int64_t)Epl;
-    std::vector<int64_t> tab((size_t)M.n_out);
-    int64_t *t = tab.data(); bool ok = true;
-    for (int p = 0; p < N; ++p, t += 9) ok = marg_block(g, P.pose_gidx[p], 3, P.pose_gidx[p], 3, t) && ok;
-    for (int l = 0; l < Ml; ++l, t += 4) ok = marg_block(g, P.lm_gidx[l], 2, P.lm_gidx[l], 2, t) && ok;
-    for (int k = 0; k < Epp; ++k, t += 9) ok = marg_block(g, P.pose_gidx[h.pp_i[k]], 3, P.pose_gidx[h.pp_j[k]], 3, t) && ok;
-    for (int k = 0; k < Epl; ++k, t += 6) ok = marg_block(g, P.pose_gidx[h.pl_p[k]], 3, P.lm_gidx[h.pl_l[k]], 2, t) && ok;
-    if (!ok) return fail(GS_ERR_INVALID, "marginals: an edge's block lies outside the pattern of the factor (plan inconsistent)");
-    int rc;
-    if ((rc = marg_buffer(g, &M.sig, M.cap_sig, M.sig_doubles)) != GS_OK || (rc = marg_buffer(g, &M.dpiv, M.cap_piv, P.n_scalar)) != GS_OK ||
-        (rc = marg_buffer(g, &M.d_sig_off, M.cap_fronts, S)) != GS_OK || (rc = marg_buffer(g, &M.d_tab, M.cap_out, M.n_out)) != GS_OK ||
-        (rc = marg_buffer(g, &M.d_list, M.cap_list, (int64_t)M.sel_list.size())) != GS_OK) return rc;
-    if ((rc = marg_buffer(g, &M.d_out, M.cap_dout, M.n_out)) != GS_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(M.d_sig_off, M.sig_off.data(), (size_t)S * sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
-    if (!M.sel_list.empty()) HIP_TRY(hipMemcpyAsync(M.d_list, M.sel_list.data(), M.sel_list.size() * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
-    if (M.n_out) HIP_TRY(hipMemcpyAsync(M.d_tab, tab.data(), (size_t)M.n_out * sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));                       // (tab is a host temporary)
-    M.plan_version = g->plan_version;
-    return GS_OK;
-}
-extern "C" int gs_compute_marginals(gs_graph *g, gs_marginals_info *info) {
-    if (!g) return fail(GS_ERR_INVALID, "null graph");
-    g->marg.valid = false;
-    if (info) { std::memset(info, 0, sizeof(*info)); info->struct_size = (int32_t)sizeof(*info); }
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: marginals need the whole factor on one device (not supported on sharded handles)");
-    rc = ensure_ready(g); if (rc != GS_OK) return rc;
-    if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: marginals need the whole factor on one device (not supported on sharded handles)");
-    rc = marg_tables(g); if (rc != GS_OK) return rc;
-    auto &M = g->marg;
-    // the failure state of the iterations is put aside and restored: this call's codes are its own
-    int32_t saved[4] = {0, 0, 0, 0}, ff[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(saved, g->d.fail, sizeof(saved), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    HIP_TRY(hipMemsetAsync(g->d.fail, 0, sizeof(saved), g->stream));
-    const int ii = g->d.inject_iter, ic = g->d.inject_code; g->d.inject_iter = 0;      // (fault injection belongs to the iterations: kept armed for them)
-    g->d.dpiv = M.dpiv;                                             // the LDL^T factor kernels write D (variant 4: L L^T, nothing to capture)
-    hipEventRecord(g->ev[0], g->stream);
-    launch_linearize(g->d, g->stream);
-    launch_linearize_tail(g->d, g->stream);
-    enqueue_factor_levels(g, g->own, 0, 0);
-    hipEventRecord(g->ev[1], g->stream);
-    const int nlev = (int)g->own.start.size() - 1;
-    if (g->enqueue_rc == GS_OK)
-        for (const auto &Lc : M.sel_launch) launch_selinv(g->d, M.d_sig_off, M.sig, M.d_list + Lc.first, Lc.count, Lc.max_f, g->stream);
-    hipEventRecord(g->ev[2], g->stream);
-    launch_sigma_gather(M.n_out, M.d_tab, M.sig, M.d_out, g->stream);
-    hipEventRecord(g->ev[3], g->stream);
-    g->d.dpiv = nullptr;
-    M.out.resize((size_t)M.n_out);
-    if (M.n_out) HIP_TRY(hipMemcpyAsync(M.out.data(), M.d_out, (size_t)M.n_out * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    hipEventRecord(g->ev[4], g->stream);
-    HIP_TRY(hipMemcpyAsync(ff, g->d.fail, sizeof(ff), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    auto rearm = [&]() { g->d.inject_iter = ii; g->d.inject_code = ic; };     // (reset_failure disarms it)
-    if (g->enqueue_rc != GS_OK) { reset_failure(g); rearm(); hipMemcpy(g->d.fail, saved, sizeof(saved), hipMemcpyHostToDevice); return take_enqueue_error(g); }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { reset_failure(g); rearm(); return fail(GS_ERR_HIP, std::string("marginals: ") + hipGetErrorString(e)); }
-    if (ff[0] != 0) { rc = reset_failure(g); rearm(); if (rc != GS_OK) return rc; }
-    rearm();
-    HIP_TRY(hipMemcpyAsync(g->d.fail, saved, sizeof(saved), hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));                       // (saved is on this stack)
-    if (info) {
-        float a = 0, b = 0, c = 0, t = 0;
-        hipEventElapsedTime(&a, g->ev[0], g->ev[1]); hipEventElapsedTime(&b, g->ev[1], g->ev[2]); hipEventElapsedTime(&c, g->ev[2], g->ev[3]); hipEventElapsedTime(&t, g->ev[0], g->ev[4]);
-        info->numeric_failure = ff[0]; info->n_fronts = (int32_t)g->plan.fronts.size(); info->n_levels = nlev;
-        info->sigma_bytes = M.sig_doubles * (int64_t)sizeof(double);
-        info->ms_linearize_factor = a; info->ms_selinv = b; info->ms_extract = c; info->ms_total = t; }
-    if (ff[0] == 2) { if (g->d.tree) fall_back_to_levels(g);
-        return fail(GS_ERR_TIMEOUT, "marginals: a whole-tree launch gave up waiting for a front's flag; the handle now uses one launch per level (call again)"); }
-    if (ff[0] != 0) return fail(GS_ERR_NUMERIC, "marginals: zero pivot, H is singular (no covariances)");
-    M.valid = true; M.structure_version = g->h.structure_version; M.estimate_version = g->h.estimate_version; M.iter = g->d.iter;
-    return GS_OK;
-}
-static int marg_ready(gs_graph *g) {
-    const auto &M = g->marg;
-    if (!M.valid || !g->dev_valid || M.structure_version != g->h.structure_version || M.estimate_version != g->h.estimate_version || M.iter != g->d.iter)
-        return fail(GS_ERR_NOT_INITIALIZED, "no marginals for the current graph and estimates: call gs_compute_marginals (results go stale after an "
-                                            "iteration, gs_set_*_estimate, gs_add_*, a fixed flag or gs_clear)");
-    return GS_OK;
-}
-static int marg_copy(gs_graph *g, int64_t first, int n, int per, int32_t cap, double *out) {
-    int rc = marg_ready(g); if (rc != GS_OK) return rc;
-    if (cap < n) return fail(GS_ERR_CAPACITY, "buffer too small");
-    if (n) std::memcpy(out, g->marg.out.data() + first, (size_t)n * per * sizeof(double));
-    return n;
-}
-extern "C" int gs_get_pose_covariances(gs_graph *g, int32_t cap, int32_t *ids, double *out) {
-    if (!g || !out) return fail(GS_ERR_INVALID, "null argument");
-    const int n = g->h.n_poses();
-    { int rc = marg_copy(g, 0, n, 9, cap, out); if (rc < 0) return rc; }
-    if (ids && n) std::memcpy(ids, g->h.pose_id.data(), (size_t)n * sizeof(int32_t));
-    return n;
-}
-extern "C" int gs_get_landmark_covariances(gs_graph *g, int32_t cap, int32_t *ids, double *out) {
-    if (!g || !out) return fail(GS_ERR_INVALID, "null argument");
-    const int n = g->h.n_lms();
-    { int rc = marg_copy(g, 9 * (int64_t)g->h.n_poses(), n, 4, cap, out); if (rc < 0) return rc; }
-    if (ids && n) std::memcpy(ids, g->h.lm_id.data(), (size_t)n * sizeof(int32_t));
-    return n;
-}
-extern "C" int gs_get_odometry_edge_covariances(gs_graph *g, int32_t cap, double *out) {
-    if (!g || !out) return fail(GS_ERR_INVALID, "null argument");
-    return marg_copy(g, 9 * (int64_t)g->h.n_poses() + 4 * (int64_t)g->h.n_lms(), g->h.n_pp(), 9, cap, out);
-}
-extern "C" int gs_get_observation_edge_covariances(gs_graph *g, int32_t cap, double *out) {
-    if (!g || !out) return fail(GS_ERR_INVALID, "null argument");
-    return marg_copy(g, 9 * (int64_t)g->h.n_poses() + 4 * (int64_t)g->h.n_lms() + 9 * (int64_t)g->h.n_pp(), g->h.n_pl(), 6, cap, out);
-}
-extern "C" int gs_get_covariance_block(gs_graph *g, int32_t kind_a, int32_t id_a, int32_t kind_b, int32_t id_b, double *out) {
-    if (!g || !out) return fail(GS_ERR_INVALID, "null argument");
-    if ((kind_a != 0 && kind_a != 1) || (kind_b != 0 && kind_b != 1)) return fail(GS_ERR_INVALID, "kind must be 0 (pose) or 1 (landmark)");
-    int rc = marg_ready(g); if (rc != GS_OK) return rc;
-    auto vertex = [&](int kind, int32_t id, int &gidx, int &n) -> bool {
-        const auto &ix = kind == 0 ? g->h.pose_index : g->h.lm_index;
-        auto it = ix.find(id); if (it == ix.end()) return false;
-        gidx = kind == 0 ? g->plan.pose_gidx[it->second] : g->plan.lm_gidx[it->second]; n = kind == 0 ? 3 : 2; return true; };
-    int ga, na, gb, nb;
-    if (!vertex(kind_a, id_a, ga, na) || !vertex(kind_b, id_b, gb, nb)) return fail(GS_ERR_UNKNOWN_ID, "unknown vertex id");
-    int64_t off[9];
-    if (!marg_block(g, ga, na, gb, nb, off))
-        return fail(GS_ERR_OUT_OF_PATTERN, "the pair's block lies outside the pattern of the factor (no front holds both vertices): not computed by the selected inversion");
-    rc = ensure_device(g); if (rc != GS_OK) return rc;
-    for (int k = 0; k < na * nb; ++k) {
-        out[k] = 0.0;
-        if (off[k] >= 0) HIP_TRY(hipMemcpyAsync(out + k, g->marg.sig + off[k], sizeof(double), hipMemcpyDeviceToHost, g->stream)); }
-    HIP_TRY(hipStreamSynchronize(g->stream));
     return GS_OK;
 }

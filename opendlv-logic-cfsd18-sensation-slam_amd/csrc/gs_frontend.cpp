@@ -1,0 +1,263 @@
+// gs_frontend.cpp — the front end (A0, A1) of the C-ABI: batch conversions, association, the resident map.
+#include "../../include/graphslam.h"
+#include "../../include/graphslam_debug.h"
+#include "gs_private.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+using namespace gs;
+
+// ------------------------------------------------------------------ front end (A0, A1)
+// Device memory of the front end lives on the handle and only ever grows: the batch calls carve a scratch arena, the
+// per-frame path has pinned staging buffers and a device-resident copy of the map.  Nothing is allocated, freed or
+// synchronised beyond the one wait for the results per call.
+namespace {
+struct Carver {   // carves the handle's grow-only arena (256-byte aligned pieces), valid until the next front-end call
+    gs_graph *g; size_t off = 0;
+    template <class T> T *get(size_t n) { T *p = (T *)(g->fe.arena + off); off += (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255; return p; }
+};
+}
+static int arena_reserve(gs_graph *g, size_t bytes) {
+    if (bytes <= g->fe.arena_bytes) return GS_OK;
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    if (g->fe.arena) { hipFree(g->fe.arena); g->fe.arena = nullptr; g->fe.arena_bytes = 0; }
+    const size_t want = bytes + bytes / 2 + 4096;
+    HIP_TRY(hipMalloc((void **)&g->fe.arena, want));
+    g->fe.arena_bytes = want;
+    return GS_OK;
+}
+static size_t padded(size_t n, size_t elem) { return (std::max<size_t>(n, 1) * elem + 255) & ~(size_t)255; }
+void gs_frontend_release(gs_graph *g) {      // gs_destroy
+    if (g->fe.arena) hipFree(g->fe.arena);
+    if (g->fe.pin_in) hipHostFree(g->fe.pin_in);
+    if (g->fe.pin_out) hipHostFree(g->fe.pin_out);
+    if (g->fe.dev_in) hipFree(g->fe.dev_in);
+    if (g->fe.dev_out) hipFree(g->fe.dev_out);
+    if (g->fe.map_xy) hipFree(g->fe.map_xy);
+    if (g->fe.map_type) hipFree(g->fe.map_type);
+    if (g->fe.pin_map) hipHostFree(g->fe.pin_map);
+    if (g->fe.grid_mem) hipFree(g->fe.grid_mem);
+    if (g->fe.pcs) hipFree(g->fe.pcs);
+    g->fe = gs_graph::FrontEnd();
+}
+
+extern "C" int gs_polar_to_xy_batch(gs_graph *g, int32_t n, const double *az, const double *zen, const double *dist, double *out) {
+    if (!g || n < 0 || (n > 0 && (!az || !zen || !dist || !out))) return fail(GS_ERR_INVALID, "bad argument");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n == 0) return GS_OK;
+    if ((rc = arena_reserve(g, 3 * padded(n, 8) + padded(2 * (size_t)n, 8))) != GS_OK) return rc;
+    Carver c{g}; double *a = c.get<double>(n), *z = c.get<double>(n), *d = c.get<double>(n), *o = c.get<double>(2 * (size_t)n);
+    HIP_TRY(hipMemcpyAsync(a, az, (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(z, zen, (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(d, dist, (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
+    launch_polar_to_xy(n, a, z, d, g->cfg.lidar_to_cog, o, g->stream);
+    HIP_TRY(hipMemcpyAsync(out, o, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return GS_OK;
+}
+extern "C" int gs_cone_to_global_batch(gs_graph *g, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs,
+                                       const double *obs, double *out) {
+    if (!g || n < 0 || npose < 0 || (n > 0 && (!poses || !pose_of_obs || !obs || !out))) return fail(GS_ERR_INVALID, "bad argument");
+    for (int i = 0; i < n; ++i) if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n == 0) return GS_OK;
+    if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded(2 * (size_t)n, 8))) != GS_OK) return rc;
+    Carver c{g}; double *p = c.get<double>(3 * (size_t)npose); int32_t *po = c.get<int32_t>(n);
+    double *ob = c.get<double>(4 * (size_t)n), *o = c.get<double>(2 * (size_t)n);
+    HIP_TRY(hipMemcpyAsync(p, poses, 3 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(po, pose_of_obs, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
+    launch_cone_to_global(n, p, po, ob, g->cfg.lidar_to_cog, o, g->stream);
+    HIP_TRY(hipMemcpyAsync(out, o, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return GS_OK;
+}
+// the hashed grid of a map that is in device memory: built on the device (launch_grid_build), nothing crosses PCIe, nothing waits
+struct GridBufs { int32_t *count, *start, *cursor, *items; long long buckets; };
+static size_t grid_bytes(int n_map, long long &buckets) {
+    buckets = 4096; while (buckets < 4 * (long long)n_map) buckets <<= 1;      // a power of two >= 4 n_map: mostly empty buckets, L2-resident
+    return 3 * padded((size_t)buckets + 1, 4) + padded((size_t)n_map, 4);
+}
+static GridBufs grid_carve(char *base, int n_map, long long buckets) {
+    GridBufs b; size_t off = 0; auto take = [&](size_t bytes) { char *p = base + off; off += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return p; };
+    b.count = (int32_t *)take(((size_t)buckets + 1) * 4); b.start = (int32_t *)take(((size_t)buckets + 1) * 4);
+    b.cursor = (int32_t *)take(((size_t)buckets + 1) * 4); b.items = (int32_t *)take((size_t)n_map * 4); b.buckets = buckets;
+    return b;
+}
+extern "C" int gs_associate_batch(gs_graph *g, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs, const double *obs,
+                                  int32_t n_map, const double *map_xy, const int32_t *map_type, double thr, double type_tol, int32_t *out) {
+    if (!g || n < 0 || npose < 0 || n_map < 0 || (n > 0 && (!poses || !pose_of_obs || !obs || !out)) || (n_map > 0 && (!map_xy || !map_type)))
+        return fail(GS_ERR_INVALID, "bad argument");
+    for (int i = 0; i < n; ++i) if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n == 0) return GS_OK;
+    // maps beyond a few LDS tiles go through a hashed uniform grid (cell edge a hair above the threshold, so that every cone
+    // within the threshold sits in the 3 x 3 cells around the query) that is BUILT ON THE DEVICE from the uploaded map; the brute-force
+    // kernel stays for small maps and non-positive thresholds.  gs_debug_options.assoc_grid = 0 / 1 forces either (A/B, tests).
+    bool grid = n_map >= 2048 && thr > 0.0;
+    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && n_map > 0 && thr > 0.0;
+    long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
+    if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded(2 * (size_t)n_map, 8) +
+                               padded(n_map, 4) + padded(n, 4) + gbytes + padded(2 * (size_t)npose, 8))) != GS_OK) return rc;
+    Carver c{g}; double *p = c.get<double>(3 * (size_t)npose); int32_t *po = c.get<int32_t>(n); double *pcs = c.get<double>(2 * (size_t)npose);
+    double *ob = c.get<double>(4 * (size_t)n), *mx = c.get<double>(2 * (size_t)n_map);
+    int32_t *mt = c.get<int32_t>(n_map), *o = c.get<int32_t>(n);
+    HIP_TRY(hipMemcpyAsync(p, poses, 3 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(po, pose_of_obs, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
+    if (n_map > 0) { HIP_TRY(hipMemcpyAsync(mx, map_xy, 2 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream));
+                     HIP_TRY(hipMemcpyAsync(mt, map_type, (size_t)n_map * 4, hipMemcpyHostToDevice, g->stream)); }
+    if (grid) { const GridBufs gb = grid_carve(c.get<char>(gbytes), n_map, buckets);
+        launch_grid_build(n_map, mx, thr, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream);
+        launch_associate_grid_dev(n, p, po, ob, g->cfg.lidar_to_cog, mx, mt, thr, type_tol, buckets, gb.start, gb.items, o, npose, pcs, g->stream);
+    } else launch_associate(n, p, po, ob, g->cfg.lidar_to_cog, n_map, mx, mt, thr, type_tol, o, g->stream);
+    HIP_TRY(hipMemcpyAsync(out, o, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));        // the one wait of the call: the result copy
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("association: ") + hipGetErrorString(e));
+    return GS_OK;
+}
+// A1 batched with EVERYTHING resident: the map of gs_map_append (its grid is built on the device, once per map change or threshold),
+// poses / observations / result in device memory, asynchronous on the handle's stream (the caller waits: gs_stream_synchronize).
+static int resident_grid(gs_graph *g, double thr) {
+    auto &fe = g->fe;
+    if (fe.grid_valid && fe.grid_map_n == fe.map_n && fe.grid_thr == thr) return GS_OK;
+    long long buckets = 0; const size_t bytes = grid_bytes(fe.map_n, buckets) + 5 * 256;
+    if (bytes > fe.grid_bytes) { HIP_TRY(hipStreamSynchronize(g->stream));
+        if (fe.grid_mem) hipFree(fe.grid_mem);
+        fe.grid_mem = nullptr; fe.grid_bytes = 0;
+        HIP_TRY(hipMalloc((void **)&fe.grid_mem, bytes + bytes / 2)); fe.grid_bytes = bytes + bytes / 2; }
+    const GridBufs gb = grid_carve(fe.grid_mem, fe.map_n, buckets);
+    launch_grid_build(fe.map_n, fe.map_xy, thr, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream);
+    fe.grid_valid = true; fe.grid_map_n = fe.map_n; fe.grid_thr = thr; fe.grid_max_cells = buckets;
+    return GS_OK;
+}
+extern "C" int gs_associate_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
+                                     double thr, double type_tol, int32_t *dev_out) {
+    if (!g || n < 0 || npose < 0 || (n > 0 && (!dev_poses || !dev_pose_of_obs || !dev_obs || !dev_out))) return fail(GS_ERR_INVALID, "bad argument");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n == 0) return GS_OK;
+    auto &fe = g->fe;
+    const bool grid = thr > 0.0 && fe.map_n > 0 && g->opt.assoc_grid != 0;
+    if (grid) { if ((rc = resident_grid(g, thr)) != GS_OK) return rc;
+        if ((size_t)npose * 2 * sizeof(double) > fe.pcs_bytes) { HIP_TRY(hipStreamSynchronize(g->stream));      // scratch for the poses' cos / sin, grow-only
+            if (fe.pcs) hipFree(fe.pcs);
+            fe.pcs = nullptr; fe.pcs_bytes = 0;
+            const size_t want = (size_t)npose * 2 * sizeof(double) * 3 / 2 + 4096;
+            HIP_TRY(hipMalloc((void **)&fe.pcs, want)); fe.pcs_bytes = want; }
+        const GridBufs gb = grid_carve(fe.grid_mem, fe.map_n, fe.grid_max_cells);
+        launch_associate_grid_dev(n, dev_poses, dev_pose_of_obs, dev_obs, g->cfg.lidar_to_cog, fe.map_xy, fe.map_type, thr, type_tol, gb.buckets, gb.start, gb.items, dev_out,
+                                  npose, fe.pcs, g->stream, g->ev_lin[0], g->ev_lin[1]);
+    } else launch_associate(n, dev_poses, dev_pose_of_obs, dev_obs, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, thr, type_tol, dev_out, g->stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("association: ") + hipGetErrorString(e));
+    return GS_OK;
+}
+// bench / profiling hook (graphslam_debug.h): `reps` launches of the resident association, each with a start / stop event pair attached to
+// its dispatch (the kernel's own begin -> end, as for the linearisation kernel); mean milliseconds per launch; the grid is built before
+extern "C" int gs_debug_time_associate_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
+                                                const double *dev_obs, double thr, double type_tol, int32_t *dev_out, int32_t reps, double *out_ms) {
+    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
+    int rc = gs_associate_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, thr, type_tol, dev_out); if (rc != GS_OK) return rc;     // warm (and the grid)
+    std::vector<hipEvent_t> ev(2 * (size_t)reps); for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    for (int r = 0; r < reps && rc == GS_OK; ++r) { g->ev_lin[0] = ev[2 * (size_t)r]; g->ev_lin[1] = ev[2 * (size_t)r + 1];
+        rc = gs_associate_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, thr, type_tol, dev_out); }
+    g->ev_lin[0] = g->ev_lin[1] = nullptr;
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    double tot = 0; int cnt = 0;
+    for (int r = 0; r < reps; ++r) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]) == hipSuccess && ms > 0) { tot += ms; ++cnt; } }
+    (void)hipGetLastError();
+    for (auto &e : ev) hipEventDestroy(e);
+    *out_ms = cnt ? tot / cnt : 0.0;
+    return rc;
+}
+
+// ---- the per-keyframe path: resident map + one fused launch -------------------------------------------------------
+static int map_reserve(gs_graph *g, int want) {
+    if (want <= g->fe.map_cap) return GS_OK;
+    const int cap = std::max(want + want / 2, 1024);
+    double *xy = nullptr; int32_t *ty = nullptr;
+    HIP_TRY(hipMalloc((void **)&xy, (size_t)cap * 2 * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&ty, (size_t)cap * sizeof(int32_t)));
+    if (g->fe.map_n > 0) { HIP_TRY(hipMemcpyAsync(xy, g->fe.map_xy, (size_t)g->fe.map_n * 2 * sizeof(double), hipMemcpyDeviceToDevice, g->stream));
+                           HIP_TRY(hipMemcpyAsync(ty, g->fe.map_type, (size_t)g->fe.map_n * sizeof(int32_t), hipMemcpyDeviceToDevice, g->stream)); }
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    if (g->fe.map_xy) hipFree(g->fe.map_xy);
+    if (g->fe.map_type) hipFree(g->fe.map_type);
+    g->fe.map_xy = xy; g->fe.map_type = ty; g->fe.map_cap = cap;
+    return GS_OK;
+}
+static int pin_map_reserve(gs_graph *g, size_t bytes) {
+    if (bytes <= g->fe.pin_map_bytes) return GS_OK;
+    HIP_TRY(hipStreamSynchronize(g->stream));                       // a previous staged copy may still be in flight
+    if (g->fe.pin_map) hipHostFree(g->fe.pin_map);
+    g->fe.pin_map = nullptr; g->fe.pin_map_bytes = 0;
+    const size_t want = std::max<size_t>(bytes + bytes / 2, 1 << 16);
+    HIP_TRY(hipHostMalloc((void **)&g->fe.pin_map, want, hipHostMallocDefault));
+    g->fe.pin_map_bytes = want;
+    return GS_OK;
+}
+extern "C" int gs_map_size(gs_graph *g) { return g ? g->fe.map_n : fail(GS_ERR_INVALID, "null graph"); }
+extern "C" int gs_map_clear(gs_graph *g) { if (!g) return fail(GS_ERR_INVALID, "null graph"); g->fe.map_n = 0; g->fe.grid_valid = false; return GS_OK; }
+extern "C" int gs_map_append(gs_graph *g, int32_t n, const double *xy, const int32_t *type) {
+    if (!g || n < 0 || (n > 0 && (!xy || !type))) return fail(GS_ERR_INVALID, "bad argument");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n == 0) return GS_OK;
+    if ((rc = map_reserve(g, g->fe.map_n + n)) != GS_OK) return rc;
+    // staged through pinned memory so that the copy is asynchronous; the staging buffer is reused once the stream has passed
+    // it — every gs_frame_frontend call waits for the stream, and two appends without one in between wait here
+    const size_t bx = (size_t)n * 2 * sizeof(double), bt = (size_t)n * sizeof(int32_t);
+    if (g->fe.pin_map_busy) { HIP_TRY(hipStreamSynchronize(g->stream)); g->fe.pin_map_busy = false; }
+    if ((rc = pin_map_reserve(g, bx + bt)) != GS_OK) return rc;
+    std::memcpy(g->fe.pin_map, xy, bx); std::memcpy(g->fe.pin_map + bx, type, bt);
+    HIP_TRY(hipMemcpyAsync(g->fe.map_xy + 2 * (size_t)g->fe.map_n, g->fe.pin_map, bx, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(g->fe.map_type + g->fe.map_n, g->fe.pin_map + bx, bt, hipMemcpyHostToDevice, g->stream));
+    g->fe.pin_map_busy = true;                                      // no wait here: the next frame's launch is ordered behind the copies
+    g->fe.map_n += n; g->fe.grid_valid = false;
+    return GS_OK;
+}
+extern "C" int gs_map_set_xy(gs_graph *g, int32_t first, int32_t n, const double *xy) {
+    if (!g || first < 0 || n < 0 || (n > 0 && !xy)) return fail(GS_ERR_INVALID, "bad argument");
+    if (first + n > g->fe.map_n) return fail(GS_ERR_INVALID, "beyond the end of the map");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n == 0) return GS_OK;
+    HIP_TRY(hipMemcpyAsync(g->fe.map_xy + 2 * (size_t)first, xy, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));                       // pageable source: the caller's buffer is free on return
+    g->fe.pin_map_busy = false; g->fe.grid_valid = false;
+    return GS_OK;
+}
+extern "C" int gs_frame_frontend(gs_graph *g, const double pose[3], const double *obs, int32_t k, double thr, double type_tol,
+                                 int32_t signed_type, double *out_zxy, double *out_gxy, int32_t *out_idx) {
+    if (!g || !pose || k < 0 || (k > 0 && (!obs || !out_zxy || !out_gxy || !out_idx))) return fail(GS_ERR_INVALID, "bad argument");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (k == 0) return GS_OK;
+    if (k > g->fe.cap_obs) {                                        // grow-only: staging and device buffers for k observations
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        if (g->fe.pin_in) hipHostFree(g->fe.pin_in);
+        if (g->fe.pin_out) hipHostFree(g->fe.pin_out);
+        if (g->fe.dev_in) hipFree(g->fe.dev_in);
+        if (g->fe.dev_out) hipFree(g->fe.dev_out);
+        g->fe.pin_in = nullptr; g->fe.pin_out = nullptr; g->fe.dev_in = nullptr; g->fe.dev_out = nullptr; g->fe.cap_obs = 0;
+        const int cap = std::max(64, k + k / 2);
+        const size_t bin = (3 + 4 * (size_t)cap) * sizeof(double), bout = (size_t)cap * (4 * sizeof(double) + sizeof(int32_t));
+        HIP_TRY(hipHostMalloc((void **)&g->fe.pin_in, bin, hipHostMallocDefault)); HIP_TRY(hipHostMalloc((void **)&g->fe.pin_out, bout, hipHostMallocDefault));
+        HIP_TRY(hipMalloc((void **)&g->fe.dev_in, bin)); HIP_TRY(hipMalloc((void **)&g->fe.dev_out, bout));
+        g->fe.cap_obs = cap;
+    }
+    const size_t bin = (3 + 4 * (size_t)k) * sizeof(double), bz = (size_t)k * 2 * sizeof(double), bi = (size_t)k * sizeof(int32_t);
+    std::memcpy(g->fe.pin_in, pose, 3 * sizeof(double)); std::memcpy(g->fe.pin_in + 3, obs, 4 * (size_t)k * sizeof(double));
+    double *dz = (double *)g->fe.dev_out, *dg = dz + 2 * (size_t)k; int32_t *di = (int32_t *)(dg + 2 * (size_t)k);
+    HIP_TRY(hipMemcpyAsync(g->fe.dev_in, g->fe.pin_in, bin, hipMemcpyHostToDevice, g->stream));
+    launch_frame_frontend(k, g->fe.dev_in, g->cfg.lidar_to_cog, g->fe.map_n, g->fe.map_xy, g->fe.map_type, thr, type_tol, signed_type, dz, dg, di, g->stream);
+    HIP_TRY(hipMemcpyAsync(g->fe.pin_out, g->fe.dev_out, 2 * bz + bi, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    g->fe.pin_map_busy = false;
+    std::memcpy(out_zxy, g->fe.pin_out, bz); std::memcpy(out_gxy, g->fe.pin_out + bz, bz); std::memcpy(out_idx, g->fe.pin_out + 2 * bz, bi);
+    return GS_OK;
+}

@@ -1,4 +1,4 @@
-// gs_internal.hpp — the opaque handle behind gs_graph (shared by gs_api.cpp and gs_slam.cpp).
+// gs_internal.hpp — the opaque handle behind gs_graph (shared by the C-ABI units, see gs_private.hpp, and gs_slam.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,11 +11,9 @@
 #include "gs_device.hpp"
 #include "gs_host.hpp"
 #include "gs_lm.hpp"
+#include "gs_schedule.hpp"
 
 struct gs_graph {
-    // launch parameters of one list of fronts grouped by level
-    struct LevelSet { std::vector<int32_t> start; std::vector<int> max_f, max_npiv, max_nbnd; };
-
     gs_config cfg{};
     gs_debug_options opt{};                 // every tuning switch (graphslam_debug.h): filled once at gs_create, replaced by gs_debug_set_options
     int device = 0;
@@ -39,12 +37,8 @@ struct gs_graph {
     hipStream_t stream = nullptr; bool own_stream = false;
     hipEvent_t ev[8]{};
     hipEvent_t ev_lin[2]{};                 // timed iterations: start / stop attached to the linearisation dispatch (null: none)
-    LevelSet own, shared;                   // this rank's fronts / the shared top (pose-window shards)
-    int shared_base = 0;                    // offset of the shared list inside d.level_fronts
-    int leaf_max_f = 0;                     // largest leaf front (<= 47: the three-tile-row leaf instance)
-    int block_n = -1;                       // trailing level positions of the whole-tree factor launch that get a workgroup each (-1: not decided yet)
-    int leaf_n = -1, leaf_slot = 0;             // level-0 fronts handled by the leaf instance of the factor kernel, its LDS slot (doubles per wave)
-    int sub_n = 0, sub_first = 0, sub_free = 0; // bottom subtrees (k_factor3_sub): level-1 fronts [sub_first, sub_first + sub_n) each take the leaves below them; the leaf launch covers [0, sub_free)
+    gs::Schedule sched;                     // the solver launches of the CURRENT plan (gs_schedule.hpp): built with the plan by upload_graph / upload_growth, read by the enqueue path
+    int2 *d_wg[gs::N_TABS]{};               // device copies of sched.tab (plans with a front of more than 63 scalars; else null)
     int32_t *d_posof = nullptr;                 // device: front -> level position
     double ms_structure = 0;
     int rank = 0, world = 1;
@@ -64,15 +58,6 @@ struct gs_graph {
         double *pcs = nullptr; size_t pcs_bytes = 0;            // cos / sin of the poses of a batched association (scratch, grow-only)
     } fe;
     int default_factor_variant = 0;         // see upload_graph
-    // plans that hold a front of more than 63 scalars: table-driven whole-tree launches (workgroup -> {level position, kind | count << 8}),
-    // built once per plan; *_level[l] = first table entry of level l (one launch per level after a fallback)
-    struct WgSeg { int first, count, level; size_t lds; int cls; };  // a run of table entries of one level with the same LDS need and kernel class
-    std::vector<WgSeg> seg_f, seg_b;
-    std::vector<int32_t> wg_f, wg_b;
-    int2 *d_wg_f = nullptr, *d_wg_b = nullptr; int small_max_npiv = 0, small_max_f = 0;
-    std::vector<WgSeg> segs_c, segs_t, segs_b; std::vector<int32_t> wgs_c, wgs_t, wgs_b;     // the SHARED top of a sharded plan with workgroup fronts: contributions, top, backward solve
-    int2 *d_wgs_c = nullptr, *d_wgs_t = nullptr, *d_wgs_b = nullptr;
-    int enqueue_rc = 0; std::string enqueue_err;     // a failure of the enqueue itself (the lazily built launch tables): returned by the entry point that enqueued
     bool tree_proven = false;               // a whole-tree launch sequence of the CURRENT plan has completed without a flag timeout (gs_optimize then sends all iterations of a call at once)
     bool fell_back = false;                 // a whole-tree launch gave up on a flag: this handle uses one launch per level — until the next plan, or until a retry (below) comes back clean
     int fallback_calls = 0, fallback_retry_after = 4; bool fallback_retrying = false;   // gs_optimize calls on the slow path since the fallback; the call that tries the whole-tree launches again

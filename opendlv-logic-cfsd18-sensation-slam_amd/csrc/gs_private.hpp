@@ -1,0 +1,66 @@
+// gs_private.hpp — what the translation units behind the C-ABI (gs_api.cpp, gs_solve.cpp, gs_frontend.cpp, gs_dist.cpp,
+// gs_marginals.cpp) share beyond the handle itself.
+#pragma once
+#include "gs_internal.hpp"
+
+#include <algorithm>
+#include <string>
+
+#define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
+    return gs::fail(GS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
+
+// Device memory of a plan comes out of a few large chunks (8 MB, then doubling): the ~70 arrays of one structure phase
+// cost a dozen hipMalloc calls instead of 70 (each is 50-100 us of the structure phase), and dev_free_all returns them together.
+// Arrays of 32 MB and more get an allocation of their own.
+// gs_debug_options.pool_poison (tests): every chunk is filled with 0xFF bytes (NaN doubles, negative indices) when it is allocated and whenever a plan
+// releases it — an array that is read before this code writes it cannot pass for zero-initialised
+static inline bool pool_poison(const gs_graph *g) { return g->opt.pool_poison > 0; }
+template <class T> int dev_alloc(gs_graph *g, T **ptr, size_t count) {
+    *ptr = nullptr;
+    const size_t bytes = (std::max<size_t>(count, 1) * sizeof(T) + 255) & ~(size_t)255;
+    if (bytes >= ((size_t)32 << 20)) {                                // a big array: its own allocation, exactly its size (a chunk rounded up to a
+        int best = -1;                                                // power of two for it, or the abandoned rest of the current chunk, were 270 MB of
+        for (size_t i = 0; i < g->allocs.size(); ++i) { const auto &c = g->allocs[i];      // an 800 MB footprint at 100k poses); one kept from the last plan
+            if (c.big && !c.in_use && c.size >= bytes && c.size <= bytes + bytes / 4 && (best < 0 || c.size < g->allocs[best].size)) best = (int)i; }   // serves if it fits within 25 %
+        if (best < 0) { void *p = nullptr;
+            HIP_TRY(hipMalloc(&p, bytes));
+            if (pool_poison(g)) HIP_TRY(hipMemsetAsync(p, 0xFF, bytes, g->stream));
+            gs_graph::DevChunk c; c.p = p; c.size = bytes; c.big = true; g->allocs.push_back(c); best = (int)g->allocs.size() - 1; }
+        g->allocs[best].in_use = true; g->pool_total += g->allocs[best].size; *ptr = (T *)g->allocs[best].p;
+        return GS_OK; }
+    if (g->pool_off + bytes > g->pool_size) {
+        size_t want = std::max<size_t>(g->pool_next, (size_t)8 << 20);
+        while (want < bytes) want <<= 1;
+        int pick = -1;
+        for (size_t i = 0; i < g->allocs.size() && pick < 0; ++i) { const auto &c = g->allocs[i]; if (!c.big && !c.in_use && c.size >= want) pick = (int)i; }   // a chunk of the last plan
+        if (pick < 0) { void *p = nullptr;
+            HIP_TRY(hipMalloc(&p, want));
+            if (pool_poison(g)) HIP_TRY(hipMemsetAsync(p, 0xFF, want, g->stream));
+            gs_graph::DevChunk c; c.p = p; c.size = want; g->allocs.push_back(c); pick = (int)g->allocs.size() - 1; }
+        auto &c = g->allocs[pick]; c.in_use = true; g->pool_total += c.size;
+        g->pool_base = (char *)c.p; g->pool_size = c.size; g->pool_off = 0;
+        g->pool_next = std::min<size_t>(std::max(want, c.size) << 1, (size_t)128 << 20);      // chunks of at most 128 MB: little slack in the footprint
+    }
+    *ptr = (T *)(g->pool_base + g->pool_off);
+    g->pool_off += bytes;
+    return GS_OK;
+}
+
+// gs_api.cpp
+int ensure_device(gs_graph *g);
+int ensure_ready(gs_graph *g);                 // the structure phase if the graph changed, host-side estimates to the device
+int pull_estimates_if_needed(gs_graph *g);
+int pull_estimates_enqueue(gs_graph *g, bool &pull);        // the copies only: they come back with the caller's next wait, which then clears dev_estimates_newer if `pull`
+int reset_failure(gs_graph *g);
+void fill_plan_stats(gs_graph *g, gs_stats *s);
+// gs_solve.cpp
+void enqueue_factor_levels(gs_graph *g, const gs::LevelSet &ls, int base, int mode);
+void enqueue_local(gs_graph *g, bool timed);
+void enqueue_finish(gs_graph *g, bool timed);
+void fall_back_to_levels(gs_graph *g);
+// the run scaffold gs_optimize* / gs_optimize_lm share; gs_dist_optimize uses these pieces of it
+int run_begin(gs_graph *g, int32_t iterations, bool retry);
+int run_check(gs_graph *g, const char *what, float *ms);
+void run_stats(gs_graph *g, gs_stats *stats, int32_t iterations, int32_t failure, int first_failure, double chi2_initial, double chi2_final, float ms);
+void gs_frontend_release(gs_graph *g);       // gs_frontend.cpp: front-end buffers of the handle
+void gs_dist_comm_release(gs_graph *g);      // gs_dist.cpp: the handle's own RCCL communicator

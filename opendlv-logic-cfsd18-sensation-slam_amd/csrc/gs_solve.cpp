@@ -1,0 +1,484 @@
+// gs_solve.cpp — the solver launches of one iteration and the entry points that run iterations (gs_iterate, gs_optimize*,
+// gs_optimize_lm), with the timing and export hooks.
+#include "../../include/graphslam.h"
+#include "../../include/graphslam_debug.h"
+#include "gs_private.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+using namespace gs;
+
+// ------------------------------------------------------------------ one Gauss-Newton iteration (A5-A9)
+// The launches an iteration is made of are decided with the plan (gs_schedule.hpp: build_schedule, walk_*); nothing is decided here:
+// this sink hands each launch of the walk to its launcher on the handle's stream
+namespace {
+struct Launcher {
+    gs_graph *g;
+    void epoch() { ++g->d.epoch; }
+    void factor_tree(int n_leaf, int leaf_slot, int leaf_max_f, int count, int n_block, int sub_first, int n_sub) { launch_factor_tree(g->d, n_leaf, leaf_slot, leaf_max_f, count, n_block, sub_first, n_sub, g->stream); }
+    void factor_level(int off, int count, int max_f, int mode) { launch_factor_level(g->d, off, count, max_f, mode, g->stream); }
+    void factor_tree_top(int first, int count) { launch_factor_tree_top(g->d, first, count, g->stream); }
+    void factor_tab(int t, int first, int n, int leaf_pre, size_t lds, int cls, int mode) { launch_factor_tab(g->d, g->d_wg[t] + first, n, leaf_pre, lds, cls, g->stream, mode); }
+    void backsolve_tree(int first, int count, int max_npiv, int max_f) { launch_backsolve_tree(g->d, first, count, max_npiv, max_f, g->stream); }
+    void backsolve_level(int off, int count, int max_npiv, int max_nbnd) { launch_backsolve_level(g->d, off, count, max_npiv, max_nbnd, g->stream); }
+    void backsolve_tab(int t, int first, int n, int max_npiv_small, int max_f_small, size_t lds, int cls) { launch_backsolve_tab(g->d, g->d_wg[t] + first, n, max_npiv_small, max_f_small, lds, cls, g->stream); }
+};
+}  // namespace
+void enqueue_factor_levels(gs_graph *g, const LevelSet &ls, int base, int mode) { Launcher L{g}; walk_factor_levels(g->sched, g->d.tree != 0, ls, base, mode, L); }
+// pose-window shards, first half: linearise this shard's edges, factorise its own subtrees, write its contribution
+// to every shared front into the exchange buffer (the caller all-reduces that buffer: RCCL sum, fp64)
+void enqueue_local(gs_graph *g, bool timed) {
+    ++g->d.iter;                                                     // kernels see the iteration they belong to (fault injection, gs_debug_fail_at_iteration)
+    if (timed) hipEventRecord(g->ev[0], g->stream);
+    launch_linearize(g->d, g->stream, g->ev_lin[0], g->ev_lin[1]);   // (null outside gs_time_iterations' second pass)
+    launch_linearize_tail(g->d, g->stream);                          // a grown plan's tail (no launch without one)
+    if (timed) hipEventRecord(g->ev[1], g->stream);
+    Launcher L{g}; walk_local(g->sched, g->d.tree != 0, L);
+}
+// second half: the shared top (redundantly on every rank), backward solve top-down, update
+void enqueue_finish(gs_graph *g, bool timed) {
+    Launcher L{g}; const bool tree = g->d.tree != 0;
+    walk_finish_factor(g->sched, tree, L);
+    if (timed) hipEventRecord(g->ev[2], g->stream);
+    walk_finish_backsolve(g->sched, tree, L);
+    if (timed) hipEventRecord(g->ev[3], g->stream);
+    launch_update(g->d, g->stream);
+    if (timed) hipEventRecord(g->ev[4], g->stream);
+    g->dev_estimates_newer = true;
+}
+static void enqueue_iteration(gs_graph *g, bool timed) { enqueue_local(g, timed); enqueue_finish(g, timed); }
+
+extern "C" int gs_iterate(gs_graph *g) {
+    if (!g) return fail(GS_ERR_INVALID, "null graph");
+    if (!g->dev_valid || g->plan_version != g->h.structure_version) return fail(GS_ERR_NOT_INITIALIZED, "call gs_initialize_optimization first");
+    if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: use gs_dist_iterate (RCCL inside the library) or gs_dist_iterate_local / all-reduce / gs_dist_iterate_finish");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    enqueue_iteration(g, false);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return 1;
+}
+
+// ------------------------------------------------------------------ the run scaffold of gs_optimize*, gs_optimize_lm (and, in parts, gs_dist_optimize)
+// a whole-tree launch gave up on a front's flag: one launch per level from now on; a retry of the whole-tree launches that ends this way
+// waits four times longer before the next one (run_begin, gs_compute_marginals)
+void fall_back_to_levels(gs_graph *g) {
+    if (g->fallback_retrying) { g->fallback_retrying = false; g->fallback_retry_after = std::min(g->fallback_retry_after * 4, 1024); }
+    g->fallback_calls = 0;
+    g->d.tree = 0; g->fell_back = true;
+}
+// Before the first launch of a call.  retry: a handle that fell back to one launch per level (a whole-tree launch gave up on a front's flag)
+// does not stay there until the next plan: what makes a flag late — the chip shared with another process, a debugger, a profiler replaying
+// kernels — passes.  After 4 calls on the slow path the whole-tree launches are tried again (first iteration on its own, like a new
+// plan's); another timeout quadruples the wait (16, 64, ... 1024 calls), a clean launch ends the episode.
+// The failure state starts from zero; an armed fault injection (host-side fields) survives.
+int run_begin(gs_graph *g, int32_t iterations, bool retry) {
+    if (retry && g->fell_back && iterations > 0 && g->opt.tree != 0 && !g->d.tree && ++g->fallback_calls >= g->fallback_retry_after) {
+        g->d.tree = 1; g->tree_proven = false; g->fallback_calls = 0; g->fallback_retrying = true; }
+    HIP_TRY(hipMemsetAsync(g->d.fail, 0, 4 * sizeof(int32_t), g->stream));
+    return GS_OK;
+}
+// After a chunk of iterations is enqueued (and whatever else the caller wants back with the same wait): the ONE host round trip of the
+// chunk, then the bookkeeping every run shares.  A flag timeout of a whole-tree launch (code 2) is not a property of H: the handle falls
+// back to one launch per level, once per call, and the caller runs the iterations that were not applied again (RUN_RERUN; the code is
+// cleared, the update count fail[1] goes on).
+enum { RUN_CONTINUE = 0, RUN_RERUN = 1, RUN_STOP = 2 };
+struct RunState { int32_t ff[4] = {0, 0, 0, 0}; int first_failure = 0; bool fell_back = false; };
+static int run_chunk_done(gs_graph *g, RunState &R) {
+    HIP_TRY(hipMemcpyAsync(R.ff, g->d.fail, sizeof(R.ff), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    if (R.ff[0] == 0 && g->d.tree) { g->tree_proven = true;
+        if (g->fallback_retrying) { g->fallback_retrying = false; g->fell_back = false; g->fallback_retry_after = 4; } }     // back on the whole-tree launches
+    if (R.ff[0] != 0 && R.first_failure == 0) R.first_failure = R.ff[0];
+    if (R.ff[0] == 2 && g->d.tree && !R.fell_back) {
+        fall_back_to_levels(g);
+        R.fell_back = true; g->d.inject_iter = 0;
+        HIP_TRY(hipMemsetAsync(g->d.fail, 0, sizeof(int32_t), g->stream));      // the code only: the update count goes on
+        R.ff[0] = 0; return RUN_RERUN; }
+    return R.ff[0] != 0 ? RUN_STOP : RUN_CONTINUE;
+}
+// After the last wait of a call: a launch that never ran (the ticket counter and its running sum start again), the time between ev[5] and ev[6]
+int run_check(gs_graph *g, const char *what, float *ms) {
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { reset_failure(g); return fail(GS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
+    *ms = 0; hipEventElapsedTime(ms, g->ev[5], g->ev[6]);
+    return GS_OK;
+}
+// The end of a call, behind the caller's own result copies: the estimates come back with the same wait (on failure: the last good
+// iterate, what g2o's vertices hold)
+static int run_end(gs_graph *g, const char *what, float *ms) {
+    bool pull = false; int rc = pull_estimates_enqueue(g, pull); if (rc != GS_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    if (pull) g->dev_estimates_newer = false;
+    return run_check(g, what, ms);
+}
+void run_stats(gs_graph *g, gs_stats *stats, int32_t iterations, int32_t failure, int first_failure, double chi2_initial, double chi2_final, float ms) {
+    if (!stats) return;
+    std::memset(stats, 0, sizeof(*stats)); stats->struct_size = (int32_t)sizeof(*stats);
+    fill_plan_stats(g, stats); stats->iterations = iterations; stats->numeric_failure = failure; stats->first_failure = first_failure;
+    stats->chi2_initial = chi2_initial; stats->chi2_final = chi2_final; stats->ms_total = ms;
+}
+
+// gs_optimize (rel_tol < 0: the reference's fixed iteration count) and gs_optimize_until (rel_tol >= 0: the stop rule)
+static int optimize_impl(gs_graph *g, int32_t iterations, double rel_tol, gs_stats *stats) {
+    if (!g) return fail(GS_ERR_INVALID, "null graph");
+    if (iterations < 0) return fail(GS_ERR_INVALID, "negative iteration count");
+    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: use gs_dist_optimize (RCCL inside the library), or drive gs_dist_iterate_local / all-reduce / gs_dist_iterate_finish");
+    // g2o: optimize() is always preceded by initializeOptimization() (reference src/slam.cpp:480-481);
+    // the plan is rebuilt only when the structure changed since the last call.
+    int rc = ensure_ready(g); if (rc != GS_OK) return rc;
+    if ((rc = run_begin(g, iterations, true)) != GS_OK) return rc;
+    const bool until = rel_tol >= 0.0;
+    g->d.conv_tol = until ? rel_tol : -1.0;
+    if (until) { const double none = -1.0; HIP_TRY(hipMemcpyAsync(g->d.chi2 + 70, &none, sizeof(double), hipMemcpyHostToDevice, g->stream)); }
+    hipEventRecord(g->ev[5], g->stream);
+    const int nh = std::min(iterations, 64);
+    // All iterations are enqueued up front (no host round trip between them).  g2o leaves its loop at the first failed
+    // solve and keeps the previous iterate: k_update applies nothing once the failure flag is up, and fail[1] says how
+    // many updates went in.  After a flag timeout (run_chunk_done) the remaining iterations run again from the last good iterate.
+    // Stop rule (gs_optimize_until): k_update compares the chi2 of consecutive linearisation points on the device and
+    // raises fail[2]; later updates are skipped like after a failure.  The host enqueues chunks of 4 iterations and
+    // looks at the flags in between, so at most 3 enqueued iterations run as no-ops after convergence.
+    // Chunks: the FIRST iteration on its own, then groups of 8 — a remainder of up to 12 in one — (stop rule: 4).  A whole-tree launch whose flag hand-off fails
+    // (its pollers are bounded and leave at once when any front has reported a failure, so such a launch drains in one poll
+    // budget, ~30 ms) would otherwise have every remaining iteration queued up behind it, each paying the same again: with
+    // chunks a timeout costs one chunk before the per-level fallback takes over.  One host round trip per chunk.
+    int applied = 0, enq = 0; RunState R; const int32_t *ff = R.ff;
+    while (enq < iterations) {
+        // (a remainder of up to 12 goes out as one chunk: the reference's optimize(10) is 1 + 9, two host round trips instead of three)
+        // (the FIRST iteration goes out alone only until a whole-tree launch of THIS plan has come back clean once: the flag hand-off
+        // depends on the launch geometry, not on the numbers — a repeated optimize(10), the reference's quirk path, is one host round trip)
+        const bool alone = enq == 0 && !(g->tree_proven && g->d.tree);
+        const int upto = std::min(iterations, alone ? 1 : (until ? enq + 4 : (iterations - enq <= 12 ? iterations : enq + 8)));
+        for (int it = enq; it < upto; ++it) {
+            g->d.hist_slot = it < nh ? it : -1;                      // k_update files the chi2 of this iteration's linearisation point itself
+            enqueue_iteration(g, false);
+        }
+        g->d.hist_slot = -1;
+        enq = upto;
+        const int next = run_chunk_done(g, R); if (next < 0) return next;
+        applied = ff[1];
+        if (next == RUN_RERUN) { enq = applied; continue; }
+        if (next == RUN_STOP || ff[2] != 0) break;
+    }
+    g->d.conv_tol = -1.0;
+    if (until) HIP_TRY(hipMemsetAsync(g->d.fail + 2, 0, sizeof(int32_t), g->stream));     // the stop flag must not gate later gs_iterate calls
+    const int nshow = std::min(applied, nh);
+    if (g->cfg.verbose || stats) { launch_chi2_only(g->d, g->stream);
+        hipMemcpyAsync(g->d.chi2 + 1 + nh, g->d.chi2, sizeof(double), hipMemcpyDeviceToDevice, g->stream); }
+    hipEventRecord(g->ev[6], g->stream);
+    double hist[80]; float ms;
+    HIP_TRY(hipMemcpyAsync(hist, g->d.chi2, sizeof(hist), hipMemcpyDeviceToHost, g->stream));
+    if ((rc = run_end(g, "iteration", &ms)) != GS_OK) return rc;
+    if (g->cfg.verbose) for (int it = 0; it < nshow; ++it)  // g2o prints the chi2 AFTER the update of iteration it
+        std::fprintf(stderr, "iteration= %d\t chi2= %.6f\t edges= %d\t schur= 0\n", it, it + 1 < applied ? hist[2 + it] : hist[1 + nh], g->h.n_pp() + g->h.n_pl());
+    run_stats(g, stats, applied, ff[0], R.first_failure, iterations > 0 ? hist[1] : hist[1 + nh], hist[1 + nh], ms);
+    if (ff[0]) { rc = reset_failure(g); if (rc != GS_OK) return rc; }
+    if (ff[0] == 2) { g_last_error = "a front's completion flag did not arrive in time, with one launch per level as well"; return 0; }
+    if (ff[0]) { g_last_error = "zero pivot: H is singular (g2o: optimize() returns 0, the vertices keep the last good iterate)"; return 0; }
+    return applied;
+}
+extern "C" int gs_optimize(gs_graph *g, int32_t iterations, gs_stats *stats) { return optimize_impl(g, iterations, -1.0, stats); }
+extern "C" int gs_optimize_until(gs_graph *g, int32_t max_iterations, double rel_chi2_tol, gs_stats *stats) {
+    if (!(rel_chi2_tol >= 0.0)) return fail(GS_ERR_INVALID, "rel_chi2_tol must be >= 0");
+    return optimize_impl(g, max_iterations, rel_chi2_tol, stats);
+}
+
+// ------------------------------------------------------------------ Levenberg-Marquardt (gs_lm.hpp: trial sequence, device record)
+extern "C" int gs_lm_params_default(gs_lm_params *p) {
+    if (!p) return fail(GS_ERR_INVALID, "null params");
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(*p); p->max_trials_after_failure = 10; p->initial_lambda = 0.0; p->tau = 1e-5;
+    return GS_OK;
+}
+// the handle's LM buffers: one allocation of its own (not pool memory: it outlives the plans), grow-only
+static int lm_reserve(gs_graph *g) {
+    auto &W = g->lm; const size_t NP = (size_t)(g->d.N + g->d.tN), ML = (size_t)(g->d.M + g->d.tM);
+    const size_t np = (size_t)lm_grid(g->d);
+    if (!W.mem || NP > W.cap_p || ML > W.cap_l) {
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        if (W.mem) { hipFree(W.mem); W.mem = nullptr; }
+        const size_t cp = NP + 64, cl = ML + 64, cpart = (cp + cl + 255) / 256 + 1;
+        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const size_t o_state = 0, o_hc = al(2 * sizeof(LmState)), o_hl = o_hc + al(64 * 8), o_ht = o_hl + al(64 * 8), o_bp = o_ht + al(64 * 4),
+                     o_bc = o_bp + al(cp * 24), o_bl = o_bc + al(cp * 16), o_part = o_bl + al(cl * 16), total = o_part + al(cpart * 8);
+        HIP_TRY(hipMalloc(&W.mem, total));
+        char *b = (char *)W.mem;
+        W.dev.state = (LmState *)(b + o_state); W.dev.hist_chi2 = (double *)(b + o_hc); W.dev.hist_lambda = (double *)(b + o_hl); W.dev.hist_trials = (int32_t *)(b + o_ht);
+        W.dev.base_pose = (double *)(b + o_bp); W.dev.base_cs = (double *)(b + o_bc); W.dev.base_lm = (double *)(b + o_bl); W.dev.part = (double *)(b + o_part);
+        W.cap_p = cp; W.cap_l = cl; }
+    W.dev.n_part = (int32_t)np;
+    return GS_OK;
+}
+// one trial, asynchronous: today's linearise / factor / back-solve / update launches in today's launch modes, with the LM kernels around them
+static void enqueue_lm_trial(gs_graph *g, int par, bool init) {
+    const LmDev &lm = g->lm.dev;
+    ++g->d.iter;
+    launch_linearize(g->d, g->stream);
+    launch_linearize_tail(g->d, g->stream);
+    if (init) launch_lm_maxdiag(g->d, lm, g->stream);
+    launch_lm_damp(g->d, lm, par, init ? 1 : 0, g->stream);
+    enqueue_factor_levels(g, g->sched.own, 0, 0);
+    enqueue_finish(g, false);                                        // (no shared top on a single device), back-solve, update
+    launch_lm_scale(g->d, lm, par, g->stream);
+    launch_chi2_only(g->d, g->stream);                               // chi2 at x_try -> chi2[0]
+    launch_lm_step(g->d, lm, par, g->stream);
+}
+extern "C" int gs_optimize_lm(gs_graph *g, int32_t iterations, const gs_lm_params *params, gs_stats *stats, gs_lm_info *info) {
+    if (!g) return fail(GS_ERR_INVALID, "null graph");
+    if (iterations < 0) return fail(GS_ERR_INVALID, "negative iteration count");
+    gs_lm_params P; gs_lm_params_default(&P);
+    if (params) { std::memcpy(&P, params, std::min<size_t>(sizeof(P), (size_t)std::max(params->struct_size, 0))); P.struct_size = (int32_t)sizeof(P); }
+    if (!std::isfinite(P.tau) || !(P.tau > 0.0)) return fail(GS_ERR_INVALID, "gs_lm_params.tau must be finite and > 0");
+    if (!std::isfinite(P.initial_lambda)) return fail(GS_ERR_INVALID, "gs_lm_params.initial_lambda must be finite (<= 0: tau * max diag(H))");
+    if (P.max_trials_after_failure < 1) return fail(GS_ERR_INVALID, "gs_lm_params.max_trials_after_failure must be >= 1");
+    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: Levenberg-Marquardt is not supported on sharded handles");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    rc = ensure_ready(g); if (rc != GS_OK) return rc;
+    if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: Levenberg-Marquardt is not supported on sharded handles");
+    rc = lm_reserve(g); if (rc != GS_OK) return rc;
+    if ((rc = run_begin(g, iterations, true)) != GS_OK) return rc;
+    g->d.conv_tol = -1.0; g->d.hist_slot = -1;
+    LmState *H = g->lm.host; std::memset(H, 0, 2 * sizeof(LmState));
+    LmState &S0 = H[0];
+    S0.lambda = P.initial_lambda > 0.0 ? P.initial_lambda : 0.0; S0.lambda_initial = S0.lambda; S0.nu = 2.0; S0.tau = P.tau;
+    S0.budget = iterations; S0.max_trials = P.max_trials_after_failure; S0.need_lambda = P.initial_lambda > 0.0 ? 0 : 1;
+    HIP_TRY(hipMemcpyAsync(g->lm.dev.state, H, 2 * sizeof(LmState), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemsetAsync(g->lm.dev.hist_chi2, 0, 64 * sizeof(double), g->stream));
+    HIP_TRY(hipMemsetAsync(g->lm.dev.hist_lambda, 0, 64 * sizeof(double), g->stream));
+    HIP_TRY(hipMemsetAsync(g->lm.dev.hist_trials, 0, 64 * sizeof(int32_t), g->stream));
+    hipEventRecord(g->ev[5], g->stream);
+    // Chunks of trials, the device record read in between (one host round trip per chunk).  Never more trials than iterations still
+    // to accept — each needs one at least —, so the only trials that run as no-ops are the ones enqueued behind a "terminate"; the first
+    // trial alone until a whole-tree launch of this plan has come back clean, as in gs_optimize.
+    LmState S = S0; int seq = 0; RunState R; const int32_t *ff = R.ff;
+    while (iterations > 0 && !S.done && S.iterations < iterations) {
+        const bool alone = S.trials == 0 && !(g->tree_proven && g->d.tree);
+        const int n = alone ? 1 : std::min(iterations - S.iterations, 8);
+        for (int k = 0; k < n; ++k, ++seq) enqueue_lm_trial(g, seq & 1, k == 0 && S.trials == 0 && S.need_lambda != 0);
+        HIP_TRY(hipMemcpyAsync(&H[1], g->lm.dev.state + (seq & 1), sizeof(LmState), hipMemcpyDeviceToHost, g->stream));
+        const int next = run_chunk_done(g, R); if (next < 0) return next;
+        S = H[1];
+        if (next == RUN_STOP) break;                                // (RUN_RERUN: the trials behind the timeout were no-ops: the loop runs them again, one launch per level)
+    }
+    HIP_TRY(hipMemsetAsync(g->d.fail + 1, 0, 2 * sizeof(int32_t), g->stream));     // the update count and the stop flag must not gate later gs_iterate calls
+    if (S.trials == 0 && (stats || info || g->cfg.verbose)) launch_chi2_only(g->d, g->stream);     // nothing ran: chi2 at the estimates as they are
+    hipEventRecord(g->ev[6], g->stream);
+    double chi_here = 0.0, hc[64], hl[64]; int32_t ht[64];
+    HIP_TRY(hipMemcpyAsync(&chi_here, g->d.chi2, sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(hc, g->lm.dev.hist_chi2, sizeof(hc), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(hl, g->lm.dev.hist_lambda, sizeof(hl), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(ht, g->lm.dev.hist_trials, sizeof(ht), hipMemcpyDeviceToHost, g->stream));
+    float ms;
+    if ((rc = run_end(g, "LM iteration", &ms)) != GS_OK) return rc;
+    const double chi_first = S.trials > 0 ? hc[0] : chi_here, chi_last = S.trials > 0 ? S.chi_base : chi_here;
+    if (g->cfg.verbose) for (int it = 0; it < std::min(S.iterations, 64); ++it)
+        std::fprintf(stderr, "iteration= %d\t chi2= %.6f\t edges= %d\t schur= 0\t lambda= %.6g\t levenbergIter= %d\n", it,
+                     it + 1 < S.iterations && it + 1 < 64 ? hc[it + 1] : chi_last, g->h.n_pp() + g->h.n_pl(), hl[it], ht[it]);
+    run_stats(g, stats, S.iterations, ff[0], R.first_failure, chi_first, chi_last, ms);
+    if (info) { std::memset(info, 0, sizeof(*info)); info->struct_size = (int32_t)sizeof(*info);
+        info->iterations = S.iterations; info->trials = S.trials; info->rejected = S.rejected; info->terminated = S.terminated;
+        info->lambda_initial = S.lambda_initial; info->lambda_final = S.lambda;
+        std::memcpy(info->chi2, hc, sizeof(hc)); std::memcpy(info->lambda, hl, sizeof(hl)); std::memcpy(info->n_trials, ht, sizeof(ht)); }
+    if (ff[0]) { rc = reset_failure(g); if (rc != GS_OK) return rc;
+        if (ff[0] == 2) return fail(GS_ERR_TIMEOUT, "a front's completion flag did not arrive in time, with one launch per level as well (estimates = last accepted point)");
+        return fail(GS_ERR_NUMERIC, "a solver failure the step control could not treat as a rejected trial (estimates = last accepted point)"); }
+    return S.iterations;
+}
+
+extern "C" int gs_chi2(gs_graph *g, double *out) {
+    if (!g || !out) return fail(GS_ERR_INVALID, "null argument");
+    int rc = ensure_ready(g); if (rc != GS_OK) return rc;
+    launch_chi2_only(g->d, g->stream);
+    HIP_TRY(hipMemcpyAsync(out, g->d.chi2, sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return GS_OK;
+}
+
+// ------------------------------------------------------------------ measurement / parity hooks
+extern "C" int gs_linearize(gs_graph *g) {
+    if (!g) return fail(GS_ERR_INVALID, "null graph");
+    int rc = ensure_ready(g); if (rc != GS_OK) return rc;
+    launch_linearize(g->d, g->stream);
+    launch_linearize_tail(g->d, g->stream);
+    launch_linearize_finalize(g->d, g->stream);              // stand-alone pass: materialise H_ll, b_l, chi2 for export
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("linearize: ") + hipGetErrorString(e));
+    return GS_OK;
+}
+extern "C" int gs_time_linearize(gs_graph *g, int32_t reps, double *out_ms) {
+    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
+    int rc = ensure_ready(g); if (rc != GS_OK) return rc;
+    launch_linearize(g->d, g->stream);                       // warm
+    hipEventRecord(g->ev[0], g->stream);
+    for (int r = 0; r < reps; ++r) launch_linearize(g->d, g->stream);
+    hipEventRecord(g->ev[1], g->stream);
+    HIP_TRY(hipEventSynchronize(g->ev[1]));
+    float ms = 0; HIP_TRY(hipEventElapsedTime(&ms, g->ev[0], g->ev[1]));
+    *out_ms = (double)ms / reps;
+    return GS_OK;
+}
+extern "C" int gs_debug_front_times(gs_graph *g, int64_t *out, int64_t capacity) {
+    if (!g || !out) return fail(GS_ERR_INVALID, "null argument");
+    if (!g->dev_valid) return fail(GS_ERR_NOT_INITIALIZED, "nothing on the device yet");
+    const int64_t n = 2 * (int64_t)g->plan.fronts.size();
+    if (capacity < n) return fail(GS_ERR_CAPACITY, "buffer too small");
+    HIP_TRY(hipMemcpyAsync(out, g->d.done_ts, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return (int)(n / 2);
+}
+extern "C" int gs_debug_timestamps(gs_graph *g, int64_t *out64) {
+    if (!g || !out64) return fail(GS_ERR_INVALID, "null argument");
+    if (!g->dev_valid) return fail(GS_ERR_NOT_INITIALIZED, "nothing on the device yet");
+    HIP_TRY(hipMemcpyAsync(out64, g->d.dbg_ts, 64 * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return GS_OK;
+}
+extern "C" int64_t gs_linearize_bytes(gs_graph *g) {
+    if (!g) return 0;
+    return (int64_t)g->h.n_pp() * 152 + (int64_t)g->h.n_pl() * 96 + (int64_t)g->h.n_poses() * 120 + (int64_t)g->h.n_lms() * 64;
+}
+extern "C" int gs_export_system(gs_graph *g, double *Hpp_diag, double *Hll_diag, double *Hpp_off, double *Hpl,
+                                double *b_pose, double *b_lm, int32_t *pp_order, int32_t *pl_order) {
+    if (!g) return fail(GS_ERR_INVALID, "null graph");
+    if (!g->dev_valid) return fail(GS_ERR_NOT_INITIALIZED, "nothing linearised yet");
+    if (g->d.tN > 0) return fail(GS_ERR_INVALID, "the plan has grown by appended poses: their blocks live in the tail arenas, which this export does not read (gs_initialize_optimization with GS_GROW=0 rebuilds)");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    const DevGraph &d = g->d;
+    // an iteration and gs_compute_marginals leave the landmark blocks as per-edge partials (the fronts sum them): sum them here, so
+    // that H_ll and b_l are those of the last linearisation whichever call ran it
+    launch_linearize_finalize(d, g->stream, false);
+    { const hipError_t e = hipGetLastError(); if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("export: ") + hipGetErrorString(e)); }
+    // the device keeps these arrays structure-of-arrays (and the diagonal blocks packed symmetric); the
+    // export format is array-of-blocks, full and row-major
+    const size_t N = (size_t)d.N, M = (size_t)d.M, Epp = (size_t)d.Epp, Epl = (size_t)d.Epl;
+    const size_t L = (size_t)d.ell_len;
+    std::vector<double> t0(N * 6), t1(M * 3), t2(Epp * 9), t3(L * 6), t4(N * 3), t5(M * 2);
+    auto dl = [&](std::vector<double> &dst, const double *src) -> hipError_t {
+        return dst.empty() ? hipSuccess : hipMemcpyAsync(dst.data(), src, dst.size() * sizeof(double), hipMemcpyDeviceToHost, g->stream); };
+    HIP_TRY(dl(t0, d.Hpp_diag)); HIP_TRY(dl(t1, d.Hll_diag)); HIP_TRY(dl(t2, d.Hpp_off)); HIP_TRY(dl(t3, d.Hpl));
+    HIP_TRY(dl(t4, d.b_pose)); HIP_TRY(dl(t5, d.b_lm));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    static const int sym3[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}}, sym2[2][2] = {{0, 1}, {1, 2}};
+    if (Hpp_diag) for (size_t p = 0; p < N; ++p) for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) Hpp_diag[9 * p + 3 * r + c] = t0[sym3[r][c] * N + p];
+    if (Hll_diag) for (size_t l = 0; l < M; ++l) for (int r = 0; r < 2; ++r) for (int c = 0; c < 2; ++c) Hll_diag[4 * l + 2 * r + c] = t1[sym2[r][c] * M + l];
+    if (Hpp_off) for (size_t k = 0; k < Epp; ++k) for (int c = 0; c < 9; ++c) Hpp_off[9 * k + c] = t2[c * Epp + k];
+    if (Hpl) for (size_t k = 0; k < Epl; ++k) { const int32_t e = g->plan.ell_of_ins[k];                 // insertion order; an edge outside this rank's layout: zeros
+        for (int c = 0; c < 6; ++c) Hpl[6 * k + c] = e >= 0 ? t3[c * L + (size_t)e] : 0.0; }
+    if (b_pose) for (size_t p = 0; p < N; ++p) for (int c = 0; c < 3; ++c) b_pose[3 * p + c] = t4[c * N + p];
+    if (b_lm) for (size_t l = 0; l < M; ++l) for (int c = 0; c < 2; ++c) b_lm[2 * l + c] = t5[c * M + l];
+    if (pp_order) std::memcpy(pp_order, g->plan.pp_order.data(), g->plan.pp_order.size() * sizeof(int32_t));
+    if (pl_order) for (size_t k = 0; k < Epl; ++k) pl_order[k] = (int32_t)k;                 // exported in insertion order
+    return GS_OK;
+}
+// per-edge s = e^T W e and weight at the current estimates (k_edge_chi2).  The index table of the kind's edges goes up with the call
+// (a query, not part of an iteration): endpoints from the host graph, an observation edge's place from the plan — its ELL index,
+// or its tail slot when a growth step appended it
+extern "C" int gs_get_edge_chi2(gs_graph *g, int32_t edge_kind, int32_t capacity, double *out_chi2, double *out_weight) {
+    if (!g) return fail(GS_ERR_INVALID, "null graph");
+    if (edge_kind != GS_EDGE_ODOMETRY && edge_kind != GS_EDGE_OBSERVATION) return fail(GS_ERR_INVALID, "edge kind must be GS_EDGE_ODOMETRY or GS_EDGE_OBSERVATION");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: per-edge chi2 is not supported on sharded handles");
+    rc = ensure_ready(g); if (rc != GS_OK) return rc;
+    if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: per-edge chi2 is not supported on sharded handles");
+    const HostGraph &h = g->h; const Plan &P = g->plan;
+    const bool pp = edge_kind == GS_EDGE_ODOMETRY;
+    const int n = pp ? h.n_pp() : h.n_pl();
+    if ((out_chi2 || out_weight) && capacity < n) return fail(GS_ERR_CAPACITY, "buffer too small");
+    if (n == 0 || (!out_chi2 && !out_weight)) return n;
+    const int per = pp ? 2 : 3;
+    std::vector<int32_t> tab((size_t)n * per);
+    if (pp) for (int k = 0; k < n; ++k) { tab[2 * (size_t)k] = h.pp_i[k]; tab[2 * (size_t)k + 1] = h.pp_j[k]; }
+    else for (int k = 0; k < n; ++k) {
+        int32_t src;
+        if (k < P.base_Epl) { src = P.ell_of_ins[k]; if (src < 0) return fail(GS_ERR_INVALID, "observation edge outside the linearisation layout"); }
+        else { if (k - P.base_Epl >= g->d.tEpl) return fail(GS_ERR_INVALID, "observation edge not on the device"); src = -(k - P.base_Epl) - 1; }
+        tab[3 * (size_t)k] = h.pl_p[k]; tab[3 * (size_t)k + 1] = h.pl_l[k]; tab[3 * (size_t)k + 2] = src; }
+    if (pp && n > g->d.Epp + g->d.tEpp) return fail(GS_ERR_INVALID, "odometry edge not on the device");
+    int32_t *dtab = nullptr; double *dout = nullptr;
+    HIP_TRY(hipMalloc((void **)&dtab, tab.size() * sizeof(int32_t)));
+    if (hipMalloc((void **)&dout, (size_t)n * 2 * sizeof(double)) != hipSuccess) { hipFree(dtab); return fail(GS_ERR_HIP, "hipMalloc failed"); }
+    std::vector<double> out((size_t)n * 2);
+    hipError_t e = hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, g->stream);
+    if (e == hipSuccess) { launch_edge_chi2(g->d, edge_kind, n, dtab, dout, g->stream); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpyAsync(out.data(), dout, out.size() * sizeof(double), hipMemcpyDeviceToHost, g->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(g->stream); else hipStreamSynchronize(g->stream);
+    hipFree(dtab); hipFree(dout);
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("edge chi2: ") + hipGetErrorString(e));
+    if (out_chi2) std::memcpy(out_chi2, out.data(), (size_t)n * sizeof(double));
+    if (out_weight) std::memcpy(out_weight, out.data() + n, (size_t)n * sizeof(double));
+    return n;
+}
+extern "C" int gs_export_delta(gs_graph *g, double *dpose, double *dlm) {
+    if (!g) return fail(GS_ERR_INVALID, "null graph");
+    if (!g->dev_valid) return fail(GS_ERR_NOT_INITIALIZED, "no iteration run yet");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (dpose && g->d.N) HIP_TRY(hipMemcpyAsync(dpose, g->d.dpose, (size_t)(g->d.N + g->d.tN) * 3 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    if (dlm && g->d.M) HIP_TRY(hipMemcpyAsync(dlm, g->d.dlm, (size_t)(g->d.M + g->d.tM) * 2 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    return GS_OK;
+}
+extern "C" int gs_time_iterations(gs_graph *g, int32_t reps, gs_stats *s) {
+    if (!g || !s || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
+    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: time the two halves from the caller");
+    int rc = ensure_ready(g); if (rc != GS_OK) return rc;
+    const int N = g->d.N + g->d.tN, M = g->d.M + g->d.tM;
+    double *sp = nullptr, *sl = nullptr;                        // save estimates
+    HIP_TRY(hipMalloc((void **)&sp, std::max<size_t>((size_t)N * 3, 1) * sizeof(double)));
+    HIP_TRY(hipMalloc((void **)&sl, std::max<size_t>((size_t)M * 2, 1) * sizeof(double)));
+    hipMemcpyAsync(sp, g->d.pose_est, (size_t)N * 3 * sizeof(double), hipMemcpyDeviceToDevice, g->stream);
+    hipMemcpyAsync(sl, g->d.lm_est, (size_t)M * 2 * sizeof(double), hipMemcpyDeviceToDevice, g->stream);
+    const bool newer = g->dev_estimates_newer;
+    std::memset(s, 0, sizeof(*s)); s->struct_size = (int32_t)sizeof(*s); fill_plan_stats(g, s);
+    enqueue_iteration(g, false);                                 // warm
+    // all repetitions are enqueued back to back like the iterations of gs_optimize (no host round trip in between);
+    // every repetition has its own five phase events plus a sixth right behind the fifth: that empty interval is what
+    // one event boundary costs on this stream (ms_event_overhead), i.e. how much of each phase time is the measurement
+    // ... then `reps` more iterations with a start / stop pair attached to the linearisation kernel's own dispatch (hipExtLaunchKernelGGL):
+    // its begin -> end as a kernel trace reports it, without the hand-over from k_update that the event-to-event interval also holds
+    std::vector<hipEvent_t> evs((size_t)reps * 8);
+    for (auto &e : evs) HIP_TRY(hipEventCreate(&e));
+    hipEvent_t saved[5]; for (int k = 0; k < 5; ++k) saved[k] = g->ev[k];
+    for (int r = 0; r < reps; ++r) {
+        for (int k = 0; k < 5; ++k) g->ev[k] = evs[(size_t)r * 8 + k];
+        enqueue_iteration(g, true);
+        hipEventRecord(evs[(size_t)r * 8 + 5], g->stream);
+    }
+    for (int k = 0; k < 5; ++k) g->ev[k] = saved[k];
+    // second pass, nothing recorded between the phases (a dispatch with events attached lengthens the event-to-event interval
+    // around it by ~10 us: the two measurements do not share iterations)
+    for (int r = 0; r < reps; ++r) {
+        g->ev_lin[0] = evs[(size_t)r * 8 + 6]; g->ev_lin[1] = evs[(size_t)r * 8 + 7];
+        enqueue_iteration(g, false);
+    }
+    g->ev_lin[0] = g->ev_lin[1] = nullptr;
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    double ovh = 0.0, link = 0.0; int nlink = 0;
+    for (int r = 0; r < reps; ++r) { const hipEvent_t *e = &evs[(size_t)r * 8];
+        float a = 0, b = 0, c = 0, dd = 0, o = 0, lk = 0;
+        hipEventElapsedTime(&a, e[0], e[1]); hipEventElapsedTime(&b, e[1], e[2]);
+        hipEventElapsedTime(&c, e[2], e[3]); hipEventElapsedTime(&dd, e[3], e[4]); hipEventElapsedTime(&o, e[4], e[5]);
+        if (hipEventElapsedTime(&lk, e[6], e[7]) == hipSuccess && lk > 0) { link += lk; ++nlink; }     // (the gather path launches several kernels: no pair)
+        s->ms_linearize += a; s->ms_factor += b; s->ms_backsolve += c; s->ms_update += dd; ovh += o; }
+    (void)hipGetLastError();
+    for (auto &e : evs) hipEventDestroy(e);
+    s->ms_linearize /= reps; s->ms_factor /= reps; s->ms_backsolve /= reps; s->ms_update /= reps; s->ms_event_overhead = ovh / reps;
+    s->ms_linearize_kernel = nlink > 0 ? link / nlink : 0.0;
+    s->ms_total = s->ms_linearize + s->ms_factor + s->ms_backsolve + s->ms_update; s->iterations = reps;
+    hipMemcpyAsync(g->d.pose_est, sp, (size_t)N * 3 * sizeof(double), hipMemcpyDeviceToDevice, g->stream);
+    launch_pose_trig(g->d, g->stream);
+    hipMemcpyAsync(g->d.lm_est, sl, (size_t)M * 2 * sizeof(double), hipMemcpyDeviceToDevice, g->stream);
+    int32_t failflag = 0;
+    hipMemcpyAsync(&failflag, g->d.fail, sizeof(int32_t), hipMemcpyDeviceToHost, g->stream);
+    hipMemsetAsync(g->d.fail, 0, sizeof(int32_t), g->stream);
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    hipFree(sp); hipFree(sl);
+    g->dev_estimates_newer = newer; s->numeric_failure = failflag;
+    return GS_OK;
+}

@@ -140,7 +140,7 @@ def test_tuning_switches_live_in_one_struct_outside_the_public_header(pkg, monke
     assert "gs_debug" not in pub and "getenv" not in pub
     dbg = set(pkg.binding.declared_symbols()) - set(pkg.binding.declared_symbols(debug=False))
     assert {"gs_debug_options_default", "gs_debug_get_options", "gs_debug_set_options", "gs_debug_fail_at_iteration",
-            "gs_debug_select_factor_variant", "gs_debug_timestamps", "gs_debug_front_times"} <= dbg
+            "gs_debug_select_factor_variant", "gs_debug_timestamps", "gs_debug_front_times", "gs_debug_schedule_export"} <= dbg
     d = pkg.binding.DebugOptions(); assert pkg.binding.lib().gs_debug_options_default(d) == 0
     assert d.struct_size == C.sizeof(pkg.binding.DebugOptions)
     assert (d.tree, d.block_fronts, d.leaf_min, d.grow, d.grow_min_poses, d.assoc_grid, d.force_shared_top) == (1, 512, 2048, 1, 128, -1, 0)

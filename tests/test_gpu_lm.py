@@ -470,3 +470,21 @@ def test_zero_pivot_in_a_trial_is_a_rejection(pkg, po, bench_graphs):
     assert e_est <= max(4 * y, 1e-9) and e_lam <= max(4 * y, 1e-9)
     done, st = G.optimize(2); assert done == 2 and st.numeric_failure == 0
     G.close()
+
+
+# ---------------------------------------------------------------- 11. a flag timeout inside an LM call
+def test_flag_timeout_falls_back_to_level_launches_and_finishes(pkg, bench_graphs):
+    """The branch gs_optimize_lm shares with gs_optimize: gs_debug_fail_at_iteration arms code 2 (a whole-tree launch gave up on a front's
+    flag; the hook sets the status word, nothing stalls) on the first trial.  The call falls back to one launch per level, runs the trial
+    again and finishes: three accepted iterations, and — the launch modes being bit-identical — the estimates of an uninjected handle."""
+    _, g = bench_graphs(1000, 200)
+    A = fresh(pkg, g); da, sa, _ = A.optimize_lm(3)
+    G = fresh(pkg, g); G.initialize_optimization()
+    G.debug_fail_at_iteration(1, 2)
+    done, st, info = G.optimize_lm(3)
+    print("LM through a flag timeout: accepted %d (uninjected %d) first_failure %d fell_back %d numeric_failure %d n_trials %s"
+          % (done, da, st.first_failure, st.fell_back, st.numeric_failure, info["n_trials"].tolist()))
+    assert st.first_failure == 2 and st.fell_back == 1 and st.numeric_failure == 0
+    assert done == 3 and da == 3 and sa.fell_back == 0 and sa.first_failure == 0
+    assert np.array_equal(G.poses(), A.poses()) and np.array_equal(G.landmarks(), A.landmarks())
+    A.close(); G.close()
