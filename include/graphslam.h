@@ -131,6 +131,8 @@ typedef struct gs_stats {
                                     is event to event on the stream: it also holds the hand-over from the previous kernel) */
     int32_t n_growths;          /* append-only growth steps the current plan has absorbed since the last full structure phase (0: none) */
     int32_t n_subtrees;         /* level-1 fronts that run with the leaves below them in ONE workgroup (k_factor3_sub; known after the first iteration of a plan) */
+    int32_t n_pose_priors, n_landmark_priors;   /* prior edges the handle holds (gs_add_*_prior; XY priors count as pose priors).  The last fields so far:
+                                   present when the struct_size the library writes is >= offsetof(gs_stats, n_landmark_priors) + 4 */
 } gs_stats;
 
 int  gs_version(void);                               /* major*100+minor */
@@ -141,7 +143,7 @@ int  gs_device_count(void);                           /* number of usable gfx950
 /* ---- lifetime: replaces Slam::setupOptimizer (src/slam.cpp:53-65) -------- */
 int  gs_create(const gs_config *cfg, gs_graph **out);
 int  gs_destroy(gs_graph *g);
-int  gs_clear(gs_graph *g);                           /* drop all vertices and edges */
+int  gs_clear(gs_graph *g);                           /* drop all vertices, edges and priors */
 /* use an externally owned hipStream_t (e.g. torch's current stream); NULL = own stream */
 int  gs_set_stream(gs_graph *g, void *hip_stream);
 /* Device memory for the first structure phase, taken (and touched) now — e.g. at start-up, where the reference constructs its
@@ -311,6 +313,49 @@ int  gs_optimize_lm(gs_graph *g, int32_t iterations, const gs_lm_params *p /* NU
 int  gs_set_robust_kernel(gs_graph *g, int32_t edge_kind, int32_t kernel, double delta);
 int  gs_get_robust_kernel(gs_graph *g, int32_t edge_kind, int32_t *out_kernel, double *out_delta);
 int  gs_get_edge_chi2(gs_graph *g, int32_t edge_kind, int32_t capacity, double *out_chi2, double *out_weight);
+
+/* ---- prior edges ------------------------------------------------------------
+ * Unary edges: "this vertex is about HERE, with this uncertainty" — an absolute measurement (a GPS fix), or a soft gauge in place of a
+ * fixed flag.  <- g2o EdgeSE2Prior, EdgeSE2XYPrior, EdgeXYPrior (the reference adds none; the formulas are restated from g2o's
+ * published text, not pinned against a g2o build: g2o is not part of this project's checkers).
+ *   gs_add_pose_prior      z = (zx, zy, ztheta), Omega 3x3:  e = vec(z^-1 o x), i.e. e_t = R_z^T (t - t_z), e_theta = normalize(theta - ztheta);
+ *                          J = diag(R_z^T, 1) with the additive update of gs_iterate
+ *   gs_add_pose_xy_prior   z = (zx, zy), Omega 2x2:  e = t - z (position only, no heading: the GPS case) — the pose prior with ztheta = 0
+ *                          and Omega in the upper-left 2x2 of a 3x3 that is zero elsewhere, and stored as one
+ *   gs_add_landmark_prior  z = (zx, zy), Omega 2x2:  e = l - z, J = I
+ * A prior contributes J^T Omega J to the diagonal block of its vertex, -J^T Omega e to its right-hand side and e^T Omega e to chi2 —
+ * nothing else: no off-diagonal block, so the plan, the fronts and the launch schedule do not change.  ADDING OR CLEARING PRIORS IS NOT
+ * A STRUCTURAL CHANGE: it triggers no structure phase and does not turn a growth step into a full phase (a keyframe appended together
+ * with its GPS prior is absorbed by growth); the prior tables travel whole to the device at the next call that computes.  Like any
+ * change it makes the marginals stale.  A handle without priors runs exactly the launches it ran before.
+ * A prior on a FIXED vertex is accepted and stays out of H, b and chi2 (g2o: an edge whose vertices are all fixed is inactive).
+ * Several priors on one vertex are summed in insertion order.  Every chi2 the library reports includes the priors (gs_chi2,
+ * gs_stats.chi2_*, the verbose line, the stop rule of gs_optimize_until, chi_old / chi_new of gs_optimize_lm); gs_export_system
+ * returns H and b with them, gs_compute_marginals inverts that H — with a prior in place of a fixed flag every vertex has a covariance.
+ * information: row-major full (9 resp. 4 doubles), symmetric, REQUIRED (also in the bulk forms).  Priors belong to their vertices:
+ * gs_clear drops them; gs_clear_priors drops all of them and nothing else.
+ * gs_num_pose_priors counts the XY priors too.
+ * gs_get_prior_chi2: per prior of the kind (0 pose, 1 landmark), insertion order, e^T Omega e at the CURRENT estimates; priors on
+ *      fixed vertices are reported too (they stay out of chi2).  out_chi2 may be NULL; returns the number of priors (GS_ERR_CAPACITY
+ *      when capacity is below it and a pointer is given); a host-only handle GS_ERR_NO_DEVICE, a sharded handle GS_ERR_INVALID.
+ * Errors: unknown id GS_ERR_UNKNOWN_ID; a null pointer, a z that is not finite, an information matrix that gs_add_*_edge would
+ *      refuse: GS_ERR_INVALID.  On a host-only handle everything but gs_get_prior_chi2 works.
+ * NOT DONE: robust kernels are not applied to priors (weight 1 whatever gs_set_robust_kernel says); pose-window shards — a gs_add_*_prior
+ *      on a handle configured with gs_dist_configure(world > 1), and gs_dist_configure(world > 1) on a handle that holds priors, return
+ *      GS_ERR_INVALID; a FREE landmark whose only measurement is a prior (the fused linearisation keeps a landmark's block in the
+ *      partial-sum slots of its observation edges; without one there is no address for it): the next computing call returns
+ *      GS_ERR_INVALID with a message, on both linearisation paths, until the prior is cleared or an observation edge is added;
+ *      removal of single priors; the Slam mirror and the microservice shell add no priors. */
+int  gs_add_pose_prior(gs_graph *g, int32_t pose_id, const double z_xytheta[3], const double information[9]);
+int  gs_add_pose_xy_prior(gs_graph *g, int32_t pose_id, const double z_xy[2], const double information[4]);
+int  gs_add_landmark_prior(gs_graph *g, int32_t lm_id, const double z_xy[2], const double information[4]);
+int  gs_add_pose_priors(gs_graph *g, int32_t count, const int32_t *pose_ids, const double *z_xytheta, const double *information /* count*9 */);
+int  gs_add_pose_xy_priors(gs_graph *g, int32_t count, const int32_t *pose_ids, const double *z_xy, const double *information /* count*4 */);
+int  gs_add_landmark_priors(gs_graph *g, int32_t count, const int32_t *lm_ids, const double *z_xy, const double *information /* count*4 */);
+int  gs_num_pose_priors(gs_graph *g);
+int  gs_num_landmark_priors(gs_graph *g);
+int  gs_clear_priors(gs_graph *g);
+int  gs_get_prior_chi2(gs_graph *g, int32_t kind /* 0 pose, 1 landmark */, int32_t capacity, double *out_chi2);
 
 /* ---- measurement / parity hooks (tuning, fault injection and timestamps: include/graphslam_debug.h) ----------
  * gs_linearize: one A5+A6+A7 pass (the roofline kernel) on the stream, nothing else.

@@ -60,7 +60,8 @@ class Stats(C.Structure):
                 ("factor_flops", C.c_int64), ("factor_bytes", C.c_int64), ("ms_event_overhead", C.c_double),
                 ("fell_back", C.c_int32), ("first_failure", C.c_int32), ("factor_variant", C.c_int32), ("n_big_fronts", C.c_int32),
                 ("device_bytes", C.c_int64), ("n_own_fronts", C.c_int32), ("n_shared_fronts", C.c_int32), ("ms_plan_host", C.c_double),
-                ("ms_linearize_kernel", C.c_double), ("n_growths", C.c_int32), ("n_subtrees", C.c_int32)]
+                ("ms_linearize_kernel", C.c_double), ("n_growths", C.c_int32), ("n_subtrees", C.c_int32),
+                ("n_pose_priors", C.c_int32), ("n_landmark_priors", C.c_int32)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -255,6 +256,14 @@ def lib():
     if hasattr(L, "gs_optimize_lm"):                       # (a tuning build of an older tree loaded through GS_LIB may predate Levenberg-Marquardt)
         L.gs_lm_params_default.argtypes = [C.POINTER(LmParams)]
         L.gs_optimize_lm.argtypes = [vp, C.c_int32, C.POINTER(LmParams), C.POINTER(Stats), C.POINTER(LmInfo)]
+    if hasattr(L, "gs_add_pose_prior"):                    # (a tuning build of an older tree loaded through GS_LIB may predate the prior edges)
+        for name in ("gs_add_pose_prior", "gs_add_pose_xy_prior", "gs_add_landmark_prior"):
+            getattr(L, name).argtypes = [vp, C.c_int32, _dp, _dp]
+        for name in ("gs_add_pose_priors", "gs_add_pose_xy_priors", "gs_add_landmark_priors"):
+            getattr(L, name).argtypes = [vp, C.c_int32, _ip, _dp, _dp]
+        for name in ("gs_num_pose_priors", "gs_num_landmark_priors", "gs_clear_priors"):
+            getattr(L, name).argtypes = [vp]
+        L.gs_get_prior_chi2.argtypes = [vp, C.c_int32, C.c_int32, _dp]
     L.gs_slam_get_send_pose.argtypes = [vp, _dp]
     L.gs_slam_collect_direction.argtypes = [vp, C.c_uint32, C.c_double, C.c_double]
     L.gs_slam_collect_distance.argtypes = [vp, C.c_uint32, C.c_double]
@@ -622,6 +631,41 @@ class Graph:
         n = self.n_pp if kd == 0 else self.n_pl
         s = np.zeros(n); w = np.zeros(n)
         self._check(self.L.gs_get_edge_chi2(self.h, kd, n, _d(s), _d(w))); return s, w
+
+    # ---- prior edges (gs_add_*_prior: unary edges on a pose or a landmark; information full, row-major, required)
+    def add_pose_prior(self, pid, z, info):
+        """z = (x, y, theta), information 3x3"""
+        z = _f64(z); info = _f64(info); self._check(self.L.gs_add_pose_prior(self.h, int(pid), _d(z), _d(info)))
+
+    def add_pose_xy_prior(self, pid, z, info):
+        """position only (the GPS case): z = (x, y), information 2x2"""
+        z = _f64(z); info = _f64(info); self._check(self.L.gs_add_pose_xy_prior(self.h, int(pid), _d(z), _d(info)))
+
+    def add_landmark_prior(self, lid, z, info):
+        z = _f64(z); info = _f64(info); self._check(self.L.gs_add_landmark_prior(self.h, int(lid), _d(z), _d(info)))
+
+    def add_pose_priors(self, ids, z, info):
+        ids = _i32(ids); z = _f64(z); info = _f64(info); self._check(self.L.gs_add_pose_priors(self.h, len(ids), _i(ids), _d(z), _d(info)))
+
+    def add_pose_xy_priors(self, ids, z, info):
+        ids = _i32(ids); z = _f64(z); info = _f64(info); self._check(self.L.gs_add_pose_xy_priors(self.h, len(ids), _i(ids), _d(z), _d(info)))
+
+    def add_landmark_priors(self, ids, z, info):
+        ids = _i32(ids); z = _f64(z); info = _f64(info); self._check(self.L.gs_add_landmark_priors(self.h, len(ids), _i(ids), _d(z), _d(info)))
+
+    @property
+    def n_pose_priors(self): return self._check(self.L.gs_num_pose_priors(self.h))
+    @property
+    def n_landmark_priors(self): return self._check(self.L.gs_num_landmark_priors(self.h))
+
+    def clear_priors(self):
+        self._check(self.L.gs_clear_priors(self.h))
+
+    def prior_chi2(self, kind):
+        """e^T Omega e of every prior of the kind ("pose" / "landmark" or 0 / 1) at the current estimates, insertion order"""
+        kd = int({"pose": 0, "landmark": 1}.get(kind, kind))
+        n = self._check(self.L.gs_get_prior_chi2(self.h, kd, 0, None)); out = np.zeros(n)
+        self._check(self.L.gs_get_prior_chi2(self.h, kd, n, _d(out))); return out
 
     # ---- host-only plan (no device work)
     def plan_build_host(self):

@@ -185,6 +185,7 @@ extern "C" int gs_destroy(gs_graph *g) {
     hipStreamSynchronize(g->stream);
     dev_free_all(g);
     if (g->lm.mem) hipFree(g->lm.mem);
+    if (g->prior.mem) hipFree(g->prior.mem);
     gs_dist_comm_release(g);
     gs_frontend_release(g);
     for (auto &e : g->ev) hipEventDestroy(e);
@@ -197,6 +198,7 @@ extern "C" int gs_clear(gs_graph *g) {
     if (!g) return fail(GS_ERR_INVALID, "null graph");
     if (!g->host_only) { hipSetDevice(g->device); hipStreamSynchronize(g->stream); dev_free_all(g); }
     g->h.clear(); g->plan = Plan(); g->plan_version = ~0ull;
+    g->prior.store.clear(); g->prior.dev.n_pv = g->prior.dev.n_lv = 0; g->prior.sync.invalidate();      // the priors go with their vertices
     return GS_OK;
 }
 
@@ -267,7 +269,7 @@ extern "C" int gs_add_landmark(gs_graph *g, int32_t id, const double est[2]) {
     ++g->h.structure_version;
     return GS_OK;
 }
-static bool sym_ok(const double *m, int n) {
+bool sym_ok(const double *m, int n) {
     for (int r = 0; r < n; ++r) for (int c = 0; c < r; ++c) {
         double a = m[r * n + c], b = m[c * n + r];
         if (!(std::fabs(a - b) <= 1e-12 * (std::fabs(a) + std::fabs(b)) + 1e-300)) return false;
@@ -994,12 +996,29 @@ extern "C" int gs_debug_schedule_export(gs_graph *g, int32_t *out, int64_t *out_
     return GS_OK;
 }
 
+// host-side setEstimate since the upload: the estimates (and the poses' cos / sin) to the device of the current plan
+static int push_estimates(gs_graph *g) {
+    if (g->dev_estimate_version == g->h.estimate_version) return GS_OK;
+    const int N = g->d.N + g->d.tN, M = g->d.M + g->d.tM;
+    if (N > 0) HIP_TRY(hipMemcpyAsync(g->d.pose_est, g->h.pose_est.data(), (size_t)N * 3 * sizeof(double), hipMemcpyHostToDevice, g->stream));
+    if (M > 0) HIP_TRY(hipMemcpyAsync(g->d.lm_est, g->h.lm_est.data(), (size_t)M * 2 * sizeof(double), hipMemcpyHostToDevice, g->stream));
+    launch_pose_trig(g->d, g->stream);
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    g->dev_estimate_version = g->h.estimate_version; g->dev_estimates_newer = false;
+    return GS_OK;
+}
 extern "C" int gs_initialize_optimization(gs_graph *g) {
     if (!g) return fail(GS_ERR_INVALID, "null graph");
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
     auto t0 = std::chrono::steady_clock::now();
     rc = pull_estimates_if_needed(g); if (rc != GS_OK) return rc;
     HIP_TRY(hipStreamSynchronize(g->stream));
+    // priors added or cleared since the last call, nothing else: not a structural change — the plan on the device stays (grown or not),
+    // the prior tables go up.  (A call with NO change at all still rebuilds, as g2o's initializeOptimization does.)
+    if (g->dev_valid && g->plan.valid && g->plan_version == g->h.structure_version && g->prior.store.version != g->prior.settled) {
+        g->no_growth_reason.clear();
+        rc = push_estimates(g); if (rc != GS_OK) return rc;          // (what the rebuild this call replaces would have uploaded: gs_iterate does not look)
+        return prior_sync(g); }
     // append-only growth: poses / edges added since the plan was built enter the existing plan and device tables (gs::grow_plan,
     // upload_growth); anything else — or GS_GROW=0 — rebuilds
     g->no_growth_reason.clear();
@@ -1043,16 +1062,9 @@ extern "C" int gs_initialize_optimization(gs_graph *g) {
 
 int ensure_ready(gs_graph *g) {
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (!g->dev_valid || g->plan_version != g->h.structure_version) return gs_initialize_optimization(g);
-    if (g->dev_estimate_version != g->h.estimate_version) {      // host-side setEstimate since the upload
-        const int N = g->d.N + g->d.tN, M = g->d.M + g->d.tM;
-        if (N > 0) HIP_TRY(hipMemcpyAsync(g->d.pose_est, g->h.pose_est.data(), (size_t)N * 3 * sizeof(double), hipMemcpyHostToDevice, g->stream));
-        if (M > 0) HIP_TRY(hipMemcpyAsync(g->d.lm_est, g->h.lm_est.data(), (size_t)M * 2 * sizeof(double), hipMemcpyHostToDevice, g->stream));
-        launch_pose_trig(g->d, g->stream);
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        g->dev_estimate_version = g->h.estimate_version; g->dev_estimates_newer = false;
-    }
-    return GS_OK;
+    if (!g->dev_valid || g->plan_version != g->h.structure_version) { rc = gs_initialize_optimization(g); return rc != GS_OK ? rc : prior_sync(g); }
+    if ((rc = push_estimates(g)) != GS_OK) return rc;
+    return prior_sync(g);                                            // (nothing without priors)
 }
 
 void fill_plan_stats(gs_graph *g, gs_stats *s) {
@@ -1070,6 +1082,7 @@ void fill_plan_stats(gs_graph *g, gs_stats *s) {
     s->device_bytes = (int64_t)g->pool_total; s->ms_plan_host = P.ms_build; s->n_growths = P.n_growths;
     s->n_own_fronts = (int32_t)P.level_fronts_owned.size(); s->n_shared_fronts = (int32_t)P.level_fronts_shared.size();
     s->n_subtrees = g->sched.sub_n;
+    s->n_pose_priors = g->prior.store.n_pose(); s->n_landmark_priors = g->prior.store.n_lm();
 }
 
 extern "C" int gs_get_stats(gs_graph *g, gs_stats *s) {

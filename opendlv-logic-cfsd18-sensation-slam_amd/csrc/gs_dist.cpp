@@ -21,6 +21,8 @@ extern "C" int gs_dist_configure(gs_graph *g, int32_t rank, int32_t world) {
     if (!g || world < 1 || rank < 0 || rank >= world) return fail(GS_ERR_INVALID, "bad rank/world");
     if (world > 1 && (g->cfg.odometry_robust_kernel != GS_ROBUST_NONE || g->cfg.observation_robust_kernel != GS_ROBUST_NONE))
         return fail(GS_ERR_INVALID, "robust kernels are not supported on sharded handles: set GS_ROBUST_NONE on both edge kinds first");
+    if (world > 1 && !g->prior.store.empty())
+        return fail(GS_ERR_INVALID, "prior edges are not supported on sharded handles: gs_clear_priors first");
     g->rank = rank; g->world = world; ++g->h.structure_version; ++g->h.reshape_version;
     return GS_OK;
 }
@@ -73,6 +75,7 @@ static int dist_ready(gs_graph *g) {
     if (!g) return fail(GS_ERR_INVALID, "null graph");
     if (!g->dev_valid || g->plan_version != g->h.structure_version) return fail(GS_ERR_NOT_INITIALIZED, "call gs_initialize_optimization first");
     if (g->plan.dist && !g->d.exchange) return fail(GS_ERR_NOT_INITIALIZED, "no exchange buffer");
+    if (!g->prior.store.empty()) return fail(GS_ERR_INVALID, "prior edges are not supported by the two-half (sharded) iteration");
     return ensure_device(g);
 }
 extern "C" int gs_dist_iterate_local(gs_graph *g) {

@@ -11,6 +11,7 @@
 #include "gs_device.hpp"
 #include "gs_host.hpp"
 #include "gs_lm.hpp"
+#include "gs_prior.hpp"
 #include "gs_schedule.hpp"
 
 struct gs_graph {
@@ -86,6 +87,10 @@ struct gs_graph {
     // gs_optimize_lm: the device state record, history, base copy of the estimates and reduction partials (gs_lm.hpp) — one allocation of
     // the handle's own, grow-only, sized for cap_p poses / cap_l landmarks (tail included)
     struct Lm { gs::LmDev dev{}; void *mem = nullptr; size_t cap_p = 0, cap_l = 0; gs::LmState host[2]{}; } lm;
+    // prior edges (gs_prior.hpp): the priors as added, the grouped tables, and their device copy — one allocation of the handle's own,
+    // grow-only; uploaded whole by prior_sync when the priors or the plan changed.  dev stays empty while there is no prior on a free vertex
+    struct Prior { gs::PriorStore store; gs::PriorTables tab; gs::PriorSync sync; gs::PriorDev dev{}; void *mem = nullptr; size_t cap = 0;
+                   uint64_t settled = 0; /* store.version prior_sync last looked at */ } prior;
 };
 
 namespace gs {

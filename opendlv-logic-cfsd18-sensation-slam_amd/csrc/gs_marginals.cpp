@@ -105,8 +105,7 @@ extern "C" int gs_compute_marginals(gs_graph *g, gs_marginals_info *info) {
     const int ii = g->d.inject_iter, ic = g->d.inject_code; g->d.inject_iter = 0;      // (fault injection belongs to the iterations: kept armed for them)
     g->d.dpiv = M.dpiv;                                             // the LDL^T factor kernels write D (variant 4: L L^T, nothing to capture)
     hipEventRecord(g->ev[0], g->stream);
-    launch_linearize(g->d, g->stream);
-    launch_linearize_tail(g->d, g->stream);
+    enqueue_linearize(g);
     enqueue_factor_levels(g, g->sched.own, 0, 0);
     hipEventRecord(g->ev[1], g->stream);
     const int nlev = (int)g->sched.own.start.size() - 1;

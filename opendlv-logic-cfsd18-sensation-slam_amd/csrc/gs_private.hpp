@@ -47,13 +47,19 @@ template <class T> int dev_alloc(gs_graph *g, T **ptr, size_t count) {
 }
 
 // gs_api.cpp
+bool sym_ok(const double *m, int n);           // the information-matrix check of every gs_add_*_edge / gs_add_*_prior
 int ensure_device(gs_graph *g);
 int ensure_ready(gs_graph *g);                 // the structure phase if the graph changed, host-side estimates to the device
 int pull_estimates_if_needed(gs_graph *g);
 int pull_estimates_enqueue(gs_graph *g, bool &pull);        // the copies only: they come back with the caller's next wait, which then clears dev_estimates_newer if `pull`
 int reset_failure(gs_graph *g);
 void fill_plan_stats(gs_graph *g, gs_stats *s);
+// gs_prior_api.cpp
+int prior_sync(gs_graph *g);                   // the prior tables to the device when the priors or the plan changed (ensure_ready, gs_iterate); nothing without priors
 // gs_solve.cpp
+// every linearisation of H and every chi2 pass goes through these two, so that no site can leave the priors out
+void enqueue_linearize(gs_graph *g, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);   // linearise + a grown plan's tail + the priors (start / stop: on the linearisation dispatch)
+void enqueue_chi2(gs_graph *g);                // chi2 at the current estimates -> chi2[0], priors included
 void enqueue_factor_levels(gs_graph *g, const gs::LevelSet &ls, int base, int mode);
 void enqueue_local(gs_graph *g, bool timed);
 void enqueue_finish(gs_graph *g, bool timed);

@@ -31,13 +31,26 @@ struct Launcher {
 };
 }  // namespace
 void enqueue_factor_levels(gs_graph *g, const LevelSet &ls, int base, int mode) { Launcher L{g}; walk_factor_levels(g->sched, g->d.tree != 0, ls, base, mode, L); }
+// linearise -> tail -> priors.  The prior total of chi2 goes where this pass's total is formed from: a partial k_update / k_linearize_finalize
+// sum (fused kernel), or chi2[0] (gather kernels: k_reduce_chi2 has totalled it).  A handle without priors launches what it always did
+void enqueue_linearize(gs_graph *g, hipEvent_t start, hipEvent_t stop) {
+    launch_linearize(g->d, g->stream, start, stop);
+    launch_linearize_tail(g->d, g->stream);                          // a grown plan's tail (no launch without one)
+    const bool fused = g->d.n_wtiles > 0;
+    if (fused && g->d.wt_hi <= g->d.wt_lo && prior_grid(g->prior.dev) > 0)      // no wave tile swept, no launch above: nobody has written the slot the pass adds to
+        hipMemsetAsync(g->d.chi2_partial, 0, sizeof(double), g->stream);
+    launch_prior_pass(g->d, g->prior.dev, true, fused ? g->d.chi2_partial : g->d.chi2, g->stream);
+}
+void enqueue_chi2(gs_graph *g) {
+    launch_chi2_only(g->d, g->stream);
+    launch_prior_pass(g->d, g->prior.dev, false, g->d.chi2, g->stream);
+}
 // pose-window shards, first half: linearise this shard's edges, factorise its own subtrees, write its contribution
 // to every shared front into the exchange buffer (the caller all-reduces that buffer: RCCL sum, fp64)
 void enqueue_local(gs_graph *g, bool timed) {
     ++g->d.iter;                                                     // kernels see the iteration they belong to (fault injection, gs_debug_fail_at_iteration)
     if (timed) hipEventRecord(g->ev[0], g->stream);
-    launch_linearize(g->d, g->stream, g->ev_lin[0], g->ev_lin[1]);   // (null outside gs_time_iterations' second pass)
-    launch_linearize_tail(g->d, g->stream);                          // a grown plan's tail (no launch without one)
+    enqueue_linearize(g, g->ev_lin[0], g->ev_lin[1]);                // (null outside gs_time_iterations' second pass)
     if (timed) hipEventRecord(g->ev[1], g->stream);
     Launcher L{g}; walk_local(g->sched, g->d.tree != 0, L);
 }
@@ -59,6 +72,7 @@ extern "C" int gs_iterate(gs_graph *g) {
     if (!g->dev_valid || g->plan_version != g->h.structure_version) return fail(GS_ERR_NOT_INITIALIZED, "call gs_initialize_optimization first");
     if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: use gs_dist_iterate (RCCL inside the library) or gs_dist_iterate_local / all-reduce / gs_dist_iterate_finish");
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if ((rc = prior_sync(g)) != GS_OK) return rc;
     enqueue_iteration(g, false);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
@@ -170,7 +184,7 @@ static int optimize_impl(gs_graph *g, int32_t iterations, double rel_tol, gs_sta
     g->d.conv_tol = -1.0;
     if (until) HIP_TRY(hipMemsetAsync(g->d.fail + 2, 0, sizeof(int32_t), g->stream));     // the stop flag must not gate later gs_iterate calls
     const int nshow = std::min(applied, nh);
-    if (g->cfg.verbose || stats) { launch_chi2_only(g->d, g->stream);
+    if (g->cfg.verbose || stats) { enqueue_chi2(g);
         hipMemcpyAsync(g->d.chi2 + 1 + nh, g->d.chi2, sizeof(double), hipMemcpyDeviceToDevice, g->stream); }
     hipEventRecord(g->ev[6], g->stream);
     double hist[80]; float ms;
@@ -220,14 +234,13 @@ static int lm_reserve(gs_graph *g) {
 static void enqueue_lm_trial(gs_graph *g, int par, bool init) {
     const LmDev &lm = g->lm.dev;
     ++g->d.iter;
-    launch_linearize(g->d, g->stream);
-    launch_linearize_tail(g->d, g->stream);
+    enqueue_linearize(g);
     if (init) launch_lm_maxdiag(g->d, lm, g->stream);
     launch_lm_damp(g->d, lm, par, init ? 1 : 0, g->stream);
     enqueue_factor_levels(g, g->sched.own, 0, 0);
     enqueue_finish(g, false);                                        // (no shared top on a single device), back-solve, update
     launch_lm_scale(g->d, lm, par, g->stream);
-    launch_chi2_only(g->d, g->stream);                               // chi2 at x_try -> chi2[0]
+    enqueue_chi2(g);                                                 // chi2 at x_try -> chi2[0]
     launch_lm_step(g->d, lm, par, g->stream);
 }
 extern "C" int gs_optimize_lm(gs_graph *g, int32_t iterations, const gs_lm_params *params, gs_stats *stats, gs_lm_info *info) {
@@ -268,7 +281,7 @@ extern "C" int gs_optimize_lm(gs_graph *g, int32_t iterations, const gs_lm_param
         if (next == RUN_STOP) break;                                // (RUN_RERUN: the trials behind the timeout were no-ops: the loop runs them again, one launch per level)
     }
     HIP_TRY(hipMemsetAsync(g->d.fail + 1, 0, 2 * sizeof(int32_t), g->stream));     // the update count and the stop flag must not gate later gs_iterate calls
-    if (S.trials == 0 && (stats || info || g->cfg.verbose)) launch_chi2_only(g->d, g->stream);     // nothing ran: chi2 at the estimates as they are
+    if (S.trials == 0 && (stats || info || g->cfg.verbose)) enqueue_chi2(g);     // nothing ran: chi2 at the estimates as they are
     hipEventRecord(g->ev[6], g->stream);
     double chi_here = 0.0, hc[64], hl[64]; int32_t ht[64];
     HIP_TRY(hipMemcpyAsync(&chi_here, g->d.chi2, sizeof(double), hipMemcpyDeviceToHost, g->stream));
@@ -295,7 +308,7 @@ extern "C" int gs_optimize_lm(gs_graph *g, int32_t iterations, const gs_lm_param
 extern "C" int gs_chi2(gs_graph *g, double *out) {
     if (!g || !out) return fail(GS_ERR_INVALID, "null argument");
     int rc = ensure_ready(g); if (rc != GS_OK) return rc;
-    launch_chi2_only(g->d, g->stream);
+    enqueue_chi2(g);
     HIP_TRY(hipMemcpyAsync(out, g->d.chi2, sizeof(double), hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
     return GS_OK;
@@ -305,8 +318,7 @@ extern "C" int gs_chi2(gs_graph *g, double *out) {
 extern "C" int gs_linearize(gs_graph *g) {
     if (!g) return fail(GS_ERR_INVALID, "null graph");
     int rc = ensure_ready(g); if (rc != GS_OK) return rc;
-    launch_linearize(g->d, g->stream);
-    launch_linearize_tail(g->d, g->stream);
+    enqueue_linearize(g);
     launch_linearize_finalize(g->d, g->stream);              // stand-alone pass: materialise H_ll, b_l, chi2 for export
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("linearize: ") + hipGetErrorString(e));

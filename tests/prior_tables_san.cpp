@@ -1,0 +1,91 @@
+// prior_tables_san.cpp — stand-alone check of the host side of the prior edges (csrc/gs_prior_host.hpp: the store, the grouping by
+// vertex, the structure-of-arrays packing, the refusals and the "does the device copy need to go up again" rule), with its own main().
+// Built and run on the host with the sanitizers, no HIP and no GPU:
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined tests/prior_tables_san.cpp -o prior_tables_san && ./prior_tables_san
+#include "../opendlv-logic-cfsd18-sensation-slam_amd/csrc/gs_prior_host.hpp"
+
+#include <cstdio>
+#include <cstdlib>
+#include <random>
+
+using namespace gs;
+
+#define CHECK(c) do { if (!(c)) { std::fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #c); std::exit(1); } } while (0)
+
+static void random_case(unsigned seed, int N, int M, int n_pose, int n_lm) {
+    std::mt19937 rng(seed);
+    std::uniform_real_distribution<double> u(-3.0, 3.0);
+    std::vector<uint8_t> pf((size_t)N, 0), lf((size_t)M, 0);
+    for (int k = 0; k < N; k += 9) pf[(size_t)k] = 1;
+    for (int k = 0; k < M; k += 7) lf[(size_t)k] = 1;
+    std::vector<int32_t> obs((size_t)M, 2);
+    PriorStore S;
+    const uint64_t v0 = S.version;
+    for (int k = 0; k < n_pose; ++k) { const double z[3] = {u(rng), u(rng), 4.0 * u(rng)}, w[6] = {2 + u(rng), u(rng), u(rng), 9, u(rng), 7};
+        S.add_pose((int32_t)(rng() % (unsigned)N), z, w); }
+    for (int k = 0; k < n_lm; ++k) { const double z[2] = {u(rng), u(rng)}, w[3] = {5, u(rng), 6};
+        S.add_lm((int32_t)(rng() % (unsigned)M), z, w); }
+    CHECK(S.version == v0 + (uint64_t)(n_pose + n_lm) && S.n_pose() == n_pose && S.n_lm() == n_lm);
+    PriorTables T; std::string err;
+    CHECK(build_prior_tables(S, pf.data(), N, lf.data(), M, obs.data(), T, err));
+    // every free-vertex prior appears once, in its vertex's run, insertion order inside the run; fixed vertices are not listed
+    auto verify = [&](const std::vector<int32_t> &vert, const std::vector<double> &rec, int per, const std::vector<uint8_t> &fixed,
+                      const std::vector<int32_t> &ids, const std::vector<int32_t> &start, const std::vector<double> &planes, int32_t n_rec) {
+        CHECK(start.size() == ids.size() + 1 && start.front() == 0 && start.back() == n_rec && planes.size() == (size_t)per * (size_t)n_rec);
+        int32_t n_free = 0; for (int32_t v : vert) n_free += !fixed[(size_t)v];
+        CHECK(n_free == n_rec);
+        for (size_t j = 0; j < ids.size(); ++j) {
+            CHECK(!fixed[(size_t)ids[j]] && start[j] < start[j + 1] && (j == 0 || ids[j - 1] < ids[j]));
+            int32_t r = start[j];
+            for (size_t k = 0; k < vert.size(); ++k) if (vert[k] == ids[j]) {
+                for (int c = 0; c < per; ++c) CHECK(planes[(size_t)c * (size_t)n_rec + (size_t)r] == rec[k * (size_t)per + (size_t)c]);
+                ++r; }
+            CHECK(r == start[j + 1]); } };
+    verify(S.pose_v, S.pose_rec, PRIOR_POSE_REC, pf, T.pv_id, T.pv_start, T.pr, T.n_pr);
+    verify(S.lm_v, S.lm_rec, PRIOR_LM_REC, lf, T.lv_id, T.lv_start, T.lr, T.n_lr);
+    CHECK(T.n_vertices() == (int)(T.pv_id.size() + T.lv_id.size()));
+    // the inverse measurement: composing it with z gives the identity, its cos / sin belong to its angle
+    for (int k = 0; k < n_pose; ++k) { const double *r = &S.pose_rec[(size_t)k * PRIOR_POSE_REC];
+        CHECK(std::fabs(r[3] - std::cos(r[2])) < 1e-15 && std::fabs(r[4] - std::sin(r[2])) < 1e-15 && r[2] >= -M_PI && r[2] < M_PI); }
+}
+
+int main() {
+    for (unsigned s = 0; s < 20; ++s) random_case(s, 40 + (int)s * 13, 25 + (int)s * 5, (int)(s * 17) % 90, (int)(s * 11) % 60);
+    random_case(99, 1, 1, 5, 5);                                    // one vertex of each kind carries everything (vertex 0 is fixed here: empty tables)
+    random_case(100, 3000, 700, 4000, 900);
+    {   // empty store, empty graph
+        PriorStore S; PriorTables T; std::string err;
+        CHECK(build_prior_tables(S, nullptr, 0, nullptr, 0, nullptr, T, err));
+        CHECK(T.n_vertices() == 0 && T.pv_start.size() == 1 && T.lv_start.size() == 1 && T.n_pr == 0 && T.n_lr == 0 && T.pr.empty());
+        const uint64_t v = S.version; S.clear(); CHECK(S.version == v);             // clearing nothing is no change
+    }
+    {   // XY prior: the record of (zx, zy, 0) — inverse (-zx, -zy, 0), cos 1, sin 0 — and the embedded Omega
+        PriorStore S; const double z[3] = {12.5, -3.25, 0.0}, w[6] = {2, 0.5, 0, 3, 0, 0};
+        S.add_pose(0, z, w);
+        const double want[PRIOR_POSE_REC] = {-12.5, 3.25, 0, 1, 0, 2, 0.5, 0, 3, 0, 0};
+        for (int c = 0; c < PRIOR_POSE_REC; ++c) CHECK(S.pose_rec[(size_t)c] == want[c]);
+    }
+    {   // refusals: a vertex outside the graph, a free landmark whose only measurement is a prior (a fixed one is fine)
+        PriorStore S; PriorTables T; std::string err; const double z[3] = {0, 0, 0}, w[6] = {1, 0, 0, 1, 0, 1};
+        std::vector<uint8_t> pf(4, 0), lf(4, 0); lf[1] = 1; std::vector<int32_t> obs = {1, 0, 0, 3};
+        S.add_lm(1, z, w);
+        CHECK(build_prior_tables(S, pf.data(), 4, lf.data(), 4, obs.data(), T, err) && T.n_vertices() == 0);
+        S.add_lm(2, z, w);
+        CHECK(!build_prior_tables(S, pf.data(), 4, lf.data(), 4, obs.data(), T, err) && !err.empty());
+        S.clear(); S.add_pose(4, z, w); err.clear();
+        CHECK(!build_prior_tables(S, pf.data(), 4, lf.data(), 4, obs.data(), T, err) && !err.empty());
+        S.clear(); S.add_pose(-1, z, w);
+        CHECK(!build_prior_tables(S, pf.data(), 4, lf.data(), 4, obs.data(), T, err));
+    }
+    {   // the upload rule
+        PriorSync Y; PriorStore S; const double z[3] = {0, 0, 0}, w[6] = {1, 0, 0, 1, 0, 1};
+        CHECK(Y.needed(S.version, 7));                               // nothing uploaded yet
+        Y.done(S.version, 7); CHECK(!Y.needed(S.version, 7));
+        S.add_pose(0, z, w); CHECK(Y.needed(S.version, 7));          // the priors changed
+        Y.done(S.version, 7); CHECK(!Y.needed(S.version, 7) && Y.needed(S.version, 8));     // another plan (a growth step, a structure phase)
+        S.clear(); CHECK(Y.needed(S.version, 7));
+        Y.done(S.version, 7); Y.invalidate(); CHECK(Y.needed(S.version, 7));
+    }
+    std::puts("prior tables: ok");
+    return 0;
+}
