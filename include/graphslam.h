@@ -357,6 +357,45 @@ int  gs_num_landmark_priors(gs_graph *g);
 int  gs_clear_priors(gs_graph *g);
 int  gs_get_prior_chi2(gs_graph *g, int32_t kind /* 0 pose, 1 landmark */, int32_t capacity, double *out_chi2);
 
+/* ---- edge deactivation ------------------------------------------------------
+ * Per-edge levels, restated from g2o's published text (OptimizableGraph::Edge::setLevel, initializeOptimization(level)); nothing
+ * here is pinned against a g2o build.  An edge is active (level 0) or inactive (level 1); a new edge is active.  The standard outlier
+ * workflow: optimise with a robust kernel, gs_deactivate_edges_above a gate, optimise without the kernel on the inliers.
+ * Edges are named by kind (GS_EDGE_ODOMETRY / GS_EDGE_OBSERVATION) and insertion index within the kind — the indices gs_get_edge_chi2
+ * reports in.
+ * An inactive edge contributes nothing to H, b or any chi2 the library reports (gs_chi2, gs_stats.chi2_*, the verbose line, the stop
+ * rule of gs_optimize_until, the step control of gs_optimize_lm); gs_export_system returns zeros for its blocks; gs_compute_marginals
+ * inverts the H without it.  gs_get_edge_chi2 still reports its s, with the edge's own information at the current estimates (so that
+ * the caller can reconsider it), and weight 0.  On a handle with no inactive edge every call returns what it returned before.
+ * Changing a flag is NOT a structural change: no structure phase, a growth step stays a growth step.  It may happen between two
+ * gs_iterate calls and is applied on the handle's stream at the next call that computes.  Like any change it makes the marginals
+ * stale.  Flags survive growth steps and full structure phases; gs_clear drops them.
+ * Isolated vertices: a FREE vertex that carries no prior and has no active edge (its diagonal block would be zero).
+ * gs_find_isolated_vertex reports the first one — poses in insertion order, then landmarks — as kind (0 pose, 1 landmark) and id;
+ * returns 1 when there is one, 0 when not (host only: works on every handle).  While a handle with inactive edges has one, every
+ * call that computes returns GS_ERR_INVALID with a message naming the vertex, before anything is launched.  A graph that deactivation
+ * cuts into a component without gauge is the caller's business, as any under-constrained graph is.
+ * gs_set_edges_active: active == NULL switches all the listed edges off.  All or nothing: a bad index changes no flag.
+ * gs_get_edges_active: one byte per edge of the kind (1 active); out_active may be NULL; returns the number of edges.
+ * gs_deactivate_edges_above: the device computes s = e^T Omega e of every edge of the kind with the edge's own information at the
+ *      current estimates and marks the ACTIVE edges with s > s_threshold; the host walks the marked edges in insertion order and
+ *      switches each off — except, with keep_connected != 0, one that would leave a free, prior-less endpoint without an active edge,
+ *      given the decisions taken so far.  Inactive edges stay inactive.  *out_deactivated (may be NULL) = edges newly switched off.
+ *      Deterministic.  s_threshold must be finite and >= 0.
+ * Errors: unknown kind, index out of range, a null pointer with count > 0: GS_ERR_INVALID; capacity below the edge count:
+ *      GS_ERR_CAPACITY.  On a host-only handle everything works but gs_deactivate_edges_above (GS_ERR_NO_DEVICE).
+ * NOT DONE: pose-window shards — a flag change to inactive (gs_deactivate_edges_above included) on a handle configured with
+ *      gs_dist_configure(world > 1), and gs_dist_configure(world > 1) on a handle with inactive edges, return GS_ERR_INVALID; physical
+ *      removal of edges or vertices; levels other than 0 / 1; pinning an isolated vertex instead of refusing it; the Slam mirror and
+ *      the microservice shell deactivate nothing. */
+int  gs_set_edge_active(gs_graph *g, int32_t edge_kind, int32_t index, int32_t active);
+int  gs_set_edges_active(gs_graph *g, int32_t edge_kind, int32_t count, const int32_t *indices, const uint8_t *active /* NULL: all 0 */);
+int  gs_get_edges_active(gs_graph *g, int32_t edge_kind, int32_t capacity, uint8_t *out_active);
+int  gs_activate_all_edges(gs_graph *g);
+int  gs_num_inactive_edges(gs_graph *g, int32_t edge_kind);
+int  gs_find_isolated_vertex(gs_graph *g, int32_t *out_kind, int32_t *out_id);
+int  gs_deactivate_edges_above(gs_graph *g, int32_t edge_kind, double s_threshold, int32_t keep_connected, int32_t *out_deactivated);
+
 /* ---- measurement / parity hooks (tuning, fault injection and timestamps: include/graphslam_debug.h) ----------
  * gs_linearize: one A5+A6+A7 pass (the roofline kernel) on the stream, nothing else.
  * gs_time_linearize: `reps` back-to-back passes bracketed by HIP events on the handle's

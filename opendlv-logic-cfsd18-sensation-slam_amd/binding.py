@@ -264,6 +264,15 @@ def lib():
         for name in ("gs_num_pose_priors", "gs_num_landmark_priors", "gs_clear_priors"):
             getattr(L, name).argtypes = [vp]
         L.gs_get_prior_chi2.argtypes = [vp, C.c_int32, C.c_int32, _dp]
+    if hasattr(L, "gs_set_edge_active"):                   # (the same for edge deactivation)
+        u8p = C.POINTER(C.c_uint8)
+        L.gs_set_edge_active.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
+        L.gs_set_edges_active.argtypes = [vp, C.c_int32, C.c_int32, _ip, u8p]
+        L.gs_get_edges_active.argtypes = [vp, C.c_int32, C.c_int32, u8p]
+        L.gs_activate_all_edges.argtypes = [vp]
+        L.gs_num_inactive_edges.argtypes = [vp, C.c_int32]
+        L.gs_find_isolated_vertex.argtypes = [vp, _ip, _ip]
+        L.gs_deactivate_edges_above.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, _ip]
     L.gs_slam_get_send_pose.argtypes = [vp, _dp]
     L.gs_slam_collect_direction.argtypes = [vp, C.c_uint32, C.c_double, C.c_double]
     L.gs_slam_collect_distance.argtypes = [vp, C.c_uint32, C.c_double]
@@ -668,6 +677,42 @@ class Graph:
         self._check(self.L.gs_get_prior_chi2(self.h, kd, n, _d(out))); return out
 
     # ---- host-only plan (no device work)
+    # ---- edge deactivation (gs_set_edge_active ...: per-edge levels; kind "odometry" / "observation", index = insertion index within the kind)
+    def set_edge_active(self, kind, index, active=True):
+        self._check(self.L.gs_set_edge_active(self.h, int(EDGE_KINDS.get(kind, kind)), int(index), int(bool(active))))
+
+    def set_edges_active(self, kind, indices, active=None):
+        """active: one flag per index, or None to switch all the listed edges off"""
+        idx = _i32(indices); n = len(idx)
+        a = None if active is None else np.ascontiguousarray(np.broadcast_to(np.asarray(active, dtype=bool), (n,)), dtype=np.uint8)
+        self._check(self.L.gs_set_edges_active(self.h, int(EDGE_KINDS.get(kind, kind)), n, _i(idx),
+                                               None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def edges_active(self, kind):
+        """bool per edge of the kind, insertion order"""
+        kd = int(EDGE_KINDS.get(kind, kind))
+        n = self._check(self.L.gs_get_edges_active(self.h, kd, 0, None)); out = np.zeros(n, dtype=np.uint8)
+        self._check(self.L.gs_get_edges_active(self.h, kd, n, out.ctypes.data_as(C.POINTER(C.c_uint8)))); return out.astype(bool)
+
+    def activate_all_edges(self):
+        self._check(self.L.gs_activate_all_edges(self.h))
+
+    def n_inactive_edges(self, kind):
+        return self._check(self.L.gs_num_inactive_edges(self.h, int(EDGE_KINDS.get(kind, kind))))
+
+    def find_isolated_vertex(self):
+        """("pose" | "landmark", id) of the first free vertex without a prior and without an active edge, or None"""
+        k = C.c_int32(); i = C.c_int32()
+        if self._check(self.L.gs_find_isolated_vertex(self.h, C.byref(k), C.byref(i))) == 0:
+            return None
+        return ("pose", "landmark")[k.value], i.value
+
+    def deactivate_edges_above(self, kind, s_threshold, keep_connected=False):
+        """switches off the active edges of the kind with e^T Omega e > s_threshold at the current estimates; returns how many"""
+        n = C.c_int32()
+        self._check(self.L.gs_deactivate_edges_above(self.h, int(EDGE_KINDS.get(kind, kind)), float(s_threshold), int(bool(keep_connected)), C.byref(n)))
+        return n.value
+
     def plan_build_host(self):
         info = PlanInfo(); self._check(self.L.gs_plan_build_host(self.h, C.byref(info))); return info
 

@@ -186,6 +186,7 @@ extern "C" int gs_destroy(gs_graph *g) {
     dev_free_all(g);
     if (g->lm.mem) hipFree(g->lm.mem);
     if (g->prior.mem) hipFree(g->prior.mem);
+    if (g->emask.mem) hipFree(g->emask.mem);
     gs_dist_comm_release(g);
     gs_frontend_release(g);
     for (auto &e : g->ev) hipEventDestroy(e);
@@ -199,6 +200,7 @@ extern "C" int gs_clear(gs_graph *g) {
     if (!g->host_only) { hipSetDevice(g->device); hipStreamSynchronize(g->stream); dev_free_all(g); }
     g->h.clear(); g->plan = Plan(); g->plan_version = ~0ull;
     g->prior.store.clear(); g->prior.dev.n_pv = g->prior.dev.n_lv = 0; g->prior.sync.invalidate();      // the priors go with their vertices
+    g->emask.store.clear(); g->emask.sync.invalidate();              // ... and the flags with their edges
     return GS_OK;
 }
 
@@ -790,6 +792,7 @@ static int upload_graph(gs_graph *g, RawUpload &raw) {
     HIP_TRY(hipStreamSynchronize(g->stream));
     GS_UT("final sync");
     g->dev_valid = true; g->dev_estimates_newer = false; g->tree_proven = false;
+    ++g->value_uploads;                                              // every edge's own information is on the device again (edge_mask_sync)
     g->dev_estimate_version = h.estimate_version;
     return GS_OK;
 }
@@ -1062,9 +1065,10 @@ extern "C" int gs_initialize_optimization(gs_graph *g) {
 
 int ensure_ready(gs_graph *g) {
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (!g->dev_valid || g->plan_version != g->h.structure_version) { rc = gs_initialize_optimization(g); return rc != GS_OK ? rc : prior_sync(g); }
-    if ((rc = push_estimates(g)) != GS_OK) return rc;
-    return prior_sync(g);                                            // (nothing without priors)
+    if (!g->dev_valid || g->plan_version != g->h.structure_version) { if ((rc = gs_initialize_optimization(g)) != GS_OK) return rc; }
+    else if ((rc = push_estimates(g)) != GS_OK) return rc;
+    if ((rc = prior_sync(g)) != GS_OK) return rc;                    // (nothing without priors)
+    return edge_mask_sync(g);                                        // (nothing on a handle that never had an inactive edge)
 }
 
 void fill_plan_stats(gs_graph *g, gs_stats *s) {

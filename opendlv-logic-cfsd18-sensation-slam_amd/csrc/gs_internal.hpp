@@ -9,6 +9,7 @@
 #include "../../include/graphslam.h"
 #include "../../include/graphslam_debug.h"
 #include "gs_device.hpp"
+#include "gs_edge_mask.hpp"
 #include "gs_host.hpp"
 #include "gs_lm.hpp"
 #include "gs_prior.hpp"
@@ -91,6 +92,11 @@ struct gs_graph {
     // grow-only; uploaded whole by prior_sync when the priors or the plan changed.  dev stays empty while there is no prior on a free vertex
     struct Prior { gs::PriorStore store; gs::PriorTables tab; gs::PriorSync sync; gs::PriorDev dev{}; void *mem = nullptr; size_t cap = 0;
                    uint64_t settled = 0; /* store.version prior_sync last looked at */ } prior;
+    // edge deactivation (gs_edge_mask.hpp): the flags, what the device holds against them, and the staging of one k_edge_mask_apply
+    // launch per kind — one allocation of the handle's own, grow-only, made at the first sync of a handle that has had an inactive edge
+    struct EdgeMask { gs::EdgeMaskStore store; gs::EdgeMaskSync sync; void *mem = nullptr; size_t cap = 0;
+                      std::vector<int32_t> loc; std::vector<double> orig; std::vector<uint8_t> act; /* host side of the staging */ } emask;
+    uint64_t value_uploads = 0;             // full uploads of the edge values (upload_graph): each puts every edge's own information on the device
 };
 
 namespace gs {

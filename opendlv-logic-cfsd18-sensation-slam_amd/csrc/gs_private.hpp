@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <string>
+#include <vector>
 
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
     return gs::fail(GS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
@@ -56,6 +57,9 @@ int reset_failure(gs_graph *g);
 void fill_plan_stats(gs_graph *g, gs_stats *s);
 // gs_prior_api.cpp
 int prior_sync(gs_graph *g);                   // the prior tables to the device when the priors or the plan changed (ensure_ready, gs_iterate); nothing without priors
+// gs_edge_mask_api.cpp
+int edge_mask_sync(gs_graph *g);               // the information of the edges whose flag changed (or that an upload rewrote) on the device; called where prior_sync is; nothing on a handle that never had an inactive edge
+int edge_mask_edge_chi2(gs_graph *g, int32_t kind, int32_t n, const std::vector<int32_t> &tab, double *out_chi2, double *out_weight);   // gs_get_edge_chi2 on a handle with inactive edges: s with the edges' own information
 // gs_solve.cpp
 // every linearisation of H and every chi2 pass goes through these two, so that no site can leave the priors out
 void enqueue_linearize(gs_graph *g, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);   // linearise + a grown plan's tail + the priors (start / stop: on the linearisation dispatch)

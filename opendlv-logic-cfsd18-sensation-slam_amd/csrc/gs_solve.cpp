@@ -73,6 +73,7 @@ extern "C" int gs_iterate(gs_graph *g) {
     if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: use gs_dist_iterate (RCCL inside the library) or gs_dist_iterate_local / all-reduce / gs_dist_iterate_finish");
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
     if ((rc = prior_sync(g)) != GS_OK) return rc;
+    if ((rc = edge_mask_sync(g)) != GS_OK) return rc;
     enqueue_iteration(g, false);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
@@ -413,6 +414,7 @@ extern "C" int gs_get_edge_chi2(gs_graph *g, int32_t edge_kind, int32_t capacity
         else { if (k - P.base_Epl >= g->d.tEpl) return fail(GS_ERR_INVALID, "observation edge not on the device"); src = -(k - P.base_Epl) - 1; }
         tab[3 * (size_t)k] = h.pl_p[k]; tab[3 * (size_t)k + 1] = h.pl_l[k]; tab[3 * (size_t)k + 2] = src; }
     if (pp && n > g->d.Epp + g->d.tEpp) return fail(GS_ERR_INVALID, "odometry edge not on the device");
+    if (g->emask.store.any_off()) return edge_mask_edge_chi2(g, edge_kind, n, tab, out_chi2, out_weight);     // the device arrays hold zeros for the inactive edges: s from the edges' own information
     int32_t *dtab = nullptr; double *dout = nullptr;
     HIP_TRY(hipMalloc((void **)&dtab, tab.size() * sizeof(int32_t)));
     if (hipMalloc((void **)&dout, (size_t)n * 2 * sizeof(double)) != hipSuccess) { hipFree(dtab); return fail(GS_ERR_HIP, "hipMalloc failed"); }
