@@ -396,6 +396,49 @@ int  gs_num_inactive_edges(gs_graph *g, int32_t edge_kind);
 int  gs_find_isolated_vertex(gs_graph *g, int32_t *out_kind, int32_t *out_id);
 int  gs_deactivate_edges_above(gs_graph *g, int32_t edge_kind, double s_threshold, int32_t keep_connected, int32_t *out_deactivated);
 
+/* ---- polar observation edges -------------------------------------------------
+ * The sensor's own measurement model: a cone detection is accurate in bearing and poor in range, and a camera-only cone is a bearing
+ * with no range at all.  Two edge types between a pose and a landmark beside the Cartesian gs_add_observation_edge (<- g2o
+ * EdgeSE2PointXYBearing for the bearing-only one; the formulas are restated, nothing here is pinned against a g2o build).
+ * With d = x_p^-1 * l the landmark in the pose frame, r = |d| and beta = atan2(dy, dx):
+ *   gs_add_range_bearing_edge  z = (z_r >= 0, z_beta in radians), Omega 2x2 symmetric in (range, bearing):
+ *                              e = (r - z_r, normalize_theta(beta - z_beta))
+ *   gs_add_bearing_edge        z_beta, omega >= 0: the range-bearing edge with z_r = 0 and Omega = [[0, 0], [0, omega]], and stored as one
+ * g2o's EdgeSE2PointXYBearing takes z - beta; the sign changes neither H, b nor chi2.  z_beta is normalised when stored.  The bearing
+ * is taken at the pose's origin.  Jacobians are analytic, for the additive update of gs_iterate: Jd = d(r, beta)/dd =
+ * [[dx/r, dy/r], [-dy/r^2, dx/r^2]], B = Jd R^T for the landmark, A = [-B | (0, -1)^T] for the pose.  The edge contributes w A^T Omega A,
+ * w A^T Omega B, w B^T Omega B to H, -w A^T Omega e and -w B^T Omega e to b and rho(s) to chi2, with s = e^T Omega e and w, rho from the
+ * OBSERVATION kind's robust kernel.  An edge with r == 0 exactly contributes nothing in that pass and reports s = 0.  Fixed vertices as
+ * for every edge: a fixed endpoint stays out of H, an edge between two fixed vertices out of chi2.
+ * A POLAR EDGE IS AN OBSERVATION EDGE.  It takes the next observation-edge index, gs_num_observation_edges counts it, and that index
+ * names it in gs_get_edge_chi2 (s with its own Omega, the kind's weight), gs_set_edge_active / gs_set_edges_active,
+ * gs_export_system (its Hpl row) and gs_get_observation_edge_covariances.  Adding one is a structural change exactly like
+ * gs_add_observation_edge: the same growth rules apply (a keyframe appended with polar edges to old cones is absorbed by growth).
+ * gs_clear drops polar edges.  Everything that linearises or sums chi2 sees them: gs_iterate, gs_optimize, gs_optimize_until,
+ * gs_optimize_lm, gs_chi2, gs_compute_marginals, gs_export_system, with robust kernels, priors and inactive edges.  A handle without
+ * polar edges runs exactly the launches it ran before and allocates nothing new.
+ * information is REQUIRED (also in the bulk forms: count*4 resp. count doubles).
+ * gs_num_polar_edges / gs_get_polar_edges: the polar edges in insertion order as observation-edge index and model (GS_OBS_RANGE_BEARING /
+ *      GS_OBS_BEARING; every other observation edge is GS_OBS_CARTESIAN); either pointer may be NULL; returns the count (GS_ERR_CAPACITY
+ *      when capacity is below it and a pointer is given).
+ * Errors: unknown id GS_ERR_UNKNOWN_ID; a null pointer, a z that is not finite, z_r < 0, an Omega that is not finite or not symmetric,
+ *      omega < 0 or not finite: GS_ERR_INVALID — a refused edge leaves nothing behind.  On a host-only handle everything here works;
+ *      the computing calls return GS_ERR_NO_DEVICE as before.
+ * NOT DONE: pose-window shards — a polar add on a handle configured with gs_dist_configure(world > 1), and gs_dist_configure(world > 1)
+ *      on a handle that holds polar edges, return GS_ERR_INVALID; gs_deactivate_edges_above never selects a polar edge (its gate sees the
+ *      zero information the edge is carried with): gate on gs_get_edge_chi2 and use gs_set_edges_active; removal of single edges; a
+ *      sensor offset; the Slam mirror and the microservice shell keep adding Cartesian edges; gs_time_linearize keeps timing the
+ *      roofline kernel alone. */
+#define GS_OBS_CARTESIAN      0
+#define GS_OBS_RANGE_BEARING  1
+#define GS_OBS_BEARING        2
+int  gs_add_range_bearing_edge(gs_graph *g, int32_t pose_id, int32_t lm_id, const double z_rb[2], const double information[4]);
+int  gs_add_bearing_edge(gs_graph *g, int32_t pose_id, int32_t lm_id, double z_bearing, double information);
+int  gs_add_range_bearing_edges(gs_graph *g, int32_t count, const int32_t *pose_ids, const int32_t *lm_ids, const double *z_rb, const double *information /* count*4, required */);
+int  gs_add_bearing_edges(gs_graph *g, int32_t count, const int32_t *pose_ids, const int32_t *lm_ids, const double *z_bearing, const double *information /* count, required */);
+int  gs_num_polar_edges(gs_graph *g);
+int  gs_get_polar_edges(gs_graph *g, int32_t capacity, int32_t *out_observation_index, int32_t *out_model);
+
 /* ---- measurement / parity hooks (tuning, fault injection and timestamps: include/graphslam_debug.h) ----------
  * gs_linearize: one A5+A6+A7 pass (the roofline kernel) on the stream, nothing else.
  * gs_time_linearize: `reps` back-to-back passes bracketed by HIP events on the handle's

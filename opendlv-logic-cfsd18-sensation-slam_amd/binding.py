@@ -273,6 +273,13 @@ def lib():
         L.gs_num_inactive_edges.argtypes = [vp, C.c_int32]
         L.gs_find_isolated_vertex.argtypes = [vp, _ip, _ip]
         L.gs_deactivate_edges_above.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, _ip]
+    if hasattr(L, "gs_add_range_bearing_edge"):            # (the same for the polar observation edges)
+        L.gs_add_range_bearing_edge.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp]
+        L.gs_add_bearing_edge.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_double]
+        L.gs_add_range_bearing_edges.argtypes = [vp, C.c_int32, _ip, _ip, _dp, _dp]
+        L.gs_add_bearing_edges.argtypes = [vp, C.c_int32, _ip, _ip, _dp, _dp]
+        L.gs_num_polar_edges.argtypes = [vp]
+        L.gs_get_polar_edges.argtypes = [vp, C.c_int32, _ip, _ip]
     L.gs_slam_get_send_pose.argtypes = [vp, _dp]
     L.gs_slam_collect_direction.argtypes = [vp, C.c_uint32, C.c_double, C.c_double]
     L.gs_slam_collect_distance.argtypes = [vp, C.c_uint32, C.c_double]
@@ -675,6 +682,31 @@ class Graph:
         kd = int({"pose": 0, "landmark": 1}.get(kind, kind))
         n = self._check(self.L.gs_get_prior_chi2(self.h, kd, 0, None)); out = np.zeros(n)
         self._check(self.L.gs_get_prior_chi2(self.h, kd, n, _d(out))); return out
+
+    # ---- polar observation edges (gs_add_range_bearing_edge / gs_add_bearing_edge: observation edges with a polar measurement model)
+    def add_range_bearing_edge(self, p, l, z, info):
+        """z = (range >= 0, bearing in radians), information 2x2 in (range, bearing)"""
+        z = _f64(z); info = _f64(info); self._check(self.L.gs_add_range_bearing_edge(self.h, int(p), int(l), _d(z), _d(info)))
+
+    def add_bearing_edge(self, p, l, z, info):
+        """bearing only: z in radians, information a scalar >= 0"""
+        self._check(self.L.gs_add_bearing_edge(self.h, int(p), int(l), float(z), float(info)))
+
+    def add_range_bearing_edges(self, p, l, z, info):
+        p = _i32(p); l = _i32(l); z = _f64(z); info = _f64(info)
+        self._check(self.L.gs_add_range_bearing_edges(self.h, len(p), _i(p), _i(l), _d(z), _d(info)))
+
+    def add_bearing_edges(self, p, l, z, info):
+        p = _i32(p); l = _i32(l); z = _f64(z); info = _f64(info)
+        self._check(self.L.gs_add_bearing_edges(self.h, len(p), _i(p), _i(l), _d(z), _d(info)))
+
+    def num_polar_edges(self):
+        return self._check(self.L.gs_num_polar_edges(self.h))
+
+    def polar_edges(self):
+        """(observation-edge index, model) of every polar edge, insertion order; model 1 range-bearing, 2 bearing-only"""
+        n = self.num_polar_edges(); idx = np.zeros(n, dtype=np.int32); model = np.zeros(n, dtype=np.int32)
+        self._check(self.L.gs_get_polar_edges(self.h, n, _i(idx), _i(model))); return idx, model
 
     # ---- host-only plan (no device work)
     # ---- edge deactivation (gs_set_edge_active ...: per-edge levels; kind "odometry" / "observation", index = insertion index within the kind)

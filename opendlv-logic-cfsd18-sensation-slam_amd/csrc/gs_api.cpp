@@ -187,6 +187,7 @@ extern "C" int gs_destroy(gs_graph *g) {
     if (g->lm.mem) hipFree(g->lm.mem);
     if (g->prior.mem) hipFree(g->prior.mem);
     if (g->emask.mem) hipFree(g->emask.mem);
+    if (g->polar.mem) hipFree(g->polar.mem);
     gs_dist_comm_release(g);
     gs_frontend_release(g);
     for (auto &e : g->ev) hipEventDestroy(e);
@@ -201,6 +202,7 @@ extern "C" int gs_clear(gs_graph *g) {
     g->h.clear(); g->plan = Plan(); g->plan_version = ~0ull;
     g->prior.store.clear(); g->prior.dev.n_pv = g->prior.dev.n_lv = 0; g->prior.sync.invalidate();      // the priors go with their vertices
     g->emask.store.clear(); g->emask.sync.invalidate();              // ... and the flags with their edges
+    g->polar.store.clear(); g->polar.dev = PolarDev(); g->polar.sync.invalidate();                      // ... and the polar measurements with their carriers
     return GS_OK;
 }
 
@@ -1068,7 +1070,8 @@ int ensure_ready(gs_graph *g) {
     if (!g->dev_valid || g->plan_version != g->h.structure_version) { if ((rc = gs_initialize_optimization(g)) != GS_OK) return rc; }
     else if ((rc = push_estimates(g)) != GS_OK) return rc;
     if ((rc = prior_sync(g)) != GS_OK) return rc;                    // (nothing without priors)
-    return edge_mask_sync(g);                                        // (nothing on a handle that never had an inactive edge)
+    if ((rc = edge_mask_sync(g)) != GS_OK) return rc;                // (nothing on a handle that never had an inactive edge)
+    return polar_sync(g);                                            // (nothing without polar edges)
 }
 
 void fill_plan_stats(gs_graph *g, gs_stats *s) {

@@ -23,6 +23,8 @@ extern "C" int gs_dist_configure(gs_graph *g, int32_t rank, int32_t world) {
         return fail(GS_ERR_INVALID, "robust kernels are not supported on sharded handles: set GS_ROBUST_NONE on both edge kinds first");
     if (world > 1 && !g->prior.store.empty())
         return fail(GS_ERR_INVALID, "prior edges are not supported on sharded handles: gs_clear_priors first");
+    if (world > 1 && !g->polar.store.empty())
+        return fail(GS_ERR_INVALID, "polar observation edges are not supported on sharded handles: gs_clear first");
     if (world > 1 && g->emask.store.any_off())
         return fail(GS_ERR_INVALID, "inactive edges are not supported on sharded handles: gs_activate_all_edges first");
     g->rank = rank; g->world = world; ++g->h.structure_version; ++g->h.reshape_version;

@@ -177,6 +177,7 @@ static int eval_edges(gs_graph *g, int32_t kind, int32_t n, const std::vector<in
     if (e == hipSuccess) { launch_edge_select(g->d, kind, n, (const int32_t *)(b + o_tab), (const double *)(b + o_info), (const uint8_t *)(b + o_act), threshold,
                                               sw ? (double *)(b + o_sw) : nullptr, cand ? (uint8_t *)(b + o_cand) : nullptr, (int32_t *)(b + o_cnt), g->stream);
         e = hipGetLastError(); }
+    if (e == hipSuccess && sw && !pp && polar_edge_chi2_overwrite(g, n, (double *)(b + o_sw)) != GS_OK) { hipStreamSynchronize(g->stream); hipFree(b); return GS_ERR_HIP; }   // (the polar edges' own s and weight; nothing without polar edges)
     if (e == hipSuccess && sw) e = hipMemcpyAsync(sw->data(), b + o_sw, (size_t)n * 2 * 8, hipMemcpyDeviceToHost, g->stream);
     if (e == hipSuccess && cand) e = hipMemcpyAsync(cand->data(), b + o_cand, (size_t)n, hipMemcpyDeviceToHost, g->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), b + o_cnt, (size_t)grid * 4, hipMemcpyDeviceToHost, g->stream);

@@ -12,6 +12,7 @@
 #include "gs_edge_mask.hpp"
 #include "gs_host.hpp"
 #include "gs_lm.hpp"
+#include "gs_polar.hpp"
 #include "gs_prior.hpp"
 #include "gs_schedule.hpp"
 
@@ -96,6 +97,9 @@ struct gs_graph {
     // launch per kind — one allocation of the handle's own, grow-only, made at the first sync of a handle that has had an inactive edge
     struct EdgeMask { gs::EdgeMaskStore store; gs::EdgeMaskSync sync; void *mem = nullptr; size_t cap = 0;
                       std::vector<int32_t> loc; std::vector<double> orig; std::vector<uint8_t> act; /* host side of the staging */ } emask;
+    // polar observation edges (gs_polar.hpp): the measurements as added (under their carriers' observation indices), the tables, and
+    // their device copy — one allocation of the handle's own, grow-only, made at the first sync of a handle that holds a polar edge
+    struct Polar { gs::PolarStore store; gs::PolarTables tab; gs::PolarSync sync; gs::PolarDev dev{}; void *mem = nullptr; size_t cap = 0; } polar;
     uint64_t value_uploads = 0;             // full uploads of the edge values (upload_graph): each puts every edge's own information on the device
 };
 

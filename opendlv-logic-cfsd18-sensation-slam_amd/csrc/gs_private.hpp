@@ -60,6 +60,9 @@ int prior_sync(gs_graph *g);                   // the prior tables to the device
 // gs_edge_mask_api.cpp
 int edge_mask_sync(gs_graph *g);               // the information of the edges whose flag changed (or that an upload rewrote) on the device; called where prior_sync is; nothing on a handle that never had an inactive edge
 int edge_mask_edge_chi2(gs_graph *g, int32_t kind, int32_t n, const std::vector<int32_t> &tab, double *out_chi2, double *out_weight);   // gs_get_edge_chi2 on a handle with inactive edges: s with the edges' own information
+// gs_polar_api.cpp
+int polar_sync(gs_graph *g);                   // the polar edges' tables to the device when they, the plan, the edge flags or the edge values changed; called where prior_sync is; nothing without polar edges
+int polar_edge_chi2_overwrite(gs_graph *g, int32_t n, double *dev_out);   // gs_get_edge_chi2 (observation kind): s and weight of the polar edges over the per-edge kernel's device output [2][n]; nothing without polar edges
 // gs_solve.cpp
 // every linearisation of H and every chi2 pass goes through these two, so that no site can leave the priors out
 void enqueue_linearize(gs_graph *g, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);   // linearise + a grown plan's tail + the priors (start / stop: on the linearisation dispatch)

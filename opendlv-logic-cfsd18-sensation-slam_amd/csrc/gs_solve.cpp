@@ -31,19 +31,22 @@ struct Launcher {
 };
 }  // namespace
 void enqueue_factor_levels(gs_graph *g, const LevelSet &ls, int base, int mode) { Launcher L{g}; walk_factor_levels(g->sched, g->d.tree != 0, ls, base, mode, L); }
-// linearise -> tail -> priors.  The prior total of chi2 goes where this pass's total is formed from: a partial k_update / k_linearize_finalize
-// sum (fused kernel), or chi2[0] (gather kernels: k_reduce_chi2 has totalled it).  A handle without priors launches what it always did
+// linearise -> tail -> priors -> polar edges.  The prior total of chi2 goes where this pass's total is formed from: a partial k_update / k_linearize_finalize
+// sum (fused kernel), or chi2[0] (gather kernels: k_reduce_chi2 has totalled it); the polar pass adds its total to the same slot.  A handle
+// without priors and without polar edges launches what it always did
 void enqueue_linearize(gs_graph *g, hipEvent_t start, hipEvent_t stop) {
     launch_linearize(g->d, g->stream, start, stop);
     launch_linearize_tail(g->d, g->stream);                          // a grown plan's tail (no launch without one)
     const bool fused = g->d.n_wtiles > 0;
-    if (fused && g->d.wt_hi <= g->d.wt_lo && prior_grid(g->prior.dev) > 0)      // no wave tile swept, no launch above: nobody has written the slot the pass adds to
+    if (fused && g->d.wt_hi <= g->d.wt_lo && (prior_grid(g->prior.dev) > 0 || polar_grid(g->polar.dev) > 0))      // no wave tile swept, no launch above: nobody has written the slot the pass adds to
         hipMemsetAsync(g->d.chi2_partial, 0, sizeof(double), g->stream);
     launch_prior_pass(g->d, g->prior.dev, true, fused ? g->d.chi2_partial : g->d.chi2, g->stream);
+    launch_polar_pass(g->d, g->polar.dev, true, fused ? g->d.chi2_partial : g->d.chi2, g->stream);      // (returns on an empty table)
 }
 void enqueue_chi2(gs_graph *g) {
     launch_chi2_only(g->d, g->stream);
     launch_prior_pass(g->d, g->prior.dev, false, g->d.chi2, g->stream);
+    launch_polar_pass(g->d, g->polar.dev, false, g->d.chi2, g->stream);
 }
 // pose-window shards, first half: linearise this shard's edges, factorise its own subtrees, write its contribution
 // to every shared front into the exchange buffer (the caller all-reduces that buffer: RCCL sum, fp64)
@@ -74,6 +77,7 @@ extern "C" int gs_iterate(gs_graph *g) {
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
     if ((rc = prior_sync(g)) != GS_OK) return rc;
     if ((rc = edge_mask_sync(g)) != GS_OK) return rc;
+    if ((rc = polar_sync(g)) != GS_OK) return rc;
     enqueue_iteration(g, false);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
@@ -421,6 +425,7 @@ extern "C" int gs_get_edge_chi2(gs_graph *g, int32_t edge_kind, int32_t capacity
     std::vector<double> out((size_t)n * 2);
     hipError_t e = hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, g->stream);
     if (e == hipSuccess) { launch_edge_chi2(g->d, edge_kind, n, dtab, dout, g->stream); e = hipGetLastError(); }
+    if (e == hipSuccess && !pp && polar_edge_chi2_overwrite(g, n, dout) != GS_OK) { hipStreamSynchronize(g->stream); hipFree(dtab); hipFree(dout); return GS_ERR_HIP; }   // (nothing without polar edges)
     if (e == hipSuccess) e = hipMemcpyAsync(out.data(), dout, out.size() * sizeof(double), hipMemcpyDeviceToHost, g->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(g->stream); else hipStreamSynchronize(g->stream);
     hipFree(dtab); hipFree(dout);
