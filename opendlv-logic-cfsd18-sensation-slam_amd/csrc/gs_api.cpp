@@ -185,9 +185,7 @@ extern "C" int gs_destroy(gs_graph *g) {
     hipStreamSynchronize(g->stream);
     dev_free_all(g);
     if (g->lm.mem) hipFree(g->lm.mem);
-    if (g->prior.mem) hipFree(g->prior.mem);
-    if (g->emask.mem) hipFree(g->emask.mem);
-    if (g->polar.mem) hipFree(g->polar.mem);
+    side_release(g);
     gs_dist_comm_release(g);
     gs_frontend_release(g);
     for (auto &e : g->ev) hipEventDestroy(e);
@@ -200,9 +198,7 @@ extern "C" int gs_clear(gs_graph *g) {
     if (!g) return fail(GS_ERR_INVALID, "null graph");
     if (!g->host_only) { hipSetDevice(g->device); hipStreamSynchronize(g->stream); dev_free_all(g); }
     g->h.clear(); g->plan = Plan(); g->plan_version = ~0ull;
-    g->prior.store.clear(); g->prior.dev.n_pv = g->prior.dev.n_lv = 0; g->prior.sync.invalidate();      // the priors go with their vertices
-    g->emask.store.clear(); g->emask.sync.invalidate();              // ... and the flags with their edges
-    g->polar.store.clear(); g->polar.dev = PolarDev(); g->polar.sync.invalidate();                      // ... and the polar measurements with their carriers
+    side_clear(g);
     return GS_OK;
 }
 
@@ -1069,9 +1065,44 @@ int ensure_ready(gs_graph *g) {
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (!g->dev_valid || g->plan_version != g->h.structure_version) { if ((rc = gs_initialize_optimization(g)) != GS_OK) return rc; }
     else if ((rc = push_estimates(g)) != GS_OK) return rc;
-    if ((rc = prior_sync(g)) != GS_OK) return rc;                    // (nothing without priors)
+    return side_sync(g);
+}
+
+// ------------------------------------------------------------------ what the three side passes share on the host (gs_private.hpp)
+int arena_reserve(gs_graph *g, DevArena &a, size_t total) {
+    if (a.mem && total <= a.cap) return GS_OK;
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    arena_release(a);
+    const size_t cap = total + total / 2 + 4096;
+    if (hipMalloc(&a.mem, cap) != hipSuccess) { a.mem = nullptr; return fail(GS_ERR_HIP, "hipMalloc failed"); }
+    a.cap = cap;
+    return GS_OK;
+}
+hipError_t arena_upload(gs_graph *g, const DevArena &a, size_t off, const void *src, size_t bytes) {
+    return bytes ? hipMemcpyAsync(a.at(off), src, bytes, hipMemcpyHostToDevice, g->stream) : hipSuccess;
+}
+void arena_release(DevArena &a) { if (a.mem) hipFree(a.mem); a.mem = nullptr; a.cap = 0; }
+
+int side_sync(gs_graph *g) {
+    int rc = prior_sync(g); if (rc != GS_OK) return rc;              // (nothing without priors)
     if ((rc = edge_mask_sync(g)) != GS_OK) return rc;                // (nothing on a handle that never had an inactive edge)
     return polar_sync(g);                                            // (nothing without polar edges)
+}
+void side_clear(gs_graph *g) {
+    g->prior.store.clear(); g->prior.dev.n_pv = g->prior.dev.n_lv = 0; g->prior.sync.invalidate();      // the priors go with their vertices
+    g->emask.store.clear(); g->emask.sync.invalidate();              // ... and the flags with their edges
+    g->polar.store.clear(); g->polar.dev = PolarDev(); g->polar.sync.invalidate();                      // ... and the polar measurements with their carriers
+}
+void side_release(gs_graph *g) { arena_release(g->prior.arena); arena_release(g->emask.arena); arena_release(g->polar.arena); }
+int pl_location(const gs_graph *g, int32_t k, int32_t &src, const char *prefix) {
+    const Plan &P = g->plan;
+    if (k < P.base_Epl) { src = (size_t)k < P.ell_of_ins.size() ? P.ell_of_ins[(size_t)k] : -1;
+        if (src < 0) return fail(GS_ERR_INVALID, std::string(prefix) + "observation edge outside the linearisation layout"); }
+    else { if (k - P.base_Epl >= g->d.tEpl) return fail(GS_ERR_INVALID, std::string(prefix) + "observation edge not on the device"); src = -(k - P.base_Epl) - 1; }
+    return GS_OK;
+}
+bool lm_lacks_fused_slot(const gs_graph *g, int32_t l) {
+    return g->d.n_wtiles > 0 && l < g->d.M && !g->h.lm_fixed[(size_t)l] && !(g->plan.lm_grp_start[(size_t)l] < g->plan.lm_grp_start[(size_t)l + 1]);
 }
 
 void fill_plan_stats(gs_graph *g, gs_stats *s) {

@@ -14,42 +14,21 @@
 //                     byte (active and s > threshold) and the candidates per workgroup (waves by ballot, then the four waves' counts
 //                     in index order: integers, no floating-point atomics, nothing order-dependent).
 #include "gs_edge_mask.hpp"
+#include "gs_side_dev.hpp"
 
 namespace gs {
 
-static constexpr double kMaskPi = 3.14159265358979323846;
-
-__device__ __forceinline__ double mask_normalize_theta(double th) {      // g2o normalize_theta, as in gs_kernels.hip
-#pragma clang fp contract(off)
-    if (th >= -kMaskPi && th < kMaskPi) return th;
-    const double m = floor(th / (2.0 * kMaskPi));
-    th = th - m * 2.0 * kMaskPi;
-    if (th >= kMaskPi) th -= 2.0 * kMaskPi;
-    if (th < -kMaskPi) th += 2.0 * kMaskPi;
-    return th;
-}
-// rho'(s) of robust_rho (gs_kernels.hip): 1 where the kernel does not act
-__device__ __forceinline__ double mask_robust_weight(int kernel, double delta, double s) {
-#pragma clang fp contract(off)
-    if (kernel == 1) { const double d2 = delta * delta; return s > d2 ? delta / sqrt(s) : 1.0; }
-    if (kernel == 2) { const double d2 = delta * delta, aux = 1.0 + s / d2; return 1.0 / aux; }
-    return 1.0;
-}
 // EdgeSE2PointXY: e = (x_p^-1 * l) - z, s = e^T W e (edge_pl + the first lines of quad_pl)
 __device__ __forceinline__ double mask_s_pl(double px, double py, double c, double s, double lx, double ly, double zx, double zy, double w00, double w01, double w11) {
-    double ex, ey;
-    {
-#pragma clang fp contract(off)
-        const double ix = -(c * px + s * py), iy = s * px - c * py;
-        ex = ((c * lx + s * ly) + ix) - zx;
-        ey = ((c * ly - s * lx) + iy) - zy;
-    }
+    double dx, dy;
+    side_lm_in_pose_frame(px, py, c, s, lx, ly, dx, dy);
+    const double ex = dx - zx, ey = dy - zy;
     const double We0 = w00 * ex + w01 * ey, We1 = w01 * ex + w11 * ey;
     return ex * We0 + ey * We1;
 }
 // EdgeSE2: e = vec(z^-1 * (x_i^-1 * x_j)), s = e^T W e (the residual of pp_incidence)
 __device__ __forceinline__ double mask_s_pp(const double xi[3], const double xj[3], double ci, double si, const double zinv5[5], const double w[6]) {
-    const double rth = mask_normalize_theta(mask_normalize_theta(-xi[2]) + xj[2]);
+    const double rth = side_normalize_theta(side_normalize_theta(-xi[2]) + xj[2]);
     const double cz = zinv5[3], sz = zinv5[4];
     double e0, e1;
     {
@@ -58,7 +37,7 @@ __device__ __forceinline__ double mask_s_pp(const double xi[3], const double xj[
         const double qx = ix + (ci * xj[0] + si * xj[1]), qy = iy + (ci * xj[1] - si * xj[0]);
         e0 = zinv5[0] + (cz * qx - sz * qy); e1 = zinv5[1] + (sz * qx + cz * qy);
     }
-    const double e2 = mask_normalize_theta(zinv5[2] + rth);
+    const double e2 = side_normalize_theta(zinv5[2] + rth);
     const double We0 = w[0] * e0 + w[1] * e1 + w[2] * e2, We1 = w[1] * e0 + w[3] * e1 + w[4] * e2, We2 = w[2] * e0 + w[4] * e1 + w[5] * e2;
     return e0 * We0 + e1 * We1 + e2 * We2;
 }
@@ -75,15 +54,12 @@ __global__ void __launch_bounds__(256) k_edge_mask_apply(DevGraph d, int kind, i
 #pragma unroll
         for (int c = 0; c < 6; ++c) w[c] = on ? orig[6 * (int64_t)t + c] : 0.0;
     } else {
-        const int src = loc[t];
-        if (src >= 0) {
-            const int64_t L = d.ell_len;
-            if ((int64_t)src >= L || !d.ell_w) return;
+        const int src = loc[t]; int e;
+        if (side_pl_in_ell(d, src)) { const int64_t L = d.ell_len;
+            if (!d.ell_w) return;
 #pragma unroll
             for (int c = 0; c < 3; ++c) d.ell_w[c * L + src] = on ? orig[3 * (int64_t)t + c] : 0.0;
-        } else {
-            const int e = -(src + 1);
-            if (e < 0 || e >= d.tEpl || e >= d.tcapEpl || !d.t_pl_w) return;
+        } else if (side_pl_in_tail(d, src, e) && d.t_pl_w) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) d.t_pl_w[3 * e + c] = on ? orig[3 * (int64_t)t + c] : 0.0;
         }
@@ -112,18 +88,18 @@ __global__ void __launch_bounds__(256) k_edge_select(DevGraph d, int kind, int n
                 for (int c = 0; c < 6; ++c) wi[c] = info[6 * (int64_t)k + c];
                 const double2 ci = reinterpret_cast<const double2 *>(d.pose_cs)[i];
                 s = mask_s_pp(xi, xj, ci.x, ci.y, z5, wi);
-                w = on ? mask_robust_weight(d.rk_pp, d.rd_pp, s) : 0.0;
+                if (on) side_robust_rho(d.rk_pp, d.rd_pp, s, w);
                 ok = true; }
         } else {
             const int p = tab[3 * (int64_t)k], l = tab[3 * (int64_t)k + 1], src = tab[3 * (int64_t)k + 2];
-            double zx = 0.0, zy = 0.0; bool have = false;
-            if (src >= 0) { const int64_t L = d.ell_len; if ((int64_t)src < L && d.ell_z) { zx = d.ell_z[src]; zy = d.ell_z[L + src]; have = true; } }
-            else { const int e = -(src + 1); if (e >= 0 && e < d.tEpl && d.t_pl_z) { zx = d.t_pl_z[2 * e]; zy = d.t_pl_z[2 * e + 1]; have = true; } }
+            double zx = 0.0, zy = 0.0; bool have = false; int e;
+            if (side_pl_in_ell(d, src)) { if (d.ell_z) { zx = d.ell_z[src]; zy = d.ell_z[d.ell_len + src]; have = true; } }
+            else if (side_pl_in_tail(d, src, e) && d.t_pl_z) { zx = d.t_pl_z[2 * e]; zy = d.t_pl_z[2 * e + 1]; have = true; }
             if (have && p >= 0 && p < NP && l >= 0 && l < NL) {
                 const double2 cs = reinterpret_cast<const double2 *>(d.pose_cs)[p];
                 s = mask_s_pl(d.pose_est[3 * (int64_t)p], d.pose_est[3 * (int64_t)p + 1], cs.x, cs.y, d.lm_est[2 * (int64_t)l], d.lm_est[2 * (int64_t)l + 1],
                               zx, zy, info[3 * (int64_t)k], info[3 * (int64_t)k + 1], info[3 * (int64_t)k + 2]);
-                w = on ? mask_robust_weight(d.rk_pl, d.rd_pl, s) : 0.0;
+                if (on) side_robust_rho(d.rk_pl, d.rd_pl, s, w);
                 ok = true; }
         }
     }

@@ -35,15 +35,6 @@ std::string vertex_name(const gs_graph *g, int32_t kind, int32_t index) {
 int shard_refusal(const gs_graph *g) {
     return g->world > 1 ? fail(GS_ERR_INVALID, "inactive edges are not supported on sharded handles (gs_dist_configure with world > 1)") : GS_OK;
 }
-// where observation edge k lives on the device: its ELL index, or -(tail slot) - 1 (the table format of launch_edge_chi2)
-int pl_location(const gs_graph *g, int32_t k, int32_t &src) {
-    const Plan &P = g->plan;
-    if (k < P.base_Epl) { src = (size_t)k < P.ell_of_ins.size() ? P.ell_of_ins[(size_t)k] : -1;
-        if (src < 0) return fail(GS_ERR_INVALID, "observation edge outside the linearisation layout"); }
-    else { if (k - P.base_Epl >= g->d.tEpl) return fail(GS_ERR_INVALID, "observation edge not on the device"); src = -(k - P.base_Epl) - 1; }
-    return GS_OK;
-}
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 }  // namespace
 
 static int set_flag(gs_graph *g, int32_t kind, int32_t index, bool on) {
@@ -128,25 +119,20 @@ int edge_mask_sync(gs_graph *g) {
         E.loc[t] = k; E.act[t] = E.store.active(0, k) ? 1 : 0;
         std::memcpy(&E.orig[6 * t], &h.pp_info[6 * (size_t)k], 6 * sizeof(double)); }
     for (size_t t = 0; t < n1; ++t) { const int32_t k = ch[1][t]; int32_t src = -1;
-        int rc = pl_location(g, k, src); if (rc != GS_OK) return rc;
+        int rc = pl_location(g, k, src, ""); if (rc != GS_OK) return rc;
         E.loc[n0 + t] = src; E.act[n0 + t] = E.store.active(1, k) ? 1 : 0;
         std::memcpy(&E.orig[6 * n0 + 3 * t], &h.pl_info[3 * (size_t)k], 3 * sizeof(double)); }
-    const size_t o_orig = 0, o_loc = o_orig + al256(E.orig.size() * 8), o_act = o_loc + al256(n * 4), total = o_act + al256(n);
-    if (!E.mem || total > E.cap) {
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        if (E.mem) { hipFree(E.mem); E.mem = nullptr; E.cap = 0; }
-        const size_t cap = total + total / 2 + 4096;
-        if (hipMalloc(&E.mem, cap) != hipSuccess) { E.mem = nullptr; return fail(GS_ERR_HIP, "hipMalloc failed"); }
-        E.cap = cap; }
-    char *b = (char *)E.mem;
-    hipError_t e = hipMemcpyAsync(b + o_orig, E.orig.data(), E.orig.size() * 8, hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(b + o_loc, E.loc.data(), n * 4, hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(b + o_act, E.act.data(), n, hipMemcpyHostToDevice, g->stream);
+    ArenaLayout lay; const size_t o_orig = lay.add(E.orig.size() * 8), o_loc = lay.add(n * 4), o_act = lay.add(n);
+    int rc = arena_reserve(g, E.arena, lay.total); if (rc != GS_OK) return rc;
+    char *b = E.arena.at(0);
+    hipError_t e = arena_upload(g, E.arena, o_orig, E.orig.data(), E.orig.size() * 8);
+    HIP_NEXT(e, arena_upload(g, E.arena, o_loc, E.loc.data(), n * 4));
+    HIP_NEXT(e, arena_upload(g, E.arena, o_act, E.act.data(), n));
     if (e == hipSuccess) {
         launch_edge_mask_apply(d, 0, (int)n0, (const int32_t *)(b + o_loc), (const double *)(b + o_orig), (const uint8_t *)(b + o_act), g->stream);
         launch_edge_mask_apply(d, 1, (int)n1, (const int32_t *)(b + o_loc) + n0, (const double *)(b + o_orig) + 6 * n0, (const uint8_t *)(b + o_act) + n0, g->stream);
         e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream); else hipStreamSynchronize(g->stream);     // (the staging is rebuilt in place by the next change)
+    e = sync_keep_first(e, g->stream);                               // (the staging is rebuilt in place by the next change)
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("edge deactivation: ") + hipGetErrorString(e));
     E.sync.commit(E.store, n_edges, ch);
     E.sync.done(E.store.version, g->value_uploads, g->plan_version, g->prior.store.version);
@@ -164,25 +150,25 @@ static int eval_edges(gs_graph *g, int32_t kind, int32_t n, const std::vector<in
     std::vector<uint8_t> act((size_t)n);
     for (int32_t k = 0; k < n; ++k) act[(size_t)k] = g->emask.store.active(kind, k) ? 1 : 0;
     const int grid = edge_select_grid(n);
-    const size_t o_info = 0, o_sw = o_info + al256((size_t)n * per * 8), o_tab = o_sw + al256((size_t)n * 2 * 8), o_cnt = o_tab + al256(tab.size() * 4),
-                 o_act = o_cnt + al256((size_t)grid * 4), o_cand = o_act + al256((size_t)n), total = o_cand + al256((size_t)n);
-    char *b = nullptr;
-    HIP_TRY(hipMalloc((void **)&b, total));
+    ArenaLayout lay;
+    const size_t o_info = lay.add((size_t)n * per * 8), o_sw = lay.add((size_t)n * 2 * 8), o_tab = lay.add(tab.size() * 4), o_cnt = lay.add((size_t)grid * 4),
+                 o_act = lay.add((size_t)n), o_cand = lay.add((size_t)n);
+    DevScratch s; HIP_TRY(s.alloc(lay.total));
+    char *b = s.p;
     std::vector<int32_t> cnt((size_t)grid, 0);
     if (sw) sw->assign((size_t)n * 2, 0.0);
     if (cand) cand->assign((size_t)n, 0);
     hipError_t e = hipMemcpyAsync(b + o_info, info, (size_t)n * per * 8, hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(b + o_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(b + o_act, act.data(), (size_t)n, hipMemcpyHostToDevice, g->stream);
+    HIP_NEXT(e, hipMemcpyAsync(b + o_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, g->stream));
+    HIP_NEXT(e, hipMemcpyAsync(b + o_act, act.data(), (size_t)n, hipMemcpyHostToDevice, g->stream));
     if (e == hipSuccess) { launch_edge_select(g->d, kind, n, (const int32_t *)(b + o_tab), (const double *)(b + o_info), (const uint8_t *)(b + o_act), threshold,
                                               sw ? (double *)(b + o_sw) : nullptr, cand ? (uint8_t *)(b + o_cand) : nullptr, (int32_t *)(b + o_cnt), g->stream);
         e = hipGetLastError(); }
-    if (e == hipSuccess && sw && !pp && polar_edge_chi2_overwrite(g, n, (double *)(b + o_sw)) != GS_OK) { hipStreamSynchronize(g->stream); hipFree(b); return GS_ERR_HIP; }   // (the polar edges' own s and weight; nothing without polar edges)
-    if (e == hipSuccess && sw) e = hipMemcpyAsync(sw->data(), b + o_sw, (size_t)n * 2 * 8, hipMemcpyDeviceToHost, g->stream);
-    if (e == hipSuccess && cand) e = hipMemcpyAsync(cand->data(), b + o_cand, (size_t)n, hipMemcpyDeviceToHost, g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), b + o_cnt, (size_t)grid * 4, hipMemcpyDeviceToHost, g->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream); else hipStreamSynchronize(g->stream);
-    hipFree(b);
+    if (e == hipSuccess && sw && !pp && polar_edge_chi2_overwrite(g, n, (double *)(b + o_sw)) != GS_OK) { hipStreamSynchronize(g->stream); return GS_ERR_HIP; }   // (the polar edges' own s and weight; nothing without polar edges)
+    if (sw) HIP_NEXT(e, hipMemcpyAsync(sw->data(), b + o_sw, (size_t)n * 2 * 8, hipMemcpyDeviceToHost, g->stream));
+    if (cand) HIP_NEXT(e, hipMemcpyAsync(cand->data(), b + o_cand, (size_t)n, hipMemcpyDeviceToHost, g->stream));
+    HIP_NEXT(e, hipMemcpyAsync(cnt.data(), b + o_cnt, (size_t)grid * 4, hipMemcpyDeviceToHost, g->stream));
+    e = sync_keep_first(e, g->stream);
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("edge select: ") + hipGetErrorString(e));
     if (n_cand) { *n_cand = 0; for (int32_t c : cnt) *n_cand += c; }
     return GS_OK;
@@ -215,7 +201,7 @@ extern "C" int gs_deactivate_edges_above(gs_graph *g, int32_t kind, double s_thr
         for (int32_t k = 0; k < n; ++k) { tab[2 * (size_t)k] = h.pp_i[(size_t)k]; tab[2 * (size_t)k + 1] = h.pp_j[(size_t)k]; }
     } else {
         tab.resize((size_t)n * 3);
-        for (int32_t k = 0; k < n; ++k) { int32_t src; rc = pl_location(g, k, src); if (rc != GS_OK) return rc;
+        for (int32_t k = 0; k < n; ++k) { int32_t src; rc = pl_location(g, k, src, ""); if (rc != GS_OK) return rc;
             tab[3 * (size_t)k] = h.pl_p[(size_t)k]; tab[3 * (size_t)k + 1] = h.pl_l[(size_t)k]; tab[3 * (size_t)k + 2] = src; }
     }
     std::vector<uint8_t> cand; int64_t n_cand = 0;

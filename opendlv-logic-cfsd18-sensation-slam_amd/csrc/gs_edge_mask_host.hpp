@@ -8,9 +8,7 @@
 // never saw a deactivation (both vectors empty: the handle then does nothing new anywhere).
 // A FREE vertex is isolated when it carries no prior and none of its edges is active: its diagonal block of H would be zero.
 #pragma once
-#include <cstddef>
-#include <cstdint>
-#include <vector>
+#include "gs_side_host.hpp"
 
 namespace gs {
 
@@ -96,11 +94,11 @@ inline std::vector<int32_t> deactivate_candidates(const MaskGraphView &v, EdgeMa
 // writes the appended edges only; they are beyond have[]'s end, i.e. "own information", until a sync says otherwise.
 struct EdgeMaskSync {
     std::vector<uint8_t> have[2];
-    uint64_t store_version = ~0ull, uploads = ~0ull, plan_version = ~0ull, prior_version = ~0ull;
-    bool needed(uint64_t sv, uint64_t up, uint64_t pv, uint64_t prv) const { return store_version != sv || uploads != up || plan_version != pv || prior_version != prv; }
+    SyncStamp<4> stamp;                              // the flags' version, the full uploads of the edge values, the plan's version, the priors'
+    bool needed(uint64_t sv, uint64_t up, uint64_t pv, uint64_t prv) const { return stamp.needed(sv, up, pv, prv); }
     // the edges whose device values differ from what the flags ask for, per kind, ascending (after a full upload: every inactive edge)
     void changes(const EdgeMaskStore &s, const int32_t n_edges[2], uint64_t uploads_now, std::vector<int32_t> out[2]) {
-        if (uploads != uploads_now) { have[0].clear(); have[1].clear(); uploads = uploads_now; }
+        if (stamp.at[1] != uploads_now) { have[0].clear(); have[1].clear(); stamp.at[1] = uploads_now; }
         for (int kind = 0; kind < 2; ++kind) {
             out[kind].clear();
             const std::vector<uint8_t> &h = have[kind];
@@ -116,8 +114,8 @@ struct EdgeMaskSync {
             if (!list[kind].empty() && h.size() < (std::size_t)n_edges[kind]) h.resize((std::size_t)n_edges[kind], 1);
             for (int32_t k : list[kind]) h[(std::size_t)k] = s.active(kind, k) ? 1 : 0; }
     }
-    void done(uint64_t sv, uint64_t up, uint64_t pv, uint64_t prv) { store_version = sv; uploads = up; plan_version = pv; prior_version = prv; }
-    void invalidate() { have[0].clear(); have[1].clear(); store_version = uploads = plan_version = prior_version = ~0ull; }
+    void done(uint64_t sv, uint64_t up, uint64_t pv, uint64_t prv) { stamp.done(sv, up, pv, prv); }
+    void invalidate() { have[0].clear(); have[1].clear(); stamp = SyncStamp<4>(); }
 };
 
 }  // namespace gs

@@ -16,6 +16,12 @@
 #include "gs_prior.hpp"
 #include "gs_schedule.hpp"
 
+namespace gs {
+// One grow-only device allocation of the handle's own, holding the blocks of an ArenaLayout (gs_side_host.hpp); reserve / upload /
+// release: gs_private.hpp
+struct DevArena { void *mem = nullptr; size_t cap = 0; char *at(size_t off) const { return (char *)mem + off; } };
+}
+
 struct gs_graph {
     gs_config cfg{};
     gs_debug_options opt{};                 // every tuning switch (graphslam_debug.h): filled once at gs_create, replaced by gs_debug_set_options
@@ -91,15 +97,15 @@ struct gs_graph {
     struct Lm { gs::LmDev dev{}; void *mem = nullptr; size_t cap_p = 0, cap_l = 0; gs::LmState host[2]{}; } lm;
     // prior edges (gs_prior.hpp): the priors as added, the grouped tables, and their device copy — one allocation of the handle's own,
     // grow-only; uploaded whole by prior_sync when the priors or the plan changed.  dev stays empty while there is no prior on a free vertex
-    struct Prior { gs::PriorStore store; gs::PriorTables tab; gs::PriorSync sync; gs::PriorDev dev{}; void *mem = nullptr; size_t cap = 0;
+    struct Prior { gs::PriorStore store; gs::PriorTables tab; gs::PriorSync sync; gs::PriorDev dev{}; gs::DevArena arena;
                    uint64_t settled = 0; /* store.version prior_sync last looked at */ } prior;
     // edge deactivation (gs_edge_mask.hpp): the flags, what the device holds against them, and the staging of one k_edge_mask_apply
     // launch per kind — one allocation of the handle's own, grow-only, made at the first sync of a handle that has had an inactive edge
-    struct EdgeMask { gs::EdgeMaskStore store; gs::EdgeMaskSync sync; void *mem = nullptr; size_t cap = 0;
+    struct EdgeMask { gs::EdgeMaskStore store; gs::EdgeMaskSync sync; gs::DevArena arena;
                       std::vector<int32_t> loc; std::vector<double> orig; std::vector<uint8_t> act; /* host side of the staging */ } emask;
     // polar observation edges (gs_polar.hpp): the measurements as added (under their carriers' observation indices), the tables, and
     // their device copy — one allocation of the handle's own, grow-only, made at the first sync of a handle that holds a polar edge
-    struct Polar { gs::PolarStore store; gs::PolarTables tab; gs::PolarSync sync; gs::PolarDev dev{}; void *mem = nullptr; size_t cap = 0; } polar;
+    struct Polar { gs::PolarStore store; gs::PolarTables tab; gs::PolarSync sync; gs::PolarDev dev{}; gs::DevArena arena; } polar;
     uint64_t value_uploads = 0;             // full uploads of the edge values (upload_graph): each puts every edge's own information on the device
 };
 

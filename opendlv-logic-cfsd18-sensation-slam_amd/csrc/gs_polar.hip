@@ -16,42 +16,17 @@
 // is STORED at the record's location (Hpl planes, stride ell_len, or t_Hpl, stride tcapEpl: the carrier's block, which the linearisation
 // wrote as zeros), A^T Omega A and -A^T Omega e are summed in registers and ADDED to Hpp_diag / b_pose (t_Hpp_diag / t_b_pose for a tail
 // pose), rho(s) is summed for chi2.  k_polar_lm: thread j < n_lv is listed landmark j; it walks the landmark's run (the second index),
-// recomputes B^T Omega B and -B^T Omega e by the same expressions and ADDS them where the front assembly reads the landmark — the four
-// address cases of k_prior_pass:
-//   landmark l < M          gather path: Hll_diag planes 0 .. 2, b_lm planes 0, 1 (stride M); fused path: entries 0 .. 4 of the landmark's
-//                           FIRST lm_part slot (the fronts and k_linearize_finalize sum the landmark's run of slots)
-//   tail landmark           t_Hll_diag, t_b_lm (stride tcapM), slot l - M
+// recomputes B^T Omega B and -B^T Omega e by the same expressions and ADDS them where the front assembly reads the landmark
+// (side_add_lm, gs_side_dev.hpp).
 // Fixed vertices as in the main kernels: a fixed endpoint stays out of H (its diagonal share is not added, the H_pl block is zero), an
 // edge between two fixed vertices stays out of chi2.  One writer per address (a vertex is listed once, an edge has one location), no
 // floating-point atomics, every index checked against the plan's counts, plain vector stores.  chi2: one partial per workgroup, lanes ->
 // waves in a fixed order; the total of the partials, summed by one workgroup in a fixed order, is ADDED to *chi_target by one thread
-// (k_polar_total, or the pose side itself when it is one workgroup).
+// (k_side_total, or the pose side itself when it is one workgroup).
 #include "gs_polar.hpp"
+#include "gs_side_dev.hpp"
 
 namespace gs {
-
-static constexpr int POLAR_LM_PART = 8;      // doubles per lm_part record (gs_kernels.hip)
-static constexpr double kPolarPi = 3.14159265358979323846;
-
-__device__ __forceinline__ double polar_normalize_theta(double th) {     // g2o normalize_theta, as in gs_kernels.hip
-#pragma clang fp contract(off)
-    if (th >= -kPolarPi && th < kPolarPi) return th;
-    const double m = floor(th / (2.0 * kPolarPi));
-    th = th - m * 2.0 * kPolarPi;
-    if (th >= kPolarPi) th -= 2.0 * kPolarPi;
-    if (th < -kPolarPi) th += 2.0 * kPolarPi;
-    return th;
-}
-// rho(s) and w = rho'(s) of robust_rho (gs_kernels.hip): w exactly 1 where the kernel does not act
-__device__ __forceinline__ double polar_robust_rho(int kernel, double delta, double s, double &w) {
-#pragma clang fp contract(off)
-    w = 1.0;
-    if (kernel == 1) { const double d2 = delta * delta;
-        if (s > d2) { const double r = sqrt(s); w = delta / r; return 2.0 * r * delta - d2; }
-        return s; }
-    if (kernel == 2) { const double d2 = delta * delta, aux = 1.0 + s / d2; w = 1.0 / aux; return d2 * log(aux); }
-    return s;
-}
 
 // everything one polar edge produces, packed as PlQuad of gs_kernels.hip: Hp = A^T W A (xx xy xt yy yt tt), bp = -A^T W e,
 // W6 = A^T W B (3 x 2 row-major), Hl = B^T W B (00 01 11), bl = -B^T W e with W = w Omega; s = e^T Omega e, chi = rho(s), wr = w
@@ -61,24 +36,19 @@ struct PolarQuad { double Hp[6], bp[3], W6[6], Hl[3], bl[2], s, chi, wr; };
 __device__ __forceinline__ bool polar_quad(double px, double py, double c, double s, double lx, double ly, double zr, double zb,
                                            double w00, double w01, double w11, int rk, double rd, PolarQuad &q) {
     double dx, dy;
-    {
-#pragma clang fp contract(off)
-        const double ix = -(c * px + s * py), iy = s * px - c * py;
-        dx = (c * lx + s * ly) + ix;
-        dy = (c * ly - s * lx) + iy;
-    }
+    side_lm_in_pose_frame(px, py, c, s, lx, ly, dx, dy);
     const double r2 = dx * dx + dy * dy;
     q.s = 0.0; q.chi = 0.0; q.wr = 1.0;
     if (!(r2 > 0.0)) return false;
     const double r = sqrt(r2), beta = atan2(dy, dx);
-    const double e0 = r - zr, e1 = polar_normalize_theta(beta - zb);
+    const double e0 = r - zr, e1 = side_normalize_theta(beta - zb);
     const double j00 = dx / r, j01 = dy / r, j10 = -dy / r2, j11 = dx / r2;
     // B = Jd R^T, R^T rows (c, s), (-s, c)
     const double B0[2] = {j00 * c - j01 * s, j00 * s + j01 * c}, B1[2] = {j10 * c - j11 * s, j10 * s + j11 * c};
     const double A0[3] = {-B0[0], -B0[1], 0.0}, A1[3] = {-B1[0], -B1[1], -1.0};
     double We0 = w00 * e0 + w01 * e1, We1 = w01 * e0 + w11 * e1;
     q.s = e0 * We0 + e1 * We1;
-    q.chi = polar_robust_rho(rk, rd, q.s, q.wr);
+    q.chi = side_robust_rho(rk, rd, q.s, q.wr);
     w00 *= q.wr; w01 *= q.wr; w11 *= q.wr; We0 *= q.wr; We1 *= q.wr;
     double WA0[3], WA1[3];
 #pragma unroll
@@ -101,15 +71,6 @@ __device__ __forceinline__ bool polar_record(const DevGraph &d, const PolarDev &
     const double2 cs = reinterpret_cast<const double2 *>(d.pose_cs)[p];
     return polar_quad(d.pose_est[3 * (int64_t)p], d.pose_est[3 * (int64_t)p + 1], cs.x, cs.y, d.lm_est[2 * (int64_t)l], d.lm_est[2 * (int64_t)l + 1],
                       pd.planes[r], pd.planes[S + r], pd.planes[2 * S + r], pd.planes[3 * S + r], pd.planes[4 * S + r], d.rk_pl, d.rd_pl, q);
-}
-
-// fixed-order sum over the 256 threads, the result in thread 0 (red: 4 doubles of LDS)
-__device__ __forceinline__ double polar_block_sum(double v, double *red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
 template <bool APPLY>
@@ -135,44 +96,24 @@ __global__ void __launch_bounds__(256) k_polar_pose(DevGraph d, PolarDev pd, dou
                 if (!(fp && fl)) chi += q.chi;
                 if (APPLY) {
                     const bool both = !fp && !fl;
-                    const int src = pd.rec_src[r];
-                    if (src >= 0) { const int64_t L = d.ell_len;
-                        if ((int64_t)src < L && d.Hpl) {
+                    const int src = pd.rec_src[r]; int e;
+                    if (side_pl_in_ell(d, src)) { const int64_t L = d.ell_len;
+                        if (d.Hpl) {
 #pragma unroll
                             for (int k = 0; k < 6; ++k) d.Hpl[k * L + src] = both ? q.W6[k] : 0.0; } }
-                    else { const int e = -(src + 1); const int64_t St = d.tcapEpl;
-                        if (e >= 0 && e < d.tEpl && e < d.tcapEpl && d.t_Hpl) {
+                    else if (side_pl_in_tail(d, src, e) && d.t_Hpl) { const int64_t St = d.tcapEpl;
 #pragma unroll
-                            for (int k = 0; k < 6; ++k) d.t_Hpl[k * St + e] = both ? q.W6[k] : 0.0; } }
+                        for (int k = 0; k < 6; ++k) d.t_Hpl[k * St + e] = both ? q.W6[k] : 0.0; }
 #pragma unroll
                     for (int k = 0; k < 6; ++k) H[k] += q.Hp[k];
 #pragma unroll
                     for (int k = 0; k < 3; ++k) b[k] += q.bp[k];
                 }
             }
-            if (APPLY && !fp && (p < d.N || (p - d.N) < d.tcapN)) {
-                double *Hd = p < d.N ? d.Hpp_diag + p : d.t_Hpp_diag + (p - d.N), *bd = p < d.N ? d.b_pose + p : d.t_b_pose + (p - d.N);
-                const int64_t St = p < d.N ? d.N : d.tcapN;
-#pragma unroll
-                for (int k = 0; k < 6; ++k) Hd[k * St] += H[k];
-#pragma unroll
-                for (int k = 0; k < 3; ++k) bd[k * St] += b[k]; }
+            if (APPLY && !fp) side_add_pose(d, p, H, b);
         }
     }
-    const double tot = polar_block_sum(chi, red);
-    if (threadIdx.x == 0) {
-        // (+=: the slot holds this pass's total or one of its partials, written EARLIER ON THIS STREAM by the linearisation / chi2 / prior
-        // launches; the pass must stay behind them)
-        if (gridDim.x == 1) *chi_target += tot;                         // the whole pose side is this workgroup: no second launch
-        else pd.part[blockIdx.x] = tot; }
-}
-// the workgroups' partials by ONE workgroup in a fixed order, as k_prior_total does
-__global__ void __launch_bounds__(256) k_polar_total(PolarDev pd, int n_part, double *__restrict__ chi_target) {
-    __shared__ double red[4];
-    double s = 0.0;
-    for (int k = threadIdx.x; k < n_part; k += 256) s += pd.part[k];
-    const double tot = polar_block_sum(s, red);
-    if (threadIdx.x == 0) *chi_target += tot;
+    side_chi2_finish(chi, red, pd.part, chi_target);
 }
 
 __global__ void __launch_bounds__(256) k_polar_lm(DevGraph d, PolarDev pd) {
@@ -194,16 +135,7 @@ __global__ void __launch_bounds__(256) k_polar_lm(DevGraph d, PolarDev pd) {
         if (!polar_record(d, pd, r, p, l, q)) continue;
         H[0] += q.Hl[0]; H[1] += q.Hl[1]; H[2] += q.Hl[2]; b[0] += q.bl[0]; b[1] += q.bl[1];
     }
-    if (l >= d.M) { const int o = l - d.M; const int64_t St = d.tcapM;
-        if (o < d.tcapM && d.t_Hll_diag) {
-            d.t_Hll_diag[o] += H[0]; d.t_Hll_diag[St + o] += H[1]; d.t_Hll_diag[2 * St + o] += H[2]; d.t_b_lm[o] += b[0]; d.t_b_lm[St + o] += b[1]; } }
-    // (fused path: the landmark has a partial-sum slot — its carrier is an observation edge of the layout, or the host refused the
-    // upload; the guard keeps the store in bounds whatever the tables say)
-    else if (d.n_wtiles > 0) { const int q0 = d.lm_grp_start[l];
-        if (q0 >= 0 && q0 < d.lm_grp_start[l + 1] && q0 < d.n_groups) { double *s = d.lm_part + (int64_t)q0 * POLAR_LM_PART;
-            s[0] += H[0]; s[1] += H[1]; s[2] += H[2]; s[3] += b[0]; s[4] += b[1]; } }
-    else { const int64_t St = d.M;
-        d.Hll_diag[l] += H[0]; d.Hll_diag[St + l] += H[1]; d.Hll_diag[2 * St + l] += H[2]; d.b_lm[l] += b[0]; d.b_lm[St + l] += b[1]; }
+    side_add_lm(d, l, H, b);
 }
 
 // gs_get_edge_chi2: s and weight of the polar edges over what the per-edge kernel wrote for their carriers (fixed vertices do not matter here)
@@ -227,7 +159,7 @@ void launch_polar_pass(const DevGraph &d, const PolarDev &pd, bool apply, double
     if (grid <= 0) return;
     if (apply) hipLaunchKernelGGL(k_polar_pose<true>, dim3(grid), dim3(256), 0, st, d, pd, chi_target);
     else hipLaunchKernelGGL(k_polar_pose<false>, dim3(grid), dim3(256), 0, st, d, pd, chi_target);
-    if (grid > 1) hipLaunchKernelGGL(k_polar_total, dim3(1), dim3(256), 0, st, pd, grid, chi_target);
+    if (grid > 1) launch_side_total(pd.part, grid, chi_target, st);
     if (apply && pd.n_lv > 0) hipLaunchKernelGGL(k_polar_lm, dim3((pd.n_lv + 255) / 256), dim3(256), 0, st, d, pd);
 }
 void launch_polar_edge_chi2(const DevGraph &d, int n_pol, const int32_t *tab, const double *vals, const uint8_t *act, int n, double *out, hipStream_t st) {

@@ -13,15 +13,6 @@
 using namespace gs;
 
 namespace {
-size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
-// where observation edge k lives on the device: its ELL index, or -(tail slot) - 1 (the table format of launch_edge_chi2)
-int polar_location(const gs_graph *g, int32_t k, int32_t &src) {
-    const Plan &P = g->plan;
-    if (k < P.base_Epl) { src = (size_t)k < P.ell_of_ins.size() ? P.ell_of_ins[(size_t)k] : -1;
-        if (src < 0) return fail(GS_ERR_INVALID, "polar edges: observation edge outside the linearisation layout"); }
-    else { if (k - P.base_Epl >= g->d.tEpl) return fail(GS_ERR_INVALID, "polar edges: observation edge not on the device"); src = -(k - P.base_Epl) - 1; }
-    return GS_OK;
-}
 // the checks every add shares; on GS_OK p / l are the vertex indices.  Nothing has been appended when this refuses
 int polar_check(gs_graph *g, int32_t pose_id, int32_t lm_id, int32_t &p, int32_t &l) {
     if (g->world > 1) return fail(GS_ERR_INVALID, "polar observation edges are not supported on sharded handles (gs_dist_configure with world > 1)");
@@ -97,38 +88,29 @@ int polar_sync(gs_graph *g) {
     for (int32_t k : S.obs) {
         if (k < 0 || k >= Epl || h.pl_info[3 * (size_t)k] != 0.0 || h.pl_info[3 * (size_t)k + 1] != 0.0 || h.pl_info[3 * (size_t)k + 2] != 0.0)
             return fail(GS_ERR_INVALID, "polar edges: a carrier is not the zero-information observation edge it was added as");
-        int rc = polar_location(g, k, src[(size_t)k]); if (rc != GS_OK) return rc; }
+        int rc = pl_location(g, k, src[(size_t)k], "polar edges: "); if (rc != GS_OK) return rc; }
     if (g->emask.store.any_off()) { act.assign((size_t)Epl, 1); for (int32_t k : S.obs) act[(size_t)k] = g->emask.store.active(1, k) ? 1 : 0; }
     std::string err;
     if (!build_polar_tables(S, N, M, Epl, src.data(), act.empty() ? nullptr : act.data(), P.tab, err)) return fail(GS_ERR_INVALID, "polar edges: " + err);
     const PolarTables &T = P.tab;
-    // fused linearisation: an old landmark's block lives in its first partial-sum slot — it must have one
-    if (d.n_wtiles > 0) for (int32_t l : T.lv_id)
-        if (l < d.M && !h.lm_fixed[(size_t)l] && !(g->plan.lm_grp_start[(size_t)l] < g->plan.lm_grp_start[(size_t)l + 1]))
-            return fail(GS_ERR_INVALID, "polar edges: a free landmark without an observation edge in the linearisation layout cannot carry one");
-    const size_t n = (size_t)T.n_rec, npv = T.pv_id.size(), nlv = T.lv_id.size(), n_part = (npv + 255) / 256;
-    const size_t o_pv = 0, o_ps = o_pv + al256(npv * 4), o_lv = o_ps + al256((npv + 1) * 4), o_ls = o_lv + al256(nlv * 4), o_rp = o_ls + al256((nlv + 1) * 4),
-                 o_rl = o_rp + al256(n * 4), o_rs = o_rl + al256(n * 4), o_lo = o_rs + al256(n * 4), o_pl = o_lo + al256(n * 4),
-                 o_part = o_pl + al256(T.planes.size() * 8), total = o_part + al256(n_part * 8);
-    if (!P.mem || total > P.cap) {
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        if (P.mem) { hipFree(P.mem); P.mem = nullptr; P.cap = 0; }
-        const size_t cap = total + total / 2 + 4096;
-        if (hipMalloc(&P.mem, cap) != hipSuccess) { P.mem = nullptr; return fail(GS_ERR_HIP, "hipMalloc failed"); }
-        P.cap = cap; }
-    char *b = (char *)P.mem;
-    auto up = [&](size_t off, const void *s, size_t bytes) -> hipError_t {
-        return bytes ? hipMemcpyAsync(b + off, s, bytes, hipMemcpyHostToDevice, g->stream) : hipSuccess; };
-    HIP_TRY(up(o_pv, T.pv_id.data(), npv * 4)); HIP_TRY(up(o_ps, T.pv_start.data(), (npv + 1) * 4));
-    HIP_TRY(up(o_lv, T.lv_id.data(), nlv * 4)); HIP_TRY(up(o_ls, T.lv_start.data(), (nlv + 1) * 4));
-    HIP_TRY(up(o_rp, T.rec_pose.data(), n * 4)); HIP_TRY(up(o_rl, T.rec_lm.data(), n * 4)); HIP_TRY(up(o_rs, T.rec_src.data(), n * 4));
-    HIP_TRY(up(o_lo, T.lm_order.data(), n * 4)); HIP_TRY(up(o_pl, T.planes.data(), T.planes.size() * 8));
+    for (int32_t l : T.lv_id) if (lm_lacks_fused_slot(g, l))
+        return fail(GS_ERR_INVALID, "polar edges: a free landmark without an observation edge in the linearisation layout cannot carry one");
+    const size_t n = (size_t)T.n_rec, npv = T.pv_id.size(), nlv = T.lv_id.size();
+    ArenaLayout lay;
+    const size_t o_pv = lay.add(npv * 4), o_ps = lay.add((npv + 1) * 4), o_lv = lay.add(nlv * 4), o_ls = lay.add((nlv + 1) * 4), o_rp = lay.add(n * 4),
+                 o_rl = lay.add(n * 4), o_rs = lay.add(n * 4), o_lo = lay.add(n * 4), o_pl = lay.add(T.planes.size() * 8), o_part = lay.add((npv + 255) / 256 * 8);
+    int rc = arena_reserve(g, P.arena, lay.total); if (rc != GS_OK) return rc;
+    const DevArena &A = P.arena;
+    HIP_TRY(arena_upload(g, A, o_pv, T.pv_id.data(), npv * 4)); HIP_TRY(arena_upload(g, A, o_ps, T.pv_start.data(), (npv + 1) * 4));
+    HIP_TRY(arena_upload(g, A, o_lv, T.lv_id.data(), nlv * 4)); HIP_TRY(arena_upload(g, A, o_ls, T.lv_start.data(), (nlv + 1) * 4));
+    HIP_TRY(arena_upload(g, A, o_rp, T.rec_pose.data(), n * 4)); HIP_TRY(arena_upload(g, A, o_rl, T.rec_lm.data(), n * 4)); HIP_TRY(arena_upload(g, A, o_rs, T.rec_src.data(), n * 4));
+    HIP_TRY(arena_upload(g, A, o_lo, T.lm_order.data(), n * 4)); HIP_TRY(arena_upload(g, A, o_pl, T.planes.data(), T.planes.size() * 8));
     HIP_TRY(hipStreamSynchronize(g->stream));                        // (the tables are rebuilt in place by the next change)
     PolarDev D;
     D.n_rec = T.n_rec; D.n_pv = (int32_t)npv; D.n_lv = (int32_t)nlv;
-    D.pv_id = (const int32_t *)(b + o_pv); D.pv_start = (const int32_t *)(b + o_ps); D.lv_id = (const int32_t *)(b + o_lv); D.lv_start = (const int32_t *)(b + o_ls);
-    D.rec_pose = (const int32_t *)(b + o_rp); D.rec_lm = (const int32_t *)(b + o_rl); D.rec_src = (const int32_t *)(b + o_rs); D.lm_order = (const int32_t *)(b + o_lo);
-    D.planes = (const double *)(b + o_pl); D.part = (double *)(b + o_part);
+    D.pv_id = (const int32_t *)A.at(o_pv); D.pv_start = (const int32_t *)A.at(o_ps); D.lv_id = (const int32_t *)A.at(o_lv); D.lv_start = (const int32_t *)A.at(o_ls);
+    D.rec_pose = (const int32_t *)A.at(o_rp); D.rec_lm = (const int32_t *)A.at(o_rl); D.rec_src = (const int32_t *)A.at(o_rs); D.lm_order = (const int32_t *)A.at(o_lo);
+    D.planes = (const double *)A.at(o_pl); D.part = (double *)A.at(o_part);
     P.dev = D;
     P.sync.done(P.store.version, g->plan_version, g->emask.store.version, g->value_uploads);
     return GS_OK;
@@ -144,16 +126,14 @@ int polar_edge_chi2_overwrite(gs_graph *g, int32_t n, double *dev_out) {
     std::vector<int32_t> tab((size_t)np * 3); std::vector<uint8_t> act((size_t)np);
     for (int k = 0; k < np; ++k) { tab[3 * (size_t)k] = S.obs[(size_t)k]; tab[3 * (size_t)k + 1] = S.pose_v[(size_t)k]; tab[3 * (size_t)k + 2] = S.lm_v[(size_t)k];
         act[(size_t)k] = g->emask.store.active(1, S.obs[(size_t)k]) ? 1 : 0; }
-    const size_t o_vals = 0, o_tab = o_vals + al256(S.rec.size() * 8), o_act = o_tab + al256(tab.size() * 4), total = o_act + al256((size_t)np);
-    char *b = nullptr;
-    HIP_TRY(hipMalloc((void **)&b, total));
-    hipError_t e = hipMemcpyAsync(b + o_vals, S.rec.data(), S.rec.size() * 8, hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(b + o_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(b + o_act, act.data(), (size_t)np, hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) { launch_polar_edge_chi2(g->d, np, (const int32_t *)(b + o_tab), (const double *)(b + o_vals), (const uint8_t *)(b + o_act), n, dev_out, g->stream);
+    ArenaLayout lay; const size_t o_vals = lay.add(S.rec.size() * 8), o_tab = lay.add(tab.size() * 4), o_act = lay.add((size_t)np);
+    DevScratch s; HIP_TRY(s.alloc(lay.total));
+    hipError_t e = hipMemcpyAsync(s.p + o_vals, S.rec.data(), S.rec.size() * 8, hipMemcpyHostToDevice, g->stream);
+    HIP_NEXT(e, hipMemcpyAsync(s.p + o_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, g->stream));
+    HIP_NEXT(e, hipMemcpyAsync(s.p + o_act, act.data(), (size_t)np, hipMemcpyHostToDevice, g->stream));
+    if (e == hipSuccess) { launch_polar_edge_chi2(g->d, np, (const int32_t *)(s.p + o_tab), (const double *)(s.p + o_vals), (const uint8_t *)(s.p + o_act), n, dev_out, g->stream);
         e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream); else hipStreamSynchronize(g->stream);     // (the staging is freed below)
-    hipFree(b);
+    e = sync_keep_first(e, g->stream);
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("polar edge chi2: ") + hipGetErrorString(e));
     return GS_OK;
 }

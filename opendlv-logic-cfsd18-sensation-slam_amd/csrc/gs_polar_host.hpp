@@ -14,10 +14,9 @@
 // An inactive edge (gs_set_edge_active) goes up with Omega = 0: exact zeros in H, b and chi2, as the carrier gives.
 // Fixed vertices stay listed: the kernels read the device's fixed flags (a fixed pose's edges still count in chi2 and zero their H_pl block).
 #pragma once
-#include <cmath>
-#include <cstdint>
 #include <string>
-#include <vector>
+
+#include "gs_side_host.hpp"
 
 namespace gs {
 
@@ -30,13 +29,6 @@ struct PolarStore {                                  // insertion order; vertex 
     int n() const { return (int)obs.size(); }
     bool empty() const { return obs.empty(); }
     void clear() { if (!empty()) ++version; obs.clear(); model.clear(); pose_v.clear(); lm_v.clear(); rec.clear(); }
-    static double normalize_theta(double th) {
-        if (th >= -M_PI && th < M_PI) return th;
-        const double m = std::floor(th / (2 * M_PI)); th -= m * 2 * M_PI;
-        if (th >= M_PI) th -= 2 * M_PI;
-        if (th < -M_PI) th += 2 * M_PI;
-        return th;
-    }
     // w = (w_rr, w_rb, w_bb); z_beta is normalised when stored
     void add(int32_t obs_index, int32_t mdl, int32_t p, int32_t l, double z_r, double z_beta, const double w[3]) {
         const double r[POLAR_REC] = {z_r, normalize_theta(z_beta), w[0], w[1], w[2]};
@@ -53,18 +45,6 @@ struct PolarTables {
     std::vector<double> planes;                                 // [POLAR_REC][n_rec]
 };
 
-// counting sort of `key` (values in [0, n_key)): ids = the keys that occur (ascending), start = run starts, order = the items sorted
-// by key, stable
-inline void polar_group(const std::vector<int32_t> &key, int n_key, std::vector<int32_t> &ids, std::vector<int32_t> &start, std::vector<int32_t> &order) {
-    ids.clear(); start.clear(); order.assign(key.size(), 0);
-    std::vector<int32_t> count((size_t)n_key + 1, 0), slot((size_t)n_key + 1, 0);
-    for (int32_t v : key) ++count[(size_t)v];
-    int32_t at = 0;
-    for (int v = 0; v < n_key; ++v) if (count[(size_t)v] > 0) { ids.push_back(v); start.push_back(at); slot[(size_t)v] = at; at += count[(size_t)v]; }
-    start.push_back(at);
-    for (size_t k = 0; k < key.size(); ++k) order[(size_t)slot[(size_t)key[k]]++] = (int32_t)k;
-}
-
 // N, M, Epl: the graph's counts; src_of_obs[Epl]: the location of every observation edge's H_pl block (encoding above; only the polar
 // edges' entries are read); active[Epl]: 0 = switched off (nullptr: all active)
 inline bool build_polar_tables(const PolarStore &S, int N, int M, int Epl, const int32_t *src_of_obs, const uint8_t *active, PolarTables &T, std::string &err) {
@@ -75,24 +55,19 @@ inline bool build_polar_tables(const PolarStore &S, int N, int M, int Epl, const
         if (S.obs[(size_t)k] < 0 || S.obs[(size_t)k] >= Epl) { err = "polar edge without its observation edge"; return false; } }
     T.n_rec = n;
     std::vector<int32_t> by_pose;
-    polar_group(S.pose_v, N, T.pv_id, T.pv_start, by_pose);
+    group_by_key(S.pose_v, N, nullptr, T.pv_id, T.pv_start, by_pose);
     T.rec_pose.resize((size_t)n); T.rec_lm.resize((size_t)n); T.rec_src.resize((size_t)n); T.rec_obs.resize((size_t)n);
     T.planes.assign((size_t)POLAR_REC * (size_t)n, 0.0);
     for (int r = 0; r < n; ++r) { const size_t k = (size_t)by_pose[(size_t)r];
         T.rec_pose[(size_t)r] = S.pose_v[k]; T.rec_lm[(size_t)r] = S.lm_v[k]; T.rec_obs[(size_t)r] = S.obs[k]; T.rec_src[(size_t)r] = src_of_obs[(size_t)S.obs[k]];
         const bool on = !active || active[(size_t)S.obs[k]] != 0;
         for (int c = 0; c < POLAR_REC; ++c) T.planes[(size_t)c * (size_t)n + (size_t)r] = (c >= 2 && !on) ? 0.0 : S.rec[k * POLAR_REC + (size_t)c]; }
-    polar_group(T.rec_lm, M, T.lv_id, T.lv_start, T.lm_order);
+    group_by_key(T.rec_lm, M, nullptr, T.lv_id, T.lv_start, T.lm_order);
     return true;
 }
 
 // What the device holds against what the handle holds: the tables go up again (whole: they are small) when the polar edges, the plan
 // (locations, counts, the tail), the edge flags or the edge values on the device changed
-struct PolarSync {
-    uint64_t store_version = ~0ull, plan_version = ~0ull, mask_version = ~0ull, value_uploads = ~0ull; bool valid = false;
-    bool needed(uint64_t s, uint64_t p, uint64_t m, uint64_t u) const { return !valid || store_version != s || plan_version != p || mask_version != m || value_uploads != u; }
-    void done(uint64_t s, uint64_t p, uint64_t m, uint64_t u) { store_version = s; plan_version = p; mask_version = m; value_uploads = u; valid = true; }
-    void invalidate() { valid = false; }
-};
+using PolarSync = SyncStamp<4>;                     // the store's version, the plan's, the edge flags', the full uploads of the edge values
 
 }  // namespace gs

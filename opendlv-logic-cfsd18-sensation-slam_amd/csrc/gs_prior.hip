@@ -10,33 +10,13 @@
 //
 // k_prior_pass: thread v < n_pv is listed pose v, thread n_pv + j listed landmark j; 256 threads per workgroup.  The thread walks its
 // vertex's run of records in order, sums J^T Omega J (packed symmetric), -J^T Omega e and e^T Omega e, and ADDS block and right-hand
-// side where the front assembly reads them (the address cases of k_lm_damp / k_lm_scale):
-//   pose p < N              Hpp_diag planes 0 .. 5, b_pose planes 0 .. 2 (stride N)
-//   tail pose               t_Hpp_diag, t_b_pose (stride tcapN), slot p - N
-//   landmark l < M          gather path: Hll_diag planes 0 .. 2, b_lm planes 0, 1 (stride M); fused path: entries 0 .. 4 of the landmark's
-//                           FIRST lm_part slot (the fronts and k_linearize_finalize sum the landmark's run of slots)
-//   tail landmark           t_Hll_diag, t_b_lm (stride tcapM), slot l - M
-// One writer per address (a vertex is listed once), no atomics.  chi2: one partial per workgroup, lanes -> waves in a fixed order; the
-// total of the partials, summed by one workgroup in a fixed order, is ADDED to *chi_target by one thread (k_prior_total, or the pass itself
-// when it is one workgroup).
+// side where the front assembly reads them (side_add_pose / side_add_lm, gs_side_dev.hpp).  One writer per address (a vertex is listed
+// once), no atomics.  chi2: one partial per workgroup, lanes -> waves in a fixed order; the total of the partials, summed by one
+// workgroup in a fixed order, is ADDED to *chi_target by one thread (k_side_total, or the pass itself when it is one workgroup).
 #include "gs_prior.hpp"
-
-#include <algorithm>
+#include "gs_side_dev.hpp"
 
 namespace gs {
-
-static constexpr int PRIOR_LM_PART = 8;      // doubles per lm_part record (gs_kernels.hip)
-static constexpr double kPriorPi = 3.14159265358979323846;
-
-__device__ __forceinline__ double prior_normalize_theta(double th) {     // g2o normalize_theta, as in gs_kernels.hip
-#pragma clang fp contract(off)
-    if (th >= -kPriorPi && th < kPriorPi) return th;
-    const double m = floor(th / (2.0 * kPriorPi));
-    th = th - m * 2.0 * kPriorPi;
-    if (th >= kPriorPi) th -= 2.0 * kPriorPi;
-    if (th < -kPriorPi) th += 2.0 * kPriorPi;
-    return th;
-}
 
 // one pose-prior record (plane stride S, record r) at the estimate x: adds to H (xx xy xt yy yt tt) and b, returns e^T Omega e
 template <bool APPLY>
@@ -47,7 +27,7 @@ __device__ __forceinline__ double prior_pose_record(const double *__restrict__ r
     for (int k = 0; k < PRIOR_POSE_REC; ++k) v[k] = rec[(int64_t)k * S + r];
     const double cz = v[3], sz = v[4];
     const double e0 = v[0] + (cz * x[0] - sz * x[1]), e1 = v[1] + (sz * x[0] + cz * x[1]);
-    const double e2 = prior_normalize_theta(v[2] + prior_normalize_theta(x[2]));
+    const double e2 = side_normalize_theta(v[2] + side_normalize_theta(x[2]));
     const double w00 = v[5], w01 = v[6], w02 = v[7], w11 = v[8], w12 = v[9], w22 = v[10];
     const double We0 = w00 * e0 + w01 * e1 + w02 * e2, We1 = w01 * e0 + w11 * e1 + w12 * e2, We2 = w02 * e0 + w12 * e1 + w22 * e2;
     if (APPLY) {
@@ -72,15 +52,6 @@ __device__ __forceinline__ double prior_lm_record(const double *__restrict__ rec
     return e0 * We0 + e1 * We1;
 }
 
-// fixed-order sum over the 256 threads, the result in thread 0 (red: 4 doubles of LDS)
-__device__ __forceinline__ double prior_block_sum(double v, double *red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 template <bool APPLY>
 __global__ void __launch_bounds__(256) k_prior_pass(DevGraph d, PriorDev pd, double *__restrict__ chi_target) {
     __shared__ double red[4];
@@ -93,45 +64,28 @@ __global__ void __launch_bounds__(256) k_prior_pass(DevGraph d, PriorDev pd, dou
 #pragma unroll
             for (int c = 0; c < 3; ++c) x[c] = d.pose_est[3 * (int64_t)p + c];
             for (int r = pd.pv_start[v]; r < pd.pv_start[v + 1]; ++r) chi += prior_pose_record<APPLY>(pd.pr, pd.n_pr, r, x, H, b);
-            if (APPLY) {
-                double *Hd = p < d.N ? d.Hpp_diag + p : d.t_Hpp_diag + (p - d.N), *bd = p < d.N ? d.b_pose + p : d.t_b_pose + (p - d.N);
-                const int64_t St = p < d.N ? d.N : d.tcapN;
-#pragma unroll
-                for (int c = 0; c < 6; ++c) Hd[c * St] += H[c];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) bd[c * St] += b[c]; } }
+            if (APPLY) side_add_pose(d, p, H, b); }
     } else if (v < pd.n_pv + pd.n_lv) {
         const int j = v - pd.n_pv, l = pd.lv_id[j];
         if (l >= 0 && l < d.M + d.tM) {
             double x[2] = {d.lm_est[2 * (int64_t)l], d.lm_est[2 * (int64_t)l + 1]}, H[3] = {0, 0, 0}, b[2] = {0, 0};
             for (int r = pd.lv_start[j]; r < pd.lv_start[j + 1]; ++r) chi += prior_lm_record<APPLY>(pd.lr, pd.n_lr, r, x, H, b);
-            if (APPLY) {
-                if (l >= d.M) { const int o = l - d.M; const int64_t St = d.tcapM;
-                    d.t_Hll_diag[o] += H[0]; d.t_Hll_diag[St + o] += H[1]; d.t_Hll_diag[2 * St + o] += H[2]; d.t_b_lm[o] += b[0]; d.t_b_lm[St + o] += b[1]; }
-                // (fused path: a landmark without a partial-sum slot has no observation edge in the layout; the host refuses a prior on it
-                // before anything is uploaded, and the guard keeps the store in bounds whatever the tables say — k_lm_damp has the same one)
-                else if (d.n_wtiles > 0) { const int q = d.lm_grp_start[l];
-                    if (q < d.lm_grp_start[l + 1]) { double *s = d.lm_part + (int64_t)q * PRIOR_LM_PART;
-                        s[0] += H[0]; s[1] += H[1]; s[2] += H[2]; s[3] += b[0]; s[4] += b[1]; } }
-                else { const int64_t St = d.M;
-                    d.Hll_diag[l] += H[0]; d.Hll_diag[St + l] += H[1]; d.Hll_diag[2 * St + l] += H[2]; d.b_lm[l] += b[0]; d.b_lm[St + l] += b[1]; } } }
+            if (APPLY) side_add_lm(d, l, H, b); }
     }
-    const double tot = prior_block_sum(chi, red);
-    if (threadIdx.x == 0) {
-        // (+=: the slot holds this pass's total or one of its partials, written EARLIER ON THIS STREAM by the linearisation / chi2 launches,
-        // or zeroed by enqueue_linearize when no wave tile is swept; the pass must stay behind them)
-        if (gridDim.x == 1) *chi_target += tot;                         // the whole pass is this workgroup: no second launch
-        else pd.part[blockIdx.x] = tot; }
+    side_chi2_finish(chi, red, pd.part, chi_target);
 }
 // the workgroups' partials by ONE workgroup in a fixed order, as k_reduce_chi2 sums the linearisation's: thread t takes partials t, t + 256, ...
 // in index order, then lanes -> waves; thread 0 writes.  (One thread walking all of them is a chain of dependent adds: 391 at cfg4 with a
 // prior on every pose.)
-__global__ void __launch_bounds__(256) k_prior_total(PriorDev pd, int n_part, double *__restrict__ chi_target) {
+__global__ void __launch_bounds__(256) k_side_total(const double *__restrict__ part, int n_part, double *__restrict__ chi_target) {
     __shared__ double red[4];
     double s = 0.0;
-    for (int k = threadIdx.x; k < n_part; k += 256) s += pd.part[k];
-    const double tot = prior_block_sum(s, red);
+    for (int k = threadIdx.x; k < n_part; k += 256) s += part[k];
+    const double tot = side_block_sum(s, red);
     if (threadIdx.x == 0) *chi_target += tot;
+}
+void launch_side_total(const double *part, int n_part, double *chi_target, hipStream_t st) {
+    hipLaunchKernelGGL(k_side_total, dim3(1), dim3(256), 0, st, part, n_part, chi_target);
 }
 
 // gs_get_prior_chi2: e^T Omega e per record, fixed vertices too (the same expressions as the pass)
@@ -153,7 +107,7 @@ void launch_prior_pass(const DevGraph &d, const PriorDev &pd, bool apply, double
     if (grid <= 0) return;
     if (apply) hipLaunchKernelGGL(k_prior_pass<true>, dim3(grid), dim3(256), 0, st, d, pd, chi_target);
     else hipLaunchKernelGGL(k_prior_pass<false>, dim3(grid), dim3(256), 0, st, d, pd, chi_target);
-    if (grid > 1) hipLaunchKernelGGL(k_prior_total, dim3(1), dim3(256), 0, st, pd, grid, chi_target);
+    if (grid > 1) launch_side_total(pd.part, grid, chi_target, st);
 }
 void launch_prior_chi2_each(const DevGraph &d, int kind, int n, const int32_t *vert, const double *rec, double *out, hipStream_t st) {
     if (n > 0) hipLaunchKernelGGL(k_prior_chi2_each, dim3((n + 255) / 256), dim3(256), 0, st, d, kind, n, vert, rec, out);

@@ -86,34 +86,24 @@ int prior_sync(gs_graph *g) {
     for (int32_t l : h.pl_l) ++lm_obs[(size_t)l];
     std::string err;
     if (!build_prior_tables(P.store, h.pose_fixed.data(), N, h.lm_fixed.data(), M, lm_obs.data(), P.tab, err)) return fail(GS_ERR_INVALID, "priors: " + err);
-    // fused linearisation: the landmark's block lives in its first partial-sum slot — it must have one
-    if (d.n_wtiles > 0) for (int32_t l : P.tab.lv_id)
-        if (l < d.M && !(g->plan.lm_grp_start[(size_t)l] < g->plan.lm_grp_start[(size_t)l + 1]))
-            return fail(GS_ERR_INVALID, "priors: a free landmark without an observation edge in the linearisation layout cannot carry a prior");
+    for (int32_t l : P.tab.lv_id) if (lm_lacks_fused_slot(g, l))
+        return fail(GS_ERR_INVALID, "priors: a free landmark without an observation edge in the linearisation layout cannot carry a prior");
     const PriorTables &T = P.tab;
     const size_t npv = T.pv_id.size(), nlv = T.lv_id.size();
     if (npv + nlv == 0) { P.sync.done(P.store.version, g->plan_version); P.settled = P.store.version; return GS_OK; }     // every prior sits on a fixed vertex
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t n_part = (npv + nlv + 255) / 256;
-    const size_t o_pv = 0, o_ps = o_pv + al(npv * 4), o_lv = o_ps + al((npv + 1) * 4), o_ls = o_lv + al(nlv * 4), o_pr = o_ls + al((nlv + 1) * 4),
-                 o_lr = o_pr + al(T.pr.size() * 8), o_part = o_lr + al(T.lr.size() * 8), total = o_part + al(n_part * 8);
-    if (!P.mem || total > P.cap) {
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        if (P.mem) { hipFree(P.mem); P.mem = nullptr; P.cap = 0; }
-        const size_t cap = total + total / 2 + 4096;
-        HIP_TRY(hipMalloc(&P.mem, cap));
-        P.cap = cap; }
-    char *b = (char *)P.mem;
-    auto up = [&](size_t off, const void *src, size_t bytes) -> hipError_t {
-        return bytes ? hipMemcpyAsync(b + off, src, bytes, hipMemcpyHostToDevice, g->stream) : hipSuccess; };
-    HIP_TRY(up(o_pv, T.pv_id.data(), npv * 4)); HIP_TRY(up(o_ps, T.pv_start.data(), (npv + 1) * 4));
-    HIP_TRY(up(o_lv, T.lv_id.data(), nlv * 4)); HIP_TRY(up(o_ls, T.lv_start.data(), (nlv + 1) * 4));
-    HIP_TRY(up(o_pr, T.pr.data(), T.pr.size() * 8)); HIP_TRY(up(o_lr, T.lr.data(), T.lr.size() * 8));
+    ArenaLayout lay;
+    const size_t o_pv = lay.add(npv * 4), o_ps = lay.add((npv + 1) * 4), o_lv = lay.add(nlv * 4), o_ls = lay.add((nlv + 1) * 4),
+                 o_pr = lay.add(T.pr.size() * 8), o_lr = lay.add(T.lr.size() * 8), o_part = lay.add((npv + nlv + 255) / 256 * 8);
+    int rc = arena_reserve(g, P.arena, lay.total); if (rc != GS_OK) return rc;
+    const DevArena &A = P.arena;
+    HIP_TRY(arena_upload(g, A, o_pv, T.pv_id.data(), npv * 4)); HIP_TRY(arena_upload(g, A, o_ps, T.pv_start.data(), (npv + 1) * 4));
+    HIP_TRY(arena_upload(g, A, o_lv, T.lv_id.data(), nlv * 4)); HIP_TRY(arena_upload(g, A, o_ls, T.lv_start.data(), (nlv + 1) * 4));
+    HIP_TRY(arena_upload(g, A, o_pr, T.pr.data(), T.pr.size() * 8)); HIP_TRY(arena_upload(g, A, o_lr, T.lr.data(), T.lr.size() * 8));
     HIP_TRY(hipStreamSynchronize(g->stream));                        // (the tables are rebuilt in place by the next change)
     PriorDev D;
     D.n_pv = (int32_t)npv; D.n_lv = (int32_t)nlv; D.n_pr = T.n_pr; D.n_lr = T.n_lr;
-    D.pv_id = (const int32_t *)(b + o_pv); D.pv_start = (const int32_t *)(b + o_ps); D.lv_id = (const int32_t *)(b + o_lv); D.lv_start = (const int32_t *)(b + o_ls);
-    D.pr = (const double *)(b + o_pr); D.lr = (const double *)(b + o_lr); D.part = (double *)(b + o_part);
+    D.pv_id = (const int32_t *)A.at(o_pv); D.pv_start = (const int32_t *)A.at(o_ps); D.lv_id = (const int32_t *)A.at(o_lv); D.lv_start = (const int32_t *)A.at(o_ls);
+    D.pr = (const double *)A.at(o_pr); D.lr = (const double *)A.at(o_lr); D.part = (double *)A.at(o_part);
     P.dev = D;
     P.sync.done(P.store.version, g->plan_version); P.settled = P.store.version;     // (only now: a refused upload stays "pending" for gs_initialize_optimization)
     return GS_OK;
@@ -134,17 +124,14 @@ extern "C" int gs_get_prior_chi2(gs_graph *g, int32_t kind, int32_t capacity, do
     const std::vector<int32_t> &vert = kind == 0 ? S.pose_v : S.lm_v; const std::vector<double> &rec = kind == 0 ? S.pose_rec : S.lm_rec;
     std::vector<double> planes((size_t)per * n);
     for (int k = 0; k < n; ++k) for (int c = 0; c < per; ++c) planes[(size_t)c * n + k] = rec[(size_t)k * per + c];
-    int32_t *dv = nullptr; double *dr = nullptr, *dout = nullptr;
-    HIP_TRY(hipMalloc((void **)&dv, (size_t)n * sizeof(int32_t)));
-    if (hipMalloc((void **)&dr, planes.size() * sizeof(double)) != hipSuccess) { hipFree(dv); return fail(GS_ERR_HIP, "hipMalloc failed"); }
-    if (hipMalloc((void **)&dout, (size_t)n * sizeof(double)) != hipSuccess) { hipFree(dv); hipFree(dr); return fail(GS_ERR_HIP, "hipMalloc failed"); }
+    ArenaLayout lay; const size_t o_v = lay.add((size_t)n * sizeof(int32_t)), o_r = lay.add(planes.size() * sizeof(double)), o_out = lay.add((size_t)n * sizeof(double));
+    DevScratch s; HIP_TRY(s.alloc(lay.total));
     std::vector<double> out((size_t)n);
-    hipError_t e = hipMemcpyAsync(dv, vert.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dr, planes.data(), planes.size() * sizeof(double), hipMemcpyHostToDevice, g->stream);
-    if (e == hipSuccess) { launch_prior_chi2_each(g->d, kind, n, dv, dr, dout, g->stream); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpyAsync(out.data(), dout, out.size() * sizeof(double), hipMemcpyDeviceToHost, g->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream); else hipStreamSynchronize(g->stream);
-    hipFree(dv); hipFree(dr); hipFree(dout);
+    hipError_t e = hipMemcpyAsync(s.p + o_v, vert.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, g->stream);
+    HIP_NEXT(e, hipMemcpyAsync(s.p + o_r, planes.data(), planes.size() * sizeof(double), hipMemcpyHostToDevice, g->stream));
+    if (e == hipSuccess) { launch_prior_chi2_each(g->d, kind, n, (const int32_t *)(s.p + o_v), (const double *)(s.p + o_r), (double *)(s.p + o_out), g->stream); e = hipGetLastError(); }
+    HIP_NEXT(e, hipMemcpyAsync(out.data(), s.p + o_out, out.size() * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    e = sync_keep_first(e, g->stream);
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("prior chi2: ") + hipGetErrorString(e));
     std::memcpy(out_chi2, out.data(), (size_t)n * sizeof(double));
     return n;

@@ -12,10 +12,9 @@
 // vertex, insertion order within a vertex.  A prior on a fixed vertex stays out of the tables (g2o: an edge whose vertices are all
 // fixed is inactive); gs_get_prior_chi2 reads the store.
 #pragma once
-#include <cmath>
-#include <cstdint>
 #include <string>
-#include <vector>
+
+#include "gs_side_host.hpp"
 
 namespace gs {
 
@@ -31,9 +30,7 @@ struct PriorStore {                                  // insertion order, vertex 
     void clear() { if (!empty()) ++version; pose_v.clear(); lm_v.clear(); pose_rec.clear(); lm_rec.clear(); }
     // z = (x, y, theta), w = the six distinct entries of Omega (xx xy xt yy yt tt)
     void add_pose(int32_t v, const double z[3], const double w[6]) {
-        auto norm = [](double th) { if (th >= -M_PI && th < M_PI) return th; const double m = std::floor(th / (2 * M_PI)); th -= m * 2 * M_PI;
-                                    if (th >= M_PI) th -= 2 * M_PI; if (th < -M_PI) th += 2 * M_PI; return th; };
-        const double th = norm(-z[2]), c = std::cos(th), s = std::sin(th);
+        const double th = normalize_theta(-z[2]), c = std::cos(th), s = std::sin(th);
         const double r[PRIOR_POSE_REC] = {c * (-z[0]) - s * (-z[1]), s * (-z[0]) + c * (-z[1]), th, c, s, w[0], w[1], w[2], w[3], w[4], w[5]};
         pose_v.push_back(v); pose_rec.insert(pose_rec.end(), r, r + PRIOR_POSE_REC); ++version;
     }
@@ -50,24 +47,20 @@ struct PriorTables {
     int n_vertices() const { return (int)(pv_id.size() + lv_id.size()); }
 };
 
-// one kind: the priors of free vertices v < n_vertex, counting sort by vertex (stable: insertion order within a vertex)
+// one kind: the priors of free vertices v < n_vertex grouped by vertex (group_by_key: insertion order within a vertex)
 inline bool prior_group(const std::vector<int32_t> &vert, const std::vector<double> &rec, int per, const uint8_t *fixed, int n_vertex,
                         std::vector<int32_t> &ids, std::vector<int32_t> &start, std::vector<double> &planes, int32_t &n_rec, std::string &err) {
     ids.clear(); start.clear(); planes.clear(); n_rec = 0;
-    std::vector<int32_t> count((size_t)n_vertex + 1, 0);
+    std::vector<uint8_t> skip(vert.size());
     for (size_t k = 0; k < vert.size(); ++k) {
         const int32_t v = vert[k];
         if (v < 0 || v >= n_vertex) { err = "prior on a vertex that is not in the graph"; return false; }
-        if (!fixed[v]) { ++count[(size_t)v]; ++n_rec; } }
-    std::vector<int32_t> slot((size_t)n_vertex, -1);              // vertex -> next free record of its run
-    int32_t at = 0;
-    for (int v = 0; v < n_vertex; ++v) if (count[(size_t)v] > 0) { ids.push_back(v); start.push_back(at); slot[(size_t)v] = at; at += count[(size_t)v]; }
-    start.push_back(at);
+        skip[k] = fixed[v]; }
+    std::vector<int32_t> order;
+    group_by_key(vert, n_vertex, skip.data(), ids, start, order);
+    n_rec = (int32_t)order.size();
     planes.resize((size_t)per * (size_t)n_rec);
-    for (size_t k = 0; k < vert.size(); ++k) { const int32_t v = vert[k];
-        if (fixed[v]) continue;
-        const int32_t r = slot[(size_t)v]++;
-        for (int c = 0; c < per; ++c) planes[(size_t)c * (size_t)n_rec + (size_t)r] = rec[k * (size_t)per + (size_t)c]; }
+    for (size_t r = 0; r < order.size(); ++r) for (int c = 0; c < per; ++c) planes[(size_t)c * (size_t)n_rec + r] = rec[(size_t)order[r] * (size_t)per + (size_t)c];
     return true;
 }
 
@@ -83,11 +76,6 @@ inline bool build_prior_tables(const PriorStore &S, const uint8_t *pose_fixed, i
 
 // What the device holds against what the handle holds: the tables go up again (whole: they are small) when the priors changed or
 // when another plan came (fixed flags, vertex counts and the tail may differ)
-struct PriorSync {
-    uint64_t store_version = ~0ull, plan_version = ~0ull; bool valid = false;
-    bool needed(uint64_t store_now, uint64_t plan_now) const { return !valid || store_version != store_now || plan_version != plan_now; }
-    void done(uint64_t store_now, uint64_t plan_now) { store_version = store_now; plan_version = plan_now; valid = true; }
-    void invalidate() { valid = false; }
-};
+using PriorSync = SyncStamp<2>;                     // the store's version, the plan's version
 
 }  // namespace gs

@@ -47,7 +47,37 @@ template <class T> int dev_alloc(gs_graph *g, T **ptr, size_t count) {
     return GS_OK;
 }
 
+// Query calls (per-edge / per-prior values): "first error wins" over a chain of HIP calls — a call behind a failed one is not made —
+// and one device scratch per call, laid out by an ArenaLayout and freed on every exit
+#define HIP_NEXT(e, expr) do { if ((e) == hipSuccess) (e) = (expr); } while (0)
+static inline hipError_t sync_keep_first(hipError_t e, hipStream_t st) { const hipError_t s = hipStreamSynchronize(st); return e != hipSuccess ? e : s; }   // (waits either way: the scratch is freed behind it)
+struct DevScratch {
+    char *p = nullptr;
+    DevScratch() = default;
+    DevScratch(const DevScratch &) = delete;
+    DevScratch &operator=(const DevScratch &) = delete;
+    ~DevScratch() { if (p) hipFree(p); }
+    hipError_t alloc(size_t bytes) { const hipError_t e = hipMalloc((void **)&p, bytes); if (e != hipSuccess) p = nullptr; return e; }
+};
+
 // gs_api.cpp
+// the handle's grow-only arenas (gs::DevArena): room for `total` bytes — a larger allocation (total + total / 2 + 4096) behind a wait for
+// the stream when the present one is too small, which then holds nothing; on failure the arena is empty —, a block to offset `off` on
+// the handle's stream, and the release
+int arena_reserve(gs_graph *g, gs::DevArena &a, size_t total);
+hipError_t arena_upload(gs_graph *g, const gs::DevArena &a, size_t off, const void *src, size_t bytes);
+void arena_release(gs::DevArena &a);
+// the three side passes (priors, edge flags, polar edges) together: their device copies brought up to date, in this order, with the plan
+// of the CURRENT graph on the device (ensure_ready, gs_iterate); the handle's stores emptied (gs_clear); the arenas freed (gs_destroy)
+int side_sync(gs_graph *g);
+void side_clear(gs_graph *g);
+void side_release(gs_graph *g);
+// where observation edge k lives on the device: its ELL index, or -(tail slot) - 1 (the table format of launch_edge_chi2); the refusals
+// start with `prefix`
+int pl_location(const gs_graph *g, int32_t k, int32_t &src, const char *prefix);
+// fused linearisation: the block of a free landmark of the layout lives in its first partial-sum slot — true when landmark l has none
+// (no observation edge in the linearisation layout), i.e. there is no address a side pass could add its block to
+bool lm_lacks_fused_slot(const gs_graph *g, int32_t l);
 bool sym_ok(const double *m, int n);           // the information-matrix check of every gs_add_*_edge / gs_add_*_prior
 int ensure_device(gs_graph *g);
 int ensure_ready(gs_graph *g);                 // the structure phase if the graph changed, host-side estimates to the device
@@ -56,12 +86,12 @@ int pull_estimates_enqueue(gs_graph *g, bool &pull);        // the copies only: 
 int reset_failure(gs_graph *g);
 void fill_plan_stats(gs_graph *g, gs_stats *s);
 // gs_prior_api.cpp
-int prior_sync(gs_graph *g);                   // the prior tables to the device when the priors or the plan changed (ensure_ready, gs_iterate); nothing without priors
+int prior_sync(gs_graph *g);                   // the prior tables to the device when the priors or the plan changed (side_sync); nothing without priors
 // gs_edge_mask_api.cpp
-int edge_mask_sync(gs_graph *g);               // the information of the edges whose flag changed (or that an upload rewrote) on the device; called where prior_sync is; nothing on a handle that never had an inactive edge
+int edge_mask_sync(gs_graph *g);               // the information of the edges whose flag changed (or that an upload rewrote) on the device (side_sync); nothing on a handle that never had an inactive edge
 int edge_mask_edge_chi2(gs_graph *g, int32_t kind, int32_t n, const std::vector<int32_t> &tab, double *out_chi2, double *out_weight);   // gs_get_edge_chi2 on a handle with inactive edges: s with the edges' own information
 // gs_polar_api.cpp
-int polar_sync(gs_graph *g);                   // the polar edges' tables to the device when they, the plan, the edge flags or the edge values changed; called where prior_sync is; nothing without polar edges
+int polar_sync(gs_graph *g);                   // the polar edges' tables to the device when they, the plan, the edge flags or the edge values changed (side_sync); nothing without polar edges
 int polar_edge_chi2_overwrite(gs_graph *g, int32_t n, double *dev_out);   // gs_get_edge_chi2 (observation kind): s and weight of the polar edges over the per-edge kernel's device output [2][n]; nothing without polar edges
 // gs_solve.cpp
 // every linearisation of H and every chi2 pass goes through these two, so that no site can leave the priors out

@@ -75,9 +75,7 @@ extern "C" int gs_iterate(gs_graph *g) {
     if (!g->dev_valid || g->plan_version != g->h.structure_version) return fail(GS_ERR_NOT_INITIALIZED, "call gs_initialize_optimization first");
     if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: use gs_dist_iterate (RCCL inside the library) or gs_dist_iterate_local / all-reduce / gs_dist_iterate_finish");
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if ((rc = prior_sync(g)) != GS_OK) return rc;
-    if ((rc = edge_mask_sync(g)) != GS_OK) return rc;
-    if ((rc = polar_sync(g)) != GS_OK) return rc;
+    if ((rc = side_sync(g)) != GS_OK) return rc;
     enqueue_iteration(g, false);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
@@ -404,7 +402,7 @@ extern "C" int gs_get_edge_chi2(gs_graph *g, int32_t edge_kind, int32_t capacity
     if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: per-edge chi2 is not supported on sharded handles");
     rc = ensure_ready(g); if (rc != GS_OK) return rc;
     if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: per-edge chi2 is not supported on sharded handles");
-    const HostGraph &h = g->h; const Plan &P = g->plan;
+    const HostGraph &h = g->h;
     const bool pp = edge_kind == GS_EDGE_ODOMETRY;
     const int n = pp ? h.n_pp() : h.n_pl();
     if ((out_chi2 || out_weight) && capacity < n) return fail(GS_ERR_CAPACITY, "buffer too small");
@@ -413,22 +411,19 @@ extern "C" int gs_get_edge_chi2(gs_graph *g, int32_t edge_kind, int32_t capacity
     std::vector<int32_t> tab((size_t)n * per);
     if (pp) for (int k = 0; k < n; ++k) { tab[2 * (size_t)k] = h.pp_i[k]; tab[2 * (size_t)k + 1] = h.pp_j[k]; }
     else for (int k = 0; k < n; ++k) {
-        int32_t src;
-        if (k < P.base_Epl) { src = P.ell_of_ins[k]; if (src < 0) return fail(GS_ERR_INVALID, "observation edge outside the linearisation layout"); }
-        else { if (k - P.base_Epl >= g->d.tEpl) return fail(GS_ERR_INVALID, "observation edge not on the device"); src = -(k - P.base_Epl) - 1; }
+        int32_t src; rc = pl_location(g, k, src, ""); if (rc != GS_OK) return rc;
         tab[3 * (size_t)k] = h.pl_p[k]; tab[3 * (size_t)k + 1] = h.pl_l[k]; tab[3 * (size_t)k + 2] = src; }
     if (pp && n > g->d.Epp + g->d.tEpp) return fail(GS_ERR_INVALID, "odometry edge not on the device");
     if (g->emask.store.any_off()) return edge_mask_edge_chi2(g, edge_kind, n, tab, out_chi2, out_weight);     // the device arrays hold zeros for the inactive edges: s from the edges' own information
-    int32_t *dtab = nullptr; double *dout = nullptr;
-    HIP_TRY(hipMalloc((void **)&dtab, tab.size() * sizeof(int32_t)));
-    if (hipMalloc((void **)&dout, (size_t)n * 2 * sizeof(double)) != hipSuccess) { hipFree(dtab); return fail(GS_ERR_HIP, "hipMalloc failed"); }
+    ArenaLayout lay; const size_t o_out = lay.add((size_t)n * 2 * sizeof(double)), o_tab = lay.add(tab.size() * sizeof(int32_t));
+    DevScratch s; HIP_TRY(s.alloc(lay.total));
+    int32_t *dtab = (int32_t *)(s.p + o_tab); double *dout = (double *)(s.p + o_out);
     std::vector<double> out((size_t)n * 2);
     hipError_t e = hipMemcpyAsync(dtab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, g->stream);
     if (e == hipSuccess) { launch_edge_chi2(g->d, edge_kind, n, dtab, dout, g->stream); e = hipGetLastError(); }
-    if (e == hipSuccess && !pp && polar_edge_chi2_overwrite(g, n, dout) != GS_OK) { hipStreamSynchronize(g->stream); hipFree(dtab); hipFree(dout); return GS_ERR_HIP; }   // (nothing without polar edges)
-    if (e == hipSuccess) e = hipMemcpyAsync(out.data(), dout, out.size() * sizeof(double), hipMemcpyDeviceToHost, g->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(g->stream); else hipStreamSynchronize(g->stream);
-    hipFree(dtab); hipFree(dout);
+    if (e == hipSuccess && !pp && polar_edge_chi2_overwrite(g, n, dout) != GS_OK) { hipStreamSynchronize(g->stream); return GS_ERR_HIP; }   // (nothing without polar edges)
+    HIP_NEXT(e, hipMemcpyAsync(out.data(), dout, out.size() * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    e = sync_keep_first(e, g->stream);
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("edge chi2: ") + hipGetErrorString(e));
     if (out_chi2) std::memcpy(out_chi2, out.data(), (size_t)n * sizeof(double));
     if (out_weight) std::memcpy(out_weight, out.data() + n, (size_t)n * sizeof(double));

@@ -1,5 +1,6 @@
 // prior_tables_san.cpp — stand-alone check of the host side of the prior edges (csrc/gs_prior_host.hpp: the store, the grouping by
-// vertex, the structure-of-arrays packing, the refusals and the "does the device copy need to go up again" rule), with its own main().
+// vertex, the structure-of-arrays packing, the refusals and the "does the device copy need to go up again" rule) and of what the three side
+// passes share (csrc/gs_side_host.hpp: the grouping, the stamp record, the arena layout), with its own main().
 // Built and run on the host with the sanitizers, no HIP and no GPU:
 //   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined tests/prior_tables_san.cpp -o prior_tables_san && ./prior_tables_san
 #include "../opendlv-logic-cfsd18-sensation-slam_amd/csrc/gs_prior_host.hpp"
@@ -85,6 +86,47 @@ int main() {
         Y.done(S.version, 7); CHECK(!Y.needed(S.version, 7) && Y.needed(S.version, 8));     // another plan (a growth step, a structure phase)
         S.clear(); CHECK(Y.needed(S.version, 7));
         Y.done(S.version, 7); Y.invalidate(); CHECK(Y.needed(S.version, 7));
+    }
+    {   // the shared grouping (csrc/gs_side_host.hpp): no item, one key, every item skipped, a skip in the middle of a run
+        std::vector<int32_t> ids, start, order;
+        group_by_key({}, 0, nullptr, ids, start, order);
+        CHECK(ids.empty() && order.empty() && start.size() == 1 && start[0] == 0);
+        group_by_key({}, 5, nullptr, ids, start, order);
+        CHECK(ids.empty() && order.empty() && start.size() == 1 && start[0] == 0);
+        const std::vector<int32_t> one(4, 2);
+        group_by_key(one, 3, nullptr, ids, start, order);
+        CHECK(ids.size() == 1 && ids[0] == 2 && start.size() == 2 && start[0] == 0 && start[1] == 4 && order.size() == 4);
+        for (int k = 0; k < 4; ++k) CHECK(order[(size_t)k] == k);                       // insertion order inside the run
+        const std::vector<uint8_t> all(4, 1);
+        group_by_key(one, 3, all.data(), ids, start, order);
+        CHECK(ids.empty() && order.empty() && start.size() == 1 && start[0] == 0);
+        const std::vector<int32_t> key = {3, 0, 3, 1, 0, 3}; const std::vector<uint8_t> skip = {0, 0, 1, 0, 0, 0};
+        group_by_key(key, 4, skip.data(), ids, start, order);
+        CHECK(ids == std::vector<int32_t>({0, 1, 3}) && start == std::vector<int32_t>({0, 2, 3, 5}) && order == std::vector<int32_t>({1, 4, 3, 0, 5}));
+    }
+    {   // the shared stamp: never done, done, each counter on its own, invalidated, done again
+        SyncStamp<3> Y;
+        CHECK(Y.needed(0, 0, 0) && Y.needed(~0ull, ~0ull, ~0ull));                   // (nothing uploaded yet, whatever the counters say)
+        Y.done(1, 2, 3);
+        CHECK(!Y.needed(1, 2, 3) && Y.needed(0, 2, 3) && Y.needed(1, 0, 3) && Y.needed(1, 2, 0));
+        Y.invalidate(); CHECK(Y.needed(1, 2, 3));
+        Y.done(1, 2, 4); CHECK(!Y.needed(1, 2, 4) && Y.needed(1, 2, 3));
+        SyncStamp<1> Z; CHECK(Z.needed(5)); Z.done(5); CHECK(!Z.needed(5) && Z.needed(6));
+    }
+    {   // the shared arena layout: aligned, increasing, non-overlapping; a block of zero bytes is legal and takes no room
+        ArenaLayout lay;
+        CHECK(lay.total == 0);
+        const size_t bytes[8] = {1, 255, 256, 257, 0, 4, 0, 100000};
+        size_t off[8], end = 0;
+        for (int k = 0; k < 8; ++k) {
+            off[k] = lay.add(bytes[k]);
+            CHECK(off[k] % 256 == 0 && off[k] >= end && lay.total % 256 == 0 && lay.total >= off[k] + bytes[k]);
+            CHECK(k == 0 || off[k] >= off[k - 1]);
+            if (k > 0 && bytes[k - 1] > 0) CHECK(off[k] > off[k - 1]);
+            end = off[k] + bytes[k]; }
+        CHECK(off[0] == 0 && off[1] == 256 && off[2] == 512 && off[3] == 768 && off[4] == 1280 && off[5] == 1280 && off[6] == 1536 && off[7] == 1536);
+        CHECK(lay.total == 1536 + 100096);
+        ArenaLayout none; CHECK(none.add(0) == 0 && none.total == 0);
     }
     std::puts("prior tables: ok");
     return 0;

@@ -341,3 +341,44 @@ def test_sharded_handles_are_refused(pkg, bench_graphs):
         assert e.value.code == -1 and "shard" in str(e.value)
     assert G.n_pl == n and G.num_polar_edges() == 0
     G.close()
+
+
+# ---------------------------------------------------------------- the chi2 finish at the one / two workgroup boundary
+@pytest.mark.parametrize("gather", [0, 1])
+def test_chi2_finish_at_the_workgroup_boundary(pkg, bench_graphs, gather):
+    """One range-bearing edge each on 255, 256 and 257 free poses of a 300-pose / 40-cone graph, to a cone the pose has no edge to: the
+    pose side is one workgroup of 255 and of 256 listed poses (its total added by the pass itself) and two workgroups at 257 (partials,
+    then the totalling kernel).  The pairs beyond the count are added as what a carrier is — a Cartesian edge with zero information —, so
+    the three handles have one structure.  The handle's chi2 minus the graph's own chi2 is the sum of the per-edge values (1e-9 of
+    chi2, the bar of test_chi2_and_per_prior_chi2), and the exported diagonal blocks and right-hand sides of the first 255 carrying
+    poses do not depend on the count, bit for bit."""
+    g = bench_graphs(300, 40)[1]
+    rng = np.random.default_rng(257)
+    P = np.asarray(g["pose_est"], dtype=np.float64).reshape(-1, 3); L = np.asarray(g["lm_est"], dtype=np.float64).reshape(-1, 2)
+    pl_p, pl_l = np.asarray(g["pl_p"], dtype=np.int64), np.asarray(g["pl_l"], dtype=np.int64)
+    free = np.setdiff1d(np.arange(len(P)), np.asarray(g["fixed_poses"], dtype=np.int64))[:257]
+    free_l = np.setdiff1d(np.arange(len(L)), np.asarray(g["fixed_landmarks"], dtype=np.int64))
+    cone = np.array([np.setdiff1d(free_l, pl_l[pl_p == p])[0] for p in free])           # (the lowest index among the free cones p does not observe)
+    assert len(free) == 257
+    d = L[cone] - P[free, :2]; th = P[free, 2]
+    dx, dy = np.cos(th) * d[:, 0] + np.sin(th) * d[:, 1], np.cos(th) * d[:, 1] - np.sin(th) * d[:, 0]
+    z = np.stack([np.hypot(dx, dy), np.arctan2(dy, dx)], 1) + rng.normal(0, 0.05, (257, 2))
+    assert np.all(z[:, 0] > 0)
+    W = np.stack([pr.spd(rng, 2, 0.3) for _ in range(257)])
+    G0 = pkg.Graph(device=0, linearize_gather=gather); G0.load_bench_graph(g); chi0 = G0.chi2(); G0.close()
+    blocks = {}
+    for count in (255, 256, 257):
+        G = pkg.Graph(device=0, linearize_gather=gather); G.load_bench_graph(g)
+        G.add_range_bearing_edges(free[:count], cone[:count], z[:count], W[:count].reshape(-1, 4))
+        if count < 257:
+            G.add_observation_edges(free[count:], cone[count:], np.zeros((257 - count, 2)), np.zeros((257 - count, 4)))
+        chi = G.chi2(); s, w = G.edge_chi2("observation"); idx, _ = G.polar_edges()
+        G.linearize(); S = G.export_system()
+        blocks[count] = (S["Hpp_diag"][free[:255]].copy(), S["b_pose"][free[:255]].copy())
+        print("gather=%d %d polar edges: chi2 %.10g without %.10g difference %.10g sum of the per-edge values %.10g (rel %.2e)"
+              % (gather, count, chi, chi0, chi - chi0, s[idx].sum(), abs((chi - chi0) - s[idx].sum()) / chi))
+        assert len(idx) == count and np.all(s[idx] > 0) and np.all(w == 1.0) and np.all(s[len(pl_p) + count:] == 0.0)
+        assert abs((chi - chi0) - s[idx].sum()) <= 1e-9 * chi
+        G.close()
+    for count in (256, 257):
+        assert np.array_equal(blocks[count][0], blocks[255][0]) and np.array_equal(blocks[count][1], blocks[255][1]), count

@@ -439,3 +439,34 @@ def test_estimates_set_with_a_prior_reach_the_device_before_iterate(pkg, po, ben
             G.initialize_optimization()
         assert e.value.code == -1 and "prior" in str(e.value)
     G.close(); F.close()
+
+
+# ---------------------------------------------------------------- the chi2 finish at the one / two workgroup boundary
+@pytest.mark.parametrize("gather", [0, 1])
+def test_chi2_finish_at_the_workgroup_boundary(pkg, bench_graphs, gather):
+    """One XY prior each on the first 255, 256 and 257 free poses of a 300-pose / 40-cone graph: the pass is one workgroup of 255 and of
+    256 threads (its total added by the pass itself) and two workgroups at 257 (partials, then the totalling kernel).  The handle's chi2
+    minus the chi2 of the same handle without priors is the sum of the per-prior values (1e-9 of chi2, the bar of
+    test_chi2_and_per_prior_chi2), and the exported diagonal blocks and right-hand sides of the first 255 carrying poses do not depend
+    on the count, bit for bit."""
+    g = bench_graphs(300, 40)[1]
+    rng = np.random.default_rng(256)
+    P = np.asarray(g["pose_est"], dtype=np.float64).reshape(-1, 3)
+    free = np.setdiff1d(np.arange(len(P)), np.asarray(g["fixed_poses"], dtype=np.int64))[:257]
+    assert len(free) == 257
+    z = P[free, :2] + rng.normal(0, 0.2, (257, 2)); W = np.stack([pr.spd(rng, 2, 0.3) for _ in range(257)])
+    blocks = {}
+    for count in (255, 256, 257):
+        G = fresh(pkg, g, linearize_gather=gather)
+        G.add_pose_xy_priors(free[:count], z[:count], W[:count].reshape(-1, 4))
+        chi = G.chi2(); each = G.prior_chi2("pose")
+        G.linearize(); S = G.export_system()
+        blocks[count] = (S["Hpp_diag"][free[:255]].copy(), S["b_pose"][free[:255]].copy())
+        G.clear_priors(); chi0 = G.chi2()
+        print("gather=%d %d priors: chi2 %.10g without %.10g difference %.10g sum of the per-prior values %.10g (rel %.2e)"
+              % (gather, count, chi, chi0, chi - chi0, each.sum(), abs((chi - chi0) - each.sum()) / chi))
+        assert len(each) == count and np.all(each > 0)
+        assert abs((chi - chi0) - each.sum()) <= 1e-9 * chi
+        G.close()
+    for count in (256, 257):
+        assert np.array_equal(blocks[count][0], blocks[255][0]) and np.array_equal(blocks[count][1], blocks[255][1]), count
