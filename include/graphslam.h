@@ -485,7 +485,7 @@ int  gs_plan_build_host(gs_graph *g, gs_plan_info *info);
  * the last full phase; every front stays within its form (63 scalars, or 159 in a plan with workgroup fronts) — gs_initialize_optimization /
  * gs_optimize keep the plan: the new vertices become
  * pivots of the root front, the fronts between a neighbour's front and the root gain them as boundary rows, and only those fronts' tables
- * are rebuilt (csrc/gs_plan.cpp grow_plan, csrc/gs_api.cpp upload_growth).  Anything else (a fixed flag, an edge between old vertices,
+ * are rebuilt (csrc/gs_plan.cpp grow_plan, csrc/gs_upload.cpp upload_growth).  Anything else (a fixed flag, an edge between old vertices,
  * a graph below 128 poses, where there is nothing to gain; switches: gs_debug_options.grow / grow_min_poses, graphslam_debug.h) is a full structure phase.
  * gs_plan_growths: steps absorbed by the current plan; gs_growth_refusal: why the last change was NOT absorbed ("" if it was). */
 int  gs_plan_growths(gs_graph *g);

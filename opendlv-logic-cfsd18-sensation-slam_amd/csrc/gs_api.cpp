@@ -4,7 +4,7 @@
 #include "../../include/graphslam.h"
 #include "../../include/graphslam_debug.h"
 #include "gs_private.hpp"
-#include "gs_parallel.hpp"
+#include "gs_upload_host.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -13,7 +13,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include <thread>
 #include <vector>
 
 using namespace gs;
@@ -30,12 +29,6 @@ static int usable_devices() {
     return n;
 }
 
-template <class T, class A> static int dev_upload(gs_graph *g, T **ptr, const std::vector<T, A> &v) {
-    int rc = dev_alloc(g, ptr, v.size());
-    if (rc != GS_OK) return rc;
-    if (!v.empty()) HIP_TRY(hipMemcpyAsync(*ptr, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, g->stream));
-    return GS_OK;
-}
 // the handle's robust kernels (cfg.*_robust_*) travel to the kernels by value in DevGraph
 static void apply_robust(gs_graph *g) {
     g->d.rk_pp = g->cfg.odometry_robust_kernel; g->d.rd_pp = g->cfg.odometry_robust_delta;
@@ -167,7 +160,7 @@ extern "C" int gs_create(const gs_config *cfg, gs_graph **out) {
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(GS_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", kernels are built for gfx950 only");
     gs_graph *g = new gs_graph();
-    g->cfg = c; g->device = dev; g->force_gather = c.linearize_gather != 0; g->default_factor_variant = c.factor_variant;
+    g->cfg = c; g->device = dev; g->force_gather = c.linearize_gather != 0;
     apply_robust(g);
     options_from_environment(g->opt);
     HIP_TRY(hipSetDevice(dev));
@@ -463,453 +456,7 @@ extern "C" int gs_get_landmarks(gs_graph *g, int32_t cap, int32_t *ids, double *
     return g->h.n_lms();
 }
 
-// ------------------------------------------------------------------ structure phase (A3/A4) + upload
-static void se2_inverse_host(const double *a, double *out) {
-    auto norm = [](double th) { if (th >= -M_PI && th < M_PI) return th; double m = std::floor(th / (2 * M_PI)); th -= m * 2 * M_PI;
-                                if (th >= M_PI) th -= 2 * M_PI; if (th < -M_PI) th += 2 * M_PI; return th; };
-    double th = norm(-a[2]); double c = std::cos(th), s = std::sin(th);
-    out[0] = c * (-a[0]) - s * (-a[1]); out[1] = s * (-a[0]) + c * (-a[1]); out[2] = th;
-}
-
-// Everything that does not depend on the plan goes to HBM on a helper thread WHILE the host builds the plan: estimates,
-// fixed flags, odometry measurements (inverted, with their cos/sin: g2o keeps _inverseMeasurement) and information,
-// and the observation edges as inserted (permuted into the ELL layout on the device afterwards).
-struct RawUpload {
-    std::thread th; int rc = GS_OK; std::string err;
-    ~RawUpload() { if (th.joinable()) th.join(); }                  // an exception (bad_alloc in the plan build) must not meet a joinable thread: std::terminate
-    int32_t *pl_l = nullptr; double *pl_z = nullptr, *pl_info = nullptr;
-    std::vector<double> zinv; size_t pp_lo = 0, pp_hi = 0;         // the odometry edges whose records went up: [pp_lo, pp_hi) (all of them on a single GPU)
-    uvec<int32_t> ell_l; uvec<double> ell_z, ell_w;               // pose-window shards: the ELL streams, filled on the host (they must outlive the copies: upload_graph ends with a sync)
-};
-static int upload_raw_begin(gs_graph *g, RawUpload &R) {
-    const HostGraph &h = g->h; DevGraph &d = g->d;
-    const size_t N = h.n_poses(), M = h.n_lms(), Epp = h.n_pp(), Epl = h.n_pl();
-    int rc;
-    // room for the tail of a grown plan (gs::grow_plan) behind the per-pose and per-odometry-edge arrays
-    const size_t TP = TAIL_POSES, TPP = TAIL_PP;
-    const size_t TL = TAIL_LMS;
-    if ((rc = dev_alloc(g, &d.pose_est, (N + TP) * 3)) != GS_OK || (rc = dev_alloc(g, &d.lm_est, (M + TL) * 2)) != GS_OK ||
-        (rc = dev_alloc(g, &d.pose_fixed, N + TP)) != GS_OK || (rc = dev_alloc(g, &d.lm_fixed, M + TL)) != GS_OK ||
-        (rc = dev_alloc(g, &d.pose_cs, (N + TP) * 2)) != GS_OK || (rc = dev_alloc(g, &d.pp_zinv, (Epp + TPP) * 5)) != GS_OK ||
-        (rc = dev_alloc(g, &d.pp_info, (Epp + TPP) * 6)) != GS_OK) return rc;
-    HIP_TRY(hipMemsetAsync(d.pose_fixed + N, 0, TP, g->stream)); HIP_TRY(hipMemsetAsync(d.lm_fixed + M, 0, TL, g->stream));
-    // the observation edges as inserted travel now only on a single GPU; a pose-window shard uploads the ones it evaluates, in
-    // device layout, once the plan says which they are (upload_graph)
-    const bool raw_pl = g->world <= 1;
-    if (raw_pl && ((rc = dev_alloc(g, &R.pl_l, Epl)) != GS_OK || (rc = dev_alloc(g, &R.pl_z, Epl * 2)) != GS_OK || (rc = dev_alloc(g, &R.pl_info, Epl * 3)) != GS_OK)) return rc;
-    R.th = std::thread([g, &R, N, M, Epp, Epl, raw_pl] {
-        const HostGraph &h = g->h; DevGraph &d = g->d;
-        auto cp = [&](void *dst, const void *src, size_t bytes) {
-            if (R.rc != GS_OK || bytes == 0) return;
-            hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, g->stream);
-            if (e != hipSuccess) { R.rc = GS_ERR_HIP; R.err = std::string("raw upload: ") + hipGetErrorString(e); } };
-        if (hipSetDevice(g->device) != hipSuccess) { R.rc = GS_ERR_HIP; R.err = "hipSetDevice failed on the upload thread"; return; }
-        cp(d.pose_est, h.pose_est.data(), N * 3 * sizeof(double)); cp(d.lm_est, h.lm_est.data(), M * 2 * sizeof(double));
-        cp(d.pose_fixed, h.pose_fixed.data(), N); cp(d.lm_fixed, h.lm_fixed.data(), M);
-        if (raw_pl) { cp(R.pl_l, h.pl_l.data(), Epl * sizeof(int32_t)); cp(R.pl_z, h.pl_z.data(), Epl * 2 * sizeof(double));
-            cp(R.pl_info, h.pl_info.data(), Epl * 3 * sizeof(double)); }
-        // odometry edges keep their insertion order on the device.  A pose-window shard evaluates an odometry edge only if one of its poses lies in
-        // the shard's window (gs_plan.cpp, rank_of_pp: the owner of an interior endpoint, else the window of the pose; an edge between two fixed
-        // poses is rank 0's): the records of the first to the last such edge go up — an eighth of 0.8 M inverses, cosines, sines and of 70 MB at
-        // world 8 (this thread took longer than the plan build).  upload_graph checks the plan's assignment against the range and sends what is missing.
-        size_t k0 = 0, k1 = Epp;
-        if (g->world > 1 && Epp > 0) {
-            size_t nfree = 0; for (size_t p = 0; p < N; ++p) nfree += !h.pose_fixed[p];
-            const size_t W = (size_t)g->world, r = (size_t)g->rank, f_lo = (r * nfree + W - 1) / W, f_hi = ((r + 1) * nfree + W - 1) / W;
-            size_t p_lo = N, p_hi = N, f = 0;                        // insertion indices of the window's first free pose and of the next window's
-            for (size_t p = 0; p < N; ++p) if (!h.pose_fixed[p]) { if (f == f_lo) p_lo = p; if (f == f_hi) { p_hi = p; break; } ++f; }
-            auto in = [&](int32_t p) { return (size_t)p >= p_lo && (size_t)p < p_hi; };
-            k0 = Epp; k1 = 0;
-            for (size_t k = 0; k < Epp; ++k) { const int32_t i = h.pp_i[k], j = h.pp_j[k];
-                if (in(i) || in(j) || (r == 0 && h.pose_fixed[i] && h.pose_fixed[j])) { k0 = std::min(k0, k); k1 = std::max(k1, k + 1); } }
-            if (k1 <= k0) k0 = k1 = 0; }
-        R.pp_lo = k0; R.pp_hi = k1;
-        cp(d.pp_info + 6 * k0, h.pp_info.data() + 6 * k0, (k1 - k0) * 6 * sizeof(double));
-        R.zinv.resize((k1 - k0) * 5);
-        for (size_t k = k0; k < k1; ++k) { double inv[3]; se2_inverse_host(&h.pp_z[3 * k], inv);
-            double *o = &R.zinv[5 * (k - k0)]; o[0] = inv[0]; o[1] = inv[1]; o[2] = inv[2]; o[3] = std::cos(inv[2]); o[4] = std::sin(inv[2]); }
-        cp(d.pp_zinv + 5 * k0, R.zinv.data(), (k1 - k0) * 5 * sizeof(double));
-    });
-    return GS_OK;
-}
-
-// the workgroup tables of the schedule (plans with a front of more than 63 scalars) go to the device with the plan; the copies read the
-// handle's own vectors
-static int upload_tables(gs_graph *g) {
-    for (int t = 0; t < N_TABS; ++t) { g->d_wg[t] = nullptr;
-        if (g->sched.big) { int rc = dev_upload(g, (int32_t **)&g->d_wg[t], g->sched.tab[t].wg); if (rc != GS_OK) return rc; } }
-    return GS_OK;
-}
-
-static int upload_graph(gs_graph *g, RawUpload &raw) {
-    const HostGraph &h = g->h; const Plan &P = g->plan; DevGraph &d = g->d;
-    const bool ut_on = g->opt.plan_timing > 0; auto ut_prev = std::chrono::steady_clock::now();
-#define GS_UT(name) do { if (ut_on) { auto n_ = std::chrono::steady_clock::now(); std::fprintf(stderr, "upload %-18s %.2f ms\n", (name), std::chrono::duration<double, std::milli>(n_ - ut_prev).count()); ut_prev = n_; } } while (0)
-    const int N = h.n_poses(), M = h.n_lms(), Epp = h.n_pp(), Epl = h.n_pl();
-    d.N = N; d.M = M; d.Epp = Epp; d.Epl = Epl; d.n_scalar = P.n_scalar;
-    int rc;
-#define UP(dst, vec) if ((rc = dev_upload(g, &d.dst, vec)) != GS_OK) return rc
-    // estimates, fixed flags, odometry edges and the insertion-order observation arrays are in HBM already (RawUpload)
-    launch_pose_trig(d, g->stream);
-    // gs_debug_options.host_trig (an experiment, scripts/parity_spread.py): the cos / sin of the INITIAL pose angles from the host's libm
-    // instead of the device's — what the CPU oracle linearises with — to tell how much of the first increment's distance
-    // to the CPU paths is the last bit of two transcendental functions
-    if (g->opt.host_trig > 0 && N > 0) {
-        std::vector<double> cs(2 * (size_t)N);
-        for (int p = 0; p < N; ++p) { cs[2 * (size_t)p] = std::cos(h.pose_est[3 * (size_t)p + 2]); cs[2 * (size_t)p + 1] = std::sin(h.pose_est[3 * (size_t)p + 2]); }
-        HIP_TRY(hipMemcpyAsync(d.pose_cs, cs.data(), cs.size() * sizeof(double), hipMemcpyHostToDevice, g->stream));
-        HIP_TRY(hipStreamSynchronize(g->stream)); }
-    g->room = gs_graph::GrowRoom(); d.tN = d.tM = d.tEpp = d.tEpl = d.tLt = 0; d.tcapN = TAIL_POSES; d.tcapM = TAIL_LMS; d.tcapEpp = TAIL_PP; d.tcapEpl = TAIL_PL;
-    if ((rc = dev_alloc(g, &d.pose_gidx, (size_t)N + TAIL_POSES)) != GS_OK) return rc;              // (room for a grown plan's tail poses)
-    if (N > 0) HIP_TRY(hipMemcpyAsync(d.pose_gidx, P.pose_gidx.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
-    if ((rc = dev_alloc(g, &d.lm_gidx, (size_t)M + TAIL_LMS)) != GS_OK) return rc;
-    if (M > 0) HIP_TRY(hipMemcpyAsync(d.lm_gidx, P.lm_gidx.data(), (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, g->stream));
-    d.ell_T = P.ell_T; d.ell_R = P.ell_R; d.ell_len = P.ell_len; d.ell_p0 = P.ell_p0; d.ell_np = P.ell_np;
-    { const size_t L = (size_t)P.ell_len;
-      if ((rc = dev_alloc(g, &d.ell_l, L)) != GS_OK || (rc = dev_alloc(g, &d.ell_z, 2 * L)) != GS_OK || (rc = dev_alloc(g, &d.ell_w, 3 * L)) != GS_OK) return rc;
-      if (P.world <= 1) {                                            // ELL streams: permuted on the device out of the arrays that travelled during the plan build (k_build_ell)
-          int32_t *ins = nullptr;
-          if ((rc = dev_upload(g, &ins, P.ell_ins)) != GS_OK) return rc;
-          launch_build_ell((int64_t)L, ins, raw.pl_l, raw.pl_z, raw.pl_info, nullptr, P.rank, d.ell_l, d.ell_z, d.ell_w, g->stream);
-      } else {                                                       // pose-window shard: only the poses it sweeps are laid out; the streams are filled on the host
-          // ... on a thread of its own, beside the rest of this function (nothing here reads the streams; joined before the final wait): the fill
-          // and three copies out of pageable memory were 2.5-5 of a rank's ~8 ms of upload at 8 x 100k poses
-          raw.ell_l.resize(L); raw.ell_z.resize(2 * L); raw.ell_w.resize(3 * L);        // (threads) with the edges this rank evaluates, the others stay empty (l = -1)
-          raw.th = std::thread([g, &raw, L] { const HostGraph &h = g->h; const Plan &P = g->plan; DevGraph &d = g->d;
-              if (hipSetDevice(g->device) != hipSuccess) { raw.rc = GS_ERR_HIP; raw.err = "hipSetDevice failed on the upload thread"; return; }
-              parallel_chunks((int64_t)L, 16384, [&](int64_t b, int64_t e2, int) {
-                  for (int64_t e = b; e < e2; ++e) { int k = P.ell_ins[(size_t)e]; if (k >= 0 && P.pl_rank[k] != P.rank) k = -1;
-                      raw.ell_l[e] = k >= 0 ? h.pl_l[k] : -1;
-                      raw.ell_z[e] = k >= 0 ? h.pl_z[2 * (size_t)k] : 0.0; raw.ell_z[L + e] = k >= 0 ? h.pl_z[2 * (size_t)k + 1] : 0.0;
-                      raw.ell_w[e] = k >= 0 ? h.pl_info[3 * (size_t)k] : 0.0; raw.ell_w[L + e] = k >= 0 ? h.pl_info[3 * (size_t)k + 1] : 0.0;
-                      raw.ell_w[2 * L + e] = k >= 0 ? h.pl_info[3 * (size_t)k + 2] : 0.0; } });
-              hipError_t e1 = hipMemcpyAsync(d.ell_l, raw.ell_l.data(), L * sizeof(int32_t), hipMemcpyHostToDevice, g->stream);
-              hipError_t e2 = hipMemcpyAsync(d.ell_z, raw.ell_z.data(), 2 * L * sizeof(double), hipMemcpyHostToDevice, g->stream);
-              hipError_t e3 = hipMemcpyAsync(d.ell_w, raw.ell_w.data(), 3 * L * sizeof(double), hipMemcpyHostToDevice, g->stream);
-              if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) { raw.rc = GS_ERR_HIP; raw.err = "edge streams: copy to the device failed"; } }); } }
-    GS_UT("estimates+edges");
-    UP(lm_start, P.lm_start); UP(lm_edges, P.lm_edges); UP(ppadj_start, P.ppadj_start);
-    { const size_t Q = P.ppinc.size() / 4;                                // device records are 8 bytes: {edge, other endpoint | role << 31}; the pose that
-      std::vector<int32_t> inc(2 * Q);                                    // holds the record is known to the kernel; an edge another rank evaluates: edge = -1
-      for (size_t q = 0; q < Q; ++q) { const int32_t k = P.ppinc[4 * q], role = P.ppinc[4 * q + 1], other = role ? P.ppinc[4 * q + 2] : P.ppinc[4 * q + 3];
-          inc[2 * q] = (P.world > 1 && P.pp_rank[k] != P.rank) ? -1 : k; inc[2 * q + 1] = (int32_t)((uint32_t)other | ((uint32_t)role << 31)); }
-      UP(ppinc, inc);
-      // a shard's helper thread sent the records of the odometry edges [pp_lo, pp_hi) — the ones that touch its window; an edge the plan gives
-      // this rank outside that range (none, by the assignment rule: kept as a check that cannot go wrong silently) is sent now
-      std::vector<int32_t> miss;
-      for (size_t q = 0; q < Q; ++q) { const int32_t k = inc[2 * q]; if (k >= 0 && ((size_t)k < raw.pp_lo || (size_t)k >= raw.pp_hi)) miss.push_back(k); }
-      std::sort(miss.begin(), miss.end()); miss.erase(std::unique(miss.begin(), miss.end()), miss.end());
-      for (int32_t k : miss) { double inv[3], o[5]; se2_inverse_host(&h.pp_z[3 * (size_t)k], inv);
-          o[0] = inv[0]; o[1] = inv[1]; o[2] = inv[2]; o[3] = std::cos(inv[2]); o[4] = std::sin(inv[2]);
-          HIP_TRY(hipMemcpy(d.pp_zinv + 5 * (size_t)k, o, sizeof(o), hipMemcpyHostToDevice));
-          HIP_TRY(hipMemcpy(d.pp_info + 6 * (size_t)k, &h.pp_info[6 * (size_t)k], 6 * sizeof(double), hipMemcpyHostToDevice)); }
-      g->pp_records_late = (int)miss.size();
-      if (ut_on && !miss.empty()) std::fprintf(stderr, "upload: %d odometry edge records sent after the plan\n", (int)miss.size()); }
-#define AL(dst, cnt) if ((rc = dev_alloc(g, &d.dst, (size_t)(cnt))) != GS_OK) return rc
-#define ZERO(dst, cnt) HIP_TRY(hipMemsetAsync(d.dst, 0, std::max<size_t>((size_t)(cnt), 1) * sizeof(*d.dst), g->stream))
-    d.n_wtiles = 0; d.n_groups = 0; d.wt_lo = 0; d.wt_hi = 0; d.rank = P.rank;
-    // the fused kernel addresses the ELL planes with 32-bit byte offsets: 8 B * ell_len must stay below 4 GiB
-    if (P.lin_ell_ok && !g->force_gather && P.ell_len < ((int64_t)1 << 29)) {
-        d.n_wtiles = P.n_wtiles; d.n_groups = (int32_t)P.grp_lm.size();
-        UP(wt_desc, P.wt_desc); UP(lm_grp_start, P.lm_grp_start);
-        { const size_t Gn = P.grp_slot.size(); std::vector<int32_t> gt(2 * Gn + 2, 0);   // per group {first | end << 16 of its tile-local positions, partial-sum slot}
-          for (int w = P.wt_lo; w < P.wt_hi; ++w) { const int ga = P.wt_desc[4 * (size_t)w], gn = P.wt_desc[4 * (size_t)w + 1], pos_off = P.wt_desc[4 * (size_t)w + 2];
-              for (int q = ga; q < ga + gn; ++q) { gt[2 * (size_t)q] = (P.grp_pos_start[q] - pos_off) | ((P.grp_pos_start[q + 1] - pos_off) << 16); gt[2 * (size_t)q + 1] = P.grp_slot[q]; } }
-          UP(grp_tab, gt); }
-        UP(ell_dst, P.ell_dst);
-        d.wt_lo = P.wt_lo; d.wt_hi = P.wt_hi;                             // the wave tiles this shard has any edge in (gs_plan.cpp)
-    } else if (P.world > 1) return fail(GS_ERR_INVALID, "pose-window shards need the fused linearisation layout (<= 32 observations per pose)");
-    // block-sparse H and b live in ONE arena (the variant-3 front assembly addresses every scalar by its offset in it)
-    int64_t arena_off[14], arena_doubles = 0;
-    { // (the last six parts: the blocks of a grown plan's tail — diagonal blocks and rhs of tail poses / landmarks, off-diagonal blocks of tail edges)
-      const int64_t sizes[13] = {(int64_t)N * 6, (int64_t)N * 3, (int64_t)Epp * 9, (int64_t)P.ell_len * 6, (int64_t)d.n_groups * 8, (int64_t)M * 3, (int64_t)M * 2,
-                                 (int64_t)TAIL_POSES * 6, (int64_t)TAIL_POSES * 3, (int64_t)TAIL_PP * 9, (int64_t)TAIL_PL * 6, (int64_t)TAIL_LMS * 3, (int64_t)TAIL_LMS * 2};
-      arena_off[0] = 0;
-      for (int k = 0; k < 13; ++k) { arena_off[k + 1] = arena_off[k] + ((sizes[k] + 1) & ~(int64_t)1);       // 16-byte aligned parts
-          if (k + 1 == 4) arena_off[4] = (arena_off[4] + 7) & ~(int64_t)7; }                                   // (the partial-sum records: one 64-byte line each)
-      if (arena_off[13] >= ((int64_t)1 << 31)) return fail(GS_ERR_INVALID, "graph too large for 32-bit arena offsets");
-      arena_doubles = arena_off[13];
-      AL(H_arena, (size_t)arena_off[13] + 2);
-      // blocks of edges / tiles this rank never evaluates must read as zero
-      ZERO(H_arena, (size_t)arena_off[13] + 2);
-      d.t_Hpp_diag = d.H_arena + arena_off[7]; d.t_b_pose = d.H_arena + arena_off[8]; d.t_Hpp_off = d.H_arena + arena_off[9]; d.t_Hpl = d.H_arena + arena_off[10];
-      d.t_Hll_diag = d.H_arena + arena_off[11]; d.t_b_lm = d.H_arena + arena_off[12];
-      AL(t_pp_ij, (size_t)TAIL_PP * 2); AL(t_pl, (size_t)TAIL_PL * 2); AL(t_pl_z, (size_t)TAIL_PL * 2); AL(t_pl_w, (size_t)TAIL_PL * 3);
-      AL(t_pose_start, (size_t)TAIL_POSES + 1); AL(t_pose_edges, (size_t)TAIL_PL); AL(t_lt_id, (size_t)TAIL_PL); AL(t_lt_start, (size_t)TAIL_PL + 1); AL(t_lt_edges, (size_t)TAIL_PL);
-      // (the fused linearisation kernel stores Hpp_diag's 6 planes and b_pose's 3 as 9 contiguous planes: 6N is even, no padding between)
-      d.Hpp_diag = d.H_arena + arena_off[0]; d.b_pose = d.H_arena + arena_off[1]; d.Hpp_off = d.H_arena + arena_off[2];
-      d.Hpl = d.H_arena + arena_off[3]; d.lm_part = d.H_arena + arena_off[4]; d.Hll_diag = d.H_arena + arena_off[5]; d.b_lm = d.H_arena + arena_off[6]; }
-    d.n_chi2_partial = std::max((N + 255) / 256, d.n_wtiles);
-    AL(chi2_partial, d.n_chi2_partial + 1); AL(chi2, 80); ZERO(chi2_partial, d.n_chi2_partial + 1);     // (+1: the partial of a grown plan's tail)
-    UP(pose_known, P.pose_known); UP(lm_known, P.lm_known);
-    GS_UT("tiles+arena");
-    // plan
-    { std::vector<DevFront> df(P.fronts.size());
-      for (size_t s = 0; s < P.fronts.size(); ++s) { const Front &F = P.fronts[s]; DevFront &o = df[s];
-          o.npiv = F.npiv; o.nbnd = F.nbnd; o.piv0 = F.piv0; o.parent = F.parent; o.asm_off = F.asm_off; o.asm_cnt = F.asm_cnt;
-          o.asm_dup = F.asm_dup; o.child_off = F.child_off; o.child_cnt = F.child_cnt; o.owner = F.owner; o.level = F.level; o.pad0 = 0;
-          o.bnd_off = F.bnd_off; o.map_off = F.map_off; o.L_off = F.L_off; o.U_off = F.U_off; }
-      UP(fronts, df); d.n_fronts = (int32_t)df.size(); }
-    // boundary rows, child maps and assembly records with room behind them: a growth step re-writes the runs of the fronts it changes there
-    // (sized with the plan, within bounds: a lap-sized graph must not pay for a 100k-pose graph's room with extra device chunks)
-    auto room_of = [](size_t n, size_t lo, size_t hi) { return std::min(hi, std::max(lo, n / 2)); };
-    const size_t ROOM_ROWS = room_of(P.bnd_rows.size(), 8 * 1024, 64 * 1024), ROOM_RECS = room_of(P.asm_recs.size(), 12 * 1024, 96 * 1024);
-    { auto up_room = [&](int32_t **dst, const int32_t *src, size_t n, size_t room) -> int {
-          int r2 = dev_alloc(g, dst, n + room); if (r2 != GS_OK) return r2;
-          if (n) { hipError_t e = hipMemcpyAsync(*dst, src, n * sizeof(int32_t), hipMemcpyHostToDevice, g->stream); if (e != hipSuccess) return fail(GS_ERR_HIP, hipGetErrorString(e)); }
-          return GS_OK; };
-      if ((rc = up_room(&d.bnd_rows, P.bnd_rows.data(), P.bnd_rows.size(), ROOM_ROWS)) != GS_OK) return rc;
-      if ((rc = up_room(&d.child_map, P.child_map.data(), P.child_map.size(), ROOM_ROWS)) != GS_OK) return rc;
-      g->room.cap_bnd = (int64_t)(P.bnd_rows.size() + ROOM_ROWS); g->room.cap_map = (int64_t)(P.child_map.size() + ROOM_ROWS); }
-    UP(children, P.children);
-    { std::vector<int32_t> cd(P.children.size() * 4);
-      for (size_t q = 0; q < P.children.size(); ++q) { const Front &C = P.fronts[P.children[q]];
-          cd[4 * q] = P.children[q]; cd[4 * q + 1] = C.npiv | (C.nbnd << 16); cd[4 * q + 2] = C.owner; cd[4 * q + 3] = (int32_t)C.map_off; }
-      UP(child_desc, cd); }
-    // level lists on the device: this rank's own fronts, then the shared top (empty when world == 1)
-    { std::vector<int32_t> lf = P.level_fronts_owned;
-      lf.insert(lf.end(), P.level_fronts_shared.begin(), P.level_fronts_shared.end());
-      UP(level_fronts, lf); }
-    d.xfail_off = -1; d.iter = 0; d.inject_iter = 0; d.inject_code = 0;
-    if (P.dist) { UP(x_off, P.x_off);
-        d.xfail_off = P.exchange_doubles - 2;                             // the ranks' failure flags ride at the tail of the exchange buffer
-        if (!g->exchange_external) { AL(exchange, P.exchange_doubles); ZERO(exchange, P.exchange_doubles); }
-        else d.exchange = g->exchange; }
-    { static_assert(sizeof(AsmRec) == 16, "AsmRec is uploaded as 4 int32");
-      if ((rc = dev_alloc(g, &d.asm_recs, (P.asm_recs.size() + ROOM_RECS) * 4)) != GS_OK) return rc;
-      if (!P.asm_recs.empty()) HIP_TRY(hipMemcpyAsync(d.asm_recs, P.asm_recs.data(), P.asm_recs.size() * sizeof(AsmRec), hipMemcpyHostToDevice, g->stream));
-      g->room.cap_asm = (int64_t)(P.asm_recs.size() + ROOM_RECS); }
-    GS_UT("plan arrays");
-    // factor kernel variant (gs_config.factor_variant; gs_debug_options.factor_variant overrides): 0 = default = 3 when every
-    // front fits 159 scalars, else 4.  3 = LDL^T on the fp64 matrix cores, a wave or a workgroup per front; 4 = block-per-front
-    // VALU Cholesky (any front size).
-    { int v = g->default_factor_variant;
-      if (g->opt.factor_variant > 0) v = g->opt.factor_variant;
-      v = gs_debug_select_factor_variant(v, P.max_front, arena_doubles);
-      if (v == 4) v = 0;                                              // device-side code for the block-per-front kernel
-      d.factor_variant = v;
-      d.dbg = g->opt.dbg; d.leaf_nt3 = g->opt.leaf_nt3 != 0 ? 1 : 0; d.f3_lds_kb = std::max(g->opt.f3_lds_kb, 0);
-      if (v == 3) {
-          std::vector<int32_t> lf = P.level_fronts_owned;
-          lf.insert(lf.end(), P.level_fronts_shared.begin(), P.level_fronts_shared.end());
-          constexpr int F3W = 224;                           // 32 descriptor ints + the row tables of the first two children + the front's own store table
-          // update matrices, packed: row r' (0 .. nbnd, the last = rhs) of the boundary block holds columns 0 .. min(r', nbnd - 1)
-          // at r'(r'+1)/2; then one double that stays zero (clamped gathers land on it) and one that collects clamped stores
-          std::vector<int32_t> u3_off(P.fronts.size()), u3_size(P.fronts.size());
-          { int64_t tot = 0;
-            for (size_t f0 = 0; f0 < P.fronts.size(); ++f0) { const int nb = P.fronts[f0].nbnd;
-                u3_off[f0] = (int32_t)tot; u3_size[f0] = (nb * (nb + 1)) / 2 + nb; tot += ((u3_size[f0] + 2 + 1) & ~1);
-                if (tot >= ((int64_t)1 << 31)) return fail(GS_ERR_INVALID, "update-matrix arena beyond 32-bit offsets"); }
-            const int64_t ROOM_U = (int64_t)room_of((size_t)tot, (size_t)128 << 10, (size_t)(P.max_front > 63 ? 4 : 1) << 20);      // doubles: the update matrices of fronts a growth step enlarges move here
-            if (tot + ROOM_U >= ((int64_t)1 << 31)) return fail(GS_ERR_INVALID, "update-matrix arena beyond 32-bit offsets");
-            AL(Uimg, (size_t)(tot + ROOM_U) + 2); ZERO(Uimg, (size_t)(tot + ROOM_U) + 2);
-            g->room.used_U = tot; g->room.cap_U = tot + ROOM_U; }
-          UP(u3_off, u3_off); UP(u3_size, u3_size);
-          g->u3_off_host = u3_off; g->u3_size_host = u3_size;
-          AL(done_f, P.fronts.size()); ZERO(done_f, P.fronts.size());
-          d.tickets = nullptr; d.ticket_base = 0;
-          if (g->opt.tickets != 0) { AL(tickets, 2); ZERO(tickets, 2); }    // workgroups of the whole-tree launches take their number from this counter (gs_kernels.hip, "tickets")
-          d.epoch = 0; d.tree = g->opt.tree != 0 ? 1 : 0; g->fell_back = false; g->fallback_calls = 0; g->fallback_retry_after = 4; g->fallback_retrying = false;   // whole-tree launches for this rank's own subtrees (gs_debug_options.tree = 0: one launch per level)
-          // ---- everything below is expanded ON THE DEVICE from the compact plan arrays
-          const bool fused = P.lin_ell_ok && d.n_wtiles > 0;
-          // block assembly records: the plan's, as they are (AsmRec = 4 ints); landmark-diagonal records of the fused
-          // linearisation get their partial-slot range patched in by a kernel
-          if ((rc = dev_alloc(g, &d.asm3, (P.asm_recs.size() + ROOM_RECS) * 4)) != GS_OK) return rc;
-          if (!P.asm_recs.empty()) HIP_TRY(hipMemcpyAsync(d.asm3, P.asm_recs.data(), P.asm_recs.size() * sizeof(AsmRec), hipMemcpyHostToDevice, g->stream));
-          if (fused) { for (int l = 0; l < M; ++l) if (P.lm_grp_start[l + 1] - P.lm_grp_start[l] >= (1 << 22)) return fail(GS_ERR_INVALID, "landmark seen from too many wave tiles");
-              launch_patch_asm3((int64_t)P.asm_recs.size(), d.asm3, d.lm_grp_start, g->stream); }
-          GS_UT("asm3");
-          // scalar assembly records {offset in H_arena, offset in the staging image}, padded per front to a multiple of
-          // 64 with (0 -> image offset 1, a don't-care upper-triangle slot); fused landmark diagonals go to lm3.
-          // The host only counts them per front.
-          { const size_t S = P.fronts.size();
-            std::vector<int32_t> bf(8 * S, 0);
-            parallel_chunks((int64_t)S, 2048, [&](int64_t b, int64_t e, int) {
-                for (int64_t sidx = b; sidx < e; ++sidx) { const Front &F = P.fronts[sidx]; int ns = 0, nl = 0;
-                    for (int t = F.asm_off; t < F.asm_off + F.asm_cnt - F.asm_dup; ++t) { const int k = P.asm_recs[t].kind;
-                        if (k == 0) ns += 9; else if (k == 1) { if (fused) ++nl; else ns += 5; } else if (k <= 3) ns += 9; else if (k == 6) ns += 5; else ns += 6; }
-                    bf[8 * sidx + 4] = (ns + 63) & ~63; bf[8 * sidx + 6] = nl; } });
-            int64_t so = 0, lo = 0;
-            for (size_t sidx = 0; sidx < S; ++sidx) { const Front &F = P.fronts[sidx]; int32_t *r = &bf[8 * sidx];
-                if (so >= ((int64_t)1 << 31) - 64) return fail(GS_ERR_INVALID, "too many assembly scalars");
-                r[0] = F.asm_off; r[1] = F.asm_cnt - F.asm_dup; r[2] = F.npiv + F.nbnd; r[3] = (int32_t)so; r[5] = (int32_t)lo; so += r[4]; lo += r[6]; }
-            const int64_t ROOM_SC = (int64_t)room_of((size_t)so, (size_t)64 << 10, (size_t)(P.max_front > 63 ? 4 : 1) << 19);         // scalar records of the fronts a growth step rebuilds
-            if (so + ROOM_SC >= ((int64_t)1 << 31) - 64) return fail(GS_ERR_INVALID, "too many assembly scalars");
-            AL(sc3, 2 * (size_t)(so + ROOM_SC) + 2); AL(lm3, 4 * (size_t)lo + 4);
-            g->room.used_sc = so; g->room.cap_sc = so + ROOM_SC;
-            int32_t *bf_dev = nullptr; if ((rc = dev_upload(g, &bf_dev, bf)) != GS_OK) return rc;
-            g->d_bf = bf_dev; g->bf_host = bf;
-            Sc3Args A; for (int k = 0; k < 8; ++k) A.off[k] = arena_off[k];
-            A.L = P.ell_len; A.N = N; A.M = M; A.Epp = Epp; A.fused = fused ? 1 : 0;
-            for (int k = 0; k < 6; ++k) A.toff[k] = arena_off[7 + k];
-            A.tcapN = TAIL_POSES; A.tcapEpp = TAIL_PP; A.tcapEpl = TAIL_PL; A.tcapM = TAIL_LMS;
-            g->sc3_args = A;
-            launch_build_sc3(bf_dev, d.asm3, d.sc3, d.lm3, (int)S, A, g->stream);
-            GS_UT("sc3 build");
-            // descriptors + children tables: one wave per level position (k_build_f3)
-            d.f3x_stride = P.max_front > 63 ? 168 : 72;                 // a child's row table: 64 entries, or 160 when the plan holds a big front
-            std::vector<int32_t> xrow(lf.size() + 1, 0);
-            for (size_t q = 0; q < lf.size(); ++q) { xrow[q + 1] = xrow[q] + d.f3x_stride * P.fronts[lf[q]].child_cnt;
-                if (xrow[q + 1] >= (1 << 30)) return fail(GS_ERR_INVALID, "children table too large"); }
-            int32_t *xrow_dev = nullptr; if ((rc = dev_upload(g, &xrow_dev, xrow)) != GS_OK) return rc;
-            g->d_xrow = xrow_dev;
-            g->pos_of_front.assign(P.fronts.size(), -1);
-            for (size_t q = 0; q < lf.size(); ++q) g->pos_of_front[lf[q]] = (int32_t)q;
-            if ((rc = dev_upload(g, &g->d_posof, g->pos_of_front)) != GS_OK) return rc;      // front -> level position: into the children's headers (k_factor3_sub finds a leaf's descriptor through it)
-            if ((rc = dev_alloc(g, &g->d_patch, (size_t)1024 * 32)) != GS_OK || (rc = dev_alloc(g, &g->d_list, (size_t)2048)) != GS_OK) return rc;
-            AL(f3_desc, lf.size() * (size_t)F3W); AL(f3_x, (size_t)xrow[lf.size()] + 168);
-            launch_build_f3((int)lf.size(), d.level_fronts, d.fronts, d.children, d.child_map, d.u3_off, d.u3_size, bf_dev, xrow_dev,
-                            P.dist ? d.x_off : nullptr, d.f3_desc, d.f3_x, d.f3x_stride, g->stream, nullptr, g->d_posof);
-            // a growth step needs all of the above: variant 3, one GPU, the fused linearisation layout
-            g->room.ok = !P.dist && fused;
-            GS_UT("f3 tables"); }
-      } }
-    GS_UT("f3 x+desc upload");
-    AL(dbg_ts, 64); ZERO(dbg_ts, 64);
-    AL(done_ts, 2 * P.fronts.size() + 2); ZERO(done_ts, 2 * P.fronts.size() + 2);
-    { const int64_t room_L = g->room.ok ? (int64_t)room_of((size_t)P.l_doubles, (size_t)256 << 10, (size_t)(P.max_front > 63 ? 8 : 2) << 20) : 0;          // doubles: the L panels of fronts a growth step enlarges move here
-      AL(Lbuf, P.l_doubles + room_L); g->room.cap_L = P.l_doubles + room_L; }
-    AL(Ubuf, d.factor_variant == 0 ? P.u_doubles : 1);              // variant 3 keeps its update matrices in Uimg
-    AL(xe, P.n_scalar + 3 * TAIL_POSES + 2 * TAIL_LMS); g->room.cap_xe = P.n_scalar + 3 * TAIL_POSES + 2 * TAIL_LMS;
-    AL(dpose, ((size_t)N + TAIL_POSES) * 3); AL(dlm, ((size_t)M + TAIL_LMS) * 2); AL(fail, 4);
-    HIP_TRY(hipMemsetAsync(d.fail, 0, 4 * sizeof(int32_t), g->stream));
-    HIP_TRY(hipMemsetAsync(d.chi2, 0, 80 * sizeof(double), g->stream));
-    HIP_TRY(hipMemsetAsync(d.dpose, 0, ((size_t)N + TAIL_POSES) * 3 * sizeof(double), g->stream));
-    HIP_TRY(hipMemsetAsync(d.dlm, 0, ((size_t)M + TAIL_LMS) * 2 * sizeof(double), g->stream));
-    // the solver launches of this plan, decided here once (gs_schedule.hpp); the global workspace for fronts beyond the LDS limit,
-    // one slice per block; the workgroup tables of a plan with fronts beyond a wave
-    g->sched = build_schedule(P, g->pos_of_front, d.factor_variant, g->opt.tree != 0, g->opt);
-    d.front_ws_stride = g->sched.front_ws_stride;
-    if (g->sched.ws_blocks > 0) AL(front_ws, d.front_ws_stride * g->sched.ws_blocks);
-    if ((rc = upload_tables(g)) != GS_OK) return rc;
-#undef UP
-#undef AL
-#undef ZERO
-    GS_UT("arenas+levels");
-    if (raw.th.joinable()) { raw.th.join(); if (raw.rc != GS_OK) return fail(raw.rc, raw.err); }      // a shard's edge streams (above)
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    GS_UT("final sync");
-    g->dev_valid = true; g->dev_estimates_newer = false; g->tree_proven = false;
-    ++g->value_uploads;                                              // every edge's own information is on the device again (edge_mask_sync)
-    g->dev_estimate_version = h.estimate_version;
-    return GS_OK;
-}
-
-// ---- append-only growth on the device (after gs::grow_plan changed the host plan): the new poses' and edges' data into the tail
-// arrays, the re-written runs of the changed fronts behind the plan arrays, those fronts' rows of the compact tables through one
-// patch buffer, then the device-side expansion (k_build_sc3, k_build_f3) for those fronts only.  Everything older stays where it
-// is.  Returns GS_ERR_CAPACITY when the room left by the full structure phase is used up (the caller rebuilds).
-static int upload_growth(gs_graph *g, const Growth &gr) {
-    const HostGraph &h = g->h; const Plan &P = g->plan; DevGraph &d = g->d;
-    if (!g->room.ok || d.factor_variant != 3) return fail(GS_ERR_CAPACITY, "growth: this plan was not uploaded with room to grow");
-    const int nf = (int)gr.fronts.size();
-    if (nf > 1024 || (int64_t)P.bnd_rows.size() > g->room.cap_bnd || (int64_t)P.child_map.size() > g->room.cap_map ||
-        (int64_t)P.asm_recs.size() > g->room.cap_asm || P.l_doubles > g->room.cap_L || P.n_scalar > g->room.cap_xe)
-        return fail(GS_ERR_CAPACITY, "growth: room behind the plan arrays used up");
-    const bool fused = g->sc3_args.fused != 0;
-    // update-matrix slots and scalar-record runs of the changed fronts
-    std::vector<int32_t> patch((size_t)nf * 32, 0), poslist(nf);
-    int64_t used_U = g->room.used_U, used_sc = g->room.used_sc;
-    for (int i = 0; i < nf; ++i) { const int s = gr.fronts[i]; const Front &F = P.fronts[s]; int32_t *r = &patch[(size_t)i * 32];
-        const int nb = F.nbnd; const int32_t usz = (nb * (nb + 1)) / 2 + nb;
-        int ns = 0;
-        for (int t = F.asm_off; t < F.asm_off + F.asm_cnt - F.asm_dup; ++t) { const int k = P.asm_recs[t].kind;
-            if (k == 0) ns += 9; else if (k == 1) { if (!fused) ns += 5; } else if (k <= 3) ns += 9; else if (k == 6) ns += 5; else ns += 6; }
-        const int32_t sc_cnt = (ns + 63) & ~63;
-        if (used_U + usz + 4 > g->room.cap_U || used_sc + sc_cnt > g->room.cap_sc) return fail(GS_ERR_CAPACITY, "growth: room behind the update matrices / scalar records used up");
-        DevFront o; o.npiv = F.npiv; o.nbnd = F.nbnd; o.piv0 = F.piv0; o.parent = F.parent; o.asm_off = F.asm_off; o.asm_cnt = F.asm_cnt;
-        o.asm_dup = F.asm_dup; o.child_off = F.child_off; o.child_cnt = F.child_cnt; o.owner = F.owner; o.level = F.level; o.pad0 = 0;
-        o.bnd_off = F.bnd_off; o.map_off = F.map_off; o.L_off = F.L_off; o.U_off = F.U_off;
-        r[0] = s; std::memcpy(r + 1, &o, sizeof(o));
-        r[21] = (int32_t)used_U; r[22] = usz; used_U += (usz + 2 + 1) & ~1;
-        const int32_t *b0 = &g->bf_host[8 * (size_t)s];
-        r[23] = F.asm_off; r[24] = F.asm_cnt - F.asm_dup; r[25] = F.npiv + F.nbnd; r[26] = (int32_t)used_sc; r[27] = sc_cnt; r[28] = b0[5]; r[29] = b0[6]; r[30] = 0;
-        used_sc += sc_cnt;
-        poslist[i] = g->pos_of_front[s];
-        if (poslist[i] < 0) return fail(GS_ERR_INVALID, "growth: front without a level position"); }
-    // ---- from here on the device changes
-    const int N0 = gr.first_pose, N1 = P.planned_N, E0 = gr.first_pp, E1 = P.planned_Epp, K0 = gr.first_pl, K1 = P.planned_Epl;
-    std::vector<double> zinv((size_t)(E1 - E0) * 5), plz((size_t)(K1 - K0) * 2), plw((size_t)(K1 - K0) * 3);
-    std::vector<int32_t> ppij((size_t)(E1 - E0) * 2), plpl((size_t)(K1 - K0) * 2);
-    auto H2D = [&](void *dst, const void *src, size_t bytes) -> int {
-        if (!bytes) return GS_OK;
-        hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, g->stream);
-        return e == hipSuccess ? GS_OK : fail(GS_ERR_HIP, std::string("growth upload: ") + hipGetErrorString(e)); };
-    int rc;
-    if ((rc = H2D(d.pose_est + 3 * (size_t)N0, &h.pose_est[3 * (size_t)N0], (size_t)(N1 - N0) * 3 * sizeof(double))) != GS_OK) return rc;
-    if ((rc = H2D(d.pose_gidx + N0, &P.pose_gidx[N0], (size_t)(N1 - N0) * sizeof(int32_t))) != GS_OK) return rc;
-    { const int M0 = gr.first_lm, M1 = P.planned_M;                  // landmarks first seen by the new poses
-      if (M1 > M0) { if ((rc = H2D(d.lm_est + 2 * (size_t)M0, &h.lm_est[2 * (size_t)M0], (size_t)(M1 - M0) * 2 * sizeof(double))) != GS_OK) return rc;
-          if ((rc = H2D(d.lm_gidx + M0, &P.lm_gidx[M0], (size_t)(M1 - M0) * sizeof(int32_t))) != GS_OK) return rc; } }
-    if (g->dev_estimate_version != h.estimate_version) {          // a host-side setEstimate on an OLDER vertex since the last upload (g2o: setEstimate, then
-        const int M1 = P.planned_M;                                 // optimize() uses the new value): the whole estimate arrays go up again, not only the tail's
-        if ((rc = H2D(d.pose_est, h.pose_est.data(), (size_t)N1 * 3 * sizeof(double))) != GS_OK) return rc;
-        if ((rc = H2D(d.lm_est, h.lm_est.data(), (size_t)M1 * 2 * sizeof(double))) != GS_OK) return rc;
-        launch_pose_trig_range(d, 0, N1, g->stream);
-    } else launch_pose_trig_range(d, N0, N1 - N0, g->stream);
-    for (int k = E0; k < E1; ++k) { double inv[3]; se2_inverse_host(&h.pp_z[3 * (size_t)k], inv);
-        double *o = &zinv[5 * (size_t)(k - E0)]; o[0] = inv[0]; o[1] = inv[1]; o[2] = inv[2]; o[3] = std::cos(inv[2]); o[4] = std::sin(inv[2]);
-        ppij[2 * (size_t)(k - E0)] = h.pp_i[k]; ppij[2 * (size_t)(k - E0) + 1] = h.pp_j[k]; }
-    if ((rc = H2D(d.pp_zinv + 5 * (size_t)E0, zinv.data(), zinv.size() * sizeof(double))) != GS_OK) return rc;
-    if ((rc = H2D(d.pp_info + 6 * (size_t)E0, &h.pp_info[6 * (size_t)E0], (size_t)(E1 - E0) * 6 * sizeof(double))) != GS_OK) return rc;
-    if ((rc = H2D(d.t_pp_ij + 2 * (size_t)(E0 - P.base_Epp), ppij.data(), ppij.size() * sizeof(int32_t))) != GS_OK) return rc;
-    for (int k = K0; k < K1; ++k) { const size_t q = (size_t)(k - K0);
-        plpl[2 * q] = h.pl_p[k]; plpl[2 * q + 1] = h.pl_l[k]; plz[2 * q] = h.pl_z[2 * (size_t)k]; plz[2 * q + 1] = h.pl_z[2 * (size_t)k + 1];
-        for (int c = 0; c < 3; ++c) plw[3 * q + c] = h.pl_info[3 * (size_t)k + c]; }
-    { const size_t s0 = (size_t)(K0 - P.base_Epl);
-      if ((rc = H2D(d.t_pl + 2 * s0, plpl.data(), plpl.size() * sizeof(int32_t))) != GS_OK) return rc;
-      if ((rc = H2D(d.t_pl_z + 2 * s0, plz.data(), plz.size() * sizeof(double))) != GS_OK) return rc;
-      if ((rc = H2D(d.t_pl_w + 3 * s0, plw.data(), plw.size() * sizeof(double))) != GS_OK) return rc; }
-    // the tail's edges grouped by pose and by touched landmark (edge order inside a group: the order of the sums in k_linearize_tail);
-    // the whole tail, not only this step's part
-    std::vector<int32_t> tps, tpe, ltid, lts, lte;
-    { const int tN = N1 - P.base_N, tE = K1 - P.base_Epl;
-      tps.assign((size_t)tN + 1, 0); tpe.resize((size_t)tE);
-      for (int e = 0; e < tE; ++e) tps[(size_t)(h.pl_p[P.base_Epl + e] - P.base_N) + 1]++;
-      for (int t = 0; t < tN; ++t) tps[(size_t)t + 1] += tps[(size_t)t];
-      { std::vector<int32_t> fill(tps.begin(), tps.end() - 1); for (int e = 0; e < tE; ++e) tpe[(size_t)fill[(size_t)(h.pl_p[P.base_Epl + e] - P.base_N)]++] = e; }
-      std::vector<std::pair<int32_t, int32_t>> le; le.reserve((size_t)tE);        // (landmark, edge), fixed cones left out: nothing is summed for them
-      for (int e = 0; e < tE; ++e) { const int l = h.pl_l[P.base_Epl + e]; if (!h.lm_fixed[l]) le.emplace_back(l, e); }
-      std::sort(le.begin(), le.end());
-      lts.push_back(0);
-      for (size_t q = 0; q < le.size(); ++q) { if (q == 0 || le[q].first != le[q - 1].first) { if (q) lts.push_back((int32_t)q); ltid.push_back(le[q].first); } lte.push_back(le[q].second); }
-      if (!le.empty()) lts.push_back((int32_t)le.size());
-      d.tLt = (int32_t)ltid.size();
-      if ((rc = H2D(d.t_pose_start, tps.data(), tps.size() * sizeof(int32_t))) != GS_OK || (rc = H2D(d.t_pose_edges, tpe.data(), tpe.size() * sizeof(int32_t))) != GS_OK ||
-          (rc = H2D(d.t_lt_id, ltid.data(), ltid.size() * sizeof(int32_t))) != GS_OK || (rc = H2D(d.t_lt_start, lts.data(), lts.size() * sizeof(int32_t))) != GS_OK ||
-          (rc = H2D(d.t_lt_edges, lte.data(), lte.size() * sizeof(int32_t))) != GS_OK) return rc; }
-    // the re-written runs
-    if ((rc = H2D(d.bnd_rows + gr.bnd_from, &P.bnd_rows[(size_t)gr.bnd_from], (P.bnd_rows.size() - (size_t)gr.bnd_from) * sizeof(int32_t))) != GS_OK) return rc;
-    if ((rc = H2D(d.child_map + gr.map_from, &P.child_map[(size_t)gr.map_from], (P.child_map.size() - (size_t)gr.map_from) * sizeof(int32_t))) != GS_OK) return rc;
-    { const size_t na = P.asm_recs.size() - (size_t)gr.asm_from;
-      if (na) { if ((rc = H2D(d.asm_recs + 4 * gr.asm_from, &P.asm_recs[(size_t)gr.asm_from], na * sizeof(AsmRec))) != GS_OK) return rc;
-          if ((rc = H2D(d.asm3 + 4 * gr.asm_from, &P.asm_recs[(size_t)gr.asm_from], na * sizeof(AsmRec))) != GS_OK) return rc;
-          if (fused) launch_patch_asm3((int64_t)na, d.asm3 + 4 * gr.asm_from, d.lm_grp_start, g->stream); } }
-    // compact tables: the changed fronts' rows
-    if ((rc = H2D(g->d_patch, patch.data(), patch.size() * sizeof(int32_t))) != GS_OK) return rc;
-    launch_apply_front_patch(nf, g->d_patch, d.fronts, d.u3_off, d.u3_size, g->d_bf, g->stream);
-    if ((rc = H2D(g->d_list, gr.fronts.data(), (size_t)nf * sizeof(int32_t))) != GS_OK) return rc;
-    if ((rc = H2D(g->d_list + 1024, poslist.data(), (size_t)nf * sizeof(int32_t))) != GS_OK) return rc;
-    // device-side expansion for those fronts: scalar records, then descriptors + children tables (a changed front's parent is a
-    // changed front too: its copy of the child's row table is rebuilt with it)
-    launch_build_sc3(g->d_bf, d.asm3, d.sc3, d.lm3, nf, g->sc3_args, g->stream, g->d_list);
-    launch_build_f3(nf, d.level_fronts, d.fronts, d.children, d.child_map, d.u3_off, d.u3_size, g->d_bf, g->d_xrow, nullptr, d.f3_desc, d.f3_x, d.f3x_stride, g->stream, g->d_list + 1024, g->d_posof);
-    d.n_scalar = P.n_scalar; d.tN = N1 - P.base_N; d.tM = P.planned_M - P.base_M; d.tEpp = E1 - P.base_Epp; d.tEpl = K1 - P.base_Epl;
-    HIP_TRY(hipStreamSynchronize(g->stream));                       // the staging vectors above go out of scope
-    { hipError_t e = hipGetLastError(); if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("growth: ") + hipGetErrorString(e)); }
-    // host mirrors and launch parameters
-    for (int i = 0; i < nf; ++i) { const int s = gr.fronts[i]; const int32_t *r = &patch[(size_t)i * 32];
-        g->u3_off_host[s] = r[21]; g->u3_size_host[s] = r[22]; for (int c = 0; c < 8; ++c) g->bf_host[8 * (size_t)s + c] = r[23 + c]; }
-    g->room.used_U = used_U; g->room.used_sc = used_sc;
-    // the launch geometry is chosen again from the grown fronts: level maxima, leaf instance and its LDS slot, the workgroup tables (a
-    // grown front may change its size class).  The old tables stay in the pool until the next full structure phase.
-    g->sched = build_schedule(P, g->pos_of_front, d.factor_variant, g->opt.tree != 0, g->opt);
-    if ((rc = upload_tables(g)) != GS_OK) return rc;
-    g->tree_proven = false;
-    g->dev_estimate_version = h.estimate_version;
-    return GS_OK;
-}
-
+// ------------------------------------------------------------------ structure phase (A3/A4); the upload: gs_upload.cpp
 // The factor kernel a plan gets (gs_config.factor_variant; gs_debug_options.factor_variant overrides): 0 = default = 3.
 //   3 = LDL^T on the fp64 matrix cores, latency-shaped: a front of up to 63 scalars a wave, one of 64 .. 159 a workgroup, chosen per
 //   front; 4 = block-per-front VALU Cholesky (any front size, 64-bit addressing throughout).  (Rounds 1-3 also kept a wave-per-front
@@ -923,6 +470,12 @@ extern "C" int gs_debug_select_factor_variant(int32_t requested, int32_t max_fro
     if (v == 3 && max_front > 159) v = 4;                           // variant 3: a wave up to 63 scalars, a workgroup up to 159 (ten tile rows)
     if (v == 3 && arena_doubles >= ((int64_t)1 << 29)) v = 4;
     return v;
+}
+
+// ... as the device-side code a plan's upload and its schedule use (0 = the block-per-front kernel)
+int plan_factor_variant(const gs_graph *g, int64_t arena_doubles) {
+    const int v = gs_debug_select_factor_variant(g->opt.factor_variant > 0 ? g->opt.factor_variant : g->cfg.factor_variant, g->plan.max_front, arena_doubles);
+    return v == 4 ? 0 : v;
 }
 
 static int build_plan_host(gs_graph *g) {
@@ -985,29 +538,14 @@ extern "C" int gs_debug_schedule_export(gs_graph *g, int32_t *out, int64_t *out_
     std::vector<int32_t> v;
     if (g->dev_valid && g->plan_version == g->h.structure_version) export_schedule(g->plan, g->sched, v);
     else { const Plan &P = g->plan;
-        int fv = gs_debug_select_factor_variant(g->opt.factor_variant > 0 ? g->opt.factor_variant : g->cfg.factor_variant, P.max_front, 0);
-        if (fv == 4) fv = 0;
-        std::vector<int32_t> pos(P.fronts.size(), -1); int32_t q = 0;
-        for (int32_t s : P.level_fronts_owned) pos[s] = q++;
-        for (int32_t s : P.level_fronts_shared) pos[s] = q++;
-        export_schedule(P, build_schedule(P, pos, fv, g->opt.tree != 0, g->opt), v); }
+        const std::vector<int32_t> pos = pos_of_front(P, level_list(P));
+        export_schedule(P, build_schedule(P, pos, plan_factor_variant(g, 0), g->opt.tree != 0, g->opt), v); }
     if (!out) { *out_len = (int64_t)v.size(); return GS_OK; }
     if (*out_len < (int64_t)v.size()) return fail(GS_ERR_CAPACITY, "buffer too small");
     std::memcpy(out, v.data(), v.size() * sizeof(int32_t)); *out_len = (int64_t)v.size();
     return GS_OK;
 }
 
-// host-side setEstimate since the upload: the estimates (and the poses' cos / sin) to the device of the current plan
-static int push_estimates(gs_graph *g) {
-    if (g->dev_estimate_version == g->h.estimate_version) return GS_OK;
-    const int N = g->d.N + g->d.tN, M = g->d.M + g->d.tM;
-    if (N > 0) HIP_TRY(hipMemcpyAsync(g->d.pose_est, g->h.pose_est.data(), (size_t)N * 3 * sizeof(double), hipMemcpyHostToDevice, g->stream));
-    if (M > 0) HIP_TRY(hipMemcpyAsync(g->d.lm_est, g->h.lm_est.data(), (size_t)M * 2 * sizeof(double), hipMemcpyHostToDevice, g->stream));
-    launch_pose_trig(g->d, g->stream);
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    g->dev_estimate_version = g->h.estimate_version; g->dev_estimates_newer = false;
-    return GS_OK;
-}
 extern "C" int gs_initialize_optimization(gs_graph *g) {
     if (!g) return fail(GS_ERR_INVALID, "null graph");
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
@@ -1040,9 +578,7 @@ extern "C" int gs_initialize_optimization(gs_graph *g) {
             g->no_growth_reason = g_last_error;                     // (the plan object is rebuilt from scratch below)
         } else g->no_growth_reason = why;
     }
-    const bool st_on = g->opt.plan_timing != 0; auto st_prev = std::chrono::steady_clock::now();      // gs_debug_options.plan_timing: the steps of this call on stderr
-    auto ST = [&](const char *what) { if (st_on) { auto n_ = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "structure %-24s %.2f ms\n", what, std::chrono::duration<double, std::milli>(n_ - st_prev).count()); st_prev = n_; } };
+    StepTimer ST(g->opt.plan_timing != 0, "structure", 24);
     dev_release(g, true);                                            // the handle keeps its device memory for the new plan
     RawUpload raw;
     rc = upload_raw_begin(g, raw); if (rc != GS_OK) { if (raw.th.joinable()) raw.th.join(); dev_free_all(g); return rc; }

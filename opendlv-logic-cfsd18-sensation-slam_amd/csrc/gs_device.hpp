@@ -14,15 +14,9 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-namespace gs {
+#include "gs_layout.hpp"       // DevFront, the parts of H_arena, Sc3Args, the growth patch record
 
-// Mirror of Front for the device (POD, 80 bytes)
-struct DevFront {
-    int32_t npiv, nbnd, piv0, parent;
-    int32_t asm_off, asm_cnt, asm_dup, child_off;
-    int32_t child_cnt, owner, level, pad0;
-    int64_t bnd_off, map_off, L_off, U_off;
-};
+namespace gs {
 
 struct DevGraph {
     int32_t N = 0, M = 0, Epp = 0, Epl = 0, n_scalar = 0;
@@ -135,13 +129,12 @@ void launch_associate_grid_dev(int n, const double *poses, const int32_t *pose_o
                                const int32_t *map_type, double thr, double type_tol, long long buckets, const int32_t *cell_start, const int32_t *cell_items,
                                int32_t *out, int n_poses, double *pose_cs_scratch /* [n_poses][2] */, hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 // structure phase on the device: expand the block assembly records into scalar / landmark records (k_build_sc3)
-struct Sc3Args { int64_t off[8]; int64_t L; int32_t N, M, Epp, fused;
-                 int64_t toff[6]; int32_t tcapN, tcapEpp, tcapEpl, tcapM; };   // tail blocks (grow_plan): arena offsets of t_Hpp_diag, t_b_pose, t_Hpp_off, t_Hpl, t_Hll_diag, t_b_lm; plane strides
 // list != nullptr: only the fronts list[0 .. n_fronts) (growth)
 void launch_build_sc3(const int32_t *bf, const int32_t *asm3, int32_t *sc3, int32_t *lm3, int n_fronts, const Sc3Args &A, hipStream_t st, const int32_t *list = nullptr);
 void launch_linearize_tail(const DevGraph &d, hipStream_t st);  // the tail's edges: their blocks into the tail arenas, their shares of old vertices' diagonal blocks added in place
 void launch_pose_trig_range(const DevGraph &d, int first, int count, hipStream_t st);
-// growth: per-front patch records {front, DevFront (20 ints), u3_off, u3_size, bf[8]} = 32 ints each -> fronts / u3_off / u3_size / bf
+// growth: per-front patch records of PATCH_INTS = 32 ints each (gs_layout.hpp: PATCH_FRONT 0, PATCH_DEVFRONT 1 .. 20, PATCH_U3_OFF 21, PATCH_U3_SIZE 22,
+// PATCH_BF 23 .. 30, PATCH_SPARE 31) -> fronts / u3_off / u3_size / bf
 void launch_apply_front_patch(int n, const int32_t *patch, DevFront *fronts, int32_t *u3_off, int32_t *u3_size, int32_t *bf, hipStream_t st);
 void launch_build_ell(int64_t L, const int32_t *ell_ins, const int32_t *raw_l, const double *raw_z, const double *raw_info,
                       const int32_t *pl_rank, int rank, int32_t *ell_l, double *ell_z, double *ell_w, hipStream_t st);

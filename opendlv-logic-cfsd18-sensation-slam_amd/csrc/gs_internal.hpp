@@ -66,7 +66,6 @@ struct gs_graph {
         bool grid_valid = false; int grid_map_n = 0; double grid_thr = 0.0; long long grid_max_cells = 0;
         double *pcs = nullptr; size_t pcs_bytes = 0;            // cos / sin of the poses of a batched association (scratch, grow-only)
     } fe;
-    int default_factor_variant = 0;         // see upload_graph
     bool tree_proven = false;               // a whole-tree launch sequence of the CURRENT plan has completed without a flag timeout (gs_optimize then sends all iterations of a call at once)
     bool fell_back = false;                 // a whole-tree launch gave up on a flag: this handle uses one launch per level — until the next plan, or until a retry (below) comes back clean
     int fallback_calls = 0, fallback_retry_after = 4; bool fallback_retrying = false;   // gs_optimize calls on the slow path since the fallback; the call that tries the whole-tree launches again

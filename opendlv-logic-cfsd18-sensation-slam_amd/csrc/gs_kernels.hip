@@ -2728,22 +2728,22 @@ __global__ void __launch_bounds__(256) k_build_sc3(const int32_t *__restrict__ b
         const int64_t src = r.y; const int r0 = r.z, c0 = r.w;
         if (on) switch (kind) {
             case 0: { const bool tl = src >= A.N;                          // sources beyond the base counts: the tail arenas (grow_plan)
-                const int64_t N = tl ? A.tcapN : A.N, H = tl ? A.toff[0] - A.N : A.off[0], B = tl ? A.toff[1] - A.N : A.off[1];
+                const int64_t N = tl ? A.tcapN : A.N, H = tl ? A.toff[ARENA_t_Hpp_diag - ARENA_TAIL] - A.N : A.off[ARENA_Hpp_diag], B = tl ? A.toff[ARENA_t_b_pose - ARENA_TAIL] - A.N : A.off[ARENA_b_pose];
                 add(H + src, r0, c0); add(H + N + src, r0 + 1, c0); add(H + 2 * N + src, r0 + 2, c0);
                 add(H + 3 * N + src, r0 + 1, c0 + 1); add(H + 4 * N + src, r0 + 2, c0 + 1); add(H + 5 * N + src, r0 + 2, c0 + 2);
                 for (int k = 0; k < 3; ++k) add(B + k * N + src, f, c0 + k); } break;
             case 1:
                 if (A.fused) { int32_t *o = lm3 + 4 * (int64_t)(lbase + pl - 1); o[0] = r.x >> 8; o[1] = r.y; o[2] = r0; o[3] = c0; }
-                else { const int64_t H = A.off[5], B = A.off[6], M = A.M;
+                else { const int64_t H = A.off[ARENA_Hll_diag], B = A.off[ARENA_b_lm], M = A.M;
                     add(H + src, r0, c0); add(H + M + src, r0 + 1, c0); add(H + 2 * M + src, r0 + 1, c0 + 1); add(B + src, f, c0); add(B + M + src, f, c0 + 1); }
                 break;
-            case 6: { const int64_t H = A.toff[4] - A.M, B = A.toff[5] - A.M, M = A.tcapM;   // tail landmark: diagonal block + rhs out of the tail arena
+            case 6: { const int64_t H = A.toff[ARENA_t_Hll_diag - ARENA_TAIL] - A.M, B = A.toff[ARENA_t_b_lm - ARENA_TAIL] - A.M, M = A.tcapM;   // tail landmark: diagonal block + rhs out of the tail arena
                 add(H + src, r0, c0); add(H + M + src, r0 + 1, c0); add(H + 2 * M + src, r0 + 1, c0 + 1); add(B + src, f, c0); add(B + M + src, f, c0 + 1); } break;
             case 2: case 3: { const bool tl = src >= A.Epp;
-                const int64_t E = tl ? A.tcapEpp : A.Epp, H = tl ? A.toff[2] - A.Epp : A.off[2];
+                const int64_t E = tl ? A.tcapEpp : A.Epp, H = tl ? A.toff[ARENA_t_Hpp_off - ARENA_TAIL] - A.Epp : A.off[ARENA_Hpp_off];
                 for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) add(H + (kind == 2 ? 3 * a + b : 3 * b + a) * E + src, r0 + a, c0 + b); } break;
             default: { const bool tl = src >= A.L;                       // kinds 4, 5
-                const int64_t L = tl ? (int64_t)A.tcapEpl : A.L, H = tl ? A.toff[3] - A.L : A.off[3];
+                const int64_t L = tl ? (int64_t)A.tcapEpl : A.L, H = tl ? A.toff[ARENA_t_Hpl - ARENA_TAIL] - A.L : A.off[ARENA_Hpl];
                 if (kind == 4) { for (int a = 0; a < 3; ++a) for (int b = 0; b < 2; ++b) add(H + (2 * a + b) * L + src, r0 + a, c0 + b); }
                 else { for (int a = 0; a < 2; ++a) for (int b = 0; b < 3; ++b) add(H + (2 * b + a) * L + src, r0 + a, c0 + b); } } break;
         }

@@ -1,4 +1,4 @@
-// gs_parallel.hpp — host threads for the structure phase (plan build + table construction in upload_graph).
+// gs_parallel.hpp — host threads for the structure phase (plan build + table construction in gs_upload.cpp).
 // The reference runs initializeOptimization / analyzePattern single-threaded (reference src/slam.cpp:480); here the
 // structure phase is loops over poses / wave tiles / fronts that are independent once their output offsets are
 // known, so it is split over the host cores next to the GPU (GS_THREADS, default min(16, hardware threads)).

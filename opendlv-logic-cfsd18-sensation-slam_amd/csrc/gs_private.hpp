@@ -1,10 +1,13 @@
-// gs_private.hpp — what the translation units behind the C-ABI (gs_api.cpp, gs_solve.cpp, gs_frontend.cpp, gs_dist.cpp,
+// gs_private.hpp — what the translation units behind the C-ABI (gs_api.cpp, gs_upload.cpp, gs_solve.cpp, gs_frontend.cpp, gs_dist.cpp,
 // gs_marginals.cpp) share beyond the handle itself.
 #pragma once
 #include "gs_internal.hpp"
 
 #include <algorithm>
+#include <chrono>
+#include <cstdio>
 #include <string>
+#include <thread>
 #include <vector>
 
 #define HIP_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
@@ -85,6 +88,31 @@ int pull_estimates_if_needed(gs_graph *g);
 int pull_estimates_enqueue(gs_graph *g, bool &pull);        // the copies only: they come back with the caller's next wait, which then clears dev_estimates_newer if `pull`
 int reset_failure(gs_graph *g);
 void fill_plan_stats(gs_graph *g, gs_stats *s);
+int plan_factor_variant(const gs_graph *g, int64_t arena_doubles);   // the factor kernel of the current plan as DevGraph::factor_variant names it: 3, or 0 for the C-ABI's variant 4
+// gs_debug_options.plan_timing: the steps of a structure phase on stderr, "<phase> <step, padded to width> <ms> ms" each (scripts/plan_phase_table.py
+// reads the lines)
+struct StepTimer {
+    bool on; const char *phase; int width; std::chrono::steady_clock::time_point prev = std::chrono::steady_clock::now();
+    StepTimer(bool on_, const char *phase_, int width_) : on(on_), phase(phase_), width(width_) {}
+    void operator()(const char *step) { if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "%s %-*s %.2f ms\n", phase, width, step, std::chrono::duration<double, std::milli>(now - prev).count()); prev = now; }
+};
+// gs_upload.cpp
+// What does not depend on the plan travels on a helper thread while the host builds the plan (upload_raw_begin starts it; the caller joins
+// it before upload_graph); a pose-window shard's edge streams travel on a second one beside upload_graph, which joins it
+struct RawUpload {
+    std::thread th; int rc = GS_OK; std::string err;
+    ~RawUpload() { if (th.joinable()) th.join(); }                  // an exception (bad_alloc in the plan build) must not meet a joinable thread: std::terminate
+    int32_t *pl_l = nullptr; double *pl_z = nullptr, *pl_info = nullptr;
+    std::vector<double> zinv; size_t pp_lo = 0, pp_hi = 0;         // the odometry edges whose records went up: [pp_lo, pp_hi) (all of them on a single GPU)
+    gs::uvec<int32_t> ell_l; gs::uvec<double> ell_z, ell_w;       // pose-window shards: the ELL streams, filled on the host (they must outlive the copies: upload_graph ends with a sync)
+};
+int upload_raw_begin(gs_graph *g, RawUpload &R);
+int upload_tables(gs_graph *g);                // the schedule's workgroup tables (g->sched) to the device
+int upload_graph(gs_graph *g, RawUpload &raw); // the plan of the current graph to the device, schedule included
+int upload_growth(gs_graph *g, const gs::Growth &gr);          // what gs::grow_plan changed; GS_ERR_CAPACITY: the room behind the plan's arrays is used up (the caller rebuilds)
+int push_estimates(gs_graph *g);               // host-side setEstimate since the upload: estimates and the poses' cos / sin to the device
 // gs_prior_api.cpp
 int prior_sync(gs_graph *g);                   // the prior tables to the device when the priors or the plan changed (side_sync); nothing without priors
 // gs_edge_mask_api.cpp

@@ -1,0 +1,22 @@
+"""The upload of a plan without a GPU: the table builders that the full upload and the append-only growth share
+(csrc/gs_upload_host.hpp, csrc/gs_layout.hpp) on real plans, under the host sanitizers."""
+import os
+import shutil
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "opendlv-logic-cfsd18-sensation-slam_amd", "csrc")
+
+
+def test_upload_table_builders_under_address_and_undefined_sanitizers(tmp_path):
+    """tests/upload_tables_san.cpp: a stand-alone program (its own main, no HIP, nothing loaded into python) linked with csrc/gs_plan.cpp.
+    It plans a 160-pose chain (wave fronts only) and grows it by 4 poses, plans the smallest shape graph with a front of more than 63
+    scalars, and plans the chain as rank 3 of 8; the arena layout, the record counts, the update-matrix slots, the growth patch records,
+    the incidence records and the tail's groupings are checked against brute-force restatements."""
+    cxx = shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "upload_tables_san")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I", CSRC,
+                           os.path.join(ROOT, "tests", "upload_tables_san.cpp"), os.path.join(CSRC, "gs_plan.cpp"), "-o", exe, "-lpthread"])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "upload tables: ok" in out.stdout, out.stdout + out.stderr
