@@ -57,7 +57,8 @@ extern "C" {
  *   experiments / diagnostics
  *     host_trig       GS_HOST_TRIG     plan  1: cos / sin of the INITIAL pose angles from the host's libm (scripts/parity_spread.py)
  *     pool_poison     GS_POOL_POISON   plan  1: device chunks are filled with 0xFF when taken and when released
- *     plan_timing     GS_PLAN_TIMING   plan  1: per-phase wall times of the structure phase on stderr
+ *     plan_timing     GS_PLAN_TIMING   plan  1: per-step wall times of the structure phase on stderr, one line "<phase> <step> <ms> ms" each: phase
+ *                                      "structure" (the driver), "plan" (the host's plan build, e.g. "plan symbolic  1.93 ms") and "upload"
  *     dbg             GS_DBG           plan  in-kernel phase timestamps: 8 | level_count << 8, 16 | level_position << 8
  * Two process-wide variables remain outside the struct: GS_THREADS (host threads of the plan build) and, Python binding only, GS_LIB. */
 typedef struct gs_debug_options {

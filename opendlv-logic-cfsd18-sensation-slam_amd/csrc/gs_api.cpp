@@ -4,6 +4,7 @@
 #include "../../include/graphslam.h"
 #include "../../include/graphslam_debug.h"
 #include "gs_private.hpp"
+#include "gs_parallel.hpp"
 #include "gs_upload_host.hpp"
 
 #include <algorithm>

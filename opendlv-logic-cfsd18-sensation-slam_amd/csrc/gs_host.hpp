@@ -158,7 +158,7 @@ struct PlanOptions { int leaf_poses = 8; int world = 1; int rank = 0; int ell_la
                      // handed over by the caller — the graph then needs the observation edges of this rank's own window, of the windows' first poses and of the
                      // fixed poses only; nullptr: computed here in one pass over all observation edges (every rank holds the whole graph)
                      const uint64_t *lm_seen_interior = nullptr, *lm_seen_first = nullptr;
-                     bool timing = false;              // per-phase wall times on stderr (gs_debug_options.plan_timing)
+                     bool timing = false;              // per-step wall times on stderr, "plan <step> <ms> ms" (gs_debug_options.plan_timing)
                      int force_shared_top = 0; };      // world 1: treat the top k levels as the shared top of a sharded graph (gs_debug_options.force_shared_top)
 
 constexpr int LIN_R = 4;               // observation slots per lane handled by the fused linearisation kernel

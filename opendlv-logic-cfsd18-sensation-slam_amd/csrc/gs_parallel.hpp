@@ -7,6 +7,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <cstdio>
 #include <cstdlib>
 #include <mutex>
 #include <thread>
@@ -133,5 +134,15 @@ template <class... Fs> void parallel_tasks(Fs &&...fs) {
     (th.emplace_back(std::forward<Fs>(fs)), ...);
     for (auto &x : th) x.join();
 }
+
+// gs_debug_options.plan_timing: the steps of a structure phase on stderr, "<phase> <step, padded to width> <ms> ms" each — phase "structure" (the driver),
+// "upload" and "plan" (build_plan's steps; scripts/plan_phase_table.py reads those lines)
+struct StepTimer {
+    bool on; const char *phase; int width; std::chrono::steady_clock::time_point prev = std::chrono::steady_clock::now();
+    StepTimer(bool on_, const char *phase_, int width_) : on(on_), phase(phase_), width(width_) {}
+    void operator()(const char *step) { if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        std::fprintf(stderr, "%s %-*s %.2f ms\n", phase, width, step, std::chrono::duration<double, std::milli>(now - prev).count()); prev = now; }
+};
 
 }  // namespace gs

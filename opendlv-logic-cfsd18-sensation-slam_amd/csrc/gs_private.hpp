@@ -89,15 +89,7 @@ int pull_estimates_enqueue(gs_graph *g, bool &pull);        // the copies only: 
 int reset_failure(gs_graph *g);
 void fill_plan_stats(gs_graph *g, gs_stats *s);
 int plan_factor_variant(const gs_graph *g, int64_t arena_doubles);   // the factor kernel of the current plan as DevGraph::factor_variant names it: 3, or 0 for the C-ABI's variant 4
-// gs_debug_options.plan_timing: the steps of a structure phase on stderr, "<phase> <step, padded to width> <ms> ms" each (scripts/plan_phase_table.py
-// reads the lines)
-struct StepTimer {
-    bool on; const char *phase; int width; std::chrono::steady_clock::time_point prev = std::chrono::steady_clock::now();
-    StepTimer(bool on_, const char *phase_, int width_) : on(on_), phase(phase_), width(width_) {}
-    void operator()(const char *step) { if (!on) return;
-        const auto now = std::chrono::steady_clock::now();
-        std::fprintf(stderr, "%s %-*s %.2f ms\n", phase, width, step, std::chrono::duration<double, std::milli>(now - prev).count()); prev = now; }
-};
+// (gs::StepTimer, the plan_timing lines of the structure driver, the upload and the plan build: gs_parallel.hpp)
 // gs_upload.cpp
 // What does not depend on the plan travels on a helper thread while the host builds the plan (upload_raw_begin starts it; the caller joins
 // it before upload_graph); a pose-window shard's edge streams travel on a second one beside upload_graph, which joins it

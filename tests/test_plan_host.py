@@ -128,6 +128,29 @@ def test_plan_is_the_same_for_any_number_of_host_threads(pkg):
     assert len(digests) == 1, digests
 
 
+def test_plans_match_the_recorded_digests_for_any_number_of_host_threads(tmp_path):
+    """tests/plan_digest.cpp: a stand-alone program (its own main, no HIP, nothing loaded into python) linked with csrc/gs_plan.cpp.  It builds
+    (and, for the chain, grows) the smallest graphs that reach each branch of build_plan / grow_plan — wave fronts only, a workgroup front, wide
+    views, a pose past the fused layout, shuffled insertion order with parallel edges, the leaf sizes, the lane overrides, every rank of 8 by
+    windows / by the general recursion / with the masks handed over, a window with several roots, a forced shared top, the refusals, 40 000 poses
+    on the worker pool, every case again on one recycled Plan — and prints one FNV-1a digest per case over EVERY member of the plan.  The output
+    must equal tests/golden/plan_digests.txt byte for byte with GS_THREADS = 1, 3 and 8.  A change that is MEANT to alter a plan regenerates the
+    file in the same commit (./plan_digest > tests/golden/plan_digests.txt; --members names the arrays that moved)."""
+    import shutil
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "opendlv-logic-cfsd18-sensation-slam_amd", "csrc")
+    cxx = shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "plan_digest")
+    subprocess.check_call([cxx, "-std=c++17", "-O2", "-I", csrc, os.path.join(root, "tests", "plan_digest.cpp"), os.path.join(csrc, "gs_plan.cpp"), "-o", exe, "-lpthread"])
+    golden = open(os.path.join(root, "tests", "golden", "plan_digests.txt")).read()
+    for n in ("1", "3", "8"):
+        r = subprocess.run([exe], env=dict(os.environ, GS_THREADS=n), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-1000:]
+        assert r.stdout == golden, "GS_THREADS=%s: %s" % (n, [a for a, b in zip(r.stdout.splitlines(), golden.splitlines()) if a != b][:5])
+
+
 def test_a_rank_plans_its_own_window_and_the_shared_top_only(pkg, bench_graphs):
     """Pose-window shards: the other ranks' subtrees stay single (opaque) supernodes in a rank's plan — vertices and boundary,
     no records, no storage — and the observation edges are laid out for the poses the rank sweeps only.  Fronts, factor
