@@ -40,7 +40,11 @@ roundings on the longest chain from an input to one edge's term (each counted as
                the second level of the finalize pass;  together  L + n,  doubled as the solver tests' 64 (f_max + 2) u carries its own margin.
 
 The bound can fail: `check_can_fail` multiplies one contributing edge's term of an entry by (1 + 1e-9); the unperturbed result must then violate
-the bound at that entry wherever 1e-9 |term| > 2 C(n) u S, i.e. wherever ANY fp64 evaluation could tell (see check_can_fail)."""
+the bound at that entry wherever 1e-9 |term| > 2 C(n) u S, i.e. wherever ANY fp64 evaluation could tell (see check_can_fail).
+
+The passes that run behind the linearisation and write into the same arrays (prior edges, polar observation edges) add their terms to the
+same Exact through add(..., L, tag) with the L of their own rounding count (tests/side_exact_ref.py): an entry's constant is then
+2 (L + n) with L the longest chain among its terms — for an entry that holds only the linearisation's terms, what it was."""
 import numpy as np
 import mpmath
 
@@ -182,13 +186,28 @@ class Exact:
         self.terms = {k: {} for k in ARRAYS}
         self.chi2, self.chi2_Sm, self.chi2_n, self.chi2_terms = ZERO, ZERO, 0, []
         self.s_pp, self.s_pl, self.S_s_pp, self.S_s_pl = [], [], [], []
+        # L of the bound per entry: the longest chain among the terms summed into it.  The linearisation's own terms have L_PLAIN / L_ROBUST
+        # (the module docstring); a side pass (tests/side_exact_ref.py) passes the L of its own count and a tag naming the pass
+        self.base_L = L_ROBUST if robust_on else L_PLAIN
+        self.L = {k: np.zeros(sizes[k] * WIDTH[k], dtype=np.int64) for k in ARRAYS}
+        self.tags = {k: {} for k in ARRAYS}
+        self.chi2_L, self.chi2_tags = self.base_L, []
+        self.L_s_pl = None                                         # per observation edge, where a side pass has a longer chain to s than L_PLAIN
 
-    def add(self, name, row, vals, mags):
+    def add(self, name, row, vals, mags, L=None, tag=None):
         w = WIDTH[name]
         for t, (v, m) in enumerate(zip(vals, mags)):
             k = row * w + t
             self.val[name][k] += v; self.Sm[name][k] += m; self.n[name][k] += 1
-            self.terms[name].setdefault(k, []).append(v)
+            self.L[name][k] = max(self.L[name][k], self.base_L if L is None else L)
+            self.terms[name].setdefault(k, []).append(v); self.tags[name].setdefault(k, []).append(tag)
+
+    def bound(self, name):
+        """C(n) = 2 (L + n) per entry of an array"""
+        return 2.0 * (self.L[name] + self.n[name]).astype(np.float64)
+
+    def chi2_bound(self):
+        return 2.0 * (self.chi2_L + self.chi2_n)
 
     def finish(self):
         self.S = {k: np.array([float(v) for v in self.Sm[k]]) for k in ARRAYS}
@@ -223,7 +242,7 @@ def linearize(g, kernels=None, poses=None, lms=None):
         return s, S_s, rho, S_rho, H, b
 
     def count_chi(rho, S_rho):
-        X.chi2 += rho; X.chi2_Sm += S_rho; X.chi2_n += 1; X.chi2_terms.append(rho)
+        X.chi2 += rho; X.chi2_Sm += S_rho; X.chi2_n += 1; X.chi2_terms.append(rho); X.chi2_tags.append(None)
 
     Zpp = _m(g["pp_z"], (-1, 3)); Wpp = np.asarray(g["pp_info"], dtype=np.float64).reshape(-1, 3, 3)
     for k, (i, j) in enumerate(zip(g["pp_i"], g["pp_j"])):
@@ -272,48 +291,56 @@ def _ratio(err, S):
 
 
 def check(X, blocks, chi2=None, s_pp=None, s_pl=None, tag=""):
-    """asserts the bound on every entry of the six arrays, on the chi2 total and on the per-edge s; returns the worst err / (u S) per array"""
+    """asserts the bound on every entry of the six arrays (blocks = None: there is no export, as on a grown plan), on the chi2 total and on
+    the per-edge s; returns the worst err / (u S) per array"""
     worst = {}
-    for k in ARRAYS:
-        r = _ratio(_err(blocks[k], X.val[k]), X.S[k]); c = C(X.n[k], X.robust)
+    for k in ARRAYS if blocks is not None else ():
+        r = _ratio(_err(blocks[k], X.val[k]), X.S[k]); c = X.bound(k)
         worst[k] = float(r.max()) if len(r) else 0.0
         bad = np.flatnonzero(r > c)
         assert not len(bad), (tag, k, "entry", int(bad[0]) // WIDTH[k], int(bad[0]) % WIDTH[k], "err / (u S)", float(r[bad[0]]), "C", float(c[bad[0]]), "n", int(X.n[k][bad[0]]))
     if chi2 is not None:
         r = float(_ratio(_err([chi2], [X.chi2]), np.array([X.chi2_S]))[0]); worst["chi2"] = r
-        assert r <= C(X.chi2_n, X.robust), (tag, "chi2", r, float(C(X.chi2_n, X.robust)))
+        assert r <= X.chi2_bound(), (tag, "chi2", r, float(X.chi2_bound()))
     for name, got, ex, S in (("s_pp", s_pp, X.s_pp, X.S_s_pp), ("s_pl", s_pl, X.s_pl, X.S_s_pl)):
         if got is not None:
             r = _ratio(_err(got, ex), np.asarray(S)); worst[name] = float(r.max()) if len(r) else 0.0
-            assert np.all(r <= C(1)), (tag, name, int(np.argmax(r)), float(r.max()), float(C(1)))
+            c = 2.0 * (X.L_s_pl + 1.0) if name == "s_pl" and X.L_s_pl is not None else np.full(len(r), float(C(1)))
+            bad = np.flatnonzero(r > c)
+            assert not len(bad), (tag, name, "edge", int(bad[0]), "err / (u S)", float(r[bad[0]]), "C", float(c[bad[0]]))
     return worst
 
 
-def check_can_fail(X, blocks, chi2=None, tag=""):
+def check_can_fail(X, blocks, chi2=None, tag="", side=None):
     """the two-sided half: in every array the entry with the largest S gets one contributing edge's term (its largest) times (1 + 1e-9) in the
     reference, and `blocks` must then violate the bound there.  Where cancellation makes 2 C u S of that entry exceed 1e-9 |term| no fp64
     evaluation can tell the two references apart (kilometre coordinates: S of a theta-theta entry is 1e8 times the entry); the check then moves
     to the entry with the largest S at which it can, and says so in what it returns: {array: (flat index, perturbed err / (u S), C, moved)},
-    None for an array (or for chi2, one number) in which 1e-9 of a term can show nowhere — the callers assert where that is allowed."""
+    None for an array (or for chi2, one number) in which 1e-9 of a term can show nowhere — the callers assert where that is allowed.
+    side: the tag of a side pass ("polar", "prior"): the perturbed term is then one of that pass's own, and only arrays that hold such terms
+    are reported."""
     out = {}
     for k in ARRAYS:
-        if not X.terms[k]:
+        mine = {idx: [t for t, g in zip(ts, X.tags[k][idx]) if side is None or g == side] for idx, ts in X.terms[k].items()}
+        mine = {idx: ts for idx, ts in mine.items() if ts}
+        if not mine:
             continue
-        c = C(X.n[k], X.robust)
+        c = X.bound(k)
         big = np.zeros(len(X.S[k]))
-        for idx, ts in X.terms[k].items():
+        for idx, ts in mine.items():
             big[idx] = float(max(abs(t) for t in ts))
         can = REL * big > 2 * c * U * X.S[k]
         if not can.any():
             out[k] = None; continue
         first = int(np.argmax(X.S[k])); idx = first if can[first] else int(np.argmax(np.where(can, X.S[k], -1.0)))
-        t = max(X.terms[k][idx], key=abs)
+        t = max(mine[idx], key=abs)
         got = mpf(float(np.asarray(blocks[k], dtype=np.float64).reshape(-1)[idx]))
         r = float(abs(got - (X.val[k][idx] + REL * t))) / (U * X.S[k][idx])
         assert r > c[idx], (tag, k, idx, "a term off by 1e-9 stays inside the bound", r, float(c[idx]))
         out[k] = (idx, r, float(c[idx]), idx != first)
-    if chi2 is not None and X.chi2_terms:
-        t = max(X.chi2_terms, key=abs); c = float(C(X.chi2_n, X.robust))
+    mine = [t for t, g in zip(X.chi2_terms, X.chi2_tags) if side is None or g == side]
+    if chi2 is not None and mine:
+        t = max(mine, key=abs); c = float(X.chi2_bound())
         if REL * float(abs(t)) > 2 * c * U * X.chi2_S:
             r = float(abs(mpf(float(chi2)) - (X.chi2 + REL * t))) / (U * X.chi2_S)
             assert r > c, (tag, "chi2", "a term off by 1e-9 stays inside the bound", r, c)
