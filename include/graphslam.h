@@ -260,7 +260,7 @@ int  gs_get_stats(gs_graph *g, gs_stats *stats);      /* plan statistics after i
  * did not arrive with one launch per level either, GS_ERR_NUMERIC for any other failure code; the estimates are the last accepted
  * ones, stats and info are filled (stats->numeric_failure = the code), and the handle is clean for the next call.
  * NOT DONE: pose-window shards (a handle configured with gs_dist_configure(world > 1) returns GS_ERR_INVALID); Marquardt's diagonal
- * scaling, dogleg; a convergence stop rule other than "terminate"; the Slam mirror keeps calling gs_optimize. */
+ * scaling; a convergence stop rule other than "terminate"; the Slam mirror keeps calling gs_optimize. */
 typedef struct gs_lm_params {
     int32_t struct_size;                /* sizeof(gs_lm_params), for ABI evolution                           */
     int32_t max_trials_after_failure;   /* 10 (g2o's default)                                                */
@@ -282,6 +282,63 @@ typedef struct gs_lm_info {
 int  gs_lm_params_default(gs_lm_params *p);
 int  gs_optimize_lm(gs_graph *g, int32_t iterations, const gs_lm_params *p /* NULL: defaults */,
                     gs_stats *stats /* may be NULL */, gs_lm_info *info /* may be NULL */);
+
+/* ---- Powell's dogleg -----------------------------------------------------------
+ * gs_optimize_dogleg <- g2o OptimizationAlgorithmDogleg, the third algorithm at the reference's call site (src/slam.cpp:61).  g2o is not
+ * part of this project's checkers: the rule is restated from g2o's published text and is not pinned against a g2o build.  State: the
+ * trust radius delta (initial_delta at the start).  All vectors are over the free scalars.  Per iteration, at the accepted estimates x:
+ *   1. chi_old = chi2(x) (with a robust kernel set: the sum of rho(s)); H and b linearised at x.
+ *   2. steepest descent: alpha = (b^T b) / (b^T H b), h_sd = alpha b.  (Not g2o's: alpha = 0 when b^T H b is not finite or not > 0.)
+ *   3. h_gn = the Gauss-Newton step: the factorisation and back-solve of gs_iterate, no damping.
+ *   4. trials, at most max_trials_after_failure:
+ *        |h_gn| < delta:       h_dl = h_gn                                (GS_DOGLEG_GN)
+ *        else |h_sd| > delta:  h_dl = (delta / |h_sd|) h_sd               (GS_DOGLEG_SD)
+ *        else:                 h_dl = h_sd + beta a                       (GS_DOGLEG_DL)  with a = h_gn - h_sd, c = h_sd^T a, q = a^T a,
+ *                              m = delta^2 - |h_sd|^2, beta = (-c + sqrt(c^2 + q m)) / q if c <= 0, else m / (c + sqrt(c^2 + q m))
+ *      gain = -h_dl^T (H h_dl) + 2 b^T h_dl (|gain| < 1e-12: 1e-12); x_try = x [+] h_dl (the update of gs_iterate, angle normalisation
+ *      included); chi_new = chi2(x_try); rho = (chi_old - chi_new) / gain.  rho > 0 and chi_new finite: ACCEPT; otherwise x is put back
+ *      bit for bit.  Either way rho > 0.75 sets delta = max(delta, 3 |h_dl|) and rho < 0.25 halves delta.
+ *   5. every trial of an iteration rejected: the call ends ("terminate"), the estimates are the last accepted ones.
+ * The whole call runs on the handle's stream with no host decision inside a trial, as gs_optimize_lm does: a trial is the launch sequence
+ * of gs_iterate with the two Hessian-vector products (H b and H h_dl: the kernel behind gs_multiply_hessian), six vertex-parallel
+ * kernels and the chi2 pass around it; delta, the counters and the verdict live in a device record the host reads between chunks of
+ * trials.  A retrial runs the whole sequence again at the restored estimates.  gs_export_delta afterwards returns h_dl of the last trial.
+ * Returns the number of ACCEPTED iterations; a call that ends by "terminate" returns the count so far with info->terminated = 1 — not an
+ * error.  gs_stats: chi2_initial / chi2_final are the values at the first / last accepted point, iterations the accepted count.  Works
+ * with robust kernels, priors, polar edges, inactive edges, grown plans, factor_variant 3 and 4, both linearisation paths; makes the
+ * marginals stale like an iteration; leaves no failure, stop or dogleg state behind that gates a later gs_iterate / gs_optimize /
+ * gs_optimize_lm.  A flag timeout of a whole-tree launch is repaired by the per-level fallback as in gs_optimize.
+ * Errors: iterations < 0, an initial_delta that is not finite or <= 0, max_trials_after_failure < 1: GS_ERR_INVALID; a host-only handle
+ * GS_ERR_NO_DEVICE.  A zero pivot in the Gauss-Newton solve is g2o's "Fail": the call ends with GS_ERR_NUMERIC (GS_ERR_TIMEOUT when a
+ * front's flag did not arrive with one launch per level either), the estimates are the last accepted ones, stats and info are filled and
+ * the handle is clean for the next call.
+ * NOT DONE: g2o's lambda-damping of H when it was not positive definite; reuse of h_gn across the retrials of an iteration (a retrial
+ * factorises again); pose-window shards (a handle configured with gs_dist_configure(world > 1) returns GS_ERR_INVALID); the Slam mirror
+ * keeps calling gs_optimize. */
+#define GS_DOGLEG_GN 0
+#define GS_DOGLEG_SD 1
+#define GS_DOGLEG_DL 2
+typedef struct gs_dogleg_params {
+    int32_t struct_size;                /* sizeof(gs_dogleg_params), for ABI evolution                       */
+    int32_t max_trials_after_failure;   /* 100 (g2o's default)                                               */
+    double  initial_delta;              /* 1e4 (g2o's default)                                               */
+} gs_dogleg_params;
+typedef struct gs_dogleg_info {
+    int32_t struct_size;
+    int32_t iterations;                 /* accepted                                                          */
+    int32_t trials, rejected;           /* trials run, trials rejected                                       */
+    int32_t terminated;                 /* 1: an iteration used up its trials without an accepted step       */
+    int32_t reserved;
+    int32_t n_gn, n_sd, n_dl;           /* accepted steps by kind                                            */
+    double  delta_initial, delta_final; /* of the first trial; the one a next trial would have used          */
+    /* per ITERATION (the first 64): chi2 at the accepted point the iteration started from, delta and kind (GS_DOGLEG_*) of its accepted
+       (or last) trial, its number of trials.  A call that terminates has one more entry than accepted iterations. */
+    double  chi2[64], delta[64];
+    int32_t n_trials[64], step_kind[64];
+} gs_dogleg_info;
+int  gs_dogleg_params_default(gs_dogleg_params *p);
+int  gs_optimize_dogleg(gs_graph *g, int32_t iterations, const gs_dogleg_params *p /* NULL: defaults */,
+                        gs_stats *stats /* may be NULL */, gs_dogleg_info *info /* may be NULL */);
 
 /* ---- robust kernels ---------------------------------------------------------
  * <- g2o OptimizableGraph::Edge::setRobustKernel with RobustKernelHuber / RobustKernelCauchy (the reference never sets one; the
@@ -452,7 +509,15 @@ int  gs_get_polar_edges(gs_graph *g, int32_t capacity, int32_t *out_observation_
  *      Hpp_diag [N*9], Hll_diag [M*4], Hpp_off [Epp*9] (= A^T Omega B), Hpl [Epl*6] (= A^T Omega B,
  *      3x2 row-major), b_pose [N*3], b_lm [M*2].  Any pointer may be NULL.
  * gs_export_delta: the last solve's increment, per vertex in insertion order
- *      (zeros for fixed vertices): dpose [N*3], dlm [M*2]. */
+ *      (zeros for fixed vertices): dpose [N*3], dlm [M*2].
+ * gs_multiply_hessian: y = H v on the device, H the system gs_export_system would return (the last linearisation as it lies in HBM:
+ *      robust weights, priors, polar and inactive edges as they went in, the lambda of a preceding gs_optimize_lm trial on the diagonal
+ *      included) — and it works on a grown plan, which gs_export_system refuses.  v and y per vertex in insertion order; rows and
+ *      columns of fixed vertices are zero: y is 0 there and v is not read there.  Either output may be NULL.  Changes no state; a
+ *      handle that never calls it (or gs_optimize_dogleg) allocates and launches nothing for it.
+ *      Errors: a null v, or a v entry on a free vertex that is not finite: GS_ERR_INVALID; a sharded handle GS_ERR_INVALID; a
+ *      host-only handle GS_ERR_NO_DEVICE; nothing linearised since the last structure phase or growth step (or the graph changed
+ *      since): GS_ERR_NOT_INITIALIZED. */
 int  gs_linearize(gs_graph *g);
 int  gs_time_linearize(gs_graph *g, int32_t reps, double *out_ms_per_pass);
 
@@ -461,6 +526,8 @@ int  gs_export_system(gs_graph *g, double *Hpp_diag, double *Hll_diag, double *H
                       double *Hpl, double *b_pose, double *b_lm,
                       int32_t *odometry_edge_order, int32_t *observation_edge_order);
 int  gs_export_delta(gs_graph *g, double *dpose, double *dlm);
+int  gs_multiply_hessian(gs_graph *g, const double *v_pose /* [n_poses*3] */, const double *v_lm /* [n_lms*2] */,
+                         double *out_pose, double *out_lm);   /* insertion order, either output may be NULL */
 /* per-phase timing of `reps` full iterations (events on the stream); fills stats->ms_* with
  * per-iteration means.  Estimates are restored afterwards. */
 int  gs_time_iterations(gs_graph *g, int32_t reps, gs_stats *stats);

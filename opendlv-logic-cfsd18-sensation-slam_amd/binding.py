@@ -118,6 +118,30 @@ class LmInfo(C.Structure):
         return o
 
 
+class DoglegParams(C.Structure):
+    """gs_dogleg_params (include/graphslam.h)"""
+    _fields_ = [("struct_size", C.c_int32), ("max_trials_after_failure", C.c_int32), ("initial_delta", C.c_double)]
+
+
+DOGLEG_KINDS = ("GN", "SD", "DL")                           # GS_DOGLEG_GN / _SD / _DL
+
+
+class DoglegInfo(C.Structure):
+    """gs_dogleg_info: counters of a gs_optimize_dogleg call and its per-iteration history (the first 64 iterations)"""
+    _fields_ = [("struct_size", C.c_int32), ("iterations", C.c_int32), ("trials", C.c_int32), ("rejected", C.c_int32),
+                ("terminated", C.c_int32), ("reserved", C.c_int32), ("n_gn", C.c_int32), ("n_sd", C.c_int32), ("n_dl", C.c_int32),
+                ("delta_initial", C.c_double), ("delta_final", C.c_double),
+                ("chi2", C.c_double * 64), ("delta", C.c_double * 64), ("n_trials", C.c_int32 * 64), ("step_kind", C.c_int32 * 64)]
+
+    def as_dict(self):
+        """scalars as they are; the histories as arrays cut to the iterations that ran (one more than accepted after a terminate)"""
+        n = min(self.iterations + (1 if self.terminated else 0), 64)
+        o = {k: getattr(self, k) for k in ("iterations", "trials", "rejected", "terminated", "n_gn", "n_sd", "n_dl", "delta_initial", "delta_final")}
+        o["chi2"] = np.array(self.chi2[:n]); o["delta"] = np.array(self.delta[:n])
+        o["n_trials"] = np.array(self.n_trials[:n], dtype=np.int32); o["step_kind"] = np.array(self.step_kind[:n], dtype=np.int32)
+        return o
+
+
 def declared_symbols(debug=True):
     """Every function name include/graphslam.h (and, debug=True, include/graphslam_debug.h) declares."""
     names = set()
@@ -256,6 +280,10 @@ def lib():
     if hasattr(L, "gs_optimize_lm"):                       # (a tuning build of an older tree loaded through GS_LIB may predate Levenberg-Marquardt)
         L.gs_lm_params_default.argtypes = [C.POINTER(LmParams)]
         L.gs_optimize_lm.argtypes = [vp, C.c_int32, C.POINTER(LmParams), C.POINTER(Stats), C.POINTER(LmInfo)]
+    if hasattr(L, "gs_optimize_dogleg"):                   # (the same for the dogleg and the Hessian-vector product)
+        L.gs_dogleg_params_default.argtypes = [C.POINTER(DoglegParams)]
+        L.gs_optimize_dogleg.argtypes = [vp, C.c_int32, C.POINTER(DoglegParams), C.POINTER(Stats), C.POINTER(DoglegInfo)]
+        L.gs_multiply_hessian.argtypes = [vp, _dp, _dp, _dp, _dp]
     if hasattr(L, "gs_add_pose_prior"):                    # (a tuning build of an older tree loaded through GS_LIB may predate the prior edges)
         for name in ("gs_add_pose_prior", "gs_add_pose_xy_prior", "gs_add_landmark_prior"):
             getattr(L, name).argtypes = [vp, C.c_int32, _dp, _dp]
@@ -396,6 +424,21 @@ def lm_params(**kw):
     for k, v in kw.items():
         if k not in ("max_trials_after_failure", "initial_lambda", "tau"):
             raise AttributeError("gs_lm_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def dogleg_params(**kw):
+    """gs_dogleg_params_default with the named fields replaced (max_trials: short for max_trials_after_failure)"""
+    p = DoglegParams()
+    rc = lib().gs_dogleg_params_default(C.byref(p))
+    if rc < 0:
+        raise GsError(rc, (lib().gs_last_error() or b"").decode())
+    if "max_trials" in kw:
+        kw["max_trials_after_failure"] = kw.pop("max_trials")
+    for k, v in kw.items():
+        if k not in ("max_trials_after_failure", "initial_delta"):
+            raise AttributeError("gs_dogleg_params has no field %r" % k)
         setattr(p, k, v)
     return p
 
@@ -544,6 +587,15 @@ class Graph:
         done = self._check(self.L.gs_optimize_lm(self.h, int(iterations), C.byref(p), C.byref(st), C.byref(info)))
         return done, st, info.as_dict()
 
+    def optimize_dogleg(self, iterations=10, **params):
+        """gs_optimize_dogleg (Powell's dogleg, g2o's rule): params = fields of gs_dogleg_params (max_trials_after_failure or max_trials,
+        initial_delta); returns (accepted iterations, Stats, gs_dogleg_info as a dict)"""
+        p = dogleg_params(**params)
+        st = Stats(); st.struct_size = C.sizeof(Stats)
+        info = DoglegInfo(); info.struct_size = C.sizeof(DoglegInfo)
+        done = self._check(self.L.gs_optimize_dogleg(self.h, int(iterations), C.byref(p), C.byref(st), C.byref(info)))
+        return done, st, info.as_dict()
+
     def debug_fail_at_iteration(self, k, code=1):
         self._check(self.L.gs_debug_fail_at_iteration(self.h, int(k), int(code)))
 
@@ -602,6 +654,12 @@ class Graph:
     def export_delta(self):
         dp = np.zeros((self.n_poses, 3)); dl = np.zeros((self.n_landmarks, 2))
         self._check(self.L.gs_export_delta(self.h, _d(dp), _d(dl))); return dp, dl
+
+    def multiply_hessian(self, v_pose, v_lm):
+        """gs_multiply_hessian: (H v) per pose [N,3] and per landmark [M,2], H the system of the last linearisation on the device"""
+        vp = _f64(v_pose, (self.n_poses, 3)); vl = _f64(v_lm, (self.n_landmarks, 2))
+        yp = np.zeros_like(vp); yl = np.zeros_like(vl)
+        self._check(self.L.gs_multiply_hessian(self.h, _d(vp), _d(vl), _d(yp), _d(yl))); return yp, yl
 
     # ---- marginal covariances (gs_compute_marginals: selected inversion of the factor at the current estimates)
     def compute_marginals(self):

@@ -46,7 +46,7 @@ static void dev_release(gs_graph *g, bool keep) {
     else for (auto &c : g->allocs) { c.in_use = false; if (pool_poison(g) && g->stream) hipMemsetAsync(c.p, 0xFF, c.size, g->stream); }
     g->pool_base = nullptr; g->pool_size = g->pool_off = 0; g->pool_next = 0; g->pool_total = 0;
     g->d = DevGraph(); apply_robust(g);
-    g->dev_valid = false;
+    g->dev_valid = false; g->linearised = false;
     g->room = gs_graph::GrowRoom(); g->d_bf = g->d_xrow = g->d_patch = g->d_list = nullptr;
     g->marg = gs_graph::Marginals();                                // its buffers were pool memory of the plan
     g->sched = Schedule(); for (auto &t : g->d_wg) t = nullptr;     // ... and so were the schedule's tables
@@ -179,6 +179,7 @@ extern "C" int gs_destroy(gs_graph *g) {
     hipStreamSynchronize(g->stream);
     dev_free_all(g);
     if (g->lm.mem) hipFree(g->lm.mem);
+    if (g->dl.mem) hipFree(g->dl.mem);
     side_release(g);
     gs_dist_comm_release(g);
     gs_frontend_release(g);

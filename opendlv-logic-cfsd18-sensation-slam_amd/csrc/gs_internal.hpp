@@ -9,6 +9,7 @@
 #include "../../include/graphslam.h"
 #include "../../include/graphslam_debug.h"
 #include "gs_device.hpp"
+#include "gs_dogleg.hpp"
 #include "gs_edge_mask.hpp"
 #include "gs_host.hpp"
 #include "gs_lm.hpp"
@@ -41,6 +42,7 @@ struct gs_graph {
     std::vector<DevChunk> allocs;
     char *pool_base = nullptr; size_t pool_size = 0, pool_off = 0, pool_next = 0, pool_total = 0;     // pool_total: bytes of the chunks in use
     bool dev_valid = false;                 // device mirrors the host graph + plan
+    bool linearised = false;                // the H arena holds a linearisation of the CURRENT plan (enqueue_linearize ran since the last upload / growth step): gs_multiply_hessian
     bool dev_estimates_newer = false;       // estimates in HBM are ahead of the host copy
     uint64_t dev_estimate_version = 0;
     hipStream_t stream = nullptr; bool own_stream = false;
@@ -94,6 +96,9 @@ struct gs_graph {
     // gs_optimize_lm: the device state record, history, base copy of the estimates and reduction partials (gs_lm.hpp) — one allocation of
     // the handle's own, grow-only, sized for cap_p poses / cap_l landmarks (tail included)
     struct Lm { gs::LmDev dev{}; void *mem = nullptr; size_t cap_p = 0, cap_l = 0; gs::LmState host[2]{}; } lm;
+    // gs_optimize_dogleg and gs_multiply_hessian: the device state record, history, base copy of the estimates, the vertex-order vectors
+    // and the reduction partials (gs_dogleg.hpp) — one allocation of the handle's own, grow-only, made by the first call of either
+    struct Dogleg { gs::DlDev dev{}; void *mem = nullptr; size_t cap_p = 0, cap_l = 0; gs::DlState host[2]{}; } dl;
     // prior edges (gs_prior.hpp): the priors as added, the grouped tables, and their device copy — one allocation of the handle's own,
     // grow-only; uploaded whole by prior_sync when the priors or the plan changed.  dev stays empty while there is no prior on a free vertex
     struct Prior { gs::PriorStore store; gs::PriorTables tab; gs::PriorSync sync; gs::PriorDev dev{}; gs::DevArena arena;

@@ -14,6 +14,7 @@
 //                            slot (the fronts sum the landmark's run of slots; k_linearize_tail adds there too)
 //   free tail landmark       t_Hll_diag planes 0, 2 with stride tcapM
 #include "gs_lm.hpp"
+#include "gs_blocksum_dev.hpp"      // lm_block_sum / lm_block_max: the two-stage fixed-order reductions (shared with gs_dogleg.hip)
 
 #include <algorithm>
 #include <cmath>
@@ -21,38 +22,6 @@
 namespace gs {
 
 static constexpr int LM_REC = 8;        // doubles per lm_part record (gs_kernels.hip)
-
-__device__ __forceinline__ double lm_wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ __forceinline__ double lm_wave_max(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
-    return v;
-}
-// fixed-order sum / max over the 256 threads, the result in EVERY thread (red: 5 doubles of LDS)
-__device__ __forceinline__ double lm_block_sum(double v, double *red) {
-    v = lm_wave_sum(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) red[4] = ((red[0] + red[1]) + red[2]) + red[3];
-    __syncthreads();
-    const double r = red[4];
-    __syncthreads();
-    return r;
-}
-__device__ __forceinline__ double lm_block_max(double v, double *red) {
-    v = lm_wave_max(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) red[4] = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-    __syncthreads();
-    const double r = red[4];
-    __syncthreads();
-    return r;
-}
 
 // the two diagonal scalars of free landmark l (any path), as the fronts see them
 __device__ __forceinline__ void lm_diag_of(const DevGraph &d, int l, double &h00, double &h11) {

@@ -1,8 +1,9 @@
 // gs_solve.cpp — the solver launches of one iteration and the entry points that run iterations (gs_iterate, gs_optimize*,
-// gs_optimize_lm), with the timing and export hooks.
+// gs_optimize_lm, gs_optimize_dogleg), with the timing and export hooks (gs_export_system, gs_multiply_hessian, ...).
 #include "../../include/graphslam.h"
 #include "../../include/graphslam_debug.h"
 #include "gs_private.hpp"
+#include "gs_hmul.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -35,6 +36,7 @@ void enqueue_factor_levels(gs_graph *g, const LevelSet &ls, int base, int mode) 
 // sum (fused kernel), or chi2[0] (gather kernels: k_reduce_chi2 has totalled it); the polar pass adds its total to the same slot.  A handle
 // without priors and without polar edges launches what it always did
 void enqueue_linearize(gs_graph *g, hipEvent_t start, hipEvent_t stop) {
+    g->linearised = true;
     launch_linearize(g->d, g->stream, start, stop);
     launch_linearize_tail(g->d, g->stream);                          // a grown plan's tail (no launch without one)
     const bool fused = g->d.n_wtiles > 0;
@@ -308,6 +310,123 @@ extern "C" int gs_optimize_lm(gs_graph *g, int32_t iterations, const gs_lm_param
     return S.iterations;
 }
 
+// ------------------------------------------------------------------ Powell's dogleg (gs_dogleg.hpp: trial sequence, device record)
+extern "C" int gs_dogleg_params_default(gs_dogleg_params *p) {
+    if (!p) return fail(GS_ERR_INVALID, "null params");
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (int32_t)sizeof(*p); p->max_trials_after_failure = 100; p->initial_delta = 1e4;
+    return GS_OK;
+}
+// the handle's dogleg / Hessian-product buffers: one allocation of its own (not pool memory: it outlives the plans), grow-only
+static int dl_reserve(gs_graph *g) {
+    auto &W = g->dl; const size_t NP = (size_t)(g->d.N + g->d.tN), ML = (size_t)(g->d.M + g->d.tM);
+    if (!W.mem || NP > W.cap_p || ML > W.cap_l) {
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        if (W.mem) { hipFree(W.mem); W.mem = nullptr; }
+        const size_t cp = NP + 64, cl = ML + 64, cpart = (cp + cl + 255) / 256 + 1;
+        size_t total = 0;
+        auto take = [&total](size_t b) { const size_t o = total; total += (b + 255) & ~(size_t)255; return o; };
+        const size_t o_state = take(2 * sizeof(DlState)), o_hc = take(64 * 8), o_hd = take(64 * 8), o_ht = take(64 * 4), o_hk = take(64 * 4),
+                     o_bp = take(cp * 24), o_bc = take(cp * 16), o_bl = take(cl * 16), o_part = take(DL_NPART * cpart * 8);
+        size_t o_vp[4], o_vl[4];
+        for (int k = 0; k < 4; ++k) { o_vp[k] = take(cp * 24); o_vl[k] = take(cl * 16); }
+        HIP_TRY(hipMalloc(&W.mem, total));
+        char *b = (char *)W.mem; DlDev &D = W.dev;
+        D.state = (DlState *)(b + o_state); D.hist_chi2 = (double *)(b + o_hc); D.hist_delta = (double *)(b + o_hd);
+        D.hist_trials = (int32_t *)(b + o_ht); D.hist_kind = (int32_t *)(b + o_hk);
+        D.base_pose = (double *)(b + o_bp); D.base_cs = (double *)(b + o_bc); D.base_lm = (double *)(b + o_bl);
+        D.part = (double *)(b + o_part); D.part_stride = (int32_t)cpart;
+        double **vp[4] = {&D.b_pose, &D.Hb_pose, &D.h_pose, &D.Hh_pose}, **vl[4] = {&D.b_lm, &D.Hb_lm, &D.h_lm, &D.Hh_lm};
+        for (int k = 0; k < 4; ++k) { *vp[k] = (double *)(b + o_vp[k]); *vl[k] = (double *)(b + o_vl[k]); }
+        W.cap_p = cp; W.cap_l = cl; }
+    W.dev.n_part = (int32_t)lm_grid(g->d);
+    return GS_OK;
+}
+// one trial, asynchronous: today's linearise / factor / back-solve / update launches in today's launch modes, with the dogleg kernels and
+// the two Hessian products around them.  Both products run before the chi2 pass (on a grown plan it is a full linearisation)
+static void enqueue_dogleg_trial(gs_graph *g, int par) {
+    const DlDev &dl = g->dl.dev; const bool tree = g->d.tree != 0;
+    ++g->d.iter;
+    enqueue_linearize(g);
+    launch_dl_begin(g->d, dl, g->stream);
+    launch_hmul(g->d, dl.b_pose, dl.b_lm, dl.Hb_pose, dl.Hb_lm, g->stream);
+    launch_dl_dot(g->d, dl, g->stream);
+    enqueue_factor_levels(g, g->sched.own, 0, 0);
+    { Launcher L{g}; walk_finish_factor(g->sched, tree, L); walk_finish_backsolve(g->sched, tree, L); }     // (no shared top on a single device), back-solve: xe = h_gn
+    launch_dl_norms(g->d, dl, g->stream);
+    launch_dl_blend(g->d, dl, par, g->stream);                       // xe = h_dl
+    launch_hmul(g->d, dl.h_pose, dl.h_lm, dl.Hh_pose, dl.Hh_lm, g->stream);
+    launch_update(g->d, g->stream);
+    g->dev_estimates_newer = true;
+    launch_dl_gain(g->d, dl, par, g->stream);
+    enqueue_chi2(g);                                                 // chi2 at x_try -> chi2[0]
+    launch_dl_step(g->d, dl, par, g->stream);
+}
+extern "C" int gs_optimize_dogleg(gs_graph *g, int32_t iterations, const gs_dogleg_params *params, gs_stats *stats, gs_dogleg_info *info) {
+    if (!g) return fail(GS_ERR_INVALID, "null graph");
+    if (iterations < 0) return fail(GS_ERR_INVALID, "negative iteration count");
+    gs_dogleg_params P; gs_dogleg_params_default(&P);
+    if (params) { std::memcpy(&P, params, std::min<size_t>(sizeof(P), (size_t)std::max(params->struct_size, 0))); P.struct_size = (int32_t)sizeof(P); }
+    if (!std::isfinite(P.initial_delta) || !(P.initial_delta > 0.0)) return fail(GS_ERR_INVALID, "gs_dogleg_params.initial_delta must be finite and > 0");
+    if (P.max_trials_after_failure < 1) return fail(GS_ERR_INVALID, "gs_dogleg_params.max_trials_after_failure must be >= 1");
+    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: the dogleg is not supported on sharded handles");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    rc = ensure_ready(g); if (rc != GS_OK) return rc;
+    if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: the dogleg is not supported on sharded handles");
+    rc = dl_reserve(g); if (rc != GS_OK) return rc;
+    if ((rc = run_begin(g, iterations, true)) != GS_OK) return rc;
+    g->d.conv_tol = -1.0; g->d.hist_slot = -1;
+    DlState *H = g->dl.host; std::memset(H, 0, 2 * sizeof(DlState));
+    DlState &S0 = H[0];
+    S0.delta = P.initial_delta; S0.delta_initial = P.initial_delta; S0.budget = iterations; S0.max_trials = P.max_trials_after_failure;
+    const DlDev &dl = g->dl.dev;
+    HIP_TRY(hipMemcpyAsync(dl.state, H, 2 * sizeof(DlState), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemsetAsync(dl.hist_chi2, 0, 64 * sizeof(double), g->stream));
+    HIP_TRY(hipMemsetAsync(dl.hist_delta, 0, 64 * sizeof(double), g->stream));
+    HIP_TRY(hipMemsetAsync(dl.hist_trials, 0, 64 * sizeof(int32_t), g->stream));
+    HIP_TRY(hipMemsetAsync(dl.hist_kind, 0, 64 * sizeof(int32_t), g->stream));
+    hipEventRecord(g->ev[5], g->stream);
+    // Chunks of trials, the device record read in between (one host round trip per chunk), as in gs_optimize_lm: never more trials than
+    // iterations still to accept, the first trial alone until a whole-tree launch of this plan has come back clean
+    DlState S = S0; int seq = 0; RunState R; const int32_t *ff = R.ff;
+    while (iterations > 0 && !S.done && S.iterations < iterations) {
+        const bool alone = S.trials == 0 && !(g->tree_proven && g->d.tree);
+        const int n = alone ? 1 : std::min(iterations - S.iterations, 8);
+        for (int k = 0; k < n; ++k, ++seq) enqueue_dogleg_trial(g, seq & 1);
+        HIP_TRY(hipMemcpyAsync(&H[1], dl.state + (seq & 1), sizeof(DlState), hipMemcpyDeviceToHost, g->stream));
+        const int next = run_chunk_done(g, R); if (next < 0) return next;
+        S = H[1];
+        if (next == RUN_STOP) break;                                // (RUN_RERUN: the trials behind the timeout were no-ops: the loop runs them again, one launch per level)
+    }
+    HIP_TRY(hipMemsetAsync(g->d.fail + 1, 0, 2 * sizeof(int32_t), g->stream));     // the update count and the stop flag must not gate later gs_iterate calls
+    if (S.trials == 0 && (stats || info || g->cfg.verbose)) enqueue_chi2(g);     // nothing ran: chi2 at the estimates as they are
+    hipEventRecord(g->ev[6], g->stream);
+    double chi_here = 0.0, hc[64], hd[64]; int32_t ht[64], hk[64];
+    HIP_TRY(hipMemcpyAsync(&chi_here, g->d.chi2, sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(hc, dl.hist_chi2, sizeof(hc), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(hd, dl.hist_delta, sizeof(hd), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(ht, dl.hist_trials, sizeof(ht), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(hk, dl.hist_kind, sizeof(hk), hipMemcpyDeviceToHost, g->stream));
+    float ms;
+    if ((rc = run_end(g, "dogleg iteration", &ms)) != GS_OK) return rc;
+    const double chi_first = S.trials > 0 ? hc[0] : chi_here, chi_last = S.trials > 0 ? S.chi_base : chi_here;
+    static const char *const kind_name[3] = {"GN", "SD", "DL"};
+    if (g->cfg.verbose) for (int it = 0; it < std::min(S.iterations, 64); ++it)
+        std::fprintf(stderr, "iteration= %d\t chi2= %.6f\t edges= %d\t schur= 0\t delta= %.6g\t kind= %s\t tries= %d\n", it,
+                     it + 1 < S.iterations && it + 1 < 64 ? hc[it + 1] : chi_last, g->h.n_pp() + g->h.n_pl(), hd[it], kind_name[hk[it] % 3], ht[it]);
+    run_stats(g, stats, S.iterations, ff[0], R.first_failure, chi_first, chi_last, ms);
+    if (info) { std::memset(info, 0, sizeof(*info)); info->struct_size = (int32_t)sizeof(*info);
+        info->iterations = S.iterations; info->trials = S.trials; info->rejected = S.rejected; info->terminated = S.terminated;
+        info->n_gn = S.n_kind[DL_GN]; info->n_sd = S.n_kind[DL_SD]; info->n_dl = S.n_kind[DL_DL];
+        info->delta_initial = S.delta_initial; info->delta_final = S.delta;
+        std::memcpy(info->chi2, hc, sizeof(hc)); std::memcpy(info->delta, hd, sizeof(hd));
+        std::memcpy(info->n_trials, ht, sizeof(ht)); std::memcpy(info->step_kind, hk, sizeof(hk)); }
+    if (ff[0]) { rc = reset_failure(g); if (rc != GS_OK) return rc;
+        if (ff[0] == 2) return fail(GS_ERR_TIMEOUT, "a front's completion flag did not arrive in time, with one launch per level as well (estimates = last accepted point)");
+        return fail(GS_ERR_NUMERIC, "the Gauss-Newton solve of a dogleg trial failed (zero pivot: H is singular; estimates = last accepted point)"); }
+    return S.iterations;
+}
+
 extern "C" int gs_chi2(gs_graph *g, double *out) {
     if (!g || !out) return fail(GS_ERR_INVALID, "null argument");
     int rc = ensure_ready(g); if (rc != GS_OK) return rc;
@@ -390,6 +509,34 @@ extern "C" int gs_export_system(gs_graph *g, double *Hpp_diag, double *Hll_diag,
     if (b_lm) for (size_t l = 0; l < M; ++l) for (int c = 0; c < 2; ++c) b_lm[2 * l + c] = t5[c * M + l];
     if (pp_order) std::memcpy(pp_order, g->plan.pp_order.data(), g->plan.pp_order.size() * sizeof(int32_t));
     if (pl_order) for (size_t k = 0; k < Epl; ++k) pl_order[k] = (int32_t)k;                 // exported in insertion order
+    return GS_OK;
+}
+// y = H v with the H of the last linearisation, as it lies in HBM (gs_hmul.hpp); changes no state of the handle
+extern "C" int gs_multiply_hessian(gs_graph *g, const double *v_pose, const double *v_lm, double *out_pose, double *out_lm) {
+    if (!g) return fail(GS_ERR_INVALID, "null graph");
+    const HostGraph &h = g->h; const size_t NP = (size_t)h.n_poses(), ML = (size_t)h.n_lms();
+    if ((NP > 0 && !v_pose) || (ML > 0 && !v_lm)) return fail(GS_ERR_INVALID, "null vector");
+    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: the Hessian product is not supported on sharded handles");
+    // fixed vertices: their entries of v are ignored (sent as zeros); every other entry must be finite
+    std::vector<double> vp(3 * NP), vl(2 * ML);
+    for (size_t p = 0; p < NP; ++p) for (int c = 0; c < 3; ++c) { const double x = h.pose_fixed[p] ? 0.0 : v_pose[3 * p + c];
+        if (!std::isfinite(x)) return fail(GS_ERR_INVALID, "v_pose holds a value that is not finite"); vp[3 * p + c] = x; }
+    for (size_t l = 0; l < ML; ++l) for (int c = 0; c < 2; ++c) { const double x = h.lm_fixed[l] ? 0.0 : v_lm[2 * l + c];
+        if (!std::isfinite(x)) return fail(GS_ERR_INVALID, "v_lm holds a value that is not finite"); vl[2 * l + c] = x; }
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (!g->dev_valid || !g->linearised) return fail(GS_ERR_NOT_INITIALIZED, "nothing linearised yet (since the last structure phase or growth step)");
+    if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: the Hessian product is not supported on sharded handles");
+    if (g->plan_version != h.structure_version || (size_t)(g->d.N + g->d.tN) != NP || (size_t)(g->d.M + g->d.tM) != ML)
+        return fail(GS_ERR_NOT_INITIALIZED, "the graph changed since the last linearisation");
+    if ((rc = dl_reserve(g)) != GS_OK) return rc;
+    const DlDev &dl = g->dl.dev;
+    if (NP) HIP_TRY(hipMemcpyAsync(dl.b_pose, vp.data(), vp.size() * sizeof(double), hipMemcpyHostToDevice, g->stream));
+    if (ML) HIP_TRY(hipMemcpyAsync(dl.b_lm, vl.data(), vl.size() * sizeof(double), hipMemcpyHostToDevice, g->stream));
+    launch_hmul(g->d, dl.b_pose, dl.b_lm, dl.Hb_pose, dl.Hb_lm, g->stream);
+    { const hipError_t e = hipGetLastError(); if (e != hipSuccess) { hipStreamSynchronize(g->stream); return fail(GS_ERR_HIP, std::string("Hessian product: ") + hipGetErrorString(e)); } }
+    if (out_pose && NP) HIP_TRY(hipMemcpyAsync(out_pose, dl.Hb_pose, vp.size() * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    if (out_lm && ML) HIP_TRY(hipMemcpyAsync(out_lm, dl.Hb_lm, vl.size() * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));                        // (vp / vl are host temporaries)
     return GS_OK;
 }
 // per-edge s = e^T W e and weight at the current estimates (k_edge_chi2).  The index table of the kind's edges goes up with the call

@@ -346,7 +346,7 @@ int upload_graph(gs_graph *g, RawUpload &raw) {
     if (raw.th.joinable()) { raw.th.join(); if (raw.rc != GS_OK) return fail(raw.rc, raw.err); }      // a shard's edge streams (up_estimates_and_edges)
     HIP_TRY(hipStreamSynchronize(g->stream));
     U.ut("final sync");
-    g->dev_valid = true; g->dev_estimates_newer = false; g->tree_proven = false;
+    g->dev_valid = true; g->linearised = false; g->dev_estimates_newer = false; g->tree_proven = false;
     ++g->value_uploads;                                              // every edge's own information is on the device again (edge_mask_sync)
     g->dev_estimate_version = h.estimate_version;
     return GS_OK;
@@ -453,7 +453,7 @@ int upload_growth(gs_graph *g, const Growth &gr) {
     // grown front may change its size class).  The old tables stay in the pool until the next full structure phase.
     g->sched = build_schedule(P, g->pos_of_front, d.factor_variant, g->opt.tree != 0, g->opt);
     if ((rc = upload_tables(g)) != GS_OK) return rc;
-    g->tree_proven = false;
+    g->tree_proven = false; g->linearised = false;                  // (the tail arenas hold nothing of the new edges yet)
     g->dev_estimate_version = h.estimate_version;
     return GS_OK;
 }
