@@ -606,6 +606,8 @@ int  gs_get_covariance_block(gs_graph *g, int32_t kind_a, int32_t id_a, int32_t 
 /* ---- front end (A0, A1) ----------------------------------------------------
  * gs_polar_to_xy_batch  <- Slam::Spherical2Cartesian + transformConeToCoG    (src/slam.cpp:637-654, 513-523)
  *      in : az_deg[n], zen_deg[n], dist[n]   out: xy[n*2] (CoG-frame x,y)
+ *      The reference's formula, kept with its quirks: NaN at az == 0 (sign = az / |az|), and next to dist * cos(az) = -lidar_to_cog
+ *      (the cone abeam of the CoG, where asin's argument is 1) NaN or an error of order sqrt(2^-53) * dist in x.
  * gs_cone_to_global_batch <- Slam::coneToGlobal                               (src/slam.cpp:499-510)
  *      in : pose_of_obs[n] index into poses[npose*3]; out: xy_global[n*2]
  * gs_associate_batch    <- association loop of Slam::addConesToMap against a FIXED map
