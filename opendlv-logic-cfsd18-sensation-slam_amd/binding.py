@@ -413,34 +413,29 @@ def dist_unique_id():
     return buf.raw
 
 
-def lm_params(**kw):
-    """gs_lm_params_default with the named fields replaced (max_trials: short for max_trials_after_failure)"""
-    p = LmParams()
-    rc = lib().gs_lm_params_default(C.byref(p))
+def _step_params(cls, default, name, fields, kw):
+    """a step-control method's parameter struct: its defaults with the named fields replaced (max_trials: short for max_trials_after_failure)"""
+    p = cls()
+    rc = default(C.byref(p))
     if rc < 0:
         raise GsError(rc, (lib().gs_last_error() or b"").decode())
     if "max_trials" in kw:
         kw["max_trials_after_failure"] = kw.pop("max_trials")
     for k, v in kw.items():
-        if k not in ("max_trials_after_failure", "initial_lambda", "tau"):
-            raise AttributeError("gs_lm_params has no field %r" % k)
+        if k not in ("max_trials_after_failure",) + fields:
+            raise AttributeError("%s has no field %r" % (name, k))
         setattr(p, k, v)
     return p
+
+
+def lm_params(**kw):
+    """gs_lm_params_default with the named fields replaced (max_trials: short for max_trials_after_failure)"""
+    return _step_params(LmParams, lib().gs_lm_params_default, "gs_lm_params", ("initial_lambda", "tau"), kw)
 
 
 def dogleg_params(**kw):
     """gs_dogleg_params_default with the named fields replaced (max_trials: short for max_trials_after_failure)"""
-    p = DoglegParams()
-    rc = lib().gs_dogleg_params_default(C.byref(p))
-    if rc < 0:
-        raise GsError(rc, (lib().gs_last_error() or b"").decode())
-    if "max_trials" in kw:
-        kw["max_trials_after_failure"] = kw.pop("max_trials")
-    for k, v in kw.items():
-        if k not in ("max_trials_after_failure", "initial_delta"):
-            raise AttributeError("gs_dogleg_params has no field %r" % k)
-        setattr(p, k, v)
-    return p
+    return _step_params(DoglegParams, lib().gs_dogleg_params_default, "gs_dogleg_params", ("initial_delta",), kw)
 
 
 def device_count():
@@ -578,23 +573,22 @@ class Graph:
         done = self._check(self.L.gs_optimize_until(self.h, int(max_iterations), float(rel_chi2_tol), C.byref(st)))
         return done, st
 
+    def _optimize_steps(self, entry, p, info, iterations):
+        """an entry point of a step-control method: (accepted iterations, Stats, its info struct as a dict)"""
+        st = Stats(); st.struct_size = C.sizeof(Stats)
+        info.struct_size = C.sizeof(info)
+        done = self._check(entry(self.h, int(iterations), C.byref(p), C.byref(st), C.byref(info)))
+        return done, st, info.as_dict()
+
     def optimize_lm(self, iterations=10, **params):
         """gs_optimize_lm (Levenberg-Marquardt, g2o's rule): params = fields of gs_lm_params (max_trials_after_failure or max_trials,
         initial_lambda, tau); returns (accepted iterations, Stats, gs_lm_info as a dict)"""
-        p = lm_params(**params)
-        st = Stats(); st.struct_size = C.sizeof(Stats)
-        info = LmInfo(); info.struct_size = C.sizeof(LmInfo)
-        done = self._check(self.L.gs_optimize_lm(self.h, int(iterations), C.byref(p), C.byref(st), C.byref(info)))
-        return done, st, info.as_dict()
+        return self._optimize_steps(self.L.gs_optimize_lm, lm_params(**params), LmInfo(), iterations)
 
     def optimize_dogleg(self, iterations=10, **params):
         """gs_optimize_dogleg (Powell's dogleg, g2o's rule): params = fields of gs_dogleg_params (max_trials_after_failure or max_trials,
         initial_delta); returns (accepted iterations, Stats, gs_dogleg_info as a dict)"""
-        p = dogleg_params(**params)
-        st = Stats(); st.struct_size = C.sizeof(Stats)
-        info = DoglegInfo(); info.struct_size = C.sizeof(DoglegInfo)
-        done = self._check(self.L.gs_optimize_dogleg(self.h, int(iterations), C.byref(p), C.byref(st), C.byref(info)))
-        return done, st, info.as_dict()
+        return self._optimize_steps(self.L.gs_optimize_dogleg, dogleg_params(**params), DoglegInfo(), iterations)
 
     def debug_fail_at_iteration(self, k, code=1):
         self._check(self.L.gs_debug_fail_at_iteration(self.h, int(k), int(code)))

@@ -2,8 +2,8 @@
 // trial sequence and the double-buffered state record.  A translation unit of its own, like gs_lm.hip: the kernels of gs_kernels.hip
 // are not touched and DevGraph is what it was.
 //
-// All six kernels are vertex-parallel with the geometry of gs_lm.hip: thread v < NP = N + tN is pose v, thread NP + l is landmark
-// l < ML = M + tM; 256 threads per workgroup, lm_grid() workgroups.  A total is formed by EVERY workgroup that needs it from the same
+// All six kernels are vertex-parallel with the geometry of gs_trial_dev.hpp, which holds what they share with gs_lm.hip (reductions, b on
+// any path, base copy, the method-independent half of the verdict).  A total is formed by EVERY workgroup that needs it from the same
 // partials in index order, so all of them take the same branch; one writer per address, no atomics.
 //
 // Free vertices are told by pose_gidx / lm_gidx alone.  k_update also asks pose_known / lm_known, which differ from "every vertex" only
@@ -15,46 +15,32 @@
 // overwrites every free scalar of xe with h_dl by plain stores, which is the state k_update expects (values), and the next trial's
 // factor launch resets the rows again before anything polls them.
 #include "gs_dogleg.hpp"
-#include "gs_blocksum_dev.hpp"
+#include "gs_trial_dev.hpp"
 #include "gs_lm.hpp"                    // lm_grid: the geometry the vertex-parallel kernels share
 
 #include <cmath>
 
 namespace gs {
 
-static constexpr int DL_REC = 8;        // doubles per lm_part record (gs_kernels.hip)
-
 // the total of partial array `which`, the same bits in every thread of every workgroup
-__device__ __forceinline__ double dl_total(const DlDev &dl, int which, double *red) {
-    const double *p = dl.part + (int64_t)which * dl.part_stride;
-    double s = 0.0;
-    for (int k = threadIdx.x; k < dl.n_part; k += 256) s += p[k];
-    return lm_block_sum(s, red);
-}
+__device__ __forceinline__ double dl_total(const DlDev &dl, int which, double *red) { return part_total(dl.t.part + (int64_t)which * dl.part_stride, dl.t.n_part, red); }
 __device__ __forceinline__ void dl_put(const DlDev &dl, int which, double v, double *red) {
     v = lm_block_sum(v, red);
-    if (threadIdx.x == 0) dl.part[(int64_t)which * dl.part_stride + blockIdx.x] = v;
+    if (threadIdx.x == 0) dl.t.part[(int64_t)which * dl.part_stride + blockIdx.x] = v;
 }
 __device__ __forceinline__ double dl_alpha(double bb, double bHb) { return (isfinite(bHb) && bHb > 0.0) ? bb / bHb : 0.0; }
 
 __global__ void __launch_bounds__(256) k_dl_begin(DevGraph d, DlDev dl) {
     const int v = blockIdx.x * 256 + threadIdx.x, NP = d.N + d.tN, ML = d.M + d.tM;
+    save_base(d, dl.t, v);
     if (v < NP) { const int p = v;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) dl.base_pose[3 * (int64_t)p + c] = d.pose_est[3 * (int64_t)p + c];
-        dl.base_cs[2 * (int64_t)p] = d.pose_cs[2 * (int64_t)p]; dl.base_cs[2 * (int64_t)p + 1] = d.pose_cs[2 * (int64_t)p + 1];
         const bool fr = d.pose_gidx[p] >= 0;
-        const double *b = p < d.N ? d.b_pose + p : d.t_b_pose + (p - d.N); const int64_t St = p < d.N ? d.N : d.tcapN;
+        int64_t St; const double *b = pose_plane<const double>(d, d.b_pose, d.t_b_pose, p, St);
 #pragma unroll
         for (int c = 0; c < 3; ++c) dl.b_pose[3 * (int64_t)p + c] = fr ? b[c * St] : 0.0;
     } else if (v < NP + ML) { const int l = v - NP;
-        dl.base_lm[2 * (int64_t)l] = d.lm_est[2 * (int64_t)l]; dl.base_lm[2 * (int64_t)l + 1] = d.lm_est[2 * (int64_t)l + 1];
         double b0 = 0.0, b1 = 0.0;
-        if (d.lm_gidx[l] >= 0) {
-            if (l >= d.M) { const int o = l - d.M; b0 = d.t_b_lm[o]; b1 = d.t_b_lm[(int64_t)d.tcapM + o]; }
-            else if (d.n_wtiles > 0) {
-                for (int q = d.lm_grp_start[l]; q < d.lm_grp_start[l + 1]; ++q) { b0 += d.lm_part[(int64_t)q * DL_REC + 3]; b1 += d.lm_part[(int64_t)q * DL_REC + 4]; } }
-            else { b0 = d.b_lm[l]; b1 = d.b_lm[(int64_t)d.M + l]; } }
+        if (d.lm_gidx[l] >= 0) lm_rhs_pair(d, l, b0, b1);
         dl.b_lm[2 * (int64_t)l] = b0; dl.b_lm[2 * (int64_t)l + 1] = b1; }
 }
 
@@ -130,50 +116,34 @@ __global__ void __launch_bounds__(256) k_dl_gain(DevGraph d, DlDev dl, int par) 
 #pragma unroll
         for (int c = 0; c < 2; ++c) { const double h = dl.h_lm[2 * (int64_t)l + c]; hHh += h * dl.Hh_lm[2 * (int64_t)l + c]; bh += dl.b_lm[2 * (int64_t)l + c] * h; hh += h * h; } }
     dl_put(dl, DL_HHH, hHh, red); dl_put(dl, DL_BH, bh, red); dl_put(dl, DL_HH, hh, red);
-    // chi2[0] is still the total at the linearisation point (k_update / k_reduce_chi2 filed it); fail[0] is final for this trial
-    if (blockIdx.x == 0 && threadIdx.x == 0) { S.chi_old = d.chi2[0]; S.failcode = d.fail[0]; }
+    if (blockIdx.x == 0 && threadIdx.x == 0) trial_file(d, S.t);
 }
 
 // The verdict.  Every workgroup forms it from the same read-only inputs and restores its share of the estimates on a rejection;
-// workgroup 0 writes the next record, the history and the flags.  Any failure code (a zero pivot is g2o's "Fail" here, not a rejected
-// trial): k_update applied nothing, nothing moves, the host ends the call or — a flag timeout — repairs it and runs the trial again.
+// workgroup 0 writes the next record, the history and the flags (trial_verdict) and what is the dogleg's own: delta and the kinds.  Any
+// failure code (a zero pivot is g2o's "Fail" here, not a rejected trial): k_update applied nothing, nothing moves, the host ends the
+// call or — a flag timeout — repairs it and runs the trial again.
 __global__ void __launch_bounds__(256) k_dl_step(DevGraph d, DlDev dl, int par) {
     __shared__ double red[5];
     const DlState S = dl.state[par];
-    const int v = blockIdx.x * 256 + threadIdx.x, NP = d.N + d.tN, ML = d.M + d.tM;
+    const int v = blockIdx.x * 256 + threadIdx.x;
     const double hHh = dl_total(dl, DL_HHH, red), bh = dl_total(dl, DL_BH, red), hh = dl_total(dl, DL_HH, red);
     double gain = -hHh + 2.0 * bh;
     if (fabs(gain) < 1e-12) gain = 1e-12;
     const double chi_new = d.chi2[0];
-    const bool active = S.done == 0 && S.failcode == 0;
-    const double rho = (S.chi_old - chi_new) / gain;
+    const bool active = S.t.done == 0 && S.t.failcode == 0;
+    const double rho = (S.t.chi_old - chi_new) / gain;
     const bool accept = active && rho > 0.0 && isfinite(chi_new);
-    if (active && !accept) {                                        // put x back (bit for bit: copies)
-        if (v < NP) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) d.pose_est[3 * (int64_t)v + c] = dl.base_pose[3 * (int64_t)v + c];
-            d.pose_cs[2 * (int64_t)v] = dl.base_cs[2 * (int64_t)v]; d.pose_cs[2 * (int64_t)v + 1] = dl.base_cs[2 * (int64_t)v + 1];
-        } else if (v < NP + ML) { const int l = v - NP;
-            d.lm_est[2 * (int64_t)l] = dl.base_lm[2 * (int64_t)l]; d.lm_est[2 * (int64_t)l + 1] = dl.base_lm[2 * (int64_t)l + 1]; } }
+    if (active && !accept) restore_base(d, dl.t, v);
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     DlState T = S;
-    T.failcode = 0;
+    T.t.failcode = 0;
     if (active) {
-        const int it = S.iterations;
-        if (S.trials == 0) T.chi_base = S.chi_old;
-        if (it < 64) { dl.hist_chi2[it] = S.chi_old; dl.hist_delta[it] = S.delta; dl.hist_trials[it] = S.trials_iter + 1; dl.hist_kind[it] = S.kind; }
-        T.trials = S.trials + 1;
+        if (S.t.iterations < 64) { dl.hist_delta[S.t.iterations] = S.delta; dl.hist_kind[S.t.iterations] = S.kind; }
         if (rho > 0.75) T.delta = fmax(S.delta, 3.0 * sqrt(hh));
         else if (rho < 0.25) T.delta = 0.5 * S.delta;
-        if (accept) {
-            T.iterations = it + 1; T.trials_iter = 0; T.chi_base = chi_new;
-            T.n_kind[DL_GN] += S.kind == DL_GN; T.n_kind[DL_SD] += S.kind == DL_SD; T.n_kind[DL_DL] += S.kind == DL_DL;      // (constant indices: the record stays in registers)
-            if (T.iterations >= S.budget) T.done = 1;
-        } else {
-            T.rejected = S.rejected + 1; T.trials_iter = S.trials_iter + 1;
-            if (T.trials_iter >= S.max_trials) { T.terminated = 1; T.done = 1; }
-        }
-        if (T.done) d.fail[2] = d.iter;
+        if (accept) { T.n_kind[DL_GN] += S.kind == DL_GN; T.n_kind[DL_SD] += S.kind == DL_SD; T.n_kind[DL_DL] += S.kind == DL_DL; }      // (constant indices: the record stays in registers)
+        trial_verdict(d, dl.t, S.t, T.t, accept, chi_new);
     }
     dl.state[par ^ 1] = T;
 }

@@ -26,12 +26,11 @@
 //                 (all of its edges are tail edges) stores t_Hll_diag v + that sum, an old one adds the sum to its row.
 // The old vertices' diagonal shares that come from tail edges are where k_linearize_tail added them: Hpp_diag and the first lm_part slot.
 #include "gs_hmul.hpp"
+#include "gs_trial_dev.hpp"             // lm_slot_sum: a landmark's run of lm_part slots, summed in slot order
 
 #include <algorithm>
 
 namespace gs {
-
-static constexpr int HM_REC = 8;        // doubles per lm_part record (gs_kernels.hip)
 
 // y += O u (tr == false) or O^T u (tr == true), O a 3 x 3 row-major block in planes of stride S
 __device__ __forceinline__ void hm_add33(const double *O, int64_t S, bool tr, const double *u, double &y0, double &y1, double &y2) {
@@ -69,12 +68,11 @@ __global__ void __launch_bounds__(256) k_hmul(DevGraph d, const double *__restri
     } else if (t < d.N + d.M) { const int l = t - d.N;
         double y0 = 0.0, y1 = 0.0;
         if (d.lm_gidx[l] >= 0) {
-            double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-            if (d.n_wtiles > 0) {
-                for (int q = d.lm_grp_start[l]; q < d.lm_grp_start[l + 1]; ++q) { const double *r = d.lm_part + (int64_t)q * HM_REC; a0 += r[0]; a1 += r[1]; a2 += r[2]; } }
-            else { a0 = d.Hll_diag[l]; a1 = d.Hll_diag[(int64_t)d.M + l]; a2 = d.Hll_diag[2 * (int64_t)d.M + l]; }
+            double a[3];
+            if (d.n_wtiles > 0) lm_slot_sum(d, l, {0, 1, 2}, a);
+            else { a[0] = d.Hll_diag[l]; a[1] = d.Hll_diag[(int64_t)d.M + l]; a[2] = d.Hll_diag[2 * (int64_t)d.M + l]; }
             const double v0 = vl[2 * (int64_t)l], v1 = vl[2 * (int64_t)l + 1];
-            y0 = a0 * v0 + a1 * v1; y1 = a1 * v0 + a2 * v1;
+            y0 = a[0] * v0 + a[1] * v1; y1 = a[1] * v0 + a[2] * v1;
             const int64_t L = d.ell_len, S = (int64_t)d.ell_T * d.ell_np;
             for (int q = d.lm_start[l]; q < d.lm_start[l + 1]; ++q) {
                 const int64_t e = d.lm_edges[q];

@@ -93,12 +93,10 @@ struct gs_graph {
         bool valid = false; uint64_t structure_version = 0, estimate_version = 0; int32_t iter = 0;
         std::vector<double> out;
     } marg;
-    // gs_optimize_lm: the device state record, history, base copy of the estimates and reduction partials (gs_lm.hpp) — one allocation of
-    // the handle's own, grow-only, sized for cap_p poses / cap_l landmarks (tail included)
-    struct Lm { gs::LmDev dev{}; void *mem = nullptr; size_t cap_p = 0, cap_l = 0; gs::LmState host[2]{}; } lm;
-    // gs_optimize_dogleg and gs_multiply_hessian: the device state record, history, base copy of the estimates, the vertex-order vectors
-    // and the reduction partials (gs_dogleg.hpp) — one allocation of the handle's own, grow-only, made by the first call of either
-    struct Dogleg { gs::DlDev dev{}; void *mem = nullptr; size_t cap_p = 0, cap_l = 0; gs::DlState host[2]{}; } dl;
+    // gs_optimize_lm, and gs_optimize_dogleg with gs_multiply_hessian (the allocation is made by the first call of either): the device
+    // state record, history, base copy of the estimates, reduction partials and the dogleg's vertex-order vectors (gs_trial.hpp)
+    gs::TrialWs<gs::LmDev, gs::LmState> lm;
+    gs::TrialWs<gs::DlDev, gs::DlState> dl;
     // prior edges (gs_prior.hpp): the priors as added, the grouped tables, and their device copy — one allocation of the handle's own,
     // grow-only; uploaded whole by prior_sync when the priors or the plan changed.  dev stays empty while there is no prior on a free vertex
     struct Prior { gs::PriorStore store; gs::PriorTables tab; gs::PriorSync sync; gs::PriorDev dev{}; gs::DevArena arena;

@@ -2,10 +2,9 @@
 // sequence and the double-buffered state record.  A translation unit of its own: the kernels of gs_kernels.hip are not touched,
 // not re-instantiated, and DevGraph is what it was.
 //
-// All four kernels are vertex-parallel with the same geometry: thread v < NP = N + tN is pose v (a grown plan's tail poses follow
-// the base ones in every per-pose array), thread NP + l is landmark l < ML = M + tM; 256 threads per workgroup, lm_grid()
-// workgroups.  Every sum is two-stage in a fixed order — lanes by shuffle, waves in wave order, then the workgroups' partials in
-// index order — so no value depends on the solver's launch mode.  One writer per address, no atomics.
+// All four kernels are vertex-parallel with the geometry of gs_trial_dev.hpp, which also holds what they share with gs_dogleg.hip and
+// gs_hmul.hip: the fixed-order reductions, a vertex's diagonal and right-hand side on any path, the base copy of the estimates and the
+// method-independent half of the verdict.  One writer per address, no atomics.
 //
 // Where lambda goes (wherever the front assembly reads the diagonal scalar from):
 //   free pose p < N          Hpp_diag planes xx, yy, tt (0, 3, 5)
@@ -14,22 +13,12 @@
 //                            slot (the fronts sum the landmark's run of slots; k_linearize_tail adds there too)
 //   free tail landmark       t_Hll_diag planes 0, 2 with stride tcapM
 #include "gs_lm.hpp"
-#include "gs_blocksum_dev.hpp"      // lm_block_sum / lm_block_max: the two-stage fixed-order reductions (shared with gs_dogleg.hip)
+#include "gs_trial_dev.hpp"
 
 #include <algorithm>
 #include <cmath>
 
 namespace gs {
-
-static constexpr int LM_REC = 8;        // doubles per lm_part record (gs_kernels.hip)
-
-// the two diagonal scalars of free landmark l (any path), as the fronts see them
-__device__ __forceinline__ void lm_diag_of(const DevGraph &d, int l, double &h00, double &h11) {
-    if (l >= d.M) { const int o = l - d.M; h00 = d.t_Hll_diag[o]; h11 = d.t_Hll_diag[2 * (int64_t)d.tcapM + o]; }
-    else if (d.n_wtiles > 0) { h00 = 0.0; h11 = 0.0;
-        for (int q = d.lm_grp_start[l]; q < d.lm_grp_start[l + 1]; ++q) { h00 += d.lm_part[(int64_t)q * LM_REC]; h11 += d.lm_part[(int64_t)q * LM_REC + 2]; } }
-    else { h00 = d.Hll_diag[l]; h11 = d.Hll_diag[2 * (int64_t)d.M + l]; }
-}
 
 __global__ void __launch_bounds__(256) k_lm_maxdiag(DevGraph d, LmDev lm) {
     __shared__ double red[5];
@@ -37,12 +26,12 @@ __global__ void __launch_bounds__(256) k_lm_maxdiag(DevGraph d, LmDev lm) {
     double m = 0.0;
     if (v < NP) { const int p = v;
         if (d.pose_gidx[p] >= 0) {
-            const double *H = p < d.N ? d.Hpp_diag + p : d.t_Hpp_diag + (p - d.N); const int64_t S = p < d.N ? d.N : d.tcapN;
+            int64_t S; const double *H = pose_plane<const double>(d, d.Hpp_diag, d.t_Hpp_diag, p, S);
             m = fmax(fabs(H[0]), fmax(fabs(H[3 * S]), fabs(H[5 * S]))); }
     } else if (v < NP + ML) { const int l = v - NP;
-        if (d.lm_gidx[l] >= 0) { double a, b; lm_diag_of(d, l, a, b); m = fmax(fabs(a), fabs(b)); } }
+        if (d.lm_gidx[l] >= 0) { double a, b; lm_diag_pair(d, l, a, b); m = fmax(fabs(a), fabs(b)); } }
     m = lm_block_max(m, red);
-    if (threadIdx.x == 0) lm.part[blockIdx.x] = m;
+    if (threadIdx.x == 0) lm.t.part[blockIdx.x] = m;
 }
 
 // base copy of the estimates (the trial starts at the accepted point) + lambda on the free diagonal scalars.
@@ -53,21 +42,18 @@ __global__ void __launch_bounds__(256) k_lm_damp(DevGraph d, LmDev lm, int par, 
     __shared__ double red[5];
     LmState &S = lm.state[par];
     const int v = blockIdx.x * 256 + threadIdx.x, NP = d.N + d.tN, ML = d.M + d.tM;
-    const bool first = init != 0 && S.need_lambda != 0, done = S.done != 0;
+    const bool first = init != 0 && S.need_lambda != 0, done = S.t.done != 0;
     double lam;
     if (first) { double m = 0.0;
-        for (int k = threadIdx.x; k < lm.n_part; k += 256) m = fmax(m, lm.part[k]);
+        for (int k = threadIdx.x; k < lm.t.n_part; k += 256) m = fmax(m, lm.t.part[k]);
         lam = S.tau * lm_block_max(m, red);
     } else lam = done ? S.lambda_last : S.lambda;
+    save_base(d, lm.t, v);
     if (v < NP) { const int p = v;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) lm.base_pose[3 * (int64_t)p + c] = d.pose_est[3 * (int64_t)p + c];
-        lm.base_cs[2 * (int64_t)p] = d.pose_cs[2 * (int64_t)p]; lm.base_cs[2 * (int64_t)p + 1] = d.pose_cs[2 * (int64_t)p + 1];
         if (d.pose_gidx[p] >= 0) {
-            double *H = p < d.N ? d.Hpp_diag + p : d.t_Hpp_diag + (p - d.N); const int64_t St = p < d.N ? d.N : d.tcapN;
+            int64_t St; double *H = pose_plane(d, d.Hpp_diag, d.t_Hpp_diag, p, St);
             H[0] += lam; H[3 * St] += lam; H[5 * St] += lam; }
     } else if (v < NP + ML) { const int l = v - NP;
-        lm.base_lm[2 * (int64_t)l] = d.lm_est[2 * (int64_t)l]; lm.base_lm[2 * (int64_t)l + 1] = d.lm_est[2 * (int64_t)l + 1];
         if (d.lm_gidx[l] >= 0) {
             if (l >= d.M) { const int o = l - d.M; d.t_Hll_diag[o] += lam; d.t_Hll_diag[2 * (int64_t)d.tcapM + o] += lam; }
             // (fused path: a free base landmark always has a slot — the plan gives every landmark with an observation edge in the layout one
@@ -76,7 +62,7 @@ __global__ void __launch_bounds__(256) k_lm_damp(DevGraph d, LmDev lm, int par, 
             // would read a lambda from: its diagonal is assembled as 0, H + lambda I stays singular there, and the zero pivot makes every
             // trial a rejected one — the call terminates instead of moving a vertex no measurement holds.  The guard keeps the store in bounds.)
             else if (d.n_wtiles > 0) { const int q = d.lm_grp_start[l];
-                if (q < d.lm_grp_start[l + 1]) { d.lm_part[(int64_t)q * LM_REC] += lam; d.lm_part[(int64_t)q * LM_REC + 2] += lam; } }
+                if (q < d.lm_grp_start[l + 1]) { d.lm_part[(int64_t)q * LM_PART_REC] += lam; d.lm_part[(int64_t)q * LM_PART_REC + 2] += lam; } }
             else { d.Hll_diag[l] += lam; d.Hll_diag[2 * (int64_t)d.M + l] += lam; } } }
     if (blockIdx.x == 0 && threadIdx.x == 0 && !done) {             // (fields no other workgroup of this launch reads)
         S.lambda_last = lam;
@@ -93,71 +79,51 @@ __global__ void __launch_bounds__(256) k_lm_scale(DevGraph d, LmDev lm, int par)
     double s = 0.0;
     if (v < NP) { const int p = v;
         if (d.pose_gidx[p] >= 0) {
-            const double *b = p < d.N ? d.b_pose + p : d.t_b_pose + (p - d.N); const int64_t St = p < d.N ? d.N : d.tcapN;
+            int64_t St; const double *b = pose_plane<const double>(d, d.b_pose, d.t_b_pose, p, St);
 #pragma unroll
             for (int c = 0; c < 3; ++c) { const double dx = d.dpose[3 * (int64_t)p + c]; s += dx * (lam * dx + b[c * St]); } }
     } else if (v < NP + ML) { const int l = v - NP;
         if (d.lm_gidx[l] >= 0) {
-            double b0, b1;
-            if (l >= d.M) { const int o = l - d.M; b0 = d.t_b_lm[o]; b1 = d.t_b_lm[(int64_t)d.tcapM + o]; }
-            else if (d.n_wtiles > 0) { b0 = 0.0; b1 = 0.0;
-                for (int q = d.lm_grp_start[l]; q < d.lm_grp_start[l + 1]; ++q) { b0 += d.lm_part[(int64_t)q * LM_REC + 3]; b1 += d.lm_part[(int64_t)q * LM_REC + 4]; } }
-            else { b0 = d.b_lm[l]; b1 = d.b_lm[(int64_t)d.M + l]; }
+            double b0, b1; lm_rhs_pair(d, l, b0, b1);
             const double d0 = d.dlm[2 * (int64_t)l], d1 = d.dlm[2 * (int64_t)l + 1];
             s += d0 * (lam * d0 + b0); s += d1 * (lam * d1 + b1); } }
     s = lm_block_sum(s, red);
-    if (threadIdx.x == 0) lm.part[blockIdx.x] = s;
-    // chi2[0] is still the total at the linearisation point (k_update / k_reduce_chi2 filed it); fail[0] is final for this trial
-    // (only the solver kernels raise it).  Fields no workgroup of this launch reads.
-    if (blockIdx.x == 0 && threadIdx.x == 0) { S.chi_old = d.chi2[0]; S.failcode = d.fail[0]; }
+    if (threadIdx.x == 0) lm.t.part[blockIdx.x] = s;
+    if (blockIdx.x == 0 && threadIdx.x == 0) trial_file(d, S.t);
 }
 
 // The verdict.  Every workgroup forms it from the same read-only inputs — state[par], the scale partials in index order, chi2[0] of
-// the chi2 pass — and restores its share of the estimates on a rejection; workgroup 0 writes the next record, the history and the flags.
+// the chi2 pass — and restores its share of the estimates on a rejection; workgroup 0 writes the next record, the history and the flags
+// (trial_verdict), and what is LM's own here: lambda, nu, and
 //   fail[0] == 1 (zero pivot in this trial's factorisation; k_update applied nothing): a rejected trial, the code is cleared.
 //   fail[0] >= 2 (a whole-tree launch gave up on a flag, ...): nothing moves, the host repairs it and runs the trial again.
-//   done: fail[2] = this trial's iteration number makes k_update skip every later enqueued trial (the rule of gs_optimize_until).
 __global__ void __launch_bounds__(256) k_lm_step(DevGraph d, LmDev lm, int par) {
     __shared__ double red[5];
     const LmState S = lm.state[par];
-    const int v = blockIdx.x * 256 + threadIdx.x, NP = d.N + d.tN, ML = d.M + d.tM;
-    double s = 0.0;
-    for (int k = threadIdx.x; k < lm.n_part; k += 256) s += lm.part[k];
-    const double scale = lm_block_sum(s, red) + 1e-3;
+    const int v = blockIdx.x * 256 + threadIdx.x;
+    const double scale = part_total(lm.t.part, lm.t.n_part, red) + 1e-3;
     const double chi_new = d.chi2[0];
-    const bool active = S.done == 0 && (S.failcode == 0 || S.failcode == 1);
-    const double rho = (S.chi_old - chi_new) / scale;
-    const bool accept = active && S.failcode == 0 && rho > 0.0 && isfinite(chi_new);
-    if (active && !accept) {                                        // put x back (bit for bit: copies)
-        if (v < NP) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) d.pose_est[3 * (int64_t)v + c] = lm.base_pose[3 * (int64_t)v + c];
-            d.pose_cs[2 * (int64_t)v] = lm.base_cs[2 * (int64_t)v]; d.pose_cs[2 * (int64_t)v + 1] = lm.base_cs[2 * (int64_t)v + 1];
-        } else if (v < NP + ML) { const int l = v - NP;
-            d.lm_est[2 * (int64_t)l] = lm.base_lm[2 * (int64_t)l]; d.lm_est[2 * (int64_t)l + 1] = lm.base_lm[2 * (int64_t)l + 1]; } }
+    const bool active = S.t.done == 0 && (S.t.failcode == 0 || S.t.failcode == 1);
+    const double rho = (S.t.chi_old - chi_new) / scale;
+    const bool accept = active && S.t.failcode == 0 && rho > 0.0 && isfinite(chi_new);
+    if (active && !accept) restore_base(d, lm.t, v);
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     LmState T = S;
-    T.failcode = 0;
+    T.t.failcode = 0;
     if (active) {
-        const int it = S.iterations;
-        if (S.trials == 0) T.chi_base = S.chi_old;
-        if (it < 64) { lm.hist_chi2[it] = S.chi_old; lm.hist_lambda[it] = S.lambda_last; lm.hist_trials[it] = S.trials_iter + 1; }
-        T.need_lambda = 0; T.trials = S.trials + 1;
+        if (S.t.iterations < 64) lm.hist_lambda[S.t.iterations] = S.lambda_last;
+        T.need_lambda = 0;
         if (accept) {
             const double t = 2.0 * rho - 1.0;
             double alpha = 1.0 - t * t * t;
             alpha = fmin(alpha, 2.0 / 3.0);
             T.lambda = S.lambda_last * fmax(1.0 / 3.0, alpha); T.nu = 2.0;
-            T.iterations = it + 1; T.trials_iter = 0; T.chi_base = chi_new;
-            if (T.iterations >= S.budget) T.done = 1;
         } else {
             T.lambda = S.lambda_last * S.nu; T.nu = 2.0 * S.nu;
-            T.rejected = S.rejected + 1; T.trials_iter = S.trials_iter + 1;
-            if (S.failcode == 1) d.fail[0] = 0;
-            if (T.trials_iter >= S.max_trials) { T.terminated = 1; T.done = 1; }
+            if (S.t.failcode == 1) d.fail[0] = 0;
         }
-        if (T.done) d.fail[2] = d.iter;
-    } else if (S.done != 0 && S.failcode == 1) d.fail[0] = 0;      // a no-op trial behind the end of the call factorised the last trial's system again: its zero pivot is that trial's, already counted
+        trial_verdict(d, lm.t, S.t, T.t, accept, chi_new);
+    } else if (S.t.done != 0 && S.t.failcode == 1) d.fail[0] = 0;  // a no-op trial behind the end of the call factorised the last trial's system again: its zero pivot is that trial's, already counted
     lm.state[par ^ 1] = T;
 }
 

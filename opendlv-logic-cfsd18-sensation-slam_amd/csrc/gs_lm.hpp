@@ -5,32 +5,27 @@
 // gs_kernels.hip do not know about LM: everything below travels in LmDev, a kernel argument of the new kernels only).
 // No host decision inside a trial: lambda, nu, the counters and the accept / reject verdict live in LmState on the device.  The
 // record is double-buffered — trial number q (counted by the host as it enqueues) reads state[q & 1] and its step kernel writes
-// state[(q + 1) & 1] — so that every workgroup of a launch sees the same record whatever the timing.
+// state[(q + 1) & 1] — so that every workgroup of a launch sees the same record whatever the timing.  The record and LmDev begin with
+// the parts every step-control method has (gs_trial.hpp); the host's trial loop is run_trials (gs_solve.cpp).
 #pragma once
 #include "gs_device.hpp"
+#include "gs_trial.hpp"
 
 namespace gs {
 
 struct LmState {
+    TrialState t;               // (gs_trial.hpp; failcode 1, a zero pivot, is a rejected trial here; 2 ..: the host's business)
     double lambda;              // of the next trial (need_lambda: not known yet, the first damp kernel computes tau * max |H_jj|)
     double nu;                  // rejection factor, 2 after every accepted step
-    double chi_old;             // chi2 at the accepted point the trial started from (filed by the scale kernel)
-    double chi_base;            // chi2 at the last accepted point
     double lambda_initial, lambda_last;     // first lambda of the call; lambda of the last trial that ran
     double tau;
-    int32_t iterations, trials, rejected, terminated;       // accepted iterations, trials, rejected trials, "terminate"
-    int32_t done;               // budget used up or terminated: every later enqueued trial is a no-op
-    int32_t trials_iter;        // rejected trials of the current iteration
-    int32_t failcode;           // d.fail[0] as the scale kernel found it (1: zero pivot = a rejected trial; 2 ..: the host's business)
-    int32_t budget, max_trials, need_lambda;
+    int32_t need_lambda, pad;
 };
 
 struct LmDev {
+    TrialDev t;                                                     // history, base copy, partials (max |H_jj|, then scale)
     LmState *state = nullptr;                                       // [2]
-    double *hist_chi2 = nullptr, *hist_lambda = nullptr;            // [64] per ITERATION: chi2 at its starting point, lambda of its accepted (or last) trial
-    int32_t *hist_trials = nullptr;                                 // [64] trials of the iteration
-    double *base_pose = nullptr, *base_cs = nullptr, *base_lm = nullptr;   // the accepted estimates: [3 (N + tN)], [2 (N + tN)], [2 (M + tM)]
-    double *part = nullptr; int32_t n_part = 0;                     // one partial per workgroup of the vertex-parallel kernels (max |H_jj|, then scale)
+    double *hist_lambda = nullptr;                                  // [64] per ITERATION: lambda of its accepted (or last) trial
 };
 
 int  lm_grid(const DevGraph &d);                                    // workgroups of the vertex-parallel kernels (= n_part)

@@ -84,7 +84,7 @@ extern "C" int gs_iterate(gs_graph *g) {
     return 1;
 }
 
-// ------------------------------------------------------------------ the run scaffold of gs_optimize*, gs_optimize_lm (and, in parts, gs_dist_optimize)
+// ------------------------------------------------------------------ the run scaffold of gs_optimize*, run_trials (and, in parts, gs_dist_optimize)
 // a whole-tree launch gave up on a front's flag: one launch per level from now on; a retry of the whole-tree launches that ends this way
 // waits four times longer before the next one (run_begin, gs_compute_marginals)
 void fall_back_to_levels(gs_graph *g) {
@@ -209,6 +209,91 @@ extern "C" int gs_optimize_until(gs_graph *g, int32_t max_iterations, double rel
     return optimize_impl(g, max_iterations, rel_chi2_tol, stats);
 }
 
+// ------------------------------------------------------------------ the step-control methods: one trial scaffold for both (gs_trial.hpp)
+// a caller's parameter struct over the defaults: as many bytes as its struct_size says it holds
+template <class P> static void copy_params(P &dst, const P *src) {
+    if (!src) return;
+    std::memcpy(&dst, src, std::min<size_t>(sizeof(P), (size_t)std::max(src->struct_size, 0))); dst.struct_size = (int32_t)sizeof(P);
+}
+// the entry points that run on one device only ask twice: the handle's configuration before ensure_ready, the plan it built after it
+static int single_device_only(const gs_graph *g, bool plan_built, const char *what) {
+    if (plan_built ? !!g->plan.dist : (g->world > 1 || g->opt.force_shared_top > 0))
+        return fail(GS_ERR_INVALID, std::string("sharded graph: ") + what + " is not supported on sharded handles");
+    return GS_OK;
+}
+// ... and what lies between: the device, the structure phase if the graph changed
+static int ready_on_one_device(gs_graph *g, const char *what) {
+    int rc = single_device_only(g, false, what); if (rc != GS_OK) return rc;
+    if ((rc = ensure_device(g)) != GS_OK || (rc = ensure_ready(g)) != GS_OK) return rc;
+    return single_device_only(g, true, what);
+}
+// a method's workspace, grow-only.  b: the allocation when this call made it (the method then sets its own pointers from L), else null
+template <class Ws> static int trial_reserve(gs_graph *g, Ws &W, const TrialExtras &x, TrialLayout &L, char *&b) {
+    const size_t NP = (size_t)(g->d.N + g->d.tN), ML = (size_t)(g->d.M + g->d.tM);
+    b = nullptr;
+    if (!W.mem || NP > W.cap_p || ML > W.cap_l) {
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        if (W.mem) { hipFree(W.mem); W.mem = nullptr; }
+        L = trial_carve(NP, ML, x);
+        HIP_TRY(hipMalloc(&W.mem, L.total));
+        b = (char *)W.mem; TrialDev &T = W.dev.t; W.dev.state = (decltype(W.dev.state))(b + L.state);
+        T.hist_chi2 = (double *)(b + L.hist_chi2); T.hist_trials = (int32_t *)(b + L.hist_trials);
+        T.base_pose = (double *)(b + L.base_pose); T.base_cs = (double *)(b + L.base_cs); T.base_lm = (double *)(b + L.base_lm); T.part = (double *)(b + L.part);
+        W.cap_p = L.cp; W.cap_l = L.cl; }
+    W.dev.t.n_part = (int32_t)lm_grid(g->d);
+    return GS_OK;
+}
+struct TrialHist { void *dev, *host; size_t bytes; };               // a method's own [64] history array, and where the host wants it
+struct TrialCall { int32_t iterations; gs_stats *stats; bool want_chi2; const char *what, *numeric_msg; int n_hist; TrialHist hist[2]; };
+struct TrialOut { double chi_last, chi2[64]; int32_t n_trials[64]; };
+// The trials of one call from the record W.host[0].  enqueue(seq, first): one trial, asynchronous, reading state[seq & 1] (first: no
+// trial of this call has run).  tail(it, O, buf, n): the method's end of iteration it's verbose line.  report(S, O): its info struct.
+template <class Ws, class Enqueue, class Tail, class Report>
+static int run_trials(gs_graph *g, Ws &W, const TrialCall &c, Enqueue enqueue, Tail tail, Report report) {
+    auto *H = W.host; auto S = H[0]; const TrialDev &T = W.dev.t; const int32_t iterations = c.iterations;
+    int rc = run_begin(g, iterations, true); if (rc != GS_OK) return rc;
+    g->d.conv_tol = -1.0; g->d.hist_slot = -1;
+    HIP_TRY(hipMemcpyAsync(W.dev.state, H, 2 * sizeof(S), hipMemcpyHostToDevice, g->stream));
+    TrialOut O; const TrialHist hist[4] = {{T.hist_chi2, O.chi2, sizeof(O.chi2)}, {T.hist_trials, O.n_trials, sizeof(O.n_trials)}, c.hist[0], c.hist[1]};
+    for (int k = 0; k < 2 + c.n_hist; ++k) HIP_TRY(hipMemsetAsync(hist[k].dev, 0, hist[k].bytes, g->stream));
+    hipEventRecord(g->ev[5], g->stream);
+    // Chunks of trials, the device record read in between (one host round trip per chunk).  Never more trials than iterations still
+    // to accept — each needs one at least —, so the only trials that run as no-ops are the ones enqueued behind a "terminate"; the first
+    // trial alone until a whole-tree launch of this plan has come back clean, as in gs_optimize.
+    int seq = 0; RunState R; const int32_t *ff = R.ff;
+    while (iterations > 0 && !S.t.done && S.t.iterations < iterations) {
+        const bool alone = S.t.trials == 0 && !(g->tree_proven && g->d.tree);
+        const int n = alone ? 1 : std::min(iterations - S.t.iterations, 8);
+        for (int k = 0; k < n; ++k, ++seq) enqueue(seq, k == 0 && S.t.trials == 0);
+        HIP_TRY(hipMemcpyAsync(&H[1], W.dev.state + (seq & 1), sizeof(S), hipMemcpyDeviceToHost, g->stream));
+        const int next = run_chunk_done(g, R); if (next < 0) return next;
+        S = H[1];
+        if (next == RUN_STOP) break;                                // (RUN_RERUN: the trials behind the timeout were no-ops: the loop runs them again, one launch per level)
+    }
+    HIP_TRY(hipMemsetAsync(g->d.fail + 1, 0, 2 * sizeof(int32_t), g->stream));     // the update count and the stop flag must not gate later gs_iterate calls
+    if (S.t.trials == 0 && c.want_chi2) enqueue_chi2(g);           // nothing ran: chi2 at the estimates as they are
+    hipEventRecord(g->ev[6], g->stream);
+    double chi_here = 0.0; float ms;
+    HIP_TRY(hipMemcpyAsync(&chi_here, g->d.chi2, sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    for (int k = 0; k < 2 + c.n_hist; ++k) HIP_TRY(hipMemcpyAsync(hist[k].host, hist[k].dev, hist[k].bytes, hipMemcpyDeviceToHost, g->stream));
+    if ((rc = run_end(g, c.what, &ms)) != GS_OK) return rc;
+    const double chi_first = S.t.trials > 0 ? O.chi2[0] : chi_here; O.chi_last = S.t.trials > 0 ? S.t.chi_base : chi_here;
+    if (g->cfg.verbose) for (int it = 0; it < std::min(S.t.iterations, 64); ++it) { char buf[96]; tail(it, O, buf, sizeof(buf));
+        std::fprintf(stderr, "iteration= %d\t chi2= %.6f\t edges= %d\t schur= 0\t %s\n", it,
+                     it + 1 < S.t.iterations && it + 1 < 64 ? O.chi2[it + 1] : O.chi_last, g->h.n_pp() + g->h.n_pl(), buf); }
+    run_stats(g, c.stats, S.t.iterations, ff[0], R.first_failure, chi_first, O.chi_last, ms);
+    report(S, O);
+    if (ff[0]) { rc = reset_failure(g); if (rc != GS_OK) return rc;
+        if (ff[0] == 2) return fail(GS_ERR_TIMEOUT, "a front's completion flag did not arrive in time, with one launch per level as well (estimates = last accepted point)");
+        return fail(GS_ERR_NUMERIC, c.numeric_msg); }
+    return S.t.iterations;
+}
+template <class Info> static void info_counts(Info *info, const TrialState &t, const TrialOut &O) {
+    std::memset(info, 0, sizeof(*info)); info->struct_size = (int32_t)sizeof(*info);
+    info->iterations = t.iterations; info->trials = t.trials; info->rejected = t.rejected; info->terminated = t.terminated;
+    std::memcpy(info->chi2, O.chi2, sizeof(O.chi2)); std::memcpy(info->n_trials, O.n_trials, sizeof(O.n_trials));
+}
+
 // ------------------------------------------------------------------ Levenberg-Marquardt (gs_lm.hpp: trial sequence, device record)
 extern "C" int gs_lm_params_default(gs_lm_params *p) {
     if (!p) return fail(GS_ERR_INVALID, "null params");
@@ -216,24 +301,11 @@ extern "C" int gs_lm_params_default(gs_lm_params *p) {
     p->struct_size = (int32_t)sizeof(*p); p->max_trials_after_failure = 10; p->initial_lambda = 0.0; p->tau = 1e-5;
     return GS_OK;
 }
-// the handle's LM buffers: one allocation of its own (not pool memory: it outlives the plans), grow-only
 static int lm_reserve(gs_graph *g) {
-    auto &W = g->lm; const size_t NP = (size_t)(g->d.N + g->d.tN), ML = (size_t)(g->d.M + g->d.tM);
-    const size_t np = (size_t)lm_grid(g->d);
-    if (!W.mem || NP > W.cap_p || ML > W.cap_l) {
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        if (W.mem) { hipFree(W.mem); W.mem = nullptr; }
-        const size_t cp = NP + 64, cl = ML + 64, cpart = (cp + cl + 255) / 256 + 1;
-        auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-        const size_t o_state = 0, o_hc = al(2 * sizeof(LmState)), o_hl = o_hc + al(64 * 8), o_ht = o_hl + al(64 * 8), o_bp = o_ht + al(64 * 4),
-                     o_bc = o_bp + al(cp * 24), o_bl = o_bc + al(cp * 16), o_part = o_bl + al(cl * 16), total = o_part + al(cpart * 8);
-        HIP_TRY(hipMalloc(&W.mem, total));
-        char *b = (char *)W.mem;
-        W.dev.state = (LmState *)(b + o_state); W.dev.hist_chi2 = (double *)(b + o_hc); W.dev.hist_lambda = (double *)(b + o_hl); W.dev.hist_trials = (int32_t *)(b + o_ht);
-        W.dev.base_pose = (double *)(b + o_bp); W.dev.base_cs = (double *)(b + o_bc); W.dev.base_lm = (double *)(b + o_bl); W.dev.part = (double *)(b + o_part);
-        W.cap_p = cp; W.cap_l = cl; }
-    W.dev.n_part = (int32_t)np;
-    return GS_OK;
+    TrialLayout L; char *b;
+    const int rc = trial_reserve(g, g->lm, {2 * sizeof(LmState), 1, 0, 1, 0}, L, b);       // + hist_lambda; one partial array
+    if (rc == GS_OK && b) g->lm.dev.hist_lambda = (double *)(b + L.hist_f64[0]);
+    return rc;
 }
 // one trial, asynchronous: today's linearise / factor / back-solve / update launches in today's launch modes, with the LM kernels around them
 static void enqueue_lm_trial(gs_graph *g, int par, bool init) {
@@ -251,63 +323,23 @@ static void enqueue_lm_trial(gs_graph *g, int par, bool init) {
 extern "C" int gs_optimize_lm(gs_graph *g, int32_t iterations, const gs_lm_params *params, gs_stats *stats, gs_lm_info *info) {
     if (!g) return fail(GS_ERR_INVALID, "null graph");
     if (iterations < 0) return fail(GS_ERR_INVALID, "negative iteration count");
-    gs_lm_params P; gs_lm_params_default(&P);
-    if (params) { std::memcpy(&P, params, std::min<size_t>(sizeof(P), (size_t)std::max(params->struct_size, 0))); P.struct_size = (int32_t)sizeof(P); }
+    gs_lm_params P; gs_lm_params_default(&P); copy_params(P, params);
     if (!std::isfinite(P.tau) || !(P.tau > 0.0)) return fail(GS_ERR_INVALID, "gs_lm_params.tau must be finite and > 0");
     if (!std::isfinite(P.initial_lambda)) return fail(GS_ERR_INVALID, "gs_lm_params.initial_lambda must be finite (<= 0: tau * max diag(H))");
     if (P.max_trials_after_failure < 1) return fail(GS_ERR_INVALID, "gs_lm_params.max_trials_after_failure must be >= 1");
-    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: Levenberg-Marquardt is not supported on sharded handles");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    rc = ensure_ready(g); if (rc != GS_OK) return rc;
-    if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: Levenberg-Marquardt is not supported on sharded handles");
+    int rc = ready_on_one_device(g, "Levenberg-Marquardt"); if (rc != GS_OK) return rc;
     rc = lm_reserve(g); if (rc != GS_OK) return rc;
-    if ((rc = run_begin(g, iterations, true)) != GS_OK) return rc;
-    g->d.conv_tol = -1.0; g->d.hist_slot = -1;
-    LmState *H = g->lm.host; std::memset(H, 0, 2 * sizeof(LmState));
-    LmState &S0 = H[0];
-    S0.lambda = P.initial_lambda > 0.0 ? P.initial_lambda : 0.0; S0.lambda_initial = S0.lambda; S0.nu = 2.0; S0.tau = P.tau;
-    S0.budget = iterations; S0.max_trials = P.max_trials_after_failure; S0.need_lambda = P.initial_lambda > 0.0 ? 0 : 1;
-    HIP_TRY(hipMemcpyAsync(g->lm.dev.state, H, 2 * sizeof(LmState), hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemsetAsync(g->lm.dev.hist_chi2, 0, 64 * sizeof(double), g->stream));
-    HIP_TRY(hipMemsetAsync(g->lm.dev.hist_lambda, 0, 64 * sizeof(double), g->stream));
-    HIP_TRY(hipMemsetAsync(g->lm.dev.hist_trials, 0, 64 * sizeof(int32_t), g->stream));
-    hipEventRecord(g->ev[5], g->stream);
-    // Chunks of trials, the device record read in between (one host round trip per chunk).  Never more trials than iterations still
-    // to accept — each needs one at least —, so the only trials that run as no-ops are the ones enqueued behind a "terminate"; the first
-    // trial alone until a whole-tree launch of this plan has come back clean, as in gs_optimize.
-    LmState S = S0; int seq = 0; RunState R; const int32_t *ff = R.ff;
-    while (iterations > 0 && !S.done && S.iterations < iterations) {
-        const bool alone = S.trials == 0 && !(g->tree_proven && g->d.tree);
-        const int n = alone ? 1 : std::min(iterations - S.iterations, 8);
-        for (int k = 0; k < n; ++k, ++seq) enqueue_lm_trial(g, seq & 1, k == 0 && S.trials == 0 && S.need_lambda != 0);
-        HIP_TRY(hipMemcpyAsync(&H[1], g->lm.dev.state + (seq & 1), sizeof(LmState), hipMemcpyDeviceToHost, g->stream));
-        const int next = run_chunk_done(g, R); if (next < 0) return next;
-        S = H[1];
-        if (next == RUN_STOP) break;                                // (RUN_RERUN: the trials behind the timeout were no-ops: the loop runs them again, one launch per level)
-    }
-    HIP_TRY(hipMemsetAsync(g->d.fail + 1, 0, 2 * sizeof(int32_t), g->stream));     // the update count and the stop flag must not gate later gs_iterate calls
-    if (S.trials == 0 && (stats || info || g->cfg.verbose)) enqueue_chi2(g);     // nothing ran: chi2 at the estimates as they are
-    hipEventRecord(g->ev[6], g->stream);
-    double chi_here = 0.0, hc[64], hl[64]; int32_t ht[64];
-    HIP_TRY(hipMemcpyAsync(&chi_here, g->d.chi2, sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipMemcpyAsync(hc, g->lm.dev.hist_chi2, sizeof(hc), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipMemcpyAsync(hl, g->lm.dev.hist_lambda, sizeof(hl), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipMemcpyAsync(ht, g->lm.dev.hist_trials, sizeof(ht), hipMemcpyDeviceToHost, g->stream));
-    float ms;
-    if ((rc = run_end(g, "LM iteration", &ms)) != GS_OK) return rc;
-    const double chi_first = S.trials > 0 ? hc[0] : chi_here, chi_last = S.trials > 0 ? S.chi_base : chi_here;
-    if (g->cfg.verbose) for (int it = 0; it < std::min(S.iterations, 64); ++it)
-        std::fprintf(stderr, "iteration= %d\t chi2= %.6f\t edges= %d\t schur= 0\t lambda= %.6g\t levenbergIter= %d\n", it,
-                     it + 1 < S.iterations && it + 1 < 64 ? hc[it + 1] : chi_last, g->h.n_pp() + g->h.n_pl(), hl[it], ht[it]);
-    run_stats(g, stats, S.iterations, ff[0], R.first_failure, chi_first, chi_last, ms);
-    if (info) { std::memset(info, 0, sizeof(*info)); info->struct_size = (int32_t)sizeof(*info);
-        info->iterations = S.iterations; info->trials = S.trials; info->rejected = S.rejected; info->terminated = S.terminated;
-        info->lambda_initial = S.lambda_initial; info->lambda_final = S.lambda;
-        std::memcpy(info->chi2, hc, sizeof(hc)); std::memcpy(info->lambda, hl, sizeof(hl)); std::memcpy(info->n_trials, ht, sizeof(ht)); }
-    if (ff[0]) { rc = reset_failure(g); if (rc != GS_OK) return rc;
-        if (ff[0] == 2) return fail(GS_ERR_TIMEOUT, "a front's completion flag did not arrive in time, with one launch per level as well (estimates = last accepted point)");
-        return fail(GS_ERR_NUMERIC, "a solver failure the step control could not treat as a rejected trial (estimates = last accepted point)"); }
-    return S.iterations;
+    LmState *H = g->lm.host, &S0 = H[0]; std::memset(H, 0, 2 * sizeof(LmState));
+    double hl[64]; const bool need_lambda = !(P.initial_lambda > 0.0);
+    S0.lambda = need_lambda ? 0.0 : P.initial_lambda; S0.lambda_initial = S0.lambda; S0.nu = 2.0; S0.tau = P.tau;
+    S0.t.budget = iterations; S0.t.max_trials = P.max_trials_after_failure; S0.need_lambda = need_lambda ? 1 : 0;
+    const TrialCall call{iterations, stats, stats || info || g->cfg.verbose, "LM iteration",
+        "a solver failure the step control could not treat as a rejected trial (estimates = last accepted point)", 1, {{g->lm.dev.hist_lambda, hl, sizeof(hl)}}};
+    return run_trials(g, g->lm, call,
+        [&](int seq, bool first) { enqueue_lm_trial(g, seq & 1, first && need_lambda); },
+        [&](int it, const TrialOut &O, char *buf, size_t n) { std::snprintf(buf, n, "lambda= %.6g\t levenbergIter= %d", hl[it], O.n_trials[it]); },
+        [&](const LmState &S, const TrialOut &O) { if (!info) return;
+            info_counts(info, S.t, O); info->lambda_initial = S.lambda_initial; info->lambda_final = S.lambda; std::memcpy(info->lambda, hl, sizeof(hl)); });
 }
 
 // ------------------------------------------------------------------ Powell's dogleg (gs_dogleg.hpp: trial sequence, device record)
@@ -317,30 +349,14 @@ extern "C" int gs_dogleg_params_default(gs_dogleg_params *p) {
     p->struct_size = (int32_t)sizeof(*p); p->max_trials_after_failure = 100; p->initial_delta = 1e4;
     return GS_OK;
 }
-// the handle's dogleg / Hessian-product buffers: one allocation of its own (not pool memory: it outlives the plans), grow-only
+// (also the vectors gs_multiply_hessian stages its operand and result in)
 static int dl_reserve(gs_graph *g) {
-    auto &W = g->dl; const size_t NP = (size_t)(g->d.N + g->d.tN), ML = (size_t)(g->d.M + g->d.tM);
-    if (!W.mem || NP > W.cap_p || ML > W.cap_l) {
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        if (W.mem) { hipFree(W.mem); W.mem = nullptr; }
-        const size_t cp = NP + 64, cl = ML + 64, cpart = (cp + cl + 255) / 256 + 1;
-        size_t total = 0;
-        auto take = [&total](size_t b) { const size_t o = total; total += (b + 255) & ~(size_t)255; return o; };
-        const size_t o_state = take(2 * sizeof(DlState)), o_hc = take(64 * 8), o_hd = take(64 * 8), o_ht = take(64 * 4), o_hk = take(64 * 4),
-                     o_bp = take(cp * 24), o_bc = take(cp * 16), o_bl = take(cl * 16), o_part = take(DL_NPART * cpart * 8);
-        size_t o_vp[4], o_vl[4];
-        for (int k = 0; k < 4; ++k) { o_vp[k] = take(cp * 24); o_vl[k] = take(cl * 16); }
-        HIP_TRY(hipMalloc(&W.mem, total));
-        char *b = (char *)W.mem; DlDev &D = W.dev;
-        D.state = (DlState *)(b + o_state); D.hist_chi2 = (double *)(b + o_hc); D.hist_delta = (double *)(b + o_hd);
-        D.hist_trials = (int32_t *)(b + o_ht); D.hist_kind = (int32_t *)(b + o_hk);
-        D.base_pose = (double *)(b + o_bp); D.base_cs = (double *)(b + o_bc); D.base_lm = (double *)(b + o_bl);
-        D.part = (double *)(b + o_part); D.part_stride = (int32_t)cpart;
+    TrialLayout L; char *b; DlDev &D = g->dl.dev;
+    const int rc = trial_reserve(g, g->dl, {2 * sizeof(DlState), 1, 1, DL_NPART, 4}, L, b);      // + hist_delta, hist_kind; b, H b, h_dl, H h_dl
+    if (rc == GS_OK && b) { D.hist_delta = (double *)(b + L.hist_f64[0]); D.hist_kind = (int32_t *)(b + L.hist_i32[0]); D.part_stride = (int32_t)L.cpart;
         double **vp[4] = {&D.b_pose, &D.Hb_pose, &D.h_pose, &D.Hh_pose}, **vl[4] = {&D.b_lm, &D.Hb_lm, &D.h_lm, &D.Hh_lm};
-        for (int k = 0; k < 4; ++k) { *vp[k] = (double *)(b + o_vp[k]); *vl[k] = (double *)(b + o_vl[k]); }
-        W.cap_p = cp; W.cap_l = cl; }
-    W.dev.n_part = (int32_t)lm_grid(g->d);
-    return GS_OK;
+        for (int k = 0; k < 4; ++k) { *vp[k] = (double *)(b + L.vec_pose[k]); *vl[k] = (double *)(b + L.vec_lm[k]); } }
+    return rc;
 }
 // one trial, asynchronous: today's linearise / factor / back-solve / update launches in today's launch modes, with the dogleg kernels and
 // the two Hessian products around them.  Both products run before the chi2 pass (on a grown plan it is a full linearisation)
@@ -365,66 +381,24 @@ static void enqueue_dogleg_trial(gs_graph *g, int par) {
 extern "C" int gs_optimize_dogleg(gs_graph *g, int32_t iterations, const gs_dogleg_params *params, gs_stats *stats, gs_dogleg_info *info) {
     if (!g) return fail(GS_ERR_INVALID, "null graph");
     if (iterations < 0) return fail(GS_ERR_INVALID, "negative iteration count");
-    gs_dogleg_params P; gs_dogleg_params_default(&P);
-    if (params) { std::memcpy(&P, params, std::min<size_t>(sizeof(P), (size_t)std::max(params->struct_size, 0))); P.struct_size = (int32_t)sizeof(P); }
+    gs_dogleg_params P; gs_dogleg_params_default(&P); copy_params(P, params);
     if (!std::isfinite(P.initial_delta) || !(P.initial_delta > 0.0)) return fail(GS_ERR_INVALID, "gs_dogleg_params.initial_delta must be finite and > 0");
     if (P.max_trials_after_failure < 1) return fail(GS_ERR_INVALID, "gs_dogleg_params.max_trials_after_failure must be >= 1");
-    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: the dogleg is not supported on sharded handles");
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    rc = ensure_ready(g); if (rc != GS_OK) return rc;
-    if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: the dogleg is not supported on sharded handles");
+    int rc = ready_on_one_device(g, "the dogleg"); if (rc != GS_OK) return rc;
     rc = dl_reserve(g); if (rc != GS_OK) return rc;
-    if ((rc = run_begin(g, iterations, true)) != GS_OK) return rc;
-    g->d.conv_tol = -1.0; g->d.hist_slot = -1;
-    DlState *H = g->dl.host; std::memset(H, 0, 2 * sizeof(DlState));
-    DlState &S0 = H[0];
-    S0.delta = P.initial_delta; S0.delta_initial = P.initial_delta; S0.budget = iterations; S0.max_trials = P.max_trials_after_failure;
-    const DlDev &dl = g->dl.dev;
-    HIP_TRY(hipMemcpyAsync(dl.state, H, 2 * sizeof(DlState), hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemsetAsync(dl.hist_chi2, 0, 64 * sizeof(double), g->stream));
-    HIP_TRY(hipMemsetAsync(dl.hist_delta, 0, 64 * sizeof(double), g->stream));
-    HIP_TRY(hipMemsetAsync(dl.hist_trials, 0, 64 * sizeof(int32_t), g->stream));
-    HIP_TRY(hipMemsetAsync(dl.hist_kind, 0, 64 * sizeof(int32_t), g->stream));
-    hipEventRecord(g->ev[5], g->stream);
-    // Chunks of trials, the device record read in between (one host round trip per chunk), as in gs_optimize_lm: never more trials than
-    // iterations still to accept, the first trial alone until a whole-tree launch of this plan has come back clean
-    DlState S = S0; int seq = 0; RunState R; const int32_t *ff = R.ff;
-    while (iterations > 0 && !S.done && S.iterations < iterations) {
-        const bool alone = S.trials == 0 && !(g->tree_proven && g->d.tree);
-        const int n = alone ? 1 : std::min(iterations - S.iterations, 8);
-        for (int k = 0; k < n; ++k, ++seq) enqueue_dogleg_trial(g, seq & 1);
-        HIP_TRY(hipMemcpyAsync(&H[1], dl.state + (seq & 1), sizeof(DlState), hipMemcpyDeviceToHost, g->stream));
-        const int next = run_chunk_done(g, R); if (next < 0) return next;
-        S = H[1];
-        if (next == RUN_STOP) break;                                // (RUN_RERUN: the trials behind the timeout were no-ops: the loop runs them again, one launch per level)
-    }
-    HIP_TRY(hipMemsetAsync(g->d.fail + 1, 0, 2 * sizeof(int32_t), g->stream));     // the update count and the stop flag must not gate later gs_iterate calls
-    if (S.trials == 0 && (stats || info || g->cfg.verbose)) enqueue_chi2(g);     // nothing ran: chi2 at the estimates as they are
-    hipEventRecord(g->ev[6], g->stream);
-    double chi_here = 0.0, hc[64], hd[64]; int32_t ht[64], hk[64];
-    HIP_TRY(hipMemcpyAsync(&chi_here, g->d.chi2, sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipMemcpyAsync(hc, dl.hist_chi2, sizeof(hc), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipMemcpyAsync(hd, dl.hist_delta, sizeof(hd), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipMemcpyAsync(ht, dl.hist_trials, sizeof(ht), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipMemcpyAsync(hk, dl.hist_kind, sizeof(hk), hipMemcpyDeviceToHost, g->stream));
-    float ms;
-    if ((rc = run_end(g, "dogleg iteration", &ms)) != GS_OK) return rc;
-    const double chi_first = S.trials > 0 ? hc[0] : chi_here, chi_last = S.trials > 0 ? S.chi_base : chi_here;
-    static const char *const kind_name[3] = {"GN", "SD", "DL"};
-    if (g->cfg.verbose) for (int it = 0; it < std::min(S.iterations, 64); ++it)
-        std::fprintf(stderr, "iteration= %d\t chi2= %.6f\t edges= %d\t schur= 0\t delta= %.6g\t kind= %s\t tries= %d\n", it,
-                     it + 1 < S.iterations && it + 1 < 64 ? hc[it + 1] : chi_last, g->h.n_pp() + g->h.n_pl(), hd[it], kind_name[hk[it] % 3], ht[it]);
-    run_stats(g, stats, S.iterations, ff[0], R.first_failure, chi_first, chi_last, ms);
-    if (info) { std::memset(info, 0, sizeof(*info)); info->struct_size = (int32_t)sizeof(*info);
-        info->iterations = S.iterations; info->trials = S.trials; info->rejected = S.rejected; info->terminated = S.terminated;
-        info->n_gn = S.n_kind[DL_GN]; info->n_sd = S.n_kind[DL_SD]; info->n_dl = S.n_kind[DL_DL];
-        info->delta_initial = S.delta_initial; info->delta_final = S.delta;
-        std::memcpy(info->chi2, hc, sizeof(hc)); std::memcpy(info->delta, hd, sizeof(hd));
-        std::memcpy(info->n_trials, ht, sizeof(ht)); std::memcpy(info->step_kind, hk, sizeof(hk)); }
-    if (ff[0]) { rc = reset_failure(g); if (rc != GS_OK) return rc;
-        if (ff[0] == 2) return fail(GS_ERR_TIMEOUT, "a front's completion flag did not arrive in time, with one launch per level as well (estimates = last accepted point)");
-        return fail(GS_ERR_NUMERIC, "the Gauss-Newton solve of a dogleg trial failed (zero pivot: H is singular; estimates = last accepted point)"); }
-    return S.iterations;
+    DlState *H = g->dl.host, &S0 = H[0]; std::memset(H, 0, 2 * sizeof(DlState));
+    S0.delta = P.initial_delta; S0.delta_initial = P.initial_delta; S0.t.budget = iterations; S0.t.max_trials = P.max_trials_after_failure;
+    double hd[64]; int32_t hk[64]; const DlDev &dl = g->dl.dev; static const char *const kind_name[3] = {"GN", "SD", "DL"};
+    const TrialCall call{iterations, stats, stats || info || g->cfg.verbose, "dogleg iteration",
+        "the Gauss-Newton solve of a dogleg trial failed (zero pivot: H is singular; estimates = last accepted point)", 2,
+        {{dl.hist_delta, hd, sizeof(hd)}, {dl.hist_kind, hk, sizeof(hk)}}};
+    return run_trials(g, g->dl, call,
+        [&](int seq, bool) { enqueue_dogleg_trial(g, seq & 1); },
+        [&](int it, const TrialOut &O, char *buf, size_t n) { std::snprintf(buf, n, "delta= %.6g\t kind= %s\t tries= %d", hd[it], kind_name[hk[it] % 3], O.n_trials[it]); },
+        [&](const DlState &S, const TrialOut &O) { if (!info) return;
+            info_counts(info, S.t, O); info->n_gn = S.n_kind[DL_GN]; info->n_sd = S.n_kind[DL_SD]; info->n_dl = S.n_kind[DL_DL];
+            info->delta_initial = S.delta_initial; info->delta_final = S.delta;
+            std::memcpy(info->delta, hd, sizeof(hd)); std::memcpy(info->step_kind, hk, sizeof(hk)); });
 }
 
 extern "C" int gs_chi2(gs_graph *g, double *out) {
@@ -516,16 +490,16 @@ extern "C" int gs_multiply_hessian(gs_graph *g, const double *v_pose, const doub
     if (!g) return fail(GS_ERR_INVALID, "null graph");
     const HostGraph &h = g->h; const size_t NP = (size_t)h.n_poses(), ML = (size_t)h.n_lms();
     if ((NP > 0 && !v_pose) || (ML > 0 && !v_lm)) return fail(GS_ERR_INVALID, "null vector");
-    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: the Hessian product is not supported on sharded handles");
+    int rc = single_device_only(g, false, "the Hessian product"); if (rc != GS_OK) return rc;
     // fixed vertices: their entries of v are ignored (sent as zeros); every other entry must be finite
     std::vector<double> vp(3 * NP), vl(2 * ML);
     for (size_t p = 0; p < NP; ++p) for (int c = 0; c < 3; ++c) { const double x = h.pose_fixed[p] ? 0.0 : v_pose[3 * p + c];
         if (!std::isfinite(x)) return fail(GS_ERR_INVALID, "v_pose holds a value that is not finite"); vp[3 * p + c] = x; }
     for (size_t l = 0; l < ML; ++l) for (int c = 0; c < 2; ++c) { const double x = h.lm_fixed[l] ? 0.0 : v_lm[2 * l + c];
         if (!std::isfinite(x)) return fail(GS_ERR_INVALID, "v_lm holds a value that is not finite"); vl[2 * l + c] = x; }
-    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (!g->dev_valid || !g->linearised) return fail(GS_ERR_NOT_INITIALIZED, "nothing linearised yet (since the last structure phase or growth step)");
-    if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: the Hessian product is not supported on sharded handles");
+    if ((rc = single_device_only(g, true, "the Hessian product")) != GS_OK) return rc;
     if (g->plan_version != h.structure_version || (size_t)(g->d.N + g->d.tN) != NP || (size_t)(g->d.M + g->d.tM) != ML)
         return fail(GS_ERR_NOT_INITIALIZED, "the graph changed since the last linearisation");
     if ((rc = dl_reserve(g)) != GS_OK) return rc;
@@ -546,9 +520,9 @@ extern "C" int gs_get_edge_chi2(gs_graph *g, int32_t edge_kind, int32_t capacity
     if (!g) return fail(GS_ERR_INVALID, "null graph");
     if (edge_kind != GS_EDGE_ODOMETRY && edge_kind != GS_EDGE_OBSERVATION) return fail(GS_ERR_INVALID, "edge kind must be GS_EDGE_ODOMETRY or GS_EDGE_OBSERVATION");
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (g->world > 1 || g->opt.force_shared_top > 0) return fail(GS_ERR_INVALID, "sharded graph: per-edge chi2 is not supported on sharded handles");
+    if ((rc = single_device_only(g, false, "per-edge chi2")) != GS_OK) return rc;
     rc = ensure_ready(g); if (rc != GS_OK) return rc;
-    if (g->plan.dist) return fail(GS_ERR_INVALID, "sharded graph: per-edge chi2 is not supported on sharded handles");
+    if ((rc = single_device_only(g, true, "per-edge chi2")) != GS_OK) return rc;
     const HostGraph &h = g->h;
     const bool pp = edge_kind == GS_EDGE_ODOMETRY;
     const int n = pp ? h.n_pp() : h.n_pl();

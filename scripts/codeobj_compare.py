@@ -85,8 +85,8 @@ def main():
             differ += verdict != "same"
             print("  %-7s %6d %5s %5s %5s %7s %6s %4s  %s" % ((verdict, len(db.get(name, da.get(name, [])))) + tuple(r.get(f, "-") for f in FIELDS[:4]) +
                                                                  (r.get(FIELDS[5], "-"), r.get(FIELDS[4], "-"), name)))
-            if verdict == "RES":
-                print("          A: %s\n          B: %s" % (ra.get(name), rb.get(name)))
+            if verdict != "same":
+                print("          A: %d instr, %s\n          B: %d instr, %s" % (len(da.get(name, [])), ra.get(name), len(db.get(name, [])), rb.get(name)))
     print("\nverdict: %s" % ("every kernel's disassembly and resource lines are identical" if not differ else "%d kernels differ" % differ))
     return 1 if differ else 0
 

@@ -9,7 +9,7 @@ import pytest
 
 import dogleg_ref as dr
 import polar_ref as plr
-from test_lm_cpu import robust_case, starts
+from test_lm_cpu import BOUNDARY, boundary_start, robust_case, starts
 
 DEFAULT_TRIALS = [4, 1, 1, 1, 1, 1]
 DEFAULT_KINDS = ["GN", "GN", "GN", "DL", "DL", "GN", "DL", "GN", "GN"]           # per trial; the first three are rejected
@@ -99,6 +99,23 @@ def test_three_trials_from_x1_terminate(po, bench_graphs):
     assert all(t["kind"] == dr.GN and abs(t["rho"] + 0.2318) < 1e-3 for t in r["trials"])
     dr.conditions(r)
     assert r["delta_final"] == 1e4 / 8
+
+
+def boundary_terminate(po, g, P1, L1):
+    """the checker's run from a boundary start (test_lm_cpu.boundary_start) with max_trials = 3 and the default initial_delta; asserted:
+    three rejections, "terminate", and dogleg_ref.conditions on every trial"""
+    r = dr.run(dr.Model(po, g), 6, poses=P1, lms=L1, max_trials=3)
+    assert r["terminated"] and r["accepted"] == 0 and r["rejected"] == 3 and r["n_trials"].tolist() == [3]
+    dr.conditions(r)
+    return r
+
+
+@pytest.mark.parametrize("total", sorted(BOUNDARY))
+def test_boundary_graphs_terminate_with_the_checker_alone(po, bench_graphs, total):
+    """The condition of test_gpu_dogleg.py's terminate-and-restore test at N + M = 255, 256, 257 (one workgroup with an idle thread,
+    exactly one, a second one of a single landmark): three rejected trials, every margin, rho gap and branch gap (printed)."""
+    g, P1, L1 = boundary_start(po, bench_graphs, total)
+    show("N + M = %d" % total, boundary_terminate(po, g, P1, L1))
 
 
 def test_robust_and_side_pass_case(po, bench_graphs):

@@ -25,9 +25,9 @@ import lm_ref
 import polar_ref as plr
 import prior_ref as pr
 from conftest import make_oracle_graph
-from test_dogleg_cpu import DEFAULT_TRIALS, SIDE_ITERATIONS, side_case, side_run, x1_run
+from test_dogleg_cpu import DEFAULT_TRIALS, SIDE_ITERATIONS, boundary_terminate, side_case, side_run, x1_run
 from test_gpu_lm import fresh, graph_of, handle_of, rel
-from test_lm_cpu import starts
+from test_lm_cpu import BOUNDARY, boundary_start, starts
 
 pytestmark = pytest.mark.gpu
 NUMERIC = -8
@@ -39,6 +39,7 @@ def kinds(a):
 
 # ---------------------------------------------------------------- 1. one trial per kind
 CASES_1 = [(n, v, 0) for n in ("bench50", "bench1000", "random", "grown", "track400_K16") for v in (3, 4) if not (n == "grown" and v == 4)] + [("bench1000", 3, 1)]
+CASES_1 += [(n, 3, gather) for n in ("n255", "n256", "n257") for gather in (0, 1)]     # N + M = 255, 256, 257 (test_lm_cpu.boundary_start): the workgroup boundary of the vertex-parallel kernels
 
 
 @pytest.mark.parametrize("name,variant,gather", CASES_1)
@@ -166,6 +167,28 @@ def test_terminate_leaves_the_estimates_bit_identical(pkg, po, bench_graphs):
     G.close()
 
 
+@pytest.mark.parametrize("total", sorted(BOUNDARY))
+def test_terminate_at_the_workgroup_boundary_leaves_the_estimates_bit_identical(pkg, po, bench_graphs, total):
+    """The test above at N + M = 255, 256, 257 from test_lm_cpu.boundary_start: one workgroup of the vertex-parallel kernels with an
+    idle last thread, exactly one, and a second one whose only thread is a landmark (every total then has two partials, the second from
+    a single thread).  The checker rejects all three Gauss-Newton trials (rho -0.148 / -0.688 / -0.239; dogleg_ref.conditions asserted
+    here again, test_dogleg_cpu.py asserts them without a GPU); the call returns 0 with terminated = 1, rejected = 3,
+    delta_final = 1e4 / 8, and every vertex bit-identical to the start.
+    Measured on an MI355X (profiles/trial_scaffold_gpu_suite.txt): so at all three sizes, chi2 equal to the checker's to the 10 digits printed."""
+    g, P1, L1 = boundary_start(po, bench_graphs, total)
+    r = boundary_terminate(po, g, P1, L1)
+    G = fresh(pkg, dict(g, pose_est=P1, lm_est=L1))
+    done, st, info = G.optimize_dogleg(6, max_trials=3)
+    print("N + M = %d terminate: returned %d, terminated %d, rejected %d, trials %d, n_trials %s, kinds %s, delta[] %s, delta_final %.6g, chi2 %.10g (checker %.10g, rho %.4f)"
+          % (total, done, info["terminated"], info["rejected"], info["trials"], info["n_trials"].tolist(), kinds(info["step_kind"]), info["delta"].tolist(),
+             info["delta_final"], st.chi2_final, r["chi2_final"], r["trials"][0]["rho"]))
+    assert done == 0 and info["terminated"] == 1 and info["rejected"] == 3 and info["trials"] == 3 and info["iterations"] == 0
+    assert info["n_trials"].tolist() == [3] and info["step_kind"].tolist() == [dr.GN] and info["delta"][0] == 2500.0 and info["delta_final"] == 1250.0
+    assert np.array_equal(G.poses(), P1) and np.array_equal(G.landmarks(), L1)
+    assert st.chi2_initial == st.chi2_final and abs(st.chi2_final - r["chi2_final"]) <= 1e-9 * r["chi2_final"]
+    G.close()
+
+
 # ---------------------------------------------------------------- 3. robust kernel and the side passes
 def side_handle(pkg, g, P1, L1, kernels, polar, pri, off):
     G = pkg.Graph(device=0)
@@ -239,6 +262,21 @@ def test_zero_pivot_ends_the_call_with_a_numeric_error(pkg, po, bench_graphs):
     assert d1 == d2 == 2 and s1.numeric_failure == 0 and s1.first_failure == 0
     assert np.array_equal(G.poses(), F.poses()) and np.array_equal(G.landmarks(), F.landmarks()) and s1.chi2_final == s2.chi2_final
     G.close(); F.close()
+
+
+def test_zero_pivot_with_a_second_workgroup_of_one_landmark_ends_the_call(pkg, po, bench_graphs):
+    """The test above at N + M = 257 (test_lm_cpu.boundary_start: the second workgroup of the vertex-parallel kernels is one landmark):
+    GS_ERR_NUMERIC, the start's bits in every vertex, and a following optimize(2) runs clean."""
+    g, P1, L1 = boundary_start(po, bench_graphs, 257)
+    G = fresh(pkg, dict(g, pose_est=P1, lm_est=L1)); G.initialize_optimization()
+    G.debug_fail_at_iteration(1, 1)
+    with pytest.raises(pkg.binding.GsError) as e:
+        G.optimize_dogleg(4)
+    print("N + M = 257 zero pivot: code %d (%s)" % (e.value.code, e.value))
+    assert e.value.code == NUMERIC
+    assert np.array_equal(G.poses(), P1) and np.array_equal(G.landmarks(), L1)
+    done, st = G.optimize(2); assert done == 2 and st.numeric_failure == 0 and st.first_failure == 0
+    G.close()
 
 
 def test_flag_timeout_falls_back_to_level_launches_and_finishes(pkg, bench_graphs):

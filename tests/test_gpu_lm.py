@@ -22,7 +22,7 @@ import pytest
 import lm_ref
 import robust_ref as rr
 from conftest import append_tail, make_oracle_graph, random_graph, split_for_growth
-from test_lm_cpu import REJECTION_LAMBDA0, REJECTION_TRIALS, ROBUST_TRIALS, robust_case, starts
+from test_lm_cpu import BOUNDARY, REJECTION_LAMBDA0, REJECTION_TRIALS, ROBUST_TRIALS, boundary_start, boundary_terminate, robust_case, starts
 
 pytestmark = pytest.mark.gpu
 DIAG3 = (0, 4, 8); DIAG2 = (0, 3)
@@ -57,7 +57,9 @@ def graph_of(pkg, bench_graphs, frontend, name):
         return random_graph(7)
     if name == "track400_K16":
         return pkg.track.bench_graph(pkg.track.generate(400, 150, 16), frontend)
-    return bench_graphs(*{"bench50": (50, 30), "bench1000": (1000, 200), "bench10k": (10000, 2000), "grown": (1000, 200)}[name])[1]
+    sizes = {"bench50": (50, 30), "bench1000": (1000, 200), "bench10k": (10000, 2000), "grown": (1000, 200)}
+    sizes.update({"n%d" % total: nm[:2] for total, nm in BOUNDARY.items()})      # N + M = 255, 256, 257 (test_lm_cpu.boundary_start)
+    return bench_graphs(*sizes[name])[1]
 
 
 def handle_of(pkg, g, name, **kw):
@@ -132,7 +134,8 @@ def test_export_of_a_grown_plan_is_still_refused(pkg, bench_graphs):
 
 # ---------------------------------------------------------------- 2. one trial
 @pytest.mark.parametrize("name,variant", [(n, v) for n in ("bench50", "bench1000", "bench10k", "random", "grown", "track400_K16") for v in (3, 4)
-                                          if not (n == "grown" and v == 4)])      # (append-only growth exists for factor_variant 3 only)
+                                          if not (n == "grown" and v == 4)] +     # (append-only growth exists for factor_variant 3 only)
+                                         [(n + path, 3) for n in ("n255", "n256", "n257") for path in ("", "-gather")])
 def test_one_trial_increment_and_chi2_match_the_checker(pkg, po, bench_graphs, frontend, name, variant):
     """The increment (export_delta) and chi_new of ONE trial against the checker's, lambda in {1e-12 max diag, the default 1e-5 max
     diag, 1e3 max diag} and — added, so that a large lambda is fully asserted too — 1e1 max diag (margins 4.7e-3 .. 2.0e-2).  The grown
@@ -151,9 +154,17 @@ def test_one_trial_increment_and_chi2_match_the_checker(pkg, po, bench_graphs, f
     ill-conditioned system, both far under the 1e-8 floor that decides there).  With a lambda that matters LM is 2 - 6 orders under the plain figure;
     at 1e-12 max diag the system is the undamped one to rounding and the two figures are the same size (1.35x at most, 1000/200 v3),
     far inside 4x.  chi_old at most 1.4e-15, chi_new at most 1.5e-11 (10k/2k, lambda 1e-12: behind the 6.4e-7 increment), lambda_0 exact
-    or 1 ulp.  All 33 trials were accepted on GPU and checker alike."""
+    or 1 ulp.  All 33 trials were accepted on GPU and checker alike.
+    n255 / n256 / n257 (and -gather: linearize_gather = 1): bench graphs with N + M = 255, 256, 257 vertices from their own start, the
+    sizes at which the vertex-parallel kernels go from one workgroup with an idle thread to exactly one to a second one whose only
+    thread is a landmark (test_lm_cpu.boundary_start).  Checker margins there: 0.69 .. 0.75 at 1e-12 and 1e-5 max diag, 1.2e-2 ..
+    1.7e-2 at 1e1, 1.4e-4 .. 1.8e-4 at 1e3.  Measured on an MI355X (profiles/trial_scaffold_gpu_suite.txt): plain increment 1.3e-13 ..
+    1.9e-13 fused, 2.2e-12 .. 3.4e-12 gather; LM increment at most 1.7e-13 fused and 3.4e-12 gather (1e-12 max diag, the undamped system
+    to rounding), chi_new at most 4.1e-15, lambda_0 exact; all 24 trials accepted on both sides."""
+    name, _, path = name.partition("-")
+    kw = dict(factor_variant=variant, **({"linearize_gather": 1} if path == "gather" else {}))
     g0 = graph_of(pkg, bench_graphs, frontend, name)
-    A, g = handle_of(pkg, g0, name, factor_variant=variant)
+    A, g = handle_of(pkg, g0, name, **kw)
     og = make_oracle_graph(po, g); og.build_system(); og.apply_update(og.solve_ldlt(1)); dp_o, dl_o = og.delta()
     done, st = A.optimize(1); assert done == 1
     dp, dl = A.export_delta(); sc = max(np.abs(dp_o).max(), np.abs(dl_o).max())
@@ -169,15 +180,15 @@ def test_one_trial_increment_and_chi2_match_the_checker(pkg, po, bench_graphs, f
         lam = 1e-5 * md if f is None else f * md
         t = lm_ref.trial(po, g, g["pose_est"], g["lm_est"], lam)
         margin = abs(t["chi_old"] - t["chi_new"]) / t["chi_old"]
-        G, _ = handle_of(pkg, g0, name, factor_variant=variant)
+        G, _ = handle_of(pkg, g0, name, **kw)
         done, st, info = G.optimize_lm(1, max_trials=1, **({} if f is None else {"initial_lambda": lam}))
         dp, dl = G.export_delta(); sc = max(np.abs(t["dpose"]).max(), np.abs(t["dlm"]).max())
         e_inc = max(np.abs(dp - t["dpose"]).max(), np.abs(dl - t["dlm"]).max()) / sc
         e_lam = abs(info["lambda_initial"] - lam) / lam
         e_old = abs(info["chi2"][0] - t["chi_old"]) / t["chi_old"]
         e_new = abs(st.chi2_final - t["chi_new"]) / t["chi_new"] if done == 1 else float("nan")
-        print("%s v%d lambda %.3e (%s max diag): plain increment %.2e chi2 %.2e | LM increment %.2e lambda %.2e chi_old %.2e chi_new %.2e | rho %+.4f margin %.2e accepted %d"
-              % (name, variant, lam, "1e-5" if f is None else "%g" % f, y_inc, y_chi, e_inc, e_lam, e_old, e_new, t["rho"], margin, done))
+        print("%s%s v%d lambda %.3e (%s max diag): plain increment %.2e chi2 %.2e | LM increment %.2e lambda %.2e chi_old %.2e chi_new %.2e | rho %+.4f margin %.2e accepted %d"
+              % (name, " " + path if path else "", variant, lam, "1e-5" if f is None else "%g" % f, y_inc, y_chi, e_inc, e_lam, e_old, e_new, t["rho"], margin, done))
         assert e_inc <= tol_inc and e_lam <= 1e-11 and e_old <= 1e-9
         assert info["trials"] == 1 and info["rejected"] == 1 - done and info["terminated"] == 1 - done
         if f != 1e3:
@@ -362,6 +373,43 @@ def test_terminate_leaves_the_estimates_bit_identical(pkg, po, bench_graphs):
     assert st.chi2_initial == st.chi2_final and abs(st.chi2_final - r["chi2_final"]) <= 1e-9 * r["chi2_final"]
     assert abs(G.chi2() - st.chi2_final) <= 1e-12 * st.chi2_final
     G.close()
+
+
+@pytest.mark.parametrize("total", sorted(BOUNDARY))
+def test_terminate_at_the_workgroup_boundary_leaves_the_estimates_bit_identical(pkg, po, bench_graphs, total):
+    """The test above at N + M = 255, 256, 257 from test_lm_cpu.boundary_start: one workgroup of the vertex-parallel kernels with an
+    idle last thread, exactly one, and a second one whose only thread is a landmark (two scale partials, the second from a single
+    thread; the restore of the last landmark is that workgroup's).  The checker rejects all three trials (rho -0.148 / -0.688 / -0.239,
+    margins 0.14 / 0.60 / 0.23: asserted here again, test_lm_cpu.py asserts them without a GPU); the call returns 0 with terminated = 1,
+    rejected = 3 and every pose and landmark holds the bits from before the call.
+    Measured on an MI355X: so at all three sizes; lambda[0] = 8e-12, chi2 12834.73073 / 10548.07652 / 12691.96237 on both sides."""
+    g, P1, L1 = boundary_start(po, bench_graphs, total)
+    r = boundary_terminate(po, g, P1, L1)
+    G = fresh(pkg, dict(g, pose_est=P1, lm_est=L1))
+    P_before, L_before = G.poses(), G.landmarks()
+    done, st, info = G.optimize_lm(6, initial_lambda=REJECTION_LAMBDA0, max_trials=3)
+    print("N + M = %d terminate: returned %d, terminated %d, rejected %d, trials %d, n_trials %s, lambda[] %s, chi2 %.10g (checker %.10g, rho %.4f)"
+          % (total, done, info["terminated"], info["rejected"], info["trials"], info["n_trials"].tolist(), info["lambda"].tolist(), st.chi2_final, r["chi2_final"], r["trials"][0]["rho"]))
+    assert done == 0 and info["terminated"] == 1 and info["rejected"] == 3 and info["trials"] == 3 and info["iterations"] == 0
+    assert info["n_trials"].tolist() == [3] and info["lambda"][0] == 8e-12
+    assert np.array_equal(G.poses(), P_before) and np.array_equal(G.landmarks(), L_before)
+    assert np.array_equal(P_before, P1) and np.array_equal(L_before, L1)
+    assert st.chi2_initial == st.chi2_final and abs(st.chi2_final - r["chi2_final"]) <= 1e-9 * r["chi2_final"]
+    G.close()
+
+
+def test_zero_pivot_with_a_second_workgroup_of_one_landmark_is_a_rejection(pkg, po, bench_graphs):
+    """N + M = 257, a zero pivot injected into the only trial (gs_debug_fail_at_iteration(1, 1), as in the tests above and below;
+    max_trials = 1): the call returns 0 with rejected = 1, terminated = 1 and numeric_failure = 0, and leaves the start's bits in every
+    vertex, the landmark of the second workgroup included; a following optimize(2) runs clean."""
+    g, P1, L1 = boundary_start(po, bench_graphs, 257)
+    Z = fresh(pkg, dict(g, pose_est=P1, lm_est=L1)); Z.optimize(0); Z.debug_fail_at_iteration(1, 1)
+    done, st, info = Z.optimize_lm(4, max_trials=1)
+    print("N + M = 257 zero pivot: returned %d terminated %d rejected %d numeric_failure %d first_failure %d" % (done, info["terminated"], info["rejected"], st.numeric_failure, st.first_failure))
+    assert done == 0 and info["terminated"] == 1 and info["rejected"] == 1 and st.numeric_failure == 0
+    assert np.array_equal(Z.poses(), P1) and np.array_equal(Z.landmarks(), L1)
+    done, st = Z.optimize(2); assert done == 2 and st.numeric_failure == 0
+    Z.close()
 
 
 # ---------------------------------------------------------------- 6. monotone where Gauss-Newton is not
