@@ -253,7 +253,8 @@ int  gs_get_stats(gs_graph *g, gs_stats *stats);      /* plan statistics after i
  * count.  Works with robust kernels, grown plans, factor_variant 3 and 4, workgroup fronts, both linearisation paths; makes the
  * marginals stale like an iteration; leaves no failure, stop or LM state behind that gates a later gs_iterate / gs_optimize.
  * gs_export_system afterwards returns the system of the LAST TRIAL AS IT WAS FACTORISED: H at that trial's starting point with its
- * lambda on the free diagonal scalars (b and the off-diagonal blocks undamped).
+ * lambda on the free diagonal scalars (b and the off-diagonal blocks undamped).  On a grown plan as well: lambda is on the
+ * diagonal scalars of tail poses and tail cones as on those of old vertices (a trial's chi2 at its trial point writes nothing of H or b).
  * Errors: iterations < 0, a tau or initial_lambda that is not finite, tau <= 0, max_trials_after_failure < 1: GS_ERR_INVALID;
  * a host-only handle GS_ERR_NO_DEVICE.  A solver failure the step control cannot turn into a rejected trial ends the call with an
  * error code, NOT with gs_optimize's "return 0" (0 is a regular result here: no trial accepted): GS_ERR_TIMEOUT when a front's flag
@@ -508,11 +509,15 @@ int  gs_get_polar_edges(gs_graph *g, int32_t capacity, int32_t *out_observation_
  *      (vertex arrays in insertion order, edge arrays in the order reported by *_edge_order):
  *      Hpp_diag [N*9], Hll_diag [M*4], Hpp_off [Epp*9] (= A^T Omega B), Hpl [Epl*6] (= A^T Omega B,
  *      3x2 row-major), b_pose [N*3], b_lm [M*2].  Any pointer may be NULL.
+ *      A plan grown by appended keyframes exports the system of the WHOLE graph the handle holds: N, M, Epp and Epl count the
+ *      appended poses, cones and edges too, in the same insertion order; an appended vertex's or edge's blocks come from the tail
+ *      arenas, and an older vertex's entries hold the shares of the appended edges, summed as the solver's fronts read them.
+ *      gs_chi2 changes nothing of it, on a grown plan either.
  * gs_export_delta: the last solve's increment, per vertex in insertion order
  *      (zeros for fixed vertices): dpose [N*3], dlm [M*2].
  * gs_multiply_hessian: y = H v on the device, H the system gs_export_system would return (the last linearisation as it lies in HBM:
  *      robust weights, priors, polar and inactive edges as they went in, the lambda of a preceding gs_optimize_lm trial on the diagonal
- *      included) — and it works on a grown plan, which gs_export_system refuses.  v and y per vertex in insertion order; rows and
+ *      included), on a grown plan as well: the two agree block by block there too.  v and y per vertex in insertion order; rows and
  *      columns of fixed vertices are zero: y is 0 there and v is not read there.  Either output may be NULL.  Changes no state; a
  *      handle that never calls it (or gs_optimize_dogleg) allocates and launches nothing for it.
  *      Errors: a null v, or a v entry on a free vertex that is not finite: GS_ERR_INVALID; a sharded handle GS_ERR_INVALID; a

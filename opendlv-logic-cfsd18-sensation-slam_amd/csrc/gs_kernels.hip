@@ -854,17 +854,35 @@ void launch_linearize(const DevGraph &d, hipStream_t st, hipEvent_t start, hipEv
 //   3. thread 0 walks the tail odometry edges in order: the new pose's share into the LDS accumulators, the older end's share into
 //      its accumulator (a tail pose) or, read-modify-write, into the old pose's H_pp / b entries; off-diagonal blocks to the tail arena;
 //   4. the tail poses' diagonal blocks and rhs out; chi2 of the tail (edges in order) as one more partial for k_update.
+// the two tail kernels (k_linearize_tail, k_chi2_tail) evaluate a tail edge through these, so that the chi2-only pass sees the operands
+// and the expressions of the linearisation: tail observation edge e, tail odometry edge kk (operands of pp_incidence)
+template <bool ROBUST>
+__device__ __forceinline__ void tail_quad_pl(const DevGraph &d, int e, int &p, int &l, PlQuad &q) {
+    p = d.t_pl[2 * e]; l = d.t_pl[2 * e + 1];
+    const double2 cs = reinterpret_cast<const double2 *>(d.pose_cs)[p];
+    quad_pl<ROBUST>(d.pose_est[3 * p], d.pose_est[3 * p + 1], cs.x, cs.y, d.lm_est[2 * l], d.lm_est[2 * l + 1], d.t_pl_z[2 * e], d.t_pl_z[2 * e + 1],
+                    d.t_pl_w[3 * e], d.t_pl_w[3 * e + 1], d.t_pl_w[3 * e + 2], q, d.rk_pl, d.rd_pl);
+}
+struct TailPp { int i, j; int64_t k; double xi[3], xj[3], z5[5], w[6]; double2 ci; bool fi, fj; };
+__device__ __forceinline__ void tail_pp_load(const DevGraph &d, int kk, TailPp &o) {
+    o.i = d.t_pp_ij[2 * kk]; o.j = d.t_pp_ij[2 * kk + 1]; o.k = (int64_t)d.Epp + kk;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { o.xi[c] = d.pose_est[3 * o.i + c]; o.xj[c] = d.pose_est[3 * o.j + c]; }
+#pragma unroll
+    for (int c = 0; c < 5; ++c) o.z5[c] = d.pp_zinv[5 * o.k + c];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) o.w[c] = d.pp_info[6 * o.k + c];
+    o.ci = reinterpret_cast<const double2 *>(d.pose_cs)[o.i];
+    o.fi = d.pose_fixed[o.i]; o.fj = d.pose_fixed[o.j];
+}
 template <bool ROBUST = false>
 __global__ void __launch_bounds__(256) k_linearize_tail(DevGraph d) {
-    constexpr int EC = 512, PC = 16;                                 // == gs::TAIL_PL, gs::TAIL_POSES (launch_linearize_tail checks)
+    constexpr int EC = 512, PC = 16;                                 // == gs::TAIL_PL, gs::TAIL_POSES (tail_launches checks)
     __shared__ double s_p[9][EC], s_l[5][EC], s_chi[EC], s_acc[PC][9];
     const int tid = threadIdx.x;
     for (int e = tid; e < d.tEpl; e += 256) {
-        const int p = d.t_pl[2 * e], l = d.t_pl[2 * e + 1];
-        const double2 cs = reinterpret_cast<const double2 *>(d.pose_cs)[p];
-        PlQuad q;
-        quad_pl<ROBUST>(d.pose_est[3 * p], d.pose_est[3 * p + 1], cs.x, cs.y, d.lm_est[2 * l], d.lm_est[2 * l + 1], d.t_pl_z[2 * e], d.t_pl_z[2 * e + 1],
-                        d.t_pl_w[3 * e], d.t_pl_w[3 * e + 1], d.t_pl_w[3 * e + 2], q, d.rk_pl, d.rd_pl);
+        int p, l; PlQuad q;
+        tail_quad_pl<ROBUST>(d, e, p, l, q);
         const bool fl = d.lm_fixed[l];
 #pragma unroll
         for (int k = 0; k < 6; ++k) { s_p[k][e] = q.Hp[k]; d.t_Hpl[(int64_t)k * d.tcapEpl + e] = fl ? 0.0 : q.W6[k]; }
@@ -896,20 +914,11 @@ __global__ void __launch_bounds__(256) k_linearize_tail(DevGraph d) {
     __syncthreads();
     double chi = 0.0;
     if (tid == 0) {
-        for (int kk = 0; kk < d.tEpp; ++kk) { const int i = d.t_pp_ij[2 * kk], j = d.t_pp_ij[2 * kk + 1];
-            const int64_t k = (int64_t)d.Epp + kk;
-            double xi[3], xj[3], z5[5], w[6];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { xi[c] = d.pose_est[3 * i + c]; xj[c] = d.pose_est[3 * j + c]; }
-#pragma unroll
-            for (int c = 0; c < 5; ++c) z5[c] = d.pp_zinv[5 * k + c];
-#pragma unroll
-            for (int c = 0; c < 6; ++c) w[c] = d.pp_info[6 * k + c];
-            const double2 ci = reinterpret_cast<const double2 *>(d.pose_cs)[i];
-            const bool fi = d.pose_fixed[i], fj = d.pose_fixed[j];
+        for (int kk = 0; kk < d.tEpp; ++kk) { TailPp o; tail_pp_load(d, kk, o);
+            const int i = o.i, j = o.j;
             double Hi[6] = {0, 0, 0, 0, 0, 0}, bi[3] = {0, 0, 0}, Hj[6] = {0, 0, 0, 0, 0, 0}, bj[3] = {0, 0, 0};
-            chi += pp_incidence<true, ROBUST>(d, (int)k, 0, xi, xj, ci.x, ci.y, z5, w, fi, fj, Hi, bi, d.t_Hpp_off + kk, d.tcapEpp);
-            pp_incidence<true, ROBUST>(d, (int)k, 1, xi, xj, ci.x, ci.y, z5, w, fi, fj, Hj, bj);
+            chi += pp_incidence<true, ROBUST>(d, (int)o.k, 0, o.xi, o.xj, o.ci.x, o.ci.y, o.z5, o.w, o.fi, o.fj, Hi, bi, d.t_Hpp_off + kk, d.tcapEpp);
+            pp_incidence<true, ROBUST>(d, (int)o.k, 1, o.xi, o.xj, o.ci.x, o.ci.y, o.z5, o.w, o.fi, o.fj, Hj, bj);
             auto share = [&](int v, const double *H, const double *b) {   // endpoint v's share of the edge
                 if (d.pose_fixed[v]) return;
                 if (v >= d.N) {
@@ -935,17 +944,48 @@ __global__ void __launch_bounds__(256) k_linearize_tail(DevGraph d) {
         for (int c = 0; c < 3; ++c) d.t_b_pose[(int64_t)c * d.tcapN + tid] = s_acc[tid][6 + c];
     }
 }
+// a tail the two tail kernels' LDS arrays hold (gs_upload.cpp sets the capacities to gs::TAIL_PL = 512, gs::TAIL_POSES = 16): ONE predicate for
+// the linearisation and for the chi2-only pass, so that the two never disagree about whether the tail counts
+static inline bool tail_launches(const DevGraph &d) { return d.tN > 0 && d.tcapEpl <= 512 && d.tcapN <= 16; }
 void launch_linearize_tail(const DevGraph &d, hipStream_t st) {
-    if (!(d.tN > 0 && d.tcapEpl <= 512 && d.tcapN <= 16)) return;
+    if (!tail_launches(d)) return;
     if (robust_on(d)) hipLaunchKernelGGL(k_linearize_tail<true>, dim3(1), dim3(256), 0, st, d);
     else hipLaunchKernelGGL(k_linearize_tail<false>, dim3(1), dim3(256), 0, st, d);
 }
+// chi2 of the tail alone, the edges in k_linearize_tail's order, as partial `slot`: NOTHING of H or b is written (the chi2-only pass of a
+// grown plan must leave the last linearisation in HBM as it does on any other plan: gs_export_system, gs_multiply_hessian, the damped
+// system of an LM trial and a dogleg retrial read it afterwards)
+template <bool ROBUST = false>
+__global__ void __launch_bounds__(256) k_chi2_tail(DevGraph d, int slot) {
+    constexpr int EC = 512;                                          // == gs::TAIL_PL (tail_launches checks)
+    __shared__ double s_chi[EC];
+    const int tid = threadIdx.x;
+    for (int e = tid; e < d.tEpl; e += 256) {
+        int p, l; PlQuad q;
+        tail_quad_pl<ROBUST>(d, e, p, l, q);
+        s_chi[e] = q.chi;                                            // (a tail pose is free: the edge counts)
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double chi = 0.0;
+        for (int kk = 0; kk < d.tEpp; ++kk) { TailPp o; tail_pp_load(d, kk, o);
+            double H[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
+            chi += pp_incidence<false, ROBUST>(d, (int)o.k, 0, o.xi, o.xj, o.ci.x, o.ci.y, o.z5, o.w, o.fi, o.fj, H, b);
+        }
+        for (int e = 0; e < d.tEpl; ++e) chi += s_chi[e];
+        d.chi2_partial[slot] = chi;
+    }
+}
 void launch_chi2_only(const DevGraph &d, hipStream_t st) {
-    if (d.tN > 0 && d.n_wtiles > 0) { launch_linearize(d, st); launch_linearize_tail(d, st); launch_linearize_finalize(d, st); return; }   // a grown plan: the full pass (the gather kernels do not know the tail)
     const int gp = (d.N + 255) / 256;
     if (gp > 0 && robust_on(d)) hipLaunchKernelGGL((k_linearize_pose_gather<false, true>), dim3(gp), dim3(256), 0, st, d);
     else if (gp > 0) hipLaunchKernelGGL(k_linearize_pose_gather<false>, dim3(gp), dim3(256), 0, st, d);
-    hipLaunchKernelGGL(k_reduce_chi2, dim3(1), dim3(256), 0, st, d, gp);
+    // a grown plan (only a plan of the fused path grows): the tail's edges as one more partial behind the gather kernel's, which sweeps the
+    // base; chi2_partial has n_chi2_partial + 1 >= gp + 1 entries (gs_upload.cpp)
+    const bool tail = tail_launches(d) && d.n_wtiles > 0;
+    if (tail && robust_on(d)) hipLaunchKernelGGL(k_chi2_tail<true>, dim3(1), dim3(256), 0, st, d, gp);
+    else if (tail) hipLaunchKernelGGL(k_chi2_tail<false>, dim3(1), dim3(256), 0, st, d, gp);
+    hipLaunchKernelGGL(k_reduce_chi2, dim3(1), dim3(256), 0, st, d, gp + (tail ? 1 : 0));
 }
 // ---- gs_get_edge_chi2: s = e^T W e of every edge of one kind at the current estimates and the weight rho'(s) of the kind's kernel.
 // A thread per edge, insertion order (the host hands the per-edge index table over: gs_device.hpp); s comes out of the SAME

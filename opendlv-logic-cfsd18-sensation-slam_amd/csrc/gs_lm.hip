@@ -70,7 +70,7 @@ __global__ void __launch_bounds__(256) k_lm_damp(DevGraph d, LmDev lm, int par, 
 }
 
 // scale = sum_j D_j (lambda D_j + b_j) over the free scalars, g2o's computeScale: one partial per workgroup.  Runs BEHIND the update
-// (dpose / dlm are the increment) and BEFORE the chi2 pass (on a grown plan that pass is a full linearisation: it overwrites b).
+// (dpose / dlm are the increment) and before the chi2 pass (which reads the new estimates and writes nothing of H or b).
 __global__ void __launch_bounds__(256) k_lm_scale(DevGraph d, LmDev lm, int par) {
     __shared__ double red[5];
     LmState &S = lm.state[par];

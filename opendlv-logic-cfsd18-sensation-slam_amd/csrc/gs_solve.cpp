@@ -4,6 +4,7 @@
 #include "../../include/graphslam_debug.h"
 #include "gs_private.hpp"
 #include "gs_hmul.hpp"
+#include "gs_export_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -359,7 +360,7 @@ static int dl_reserve(gs_graph *g) {
     return rc;
 }
 // one trial, asynchronous: today's linearise / factor / back-solve / update launches in today's launch modes, with the dogleg kernels and
-// the two Hessian products around them.  Both products run before the chi2 pass (on a grown plan it is a full linearisation)
+// the two Hessian products around them.  Both products run before the chi2 pass (which writes nothing of H or b, on a grown plan either: the order is free)
 static void enqueue_dogleg_trial(gs_graph *g, int par) {
     const DlDev &dl = g->dl.dev; const bool tree = g->d.tree != 0;
     ++g->d.iter;
@@ -456,31 +457,33 @@ extern "C" int gs_export_system(gs_graph *g, double *Hpp_diag, double *Hll_diag,
                                 double *b_pose, double *b_lm, int32_t *pp_order, int32_t *pl_order) {
     if (!g) return fail(GS_ERR_INVALID, "null graph");
     if (!g->dev_valid) return fail(GS_ERR_NOT_INITIALIZED, "nothing linearised yet");
-    if (g->d.tN > 0) return fail(GS_ERR_INVALID, "the plan has grown by appended poses: their blocks live in the tail arenas, which this export does not read (gs_initialize_optimization with GS_GROW=0 rebuilds)");
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
     const DevGraph &d = g->d;
     // an iteration and gs_compute_marginals leave the landmark blocks as per-edge partials (the fronts sum them): sum them here, so
-    // that H_ll and b_l are those of the last linearisation whichever call ran it
+    // that H_ll and b_l are those of the last linearisation whichever call ran it (an old cone's first slot holds the tail's shares)
     launch_linearize_finalize(d, g->stream, false);
     { const hipError_t e = hipGetLastError(); if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("export: ") + hipGetErrorString(e)); }
-    // the device keeps these arrays structure-of-arrays (and the diagonal blocks packed symmetric); the
-    // export format is array-of-blocks, full and row-major
-    const size_t N = (size_t)d.N, M = (size_t)d.M, Epp = (size_t)d.Epp, Epl = (size_t)d.Epl;
+    // the device keeps these arrays structure-of-arrays (and the diagonal blocks packed symmetric), a grown plan's tail in arenas of
+    // their own; the export format is array-of-blocks, full and row-major: gs_export_host.hpp
+    const size_t N = (size_t)d.N, M = (size_t)d.M, Epp = (size_t)d.Epp, Epl = (size_t)d.Epl + (size_t)d.tEpl;
     const size_t L = (size_t)d.ell_len;
+    if (g->plan.ell_of_ins.size() < Epl) return fail(GS_ERR_INVALID, "export: the plan does not cover the device's observation edges");
+    const bool tail = d.tN > 0;                                      // (tail cones and edges come with tail poses only)
+    const size_t cN = tail ? (size_t)d.tcapN : 0, cM = tail ? (size_t)d.tcapM : 0, cPP = tail ? (size_t)d.tcapEpp : 0, cPL = tail ? (size_t)d.tcapEpl : 0;
     std::vector<double> t0(N * 6), t1(M * 3), t2(Epp * 9), t3(L * 6), t4(N * 3), t5(M * 2);
+    std::vector<double> u0(cN * 6), u1(cM * 3), u2(cPP * 9), u3(cPL * 6), u4(cN * 3), u5(cM * 2);
     auto dl = [&](std::vector<double> &dst, const double *src) -> hipError_t {
         return dst.empty() ? hipSuccess : hipMemcpyAsync(dst.data(), src, dst.size() * sizeof(double), hipMemcpyDeviceToHost, g->stream); };
     HIP_TRY(dl(t0, d.Hpp_diag)); HIP_TRY(dl(t1, d.Hll_diag)); HIP_TRY(dl(t2, d.Hpp_off)); HIP_TRY(dl(t3, d.Hpl));
     HIP_TRY(dl(t4, d.b_pose)); HIP_TRY(dl(t5, d.b_lm));
+    HIP_TRY(dl(u0, d.t_Hpp_diag)); HIP_TRY(dl(u1, d.t_Hll_diag)); HIP_TRY(dl(u2, d.t_Hpp_off)); HIP_TRY(dl(u3, d.t_Hpl));
+    HIP_TRY(dl(u4, d.t_b_pose)); HIP_TRY(dl(u5, d.t_b_lm));
     HIP_TRY(hipStreamSynchronize(g->stream));
-    static const int sym3[3][3] = {{0, 1, 2}, {1, 3, 4}, {2, 4, 5}}, sym2[2][2] = {{0, 1}, {1, 2}};
-    if (Hpp_diag) for (size_t p = 0; p < N; ++p) for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) Hpp_diag[9 * p + 3 * r + c] = t0[sym3[r][c] * N + p];
-    if (Hll_diag) for (size_t l = 0; l < M; ++l) for (int r = 0; r < 2; ++r) for (int c = 0; c < 2; ++c) Hll_diag[4 * l + 2 * r + c] = t1[sym2[r][c] * M + l];
-    if (Hpp_off) for (size_t k = 0; k < Epp; ++k) for (int c = 0; c < 9; ++c) Hpp_off[9 * k + c] = t2[c * Epp + k];
-    if (Hpl) for (size_t k = 0; k < Epl; ++k) { const int32_t e = g->plan.ell_of_ins[k];                 // insertion order; an edge outside this rank's layout: zeros
-        for (int c = 0; c < 6; ++c) Hpl[6 * k + c] = e >= 0 ? t3[c * L + (size_t)e] : 0.0; }
-    if (b_pose) for (size_t p = 0; p < N; ++p) for (int c = 0; c < 3; ++c) b_pose[3 * p + c] = t4[c * N + p];
-    if (b_lm) for (size_t l = 0; l < M; ++l) for (int c = 0; c < 2; ++c) b_lm[2 * l + c] = t5[c * M + l];
+    const ExportCounts cnt{(int64_t)N, (int64_t)M, (int64_t)Epp, (int64_t)L, (int64_t)Epl, tail ? d.tN : 0, tail ? d.tM : 0, tail ? d.tEpp : 0, tail ? d.tEpl : 0,
+                           (int64_t)cN, (int64_t)cM, (int64_t)cPP, (int64_t)cPL};
+    const ExportSrc src{t0.data(), t1.data(), t2.data(), t3.data(), t4.data(), t5.data(), u0.data(), u1.data(), u2.data(), u3.data(), u4.data(), u5.data(),
+                        g->plan.ell_of_ins.data()};
+    export_layout(cnt, src, ExportDst{Hpp_diag, Hll_diag, Hpp_off, Hpl, b_pose, b_lm});
     if (pp_order) std::memcpy(pp_order, g->plan.pp_order.data(), g->plan.pp_order.size() * sizeof(int32_t));
     if (pl_order) for (size_t k = 0; k < Epl; ++k) pl_order[k] = (int32_t)k;                 // exported in insertion order
     return GS_OK;

@@ -277,6 +277,52 @@ def linearize(g, kernels=None, poses=None, lms=None):
     return X.finish()
 
 
+def magnitudes(g, poses=None, lms=None):
+    """(S, n) per entry of the six arrays as Exact.S / Exact.n without a robust kernel, restated in float64 numpy for graphs that are too
+    large for mpmath (S only scales a bound: its own rounding, 1e-15 relative, does not matter; test_tail_exact_cpu.py holds it to Exact.S)"""
+    P = np.asarray(g["pose_est"] if poses is None else poses, dtype=np.float64).reshape(-1, 3); Lm = np.asarray(g["lm_est"] if lms is None else lms, dtype=np.float64).reshape(-1, 2)
+    N, M = len(P), len(Lm)
+    pf = np.zeros(N, dtype=bool); pf[np.asarray(g["fixed_poses"], dtype=np.int64)] = True
+    lf = np.zeros(M, dtype=bool); lf[np.asarray(g["fixed_landmarks"], dtype=np.int64)] = True
+    pp_i, pp_j = np.asarray(g["pp_i"], dtype=np.int64), np.asarray(g["pp_j"], dtype=np.int64)
+    pl_p, pl_l = np.asarray(g["pl_p"], dtype=np.int64), np.asarray(g["pl_l"], dtype=np.int64)
+    sizes = dict(Hpp_diag=N, Hll_diag=M, Hpp_off=len(pp_i), Hpl=len(pl_p), b_pose=N, b_lm=M)
+    S = {k: np.zeros((sizes[k], WIDTH[k])) for k in ARRAYS}; n = {k: np.zeros((sizes[k], WIDTH[k]), dtype=np.int64) for k in ARRAYS}
+
+    def put(name, rows, vals, mask):
+        np.add.at(S[name], rows[mask], vals.reshape(len(rows), -1)[mask]); np.add.at(n[name], rows[mask], 1)
+    # odometry edges (mag_pp)
+    xi, xj, z = P[pp_i], P[pp_j], np.asarray(g["pp_z"], dtype=np.float64).reshape(-1, 3)
+    W = np.abs(np.asarray(g["pp_info"], dtype=np.float64).reshape(-1, 3, 3))
+    ci, si, cz, sz = np.abs(np.cos(xi[:, 2])), np.abs(np.sin(xi[:, 2])), np.abs(np.cos(z[:, 2])), np.abs(np.sin(z[:, 2]))
+    ax, ay = np.abs(xj[:, 0]) + np.abs(xi[:, 0]), np.abs(xj[:, 1]) + np.abs(xi[:, 1])
+    qx, qy = ci * ax + si * ay + np.abs(z[:, 0]), si * ax + ci * ay + np.abs(z[:, 1])
+    e = np.stack([cz * qx + sz * qy, sz * qx + cz * qy, np.abs(xj[:, 2]) + np.abs(xi[:, 2]) + np.abs(z[:, 2])], axis=1)
+    o, l = np.zeros_like(ci), np.ones_like(ci)
+    Z = np.stack([np.stack([cz, sz, o], 1), np.stack([sz, cz, o], 1), np.stack([o, o, l], 1)], 1)
+    Ji = np.stack([np.stack([ci, si, si * ax + ci * ay], 1), np.stack([si, ci, ci * ax + si * ay], 1), np.stack([o, o, l], 1)], 1)
+    Jj = np.stack([np.stack([ci, si, o], 1), np.stack([si, ci, o], 1), np.stack([o, o, l], 1)], 1)
+    A, B = Z @ Ji, Z @ Jj
+    fi, fj = ~pf[pp_i], ~pf[pp_j]; k = np.arange(len(pp_i))
+    AT, BT = A.transpose(0, 2, 1), B.transpose(0, 2, 1); We = (W @ e[:, :, None])
+    put("Hpp_diag", pp_i, AT @ W @ A, fi); put("b_pose", pp_i, AT @ We, fi)
+    put("Hpp_diag", pp_j, BT @ W @ B, fj); put("b_pose", pp_j, BT @ We, fj)
+    put("Hpp_off", k, AT @ W @ B, fi & fj)
+    # observation edges (mag_pl)
+    xp, lm, z = P[pl_p], Lm[pl_l], np.asarray(g["pl_z"], dtype=np.float64).reshape(-1, 2)
+    W = np.abs(np.asarray(g["pl_info"], dtype=np.float64).reshape(-1, 2, 2))
+    c, s = np.abs(np.cos(xp[:, 2])), np.abs(np.sin(xp[:, 2])); px, py, lx_, ly = np.abs(xp[:, 0]), np.abs(xp[:, 1]), np.abs(lm[:, 0]), np.abs(lm[:, 1])
+    e = np.stack([c * lx_ + s * ly + c * px + s * py + np.abs(z[:, 0]), s * lx_ + c * ly + s * px + c * py + np.abs(z[:, 1])], axis=1)
+    A = np.stack([np.stack([c, s, c * ly + c * py + s * lx_ + s * px], 1), np.stack([s, c, s * ly + s * py + c * lx_ + c * px], 1)], 1)
+    B = np.stack([np.stack([c, s], 1), np.stack([s, c], 1)], 1)
+    fp, fl = ~pf[pl_p], ~lf[pl_l]; k = np.arange(len(pl_p))
+    AT, BT = A.transpose(0, 2, 1), B.transpose(0, 2, 1); We = (W @ e[:, :, None])
+    put("Hpp_diag", pl_p, AT @ W @ A, fp); put("b_pose", pl_p, AT @ We, fp)
+    put("Hll_diag", pl_l, BT @ W @ B, fl); put("b_lm", pl_l, BT @ We, fl)
+    put("Hpl", k, AT @ W @ B, fp & fl)
+    return {k: v.reshape(-1) for k, v in S.items()}, {k: v.reshape(-1) for k, v in n.items()}
+
+
 # ---- the checks
 def _err(got, exact):
     got = np.asarray(got, dtype=np.float64).reshape(-1)

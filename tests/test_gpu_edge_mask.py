@@ -90,10 +90,9 @@ def same_bits(a, b):
 
 
 def system_of(G):
-    """(export_system() of a fresh linearisation, chi2); a plan with a tail exports nothing — gs_export_system refuses it, an existing
-    rule (it does not read the tail arenas, test_gpu_lm.py) — so a grown plan is compared by chi2, per-edge values and estimates"""
+    """(export_system() of a fresh linearisation, chi2); a grown plan exports the whole graph's system, tail arenas included"""
     G.linearize()
-    return ({} if G.plan_growths() > 0 else G.export_system()), G.chi2()
+    return G.export_system(), G.chi2()
 
 
 # ---------------------------------------------------------------- 1. bit for bit against zero-information edges
@@ -106,8 +105,8 @@ def test_masked_handle_equals_zero_information_edges_bit_for_bit(pkg, bench_grap
     Z = handle(pkg, name, em.masked(g, a_pp, a_pl), base, tail, linearize_gather=gather)
     SA, ca = system_of(A); SZ, cz = system_of(Z)
     sys_same = {k: same_bits(SA[k], SZ[k]) for k in SA}
-    zero_blocks = name == "grown" or (not SA["Hpl"][~a_pl].any() and not SA["Hpp_off"][~a_pp].any())
-    assert (name == "grown") == (len(SA) == 0) and len(SA) == len(SZ)
+    zero_blocks = not SA["Hpl"][~a_pl].any() and not SA["Hpp_off"][~a_pp].any()
+    assert len(SA) == len(BLOCKS) == len(SZ) and (name != "grown" or (A.plan_growths() > 0 and not a_pl[len(base["pl_p"]):].all()))
     PA, LA = three_iterations(A); PZ, LZ = three_iterations(Z)
     print("%s gather=%d (%d + %d edges off): system %s chi2 %.17g / %.17g estimates after 3 iterations %s %s; growths %d"
           % (name, gather, (~a_pp).sum(), (~a_pl).sum(), sys_same, ca, cz, same_bits(PA, PZ), same_bits(LA, LZ), A.plan_growths()))
@@ -223,8 +222,9 @@ def test_flags_survive_a_full_structure_phase(pkg, po, bench_graphs, gather):
 
 def test_flags_survive_a_growth_step(pkg, po, bench_graphs):
     """Deactivate on a grown plan (tail slots among the inactive edges), then one more keyframe: absorbed by growth (plan_growths
-    increases), the flags are what they were, the new edges are active.  (gs_export_system refuses a plan with a tail: the inactive
-    edges are seen in chi2 1e-10, the per-edge s 1e-11 and weights, and three iterations 1e-9 against the oracle on the masked graph.)"""
+    increases), the flags are what they were, the new edges are active.  The inactive edges are seen in the exported blocks (exact
+    zeros on them, the rest 1e-11 against the oracle on the masked graph), chi2 1e-10, the per-edge s 1e-11 and weights, and three
+    iterations 1e-9."""
     g0 = bench_graphs(1000, 200)[1]
     base, tail, full7 = split_for_growth(g0, GROW_H + 1, GROW_KEEP)
     _, _, full = split_for_growth(g0, GROW_H, GROW_KEEP - 1)        # what the handle holds after its first growth step: the stretch without its last pose
@@ -247,6 +247,10 @@ def test_flags_survive_a_growth_step(pkg, po, bench_graphs):
     chi = G.chi2()
     gm = em.masked(full_now, b_pp, b_pl); chi_o = make_oracle_graph(po, gm).chi2()
     s, w = G.edge_chi2("observation"); s_ref = rr.edge_s(full_now, full_now["pose_est"], full_now["lm_est"])[1]
+    G.linearize(); S = G.export_system(); ref = make_oracle_graph(po, gm).linearize_blocks()
+    figs = {k: rel(S[k], ref[k]) for k in BLOCKS}
+    print("growth step: exported blocks against the oracle on the masked graph: %s" % " ".join("%s %.2e" % kv for kv in figs.items()))
+    assert zero_rows(S, b_pp, b_pl) and all(v < 1e-11 for v in figs.values()) and G.plan_growths() == n0 + 1
     done, st = G.optimize(3); og = make_oracle_graph(po, gm); og.optimize(3, ordering=1)
     e_p, e_l = rel(G.poses(), og.poses()), rel(G.landmarks(), og.landmarks())
     print("growth step: growths %d -> %d; chi2 before %.2e after %.2e; per-edge s %.2e, weight 0 on %d edges; optimize(3) poses %.2e landmarks %.2e"

@@ -36,6 +36,7 @@ import pytest
 
 from conftest import append_tail, split_for_growth
 import exact_ref as xr
+import lin_exact_ref as lx
 from plan_exec import Plan
 import selinv_exec as sx
 import shape_graphs as sg
@@ -178,8 +179,10 @@ def test_solver_launch_modes(pkg, bench_graphs, env):
 
 def test_growth_across_the_wave_workgroup_split(pkg, frontend):
     """K = 16 track of 1 000 poses, three appended keyframes: fronts of 61 and 63 scalars grow to 64 and 72 (a wave front becomes a
-    workgroup front).  A grown plan's blocks live in tail arenas that gs_export_system does not read: H and b are those of a fresh
-    handle of the whole graph linearised at the grown handle's estimates (the same per-edge kernels)."""
+    workgroup front).  H and b are the grown handle's own export (tail arenas and the tail's shares in base storage); a fresh handle of
+    the whole graph linearised at the grown handle's estimates is the cross-check: the two systems agree entry by entry within twice the
+    linearisation bound 2 (34 + n) u S (each is within it of the exact system; S and n from lin_exact_ref.magnitudes, exact zeros where
+    S = 0).  test_gpu_tail_exact.py holds both handles to the mpmath reference itself on this track cut to 60 poses."""
     t = pkg.track.generate(1000, 200, 16); g = pkg.track.bench_graph(t, frontend)
     base, tail, full = split_for_growth(g, 3)
     G = fresh(pkg, base); G.optimize(2)
@@ -192,9 +195,18 @@ def test_growth_across_the_wave_workgroup_split(pkg, frontend):
     assert ((f0 <= 63) & (f1 >= 64)).any(), "no front crossed from a wave to a workgroup"
 
     def system():
+        """the grown handle's system at its current estimates (gs_linearize, as the fresh handle below) against a fresh handle's"""
+        G.linearize(); own = G.export_system()
         F = fresh(pkg, dict(full, pose_est=G.poses(), lm_est=G.landmarks()))
         F.linearize(); sysm = F.export_system(); F.close()
-        return xr.BlockSystem(sysm, full, P.pose_gidx, P.lm_gidx)
+        Sm, n = lx.magnitudes(full, G.poses(), G.landmarks()); worst = 0.0
+        for k in own:
+            assert own[k].shape == sysm[k].shape, k
+            d = np.abs(own[k] - sysm[k]).reshape(-1); tol = 2 * lx.C(n[k]) * U * Sm[k]
+            assert np.all(d <= tol), (k, int(np.argmax(d - tol)), float((d - tol).max()))
+            worst = max(worst, float((d[tol > 0] / tol[tol > 0]).max()))
+        print("growth: the grown handle's export against a fresh handle's: worst |difference| / (2 C(n) u S) %.4f" % worst)
+        return xr.BlockSystem(own, full, P.pose_gidx, P.lm_gidx)
     S = system()
     done, st = G.optimize(1)
     assert done == 1 and st.numeric_failure == 0

@@ -10,10 +10,9 @@ reduction), with the bound of the corresponding test_gpu_parity.py test as the f
 increments 1e-8 of the largest increment — 1e-9 on the random graph —, estimates and chi2 1e-9).  Every test prints its figures
 before it asserts (-s); the printed run is profiles/lm_gpu_suite.txt.
 
-NOT as the issue of this feature states it: the damping-as-factorised test does not export the system of a GROWN plan.
-gs_export_system refuses a plan with a tail (an existing rule: it does not read the tail arenas), and on a grown plan a trial's chi2
-pass is a full linearisation, which leaves the undamped system at x_try behind: there is no damped system left to export.  The tail
-arenas are pinned through what they decide instead, on a plan grown by 6 poses AND 2 cones (grown(): an open stretch of the lap):
+The damping-as-factorised test has its GROWN case in test_damping_as_factorised_on_a_grown_plan (gs_export_system reads the tail
+arenas, and a trial's chi2 pass on a grown plan writes nothing of H: k_chi2_tail).  The tail arenas are also pinned through what they
+decide, on a plan grown by 6 poses AND 2 cones (grown(): an open stretch of the lap):
 a six-iteration trajectory with seven rejections against the checker, a terminated call compared bit for bit on every vertex, one
 trial at four lambda, and lambda_0 with the largest diagonal entry on a tail pose."""
 import numpy as np
@@ -122,13 +121,39 @@ def test_damping_as_factorised(pkg, po, bench_graphs, frontend, name, gather):
     G.close()
 
 
-def test_export_of_a_grown_plan_is_still_refused(pkg, bench_graphs):
-    """(the existing rule of gs_export_system; why test 1 has no grown case: module docstring)"""
+def test_damping_as_factorised_on_a_grown_plan(pkg, po, bench_graphs):
+    """test_damping_as_factorised on a GROWN handle (gs_export_system used to refuse one): after optimize_lm(1, initial_lambda,
+    max_trials = 1) the exported diagonal blocks minus the oracle's at the trial's starting estimates are lambda on every free diagonal
+    scalar — on the 6 tail poses and the 2 tail cones too, where the header promises "as it was factorised" — and 0 elsewhere; the
+    off-diagonal blocks and b are the oracle's.  lambda = 0.01 max diag(H); bound 1e-11 of each array's largest entry, as there.  (The chi2
+    at the trial point used to be a whole linearisation on a grown plan and left the undamped system at x_try: k_chi2_tail.)"""
     G, full = grown(pkg, bench_graphs(1000, 200)[1])
-    G.optimize_lm(1, max_trials=1)
-    with pytest.raises(pkg.binding.GsError) as e:
-        G.export_system()
-    assert e.value.code == -1
+    lam = 0.01 * lm_ref.max_diag(po, full, full["pose_est"], full["lm_est"], {})
+    ref = make_oracle_graph(po, full).linearize_blocks()
+    done, st, info = G.optimize_lm(1, initial_lambda=lam, max_trials=1)
+    assert info["trials"] == 1 and info["lambda_initial"] == lam and G.plan_growths() > 0
+    S = G.export_system()
+    N, M = len(full["pose_est"]), len(full["lm_est"]); Nb, Mb = N - GROWN_H, M - 2
+    assert S["Hpp_diag"].shape == (N, 9) and S["Hll_diag"].shape == (M, 4) and S["Hpl"].shape == (len(full["pl_p"]), 6)
+    fp, fl = free_masks(full)
+    assert fp[Nb:].all() and fl[Mb:].all()
+    want = {k: v.copy() for k, v in ref.items()}
+    for c in DIAG3:
+        want["Hpp_diag"][fp, c] += lam
+    for c in DIAG2:
+        want["Hll_diag"][fl, c] += lam
+    dpp = (S["Hpp_diag"] - ref["Hpp_diag"]); dll = (S["Hll_diag"] - ref["Hll_diag"])
+    figs = {k: rel(S[k], want[k]) for k in want}
+    print("grown lambda %.6g accepted %d: " % (lam, done) + " ".join("%s %.2e" % kv for kv in figs.items()) +
+          " | lambda on the tail: poses %.3e cones %.3e off" % (np.abs(dpp[Nb:][:, DIAG3] - lam).max(), np.abs(dll[Mb:][:, DIAG2] - lam).max()))
+    for k, v in figs.items():
+        assert v < 1e-11, k
+    tol = 1e-11 * np.abs(want["Hpp_diag"]).max()
+    assert np.abs(dpp[fp][:, DIAG3] - lam).max() <= tol and np.abs(dpp[~fp]).max(initial=0.0) == 0.0
+    assert np.abs(dpp[Nb:][:, DIAG3] - lam).max() <= tol and np.abs(np.delete(dpp, DIAG3, axis=1)).max() <= tol
+    tol = 1e-11 * np.abs(want["Hll_diag"]).max()
+    assert np.abs(dll[fl][:, DIAG2] - lam).max() <= tol and np.abs(dll[~fl]).max(initial=0.0) == 0.0
+    assert np.abs(dll[Mb:][:, DIAG2] - lam).max() <= tol
     G.close()
 
 

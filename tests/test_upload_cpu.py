@@ -20,3 +20,17 @@ def test_upload_table_builders_under_address_and_undefined_sanitizers(tmp_path):
                            os.path.join(ROOT, "tests", "upload_tables_san.cpp"), os.path.join(CSRC, "gs_plan.cpp"), "-o", exe, "-lpthread"])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "upload tables: ok" in out.stdout, out.stdout + out.stderr
+
+
+def test_export_layout_under_address_and_undefined_sanitizers(tmp_path):
+    """tests/export_layout_san.cpp: a stand-alone program (its own main, no HIP, nothing loaded into python) around csrc/gs_export_host.hpp,
+    the device-layout -> export-layout conversion of gs_export_system.  Index-coded planes with no tail, a tail of 1, a tail at TAIL_POSES /
+    TAIL_LMS / TAIL_PP / TAIL_PL and capacities larger than the counts: every exported entry names the plane and index it must come from,
+    the guard cells around every output are untouched, a null output is skipped."""
+    cxx = shutil.which("g++") or shutil.which("clang++")
+    assert cxx, "no host C++ compiler"
+    exe = str(tmp_path / "export_layout_san")
+    subprocess.check_call([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-I", CSRC,
+                           os.path.join(ROOT, "tests", "export_layout_san.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "export layout: ok" in out.stdout, out.stdout + out.stderr
