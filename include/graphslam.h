@@ -651,6 +651,70 @@ int  gs_map_size(gs_graph *g);
 int  gs_frame_frontend(gs_graph *g, const double pose_xytheta[3], const double *obs_4xk, int32_t k, double threshold,
                        double type_tol, int32_t signed_type, double *out_zxy, double *out_gxy, int32_t *out_index);
 
+/* ---- covariance-gated association: the nearest cone by Mahalanobis distance inside a chi-square gate --------------
+ * The loops these replace are the same two as above (src/slam.cpp:570-607, the association of addConesToMap, and :350-382, the
+ * localizer's), which take the LOWEST map index inside a fixed Euclidean radius.  Here every map cone carries a 2x2 covariance (from
+ * gs_compute_marginals or the caller), the measurement carries a range / bearing noise model, and the winner is the admissible cone with
+ * the SMALLEST Mahalanobis distance.  The reference has no noise model: the rule and the defaults of gs_nn_params are build-defined.
+ *
+ * Rule.  Observation i of pose p = pose_of_obs[i] = (t, theta):  z = its CoG-frame XY (the A0 formula above, quirks included),
+ *      w = R(theta) z,  g = w + t,  r^2 = zx^2 + zy^2,  wp = (-w_y, w_x).
+ *      Q = (sigma_range^2 / r^2) w w^T + sigma_bearing^2 wp wp^T + sigma_xy^2 I      range along the ray, bearing across it (the bearing
+ *                                                                                     is taken at the pose's origin, as the polar edges do)
+ *      P = G Sigma_p G^T,  G = [I2 | wp],  Sigma_p = the pose's 3x3 covariance, row-major, the upper triangle read; NULL = zero
+ *      Q + P is computed once per observation.  Candidate cone j at l_j with covariance Sigma_j (row-major 2x2, entry [1] read):
+ *      S = Sigma_j + (Q + P),  nu = l_j - g,  det = S00 S11 - S01^2,  d2 = (S11 nu0^2 - 2 S01 nu0 nu1 + S00 nu1^2) / det.
+ *      j is admissible iff ALL of  |type_j - type_i| < type_tol,  sqrt(nu0^2 + nu1^2) < max_distance,  det > 0,  S00 > 0,  d2 < gate_chi2
+ *      hold (positive tests: any NaN skips the candidate).
+ *      index     = the admissible j with the smallest d2, exact ties to the lowest index; -1 when there is none
+ *      d2        = its d2; +inf when there is none
+ *      second_d2 = the smallest d2 among the OTHER admissible candidates, +inf when there is none (what counts as ambiguous is the caller's call)
+ *      A query whose g is not finite (azimuth 0) or whose r is 0 gets -1.  The cross-covariance Sigma(pose, cone) is IGNORED: for a
+ *      candidate pair without an edge it lies outside the pattern of the factor, so the selected inversion does not have it.
+ *      All paths below (batch with either search, resident with either search, the frame call) return identical bits.
+ *
+ * gs_map_set_cov / gs_map_get_cov: row-major 2x2 blocks of the resident map's cones [first, first + n).  set refuses (GS_ERR_INVALID, all
+ *      or nothing) a block that is not finite, not bitwise symmetric or has a negative diagonal, and a range beyond the end of the map.
+ *      Cones of gs_map_append have zero covariance until one is set; gs_map_clear drops them, gs_map_set_xy leaves them, growth keeps them.
+ *      The array exists from the first set call on: a handle that never sets one allocates and launches nothing for it.
+ * gs_map_set_cov_from_marginals: map cone first + k takes the 2x2 block of landmark lm_ids[k] (-1: zeros) out of the last
+ *      gs_compute_marginals — device to device, one gather kernel, no host round trip of the values.  Unknown id GS_ERR_UNKNOWN_ID; stale or
+ *      missing marginals GS_ERR_NOT_INITIALIZED (the getters' test).
+ * gs_associate_nn_batch: host arrays in gs_associate_batch's layout plus map_cov (n_map x 4, NULL = zeros) and pose_cov (n_poses x 9,
+ *      NULL = zeros); out_d2 / out_second_d2 may be NULL.  Grid (cell edge from max_distance) from 2048 cones, LDS tiles below;
+ *      gs_debug_options.assoc_grid forces either, as for gs_associate_batch.
+ * gs_associate_nn_resident: everything in DEVICE memory against the resident map and its covariances, asynchronous on the handle's stream.
+ *      dev_pose_cov, dev_out_d2, dev_out_second_d2 may be NULL.  A dev_obs that is not 32-byte aligned is GS_ERR_INVALID; an observation whose
+ *      pose_of_obs lies outside [0, n_poses) gets -1 (nothing is read through it).
+ * gs_frame_frontend_nn: one frame in one launch, as gs_frame_frontend; pose_cov_3x3 may be NULL.
+ * Errors (before the device is touched): a null pointer, a parameter that is not finite, gate_chi2 <= 0, max_distance <= 0, a negative sigma,
+ *      a wrong struct_size: GS_ERR_INVALID.  A host-only handle: GS_ERR_NO_DEVICE.
+ * NOT DONE: the Slam mirror and the shell keep the Euclidean rule; no one-cone-per-observation resolution inside a frame (two observations
+ *      may take the same cone); no cross-covariance (above); no signed localizer type test (gs_frame_frontend's signed_type); sharded
+ *      handles: nothing beyond what the Euclidean calls do (the map and the search are per handle). */
+typedef struct gs_nn_params {
+    int32_t struct_size;
+    int32_t reserved;
+    double gate_chi2;      /* 5.991464547107979: 95 %, 2 dof */
+    double max_distance;   /* 3.0 m: Euclidean pre-gate and grid cell */
+    double type_tol;       /* 1e-4 */
+    double sigma_range;    /* 0.3 m */
+    double sigma_bearing;  /* 0.02 rad */
+    double sigma_xy;       /* 0.05 m */
+} gs_nn_params;
+int  gs_nn_params_default(gs_nn_params *p);
+int  gs_map_set_cov(gs_graph *g, int32_t first, int32_t n, const double *cov_2x2);
+int  gs_map_get_cov(gs_graph *g, int32_t first, int32_t n, double *out_cov_2x2);
+int  gs_map_set_cov_from_marginals(gs_graph *g, int32_t first, int32_t n, const int32_t *lm_ids);
+int  gs_associate_nn_batch(gs_graph *g, int32_t n, const double *poses_xytheta, int32_t n_poses, const int32_t *pose_of_obs, const double *obs_4xn,
+                           int32_t n_map, const double *map_xy, const int32_t *map_type, const double *map_cov_2x2, const double *pose_cov_3x3,
+                           const gs_nn_params *params, int32_t *out_index, double *out_d2, double *out_second_d2);
+int  gs_associate_nn_resident(gs_graph *g, int32_t n, const double *dev_poses_xytheta, int32_t n_poses, const int32_t *dev_pose_of_obs,
+                              const double *dev_obs_4xn, const double *dev_pose_cov_3x3, const gs_nn_params *params,
+                              int32_t *dev_out_index, double *dev_out_d2, double *dev_out_second_d2);
+int  gs_frame_frontend_nn(gs_graph *g, const double pose_xytheta[3], const double *pose_cov_3x3, const double *obs_4xk, int32_t k,
+                          const gs_nn_params *params, double *out_zxy, double *out_gxy, int32_t *out_index, double *out_d2, double *out_second_d2);
+
 /* ---- multi-GPU: pose-window shards -----------------------------
  * Each rank owns a contiguous pose window and builds the SAME global plan; it linearises and
  * factorises only its own subtrees, exports the update contributions to the shared top of the

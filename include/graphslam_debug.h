@@ -92,6 +92,10 @@ int gs_debug_fail_at_iteration(gs_graph *g, int32_t k, int32_t code);
  * start / stop event pair attached to the query kernel's dispatch (its own begin -> end, on the handle's stream); mean ms per launch. */
 int gs_debug_time_associate_resident(gs_graph *g, int32_t n, const double *dev_poses_xytheta, int32_t n_poses, const int32_t *dev_pose_of_obs,
                                      const double *dev_obs_4xn, double threshold, double type_tol, int32_t *dev_out_index, int32_t reps, double *out_ms);
+/* Its twin for the covariance-gated association: `reps` launches of gs_associate_nn_resident, timed the same way. */
+int gs_debug_time_associate_nn_resident(gs_graph *g, int32_t n, const double *dev_poses_xytheta, int32_t n_poses, const int32_t *dev_pose_of_obs,
+                                        const double *dev_obs_4xn, const double *dev_pose_cov_3x3, const gs_nn_params *params, int32_t *dev_out_index,
+                                        double *dev_out_d2, double *dev_out_second_d2, int32_t reps, double *out_ms);
 /* Measurement hook of the sharded iteration (bench.py's `ms_exchange`): `reps` RCCL all-reduces of the exchange buffer back to back on the
  * handle's stream, HIP events around them; mean ms per all-reduce.  Collective: every rank of the communicator calls it. */
 int gs_debug_time_exchange(gs_graph *g, int32_t reps, double *out_ms);

@@ -118,6 +118,24 @@ class LmInfo(C.Structure):
         return o
 
 
+class NnParams(C.Structure):
+    """gs_nn_params (include/graphslam.h): the gate and the noise model of the covariance-gated association"""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("gate_chi2", C.c_double), ("max_distance", C.c_double),
+                ("type_tol", C.c_double), ("sigma_range", C.c_double), ("sigma_bearing", C.c_double), ("sigma_xy", C.c_double)]
+
+
+def nn_params(**kw):
+    """the library's gs_nn_params defaults with the given fields replaced"""
+    p = NnParams(); rc = lib().gs_nn_params_default(C.byref(p))
+    if rc != GS_OK:
+        raise GsError(rc, "gs_nn_params_default")
+    for k, v in kw.items():
+        if k not in dict(NnParams._fields_):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
 class DoglegParams(C.Structure):
     """gs_dogleg_params (include/graphslam.h)"""
     _fields_ = [("struct_size", C.c_int32), ("max_trials_after_failure", C.c_int32), ("initial_delta", C.c_double)]
@@ -273,6 +291,16 @@ def lib():
         L.gs_get_odometry_edge_covariances.argtypes = [vp, C.c_int32, _dp]
         L.gs_get_observation_edge_covariances.argtypes = [vp, C.c_int32, _dp]
         L.gs_get_covariance_block.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp]
+    if hasattr(L, "gs_associate_nn_batch"):                # (the same for the covariance-gated association)
+        npp = C.POINTER(NnParams)
+        L.gs_nn_params_default.argtypes = [npp]
+        L.gs_map_set_cov.argtypes = [vp, C.c_int32, C.c_int32, _dp]
+        L.gs_map_get_cov.argtypes = [vp, C.c_int32, C.c_int32, _dp]
+        L.gs_map_set_cov_from_marginals.argtypes = [vp, C.c_int32, C.c_int32, _ip]
+        L.gs_associate_nn_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32, _dp, _ip, _dp, _dp, npp, _ip, _dp, _dp]
+        L.gs_associate_nn_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, npp, vp, vp, vp]
+        L.gs_debug_time_associate_nn_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, npp, vp, vp, vp, C.c_int32, _dp]
+        L.gs_frame_frontend_nn.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, _dp, _dp, _ip, _dp, _dp]
     if hasattr(L, "gs_set_robust_kernel"):                 # (a tuning build of an older tree loaded through GS_LIB may predate the robust kernels)
         L.gs_set_robust_kernel.argtypes = [vp, C.c_int32, C.c_int32, C.c_double]
         L.gs_get_robust_kernel.argtypes = [vp, C.c_int32, _ip, _dp]
@@ -885,6 +913,53 @@ class Graph:
         z = np.zeros((k, 2)); gx = np.zeros((k, 2)); idx = np.zeros(k, dtype=np.int32)
         self._check(self.L.gs_frame_frontend(self.h, _d(pose), _d(obs), k, float(thr), float(type_tol), int(signed_type), _d(z), _d(gx), _i(idx)))
         return z, gx, idx
+
+    # ---- covariance-gated association (include/graphslam.h): params = NnParams (None: the library's defaults)
+    def map_set_cov(self, first, cov):
+        cov = _f64(cov, (-1, 4)); self._check(self.L.gs_map_set_cov(self.h, int(first), len(cov), _d(cov)))
+
+    def map_cov(self, first=0, n=None):
+        """[n,2,2] covariance blocks of the resident map's cones [first, first + n) (n = None: to the end)"""
+        n = self.map_size() - int(first) if n is None else int(n)
+        out = np.zeros((max(n, 0), 2, 2)); self._check(self.L.gs_map_get_cov(self.h, int(first), n, _d(out))); return out
+
+    def map_set_cov_from_marginals(self, first, lm_ids):
+        ids = _i32(lm_ids); self._check(self.L.gs_map_set_cov_from_marginals(self.h, int(first), len(ids), _i(ids)))
+
+    def associate_nn(self, poses, pose_of_obs, obs, map_xy, map_type, map_cov=None, pose_cov=None, params=None):
+        """gs_associate_nn_batch: (index [n] int32, d2 [n], second_d2 [n])"""
+        poses = _f64(poses, (-1, 3)); obs = _f64(obs, (-1, 4)); po = _i32(pose_of_obs)
+        map_xy = _f64(map_xy, (-1, 2)); map_type = _i32(map_type); n = len(obs)
+        mc = None if map_cov is None else _f64(map_cov, (-1, 4)); pc = None if pose_cov is None else _f64(pose_cov, (-1, 9))
+        assert mc is None or len(mc) == len(map_xy); assert pc is None or len(pc) == len(poses)
+        p = nn_params() if params is None else params
+        idx = np.zeros(n, dtype=np.int32); d2 = np.zeros(n); sec = np.zeros(n)
+        self._check(self.L.gs_associate_nn_batch(self.h, n, _d(poses), len(poses), _i(po), _d(obs), len(map_xy), _d(map_xy), _i(map_type),
+                                                 None if mc is None else _d(mc), None if pc is None else _d(pc), C.byref(p), _i(idx), _d(d2), _d(sec)))
+        return idx, d2, sec
+
+    def associate_nn_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, d_out, d_out_d2=None, d_out_second=None, d_pose_cov=None, params=None):
+        """gs_associate_nn_resident: the resident map and its covariances, everything else DeviceArray; asynchronous (synchronize() before reading)"""
+        p = nn_params() if params is None else params
+        opt = lambda a: None if a is None else a.ptr
+        self._check(self.L.gs_associate_nn_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, opt(d_pose_cov), C.byref(p),
+                                                    d_out.ptr, opt(d_out_d2), opt(d_out_second)))
+
+    def time_associate_nn_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, d_out, reps, d_out_d2=None, d_out_second=None, d_pose_cov=None, params=None):
+        p = nn_params() if params is None else params
+        opt = lambda a: None if a is None else a.ptr
+        ms = C.c_double()
+        self._check(self.L.gs_debug_time_associate_nn_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, opt(d_pose_cov), C.byref(p),
+                                                               d_out.ptr, opt(d_out_d2), opt(d_out_second), int(reps), C.byref(ms)))
+        return ms.value
+
+    def frame_frontend_nn(self, pose, obs, pose_cov=None, params=None):
+        """(zxy [k,2], gxy [k,2], idx [k], d2 [k], second_d2 [k]) of one frame's observations [k,4] against the resident map and its covariances"""
+        pose = _f64(pose); obs = _f64(obs, (-1, 4)); k = len(obs); pc = None if pose_cov is None else _f64(pose_cov, (9,))
+        p = nn_params() if params is None else params
+        z = np.zeros((k, 2)); gx = np.zeros((k, 2)); idx = np.zeros(k, dtype=np.int32); d2 = np.zeros(k); sec = np.zeros(k)
+        self._check(self.L.gs_frame_frontend_nn(self.h, _d(pose), None if pc is None else _d(pc), _d(obs), k, C.byref(p), _d(z), _d(gx), _i(idx), _d(d2), _d(sec)))
+        return z, gx, idx, d2, sec
 
     # ---- pose-window shards (one handle per rank / GPU)
     def dist_configure(self, rank, world):

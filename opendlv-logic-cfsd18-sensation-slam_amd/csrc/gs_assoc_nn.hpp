@@ -1,0 +1,29 @@
+// gs_assoc_nn.hpp — launchers of the covariance-gated association (gs_assoc_nn.hip): nearest cone by Mahalanobis distance inside a
+// chi-square gate, against a map with a 2x2 covariance per cone.  Host side: gs_frontend.cpp (gs_associate_nn_*, gs_frame_frontend_nn,
+// gs_map_set_cov*).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace gs {
+
+// gs_nn_params as the kernels take it (the sigmas are squared on the device, inside the one function all kernels share)
+struct NnDev { double gate_chi2, max_distance, type_tol, sigma_range, sigma_bearing, sigma_xy; };
+
+// a thread per observation, the map through LDS in tiles of 1024.  map_cov (n_map x 4) and pose_cov (n_poses x 9) may be null: zeros.
+// out_d2 / out_second may be null.  start / stop: events on the dispatch (timing hook), may be null.
+void launch_assoc_nn(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, double lidar, int n_map,
+                     const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
+                     int32_t *out_idx, double *out_d2, double *out_second, hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// the same against the hashed grid of launch_grid_build (cell edge from max_distance): nine buckets per observation
+void launch_assoc_nn_grid(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, double lidar,
+                          const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
+                          long long buckets, const int32_t *cell_start, const int32_t *cell_items,
+                          int32_t *out_idx, double *out_d2, double *out_second, hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// one frame: in = {pose x, y, theta, pose_cov[9], obs[4 * k]} (has_pose_cov == 0: the nine are not read), a workgroup per observation
+void launch_frame_nn(int k, const double *in, int has_pose_cov, double lidar, int n_map, const double *map_xy, const int32_t *map_type,
+                     const double *map_cov, NnDev p, double *out_z, double *out_g, int32_t *out_idx, double *out_d2, double *out_second, hipStream_t st);
+// map_cov[4 * (first + k) + c] = src[k] < 0 ? 0 : values[src[k] + c], k < n, c < 4
+void launch_map_cov_gather(int n, const int64_t *src, const double *values, double *map_cov_first, hipStream_t st);
+
+}  // namespace gs

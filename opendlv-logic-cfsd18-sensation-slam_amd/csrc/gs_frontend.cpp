@@ -2,6 +2,7 @@
 #include "../../include/graphslam.h"
 #include "../../include/graphslam_debug.h"
 #include "gs_private.hpp"
+#include "gs_assoc_nn.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -44,6 +45,12 @@ void gs_frontend_release(gs_graph *g) {      // gs_destroy
     if (g->fe.pin_map) hipHostFree(g->fe.pin_map);
     if (g->fe.grid_mem) hipFree(g->fe.grid_mem);
     if (g->fe.pcs) hipFree(g->fe.pcs);
+    if (g->fe.map_cov) hipFree(g->fe.map_cov);
+    if (g->fe.cov_src) hipFree(g->fe.cov_src);
+    if (g->fe.nn_pin_in) hipHostFree(g->fe.nn_pin_in);
+    if (g->fe.nn_pin_out) hipHostFree(g->fe.nn_pin_out);
+    if (g->fe.nn_dev_in) hipFree(g->fe.nn_dev_in);
+    if (g->fe.nn_dev_out) hipFree(g->fe.nn_dev_out);
     g->fe = gs_graph::FrontEnd();
 }
 
@@ -182,14 +189,19 @@ extern "C" int gs_debug_time_associate_resident(gs_graph *g, int32_t n, const do
 static int map_reserve(gs_graph *g, int want) {
     if (want <= g->fe.map_cap) return GS_OK;
     const int cap = std::max(want + want / 2, 1024);
-    double *xy = nullptr; int32_t *ty = nullptr;
+    double *xy = nullptr, *cv = nullptr; int32_t *ty = nullptr;
     HIP_TRY(hipMalloc((void **)&xy, (size_t)cap * 2 * sizeof(double)));
     HIP_TRY(hipMalloc((void **)&ty, (size_t)cap * sizeof(int32_t)));
+    if (g->fe.map_cov) {                                            // a handle that set covariances: they grow with the map (the rest is zero)
+        HIP_TRY(hipMalloc((void **)&cv, (size_t)cap * 4 * sizeof(double)));
+        HIP_TRY(hipMemsetAsync(cv, 0, (size_t)cap * 4 * sizeof(double), g->stream));
+        if (g->fe.map_n > 0) HIP_TRY(hipMemcpyAsync(cv, g->fe.map_cov, (size_t)g->fe.map_n * 4 * sizeof(double), hipMemcpyDeviceToDevice, g->stream)); }
     if (g->fe.map_n > 0) { HIP_TRY(hipMemcpyAsync(xy, g->fe.map_xy, (size_t)g->fe.map_n * 2 * sizeof(double), hipMemcpyDeviceToDevice, g->stream));
                            HIP_TRY(hipMemcpyAsync(ty, g->fe.map_type, (size_t)g->fe.map_n * sizeof(int32_t), hipMemcpyDeviceToDevice, g->stream)); }
     HIP_TRY(hipStreamSynchronize(g->stream));
     if (g->fe.map_xy) hipFree(g->fe.map_xy);
     if (g->fe.map_type) hipFree(g->fe.map_type);
+    if (cv) { hipFree(g->fe.map_cov); g->fe.map_cov = cv; }
     g->fe.map_xy = xy; g->fe.map_type = ty; g->fe.map_cap = cap;
     return GS_OK;
 }
@@ -219,6 +231,7 @@ extern "C" int gs_map_append(gs_graph *g, int32_t n, const double *xy, const int
     HIP_TRY(hipMemcpyAsync(g->fe.map_xy + 2 * (size_t)g->fe.map_n, g->fe.pin_map, bx, hipMemcpyHostToDevice, g->stream));
     HIP_TRY(hipMemcpyAsync(g->fe.map_type + g->fe.map_n, g->fe.pin_map + bx, bt, hipMemcpyHostToDevice, g->stream));
     g->fe.pin_map_busy = true;                                      // no wait here: the next frame's launch is ordered behind the copies
+    if (g->fe.map_cov) HIP_TRY(hipMemsetAsync(g->fe.map_cov + 4 * (size_t)g->fe.map_n, 0, (size_t)n * 4 * sizeof(double), g->stream));   // (also what gs_map_clear's "drops covariances" rests on)
     g->fe.map_n += n; g->fe.grid_valid = false;
     return GS_OK;
 }
@@ -259,5 +272,197 @@ extern "C" int gs_frame_frontend(gs_graph *g, const double pose[3], const double
     HIP_TRY(hipStreamSynchronize(g->stream));
     g->fe.pin_map_busy = false;
     std::memcpy(out_zxy, g->fe.pin_out, bz); std::memcpy(out_gxy, g->fe.pin_out + bz, bz); std::memcpy(out_idx, g->fe.pin_out + 2 * bz, bi);
+    return GS_OK;
+}
+
+// ---- covariance-gated association (gs_assoc_nn.hip): the map's 2x2 blocks, the batch / resident / frame calls ----------------------
+extern "C" int gs_nn_params_default(gs_nn_params *p) {
+    if (!p) return fail(GS_ERR_INVALID, "null params");
+    std::memset(p, 0, sizeof(*p)); p->struct_size = (int32_t)sizeof(*p);
+    p->gate_chi2 = 5.991464547107979; p->max_distance = 3.0; p->type_tol = 1e-4; p->sigma_range = 0.3; p->sigma_bearing = 0.02; p->sigma_xy = 0.05;
+    return GS_OK;
+}
+// everything a caller can get wrong about the parameters, decided before the device is touched
+static int nn_params_check(const gs_nn_params *p, NnDev &d) {
+    if (!p) return fail(GS_ERR_INVALID, "null params");
+    if (p->struct_size != (int32_t)sizeof(gs_nn_params)) return fail(GS_ERR_INVALID, "gs_nn_params: wrong struct_size");
+    const double v[6] = {p->gate_chi2, p->max_distance, p->type_tol, p->sigma_range, p->sigma_bearing, p->sigma_xy};
+    for (double x : v) if (!std::isfinite(x)) return fail(GS_ERR_INVALID, "gs_nn_params: a parameter is not finite");
+    if (p->gate_chi2 <= 0.0 || p->max_distance <= 0.0) return fail(GS_ERR_INVALID, "gs_nn_params: gate_chi2 and max_distance must be positive");
+    if (p->sigma_range < 0.0 || p->sigma_bearing < 0.0 || p->sigma_xy < 0.0) return fail(GS_ERR_INVALID, "gs_nn_params: a sigma is negative");
+    d = NnDev{p->gate_chi2, p->max_distance, p->type_tol, p->sigma_range, p->sigma_bearing, p->sigma_xy};
+    return GS_OK;
+}
+// the covariance array, allocated (zeros) at the first call that needs it
+static int map_cov_ensure(gs_graph *g) {
+    auto &fe = g->fe;
+    if (fe.map_cov || fe.map_cap == 0) return GS_OK;
+    HIP_TRY(hipMalloc((void **)&fe.map_cov, (size_t)fe.map_cap * 4 * sizeof(double)));
+    HIP_TRY(hipMemsetAsync(fe.map_cov, 0, (size_t)fe.map_cap * 4 * sizeof(double), g->stream));
+    return GS_OK;
+}
+extern "C" int gs_map_set_cov(gs_graph *g, int32_t first, int32_t n, const double *cov) {
+    if (!g || first < 0 || n < 0 || (n > 0 && !cov)) return fail(GS_ERR_INVALID, "bad argument");
+    if ((int64_t)first + n > g->fe.map_n) return fail(GS_ERR_INVALID, "beyond the end of the map");
+    for (int k = 0; k < n; ++k) { const double *c = cov + 4 * (size_t)k;              // all or nothing: nothing is uploaded before every block passed
+        if (!(std::isfinite(c[0]) && std::isfinite(c[1]) && std::isfinite(c[2]) && std::isfinite(c[3]))) return fail(GS_ERR_INVALID, "map covariance: a block is not finite");
+        if (std::memcmp(c + 1, c + 2, sizeof(double)) != 0) return fail(GS_ERR_INVALID, "map covariance: a block is not symmetric");
+        if (c[0] < 0.0 || c[3] < 0.0) return fail(GS_ERR_INVALID, "map covariance: a negative diagonal"); }
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n == 0) return GS_OK;
+    if ((rc = map_cov_ensure(g)) != GS_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(g->fe.map_cov + 4 * (size_t)first, cov, (size_t)n * 4 * sizeof(double), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));                       // pageable source: the caller's buffer is free on return
+    g->fe.pin_map_busy = false;
+    return GS_OK;
+}
+extern "C" int gs_map_get_cov(gs_graph *g, int32_t first, int32_t n, double *out) {
+    if (!g || first < 0 || n < 0 || (n > 0 && !out)) return fail(GS_ERR_INVALID, "bad argument");
+    if ((int64_t)first + n > g->fe.map_n) return fail(GS_ERR_INVALID, "beyond the end of the map");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n == 0) return GS_OK;
+    if (!g->fe.map_cov) { std::memset(out, 0, (size_t)n * 4 * sizeof(double)); return GS_OK; }     // never set: zeros, and nothing allocated for asking
+    HIP_TRY(hipMemcpyAsync(out, g->fe.map_cov + 4 * (size_t)first, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    g->fe.pin_map_busy = false;
+    return GS_OK;
+}
+extern "C" int gs_map_set_cov_from_marginals(gs_graph *g, int32_t first, int32_t n, const int32_t *lm_ids) {
+    if (!g || first < 0 || n < 0 || (n > 0 && !lm_ids)) return fail(GS_ERR_INVALID, "bad argument");
+    if ((int64_t)first + n > g->fe.map_n) return fail(GS_ERR_INVALID, "beyond the end of the map");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if ((rc = marg_ready(g)) != GS_OK) return rc;
+    // landmark l's block sits at 9 n_poses + 4 l of the gathered result gs_compute_marginals keeps in device memory (gs_marginals.cpp, d_out)
+    std::vector<int64_t> src((size_t)n);
+    const int64_t base = 9 * (int64_t)g->h.n_poses();
+    for (int k = 0; k < n; ++k) {
+        if (lm_ids[k] == -1) { src[k] = -1; continue; }
+        auto it = g->h.lm_index.find(lm_ids[k]);
+        if (it == g->h.lm_index.end()) return fail(GS_ERR_UNKNOWN_ID, "unknown landmark id");
+        src[k] = base + 4 * (int64_t)it->second; }
+    if (n == 0) return GS_OK;
+    auto &fe = g->fe;
+    if ((rc = map_cov_ensure(g)) != GS_OK) return rc;
+    if ((size_t)n > fe.cov_src_n) { HIP_TRY(hipStreamSynchronize(g->stream));
+        if (fe.cov_src) hipFree(fe.cov_src);
+        fe.cov_src = nullptr; fe.cov_src_n = 0;
+        const size_t want = (size_t)n + (size_t)n / 2 + 64;
+        HIP_TRY(hipMalloc((void **)&fe.cov_src, want * sizeof(int64_t))); fe.cov_src_n = want; }
+    HIP_TRY(hipMemcpyAsync(fe.cov_src, src.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, g->stream));
+    launch_map_cov_gather(n, fe.cov_src, g->marg.d_out, fe.map_cov + 4 * (size_t)first, g->stream);      // device to device: the values never visit the host
+    HIP_TRY(hipStreamSynchronize(g->stream));                       // (src is a host temporary)
+    g->fe.pin_map_busy = false;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("map covariances from marginals: ") + hipGetErrorString(e));
+    return GS_OK;
+}
+extern "C" int gs_associate_nn_batch(gs_graph *g, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs, const double *obs,
+                                     int32_t n_map, const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov,
+                                     const gs_nn_params *params, int32_t *out, double *out_d2, double *out_second) {
+    if (!g || n < 0 || npose < 0 || n_map < 0 || (n > 0 && (!poses || !pose_of_obs || !obs || !out)) || (n_map > 0 && (!map_xy || !map_type)))
+        return fail(GS_ERR_INVALID, "bad argument");
+    NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
+    for (int i = 0; i < n; ++i) if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n == 0) return GS_OK;
+    bool grid = n_map >= 2048;                                      // as gs_associate_batch: the grid beyond a few LDS tiles, gs_debug_options.assoc_grid forces either
+    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && n_map > 0;
+    long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
+    if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(9 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded(2 * (size_t)n_map, 8) +
+                               padded(4 * (size_t)n_map, 8) + padded(n_map, 4) + padded(n, 4) + 2 * padded(n, 8) + gbytes)) != GS_OK) return rc;
+    Carver c{g}; double *p = c.get<double>(3 * (size_t)npose), *pcv = c.get<double>(9 * (size_t)npose); int32_t *po = c.get<int32_t>(n);
+    double *ob = c.get<double>(4 * (size_t)n), *mx = c.get<double>(2 * (size_t)n_map), *mc = c.get<double>(4 * (size_t)n_map);
+    int32_t *mt = c.get<int32_t>(n_map), *o = c.get<int32_t>(n); double *od = c.get<double>(n), *os = c.get<double>(n);
+    HIP_TRY(hipMemcpyAsync(p, poses, 3 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
+    if (pose_cov && npose > 0) HIP_TRY(hipMemcpyAsync(pcv, pose_cov, 9 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(po, pose_of_obs, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
+    if (n_map > 0) { HIP_TRY(hipMemcpyAsync(mx, map_xy, 2 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream));
+                     HIP_TRY(hipMemcpyAsync(mt, map_type, (size_t)n_map * 4, hipMemcpyHostToDevice, g->stream));
+                     if (map_cov) HIP_TRY(hipMemcpyAsync(mc, map_cov, 4 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream)); }
+    const double *dmc = map_cov ? mc : nullptr, *dpc = pose_cov ? pcv : nullptr;
+    if (grid) { const GridBufs gb = grid_carve(c.get<char>(gbytes), n_map, buckets);
+        launch_grid_build(n_map, mx, nd.max_distance, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream);
+        launch_assoc_nn_grid(n, p, npose, po, ob, g->cfg.lidar_to_cog, mx, mt, dmc, dpc, nd, buckets, gb.start, gb.items, o, od, os, g->stream);
+    } else launch_assoc_nn(n, p, npose, po, ob, g->cfg.lidar_to_cog, n_map, mx, mt, dmc, dpc, nd, o, od, os, g->stream);
+    HIP_TRY(hipMemcpyAsync(out, o, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (out_d2) HIP_TRY(hipMemcpyAsync(out_d2, od, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    if (out_second) HIP_TRY(hipMemcpyAsync(out_second, os, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));        // the one wait of the call: the result copies
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("association (nn): ") + hipGetErrorString(e));
+    return GS_OK;
+}
+extern "C" int gs_associate_nn_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
+                                        const double *dev_pose_cov, const gs_nn_params *params, int32_t *dev_out, double *dev_out_d2, double *dev_out_second) {
+    if (!g || n < 0 || npose < 0 || (n > 0 && (!dev_poses || !dev_pose_of_obs || !dev_obs || !dev_out))) return fail(GS_ERR_INVALID, "bad argument");
+    NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
+    if (((uintptr_t)dev_obs & 31) != 0) return fail(GS_ERR_INVALID, "dev_obs must be 32-byte aligned (an observation is read in one load)");
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n == 0) return GS_OK;
+    auto &fe = g->fe;
+    const bool grid = fe.map_n > 0 && g->opt.assoc_grid != 0;
+    if (grid) { if ((rc = resident_grid(g, nd.max_distance)) != GS_OK) return rc;
+        const GridBufs gb = grid_carve(fe.grid_mem, fe.map_n, fe.grid_max_cells);
+        launch_assoc_nn_grid(n, dev_poses, npose, dev_pose_of_obs, dev_obs, g->cfg.lidar_to_cog, fe.map_xy, fe.map_type, fe.map_cov, dev_pose_cov, nd,
+                             gb.buckets, gb.start, gb.items, dev_out, dev_out_d2, dev_out_second, g->stream, g->ev_lin[0], g->ev_lin[1]);
+    } else launch_assoc_nn(n, dev_poses, npose, dev_pose_of_obs, dev_obs, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, fe.map_cov, dev_pose_cov, nd,
+                           dev_out, dev_out_d2, dev_out_second, g->stream, g->ev_lin[0], g->ev_lin[1]);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("association (nn): ") + hipGetErrorString(e));
+    return GS_OK;
+}
+// the twin of gs_debug_time_associate_resident: start / stop events on the query kernel's dispatch, the grid built before
+extern "C" int gs_debug_time_associate_nn_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
+                                                   const double *dev_obs, const double *dev_pose_cov, const gs_nn_params *params, int32_t *dev_out,
+                                                   double *dev_out_d2, double *dev_out_second, int32_t reps, double *out_ms) {
+    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
+    int rc = gs_associate_nn_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, dev_pose_cov, params, dev_out, dev_out_d2, dev_out_second);     // warm (and the grid)
+    if (rc != GS_OK) return rc;
+    std::vector<hipEvent_t> ev(2 * (size_t)reps); for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    for (int r = 0; r < reps && rc == GS_OK; ++r) { g->ev_lin[0] = ev[2 * (size_t)r]; g->ev_lin[1] = ev[2 * (size_t)r + 1];
+        rc = gs_associate_nn_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, dev_pose_cov, params, dev_out, dev_out_d2, dev_out_second); }
+    g->ev_lin[0] = g->ev_lin[1] = nullptr;
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    double tot = 0; int cnt = 0;
+    for (int r = 0; r < reps; ++r) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]) == hipSuccess && ms > 0) { tot += ms; ++cnt; } }
+    (void)hipGetLastError();
+    for (auto &e : ev) hipEventDestroy(e);
+    *out_ms = cnt ? tot / cnt : 0.0;
+    return rc;
+}
+extern "C" int gs_frame_frontend_nn(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
+                                    double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2, double *out_second) {
+    if (!g || !pose || k < 0 || (k > 0 && (!obs || !out_zxy || !out_gxy || !out_idx || !out_d2 || !out_second))) return fail(GS_ERR_INVALID, "bad argument");
+    NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (k == 0) return GS_OK;
+    auto &fe = g->fe;
+    if (k > fe.nn_cap_obs) {                                         // grow-only, as gs_frame_frontend's
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        if (fe.nn_pin_in) hipHostFree(fe.nn_pin_in);
+        if (fe.nn_pin_out) hipHostFree(fe.nn_pin_out);
+        if (fe.nn_dev_in) hipFree(fe.nn_dev_in);
+        if (fe.nn_dev_out) hipFree(fe.nn_dev_out);
+        fe.nn_pin_in = nullptr; fe.nn_pin_out = nullptr; fe.nn_dev_in = nullptr; fe.nn_dev_out = nullptr; fe.nn_cap_obs = 0;
+        const int cap = std::max(64, k + k / 2);
+        const size_t bin = (12 + 4 * (size_t)cap) * sizeof(double), bout = (size_t)cap * (6 * sizeof(double) + sizeof(int32_t));
+        HIP_TRY(hipHostMalloc((void **)&fe.nn_pin_in, bin, hipHostMallocDefault)); HIP_TRY(hipHostMalloc((void **)&fe.nn_pin_out, bout, hipHostMallocDefault));
+        HIP_TRY(hipMalloc((void **)&fe.nn_dev_in, bin)); HIP_TRY(hipMalloc((void **)&fe.nn_dev_out, bout));
+        fe.nn_cap_obs = cap;
+    }
+    const size_t bin = (12 + 4 * (size_t)k) * sizeof(double), bz = (size_t)k * 2 * sizeof(double), bd = (size_t)k * sizeof(double), bi = (size_t)k * sizeof(int32_t);
+    std::memcpy(fe.nn_pin_in, pose, 3 * sizeof(double));
+    if (pose_cov) std::memcpy(fe.nn_pin_in + 3, pose_cov, 9 * sizeof(double)); else std::memset(fe.nn_pin_in + 3, 0, 9 * sizeof(double));
+    std::memcpy(fe.nn_pin_in + 12, obs, 4 * (size_t)k * sizeof(double));
+    double *dz = (double *)fe.nn_dev_out, *dg = dz + 2 * (size_t)k, *dd = dg + 2 * (size_t)k, *ds = dd + k; int32_t *di = (int32_t *)(ds + k);
+    HIP_TRY(hipMemcpyAsync(fe.nn_dev_in, fe.nn_pin_in, bin, hipMemcpyHostToDevice, g->stream));
+    launch_frame_nn(k, fe.nn_dev_in, pose_cov ? 1 : 0, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, fe.map_cov, nd, dz, dg, di, dd, ds, g->stream);
+    HIP_TRY(hipMemcpyAsync(fe.nn_pin_out, fe.nn_dev_out, 2 * bz + 2 * bd + bi, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    fe.pin_map_busy = false;
+    const char *po = fe.nn_pin_out;
+    std::memcpy(out_zxy, po, bz); std::memcpy(out_gxy, po + bz, bz); std::memcpy(out_d2, po + 2 * bz, bd); std::memcpy(out_second, po + 2 * bz + bd, bd);
+    std::memcpy(out_idx, po + 2 * bz + 2 * bd, bi);
     return GS_OK;
 }

@@ -67,6 +67,11 @@ struct gs_graph {
         char *grid_mem = nullptr; size_t grid_bytes = 0;        // the resident map's uniform grid, built on the device (gs_associate_resident): parameters, cell starts, items
         bool grid_valid = false; int grid_map_n = 0; double grid_thr = 0.0; long long grid_max_cells = 0;
         double *pcs = nullptr; size_t pcs_bytes = 0;            // cos / sin of the poses of a batched association (scratch, grow-only)
+        // covariance-gated association: the resident map's 2x2 blocks (map_cap x 4; null until a call needs them: every cone's block is
+        // zero then), the index table of gs_map_set_cov_from_marginals, and the frame path's own staging (capacity in observations)
+        double *map_cov = nullptr;
+        int64_t *cov_src = nullptr; size_t cov_src_n = 0;
+        double *nn_pin_in = nullptr, *nn_dev_in = nullptr; char *nn_pin_out = nullptr, *nn_dev_out = nullptr; int nn_cap_obs = 0;
     } fe;
     bool tree_proven = false;               // a whole-tree launch sequence of the CURRENT plan has completed without a flag timeout (gs_optimize then sends all iterations of a call at once)
     bool fell_back = false;                 // a whole-tree launch gave up on a flag: this handle uses one launch per level — until the next plan, or until a retry (below) comes back clean

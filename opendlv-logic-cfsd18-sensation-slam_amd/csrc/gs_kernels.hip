@@ -15,6 +15,7 @@
 //
 // All fp64; every sum has a fixed order (no floating-point atomics) so results are bitwise reproducible.
 #include "gs_device.hpp"
+#include "gs_frontend_dev.hpp"
 #include <hip/hip_ext.h>
 #include <algorithm>
 #include <mutex>
@@ -32,10 +33,7 @@ static constexpr int LM_REC = 8;       // doubles per (wave tile, landmark) part
 #define GS_G2O_ORDER 1
 #endif
 
-// constants exactly as the reference declares them (src/slam.hpp:134-136; PI is a FLOAT literal)
-__device__ static constexpr double kDeg2Rad = 0.017453292522222;
-__device__ static constexpr double kRad2Deg = 57.295779513082325;
-__device__ static constexpr double kPiF = (double)3.14159265f;
+// (kDeg2Rad, kRad2Deg, kPiF: gs_frontend_dev.hpp)
 __device__ static constexpr double kPi = 3.14159265358979323846;
 
 // g2o normalize_theta
@@ -49,21 +47,7 @@ __device__ __forceinline__ double normalize_theta(double th) {
     return th;
 }
 
-// ------------------------------------------------------------------ A0
-__device__ __forceinline__ void polar_to_xy(double az, double zen, double dist, double lidar, double &x, double &y) {
-    // transformConeToCoG: sign is NaN at az == 0 (kept)
-    double sign = az / fabs(az);
-    double ang = kPiF - fabs(az * kDeg2Rad);
-    double sa, ca; sincos(ang, &sa, &ca);                           // (one range reduction for the pair: the batched association is bound by these calls)
-    double dnew = sqrt(lidar * lidar + dist * dist - 2.0 * lidar * dist * ca);
-    double anew = asin((sa * dist) / dnew) * kRad2Deg;
-    double az2 = anew * sign;
-    // Spherical2Cartesian
-    double cz = cos(zen * kDeg2Rad);
-    double s2, c2; sincos(az2 * kDeg2Rad, &s2, &c2);
-    x = dnew * cz * c2;
-    y = dnew * cz * s2;
-}
+// ------------------------------------------------------------------ A0  (polar_to_xy, cone_to_global_cs: gs_frontend_dev.hpp)
 
 __global__ void k_polar_to_xy(int n, const double *__restrict__ az, const double *__restrict__ zen,
                               const double *__restrict__ dist, double lidar, double *__restrict__ out) {
@@ -73,11 +57,6 @@ __global__ void k_polar_to_xy(int n, const double *__restrict__ az, const double
     out[2 * i] = x; out[2 * i + 1] = y;
 }
 
-__device__ __forceinline__ void cone_to_global_cs(double px, double py, double c, double s, const double *obs, double lidar, double &gx, double &gy) {
-    double x, y; polar_to_xy(obs[0], obs[1], obs[2], lidar, x, y);
-    gx = (x * c - y * s) + px;
-    gy = (x * s + y * c) + py;
-}
 __device__ __forceinline__ void cone_to_global(const double *pose, const double *obs, double lidar, double &gx, double &gy) {
     double s, c; sincos(pose[2], &s, &c);
     cone_to_global_cs(pose[0], pose[1], c, s, obs, lidar, gx, gy);
@@ -130,11 +109,6 @@ __global__ void k_pose_trig(int n, const double *__restrict__ pose_est, double *
 // fill (k_grid_fill: the order inside a bucket is whatever the atomics give — the query takes the LOWEST matching index over its nine
 // buckets, which does not depend on it; a colliding cone of some far cell is one more candidate that fails the distance test).  Same
 // pair test, same arithmetic as k_associate => identical indices.  No host pass over the map, no host round trip.
-struct GridParams { double inv_cell; uint32_t mask; int pad; };
-__device__ __forceinline__ long long grid_coord(double v, double inv_cell) { return (long long)fmin(fmax(floor(v * inv_cell), -4.0e15), 4.0e15); }   // (finite input; clamped: no overflow of the cast)
-__device__ __forceinline__ uint32_t grid_bucket(long long cx, long long cy, uint32_t mask) {
-    return (((uint32_t)cx * 73856093u) ^ ((uint32_t)cy * 19349663u)) & mask;
-}
 __global__ void __launch_bounds__(256) k_grid_count(int n_map, const double *__restrict__ map_xy, GridParams g, int32_t *__restrict__ count) {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= n_map) return;
@@ -205,7 +179,6 @@ __global__ void __launch_bounds__(256) k_associate_grid_dev(int n, const double 
     }
     out[i] = found == 0x7fffffff ? -1 : found;
 }
-static GridParams grid_params_of(double thr, long long buckets) { GridParams g; g.inv_cell = 1.0 / (thr * (1.0 + 1e-9)); g.mask = (uint32_t)(buckets - 1); g.pad = 0; return g; }
 // buckets: a power of two; count / start / cursor: buckets + 1 ints each, items: n_map ints
 void launch_grid_build(int n_map, const double *map_xy, double thr, long long buckets, int32_t *count, int32_t *start, int32_t *cursor, int32_t *items, hipStream_t st) {
     const GridParams g = grid_params_of(thr, buckets);

@@ -138,7 +138,7 @@ extern "C" int gs_compute_marginals(gs_graph *g, gs_marginals_info *info) {
     M.valid = true; M.structure_version = g->h.structure_version; M.estimate_version = g->h.estimate_version; M.iter = g->d.iter;
     return GS_OK;
 }
-static int marg_ready(gs_graph *g) {
+int marg_ready(gs_graph *g) {
     const auto &M = g->marg;
     if (!M.valid || !g->dev_valid || M.structure_version != g->h.structure_version || M.estimate_version != g->h.estimate_version || M.iter != g->d.iter)
         return fail(GS_ERR_NOT_INITIALIZED, "no marginals for the current graph and estimates: call gs_compute_marginals (results go stale after an "

@@ -125,5 +125,6 @@ void fall_back_to_levels(gs_graph *g);
 int run_begin(gs_graph *g, int32_t iterations, bool retry);
 int run_check(gs_graph *g, const char *what, float *ms);
 void run_stats(gs_graph *g, gs_stats *stats, int32_t iterations, int32_t failure, int first_failure, double chi2_initial, double chi2_final, float ms);
+int marg_ready(gs_graph *g);                  // gs_marginals.cpp: GS_OK when the last gs_compute_marginals still describes the graph and its estimates (the getters' test)
 void gs_frontend_release(gs_graph *g);       // gs_frontend.cpp: front-end buffers of the handle
 void gs_dist_comm_release(gs_graph *g);      // gs_dist.cpp: the handle's own RCCL communicator
