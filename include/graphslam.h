@@ -689,9 +689,10 @@ int  gs_frame_frontend(gs_graph *g, const double pose_xytheta[3], const double *
  * gs_frame_frontend_nn: one frame in one launch, as gs_frame_frontend; pose_cov_3x3 may be NULL.
  * Errors (before the device is touched): a null pointer, a parameter that is not finite, gate_chi2 <= 0, max_distance <= 0, a negative sigma,
  *      a wrong struct_size: GS_ERR_INVALID.  A host-only handle: GS_ERR_NO_DEVICE.
- * NOT DONE: the Slam mirror and the shell keep the Euclidean rule; no one-cone-per-observation resolution inside a frame (two observations
- *      may take the same cone); no cross-covariance (above); no signed localizer type test (gs_frame_frontend's signed_type); sharded
- *      handles: nothing beyond what the Euclidean calls do (the map and the search are per handle). */
+ * NOT DONE: the Slam mirror and the shell keep the Euclidean rule; these calls decide every observation on its own, so two observations
+ *      of a frame may take the same cone (the one-to-one association below resolves that); no cross-covariance (above); no signed localizer
+ *      type test (gs_frame_frontend's signed_type); sharded handles: nothing beyond what the Euclidean calls do (the map and the search are
+ *      per handle). */
 typedef struct gs_nn_params {
     int32_t struct_size;
     int32_t reserved;
@@ -714,6 +715,51 @@ int  gs_associate_nn_resident(gs_graph *g, int32_t n, const double *dev_poses_xy
                               int32_t *dev_out_index, double *dev_out_d2, double *dev_out_second_d2);
 int  gs_frame_frontend_nn(gs_graph *g, const double pose_xytheta[3], const double *pose_cov_3x3, const double *obs_4xk, int32_t k,
                           const gs_nn_params *params, double *out_zxy, double *out_gxy, int32_t *out_index, double *out_d2, double *out_second_d2);
+
+/* ---- one-to-one association: each frame's cones matched by ascending d2 ------------------------------------------
+ * The calls above decide every observation on its own, so two observations of one frame can take the same cone — which a lidar frame
+ * cannot see twice.  These calls resolve that on the device, where the candidates are (the host only ever sees best and runner-up).
+ *
+ * Frame.  A frame is a consecutive run of observations [frame_start[f], frame_start[f + 1]).
+ * Pair distance.  For observation i and cone j, d2(i, j) and "admissible" are exactly those of the covariance-gated association above:
+ *      the same fp64 operations, no contraction.  Nothing about a pair changes.
+ * Assignment.  Inside a frame a cone is given to at most one observation and an observation gets at most one cone: the GREEDY matching over
+ *      the frame's admissible pairs in ascending order of the key (d2, observation index, cone index).  Walk the pairs in that order; take a
+ *      pair when its observation is still unassigned and its cone still unclaimed in this frame.  The observation index in the key is the
+ *      position in the call's arrays.  The order is strict and total, so the result is unique and does not depend on how the device gets
+ *      there (it takes, round by round, the smallest pair still open).
+ * Outputs, per observation.  index = the cone, or -1;  d2 = the d2 of the taken pair, or +inf.  An observation whose query is invalid
+ *      (azimuth 0, r == 0, pose index out of range) gets -1 and takes part in nothing.
+ * Scope.  Frames are independent: the same cone may be taken in two different frames.
+ * Consequences.  In a frame where gs_associate_nn_* returns no cone twice the result equals it in index and d2, bit for bit.  The matching
+ *      equals the fixed point of "mutual best" rounds (every unassigned observation proposes its best unclaimed cone by (d2, j); a proposal
+ *      (i, c) commits iff no other UNASSIGNED observation i' of the frame — not only those that proposed c — has an admissible d2(i', c)
+ *      with (d2, i') below (d2(i, c), i)).
+ *
+ * gs_assign_nn_batch: the layouts of gs_associate_nn_batch plus frame_start (n_frames + 1 entries): frame_start[0] == 0, ascending (empty
+ *      frames allowed), frame_start[n_frames] == n, every frame of at most GS_NN_FRAME_MAX observations — anything else GS_ERR_INVALID
+ *      before the device is touched, as are all the refusals of gs_associate_nn_batch.  out_d2 may be NULL.  The search is chosen as there.
+ * gs_assign_nn_resident: everything in DEVICE memory against the resident map and its covariances, asynchronous on the handle's stream, no
+ *      wait.  dev_pose_cov and dev_out_d2 may be NULL; dev_obs must be 32-byte aligned.  The host cannot see the offsets, so the kernel
+ *      defends itself: a frame whose bounds are not 0 <= a <= b <= n reads and writes nothing; a frame longer than GS_NN_FRAME_MAX writes
+ *      -1 / +inf for all its observations; OBSERVATIONS THAT NO FRAME COVERS ARE NOT WRITTEN (the outputs keep what they held); an
+ *      observation that two frames cover is written by both, in no stated order.
+ * gs_frame_frontend_assign: one frame of k <= GS_NN_FRAME_MAX observations in one launch against the resident map (the grid from 2048
+ *      cones, brute force below; gs_debug_options.assoc_grid forces either); out_zxy / out_gxy are the bits gs_frame_frontend_nn returns.
+ *      k above the cap: GS_ERR_INVALID.  Its staging buffers exist from the first call on and only grow.
+ * A handle that never calls any of these allocates and launches nothing for them; the calls above are unchanged by them.
+ * NOT DONE: this is NOT the minimum-sum assignment (Hungarian) and NOT joint compatibility — a greedy matching can be beaten in total d2;
+ *      the Slam mirror and the shell keep the Euclidean lowest-index rule; no cross-covariance; no signed localizer type test; frames of
+ *      more than GS_NN_FRAME_MAX observations; sharded handles: nothing beyond what the gs_associate_nn_* calls give. */
+#define GS_NN_FRAME_MAX 256
+int  gs_assign_nn_batch(gs_graph *g, int32_t n, const double *poses_xytheta, int32_t n_poses, const int32_t *pose_of_obs, const double *obs_4xn,
+                        int32_t n_frames, const int32_t *frame_start, int32_t n_map, const double *map_xy, const int32_t *map_type,
+                        const double *map_cov_2x2, const double *pose_cov_3x3, const gs_nn_params *params, int32_t *out_index, double *out_d2);
+int  gs_assign_nn_resident(gs_graph *g, int32_t n, const double *dev_poses_xytheta, int32_t n_poses, const int32_t *dev_pose_of_obs,
+                           const double *dev_obs_4xn, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov_3x3,
+                           const gs_nn_params *params, int32_t *dev_out_index, double *dev_out_d2);
+int  gs_frame_frontend_assign(gs_graph *g, const double pose_xytheta[3], const double *pose_cov_3x3, const double *obs_4xk, int32_t k,
+                              const gs_nn_params *params, double *out_zxy, double *out_gxy, int32_t *out_index, double *out_d2);
 
 /* ---- multi-GPU: pose-window shards -----------------------------
  * Each rank owns a contiguous pose window and builds the SAME global plan; it linearises and

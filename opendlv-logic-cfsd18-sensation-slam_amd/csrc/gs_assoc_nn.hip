@@ -5,6 +5,7 @@
 //   k_assoc_nn_grid   a thread per observation, the nine buckets of the hashed grid around it (cell edge from max_distance)
 //   k_frame_nn        one frame in one launch: a workgroup per observation, its 256 threads stride over the map
 //   k_map_cov_gather  map covariances out of the gathered marginals (gs_map_set_cov_from_marginals)
+//   k_assign_nn       the one-to-one association inside frames (gs_assign_nn_*, gs_frame_frontend_assign): further down, with its own text
 //
 // The three association kernels return IDENTICAL bits: the query's side (z, g, Q + P) is nn_query, one candidate's side (S, det, d2 and
 // the five tests) is nn_pair, both without contraction, the A0 conversion is ONE out-of-line function (polar_to_xy compiled once, not
@@ -183,6 +184,138 @@ __global__ void __launch_bounds__(256) k_map_cov_gather(int n, const int64_t *__
     dst[4 * (size_t)k] = v.x; dst[4 * (size_t)k + 1] = v.y; dst[4 * (size_t)k + 2] = v.z; dst[4 * (size_t)k + 3] = v.w;
 }
 
+// ---- one-to-one association inside a frame (include/graphslam.h, "one-to-one association"): the greedy matching over the frame's admissible
+// pairs in ascending (d2, observation, cone).  A wave owns fpw consecutive frames (1, 2, 4 or 8: the host's guess from the mean frame size,
+// which decides speed only) and gives each W lanes, W = 64 / fpw or the power of two that holds the wave's largest frame: 64 / W frames run
+// side by side, the rest in further passes — a frame of 8 keeps 8 lanes busy, not 64.  With W = 64 lane l owns observations l, l + 64,
+// l + 128, l + 192 of the one frame.  No barrier between waves (their round counts differ).  Per observation the wave keeps its PROPOSAL —
+// the best admissible cone by (d2, j) that no observation of the frame has taken — in LDS (12 bytes), and each frame's taken cones in an
+// open-addressed table (512 words of LDS a wave, shared out among its frames: always at least two words per observation).
+// A round: (1) observations without a proposal search (all of them in the first round, afterwards only those whose
+// proposed cone was just taken; the query is recomputed by nn_query, the same bits, rather than kept for 256 observations), (2) the minimum
+// of the open proposals by (d2, i, j) over the wave, (3) that pair is taken.  The minimum open proposal IS the frame's smallest open pair —
+// every open observation proposes its own smallest open pair — so the pairs are taken in exactly the greedy's order, one per round; the
+// mutual-best contest of the rule's text would take several per round at k pair evaluations per observation, which costs more than the
+// 24 shuffles of a round here.  d2 and "admissible" are nn_query / nn_pair: nothing about a pair differs from the kernels above.
+static constexpr int AS_NEED = -3, AS_DONE = -2;                               // an observation's state where it holds no proposal
+static constexpr int AS_TABLE = 512;                                           // >= 2 x GS_NN_FRAME_MAX: a probe always meets an empty word
+static constexpr int AS_SLOTS = 4;                                             // GS_NN_FRAME_MAX / 64
+static constexpr int AS_PACKED_TABLE = 128;                                    // the wave's table words in use when groups share it (64 / W groups of 2 W words)
+
+// a frame's taken cones: its words of the wave's table in LDS (-1 = empty), mask + 1 of them, at least twice the frame's observations
+struct AsTaken { int32_t *t; uint32_t mask; };
+__device__ __forceinline__ uint32_t as_hash(int j, uint32_t mask) { return (((uint32_t)j * 2654435761u) >> 23) & mask; }
+__device__ __forceinline__ bool as_taken(const AsTaken &tk, int j) {
+    for (uint32_t h = as_hash(j, tk.mask);; h = (h + 1) & tk.mask) { const int v = tk.t[h]; if (v == j) return true; if (v < 0) return false; }
+}
+__device__ __forceinline__ void as_take(const AsTaken &tk, int j) {
+    uint32_t h = as_hash(j, tk.mask); while (tk.t[h] >= 0) h = (h + 1) & tk.mask;
+    tk.t[h] = j;
+}
+// the proposal's order (d2, j); a taken cone is looked up only when it would win
+__device__ __forceinline__ void as_offer(double &bd, int &bj, double d2, int j, const AsTaken &tk) {
+    if ((d2 < bd || (d2 == bd && j < bj)) && !as_taken(tk, j)) { bd = d2; bj = j; }
+}
+// (bd, bj) <- the query's best admissible cone that is not taken: the nine buckets of the grid (as k_assoc_nn_grid walks them) or the whole map
+template <bool GRID>
+__device__ __forceinline__ void as_search(const NnQuery &q, const NnDev &p, int n_map, const double *__restrict__ map_xy, const int32_t *__restrict__ map_type,
+        const double *__restrict__ map_cov, const GridParams &g, const int32_t *__restrict__ cell_start, const int32_t *__restrict__ cell_items,
+        const AsTaken &tk, double &bd, int &bj) {
+    if (GRID) {
+        const long long cx = grid_coord(q.gx, g.inv_cell), cy = grid_coord(q.gy, g.inv_cell);
+        uint32_t bk[9]; int s0[9], s1[9];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) { bk[c] = grid_bucket(cx + (c % 3) - 1, cy + (c / 3) - 1, g.mask); s0[c] = cell_start[bk[c]]; s1[c] = cell_start[bk[c] + 1]; }
+#pragma unroll
+        for (int c = 1; c < 9; ++c)                                            // two of the nine cells in ONE bucket: walked once
+            for (int m = 0; m < c; ++m) if (bk[m] == bk[c]) s1[c] = s0[c];
+#pragma unroll
+        for (int c = 0; c < 9; ++c)
+            for (int t = s0[c]; t < s1[c]; ++t) { const int j = cell_items[t];
+                const double2 xy = reinterpret_cast<const double2 *>(map_xy)[j];
+                double c00 = 0.0, c01 = 0.0, c11 = 0.0;
+                if (map_cov) { const double4 cv = reinterpret_cast<const double4 *>(map_cov)[j]; c00 = cv.x; c01 = cv.y; c11 = cv.w; }
+                double d2;
+                if (nn_pair(q, p, xy.x, xy.y, c00, c01, c11, map_type[j], d2)) as_offer(bd, bj, d2, j, tk); }
+    } else {
+        for (int j = 0; j < n_map; ++j) {
+            const double2 xy = reinterpret_cast<const double2 *>(map_xy)[j];
+            double c00 = 0.0, c01 = 0.0, c11 = 0.0;
+            if (map_cov) { const double4 cv = reinterpret_cast<const double4 *>(map_cov)[j]; c00 = cv.x; c01 = cv.y; c11 = cv.w; }
+            double d2;
+            if (nn_pair(q, p, xy.x, xy.y, c00, c01, c11, map_type[j], d2)) as_offer(bd, bj, d2, j, tk);
+        }
+    }
+}
+
+template <bool GRID>
+__global__ void __launch_bounds__(256) k_assign_nn(int n, const double *__restrict__ poses, int n_poses, const int32_t *__restrict__ pose_of_obs,
+        const double *__restrict__ obs, int n_frames, const int32_t *__restrict__ frame_start, int fpw, double lidar, int n_map,
+        const double *__restrict__ map_xy, const int32_t *__restrict__ map_type, const double *__restrict__ map_cov,
+        const double *__restrict__ pose_cov, NnDev p, GridParams g, const int32_t *__restrict__ cell_start, const int32_t *__restrict__ cell_items,
+        int32_t *__restrict__ out_idx, double *__restrict__ out_d2, double *__restrict__ out_z, double *__restrict__ out_g) {
+    __shared__ double s_d2[4][AS_SLOTS * 64];                                  // 8 + 4 + 8 = 20 KB a workgroup
+    __shared__ int32_t s_j[4][AS_SLOTS * 64];
+    __shared__ int32_t s_taken[4][AS_TABLE];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int f0 = (blockIdx.x * 4 + w) * fpw;                                 // this wave's frames: [f0, f0 + fpw), fpw in {1, 2, 4, 8}
+    if (f0 >= n_frames) return;
+    // W lanes per frame: 64 / fpw when every frame of the wave fits, else the next power of two that holds the largest (wave-uniform)
+    int W = 64 / fpw;
+    for (int t = 0; t < fpw && f0 + t < n_frames; ++t) { const int a = frame_start[f0 + t], b = frame_start[f0 + t + 1];
+        if (a >= 0 && b >= a && b <= n && b - a <= AS_SLOTS * 64) while (W < 64 && W < b - a) W <<= 1; }
+    const int gp = 64 / W, gi = lane >> __builtin_ctz(W), lg = lane & (W - 1);    // frames per pass, this lane's group and its place in it
+    const int tsz = W == 64 ? AS_TABLE : 2 * W;
+    double *pd = s_d2[w]; int32_t *pj = s_j[w]; const AsTaken tk{s_taken[w] + gi * tsz, (uint32_t)tsz - 1};
+    for (int ps = 0; ps * gp < fpw; ++ps) {                                    // 64 / W frames side by side, pass after pass
+        int a = 0, b = 0;
+        const int f = f0 + ps * gp + gi;
+        if (ps * gp + gi < fpw && f < n_frames) {
+            a = frame_start[f]; b = frame_start[f + 1];
+            if (a < 0 || b < a || b > n) a = b = 0;                            // not a frame of this call: nothing read, nothing written
+            else if (b - a > AS_SLOTS * 64) {                                  // beyond GS_NN_FRAME_MAX: refused as a whole
+                for (int i = a + lg; i < b; i += W) { out_idx[i] = -1; if (out_d2) out_d2[i] = __builtin_inf(); }
+                a = b = 0; }
+        }
+        const int slots = (b - a + 63) >> 6;                                   // of this lane's frame: 0 (none), 1, or up to 4 when W == 64
+        for (int t = lane; t < (W == 64 ? AS_TABLE : AS_PACKED_TABLE); t += 64) s_taken[w][t] = -1;
+        for (int s = 0; s < slots; ++s) pj[s * 64 + lane] = a + s * 64 + lg < b ? AS_NEED : AS_DONE;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        for (bool first = true;; first = false) {
+            // (1) the search
+            for (int s = 0; s < slots; ++s) {
+                const int e = s * 64 + lane, i = a + s * 64 + lg;
+                if (pj[e] != AS_NEED) continue;
+                const NnQuery q = nn_query_of(i, n, poses, n_poses, pose_of_obs, obs, pose_cov, lidar, p);
+                if (first && out_z) { out_z[2 * i] = q.zx; out_z[2 * i + 1] = q.zy; out_g[2 * i] = q.gx; out_g[2 * i + 1] = q.gy; }
+                double bd = __builtin_inf(); int bj = NN_NONE;
+                if (q.valid) as_search<GRID>(q, p, n_map, map_xy, map_type, map_cov, g, cell_start, cell_items, tk, bd, bj);
+                if (bj == NN_NONE) { out_idx[i] = -1; if (out_d2) out_d2[i] = __builtin_inf(); pj[e] = AS_DONE; }      // no open cone left: final
+                else { pd[e] = bd; pj[e] = bj; }
+            }
+            // (2) the smallest open pair by (d2, i): a lane's slots ascend in i, then the frame's lanes by butterfly (every lane ends with the result)
+            double md = __builtin_inf(); int mi = NN_NONE, mj = NN_NONE;
+            for (int s = 0; s < slots; ++s) { const int e = s * 64 + lane, j = pj[e];
+                if (j >= 0) { const double d = pd[e]; if (mi == NN_NONE || d < md) { md = d; mi = a + s * 64 + lg; mj = j; } } }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) {
+                if (off >= W) continue;                                        // (wave-uniform) the butterfly stays inside the frame's W lanes
+                const double od = __shfl_xor(md, off, 64); const int oi = __shfl_xor(mi, off, 64), oj = __shfl_xor(mj, off, 64);
+                if (oi != NN_NONE && (mi == NN_NONE || od < md || (od == md && oi < mi))) { md = od; mi = oi; mj = oj; }
+            }
+            // (3) the pair is taken; whoever proposed its cone searches again.  A frame without an open proposal is finished (its lanes idle)
+            if (mi != NN_NONE) {
+                if (lg == 0) as_take(tk, mj);
+                for (int s = 0; s < slots; ++s) { const int e = s * 64 + lane;
+                    if (a + s * 64 + lg == mi) { out_idx[mi] = mj; if (out_d2) out_d2[mi] = md; pj[e] = AS_DONE; }
+                    else if (pj[e] == mj) pj[e] = AS_NEED; }
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (__ballot(mi != NN_NONE) == 0) break;                           // wave-uniform: every frame of the pass is finished
+        }
+    }
+}
+
 void launch_assoc_nn(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, double lidar, int n_map,
                      const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
                      int32_t *out_idx, double *out_d2, double *out_second, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
@@ -205,6 +338,22 @@ void launch_frame_nn(int k, const double *in, int has_pose_cov, double lidar, in
 }
 void launch_map_cov_gather(int n, const int64_t *src, const double *values, double *map_cov_first, hipStream_t st) {
     if (n > 0) hipLaunchKernelGGL(k_map_cov_gather, dim3((n + 255) / 256), dim3(256), 0, st, n, src, values, map_cov_first);
+}
+void launch_assign_nn(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, int n_frames, const int32_t *frame_start,
+                      double lidar, int n_map, const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
+                      long long buckets, const int32_t *cell_start, const int32_t *cell_items, int32_t *out_idx, double *out_d2, double *out_z, double *out_g,
+                      hipStream_t st, hipEvent_t start, hipEvent_t stop) {
+    if (n <= 0 || n_frames <= 0) return;
+    // frames per wave from the MEAN frame size (the host does not see the resident call's offsets): a guess that costs time when it is
+    // wrong — the kernel widens W to its largest frame and runs passes — and never changes a result
+    const long long mean = ((long long)n + n_frames - 1) / n_frames;
+    const int fpw = mean <= 8 ? 8 : mean <= 16 ? 4 : mean <= 32 ? 2 : 1;
+    const dim3 grid((n_frames + 4 * fpw - 1) / (4 * fpw)), block(256);
+    if (cell_start) hipExtLaunchKernelGGL(k_assign_nn<true>, grid, block, 0, st, start, stop, 0, n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, fpw, lidar,
+                                          n_map, map_xy, map_type, map_cov, pose_cov, p, grid_params_of(p.max_distance, buckets), cell_start, cell_items,
+                                          out_idx, out_d2, out_z, out_g);
+    else hipExtLaunchKernelGGL(k_assign_nn<false>, grid, block, 0, st, start, stop, 0, n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, fpw, lidar,
+                               n_map, map_xy, map_type, map_cov, pose_cov, p, GridParams{}, cell_start, cell_items, out_idx, out_d2, out_z, out_g);
 }
 
 }  // namespace gs

@@ -25,5 +25,13 @@ void launch_frame_nn(int k, const double *in, int has_pose_cov, double lidar, in
                      const double *map_cov, NnDev p, double *out_z, double *out_g, int32_t *out_idx, double *out_d2, double *out_second, hipStream_t st);
 // map_cov[4 * (first + k) + c] = src[k] < 0 ? 0 : values[src[k] + c], k < n, c < 4
 void launch_map_cov_gather(int n, const int64_t *src, const double *values, double *map_cov_first, hipStream_t st);
+// one-to-one association inside frames [frame_start[f], frame_start[f + 1]), f < n_frames (everything in device memory): a wave per 1 .. 8 frames, by their mean size.
+// cell_start != null: the nine buckets of the hashed grid (buckets, cell_start, cell_items); null: brute force over the map.
+// A frame whose bounds are not 0 <= a <= b <= n touches nothing; one above GS_NN_FRAME_MAX gets -1 / +inf.  out_d2 may be null;
+// out_z / out_g (both or neither): every covered observation's CoG-frame and global XY, as launch_frame_nn writes them.
+void launch_assign_nn(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, int n_frames, const int32_t *frame_start,
+                      double lidar, int n_map, const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
+                      long long buckets, const int32_t *cell_start, const int32_t *cell_items, int32_t *out_idx, double *out_d2, double *out_z, double *out_g,
+                      hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 }  // namespace gs

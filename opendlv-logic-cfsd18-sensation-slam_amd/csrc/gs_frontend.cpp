@@ -34,7 +34,9 @@ static int arena_reserve(gs_graph *g, size_t bytes) {
     return GS_OK;
 }
 static size_t padded(size_t n, size_t elem) { return (std::max<size_t>(n, 1) * elem + 255) & ~(size_t)255; }
+static void assign_staging_release(gs_graph *g);      // the one-to-one frame call's staging (below)
 void gs_frontend_release(gs_graph *g) {      // gs_destroy
+    assign_staging_release(g);
     if (g->fe.arena) hipFree(g->fe.arena);
     if (g->fe.pin_in) hipHostFree(g->fe.pin_in);
     if (g->fe.pin_out) hipHostFree(g->fe.pin_out);
@@ -464,5 +466,150 @@ extern "C" int gs_frame_frontend_nn(gs_graph *g, const double pose[3], const dou
     const char *po = fe.nn_pin_out;
     std::memcpy(out_zxy, po, bz); std::memcpy(out_gxy, po + bz, bz); std::memcpy(out_d2, po + 2 * bz, bd); std::memcpy(out_second, po + 2 * bz + bd, bd);
     std::memcpy(out_idx, po + 2 * bz + 2 * bd, bi);
+    return GS_OK;
+}
+
+// ---- one-to-one association inside a frame (gs_assoc_nn.hip, k_assign_nn): the batch / resident / frame calls -----------------------
+static int frame_start_check(int32_t n, int32_t n_frames, const int32_t *fs) {
+    if (n_frames < 0 || !fs) return fail(GS_ERR_INVALID, "bad argument");
+    if (fs[0] != 0 || fs[n_frames] != n) return fail(GS_ERR_INVALID, "frame_start must begin at 0 and end at n");
+    for (int f = 0; f < n_frames; ++f) {
+        if (fs[f + 1] < fs[f]) return fail(GS_ERR_INVALID, "frame_start must ascend");
+        if (fs[f + 1] - fs[f] > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations"); }
+    return GS_OK;
+}
+extern "C" int gs_assign_nn_batch(gs_graph *g, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs, const double *obs,
+                                  int32_t n_frames, const int32_t *frame_start, int32_t n_map, const double *map_xy, const int32_t *map_type,
+                                  const double *map_cov, const double *pose_cov, const gs_nn_params *params, int32_t *out, double *out_d2) {
+    if (!g || n < 0 || npose < 0 || n_map < 0 || (n > 0 && (!poses || !pose_of_obs || !obs || !out)) || (n_map > 0 && (!map_xy || !map_type)))
+        return fail(GS_ERR_INVALID, "bad argument");
+    NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
+    if ((rc = frame_start_check(n, n_frames, frame_start)) != GS_OK) return rc;
+    for (int i = 0; i < n; ++i) if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n == 0) return GS_OK;
+    bool grid = n_map >= 2048;                                      // as gs_associate_nn_batch
+    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && n_map > 0;
+    long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
+    if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(9 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded((size_t)n_frames + 1, 4) +
+                               padded(2 * (size_t)n_map, 8) + padded(4 * (size_t)n_map, 8) + padded(n_map, 4) + padded(n, 4) + padded(n, 8) + gbytes)) != GS_OK) return rc;
+    Carver c{g}; double *p = c.get<double>(3 * (size_t)npose), *pcv = c.get<double>(9 * (size_t)npose); int32_t *po = c.get<int32_t>(n);
+    double *ob = c.get<double>(4 * (size_t)n); int32_t *fs = c.get<int32_t>((size_t)n_frames + 1);
+    double *mx = c.get<double>(2 * (size_t)n_map), *mc = c.get<double>(4 * (size_t)n_map);
+    int32_t *mt = c.get<int32_t>(n_map), *o = c.get<int32_t>(n); double *od = c.get<double>(n);
+    HIP_TRY(hipMemcpyAsync(p, poses, 3 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
+    if (pose_cov && npose > 0) HIP_TRY(hipMemcpyAsync(pcv, pose_cov, 9 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(po, pose_of_obs, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(fs, frame_start, ((size_t)n_frames + 1) * 4, hipMemcpyHostToDevice, g->stream));
+    if (n_map > 0) { HIP_TRY(hipMemcpyAsync(mx, map_xy, 2 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream));
+                     HIP_TRY(hipMemcpyAsync(mt, map_type, (size_t)n_map * 4, hipMemcpyHostToDevice, g->stream));
+                     if (map_cov) HIP_TRY(hipMemcpyAsync(mc, map_cov, 4 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream)); }
+    const double *dmc = map_cov ? mc : nullptr, *dpc = pose_cov ? pcv : nullptr;
+    GridBufs gb{};
+    if (grid) { gb = grid_carve(c.get<char>(gbytes), n_map, buckets);
+        launch_grid_build(n_map, mx, nd.max_distance, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream); }
+    launch_assign_nn(n, p, npose, po, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, mt, dmc, dpc, nd, buckets, grid ? gb.start : nullptr, grid ? gb.items : nullptr,
+                     o, od, nullptr, nullptr, g->stream);
+    HIP_TRY(hipMemcpyAsync(out, o, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (out_d2) HIP_TRY(hipMemcpyAsync(out_d2, od, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));        // the one wait of the call: the result copies
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("assignment (nn): ") + hipGetErrorString(e));
+    return GS_OK;
+}
+// the resident map through either search: the launch both the resident and the frame call end in
+static int assign_resident_launch(gs_graph *g, bool grid, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
+                                  int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov, const NnDev &nd, int32_t *dev_out, double *dev_out_d2,
+                                  double *dev_z, double *dev_g) {
+    auto &fe = g->fe; GridBufs gb{}; int rc;
+    if (grid) { if ((rc = resident_grid(g, nd.max_distance)) != GS_OK) return rc;
+        gb = grid_carve(fe.grid_mem, fe.map_n, fe.grid_max_cells); }
+    launch_assign_nn(n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, fe.map_cov,
+                     dev_pose_cov, nd, gb.buckets, grid ? gb.start : nullptr, grid ? gb.items : nullptr, dev_out, dev_out_d2, dev_z, dev_g, g->stream, g->ev_lin[0], g->ev_lin[1]);
+    return GS_OK;
+}
+extern "C" int gs_assign_nn_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
+                                     int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov, const gs_nn_params *params,
+                                     int32_t *dev_out, double *dev_out_d2) {
+    if (!g || n < 0 || npose < 0 || n_frames < 0 || !dev_frame_start || (n > 0 && (!dev_poses || !dev_pose_of_obs || !dev_obs || !dev_out)))
+        return fail(GS_ERR_INVALID, "bad argument");
+    NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
+    if (((uintptr_t)dev_obs & 31) != 0) return fail(GS_ERR_INVALID, "dev_obs must be 32-byte aligned (an observation is read in one load)");
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n == 0 || n_frames == 0) return GS_OK;
+    const bool grid = g->fe.map_n > 0 && g->opt.assoc_grid != 0;     // as gs_associate_nn_resident
+    if ((rc = assign_resident_launch(g, grid, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, nd, dev_out, dev_out_d2,
+                                     nullptr, nullptr)) != GS_OK) return rc;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("assignment (nn): ") + hipGetErrorString(e));
+    return GS_OK;
+}
+// the twin of gs_debug_time_associate_nn_resident: start / stop events on the assignment kernel's dispatch, the grid built before
+extern "C" int gs_debug_time_assign_nn_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
+                                                const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov,
+                                                const gs_nn_params *params, int32_t *dev_out, double *dev_out_d2, int32_t reps, double *out_ms) {
+    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
+    int rc = gs_assign_nn_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2);     // warm (and the grid)
+    if (rc != GS_OK) return rc;
+    std::vector<hipEvent_t> ev(2 * (size_t)reps); for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    for (int r = 0; r < reps && rc == GS_OK; ++r) { g->ev_lin[0] = ev[2 * (size_t)r]; g->ev_lin[1] = ev[2 * (size_t)r + 1];
+        rc = gs_assign_nn_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2); }
+    g->ev_lin[0] = g->ev_lin[1] = nullptr;
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    double tot = 0; int cnt = 0;
+    for (int r = 0; r < reps; ++r) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]) == hipSuccess && ms > 0) { tot += ms; ++cnt; } }
+    (void)hipGetLastError();
+    for (auto &e : ev) hipEventDestroy(e);
+    *out_ms = cnt ? tot / cnt : 0.0;
+    return rc;
+}
+static void assign_staging_release(gs_graph *g) {      // gs_frontend_release, and before the staging grows
+    auto &fe = g->fe;
+    if (fe.as_pin_in) hipHostFree(fe.as_pin_in);
+    if (fe.as_pin_out) hipHostFree(fe.as_pin_out);
+    if (fe.as_dev_in) hipFree(fe.as_dev_in);
+    if (fe.as_dev_out) hipFree(fe.as_dev_out);
+    fe.as_pin_in = fe.as_pin_out = fe.as_dev_in = fe.as_dev_out = nullptr; fe.as_cap_obs = 0;
+}
+// one frame through the resident launch.  Staging (bytes): pose at 0, pose_cov at 32, obs at 128 (32-byte aligned: one load per observation),
+// then frame_start[2] and pose_of_obs[k] (zeros) as int32
+extern "C" int gs_frame_frontend_assign(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
+                                        double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2) {
+    if (!g || !pose || k < 0 || (k > 0 && (!obs || !out_zxy || !out_gxy || !out_idx || !out_d2))) return fail(GS_ERR_INVALID, "bad argument");
+    NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
+    if (k > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations");
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (k == 0) return GS_OK;
+    auto &fe = g->fe;
+    auto in_bytes = [](size_t m) { return (16 + 4 * m) * sizeof(double) + (2 + m) * sizeof(int32_t); };
+    if (k > fe.as_cap_obs) {                                         // grow-only, as gs_frame_frontend_nn's
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        assign_staging_release(g);
+        const int cap = std::min<int>(GS_NN_FRAME_MAX, std::max(64, k + k / 2));
+        const size_t bout = (size_t)cap * (5 * sizeof(double) + sizeof(int32_t));
+        HIP_TRY(hipHostMalloc((void **)&fe.as_pin_in, in_bytes(cap), hipHostMallocDefault)); HIP_TRY(hipHostMalloc((void **)&fe.as_pin_out, bout, hipHostMallocDefault));
+        HIP_TRY(hipMalloc((void **)&fe.as_dev_in, in_bytes(cap))); HIP_TRY(hipMalloc((void **)&fe.as_dev_out, bout));
+        fe.as_cap_obs = cap;
+    }
+    const size_t bz = (size_t)k * 2 * sizeof(double), bd = (size_t)k * sizeof(double), bi = (size_t)k * sizeof(int32_t), oint = (16 + 4 * (size_t)k) * sizeof(double);
+    std::memset(fe.as_pin_in, 0, in_bytes(k));
+    std::memcpy(fe.as_pin_in, pose, 3 * sizeof(double));
+    if (pose_cov) std::memcpy(fe.as_pin_in + 32, pose_cov, 9 * sizeof(double));
+    std::memcpy(fe.as_pin_in + 128, obs, 4 * (size_t)k * sizeof(double));
+    ((int32_t *)(fe.as_pin_in + oint))[1] = k;
+    const double *dp = (const double *)fe.as_dev_in; const int32_t *dfs = (const int32_t *)(fe.as_dev_in + oint);
+    double *dz = (double *)fe.as_dev_out, *dg = dz + 2 * (size_t)k, *dd = dg + 2 * (size_t)k; int32_t *di = (int32_t *)(dd + k);
+    HIP_TRY(hipMemcpyAsync(fe.as_dev_in, fe.as_pin_in, in_bytes(k), hipMemcpyHostToDevice, g->stream));
+    bool grid = fe.map_n >= 2048;                                    // by the map's size, as the batch call; gs_debug_options.assoc_grid forces either
+    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && fe.map_n > 0;
+    if ((rc = assign_resident_launch(g, grid, k, dp, 1, dfs + 2, dp + 16, 1, dfs, pose_cov ? dp + 4 : nullptr, nd, di, dd, dz, dg)) != GS_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(fe.as_pin_out, fe.as_dev_out, 2 * bz + bd + bi, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    fe.pin_map_busy = false;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("assignment (nn): ") + hipGetErrorString(e));
+    const char *po = fe.as_pin_out;
+    std::memcpy(out_zxy, po, bz); std::memcpy(out_gxy, po + bz, bz); std::memcpy(out_d2, po + 2 * bz, bd); std::memcpy(out_idx, po + 2 * bz + bd, bi);
     return GS_OK;
 }
