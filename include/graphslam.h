@@ -748,8 +748,8 @@ int  gs_frame_frontend_nn(gs_graph *g, const double pose_xytheta[3], const doubl
  *      cones, brute force below; gs_debug_options.assoc_grid forces either); out_zxy / out_gxy are the bits gs_frame_frontend_nn returns.
  *      k above the cap: GS_ERR_INVALID.  Its staging buffers exist from the first call on and only grow.
  * A handle that never calls any of these allocates and launches nothing for them; the calls above are unchanged by them.
- * NOT DONE: this is NOT the minimum-sum assignment (Hungarian) and NOT joint compatibility — a greedy matching can be beaten in total d2;
- *      the Slam mirror and the shell keep the Euclidean lowest-index rule; no cross-covariance; no signed localizer type test; frames of
+ * NOT DONE: this is NOT the minimum-sum assignment — a greedy matching can be beaten in total d2 (the minimum-cost association below is
+ *      that assignment) — and NOT joint compatibility; the Slam mirror and the shell keep the Euclidean lowest-index rule; no cross-covariance; no signed localizer type test; frames of
  *      more than GS_NN_FRAME_MAX observations; sharded handles: nothing beyond what the gs_associate_nn_* calls give. */
 #define GS_NN_FRAME_MAX 256
 int  gs_assign_nn_batch(gs_graph *g, int32_t n, const double *poses_xytheta, int32_t n_poses, const int32_t *pose_of_obs, const double *obs_4xn,
@@ -760,6 +760,48 @@ int  gs_assign_nn_resident(gs_graph *g, int32_t n, const double *dev_poses_xythe
                            const gs_nn_params *params, int32_t *dev_out_index, double *dev_out_d2);
 int  gs_frame_frontend_assign(gs_graph *g, const double pose_xytheta[3], const double *pose_cov_3x3, const double *obs_4xk, int32_t k,
                               const gs_nn_params *params, double *out_zxy, double *out_gxy, int32_t *out_index, double *out_d2);
+
+/* ---- minimum-cost association: a frame's cones matched at least total d2 ------------------------------------------
+ * The greedy matching above takes the smallest pair first, so a cone grabbed early can push a neighbour to a worse cone or to none.  These
+ * calls return the assignment of smallest total instead.
+ *
+ * Frames, pair distances, "admissible" and invalid queries are exactly those of the one-to-one association: frame_start, at most
+ *      GS_NN_FRAME_MAX observations a frame, d2(i, j) by the same fp64 operations, no contraction.  Nothing about a pair changes.
+ * Candidates.  Observation i competes with its GS_ASSIGN_CAND_MAX admissible cones of smallest (d2, cone index).  An observation with more
+ *      admissible cones loses the rest: the cut is part of the rule, and n_admissible (below) reports where it applied.
+ * Assignment.  Among all matchings of the frame over these candidate pairs — every observation at most one cone, every cone at most one
+ *      observation — one that MAXIMISES the total gain  sum (gate_chi2 - d2(i, j))  over its pairs.  That is the same as minimising
+ *      sum d2 + gate_chi2 * (unmatched observations): the usual gated assignment with one dummy column of cost gate_chi2 per observation.
+ *      d2 < gate_chi2 holds strictly for an admissible pair, so every pair has positive gain and the result is MAXIMAL: no observation is
+ *      left at -1 while a cone on its list is free.
+ * Ties.  Where two matchings have the same total, which one is returned is not stated; all calls and both searches return the same one.
+ *      The duals of the solver are fp64: the returned total is within  48 k^2 2^-53 gate_chi2  of the best (k = the frame's observations).
+ * Outputs, per observation.  index = the cone, or -1;  d2 = the pair's d2 (the bits the covariance-gated association computes), or +inf;
+ *      n_admissible (optional, int32) = how many admissible cones the search met, NOT capped: a value above GS_ASSIGN_CAND_MAX says that
+ *      the cut applied to this observation.  An invalid query gets -1, +inf and 0 and takes part in nothing.
+ * Consequences.  In a frame where gs_associate_nn_* returns no cone twice the result equals it in index and d2, bit for bit.  The total
+ *      gain is never below that of the greedy matching (ascending (d2, observation, cone)) over the same candidate pairs.
+ *
+ * gs_assign_opt_batch / gs_assign_opt_resident / gs_frame_frontend_assign_opt: the arguments, layouts, refusals, search choice (the grid from
+ *      2048 cones; gs_debug_options.assoc_grid forces either) and the resident kernel's defences of gs_assign_nn_batch /
+ *      gs_assign_nn_resident / gs_frame_frontend_assign, plus out_n_admissible (may be NULL).  The defences with it: a frame with bad bounds
+ *      reads and writes nothing; a frame longer than GS_NN_FRAME_MAX writes -1, +inf and 0 for all its observations; observations that no
+ *      frame covers are not written, in any of the three outputs.
+ * A handle that never calls any of these allocates and launches nothing for them; the calls above are unchanged by them.
+ * NOT DONE: joint compatibility; no cross-covariance; the Slam mirror and the shell keep the Euclidean lowest-index rule; frames of more than
+ *      GS_NN_FRAME_MAX observations; more than GS_ASSIGN_CAND_MAX candidates per observation; no signed localizer type test; sharded
+ *      handles: nothing beyond what the gs_associate_nn_* calls give. */
+#define GS_ASSIGN_CAND_MAX 8
+int  gs_assign_opt_batch(gs_graph *g, int32_t n, const double *poses_xytheta, int32_t n_poses, const int32_t *pose_of_obs, const double *obs_4xn,
+                         int32_t n_frames, const int32_t *frame_start, int32_t n_map, const double *map_xy, const int32_t *map_type,
+                         const double *map_cov_2x2, const double *pose_cov_3x3, const gs_nn_params *params, int32_t *out_index, double *out_d2,
+                         int32_t *out_n_admissible);
+int  gs_assign_opt_resident(gs_graph *g, int32_t n, const double *dev_poses_xytheta, int32_t n_poses, const int32_t *dev_pose_of_obs,
+                            const double *dev_obs_4xn, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov_3x3,
+                            const gs_nn_params *params, int32_t *dev_out_index, double *dev_out_d2, int32_t *dev_out_n_admissible);
+int  gs_frame_frontend_assign_opt(gs_graph *g, const double pose_xytheta[3], const double *pose_cov_3x3, const double *obs_4xk, int32_t k,
+                                  const gs_nn_params *params, double *out_zxy, double *out_gxy, int32_t *out_index, double *out_d2,
+                                  int32_t *out_n_admissible);
 
 /* ---- multi-GPU: pose-window shards -----------------------------
  * Each rank owns a contiguous pose window and builds the SAME global plan; it linearises and

@@ -307,7 +307,13 @@ def lib():
         L.gs_assign_nn_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, vp, vp]
         L.gs_debug_time_assign_nn_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, vp, vp, C.c_int32, _dp]
         L.gs_frame_frontend_assign.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, _dp, _dp, _ip, _dp]
-    if hasattr(L, "gs_set_robust_kernel"):                 # (a tuning build of an older tree loaded through GS_LIB may predate the robust kernels)
+    if hasattr(L, "gs_assign_opt_batch"):                  # (and for the minimum-cost association)
+        npp = C.POINTER(NnParams)
+        L.gs_assign_opt_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32, _ip, C.c_int32, _dp, _ip, _dp, _dp, npp, _ip, _dp, _ip]
+        L.gs_assign_opt_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, vp, vp, vp]
+        L.gs_debug_time_assign_opt_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, vp, vp, vp, C.c_int32, _dp]
+        L.gs_frame_frontend_assign_opt.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, _dp, _dp, _ip, _dp, _ip]
+    if hasattr(L, "gs_set_robust_kernel"):                # (a tuning build of an older tree loaded through GS_LIB may predate the robust kernels)
         L.gs_set_robust_kernel.argtypes = [vp, C.c_int32, C.c_int32, C.c_double]
         L.gs_get_robust_kernel.argtypes = [vp, C.c_int32, _ip, _dp]
         L.gs_get_edge_chi2.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp]
@@ -1002,6 +1008,42 @@ class Graph:
         z = np.zeros((k, 2)); gx = np.zeros((k, 2)); idx = np.zeros(k, dtype=np.int32); d2 = np.zeros(k)
         self._check(self.L.gs_frame_frontend_assign(self.h, _d(pose), None if pc is None else _d(pc), _d(obs), k, C.byref(p), _d(z), _d(gx), _i(idx), _d(d2)))
         return z, gx, idx, d2
+
+    # ---- minimum-cost association (include/graphslam.h): the same frames, the matching of largest total gain over each observation's 8 best cones
+    def assign_opt(self, poses, pose_of_obs, obs, frame_start, map_xy, map_type, map_cov=None, pose_cov=None, params=None):
+        """gs_assign_opt_batch: (index [n] int32, d2 [n], n_admissible [n] int32)"""
+        poses = _f64(poses, (-1, 3)); obs = _f64(obs, (-1, 4)); po = _i32(pose_of_obs); fs = _i32(frame_start)
+        map_xy = _f64(map_xy, (-1, 2)); map_type = _i32(map_type); n = len(obs)
+        mc = None if map_cov is None else _f64(map_cov, (-1, 4)); pc = None if pose_cov is None else _f64(pose_cov, (-1, 9))
+        assert mc is None or len(mc) == len(map_xy); assert pc is None or len(pc) == len(poses); assert len(fs) >= 1
+        p = nn_params() if params is None else params
+        idx = np.zeros(n, dtype=np.int32); d2 = np.zeros(n); na = np.zeros(n, dtype=np.int32)
+        self._check(self.L.gs_assign_opt_batch(self.h, n, _d(poses), len(poses), _i(po), _d(obs), len(fs) - 1, _i(fs), len(map_xy), _d(map_xy), _i(map_type),
+                                               None if mc is None else _d(mc), None if pc is None else _d(pc), C.byref(p), _i(idx), _d(d2), _i(na)))
+        return idx, d2, na
+
+    def assign_opt_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_out, d_out_d2=None, d_out_na=None, d_pose_cov=None, params=None):
+        """gs_assign_opt_resident: the resident map and its covariances, everything else DeviceArray; asynchronous (synchronize() before reading)"""
+        p = nn_params() if params is None else params
+        opt = lambda a: None if a is None else a.ptr
+        self._check(self.L.gs_assign_opt_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, int(n_frames), d_frame_start.ptr,
+                                                  opt(d_pose_cov), C.byref(p), d_out.ptr, opt(d_out_d2), opt(d_out_na)))
+
+    def time_assign_opt_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_out, reps, d_out_d2=None, d_out_na=None, d_pose_cov=None, params=None):
+        p = nn_params() if params is None else params
+        opt = lambda a: None if a is None else a.ptr
+        ms = C.c_double()
+        self._check(self.L.gs_debug_time_assign_opt_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, int(n_frames), d_frame_start.ptr,
+                                                             opt(d_pose_cov), C.byref(p), d_out.ptr, opt(d_out_d2), opt(d_out_na), int(reps), C.byref(ms)))
+        return ms.value
+
+    def frame_frontend_assign_opt(self, pose, obs, pose_cov=None, params=None):
+        """(zxy [k,2], gxy [k,2], idx [k], d2 [k], n_admissible [k]) of one frame's observations [k,4], matched at least total d2"""
+        pose = _f64(pose); obs = _f64(obs, (-1, 4)); k = len(obs); pc = None if pose_cov is None else _f64(pose_cov, (9,))
+        p = nn_params() if params is None else params
+        z = np.zeros((k, 2)); gx = np.zeros((k, 2)); idx = np.zeros(k, dtype=np.int32); d2 = np.zeros(k); na = np.zeros(k, dtype=np.int32)
+        self._check(self.L.gs_frame_frontend_assign_opt(self.h, _d(pose), None if pc is None else _d(pc), _d(obs), k, C.byref(p), _d(z), _d(gx), _i(idx), _d(d2), _i(na)))
+        return z, gx, idx, d2, na
 
     # ---- pose-window shards (one handle per rank / GPU)
     def dist_configure(self, rank, world):

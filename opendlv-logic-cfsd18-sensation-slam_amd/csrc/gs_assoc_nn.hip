@@ -316,6 +316,234 @@ __global__ void __launch_bounds__(256) k_assign_nn(int n, const double *__restri
     }
 }
 
+// ---- minimum-cost association inside a frame (include/graphslam.h, "minimum-cost association"): among the matchings over every observation's
+// AO_CAND admissible cones of smallest (d2, j), one of largest total gain sum(gate_chi2 - d2).  Three phases per frame:
+//   COLLECT   an observation's admissible count and its AO_CAND smallest (d2, j), kept sorted in registers by compare-and-swap (a minimum
+//             over (d2, j) does not depend on the order the cones arrive in), then in LDS, candidate-major ([t][row]: no bank conflicts).
+//   SHORTCUT  every observation claims its first candidate in the frame's open-addressed table (an LDS compare-and-swap); no claim met
+//             another one: the first candidates are the answer (each observation has its own smallest d2: no matching has a smaller sum).
+//   SOLVE     successive shortest augmenting paths (Jonker-Volgenant) over the lists, rows = the frame's observations in ascending order,
+//             a private dummy column of cost gate_chi2 per row, duals in fp64.  The search tree of a row is kept PER ROW, not per column
+//             (a row has at most AO_CAND + 1 edges): a tree row holds the distance rd it was reached at and how (pred); a column is scanned
+//             iff its matched row is in the tree; a step takes the minimum over the tree rows' unscanned edges of
+//             ((rd + d2) - u[row]) - v[column] by (value, row, slot) — the solve is a function of the lists alone.  v is nonzero only for
+//             matched columns and is stored with the matched row (vm), the table maps a matched cone to its row (matched columns stay
+//             matched, so the table only grows); unmatched and dummy columns have v = 0.  A step either adds a row to the tree or ends
+//             the path: at most rows + 1 steps per row, and every loop below is bounded by the frame's rows, AO_CAND, or the table size.
+// Lanes: as k_assign_nn — W lanes per frame, 64 / W frames side by side in a wave, wave-scope fences only.  k_assign_opt runs four waves of
+// 64 rows each (frames of up to 64 observations; 9.5 KB of LDS a wave); k_assign_opt_big is ONE wave of 256 rows (38 KB) that takes the
+// frames above 64 — either every frame (the host expects large frames) or, after k_assign_opt, only those it left out.
+static constexpr int AO_CAND = 8;                                              // GS_ASSIGN_CAND_MAX
+static constexpr int AO_DUMMY = 8, AO_NOMATE = 9;                              // a row's mate: a slot of its list, its dummy column, or nothing yet
+
+template <int SLOTS> struct AoLds {
+    static constexpr int ROWS = 64 * SLOTS, TAB = 2 * ROWS;
+    double cd[AO_CAND][ROWS];                                                  // the lists: d2 and cone, sorted by (d2, j)
+    int32_t cj[AO_CAND][ROWS];
+    double u[ROWS], vm[ROWS], rd[ROWS];                                        // row dual; the dual of the row's matched column; tree distance
+    int32_t tkey[TAB], tval[TAB];                                              // matched cone -> row (-1 = empty)
+    int32_t cnt[ROWS], mate[ROWS], stamp[ROWS], pred[ROWS];                    // candidates; mate; the root whose tree holds the row; 16 * row + slot it was reached by
+};
+struct AoArgs {
+    int n; const double *poses; int n_poses; const int32_t *pose_of_obs; const double *obs; int n_frames; const int32_t *frame_start; int fpw, only_large;
+    double lidar; int n_map; const double *map_xy; const int32_t *map_type; const double *map_cov, *pose_cov; NnDev p; GridParams g;
+    const int32_t *cell_start, *cell_items; int32_t *out_idx; double *out_d2; int32_t *out_na; double *out_z, *out_g;
+};
+__device__ __forceinline__ void ao_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+__device__ __forceinline__ uint32_t ao_hash(int j, uint32_t mask) { return (((uint32_t)j * 2654435761u) >> 21) & mask; }
+// the row matched to cone j, or -1
+__device__ __forceinline__ int ao_find(const int32_t *tkey, const int32_t *tval, uint32_t mask, int j) {
+    uint32_t h = ao_hash(j, mask);
+    for (uint32_t pr = 0; pr <= mask; ++pr, h = (h + 1) & mask) { const int v = tkey[h]; if (v == j) return tval[h]; if (v < 0) return -1; }
+    return -1;
+}
+__device__ __forceinline__ void ao_put(int32_t *tkey, int32_t *tval, uint32_t mask, int j, int row) {
+    uint32_t h = ao_hash(j, mask);
+    for (uint32_t pr = 0; pr <= mask; ++pr, h = (h + 1) & mask) { const int v = tkey[h]; if (v == j || v < 0) { tkey[h] = j; tval[h] = row; return; } }
+}
+// false when another observation of the frame has claimed cone j already
+__device__ __forceinline__ bool ao_claim(int32_t *tkey, uint32_t mask, int j) {
+    uint32_t h = ao_hash(j, mask);
+    for (uint32_t pr = 0; pr <= mask; ++pr, h = (h + 1) & mask) { const int v = atomicCAS(&tkey[h], -1, j); if (v == -1) return true; if (v == j) return false; }
+    return false;
+}
+// (d2, j) into the sorted list: static indices only, so the list stays in registers
+__device__ __forceinline__ void ao_insert(double (&bd)[AO_CAND], int (&bj)[AO_CAND], double d2, int j) {
+#pragma unroll
+    for (int t = 0; t < AO_CAND; ++t)
+        if (d2 < bd[t] || (d2 == bd[t] && j < bj[t])) { const double td = bd[t]; const int tj = bj[t]; bd[t] = d2; bj[t] = j; d2 = td; j = tj; }
+}
+template <bool GRID>
+__device__ __forceinline__ void ao_collect(const NnQuery &q, const AoArgs &A, double (&bd)[AO_CAND], int (&bj)[AO_CAND], int &na) {
+    const double *__restrict__ map_xy = A.map_xy; const double *__restrict__ map_cov = A.map_cov; const int32_t *__restrict__ map_type = A.map_type;
+    if (GRID) {
+        const long long cx = grid_coord(q.gx, A.g.inv_cell), cy = grid_coord(q.gy, A.g.inv_cell);
+        uint32_t bk[9]; int s0[9], s1[9];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) { bk[c] = grid_bucket(cx + (c % 3) - 1, cy + (c / 3) - 1, A.g.mask); s0[c] = A.cell_start[bk[c]]; s1[c] = A.cell_start[bk[c] + 1]; }
+#pragma unroll
+        for (int c = 1; c < 9; ++c)                                            // two of the nine cells in ONE bucket: walked once
+            for (int m = 0; m < c; ++m) if (bk[m] == bk[c]) s1[c] = s0[c];
+#pragma unroll
+        for (int c = 0; c < 9; ++c)
+            for (int t = s0[c]; t < s1[c]; ++t) { const int j = A.cell_items[t];
+                const double2 xy = reinterpret_cast<const double2 *>(map_xy)[j];
+                double c00 = 0.0, c01 = 0.0, c11 = 0.0;
+                if (map_cov) { const double4 cv = reinterpret_cast<const double4 *>(map_cov)[j]; c00 = cv.x; c01 = cv.y; c11 = cv.w; }
+                double d2;
+                if (nn_pair(q, A.p, xy.x, xy.y, c00, c01, c11, map_type[j], d2)) { ++na; ao_insert(bd, bj, d2, j); } }
+    } else {
+        for (int j = 0; j < A.n_map; ++j) {
+            const double2 xy = reinterpret_cast<const double2 *>(map_xy)[j];
+            double c00 = 0.0, c01 = 0.0, c11 = 0.0;
+            if (map_cov) { const double4 cv = reinterpret_cast<const double4 *>(map_cov)[j]; c00 = cv.x; c01 = cv.y; c11 = cv.w; }
+            double d2;
+            if (nn_pair(q, A.p, xy.x, xy.y, c00, c01, c11, map_type[j], d2)) { ++na; ao_insert(bd, bj, d2, j); }
+        }
+    }
+}
+
+// one pass of a wave: lane group gi (W lanes, lane lg of it) solves the frame [a, b) (a == b: none), b - a <= W (W < 64) or <= 64 * SLOTS
+template <bool GRID, int SLOTS>
+__device__ __forceinline__ void ao_pass(AoLds<SLOTS> &L, const AoArgs &A, int a, int b, int W, int gi, int lg, int lane) {
+    const int k = b - a, eb = gi * W, slots = (k + 63) >> 6;                   // rows; the LDS row of the frame's row 0; rows per lane
+    const int tsz = W == 64 ? AoLds<SLOTS>::TAB : 2 * W;                        // the frame's table: at least two words per row
+    int32_t *tkey = L.tkey + gi * tsz, *tval = L.tval + gi * tsz; const uint32_t mask = (uint32_t)tsz - 1;
+    const double gate = A.p.gate_chi2;
+    // COLLECT
+    for (int t = lane; t < AoLds<SLOTS>::TAB; t += 64) L.tkey[t] = -1;
+    for (int s = 0; s < slots; ++s) {
+        const int rl = s * 64 + lg, e = eb + rl; int c = 0;
+        if (rl < k) {
+            const int i = a + rl;
+            const NnQuery q = nn_query_of(i, A.n, A.poses, A.n_poses, A.pose_of_obs, A.obs, A.pose_cov, A.lidar, A.p);
+            if (A.out_z) { A.out_z[2 * i] = q.zx; A.out_z[2 * i + 1] = q.zy; A.out_g[2 * i] = q.gx; A.out_g[2 * i + 1] = q.gy; }
+            double bd[AO_CAND]; int bj[AO_CAND]; int na = 0;
+#pragma unroll
+            for (int t = 0; t < AO_CAND; ++t) { bd[t] = __builtin_inf(); bj[t] = NN_NONE; }
+            if (q.valid) ao_collect<GRID>(q, A, bd, bj, na);
+            if (A.out_na) A.out_na[i] = na;
+            c = na < AO_CAND ? na : AO_CAND;
+#pragma unroll
+            for (int t = 0; t < AO_CAND; ++t) { L.cd[t][e] = bd[t]; L.cj[t][e] = bj[t]; }
+        }
+        L.cnt[e] = c; L.mate[e] = AO_NOMATE; L.stamp[e] = -1;
+    }
+    ao_sync();
+    // SHORTCUT
+    bool dup = false;
+    for (int s = 0; s < slots; ++s) { const int rl = s * 64 + lg, e = eb + rl;
+        if (rl < k && L.cnt[e] > 0 && !ao_claim(tkey, mask, L.cj[0][e])) dup = true; }
+    const unsigned long long gm = W == 64 ? ~0ull : ((1ull << W) - 1) << eb;
+    const bool contested = (__ballot(dup) & gm) != 0;                          // (uniform over the frame's lanes)
+    ao_sync();
+    if (!contested) {
+        for (int s = 0; s < slots; ++s) { const int rl = s * 64 + lg, e = eb + rl;
+            if (rl < k) { const bool m = L.cnt[e] > 0; A.out_idx[a + rl] = m ? L.cj[0][e] : -1; if (A.out_d2) A.out_d2[a + rl] = m ? L.cd[0][e] : __builtin_inf(); } }
+    } else
+        for (int t = lg; t < tsz; t += W) tkey[t] = -1;
+    // SOLVE: `root` is the row being added (k: the frame is finished); rows without a candidate are passed over
+    int root = k;
+    if (contested) { root = 0; while (root < k && L.cnt[eb + root] == 0) ++root;
+        if (lg == 0 && root < k) { L.stamp[eb + root] = root; L.rd[eb + root] = 0.0; L.u[eb + root] = 0.0; } }
+    ao_sync();
+    const int cap = W == 64 ? 64 * SLOTS : W, maxit = (cap + 2) * (cap + 2);  // rows * (rows + 1) steps at the most: a hard stop all the same
+    for (int it = 0; it < maxit; ++it) {
+        const bool act = root < k;
+        if (__ballot(act) == 0) break;                                         // wave-uniform: every frame of the pass is finished
+        // (1) the smallest unscanned edge of this lane's tree rows; (row, slot) ascend, so < keeps the first
+        double mk = __builtin_inf(); int mr = NN_NONE, ms = 0;
+        if (act)
+            for (int s = 0; s < slots; ++s) { const int rl = s * 64 + lg, e = eb + rl;
+                if (rl >= k || L.stamp[e] != root) continue;
+                const double rdv = L.rd[e], uv = L.u[e]; const int c = L.cnt[e];
+                for (int t = 0; t < c; ++t) {
+                    const int r = ao_find(tkey, tval, mask, L.cj[t][e]);
+                    if (r >= 0 && L.stamp[eb + r] == root) continue;           // the column is scanned
+                    const double key = ((rdv + L.cd[t][e]) - uv) - (r >= 0 ? L.vm[eb + r] : 0.0);
+                    if (mr == NN_NONE || key < mk) { mk = key; mr = rl; ms = t; }
+                }
+                if (L.mate[e] != AO_DUMMY) { const double key = (rdv + gate) - uv;
+                    if (mr == NN_NONE || key < mk) { mk = key; mr = rl; ms = AO_DUMMY; } }
+            }
+        // (2) over the frame's lanes by butterfly, by (value, row, slot): every lane ends with the result
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            if (off >= W) continue;
+            const double od = __shfl_xor(mk, off, 64); const int orw = __shfl_xor(mr, off, 64), os = __shfl_xor(ms, off, 64);
+            if (orw != NN_NONE && (mr == NN_NONE || od < mk || (od == mk && (orw < mr || (orw == mr && os < ms))))) { mk = od; mr = orw; ms = os; }
+        }
+        // (3) a matched column: its row joins the tree.  A free or a dummy column: the path ends — duals, then the flip along pred
+        int r = -1; bool term = false;
+        if (act) {
+            if (mr == NN_NONE) root = k;                                       // (cannot happen: the root's dummy column is always free)
+            else { if (ms != AO_DUMMY) r = ao_find(tkey, tval, mask, L.cj[ms][eb + mr]);
+                term = r < 0;
+                if (!term && lg == 0) { L.stamp[eb + r] = root; L.rd[eb + r] = mk; L.pred[eb + r] = 16 * mr + ms; } }
+        }
+        if (term)
+            for (int s = 0; s < slots; ++s) { const int rl = s * 64 + lg, e = eb + rl;
+                if (rl < k && L.stamp[e] == root) { const double dl = mk - L.rd[e]; L.u[e] += dl; if (rl != root) L.vm[e] -= dl; } }
+        ao_sync();
+        if (term) {
+            if (lg == 0) {
+                int row = mr, slot = ms; double cv = 0.0;
+                for (int nn = 0; nn <= k; ++nn) {
+                    const int e = eb + row; const double ov = L.vm[e]; const int pd = L.pred[e];
+                    L.mate[e] = slot; L.vm[e] = cv;
+                    if (slot != AO_DUMMY) ao_put(tkey, tval, mask, L.cj[slot][e], row);
+                    if (row == root) break;
+                    cv = ov; row = pd >> 4; slot = pd & 15;                    // the row's old column goes to the row it was reached from
+                }
+            }
+            ++root; while (root < k && L.cnt[eb + root] == 0) ++root;
+            if (lg == 0 && root < k) { L.stamp[eb + root] = root; L.rd[eb + root] = 0.0; L.u[eb + root] = 0.0; }
+        }
+        ao_sync();
+    }
+    if (contested)
+        for (int s = 0; s < slots; ++s) { const int rl = s * 64 + lg, e = eb + rl;
+            if (rl < k) { const int m = L.mate[e]; A.out_idx[a + rl] = m < AO_CAND ? L.cj[m][e] : -1;
+                if (A.out_d2) A.out_d2[a + rl] = m < AO_CAND ? L.cd[m][e] : __builtin_inf(); } }
+    ao_sync();                                                                 // the next pass fills the same LDS
+}
+// a frame of the call, or none: bounds outside 0 <= a <= b <= n read and write nothing; above GS_NN_FRAME_MAX: -1 / +inf / 0 (when `refuse`)
+__device__ __forceinline__ void ao_frame(const AoArgs &A, int f, bool refuse, int lg, int W, int &a, int &b) {
+    a = A.frame_start[f]; b = A.frame_start[f + 1];
+    if (a < 0 || b < a || b > A.n) a = b = 0;
+    else if (b - a > 256) {
+        if (refuse) for (int i = a + lg; i < b; i += W) { A.out_idx[i] = -1; if (A.out_d2) A.out_d2[i] = __builtin_inf(); if (A.out_na) A.out_na[i] = 0; }
+        a = b = 0; }
+}
+template <bool GRID>
+__global__ void __launch_bounds__(256) k_assign_opt(AoArgs A) {
+    __shared__ AoLds<1> Ls[4];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int f0 = (blockIdx.x * 4 + w) * A.fpw;                               // this wave's frames: [f0, f0 + fpw), fpw in {2, 4, 8}
+    if (f0 >= A.n_frames) return;
+    int W = 64 / A.fpw;                                                        // as k_assign_nn; frames above 64 are k_assign_opt_big's
+    for (int t = 0; t < A.fpw && f0 + t < A.n_frames; ++t) { const int a = A.frame_start[f0 + t], b = A.frame_start[f0 + t + 1];
+        if (a >= 0 && b >= a && b <= A.n && b - a <= 64) while (W < 64 && W < b - a) W <<= 1; }
+    const int gp = 64 / W, gi = lane >> __builtin_ctz(W), lg = lane & (W - 1);
+    for (int ps = 0; ps * gp < A.fpw; ++ps) {
+        int a = 0, b = 0; const int f = f0 + ps * gp + gi;
+        if (ps * gp + gi < A.fpw && f < A.n_frames) { ao_frame(A, f, false, lg, W, a, b); if (b - a > 64) a = b = 0; }
+        ao_pass<GRID, 1>(Ls[w], A, a, b, W, gi, lg, lane);
+    }
+}
+template <bool GRID>
+__global__ void __launch_bounds__(64) k_assign_opt_big(AoArgs A) {
+    __shared__ AoLds<4> L;
+    const int lane = threadIdx.x, f0 = blockIdx.x * A.fpw;
+    for (int t = 0; t < A.fpw && f0 + t < A.n_frames; ++t) {
+        int a, b; ao_frame(A, f0 + t, true, lane, 64, a, b);
+        if (b == a || (A.only_large && b - a <= 64)) continue;                 // (wave-uniform)
+        ao_pass<GRID, 4>(L, A, a, b, 64, 0, lane, lane);
+    }
+}
+
 void launch_assoc_nn(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, double lidar, int n_map,
                      const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
                      int32_t *out_idx, double *out_d2, double *out_second, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
@@ -354,6 +582,28 @@ void launch_assign_nn(int n, const double *poses, int n_poses, const int32_t *po
                                           out_idx, out_d2, out_z, out_g);
     else hipExtLaunchKernelGGL(k_assign_nn<false>, grid, block, 0, st, start, stop, 0, n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, fpw, lidar,
                                n_map, map_xy, map_type, map_cov, pose_cov, p, GridParams{}, cell_start, cell_items, out_idx, out_d2, out_z, out_g);
+}
+void launch_assign_opt(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, int n_frames, const int32_t *frame_start,
+                       double lidar, int n_map, const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
+                       long long buckets, const int32_t *cell_start, const int32_t *cell_items, int32_t *out_idx, double *out_d2, int32_t *out_na,
+                       double *out_z, double *out_g, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
+    if (n <= 0 || n_frames <= 0) return;
+    // the MEAN frame size decides speed only, as in launch_assign_nn.  Up to 32: k_assign_opt (2 .. 8 frames a wave, frames of up to 64),
+    // then k_assign_opt_big over groups of 64 frames for those above 64 (its waves find none as a rule).  Above: k_assign_opt_big alone,
+    // a wave per frame.  start sits on the first dispatch and stop on the last.
+    const long long mean = ((long long)n + n_frames - 1) / n_frames;
+    AoArgs A{n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, 1, 0, lidar, n_map, map_xy, map_type, map_cov, pose_cov, p,
+             cell_start ? grid_params_of(p.max_distance, buckets) : GridParams{}, cell_start, cell_items, out_idx, out_d2, out_na, out_z, out_g};
+    if (mean <= 32) {
+        A.fpw = mean <= 8 ? 8 : mean <= 16 ? 4 : 2;
+        const dim3 grid((n_frames + 4 * A.fpw - 1) / (4 * A.fpw)), block(256);
+        if (cell_start) hipExtLaunchKernelGGL(k_assign_opt<true>, grid, block, 0, st, start, nullptr, 0, A);
+        else hipExtLaunchKernelGGL(k_assign_opt<false>, grid, block, 0, st, start, nullptr, 0, A);
+        A.fpw = 64; A.only_large = 1; start = nullptr;
+    }
+    const dim3 grid((n_frames + A.fpw - 1) / A.fpw), block(64);
+    if (cell_start) hipExtLaunchKernelGGL(k_assign_opt_big<true>, grid, block, 0, st, start, stop, 0, A);
+    else hipExtLaunchKernelGGL(k_assign_opt_big<false>, grid, block, 0, st, start, stop, 0, A);
 }
 
 }  // namespace gs

@@ -33,5 +33,11 @@ void launch_assign_nn(int n, const double *poses, int n_poses, const int32_t *po
                       double lidar, int n_map, const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
                       long long buckets, const int32_t *cell_start, const int32_t *cell_items, int32_t *out_idx, double *out_d2, double *out_z, double *out_g,
                       hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// minimum-cost association inside the same frames, same arguments and defences; out_na (may be null): every covered observation's count of
+// admissible cones, uncapped (0 in a frame above GS_NN_FRAME_MAX).  One or two dispatches: start on the first, stop on the last.
+void launch_assign_opt(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, int n_frames, const int32_t *frame_start,
+                       double lidar, int n_map, const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
+                       long long buckets, const int32_t *cell_start, const int32_t *cell_items, int32_t *out_idx, double *out_d2, int32_t *out_na,
+                       double *out_z, double *out_g, hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 }  // namespace gs

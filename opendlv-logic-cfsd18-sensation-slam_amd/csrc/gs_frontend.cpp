@@ -478,9 +478,10 @@ static int frame_start_check(int32_t n, int32_t n_frames, const int32_t *fs) {
         if (fs[f + 1] - fs[f] > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations"); }
     return GS_OK;
 }
-extern "C" int gs_assign_nn_batch(gs_graph *g, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs, const double *obs,
-                                  int32_t n_frames, const int32_t *frame_start, int32_t n_map, const double *map_xy, const int32_t *map_type,
-                                  const double *map_cov, const double *pose_cov, const gs_nn_params *params, int32_t *out, double *out_d2) {
+// the greedy matching (opt false: k_assign_nn) or the minimum-cost one (opt true: k_assign_opt, which also counts the admissible cones)
+static int assign_batch(gs_graph *g, bool opt, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs, const double *obs,
+                        int32_t n_frames, const int32_t *frame_start, int32_t n_map, const double *map_xy, const int32_t *map_type,
+                        const double *map_cov, const double *pose_cov, const gs_nn_params *params, int32_t *out, double *out_d2, int32_t *out_na) {
     if (!g || n < 0 || npose < 0 || n_map < 0 || (n > 0 && (!poses || !pose_of_obs || !obs || !out)) || (n_map > 0 && (!map_xy || !map_type)))
         return fail(GS_ERR_INVALID, "bad argument");
     NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
@@ -492,11 +493,11 @@ extern "C" int gs_assign_nn_batch(gs_graph *g, int32_t n, const double *poses, i
     if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && n_map > 0;
     long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
     if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(9 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded((size_t)n_frames + 1, 4) +
-                               padded(2 * (size_t)n_map, 8) + padded(4 * (size_t)n_map, 8) + padded(n_map, 4) + padded(n, 4) + padded(n, 8) + gbytes)) != GS_OK) return rc;
+                               padded(2 * (size_t)n_map, 8) + padded(4 * (size_t)n_map, 8) + padded(n_map, 4) + padded(n, 4) + padded(n, 8) + (opt ? padded(n, 4) : 0) + gbytes)) != GS_OK) return rc;
     Carver c{g}; double *p = c.get<double>(3 * (size_t)npose), *pcv = c.get<double>(9 * (size_t)npose); int32_t *po = c.get<int32_t>(n);
     double *ob = c.get<double>(4 * (size_t)n); int32_t *fs = c.get<int32_t>((size_t)n_frames + 1);
     double *mx = c.get<double>(2 * (size_t)n_map), *mc = c.get<double>(4 * (size_t)n_map);
-    int32_t *mt = c.get<int32_t>(n_map), *o = c.get<int32_t>(n); double *od = c.get<double>(n);
+    int32_t *mt = c.get<int32_t>(n_map), *o = c.get<int32_t>(n); double *od = c.get<double>(n); int32_t *ona = opt ? c.get<int32_t>(n) : nullptr;
     HIP_TRY(hipMemcpyAsync(p, poses, 3 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
     if (pose_cov && npose > 0) HIP_TRY(hipMemcpyAsync(pcv, pose_cov, 9 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
     HIP_TRY(hipMemcpyAsync(po, pose_of_obs, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
@@ -509,29 +510,45 @@ extern "C" int gs_assign_nn_batch(gs_graph *g, int32_t n, const double *poses, i
     GridBufs gb{};
     if (grid) { gb = grid_carve(c.get<char>(gbytes), n_map, buckets);
         launch_grid_build(n_map, mx, nd.max_distance, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream); }
-    launch_assign_nn(n, p, npose, po, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, mt, dmc, dpc, nd, buckets, grid ? gb.start : nullptr, grid ? gb.items : nullptr,
-                     o, od, nullptr, nullptr, g->stream);
+    if (opt) launch_assign_opt(n, p, npose, po, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, mt, dmc, dpc, nd, buckets, grid ? gb.start : nullptr,
+                               grid ? gb.items : nullptr, o, od, ona, nullptr, nullptr, g->stream);
+    else launch_assign_nn(n, p, npose, po, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, mt, dmc, dpc, nd, buckets, grid ? gb.start : nullptr, grid ? gb.items : nullptr,
+                          o, od, nullptr, nullptr, g->stream);
     HIP_TRY(hipMemcpyAsync(out, o, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
     if (out_d2) HIP_TRY(hipMemcpyAsync(out_d2, od, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    if (out_na) HIP_TRY(hipMemcpyAsync(out_na, ona, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));        // the one wait of the call: the result copies
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("assignment (nn): ") + hipGetErrorString(e));
     return GS_OK;
 }
+extern "C" int gs_assign_nn_batch(gs_graph *g, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs, const double *obs,
+                                  int32_t n_frames, const int32_t *frame_start, int32_t n_map, const double *map_xy, const int32_t *map_type,
+                                  const double *map_cov, const double *pose_cov, const gs_nn_params *params, int32_t *out, double *out_d2) {
+    return assign_batch(g, false, n, poses, npose, pose_of_obs, obs, n_frames, frame_start, n_map, map_xy, map_type, map_cov, pose_cov, params, out, out_d2, nullptr);
+}
+extern "C" int gs_assign_opt_batch(gs_graph *g, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs, const double *obs,
+                                   int32_t n_frames, const int32_t *frame_start, int32_t n_map, const double *map_xy, const int32_t *map_type,
+                                   const double *map_cov, const double *pose_cov, const gs_nn_params *params, int32_t *out, double *out_d2, int32_t *out_na) {
+    return assign_batch(g, true, n, poses, npose, pose_of_obs, obs, n_frames, frame_start, n_map, map_xy, map_type, map_cov, pose_cov, params, out, out_d2, out_na);
+}
 // the resident map through either search: the launch both the resident and the frame call end in
-static int assign_resident_launch(gs_graph *g, bool grid, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
+static int assign_resident_launch(gs_graph *g, bool opt, bool grid, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
                                   int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov, const NnDev &nd, int32_t *dev_out, double *dev_out_d2,
-                                  double *dev_z, double *dev_g) {
+                                  int32_t *dev_out_na, double *dev_z, double *dev_g) {
     auto &fe = g->fe; GridBufs gb{}; int rc;
     if (grid) { if ((rc = resident_grid(g, nd.max_distance)) != GS_OK) return rc;
         gb = grid_carve(fe.grid_mem, fe.map_n, fe.grid_max_cells); }
-    launch_assign_nn(n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, fe.map_cov,
-                     dev_pose_cov, nd, gb.buckets, grid ? gb.start : nullptr, grid ? gb.items : nullptr, dev_out, dev_out_d2, dev_z, dev_g, g->stream, g->ev_lin[0], g->ev_lin[1]);
+    if (opt) launch_assign_opt(n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, fe.map_cov,
+                               dev_pose_cov, nd, gb.buckets, grid ? gb.start : nullptr, grid ? gb.items : nullptr, dev_out, dev_out_d2, dev_out_na, dev_z, dev_g,
+                               g->stream, g->ev_lin[0], g->ev_lin[1]);
+    else launch_assign_nn(n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, fe.map_cov,
+                          dev_pose_cov, nd, gb.buckets, grid ? gb.start : nullptr, grid ? gb.items : nullptr, dev_out, dev_out_d2, dev_z, dev_g, g->stream, g->ev_lin[0], g->ev_lin[1]);
     return GS_OK;
 }
-extern "C" int gs_assign_nn_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
-                                     int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov, const gs_nn_params *params,
-                                     int32_t *dev_out, double *dev_out_d2) {
+static int assign_resident(gs_graph *g, bool opt, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
+                           int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov, const gs_nn_params *params,
+                           int32_t *dev_out, double *dev_out_d2, int32_t *dev_out_na) {
     if (!g || n < 0 || npose < 0 || n_frames < 0 || !dev_frame_start || (n > 0 && (!dev_poses || !dev_pose_of_obs || !dev_obs || !dev_out)))
         return fail(GS_ERR_INVALID, "bad argument");
     NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
@@ -539,22 +556,32 @@ extern "C" int gs_assign_nn_resident(gs_graph *g, int32_t n, const double *dev_p
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n == 0 || n_frames == 0) return GS_OK;
     const bool grid = g->fe.map_n > 0 && g->opt.assoc_grid != 0;     // as gs_associate_nn_resident
-    if ((rc = assign_resident_launch(g, grid, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, nd, dev_out, dev_out_d2,
-                                     nullptr, nullptr)) != GS_OK) return rc;
+    if ((rc = assign_resident_launch(g, opt, grid, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, nd, dev_out, dev_out_d2,
+                                     dev_out_na, nullptr, nullptr)) != GS_OK) return rc;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("assignment (nn): ") + hipGetErrorString(e));
     return GS_OK;
 }
-// the twin of gs_debug_time_associate_nn_resident: start / stop events on the assignment kernel's dispatch, the grid built before
-extern "C" int gs_debug_time_assign_nn_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
-                                                const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov,
-                                                const gs_nn_params *params, int32_t *dev_out, double *dev_out_d2, int32_t reps, double *out_ms) {
+extern "C" int gs_assign_nn_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
+                                     int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov, const gs_nn_params *params,
+                                     int32_t *dev_out, double *dev_out_d2) {
+    return assign_resident(g, false, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2, nullptr);
+}
+extern "C" int gs_assign_opt_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
+                                      int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov, const gs_nn_params *params,
+                                      int32_t *dev_out, double *dev_out_d2, int32_t *dev_out_na) {
+    return assign_resident(g, true, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2, dev_out_na);
+}
+// the twins of gs_debug_time_associate_nn_resident: start / stop events on the assignment's dispatches, the grid built before
+static int time_assign_resident(gs_graph *g, bool opt, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
+                                const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov,
+                                const gs_nn_params *params, int32_t *dev_out, double *dev_out_d2, int32_t *dev_out_na, int32_t reps, double *out_ms) {
     if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
-    int rc = gs_assign_nn_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2);     // warm (and the grid)
+    int rc = assign_resident(g, opt, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2, dev_out_na);     // warm (and the grid)
     if (rc != GS_OK) return rc;
     std::vector<hipEvent_t> ev(2 * (size_t)reps); for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
     for (int r = 0; r < reps && rc == GS_OK; ++r) { g->ev_lin[0] = ev[2 * (size_t)r]; g->ev_lin[1] = ev[2 * (size_t)r + 1];
-        rc = gs_assign_nn_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2); }
+        rc = assign_resident(g, opt, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2, dev_out_na); }
     g->ev_lin[0] = g->ev_lin[1] = nullptr;
     HIP_TRY(hipStreamSynchronize(g->stream));
     double tot = 0; int cnt = 0;
@@ -563,6 +590,16 @@ extern "C" int gs_debug_time_assign_nn_resident(gs_graph *g, int32_t n, const do
     for (auto &e : ev) hipEventDestroy(e);
     *out_ms = cnt ? tot / cnt : 0.0;
     return rc;
+}
+extern "C" int gs_debug_time_assign_nn_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
+                                                const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov,
+                                                const gs_nn_params *params, int32_t *dev_out, double *dev_out_d2, int32_t reps, double *out_ms) {
+    return time_assign_resident(g, false, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2, nullptr, reps, out_ms);
+}
+extern "C" int gs_debug_time_assign_opt_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
+                                                 const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov,
+                                                 const gs_nn_params *params, int32_t *dev_out, double *dev_out_d2, int32_t *dev_out_na, int32_t reps, double *out_ms) {
+    return time_assign_resident(g, true, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2, dev_out_na, reps, out_ms);
 }
 static void assign_staging_release(gs_graph *g) {      // gs_frontend_release, and before the staging grows
     auto &fe = g->fe;
@@ -574,8 +611,8 @@ static void assign_staging_release(gs_graph *g) {      // gs_frontend_release, a
 }
 // one frame through the resident launch.  Staging (bytes): pose at 0, pose_cov at 32, obs at 128 (32-byte aligned: one load per observation),
 // then frame_start[2] and pose_of_obs[k] (zeros) as int32
-extern "C" int gs_frame_frontend_assign(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
-                                        double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2) {
+static int frame_assign(gs_graph *g, bool opt, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
+                        double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2, int32_t *out_na) {
     if (!g || !pose || k < 0 || (k > 0 && (!obs || !out_zxy || !out_gxy || !out_idx || !out_d2))) return fail(GS_ERR_INVALID, "bad argument");
     NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
     if (k > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations");
@@ -587,7 +624,7 @@ extern "C" int gs_frame_frontend_assign(gs_graph *g, const double pose[3], const
         HIP_TRY(hipStreamSynchronize(g->stream));
         assign_staging_release(g);
         const int cap = std::min<int>(GS_NN_FRAME_MAX, std::max(64, k + k / 2));
-        const size_t bout = (size_t)cap * (5 * sizeof(double) + sizeof(int32_t));
+        const size_t bout = (size_t)cap * (5 * sizeof(double) + 2 * sizeof(int32_t));        // z, g, d2, index, admissible count
         HIP_TRY(hipHostMalloc((void **)&fe.as_pin_in, in_bytes(cap), hipHostMallocDefault)); HIP_TRY(hipHostMalloc((void **)&fe.as_pin_out, bout, hipHostMallocDefault));
         HIP_TRY(hipMalloc((void **)&fe.as_dev_in, in_bytes(cap))); HIP_TRY(hipMalloc((void **)&fe.as_dev_out, bout));
         fe.as_cap_obs = cap;
@@ -599,17 +636,26 @@ extern "C" int gs_frame_frontend_assign(gs_graph *g, const double pose[3], const
     std::memcpy(fe.as_pin_in + 128, obs, 4 * (size_t)k * sizeof(double));
     ((int32_t *)(fe.as_pin_in + oint))[1] = k;
     const double *dp = (const double *)fe.as_dev_in; const int32_t *dfs = (const int32_t *)(fe.as_dev_in + oint);
-    double *dz = (double *)fe.as_dev_out, *dg = dz + 2 * (size_t)k, *dd = dg + 2 * (size_t)k; int32_t *di = (int32_t *)(dd + k);
+    double *dz = (double *)fe.as_dev_out, *dg = dz + 2 * (size_t)k, *dd = dg + 2 * (size_t)k; int32_t *di = (int32_t *)(dd + k), *dn = di + k;
     HIP_TRY(hipMemcpyAsync(fe.as_dev_in, fe.as_pin_in, in_bytes(k), hipMemcpyHostToDevice, g->stream));
     bool grid = fe.map_n >= 2048;                                    // by the map's size, as the batch call; gs_debug_options.assoc_grid forces either
     if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && fe.map_n > 0;
-    if ((rc = assign_resident_launch(g, grid, k, dp, 1, dfs + 2, dp + 16, 1, dfs, pose_cov ? dp + 4 : nullptr, nd, di, dd, dz, dg)) != GS_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(fe.as_pin_out, fe.as_dev_out, 2 * bz + bd + bi, hipMemcpyDeviceToHost, g->stream));
+    if ((rc = assign_resident_launch(g, opt, grid, k, dp, 1, dfs + 2, dp + 16, 1, dfs, pose_cov ? dp + 4 : nullptr, nd, di, dd, opt ? dn : nullptr, dz, dg)) != GS_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(fe.as_pin_out, fe.as_dev_out, 2 * bz + bd + (opt ? 2 : 1) * bi, hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
     fe.pin_map_busy = false;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("assignment (nn): ") + hipGetErrorString(e));
     const char *po = fe.as_pin_out;
     std::memcpy(out_zxy, po, bz); std::memcpy(out_gxy, po + bz, bz); std::memcpy(out_d2, po + 2 * bz, bd); std::memcpy(out_idx, po + 2 * bz + bd, bi);
+    if (out_na) std::memcpy(out_na, po + 2 * bz + bd + bi, bi);
     return GS_OK;
+}
+extern "C" int gs_frame_frontend_assign(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
+                                        double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2) {
+    return frame_assign(g, false, pose, pose_cov, obs, k, params, out_zxy, out_gxy, out_idx, out_d2, nullptr);
+}
+extern "C" int gs_frame_frontend_assign_opt(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
+                                            double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2, int32_t *out_na) {
+    return frame_assign(g, true, pose, pose_cov, obs, k, params, out_zxy, out_gxy, out_idx, out_d2, out_na);
 }
