@@ -749,7 +749,7 @@ int  gs_frame_frontend_nn(gs_graph *g, const double pose_xytheta[3], const doubl
  *      k above the cap: GS_ERR_INVALID.  Its staging buffers exist from the first call on and only grow.
  * A handle that never calls any of these allocates and launches nothing for them; the calls above are unchanged by them.
  * NOT DONE: this is NOT the minimum-sum assignment — a greedy matching can be beaten in total d2 (the minimum-cost association below is
- *      that assignment) — and NOT joint compatibility; the Slam mirror and the shell keep the Euclidean lowest-index rule; no cross-covariance; no signed localizer type test; frames of
+ *      that assignment) — and NOT joint compatibility (a test of its own, further below); the Slam mirror and the shell keep the Euclidean lowest-index rule; no cross-covariance; no signed localizer type test; frames of
  *      more than GS_NN_FRAME_MAX observations; sharded handles: nothing beyond what the gs_associate_nn_* calls give. */
 #define GS_NN_FRAME_MAX 256
 int  gs_assign_nn_batch(gs_graph *g, int32_t n, const double *poses_xytheta, int32_t n_poses, const int32_t *pose_of_obs, const double *obs_4xn,
@@ -788,7 +788,7 @@ int  gs_frame_frontend_assign(gs_graph *g, const double pose_xytheta[3], const d
  *      reads and writes nothing; a frame longer than GS_NN_FRAME_MAX writes -1, +inf and 0 for all its observations; observations that no
  *      frame covers are not written, in any of the three outputs.
  * A handle that never calls any of these allocates and launches nothing for them; the calls above are unchanged by them.
- * NOT DONE: joint compatibility; no cross-covariance; the Slam mirror and the shell keep the Euclidean lowest-index rule; frames of more than
+ * NOT DONE: joint compatibility is a test of its own (below), not part of these calls; no cross-covariance; the Slam mirror and the shell keep the Euclidean lowest-index rule; frames of more than
  *      GS_NN_FRAME_MAX observations; more than GS_ASSIGN_CAND_MAX candidates per observation; no signed localizer type test; sharded
  *      handles: nothing beyond what the gs_associate_nn_* calls give. */
 #define GS_ASSIGN_CAND_MAX 8
@@ -802,6 +802,92 @@ int  gs_assign_opt_resident(gs_graph *g, int32_t n, const double *dev_poses_xyth
 int  gs_frame_frontend_assign_opt(gs_graph *g, const double pose_xytheta[3], const double *pose_cov_3x3, const double *obs_4xk, int32_t k,
                                   const gs_nn_params *params, double *out_zxy, double *out_gxy, int32_t *out_index, double *out_d2,
                                   int32_t *out_n_admissible);
+
+/* ---- joint compatibility: a frame's matches gated as one hypothesis ------------------------------------------------
+ * The calls above gate every pair (i, j) alone: P = G Sigma_p G^T enters each pair's S as if the pose error were drawn afresh for every
+ * observation.  All observations of a frame share ONE pose error.  A frame whose residuals all point the same way (a pose error explains
+ * it) and one whose residuals contradict each other (nothing does) pass the same per-pair gates when Sigma_p is generous; only the joint
+ * test tells them apart, and it yields the pose correction the matches imply.  The reference has no noise model: the rule is build-defined.
+ *
+ * Frames are those of gs_assign_*: frame_start, at most GS_NN_FRAME_MAX observations each.  A frame carries a HYPOTHESIS index[i] — a cone
+ *      or -1 per observation, as any of gs_associate_nn_*, gs_assign_nn_* or gs_assign_opt_* returns it.  All observations of a frame share
+ *      one pose index p; Sigma_p = that pose's 3x3 covariance (row-major, the upper triangle read), zero when pose_cov is NULL.
+ * Pair.  Observation i with j = index[i] != -1:  z, w = R(theta) z, g, wp = (-w_y, w_x) and Q are exactly those of the covariance-gated
+ *      association — the same device function, called WITHOUT a pose covariance, so that its Q + P is Q alone.
+ *      D = Sigma_j + Q,  nu = l_j - g,  det = D00 D11 - D01^2,
+ *      a_i = (((D11 nu0) nu0 - ((2 D01) nu0) nu1) + (D00 nu1) nu1) / det          the operations of the covariance-gated d2: with pose_cov == NULL
+ *                                                                                  a_i is bitwise the d2 gs_associate_nn_* returns for (i, j)
+ *      y = D^-1 nu:  y0 = (D11 nu0 - D01 nu1) / det,  y1 = (D00 nu1 - D01 nu0) / det
+ *      c_i = (y0, y1, wp_x y0 + wp_y y1)
+ *      E = D^-1:  E00 = D11 / det,  E01 = -(D01 / det),  E11 = D00 / det;   h = E wp:  h0 = E00 wp_x + E01 wp_y,  h1 = E01 wp_x + E11 wp_y
+ *      M_i = G^T D^-1 G, G = [I2 | wp], symmetric 3x3, six entries:  (E00, E01, h0, E11, h1, wp_x h0 + wp_y h1) = (M00, M01, M02, M11, M12, M22)
+ *      The pair enters the set K iff ALL of  the query is valid (as above: g finite, r > 0, pose index in range),  0 <= j < n_map,  det > 0,
+ *      D00 > 0  hold (positive tests: any NaN excludes).  Otherwise the observation gets -1 and counts in n_untestable.  No type, distance or
+ *      gate test is repeated: the hypothesis is the caller's.  An observation with index[i] == -1 has no pair: it gets -1 and counts nowhere.
+ * Sums.  a, c, M over K in a FIXED order: with r = the observation's position in its frame, lane r mod 64 adds its pairs in ascending r
+ *      starting from +0; then the 64 lane values are added pairwise at distance 32, 16, 8, 4, 2, 1 (lane l takes l + (l xor d)); a lane
+ *      without a pair holds +0.  The sums of a round are formed from the kept pairs afresh, never carried over from the round before.
+ * Joint distance.  A = I + M Sigma_p, every entry as ((M_r0 P_0s + M_r1 P_1s) + M_r2 P_2s), 1 added last on the diagonal;  C = the cofactors
+ *      of A, each a difference of two products (C00 = A11 A22 - A12 A21, C01 = A12 A20 - A10 A22, C02 = A10 A21 - A11 A20, C10 = A02 A21 -
+ *      A01 A22, C11 = A00 A22 - A02 A20, C12 = A01 A20 - A00 A21, C20 = A01 A12 - A02 A11, C21 = A02 A10 - A00 A12, C22 = A00 A11 - A01 A10);
+ *      detA = (A00 C00 + A01 C01) + A02 C02  (>= 1 in exact arithmetic);  x_s = ((C0s c0 + C1s c1) + C2s c2) / detA;
+ *      delta_r = (P_r0 x0 + P_r1 x1) + P_r2 x2;   J(K) = a - ((c0 delta0 + c1 delta1) + c2 delta2).
+ *      In exact arithmetic delta = Sigma_p (I + M Sigma_p)^-1 c and J = nu^T (blockdiag(D) + G Sigma_p G^T)^-1 nu over the stacked pairs.
+ *      delta is the correction of (x, y, theta) the kept matches imply, added to the pose as gs_iterate adds its update; the caller may apply
+ *      it.  pose_cov == NULL: no solve, delta = 0 and J = a.  No contraction anywhere.
+ * Gate.  gs_jc_params.gate[m], m = 0 .. GS_NN_FRAME_MAX: the `confidence` quantile of chi-square with 2 m degrees of freedom, gate[0] = 0,
+ *      filled on the host by gs_jc_params_default (0.95) and gs_jc_params_set_confidence (bisection on 1 - e^(-x/2) sum_{k<m} (x/2)^k / k!;
+ *      a confidence outside (0, 1): GS_ERR_INVALID).  The device reads the table as given — the rule is defined relative to the table's bits,
+ *      a caller may edit it.  A table that is not finite, has a negative entry or decreases somewhere, or a wrong struct_size: GS_ERR_INVALID.
+ * Pruning (backward elimination).  While K is not empty and NOT J(K) < gate[|K|]: remove the pair r of smallest J(K \ {r}), exact ties to the
+ *      lowest observation; repeat.  J(K \ {r}) is formed from (the round's sums - the pair's own terms), entry by entry, by the same solve.
+ * Outputs.  Per observation out_index: the cone while its pair is kept, else -1.  Per frame (each pointer may be NULL): joint_d2 = J of the
+ *      kept set (0 when it is empty);  n_kept;  n_dropped = pairs removed by pruning;  n_untestable;  delta[3] (of the kept set).
+ *      n_kept + n_dropped + n_untestable = the frame's observations with index != -1.
+ * Consequences.  With pose_cov == NULL, J is the fixed-order sum of the pairs' own d2.  A frame with J < gate[m] at once keeps its hypothesis
+ *      unchanged, index for index, after ONE round.  Frames are independent.  A cone named twice in a hypothesis is not checked: its two
+ *      pairs are treated as independent.  Batch, resident and frame call return identical bits.
+ *
+ * gs_joint_compat_batch: the host layouts of gs_assign_opt_batch without map_type, plus in_index and the table.  Of gs_nn_params only
+ *      struct_size and the three sigmas are read (the other fields may hold anything).  GS_ERR_INVALID before the device is touched:
+ *      everything gs_assign_nn_batch refuses about frames and pointers, an in_index entry outside [-1, n_map), a frame whose observations
+ *      do not share one pose index, a sigma that is negative or not finite, a bad table.
+ * gs_joint_compat_resident: everything in DEVICE memory against the resident map and its covariances, asynchronous on the handle's stream,
+ *      no wait.  dev_obs must be 32-byte aligned.  The kernel defends itself as the resident assign kernels do: a frame whose bounds are
+ *      not 0 <= a <= b <= n reads and writes nothing; a frame longer than GS_NN_FRAME_MAX writes -1 per observation, joint_d2 = +inf, counts
+ *      and delta 0; a frame whose observations name two different pose indices inside [0, n_poses) does the same; an index[i] outside
+ *      [-1, map size) makes that pair untestable; observations that no frame covers are not written.
+ * gs_frame_frontend_jc: one frame against the resident map — the minimum-cost assignment of gs_frame_frontend_assign_opt (all of
+ *      gs_nn_params read and checked as there), then the joint test of its result, enqueued back to back on the handle's stream, one wait.
+ *      out_zxy / out_gxy: the bits gs_frame_frontend_nn returns; out_index: the PRUNED index; out_d2 / out_n_admissible (may be NULL): the
+ *      assignment's, for every pair it made, pruned or not; then the frame's record.  It shares the assignment call's staging and keeps a
+ *      fixed record buffer of its own from the first call on: nothing is allocated per call after that.
+ * A handle that never calls any of these allocates and launches nothing for them; the calls above are unchanged by them.
+ * NOT DONE: pose-cone and cone-cone cross-covariances; JCBB's search over alternative cones — this PRUNES a given hypothesis, it does not
+ *      re-match; the posterior pose covariance; frames of more than GS_NN_FRAME_MAX observations; sharded handles (nothing beyond what the
+ *      gs_associate_nn_* calls give); the Slam mirror and the shell, which keep the Euclidean rule. */
+typedef struct gs_jc_params {
+    int32_t struct_size;
+    int32_t reserved;
+    double confidence;                      /* 0.95 */
+    double gate[GS_NN_FRAME_MAX + 1];       /* gate[m]: the quantile at 2 m degrees of freedom; gate[0] = 0 */
+} gs_jc_params;
+int  gs_jc_params_default(gs_jc_params *p);
+int  gs_jc_params_set_confidence(gs_jc_params *p, double confidence);
+int  gs_joint_compat_batch(gs_graph *g, int32_t n, const double *poses_xytheta, int32_t n_poses, const int32_t *pose_of_obs, const double *obs_4xn,
+                           int32_t n_frames, const int32_t *frame_start, int32_t n_map, const double *map_xy, const double *map_cov_2x2,
+                           const double *pose_cov_3x3, const gs_nn_params *params, const gs_jc_params *jc, const int32_t *in_index,
+                           int32_t *out_index, double *out_joint_d2, int32_t *out_n_kept, int32_t *out_n_dropped, int32_t *out_n_untestable,
+                           double *out_delta_3);
+int  gs_joint_compat_resident(gs_graph *g, int32_t n, const double *dev_poses_xytheta, int32_t n_poses, const int32_t *dev_pose_of_obs,
+                              const double *dev_obs_4xn, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov_3x3,
+                              const gs_nn_params *params, const gs_jc_params *jc, const int32_t *dev_in_index, int32_t *dev_out_index,
+                              double *dev_out_joint_d2, int32_t *dev_out_n_kept, int32_t *dev_out_n_dropped, int32_t *dev_out_n_untestable,
+                              double *dev_out_delta_3);
+int  gs_frame_frontend_jc(gs_graph *g, const double pose_xytheta[3], const double *pose_cov_3x3, const double *obs_4xk, int32_t k,
+                          const gs_nn_params *params, const gs_jc_params *jc, double *out_zxy, double *out_gxy, int32_t *out_index, double *out_d2,
+                          int32_t *out_n_admissible, double *out_joint_d2, int32_t *out_n_kept, int32_t *out_n_dropped, int32_t *out_n_untestable,
+                          double *out_delta_3);
 
 /* ---- multi-GPU: pose-window shards -----------------------------
  * Each rank owns a contiguous pose window and builds the SAME global plan; it linearises and

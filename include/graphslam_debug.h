@@ -105,6 +105,12 @@ int gs_debug_time_assign_opt_resident(gs_graph *g, int32_t n, const double *dev_
                                       const double *dev_obs_4xn, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov_3x3,
                                       const gs_nn_params *params, int32_t *dev_out_index, double *dev_out_d2, int32_t *dev_out_n_admissible,
                                       int32_t reps, double *out_ms);
+/* And for the joint compatibility test: `reps` launches of gs_joint_compat_resident, events from its first dispatch to its last. */
+int gs_debug_time_joint_compat_resident(gs_graph *g, int32_t n, const double *dev_poses_xytheta, int32_t n_poses, const int32_t *dev_pose_of_obs,
+                                        const double *dev_obs_4xn, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov_3x3,
+                                        const gs_nn_params *params, const gs_jc_params *jc, const int32_t *dev_in_index, int32_t *dev_out_index,
+                                        double *dev_out_joint_d2, int32_t *dev_out_n_kept, int32_t *dev_out_n_dropped, int32_t *dev_out_n_untestable,
+                                        double *dev_out_delta_3, int32_t reps, double *out_ms);
 /* Measurement hook of the sharded iteration (bench.py's `ms_exchange`): `reps` RCCL all-reduces of the exchange buffer back to back on the
  * handle's stream, HIP events around them; mean ms per all-reduce.  Collective: every rank of the communicator calls it. */
 int gs_debug_time_exchange(gs_graph *g, int32_t reps, double *out_ms);

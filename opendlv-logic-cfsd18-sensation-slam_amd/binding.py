@@ -136,6 +136,28 @@ def nn_params(**kw):
     return p
 
 
+NN_FRAME_MAX = 256                                          # GS_NN_FRAME_MAX
+
+
+class JcParams(C.Structure):
+    """gs_jc_params (include/graphslam.h): the joint compatibility test's gate per number of kept pairs"""
+    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("confidence", C.c_double), ("gate", C.c_double * (NN_FRAME_MAX + 1))]
+
+
+def jc_params(confidence=None):
+    """the library's gs_jc_params: the defaults (0.95), or the table of the given confidence"""
+    p = JcParams(); L = lib()
+    rc = L.gs_jc_params_default(C.byref(p)) if confidence is None else L.gs_jc_params_set_confidence(C.byref(p), float(confidence))
+    if rc != GS_OK:
+        raise GsError(rc, (L.gs_last_error() or b"").decode())
+    return p
+
+
+def _jc_record(n_frames):
+    return {"joint_d2": np.zeros(n_frames), "n_kept": np.zeros(n_frames, dtype=np.int32), "n_dropped": np.zeros(n_frames, dtype=np.int32),
+            "n_untestable": np.zeros(n_frames, dtype=np.int32), "delta": np.zeros((n_frames, 3))}
+
+
 class DoglegParams(C.Structure):
     """gs_dogleg_params (include/graphslam.h)"""
     _fields_ = [("struct_size", C.c_int32), ("max_trials_after_failure", C.c_int32), ("initial_delta", C.c_double)]
@@ -313,6 +335,14 @@ def lib():
         L.gs_assign_opt_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, vp, vp, vp]
         L.gs_debug_time_assign_opt_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, vp, vp, vp, C.c_int32, _dp]
         L.gs_frame_frontend_assign_opt.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, _dp, _dp, _ip, _dp, _ip]
+    if hasattr(L, "gs_joint_compat_batch"):                # (and for the joint compatibility test)
+        npp = C.POINTER(NnParams); jpp = C.POINTER(JcParams)
+        L.gs_jc_params_default.argtypes = [jpp]
+        L.gs_jc_params_set_confidence.argtypes = [jpp, C.c_double]
+        L.gs_joint_compat_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32, _ip, C.c_int32, _dp, _dp, _dp, npp, jpp, _ip, _ip, _dp, _ip, _ip, _ip, _dp]
+        L.gs_joint_compat_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, jpp, vp, vp, vp, vp, vp, vp, vp]
+        L.gs_debug_time_joint_compat_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, jpp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, _dp]
+        L.gs_frame_frontend_jc.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, jpp, _dp, _dp, _ip, _dp, _ip, _dp, _ip, _ip, _ip, _dp]
     if hasattr(L, "gs_set_robust_kernel"):                # (a tuning build of an older tree loaded through GS_LIB may predate the robust kernels)
         L.gs_set_robust_kernel.argtypes = [vp, C.c_int32, C.c_int32, C.c_double]
         L.gs_get_robust_kernel.argtypes = [vp, C.c_int32, _ip, _dp]
@@ -1044,6 +1074,50 @@ class Graph:
         z = np.zeros((k, 2)); gx = np.zeros((k, 2)); idx = np.zeros(k, dtype=np.int32); d2 = np.zeros(k); na = np.zeros(k, dtype=np.int32)
         self._check(self.L.gs_frame_frontend_assign_opt(self.h, _d(pose), None if pc is None else _d(pc), _d(obs), k, C.byref(p), _d(z), _d(gx), _i(idx), _d(d2), _i(na)))
         return z, gx, idx, d2, na
+
+    # ---- joint compatibility (include/graphslam.h): a frame's hypothesis (cone or -1 per observation) gated as a whole and pruned.
+    # A frame's record is a dict: joint_d2 [f], n_kept / n_dropped / n_untestable [f] int32, delta [f,3]
+    def joint_compat(self, poses, pose_of_obs, obs, frame_start, map_xy, in_index, map_cov=None, pose_cov=None, params=None, jc=None):
+        """gs_joint_compat_batch: (index [n] int32, record)"""
+        poses = _f64(poses, (-1, 3)); obs = _f64(obs, (-1, 4)); po = _i32(pose_of_obs); fs = _i32(frame_start); ii = _i32(in_index)
+        map_xy = _f64(map_xy, (-1, 2)); n = len(obs); nf = len(fs) - 1
+        mc = None if map_cov is None else _f64(map_cov, (-1, 4)); pc = None if pose_cov is None else _f64(pose_cov, (-1, 9))
+        assert mc is None or len(mc) == len(map_xy); assert pc is None or len(pc) == len(poses); assert len(fs) >= 1 and len(ii) == n
+        p = nn_params() if params is None else params; j = jc_params() if jc is None else jc
+        idx = np.zeros(n, dtype=np.int32); rec = _jc_record(nf)
+        self._check(self.L.gs_joint_compat_batch(self.h, n, _d(poses), len(poses), _i(po), _d(obs), nf, _i(fs), len(map_xy), _d(map_xy),
+                                                 None if mc is None else _d(mc), None if pc is None else _d(pc), C.byref(p), C.byref(j), _i(ii), _i(idx),
+                                                 _d(rec["joint_d2"]), _i(rec["n_kept"]), _i(rec["n_dropped"]), _i(rec["n_untestable"]), _d(rec["delta"])))
+        return idx, rec
+
+    def joint_compat_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_in_index, d_out, d_joint_d2=None, d_n_kept=None,
+                              d_n_dropped=None, d_n_untestable=None, d_delta=None, d_pose_cov=None, params=None, jc=None):
+        """gs_joint_compat_resident: the resident map and its covariances, everything else DeviceArray; asynchronous (synchronize() before reading)"""
+        p = nn_params() if params is None else params; j = jc_params() if jc is None else jc
+        opt = lambda a: None if a is None else a.ptr
+        self._check(self.L.gs_joint_compat_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, int(n_frames), d_frame_start.ptr,
+                                                    opt(d_pose_cov), C.byref(p), C.byref(j), d_in_index.ptr, d_out.ptr, opt(d_joint_d2), opt(d_n_kept),
+                                                    opt(d_n_dropped), opt(d_n_untestable), opt(d_delta)))
+
+    def time_joint_compat_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_in_index, d_out, reps, d_joint_d2=None,
+                                   d_n_kept=None, d_n_dropped=None, d_n_untestable=None, d_delta=None, d_pose_cov=None, params=None, jc=None):
+        p = nn_params() if params is None else params; j = jc_params() if jc is None else jc
+        opt = lambda a: None if a is None else a.ptr
+        ms = C.c_double()
+        self._check(self.L.gs_debug_time_joint_compat_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, int(n_frames), d_frame_start.ptr,
+                                                               opt(d_pose_cov), C.byref(p), C.byref(j), d_in_index.ptr, d_out.ptr, opt(d_joint_d2), opt(d_n_kept),
+                                                               opt(d_n_dropped), opt(d_n_untestable), opt(d_delta), int(reps), C.byref(ms)))
+        return ms.value
+
+    def frame_frontend_jc(self, pose, obs, pose_cov=None, params=None, jc=None):
+        """(zxy [k,2], gxy [k,2], pruned idx [k], the assignment's d2 [k] and n_admissible [k], record of the one frame) — gs_frame_frontend_assign_opt
+        followed by the joint test of its result"""
+        pose = _f64(pose); obs = _f64(obs, (-1, 4)); k = len(obs); pc = None if pose_cov is None else _f64(pose_cov, (9,))
+        p = nn_params() if params is None else params; j = jc_params() if jc is None else jc
+        z = np.zeros((k, 2)); gx = np.zeros((k, 2)); idx = np.zeros(k, dtype=np.int32); d2 = np.zeros(k); na = np.zeros(k, dtype=np.int32); rec = _jc_record(1)
+        self._check(self.L.gs_frame_frontend_jc(self.h, _d(pose), None if pc is None else _d(pc), _d(obs), k, C.byref(p), C.byref(j), _d(z), _d(gx), _i(idx), _d(d2), _i(na),
+                                                _d(rec["joint_d2"]), _i(rec["n_kept"]), _i(rec["n_dropped"]), _i(rec["n_untestable"]), _d(rec["delta"])))
+        return z, gx, idx, d2, na, rec
 
     # ---- pose-window shards (one handle per rank / GPU)
     def dist_configure(self, rank, world):

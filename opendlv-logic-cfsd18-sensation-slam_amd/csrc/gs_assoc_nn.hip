@@ -6,6 +6,8 @@
 //   k_frame_nn        one frame in one launch: a workgroup per observation, its 256 threads stride over the map
 //   k_map_cov_gather  map covariances out of the gathered marginals (gs_map_set_cov_from_marginals)
 //   k_assign_nn       the one-to-one association inside frames (gs_assign_nn_*, gs_frame_frontend_assign): further down, with its own text
+//   k_assign_opt      the minimum-cost association inside frames (gs_assign_opt_*): likewise
+//   k_joint_compat    the joint test of a frame's hypothesis (gs_joint_compat_*, gs_frame_frontend_jc): likewise
 //
 // The three association kernels return IDENTICAL bits: the query's side (z, g, Q + P) is nn_query, one candidate's side (S, det, d2 and
 // the five tests) is nn_pair, both without contraction, the A0 conversion is ONE out-of-line function (polar_to_xy compiled once, not
@@ -544,6 +546,190 @@ __global__ void __launch_bounds__(64) k_assign_opt_big(AoArgs A) {
     }
 }
 
+// ---- joint compatibility of a frame's hypothesis (include/graphslam.h, "joint compatibility"): the pairs (i, in_idx[i]) of a frame share ONE
+// pose error, so their joint innovation covariance is blockdiag(D_i) + G Sigma_p G^T and Woodbury turns nu^T S^-1 nu into sums of per-pair
+// terms and one 3x3 solve:  J = a - c^T delta,  delta = Sigma_p (I + M Sigma_p)^-1 c.  No map search: l_j and Sigma_j are gathered through
+// in_idx, so the batch, the resident and the frame call run the one function below.
+//   PAIRS   a row's ten terms (a, c[3], M[6]) once, into LDS term-major ([t][row]: no bank conflicts); only the lane that wrote a row reads it
+//   ROUND   the sums over the kept rows in a FIXED order — a lane's rows ascending from +0, then the wave's 64 lanes by butterfly at distance
+//           32, 16 .. 1 (fp64 addition commutes, so every lane holds the same bits; a lane without a kept row adds +0, which changes nothing:
+//           the bits do not depend on how many lanes W the frame was given) — and the 3x3 solve, on every lane.  J < gate[kept]: finished.
+//           Otherwise every kept row solves for (sums - its own terms) and the row of smallest (J, row) leaves.  The sums are recomputed from
+//           the kept rows in every round, never carried: a round's error does not depend on the rounds before it.
+// Lanes as k_assign_opt: W lanes per frame, 64 / W frames side by side; at most rows + 1 rounds; no barrier, no scratch, no wait.
+static constexpr int JC_TERMS = 10;                                            // a, c0 c1 c2, m00 m01 m02 m11 m12 m22
+template <int SLOTS> struct JcLds { double t[JC_TERMS][64 * SLOTS]; int32_t kj[64 * SLOTS]; };       // kj: the row's cone while it is kept, else -1
+struct JcArgs {
+    int n; const double *poses; int n_poses; const int32_t *pose_of_obs; const double *obs; int n_frames; const int32_t *frame_start; int fpw, only_large;
+    double lidar; int n_map; const double *map_xy, *map_cov, *pose_cov; NnDev p; const int32_t *in_idx;
+    int32_t *out_idx; double *out_j; int32_t *out_kept, *out_dropped, *out_untestable; double *out_delta; JcGate gate;
+};
+// J and delta of the sums S; P = Sigma_p's upper triangle (p00 p01 p02 p11 p12 p22), has_p false: Sigma_p = 0, delta = 0 and J = a
+__device__ __forceinline__ double jc_solve(const double (&S)[JC_TERMS], const double (&P)[6], bool has_p, double (&dl)[3]) {
+#pragma clang fp contract(off)
+    dl[0] = dl[1] = dl[2] = 0.0;
+    if (!has_p) return S[0];
+    const double c0 = S[1], c1 = S[2], c2 = S[3], m00 = S[4], m01 = S[5], m02 = S[6], m11 = S[7], m12 = S[8], m22 = S[9];
+    const double p00 = P[0], p01 = P[1], p02 = P[2], p11 = P[3], p12 = P[4], p22 = P[5];
+    // A = I + M Sigma_p
+    const double a00 = 1.0 + ((m00 * p00 + m01 * p01) + m02 * p02), a01 = (m00 * p01 + m01 * p11) + m02 * p12, a02 = (m00 * p02 + m01 * p12) + m02 * p22;
+    const double a10 = (m01 * p00 + m11 * p01) + m12 * p02, a11 = 1.0 + ((m01 * p01 + m11 * p11) + m12 * p12), a12 = (m01 * p02 + m11 * p12) + m12 * p22;
+    const double a20 = (m02 * p00 + m12 * p01) + m22 * p02, a21 = (m02 * p01 + m12 * p11) + m22 * p12, a22 = 1.0 + ((m02 * p02 + m12 * p12) + m22 * p22);
+    // cofactors C[r][s] of A; x = adj(A) c / det = C^T c / det
+    const double k00 = a11 * a22 - a12 * a21, k01 = a12 * a20 - a10 * a22, k02 = a10 * a21 - a11 * a20;
+    const double k10 = a02 * a21 - a01 * a22, k11 = a00 * a22 - a02 * a20, k12 = a01 * a20 - a00 * a21;
+    const double k20 = a01 * a12 - a02 * a11, k21 = a02 * a10 - a00 * a12, k22 = a00 * a11 - a01 * a10;
+    const double det = (a00 * k00 + a01 * k01) + a02 * k02;
+    const double x0 = ((k00 * c0 + k10 * c1) + k20 * c2) / det, x1 = ((k01 * c0 + k11 * c1) + k21 * c2) / det, x2 = ((k02 * c0 + k12 * c1) + k22 * c2) / det;
+    dl[0] = (p00 * x0 + p01 * x1) + p02 * x2; dl[1] = (p01 * x0 + p11 * x1) + p12 * x2; dl[2] = (p02 * x0 + p12 * x1) + p22 * x2;
+    return S[0] - ((c0 * dl[0] + c1 * dl[1]) + c2 * dl[2]);
+}
+// one pass of a wave: lane group gi (W lanes, lane lg of it) tests the frame fw = [a, b) (fw < 0: none), b - a <= W (W < 64) or <= 64 * SLOTS.
+// Row rl of the frame sits at LDS row (rl / 64) * 64 + lane: lane == eb + lg with W < 64, lane == rl % 64 with W == 64.
+template <int SLOTS>
+__device__ __forceinline__ void jc_pass(JcLds<SLOTS> &L, const JcArgs &A, int fw, int a, int b, int W, int lg, int lane) {
+#pragma clang fp contract(off)
+    const int k = fw < 0 ? 0 : b - a, slots = (k + 63) >> 6;
+    // the frame's pose: the one index inside [0, n_poses) its observations name; two different ones: the frame is refused as a whole
+    int plo = NN_NONE, phi = -1;
+    for (int s = 0; s < slots; ++s) { const int rl = s * 64 + lg;
+        if (rl < k) { const int pi = A.pose_of_obs[a + rl]; if (pi >= 0 && pi < A.n_poses) { plo = min(plo, pi); phi = max(phi, pi); } } }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        if (off >= W) continue;                                                // (wave-uniform) the butterfly stays inside the frame's W lanes
+        plo = min(plo, __shfl_xor(plo, off, 64)); phi = max(phi, __shfl_xor(phi, off, 64));
+    }
+    const bool mixed = phi >= 0 && plo != phi;
+    const bool has_p = A.pose_cov != nullptr && phi >= 0 && !mixed;
+    double P[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (has_p) { const double *pc = A.pose_cov + 9 * (size_t)plo; P[0] = pc[0]; P[1] = pc[1]; P[2] = pc[2]; P[3] = pc[4]; P[4] = pc[5]; P[5] = pc[8]; }
+    // PAIRS
+    int nun = 0;                                                               // this lane's untestable rows
+    for (int s = 0; s < slots; ++s) {
+        const int rl = s * 64 + lg, e = s * 64 + lane; int keep = -1;
+        if (rl < k && !mixed) {
+            const int i = a + rl, j = A.in_idx[i];
+            if (j != -1) {
+                const NnQuery q = nn_query_of(i, A.n, A.poses, A.n_poses, A.pose_of_obs, A.obs, nullptr, A.lidar, A.p);      // a = Q alone
+                bool ok = q.valid && j >= 0 && j < A.n_map;
+                if (ok) {
+                    const double2 xy = reinterpret_cast<const double2 *>(A.map_xy)[j];
+                    double c00 = 0.0, c01 = 0.0, c11 = 0.0;
+                    if (A.map_cov) { const double4 cv = reinterpret_cast<const double4 *>(A.map_cov)[j]; c00 = cv.x; c01 = cv.y; c11 = cv.w; }
+                    const double n0 = xy.x - q.gx, n1 = xy.y - q.gy;
+                    const double d00 = c00 + q.a00, d01 = c01 + q.a01, d11 = c11 + q.a11;
+                    const double det = d00 * d11 - d01 * d01;
+                    ok = det > 0.0 && d00 > 0.0;
+                    if (ok) {
+                        double sn, cs; sincos(A.poses[3 * (size_t)plo + 2], &sn, &cs);
+                        const double ux = -(q.zx * sn + q.zy * cs), uy = q.zx * cs - q.zy * sn;      // wp = (-w_y, w_x), w as nn_query forms it
+                        const double y0 = (d11 * n0 - d01 * n1) / det, y1 = (d00 * n1 - d01 * n0) / det;
+                        const double e00 = d11 / det, e01 = -(d01 / det), e11 = d00 / det;           // D^-1
+                        const double h0 = e00 * ux + e01 * uy, h1 = e01 * ux + e11 * uy;             // D^-1 wp
+                        L.t[0][e] = (((d11 * n0) * n0 - ((2.0 * d01) * n0) * n1) + (d00 * n1) * n1) / det;      // nn_pair's d2
+                        L.t[1][e] = y0; L.t[2][e] = y1; L.t[3][e] = ux * y0 + uy * y1;
+                        L.t[4][e] = e00; L.t[5][e] = e01; L.t[6][e] = h0; L.t[7][e] = e11; L.t[8][e] = h1; L.t[9][e] = ux * h0 + uy * h1;
+                        keep = j;
+                    }
+                }
+                if (!ok) ++nun;
+            }
+        }
+        L.kj[e] = keep;
+    }
+    // ROUNDS
+    double J = 0.0, dl[3] = {0.0, 0.0, 0.0}; int kept = 0, dropped = 0; bool open = fw >= 0 && !mixed;
+    for (int round = 0; round <= 64 * SLOTS; ++round) {                        // a round that does not finish the frame removes a row: rows + 1 at the most
+        double S[JC_TERMS]; int cnt = 0;
+#pragma unroll
+        for (int t = 0; t < JC_TERMS; ++t) S[t] = 0.0;
+        for (int s = 0; s < slots; ++s) { const int e = s * 64 + lane;
+            if (L.kj[e] >= 0) { ++cnt;
+#pragma unroll
+                for (int t = 0; t < JC_TERMS; ++t) S[t] += L.t[t][e]; } }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            if (off >= W) continue;
+            cnt += __shfl_xor(cnt, off, 64);
+#pragma unroll
+            for (int t = 0; t < JC_TERMS; ++t) S[t] += __shfl_xor(S[t], off, 64);
+        }
+        if (open) { J = jc_solve(S, P, has_p, dl); kept = cnt; open = !(cnt == 0 || J < A.gate.g[cnt]); }
+        if (__ballot(open) == 0) break;                                        // wave-uniform: every frame of the pass is finished
+        // the row whose removal leaves the smallest J, by (J, row): a lane's rows ascend, so < keeps the first
+        double mk = __builtin_inf(); int mr = NN_NONE;
+        if (open)
+            for (int s = 0; s < slots; ++s) { const int e = s * 64 + lane;
+                if (L.kj[e] < 0) continue;
+                double R[JC_TERMS], du[3];
+#pragma unroll
+                for (int t = 0; t < JC_TERMS; ++t) R[t] = S[t] - L.t[t][e];
+                const double jr = jc_solve(R, P, has_p, du);
+                if (mr == NN_NONE || jr < mk) { mk = jr; mr = s * 64 + lg; } }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            if (off >= W) continue;
+            const double od = __shfl_xor(mk, off, 64); const int orw = __shfl_xor(mr, off, 64);
+            if (orw != NN_NONE && (mr == NN_NONE || od < mk || (od == mk && orw < mr))) { mk = od; mr = orw; }
+        }
+        if (open && mr != NN_NONE) { ++dropped; if ((mr & 63) == lg) L.kj[(mr & ~63) + lane] = -1; }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { if (off >= W) continue; nun += __shfl_xor(nun, off, 64); }
+    if (fw < 0) return;
+    if (mixed) { J = __builtin_inf(); kept = dropped = 0; }
+    for (int s = 0; s < slots; ++s) { const int rl = s * 64 + lg; if (rl < k) A.out_idx[a + rl] = L.kj[s * 64 + lane]; }
+    if (lg == 0) {
+        if (A.out_j) A.out_j[fw] = J;
+        if (A.out_kept) A.out_kept[fw] = kept;
+        if (A.out_dropped) A.out_dropped[fw] = dropped;
+        if (A.out_untestable) A.out_untestable[fw] = mixed ? 0 : nun;
+        if (A.out_delta) { A.out_delta[3 * (size_t)fw] = dl[0]; A.out_delta[3 * (size_t)fw + 1] = dl[1]; A.out_delta[3 * (size_t)fw + 2] = dl[2]; }
+    }
+}
+// frame f of the call: its bounds, and whether it is one (bounds outside 0 <= a <= b <= n: not a frame, nothing read or written).  Above
+// GS_NN_FRAME_MAX (when `refuse`): -1 per observation, +inf, counts and delta 0, and not a frame for the pass
+__device__ __forceinline__ bool jc_frame(const JcArgs &A, int f, bool refuse, int lg, int W, int &a, int &b) {
+    a = A.frame_start[f]; b = A.frame_start[f + 1];
+    if (a < 0 || b < a || b > A.n) return false;
+    if (b - a <= 256) return true;
+    if (refuse) {
+        for (int i = a + lg; i < b; i += W) A.out_idx[i] = -1;
+        if (lg == 0) {
+            if (A.out_j) A.out_j[f] = __builtin_inf();
+            if (A.out_kept) A.out_kept[f] = 0;
+            if (A.out_dropped) A.out_dropped[f] = 0;
+            if (A.out_untestable) A.out_untestable[f] = 0;
+            if (A.out_delta) { A.out_delta[3 * (size_t)f] = 0.0; A.out_delta[3 * (size_t)f + 1] = 0.0; A.out_delta[3 * (size_t)f + 2] = 0.0; }
+        }
+    }
+    return false;
+}
+__global__ void __launch_bounds__(256) k_joint_compat(JcArgs A) {
+    __shared__ JcLds<1> Ls[4];                                                 // 5.25 KB a wave
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int f0 = (blockIdx.x * 4 + w) * A.fpw;                               // this wave's frames: [f0, f0 + fpw), fpw in {2, 4, 8}
+    if (f0 >= A.n_frames) return;
+    int W = 64 / A.fpw;                                                        // as k_assign_opt; frames above 64 are k_joint_compat_big's
+    for (int t = 0; t < A.fpw && f0 + t < A.n_frames; ++t) { const int a = A.frame_start[f0 + t], b = A.frame_start[f0 + t + 1];
+        if (a >= 0 && b >= a && b <= A.n && b - a <= 64) while (W < 64 && W < b - a) W <<= 1; }
+    const int gp = 64 / W, gi = lane >> __builtin_ctz(W), lg = lane & (W - 1);
+    for (int ps = 0; ps * gp < A.fpw; ++ps) {
+        int a = 0, b = 0, fw = -1; const int f = f0 + ps * gp + gi;
+        if (ps * gp + gi < A.fpw && f < A.n_frames && jc_frame(A, f, false, lg, W, a, b) && b - a <= 64) fw = f;
+        jc_pass<1>(Ls[w], A, fw, a, b, W, lg, lane);
+    }
+}
+__global__ void __launch_bounds__(64) k_joint_compat_big(JcArgs A) {
+    __shared__ JcLds<4> L;                                                     // 21 KB
+    const int lane = threadIdx.x, f0 = blockIdx.x * A.fpw;
+    for (int t = 0; t < A.fpw && f0 + t < A.n_frames; ++t) {
+        int a, b;
+        if (!jc_frame(A, f0 + t, true, lane, 64, a, b) || (A.only_large && b - a <= 64)) continue;      // (wave-uniform)
+        jc_pass<4>(L, A, f0 + t, a, b, 64, lane, lane);
+    }
+}
+
 void launch_assoc_nn(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, double lidar, int n_map,
                      const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
                      int32_t *out_idx, double *out_d2, double *out_second, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
@@ -604,6 +790,22 @@ void launch_assign_opt(int n, const double *poses, int n_poses, const int32_t *p
     const dim3 grid((n_frames + A.fpw - 1) / A.fpw), block(64);
     if (cell_start) hipExtLaunchKernelGGL(k_assign_opt_big<true>, grid, block, 0, st, start, stop, 0, A);
     else hipExtLaunchKernelGGL(k_assign_opt_big<false>, grid, block, 0, st, start, stop, 0, A);
+}
+void launch_joint_compat(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, int n_frames, const int32_t *frame_start,
+                         double lidar, int n_map, const double *map_xy, const double *map_cov, const double *pose_cov, NnDev p, const JcGate &gate,
+                         const int32_t *in_idx, int32_t *out_idx, double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable,
+                         double *out_delta, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
+    if (n_frames <= 0) return;
+    // the kernels by the MEAN frame size, exactly as launch_assign_opt: it decides speed only
+    const long long mean = ((long long)n + n_frames - 1) / n_frames;
+    JcArgs A{n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, 1, 0, lidar, n_map, map_xy, map_cov, pose_cov, p, in_idx,
+             out_idx, out_j, out_kept, out_dropped, out_untestable, out_delta, gate};
+    if (mean <= 32) {
+        A.fpw = mean <= 8 ? 8 : mean <= 16 ? 4 : 2;
+        hipExtLaunchKernelGGL(k_joint_compat, dim3((n_frames + 4 * A.fpw - 1) / (4 * A.fpw)), dim3(256), 0, st, start, nullptr, 0, A);
+        A.fpw = 64; A.only_large = 1; start = nullptr;
+    }
+    hipExtLaunchKernelGGL(k_joint_compat_big, dim3((n_frames + A.fpw - 1) / A.fpw), dim3(64), 0, st, start, stop, 0, A);
 }
 
 }  // namespace gs

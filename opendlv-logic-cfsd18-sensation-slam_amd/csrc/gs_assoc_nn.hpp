@@ -39,5 +39,14 @@ void launch_assign_opt(int n, const double *poses, int n_poses, const int32_t *p
                        double lidar, int n_map, const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
                        long long buckets, const int32_t *cell_start, const int32_t *cell_items, int32_t *out_idx, double *out_d2, int32_t *out_na,
                        double *out_z, double *out_g, hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// joint compatibility of the hypothesis in_idx (cone or -1 per observation) inside the same frames: out_idx per observation (the cone while
+// its pair is kept, else -1), and per frame J, the kept / dropped / untestable counts and delta[3] (each may be null).  gate: gs_jc_params'
+// table, passed by value (the call needs no device copy of it).  Only p's sigmas are read.  Defences as launch_assign_opt, and a frame whose
+// in-range pose indices differ is refused like one above GS_NN_FRAME_MAX: -1 per observation, J = +inf, counts and delta 0.
+struct JcGate { double g[257]; };                                             // GS_NN_FRAME_MAX + 1
+void launch_joint_compat(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, int n_frames, const int32_t *frame_start,
+                         double lidar, int n_map, const double *map_xy, const double *map_cov, const double *pose_cov, NnDev p, const JcGate &gate,
+                         const int32_t *in_idx, int32_t *out_idx, double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable,
+                         double *out_delta, hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 }  // namespace gs

@@ -53,6 +53,8 @@ void gs_frontend_release(gs_graph *g) {      // gs_destroy
     if (g->fe.nn_pin_out) hipHostFree(g->fe.nn_pin_out);
     if (g->fe.nn_dev_in) hipFree(g->fe.nn_dev_in);
     if (g->fe.nn_dev_out) hipFree(g->fe.nn_dev_out);
+    if (g->fe.jc_pin_out) hipHostFree(g->fe.jc_pin_out);
+    if (g->fe.jc_dev_out) hipFree(g->fe.jc_dev_out);
     g->fe = gs_graph::FrontEnd();
 }
 
@@ -611,13 +613,11 @@ static void assign_staging_release(gs_graph *g) {      // gs_frontend_release, a
 }
 // one frame through the resident launch.  Staging (bytes): pose at 0, pose_cov at 32, obs at 128 (32-byte aligned: one load per observation),
 // then frame_start[2] and pose_of_obs[k] (zeros) as int32
-static int frame_assign(gs_graph *g, bool opt, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
-                        double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2, int32_t *out_na) {
-    if (!g || !pose || k < 0 || (k > 0 && (!obs || !out_zxy || !out_gxy || !out_idx || !out_d2))) return fail(GS_ERR_INVALID, "bad argument");
-    NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
-    if (k > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations");
-    rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (k == 0) return GS_OK;
+// the frame in device memory once frame_assign_enqueue has run: inputs in as_dev_in, the assignment's outputs in as_dev_out
+struct FrameDev { const double *pose, *pose_cov, *obs; const int32_t *frame_start, *pose_of_obs; double *z, *g, *d2; int32_t *idx, *na; size_t out_bytes; };
+// stages the frame (growing the staging first), sends it and enqueues the assignment: no wait, nothing copied back
+static int frame_assign_enqueue(gs_graph *g, bool opt, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const NnDev &nd, FrameDev &fd) {
+    int rc;
     auto &fe = g->fe;
     auto in_bytes = [](size_t m) { return (16 + 4 * m) * sizeof(double) + (2 + m) * sizeof(int32_t); };
     if (k > fe.as_cap_obs) {                                         // grow-only, as gs_frame_frontend_nn's
@@ -641,7 +641,20 @@ static int frame_assign(gs_graph *g, bool opt, const double pose[3], const doubl
     bool grid = fe.map_n >= 2048;                                    // by the map's size, as the batch call; gs_debug_options.assoc_grid forces either
     if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && fe.map_n > 0;
     if ((rc = assign_resident_launch(g, opt, grid, k, dp, 1, dfs + 2, dp + 16, 1, dfs, pose_cov ? dp + 4 : nullptr, nd, di, dd, opt ? dn : nullptr, dz, dg)) != GS_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(fe.as_pin_out, fe.as_dev_out, 2 * bz + bd + (opt ? 2 : 1) * bi, hipMemcpyDeviceToHost, g->stream));
+    fd = FrameDev{dp, pose_cov ? dp + 4 : nullptr, dp + 16, dfs, dfs + 2, dz, dg, dd, di, dn, 2 * bz + bd + (opt ? 2 : 1) * bi};
+    return GS_OK;
+}
+static int frame_assign(gs_graph *g, bool opt, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
+                        double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2, int32_t *out_na) {
+    if (!g || !pose || k < 0 || (k > 0 && (!obs || !out_zxy || !out_gxy || !out_idx || !out_d2))) return fail(GS_ERR_INVALID, "bad argument");
+    NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
+    if (k > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations");
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (k == 0) return GS_OK;
+    auto &fe = g->fe; FrameDev fd;
+    if ((rc = frame_assign_enqueue(g, opt, pose, pose_cov, obs, k, nd, fd)) != GS_OK) return rc;
+    const size_t bz = (size_t)k * 2 * sizeof(double), bd = (size_t)k * sizeof(double), bi = (size_t)k * sizeof(int32_t);
+    HIP_TRY(hipMemcpyAsync(fe.as_pin_out, fe.as_dev_out, fd.out_bytes, hipMemcpyDeviceToHost, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));
     fe.pin_map_busy = false;
     hipError_t e = hipGetLastError();
@@ -658,4 +671,175 @@ extern "C" int gs_frame_frontend_assign(gs_graph *g, const double pose[3], const
 extern "C" int gs_frame_frontend_assign_opt(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
                                             double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2, int32_t *out_na) {
     return frame_assign(g, true, pose, pose_cov, obs, k, params, out_zxy, out_gxy, out_idx, out_d2, out_na);
+}
+
+// ---- joint compatibility of a frame's hypothesis (gs_assoc_nn.hip, k_joint_compat): the gate table, the batch / resident / frame calls ----
+// Q(m, h) = e^-h sum_{k < m} h^k / k!: the upper tail of chi-square with 2 m degrees of freedom at x = 2 h, terms by t_k = t_{k-1} h / k
+static double jc_tail(int m, double h) {
+    double t = std::exp(-h), s = t;
+    for (int k = 1; k < m; ++k) { t = t * h / k; s += t; }
+    return s;
+}
+extern "C" int gs_jc_params_set_confidence(gs_jc_params *p, double confidence) {
+    if (!p) return fail(GS_ERR_INVALID, "null params");
+    if (!(confidence > 0.0 && confidence < 1.0)) return fail(GS_ERR_INVALID, "gs_jc_params: confidence must lie inside (0, 1)");
+    std::memset(p, 0, sizeof(*p)); p->struct_size = (int32_t)sizeof(*p); p->confidence = confidence;
+    const double tail = 1.0 - confidence;
+    p->gate[0] = 0.0;
+    for (int m = 1; m <= GS_NN_FRAME_MAX; ++m) {                    // bisection on the decreasing tail until the bracket is two neighbouring doubles
+        double lo = 0.0, hi = 2.0 * m + 16.0;
+        while (jc_tail(m, hi) > tail && hi < 1e6) hi *= 2.0;
+        for (int it = 0; it < 200; ++it) { const double mid = 0.5 * (lo + hi); if (!(mid > lo && mid < hi)) break;
+            if (jc_tail(m, mid) > tail) lo = mid; else hi = mid; }
+        p->gate[m] = 2.0 * hi;
+        if (p->gate[m] < p->gate[m - 1]) p->gate[m] = p->gate[m - 1];   // (more degrees of freedom never lower a quantile; rounding must not either)
+    }
+    return GS_OK;
+}
+extern "C" int gs_jc_params_default(gs_jc_params *p) { return gs_jc_params_set_confidence(p, 0.95); }
+static int jc_params_check(const gs_jc_params *p, JcGate &gt) {
+    if (!p) return fail(GS_ERR_INVALID, "null params");
+    if (p->struct_size != (int32_t)sizeof(gs_jc_params)) return fail(GS_ERR_INVALID, "gs_jc_params: wrong struct_size");
+    for (int m = 0; m <= GS_NN_FRAME_MAX; ++m) {
+        if (!std::isfinite(p->gate[m]) || p->gate[m] < 0.0) return fail(GS_ERR_INVALID, "gs_jc_params: a gate is not finite or negative");
+        if (m > 0 && p->gate[m] < p->gate[m - 1]) return fail(GS_ERR_INVALID, "gs_jc_params: the gates must not decrease");
+        gt.g[m] = p->gate[m]; }
+    return GS_OK;
+}
+// of gs_nn_params only struct_size and the three sigmas are read: the hypothesis is the caller's, no gate or distance test is repeated
+static int jc_sigmas_check(const gs_nn_params *p, NnDev &d) {
+    if (!p) return fail(GS_ERR_INVALID, "null params");
+    if (p->struct_size != (int32_t)sizeof(gs_nn_params)) return fail(GS_ERR_INVALID, "gs_nn_params: wrong struct_size");
+    const double v[3] = {p->sigma_range, p->sigma_bearing, p->sigma_xy};
+    for (double x : v) if (!std::isfinite(x) || x < 0.0) return fail(GS_ERR_INVALID, "gs_nn_params: a sigma is not finite or negative");
+    d = NnDev{0.0, 0.0, 0.0, p->sigma_range, p->sigma_bearing, p->sigma_xy};
+    return GS_OK;
+}
+extern "C" int gs_joint_compat_batch(gs_graph *g, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs, const double *obs,
+                                     int32_t n_frames, const int32_t *frame_start, int32_t n_map, const double *map_xy, const double *map_cov,
+                                     const double *pose_cov, const gs_nn_params *params, const gs_jc_params *jc, const int32_t *in_index,
+                                     int32_t *out, double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable, double *out_delta) {
+    if (!g || n < 0 || npose < 0 || n_map < 0 || (n > 0 && (!poses || !pose_of_obs || !obs || !in_index || !out)) || (n_map > 0 && !map_xy))
+        return fail(GS_ERR_INVALID, "bad argument");
+    NnDev nd; int rc = jc_sigmas_check(params, nd); if (rc != GS_OK) return rc;
+    JcGate gt; if ((rc = jc_params_check(jc, gt)) != GS_OK) return rc;
+    if ((rc = frame_start_check(n, n_frames, frame_start)) != GS_OK) return rc;
+    for (int i = 0; i < n; ++i) {
+        if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
+        if (in_index[i] < -1 || in_index[i] >= n_map) return fail(GS_ERR_INVALID, "in_index outside [-1, n_map)"); }
+    for (int f = 0; f < n_frames; ++f)
+        for (int i = frame_start[f] + 1; i < frame_start[f + 1]; ++i)
+            if (pose_of_obs[i] != pose_of_obs[frame_start[f]]) return fail(GS_ERR_INVALID, "the observations of a frame must share one pose");
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n_frames == 0) return GS_OK;
+    const size_t nf = (size_t)n_frames;
+    if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(9 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded(nf + 1, 4) +
+                               padded(2 * (size_t)n_map, 8) + padded(4 * (size_t)n_map, 8) + 2 * padded(n, 4) + padded(nf, 8) + padded(3 * nf, 8) + 3 * padded(nf, 4))) != GS_OK) return rc;
+    Carver c{g}; double *p = c.get<double>(3 * (size_t)npose), *pcv = c.get<double>(9 * (size_t)npose); int32_t *po = c.get<int32_t>(n);
+    double *ob = c.get<double>(4 * (size_t)n); int32_t *fs = c.get<int32_t>(nf + 1);
+    double *mx = c.get<double>(2 * (size_t)n_map), *mc = c.get<double>(4 * (size_t)n_map);
+    int32_t *ii = c.get<int32_t>(n), *o = c.get<int32_t>(n); double *oj = c.get<double>(nf), *odl = c.get<double>(3 * nf);
+    int32_t *ok = c.get<int32_t>(nf), *od = c.get<int32_t>(nf), *ou = c.get<int32_t>(nf);
+    if (npose > 0) HIP_TRY(hipMemcpyAsync(p, poses, 3 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
+    if (pose_cov && npose > 0) HIP_TRY(hipMemcpyAsync(pcv, pose_cov, 9 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
+    if (n > 0) { HIP_TRY(hipMemcpyAsync(po, pose_of_obs, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
+                 HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
+                 HIP_TRY(hipMemcpyAsync(ii, in_index, (size_t)n * 4, hipMemcpyHostToDevice, g->stream)); }
+    HIP_TRY(hipMemcpyAsync(fs, frame_start, (nf + 1) * 4, hipMemcpyHostToDevice, g->stream));
+    if (n_map > 0) { HIP_TRY(hipMemcpyAsync(mx, map_xy, 2 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream));
+                     if (map_cov) HIP_TRY(hipMemcpyAsync(mc, map_cov, 4 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream)); }
+    launch_joint_compat(n, p, npose, po, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, map_cov ? mc : nullptr, pose_cov ? pcv : nullptr, nd, gt,
+                        ii, o, oj, ok, od, ou, odl, g->stream);
+    if (n > 0) HIP_TRY(hipMemcpyAsync(out, o, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (out_j) HIP_TRY(hipMemcpyAsync(out_j, oj, nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    if (out_kept) HIP_TRY(hipMemcpyAsync(out_kept, ok, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (out_dropped) HIP_TRY(hipMemcpyAsync(out_dropped, od, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (out_untestable) HIP_TRY(hipMemcpyAsync(out_untestable, ou, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (out_delta) HIP_TRY(hipMemcpyAsync(out_delta, odl, 3 * nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));        // the one wait of the call: the result copies
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("joint compatibility: ") + hipGetErrorString(e));
+    return GS_OK;
+}
+extern "C" int gs_joint_compat_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
+                                        int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov, const gs_nn_params *params,
+                                        const gs_jc_params *jc, const int32_t *dev_in_index, int32_t *dev_out, double *dev_out_j, int32_t *dev_out_kept,
+                                        int32_t *dev_out_dropped, int32_t *dev_out_untestable, double *dev_out_delta) {
+    if (!g || n < 0 || npose < 0 || n_frames < 0 || !dev_frame_start || (n > 0 && (!dev_poses || !dev_pose_of_obs || !dev_obs || !dev_in_index || !dev_out)))
+        return fail(GS_ERR_INVALID, "bad argument");
+    NnDev nd; int rc = jc_sigmas_check(params, nd); if (rc != GS_OK) return rc;
+    JcGate gt; if ((rc = jc_params_check(jc, gt)) != GS_OK) return rc;
+    if (((uintptr_t)dev_obs & 31) != 0) return fail(GS_ERR_INVALID, "dev_obs must be 32-byte aligned (an observation is read in one load)");
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n_frames == 0) return GS_OK;
+    auto &fe = g->fe;
+    launch_joint_compat(n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_cov, dev_pose_cov,
+                        nd, gt, dev_in_index, dev_out, dev_out_j, dev_out_kept, dev_out_dropped, dev_out_untestable, dev_out_delta, g->stream, g->ev_lin[0], g->ev_lin[1]);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("joint compatibility: ") + hipGetErrorString(e));
+    return GS_OK;
+}
+// the twin of gs_debug_time_assign_opt_resident: start / stop events from the first dispatch of the joint test to its last
+extern "C" int gs_debug_time_joint_compat_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
+                                                   const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov,
+                                                   const gs_nn_params *params, const gs_jc_params *jc, const int32_t *dev_in_index, int32_t *dev_out,
+                                                   double *dev_out_j, int32_t *dev_out_kept, int32_t *dev_out_dropped, int32_t *dev_out_untestable,
+                                                   double *dev_out_delta, int32_t reps, double *out_ms) {
+    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
+    auto once = [&] { return gs_joint_compat_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, jc, dev_in_index,
+                                                      dev_out, dev_out_j, dev_out_kept, dev_out_dropped, dev_out_untestable, dev_out_delta); };
+    int rc = once(); if (rc != GS_OK) return rc;                    // warm
+    std::vector<hipEvent_t> ev(2 * (size_t)reps); for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    for (int r = 0; r < reps && rc == GS_OK; ++r) { g->ev_lin[0] = ev[2 * (size_t)r]; g->ev_lin[1] = ev[2 * (size_t)r + 1]; rc = once(); }
+    g->ev_lin[0] = g->ev_lin[1] = nullptr;
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    double tot = 0; int cnt = 0;
+    for (int r = 0; r < reps; ++r) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]) == hipSuccess && ms > 0) { tot += ms; ++cnt; } }
+    (void)hipGetLastError();
+    for (auto &e : ev) hipEventDestroy(e);
+    *out_ms = cnt ? tot / cnt : 0.0;
+    return rc;
+}
+// one frame: the minimum-cost assignment of gs_frame_frontend_assign_opt, then the joint test of its result, back to back on the stream.
+// Record staging (bytes): J at 0, delta at 8, kept / dropped / untestable at 32, the pruned index at 48
+extern "C" int gs_frame_frontend_jc(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
+                                    const gs_jc_params *jc, double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2, int32_t *out_na,
+                                    double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable, double *out_delta) {
+    if (!g || !pose || k < 0 || (k > 0 && (!obs || !out_zxy || !out_gxy || !out_idx || !out_d2))) return fail(GS_ERR_INVALID, "bad argument");
+    NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
+    JcGate gt; if ((rc = jc_params_check(jc, gt)) != GS_OK) return rc;
+    if (k > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations");
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (k == 0) {                                                   // the empty frame's record, without a launch
+        if (out_j) *out_j = 0.0;
+        if (out_kept) *out_kept = 0;
+        if (out_dropped) *out_dropped = 0;
+        if (out_untestable) *out_untestable = 0;
+        if (out_delta) out_delta[0] = out_delta[1] = out_delta[2] = 0.0;
+        return GS_OK; }
+    auto &fe = g->fe; FrameDev fd;
+    const size_t jbytes = 48 + (size_t)GS_NN_FRAME_MAX * sizeof(int32_t);
+    if (!fe.jc_dev_out) {                                           // once per handle: the size does not depend on k
+        HIP_TRY(hipHostMalloc((void **)&fe.jc_pin_out, jbytes, hipHostMallocDefault)); HIP_TRY(hipMalloc((void **)&fe.jc_dev_out, jbytes)); }
+    if ((rc = frame_assign_enqueue(g, true, pose, pose_cov, obs, k, nd, fd)) != GS_OK) return rc;
+    char *jd = fe.jc_dev_out;
+    launch_joint_compat(k, fd.pose, 1, fd.pose_of_obs, fd.obs, 1, fd.frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_cov, fd.pose_cov, nd, gt, fd.idx,
+                        (int32_t *)(jd + 48), (double *)jd, (int32_t *)(jd + 32), (int32_t *)(jd + 36), (int32_t *)(jd + 40), (double *)(jd + 8), g->stream);
+    const size_t bz = (size_t)k * 2 * sizeof(double), bd = (size_t)k * sizeof(double), bi = (size_t)k * sizeof(int32_t);
+    HIP_TRY(hipMemcpyAsync(fe.as_pin_out, fe.as_dev_out, fd.out_bytes, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(fe.jc_pin_out, fe.jc_dev_out, 48 + bi, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));                       // the one wait of the call
+    fe.pin_map_busy = false;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("joint compatibility: ") + hipGetErrorString(e));
+    const char *po = fe.as_pin_out, *pj = fe.jc_pin_out;
+    std::memcpy(out_zxy, po, bz); std::memcpy(out_gxy, po + bz, bz); std::memcpy(out_d2, po + 2 * bz, bd);
+    if (out_na) std::memcpy(out_na, po + 2 * bz + bd + bi, bi);
+    std::memcpy(out_idx, pj + 48, bi);
+    if (out_j) std::memcpy(out_j, pj, sizeof(double));
+    if (out_delta) std::memcpy(out_delta, pj + 8, 3 * sizeof(double));
+    if (out_kept) std::memcpy(out_kept, pj + 32, sizeof(int32_t));
+    if (out_dropped) std::memcpy(out_dropped, pj + 36, sizeof(int32_t));
+    if (out_untestable) std::memcpy(out_untestable, pj + 40, sizeof(int32_t));
+    return GS_OK;
 }

@@ -74,6 +74,8 @@ struct gs_graph {
         double *nn_pin_in = nullptr, *nn_dev_in = nullptr; char *nn_pin_out = nullptr, *nn_dev_out = nullptr; int nn_cap_obs = 0;
         // one-to-one association: the frame call's staging (null until gs_frame_frontend_assign is called), capacity in observations
         char *as_pin_in = nullptr, *as_dev_in = nullptr, *as_pin_out = nullptr, *as_dev_out = nullptr; int as_cap_obs = 0;
+        // joint compatibility: the frame call's record and pruned index (null until gs_frame_frontend_jc is called; sized for GS_NN_FRAME_MAX)
+        char *jc_pin_out = nullptr, *jc_dev_out = nullptr;
     } fe;
     bool tree_proven = false;               // a whole-tree launch sequence of the CURRENT plan has completed without a flag timeout (gs_optimize then sends all iterations of a call at once)
     bool fell_back = false;                 // a whole-tree launch gave up on a flag: this handle uses one launch per level — until the next plan, or until a retry (below) comes back clean
