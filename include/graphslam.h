@@ -864,7 +864,7 @@ int  gs_frame_frontend_assign_opt(gs_graph *g, const double pose_xytheta[3], con
  *      fixed record buffer of its own from the first call on: nothing is allocated per call after that.
  * A handle that never calls any of these allocates and launches nothing for them; the calls above are unchanged by them.
  * NOT DONE: pose-cone and cone-cone cross-covariances; JCBB's search over alternative cones — this PRUNES a given hypothesis, it does not
- *      re-match; the posterior pose covariance; frames of more than GS_NN_FRAME_MAX observations; sharded handles (nothing beyond what the
+ *      re-match; the posterior pose covariance (frame localisation, below, returns it); frames of more than GS_NN_FRAME_MAX observations; sharded handles (nothing beyond what the
  *      gs_associate_nn_* calls give); the Slam mirror and the shell, which keep the Euclidean rule. */
 typedef struct gs_jc_params {
     int32_t struct_size;
@@ -888,6 +888,84 @@ int  gs_frame_frontend_jc(gs_graph *g, const double pose_xytheta[3], const doubl
                           const gs_nn_params *params, const gs_jc_params *jc, double *out_zxy, double *out_gxy, int32_t *out_index, double *out_d2,
                           int32_t *out_n_admissible, double *out_joint_d2, int32_t *out_n_kept, int32_t *out_n_dropped, int32_t *out_n_untestable,
                           double *out_delta_3);
+
+/* ---- frame localisation: iterated pose refinement against the map ------------------------------------------------------
+ * The joint test's delta is ONE linear step from the prior pose.  The model is not linear in the heading (w = R(theta) z against w + dtheta wp
+ * leaves r dtheta^2 / 2: 5 cm for a cone at 10 m and 0.1 rad), the joint test does not return the posterior covariance, and nothing says how
+ * well the frame fits where it ends.  These calls compute the maximum-a-posteriori pose under the prior (x0, Sigma_p) and the frame's pairs
+ * by iterated relinearisation on the device (the iterated EKF update: Gauss-Newton on three unknowns per frame), the posterior covariance
+ * and the posterior chi2.  The reference has no noise model: the rule is build-defined.
+ *
+ * Frames, the hypothesis in_index (a cone or -1 per observation) and the pose are those of gs_joint_compat_*: all observations of a frame share
+ *      one pose index; x0 = (t0, theta0) = that pose, Sigma_p = its 3x3 covariance (row-major, the upper triangle read).
+ * Iterate.  d_0 = (+0, +0, +0).  x_0 = x0 itself; for k > 0  x_k = (t0 + d_k[0:2], theta0 + d_k[2]), NOT normalised (sincos is periodic).
+ * Pair terms at x_k.  Observation i with j = in_index[i] != -1:  z by the A0 formula (it does not depend on k);  w = R(theta_k) z, g = w + t_k,
+ *      wp = (-w_y, w_x) and Q exactly as the covariance-gated association forms them from the pose x_k WITHOUT a pose covariance — with k = 0 the
+ *      bits the joint test uses;  D = Sigma_j + Q, nu = l_j - g, det, y, E, h, c_i and M_i exactly as listed under "joint compatibility".
+ *      The pair COUNTS in iteration k iff ALL of  the query is valid (g finite, r > 0, pose index in range),  0 <= j < n_map,  det > 0,  D00 > 0,
+ *      nu finite (a cone whose position is not finite never counts)  hold (positive tests, taken again in every iteration).  A pair that does
+ *      not count contributes +0.
+ * Sums.  c, M and the count m_k in the joint test's fixed order: lane r mod 64 adds its pairs in ascending r from +0, then the butterfly at
+ *      distance 32, 16, 8, 4, 2, 1.
+ * Right-hand side.  k = 0: b = c.  k > 0: b_r = c_r + ((M_r0 d_k0 + M_r1 d_k1) + M_r2 d_k2).
+ * Solve.  The joint test's operations with b in place of c:  A = I + M Sigma_p, the nine cofactors C, detA = (A00 C00 + A01 C01) + A02 C02,
+ *      x_s = ((C0s b0 + C1s b1) + C2s b2) / detA,  d_{k+1,r} = (P_r0 x0 + P_r1 x1) + P_r2 x2.  In exact arithmetic d_{k+1} = (Sigma_p^-1 + M)^-1
+ *      (c + M d_k): the Gauss-Newton step of |x - x0|^2_{Sigma_p^-1} + sum |nu_i(x)|^2_{D_i^-1}, written so that Sigma_p is never inverted and
+ *      may be singular or very wide.
+ * Stop.  Converged iff ALL of |d_{k+1,0} - d_k0| <= tol_xy, |d_{k+1,1} - d_k1| <= tol_xy, |d_{k+1,2} - d_k2| <= tol_theta hold (positive
+ *      tests).  Otherwise the next iteration runs, until max_iterations solves have been made.  No host decision between iterations.
+ * Final pass at x_f = x0 + d_f, d_f = the last d (x_f = x0 itself when no solve was made): the pair terms once more, with
+ *      a_i = (((D11 nu0) nu0 - ((2 D01) nu0) nu1) + (D00 nu1) nu1) / det, summed with M and the count as above;  A, C, detA of this pass;
+ *      cov_rs = ((P_r0 C_s0 + P_r1 C_s1) + P_r2 C_s2) / detA for r <= s, mirrored  (exactly: Sigma_p (I + M Sigma_p)^-1 = (Sigma_p^-1 + M)^-1);
+ *      chi2 = a + ((x0 d_f0 + x1 d_f1) + x2 d_f2), x of the LAST solve (the second term is d_f^T Sigma_p^-1 d_f without an inverse); it has
+ *      2 n_pairs degrees of freedom: hold it against gs_jc_params.gate[n_pairs];
+ *      pose = (t0x + d_f0, t0y + d_f1, normalize_theta(theta0 + d_f2)) — gs_iterate's addition and normalisation;
+ *      n_pairs = the pairs counted in this pass;  iterations = the solves made.
+ * Status.  0 converged.  1 the iteration limit was reached.  2 no pair counted in iteration 0: pose = x0's bits, cov = Sigma_p's (upper triangle,
+ *      mirrored), chi2 0, n_pairs 0, iterations 0 — an EMPTY frame has no pose: zeros.  3 some d or detA (of a solve or of the final pass) was
+ *      not finite: pose and cov as for 2, chi2 +inf, n_pairs 0.  4 the frame was refused (resident defences): zeros, chi2 +inf, counts 0.
+ *      pose_cov == NULL: the prior has zero covariance; no solve: status 0, iterations 0, pose = (t0, normalize_theta(theta0)), cov zeros,
+ *      chi2 = a at x0 (the fixed-order sum of the bits gs_associate_nn_* returns as d2 for the pairs), n_pairs as counted.
+ * Outputs per frame, each pointer may be NULL: out_pose[3], out_cov[9], out_chi2, out_n_pairs, out_iterations, out_status.  No contraction anywhere.
+ * Consequences.  With max_iterations = 1, d_f is BITWISE the delta of gs_joint_compat_* for a hypothesis that call keeps whole.  A frame's
+ *      result does not depend on the lanes it was given, on the kernel, or on its neighbours in the wave.  Batch, resident and frame call return
+ *      identical bits (the frame call with k == 0 makes no launch and returns status 2 with the GIVEN pose and covariance).
+ *
+ * gs_localize_batch: the host layouts of gs_joint_compat_batch (of gs_nn_params only struct_size and the three sigmas are read).  GS_ERR_INVALID
+ *      before the device is touched: everything gs_joint_compat_batch refuses, a wrong gs_loc_params.struct_size, max_iterations outside
+ *      1 .. GS_LOC_ITER_MAX, a tolerance that is negative or not finite.  A host-only handle: GS_ERR_NO_DEVICE.
+ * gs_localize_resident: everything in DEVICE memory against the resident map and its covariances, asynchronous on the handle's stream, no wait.
+ *      dev_obs must be 32-byte aligned.  A frame whose bounds are not 0 <= a <= b <= n reads and writes nothing; a frame longer than
+ *      GS_NN_FRAME_MAX, or one whose observations name two different pose indices inside [0, n_poses), gets status 4; an index[i] outside
+ *      [-1, map size) is a pair that never counts; nothing is written per observation.
+ * gs_frame_frontend_localize: gs_frame_frontend_jc (same arguments, same outputs, same bits), then the localisation under the PRUNED index,
+ *      enqueued back to back on the handle's stream, one wait.  It shares the assignment call's staging and keeps a fixed record buffer of its
+ *      own from the first call on.  To chain frames, the caller adds its motion noise to out_cov before it is the next frame's pose_cov.
+ * A handle that never calls any of these allocates and launches nothing for them; the calls above are unchanged by them.
+ * NOT DONE: the Slam mirror and the shell stay as they are (the reference's localizer reports the raw odometry pose); no prior-free (maximum-
+ *      likelihood) solve — a wide Sigma_p serves; no cross-covariances; no re-matching (the hypothesis is the caller's throughout); no sharded
+ *      handles; no frames above GS_NN_FRAME_MAX observations. */
+#define GS_LOC_ITER_MAX 16
+typedef struct gs_loc_params {
+    int32_t struct_size;
+    int32_t max_iterations;                 /* 5; 1 .. GS_LOC_ITER_MAX */
+    double tol_xy;                          /* 1e-6 m */
+    double tol_theta;                       /* 1e-8 rad */
+} gs_loc_params;
+int  gs_loc_params_default(gs_loc_params *p);
+int  gs_localize_batch(gs_graph *g, int32_t n, const double *poses_xytheta, int32_t n_poses, const int32_t *pose_of_obs, const double *obs_4xn,
+                       int32_t n_frames, const int32_t *frame_start, int32_t n_map, const double *map_xy, const double *map_cov_2x2,
+                       const double *pose_cov_3x3, const gs_nn_params *params, const gs_loc_params *loc, const int32_t *in_index,
+                       double *out_pose_3, double *out_cov_3x3, double *out_chi2, int32_t *out_n_pairs, int32_t *out_iterations, int32_t *out_status);
+int  gs_localize_resident(gs_graph *g, int32_t n, const double *dev_poses_xytheta, int32_t n_poses, const int32_t *dev_pose_of_obs,
+                          const double *dev_obs_4xn, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov_3x3,
+                          const gs_nn_params *params, const gs_loc_params *loc, const int32_t *dev_in_index, double *dev_out_pose_3,
+                          double *dev_out_cov_3x3, double *dev_out_chi2, int32_t *dev_out_n_pairs, int32_t *dev_out_iterations, int32_t *dev_out_status);
+int  gs_frame_frontend_localize(gs_graph *g, const double pose_xytheta[3], const double *pose_cov_3x3, const double *obs_4xk, int32_t k,
+                                const gs_nn_params *params, const gs_jc_params *jc, const gs_loc_params *loc, double *out_zxy, double *out_gxy,
+                                int32_t *out_index, double *out_d2, int32_t *out_n_admissible, double *out_joint_d2, int32_t *out_n_kept,
+                                int32_t *out_n_dropped, int32_t *out_n_untestable, double *out_delta_3, double *out_pose_3, double *out_cov_3x3,
+                                double *out_chi2, int32_t *out_n_pairs, int32_t *out_iterations, int32_t *out_status);
 
 /* ---- multi-GPU: pose-window shards -----------------------------
  * Each rank owns a contiguous pose window and builds the SAME global plan; it linearises and

@@ -111,6 +111,17 @@ int gs_debug_time_joint_compat_resident(gs_graph *g, int32_t n, const double *de
                                         const gs_nn_params *params, const gs_jc_params *jc, const int32_t *dev_in_index, int32_t *dev_out_index,
                                         double *dev_out_joint_d2, int32_t *dev_out_n_kept, int32_t *dev_out_n_dropped, int32_t *dev_out_n_untestable,
                                         double *dev_out_delta_3, int32_t reps, double *out_ms);
+/* Frame localisation.  gs_debug_localize: kernel = 0 forces k_localize (k_localize_big behind it for the frames above 64 observations), 1 forces
+ * k_localize_big alone, -1 (default) chooses by the mean frame size — in all three calls; results do not depend on it.  dev_out_step_3: a DEVICE
+ * buffer of 3 doubles per frame that every later gs_localize_resident call fills with d_f (zeros where no solve was made or the status is 2, 3
+ * or 4), until it is set back to NULL; the batch and the frame call do not write it.  gs_debug_time_localize_resident: `reps` launches of
+ * gs_localize_resident, events from its first dispatch to its last. */
+int gs_debug_localize(gs_graph *g, int32_t kernel, double *dev_out_step_3);
+int gs_debug_time_localize_resident(gs_graph *g, int32_t n, const double *dev_poses_xytheta, int32_t n_poses, const int32_t *dev_pose_of_obs,
+                                    const double *dev_obs_4xn, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov_3x3,
+                                    const gs_nn_params *params, const gs_loc_params *loc, const int32_t *dev_in_index, double *dev_out_pose_3,
+                                    double *dev_out_cov_3x3, double *dev_out_chi2, int32_t *dev_out_n_pairs, int32_t *dev_out_iterations,
+                                    int32_t *dev_out_status, int32_t reps, double *out_ms);
 /* Measurement hook of the sharded iteration (bench.py's `ms_exchange`): `reps` RCCL all-reduces of the exchange buffer back to back on the
  * handle's stream, HIP events around them; mean ms per all-reduce.  Collective: every rank of the communicator calls it. */
 int gs_debug_time_exchange(gs_graph *g, int32_t reps, double *out_ms);

@@ -158,6 +158,32 @@ def _jc_record(n_frames):
             "n_untestable": np.zeros(n_frames, dtype=np.int32), "delta": np.zeros((n_frames, 3))}
 
 
+LOC_ITER_MAX = 16                                           # GS_LOC_ITER_MAX
+
+
+class LocParams(C.Structure):
+    """gs_loc_params (include/graphslam.h): the iteration limit and the stop tolerances of frame localisation"""
+    _fields_ = [("struct_size", C.c_int32), ("max_iterations", C.c_int32), ("tol_xy", C.c_double), ("tol_theta", C.c_double)]
+
+
+def loc_params(**kw):
+    """the library's gs_loc_params defaults, with the named fields changed"""
+    p = LocParams(); L = lib()
+    rc = L.gs_loc_params_default(C.byref(p))
+    if rc != GS_OK:
+        raise GsError(rc, (L.gs_last_error() or b"").decode())
+    for k, v in kw.items():
+        if k not in ("max_iterations", "tol_xy", "tol_theta"):
+            raise AttributeError("gs_loc_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _loc_record(n_frames):
+    return {"pose": np.zeros((n_frames, 3)), "cov": np.zeros((n_frames, 9)), "chi2": np.zeros(n_frames), "n_pairs": np.zeros(n_frames, dtype=np.int32),
+            "iterations": np.zeros(n_frames, dtype=np.int32), "status": np.zeros(n_frames, dtype=np.int32)}
+
+
 class DoglegParams(C.Structure):
     """gs_dogleg_params (include/graphslam.h)"""
     _fields_ = [("struct_size", C.c_int32), ("max_trials_after_failure", C.c_int32), ("initial_delta", C.c_double)]
@@ -343,6 +369,14 @@ def lib():
         L.gs_joint_compat_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, jpp, vp, vp, vp, vp, vp, vp, vp]
         L.gs_debug_time_joint_compat_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, jpp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, _dp]
         L.gs_frame_frontend_jc.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, jpp, _dp, _dp, _ip, _dp, _ip, _dp, _ip, _ip, _ip, _dp]
+    if hasattr(L, "gs_localize_batch"):                    # (and for frame localisation)
+        npp = C.POINTER(NnParams); jpp = C.POINTER(JcParams); lpp = C.POINTER(LocParams)
+        L.gs_loc_params_default.argtypes = [lpp]
+        L.gs_debug_localize.argtypes = [vp, C.c_int32, vp]
+        L.gs_localize_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32, _ip, C.c_int32, _dp, _dp, _dp, npp, lpp, _ip, _dp, _dp, _dp, _ip, _ip, _ip]
+        L.gs_localize_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, lpp, vp, vp, vp, vp, vp, vp, vp]
+        L.gs_debug_time_localize_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, lpp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, _dp]
+        L.gs_frame_frontend_localize.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, jpp, lpp, _dp, _dp, _ip, _dp, _ip, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
     if hasattr(L, "gs_set_robust_kernel"):                # (a tuning build of an older tree loaded through GS_LIB may predate the robust kernels)
         L.gs_set_robust_kernel.argtypes = [vp, C.c_int32, C.c_int32, C.c_double]
         L.gs_get_robust_kernel.argtypes = [vp, C.c_int32, _ip, _dp]
@@ -1118,6 +1152,57 @@ class Graph:
         self._check(self.L.gs_frame_frontend_jc(self.h, _d(pose), None if pc is None else _d(pc), _d(obs), k, C.byref(p), C.byref(j), _d(z), _d(gx), _i(idx), _d(d2), _i(na),
                                                 _d(rec["joint_d2"]), _i(rec["n_kept"]), _i(rec["n_dropped"]), _i(rec["n_untestable"]), _d(rec["delta"])))
         return z, gx, idx, d2, na, rec
+
+    # ---- frame localisation (include/graphslam.h): the iterated pose refinement of a frame under its hypothesis.
+    # A frame's record is a dict: pose [f,3], cov [f,9], chi2 [f], n_pairs / iterations / status [f] int32
+    def localize(self, poses, pose_of_obs, obs, frame_start, map_xy, in_index, map_cov=None, pose_cov=None, params=None, loc=None):
+        """gs_localize_batch: the record of every frame"""
+        poses = _f64(poses, (-1, 3)); obs = _f64(obs, (-1, 4)); po = _i32(pose_of_obs); fs = _i32(frame_start); ii = _i32(in_index)
+        map_xy = _f64(map_xy, (-1, 2)); n = len(obs); nf = len(fs) - 1
+        mc = None if map_cov is None else _f64(map_cov, (-1, 4)); pc = None if pose_cov is None else _f64(pose_cov, (-1, 9))
+        assert mc is None or len(mc) == len(map_xy); assert pc is None or len(pc) == len(poses); assert len(fs) >= 1 and len(ii) == n
+        p = nn_params() if params is None else params; l = loc_params() if loc is None else loc
+        rec = _loc_record(nf)
+        self._check(self.L.gs_localize_batch(self.h, n, _d(poses), len(poses), _i(po), _d(obs), nf, _i(fs), len(map_xy), _d(map_xy),
+                                             None if mc is None else _d(mc), None if pc is None else _d(pc), C.byref(p), C.byref(l), _i(ii),
+                                             _d(rec["pose"]), _d(rec["cov"]), _d(rec["chi2"]), _i(rec["n_pairs"]), _i(rec["iterations"]), _i(rec["status"])))
+        return rec
+
+    def localize_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_in_index, d_pose=None, d_cov=None, d_chi2=None,
+                          d_n_pairs=None, d_iterations=None, d_status=None, d_pose_cov=None, params=None, loc=None):
+        """gs_localize_resident: the resident map and its covariances, everything else DeviceArray; asynchronous (synchronize() before reading)"""
+        p = nn_params() if params is None else params; l = loc_params() if loc is None else loc
+        opt = lambda a: None if a is None else a.ptr
+        self._check(self.L.gs_localize_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, int(n_frames), d_frame_start.ptr,
+                                                opt(d_pose_cov), C.byref(p), C.byref(l), d_in_index.ptr, opt(d_pose), opt(d_cov), opt(d_chi2),
+                                                opt(d_n_pairs), opt(d_iterations), opt(d_status)))
+
+    def time_localize_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_in_index, reps, d_pose=None, d_cov=None,
+                               d_chi2=None, d_n_pairs=None, d_iterations=None, d_status=None, d_pose_cov=None, params=None, loc=None):
+        p = nn_params() if params is None else params; l = loc_params() if loc is None else loc
+        opt = lambda a: None if a is None else a.ptr
+        ms = C.c_double()
+        self._check(self.L.gs_debug_time_localize_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, int(n_frames), d_frame_start.ptr,
+                                                           opt(d_pose_cov), C.byref(p), C.byref(l), d_in_index.ptr, opt(d_pose), opt(d_cov), opt(d_chi2),
+                                                           opt(d_n_pairs), opt(d_iterations), opt(d_status), int(reps), C.byref(ms)))
+        return ms.value
+
+    def debug_localize(self, kernel=-1, d_step=None):
+        """gs_debug_localize: force k_localize (0) or k_localize_big (1), -1 by the mean frame size; d_step: a DeviceArray of 3 doubles per frame that
+        later localize_resident calls fill with d_f, None to stop"""
+        self._check(self.L.gs_debug_localize(self.h, int(kernel), None if d_step is None else d_step.ptr))
+
+    def frame_frontend_localize(self, pose, obs, pose_cov=None, params=None, jc=None, loc=None):
+        """frame_frontend_jc's tuple (zxy, gxy, pruned idx, d2, n_admissible, joint record) + the localisation record of the one frame"""
+        pose = _f64(pose); obs = _f64(obs, (-1, 4)); k = len(obs); pc = None if pose_cov is None else _f64(pose_cov, (9,))
+        p = nn_params() if params is None else params; j = jc_params() if jc is None else jc; l = loc_params() if loc is None else loc
+        z = np.zeros((k, 2)); gx = np.zeros((k, 2)); idx = np.zeros(k, dtype=np.int32); d2 = np.zeros(k); na = np.zeros(k, dtype=np.int32)
+        rec = _jc_record(1); lr = _loc_record(1)
+        self._check(self.L.gs_frame_frontend_localize(self.h, _d(pose), None if pc is None else _d(pc), _d(obs), k, C.byref(p), C.byref(j), C.byref(l), _d(z), _d(gx),
+                                                      _i(idx), _d(d2), _i(na), _d(rec["joint_d2"]), _i(rec["n_kept"]), _i(rec["n_dropped"]), _i(rec["n_untestable"]),
+                                                      _d(rec["delta"]), _d(lr["pose"]), _d(lr["cov"]), _d(lr["chi2"]), _i(lr["n_pairs"]), _i(lr["iterations"]),
+                                                      _i(lr["status"])))
+        return z, gx, idx, d2, na, rec, lr
 
     # ---- pose-window shards (one handle per rank / GPU)
     def dist_configure(self, rank, world):

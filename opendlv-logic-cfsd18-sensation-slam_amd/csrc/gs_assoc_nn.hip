@@ -8,6 +8,7 @@
 //   k_assign_nn       the one-to-one association inside frames (gs_assign_nn_*, gs_frame_frontend_assign): further down, with its own text
 //   k_assign_opt      the minimum-cost association inside frames (gs_assign_opt_*): likewise
 //   k_joint_compat    the joint test of a frame's hypothesis (gs_joint_compat_*, gs_frame_frontend_jc): likewise
+//   k_localize        the iterated pose refinement of a frame against the map (gs_localize_*, gs_frame_frontend_localize): likewise
 //
 // The three association kernels return IDENTICAL bits: the query's side (z, g, Q + P) is nn_query, one candidate's side (S, det, d2 and
 // the five tests) is nn_pair, both without contraction, the A0 conversion is ONE out-of-line function (polar_to_xy compiled once, not
@@ -31,11 +32,10 @@ __device__ __noinline__ double2 nn_polar(double az, double zen, double dist, dou
 }
 
 // pose = (t, theta), pc = the pose's 3x3 covariance (row-major, upper triangle read) or null
-__device__ __forceinline__ NnQuery nn_query(const double *pose, const double *pc, double az, double zen, double dist, double ty, double lidar, const NnDev &p) {
+// (nn_query_at: the same from z and the heading's sin / cos, for a caller that moves the pose under a fixed z — lo_pass)
+__device__ __forceinline__ NnQuery nn_query_at(const double *pose, const double *pc, double2 z, double s, double c, double ty, const NnDev &p) {
 #pragma clang fp contract(off)
     NnQuery q;
-    const double2 z = nn_polar(az, zen, dist, lidar);
-    double s, c; sincos(pose[2], &s, &c);
     const double wx = z.x * c - z.y * s, wy = z.x * s + z.y * c;               // w = R(theta) z
     q.zx = z.x; q.zy = z.y; q.gx = wx + pose[0]; q.gy = wy + pose[1]; q.ty = ty;
     const double r2 = z.x * z.x + z.y * z.y;
@@ -52,6 +52,11 @@ __device__ __forceinline__ NnQuery nn_query(const double *pose, const double *pc
     }
     q.valid = isfinite(q.gx) && isfinite(q.gy) && r2 > 0.0;
     return q;
+}
+__device__ __forceinline__ NnQuery nn_query(const double *pose, const double *pc, double az, double zen, double dist, double ty, double lidar, const NnDev &p) {
+    const double2 z = nn_polar(az, zen, dist, lidar);
+    double s, c; sincos(pose[2], &s, &c);
+    return nn_query_at(pose, pc, z, s, c, ty, p);
 }
 
 // one candidate: true and d2 when it is admissible (all tests positive: any NaN skips it)
@@ -564,12 +569,11 @@ struct JcArgs {
     double lidar; int n_map; const double *map_xy, *map_cov, *pose_cov; NnDev p; const int32_t *in_idx;
     int32_t *out_idx; double *out_j; int32_t *out_kept, *out_dropped, *out_untestable; double *out_delta; JcGate gate;
 };
-// J and delta of the sums S; P = Sigma_p's upper triangle (p00 p01 p02 p11 p12 p22), has_p false: Sigma_p = 0, delta = 0 and J = a
-__device__ __forceinline__ double jc_solve(const double (&S)[JC_TERMS], const double (&P)[6], bool has_p, double (&dl)[3]) {
+// (the solve in three pieces, so that lo_pass below runs the same operations.)  P = Sigma_p's upper triangle (p00 p01 p02 p11 p12 p22)
+// K = the nine cofactors of A = I + M Sigma_p (K[3 r + s] = C_rs) and det A, from the sums' M (S[4 .. 9])
+__device__ __forceinline__ double jc_cofactors(const double (&S)[JC_TERMS], const double (&P)[6], double (&K)[9]) {
 #pragma clang fp contract(off)
-    dl[0] = dl[1] = dl[2] = 0.0;
-    if (!has_p) return S[0];
-    const double c0 = S[1], c1 = S[2], c2 = S[3], m00 = S[4], m01 = S[5], m02 = S[6], m11 = S[7], m12 = S[8], m22 = S[9];
+    const double m00 = S[4], m01 = S[5], m02 = S[6], m11 = S[7], m12 = S[8], m22 = S[9];
     const double p00 = P[0], p01 = P[1], p02 = P[2], p11 = P[3], p12 = P[4], p22 = P[5];
     // A = I + M Sigma_p
     const double a00 = 1.0 + ((m00 * p00 + m01 * p01) + m02 * p02), a01 = (m00 * p01 + m01 * p11) + m02 * p12, a02 = (m00 * p02 + m01 * p12) + m02 * p22;
@@ -579,10 +583,30 @@ __device__ __forceinline__ double jc_solve(const double (&S)[JC_TERMS], const do
     const double k00 = a11 * a22 - a12 * a21, k01 = a12 * a20 - a10 * a22, k02 = a10 * a21 - a11 * a20;
     const double k10 = a02 * a21 - a01 * a22, k11 = a00 * a22 - a02 * a20, k12 = a01 * a20 - a00 * a21;
     const double k20 = a01 * a12 - a02 * a11, k21 = a02 * a10 - a00 * a12, k22 = a00 * a11 - a01 * a10;
-    const double det = (a00 * k00 + a01 * k01) + a02 * k02;
+    K[0] = k00; K[1] = k01; K[2] = k02; K[3] = k10; K[4] = k11; K[5] = k12; K[6] = k20; K[7] = k21; K[8] = k22;
+    return (a00 * k00 + a01 * k01) + a02 * k02;
+}
+// x = C^T c / det A and dl = Sigma_p x, c = S[1 .. 3]; returns det A
+__device__ __forceinline__ double jc_step(const double (&S)[JC_TERMS], const double (&P)[6], double (&x)[3], double (&dl)[3]) {
+#pragma clang fp contract(off)
+    double K[9];
+    const double det = jc_cofactors(S, P, K);
+    const double c0 = S[1], c1 = S[2], c2 = S[3];
+    const double p00 = P[0], p01 = P[1], p02 = P[2], p11 = P[3], p12 = P[4], p22 = P[5];
+    const double k00 = K[0], k01 = K[1], k02 = K[2], k10 = K[3], k11 = K[4], k12 = K[5], k20 = K[6], k21 = K[7], k22 = K[8];
     const double x0 = ((k00 * c0 + k10 * c1) + k20 * c2) / det, x1 = ((k01 * c0 + k11 * c1) + k21 * c2) / det, x2 = ((k02 * c0 + k12 * c1) + k22 * c2) / det;
+    x[0] = x0; x[1] = x1; x[2] = x2;
     dl[0] = (p00 * x0 + p01 * x1) + p02 * x2; dl[1] = (p01 * x0 + p11 * x1) + p12 * x2; dl[2] = (p02 * x0 + p12 * x1) + p22 * x2;
-    return S[0] - ((c0 * dl[0] + c1 * dl[1]) + c2 * dl[2]);
+    return det;
+}
+// J and delta of the sums S; has_p false: Sigma_p = 0, delta = 0 and J = a
+__device__ __forceinline__ double jc_solve(const double (&S)[JC_TERMS], const double (&P)[6], bool has_p, double (&dl)[3]) {
+#pragma clang fp contract(off)
+    dl[0] = dl[1] = dl[2] = 0.0;
+    if (!has_p) return S[0];
+    double x[3];
+    jc_step(S, P, x, dl);
+    return S[0] - ((S[1] * dl[0] + S[2] * dl[1]) + S[3] * dl[2]);
 }
 // one pass of a wave: lane group gi (W lanes, lane lg of it) tests the frame fw = [a, b) (fw < 0: none), b - a <= W (W < 64) or <= 64 * SLOTS.
 // Row rl of the frame sits at LDS row (rl / 64) * 64 + lane: lane == eb + lg with W < 64, lane == rl % 64 with W == 64.
@@ -730,6 +754,221 @@ __global__ void __launch_bounds__(64) k_joint_compat_big(JcArgs A) {
     }
 }
 
+// ---- frame localisation (include/graphslam.h, "frame localisation"): the maximum-a-posteriori pose under the prior (x0, Sigma_p) and the
+// frame's pairs (i, in_idx[i]), by iterated relinearisation — the joint test's sums and solve at the moving pose x_k = x0 + d_k, with the
+// right-hand side c + M d_k, so that d_{k+1} = (Sigma_p^-1 + M)^-1 (c + M d_k) without inverting Sigma_p — then one more pass at the last pose for
+// the posterior covariance Sigma_p (I + M Sigma_p)^-1 and chi2.
+//   FETCH   what no iteration changes, once: z (the A0 conversion), l_j, Sigma_j — seven doubles a row, in registers for frames up to 64
+//           (a row per lane), in LDS term-major for the large form (only the lane that wrote a row reads it); a row that can never count
+//           (no pair, an index outside the map, a pose index out of range) is left out by a bit of `live`
+//   ITERATE the pair terms at x_k (nn_query_at without a pose covariance, then the joint test's D, y, E, h), the sums of c, M and the count in
+//           the joint test's fixed order, the 3x3 solve on every lane (jc_step), the stop tests; a __ballot over the frames still open ends
+//           the loop, max_iterations bounds it
+//   FINAL   the pair terms with a (nn_pair's d2), the sums, the cofactors of A once more (jc_cofactors), Sigma+ and chi2
+// Lanes as k_joint_compat: W lanes per frame, 64 / W frames side by side; no barrier, no scratch, no wait, nothing written per observation.
+static constexpr int LO_FIXED = 7;                                             // zx zy lx ly c00 c01 c11
+template <int SLOTS> struct LoRows;
+template <> struct LoRows<1> {                                                 // a row per lane: registers
+    double r[LO_FIXED];
+    __device__ __forceinline__ void put(int, int, const double (&v)[LO_FIXED]) {
+#pragma unroll
+        for (int t = 0; t < LO_FIXED; ++t) r[t] = v[t]; }
+    __device__ __forceinline__ void get(int, int, double (&v)[LO_FIXED]) const {
+#pragma unroll
+        for (int t = 0; t < LO_FIXED; ++t) v[t] = r[t]; }
+};
+struct LoLds { double f[LO_FIXED][256]; };                                     // 14 KB
+template <> struct LoRows<4> {                                                 // four rows per lane: LDS, row s * 64 + lane
+    LoLds *L;
+    __device__ __forceinline__ void put(int s, int lane, const double (&v)[LO_FIXED]) {
+#pragma unroll
+        for (int t = 0; t < LO_FIXED; ++t) L->f[t][s * 64 + lane] = v[t]; }
+    __device__ __forceinline__ void get(int s, int lane, double (&v)[LO_FIXED]) const {
+#pragma unroll
+        for (int t = 0; t < LO_FIXED; ++t) v[t] = L->f[t][s * 64 + lane]; }
+};
+struct LoArgs {
+    int n; const double *poses; int n_poses; const int32_t *pose_of_obs; const double *obs; int n_frames; const int32_t *frame_start; int fpw, only_large;
+    double lidar; int n_map; const double *map_xy, *map_cov, *pose_cov; NnDev p; const int32_t *in_idx; int max_it; double tol_xy, tol_th;
+    double *out_pose, *out_cov, *out_chi2; int32_t *out_pairs, *out_iters, *out_status; double *out_step;
+};
+__device__ __forceinline__ double lo_normalize_theta(double th) {             // g2o normalize_theta, as in gs_kernels.hip (k_update)
+#pragma clang fp contract(off)
+    constexpr double pi = 3.14159265358979323846;
+    if (th >= -pi && th < pi) return th;
+    const double m = floor(th / (2.0 * pi));
+    th = th - m * 2.0 * pi;
+    if (th >= pi) th -= 2.0 * pi;
+    if (th < -pi) th += 2.0 * pi;
+    return th;
+}
+// one row's terms at the pose (sn, cs: its heading's sin / cos) ADDED to S (a, c[3], M[6]: jc_solve's layout) when the pair counts; FINAL: a
+// and M, else c and M.  The expressions are jc_pass's
+template <bool FINAL>
+__device__ __forceinline__ bool lo_row(const double (&v)[LO_FIXED], const double (&pose)[3], double sn, double cs, const NnDev &p, double (&S)[JC_TERMS]) {
+#pragma clang fp contract(off)
+    const NnQuery q = nn_query_at(pose, nullptr, make_double2(v[0], v[1]), sn, cs, 0.0, p);
+    if (!q.valid) return false;
+    const double n0 = v[2] - q.gx, n1 = v[3] - q.gy;
+    const double d00 = v[4] + q.a00, d01 = v[5] + q.a01, d11 = v[6] + q.a11;
+    const double det = d00 * d11 - d01 * d01;
+    if (!(det > 0.0 && d00 > 0.0 && isfinite(n0) && isfinite(n1))) return false;     // (a non-finite cone position never counts)
+    const double ux = -(q.zx * sn + q.zy * cs), uy = q.zx * cs - q.zy * sn;  // wp = (-w_y, w_x), w as nn_query forms it
+    const double e00 = d11 / det, e01 = -(d01 / det), e11 = d00 / det;       // D^-1
+    const double h0 = e00 * ux + e01 * uy, h1 = e01 * ux + e11 * uy;         // D^-1 wp
+    if (FINAL) S[0] += (((d11 * n0) * n0 - ((2.0 * d01) * n0) * n1) + (d00 * n1) * n1) / det;      // nn_pair's d2
+    else { const double y0 = (d11 * n0 - d01 * n1) / det, y1 = (d00 * n1 - d01 * n0) / det;
+        S[1] += y0; S[2] += y1; S[3] += ux * y0 + uy * y1; }
+    S[4] += e00; S[5] += e01; S[6] += h0; S[7] += e11; S[8] += h1; S[9] += ux * h0 + uy * h1;
+    return true;
+}
+// the sums of the frame's live rows at the pose, in the fixed order: a lane's rows ascending from +0, then the butterfly inside the W lanes
+template <int SLOTS, bool FINAL>
+__device__ __forceinline__ int lo_sums(const LoRows<SLOTS> &R, const LoArgs &A, int live, int slots, int W, int lane, const double (&pose)[3], double (&S)[JC_TERMS]) {
+    double sn, cs; sincos(pose[2], &sn, &cs);
+    int cnt = 0;
+#pragma unroll
+    for (int t = 0; t < JC_TERMS; ++t) S[t] = 0.0;
+    for (int s = 0; s < slots; ++s)
+        if (live >> s & 1) { double v[LO_FIXED]; R.get(s, lane, v); cnt += lo_row<FINAL>(v, pose, sn, cs, A.p, S) ? 1 : 0; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        if (off >= W) continue;                                                // (wave-uniform) the butterfly stays inside the frame's W lanes
+        cnt += __shfl_xor(cnt, off, 64);
+#pragma unroll
+        for (int t = 0; t < JC_TERMS; ++t) S[t] += __shfl_xor(S[t], off, 64);
+    }
+    return cnt;
+}
+// a frame's record.  Status 4 (a refused frame): zeros, chi2 +inf
+__device__ __forceinline__ void lo_write(const LoArgs &A, int f, const double (&pose)[3], const double (&cv)[6], double chi2, int pairs, int iters, int status,
+                                         const double (&d)[3]) {
+    if (A.out_pose) { double *o = A.out_pose + 3 * (size_t)f; o[0] = pose[0]; o[1] = pose[1]; o[2] = pose[2]; }
+    if (A.out_cov) { double *o = A.out_cov + 9 * (size_t)f;                    // the upper triangle, mirrored
+        o[0] = cv[0]; o[1] = cv[1]; o[2] = cv[2]; o[3] = cv[1]; o[4] = cv[3]; o[5] = cv[4]; o[6] = cv[2]; o[7] = cv[4]; o[8] = cv[5]; }
+    if (A.out_chi2) A.out_chi2[f] = chi2;
+    if (A.out_pairs) A.out_pairs[f] = pairs;
+    if (A.out_iters) A.out_iters[f] = iters;
+    if (A.out_status) A.out_status[f] = status;
+    if (A.out_step) { double *o = A.out_step + 3 * (size_t)f; o[0] = d[0]; o[1] = d[1]; o[2] = d[2]; }
+}
+// one pass of a wave: lane group gi (W lanes, lane lg of it) localises the frame fw = [a, b) (fw < 0: none), b - a <= W (W < 64) or <= 64 * SLOTS
+template <int SLOTS>
+__device__ __forceinline__ void lo_pass(LoRows<SLOTS> &R, const LoArgs &A, int fw, int a, int b, int W, int lg, int lane) {
+#pragma clang fp contract(off)
+    const int k = fw < 0 ? 0 : b - a, slots = (k + 63) >> 6;
+    // the frame's pose, as jc_pass finds it
+    int plo = NN_NONE, phi = -1;
+    for (int s = 0; s < slots; ++s) { const int rl = s * 64 + lg;
+        if (rl < k) { const int pi = A.pose_of_obs[a + rl]; if (pi >= 0 && pi < A.n_poses) { plo = min(plo, pi); phi = max(phi, pi); } } }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        if (off >= W) continue;
+        plo = min(plo, __shfl_xor(plo, off, 64)); phi = max(phi, __shfl_xor(phi, off, 64));
+    }
+    const bool mixed = phi >= 0 && plo != phi, posed = phi >= 0 && !mixed;
+    const bool has_p = A.pose_cov != nullptr && posed;
+    double P[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, x0[3] = {0.0, 0.0, 0.0};
+    if (posed) { const double *ps = A.poses + 3 * (size_t)plo; x0[0] = ps[0]; x0[1] = ps[1]; x0[2] = ps[2]; }
+    if (has_p) { const double *pc = A.pose_cov + 9 * (size_t)plo; P[0] = pc[0]; P[1] = pc[1]; P[2] = pc[2]; P[3] = pc[4]; P[4] = pc[5]; P[5] = pc[8]; }
+    // FETCH
+    int live = 0;
+    for (int s = 0; s < slots; ++s) {
+        const int rl = s * 64 + lg;
+        if (rl < k && posed) {
+            const int i = a + rl, j = A.in_idx[i], pi = A.pose_of_obs[i];
+            if (j >= 0 && j < A.n_map && pi >= 0 && pi < A.n_poses) {
+                const double4 o4 = reinterpret_cast<const double4 *>(A.obs)[i];
+                const double2 z = nn_polar(o4.x, o4.y, o4.z, A.lidar), xy = reinterpret_cast<const double2 *>(A.map_xy)[j];
+                double v[LO_FIXED] = {z.x, z.y, xy.x, xy.y, 0.0, 0.0, 0.0};
+                if (A.map_cov) { const double4 cv = reinterpret_cast<const double4 *>(A.map_cov)[j]; v[4] = cv.x; v[5] = cv.y; v[6] = cv.w; }
+                R.put(s, lane, v); live |= 1 << s;
+            }
+        }
+    }
+    // ITERATE
+    double d[3] = {0.0, 0.0, 0.0}, x[3] = {0.0, 0.0, 0.0}, S[JC_TERMS];
+    int iters = 0, status = has_p ? 1 : posed ? 0 : 2; bool open = fw >= 0 && has_p;
+    for (int it = 0; it < A.max_it; ++it) {
+        if (__ballot(open) == 0) break;                                        // wave-uniform: every frame of the pass has stopped
+        double xk[3] = {x0[0], x0[1], x0[2]};
+        if (it > 0) { xk[0] = x0[0] + d[0]; xk[1] = x0[1] + d[1]; xk[2] = x0[2] + d[2]; }      // not normalised: sincos is periodic
+        const int cnt = lo_sums<SLOTS, false>(R, A, live, slots, W, lane, xk, S);
+        if (open && it == 0 && cnt == 0) { status = 2; open = false; }
+        if (open) {
+            if (it > 0) {                                                      // b = c + M d
+                const double b0 = S[1] + ((S[4] * d[0] + S[5] * d[1]) + S[6] * d[2]), b1 = S[2] + ((S[5] * d[0] + S[7] * d[1]) + S[8] * d[2]),
+                             b2 = S[3] + ((S[6] * d[0] + S[8] * d[1]) + S[9] * d[2]);
+                S[1] = b0; S[2] = b1; S[3] = b2; }
+            double xn[3], dn[3];
+            const double det = jc_step(S, P, xn, dn); ++iters;
+            if (!(isfinite(det) && isfinite(dn[0]) && isfinite(dn[1]) && isfinite(dn[2]))) { status = 3; open = false; }
+            else {
+                const bool conv = fabs(dn[0] - d[0]) <= A.tol_xy && fabs(dn[1] - d[1]) <= A.tol_xy && fabs(dn[2] - d[2]) <= A.tol_th;
+                d[0] = dn[0]; d[1] = dn[1]; d[2] = dn[2]; x[0] = xn[0]; x[1] = xn[1]; x[2] = xn[2];
+                if (conv) { status = 0; open = false; }
+            }
+        }
+    }
+    // FINAL
+    double xf[3] = {x0[0], x0[1], x0[2]};
+    if (iters > 0) { xf[0] = x0[0] + d[0]; xf[1] = x0[1] + d[1]; xf[2] = x0[2] + d[2]; }
+    const int pairs = lo_sums<SLOTS, true>(R, A, live, slots, W, lane, xf, S);
+    if (fw < 0 || lg != 0) return;
+    const double zero3[3] = {0.0, 0.0, 0.0}, zero6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (mixed) { lo_write(A, fw, zero3, zero6, __builtin_inf(), 0, 0, 4, zero3); return; }
+    if (status == 2) { lo_write(A, fw, x0, P, 0.0, 0, 0, 2, zero3); return; }  // (a frame without a pose: x0 and P are zeros)
+    double cv[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, chi2 = S[0];
+    if (has_p && status != 3) {
+        double K[9];
+        const double det = jc_cofactors(S, P, K);
+        if (!isfinite(det)) status = 3;
+        // Sigma+ = Sigma_p adj(A) / det A: entry (r, s) = sum_t P_rt C_st / det
+        cv[0] = ((P[0] * K[0] + P[1] * K[1]) + P[2] * K[2]) / det; cv[1] = ((P[0] * K[3] + P[1] * K[4]) + P[2] * K[5]) / det;
+        cv[2] = ((P[0] * K[6] + P[1] * K[7]) + P[2] * K[8]) / det; cv[3] = ((P[1] * K[3] + P[3] * K[4]) + P[4] * K[5]) / det;
+        cv[4] = ((P[1] * K[6] + P[3] * K[7]) + P[4] * K[8]) / det; cv[5] = ((P[2] * K[6] + P[4] * K[7]) + P[5] * K[8]) / det;
+        chi2 = S[0] + ((x[0] * d[0] + x[1] * d[1]) + x[2] * d[2]);
+    }
+    if (status == 3) { lo_write(A, fw, x0, P, __builtin_inf(), 0, iters, 3, zero3); return; }
+    xf[2] = lo_normalize_theta(xf[2]);                                         // k_update's addition and normalisation
+    lo_write(A, fw, xf, cv, chi2, pairs, iters, status, d);
+}
+// frame f of the call, as jc_frame: bounds outside 0 <= a <= b <= n: not a frame, nothing read or written; above GS_NN_FRAME_MAX (when
+// `refuse`): the record of a refused frame, and not a frame for the pass
+__device__ __forceinline__ bool lo_frame(const LoArgs &A, int f, bool refuse, int lg, int &a, int &b) {
+    a = A.frame_start[f]; b = A.frame_start[f + 1];
+    if (a < 0 || b < a || b > A.n) return false;
+    if (b - a <= 256) return true;
+    if (refuse && lg == 0) { const double zero3[3] = {0.0, 0.0, 0.0}, zero6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        lo_write(A, f, zero3, zero6, __builtin_inf(), 0, 0, 4, zero3); }
+    return false;
+}
+__global__ void __launch_bounds__(256) k_localize(LoArgs A) {
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int f0 = (blockIdx.x * 4 + w) * A.fpw;                               // this wave's frames: [f0, f0 + fpw), fpw in {2, 4, 8}
+    if (f0 >= A.n_frames) return;
+    int W = 64 / A.fpw;                                                        // as k_joint_compat; frames above 64 are k_localize_big's
+    for (int t = 0; t < A.fpw && f0 + t < A.n_frames; ++t) { const int a = A.frame_start[f0 + t], b = A.frame_start[f0 + t + 1];
+        if (a >= 0 && b >= a && b <= A.n && b - a <= 64) while (W < 64 && W < b - a) W <<= 1; }
+    const int gp = 64 / W, gi = lane >> __builtin_ctz(W), lg = lane & (W - 1);
+    for (int ps = 0; ps * gp < A.fpw; ++ps) {
+        int a = 0, b = 0, fw = -1; const int f = f0 + ps * gp + gi;
+        if (ps * gp + gi < A.fpw && f < A.n_frames && lo_frame(A, f, false, lg, a, b) && b - a <= 64) fw = f;
+        LoRows<1> R;
+        lo_pass<1>(R, A, fw, a, b, W, lg, lane);
+    }
+}
+__global__ void __launch_bounds__(64) k_localize_big(LoArgs A) {
+    __shared__ LoLds L;
+    const int lane = threadIdx.x, f0 = blockIdx.x * A.fpw;
+    LoRows<4> R{&L};
+    for (int t = 0; t < A.fpw && f0 + t < A.n_frames; ++t) {
+        int a, b;
+        if (!lo_frame(A, f0 + t, true, lane, a, b) || (A.only_large && b - a <= 64)) continue;      // (wave-uniform)
+        lo_pass<4>(R, A, f0 + t, a, b, 64, lane, lane);
+    }
+}
+
 void launch_assoc_nn(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, double lidar, int n_map,
                      const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
                      int32_t *out_idx, double *out_d2, double *out_second, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
@@ -806,6 +1045,22 @@ void launch_joint_compat(int n, const double *poses, int n_poses, const int32_t 
         A.fpw = 64; A.only_large = 1; start = nullptr;
     }
     hipExtLaunchKernelGGL(k_joint_compat_big, dim3((n_frames + A.fpw - 1) / A.fpw), dim3(64), 0, st, start, stop, 0, A);
+}
+void launch_localize(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, int n_frames, const int32_t *frame_start,
+                     double lidar, int n_map, const double *map_xy, const double *map_cov, const double *pose_cov, NnDev p, const LoParams &lp,
+                     const int32_t *in_idx, const LoOut &o, int kernel, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
+    if (n_frames <= 0) return;
+    // the kernels by the MEAN frame size, exactly as launch_joint_compat: it decides speed only.  kernel 0 / 1 (gs_debug_localize) forces
+    // k_localize (with k_localize_big behind it for the frames above 64) / k_localize_big alone
+    const long long mean = ((long long)n + n_frames - 1) / n_frames;
+    LoArgs A{n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, 1, 0, lidar, n_map, map_xy, map_cov, pose_cov, p, in_idx, lp.max_iterations, lp.tol_xy,
+             lp.tol_theta, o.pose, o.cov, o.chi2, o.n_pairs, o.iterations, o.status, o.step};
+    if (kernel == 0 || (kernel < 0 && mean <= 32)) {
+        A.fpw = mean <= 8 ? 8 : mean <= 16 ? 4 : 2;
+        hipExtLaunchKernelGGL(k_localize, dim3((n_frames + 4 * A.fpw - 1) / (4 * A.fpw)), dim3(256), 0, st, start, nullptr, 0, A);
+        A.fpw = 64; A.only_large = 1; start = nullptr;
+    }
+    hipExtLaunchKernelGGL(k_localize_big, dim3((n_frames + A.fpw - 1) / A.fpw), dim3(64), 0, st, start, stop, 0, A);
 }
 
 }  // namespace gs

@@ -48,5 +48,14 @@ void launch_joint_compat(int n, const double *poses, int n_poses, const int32_t 
                          double lidar, int n_map, const double *map_xy, const double *map_cov, const double *pose_cov, NnDev p, const JcGate &gate,
                          const int32_t *in_idx, int32_t *out_idx, double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable,
                          double *out_delta, hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+// frame localisation under the hypothesis in_idx inside the same frames: per frame the pose [3], its covariance [9], chi2, the pairs counted,
+// the solves made and the status (each may be null); step: d_f [3] per frame (gs_debug_localize's output, null as a rule).  Only p's sigmas are
+// read.  Defences as launch_joint_compat: a frame above GS_NN_FRAME_MAX or with two pose indices gets status 4.  kernel: -1 by the mean frame
+// size, 0 / 1 forces the small / the large kernel (results do not depend on it)
+struct LoParams { int max_iterations; double tol_xy, tol_theta; };
+struct LoOut { double *pose, *cov, *chi2; int32_t *n_pairs, *iterations, *status; double *step; };
+void launch_localize(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, int n_frames, const int32_t *frame_start,
+                     double lidar, int n_map, const double *map_xy, const double *map_cov, const double *pose_cov, NnDev p, const LoParams &lp,
+                     const int32_t *in_idx, const LoOut &o, int kernel, hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
 }  // namespace gs

@@ -55,6 +55,8 @@ void gs_frontend_release(gs_graph *g) {      // gs_destroy
     if (g->fe.nn_dev_out) hipFree(g->fe.nn_dev_out);
     if (g->fe.jc_pin_out) hipHostFree(g->fe.jc_pin_out);
     if (g->fe.jc_dev_out) hipFree(g->fe.jc_dev_out);
+    if (g->fe.lo_pin_out) hipHostFree(g->fe.lo_pin_out);
+    if (g->fe.lo_dev_out) hipFree(g->fe.lo_dev_out);
     g->fe = gs_graph::FrontEnd();
 }
 
@@ -841,5 +843,175 @@ extern "C" int gs_frame_frontend_jc(gs_graph *g, const double pose[3], const dou
     if (out_kept) std::memcpy(out_kept, pj + 32, sizeof(int32_t));
     if (out_dropped) std::memcpy(out_dropped, pj + 36, sizeof(int32_t));
     if (out_untestable) std::memcpy(out_untestable, pj + 40, sizeof(int32_t));
+    return GS_OK;
+}
+
+// ---- frame localisation (gs_assoc_nn.hip, k_localize): the iterated pose refinement of a frame against the map — batch / resident / frame calls ----
+extern "C" int gs_loc_params_default(gs_loc_params *p) {
+    if (!p) return fail(GS_ERR_INVALID, "null params");
+    std::memset(p, 0, sizeof(*p)); p->struct_size = (int32_t)sizeof(*p);
+    p->max_iterations = 5; p->tol_xy = 1e-6; p->tol_theta = 1e-8;
+    return GS_OK;
+}
+static int loc_params_check(const gs_loc_params *p, LoParams &lp) {
+    if (!p) return fail(GS_ERR_INVALID, "null params");
+    if (p->struct_size != (int32_t)sizeof(gs_loc_params)) return fail(GS_ERR_INVALID, "gs_loc_params: wrong struct_size");
+    if (p->max_iterations < 1 || p->max_iterations > GS_LOC_ITER_MAX) return fail(GS_ERR_INVALID, "gs_loc_params: max_iterations outside 1 .. GS_LOC_ITER_MAX");
+    if (!std::isfinite(p->tol_xy) || p->tol_xy < 0.0 || !std::isfinite(p->tol_theta) || p->tol_theta < 0.0)
+        return fail(GS_ERR_INVALID, "gs_loc_params: a tolerance is not finite or negative");
+    lp = LoParams{p->max_iterations, p->tol_xy, p->tol_theta};
+    return GS_OK;
+}
+extern "C" int gs_debug_localize(gs_graph *g, int32_t kernel, double *dev_out_step_3) {
+    if (!g || kernel < -1 || kernel > 1) return fail(GS_ERR_INVALID, "bad argument");
+    g->fe.lo_kernel = kernel; g->fe.lo_step = dev_out_step_3;
+    return GS_OK;
+}
+extern "C" int gs_localize_batch(gs_graph *g, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs, const double *obs,
+                                 int32_t n_frames, const int32_t *frame_start, int32_t n_map, const double *map_xy, const double *map_cov,
+                                 const double *pose_cov, const gs_nn_params *params, const gs_loc_params *loc, const int32_t *in_index,
+                                 double *out_pose, double *out_cov, double *out_chi2, int32_t *out_pairs, int32_t *out_iters, int32_t *out_status) {
+    if (!g || n < 0 || npose < 0 || n_map < 0 || (n > 0 && (!poses || !pose_of_obs || !obs || !in_index)) || (n_map > 0 && !map_xy))
+        return fail(GS_ERR_INVALID, "bad argument");
+    NnDev nd; int rc = jc_sigmas_check(params, nd); if (rc != GS_OK) return rc;
+    LoParams lp; if ((rc = loc_params_check(loc, lp)) != GS_OK) return rc;
+    if ((rc = frame_start_check(n, n_frames, frame_start)) != GS_OK) return rc;
+    for (int i = 0; i < n; ++i) {
+        if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
+        if (in_index[i] < -1 || in_index[i] >= n_map) return fail(GS_ERR_INVALID, "in_index outside [-1, n_map)"); }
+    for (int f = 0; f < n_frames; ++f)
+        for (int i = frame_start[f] + 1; i < frame_start[f + 1]; ++i)
+            if (pose_of_obs[i] != pose_of_obs[frame_start[f]]) return fail(GS_ERR_INVALID, "the observations of a frame must share one pose");
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n_frames == 0) return GS_OK;
+    const size_t nf = (size_t)n_frames;
+    if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(9 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded(nf + 1, 4) +
+                               padded(2 * (size_t)n_map, 8) + padded(4 * (size_t)n_map, 8) + padded(n, 4) + padded(3 * nf, 8) + padded(9 * nf, 8) + padded(nf, 8) +
+                               3 * padded(nf, 4))) != GS_OK) return rc;
+    Carver c{g}; double *p = c.get<double>(3 * (size_t)npose), *pcv = c.get<double>(9 * (size_t)npose); int32_t *po = c.get<int32_t>(n);
+    double *ob = c.get<double>(4 * (size_t)n); int32_t *fs = c.get<int32_t>(nf + 1);
+    double *mx = c.get<double>(2 * (size_t)n_map), *mc = c.get<double>(4 * (size_t)n_map);
+    int32_t *ii = c.get<int32_t>(n); double *op = c.get<double>(3 * nf), *oc = c.get<double>(9 * nf), *ox = c.get<double>(nf);
+    int32_t *on = c.get<int32_t>(nf), *oi = c.get<int32_t>(nf), *os = c.get<int32_t>(nf);
+    if (npose > 0) HIP_TRY(hipMemcpyAsync(p, poses, 3 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
+    if (pose_cov && npose > 0) HIP_TRY(hipMemcpyAsync(pcv, pose_cov, 9 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
+    if (n > 0) { HIP_TRY(hipMemcpyAsync(po, pose_of_obs, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
+                 HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
+                 HIP_TRY(hipMemcpyAsync(ii, in_index, (size_t)n * 4, hipMemcpyHostToDevice, g->stream)); }
+    HIP_TRY(hipMemcpyAsync(fs, frame_start, (nf + 1) * 4, hipMemcpyHostToDevice, g->stream));
+    if (n_map > 0) { HIP_TRY(hipMemcpyAsync(mx, map_xy, 2 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream));
+                     if (map_cov) HIP_TRY(hipMemcpyAsync(mc, map_cov, 4 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream)); }
+    launch_localize(n, p, npose, po, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, map_cov ? mc : nullptr, pose_cov ? pcv : nullptr, nd, lp, ii,
+                    LoOut{op, oc, ox, on, oi, os, nullptr}, g->fe.lo_kernel, g->stream);
+    if (out_pose) HIP_TRY(hipMemcpyAsync(out_pose, op, 3 * nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, oc, 9 * nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    if (out_chi2) HIP_TRY(hipMemcpyAsync(out_chi2, ox, nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    if (out_pairs) HIP_TRY(hipMemcpyAsync(out_pairs, on, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (out_iters) HIP_TRY(hipMemcpyAsync(out_iters, oi, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (out_status) HIP_TRY(hipMemcpyAsync(out_status, os, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));        // the one wait of the call: the result copies
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("frame localisation: ") + hipGetErrorString(e));
+    return GS_OK;
+}
+extern "C" int gs_localize_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
+                                    int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov, const gs_nn_params *params,
+                                    const gs_loc_params *loc, const int32_t *dev_in_index, double *dev_out_pose, double *dev_out_cov, double *dev_out_chi2,
+                                    int32_t *dev_out_pairs, int32_t *dev_out_iters, int32_t *dev_out_status) {
+    if (!g || n < 0 || npose < 0 || n_frames < 0 || !dev_frame_start || (n > 0 && (!dev_poses || !dev_pose_of_obs || !dev_obs || !dev_in_index)))
+        return fail(GS_ERR_INVALID, "bad argument");
+    NnDev nd; int rc = jc_sigmas_check(params, nd); if (rc != GS_OK) return rc;
+    LoParams lp; if ((rc = loc_params_check(loc, lp)) != GS_OK) return rc;
+    if (((uintptr_t)dev_obs & 31) != 0) return fail(GS_ERR_INVALID, "dev_obs must be 32-byte aligned (an observation is read in one load)");
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n_frames == 0) return GS_OK;
+    auto &fe = g->fe;
+    launch_localize(n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_cov, dev_pose_cov,
+                    nd, lp, dev_in_index, LoOut{dev_out_pose, dev_out_cov, dev_out_chi2, dev_out_pairs, dev_out_iters, dev_out_status, fe.lo_step}, fe.lo_kernel,
+                    g->stream, g->ev_lin[0], g->ev_lin[1]);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("frame localisation: ") + hipGetErrorString(e));
+    return GS_OK;
+}
+// the twin of gs_debug_time_joint_compat_resident
+extern "C" int gs_debug_time_localize_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
+                                               const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov,
+                                               const gs_nn_params *params, const gs_loc_params *loc, const int32_t *dev_in_index, double *dev_out_pose,
+                                               double *dev_out_cov, double *dev_out_chi2, int32_t *dev_out_pairs, int32_t *dev_out_iters, int32_t *dev_out_status,
+                                               int32_t reps, double *out_ms) {
+    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
+    auto once = [&] { return gs_localize_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, loc, dev_in_index,
+                                                  dev_out_pose, dev_out_cov, dev_out_chi2, dev_out_pairs, dev_out_iters, dev_out_status); };
+    int rc = once(); if (rc != GS_OK) return rc;                    // warm
+    std::vector<hipEvent_t> ev(2 * (size_t)reps); for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    for (int r = 0; r < reps && rc == GS_OK; ++r) { g->ev_lin[0] = ev[2 * (size_t)r]; g->ev_lin[1] = ev[2 * (size_t)r + 1]; rc = once(); }
+    g->ev_lin[0] = g->ev_lin[1] = nullptr;
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    double tot = 0; int cnt = 0;
+    for (int r = 0; r < reps; ++r) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]) == hipSuccess && ms > 0) { tot += ms; ++cnt; } }
+    (void)hipGetLastError();
+    for (auto &e : ev) hipEventDestroy(e);
+    *out_ms = cnt ? tot / cnt : 0.0;
+    return rc;
+}
+// one frame: the minimum-cost assignment, the joint test of its result and the localisation under the PRUNED index, back to back on the stream.
+// Record staging (bytes): the joint test's as in gs_frame_frontend_jc (J 0, delta 8, counts 32, pruned index 48), then at LO_REC the pose, at
+// + 24 its covariance, + 96 chi2, + 104 pairs / iterations / status
+extern "C" int gs_frame_frontend_localize(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
+                                          const gs_jc_params *jc, const gs_loc_params *loc, double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2,
+                                          int32_t *out_na, double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable, double *out_delta,
+                                          double *out_pose, double *out_cov, double *out_chi2, int32_t *out_pairs, int32_t *out_iters, int32_t *out_status) {
+    if (!g || !pose || k < 0 || (k > 0 && (!obs || !out_zxy || !out_gxy || !out_idx || !out_d2))) return fail(GS_ERR_INVALID, "bad argument");
+    NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
+    JcGate gt; if ((rc = jc_params_check(jc, gt)) != GS_OK) return rc;
+    LoParams lp; if ((rc = loc_params_check(loc, lp)) != GS_OK) return rc;
+    if (k > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations");
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (k == 0) {                                                   // the empty frame's records, without a launch: no pair, the prior's bits
+        if (out_j) *out_j = 0.0;
+        if (out_kept) *out_kept = 0;
+        if (out_dropped) *out_dropped = 0;
+        if (out_untestable) *out_untestable = 0;
+        if (out_delta) out_delta[0] = out_delta[1] = out_delta[2] = 0.0;
+        if (out_pose) std::memcpy(out_pose, pose, 3 * sizeof(double));
+        if (out_cov) { const int up[9] = {0, 1, 2, 1, 4, 5, 2, 5, 8}; for (int t = 0; t < 9; ++t) out_cov[t] = pose_cov ? pose_cov[up[t]] : 0.0; }
+        if (out_chi2) *out_chi2 = 0.0;
+        if (out_pairs) *out_pairs = 0;
+        if (out_iters) *out_iters = 0;
+        if (out_status) *out_status = 2;
+        return GS_OK; }
+    auto &fe = g->fe; FrameDev fd;
+    constexpr size_t LO_REC = 48 + (size_t)GS_NN_FRAME_MAX * sizeof(int32_t), lbytes = LO_REC + 120;
+    if (!fe.lo_dev_out) {                                           // once per handle: the size does not depend on k
+        HIP_TRY(hipHostMalloc((void **)&fe.lo_pin_out, lbytes, hipHostMallocDefault)); HIP_TRY(hipMalloc((void **)&fe.lo_dev_out, lbytes)); }
+    if ((rc = frame_assign_enqueue(g, true, pose, pose_cov, obs, k, nd, fd)) != GS_OK) return rc;
+    char *jd = fe.lo_dev_out, *ld = fe.lo_dev_out + LO_REC;
+    launch_joint_compat(k, fd.pose, 1, fd.pose_of_obs, fd.obs, 1, fd.frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_cov, fd.pose_cov, nd, gt, fd.idx,
+                        (int32_t *)(jd + 48), (double *)jd, (int32_t *)(jd + 32), (int32_t *)(jd + 36), (int32_t *)(jd + 40), (double *)(jd + 8), g->stream);
+    launch_localize(k, fd.pose, 1, fd.pose_of_obs, fd.obs, 1, fd.frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_cov, fd.pose_cov, nd, lp,
+                    (const int32_t *)(jd + 48), LoOut{(double *)ld, (double *)(ld + 24), (double *)(ld + 96), (int32_t *)(ld + 104), (int32_t *)(ld + 108),
+                    (int32_t *)(ld + 112), nullptr}, fe.lo_kernel, g->stream);
+    const size_t bz = (size_t)k * 2 * sizeof(double), bd = (size_t)k * sizeof(double), bi = (size_t)k * sizeof(int32_t);
+    HIP_TRY(hipMemcpyAsync(fe.as_pin_out, fe.as_dev_out, fd.out_bytes, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(fe.lo_pin_out, fe.lo_dev_out, lbytes, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));                       // the one wait of the call
+    fe.pin_map_busy = false;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("frame localisation: ") + hipGetErrorString(e));
+    const char *po = fe.as_pin_out, *pj = fe.lo_pin_out, *pl = fe.lo_pin_out + LO_REC;
+    std::memcpy(out_zxy, po, bz); std::memcpy(out_gxy, po + bz, bz); std::memcpy(out_d2, po + 2 * bz, bd);
+    if (out_na) std::memcpy(out_na, po + 2 * bz + bd + bi, bi);
+    std::memcpy(out_idx, pj + 48, bi);
+    if (out_j) std::memcpy(out_j, pj, sizeof(double));
+    if (out_delta) std::memcpy(out_delta, pj + 8, 3 * sizeof(double));
+    if (out_kept) std::memcpy(out_kept, pj + 32, sizeof(int32_t));
+    if (out_dropped) std::memcpy(out_dropped, pj + 36, sizeof(int32_t));
+    if (out_untestable) std::memcpy(out_untestable, pj + 40, sizeof(int32_t));
+    if (out_pose) std::memcpy(out_pose, pl, 3 * sizeof(double));
+    if (out_cov) std::memcpy(out_cov, pl + 24, 9 * sizeof(double));
+    if (out_chi2) std::memcpy(out_chi2, pl + 96, sizeof(double));
+    if (out_pairs) std::memcpy(out_pairs, pl + 104, sizeof(int32_t));
+    if (out_iters) std::memcpy(out_iters, pl + 108, sizeof(int32_t));
+    if (out_status) std::memcpy(out_status, pl + 112, sizeof(int32_t));
     return GS_OK;
 }

@@ -76,6 +76,9 @@ struct gs_graph {
         char *as_pin_in = nullptr, *as_dev_in = nullptr, *as_pin_out = nullptr, *as_dev_out = nullptr; int as_cap_obs = 0;
         // joint compatibility: the frame call's record and pruned index (null until gs_frame_frontend_jc is called; sized for GS_NN_FRAME_MAX)
         char *jc_pin_out = nullptr, *jc_dev_out = nullptr;
+        // frame localisation: the frame call's record (null until gs_frame_frontend_localize is called; a fixed size); gs_debug_localize's
+        // kernel choice (-1: by the mean frame size) and step output (a device pointer of the caller's, or null)
+        char *lo_pin_out = nullptr, *lo_dev_out = nullptr; int lo_kernel = -1; double *lo_step = nullptr;
     } fe;
     bool tree_proven = false;               // a whole-tree launch sequence of the CURRENT plan has completed without a flag timeout (gs_optimize then sends all iterations of a call at once)
     bool fell_back = false;                 // a whole-tree launch gave up on a flag: this handle uses one launch per level — until the next plan, or until a retry (below) comes back clean
