@@ -864,7 +864,7 @@ int  gs_frame_frontend_assign_opt(gs_graph *g, const double pose_xytheta[3], con
  *      fixed record buffer of its own from the first call on: nothing is allocated per call after that.
  * A handle that never calls any of these allocates and launches nothing for them; the calls above are unchanged by them.
  * NOT DONE: pose-cone and cone-cone cross-covariances; JCBB's search over alternative cones — this PRUNES a given hypothesis, it does not
- *      re-match; the posterior pose covariance (frame localisation, below, returns it); frames of more than GS_NN_FRAME_MAX observations; sharded handles (nothing beyond what the
+ *      re-match (a search over alternative cones WITHOUT a prior pose is "relocalisation", further below); the posterior pose covariance (frame localisation, below, returns it); frames of more than GS_NN_FRAME_MAX observations; sharded handles (nothing beyond what the
  *      gs_associate_nn_* calls give); the Slam mirror and the shell, which keep the Euclidean rule. */
 typedef struct gs_jc_params {
     int32_t struct_size;
@@ -943,7 +943,8 @@ int  gs_frame_frontend_jc(gs_graph *g, const double pose_xytheta[3], const doubl
  *      own from the first call on.  To chain frames, the caller adds its motion noise to out_cov before it is the next frame's pose_cov.
  * A handle that never calls any of these allocates and launches nothing for them; the calls above are unchanged by them.
  * NOT DONE: the Slam mirror and the shell stay as they are (the reference's localizer reports the raw odometry pose); no prior-free (maximum-
- *      likelihood) solve — a wide Sigma_p serves; no cross-covariances; no re-matching (the hypothesis is the caller's throughout); no sharded
+ *      likelihood) solve — a wide Sigma_p serves, and "relocalisation" (below) finds a pose from the frame and the map alone; no cross-covariances;
+ *      no re-matching (the hypothesis is the caller's throughout; relocalisation, below, searches the cones for one); no sharded
  *      handles; no frames above GS_NN_FRAME_MAX observations. */
 #define GS_LOC_ITER_MAX 16
 typedef struct gs_loc_params {
@@ -966,6 +967,95 @@ int  gs_frame_frontend_localize(gs_graph *g, const double pose_xytheta[3], const
                                 int32_t *out_index, double *out_d2, int32_t *out_n_admissible, double *out_joint_d2, int32_t *out_n_kept,
                                 int32_t *out_n_dropped, int32_t *out_n_untestable, double *out_delta_3, double *out_pose_3, double *out_cov_3x3,
                                 double *out_chi2, int32_t *out_n_pairs, int32_t *out_iterations, int32_t *out_status);
+
+/* ---- relocalisation: a frame's pose found on the map without a prior ---------------------------------------------------
+ * Every call above starts from a pose that is roughly right: max_distance and the chi-square gate only admit a cone near where the prior puts
+ * it.  After a restart on a saved map, a GPS jump, a spin or drift at the loop closure the prior is wrong and the chain matches nothing, or
+ * the neighbouring cones of a self-similar track.  These calls find, from ONE frame and the map alone, the rigid pose under which the most
+ * observations land on type-compatible cones, and report the best count at a clearly DIFFERENT pose, because tracks repeat themselves and
+ * the caller must be able to see that.  The reference's localizer (src/slam.cpp:340-414) trusts the odometry pose: the rule is build-defined.
+ * No contraction anywhere; only + - * / sqrt and comparisons, up to the one final atan2.
+ *
+ * Frames and observations.  Frames are runs of observations (frame_start), at most GS_NN_FRAME_MAX each, collector layout 4 x n.  z_i = the
+ *      CoG-frame XY by the A0 formula (quirks included), r2_i = zx zx + zy zy, ty_i = the type.  An observation is VALID iff zx and zy are
+ *      finite and r2 > 0.  No pose is read: there is no poses or pose_of_obs argument.
+ * Seed observations.  The frame's valid observations with the seed_obs smallest keys (r2, index): the closest cones are the best measured.
+ * Seed pairs.  All (u, v) with u < v (positions in the call's arrays) among the seed observations:  dz = z_v - z_u,
+ *      L2 = (dzx dzx) + (dzy dzy),  L = sqrt(L2).  The pair is kept iff L >= min_baseline.
+ * Seeds.  For every kept (u, v), every ordered map pair (p, q), p != q, with |type_p - ty_u| < type_tol and |type_q - ty_v| < type_tol:
+ *      dl = l_q - l_p,  M2 = (dlx dlx) + (dly dly),  M = sqrt(M2);  the lengths must match: |M - L| <= length_tol.  Then
+ *      den = sqrt(L2 M2),  c = ((dzx dlx) + (dzy dly)) / den,  s = ((dzx dly) - (dzy dlx)) / den,
+ *      mz = (0.5 (zx_u + zx_v), 0.5 (zy_u + zy_v)),  ml = (0.5 (lx_p + lx_q), 0.5 (ly_p + ly_q)),
+ *      t = (mlx - ((c mzx) - (s mzy)),  mly - ((s mzx) + (c mzy))).
+ *      The seed EXISTS iff den > 0 and c, s, tx, ty are all finite.  All tests are positive tests: a NaN cone or query takes part in nothing.
+ * Score of a seed.  For every valid observation i of the frame (not only the seed observations), in ascending i:
+ *      w = (((c zx) - (s zy)) + tx,  ((s zx) + (c zy)) + ty);  among the cones j with |type_j - ty_i| < type_tol the one of smallest
+ *      e2 = (ex ex) + (ey ey), ex = lx - wx, ey = ly - wy, exact ties to the lowest j;  i is an INLIER iff that e2 < inlier_radius inlier_radius
+ *      (the product formed once, on the host).  count = the inliers;  cost = their e2 added from +0 in ascending i.
+ *      A cone may serve two observations: uniqueness is the job of the assignment calls that follow, not of the score.
+ * Winner.  The seed with the smallest key (-count, cost, u, v, p, q).  The key is strict and total: the result does not depend on how the
+ *      device gets there.
+ * Runner-up.  The smallest key among the seeds that are NOT NEAR the winner (c*, s*, t*).  A seed is near iff
+ *      ((dx dx) + (dy dy)) < distinct_xy distinct_xy, dx = tx - tx*, dy = ty - ty*,  AND  ((c c*) + (s s*)) > distinct_cos.
+ *      The angle is passed as a cosine so that no libm call sits between the caller's number and the comparison.
+ * Outputs per frame, each pointer may be NULL:  pose[3] = (tx, ty, atan2(s, c));  count;  cost;  seed[4] = (u, v, p, q);
+ *      second_count and second_pose[3] (0 and zeros when there is none);  n_seeds (int64) = the seeds that existed;  status:
+ *      0 found, count >= min_inliers.  1 the best seed is below min_inliers; the record is written all the same.  2 no seed: pose zeros, counts
+ *      0, cost +inf, seed (-1, -1, -1, -1).  4 refused (resident defences): as 2.
+ * Outputs per observation (may be NULL):  index = the inlier's cone under the winner, else -1;  e2 = its e2, else +inf.
+ * Consequences.  Frames are independent.  Batch, resident and frame call, with either scoring search, return identical bits.
+ *
+ * gs_reloc_params_default fills the struct.  Refused (GS_ERR_INVALID) before the device is touched: a wrong struct_size; seed_obs outside
+ *      2 .. GS_RELOC_SEED_MAX; min_inliers < 2; min_baseline, length_tol, inlier_radius or distinct_xy not finite or not positive; type_tol not
+ *      finite; distinct_cos outside [-1, 1].
+ * gs_relocalize_batch: host arrays; frame_start as gs_assign_nn_batch checks it (begins at 0, ascends, ends at n, no frame above
+ *      GS_NN_FRAME_MAX).  The score searches the hashed grid (cell edge from inlier_radius, nine buckets) from 2048 cones and the whole map
+ *      below; gs_debug_options.assoc_grid forces either.  A host-only handle: GS_ERR_NO_DEVICE.
+ * gs_relocalize_resident: everything in DEVICE memory against the resident map, asynchronous on the handle's stream, no wait.  dev_obs must
+ *      be 32-byte aligned.  The kernels defend themselves: a frame whose bounds are not 0 <= a <= b <= n reads and writes nothing; a frame
+ *      above GS_NN_FRAME_MAX gets status 4 and -1 / +inf per observation; observations that no frame covers are not written.  The grid (a
+ *      second one beside the association's, so that the two cell edges do not evict each other) is used unless assoc_grid == 0.
+ * gs_frame_frontend_relocalize: one frame: the search, then the chain of gs_frame_frontend_localize (assignment -> joint test ->
+ *      localisation) from the found pose under the prior covariance diag(prior_sigma_xy^2, prior_sigma_xy^2, prior_sigma_theta^2) — all
+ *      enqueued back to back, one wait: the search's last kernel writes the pose into the frame record the chain reads.  It returns the search
+ *      record and every output of gs_frame_frontend_localize, bitwise what that call returns for the returned pose and this prior.  With
+ *      status 2 the search's last kernel EMPTIES the frame the chain reads, so the chain touches no observation: its per-observation outputs are
+ *      then zeros / -1 / +inf / 0 and its records those of an empty frame.  k == 0: nothing is launched, status 2.  k above GS_NN_FRAME_MAX,
+ *      a sigma that is negative or not finite: GS_ERR_INVALID.
+ * A handle that never calls any of these allocates and launches nothing for them; the calls above are unchanged by them.  The record buffers
+ *      exist from the first call on and only grow.
+ * NOT DONE: one-to-one inside the score (above); cross-covariances; pruning the map-pair enumeration with a coarse grid (every ordered cone
+ *      pair is met: n_map^2 length tests a frame); the Slam mirror and the shell; sharded handles; frames above GS_NN_FRAME_MAX. */
+#define GS_RELOC_SEED_MAX 16
+typedef struct gs_reloc_params {
+    int32_t struct_size;
+    int32_t seed_obs;        /* 12; 2 .. GS_RELOC_SEED_MAX */
+    int32_t min_inliers;     /* 4; >= 2 */
+    int32_t reserved;
+    double min_baseline;     /* 2.0 m */
+    double length_tol;       /* 0.3 m */
+    double inlier_radius;    /* 0.5 m */
+    double type_tol;         /* 1e-4 */
+    double distinct_xy;      /* 2.0 m */
+    double distinct_cos;     /* 0.98006657784124163 = cos 0.2 */
+} gs_reloc_params;
+int  gs_reloc_params_default(gs_reloc_params *p);
+int  gs_relocalize_batch(gs_graph *g, int32_t n, const double *obs_4xn, int32_t n_frames, const int32_t *frame_start, int32_t n_map,
+                         const double *map_xy, const int32_t *map_type, const gs_reloc_params *params, double *out_pose_3, int32_t *out_count,
+                         double *out_cost, int32_t *out_seed_4, int32_t *out_second_count, double *out_second_pose_3, int64_t *out_n_seeds,
+                         int32_t *out_status, int32_t *out_index, double *out_e2);
+int  gs_relocalize_resident(gs_graph *g, int32_t n, const double *dev_obs_4xn, int32_t n_frames, const int32_t *dev_frame_start,
+                            const gs_reloc_params *params, double *dev_out_pose_3, int32_t *dev_out_count, double *dev_out_cost,
+                            int32_t *dev_out_seed_4, int32_t *dev_out_second_count, double *dev_out_second_pose_3, int64_t *dev_out_n_seeds,
+                            int32_t *dev_out_status, int32_t *dev_out_index, double *dev_out_e2);
+int  gs_frame_frontend_relocalize(gs_graph *g, const double *obs_4xk, int32_t k, const gs_reloc_params *reloc, double prior_sigma_xy,
+                                  double prior_sigma_theta, const gs_nn_params *params, const gs_jc_params *jc, const gs_loc_params *loc,
+                                  double *out_reloc_pose_3, int32_t *out_reloc_count, double *out_reloc_cost, int32_t *out_reloc_seed_4,
+                                  int32_t *out_second_count, double *out_second_pose_3, int64_t *out_n_seeds, int32_t *out_reloc_status,
+                                  int32_t *out_reloc_index, double *out_reloc_e2, double *out_zxy, double *out_gxy, int32_t *out_index,
+                                  double *out_d2, int32_t *out_n_admissible, double *out_joint_d2, int32_t *out_n_kept, int32_t *out_n_dropped,
+                                  int32_t *out_n_untestable, double *out_delta_3, double *out_pose_3, double *out_cov_3x3, double *out_chi2,
+                                  int32_t *out_n_pairs, int32_t *out_iterations, int32_t *out_status);
 
 /* ---- multi-GPU: pose-window shards -----------------------------
  * Each rank owns a contiguous pose window and builds the SAME global plan; it linearises and

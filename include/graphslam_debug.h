@@ -122,6 +122,16 @@ int gs_debug_time_localize_resident(gs_graph *g, int32_t n, const double *dev_po
                                     const gs_nn_params *params, const gs_loc_params *loc, const int32_t *dev_in_index, double *dev_out_pose_3,
                                     double *dev_out_cov_3x3, double *dev_out_chi2, int32_t *dev_out_n_pairs, int32_t *dev_out_iterations,
                                     int32_t *dev_out_status, int32_t reps, double *out_ms);
+/* Relocalisation.  gs_debug_relocalize: slice_cones > 0 forces how many cones p a workgroup of the seed kernel enumerates (a frame then has
+ * ceil(map size / slice_cones) records for the pick kernel to reduce), 0 (default) lets the launcher choose — in all three calls; results do
+ * not depend on it.  gs_debug_time_relocalize_resident: `reps` launches of gs_relocalize_resident (the grid built before), events from its
+ * first dispatch to its last; mean milliseconds per call. */
+int gs_debug_relocalize(gs_graph *g, int32_t slice_cones);
+int gs_debug_time_relocalize_resident(gs_graph *g, int32_t n, const double *dev_obs_4xn, int32_t n_frames, const int32_t *dev_frame_start,
+                                      const gs_reloc_params *params, double *dev_out_pose_3, int32_t *dev_out_count, double *dev_out_cost,
+                                      int32_t *dev_out_seed_4, int32_t *dev_out_second_count, double *dev_out_second_pose_3,
+                                      int64_t *dev_out_n_seeds, int32_t *dev_out_status, int32_t *dev_out_index, double *dev_out_e2,
+                                      int32_t reps, double *out_ms);
 /* Measurement hook of the sharded iteration (bench.py's `ms_exchange`): `reps` RCCL all-reduces of the exchange buffer back to back on the
  * handle's stream, HIP events around them; mean ms per all-reduce.  Collective: every rank of the communicator calls it. */
 int gs_debug_time_exchange(gs_graph *g, int32_t reps, double *out_ms);

@@ -184,6 +184,34 @@ def _loc_record(n_frames):
             "iterations": np.zeros(n_frames, dtype=np.int32), "status": np.zeros(n_frames, dtype=np.int32)}
 
 
+RELOC_SEED_MAX = 16                                         # GS_RELOC_SEED_MAX
+
+
+class RelocParams(C.Structure):
+    """gs_reloc_params (include/graphslam.h): the seeds, the tolerances and what counts as a different pose in relocalisation"""
+    _fields_ = [("struct_size", C.c_int32), ("seed_obs", C.c_int32), ("min_inliers", C.c_int32), ("reserved", C.c_int32), ("min_baseline", C.c_double),
+                ("length_tol", C.c_double), ("inlier_radius", C.c_double), ("type_tol", C.c_double), ("distinct_xy", C.c_double), ("distinct_cos", C.c_double)]
+
+
+def reloc_params(**kw):
+    """the library's gs_reloc_params defaults, with the named fields changed"""
+    p = RelocParams(); L = lib()
+    rc = L.gs_reloc_params_default(C.byref(p))
+    if rc != GS_OK:
+        raise GsError(rc, (L.gs_last_error() or b"").decode())
+    for k, v in kw.items():
+        if k not in dict(RelocParams._fields_) or k == "reserved":
+            raise AttributeError("gs_reloc_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _reloc_record(n_frames):
+    return {"pose": np.zeros((n_frames, 3)), "count": np.zeros(n_frames, dtype=np.int32), "cost": np.zeros(n_frames), "seed": np.zeros((n_frames, 4), dtype=np.int32),
+            "second_count": np.zeros(n_frames, dtype=np.int32), "second_pose": np.zeros((n_frames, 3)), "n_seeds": np.zeros(n_frames, dtype=np.int64),
+            "status": np.zeros(n_frames, dtype=np.int32)}
+
+
 class DoglegParams(C.Structure):
     """gs_dogleg_params (include/graphslam.h)"""
     _fields_ = [("struct_size", C.c_int32), ("max_trials_after_failure", C.c_int32), ("initial_delta", C.c_double)]
@@ -377,6 +405,15 @@ def lib():
         L.gs_localize_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, lpp, vp, vp, vp, vp, vp, vp, vp]
         L.gs_debug_time_localize_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, lpp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, _dp]
         L.gs_frame_frontend_localize.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, jpp, lpp, _dp, _dp, _ip, _dp, _ip, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
+    if hasattr(L, "gs_relocalize_batch"):                  # (and for relocalisation)
+        npp = C.POINTER(NnParams); jpp = C.POINTER(JcParams); lpp = C.POINTER(LocParams); rpp = C.POINTER(RelocParams); _lp = C.POINTER(C.c_int64)
+        L.gs_reloc_params_default.argtypes = [rpp]
+        L.gs_debug_relocalize.argtypes = [vp, C.c_int32]
+        L.gs_relocalize_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _ip, C.c_int32, _dp, _ip, rpp, _dp, _ip, _dp, _ip, _ip, _dp, _lp, _ip, _ip, _dp]
+        L.gs_relocalize_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, rpp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.gs_debug_time_relocalize_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, rpp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, _dp]
+        L.gs_frame_frontend_relocalize.argtypes = [vp, _dp, C.c_int32, rpp, C.c_double, C.c_double, npp, jpp, lpp, _dp, _ip, _dp, _ip, _ip, _dp, _lp, _ip, _ip, _dp,
+                                                   _dp, _dp, _ip, _dp, _ip, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
     if hasattr(L, "gs_set_robust_kernel"):                # (a tuning build of an older tree loaded through GS_LIB may predate the robust kernels)
         L.gs_set_robust_kernel.argtypes = [vp, C.c_int32, C.c_int32, C.c_double]
         L.gs_get_robust_kernel.argtypes = [vp, C.c_int32, _ip, _dp]
@@ -1203,6 +1240,57 @@ class Graph:
                                                       _d(rec["delta"]), _d(lr["pose"]), _d(lr["cov"]), _d(lr["chi2"]), _i(lr["n_pairs"]), _i(lr["iterations"]),
                                                       _i(lr["status"])))
         return z, gx, idx, d2, na, rec, lr
+
+    # ---- relocalisation (include/graphslam.h): a frame's pose found on the map without a prior.
+    # A frame's record is a dict: pose [f,3], count [f], cost [f], seed [f,4], second_count [f], second_pose [f,3], n_seeds [f] int64, status [f]
+    def relocalize(self, obs, frame_start, map_xy, map_type, params=None, second=True):
+        """gs_relocalize_batch: (record of every frame, index [n], e2 [n]); second=False skips the runner-up's pass (its fields stay zero)"""
+        obs = _f64(obs, (-1, 4)); fs = _i32(frame_start); map_xy = _f64(map_xy, (-1, 2)); mt = _i32(map_type); n = len(obs); nf = len(fs) - 1
+        assert len(fs) >= 1 and len(mt) == len(map_xy)
+        p = reloc_params() if params is None else params
+        rec = _reloc_record(nf); idx = np.zeros(n, dtype=np.int32); e2 = np.zeros(n); lp = C.POINTER(C.c_int64)
+        self._check(self.L.gs_relocalize_batch(self.h, n, _d(obs), nf, _i(fs), len(map_xy), _d(map_xy), _i(mt), C.byref(p), _d(rec["pose"]), _i(rec["count"]),
+                                               _d(rec["cost"]), _i(rec["seed"]), _i(rec["second_count"]) if second else None,
+                                               _d(rec["second_pose"]) if second else None, rec["n_seeds"].ctypes.data_as(lp), _i(rec["status"]), _i(idx), _d(e2)))
+        return rec, idx, e2
+
+    def relocalize_resident(self, d_obs, n, n_frames, d_frame_start, d_pose=None, d_count=None, d_cost=None, d_seed=None, d_second_count=None,
+                            d_second_pose=None, d_n_seeds=None, d_status=None, d_index=None, d_e2=None, params=None):
+        """gs_relocalize_resident: the resident map, everything else DeviceArray; asynchronous (synchronize() before reading)"""
+        p = reloc_params() if params is None else params
+        opt = lambda a: None if a is None else a.ptr
+        self._check(self.L.gs_relocalize_resident(self.h, int(n), d_obs.ptr, int(n_frames), d_frame_start.ptr, C.byref(p), opt(d_pose), opt(d_count), opt(d_cost),
+                                                  opt(d_seed), opt(d_second_count), opt(d_second_pose), opt(d_n_seeds), opt(d_status), opt(d_index), opt(d_e2)))
+
+    def time_relocalize_resident(self, d_obs, n, n_frames, d_frame_start, reps, d_pose=None, d_count=None, d_cost=None, d_seed=None, d_second_count=None,
+                                 d_second_pose=None, d_n_seeds=None, d_status=None, d_index=None, d_e2=None, params=None):
+        p = reloc_params() if params is None else params
+        opt = lambda a: None if a is None else a.ptr
+        ms = C.c_double()
+        self._check(self.L.gs_debug_time_relocalize_resident(self.h, int(n), d_obs.ptr, int(n_frames), d_frame_start.ptr, C.byref(p), opt(d_pose), opt(d_count),
+                                                             opt(d_cost), opt(d_seed), opt(d_second_count), opt(d_second_pose), opt(d_n_seeds), opt(d_status),
+                                                             opt(d_index), opt(d_e2), int(reps), C.byref(ms)))
+        return ms.value
+
+    def debug_relocalize(self, slice_cones=0):
+        """gs_debug_relocalize: the cones p a workgroup of the seed kernel enumerates (0: the launcher's choice); results do not depend on it"""
+        self._check(self.L.gs_debug_relocalize(self.h, int(slice_cones)))
+
+    def frame_frontend_relocalize(self, obs, prior_sigma_xy, prior_sigma_theta, reloc=None, params=None, jc=None, loc=None, second=True):
+        """(search record, search index, search e2) + frame_frontend_localize's tuple from the found pose under the diagonal prior"""
+        obs = _f64(obs, (-1, 4)); k = len(obs)
+        r = reloc_params() if reloc is None else reloc
+        p = nn_params() if params is None else params; j = jc_params() if jc is None else jc; l = loc_params() if loc is None else loc
+        sr = _reloc_record(1); si = np.zeros(k, dtype=np.int32); se = np.zeros(k); lp = C.POINTER(C.c_int64)
+        z = np.zeros((k, 2)); gx = np.zeros((k, 2)); idx = np.zeros(k, dtype=np.int32); d2 = np.zeros(k); na = np.zeros(k, dtype=np.int32)
+        rec = _jc_record(1); lr = _loc_record(1)
+        self._check(self.L.gs_frame_frontend_relocalize(self.h, _d(obs), k, C.byref(r), float(prior_sigma_xy), float(prior_sigma_theta), C.byref(p), C.byref(j), C.byref(l),
+                                                        _d(sr["pose"]), _i(sr["count"]), _d(sr["cost"]), _i(sr["seed"]), _i(sr["second_count"]) if second else None,
+                                                        _d(sr["second_pose"]) if second else None, sr["n_seeds"].ctypes.data_as(lp), _i(sr["status"]), _i(si), _d(se),
+                                                        _d(z), _d(gx), _i(idx), _d(d2), _i(na), _d(rec["joint_d2"]), _i(rec["n_kept"]), _i(rec["n_dropped"]),
+                                                        _i(rec["n_untestable"]), _d(rec["delta"]), _d(lr["pose"]), _d(lr["cov"]), _d(lr["chi2"]), _i(lr["n_pairs"]),
+                                                        _i(lr["iterations"]), _i(lr["status"])))
+        return sr, si, se, z, gx, idx, d2, na, rec, lr
 
     # ---- pose-window shards (one handle per rank / GPU)
     def dist_configure(self, rank, world):

@@ -58,4 +58,22 @@ void launch_localize(int n, const double *poses, int n_poses, const int32_t *pos
                      double lidar, int n_map, const double *map_xy, const double *map_cov, const double *pose_cov, NnDev p, const LoParams &lp,
                      const int32_t *in_idx, const LoOut &o, int kernel, hipStream_t st, hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
 
+// ---- relocalisation (gs_reloc.hip): a frame's pose found on the map without a prior, inside the same frames (no pose is read).
+// gs_reloc_params as the kernels take it: inlier_r2 = inlier_radius^2 and distinct_d2 = distinct_xy^2, formed once on the host
+struct RlDev { int seed_obs, min_inliers; double min_baseline, length_tol, inlier_radius, inlier_r2, type_tol, distinct_d2, distinct_cos; };
+// what a workgroup of the seed kernel leaves behind, and what the pick kernel keeps of a frame's winner: count < 0 = none
+struct RlRec { double cost, c, s, tx, ty; long long n_seeds; int32_t count, u, v, p, q, pad; };
+struct RlOut { double *pose, *cost; int32_t *count, *seed, *second_count; double *second_pose; long long *n_seeds; int32_t *status, *index; double *e2; };
+// a workgroup enumerates `slice` cones p against the whole map: n_slices records a frame (forced > 0: gs_debug_relocalize's slice)
+int reloc_slices(int n_frames, int n_map, int forced, int &slice);
+inline size_t reloc_rec_bytes(int n_frames, int n_slices) { return ((size_t)n_frames * (size_t)n_slices + (size_t)n_frames) * sizeof(RlRec); }
+// seed kernel -> pick kernel, and both once more with the winner excluded when o.second_count or o.second_pose is set.  rec: reloc_rec_bytes
+// of device memory.  cell_start != null: the score walks the nine buckets of the hashed grid (cell edge from inlier_radius); null: the whole
+// map.  chain_pose / chain_frame_end (both or neither, one frame): the first pick kernel writes the pose there and, with status >= 2, a zero
+// to chain_frame_end.  Defences as launch_assign_nn: bad bounds touch nothing, a frame above GS_NN_FRAME_MAX gets status 4.
+void launch_relocalize(int n, const double *obs, int n_frames, const int32_t *frame_start, double lidar, int n_map, const double *map_xy,
+                       const int32_t *map_type, RlDev p, long long buckets, const int32_t *cell_start, const int32_t *cell_items, int slice,
+                       int n_slices, RlRec *rec, const RlOut &o, double *chain_pose, int32_t *chain_frame_end, hipStream_t st,
+                       hipEvent_t start = nullptr, hipEvent_t stop = nullptr);
+
 }  // namespace gs

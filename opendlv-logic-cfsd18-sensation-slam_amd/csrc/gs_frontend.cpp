@@ -57,6 +57,10 @@ void gs_frontend_release(gs_graph *g) {      // gs_destroy
     if (g->fe.jc_dev_out) hipFree(g->fe.jc_dev_out);
     if (g->fe.lo_pin_out) hipHostFree(g->fe.lo_pin_out);
     if (g->fe.lo_dev_out) hipFree(g->fe.lo_dev_out);
+    if (g->fe.rl_rec) hipFree(g->fe.rl_rec);
+    if (g->fe.rl_grid_mem) hipFree(g->fe.rl_grid_mem);
+    if (g->fe.rl_pin_out) hipHostFree(g->fe.rl_pin_out);
+    if (g->fe.rl_dev_out) hipFree(g->fe.rl_dev_out);
     g->fe = gs_graph::FrontEnd();
 }
 
@@ -222,7 +226,7 @@ static int pin_map_reserve(gs_graph *g, size_t bytes) {
     return GS_OK;
 }
 extern "C" int gs_map_size(gs_graph *g) { return g ? g->fe.map_n : fail(GS_ERR_INVALID, "null graph"); }
-extern "C" int gs_map_clear(gs_graph *g) { if (!g) return fail(GS_ERR_INVALID, "null graph"); g->fe.map_n = 0; g->fe.grid_valid = false; return GS_OK; }
+extern "C" int gs_map_clear(gs_graph *g) { if (!g) return fail(GS_ERR_INVALID, "null graph"); g->fe.map_n = 0; g->fe.grid_valid = false; g->fe.rl_grid_valid = false; return GS_OK; }
 extern "C" int gs_map_append(gs_graph *g, int32_t n, const double *xy, const int32_t *type) {
     if (!g || n < 0 || (n > 0 && (!xy || !type))) return fail(GS_ERR_INVALID, "bad argument");
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
@@ -238,7 +242,7 @@ extern "C" int gs_map_append(gs_graph *g, int32_t n, const double *xy, const int
     HIP_TRY(hipMemcpyAsync(g->fe.map_type + g->fe.map_n, g->fe.pin_map + bx, bt, hipMemcpyHostToDevice, g->stream));
     g->fe.pin_map_busy = true;                                      // no wait here: the next frame's launch is ordered behind the copies
     if (g->fe.map_cov) HIP_TRY(hipMemsetAsync(g->fe.map_cov + 4 * (size_t)g->fe.map_n, 0, (size_t)n * 4 * sizeof(double), g->stream));   // (also what gs_map_clear's "drops covariances" rests on)
-    g->fe.map_n += n; g->fe.grid_valid = false;
+    g->fe.map_n += n; g->fe.grid_valid = false; g->fe.rl_grid_valid = false;
     return GS_OK;
 }
 extern "C" int gs_map_set_xy(gs_graph *g, int32_t first, int32_t n, const double *xy) {
@@ -248,7 +252,7 @@ extern "C" int gs_map_set_xy(gs_graph *g, int32_t first, int32_t n, const double
     if (n == 0) return GS_OK;
     HIP_TRY(hipMemcpyAsync(g->fe.map_xy + 2 * (size_t)first, xy, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));                       // pageable source: the caller's buffer is free on return
-    g->fe.pin_map_busy = false; g->fe.grid_valid = false;
+    g->fe.pin_map_busy = false; g->fe.grid_valid = false; g->fe.rl_grid_valid = false;
     return GS_OK;
 }
 extern "C" int gs_frame_frontend(gs_graph *g, const double pose[3], const double *obs, int32_t k, double thr, double type_tol,
@@ -617,8 +621,12 @@ static void assign_staging_release(gs_graph *g) {      // gs_frontend_release, a
 // then frame_start[2] and pose_of_obs[k] (zeros) as int32
 // the frame in device memory once frame_assign_enqueue has run: inputs in as_dev_in, the assignment's outputs in as_dev_out
 struct FrameDev { const double *pose, *pose_cov, *obs; const int32_t *frame_start, *pose_of_obs; double *z, *g, *d2; int32_t *idx, *na; size_t out_bytes; };
-// stages the frame (growing the staging first), sends it and enqueues the assignment: no wait, nothing copied back
-static int frame_assign_enqueue(gs_graph *g, bool opt, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const NnDev &nd, FrameDev &fd) {
+// stages the frame (growing the staging first), sends it and enqueues the assignment: no wait, nothing copied back.
+// before (null as a rule): enqueued between the upload and the assignment, given the staged frame's device pointers (relocalisation's search,
+// whose last kernel writes the pose the assignment reads)
+struct FrameHook { virtual int enqueue(gs_graph *g, double *dev_pose, const double *dev_obs, int32_t *dev_frame_start) = 0; virtual ~FrameHook() {} };
+static int frame_assign_enqueue(gs_graph *g, bool opt, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const NnDev &nd, FrameDev &fd,
+                                FrameHook *before = nullptr) {
     int rc;
     auto &fe = g->fe;
     auto in_bytes = [](size_t m) { return (16 + 4 * m) * sizeof(double) + (2 + m) * sizeof(int32_t); };
@@ -640,6 +648,7 @@ static int frame_assign_enqueue(gs_graph *g, bool opt, const double pose[3], con
     const double *dp = (const double *)fe.as_dev_in; const int32_t *dfs = (const int32_t *)(fe.as_dev_in + oint);
     double *dz = (double *)fe.as_dev_out, *dg = dz + 2 * (size_t)k, *dd = dg + 2 * (size_t)k; int32_t *di = (int32_t *)(dd + k), *dn = di + k;
     HIP_TRY(hipMemcpyAsync(fe.as_dev_in, fe.as_pin_in, in_bytes(k), hipMemcpyHostToDevice, g->stream));
+    if (before && (rc = before->enqueue(g, (double *)fe.as_dev_in, dp + 16, (int32_t *)(fe.as_dev_in + oint))) != GS_OK) return rc;
     bool grid = fe.map_n >= 2048;                                    // by the map's size, as the batch call; gs_debug_options.assoc_grid forces either
     if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && fe.map_n > 0;
     if ((rc = assign_resident_launch(g, opt, grid, k, dp, 1, dfs + 2, dp + 16, 1, dfs, pose_cov ? dp + 4 : nullptr, nd, di, dd, opt ? dn : nullptr, dz, dg)) != GS_OK) return rc;
@@ -954,6 +963,12 @@ extern "C" int gs_debug_time_localize_resident(gs_graph *g, int32_t n, const dou
     *out_ms = cnt ? tot / cnt : 0.0;
     return rc;
 }
+// the launches, the copies and the one wait of gs_frame_frontend_localize for a checked frame of 1 .. GS_NN_FRAME_MAX observations (before: see
+// frame_assign_enqueue; gs_frame_frontend_relocalize puts its search there)
+static int frame_localize_run(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const NnDev &nd, const JcGate &gt,
+                              const LoParams &lp, FrameHook *before, double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2,
+                              int32_t *out_na, double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable, double *out_delta,
+                              double *out_pose, double *out_cov, double *out_chi2, int32_t *out_pairs, int32_t *out_iters, int32_t *out_status);
 // one frame: the minimum-cost assignment, the joint test of its result and the localisation under the PRUNED index, back to back on the stream.
 // Record staging (bytes): the joint test's as in gs_frame_frontend_jc (J 0, delta 8, counts 32, pruned index 48), then at LO_REC the pose, at
 // + 24 its covariance, + 96 chi2, + 104 pairs / iterations / status
@@ -980,11 +995,18 @@ extern "C" int gs_frame_frontend_localize(gs_graph *g, const double pose[3], con
         if (out_iters) *out_iters = 0;
         if (out_status) *out_status = 2;
         return GS_OK; }
-    auto &fe = g->fe; FrameDev fd;
+    return frame_localize_run(g, pose, pose_cov, obs, k, nd, gt, lp, nullptr, out_zxy, out_gxy, out_idx, out_d2, out_na, out_j, out_kept, out_dropped, out_untestable,
+                              out_delta, out_pose, out_cov, out_chi2, out_pairs, out_iters, out_status);
+}
+static int frame_localize_run(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const NnDev &nd, const JcGate &gt,
+                              const LoParams &lp, FrameHook *before, double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2,
+                              int32_t *out_na, double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable, double *out_delta,
+                              double *out_pose, double *out_cov, double *out_chi2, int32_t *out_pairs, int32_t *out_iters, int32_t *out_status) {
+    int rc; auto &fe = g->fe; FrameDev fd;
     constexpr size_t LO_REC = 48 + (size_t)GS_NN_FRAME_MAX * sizeof(int32_t), lbytes = LO_REC + 120;
     if (!fe.lo_dev_out) {                                           // once per handle: the size does not depend on k
         HIP_TRY(hipHostMalloc((void **)&fe.lo_pin_out, lbytes, hipHostMallocDefault)); HIP_TRY(hipMalloc((void **)&fe.lo_dev_out, lbytes)); }
-    if ((rc = frame_assign_enqueue(g, true, pose, pose_cov, obs, k, nd, fd)) != GS_OK) return rc;
+    if ((rc = frame_assign_enqueue(g, true, pose, pose_cov, obs, k, nd, fd, before)) != GS_OK) return rc;
     char *jd = fe.lo_dev_out, *ld = fe.lo_dev_out + LO_REC;
     launch_joint_compat(k, fd.pose, 1, fd.pose_of_obs, fd.obs, 1, fd.frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_cov, fd.pose_cov, nd, gt, fd.idx,
                         (int32_t *)(jd + 48), (double *)jd, (int32_t *)(jd + 32), (int32_t *)(jd + 36), (int32_t *)(jd + 40), (double *)(jd + 8), g->stream);
@@ -1013,5 +1035,220 @@ extern "C" int gs_frame_frontend_localize(gs_graph *g, const double pose[3], con
     if (out_pairs) std::memcpy(out_pairs, pl + 104, sizeof(int32_t));
     if (out_iters) std::memcpy(out_iters, pl + 108, sizeof(int32_t));
     if (out_status) std::memcpy(out_status, pl + 112, sizeof(int32_t));
+    return GS_OK;
+}
+
+// ---- relocalisation (gs_reloc.hip, k_reloc_seed / k_reloc_pick): a frame's pose found on the map without a prior — batch / resident / frame calls ----
+extern "C" int gs_reloc_params_default(gs_reloc_params *p) {
+    if (!p) return fail(GS_ERR_INVALID, "null params");
+    std::memset(p, 0, sizeof(*p)); p->struct_size = (int32_t)sizeof(*p);
+    p->seed_obs = 12; p->min_inliers = 4; p->min_baseline = 2.0; p->length_tol = 0.3; p->inlier_radius = 0.5; p->type_tol = 1e-4;
+    p->distinct_xy = 2.0; p->distinct_cos = 0.98006657784124163;
+    return GS_OK;
+}
+static int reloc_params_check(const gs_reloc_params *p, RlDev &d) {
+    if (!p) return fail(GS_ERR_INVALID, "null params");
+    if (p->struct_size != (int32_t)sizeof(gs_reloc_params)) return fail(GS_ERR_INVALID, "gs_reloc_params: wrong struct_size");
+    if (p->seed_obs < 2 || p->seed_obs > GS_RELOC_SEED_MAX) return fail(GS_ERR_INVALID, "gs_reloc_params: seed_obs outside 2 .. GS_RELOC_SEED_MAX");
+    if (p->min_inliers < 2) return fail(GS_ERR_INVALID, "gs_reloc_params: min_inliers below 2");
+    const double len[4] = {p->min_baseline, p->length_tol, p->inlier_radius, p->distinct_xy};
+    for (double x : len) if (!std::isfinite(x) || !(x > 0.0)) return fail(GS_ERR_INVALID, "gs_reloc_params: a length is not finite or not positive");
+    if (!std::isfinite(p->type_tol)) return fail(GS_ERR_INVALID, "gs_reloc_params: type_tol is not finite");
+    if (!(p->distinct_cos >= -1.0 && p->distinct_cos <= 1.0)) return fail(GS_ERR_INVALID, "gs_reloc_params: distinct_cos outside [-1, 1]");
+    d = RlDev{p->seed_obs, p->min_inliers, p->min_baseline, p->length_tol, p->inlier_radius, p->inlier_radius * p->inlier_radius, p->type_tol,
+              p->distinct_xy * p->distinct_xy, p->distinct_cos};
+    return GS_OK;
+}
+extern "C" int gs_debug_relocalize(gs_graph *g, int32_t slice_cones) {
+    if (!g || slice_cones < 0) return fail(GS_ERR_INVALID, "bad argument");
+    g->fe.rl_slice = slice_cones;
+    return GS_OK;
+}
+extern "C" int gs_relocalize_batch(gs_graph *g, int32_t n, const double *obs, int32_t n_frames, const int32_t *frame_start, int32_t n_map,
+                                   const double *map_xy, const int32_t *map_type, const gs_reloc_params *params, double *out_pose, int32_t *out_count,
+                                   double *out_cost, int32_t *out_seed, int32_t *out_second_count, double *out_second_pose, int64_t *out_n_seeds,
+                                   int32_t *out_status, int32_t *out_index, double *out_e2) {
+    if (!g || n < 0 || n_map < 0 || (n > 0 && !obs) || (n_map > 0 && (!map_xy || !map_type))) return fail(GS_ERR_INVALID, "bad argument");
+    RlDev rd; int rc = reloc_params_check(params, rd); if (rc != GS_OK) return rc;
+    if ((rc = frame_start_check(n, n_frames, frame_start)) != GS_OK) return rc;
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n_frames == 0) return GS_OK;
+    bool grid = n_map >= 2048;                                      // as gs_associate_nn_batch: the grid beyond a few LDS tiles, gs_debug_options.assoc_grid forces either
+    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && n_map > 0;
+    const size_t nf = (size_t)n_frames;
+    int slice = 0; const int n_slices = reloc_slices(n_frames, n_map, g->fe.rl_slice, slice);
+    long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
+    if ((rc = arena_reserve(g, padded(4 * (size_t)n, 8) + padded(nf + 1, 4) + padded(2 * (size_t)n_map, 8) + padded(n_map, 4) + gbytes +
+                               padded(reloc_rec_bytes(n_frames, n_slices), 1) + 2 * padded(3 * nf, 8) + 2 * padded(nf, 8) + padded(4 * nf, 4) + 3 * padded(nf, 4) +
+                               padded(n, 4) + padded(n, 8))) != GS_OK) return rc;
+    Carver c{g}; double *ob = c.get<double>(4 * (size_t)n); int32_t *fs = c.get<int32_t>(nf + 1);
+    double *mx = c.get<double>(2 * (size_t)n_map); int32_t *mt = c.get<int32_t>(n_map);
+    RlRec *rec = (RlRec *)c.get<char>(reloc_rec_bytes(n_frames, n_slices));
+    double *op = c.get<double>(3 * nf), *osp = c.get<double>(3 * nf), *oc = c.get<double>(nf); long long *ons = c.get<long long>(nf);
+    int32_t *osd = c.get<int32_t>(4 * nf), *ocn = c.get<int32_t>(nf), *osc = c.get<int32_t>(nf), *ost = c.get<int32_t>(nf), *oi = c.get<int32_t>(n);
+    double *oe = c.get<double>(n);
+    if (n > 0) HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(fs, frame_start, (nf + 1) * 4, hipMemcpyHostToDevice, g->stream));
+    if (n_map > 0) { HIP_TRY(hipMemcpyAsync(mx, map_xy, 2 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream));
+                     HIP_TRY(hipMemcpyAsync(mt, map_type, (size_t)n_map * 4, hipMemcpyHostToDevice, g->stream)); }
+    GridBufs gb{};
+    if (grid) { gb = grid_carve(c.get<char>(gbytes), n_map, buckets);
+        launch_grid_build(n_map, mx, rd.inlier_radius, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream); }
+    const bool second = out_second_count || out_second_pose;
+    launch_relocalize(n, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, mt, rd, buckets, grid ? gb.start : nullptr, grid ? gb.items : nullptr, slice, n_slices, rec,
+                      RlOut{op, oc, ocn, osd, second ? osc : nullptr, second ? osp : nullptr, ons, ost, oi, oe}, nullptr, nullptr, g->stream);
+    if (out_pose) HIP_TRY(hipMemcpyAsync(out_pose, op, 3 * nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    if (out_count) HIP_TRY(hipMemcpyAsync(out_count, ocn, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (out_cost) HIP_TRY(hipMemcpyAsync(out_cost, oc, nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    if (out_seed) HIP_TRY(hipMemcpyAsync(out_seed, osd, 4 * nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (out_second_count) HIP_TRY(hipMemcpyAsync(out_second_count, osc, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (out_second_pose) HIP_TRY(hipMemcpyAsync(out_second_pose, osp, 3 * nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    if (out_n_seeds) HIP_TRY(hipMemcpyAsync(out_n_seeds, ons, nf * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
+    if (out_status) HIP_TRY(hipMemcpyAsync(out_status, ost, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (out_index && n > 0) HIP_TRY(hipMemcpyAsync(out_index, oi, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (out_e2 && n > 0) HIP_TRY(hipMemcpyAsync(out_e2, oe, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));        // the one wait of the call: the result copies
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("relocalisation: ") + hipGetErrorString(e));
+    return GS_OK;
+}
+// the resident map's second grid (cell edge from inlier_radius), built on the device once per map change or radius: resident_grid's twin
+static int reloc_grid(gs_graph *g, double thr) {
+    auto &fe = g->fe;
+    if (fe.rl_grid_valid && fe.rl_grid_map_n == fe.map_n && fe.rl_grid_thr == thr) return GS_OK;
+    long long buckets = 0; const size_t bytes = grid_bytes(fe.map_n, buckets) + 5 * 256;
+    if (bytes > fe.rl_grid_bytes) { HIP_TRY(hipStreamSynchronize(g->stream));
+        if (fe.rl_grid_mem) hipFree(fe.rl_grid_mem);
+        fe.rl_grid_mem = nullptr; fe.rl_grid_bytes = 0;
+        HIP_TRY(hipMalloc((void **)&fe.rl_grid_mem, bytes + bytes / 2)); fe.rl_grid_bytes = bytes + bytes / 2; }
+    const GridBufs gb = grid_carve(fe.rl_grid_mem, fe.map_n, buckets);
+    launch_grid_build(fe.map_n, fe.map_xy, thr, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream);
+    fe.rl_grid_valid = true; fe.rl_grid_map_n = fe.map_n; fe.rl_grid_thr = thr; fe.rl_grid_cells = buckets;
+    return GS_OK;
+}
+// the search against the resident map through either scoring search: what the resident and the frame call end in
+static int reloc_resident_launch(gs_graph *g, bool grid, int32_t n, const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const RlDev &rd,
+                                 const RlOut &o, double *chain_pose, int32_t *chain_frame_end) {
+    auto &fe = g->fe; int rc; GridBufs gb{};
+    int slice = 0; const int n_slices = reloc_slices(n_frames, fe.map_n, fe.rl_slice, slice);
+    const size_t bytes = reloc_rec_bytes(n_frames, n_slices);
+    if (bytes > fe.rl_rec_bytes) { HIP_TRY(hipStreamSynchronize(g->stream));   // grow-only
+        if (fe.rl_rec) hipFree(fe.rl_rec);
+        fe.rl_rec = nullptr; fe.rl_rec_bytes = 0;
+        HIP_TRY(hipMalloc((void **)&fe.rl_rec, bytes + bytes / 2)); fe.rl_rec_bytes = bytes + bytes / 2; }
+    if (grid) { if ((rc = reloc_grid(g, rd.inlier_radius)) != GS_OK) return rc;
+        gb = grid_carve(fe.rl_grid_mem, fe.map_n, fe.rl_grid_cells); }
+    launch_relocalize(n, dev_obs, n_frames, dev_frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, rd, gb.buckets, grid ? gb.start : nullptr,
+                      grid ? gb.items : nullptr, slice, n_slices, (RlRec *)fe.rl_rec, o, chain_pose, chain_frame_end, g->stream, g->ev_lin[0], g->ev_lin[1]);
+    return GS_OK;
+}
+extern "C" int gs_relocalize_resident(gs_graph *g, int32_t n, const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start,
+                                      const gs_reloc_params *params, double *dev_out_pose, int32_t *dev_out_count, double *dev_out_cost, int32_t *dev_out_seed,
+                                      int32_t *dev_out_second_count, double *dev_out_second_pose, int64_t *dev_out_n_seeds, int32_t *dev_out_status,
+                                      int32_t *dev_out_index, double *dev_out_e2) {
+    if (!g || n < 0 || n_frames < 0 || !dev_frame_start || (n > 0 && !dev_obs)) return fail(GS_ERR_INVALID, "bad argument");
+    RlDev rd; int rc = reloc_params_check(params, rd); if (rc != GS_OK) return rc;
+    if (((uintptr_t)dev_obs & 31) != 0) return fail(GS_ERR_INVALID, "dev_obs must be 32-byte aligned (an observation is read in one load)");
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    if (n_frames == 0) return GS_OK;
+    const bool grid = g->fe.map_n > 0 && g->opt.assoc_grid != 0;     // as gs_associate_nn_resident
+    if ((rc = reloc_resident_launch(g, grid, n, dev_obs, n_frames, dev_frame_start, rd,
+                                    RlOut{dev_out_pose, dev_out_cost, dev_out_count, dev_out_seed, dev_out_second_count, dev_out_second_pose, (long long *)dev_out_n_seeds,
+                                          dev_out_status, dev_out_index, dev_out_e2}, nullptr, nullptr)) != GS_OK) return rc;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("relocalisation: ") + hipGetErrorString(e));
+    return GS_OK;
+}
+// the twin of gs_debug_time_localize_resident
+extern "C" int gs_debug_time_relocalize_resident(gs_graph *g, int32_t n, const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start,
+                                                 const gs_reloc_params *params, double *dev_out_pose, int32_t *dev_out_count, double *dev_out_cost,
+                                                 int32_t *dev_out_seed, int32_t *dev_out_second_count, double *dev_out_second_pose, int64_t *dev_out_n_seeds,
+                                                 int32_t *dev_out_status, int32_t *dev_out_index, double *dev_out_e2, int32_t reps, double *out_ms) {
+    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
+    auto once = [&] { return gs_relocalize_resident(g, n, dev_obs, n_frames, dev_frame_start, params, dev_out_pose, dev_out_count, dev_out_cost, dev_out_seed,
+                                                    dev_out_second_count, dev_out_second_pose, dev_out_n_seeds, dev_out_status, dev_out_index, dev_out_e2); };
+    int rc = once(); if (rc != GS_OK) return rc;                    // warm (and the grid)
+    std::vector<hipEvent_t> ev(2 * (size_t)reps); for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    for (int r = 0; r < reps && rc == GS_OK; ++r) { g->ev_lin[0] = ev[2 * (size_t)r]; g->ev_lin[1] = ev[2 * (size_t)r + 1]; rc = once(); }
+    g->ev_lin[0] = g->ev_lin[1] = nullptr;
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    double tot = 0; int cnt = 0;
+    for (int r = 0; r < reps; ++r) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]) == hipSuccess && ms > 0) { tot += ms; ++cnt; } }
+    (void)hipGetLastError();
+    for (auto &e : ev) hipEventDestroy(e);
+    *out_ms = cnt ? tot / cnt : 0.0;
+    return rc;
+}
+// one frame: the search, then the chain of gs_frame_frontend_localize from the found pose, back to back on the stream, one wait.
+// Record staging (bytes): pose 0, second pose 24, cost 48, n_seeds 56, seed 64, count 80, second count 84, status 88, then at 96 the index
+// and at 96 + 4 GS_NN_FRAME_MAX the e2 of every observation
+namespace {
+constexpr size_t RL_IDX = 96, RL_E2 = RL_IDX + (size_t)GS_NN_FRAME_MAX * sizeof(int32_t), RL_BYTES = RL_E2 + (size_t)GS_NN_FRAME_MAX * sizeof(double);
+struct RelocHook : FrameHook {
+    RlDev rd; int32_t k; bool second;
+    int enqueue(gs_graph *g, double *dev_pose, const double *dev_obs, int32_t *dev_frame_start) override {
+        auto &fe = g->fe; char *d = fe.rl_dev_out; int rc;
+        bool grid = fe.map_n >= 2048;                                // by the map's size, as the batch call; gs_debug_options.assoc_grid forces either
+        if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && fe.map_n > 0;
+        if ((rc = reloc_resident_launch(g, grid, k, dev_obs, 1, dev_frame_start, rd,
+                                        RlOut{(double *)d, (double *)(d + 48), (int32_t *)(d + 80), (int32_t *)(d + 64), second ? (int32_t *)(d + 84) : nullptr,
+                                              second ? (double *)(d + 24) : nullptr, (long long *)(d + 56), (int32_t *)(d + 88), (int32_t *)(d + RL_IDX), (double *)(d + RL_E2)},
+                                        dev_pose, dev_frame_start + 1)) != GS_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(fe.rl_pin_out, fe.rl_dev_out, RL_BYTES, hipMemcpyDeviceToHost, g->stream));
+        return GS_OK;
+    }
+};
+}
+extern "C" int gs_frame_frontend_relocalize(gs_graph *g, const double *obs, int32_t k, const gs_reloc_params *reloc, double prior_sigma_xy, double prior_sigma_theta,
+                                            const gs_nn_params *params, const gs_jc_params *jc, const gs_loc_params *loc, double *out_rl_pose, int32_t *out_rl_count,
+                                            double *out_rl_cost, int32_t *out_rl_seed, int32_t *out_second_count, double *out_second_pose, int64_t *out_n_seeds,
+                                            int32_t *out_rl_status, int32_t *out_rl_index, double *out_rl_e2, double *out_zxy, double *out_gxy, int32_t *out_idx,
+                                            double *out_d2, int32_t *out_na, double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable,
+                                            double *out_delta, double *out_pose, double *out_cov, double *out_chi2, int32_t *out_pairs, int32_t *out_iters,
+                                            int32_t *out_status) {
+    if (!g || k < 0 || (k > 0 && (!obs || !out_zxy || !out_gxy || !out_idx || !out_d2))) return fail(GS_ERR_INVALID, "bad argument");
+    RelocHook hook; int rc = reloc_params_check(reloc, hook.rd); if (rc != GS_OK) return rc;
+    if (!std::isfinite(prior_sigma_xy) || prior_sigma_xy < 0.0 || !std::isfinite(prior_sigma_theta) || prior_sigma_theta < 0.0)
+        return fail(GS_ERR_INVALID, "a prior sigma is not finite or negative");
+    NnDev nd; if ((rc = nn_params_check(params, nd)) != GS_OK) return rc;
+    JcGate gt; if ((rc = jc_params_check(jc, gt)) != GS_OK) return rc;
+    LoParams lp; if ((rc = loc_params_check(loc, lp)) != GS_OK) return rc;
+    if (k > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations");
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    const double zero3[3] = {0.0, 0.0, 0.0};
+    const double prior[9] = {prior_sigma_xy * prior_sigma_xy, 0.0, 0.0, 0.0, prior_sigma_xy * prior_sigma_xy, 0.0, 0.0, 0.0, prior_sigma_theta * prior_sigma_theta};
+    auto none = [&] {                                                // the record of "no seed"
+        if (out_rl_pose) std::memcpy(out_rl_pose, zero3, sizeof(zero3));
+        if (out_rl_count) *out_rl_count = 0;
+        if (out_rl_cost) *out_rl_cost = INFINITY;
+        if (out_rl_seed) out_rl_seed[0] = out_rl_seed[1] = out_rl_seed[2] = out_rl_seed[3] = -1;
+        if (out_second_count) *out_second_count = 0;
+        if (out_second_pose) std::memcpy(out_second_pose, zero3, sizeof(zero3));
+        if (out_n_seeds) *out_n_seeds = 0;
+        if (out_rl_status) *out_rl_status = 2; };
+    if (k == 0) {                                                    // nothing is launched: no seed, and the chain's empty frame at the pose zero
+        none();
+        return gs_frame_frontend_localize(g, zero3, prior, obs, 0, params, jc, loc, out_zxy, out_gxy, out_idx, out_d2, out_na, out_j, out_kept, out_dropped,
+                                          out_untestable, out_delta, out_pose, out_cov, out_chi2, out_pairs, out_iters, out_status); }
+    auto &fe = g->fe;
+    if (!fe.rl_dev_out) {                                            // once per handle: the size does not depend on k
+        HIP_TRY(hipHostMalloc((void **)&fe.rl_pin_out, RL_BYTES, hipHostMallocDefault)); HIP_TRY(hipMalloc((void **)&fe.rl_dev_out, RL_BYTES)); }
+    hook.k = k; hook.second = out_second_count || out_second_pose;
+    if ((rc = frame_localize_run(g, zero3, prior, obs, k, nd, gt, lp, &hook, out_zxy, out_gxy, out_idx, out_d2, out_na, out_j, out_kept, out_dropped, out_untestable,
+                                 out_delta, out_pose, out_cov, out_chi2, out_pairs, out_iters, out_status)) != GS_OK) return rc;
+    const char *pr = fe.rl_pin_out; int32_t status; std::memcpy(&status, pr + 88, sizeof(status));
+    if (out_rl_pose) std::memcpy(out_rl_pose, pr, 3 * sizeof(double));
+    if (out_second_pose) std::memcpy(out_second_pose, pr + 24, 3 * sizeof(double));
+    if (out_rl_cost) std::memcpy(out_rl_cost, pr + 48, sizeof(double));
+    if (out_n_seeds) std::memcpy(out_n_seeds, pr + 56, sizeof(int64_t));
+    if (out_rl_seed) std::memcpy(out_rl_seed, pr + 64, 4 * sizeof(int32_t));
+    if (out_rl_count) std::memcpy(out_rl_count, pr + 80, sizeof(int32_t));
+    if (out_second_count) std::memcpy(out_second_count, pr + 84, sizeof(int32_t));
+    if (out_rl_status) *out_rl_status = status;
+    if (out_rl_index) std::memcpy(out_rl_index, pr + RL_IDX, (size_t)k * sizeof(int32_t));
+    if (out_rl_e2) std::memcpy(out_rl_e2, pr + RL_E2, (size_t)k * sizeof(double));
+    if (status >= 2)                                                 // the chain found an empty frame: it wrote nothing per observation
+        for (int i = 0; i < k; ++i) { out_zxy[2 * i] = out_zxy[2 * i + 1] = out_gxy[2 * i] = out_gxy[2 * i + 1] = 0.0; out_idx[i] = -1; out_d2[i] = INFINITY;
+            if (out_na) out_na[i] = 0; }
     return GS_OK;
 }

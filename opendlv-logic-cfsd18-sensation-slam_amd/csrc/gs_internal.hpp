@@ -79,6 +79,12 @@ struct gs_graph {
         // frame localisation: the frame call's record (null until gs_frame_frontend_localize is called; a fixed size); gs_debug_localize's
         // kernel choice (-1: by the mean frame size) and step output (a device pointer of the caller's, or null)
         char *lo_pin_out = nullptr, *lo_dev_out = nullptr; int lo_kernel = -1; double *lo_step = nullptr;
+        // relocalisation (null until one of its calls is made): the seed kernel's records of the resident and the frame call (grow-only), a grid
+        // of its own beside the association's (cell edge from inlier_radius: the two edges must not evict each other), the frame call's
+        // record staging (a fixed size), gs_debug_relocalize's slice (0: the launcher's choice)
+        char *rl_rec = nullptr; size_t rl_rec_bytes = 0;
+        char *rl_grid_mem = nullptr; size_t rl_grid_bytes = 0; bool rl_grid_valid = false; int rl_grid_map_n = 0; double rl_grid_thr = 0.0; long long rl_grid_cells = 0;
+        char *rl_pin_out = nullptr, *rl_dev_out = nullptr; int rl_slice = 0;
     } fe;
     bool tree_proven = false;               // a whole-tree launch sequence of the CURRENT plan has completed without a flag timeout (gs_optimize then sends all iterations of a call at once)
     bool fell_back = false;                 // a whole-tree launch gave up on a flag: this handle uses one launch per level — until the next plan, or until a retry (below) comes back clean
