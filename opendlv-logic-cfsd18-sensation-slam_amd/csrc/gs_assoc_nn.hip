@@ -5,71 +5,27 @@
 //   k_assoc_nn_grid   a thread per observation, the nine buckets of the hashed grid around it (cell edge from max_distance)
 //   k_frame_nn        one frame in one launch: a workgroup per observation, its 256 threads stride over the map
 //   k_map_cov_gather  map covariances out of the gathered marginals (gs_map_set_cov_from_marginals)
-//   k_assign_nn       the one-to-one association inside frames (gs_assign_nn_*, gs_frame_frontend_assign): further down, with its own text
-//   k_assign_opt      the minimum-cost association inside frames (gs_assign_opt_*): likewise
-//   k_joint_compat    the joint test of a frame's hypothesis (gs_joint_compat_*, gs_frame_frontend_jc): likewise
-//   k_localize        the iterated pose refinement of a frame against the map (gs_localize_*, gs_frame_frontend_localize): likewise
+//   k_assign_nn       the one-to-one association inside frames (gs_assign_nn_*, gs_frame_frontend_assign)
+//   k_assign_opt      the minimum-cost association inside frames (gs_assign_opt_*), k_assign_opt_big for frames above 64 observations
+//   k_joint_compat    the joint test of a frame's hypothesis (gs_joint_compat_*, gs_frame_frontend_jc), k_joint_compat_big likewise
+//   k_localize        the iterated pose refinement of a frame against the map (gs_localize_*, gs_frame_frontend_localize), k_localize_big likewise
+// The last four have their own text further down.  What the kernels share is in gs_assoc_dev.hpp, once: the query and the candidate, the walk
+// over the map, the wave sync, the frame kernels' scaffold (argument block, lane split, frame defences, the two drivers, the launcher) and
+// the ten pair terms of the joint test and the localisation.
 //
 // The three association kernels return IDENTICAL bits: the query's side (z, g, Q + P) is nn_query, one candidate's side (S, det, d2 and
 // the five tests) is nn_pair, both without contraction, the A0 conversion is ONE out-of-line function (polar_to_xy compiled once, not
 // once per inlining context), heading cos / sin come from sincos everywhere, and the winner is a minimum over (d2, index) — which does
 // not depend on the order the candidates arrive in; the frame kernel reduces it in a fixed order all the same.
-#include "gs_assoc_nn.hpp"
-#include "gs_frontend_dev.hpp"
+#include "gs_assoc_dev.hpp"
 #include <hip/hip_ext.h>
 
 namespace gs {
 
 static constexpr int NN_TILE = 1024;
-static constexpr int NN_NONE = 0x7fffffff;
 
-struct NnQuery { double zx, zy, gx, gy, a00, a01, a11, ty; bool valid; };      // a = Q + P, once per observation
 struct NnBest { double d2; int j; double second; };
 
-__device__ __noinline__ double2 nn_polar(double az, double zen, double dist, double lidar) {
-    double x, y; polar_to_xy(az, zen, dist, lidar, x, y);
-    return make_double2(x, y);
-}
-
-// pose = (t, theta), pc = the pose's 3x3 covariance (row-major, upper triangle read) or null
-// (nn_query_at: the same from z and the heading's sin / cos, for a caller that moves the pose under a fixed z — lo_pass)
-__device__ __forceinline__ NnQuery nn_query_at(const double *pose, const double *pc, double2 z, double s, double c, double ty, const NnDev &p) {
-#pragma clang fp contract(off)
-    NnQuery q;
-    const double wx = z.x * c - z.y * s, wy = z.x * s + z.y * c;               // w = R(theta) z
-    q.zx = z.x; q.zy = z.y; q.gx = wx + pose[0]; q.gy = wy + pose[1]; q.ty = ty;
-    const double r2 = z.x * z.x + z.y * z.y;
-    const double k = (p.sigma_range * p.sigma_range) / r2, sb2 = p.sigma_bearing * p.sigma_bearing, sx2 = p.sigma_xy * p.sigma_xy;
-    // Q = (sigma_r^2 / r^2) w w^T + sigma_b^2 wp wp^T + sigma_xy^2 I,  wp = (-wy, wx)
-    q.a00 = ((k * wx) * wx + (sb2 * wy) * wy) + sx2;
-    q.a01 = (k * wx) * wy - (sb2 * wx) * wy;
-    q.a11 = ((k * wy) * wy + (sb2 * wx) * wx) + sx2;
-    if (pc) {                                                                 // P = G Sigma_p G^T, G = [I | wp]
-        const double ux = -wy, uy = wx;
-        q.a00 += (pc[0] + (2.0 * pc[2]) * ux) + (pc[8] * ux) * ux;
-        q.a01 += ((pc[1] + pc[2] * uy) + pc[5] * ux) + (pc[8] * ux) * uy;
-        q.a11 += (pc[4] + (2.0 * pc[5]) * uy) + (pc[8] * uy) * uy;
-    }
-    q.valid = isfinite(q.gx) && isfinite(q.gy) && r2 > 0.0;
-    return q;
-}
-__device__ __forceinline__ NnQuery nn_query(const double *pose, const double *pc, double az, double zen, double dist, double ty, double lidar, const NnDev &p) {
-    const double2 z = nn_polar(az, zen, dist, lidar);
-    double s, c; sincos(pose[2], &s, &c);
-    return nn_query_at(pose, pc, z, s, c, ty, p);
-}
-
-// one candidate: true and d2 when it is admissible (all tests positive: any NaN skips it)
-__device__ __forceinline__ bool nn_pair(const NnQuery &q, const NnDev &p, double lx, double ly, double c00, double c01, double c11, int32_t type, double &d2) {
-#pragma clang fp contract(off)
-    if (!(fabs((double)type - q.ty) < p.type_tol)) return false;
-    const double n0 = lx - q.gx, n1 = ly - q.gy;
-    if (!(sqrt(n0 * n0 + n1 * n1) < p.max_distance)) return false;
-    const double s00 = c00 + q.a00, s01 = c01 + q.a01, s11 = c11 + q.a11;
-    const double det = s00 * s11 - s01 * s01;
-    d2 = (((s11 * n0) * n0 - ((2.0 * s01) * n0) * n1) + (s00 * n1) * n1) / det;
-    return det > 0.0 && s00 > 0.0 && d2 < p.gate_chi2;
-}
 __device__ __forceinline__ void nn_take(NnBest &b, double d2, int j) {
     if (d2 < b.d2 || (d2 == b.d2 && j < b.j)) { b.second = b.d2; b.d2 = d2; b.j = j; }
     else if (d2 < b.second) b.second = d2;
@@ -83,17 +39,6 @@ __device__ __forceinline__ void nn_store(int i, const NnBest &b, int32_t *out_id
     out_idx[i] = b.j == NN_NONE ? -1 : b.j;
     if (out_d2) out_d2[i] = b.d2;
     if (out_second) out_second[i] = b.second;
-}
-
-// the observation's query, or an invalid one: i beyond n, or a pose index outside [0, n_poses) (nothing is read through it)
-__device__ __forceinline__ NnQuery nn_query_of(int i, int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs,
-                                               const double *pose_cov, double lidar, const NnDev &p) {
-    NnQuery q; q.valid = false; q.ty = 0; q.gx = q.gy = q.zx = q.zy = q.a00 = q.a01 = q.a11 = 0;
-    if (i >= n) return q;
-    const int pi = pose_of_obs[i];
-    if (pi < 0 || pi >= n_poses) return q;
-    const double4 o4 = reinterpret_cast<const double4 *>(obs)[i];              // (az, zen, dist, type) in one 32-byte load
-    return nn_query(poses + 3 * (size_t)pi, pose_cov ? pose_cov + 9 * (size_t)pi : nullptr, o4.x, o4.y, o4.z, o4.w, lidar, p);
 }
 
 __global__ void __launch_bounds__(256) k_assoc_nn(int n, const double *__restrict__ poses, int n_poses, const int32_t *__restrict__ pose_of_obs,
@@ -131,23 +76,10 @@ __global__ void __launch_bounds__(256) k_assoc_nn_grid(int n, const double *__re
     if (i >= n) return;
     const NnQuery q = nn_query_of(i, n, poses, n_poses, pose_of_obs, obs, pose_cov, lidar, p);
     NnBest b{__builtin_inf(), NN_NONE, __builtin_inf()};
-    if (q.valid) {
-        const long long cx = grid_coord(q.gx, g.inv_cell), cy = grid_coord(q.gy, g.inv_cell);
-        uint32_t bk[9]; int s0[9], s1[9];                                      // the nine buckets' ranges first: independent loads
-#pragma unroll
-        for (int k = 0; k < 9; ++k) { bk[k] = grid_bucket(cx + (k % 3) - 1, cy + (k / 3) - 1, g.mask); s0[k] = cell_start[bk[k]]; s1[k] = cell_start[bk[k] + 1]; }
-#pragma unroll
-        for (int k = 1; k < 9; ++k)                                            // two of the nine cells in ONE bucket: its cones are candidates once
-            for (int m = 0; m < k; ++m) if (bk[m] == bk[k]) s1[k] = s0[k];     // (a second visit would make a cone its own runner-up)
-#pragma unroll
-        for (int k = 0; k < 9; ++k)
-            for (int t = s0[k]; t < s1[k]; ++t) { const int j = cell_items[t];
-                const double2 xy = reinterpret_cast<const double2 *>(map_xy)[j];
-                double c00 = 0.0, c01 = 0.0, c11 = 0.0;
-                if (map_cov) { const double4 cv = reinterpret_cast<const double4 *>(map_cov)[j]; c00 = cv.x; c01 = cv.y; c11 = cv.w; }
-                double d2;
-                if (nn_pair(q, p, xy.x, xy.y, c00, c01, c11, map_type[j], d2)) nn_take(b, d2, j); }
-    }
+    const NnMap map{map_xy, map_type, map_cov};
+    if (q.valid)
+        grid_walk9(g, cell_start, cell_items, q.gx, q.gy, [&](int j) __attribute__((always_inline)) {
+            double d2; if (nn_candidate(map, j, q, p, d2)) nn_take(b, d2, j); });
     nn_store(i, b, out_idx, out_d2, out_second);
 }
 
@@ -159,14 +91,9 @@ __global__ void __launch_bounds__(256) k_frame_nn(int k, const double *__restric
     const double *ob = in + 12 + 4 * (size_t)i;
     const NnQuery q = nn_query(in, has_pose_cov ? in + 3 : nullptr, ob[0], ob[1], ob[2], ob[3], lidar, p);
     NnBest b{__builtin_inf(), NN_NONE, __builtin_inf()};
+    const NnMap map{map_xy, map_type, map_cov};
     if (q.valid)
-        for (int j = tid; j < n_map; j += 256) {
-            const double2 xy = reinterpret_cast<const double2 *>(map_xy)[j];
-            double c00 = 0.0, c01 = 0.0, c11 = 0.0;
-            if (map_cov) { const double4 cv = reinterpret_cast<const double4 *>(map_cov)[j]; c00 = cv.x; c01 = cv.y; c11 = cv.w; }
-            double d2;
-            if (nn_pair(q, p, xy.x, xy.y, c00, c01, c11, map_type[j], d2)) nn_take(b, d2, j);
-        }
+        for (int j = tid; j < n_map; j += 256) { double d2; if (nn_candidate(map, j, q, p, d2)) nn_take(b, d2, j); }
     // fixed order: lanes by halving distance inside a wave, then waves 0 .. 3
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
@@ -223,38 +150,6 @@ __device__ __forceinline__ void as_take(const AsTaken &tk, int j) {
 __device__ __forceinline__ void as_offer(double &bd, int &bj, double d2, int j, const AsTaken &tk) {
     if ((d2 < bd || (d2 == bd && j < bj)) && !as_taken(tk, j)) { bd = d2; bj = j; }
 }
-// (bd, bj) <- the query's best admissible cone that is not taken: the nine buckets of the grid (as k_assoc_nn_grid walks them) or the whole map
-template <bool GRID>
-__device__ __forceinline__ void as_search(const NnQuery &q, const NnDev &p, int n_map, const double *__restrict__ map_xy, const int32_t *__restrict__ map_type,
-        const double *__restrict__ map_cov, const GridParams &g, const int32_t *__restrict__ cell_start, const int32_t *__restrict__ cell_items,
-        const AsTaken &tk, double &bd, int &bj) {
-    if (GRID) {
-        const long long cx = grid_coord(q.gx, g.inv_cell), cy = grid_coord(q.gy, g.inv_cell);
-        uint32_t bk[9]; int s0[9], s1[9];
-#pragma unroll
-        for (int c = 0; c < 9; ++c) { bk[c] = grid_bucket(cx + (c % 3) - 1, cy + (c / 3) - 1, g.mask); s0[c] = cell_start[bk[c]]; s1[c] = cell_start[bk[c] + 1]; }
-#pragma unroll
-        for (int c = 1; c < 9; ++c)                                            // two of the nine cells in ONE bucket: walked once
-            for (int m = 0; m < c; ++m) if (bk[m] == bk[c]) s1[c] = s0[c];
-#pragma unroll
-        for (int c = 0; c < 9; ++c)
-            for (int t = s0[c]; t < s1[c]; ++t) { const int j = cell_items[t];
-                const double2 xy = reinterpret_cast<const double2 *>(map_xy)[j];
-                double c00 = 0.0, c01 = 0.0, c11 = 0.0;
-                if (map_cov) { const double4 cv = reinterpret_cast<const double4 *>(map_cov)[j]; c00 = cv.x; c01 = cv.y; c11 = cv.w; }
-                double d2;
-                if (nn_pair(q, p, xy.x, xy.y, c00, c01, c11, map_type[j], d2)) as_offer(bd, bj, d2, j, tk); }
-    } else {
-        for (int j = 0; j < n_map; ++j) {
-            const double2 xy = reinterpret_cast<const double2 *>(map_xy)[j];
-            double c00 = 0.0, c01 = 0.0, c11 = 0.0;
-            if (map_cov) { const double4 cv = reinterpret_cast<const double4 *>(map_cov)[j]; c00 = cv.x; c01 = cv.y; c11 = cv.w; }
-            double d2;
-            if (nn_pair(q, p, xy.x, xy.y, c00, c01, c11, map_type[j], d2)) as_offer(bd, bj, d2, j, tk);
-        }
-    }
-}
-
 template <bool GRID>
 __global__ void __launch_bounds__(256) k_assign_nn(int n, const double *__restrict__ poses, int n_poses, const int32_t *__restrict__ pose_of_obs,
         const double *__restrict__ obs, int n_frames, const int32_t *__restrict__ frame_start, int fpw, double lidar, int n_map,
@@ -267,27 +162,23 @@ __global__ void __launch_bounds__(256) k_assign_nn(int n, const double *__restri
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int f0 = (blockIdx.x * 4 + w) * fpw;                                 // this wave's frames: [f0, f0 + fpw), fpw in {1, 2, 4, 8}
     if (f0 >= n_frames) return;
-    // W lanes per frame: 64 / fpw when every frame of the wave fits, else the next power of two that holds the largest (wave-uniform)
-    int W = 64 / fpw;
-    for (int t = 0; t < fpw && f0 + t < n_frames; ++t) { const int a = frame_start[f0 + t], b = frame_start[f0 + t + 1];
-        if (a >= 0 && b >= a && b <= n && b - a <= AS_SLOTS * 64) while (W < 64 && W < b - a) W <<= 1; }
-    const int gp = 64 / W, gi = lane >> __builtin_ctz(W), lg = lane & (W - 1);    // frames per pass, this lane's group and its place in it
+    const FrameLanes l = frame_lanes(frame_start, f0, fpw, n_frames, n, NN_FRAME_MAX, lane);
+    const int W = l.W, gp = l.gp, gi = l.gi, lg = l.lg;
+    const NnMap map{map_xy, map_type, map_cov};
     const int tsz = W == 64 ? AS_TABLE : 2 * W;
     double *pd = s_d2[w]; int32_t *pj = s_j[w]; const AsTaken tk{s_taken[w] + gi * tsz, (uint32_t)tsz - 1};
     for (int ps = 0; ps * gp < fpw; ++ps) {                                    // 64 / W frames side by side, pass after pass
         int a = 0, b = 0;
         const int f = f0 + ps * gp + gi;
         if (ps * gp + gi < fpw && f < n_frames) {
-            a = frame_start[f]; b = frame_start[f + 1];
-            if (a < 0 || b < a || b > n) a = b = 0;                            // not a frame of this call: nothing read, nothing written
-            else if (b - a > AS_SLOTS * 64) {                                  // beyond GS_NN_FRAME_MAX: refused as a whole
-                for (int i = a + lg; i < b; i += W) { out_idx[i] = -1; if (out_d2) out_d2[i] = __builtin_inf(); }
-                a = b = 0; }
+            const FrameKind kind = frame_bounds(frame_start, n, f, a, b);
+            if (kind == FRAME_LARGE) for (int i = a + lg; i < b; i += W) { out_idx[i] = -1; if (out_d2) out_d2[i] = __builtin_inf(); }
+            if (kind != FRAME_OK) a = b = 0;
         }
         const int slots = (b - a + 63) >> 6;                                   // of this lane's frame: 0 (none), 1, or up to 4 when W == 64
         for (int t = lane; t < (W == 64 ? AS_TABLE : AS_PACKED_TABLE); t += 64) s_taken[w][t] = -1;
         for (int s = 0; s < slots; ++s) pj[s * 64 + lane] = a + s * 64 + lg < b ? AS_NEED : AS_DONE;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
         for (bool first = true;; first = false) {
             // (1) the search
             for (int s = 0; s < slots; ++s) {
@@ -296,7 +187,8 @@ __global__ void __launch_bounds__(256) k_assign_nn(int n, const double *__restri
                 const NnQuery q = nn_query_of(i, n, poses, n_poses, pose_of_obs, obs, pose_cov, lidar, p);
                 if (first && out_z) { out_z[2 * i] = q.zx; out_z[2 * i + 1] = q.zy; out_g[2 * i] = q.gx; out_g[2 * i + 1] = q.gy; }
                 double bd = __builtin_inf(); int bj = NN_NONE;
-                if (q.valid) as_search<GRID>(q, p, n_map, map_xy, map_type, map_cov, g, cell_start, cell_items, tk, bd, bj);
+                if (q.valid) map_walk<GRID>(n_map, g, cell_start, cell_items, q.gx, q.gy, [&](int j) __attribute__((always_inline)) {
+                    double d2; if (nn_candidate(map, j, q, p, d2)) as_offer(bd, bj, d2, j, tk); });
                 if (bj == NN_NONE) { out_idx[i] = -1; if (out_d2) out_d2[i] = __builtin_inf(); pj[e] = AS_DONE; }      // no open cone left: final
                 else { pd[e] = bd; pj[e] = bj; }
             }
@@ -317,7 +209,7 @@ __global__ void __launch_bounds__(256) k_assign_nn(int n, const double *__restri
                     if (a + s * 64 + lg == mi) { out_idx[mi] = mj; if (out_d2) out_d2[mi] = md; pj[e] = AS_DONE; }
                     else if (pj[e] == mj) pj[e] = AS_NEED; }
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_sync();
             if (__ballot(mi != NN_NONE) == 0) break;                           // wave-uniform: every frame of the pass is finished
         }
     }
@@ -337,9 +229,8 @@ __global__ void __launch_bounds__(256) k_assign_nn(int n, const double *__restri
 //             matched columns and is stored with the matched row (vm), the table maps a matched cone to its row (matched columns stay
 //             matched, so the table only grows); unmatched and dummy columns have v = 0.  A step either adds a row to the tree or ends
 //             the path: at most rows + 1 steps per row, and every loop below is bounded by the frame's rows, AO_CAND, or the table size.
-// Lanes: as k_assign_nn — W lanes per frame, 64 / W frames side by side in a wave, wave-scope fences only.  k_assign_opt runs four waves of
-// 64 rows each (frames of up to 64 observations; 9.5 KB of LDS a wave); k_assign_opt_big is ONE wave of 256 rows (38 KB) that takes the
-// frames above 64 — either every frame (the host expects large frames) or, after k_assign_opt, only those it left out.
+// Lanes: frames_small / frames_big, wave-scope syncs only.  k_assign_opt runs four waves of 64 rows each (9.5 KB of LDS a wave);
+// k_assign_opt_big is ONE wave of 256 rows (38 KB).
 static constexpr int AO_CAND = 8;                                              // GS_ASSIGN_CAND_MAX
 static constexpr int AO_DUMMY = 8, AO_NOMATE = 9;                              // a row's mate: a slot of its list, its dummy column, or nothing yet
 
@@ -351,14 +242,9 @@ template <int SLOTS> struct AoLds {
     int32_t tkey[TAB], tval[TAB];                                              // matched cone -> row (-1 = empty)
     int32_t cnt[ROWS], mate[ROWS], stamp[ROWS], pred[ROWS];                    // candidates; mate; the root whose tree holds the row; 16 * row + slot it was reached by
 };
-struct AoArgs {
-    int n; const double *poses; int n_poses; const int32_t *pose_of_obs; const double *obs; int n_frames; const int32_t *frame_start; int fpw, only_large;
-    double lidar; int n_map; const double *map_xy; const int32_t *map_type; const double *map_cov, *pose_cov; NnDev p; GridParams g;
-    const int32_t *cell_start, *cell_items; int32_t *out_idx; double *out_d2; int32_t *out_na; double *out_z, *out_g;
+struct AoArgs : FrameArgs {
+    const int32_t *map_type; GridParams g; const int32_t *cell_start, *cell_items; int32_t *out_idx; double *out_d2; int32_t *out_na; double *out_z, *out_g;
 };
-__device__ __forceinline__ void ao_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ uint32_t ao_hash(int j, uint32_t mask) { return (((uint32_t)j * 2654435761u) >> 21) & mask; }
 // the row matched to cone j, or -1
 __device__ __forceinline__ int ao_find(const int32_t *tkey, const int32_t *tval, uint32_t mask, int j) {
@@ -382,43 +268,13 @@ __device__ __forceinline__ void ao_insert(double (&bd)[AO_CAND], int (&bj)[AO_CA
     for (int t = 0; t < AO_CAND; ++t)
         if (d2 < bd[t] || (d2 == bd[t] && j < bj[t])) { const double td = bd[t]; const int tj = bj[t]; bd[t] = d2; bj[t] = j; d2 = td; j = tj; }
 }
-template <bool GRID>
-__device__ __forceinline__ void ao_collect(const NnQuery &q, const AoArgs &A, double (&bd)[AO_CAND], int (&bj)[AO_CAND], int &na) {
-    const double *__restrict__ map_xy = A.map_xy; const double *__restrict__ map_cov = A.map_cov; const int32_t *__restrict__ map_type = A.map_type;
-    if (GRID) {
-        const long long cx = grid_coord(q.gx, A.g.inv_cell), cy = grid_coord(q.gy, A.g.inv_cell);
-        uint32_t bk[9]; int s0[9], s1[9];
-#pragma unroll
-        for (int c = 0; c < 9; ++c) { bk[c] = grid_bucket(cx + (c % 3) - 1, cy + (c / 3) - 1, A.g.mask); s0[c] = A.cell_start[bk[c]]; s1[c] = A.cell_start[bk[c] + 1]; }
-#pragma unroll
-        for (int c = 1; c < 9; ++c)                                            // two of the nine cells in ONE bucket: walked once
-            for (int m = 0; m < c; ++m) if (bk[m] == bk[c]) s1[c] = s0[c];
-#pragma unroll
-        for (int c = 0; c < 9; ++c)
-            for (int t = s0[c]; t < s1[c]; ++t) { const int j = A.cell_items[t];
-                const double2 xy = reinterpret_cast<const double2 *>(map_xy)[j];
-                double c00 = 0.0, c01 = 0.0, c11 = 0.0;
-                if (map_cov) { const double4 cv = reinterpret_cast<const double4 *>(map_cov)[j]; c00 = cv.x; c01 = cv.y; c11 = cv.w; }
-                double d2;
-                if (nn_pair(q, A.p, xy.x, xy.y, c00, c01, c11, map_type[j], d2)) { ++na; ao_insert(bd, bj, d2, j); } }
-    } else {
-        for (int j = 0; j < A.n_map; ++j) {
-            const double2 xy = reinterpret_cast<const double2 *>(map_xy)[j];
-            double c00 = 0.0, c01 = 0.0, c11 = 0.0;
-            if (map_cov) { const double4 cv = reinterpret_cast<const double4 *>(map_cov)[j]; c00 = cv.x; c01 = cv.y; c11 = cv.w; }
-            double d2;
-            if (nn_pair(q, A.p, xy.x, xy.y, c00, c01, c11, map_type[j], d2)) { ++na; ao_insert(bd, bj, d2, j); }
-        }
-    }
-}
-
 // one pass of a wave: lane group gi (W lanes, lane lg of it) solves the frame [a, b) (a == b: none), b - a <= W (W < 64) or <= 64 * SLOTS
 template <bool GRID, int SLOTS>
 __device__ __forceinline__ void ao_pass(AoLds<SLOTS> &L, const AoArgs &A, int a, int b, int W, int gi, int lg, int lane) {
     const int k = b - a, eb = gi * W, slots = (k + 63) >> 6;                   // rows; the LDS row of the frame's row 0; rows per lane
     const int tsz = W == 64 ? AoLds<SLOTS>::TAB : 2 * W;                        // the frame's table: at least two words per row
     int32_t *tkey = L.tkey + gi * tsz, *tval = L.tval + gi * tsz; const uint32_t mask = (uint32_t)tsz - 1;
-    const double gate = A.p.gate_chi2;
+    const double gate = A.p.gate_chi2; const NnMap map{A.map_xy, A.map_type, A.map_cov};
     // COLLECT
     for (int t = lane; t < AoLds<SLOTS>::TAB; t += 64) L.tkey[t] = -1;
     for (int s = 0; s < slots; ++s) {
@@ -430,7 +286,8 @@ __device__ __forceinline__ void ao_pass(AoLds<SLOTS> &L, const AoArgs &A, int a,
             double bd[AO_CAND]; int bj[AO_CAND]; int na = 0;
 #pragma unroll
             for (int t = 0; t < AO_CAND; ++t) { bd[t] = __builtin_inf(); bj[t] = NN_NONE; }
-            if (q.valid) ao_collect<GRID>(q, A, bd, bj, na);
+            if (q.valid) map_walk<GRID>(A.n_map, A.g, A.cell_start, A.cell_items, q.gx, q.gy, [&](int j) __attribute__((always_inline)) {
+                double d2; if (nn_candidate(map, j, q, A.p, d2)) { ++na; ao_insert(bd, bj, d2, j); } });
             if (A.out_na) A.out_na[i] = na;
             c = na < AO_CAND ? na : AO_CAND;
 #pragma unroll
@@ -438,14 +295,14 @@ __device__ __forceinline__ void ao_pass(AoLds<SLOTS> &L, const AoArgs &A, int a,
         }
         L.cnt[e] = c; L.mate[e] = AO_NOMATE; L.stamp[e] = -1;
     }
-    ao_sync();
+    wave_sync();
     // SHORTCUT
     bool dup = false;
     for (int s = 0; s < slots; ++s) { const int rl = s * 64 + lg, e = eb + rl;
         if (rl < k && L.cnt[e] > 0 && !ao_claim(tkey, mask, L.cj[0][e])) dup = true; }
     const unsigned long long gm = W == 64 ? ~0ull : ((1ull << W) - 1) << eb;
     const bool contested = (__ballot(dup) & gm) != 0;                          // (uniform over the frame's lanes)
-    ao_sync();
+    wave_sync();
     if (!contested) {
         for (int s = 0; s < slots; ++s) { const int rl = s * 64 + lg, e = eb + rl;
             if (rl < k) { const bool m = L.cnt[e] > 0; A.out_idx[a + rl] = m ? L.cj[0][e] : -1; if (A.out_d2) A.out_d2[a + rl] = m ? L.cd[0][e] : __builtin_inf(); } }
@@ -455,7 +312,7 @@ __device__ __forceinline__ void ao_pass(AoLds<SLOTS> &L, const AoArgs &A, int a,
     int root = k;
     if (contested) { root = 0; while (root < k && L.cnt[eb + root] == 0) ++root;
         if (lg == 0 && root < k) { L.stamp[eb + root] = root; L.rd[eb + root] = 0.0; L.u[eb + root] = 0.0; } }
-    ao_sync();
+    wave_sync();
     const int cap = W == 64 ? 64 * SLOTS : W, maxit = (cap + 2) * (cap + 2);  // rows * (rows + 1) steps at the most: a hard stop all the same
     for (int it = 0; it < maxit; ++it) {
         const bool act = root < k;
@@ -493,7 +350,7 @@ __device__ __forceinline__ void ao_pass(AoLds<SLOTS> &L, const AoArgs &A, int a,
         if (term)
             for (int s = 0; s < slots; ++s) { const int rl = s * 64 + lg, e = eb + rl;
                 if (rl < k && L.stamp[e] == root) { const double dl = mk - L.rd[e]; L.u[e] += dl; if (rl != root) L.vm[e] -= dl; } }
-        ao_sync();
+        wave_sync();
         if (term) {
             if (lg == 0) {
                 int row = mr, slot = ms; double cv = 0.0;
@@ -508,47 +365,27 @@ __device__ __forceinline__ void ao_pass(AoLds<SLOTS> &L, const AoArgs &A, int a,
             ++root; while (root < k && L.cnt[eb + root] == 0) ++root;
             if (lg == 0 && root < k) { L.stamp[eb + root] = root; L.rd[eb + root] = 0.0; L.u[eb + root] = 0.0; }
         }
-        ao_sync();
+        wave_sync();
     }
     if (contested)
         for (int s = 0; s < slots; ++s) { const int rl = s * 64 + lg, e = eb + rl;
             if (rl < k) { const int m = L.mate[e]; A.out_idx[a + rl] = m < AO_CAND ? L.cj[m][e] : -1;
                 if (A.out_d2) A.out_d2[a + rl] = m < AO_CAND ? L.cd[m][e] : __builtin_inf(); } }
-    ao_sync();                                                                 // the next pass fills the same LDS
-}
-// a frame of the call, or none: bounds outside 0 <= a <= b <= n read and write nothing; above GS_NN_FRAME_MAX: -1 / +inf / 0 (when `refuse`)
-__device__ __forceinline__ void ao_frame(const AoArgs &A, int f, bool refuse, int lg, int W, int &a, int &b) {
-    a = A.frame_start[f]; b = A.frame_start[f + 1];
-    if (a < 0 || b < a || b > A.n) a = b = 0;
-    else if (b - a > 256) {
-        if (refuse) for (int i = a + lg; i < b; i += W) { A.out_idx[i] = -1; if (A.out_d2) A.out_d2[i] = __builtin_inf(); if (A.out_na) A.out_na[i] = 0; }
-        a = b = 0; }
+    wave_sync();                                                                 // the next pass fills the same LDS
 }
 template <bool GRID>
 __global__ void __launch_bounds__(256) k_assign_opt(AoArgs A) {
     __shared__ AoLds<1> Ls[4];
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int f0 = (blockIdx.x * 4 + w) * A.fpw;                               // this wave's frames: [f0, f0 + fpw), fpw in {2, 4, 8}
-    if (f0 >= A.n_frames) return;
-    int W = 64 / A.fpw;                                                        // as k_assign_nn; frames above 64 are k_assign_opt_big's
-    for (int t = 0; t < A.fpw && f0 + t < A.n_frames; ++t) { const int a = A.frame_start[f0 + t], b = A.frame_start[f0 + t + 1];
-        if (a >= 0 && b >= a && b <= A.n && b - a <= 64) while (W < 64 && W < b - a) W <<= 1; }
-    const int gp = 64 / W, gi = lane >> __builtin_ctz(W), lg = lane & (W - 1);
-    for (int ps = 0; ps * gp < A.fpw; ++ps) {
-        int a = 0, b = 0; const int f = f0 + ps * gp + gi;
-        if (ps * gp + gi < A.fpw && f < A.n_frames) { ao_frame(A, f, false, lg, W, a, b); if (b - a > 64) a = b = 0; }
-        ao_pass<GRID, 1>(Ls[w], A, a, b, W, gi, lg, lane);
-    }
+    frames_small(A, [&](int, int a, int b, const FrameLanes &l, int lane) __attribute__((always_inline)) {
+        ao_pass<GRID, 1>(Ls[threadIdx.x >> 6], A, a, b, l.W, l.gi, l.lg, lane); });
 }
 template <bool GRID>
 __global__ void __launch_bounds__(64) k_assign_opt_big(AoArgs A) {
     __shared__ AoLds<4> L;
-    const int lane = threadIdx.x, f0 = blockIdx.x * A.fpw;
-    for (int t = 0; t < A.fpw && f0 + t < A.n_frames; ++t) {
-        int a, b; ao_frame(A, f0 + t, true, lane, 64, a, b);
-        if (b == a || (A.only_large && b - a <= 64)) continue;                 // (wave-uniform)
-        ao_pass<GRID, 4>(L, A, a, b, 64, 0, lane, lane);
-    }
+    frames_big(A, [&](int, int a, int b, int lane) __attribute__((always_inline)) {      // refused: -1 / +inf / 0
+                   for (int i = a + lane; i < b; i += 64) { A.out_idx[i] = -1; if (A.out_d2) A.out_d2[i] = __builtin_inf(); if (A.out_na) A.out_na[i] = 0; } },
+               [&](int, int a, int b, const FrameLanes &l, int lane) __attribute__((always_inline)) {
+                   if (b > a) ao_pass<GRID, 4>(L, A, a, b, l.W, l.gi, l.lg, lane); });
 }
 
 // ---- joint compatibility of a frame's hypothesis (include/graphslam.h, "joint compatibility"): the pairs (i, in_idx[i]) of a frame share ONE
@@ -561,13 +398,13 @@ __global__ void __launch_bounds__(64) k_assign_opt_big(AoArgs A) {
 //           the bits do not depend on how many lanes W the frame was given) — and the 3x3 solve, on every lane.  J < gate[kept]: finished.
 //           Otherwise every kept row solves for (sums - its own terms) and the row of smallest (J, row) leaves.  The sums are recomputed from
 //           the kept rows in every round, never carried: a round's error does not depend on the rounds before it.
-// Lanes as k_assign_opt: W lanes per frame, 64 / W frames side by side; at most rows + 1 rounds; no barrier, no scratch, no wait.
-static constexpr int JC_TERMS = 10;                                            // a, c0 c1 c2, m00 m01 m02 m11 m12 m22
+// Lanes as frames_small / frames_big give them, W per frame and 64 / W frames side by side, but through this section's own copy of the two
+// drivers, and jc_pass finds the frame's pose and sums the rows in its own text (lo_pass repeats both): with the shared drivers and a shared
+// pose search and sum k_joint_compat measured 1.0 .. 1.4 % slower than before on an MI355X (profiles/assoc_scaffold_time.txt), with its own
+// it does not.  At most rows + 1 rounds; no barrier, no scratch, no wait.
 template <int SLOTS> struct JcLds { double t[JC_TERMS][64 * SLOTS]; int32_t kj[64 * SLOTS]; };       // kj: the row's cone while it is kept, else -1
-struct JcArgs {
-    int n; const double *poses; int n_poses; const int32_t *pose_of_obs; const double *obs; int n_frames; const int32_t *frame_start; int fpw, only_large;
-    double lidar; int n_map; const double *map_xy, *map_cov, *pose_cov; NnDev p; const int32_t *in_idx;
-    int32_t *out_idx; double *out_j; int32_t *out_kept, *out_dropped, *out_untestable; double *out_delta; JcGate gate;
+struct JcArgs : FrameArgs {
+    const int32_t *in_idx; int32_t *out_idx; double *out_j; int32_t *out_kept, *out_dropped, *out_untestable; double *out_delta; JcGate gate;
 };
 // (the solve in three pieces, so that lo_pass below runs the same operations.)  P = Sigma_p's upper triangle (p00 p01 p02 p11 p12 p22)
 // K = the nine cofactors of A = I + M Sigma_p (K[3 r + s] = C_rs) and det A, from the sums' M (S[4 .. 9])
@@ -637,22 +474,13 @@ __device__ __forceinline__ void jc_pass(JcLds<SLOTS> &L, const JcArgs &A, int fw
                 const NnQuery q = nn_query_of(i, A.n, A.poses, A.n_poses, A.pose_of_obs, A.obs, nullptr, A.lidar, A.p);      // a = Q alone
                 bool ok = q.valid && j >= 0 && j < A.n_map;
                 if (ok) {
-                    const double2 xy = reinterpret_cast<const double2 *>(A.map_xy)[j];
-                    double c00 = 0.0, c01 = 0.0, c11 = 0.0;
-                    if (A.map_cov) { const double4 cv = reinterpret_cast<const double4 *>(A.map_cov)[j]; c00 = cv.x; c01 = cv.y; c11 = cv.w; }
-                    const double n0 = xy.x - q.gx, n1 = xy.y - q.gy;
-                    const double d00 = c00 + q.a00, d01 = c01 + q.a01, d11 = c11 + q.a11;
-                    const double det = d00 * d11 - d01 * d01;
-                    ok = det > 0.0 && d00 > 0.0;
+                    const PairNu v = pair_nu(q, nn_cone(A.map_xy, A.map_cov, j));
+                    ok = v.det > 0.0 && v.d00 > 0.0;
                     if (ok) {
-                        double sn, cs; sincos(A.poses[3 * (size_t)plo + 2], &sn, &cs);
-                        const double ux = -(q.zx * sn + q.zy * cs), uy = q.zx * cs - q.zy * sn;      // wp = (-w_y, w_x), w as nn_query forms it
-                        const double y0 = (d11 * n0 - d01 * n1) / det, y1 = (d00 * n1 - d01 * n0) / det;
-                        const double e00 = d11 / det, e01 = -(d01 / det), e11 = d00 / det;           // D^-1
-                        const double h0 = e00 * ux + e01 * uy, h1 = e01 * ux + e11 * uy;             // D^-1 wp
-                        L.t[0][e] = (((d11 * n0) * n0 - ((2.0 * d01) * n0) * n1) + (d00 * n1) * n1) / det;      // nn_pair's d2
-                        L.t[1][e] = y0; L.t[2][e] = y1; L.t[3][e] = ux * y0 + uy * y1;
-                        L.t[4][e] = e00; L.t[5][e] = e01; L.t[6][e] = h0; L.t[7][e] = e11; L.t[8][e] = h1; L.t[9][e] = ux * h0 + uy * h1;
+                        double sn, cs, T[JC_TERMS]; sincos(A.poses[3 * (size_t)plo + 2], &sn, &cs);
+                        pair_terms(q, v, sn, cs, T);
+#pragma unroll
+                        for (int t = 0; t < JC_TERMS; ++t) L.t[t][e] = T[t];
                         keep = j;
                     }
                 }
@@ -734,7 +562,7 @@ __global__ void __launch_bounds__(256) k_joint_compat(JcArgs A) {
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int f0 = (blockIdx.x * 4 + w) * A.fpw;                               // this wave's frames: [f0, f0 + fpw), fpw in {2, 4, 8}
     if (f0 >= A.n_frames) return;
-    int W = 64 / A.fpw;                                                        // as k_assign_opt; frames above 64 are k_joint_compat_big's
+    int W = 64 / A.fpw;                                                        // (frame_lanes' text) frames above 64 are k_joint_compat_big's
     for (int t = 0; t < A.fpw && f0 + t < A.n_frames; ++t) { const int a = A.frame_start[f0 + t], b = A.frame_start[f0 + t + 1];
         if (a >= 0 && b >= a && b <= A.n && b - a <= 64) while (W < 64 && W < b - a) W <<= 1; }
     const int gp = 64 / W, gi = lane >> __builtin_ctz(W), lg = lane & (W - 1);
@@ -761,11 +589,11 @@ __global__ void __launch_bounds__(64) k_joint_compat_big(JcArgs A) {
 //   FETCH   what no iteration changes, once: z (the A0 conversion), l_j, Sigma_j — seven doubles a row, in registers for frames up to 64
 //           (a row per lane), in LDS term-major for the large form (only the lane that wrote a row reads it); a row that can never count
 //           (no pair, an index outside the map, a pose index out of range) is left out by a bit of `live`
-//   ITERATE the pair terms at x_k (nn_query_at without a pose covariance, then the joint test's D, y, E, h), the sums of c, M and the count in
+//   ITERATE the pair terms at x_k (nn_query_at without a pose covariance, then pair_nu and pair_terms), the sums of c, M and the count in
 //           the joint test's fixed order, the 3x3 solve on every lane (jc_step), the stop tests; a __ballot over the frames still open ends
 //           the loop, max_iterations bounds it
 //   FINAL   the pair terms with a (nn_pair's d2), the sums, the cofactors of A once more (jc_cofactors), Sigma+ and chi2
-// Lanes as k_joint_compat: W lanes per frame, 64 / W frames side by side; no barrier, no scratch, no wait, nothing written per observation.
+// Lanes: frames_small / frames_big; no barrier, no scratch, no wait, nothing written per observation.
 static constexpr int LO_FIXED = 7;                                             // zx zy lx ly c00 c01 c11
 template <int SLOTS> struct LoRows;
 template <> struct LoRows<1> {                                                 // a row per lane: registers
@@ -787,9 +615,8 @@ template <> struct LoRows<4> {                                                 /
 #pragma unroll
         for (int t = 0; t < LO_FIXED; ++t) v[t] = L->f[t][s * 64 + lane]; }
 };
-struct LoArgs {
-    int n; const double *poses; int n_poses; const int32_t *pose_of_obs; const double *obs; int n_frames; const int32_t *frame_start; int fpw, only_large;
-    double lidar; int n_map; const double *map_xy, *map_cov, *pose_cov; NnDev p; const int32_t *in_idx; int max_it; double tol_xy, tol_th;
+struct LoArgs : FrameArgs {
+    const int32_t *in_idx; int max_it; double tol_xy, tol_th;
     double *out_pose, *out_cov, *out_chi2; int32_t *out_pairs, *out_iters, *out_status; double *out_step;
 };
 __device__ __forceinline__ double lo_normalize_theta(double th) {             // g2o normalize_theta, as in gs_kernels.hip (k_update)
@@ -803,26 +630,22 @@ __device__ __forceinline__ double lo_normalize_theta(double th) {             //
     return th;
 }
 // one row's terms at the pose (sn, cs: its heading's sin / cos) ADDED to S (a, c[3], M[6]: jc_solve's layout) when the pair counts; FINAL: a
-// and M, else c and M.  The expressions are jc_pass's
+// and M, else c and M (the terms not added are never computed: everything here is inlined)
 template <bool FINAL>
 __device__ __forceinline__ bool lo_row(const double (&v)[LO_FIXED], const double (&pose)[3], double sn, double cs, const NnDev &p, double (&S)[JC_TERMS]) {
 #pragma clang fp contract(off)
     const NnQuery q = nn_query_at(pose, nullptr, make_double2(v[0], v[1]), sn, cs, 0.0, p);
     if (!q.valid) return false;
-    const double n0 = v[2] - q.gx, n1 = v[3] - q.gy;
-    const double d00 = v[4] + q.a00, d01 = v[5] + q.a01, d11 = v[6] + q.a11;
-    const double det = d00 * d11 - d01 * d01;
-    if (!(det > 0.0 && d00 > 0.0 && isfinite(n0) && isfinite(n1))) return false;     // (a non-finite cone position never counts)
-    const double ux = -(q.zx * sn + q.zy * cs), uy = q.zx * cs - q.zy * sn;  // wp = (-w_y, w_x), w as nn_query forms it
-    const double e00 = d11 / det, e01 = -(d01 / det), e11 = d00 / det;       // D^-1
-    const double h0 = e00 * ux + e01 * uy, h1 = e01 * ux + e11 * uy;         // D^-1 wp
-    if (FINAL) S[0] += (((d11 * n0) * n0 - ((2.0 * d01) * n0) * n1) + (d00 * n1) * n1) / det;      // nn_pair's d2
-    else { const double y0 = (d11 * n0 - d01 * n1) / det, y1 = (d00 * n1 - d01 * n0) / det;
-        S[1] += y0; S[2] += y1; S[3] += ux * y0 + uy * y1; }
-    S[4] += e00; S[5] += e01; S[6] += h0; S[7] += e11; S[8] += h1; S[9] += ux * h0 + uy * h1;
+    const PairNu nu = pair_nu(q, NnCone{v[2], v[3], v[4], v[5], v[6]});
+    if (!(nu.det > 0.0 && nu.d00 > 0.0 && isfinite(nu.n0) && isfinite(nu.n1))) return false;     // (a non-finite cone position never counts)
+    double T[JC_TERMS]; pair_terms(q, nu, sn, cs, T);
+    if (FINAL) S[0] += T[0];
+    else { S[1] += T[1]; S[2] += T[2]; S[3] += T[3]; }
+#pragma unroll
+    for (int t = 4; t < JC_TERMS; ++t) S[t] += T[t];
     return true;
 }
-// the sums of the frame's live rows at the pose, in the fixed order: a lane's rows ascending from +0, then the butterfly inside the W lanes
+// the sums of the frame's live rows at the pose, in the fixed order of jc_pass: a lane's rows ascending from +0, then the butterfly inside the W lanes
 template <int SLOTS, bool FINAL>
 __device__ __forceinline__ int lo_sums(const LoRows<SLOTS> &R, const LoArgs &A, int live, int slots, int W, int lane, const double (&pose)[3], double (&S)[JC_TERMS]) {
     double sn, cs; sincos(pose[2], &sn, &cs);
@@ -857,7 +680,7 @@ template <int SLOTS>
 __device__ __forceinline__ void lo_pass(LoRows<SLOTS> &R, const LoArgs &A, int fw, int a, int b, int W, int lg, int lane) {
 #pragma clang fp contract(off)
     const int k = fw < 0 ? 0 : b - a, slots = (k + 63) >> 6;
-    // the frame's pose, as jc_pass finds it
+    // the frame's pose, found as in jc_pass
     int plo = NN_NONE, phi = -1;
     for (int s = 0; s < slots; ++s) { const int rl = s * 64 + lg;
         if (rl < k) { const int pi = A.pose_of_obs[a + rl]; if (pi >= 0 && pi < A.n_poses) { plo = min(plo, pi); phi = max(phi, pi); } } }
@@ -879,9 +702,8 @@ __device__ __forceinline__ void lo_pass(LoRows<SLOTS> &R, const LoArgs &A, int f
             const int i = a + rl, j = A.in_idx[i], pi = A.pose_of_obs[i];
             if (j >= 0 && j < A.n_map && pi >= 0 && pi < A.n_poses) {
                 const double4 o4 = reinterpret_cast<const double4 *>(A.obs)[i];
-                const double2 z = nn_polar(o4.x, o4.y, o4.z, A.lidar), xy = reinterpret_cast<const double2 *>(A.map_xy)[j];
-                double v[LO_FIXED] = {z.x, z.y, xy.x, xy.y, 0.0, 0.0, 0.0};
-                if (A.map_cov) { const double4 cv = reinterpret_cast<const double4 *>(A.map_cov)[j]; v[4] = cv.x; v[5] = cv.y; v[6] = cv.w; }
+                const double2 z = nn_polar(o4.x, o4.y, o4.z, A.lidar); const NnCone c = nn_cone(A.map_xy, A.map_cov, j);
+                const double v[LO_FIXED] = {z.x, z.y, c.x, c.y, c.c00, c.c01, c.c11};
                 R.put(s, lane, v); live |= 1 << s;
             }
         }
@@ -933,40 +755,18 @@ __device__ __forceinline__ void lo_pass(LoRows<SLOTS> &R, const LoArgs &A, int f
     xf[2] = lo_normalize_theta(xf[2]);                                         // k_update's addition and normalisation
     lo_write(A, fw, xf, cv, chi2, pairs, iters, status, d);
 }
-// frame f of the call, as jc_frame: bounds outside 0 <= a <= b <= n: not a frame, nothing read or written; above GS_NN_FRAME_MAX (when
-// `refuse`): the record of a refused frame, and not a frame for the pass
-__device__ __forceinline__ bool lo_frame(const LoArgs &A, int f, bool refuse, int lg, int &a, int &b) {
-    a = A.frame_start[f]; b = A.frame_start[f + 1];
-    if (a < 0 || b < a || b > A.n) return false;
-    if (b - a <= 256) return true;
-    if (refuse && lg == 0) { const double zero3[3] = {0.0, 0.0, 0.0}, zero6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-        lo_write(A, f, zero3, zero6, __builtin_inf(), 0, 0, 4, zero3); }
-    return false;
-}
 __global__ void __launch_bounds__(256) k_localize(LoArgs A) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int f0 = (blockIdx.x * 4 + w) * A.fpw;                               // this wave's frames: [f0, f0 + fpw), fpw in {2, 4, 8}
-    if (f0 >= A.n_frames) return;
-    int W = 64 / A.fpw;                                                        // as k_joint_compat; frames above 64 are k_localize_big's
-    for (int t = 0; t < A.fpw && f0 + t < A.n_frames; ++t) { const int a = A.frame_start[f0 + t], b = A.frame_start[f0 + t + 1];
-        if (a >= 0 && b >= a && b <= A.n && b - a <= 64) while (W < 64 && W < b - a) W <<= 1; }
-    const int gp = 64 / W, gi = lane >> __builtin_ctz(W), lg = lane & (W - 1);
-    for (int ps = 0; ps * gp < A.fpw; ++ps) {
-        int a = 0, b = 0, fw = -1; const int f = f0 + ps * gp + gi;
-        if (ps * gp + gi < A.fpw && f < A.n_frames && lo_frame(A, f, false, lg, a, b) && b - a <= 64) fw = f;
+    frames_small(A, [&](int fw, int a, int b, const FrameLanes &l, int lane) __attribute__((always_inline)) {
         LoRows<1> R;
-        lo_pass<1>(R, A, fw, a, b, W, lg, lane);
-    }
+        lo_pass<1>(R, A, fw, a, b, l.W, l.lg, lane); });
 }
 __global__ void __launch_bounds__(64) k_localize_big(LoArgs A) {
     __shared__ LoLds L;
-    const int lane = threadIdx.x, f0 = blockIdx.x * A.fpw;
     LoRows<4> R{&L};
-    for (int t = 0; t < A.fpw && f0 + t < A.n_frames; ++t) {
-        int a, b;
-        if (!lo_frame(A, f0 + t, true, lane, a, b) || (A.only_large && b - a <= 64)) continue;      // (wave-uniform)
-        lo_pass<4>(R, A, f0 + t, a, b, 64, lane, lane);
-    }
+    frames_big(A, [&](int f, int, int, int lane) __attribute__((always_inline)) {         // refused: the record of status 4
+                   const double zero3[3] = {0.0, 0.0, 0.0}, zero6[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+                   if (lane == 0) lo_write(A, f, zero3, zero6, __builtin_inf(), 0, 0, 4, zero3); },
+               [&](int f, int a, int b, const FrameLanes &l, int lane) __attribute__((always_inline)) { lo_pass<4>(R, A, f, a, b, l.W, l.lg, lane); });
 }
 
 void launch_assoc_nn(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, double lidar, int n_map,
@@ -997,10 +797,7 @@ void launch_assign_nn(int n, const double *poses, int n_poses, const int32_t *po
                       long long buckets, const int32_t *cell_start, const int32_t *cell_items, int32_t *out_idx, double *out_d2, double *out_z, double *out_g,
                       hipStream_t st, hipEvent_t start, hipEvent_t stop) {
     if (n <= 0 || n_frames <= 0) return;
-    // frames per wave from the MEAN frame size (the host does not see the resident call's offsets): a guess that costs time when it is
-    // wrong — the kernel widens W to its largest frame and runs passes — and never changes a result
-    const long long mean = ((long long)n + n_frames - 1) / n_frames;
-    const int fpw = mean <= 8 ? 8 : mean <= 16 ? 4 : mean <= 32 ? 2 : 1;
+    const int fpw = frames_per_wave(mean_frame(n, n_frames));
     const dim3 grid((n_frames + 4 * fpw - 1) / (4 * fpw)), block(256);
     if (cell_start) hipExtLaunchKernelGGL(k_assign_nn<true>, grid, block, 0, st, start, stop, 0, n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, fpw, lidar,
                                           n_map, map_xy, map_type, map_cov, pose_cov, p, grid_params_of(p.max_distance, buckets), cell_start, cell_items,
@@ -1013,54 +810,28 @@ void launch_assign_opt(int n, const double *poses, int n_poses, const int32_t *p
                        long long buckets, const int32_t *cell_start, const int32_t *cell_items, int32_t *out_idx, double *out_d2, int32_t *out_na,
                        double *out_z, double *out_g, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
     if (n <= 0 || n_frames <= 0) return;
-    // the MEAN frame size decides speed only, as in launch_assign_nn.  Up to 32: k_assign_opt (2 .. 8 frames a wave, frames of up to 64),
-    // then k_assign_opt_big over groups of 64 frames for those above 64 (its waves find none as a rule).  Above: k_assign_opt_big alone,
-    // a wave per frame.  start sits on the first dispatch and stop on the last.
-    const long long mean = ((long long)n + n_frames - 1) / n_frames;
-    AoArgs A{n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, 1, 0, lidar, n_map, map_xy, map_type, map_cov, pose_cov, p,
-             cell_start ? grid_params_of(p.max_distance, buckets) : GridParams{}, cell_start, cell_items, out_idx, out_d2, out_na, out_z, out_g};
-    if (mean <= 32) {
-        A.fpw = mean <= 8 ? 8 : mean <= 16 ? 4 : 2;
-        const dim3 grid((n_frames + 4 * A.fpw - 1) / (4 * A.fpw)), block(256);
-        if (cell_start) hipExtLaunchKernelGGL(k_assign_opt<true>, grid, block, 0, st, start, nullptr, 0, A);
-        else hipExtLaunchKernelGGL(k_assign_opt<false>, grid, block, 0, st, start, nullptr, 0, A);
-        A.fpw = 64; A.only_large = 1; start = nullptr;
-    }
-    const dim3 grid((n_frames + A.fpw - 1) / A.fpw), block(64);
-    if (cell_start) hipExtLaunchKernelGGL(k_assign_opt_big<true>, grid, block, 0, st, start, stop, 0, A);
-    else hipExtLaunchKernelGGL(k_assign_opt_big<false>, grid, block, 0, st, start, stop, 0, A);
+    const AoArgs A{{n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, 1, 0, lidar, n_map, map_xy, map_cov, pose_cov, p}, map_type,
+                   cell_start ? grid_params_of(p.max_distance, buckets) : GridParams{}, cell_start, cell_items, out_idx, out_d2, out_na, out_z, out_g};
+    if (cell_start) launch_small_then_big(A, -1, k_assign_opt<true>, k_assign_opt_big<true>, st, start, stop);
+    else launch_small_then_big(A, -1, k_assign_opt<false>, k_assign_opt_big<false>, st, start, stop);
 }
 void launch_joint_compat(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, int n_frames, const int32_t *frame_start,
                          double lidar, int n_map, const double *map_xy, const double *map_cov, const double *pose_cov, NnDev p, const JcGate &gate,
                          const int32_t *in_idx, int32_t *out_idx, double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable,
                          double *out_delta, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
     if (n_frames <= 0) return;
-    // the kernels by the MEAN frame size, exactly as launch_assign_opt: it decides speed only
-    const long long mean = ((long long)n + n_frames - 1) / n_frames;
-    JcArgs A{n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, 1, 0, lidar, n_map, map_xy, map_cov, pose_cov, p, in_idx,
-             out_idx, out_j, out_kept, out_dropped, out_untestable, out_delta, gate};
-    if (mean <= 32) {
-        A.fpw = mean <= 8 ? 8 : mean <= 16 ? 4 : 2;
-        hipExtLaunchKernelGGL(k_joint_compat, dim3((n_frames + 4 * A.fpw - 1) / (4 * A.fpw)), dim3(256), 0, st, start, nullptr, 0, A);
-        A.fpw = 64; A.only_large = 1; start = nullptr;
-    }
-    hipExtLaunchKernelGGL(k_joint_compat_big, dim3((n_frames + A.fpw - 1) / A.fpw), dim3(64), 0, st, start, stop, 0, A);
+    const JcArgs A{{n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, 1, 0, lidar, n_map, map_xy, map_cov, pose_cov, p}, in_idx,
+                   out_idx, out_j, out_kept, out_dropped, out_untestable, out_delta, gate};
+    launch_small_then_big(A, -1, k_joint_compat, k_joint_compat_big, st, start, stop);
 }
+// kernel 0 / 1 (gs_debug_localize) forces k_localize (with k_localize_big behind it for the frames above 64) / k_localize_big alone
 void launch_localize(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, int n_frames, const int32_t *frame_start,
                      double lidar, int n_map, const double *map_xy, const double *map_cov, const double *pose_cov, NnDev p, const LoParams &lp,
                      const int32_t *in_idx, const LoOut &o, int kernel, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
     if (n_frames <= 0) return;
-    // the kernels by the MEAN frame size, exactly as launch_joint_compat: it decides speed only.  kernel 0 / 1 (gs_debug_localize) forces
-    // k_localize (with k_localize_big behind it for the frames above 64) / k_localize_big alone
-    const long long mean = ((long long)n + n_frames - 1) / n_frames;
-    LoArgs A{n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, 1, 0, lidar, n_map, map_xy, map_cov, pose_cov, p, in_idx, lp.max_iterations, lp.tol_xy,
-             lp.tol_theta, o.pose, o.cov, o.chi2, o.n_pairs, o.iterations, o.status, o.step};
-    if (kernel == 0 || (kernel < 0 && mean <= 32)) {
-        A.fpw = mean <= 8 ? 8 : mean <= 16 ? 4 : 2;
-        hipExtLaunchKernelGGL(k_localize, dim3((n_frames + 4 * A.fpw - 1) / (4 * A.fpw)), dim3(256), 0, st, start, nullptr, 0, A);
-        A.fpw = 64; A.only_large = 1; start = nullptr;
-    }
-    hipExtLaunchKernelGGL(k_localize_big, dim3((n_frames + A.fpw - 1) / A.fpw), dim3(64), 0, st, start, stop, 0, A);
+    const LoArgs A{{n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, 1, 0, lidar, n_map, map_xy, map_cov, pose_cov, p}, in_idx,
+                   lp.max_iterations, lp.tol_xy, lp.tol_theta, o.pose, o.cov, o.chi2, o.n_pairs, o.iterations, o.status, o.step};
+    launch_small_then_big(A, kernel, k_localize, k_localize_big, st, start, stop);
 }
 
 }  // namespace gs

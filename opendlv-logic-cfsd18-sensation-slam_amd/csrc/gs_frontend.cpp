@@ -34,6 +34,60 @@ static int arena_reserve(gs_graph *g, size_t bytes) {
     return GS_OK;
 }
 static size_t padded(size_t n, size_t elem) { return (std::max<size_t>(n, 1) * elem + 255) & ~(size_t)255; }
+namespace {
+// a batch call's device memory: the pieces it names, in the order it names them, carved from the handle's arena — whose size is the sum over
+// the same list, so the two cannot drift — and uploaded where a host array is given.  Valid until the next front-end call
+struct Staging {
+    struct Piece { void **dev; const void *host; size_t bytes; };
+    gs_graph *g; std::vector<Piece> pieces{};
+    // `count` elements at dev once commit() has run; host null: not uploaded (an output, scratch, or an optional input that is absent)
+    template <class T> void add(T *&dev, size_t count, const T *host = nullptr) { pieces.push_back(Piece{(void **)&dev, host, count * sizeof(T)}); }
+    int commit() {
+        size_t total = 0; for (const Piece &p : pieces) total += padded(p.bytes, 1);
+        const int rc = arena_reserve(g, total); if (rc != GS_OK) return rc;
+        size_t off = 0;
+        for (const Piece &p : pieces) { *p.dev = g->fe.arena + off; off += padded(p.bytes, 1);
+            if (p.host && p.bytes) HIP_TRY(hipMemcpyAsync(*p.dev, p.host, p.bytes, hipMemcpyHostToDevice, g->stream)); }
+        return GS_OK;
+    }
+    // a result back to the host, when the caller asked for it; after a copy that failed nothing more is enqueued, and finish() says so
+    int err = GS_OK;
+    void fetch(void *dst, const void *src, size_t bytes) {
+        if (err != GS_OK || !dst || !bytes) return;
+        const hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, g->stream);
+        if (e != hipSuccess) err = fail(GS_ERR_HIP, std::string("result copy: ") + hipGetErrorString(e));
+    }
+    // the one wait of the call (the result copies), and what the launches left behind
+    int finish(const char *what) {
+        if (err != GS_OK) return err;
+        HIP_TRY(hipStreamSynchronize(g->stream));
+        const hipError_t e = hipGetLastError();
+        return e == hipSuccess ? GS_OK : fail(GS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    }
+};
+}
+// bench / profiling hooks (graphslam_debug.h): one warming call of the resident entry point (which also builds its grid), then `reps` calls,
+// each with a start / stop event pair that the entry point attaches to its first / last dispatch (g->ev_lin: the kernels' own begin -> end);
+// mean milliseconds per call
+template <class Once>
+static int time_resident(gs_graph *g, int32_t reps, double *out_ms, Once once) {
+    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
+    int rc = once(); if (rc != GS_OK) return rc;
+    std::vector<hipEvent_t> ev(2 * (size_t)reps); for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
+    for (int r = 0; r < reps && rc == GS_OK; ++r) { g->ev_lin[0] = ev[2 * (size_t)r]; g->ev_lin[1] = ev[2 * (size_t)r + 1]; rc = once(); }
+    g->ev_lin[0] = g->ev_lin[1] = nullptr;
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    double tot = 0; int cnt = 0;
+    for (int r = 0; r < reps; ++r) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]) == hipSuccess && ms > 0) { tot += ms; ++cnt; } }
+    (void)hipGetLastError();
+    for (auto &e : ev) hipEventDestroy(e);
+    *out_ms = cnt ? tot / cnt : 0.0;
+    return rc;
+}
+static int dev_obs_aligned(const double *dev_obs) {
+    if (((uintptr_t)dev_obs & 31) != 0) return fail(GS_ERR_INVALID, "dev_obs must be 32-byte aligned (an observation is read in one load)");
+    return GS_OK;
+}
 static void assign_staging_release(gs_graph *g);      // the one-to-one frame call's staging (below)
 void gs_frontend_release(gs_graph *g) {      // gs_destroy
     assign_staging_release(g);
@@ -176,23 +230,9 @@ extern "C" int gs_associate_resident(gs_graph *g, int32_t n, const double *dev_p
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("association: ") + hipGetErrorString(e));
     return GS_OK;
 }
-// bench / profiling hook (graphslam_debug.h): `reps` launches of the resident association, each with a start / stop event pair attached to
-// its dispatch (the kernel's own begin -> end, as for the linearisation kernel); mean milliseconds per launch; the grid is built before
 extern "C" int gs_debug_time_associate_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
                                                 const double *dev_obs, double thr, double type_tol, int32_t *dev_out, int32_t reps, double *out_ms) {
-    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
-    int rc = gs_associate_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, thr, type_tol, dev_out); if (rc != GS_OK) return rc;     // warm (and the grid)
-    std::vector<hipEvent_t> ev(2 * (size_t)reps); for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-    for (int r = 0; r < reps && rc == GS_OK; ++r) { g->ev_lin[0] = ev[2 * (size_t)r]; g->ev_lin[1] = ev[2 * (size_t)r + 1];
-        rc = gs_associate_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, thr, type_tol, dev_out); }
-    g->ev_lin[0] = g->ev_lin[1] = nullptr;
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    double tot = 0; int cnt = 0;
-    for (int r = 0; r < reps; ++r) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]) == hipSuccess && ms > 0) { tot += ms; ++cnt; } }
-    (void)hipGetLastError();
-    for (auto &e : ev) hipEventDestroy(e);
-    *out_ms = cnt ? tot / cnt : 0.0;
-    return rc;
+    return time_resident(g, reps, out_ms, [&] { return gs_associate_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, thr, type_tol, dev_out); });
 }
 
 // ---- the per-keyframe path: resident map + one fused launch -------------------------------------------------------
@@ -378,36 +418,24 @@ extern "C" int gs_associate_nn_batch(gs_graph *g, int32_t n, const double *poses
     bool grid = n_map >= 2048;                                      // as gs_associate_batch: the grid beyond a few LDS tiles, gs_debug_options.assoc_grid forces either
     if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && n_map > 0;
     long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
-    if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(9 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded(2 * (size_t)n_map, 8) +
-                               padded(4 * (size_t)n_map, 8) + padded(n_map, 4) + padded(n, 4) + 2 * padded(n, 8) + gbytes)) != GS_OK) return rc;
-    Carver c{g}; double *p = c.get<double>(3 * (size_t)npose), *pcv = c.get<double>(9 * (size_t)npose); int32_t *po = c.get<int32_t>(n);
-    double *ob = c.get<double>(4 * (size_t)n), *mx = c.get<double>(2 * (size_t)n_map), *mc = c.get<double>(4 * (size_t)n_map);
-    int32_t *mt = c.get<int32_t>(n_map), *o = c.get<int32_t>(n); double *od = c.get<double>(n), *os = c.get<double>(n);
-    HIP_TRY(hipMemcpyAsync(p, poses, 3 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
-    if (pose_cov && npose > 0) HIP_TRY(hipMemcpyAsync(pcv, pose_cov, 9 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(po, pose_of_obs, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
-    if (n_map > 0) { HIP_TRY(hipMemcpyAsync(mx, map_xy, 2 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream));
-                     HIP_TRY(hipMemcpyAsync(mt, map_type, (size_t)n_map * 4, hipMemcpyHostToDevice, g->stream));
-                     if (map_cov) HIP_TRY(hipMemcpyAsync(mc, map_cov, 4 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream)); }
+    Staging sg{g}; double *p, *pcv, *ob, *mx, *mc, *od, *os; int32_t *po, *mt, *o; char *gm;
+    sg.add(p, 3 * (size_t)npose, poses); sg.add(pcv, 9 * (size_t)npose, pose_cov); sg.add(po, n, pose_of_obs); sg.add(ob, 4 * (size_t)n, obs);
+    sg.add(mx, 2 * (size_t)n_map, map_xy); sg.add(mt, n_map, map_type); sg.add(mc, 4 * (size_t)n_map, map_cov);
+    sg.add(o, n); sg.add(od, n); sg.add(os, n); sg.add(gm, gbytes);
+    if ((rc = sg.commit()) != GS_OK) return rc;
     const double *dmc = map_cov ? mc : nullptr, *dpc = pose_cov ? pcv : nullptr;
-    if (grid) { const GridBufs gb = grid_carve(c.get<char>(gbytes), n_map, buckets);
+    if (grid) { const GridBufs gb = grid_carve(gm, n_map, buckets);
         launch_grid_build(n_map, mx, nd.max_distance, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream);
         launch_assoc_nn_grid(n, p, npose, po, ob, g->cfg.lidar_to_cog, mx, mt, dmc, dpc, nd, buckets, gb.start, gb.items, o, od, os, g->stream);
     } else launch_assoc_nn(n, p, npose, po, ob, g->cfg.lidar_to_cog, n_map, mx, mt, dmc, dpc, nd, o, od, os, g->stream);
-    HIP_TRY(hipMemcpyAsync(out, o, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (out_d2) HIP_TRY(hipMemcpyAsync(out_d2, od, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    if (out_second) HIP_TRY(hipMemcpyAsync(out_second, os, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));        // the one wait of the call: the result copies
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("association (nn): ") + hipGetErrorString(e));
-    return GS_OK;
+    sg.fetch(out, o, (size_t)n * sizeof(int32_t)); sg.fetch(out_d2, od, (size_t)n * sizeof(double)); sg.fetch(out_second, os, (size_t)n * sizeof(double));
+    return sg.finish("association (nn)");
 }
 extern "C" int gs_associate_nn_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
                                         const double *dev_pose_cov, const gs_nn_params *params, int32_t *dev_out, double *dev_out_d2, double *dev_out_second) {
     if (!g || n < 0 || npose < 0 || (n > 0 && (!dev_poses || !dev_pose_of_obs || !dev_obs || !dev_out))) return fail(GS_ERR_INVALID, "bad argument");
     NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
-    if (((uintptr_t)dev_obs & 31) != 0) return fail(GS_ERR_INVALID, "dev_obs must be 32-byte aligned (an observation is read in one load)");
+    if ((rc = dev_obs_aligned(dev_obs)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n == 0) return GS_OK;
     auto &fe = g->fe;
@@ -422,24 +450,11 @@ extern "C" int gs_associate_nn_resident(gs_graph *g, int32_t n, const double *de
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("association (nn): ") + hipGetErrorString(e));
     return GS_OK;
 }
-// the twin of gs_debug_time_associate_resident: start / stop events on the query kernel's dispatch, the grid built before
 extern "C" int gs_debug_time_associate_nn_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
                                                    const double *dev_obs, const double *dev_pose_cov, const gs_nn_params *params, int32_t *dev_out,
                                                    double *dev_out_d2, double *dev_out_second, int32_t reps, double *out_ms) {
-    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
-    int rc = gs_associate_nn_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, dev_pose_cov, params, dev_out, dev_out_d2, dev_out_second);     // warm (and the grid)
-    if (rc != GS_OK) return rc;
-    std::vector<hipEvent_t> ev(2 * (size_t)reps); for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-    for (int r = 0; r < reps && rc == GS_OK; ++r) { g->ev_lin[0] = ev[2 * (size_t)r]; g->ev_lin[1] = ev[2 * (size_t)r + 1];
-        rc = gs_associate_nn_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, dev_pose_cov, params, dev_out, dev_out_d2, dev_out_second); }
-    g->ev_lin[0] = g->ev_lin[1] = nullptr;
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    double tot = 0; int cnt = 0;
-    for (int r = 0; r < reps; ++r) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]) == hipSuccess && ms > 0) { tot += ms; ++cnt; } }
-    (void)hipGetLastError();
-    for (auto &e : ev) hipEventDestroy(e);
-    *out_ms = cnt ? tot / cnt : 0.0;
-    return rc;
+    return time_resident(g, reps, out_ms, [&] {
+        return gs_associate_nn_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, dev_pose_cov, params, dev_out, dev_out_d2, dev_out_second); });
 }
 extern "C" int gs_frame_frontend_nn(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
                                     double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2, double *out_second) {
@@ -486,6 +501,20 @@ static int frame_start_check(int32_t n, int32_t n_frames, const int32_t *fs) {
         if (fs[f + 1] - fs[f] > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations"); }
     return GS_OK;
 }
+// what a batch call over frames checks of its host arrays: frame_start, pose_of_obs in range, in_index (null: the call takes none) in
+// [-1, n_map), and with one_pose_per_frame that a frame's observations share one pose
+static int frame_inputs_check(int32_t n, int32_t npose, const int32_t *pose_of_obs, int32_t n_frames, const int32_t *frame_start, const int32_t *in_index,
+                              int32_t n_map, bool one_pose_per_frame) {
+    const int rc = frame_start_check(n, n_frames, frame_start); if (rc != GS_OK) return rc;
+    for (int i = 0; i < n; ++i) {
+        if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
+        if (in_index && (in_index[i] < -1 || in_index[i] >= n_map)) return fail(GS_ERR_INVALID, "in_index outside [-1, n_map)"); }
+    if (one_pose_per_frame)
+        for (int f = 0; f < n_frames; ++f)
+            for (int i = frame_start[f] + 1; i < frame_start[f + 1]; ++i)
+                if (pose_of_obs[i] != pose_of_obs[frame_start[f]]) return fail(GS_ERR_INVALID, "the observations of a frame must share one pose");
+    return GS_OK;
+}
 // the greedy matching (opt false: k_assign_nn) or the minimum-cost one (opt true: k_assign_opt, which also counts the admissible cones)
 static int assign_batch(gs_graph *g, bool opt, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs, const double *obs,
                         int32_t n_frames, const int32_t *frame_start, int32_t n_map, const double *map_xy, const int32_t *map_type,
@@ -493,6 +522,7 @@ static int assign_batch(gs_graph *g, bool opt, int32_t n, const double *poses, i
     if (!g || n < 0 || npose < 0 || n_map < 0 || (n > 0 && (!poses || !pose_of_obs || !obs || !out)) || (n_map > 0 && (!map_xy || !map_type)))
         return fail(GS_ERR_INVALID, "bad argument");
     NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
+    if ((rc = frame_inputs_check(n, npose, pose_of_obs, n_frames, frame_start, nullptr, n_map, false)) != GS_OK) return rc;
     if ((rc = frame_start_check(n, n_frames, frame_start)) != GS_OK) return rc;
     for (int i = 0; i < n; ++i) if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
     rc = ensure_device(g); if (rc != GS_OK) return rc;
@@ -500,35 +530,23 @@ static int assign_batch(gs_graph *g, bool opt, int32_t n, const double *poses, i
     bool grid = n_map >= 2048;                                      // as gs_associate_nn_batch
     if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && n_map > 0;
     long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
-    if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(9 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded((size_t)n_frames + 1, 4) +
-                               padded(2 * (size_t)n_map, 8) + padded(4 * (size_t)n_map, 8) + padded(n_map, 4) + padded(n, 4) + padded(n, 8) + (opt ? padded(n, 4) : 0) + gbytes)) != GS_OK) return rc;
-    Carver c{g}; double *p = c.get<double>(3 * (size_t)npose), *pcv = c.get<double>(9 * (size_t)npose); int32_t *po = c.get<int32_t>(n);
-    double *ob = c.get<double>(4 * (size_t)n); int32_t *fs = c.get<int32_t>((size_t)n_frames + 1);
-    double *mx = c.get<double>(2 * (size_t)n_map), *mc = c.get<double>(4 * (size_t)n_map);
-    int32_t *mt = c.get<int32_t>(n_map), *o = c.get<int32_t>(n); double *od = c.get<double>(n); int32_t *ona = opt ? c.get<int32_t>(n) : nullptr;
-    HIP_TRY(hipMemcpyAsync(p, poses, 3 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
-    if (pose_cov && npose > 0) HIP_TRY(hipMemcpyAsync(pcv, pose_cov, 9 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(po, pose_of_obs, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(fs, frame_start, ((size_t)n_frames + 1) * 4, hipMemcpyHostToDevice, g->stream));
-    if (n_map > 0) { HIP_TRY(hipMemcpyAsync(mx, map_xy, 2 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream));
-                     HIP_TRY(hipMemcpyAsync(mt, map_type, (size_t)n_map * 4, hipMemcpyHostToDevice, g->stream));
-                     if (map_cov) HIP_TRY(hipMemcpyAsync(mc, map_cov, 4 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream)); }
+    Staging sg{g}; double *p, *pcv, *ob, *mx, *mc, *od; int32_t *po, *fs, *mt, *o, *ona = nullptr; char *gm;
+    sg.add(p, 3 * (size_t)npose, poses); sg.add(pcv, 9 * (size_t)npose, pose_cov); sg.add(po, n, pose_of_obs); sg.add(ob, 4 * (size_t)n, obs);
+    sg.add(fs, (size_t)n_frames + 1, frame_start);
+    sg.add(mx, 2 * (size_t)n_map, map_xy); sg.add(mt, n_map, map_type); sg.add(mc, 4 * (size_t)n_map, map_cov);
+    sg.add(o, n); sg.add(od, n); if (opt) sg.add(ona, n);
+    sg.add(gm, gbytes);
+    if ((rc = sg.commit()) != GS_OK) return rc;
     const double *dmc = map_cov ? mc : nullptr, *dpc = pose_cov ? pcv : nullptr;
     GridBufs gb{};
-    if (grid) { gb = grid_carve(c.get<char>(gbytes), n_map, buckets);
+    if (grid) { gb = grid_carve(gm, n_map, buckets);
         launch_grid_build(n_map, mx, nd.max_distance, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream); }
     if (opt) launch_assign_opt(n, p, npose, po, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, mt, dmc, dpc, nd, buckets, grid ? gb.start : nullptr,
                                grid ? gb.items : nullptr, o, od, ona, nullptr, nullptr, g->stream);
     else launch_assign_nn(n, p, npose, po, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, mt, dmc, dpc, nd, buckets, grid ? gb.start : nullptr, grid ? gb.items : nullptr,
                           o, od, nullptr, nullptr, g->stream);
-    HIP_TRY(hipMemcpyAsync(out, o, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (out_d2) HIP_TRY(hipMemcpyAsync(out_d2, od, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    if (out_na) HIP_TRY(hipMemcpyAsync(out_na, ona, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));        // the one wait of the call: the result copies
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("assignment (nn): ") + hipGetErrorString(e));
-    return GS_OK;
+    sg.fetch(out, o, (size_t)n * sizeof(int32_t)); sg.fetch(out_d2, od, (size_t)n * sizeof(double)); sg.fetch(out_na, ona, (size_t)n * sizeof(int32_t));
+    return sg.finish("assignment (nn)");
 }
 extern "C" int gs_assign_nn_batch(gs_graph *g, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs, const double *obs,
                                   int32_t n_frames, const int32_t *frame_start, int32_t n_map, const double *map_xy, const int32_t *map_type,
@@ -560,7 +578,7 @@ static int assign_resident(gs_graph *g, bool opt, int32_t n, const double *dev_p
     if (!g || n < 0 || npose < 0 || n_frames < 0 || !dev_frame_start || (n > 0 && (!dev_poses || !dev_pose_of_obs || !dev_obs || !dev_out)))
         return fail(GS_ERR_INVALID, "bad argument");
     NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
-    if (((uintptr_t)dev_obs & 31) != 0) return fail(GS_ERR_INVALID, "dev_obs must be 32-byte aligned (an observation is read in one load)");
+    if ((rc = dev_obs_aligned(dev_obs)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n == 0 || n_frames == 0) return GS_OK;
     const bool grid = g->fe.map_n > 0 && g->opt.assoc_grid != 0;     // as gs_associate_nn_resident
@@ -580,34 +598,17 @@ extern "C" int gs_assign_opt_resident(gs_graph *g, int32_t n, const double *dev_
                                       int32_t *dev_out, double *dev_out_d2, int32_t *dev_out_na) {
     return assign_resident(g, true, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2, dev_out_na);
 }
-// the twins of gs_debug_time_associate_nn_resident: start / stop events on the assignment's dispatches, the grid built before
-static int time_assign_resident(gs_graph *g, bool opt, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
-                                const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov,
-                                const gs_nn_params *params, int32_t *dev_out, double *dev_out_d2, int32_t *dev_out_na, int32_t reps, double *out_ms) {
-    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
-    int rc = assign_resident(g, opt, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2, dev_out_na);     // warm (and the grid)
-    if (rc != GS_OK) return rc;
-    std::vector<hipEvent_t> ev(2 * (size_t)reps); for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-    for (int r = 0; r < reps && rc == GS_OK; ++r) { g->ev_lin[0] = ev[2 * (size_t)r]; g->ev_lin[1] = ev[2 * (size_t)r + 1];
-        rc = assign_resident(g, opt, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2, dev_out_na); }
-    g->ev_lin[0] = g->ev_lin[1] = nullptr;
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    double tot = 0; int cnt = 0;
-    for (int r = 0; r < reps; ++r) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]) == hipSuccess && ms > 0) { tot += ms; ++cnt; } }
-    (void)hipGetLastError();
-    for (auto &e : ev) hipEventDestroy(e);
-    *out_ms = cnt ? tot / cnt : 0.0;
-    return rc;
-}
 extern "C" int gs_debug_time_assign_nn_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
                                                 const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov,
                                                 const gs_nn_params *params, int32_t *dev_out, double *dev_out_d2, int32_t reps, double *out_ms) {
-    return time_assign_resident(g, false, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2, nullptr, reps, out_ms);
+    return time_resident(g, reps, out_ms, [&] {
+        return assign_resident(g, false, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2, nullptr); });
 }
 extern "C" int gs_debug_time_assign_opt_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
                                                  const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov,
                                                  const gs_nn_params *params, int32_t *dev_out, double *dev_out_d2, int32_t *dev_out_na, int32_t reps, double *out_ms) {
-    return time_assign_resident(g, true, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2, dev_out_na, reps, out_ms);
+    return time_resident(g, reps, out_ms, [&] {
+        return assign_resident(g, true, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2, dev_out_na); });
 }
 static void assign_staging_release(gs_graph *g) {      // gs_frontend_release, and before the staging grows
     auto &fe = g->fe;
@@ -734,43 +735,20 @@ extern "C" int gs_joint_compat_batch(gs_graph *g, int32_t n, const double *poses
         return fail(GS_ERR_INVALID, "bad argument");
     NnDev nd; int rc = jc_sigmas_check(params, nd); if (rc != GS_OK) return rc;
     JcGate gt; if ((rc = jc_params_check(jc, gt)) != GS_OK) return rc;
-    if ((rc = frame_start_check(n, n_frames, frame_start)) != GS_OK) return rc;
-    for (int i = 0; i < n; ++i) {
-        if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
-        if (in_index[i] < -1 || in_index[i] >= n_map) return fail(GS_ERR_INVALID, "in_index outside [-1, n_map)"); }
-    for (int f = 0; f < n_frames; ++f)
-        for (int i = frame_start[f] + 1; i < frame_start[f + 1]; ++i)
-            if (pose_of_obs[i] != pose_of_obs[frame_start[f]]) return fail(GS_ERR_INVALID, "the observations of a frame must share one pose");
+    if ((rc = frame_inputs_check(n, npose, pose_of_obs, n_frames, frame_start, in_index, n_map, true)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n_frames == 0) return GS_OK;
     const size_t nf = (size_t)n_frames;
-    if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(9 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded(nf + 1, 4) +
-                               padded(2 * (size_t)n_map, 8) + padded(4 * (size_t)n_map, 8) + 2 * padded(n, 4) + padded(nf, 8) + padded(3 * nf, 8) + 3 * padded(nf, 4))) != GS_OK) return rc;
-    Carver c{g}; double *p = c.get<double>(3 * (size_t)npose), *pcv = c.get<double>(9 * (size_t)npose); int32_t *po = c.get<int32_t>(n);
-    double *ob = c.get<double>(4 * (size_t)n); int32_t *fs = c.get<int32_t>(nf + 1);
-    double *mx = c.get<double>(2 * (size_t)n_map), *mc = c.get<double>(4 * (size_t)n_map);
-    int32_t *ii = c.get<int32_t>(n), *o = c.get<int32_t>(n); double *oj = c.get<double>(nf), *odl = c.get<double>(3 * nf);
-    int32_t *ok = c.get<int32_t>(nf), *od = c.get<int32_t>(nf), *ou = c.get<int32_t>(nf);
-    if (npose > 0) HIP_TRY(hipMemcpyAsync(p, poses, 3 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
-    if (pose_cov && npose > 0) HIP_TRY(hipMemcpyAsync(pcv, pose_cov, 9 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
-    if (n > 0) { HIP_TRY(hipMemcpyAsync(po, pose_of_obs, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
-                 HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
-                 HIP_TRY(hipMemcpyAsync(ii, in_index, (size_t)n * 4, hipMemcpyHostToDevice, g->stream)); }
-    HIP_TRY(hipMemcpyAsync(fs, frame_start, (nf + 1) * 4, hipMemcpyHostToDevice, g->stream));
-    if (n_map > 0) { HIP_TRY(hipMemcpyAsync(mx, map_xy, 2 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream));
-                     if (map_cov) HIP_TRY(hipMemcpyAsync(mc, map_cov, 4 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream)); }
+    Staging sg{g}; double *p, *pcv, *ob, *mx, *mc, *oj, *odl; int32_t *po, *ii, *fs, *o, *ok, *od, *ou;
+    sg.add(p, 3 * (size_t)npose, poses); sg.add(pcv, 9 * (size_t)npose, pose_cov); sg.add(po, n, pose_of_obs); sg.add(ob, 4 * (size_t)n, obs);
+    sg.add(ii, n, in_index); sg.add(fs, nf + 1, frame_start); sg.add(mx, 2 * (size_t)n_map, map_xy); sg.add(mc, 4 * (size_t)n_map, map_cov);
+    sg.add(o, n); sg.add(oj, nf); sg.add(odl, 3 * nf); sg.add(ok, nf); sg.add(od, nf); sg.add(ou, nf);
+    if ((rc = sg.commit()) != GS_OK) return rc;
     launch_joint_compat(n, p, npose, po, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, map_cov ? mc : nullptr, pose_cov ? pcv : nullptr, nd, gt,
                         ii, o, oj, ok, od, ou, odl, g->stream);
-    if (n > 0) HIP_TRY(hipMemcpyAsync(out, o, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (out_j) HIP_TRY(hipMemcpyAsync(out_j, oj, nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    if (out_kept) HIP_TRY(hipMemcpyAsync(out_kept, ok, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (out_dropped) HIP_TRY(hipMemcpyAsync(out_dropped, od, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (out_untestable) HIP_TRY(hipMemcpyAsync(out_untestable, ou, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (out_delta) HIP_TRY(hipMemcpyAsync(out_delta, odl, 3 * nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));        // the one wait of the call: the result copies
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("joint compatibility: ") + hipGetErrorString(e));
-    return GS_OK;
+    sg.fetch(out, o, (size_t)n * sizeof(int32_t)); sg.fetch(out_j, oj, nf * sizeof(double)); sg.fetch(out_kept, ok, nf * sizeof(int32_t));
+    sg.fetch(out_dropped, od, nf * sizeof(int32_t)); sg.fetch(out_untestable, ou, nf * sizeof(int32_t)); sg.fetch(out_delta, odl, 3 * nf * sizeof(double));
+    return sg.finish("joint compatibility");
 }
 extern "C" int gs_joint_compat_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
                                         int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov, const gs_nn_params *params,
@@ -780,7 +758,7 @@ extern "C" int gs_joint_compat_resident(gs_graph *g, int32_t n, const double *de
         return fail(GS_ERR_INVALID, "bad argument");
     NnDev nd; int rc = jc_sigmas_check(params, nd); if (rc != GS_OK) return rc;
     JcGate gt; if ((rc = jc_params_check(jc, gt)) != GS_OK) return rc;
-    if (((uintptr_t)dev_obs & 31) != 0) return fail(GS_ERR_INVALID, "dev_obs must be 32-byte aligned (an observation is read in one load)");
+    if ((rc = dev_obs_aligned(dev_obs)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n_frames == 0) return GS_OK;
     auto &fe = g->fe;
@@ -790,26 +768,14 @@ extern "C" int gs_joint_compat_resident(gs_graph *g, int32_t n, const double *de
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("joint compatibility: ") + hipGetErrorString(e));
     return GS_OK;
 }
-// the twin of gs_debug_time_assign_opt_resident: start / stop events from the first dispatch of the joint test to its last
 extern "C" int gs_debug_time_joint_compat_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
                                                    const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov,
                                                    const gs_nn_params *params, const gs_jc_params *jc, const int32_t *dev_in_index, int32_t *dev_out,
                                                    double *dev_out_j, int32_t *dev_out_kept, int32_t *dev_out_dropped, int32_t *dev_out_untestable,
                                                    double *dev_out_delta, int32_t reps, double *out_ms) {
-    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
-    auto once = [&] { return gs_joint_compat_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, jc, dev_in_index,
-                                                      dev_out, dev_out_j, dev_out_kept, dev_out_dropped, dev_out_untestable, dev_out_delta); };
-    int rc = once(); if (rc != GS_OK) return rc;                    // warm
-    std::vector<hipEvent_t> ev(2 * (size_t)reps); for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-    for (int r = 0; r < reps && rc == GS_OK; ++r) { g->ev_lin[0] = ev[2 * (size_t)r]; g->ev_lin[1] = ev[2 * (size_t)r + 1]; rc = once(); }
-    g->ev_lin[0] = g->ev_lin[1] = nullptr;
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    double tot = 0; int cnt = 0;
-    for (int r = 0; r < reps; ++r) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]) == hipSuccess && ms > 0) { tot += ms; ++cnt; } }
-    (void)hipGetLastError();
-    for (auto &e : ev) hipEventDestroy(e);
-    *out_ms = cnt ? tot / cnt : 0.0;
-    return rc;
+    return time_resident(g, reps, out_ms, [&] {
+        return gs_joint_compat_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, jc, dev_in_index,
+        dev_out, dev_out_j, dev_out_kept, dev_out_dropped, dev_out_untestable, dev_out_delta); });
 }
 // one frame: the minimum-cost assignment of gs_frame_frontend_assign_opt, then the joint test of its result, back to back on the stream.
 // Record staging (bytes): J at 0, delta at 8, kept / dropped / untestable at 32, the pruned index at 48
@@ -884,44 +850,20 @@ extern "C" int gs_localize_batch(gs_graph *g, int32_t n, const double *poses, in
         return fail(GS_ERR_INVALID, "bad argument");
     NnDev nd; int rc = jc_sigmas_check(params, nd); if (rc != GS_OK) return rc;
     LoParams lp; if ((rc = loc_params_check(loc, lp)) != GS_OK) return rc;
-    if ((rc = frame_start_check(n, n_frames, frame_start)) != GS_OK) return rc;
-    for (int i = 0; i < n; ++i) {
-        if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
-        if (in_index[i] < -1 || in_index[i] >= n_map) return fail(GS_ERR_INVALID, "in_index outside [-1, n_map)"); }
-    for (int f = 0; f < n_frames; ++f)
-        for (int i = frame_start[f] + 1; i < frame_start[f + 1]; ++i)
-            if (pose_of_obs[i] != pose_of_obs[frame_start[f]]) return fail(GS_ERR_INVALID, "the observations of a frame must share one pose");
+    if ((rc = frame_inputs_check(n, npose, pose_of_obs, n_frames, frame_start, in_index, n_map, true)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n_frames == 0) return GS_OK;
     const size_t nf = (size_t)n_frames;
-    if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(9 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded(nf + 1, 4) +
-                               padded(2 * (size_t)n_map, 8) + padded(4 * (size_t)n_map, 8) + padded(n, 4) + padded(3 * nf, 8) + padded(9 * nf, 8) + padded(nf, 8) +
-                               3 * padded(nf, 4))) != GS_OK) return rc;
-    Carver c{g}; double *p = c.get<double>(3 * (size_t)npose), *pcv = c.get<double>(9 * (size_t)npose); int32_t *po = c.get<int32_t>(n);
-    double *ob = c.get<double>(4 * (size_t)n); int32_t *fs = c.get<int32_t>(nf + 1);
-    double *mx = c.get<double>(2 * (size_t)n_map), *mc = c.get<double>(4 * (size_t)n_map);
-    int32_t *ii = c.get<int32_t>(n); double *op = c.get<double>(3 * nf), *oc = c.get<double>(9 * nf), *ox = c.get<double>(nf);
-    int32_t *on = c.get<int32_t>(nf), *oi = c.get<int32_t>(nf), *os = c.get<int32_t>(nf);
-    if (npose > 0) HIP_TRY(hipMemcpyAsync(p, poses, 3 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
-    if (pose_cov && npose > 0) HIP_TRY(hipMemcpyAsync(pcv, pose_cov, 9 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
-    if (n > 0) { HIP_TRY(hipMemcpyAsync(po, pose_of_obs, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
-                 HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
-                 HIP_TRY(hipMemcpyAsync(ii, in_index, (size_t)n * 4, hipMemcpyHostToDevice, g->stream)); }
-    HIP_TRY(hipMemcpyAsync(fs, frame_start, (nf + 1) * 4, hipMemcpyHostToDevice, g->stream));
-    if (n_map > 0) { HIP_TRY(hipMemcpyAsync(mx, map_xy, 2 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream));
-                     if (map_cov) HIP_TRY(hipMemcpyAsync(mc, map_cov, 4 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream)); }
+    Staging sg{g}; double *p, *pcv, *ob, *mx, *mc, *op, *oc, *ox; int32_t *po, *ii, *fs, *on, *oi, *os;
+    sg.add(p, 3 * (size_t)npose, poses); sg.add(pcv, 9 * (size_t)npose, pose_cov); sg.add(po, n, pose_of_obs); sg.add(ob, 4 * (size_t)n, obs);
+    sg.add(ii, n, in_index); sg.add(fs, nf + 1, frame_start); sg.add(mx, 2 * (size_t)n_map, map_xy); sg.add(mc, 4 * (size_t)n_map, map_cov);
+    sg.add(op, 3 * nf); sg.add(oc, 9 * nf); sg.add(ox, nf); sg.add(on, nf); sg.add(oi, nf); sg.add(os, nf);
+    if ((rc = sg.commit()) != GS_OK) return rc;
     launch_localize(n, p, npose, po, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, map_cov ? mc : nullptr, pose_cov ? pcv : nullptr, nd, lp, ii,
                     LoOut{op, oc, ox, on, oi, os, nullptr}, g->fe.lo_kernel, g->stream);
-    if (out_pose) HIP_TRY(hipMemcpyAsync(out_pose, op, 3 * nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    if (out_cov) HIP_TRY(hipMemcpyAsync(out_cov, oc, 9 * nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    if (out_chi2) HIP_TRY(hipMemcpyAsync(out_chi2, ox, nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    if (out_pairs) HIP_TRY(hipMemcpyAsync(out_pairs, on, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (out_iters) HIP_TRY(hipMemcpyAsync(out_iters, oi, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (out_status) HIP_TRY(hipMemcpyAsync(out_status, os, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));        // the one wait of the call: the result copies
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("frame localisation: ") + hipGetErrorString(e));
-    return GS_OK;
+    sg.fetch(out_pose, op, 3 * nf * sizeof(double)); sg.fetch(out_cov, oc, 9 * nf * sizeof(double)); sg.fetch(out_chi2, ox, nf * sizeof(double));
+    sg.fetch(out_pairs, on, nf * sizeof(int32_t)); sg.fetch(out_iters, oi, nf * sizeof(int32_t)); sg.fetch(out_status, os, nf * sizeof(int32_t));
+    return sg.finish("frame localisation");
 }
 extern "C" int gs_localize_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
                                     int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov, const gs_nn_params *params,
@@ -931,7 +873,7 @@ extern "C" int gs_localize_resident(gs_graph *g, int32_t n, const double *dev_po
         return fail(GS_ERR_INVALID, "bad argument");
     NnDev nd; int rc = jc_sigmas_check(params, nd); if (rc != GS_OK) return rc;
     LoParams lp; if ((rc = loc_params_check(loc, lp)) != GS_OK) return rc;
-    if (((uintptr_t)dev_obs & 31) != 0) return fail(GS_ERR_INVALID, "dev_obs must be 32-byte aligned (an observation is read in one load)");
+    if ((rc = dev_obs_aligned(dev_obs)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n_frames == 0) return GS_OK;
     auto &fe = g->fe;
@@ -942,26 +884,14 @@ extern "C" int gs_localize_resident(gs_graph *g, int32_t n, const double *dev_po
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("frame localisation: ") + hipGetErrorString(e));
     return GS_OK;
 }
-// the twin of gs_debug_time_joint_compat_resident
 extern "C" int gs_debug_time_localize_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
                                                const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov,
                                                const gs_nn_params *params, const gs_loc_params *loc, const int32_t *dev_in_index, double *dev_out_pose,
                                                double *dev_out_cov, double *dev_out_chi2, int32_t *dev_out_pairs, int32_t *dev_out_iters, int32_t *dev_out_status,
                                                int32_t reps, double *out_ms) {
-    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
-    auto once = [&] { return gs_localize_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, loc, dev_in_index,
-                                                  dev_out_pose, dev_out_cov, dev_out_chi2, dev_out_pairs, dev_out_iters, dev_out_status); };
-    int rc = once(); if (rc != GS_OK) return rc;                    // warm
-    std::vector<hipEvent_t> ev(2 * (size_t)reps); for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-    for (int r = 0; r < reps && rc == GS_OK; ++r) { g->ev_lin[0] = ev[2 * (size_t)r]; g->ev_lin[1] = ev[2 * (size_t)r + 1]; rc = once(); }
-    g->ev_lin[0] = g->ev_lin[1] = nullptr;
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    double tot = 0; int cnt = 0;
-    for (int r = 0; r < reps; ++r) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]) == hipSuccess && ms > 0) { tot += ms; ++cnt; } }
-    (void)hipGetLastError();
-    for (auto &e : ev) hipEventDestroy(e);
-    *out_ms = cnt ? tot / cnt : 0.0;
-    return rc;
+    return time_resident(g, reps, out_ms, [&] {
+        return gs_localize_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, loc, dev_in_index,
+        dev_out_pose, dev_out_cov, dev_out_chi2, dev_out_pairs, dev_out_iters, dev_out_status); });
 }
 // the launches, the copies and the one wait of gs_frame_frontend_localize for a checked frame of 1 .. GS_NN_FRAME_MAX observations (before: see
 // frame_assign_enqueue; gs_frame_frontend_relocalize puts its search there)
@@ -1078,39 +1008,22 @@ extern "C" int gs_relocalize_batch(gs_graph *g, int32_t n, const double *obs, in
     const size_t nf = (size_t)n_frames;
     int slice = 0; const int n_slices = reloc_slices(n_frames, n_map, g->fe.rl_slice, slice);
     long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
-    if ((rc = arena_reserve(g, padded(4 * (size_t)n, 8) + padded(nf + 1, 4) + padded(2 * (size_t)n_map, 8) + padded(n_map, 4) + gbytes +
-                               padded(reloc_rec_bytes(n_frames, n_slices), 1) + 2 * padded(3 * nf, 8) + 2 * padded(nf, 8) + padded(4 * nf, 4) + 3 * padded(nf, 4) +
-                               padded(n, 4) + padded(n, 8))) != GS_OK) return rc;
-    Carver c{g}; double *ob = c.get<double>(4 * (size_t)n); int32_t *fs = c.get<int32_t>(nf + 1);
-    double *mx = c.get<double>(2 * (size_t)n_map); int32_t *mt = c.get<int32_t>(n_map);
-    RlRec *rec = (RlRec *)c.get<char>(reloc_rec_bytes(n_frames, n_slices));
-    double *op = c.get<double>(3 * nf), *osp = c.get<double>(3 * nf), *oc = c.get<double>(nf); long long *ons = c.get<long long>(nf);
-    int32_t *osd = c.get<int32_t>(4 * nf), *ocn = c.get<int32_t>(nf), *osc = c.get<int32_t>(nf), *ost = c.get<int32_t>(nf), *oi = c.get<int32_t>(n);
-    double *oe = c.get<double>(n);
-    if (n > 0) HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(fs, frame_start, (nf + 1) * 4, hipMemcpyHostToDevice, g->stream));
-    if (n_map > 0) { HIP_TRY(hipMemcpyAsync(mx, map_xy, 2 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream));
-                     HIP_TRY(hipMemcpyAsync(mt, map_type, (size_t)n_map * 4, hipMemcpyHostToDevice, g->stream)); }
+    Staging sg{g}; double *ob, *mx, *op, *osp, *oc, *oe; int32_t *fs, *mt, *osd, *ocn, *osc, *ost, *oi; long long *ons; char *rec, *gm;
+    sg.add(ob, 4 * (size_t)n, obs); sg.add(fs, nf + 1, frame_start); sg.add(mx, 2 * (size_t)n_map, map_xy); sg.add(mt, n_map, map_type);
+    sg.add(rec, reloc_rec_bytes(n_frames, n_slices)); sg.add(op, 3 * nf); sg.add(osp, 3 * nf); sg.add(oc, nf); sg.add(ons, nf);
+    sg.add(osd, 4 * nf); sg.add(ocn, nf); sg.add(osc, nf); sg.add(ost, nf); sg.add(oi, n); sg.add(oe, n); sg.add(gm, gbytes);
+    if ((rc = sg.commit()) != GS_OK) return rc;
     GridBufs gb{};
-    if (grid) { gb = grid_carve(c.get<char>(gbytes), n_map, buckets);
+    if (grid) { gb = grid_carve(gm, n_map, buckets);
         launch_grid_build(n_map, mx, rd.inlier_radius, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream); }
     const bool second = out_second_count || out_second_pose;
-    launch_relocalize(n, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, mt, rd, buckets, grid ? gb.start : nullptr, grid ? gb.items : nullptr, slice, n_slices, rec,
-                      RlOut{op, oc, ocn, osd, second ? osc : nullptr, second ? osp : nullptr, ons, ost, oi, oe}, nullptr, nullptr, g->stream);
-    if (out_pose) HIP_TRY(hipMemcpyAsync(out_pose, op, 3 * nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    if (out_count) HIP_TRY(hipMemcpyAsync(out_count, ocn, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (out_cost) HIP_TRY(hipMemcpyAsync(out_cost, oc, nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    if (out_seed) HIP_TRY(hipMemcpyAsync(out_seed, osd, 4 * nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (out_second_count) HIP_TRY(hipMemcpyAsync(out_second_count, osc, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (out_second_pose) HIP_TRY(hipMemcpyAsync(out_second_pose, osp, 3 * nf * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    if (out_n_seeds) HIP_TRY(hipMemcpyAsync(out_n_seeds, ons, nf * sizeof(int64_t), hipMemcpyDeviceToHost, g->stream));
-    if (out_status) HIP_TRY(hipMemcpyAsync(out_status, ost, nf * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (out_index && n > 0) HIP_TRY(hipMemcpyAsync(out_index, oi, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (out_e2 && n > 0) HIP_TRY(hipMemcpyAsync(out_e2, oe, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));        // the one wait of the call: the result copies
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("relocalisation: ") + hipGetErrorString(e));
-    return GS_OK;
+    launch_relocalize(n, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, mt, rd, buckets, grid ? gb.start : nullptr, grid ? gb.items : nullptr, slice, n_slices,
+                      (RlRec *)rec, RlOut{op, oc, ocn, osd, second ? osc : nullptr, second ? osp : nullptr, ons, ost, oi, oe}, nullptr, nullptr, g->stream);
+    sg.fetch(out_pose, op, 3 * nf * sizeof(double)); sg.fetch(out_count, ocn, nf * sizeof(int32_t)); sg.fetch(out_cost, oc, nf * sizeof(double));
+    sg.fetch(out_seed, osd, 4 * nf * sizeof(int32_t)); sg.fetch(out_second_count, osc, nf * sizeof(int32_t)); sg.fetch(out_second_pose, osp, 3 * nf * sizeof(double));
+    sg.fetch(out_n_seeds, ons, nf * sizeof(int64_t)); sg.fetch(out_status, ost, nf * sizeof(int32_t)); sg.fetch(out_index, oi, (size_t)n * sizeof(int32_t));
+    sg.fetch(out_e2, oe, (size_t)n * sizeof(double));
+    return sg.finish("relocalisation");
 }
 // the resident map's second grid (cell edge from inlier_radius), built on the device once per map change or radius: resident_grid's twin
 static int reloc_grid(gs_graph *g, double thr) {
@@ -1148,7 +1061,7 @@ extern "C" int gs_relocalize_resident(gs_graph *g, int32_t n, const double *dev_
                                       int32_t *dev_out_index, double *dev_out_e2) {
     if (!g || n < 0 || n_frames < 0 || !dev_frame_start || (n > 0 && !dev_obs)) return fail(GS_ERR_INVALID, "bad argument");
     RlDev rd; int rc = reloc_params_check(params, rd); if (rc != GS_OK) return rc;
-    if (((uintptr_t)dev_obs & 31) != 0) return fail(GS_ERR_INVALID, "dev_obs must be 32-byte aligned (an observation is read in one load)");
+    if ((rc = dev_obs_aligned(dev_obs)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n_frames == 0) return GS_OK;
     const bool grid = g->fe.map_n > 0 && g->opt.assoc_grid != 0;     // as gs_associate_nn_resident
@@ -1159,25 +1072,13 @@ extern "C" int gs_relocalize_resident(gs_graph *g, int32_t n, const double *dev_
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("relocalisation: ") + hipGetErrorString(e));
     return GS_OK;
 }
-// the twin of gs_debug_time_localize_resident
 extern "C" int gs_debug_time_relocalize_resident(gs_graph *g, int32_t n, const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start,
                                                  const gs_reloc_params *params, double *dev_out_pose, int32_t *dev_out_count, double *dev_out_cost,
                                                  int32_t *dev_out_seed, int32_t *dev_out_second_count, double *dev_out_second_pose, int64_t *dev_out_n_seeds,
                                                  int32_t *dev_out_status, int32_t *dev_out_index, double *dev_out_e2, int32_t reps, double *out_ms) {
-    if (!g || !out_ms || reps <= 0) return fail(GS_ERR_INVALID, "bad argument");
-    auto once = [&] { return gs_relocalize_resident(g, n, dev_obs, n_frames, dev_frame_start, params, dev_out_pose, dev_out_count, dev_out_cost, dev_out_seed,
-                                                    dev_out_second_count, dev_out_second_pose, dev_out_n_seeds, dev_out_status, dev_out_index, dev_out_e2); };
-    int rc = once(); if (rc != GS_OK) return rc;                    // warm (and the grid)
-    std::vector<hipEvent_t> ev(2 * (size_t)reps); for (auto &e : ev) HIP_TRY(hipEventCreate(&e));
-    for (int r = 0; r < reps && rc == GS_OK; ++r) { g->ev_lin[0] = ev[2 * (size_t)r]; g->ev_lin[1] = ev[2 * (size_t)r + 1]; rc = once(); }
-    g->ev_lin[0] = g->ev_lin[1] = nullptr;
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    double tot = 0; int cnt = 0;
-    for (int r = 0; r < reps; ++r) { float ms = 0; if (hipEventElapsedTime(&ms, ev[2 * (size_t)r], ev[2 * (size_t)r + 1]) == hipSuccess && ms > 0) { tot += ms; ++cnt; } }
-    (void)hipGetLastError();
-    for (auto &e : ev) hipEventDestroy(e);
-    *out_ms = cnt ? tot / cnt : 0.0;
-    return rc;
+    return time_resident(g, reps, out_ms, [&] {
+        return gs_relocalize_resident(g, n, dev_obs, n_frames, dev_frame_start, params, dev_out_pose, dev_out_count, dev_out_cost, dev_out_seed,
+        dev_out_second_count, dev_out_second_pose, dev_out_n_seeds, dev_out_status, dev_out_index, dev_out_e2); });
 }
 // one frame: the search, then the chain of gs_frame_frontend_localize from the found pose, back to back on the stream, one wait.
 // Record staging (bytes): pose 0, second pose 24, cost 48, n_seeds 56, seed 64, count 80, second count 84, status 88, then at 96 the index

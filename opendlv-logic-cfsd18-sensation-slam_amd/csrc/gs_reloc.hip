@@ -17,25 +17,17 @@
 // The key (-count, cost, u, v, p, q) is strict and total and every seed's score is formed by one lane in ascending i, so the result does not
 // depend on the slices, on the order the rings fill in or on which search scores: the hashed grid (cell edge from inlier_radius: every cone
 // inside the radius sits in the nine cells around w) and the walk over the whole map take the same minimum over (e2, j) below the radius.
-#include "gs_assoc_nn.hpp"
-#include "gs_frontend_dev.hpp"
-#include <hip/hip_ext.h>
+#include "gs_assoc_dev.hpp"
 
 #include <algorithm>
 
 namespace gs {
 
 static constexpr int RL_NONE = 0x7fffffff;
-static constexpr int RL_FRAME = 256;                                           // GS_NN_FRAME_MAX
+static constexpr int RL_FRAME = NN_FRAME_MAX;
 static constexpr int RL_SEEDS = 16;                                            // GS_RELOC_SEED_MAX
 static constexpr int RL_PAIRS = RL_SEEDS * (RL_SEEDS - 1) / 2;                 // 120
 static constexpr int RL_RING = 128;                                            // > 63 + 64: a ring is drained as soon as it holds 64
-
-// the A0 conversion out of line, as nn_polar of gs_assoc_nn.hip: polar_to_xy compiled once for this unit, not once per inlining context
-__device__ __noinline__ double2 rl_polar(double az, double zen, double dist, double lidar) {
-    double x, y; polar_to_xy(az, zen, dist, lidar, x, y);
-    return make_double2(x, y);
-}
 
 struct RlFrame { double zx[RL_FRAME], zy[RL_FRAME], ty[RL_FRAME], r2[RL_FRAME]; int32_t valid[RL_FRAME]; };       // 9 KB
 struct RlTable { double dzx[RL_PAIRS], dzy[RL_PAIRS], L2[RL_PAIRS], L[RL_PAIRS], tyu[RL_PAIRS], tyv[RL_PAIRS], mzx[RL_PAIRS], mzy[RL_PAIRS];
@@ -44,9 +36,6 @@ struct RlMap { int n_map; const double *xy; const int32_t *type; GridParams g; c
 struct RlArgs { int n; const double *obs; int n_frames; const int32_t *frame_start; double lidar; RlMap m; RlDev p; int slice, n_slices; RlRec *rec; int excl; };
 struct RlBest { int count; double cost; int u, v, p, q; double c, s, tx, ty; };
 
-__device__ __forceinline__ void rl_wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 __device__ __forceinline__ int rl_below(unsigned long long m) {               // the set bits of m below this lane
     return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
 }
@@ -87,7 +76,7 @@ __device__ __forceinline__ void rl_load(RlFrame &F, int t, int a, int k, const d
     double zx = 0.0, zy = 0.0, ty = 0.0, r2 = 0.0; int valid = 0;
     if (t < k) {
         const double4 o4 = reinterpret_cast<const double4 *>(obs)[a + t];     // (az, zen, dist, type) in one 32-byte load
-        const double2 z = rl_polar(o4.x, o4.y, o4.z, lidar);
+        const double2 z = nn_polar(o4.x, o4.y, o4.z, lidar);
         zx = z.x; zy = z.y; ty = o4.w; r2 = zx * zx + zy * zy;
         valid = isfinite(zx) && isfinite(zy) && r2 > 0.0;
     }
@@ -105,20 +94,7 @@ __device__ __forceinline__ void rl_nearest(const RlMap &M, double type_tol, doub
         const double ex = l.x - wx, ey = l.y - wy, e2 = ex * ex + ey * ey;
         if (e2 < r2max && (e2 < be || (e2 == be && j < bj))) { be = e2; bj = j; }
     };
-    if (GRID) {
-        const long long cx = grid_coord(wx, M.g.inv_cell), cy = grid_coord(wy, M.g.inv_cell);
-        uint32_t bk[9]; int s0[9], s1[9];
-#pragma unroll
-        for (int c = 0; c < 9; ++c) { bk[c] = grid_bucket(cx + (c % 3) - 1, cy + (c / 3) - 1, M.g.mask); s0[c] = M.cell_start[bk[c]]; s1[c] = M.cell_start[bk[c] + 1]; }
-#pragma unroll
-        for (int c = 1; c < 9; ++c)                                            // two of the nine cells in ONE bucket: walked once
-            for (int m = 0; m < c; ++m) if (bk[m] == bk[c]) s1[c] = s0[c];
-#pragma unroll
-        for (int c = 0; c < 9; ++c)
-            for (int t = s0[c]; t < s1[c]; ++t) offer(M.cell_items[t]);
-    } else {
-        for (int j = 0; j < M.n_map; ++j) offer(j);
-    }
+    map_walk<GRID>(M.n_map, M.g, M.cell_start, M.cell_items, wx, wy, offer);
 }
 // the score of (c, s, t): the frame's valid observations in ascending i
 template <bool GRID>
@@ -156,8 +132,8 @@ __global__ void __launch_bounds__(256) k_reloc_seed(RlArgs A) {
     __shared__ RlRec s_red[4];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int f = blockIdx.x / A.n_slices, sl = blockIdx.x - f * A.n_slices;
-    const int a = A.frame_start[f], b = A.frame_start[f + 1];
-    if (a < 0 || b < a || b > A.n || b - a > RL_FRAME) return;                 // not a frame of this call, or refused: the pick kernel reads no record of it
+    int a, b;
+    if (frame_bounds(A.frame_start, A.n, f, a, b) != FRAME_OK) return;         // not a frame of this call, or refused: the pick kernel reads no record of it
     const RlRec *win = A.rec + (size_t)A.n_frames * A.n_slices + f;
     if (A.excl && win->count < 0) return;                                      // second pass without a winner: likewise
     const int k = b - a;
@@ -206,7 +182,7 @@ __global__ void __launch_bounds__(256) k_reloc_seed(RlArgs A) {
         int32_t (*cq)[2] = s_cand[w]; int32_t (*sq)[3] = s_sq[w];
         // a lane per seed of the ring's first m entries
         auto score_batch = [&](int m) {
-            rl_wave_sync();
+            wave_sync();
             if (lane < m) {
                 const int e = (shead + lane) & (RL_RING - 1), p = sq[e][0], q = sq[e][1], t = sq[e][2];
                 const double2 lp = reinterpret_cast<const double2 *>(A.m.xy)[p], lq = reinterpret_cast<const double2 *>(A.m.xy)[q];
@@ -225,7 +201,7 @@ __global__ void __launch_bounds__(256) k_reloc_seed(RlArgs A) {
         };
         // a lane per candidate of the ring's first m entries, against every table entry
         auto match_batch = [&](int m) {
-            rl_wave_sync();
+            wave_sync();
             const bool act = lane < m; int p = 0, q = 0; double M = 0.0, tp = 0.0, tq = 0.0;
             if (act) {
                 const int e = (chead + lane) & (RL_RING - 1); p = cq[e][0]; q = cq[e][1];
@@ -270,11 +246,10 @@ __global__ void __launch_bounds__(256) k_reloc_pick(RlArgs A, RlOut O, double *c
 #pragma clang fp contract(off)
     __shared__ RlRec s_red[4];
     const int tid = threadIdx.x, f = blockIdx.x;
-    const int a = A.frame_start[f], b = A.frame_start[f + 1];
-    if (a < 0 || b < a || b > A.n) return;                                     // not a frame of this call: nothing read, nothing written
+    int a, b; const FrameKind kind = frame_bounds(A.frame_start, A.n, f, a, b);
+    if (kind == FRAME_NONE) return;                                            // not a frame of this call: nothing read, nothing written
     RlRec *win = A.rec + (size_t)A.n_frames * A.n_slices + f;
-    const int k = b - a;
-    const bool refused = k > RL_FRAME;
+    const bool refused = kind == FRAME_LARGE;
     RlBest best{-1, 0.0, -1, -1, -1, -1, 0.0, 0.0, 0.0, 0.0}; long long n_seeds = 0;
     if (!refused && !(A.excl && win->count < 0))
         for (int s = tid; s < A.n_slices; s += 256) { const RlRec r = A.rec[(size_t)f * A.n_slices + s]; n_seeds += r.n_seeds; rl_merge(best, rl_of(r)); }
@@ -293,7 +268,7 @@ __global__ void __launch_bounds__(256) k_reloc_pick(RlArgs A, RlOut O, double *c
         int j = -1; double e2 = __builtin_inf();
         if (found) {
             const double4 o4 = reinterpret_cast<const double4 *>(A.obs)[i];
-            const double2 z = rl_polar(o4.x, o4.y, o4.z, A.lidar);
+            const double2 z = nn_polar(o4.x, o4.y, o4.z, A.lidar);
             const double r2 = z.x * z.x + z.y * z.y;
             if (isfinite(z.x) && isfinite(z.y) && r2 > 0.0) {
                 const double wx = (best.c * z.x - best.s * z.y) + best.tx, wy = (best.s * z.x + best.c * z.y) + best.ty;
