@@ -941,6 +941,7 @@ int  gs_frame_frontend_jc(gs_graph *g, const double pose_xytheta[3], const doubl
  * gs_frame_frontend_localize: gs_frame_frontend_jc (same arguments, same outputs, same bits), then the localisation under the PRUNED index,
  *      enqueued back to back on the handle's stream, one wait.  It shares the assignment call's staging and keeps a fixed record buffer of its
  *      own from the first call on.  To chain frames, the caller adds its motion noise to out_cov before it is the next frame's pose_cov.
+ *      gs_follow_* and gs_frame_frontend_follow ("frame following", below) do that chaining on the device, for up to 64 poses at once.
  * A handle that never calls any of these allocates and launches nothing for them; the calls above are unchanged by them.
  * NOT DONE: the Slam mirror and the shell stay as they are (the reference's localizer reports the raw odometry pose); no prior-free (maximum-
  *      likelihood) solve — a wide Sigma_p serves, and "relocalisation" (below) finds a pose from the frame and the map alone; no cross-covariances;
@@ -1021,7 +1022,8 @@ int  gs_frame_frontend_localize(gs_graph *g, const double pose_xytheta[3], const
  *      record and every output of gs_frame_frontend_localize, bitwise what that call returns for the returned pose and this prior.  With
  *      status 2 the search's last kernel EMPTIES the frame the chain reads, so the chain touches no observation: its per-observation outputs are
  *      then zeros / -1 / +inf / 0 and its records those of an empty frame.  k == 0: nothing is launched, status 2.  k above GS_NN_FRAME_MAX,
- *      a sigma that is negative or not finite: GS_ERR_INVALID.
+ *      a sigma that is negative or not finite: GS_ERR_INVALID.  pose and second_pose are what gs_follow_set / gs_follow_batch ("frame
+ *      following", below) take as two hypotheses: the next frames decide between them.
  * A handle that never calls any of these allocates and launches nothing for them; the calls above are unchanged by them.  The record buffers
  *      exist from the first call on and only grow.
  * NOT DONE: one-to-one inside the score (above); cross-covariances; pruning the map-pair enumeration with a coarse grid (every ordered cone
@@ -1056,6 +1058,123 @@ int  gs_frame_frontend_relocalize(gs_graph *g, const double *obs_4xk, int32_t k,
                                   double *out_d2, int32_t *out_n_admissible, double *out_joint_d2, int32_t *out_n_kept, int32_t *out_n_dropped,
                                   int32_t *out_n_untestable, double *out_delta_3, double *out_pose_3, double *out_cov_3x3, double *out_chi2,
                                   int32_t *out_n_pairs, int32_t *out_iterations, int32_t *out_status);
+
+/* ---- frame following: pose hypotheses carried from frame to frame on the device ----------------------------------------------------
+ * Every call above treats a frame as an island.  These calls carry n_hyp pose hypotheses (1 .. GS_FOLLOW_HYP_MAX) through a run of frames
+ * without a host decision between the frames: per step a motion prediction, the chain minimum-cost assignment -> joint test -> localisation
+ * once per hypothesis, and an update that accepts or rejects the fit, counts, and retires hypotheses that lost the map or converged onto a
+ * lower-numbered one.  It is the reference's localizer (src/slam.cpp:340-414) with a noise model, and the consumer of relocalisation's
+ * pose / second_pose: a wrong place on a self-similar track stops matching once the car has moved.  No contraction anywhere: every product
+ * and sum below is rounded once, in the order the parentheses give.
+ *
+ * Inputs.  n_hyp poses (x, y, theta) and 3x3 covariances (row-major, the upper triangle read; covs == NULL: zeros).  n_steps frames as runs of
+ *      observations (frame_start, n_steps + 1 bounds, collector layout 4 x n), at most GS_NN_FRAME_MAX each, an empty frame is legal.
+ *      n_steps - 1 motion records u = (ux, uy, utheta): record t - 1 is the step from frame t - 1 to frame t in the body frame of t - 1 (the
+ *      measurement of an odometry edge), and per record a 3x3 covariance Qu in that body frame (upper triangle read; motion_cov == NULL: zeros).
+ * State per hypothesis (gs_follow_state): pose, cov (full, symmetric), hits = the n_pairs of the accepted steps summed, sum_chi2 = their chi2
+ *      added from +0 in step order, frames_hit, frames_missed, misses = the current run of missed frames, state (0 tracking, 1 lost,
+ *      2 duplicate), state_step (the step that retired it, -1 while tracking), duplicate_of (-1 unless a duplicate).  At the start: the given
+ *      pose's bits, the given covariance with its upper triangle mirrored, every counter 0, tracking.
+ * Prior of step t, per tracking hypothesis with state (x, y, theta, P).  t == 0 (no motion record): the state's bits.  t > 0:
+ *      (s, c) = sincos(theta), the device call the association's query side makes;  p = (c ux) - (s uy),  q = (s ux) + (c uy);
+ *      x- = x + p,  y- = y + q,  theta- = normalize_theta(theta + utheta) — gs_iterate's normalisation (the floor form, no libm);
+ *      with a = -q, b = p:   S00 = (P00 + a P02) + a (P02 + a P22)      S01 = (P01 + a P12) + b (P02 + a P22)      S02 = P02 + a P22
+ *                            S11 = (P11 + b P12) + b (P12 + b P22)      S12 = P12 + b P22                          S22 = P22
+ *      (F P F^T, F = [1 0 a; 0 1 b; 0 0 1]);  W Qu W^T, W = blockdiag(R(theta), 1) (all zeros with motion_cov == NULL):
+ *                            N00 = c (c q00 - s q01) - s (c q01 - s q11)      N01 = s (c q00 - s q01) + c (c q01 - s q11)
+ *                            N11 = s (s q00 + c q01) + c (s q01 + c q11)      N02 = c q02 - s q12      N12 = s q02 + c q12      N22 = q22
+ *      Sigma- = S + N entry by entry, upper triangle, mirrored.
+ * Chain of step t.  All n_hyp hypotheses at once, each a frame of its own holding the step's observations: the minimum-cost assignment with
+ *      pose = prior and pose_cov = Sigma- (ALWAYS an array, zeros where nothing was given: localisation then solves, it does not take its
+ *      pose_cov == NULL path), the joint test of its result, the localisation under the pruned index.  Per hypothesis the results are bitwise
+ *      what gs_assign_opt_* -> gs_joint_compat_* -> gs_localize_* return for that prior and that frame.  An EMPTY frame launches no chain:
+ *      its record is pose = the prior's bits, cov = Sigma-, chi2 0, n_pairs 0, iterations 0, status 2, n_kept 0.
+ * Update, per tracking hypothesis.  ACCEPTED iff ALL of  status <= 1,  n_pairs >= min_pairs,  chi2 <= gs_jc_params.gate[n_pairs]  hold
+ *      (positive tests: a NaN fails).  Accepted: pose, cov = the posterior; hits += n_pairs; sum_chi2 = sum_chi2 + chi2; frames_hit += 1;
+ *      misses = 0.  Otherwise: pose, cov = the prior (dead reckoning); frames_missed += 1; misses += 1; if misses >= max_misses: state = 1,
+ *      state_step = t.
+ * Duplicates, after every update of the step, for h = 1, 2, ... in ascending order.  Hypothesis h, if it tracks, becomes a duplicate of the
+ *      SMALLEST d < h that tracks (and was not made a duplicate earlier in this pass) with BOTH
+ *      ((dx dx) + (dy dy)) < merge_xy merge_xy  (dx = x_h - x_d, dy = y_h - y_d; the right side formed once, on the host)  and
+ *      |normalize_theta(theta_h - theta_d)| < merge_theta:  state = 2, duplicate_of = d, state_step = t.  The rule is sequential: a
+ *      hypothesis retired in this step or before is compared with nobody.  merge_xy == 0 switches the pass off.
+ * Retired hypotheses are frozen: no prediction, no update.  Their step records repeat the frozen pose and covariance as prior and posterior,
+ *      with chi2 0, n_pairs 0, iterations 0, status -1, n_kept 0, accepted 0; their pruned index is -1.
+ * Best.  The tracking hypothesis of smallest key (-hits, sum_chi2, h); -1 when none tracks.  n_tracking = how many track.
+ * Outputs, each pointer may be NULL.  out_steps[t n_hyp + h] (gs_follow_step): the prior, the chain's record as it came (also when it was
+ *      rejected), accepted, and the state after the step's duplicate pass.  out_index[h n + i]: observation i's cone under hypothesis h after
+ *      the joint test, or -1.  out_state[h]: the state after the last step.  out_best, out_n_tracking.
+ * Consequences.  A hypothesis does not depend on its neighbours except through the duplicate pass: with merge_xy = 0, n_hyp hypotheses in
+ *      one call equal each of them alone.  Batch, resident and a sequence of frame calls return identical bits, with either search.
+ *
+ * gs_follow_params_default fills the struct.  Refused (GS_ERR_INVALID) before the device is touched, by every call below: a wrong struct_size
+ *      of any of the four parameter blocks and whatever the chain's calls refuse of them; min_pairs < 1; max_misses < 1; a merge value that
+ *      is negative or not finite; n_hyp outside 1 .. GS_FOLLOW_HYP_MAX.  A host-only handle: GS_ERR_NO_DEVICE.
+ * gs_follow_batch: host arrays, the map as gs_localize_batch takes it plus map_type; frame_start as gs_assign_nn_batch checks it.  Everything
+ *      is uploaded once, all steps are enqueued back to back on the handle's stream, one wait.  The search as gs_assign_opt_batch chooses it.
+ * gs_follow_resident: everything in DEVICE memory against the resident map, asynchronous on the handle's stream, no wait.  dev_obs must be
+ *      32-byte aligned.  frame_cap (0 .. GS_NN_FRAME_MAX): the caller's bound on a frame's size — the host does not see dev_frame_start; it
+ *      sizes the buffers and chooses the chain's kernels, never a result.  The kernels defend themselves: a step whose bounds are not
+ *      0 <= a <= b <= n, or whose frame is above frame_cap, is no step: nothing of it is read, no state changes and no output of it is written.
+ *      dev_out_best_2: {best, n_tracking}.
+ * gs_follow_set / gs_frame_frontend_follow / gs_follow_get: the live run.  gs_follow_set puts n_hyp hypotheses on the handle (one wait);
+ *      each gs_frame_frontend_follow is one step on them, one wait, and returns that step's records (out_steps[n_hyp], out_index[h k + i]);
+ *      gs_follow_get reads the state.  motion must be NULL on the first frame after gs_follow_set ("no prediction") and given on every later
+ *      one; motion_cov may be NULL.  k above GS_NN_FRAME_MAX, a frame call or a get before gs_follow_set: GS_ERR_INVALID.  A sequence of
+ *      these calls returns bitwise the records of gs_follow_batch over the same frames.
+ * Per step: two dispatches of its own (gs_follow.hip: the prediction with the frame laid out once per hypothesis; the update) around the
+ *      chain's three to six.  The stage and chain buffers (at most 64 x 256 observations) are allocated at the first call and only grow;
+ *      stream order makes their reuse from step to step safe.  A handle that never calls any of these allocates and launches nothing for
+ *      them; the calls above are unchanged by them.
+ * NOT DONE: one fused kernel per hypothesis for the whole chain; branching (no re-matching, no hypotheses spawned on the device); feeding
+ *      relocalisation's result in automatically (the caller passes pose and second_pose); the Slam mirror and the shell; cross-covariances;
+ *      frames above GS_NN_FRAME_MAX; sharded handles; hipGraph capture of the step sequence. */
+#define GS_FOLLOW_HYP_MAX 64
+typedef struct gs_follow_params {
+    int32_t struct_size;
+    int32_t min_pairs;       /* 3; >= 1 */
+    int32_t max_misses;      /* 3; >= 1 */
+    int32_t reserved;
+    double merge_xy;         /* 0.5 m; 0 switches the duplicate pass off */
+    double merge_theta;      /* 0.1 rad */
+} gs_follow_params;
+typedef struct gs_follow_state {
+    double pose[3];
+    double cov[9];
+    double sum_chi2;
+    int32_t hits, frames_hit, frames_missed, misses;
+    int32_t state;           /* 0 tracking, 1 lost, 2 duplicate */
+    int32_t state_step;      /* -1 while tracking */
+    int32_t duplicate_of;    /* -1 unless a duplicate */
+    int32_t reserved;
+} gs_follow_state;
+typedef struct gs_follow_step {
+    double prior_pose[3];
+    double prior_cov[9];
+    double pose[3];
+    double cov[9];
+    double chi2;
+    int32_t n_pairs, iterations, status;    /* of the localisation; status -1: the hypothesis was retired before this step */
+    int32_t n_kept;                         /* of the joint test */
+    int32_t accepted;                       /* 0 / 1 */
+    int32_t state;                          /* after the step */
+} gs_follow_step;
+int  gs_follow_params_default(gs_follow_params *p);
+int  gs_follow_batch(gs_graph *g, int32_t n_hyp, const double *poses_xytheta, const double *covs_3x3, int32_t n_steps, int32_t n, const double *obs_4xn,
+                     const int32_t *frame_start, const double *motion_3, const double *motion_cov_3x3, int32_t n_map, const double *map_xy,
+                     const int32_t *map_type, const double *map_cov_2x2, const gs_nn_params *params, const gs_jc_params *jc, const gs_loc_params *loc,
+                     const gs_follow_params *follow, gs_follow_step *out_steps, int32_t *out_index, gs_follow_state *out_state, int32_t *out_best,
+                     int32_t *out_n_tracking);
+int  gs_follow_resident(gs_graph *g, int32_t n_hyp, const double *dev_poses_xytheta, const double *dev_covs_3x3, int32_t n_steps, int32_t n,
+                        const double *dev_obs_4xn, const int32_t *dev_frame_start, int32_t frame_cap, const double *dev_motion_3,
+                        const double *dev_motion_cov_3x3, const gs_nn_params *params, const gs_jc_params *jc, const gs_loc_params *loc,
+                        const gs_follow_params *follow, gs_follow_step *dev_out_steps, int32_t *dev_out_index, gs_follow_state *dev_out_state,
+                        int32_t *dev_out_best_2);
+int  gs_follow_set(gs_graph *g, int32_t n_hyp, const double *poses_xytheta, const double *covs_3x3);
+int  gs_follow_get(gs_graph *g, gs_follow_state *out_state, int32_t *out_n_hyp, int32_t *out_best, int32_t *out_n_tracking);
+int  gs_frame_frontend_follow(gs_graph *g, const double *motion_3, const double *motion_cov_3x3, const double *obs_4xk, int32_t k,
+                              const gs_nn_params *params, const gs_jc_params *jc, const gs_loc_params *loc, const gs_follow_params *follow,
+                              gs_follow_step *out_steps, int32_t *out_index, int32_t *out_best, int32_t *out_n_tracking);
 
 /* ---- multi-GPU: pose-window shards -----------------------------
  * Each rank owns a contiguous pose window and builds the SAME global plan; it linearises and

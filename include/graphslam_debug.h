@@ -132,6 +132,13 @@ int gs_debug_time_relocalize_resident(gs_graph *g, int32_t n, const double *dev_
                                       int32_t *dev_out_seed_4, int32_t *dev_out_second_count, double *dev_out_second_pose_3,
                                       int64_t *dev_out_n_seeds, int32_t *dev_out_status, int32_t *dev_out_index, double *dev_out_e2,
                                       int32_t reps, double *out_ms);
+/* Frame following.  gs_debug_time_follow_resident: `reps` calls of gs_follow_resident (the grid built before), events from the run's first
+ * dispatch (the kernel that sets the hypotheses up) to its last (the last step's update); mean milliseconds per run. */
+int gs_debug_time_follow_resident(gs_graph *g, int32_t n_hyp, const double *dev_poses_xytheta, const double *dev_covs_3x3, int32_t n_steps, int32_t n,
+                                  const double *dev_obs_4xn, const int32_t *dev_frame_start, int32_t frame_cap, const double *dev_motion_3,
+                                  const double *dev_motion_cov_3x3, const gs_nn_params *params, const gs_jc_params *jc, const gs_loc_params *loc,
+                                  const gs_follow_params *follow, gs_follow_step *dev_out_steps, int32_t *dev_out_index, gs_follow_state *dev_out_state,
+                                  int32_t *dev_out_best_2, int32_t reps, double *out_ms);
 /* Measurement hook of the sharded iteration (bench.py's `ms_exchange`): `reps` RCCL all-reduces of the exchange buffer back to back on the
  * handle's stream, HIP events around them; mean ms per all-reduce.  Collective: every rank of the communicator calls it. */
 int gs_debug_time_exchange(gs_graph *g, int32_t reps, double *out_ms);

@@ -212,6 +212,35 @@ def _reloc_record(n_frames):
             "status": np.zeros(n_frames, dtype=np.int32)}
 
 
+FOLLOW_HYP_MAX = 64                                         # GS_FOLLOW_HYP_MAX
+
+
+class FollowParams(C.Structure):
+    """gs_follow_params (include/graphslam.h): when a fit is accepted, when a hypothesis is lost, when two have become one"""
+    _fields_ = [("struct_size", C.c_int32), ("min_pairs", C.c_int32), ("max_misses", C.c_int32), ("reserved", C.c_int32), ("merge_xy", C.c_double),
+                ("merge_theta", C.c_double)]
+
+
+def follow_params(**kw):
+    """the library's gs_follow_params defaults, with the named fields changed"""
+    p = FollowParams(); L = lib()
+    rc = L.gs_follow_params_default(C.byref(p))
+    if rc != GS_OK:
+        raise GsError(rc, (L.gs_last_error() or b"").decode())
+    for k, v in kw.items():
+        if k not in ("min_pairs", "max_misses", "merge_xy", "merge_theta"):
+            raise AttributeError("gs_follow_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+# gs_follow_state and gs_follow_step as numpy records (136 and 224 bytes, no padding)
+FOLLOW_STATE = np.dtype([("pose", "<f8", 3), ("cov", "<f8", 9), ("sum_chi2", "<f8"), ("hits", "<i4"), ("frames_hit", "<i4"), ("frames_missed", "<i4"),
+                         ("misses", "<i4"), ("state", "<i4"), ("state_step", "<i4"), ("duplicate_of", "<i4"), ("reserved", "<i4")])
+FOLLOW_STEP = np.dtype([("prior_pose", "<f8", 3), ("prior_cov", "<f8", 9), ("pose", "<f8", 3), ("cov", "<f8", 9), ("chi2", "<f8"), ("n_pairs", "<i4"),
+                        ("iterations", "<i4"), ("status", "<i4"), ("n_kept", "<i4"), ("accepted", "<i4"), ("state", "<i4")])
+
+
 class DoglegParams(C.Structure):
     """gs_dogleg_params (include/graphslam.h)"""
     _fields_ = [("struct_size", C.c_int32), ("max_trials_after_failure", C.c_int32), ("initial_delta", C.c_double)]
@@ -414,6 +443,15 @@ def lib():
         L.gs_debug_time_relocalize_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, rpp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, _dp]
         L.gs_frame_frontend_relocalize.argtypes = [vp, _dp, C.c_int32, rpp, C.c_double, C.c_double, npp, jpp, lpp, _dp, _ip, _dp, _ip, _ip, _dp, _lp, _ip, _ip, _dp,
                                                    _dp, _dp, _ip, _dp, _ip, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
+    if hasattr(L, "gs_follow_batch"):                      # (and for frame following)
+        npp = C.POINTER(NnParams); jpp = C.POINTER(JcParams); lpp = C.POINTER(LocParams); fpp = C.POINTER(FollowParams)
+        L.gs_follow_params_default.argtypes = [fpp]
+        L.gs_follow_batch.argtypes = [vp, C.c_int32, _dp, _dp, C.c_int32, C.c_int32, _dp, _ip, _dp, _dp, C.c_int32, _dp, _ip, _dp, npp, jpp, lpp, fpp, vp, _ip, vp, _ip, _ip]
+        L.gs_follow_resident.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, jpp, lpp, fpp, vp, vp, vp, vp]
+        L.gs_debug_time_follow_resident.argtypes = L.gs_follow_resident.argtypes + [C.c_int32, _dp]
+        L.gs_follow_set.argtypes = [vp, C.c_int32, _dp, _dp]
+        L.gs_follow_get.argtypes = [vp, vp, _ip, _ip, _ip]
+        L.gs_frame_frontend_follow.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, jpp, lpp, fpp, vp, _ip, _ip, _ip]
     if hasattr(L, "gs_set_robust_kernel"):                # (a tuning build of an older tree loaded through GS_LIB may predate the robust kernels)
         L.gs_set_robust_kernel.argtypes = [vp, C.c_int32, C.c_int32, C.c_double]
         L.gs_get_robust_kernel.argtypes = [vp, C.c_int32, _ip, _dp]
@@ -1291,6 +1329,77 @@ class Graph:
                                                         _i(rec["n_untestable"]), _d(rec["delta"]), _d(lr["pose"]), _d(lr["cov"]), _d(lr["chi2"]), _i(lr["n_pairs"]),
                                                         _i(lr["iterations"]), _i(lr["status"])))
         return sr, si, se, z, gx, idx, d2, na, rec, lr
+
+    # ---- frame following (include/graphslam.h): pose hypotheses carried from frame to frame on the device.
+    # Records are numpy arrays of FOLLOW_STEP [n_steps, n_hyp] and FOLLOW_STATE [n_hyp]; the pruned index is [n_hyp, n]
+    @staticmethod
+    def _follow_blocks(params, jc, loc, follow):
+        return (nn_params() if params is None else params, jc_params() if jc is None else jc, loc_params() if loc is None else loc,
+                follow_params() if follow is None else follow)
+
+    def follow(self, poses, obs, frame_start, motion, map_xy, map_type, covs=None, motion_cov=None, map_cov=None, params=None, jc=None, loc=None,
+               follow=None, index=True):
+        """gs_follow_batch: {"steps", "index" (None with index=False), "state", "best", "n_tracking"} of a run over all frames"""
+        poses = _f64(poses, (-1, 3)); obs = _f64(obs, (-1, 4)); fs = _i32(frame_start); map_xy = _f64(map_xy, (-1, 2)); mt = _i32(map_type)
+        nh = len(poses); n = len(obs); ns = len(fs) - 1
+        mo = None if motion is None else _f64(motion, (-1, 3)); mq = None if motion_cov is None else _f64(motion_cov, (-1, 9))
+        cv = None if covs is None else _f64(covs, (-1, 9)); mc = None if map_cov is None else _f64(map_cov, (-1, 4))
+        assert len(fs) >= 1 and len(mt) == len(map_xy) and (mo is None or len(mo) >= ns - 1) and (mq is None or len(mq) >= ns - 1)
+        assert (cv is None or len(cv) == nh) and (mc is None or len(mc) == len(map_xy))
+        p, j, l, f = self._follow_blocks(params, jc, loc, follow)
+        steps = np.zeros((max(ns, 0), nh), dtype=FOLLOW_STEP); idx = np.zeros((nh, n), dtype=np.int32) if index else None
+        state = np.zeros(nh, dtype=FOLLOW_STATE); best = C.c_int32(-2); nt = C.c_int32(-2)
+        o = lambda a: None if a is None else _d(a)
+        self._check(self.L.gs_follow_batch(self.h, nh, _d(poses), o(cv), ns, n, _d(obs), _i(fs), o(mo), o(mq), len(map_xy), _d(map_xy), _i(mt), o(mc),
+                                           C.byref(p), C.byref(j), C.byref(l), C.byref(f), steps.ctypes.data_as(C.c_void_p), None if idx is None else _i(idx),
+                                           state.ctypes.data_as(C.c_void_p), C.byref(best), C.byref(nt)))
+        return {"steps": steps, "index": idx, "state": state, "best": best.value, "n_tracking": nt.value}
+
+    def _follow_resident_args(self, d_poses, n_hyp, d_obs, n, n_steps, d_frame_start, frame_cap, d_motion, d_covs, d_motion_cov, d_steps, d_index, d_state,
+                              d_best, params, jc, loc, follow):
+        p, j, l, f = self._follow_blocks(params, jc, loc, follow)
+        opt = lambda a: None if a is None else a.ptr
+        return [self.h, int(n_hyp), opt(d_poses), opt(d_covs), int(n_steps), int(n), opt(d_obs), opt(d_frame_start), int(frame_cap), opt(d_motion),
+                opt(d_motion_cov), C.byref(p), C.byref(j), C.byref(l), C.byref(f), opt(d_steps), opt(d_index), opt(d_state), opt(d_best)]
+
+    def follow_resident(self, d_poses, n_hyp, d_obs, n, n_steps, d_frame_start, frame_cap, d_motion=None, d_covs=None, d_motion_cov=None, d_steps=None,
+                        d_index=None, d_state=None, d_best=None, params=None, jc=None, loc=None, follow=None):
+        """gs_follow_resident: the resident map, everything else DeviceArray; asynchronous (synchronize() before reading)"""
+        self._check(self.L.gs_follow_resident(*self._follow_resident_args(d_poses, n_hyp, d_obs, n, n_steps, d_frame_start, frame_cap, d_motion, d_covs,
+                                                                          d_motion_cov, d_steps, d_index, d_state, d_best, params, jc, loc, follow)))
+
+    def time_follow_resident(self, d_poses, n_hyp, d_obs, n, n_steps, d_frame_start, frame_cap, reps, d_motion=None, d_covs=None, d_motion_cov=None,
+                             d_steps=None, d_index=None, d_state=None, d_best=None, params=None, jc=None, loc=None, follow=None):
+        """gs_debug_time_follow_resident: mean milliseconds per run, events from the run's first dispatch to its last"""
+        ms = C.c_double()
+        a = self._follow_resident_args(d_poses, n_hyp, d_obs, n, n_steps, d_frame_start, frame_cap, d_motion, d_covs, d_motion_cov, d_steps, d_index,
+                                       d_state, d_best, params, jc, loc, follow)
+        self._check(self.L.gs_debug_time_follow_resident(*(a + [int(reps), C.byref(ms)])))
+        return ms.value
+
+    def follow_set(self, poses, covs=None):
+        """gs_follow_set: put the hypotheses on the handle; the next frame_frontend_follow takes no motion"""
+        poses = _f64(poses, (-1, 3)); cv = None if covs is None else _f64(covs, (-1, 9))
+        assert cv is None or len(cv) == len(poses)
+        self._check(self.L.gs_follow_set(self.h, len(poses), _d(poses), None if cv is None else _d(cv)))
+        self._follow_n_hyp = len(poses)
+
+    def follow_get(self):
+        """gs_follow_get: (state [n_hyp], best, n_tracking) of the live run"""
+        state = np.zeros(FOLLOW_HYP_MAX, dtype=FOLLOW_STATE); nh = C.c_int32(0); best = C.c_int32(-2); nt = C.c_int32(-2)
+        self._check(self.L.gs_follow_get(self.h, state.ctypes.data_as(C.c_void_p), C.byref(nh), C.byref(best), C.byref(nt)))
+        return state[:nh.value].copy(), best.value, nt.value
+
+    def frame_frontend_follow(self, obs, motion=None, motion_cov=None, params=None, jc=None, loc=None, follow=None):
+        """gs_frame_frontend_follow: one step of the live run: (steps [n_hyp], index [n_hyp, k], best, n_tracking)"""
+        obs = _f64(obs, (-1, 4)); k = len(obs)
+        mo = None if motion is None else _f64(motion, (3,)); mq = None if motion_cov is None else _f64(motion_cov, (9,))
+        p, j, l, f = self._follow_blocks(params, jc, loc, follow)
+        steps = np.zeros(FOLLOW_HYP_MAX, dtype=FOLLOW_STEP); idx = np.zeros(FOLLOW_HYP_MAX * max(k, 1), dtype=np.int32)
+        nh = getattr(self, "_follow_n_hyp", 0); best = C.c_int32(-2); nt = C.c_int32(-2)
+        self._check(self.L.gs_frame_frontend_follow(self.h, None if mo is None else _d(mo), None if mq is None else _d(mq), _d(obs), k, C.byref(p), C.byref(j),
+                                                    C.byref(l), C.byref(f), steps.ctypes.data_as(C.c_void_p), _i(idx), C.byref(best), C.byref(nt)))
+        return steps[:nh].copy(), idx[:nh * k].reshape(nh, k).copy(), best.value, nt.value
 
     # ---- pose-window shards (one handle per rank / GPU)
     def dist_configure(self, rank, world):

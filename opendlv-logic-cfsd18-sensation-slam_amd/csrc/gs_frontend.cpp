@@ -3,6 +3,8 @@
 #include "../../include/graphslam_debug.h"
 #include "gs_private.hpp"
 #include "gs_assoc_nn.hpp"
+#include "gs_follow.hpp"
+#include "gs_follow_host.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -115,6 +117,13 @@ void gs_frontend_release(gs_graph *g) {      // gs_destroy
     if (g->fe.rl_grid_mem) hipFree(g->fe.rl_grid_mem);
     if (g->fe.rl_pin_out) hipHostFree(g->fe.rl_pin_out);
     if (g->fe.rl_dev_out) hipFree(g->fe.rl_dev_out);
+    if (g->fe.fo_mem) hipFree(g->fe.fo_mem);
+    if (g->fe.fo_state) hipFree(g->fe.fo_state);
+    if (g->fe.fo_best) hipFree(g->fe.fo_best);
+    if (g->fe.fo_pin_in) hipHostFree(g->fe.fo_pin_in);
+    if (g->fe.fo_pin_out) hipHostFree(g->fe.fo_pin_out);
+    if (g->fe.fo_dev_in) hipFree(g->fe.fo_dev_in);
+    if (g->fe.fo_dev_out) hipFree(g->fe.fo_dev_out);
     g->fe = gs_graph::FrontEnd();
 }
 
@@ -1151,5 +1160,249 @@ extern "C" int gs_frame_frontend_relocalize(gs_graph *g, const double *obs, int3
     if (status >= 2)                                                 // the chain found an empty frame: it wrote nothing per observation
         for (int i = 0; i < k; ++i) { out_zxy[2 * i] = out_zxy[2 * i + 1] = out_gxy[2 * i] = out_gxy[2 * i + 1] = 0.0; out_idx[i] = -1; out_d2[i] = INFINITY;
             if (out_na) out_na[i] = 0; }
+    return GS_OK;
+}
+
+// ---- frame following (gs_follow.hip): pose hypotheses carried from frame to frame on the device — batch / resident / live frame calls ----
+extern "C" int gs_follow_params_default(gs_follow_params *p) {
+    if (!p) return fail(GS_ERR_INVALID, "null params");
+    std::memset(p, 0, sizeof(*p)); p->struct_size = (int32_t)sizeof(*p);
+    p->min_pairs = 3; p->max_misses = 3; p->merge_xy = 0.5; p->merge_theta = 0.1;
+    return GS_OK;
+}
+namespace {
+static_assert(sizeof(gs_follow_step) == FOLLOW_STEP_BYTES && sizeof(gs_follow_state) == FOLLOW_STATE_BYTES, "gs_follow_host.hpp restates the record sizes");
+struct FoParams { int min_pairs, max_misses; double merge2, merge_theta; };
+// what a run is made of, in device memory: the frames, the motion records, the hypotheses, the map and its search, where the records go
+struct FollowRun {
+    int n_hyp, n, cap; const double *obs; const int32_t *fs; const double *motion, *motion_cov;
+    gs_follow_state *state; int32_t *best2; gs_follow_step *rec; int32_t *index;
+    int n_map; const double *map_xy; const int32_t *map_type; const double *map_cov; long long buckets; const int32_t *cell_start, *cell_items;
+    NnDev nd; JcGate gt; LoParams lp; FoParams fp;
+};
+}
+static int follow_params_check(const gs_follow_params *p, FoParams &f) {
+    if (!p) return fail(GS_ERR_INVALID, "null params");
+    if (p->struct_size != (int32_t)sizeof(gs_follow_params)) return fail(GS_ERR_INVALID, "gs_follow_params: wrong struct_size");
+    if (p->min_pairs < 1 || p->max_misses < 1) return fail(GS_ERR_INVALID, "gs_follow_params: min_pairs and max_misses must be at least 1");
+    if (!std::isfinite(p->merge_xy) || p->merge_xy < 0.0 || !std::isfinite(p->merge_theta) || p->merge_theta < 0.0)
+        return fail(GS_ERR_INVALID, "gs_follow_params: a merge value is not finite or negative");
+    f = FoParams{p->min_pairs, p->max_misses, p->merge_xy * p->merge_xy, p->merge_theta};
+    return GS_OK;
+}
+// the four parameter blocks of a following call, decided before the device is touched
+static int follow_checks(const gs_nn_params *params, const gs_jc_params *jc, const gs_loc_params *loc, const gs_follow_params *follow, FollowRun &R) {
+    int rc = nn_params_check(params, R.nd); if (rc != GS_OK) return rc;
+    if ((rc = jc_params_check(jc, R.gt)) != GS_OK) return rc;
+    if ((rc = loc_params_check(loc, R.lp)) != GS_OK) return rc;
+    return follow_params_check(follow, R.fp);
+}
+static int follow_hyp_check(int32_t n_hyp) {
+    return n_hyp < 1 || n_hyp > GS_FOLLOW_HYP_MAX ? fail(GS_ERR_INVALID, "n_hyp outside 1 .. GS_FOLLOW_HYP_MAX") : GS_OK;
+}
+// the hypotheses' state (two sets of 64: the live run's, a batch or resident run's) and the stage / chain buffers for n_hyp x cap observations
+static int follow_reserve(gs_graph *g, int n_hyp, int cap, FollowLayout &L) {
+    auto &fe = g->fe;
+    if (!follow_layout(n_hyp, cap, L)) return fail(GS_ERR_INVALID, "frame following: bad sizes");
+    if (!fe.fo_state) { HIP_TRY(hipMalloc((void **)&fe.fo_state, 2 * (size_t)GS_FOLLOW_HYP_MAX * sizeof(gs_follow_state)));
+        HIP_TRY(hipMalloc((void **)&fe.fo_best, 4 * sizeof(int32_t))); }
+    if (L.bytes > fe.fo_bytes) { HIP_TRY(hipStreamSynchronize(g->stream));       // grow-only
+        if (fe.fo_mem) hipFree(fe.fo_mem);
+        fe.fo_mem = nullptr; fe.fo_bytes = 0;
+        HIP_TRY(hipMalloc((void **)&fe.fo_mem, L.bytes)); fe.fo_bytes = L.bytes; }
+    return GS_OK;
+}
+static gs_follow_state *follow_state(gs_graph *g, bool live) { return (gs_follow_state *)g->fe.fo_state + (live ? 0 : GS_FOLLOW_HYP_MAX); }
+static int32_t *follow_best(gs_graph *g, bool live) { return g->fe.fo_best + (live ? 0 : 2); }
+// the state a run starts from, as k_follow_init writes it
+static void follow_init_host(int n_hyp, const double *poses, const double *covs, gs_follow_state *s) {
+    const int up[9] = {0, 1, 2, 1, 4, 5, 2, 5, 8};
+    std::memset(s, 0, (size_t)n_hyp * sizeof(gs_follow_state));
+    for (int h = 0; h < n_hyp; ++h) {
+        std::memcpy(s[h].pose, poses + 3 * (size_t)h, 3 * sizeof(double));
+        if (covs) for (int e = 0; e < 9; ++e) s[h].cov[e] = covs[9 * (size_t)h + up[e]];
+        s[h].state_step = -1; s[h].duplicate_of = -1; }
+}
+// one step enqueued: the stage, the chain over n_hyp frames (not for a frame the host knows to be empty), the update.
+// step: its place in the run's frame bounds and records; t: its number (state_step); k: the frame's size, or -1 where only the device knows
+// it; mrec: its motion record's place, -1 for none (no prediction)
+static void follow_step_enqueue(gs_graph *g, const FollowRun &R, const FollowLayout &L, int step, int t, int k, int mrec, hipEvent_t start, hipEvent_t stop) {
+    auto &fe = g->fe; char *m = fe.fo_mem;
+    FoArgs A{};
+    A.n_hyp = R.n_hyp; A.t = t; A.n = R.n; A.cap = R.cap; A.fs = R.fs + step; A.obs = R.obs;
+    A.motion = mrec >= 0 ? R.motion + 3 * (size_t)mrec : nullptr;
+    A.motion_cov = mrec >= 0 && R.motion_cov ? R.motion_cov + 9 * (size_t)mrec : nullptr;
+    A.state = R.state;
+    A.st_obs = (double *)(m + L.obs); A.st_pose_of_obs = (int32_t *)(m + L.pose_of_obs); A.st_frame_start = (int32_t *)(m + L.frame_start);
+    A.st_pose = (double *)(m + L.pose); A.st_cov = (double *)(m + L.cov);
+    int32_t *as_idx = (int32_t *)(m + L.as_idx), *jc_idx = (int32_t *)(m + L.jc_idx), *jc_kept = (int32_t *)(m + L.jc_kept);
+    double *as_d2 = (double *)(m + L.as_d2), *lo_pose = (double *)(m + L.lo_pose), *lo_cov = (double *)(m + L.lo_cov), *lo_chi2 = (double *)(m + L.lo_chi2);
+    int32_t *lo_pairs = (int32_t *)(m + L.lo_pairs), *lo_iters = (int32_t *)(m + L.lo_iters), *lo_status = (int32_t *)(m + L.lo_status);
+    A.jc_idx = jc_idx; A.jc_kept = jc_kept; A.lo_pose = lo_pose; A.lo_cov = lo_cov; A.lo_chi2 = lo_chi2; A.lo_pairs = lo_pairs; A.lo_iters = lo_iters; A.lo_status = lo_status;
+    A.min_pairs = R.fp.min_pairs; A.max_misses = R.fp.max_misses; A.merge2 = R.fp.merge2; A.merge_theta = R.fp.merge_theta;
+    A.rec = R.rec ? R.rec + (size_t)step * R.n_hyp : nullptr; A.out_index = R.index; A.best2 = R.best2;
+    const int kk = k >= 0 ? k : R.cap;
+    launch_follow_stage(A, kk, g->stream, start, nullptr);
+    if (kk > 0) {
+        const int nc = R.n_hyp * kk; const double lidar = g->cfg.lidar_to_cog;
+        launch_assign_opt(nc, A.st_pose, R.n_hyp, A.st_pose_of_obs, A.st_obs, R.n_hyp, A.st_frame_start, lidar, R.n_map, R.map_xy, R.map_type, R.map_cov, A.st_cov, R.nd,
+                          R.buckets, R.cell_start, R.cell_items, as_idx, as_d2, nullptr, nullptr, nullptr, g->stream);
+        launch_joint_compat(nc, A.st_pose, R.n_hyp, A.st_pose_of_obs, A.st_obs, R.n_hyp, A.st_frame_start, lidar, R.n_map, R.map_xy, R.map_cov, A.st_cov, R.nd, R.gt,
+                            as_idx, jc_idx, nullptr, jc_kept, nullptr, nullptr, nullptr, g->stream);
+        launch_localize(nc, A.st_pose, R.n_hyp, A.st_pose_of_obs, A.st_obs, R.n_hyp, A.st_frame_start, lidar, R.n_map, R.map_xy, R.map_cov, A.st_cov, R.nd, R.lp,
+                        jc_idx, LoOut{lo_pose, lo_cov, lo_chi2, lo_pairs, lo_iters, lo_status, nullptr}, fe.lo_kernel, g->stream);
+    }
+    launch_follow_update(A, R.gt, g->stream, nullptr, stop);
+}
+extern "C" int gs_follow_batch(gs_graph *g, int32_t n_hyp, const double *poses, const double *covs, int32_t n_steps, int32_t n, const double *obs,
+                               const int32_t *frame_start, const double *motion, const double *motion_cov, int32_t n_map, const double *map_xy,
+                               const int32_t *map_type, const double *map_cov, const gs_nn_params *params, const gs_jc_params *jc, const gs_loc_params *loc,
+                               const gs_follow_params *follow, gs_follow_step *out_steps, int32_t *out_index, gs_follow_state *out_state, int32_t *out_best,
+                               int32_t *out_n_tracking) {
+    if (!g || !poses || n_steps < 0 || n < 0 || n_map < 0 || (n > 0 && !obs) || (n_steps > 1 && !motion) || (n_map > 0 && (!map_xy || !map_type)))
+        return fail(GS_ERR_INVALID, "bad argument");
+    FollowRun R{}; int rc = follow_checks(params, jc, loc, follow, R); if (rc != GS_OK) return rc;
+    if ((rc = follow_hyp_check(n_hyp)) != GS_OK) return rc;
+    if ((rc = frame_start_check(n, n_steps, frame_start)) != GS_OK) return rc;
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    int cap = 0; for (int t = 0; t < n_steps; ++t) cap = std::max(cap, frame_start[t + 1] - frame_start[t]);
+    FollowLayout L; if ((rc = follow_reserve(g, n_hyp, cap, L)) != GS_OK) return rc;
+    bool grid = n_map >= 2048;                                      // as gs_assign_opt_batch
+    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && n_map > 0;
+    long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
+    std::vector<gs_follow_state> init((size_t)n_hyp); follow_init_host(n_hyp, poses, covs, init.data());
+    const int32_t best0[2] = {0, n_hyp};
+    const size_t nm = n_steps > 1 ? (size_t)n_steps - 1 : 0, nrec = (size_t)n_steps * n_hyp;
+    Staging sg{g}; double *ob, *mo, *mq, *mx, *mc; int32_t *fs, *mt, *b2, *oi; gs_follow_state *stt; gs_follow_step *rec; char *gm;
+    sg.add(stt, (size_t)n_hyp, (const gs_follow_state *)init.data()); sg.add(b2, 2, best0); sg.add(ob, 4 * (size_t)n, obs); sg.add(fs, (size_t)n_steps + 1, frame_start);
+    sg.add(mo, 3 * nm, motion); sg.add(mq, 9 * nm, motion_cov); sg.add(mx, 2 * (size_t)n_map, map_xy); sg.add(mt, n_map, map_type); sg.add(mc, 4 * (size_t)n_map, map_cov);
+    sg.add(rec, nrec); sg.add(oi, out_index ? (size_t)n_hyp * n : 0); sg.add(gm, gbytes);
+    if ((rc = sg.commit()) != GS_OK) return rc;
+    GridBufs gb{};
+    if (grid) { gb = grid_carve(gm, n_map, buckets);
+        launch_grid_build(n_map, mx, R.nd.max_distance, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream); }
+    R.n_hyp = n_hyp; R.n = n; R.cap = cap; R.obs = ob; R.fs = fs; R.motion = mo; R.motion_cov = motion_cov ? mq : nullptr;
+    R.state = stt; R.best2 = b2; R.rec = rec; R.index = out_index ? oi : nullptr;
+    R.n_map = n_map; R.map_xy = mx; R.map_type = mt; R.map_cov = map_cov ? mc : nullptr; R.buckets = buckets;
+    R.cell_start = grid ? gb.start : nullptr; R.cell_items = grid ? gb.items : nullptr;
+    for (int t = 0; t < n_steps; ++t)                               // back to back: no host decision between the frames
+        follow_step_enqueue(g, R, L, t, t, frame_start[t + 1] - frame_start[t], t - 1, nullptr, nullptr);
+    sg.fetch(out_steps, rec, nrec * sizeof(gs_follow_step)); sg.fetch(out_index, oi, (size_t)n_hyp * n * sizeof(int32_t));
+    sg.fetch(out_state, stt, (size_t)n_hyp * sizeof(gs_follow_state)); sg.fetch(out_best, b2, sizeof(int32_t)); sg.fetch(out_n_tracking, b2 + 1, sizeof(int32_t));
+    return sg.finish("frame following");                            // the one wait of the call
+}
+extern "C" int gs_follow_resident(gs_graph *g, int32_t n_hyp, const double *dev_poses, const double *dev_covs, int32_t n_steps, int32_t n, const double *dev_obs,
+                                  const int32_t *dev_frame_start, int32_t frame_cap, const double *dev_motion, const double *dev_motion_cov,
+                                  const gs_nn_params *params, const gs_jc_params *jc, const gs_loc_params *loc, const gs_follow_params *follow,
+                                  gs_follow_step *dev_out_steps, int32_t *dev_out_index, gs_follow_state *dev_out_state, int32_t *dev_out_best_2) {
+    if (!g || !dev_poses || n_steps < 0 || n < 0 || !dev_frame_start || (n > 0 && !dev_obs) || (n_steps > 1 && !dev_motion)) return fail(GS_ERR_INVALID, "bad argument");
+    FollowRun R{}; int rc = follow_checks(params, jc, loc, follow, R); if (rc != GS_OK) return rc;
+    if ((rc = follow_hyp_check(n_hyp)) != GS_OK) return rc;
+    if (frame_cap < 0 || frame_cap > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "frame_cap outside 0 .. GS_NN_FRAME_MAX");
+    if ((rc = dev_obs_aligned(dev_obs)) != GS_OK) return rc;
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    auto &fe = g->fe;
+    FollowLayout L; if ((rc = follow_reserve(g, n_hyp, frame_cap, L)) != GS_OK) return rc;
+    const bool grid = fe.map_n > 0 && g->opt.assoc_grid != 0;        // as gs_assign_opt_resident
+    GridBufs gb{};
+    if (grid) { if ((rc = resident_grid(g, R.nd.max_distance)) != GS_OK) return rc;
+        gb = grid_carve(fe.grid_mem, fe.map_n, fe.grid_max_cells); }
+    R.n_hyp = n_hyp; R.n = n; R.cap = frame_cap; R.obs = dev_obs; R.fs = dev_frame_start; R.motion = dev_motion; R.motion_cov = dev_motion_cov;
+    R.state = follow_state(g, false); R.best2 = follow_best(g, false); R.rec = dev_out_steps; R.index = dev_out_index;
+    R.n_map = fe.map_n; R.map_xy = fe.map_xy; R.map_type = fe.map_type; R.map_cov = fe.map_cov; R.buckets = gb.buckets;
+    R.cell_start = grid ? gb.start : nullptr; R.cell_items = grid ? gb.items : nullptr;
+    launch_follow_init(n_hyp, dev_poses, dev_covs, R.state, R.best2, g->stream, g->ev_lin[0], n_steps == 0 ? g->ev_lin[1] : nullptr);
+    for (int t = 0; t < n_steps; ++t) follow_step_enqueue(g, R, L, t, t, -1, t - 1, nullptr, t == n_steps - 1 ? g->ev_lin[1] : nullptr);
+    if (dev_out_state) HIP_TRY(hipMemcpyAsync(dev_out_state, R.state, (size_t)n_hyp * sizeof(gs_follow_state), hipMemcpyDeviceToDevice, g->stream));
+    if (dev_out_best_2) HIP_TRY(hipMemcpyAsync(dev_out_best_2, R.best2, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, g->stream));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("frame following: ") + hipGetErrorString(e));
+    return GS_OK;
+}
+extern "C" int gs_debug_time_follow_resident(gs_graph *g, int32_t n_hyp, const double *dev_poses, const double *dev_covs, int32_t n_steps, int32_t n,
+                                             const double *dev_obs, const int32_t *dev_frame_start, int32_t frame_cap, const double *dev_motion,
+                                             const double *dev_motion_cov, const gs_nn_params *params, const gs_jc_params *jc, const gs_loc_params *loc,
+                                             const gs_follow_params *follow, gs_follow_step *dev_out_steps, int32_t *dev_out_index, gs_follow_state *dev_out_state,
+                                             int32_t *dev_out_best_2, int32_t reps, double *out_ms) {
+    return time_resident(g, reps, out_ms, [&] {
+        return gs_follow_resident(g, n_hyp, dev_poses, dev_covs, n_steps, n, dev_obs, dev_frame_start, frame_cap, dev_motion, dev_motion_cov, params, jc, loc, follow,
+                                  dev_out_steps, dev_out_index, dev_out_state, dev_out_best_2); });
+}
+// the live run: the hypotheses stay on the handle between frames
+extern "C" int gs_follow_set(gs_graph *g, int32_t n_hyp, const double *poses, const double *covs) {
+    if (!g || !poses) return fail(GS_ERR_INVALID, "bad argument");
+    int rc = follow_hyp_check(n_hyp); if (rc != GS_OK) return rc;
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    FollowLayout L; if ((rc = follow_reserve(g, n_hyp, 0, L)) != GS_OK) return rc;
+    std::vector<gs_follow_state> init((size_t)n_hyp); follow_init_host(n_hyp, poses, covs, init.data());
+    const int32_t best0[2] = {0, n_hyp};
+    HIP_TRY(hipMemcpyAsync(follow_state(g, true), init.data(), (size_t)n_hyp * sizeof(gs_follow_state), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipMemcpyAsync(follow_best(g, true), best0, sizeof(best0), hipMemcpyHostToDevice, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));                       // pageable sources
+    g->fe.pin_map_busy = false; g->fe.fo_n_hyp = n_hyp; g->fe.fo_t = 0;
+    return GS_OK;
+}
+extern "C" int gs_follow_get(gs_graph *g, gs_follow_state *out_state, int32_t *out_n_hyp, int32_t *out_best, int32_t *out_n_tracking) {
+    if (!g) return fail(GS_ERR_INVALID, "null graph");
+    int rc = ensure_device(g); if (rc != GS_OK) return rc;
+    auto &fe = g->fe;
+    if (fe.fo_n_hyp == 0) return fail(GS_ERR_INVALID, "gs_follow_get before gs_follow_set");
+    int32_t b2[2] = {0, 0};
+    if (out_state) HIP_TRY(hipMemcpyAsync(out_state, follow_state(g, true), (size_t)fe.fo_n_hyp * sizeof(gs_follow_state), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(b2, follow_best(g, true), sizeof(b2), hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    fe.pin_map_busy = false;
+    if (out_n_hyp) *out_n_hyp = fe.fo_n_hyp;
+    if (out_best) *out_best = b2[0];
+    if (out_n_tracking) *out_n_tracking = b2[1];
+    return GS_OK;
+}
+extern "C" int gs_frame_frontend_follow(gs_graph *g, const double *motion, const double *motion_cov, const double *obs, int32_t k, const gs_nn_params *params,
+                                        const gs_jc_params *jc, const gs_loc_params *loc, const gs_follow_params *follow, gs_follow_step *out_steps,
+                                        int32_t *out_index, int32_t *out_best, int32_t *out_n_tracking) {
+    if (!g || k < 0 || (k > 0 && !obs) || (motion_cov && !motion)) return fail(GS_ERR_INVALID, "bad argument");
+    FollowRun R{}; int rc = follow_checks(params, jc, loc, follow, R); if (rc != GS_OK) return rc;
+    if (k > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations");
+    rc = ensure_device(g); if (rc != GS_OK) return rc;
+    auto &fe = g->fe;
+    if (fe.fo_n_hyp == 0) return fail(GS_ERR_INVALID, "gs_frame_frontend_follow before gs_follow_set");
+    if ((fe.fo_t == 0) != (motion == nullptr)) return fail(GS_ERR_INVALID, "motion must be NULL on the first frame after gs_follow_set and given on every later one");
+    const int n_hyp = fe.fo_n_hyp;
+    FollowLayout L; if ((rc = follow_reserve(g, n_hyp, k, L)) != GS_OK) return rc;
+    using Io = FollowFrameIo;
+    if (!fe.fo_dev_in) {                                            // once per handle: fixed sizes
+        HIP_TRY(hipHostMalloc((void **)&fe.fo_pin_in, Io::IN_BYTES, hipHostMallocDefault)); HIP_TRY(hipHostMalloc((void **)&fe.fo_pin_out, Io::OUT_BYTES, hipHostMallocDefault));
+        HIP_TRY(hipMalloc((void **)&fe.fo_dev_in, Io::IN_BYTES)); HIP_TRY(hipMalloc((void **)&fe.fo_dev_out, Io::OUT_BYTES)); }
+    std::memset(fe.fo_pin_in, 0, Io::IN_OBS);
+    if (motion) std::memcpy(fe.fo_pin_in + Io::IN_MOTION, motion, 3 * sizeof(double));
+    if (motion_cov) std::memcpy(fe.fo_pin_in + Io::IN_COV, motion_cov, 9 * sizeof(double));
+    ((int32_t *)(fe.fo_pin_in + Io::IN_FS))[1] = k;
+    if (k > 0) std::memcpy(fe.fo_pin_in + Io::IN_OBS, obs, 4 * (size_t)k * sizeof(double));
+    HIP_TRY(hipMemcpyAsync(fe.fo_dev_in, fe.fo_pin_in, Io::in_bytes(k), hipMemcpyHostToDevice, g->stream));
+    bool grid = fe.map_n >= 2048;                                    // by the map's size, as gs_frame_frontend_localize
+    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && fe.map_n > 0;
+    GridBufs gb{};
+    if (grid) { if ((rc = resident_grid(g, R.nd.max_distance)) != GS_OK) return rc;
+        gb = grid_carve(fe.grid_mem, fe.map_n, fe.grid_max_cells); }
+    R.n_hyp = n_hyp; R.n = k; R.cap = k; R.obs = (const double *)(fe.fo_dev_in + Io::IN_OBS); R.fs = (const int32_t *)(fe.fo_dev_in + Io::IN_FS);
+    R.motion = (const double *)(fe.fo_dev_in + Io::IN_MOTION); R.motion_cov = motion_cov ? (const double *)(fe.fo_dev_in + Io::IN_COV) : nullptr;
+    R.state = follow_state(g, true); R.best2 = follow_best(g, true);
+    R.rec = (gs_follow_step *)(fe.fo_dev_out + Io::OUT_REC); R.index = out_index ? (int32_t *)(fe.fo_dev_out + Io::OUT_IDX) : nullptr;
+    R.n_map = fe.map_n; R.map_xy = fe.map_xy; R.map_type = fe.map_type; R.map_cov = fe.map_cov; R.buckets = gb.buckets;
+    R.cell_start = grid ? gb.start : nullptr; R.cell_items = grid ? gb.items : nullptr;
+    follow_step_enqueue(g, R, L, 0, fe.fo_t, k, motion ? 0 : -1, nullptr, nullptr);
+    const size_t brec = (size_t)n_hyp * sizeof(gs_follow_step), bidx = (size_t)n_hyp * k * sizeof(int32_t);
+    HIP_TRY(hipMemcpyAsync(fe.fo_pin_out + Io::OUT_REC, fe.fo_dev_out + Io::OUT_REC, brec, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipMemcpyAsync(fe.fo_pin_out + Io::OUT_BEST, R.best2, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
+    if (out_index && bidx) HIP_TRY(hipMemcpyAsync(fe.fo_pin_out + Io::OUT_IDX, fe.fo_dev_out + Io::OUT_IDX, bidx, hipMemcpyDeviceToHost, g->stream));
+    HIP_TRY(hipStreamSynchronize(g->stream));                       // the one wait of the frame
+    fe.pin_map_busy = false;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("frame following: ") + hipGetErrorString(e));
+    fe.fo_t += 1;
+    if (out_steps) std::memcpy(out_steps, fe.fo_pin_out + Io::OUT_REC, brec);
+    if (out_index && bidx) std::memcpy(out_index, fe.fo_pin_out + Io::OUT_IDX, bidx);
+    if (out_best) std::memcpy(out_best, fe.fo_pin_out + Io::OUT_BEST, sizeof(int32_t));
+    if (out_n_tracking) std::memcpy(out_n_tracking, fe.fo_pin_out + Io::OUT_BEST + 4, sizeof(int32_t));
     return GS_OK;
 }

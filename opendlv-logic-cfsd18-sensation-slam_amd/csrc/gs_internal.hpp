@@ -85,6 +85,13 @@ struct gs_graph {
         char *rl_rec = nullptr; size_t rl_rec_bytes = 0;
         char *rl_grid_mem = nullptr; size_t rl_grid_bytes = 0; bool rl_grid_valid = false; int rl_grid_map_n = 0; double rl_grid_thr = 0.0; long long rl_grid_cells = 0;
         char *rl_pin_out = nullptr, *rl_dev_out = nullptr; int rl_slice = 0;
+        // frame following (null until one of its calls is made): the per-step stage and chain buffers (gs_follow_host.hpp's FollowLayout,
+        // grow-only), the hypotheses' state — 64 records that live between gs_frame_frontend_follow calls, 64 more that a batch or resident
+        // run works in — with {best, n_tracking} of either, the frame call's staging (fixed sizes), and the live run's size and step count
+        char *fo_mem = nullptr; size_t fo_bytes = 0;
+        char *fo_state = nullptr; int32_t *fo_best = nullptr;
+        char *fo_pin_in = nullptr, *fo_dev_in = nullptr, *fo_pin_out = nullptr, *fo_dev_out = nullptr;
+        int fo_n_hyp = 0, fo_t = 0;
     } fe;
     bool tree_proven = false;               // a whole-tree launch sequence of the CURRENT plan has completed without a flag timeout (gs_optimize then sends all iterations of a call at once)
     bool fell_back = false;                 // a whole-tree launch gave up on a flag: this handle uses one launch per level — until the next plan, or until a retry (below) comes back clean
