@@ -34,7 +34,7 @@ inline bool follow_layout(int n_hyp, int cap, FollowLayout &L) {
 // out: the step's n_hyp records at 0, {best, n_tracking} behind them, then the pruned index [n_hyp x k]
 struct FollowFrameIo {
     static constexpr size_t IN_MOTION = 0, IN_COV = 32, IN_FS = 128, IN_OBS = 160, IN_BYTES = IN_OBS + (size_t)FOLLOW_FRAME_MAX * 32;
-    static constexpr size_t OUT_REC = 0, OUT_BEST = (size_t)FOLLOW_HYP_MAX * FOLLOW_STEP_BYTES, OUT_IDX = OUT_BEST + 32,
+    static constexpr size_t OUT_REC = 0, OUT_BEST = (size_t)FOLLOW_HYP_MAX * FOLLOW_STEP_BYTES, OUT_N_TRACKING = OUT_BEST + 4, OUT_IDX = OUT_BEST + 32,
                             OUT_BYTES = OUT_IDX + (size_t)FOLLOW_HYP_MAX * FOLLOW_FRAME_MAX * 4;
     static size_t in_bytes(int k) { return IN_OBS + (size_t)k * 32; }
 };

@@ -5,8 +5,10 @@
 #include "gs_assoc_nn.hpp"
 #include "gs_follow.hpp"
 #include "gs_follow_host.hpp"
+#include "gs_frame_host.hpp"
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -90,14 +92,54 @@ static int dev_obs_aligned(const double *dev_obs) {
     if (((uintptr_t)dev_obs & 31) != 0) return fail(GS_ERR_INVALID, "dev_obs must be 32-byte aligned (an observation is read in one load)");
     return GS_OK;
 }
-static void assign_staging_release(gs_graph *g);      // the one-to-one frame call's staging (below)
+// which search a call takes: the hashed grid beyond a few LDS tiles of map, the tile kernel below; gs_debug_options.assoc_grid = 0 / 1 forces
+// either (A/B, tests).  usable: false where the call's threshold rules the grid out.  A batch call decides by the map it was given, a live
+// frame call the same way by the resident map; a resident call takes the grid unless told otherwise (it is built once per map change)
+static bool grid_batch(const gs_graph *g, int n_map, bool usable = true) {
+    bool grid = n_map >= 2048 && usable;
+    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && n_map > 0 && usable;
+    return grid;
+}
+static bool grid_resident(const gs_graph *g, bool usable = true) { return usable && g->fe.map_n > 0 && g->opt.assoc_grid != 0; }
+static bool grid_live(const gs_graph *g) { return grid_batch(g, g->fe.map_n); }
+
+// ---- the live frame calls' staging (gs::FrameStage, layouts: gs_frame_host.hpp) ----
+static_assert(FRAME_MAX == GS_NN_FRAME_MAX, "gs_frame_host.hpp restates the frame size");
+int gs::FrameStage::reserve(gs_graph *g, size_t want) {
+    if (want <= bytes) return GS_OK;
+    HIP_TRY(hipStreamSynchronize(g->stream));                       // a copy out of or into the smaller pair may still be in flight
+    release();
+    HIP_TRY(hipHostMalloc((void **)&pin, want, hipHostMallocDefault)); HIP_TRY(hipMalloc((void **)&dev, want));
+    bytes = want;
+    return GS_OK;
+}
+void gs::FrameStage::release() {
+    if (pin) hipHostFree(pin);
+    if (dev) hipFree(dev);
+    pin = dev = nullptr; bytes = 0;
+}
+// room for a frame of k observations in a pair that holds bytes_of(m) for m of them: grow-only, to max(64, k + k / 2) observations, `limit` at the most
+template <class BytesOf> static int stage_for(gs_graph *g, FrameStage &s, int k, int limit, BytesOf bytes_of) {
+    return bytes_of((size_t)k) <= s.bytes ? GS_OK : s.reserve(g, bytes_of((size_t)std::min(limit, std::max(64, k + k / 2))));
+}
+static int stage_send(gs_graph *g, const FrameStage &s, size_t bytes) {
+    HIP_TRY(hipMemcpyAsync(s.dev, s.pin, bytes, hipMemcpyHostToDevice, g->stream));
+    return GS_OK;
+}
+static int stage_fetch(gs_graph *g, const FrameStage &s, size_t bytes, size_t off = 0) {
+    HIP_TRY(hipMemcpyAsync(s.pin + off, s.dev + off, bytes, hipMemcpyDeviceToHost, g->stream));
+    return GS_OK;
+}
+// what every live call ends in once its copies back are enqueued: the one wait of the call, and what the launches left behind
+static int frame_finish(gs_graph *g, const char *what) {
+    HIP_TRY(hipStreamSynchronize(g->stream));
+    g->fe.pin_map_busy = false;
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? GS_OK : fail(GS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
 void gs_frontend_release(gs_graph *g) {      // gs_destroy
-    assign_staging_release(g);
+    for (FrameStage *s : {&g->fe.fr_in, &g->fe.fr_out, &g->fe.ch_rec, &g->fe.rl_out, &g->fe.fo_in, &g->fe.fo_out}) s->release();
     if (g->fe.arena) hipFree(g->fe.arena);
-    if (g->fe.pin_in) hipHostFree(g->fe.pin_in);
-    if (g->fe.pin_out) hipHostFree(g->fe.pin_out);
-    if (g->fe.dev_in) hipFree(g->fe.dev_in);
-    if (g->fe.dev_out) hipFree(g->fe.dev_out);
     if (g->fe.map_xy) hipFree(g->fe.map_xy);
     if (g->fe.map_type) hipFree(g->fe.map_type);
     if (g->fe.pin_map) hipHostFree(g->fe.pin_map);
@@ -105,25 +147,11 @@ void gs_frontend_release(gs_graph *g) {      // gs_destroy
     if (g->fe.pcs) hipFree(g->fe.pcs);
     if (g->fe.map_cov) hipFree(g->fe.map_cov);
     if (g->fe.cov_src) hipFree(g->fe.cov_src);
-    if (g->fe.nn_pin_in) hipHostFree(g->fe.nn_pin_in);
-    if (g->fe.nn_pin_out) hipHostFree(g->fe.nn_pin_out);
-    if (g->fe.nn_dev_in) hipFree(g->fe.nn_dev_in);
-    if (g->fe.nn_dev_out) hipFree(g->fe.nn_dev_out);
-    if (g->fe.jc_pin_out) hipHostFree(g->fe.jc_pin_out);
-    if (g->fe.jc_dev_out) hipFree(g->fe.jc_dev_out);
-    if (g->fe.lo_pin_out) hipHostFree(g->fe.lo_pin_out);
-    if (g->fe.lo_dev_out) hipFree(g->fe.lo_dev_out);
     if (g->fe.rl_rec) hipFree(g->fe.rl_rec);
     if (g->fe.rl_grid_mem) hipFree(g->fe.rl_grid_mem);
-    if (g->fe.rl_pin_out) hipHostFree(g->fe.rl_pin_out);
-    if (g->fe.rl_dev_out) hipFree(g->fe.rl_dev_out);
     if (g->fe.fo_mem) hipFree(g->fe.fo_mem);
     if (g->fe.fo_state) hipFree(g->fe.fo_state);
     if (g->fe.fo_best) hipFree(g->fe.fo_best);
-    if (g->fe.fo_pin_in) hipHostFree(g->fe.fo_pin_in);
-    if (g->fe.fo_pin_out) hipHostFree(g->fe.fo_pin_out);
-    if (g->fe.fo_dev_in) hipFree(g->fe.fo_dev_in);
-    if (g->fe.fo_dev_out) hipFree(g->fe.fo_dev_out);
     g->fe = gs_graph::FrontEnd();
 }
 
@@ -179,9 +207,8 @@ extern "C" int gs_associate_batch(gs_graph *g, int32_t n, const double *poses, i
     if (n == 0) return GS_OK;
     // maps beyond a few LDS tiles go through a hashed uniform grid (cell edge a hair above the threshold, so that every cone
     // within the threshold sits in the 3 x 3 cells around the query) that is BUILT ON THE DEVICE from the uploaded map; the brute-force
-    // kernel stays for small maps and non-positive thresholds.  gs_debug_options.assoc_grid = 0 / 1 forces either (A/B, tests).
-    bool grid = n_map >= 2048 && thr > 0.0;
-    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && n_map > 0 && thr > 0.0;
+    // kernel stays for small maps and non-positive thresholds (grid_batch).
+    const bool grid = grid_batch(g, n_map, thr > 0.0);
     long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
     if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded(2 * (size_t)n_map, 8) +
                                padded(n_map, 4) + padded(n, 4) + gbytes + padded(2 * (size_t)npose, 8))) != GS_OK) return rc;
@@ -224,7 +251,7 @@ extern "C" int gs_associate_resident(gs_graph *g, int32_t n, const double *dev_p
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n == 0) return GS_OK;
     auto &fe = g->fe;
-    const bool grid = thr > 0.0 && fe.map_n > 0 && g->opt.assoc_grid != 0;
+    const bool grid = grid_resident(g, thr > 0.0);
     if (grid) { if ((rc = resident_grid(g, thr)) != GS_OK) return rc;
         if ((size_t)npose * 2 * sizeof(double) > fe.pcs_bytes) { HIP_TRY(hipStreamSynchronize(g->stream));      // scratch for the poses' cos / sin, grow-only
             if (fe.pcs) hipFree(fe.pcs);
@@ -309,28 +336,19 @@ extern "C" int gs_frame_frontend(gs_graph *g, const double pose[3], const double
     if (!g || !pose || k < 0 || (k > 0 && (!obs || !out_zxy || !out_gxy || !out_idx))) return fail(GS_ERR_INVALID, "bad argument");
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (k == 0) return GS_OK;
-    if (k > g->fe.cap_obs) {                                        // grow-only: staging and device buffers for k observations
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        if (g->fe.pin_in) hipHostFree(g->fe.pin_in);
-        if (g->fe.pin_out) hipHostFree(g->fe.pin_out);
-        if (g->fe.dev_in) hipFree(g->fe.dev_in);
-        if (g->fe.dev_out) hipFree(g->fe.dev_out);
-        g->fe.pin_in = nullptr; g->fe.pin_out = nullptr; g->fe.dev_in = nullptr; g->fe.dev_out = nullptr; g->fe.cap_obs = 0;
-        const int cap = std::max(64, k + k / 2);
-        const size_t bin = (3 + 4 * (size_t)cap) * sizeof(double), bout = (size_t)cap * (4 * sizeof(double) + sizeof(int32_t));
-        HIP_TRY(hipHostMalloc((void **)&g->fe.pin_in, bin, hipHostMallocDefault)); HIP_TRY(hipHostMalloc((void **)&g->fe.pin_out, bout, hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&g->fe.dev_in, bin)); HIP_TRY(hipMalloc((void **)&g->fe.dev_out, bout));
-        g->fe.cap_obs = cap;
-    }
-    const size_t bin = (3 + 4 * (size_t)k) * sizeof(double), bz = (size_t)k * 2 * sizeof(double), bi = (size_t)k * sizeof(int32_t);
-    std::memcpy(g->fe.pin_in, pose, 3 * sizeof(double)); std::memcpy(g->fe.pin_in + 3, obs, 4 * (size_t)k * sizeof(double));
-    double *dz = (double *)g->fe.dev_out, *dg = dz + 2 * (size_t)k; int32_t *di = (int32_t *)(dg + 2 * (size_t)k);
-    HIP_TRY(hipMemcpyAsync(g->fe.dev_in, g->fe.pin_in, bin, hipMemcpyHostToDevice, g->stream));
-    launch_frame_frontend(k, g->fe.dev_in, g->cfg.lidar_to_cog, g->fe.map_n, g->fe.map_xy, g->fe.map_type, thr, type_tol, signed_type, dz, dg, di, g->stream);
-    HIP_TRY(hipMemcpyAsync(g->fe.pin_out, g->fe.dev_out, 2 * bz + bi, hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    g->fe.pin_map_busy = false;
-    std::memcpy(out_zxy, g->fe.pin_out, bz); std::memcpy(out_gxy, g->fe.pin_out + bz, bz); std::memcpy(out_idx, g->fe.pin_out + 2 * bz, bi);
+    auto &fe = g->fe; const FrameLayout L = frame_layout_plain(k);
+    if ((rc = stage_for(g, fe.fr_in, k, INT_MAX, [](size_t m) { return frame_layout_plain(m).in_bytes; })) != GS_OK) return rc;
+    if ((rc = stage_for(g, fe.fr_out, k, INT_MAX, [](size_t m) { return frame_layout_plain(m).out_bytes; })) != GS_OK) return rc;
+    std::memcpy(fe.fr_in.pin + L.pose, pose, 3 * sizeof(double)); std::memcpy(fe.fr_in.pin + L.obs, obs, 4 * (size_t)k * sizeof(double));
+    char *d = fe.fr_out.dev;
+    if ((rc = stage_send(g, fe.fr_in, L.in_bytes)) != GS_OK) return rc;
+    launch_frame_frontend(k, (const double *)fe.fr_in.dev, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, thr, type_tol, signed_type, (double *)(d + L.z),
+                          (double *)(d + L.g), (int32_t *)(d + L.idx), g->stream);
+    if ((rc = stage_fetch(g, fe.fr_out, L.out_bytes)) != GS_OK) return rc;
+    if ((rc = frame_finish(g, "association")) != GS_OK) return rc;
+    const char *po = fe.fr_out.pin;
+    std::memcpy(out_zxy, po + L.z, 2 * (size_t)k * sizeof(double)); std::memcpy(out_gxy, po + L.g, 2 * (size_t)k * sizeof(double));
+    std::memcpy(out_idx, po + L.idx, (size_t)k * sizeof(int32_t));
     return GS_OK;
 }
 
@@ -424,8 +442,7 @@ extern "C" int gs_associate_nn_batch(gs_graph *g, int32_t n, const double *poses
     for (int i = 0; i < n; ++i) if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n == 0) return GS_OK;
-    bool grid = n_map >= 2048;                                      // as gs_associate_batch: the grid beyond a few LDS tiles, gs_debug_options.assoc_grid forces either
-    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && n_map > 0;
+    const bool grid = grid_batch(g, n_map);
     long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
     Staging sg{g}; double *p, *pcv, *ob, *mx, *mc, *od, *os; int32_t *po, *mt, *o; char *gm;
     sg.add(p, 3 * (size_t)npose, poses); sg.add(pcv, 9 * (size_t)npose, pose_cov); sg.add(po, n, pose_of_obs); sg.add(ob, 4 * (size_t)n, obs);
@@ -448,7 +465,7 @@ extern "C" int gs_associate_nn_resident(gs_graph *g, int32_t n, const double *de
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n == 0) return GS_OK;
     auto &fe = g->fe;
-    const bool grid = fe.map_n > 0 && g->opt.assoc_grid != 0;
+    const bool grid = grid_resident(g);
     if (grid) { if ((rc = resident_grid(g, nd.max_distance)) != GS_OK) return rc;
         const GridBufs gb = grid_carve(fe.grid_mem, fe.map_n, fe.grid_max_cells);
         launch_assoc_nn_grid(n, dev_poses, npose, dev_pose_of_obs, dev_obs, g->cfg.lidar_to_cog, fe.map_xy, fe.map_type, fe.map_cov, dev_pose_cov, nd,
@@ -471,33 +488,21 @@ extern "C" int gs_frame_frontend_nn(gs_graph *g, const double pose[3], const dou
     NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (k == 0) return GS_OK;
-    auto &fe = g->fe;
-    if (k > fe.nn_cap_obs) {                                         // grow-only, as gs_frame_frontend's
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        if (fe.nn_pin_in) hipHostFree(fe.nn_pin_in);
-        if (fe.nn_pin_out) hipHostFree(fe.nn_pin_out);
-        if (fe.nn_dev_in) hipFree(fe.nn_dev_in);
-        if (fe.nn_dev_out) hipFree(fe.nn_dev_out);
-        fe.nn_pin_in = nullptr; fe.nn_pin_out = nullptr; fe.nn_dev_in = nullptr; fe.nn_dev_out = nullptr; fe.nn_cap_obs = 0;
-        const int cap = std::max(64, k + k / 2);
-        const size_t bin = (12 + 4 * (size_t)cap) * sizeof(double), bout = (size_t)cap * (6 * sizeof(double) + sizeof(int32_t));
-        HIP_TRY(hipHostMalloc((void **)&fe.nn_pin_in, bin, hipHostMallocDefault)); HIP_TRY(hipHostMalloc((void **)&fe.nn_pin_out, bout, hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&fe.nn_dev_in, bin)); HIP_TRY(hipMalloc((void **)&fe.nn_dev_out, bout));
-        fe.nn_cap_obs = cap;
-    }
-    const size_t bin = (12 + 4 * (size_t)k) * sizeof(double), bz = (size_t)k * 2 * sizeof(double), bd = (size_t)k * sizeof(double), bi = (size_t)k * sizeof(int32_t);
-    std::memcpy(fe.nn_pin_in, pose, 3 * sizeof(double));
-    if (pose_cov) std::memcpy(fe.nn_pin_in + 3, pose_cov, 9 * sizeof(double)); else std::memset(fe.nn_pin_in + 3, 0, 9 * sizeof(double));
-    std::memcpy(fe.nn_pin_in + 12, obs, 4 * (size_t)k * sizeof(double));
-    double *dz = (double *)fe.nn_dev_out, *dg = dz + 2 * (size_t)k, *dd = dg + 2 * (size_t)k, *ds = dd + k; int32_t *di = (int32_t *)(ds + k);
-    HIP_TRY(hipMemcpyAsync(fe.nn_dev_in, fe.nn_pin_in, bin, hipMemcpyHostToDevice, g->stream));
-    launch_frame_nn(k, fe.nn_dev_in, pose_cov ? 1 : 0, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, fe.map_cov, nd, dz, dg, di, dd, ds, g->stream);
-    HIP_TRY(hipMemcpyAsync(fe.nn_pin_out, fe.nn_dev_out, 2 * bz + 2 * bd + bi, hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    fe.pin_map_busy = false;
-    const char *po = fe.nn_pin_out;
-    std::memcpy(out_zxy, po, bz); std::memcpy(out_gxy, po + bz, bz); std::memcpy(out_d2, po + 2 * bz, bd); std::memcpy(out_second, po + 2 * bz + bd, bd);
-    std::memcpy(out_idx, po + 2 * bz + 2 * bd, bi);
+    auto &fe = g->fe; const FrameLayout L = frame_layout_nn(k);
+    if ((rc = stage_for(g, fe.fr_in, k, INT_MAX, [](size_t m) { return frame_layout_nn(m).in_bytes; })) != GS_OK) return rc;
+    if ((rc = stage_for(g, fe.fr_out, k, INT_MAX, [](size_t m) { return frame_layout_nn(m).out_bytes; })) != GS_OK) return rc;
+    char *pi = fe.fr_in.pin, *d = fe.fr_out.dev;
+    std::memcpy(pi + L.pose, pose, 3 * sizeof(double));
+    if (pose_cov) std::memcpy(pi + L.cov, pose_cov, 9 * sizeof(double)); else std::memset(pi + L.cov, 0, 9 * sizeof(double));
+    std::memcpy(pi + L.obs, obs, 4 * (size_t)k * sizeof(double));
+    if ((rc = stage_send(g, fe.fr_in, L.in_bytes)) != GS_OK) return rc;
+    launch_frame_nn(k, (const double *)fe.fr_in.dev, pose_cov ? 1 : 0, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, fe.map_cov, nd, (double *)(d + L.z),
+                    (double *)(d + L.g), (int32_t *)(d + L.idx), (double *)(d + L.d2), (double *)(d + L.second), g->stream);
+    if ((rc = stage_fetch(g, fe.fr_out, L.out_bytes)) != GS_OK) return rc;
+    if ((rc = frame_finish(g, "association (nn)")) != GS_OK) return rc;
+    const char *po = fe.fr_out.pin; const size_t bz = 2 * (size_t)k * sizeof(double), bd = (size_t)k * sizeof(double);
+    std::memcpy(out_zxy, po + L.z, bz); std::memcpy(out_gxy, po + L.g, bz); std::memcpy(out_d2, po + L.d2, bd); std::memcpy(out_second, po + L.second, bd);
+    std::memcpy(out_idx, po + L.idx, (size_t)k * sizeof(int32_t));
     return GS_OK;
 }
 
@@ -532,12 +537,9 @@ static int assign_batch(gs_graph *g, bool opt, int32_t n, const double *poses, i
         return fail(GS_ERR_INVALID, "bad argument");
     NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
     if ((rc = frame_inputs_check(n, npose, pose_of_obs, n_frames, frame_start, nullptr, n_map, false)) != GS_OK) return rc;
-    if ((rc = frame_start_check(n, n_frames, frame_start)) != GS_OK) return rc;
-    for (int i = 0; i < n; ++i) if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n == 0) return GS_OK;
-    bool grid = n_map >= 2048;                                      // as gs_associate_nn_batch
-    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && n_map > 0;
+    const bool grid = grid_batch(g, n_map);
     long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
     Staging sg{g}; double *p, *pcv, *ob, *mx, *mc, *od; int32_t *po, *fs, *mt, *o, *ona = nullptr; char *gm;
     sg.add(p, 3 * (size_t)npose, poses); sg.add(pcv, 9 * (size_t)npose, pose_cov); sg.add(po, n, pose_of_obs); sg.add(ob, 4 * (size_t)n, obs);
@@ -590,8 +592,7 @@ static int assign_resident(gs_graph *g, bool opt, int32_t n, const double *dev_p
     if ((rc = dev_obs_aligned(dev_obs)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n == 0 || n_frames == 0) return GS_OK;
-    const bool grid = g->fe.map_n > 0 && g->opt.assoc_grid != 0;     // as gs_associate_nn_resident
-    if ((rc = assign_resident_launch(g, opt, grid, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, nd, dev_out, dev_out_d2,
+    if ((rc = assign_resident_launch(g, opt, grid_resident(g), n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, nd, dev_out, dev_out_d2,
                                      dev_out_na, nullptr, nullptr)) != GS_OK) return rc;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("assignment (nn): ") + hipGetErrorString(e));
@@ -618,80 +619,6 @@ extern "C" int gs_debug_time_assign_opt_resident(gs_graph *g, int32_t n, const d
                                                  const gs_nn_params *params, int32_t *dev_out, double *dev_out_d2, int32_t *dev_out_na, int32_t reps, double *out_ms) {
     return time_resident(g, reps, out_ms, [&] {
         return assign_resident(g, true, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, dev_out, dev_out_d2, dev_out_na); });
-}
-static void assign_staging_release(gs_graph *g) {      // gs_frontend_release, and before the staging grows
-    auto &fe = g->fe;
-    if (fe.as_pin_in) hipHostFree(fe.as_pin_in);
-    if (fe.as_pin_out) hipHostFree(fe.as_pin_out);
-    if (fe.as_dev_in) hipFree(fe.as_dev_in);
-    if (fe.as_dev_out) hipFree(fe.as_dev_out);
-    fe.as_pin_in = fe.as_pin_out = fe.as_dev_in = fe.as_dev_out = nullptr; fe.as_cap_obs = 0;
-}
-// one frame through the resident launch.  Staging (bytes): pose at 0, pose_cov at 32, obs at 128 (32-byte aligned: one load per observation),
-// then frame_start[2] and pose_of_obs[k] (zeros) as int32
-// the frame in device memory once frame_assign_enqueue has run: inputs in as_dev_in, the assignment's outputs in as_dev_out
-struct FrameDev { const double *pose, *pose_cov, *obs; const int32_t *frame_start, *pose_of_obs; double *z, *g, *d2; int32_t *idx, *na; size_t out_bytes; };
-// stages the frame (growing the staging first), sends it and enqueues the assignment: no wait, nothing copied back.
-// before (null as a rule): enqueued between the upload and the assignment, given the staged frame's device pointers (relocalisation's search,
-// whose last kernel writes the pose the assignment reads)
-struct FrameHook { virtual int enqueue(gs_graph *g, double *dev_pose, const double *dev_obs, int32_t *dev_frame_start) = 0; virtual ~FrameHook() {} };
-static int frame_assign_enqueue(gs_graph *g, bool opt, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const NnDev &nd, FrameDev &fd,
-                                FrameHook *before = nullptr) {
-    int rc;
-    auto &fe = g->fe;
-    auto in_bytes = [](size_t m) { return (16 + 4 * m) * sizeof(double) + (2 + m) * sizeof(int32_t); };
-    if (k > fe.as_cap_obs) {                                         // grow-only, as gs_frame_frontend_nn's
-        HIP_TRY(hipStreamSynchronize(g->stream));
-        assign_staging_release(g);
-        const int cap = std::min<int>(GS_NN_FRAME_MAX, std::max(64, k + k / 2));
-        const size_t bout = (size_t)cap * (5 * sizeof(double) + 2 * sizeof(int32_t));        // z, g, d2, index, admissible count
-        HIP_TRY(hipHostMalloc((void **)&fe.as_pin_in, in_bytes(cap), hipHostMallocDefault)); HIP_TRY(hipHostMalloc((void **)&fe.as_pin_out, bout, hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&fe.as_dev_in, in_bytes(cap))); HIP_TRY(hipMalloc((void **)&fe.as_dev_out, bout));
-        fe.as_cap_obs = cap;
-    }
-    const size_t bz = (size_t)k * 2 * sizeof(double), bd = (size_t)k * sizeof(double), bi = (size_t)k * sizeof(int32_t), oint = (16 + 4 * (size_t)k) * sizeof(double);
-    std::memset(fe.as_pin_in, 0, in_bytes(k));
-    std::memcpy(fe.as_pin_in, pose, 3 * sizeof(double));
-    if (pose_cov) std::memcpy(fe.as_pin_in + 32, pose_cov, 9 * sizeof(double));
-    std::memcpy(fe.as_pin_in + 128, obs, 4 * (size_t)k * sizeof(double));
-    ((int32_t *)(fe.as_pin_in + oint))[1] = k;
-    const double *dp = (const double *)fe.as_dev_in; const int32_t *dfs = (const int32_t *)(fe.as_dev_in + oint);
-    double *dz = (double *)fe.as_dev_out, *dg = dz + 2 * (size_t)k, *dd = dg + 2 * (size_t)k; int32_t *di = (int32_t *)(dd + k), *dn = di + k;
-    HIP_TRY(hipMemcpyAsync(fe.as_dev_in, fe.as_pin_in, in_bytes(k), hipMemcpyHostToDevice, g->stream));
-    if (before && (rc = before->enqueue(g, (double *)fe.as_dev_in, dp + 16, (int32_t *)(fe.as_dev_in + oint))) != GS_OK) return rc;
-    bool grid = fe.map_n >= 2048;                                    // by the map's size, as the batch call; gs_debug_options.assoc_grid forces either
-    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && fe.map_n > 0;
-    if ((rc = assign_resident_launch(g, opt, grid, k, dp, 1, dfs + 2, dp + 16, 1, dfs, pose_cov ? dp + 4 : nullptr, nd, di, dd, opt ? dn : nullptr, dz, dg)) != GS_OK) return rc;
-    fd = FrameDev{dp, pose_cov ? dp + 4 : nullptr, dp + 16, dfs, dfs + 2, dz, dg, dd, di, dn, 2 * bz + bd + (opt ? 2 : 1) * bi};
-    return GS_OK;
-}
-static int frame_assign(gs_graph *g, bool opt, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
-                        double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2, int32_t *out_na) {
-    if (!g || !pose || k < 0 || (k > 0 && (!obs || !out_zxy || !out_gxy || !out_idx || !out_d2))) return fail(GS_ERR_INVALID, "bad argument");
-    NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
-    if (k > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations");
-    rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (k == 0) return GS_OK;
-    auto &fe = g->fe; FrameDev fd;
-    if ((rc = frame_assign_enqueue(g, opt, pose, pose_cov, obs, k, nd, fd)) != GS_OK) return rc;
-    const size_t bz = (size_t)k * 2 * sizeof(double), bd = (size_t)k * sizeof(double), bi = (size_t)k * sizeof(int32_t);
-    HIP_TRY(hipMemcpyAsync(fe.as_pin_out, fe.as_dev_out, fd.out_bytes, hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    fe.pin_map_busy = false;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("assignment (nn): ") + hipGetErrorString(e));
-    const char *po = fe.as_pin_out;
-    std::memcpy(out_zxy, po, bz); std::memcpy(out_gxy, po + bz, bz); std::memcpy(out_d2, po + 2 * bz, bd); std::memcpy(out_idx, po + 2 * bz + bd, bi);
-    if (out_na) std::memcpy(out_na, po + 2 * bz + bd + bi, bi);
-    return GS_OK;
-}
-extern "C" int gs_frame_frontend_assign(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
-                                        double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2) {
-    return frame_assign(g, false, pose, pose_cov, obs, k, params, out_zxy, out_gxy, out_idx, out_d2, nullptr);
-}
-extern "C" int gs_frame_frontend_assign_opt(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
-                                            double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2, int32_t *out_na) {
-    return frame_assign(g, true, pose, pose_cov, obs, k, params, out_zxy, out_gxy, out_idx, out_d2, out_na);
 }
 
 // ---- joint compatibility of a frame's hypothesis (gs_assoc_nn.hip, k_joint_compat): the gate table, the batch / resident / frame calls ----
@@ -786,49 +713,6 @@ extern "C" int gs_debug_time_joint_compat_resident(gs_graph *g, int32_t n, const
         return gs_joint_compat_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, jc, dev_in_index,
         dev_out, dev_out_j, dev_out_kept, dev_out_dropped, dev_out_untestable, dev_out_delta); });
 }
-// one frame: the minimum-cost assignment of gs_frame_frontend_assign_opt, then the joint test of its result, back to back on the stream.
-// Record staging (bytes): J at 0, delta at 8, kept / dropped / untestable at 32, the pruned index at 48
-extern "C" int gs_frame_frontend_jc(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
-                                    const gs_jc_params *jc, double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2, int32_t *out_na,
-                                    double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable, double *out_delta) {
-    if (!g || !pose || k < 0 || (k > 0 && (!obs || !out_zxy || !out_gxy || !out_idx || !out_d2))) return fail(GS_ERR_INVALID, "bad argument");
-    NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
-    JcGate gt; if ((rc = jc_params_check(jc, gt)) != GS_OK) return rc;
-    if (k > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations");
-    rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (k == 0) {                                                   // the empty frame's record, without a launch
-        if (out_j) *out_j = 0.0;
-        if (out_kept) *out_kept = 0;
-        if (out_dropped) *out_dropped = 0;
-        if (out_untestable) *out_untestable = 0;
-        if (out_delta) out_delta[0] = out_delta[1] = out_delta[2] = 0.0;
-        return GS_OK; }
-    auto &fe = g->fe; FrameDev fd;
-    const size_t jbytes = 48 + (size_t)GS_NN_FRAME_MAX * sizeof(int32_t);
-    if (!fe.jc_dev_out) {                                           // once per handle: the size does not depend on k
-        HIP_TRY(hipHostMalloc((void **)&fe.jc_pin_out, jbytes, hipHostMallocDefault)); HIP_TRY(hipMalloc((void **)&fe.jc_dev_out, jbytes)); }
-    if ((rc = frame_assign_enqueue(g, true, pose, pose_cov, obs, k, nd, fd)) != GS_OK) return rc;
-    char *jd = fe.jc_dev_out;
-    launch_joint_compat(k, fd.pose, 1, fd.pose_of_obs, fd.obs, 1, fd.frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_cov, fd.pose_cov, nd, gt, fd.idx,
-                        (int32_t *)(jd + 48), (double *)jd, (int32_t *)(jd + 32), (int32_t *)(jd + 36), (int32_t *)(jd + 40), (double *)(jd + 8), g->stream);
-    const size_t bz = (size_t)k * 2 * sizeof(double), bd = (size_t)k * sizeof(double), bi = (size_t)k * sizeof(int32_t);
-    HIP_TRY(hipMemcpyAsync(fe.as_pin_out, fe.as_dev_out, fd.out_bytes, hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipMemcpyAsync(fe.jc_pin_out, fe.jc_dev_out, 48 + bi, hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));                       // the one wait of the call
-    fe.pin_map_busy = false;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("joint compatibility: ") + hipGetErrorString(e));
-    const char *po = fe.as_pin_out, *pj = fe.jc_pin_out;
-    std::memcpy(out_zxy, po, bz); std::memcpy(out_gxy, po + bz, bz); std::memcpy(out_d2, po + 2 * bz, bd);
-    if (out_na) std::memcpy(out_na, po + 2 * bz + bd + bi, bi);
-    std::memcpy(out_idx, pj + 48, bi);
-    if (out_j) std::memcpy(out_j, pj, sizeof(double));
-    if (out_delta) std::memcpy(out_delta, pj + 8, 3 * sizeof(double));
-    if (out_kept) std::memcpy(out_kept, pj + 32, sizeof(int32_t));
-    if (out_dropped) std::memcpy(out_dropped, pj + 36, sizeof(int32_t));
-    if (out_untestable) std::memcpy(out_untestable, pj + 40, sizeof(int32_t));
-    return GS_OK;
-}
 
 // ---- frame localisation (gs_assoc_nn.hip, k_localize): the iterated pose refinement of a frame against the map — batch / resident / frame calls ----
 extern "C" int gs_loc_params_default(gs_loc_params *p) {
@@ -902,80 +786,6 @@ extern "C" int gs_debug_time_localize_resident(gs_graph *g, int32_t n, const dou
         return gs_localize_resident(g, n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, params, loc, dev_in_index,
         dev_out_pose, dev_out_cov, dev_out_chi2, dev_out_pairs, dev_out_iters, dev_out_status); });
 }
-// the launches, the copies and the one wait of gs_frame_frontend_localize for a checked frame of 1 .. GS_NN_FRAME_MAX observations (before: see
-// frame_assign_enqueue; gs_frame_frontend_relocalize puts its search there)
-static int frame_localize_run(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const NnDev &nd, const JcGate &gt,
-                              const LoParams &lp, FrameHook *before, double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2,
-                              int32_t *out_na, double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable, double *out_delta,
-                              double *out_pose, double *out_cov, double *out_chi2, int32_t *out_pairs, int32_t *out_iters, int32_t *out_status);
-// one frame: the minimum-cost assignment, the joint test of its result and the localisation under the PRUNED index, back to back on the stream.
-// Record staging (bytes): the joint test's as in gs_frame_frontend_jc (J 0, delta 8, counts 32, pruned index 48), then at LO_REC the pose, at
-// + 24 its covariance, + 96 chi2, + 104 pairs / iterations / status
-extern "C" int gs_frame_frontend_localize(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
-                                          const gs_jc_params *jc, const gs_loc_params *loc, double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2,
-                                          int32_t *out_na, double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable, double *out_delta,
-                                          double *out_pose, double *out_cov, double *out_chi2, int32_t *out_pairs, int32_t *out_iters, int32_t *out_status) {
-    if (!g || !pose || k < 0 || (k > 0 && (!obs || !out_zxy || !out_gxy || !out_idx || !out_d2))) return fail(GS_ERR_INVALID, "bad argument");
-    NnDev nd; int rc = nn_params_check(params, nd); if (rc != GS_OK) return rc;
-    JcGate gt; if ((rc = jc_params_check(jc, gt)) != GS_OK) return rc;
-    LoParams lp; if ((rc = loc_params_check(loc, lp)) != GS_OK) return rc;
-    if (k > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations");
-    rc = ensure_device(g); if (rc != GS_OK) return rc;
-    if (k == 0) {                                                   // the empty frame's records, without a launch: no pair, the prior's bits
-        if (out_j) *out_j = 0.0;
-        if (out_kept) *out_kept = 0;
-        if (out_dropped) *out_dropped = 0;
-        if (out_untestable) *out_untestable = 0;
-        if (out_delta) out_delta[0] = out_delta[1] = out_delta[2] = 0.0;
-        if (out_pose) std::memcpy(out_pose, pose, 3 * sizeof(double));
-        if (out_cov) { const int up[9] = {0, 1, 2, 1, 4, 5, 2, 5, 8}; for (int t = 0; t < 9; ++t) out_cov[t] = pose_cov ? pose_cov[up[t]] : 0.0; }
-        if (out_chi2) *out_chi2 = 0.0;
-        if (out_pairs) *out_pairs = 0;
-        if (out_iters) *out_iters = 0;
-        if (out_status) *out_status = 2;
-        return GS_OK; }
-    return frame_localize_run(g, pose, pose_cov, obs, k, nd, gt, lp, nullptr, out_zxy, out_gxy, out_idx, out_d2, out_na, out_j, out_kept, out_dropped, out_untestable,
-                              out_delta, out_pose, out_cov, out_chi2, out_pairs, out_iters, out_status);
-}
-static int frame_localize_run(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const NnDev &nd, const JcGate &gt,
-                              const LoParams &lp, FrameHook *before, double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2,
-                              int32_t *out_na, double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable, double *out_delta,
-                              double *out_pose, double *out_cov, double *out_chi2, int32_t *out_pairs, int32_t *out_iters, int32_t *out_status) {
-    int rc; auto &fe = g->fe; FrameDev fd;
-    constexpr size_t LO_REC = 48 + (size_t)GS_NN_FRAME_MAX * sizeof(int32_t), lbytes = LO_REC + 120;
-    if (!fe.lo_dev_out) {                                           // once per handle: the size does not depend on k
-        HIP_TRY(hipHostMalloc((void **)&fe.lo_pin_out, lbytes, hipHostMallocDefault)); HIP_TRY(hipMalloc((void **)&fe.lo_dev_out, lbytes)); }
-    if ((rc = frame_assign_enqueue(g, true, pose, pose_cov, obs, k, nd, fd, before)) != GS_OK) return rc;
-    char *jd = fe.lo_dev_out, *ld = fe.lo_dev_out + LO_REC;
-    launch_joint_compat(k, fd.pose, 1, fd.pose_of_obs, fd.obs, 1, fd.frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_cov, fd.pose_cov, nd, gt, fd.idx,
-                        (int32_t *)(jd + 48), (double *)jd, (int32_t *)(jd + 32), (int32_t *)(jd + 36), (int32_t *)(jd + 40), (double *)(jd + 8), g->stream);
-    launch_localize(k, fd.pose, 1, fd.pose_of_obs, fd.obs, 1, fd.frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_cov, fd.pose_cov, nd, lp,
-                    (const int32_t *)(jd + 48), LoOut{(double *)ld, (double *)(ld + 24), (double *)(ld + 96), (int32_t *)(ld + 104), (int32_t *)(ld + 108),
-                    (int32_t *)(ld + 112), nullptr}, fe.lo_kernel, g->stream);
-    const size_t bz = (size_t)k * 2 * sizeof(double), bd = (size_t)k * sizeof(double), bi = (size_t)k * sizeof(int32_t);
-    HIP_TRY(hipMemcpyAsync(fe.as_pin_out, fe.as_dev_out, fd.out_bytes, hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipMemcpyAsync(fe.lo_pin_out, fe.lo_dev_out, lbytes, hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));                       // the one wait of the call
-    fe.pin_map_busy = false;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("frame localisation: ") + hipGetErrorString(e));
-    const char *po = fe.as_pin_out, *pj = fe.lo_pin_out, *pl = fe.lo_pin_out + LO_REC;
-    std::memcpy(out_zxy, po, bz); std::memcpy(out_gxy, po + bz, bz); std::memcpy(out_d2, po + 2 * bz, bd);
-    if (out_na) std::memcpy(out_na, po + 2 * bz + bd + bi, bi);
-    std::memcpy(out_idx, pj + 48, bi);
-    if (out_j) std::memcpy(out_j, pj, sizeof(double));
-    if (out_delta) std::memcpy(out_delta, pj + 8, 3 * sizeof(double));
-    if (out_kept) std::memcpy(out_kept, pj + 32, sizeof(int32_t));
-    if (out_dropped) std::memcpy(out_dropped, pj + 36, sizeof(int32_t));
-    if (out_untestable) std::memcpy(out_untestable, pj + 40, sizeof(int32_t));
-    if (out_pose) std::memcpy(out_pose, pl, 3 * sizeof(double));
-    if (out_cov) std::memcpy(out_cov, pl + 24, 9 * sizeof(double));
-    if (out_chi2) std::memcpy(out_chi2, pl + 96, sizeof(double));
-    if (out_pairs) std::memcpy(out_pairs, pl + 104, sizeof(int32_t));
-    if (out_iters) std::memcpy(out_iters, pl + 108, sizeof(int32_t));
-    if (out_status) std::memcpy(out_status, pl + 112, sizeof(int32_t));
-    return GS_OK;
-}
 
 // ---- relocalisation (gs_reloc.hip, k_reloc_seed / k_reloc_pick): a frame's pose found on the map without a prior — batch / resident / frame calls ----
 extern "C" int gs_reloc_params_default(gs_reloc_params *p) {
@@ -1012,8 +822,7 @@ extern "C" int gs_relocalize_batch(gs_graph *g, int32_t n, const double *obs, in
     if ((rc = frame_start_check(n, n_frames, frame_start)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n_frames == 0) return GS_OK;
-    bool grid = n_map >= 2048;                                      // as gs_associate_nn_batch: the grid beyond a few LDS tiles, gs_debug_options.assoc_grid forces either
-    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && n_map > 0;
+    const bool grid = grid_batch(g, n_map);
     const size_t nf = (size_t)n_frames;
     int slice = 0; const int n_slices = reloc_slices(n_frames, n_map, g->fe.rl_slice, slice);
     long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
@@ -1073,8 +882,7 @@ extern "C" int gs_relocalize_resident(gs_graph *g, int32_t n, const double *dev_
     if ((rc = dev_obs_aligned(dev_obs)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n_frames == 0) return GS_OK;
-    const bool grid = g->fe.map_n > 0 && g->opt.assoc_grid != 0;     // as gs_associate_nn_resident
-    if ((rc = reloc_resident_launch(g, grid, n, dev_obs, n_frames, dev_frame_start, rd,
+    if ((rc = reloc_resident_launch(g, grid_resident(g), n, dev_obs, n_frames, dev_frame_start, rd,
                                     RlOut{dev_out_pose, dev_out_cost, dev_out_count, dev_out_seed, dev_out_second_count, dev_out_second_pose, (long long *)dev_out_n_seeds,
                                           dev_out_status, dev_out_index, dev_out_e2}, nullptr, nullptr)) != GS_OK) return rc;
     hipError_t e = hipGetLastError();
@@ -1089,26 +897,153 @@ extern "C" int gs_debug_time_relocalize_resident(gs_graph *g, int32_t n, const d
         return gs_relocalize_resident(g, n, dev_obs, n_frames, dev_frame_start, params, dev_out_pose, dev_out_count, dev_out_cost, dev_out_seed,
         dev_out_second_count, dev_out_second_pose, dev_out_n_seeds, dev_out_status, dev_out_index, dev_out_e2); });
 }
-// one frame: the search, then the chain of gs_frame_frontend_localize from the found pose, back to back on the stream, one wait.
-// Record staging (bytes): pose 0, second pose 24, cost 48, n_seeds 56, seed 64, count 80, second count 84, status 88, then at 96 the index
-// and at 96 + 4 GS_NN_FRAME_MAX the e2 of every observation
+
+// ---- the live chain: one frame through the assignment and what a call asks behind it, back to back on the stream, one wait —
+// gs_frame_frontend_assign / _assign_opt / _jc / _localize / _relocalize (staging and records: gs_frame_host.hpp) ----
 namespace {
-constexpr size_t RL_IDX = 96, RL_E2 = RL_IDX + (size_t)GS_NN_FRAME_MAX * sizeof(int32_t), RL_BYTES = RL_E2 + (size_t)GS_NN_FRAME_MAX * sizeof(double);
-struct RelocHook : FrameHook {
-    RlDev rd; int32_t k; bool second;
-    int enqueue(gs_graph *g, double *dev_pose, const double *dev_obs, int32_t *dev_frame_start) override {
-        auto &fe = g->fe; char *d = fe.rl_dev_out; int rc;
-        bool grid = fe.map_n >= 2048;                                // by the map's size, as the batch call; gs_debug_options.assoc_grid forces either
-        if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && fe.map_n > 0;
-        if ((rc = reloc_resident_launch(g, grid, k, dev_obs, 1, dev_frame_start, rd,
-                                        RlOut{(double *)d, (double *)(d + 48), (int32_t *)(d + 80), (int32_t *)(d + 64), second ? (int32_t *)(d + 84) : nullptr,
-                                              second ? (double *)(d + 24) : nullptr, (long long *)(d + 56), (int32_t *)(d + 88), (int32_t *)(d + RL_IDX), (double *)(d + RL_E2)},
-                                        dev_pose, dev_frame_start + 1)) != GS_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(fe.rl_pin_out, fe.rl_dev_out, RL_BYTES, hipMemcpyDeviceToHost, g->stream));
-        return GS_OK;
-    }
-};
+// the frame and the out-pointers of a call, bundled where the extern "C" function receives them (a null member: the caller did not ask)
+struct FrameIn { const double *pose, *pose_cov, *obs; int32_t k; };
+struct AssignOut { double *zxy, *gxy; int32_t *idx; double *d2; int32_t *na; };
+struct JcOut { double *j; int32_t *kept, *dropped, *untestable; double *delta; };
+struct LocOut { double *pose, *cov, *chi2; int32_t *pairs, *iters, *status; };
+struct RelocOut { double *pose; int32_t *count; double *cost; int32_t *seed, *second_count; double *second_pose; int64_t *n_seeds; int32_t *status, *index; double *e2; };
+// what a call asks of the chain: the greedy (opt false) or the minimum-cost assignment, then the joint test of its result, then the localisation
+// under the pruned index; search: relocalisation's search in front, whose last kernel writes the pose the assignment reads
+struct Chain { bool opt, jc, loc; const RlDev *search; bool second; NnDev nd; JcGate gt; LoParams lp; };
 }
+// a record to the caller's pointers: the pinned copy after the wait, or what the empty frame gets without a launch
+static void jc_store(const JcOut &o, const JcRec &r) {
+    if (o.j) *o.j = r.j;
+    if (o.delta) std::memcpy(o.delta, r.delta, sizeof(r.delta));
+    if (o.kept) *o.kept = r.kept;
+    if (o.dropped) *o.dropped = r.dropped;
+    if (o.untestable) *o.untestable = r.untestable;
+}
+static void lo_store(const LocOut &o, const LoRec &r) {
+    if (o.pose) std::memcpy(o.pose, r.pose, sizeof(r.pose));
+    if (o.cov) std::memcpy(o.cov, r.cov, sizeof(r.cov));
+    if (o.chi2) *o.chi2 = r.chi2;
+    if (o.pairs) *o.pairs = r.pairs;
+    if (o.iters) *o.iters = r.iterations;
+    if (o.status) *o.status = r.status;
+}
+static void reloc_store(const RelocOut &o, const RelocRec &r, int32_t k) {
+    if (o.pose) std::memcpy(o.pose, r.pose, sizeof(r.pose));
+    if (o.second_pose) std::memcpy(o.second_pose, r.second_pose, sizeof(r.second_pose));
+    if (o.cost) *o.cost = r.cost;
+    if (o.n_seeds) *o.n_seeds = r.n_seeds;
+    if (o.seed) std::memcpy(o.seed, r.seed, sizeof(r.seed));
+    if (o.count) *o.count = r.count;
+    if (o.second_count) *o.second_count = r.second_count;
+    if (o.status) *o.status = r.status;
+    if (o.index) std::memcpy(o.index, r.index, (size_t)k * sizeof(int32_t));
+    if (o.e2) std::memcpy(o.e2, r.e2, (size_t)k * sizeof(double));
+}
+// the empty frame's records: no pair and nothing tested (JcRec{}); the prior's bits, status 2; no seed
+static LoRec lo_empty(const double pose[3], const double *pose_cov) {
+    LoRec r{}; const int up[9] = {0, 1, 2, 1, 4, 5, 2, 5, 8};
+    std::memcpy(r.pose, pose, sizeof(r.pose));
+    for (int t = 0; t < 9; ++t) r.cov[t] = pose_cov ? pose_cov[up[t]] : 0.0;
+    r.status = 2;
+    return r;
+}
+static RelocRec reloc_none() {
+    RelocRec r{}; r.cost = INFINITY; r.seed[0] = r.seed[1] = r.seed[2] = r.seed[3] = -1; r.status = 2;
+    return r;
+}
+// everything a caller can get wrong about a chain call, decided before the device is touched; then the device
+static int chain_checks(gs_graph *g, const FrameIn &f, const AssignOut &a, const gs_nn_params *params, const gs_jc_params *jc, const gs_loc_params *loc, Chain &c) {
+    if (!g || !f.pose || f.k < 0 || (f.k > 0 && (!f.obs || !a.zxy || !a.gxy || !a.idx || !a.d2))) return fail(GS_ERR_INVALID, "bad argument");
+    int rc = nn_params_check(params, c.nd); if (rc != GS_OK) return rc;
+    if (c.jc && (rc = jc_params_check(jc, c.gt)) != GS_OK) return rc;
+    if (c.loc && (rc = loc_params_check(loc, c.lp)) != GS_OK) return rc;
+    if (f.k > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations");
+    return ensure_device(g);
+}
+// a checked frame of 0 .. GS_NN_FRAME_MAX observations: staged and sent, the search if asked, the assignment through the resident launch, the
+// joint test and the localisation if asked, the copies back, the one wait, and the results to the caller
+static int frame_chain_run(gs_graph *g, const FrameIn &f, const Chain &c, const AssignOut &a, const JcOut &jo, const LocOut &lo, const RelocOut &ro) {
+    auto &fe = g->fe; int rc; const int32_t k = f.k;
+    if (k == 0) {                                                   // nothing is launched
+        if (c.search) reloc_store(ro, reloc_none(), 0);
+        if (c.jc) jc_store(jo, JcRec{});
+        if (c.loc) lo_store(lo, lo_empty(f.pose, f.pose_cov));
+        return GS_OK; }
+    const FrameLayout L = frame_layout_chain(k);
+    if ((rc = stage_for(g, fe.fr_in, k, GS_NN_FRAME_MAX, [](size_t m) { return frame_layout_chain(m).in_bytes; })) != GS_OK) return rc;
+    if ((rc = stage_for(g, fe.fr_out, k, GS_NN_FRAME_MAX, [](size_t m) { return frame_layout_chain(m).out_bytes; })) != GS_OK) return rc;
+    if (c.jc && (rc = fe.ch_rec.reserve(g, sizeof(ChainRec))) != GS_OK) return rc;       // once per handle: the sizes do not depend on k
+    if (c.search && (rc = fe.rl_out.reserve(g, sizeof(RelocRec))) != GS_OK) return rc;
+    char *pi = fe.fr_in.pin;
+    std::memset(pi, 0, L.in_bytes);                                 // (no covariance: zeros; frame_start[0], pose_of_obs)
+    std::memcpy(pi + L.pose, f.pose, 3 * sizeof(double));
+    if (f.pose_cov) std::memcpy(pi + L.cov, f.pose_cov, 9 * sizeof(double));
+    std::memcpy(pi + L.obs, f.obs, 4 * (size_t)k * sizeof(double));
+    ((int32_t *)(pi + L.frame_start))[1] = k;
+    if ((rc = stage_send(g, fe.fr_in, L.in_bytes)) != GS_OK) return rc;
+    char *di = fe.fr_in.dev, *dv = fe.fr_out.dev;
+    double *d_pose = (double *)(di + L.pose); const double *d_cov = f.pose_cov ? (const double *)(di + L.cov) : nullptr, *d_obs = (const double *)(di + L.obs);
+    int32_t *d_fs = (int32_t *)(di + L.frame_start), *d_idx = (int32_t *)(dv + L.idx); const int32_t *d_po = (const int32_t *)(di + L.pose_of_obs);
+    const bool grid = grid_live(g); const double lidar = g->cfg.lidar_to_cog;
+    if (c.search) { RelocRec *r = (RelocRec *)fe.rl_out.dev;
+        if ((rc = reloc_resident_launch(g, grid, k, d_obs, 1, d_fs, *c.search,
+                                        RlOut{r->pose, &r->cost, &r->count, r->seed, c.second ? &r->second_count : nullptr, c.second ? r->second_pose : nullptr,
+                                              &r->n_seeds, &r->status, r->index, r->e2}, d_pose, d_fs + 1)) != GS_OK) return rc;
+        if ((rc = stage_fetch(g, fe.rl_out, sizeof(RelocRec))) != GS_OK) return rc; }
+    if ((rc = assign_resident_launch(g, c.opt, grid, k, d_pose, 1, d_po, d_obs, 1, d_fs, d_cov, c.nd, d_idx, (double *)(dv + L.d2),
+                                     c.opt ? (int32_t *)(dv + L.na) : nullptr, (double *)(dv + L.z), (double *)(dv + L.g))) != GS_OK) return rc;
+    if (c.jc) { ChainRec *cr = (ChainRec *)fe.ch_rec.dev;           // (the localisation is asked for only behind the joint test)
+        launch_joint_compat(k, d_pose, 1, d_po, d_obs, 1, d_fs, lidar, fe.map_n, fe.map_xy, fe.map_cov, d_cov, c.nd, c.gt, d_idx, cr->jc.index, &cr->jc.j,
+                            &cr->jc.kept, &cr->jc.dropped, &cr->jc.untestable, cr->jc.delta, g->stream);
+        if (c.loc) launch_localize(k, d_pose, 1, d_po, d_obs, 1, d_fs, lidar, fe.map_n, fe.map_xy, fe.map_cov, d_cov, c.nd, c.lp, cr->jc.index,
+                                   LoOut{cr->lo.pose, cr->lo.cov, &cr->lo.chi2, &cr->lo.pairs, &cr->lo.iterations, &cr->lo.status, nullptr}, fe.lo_kernel, g->stream); }
+    const size_t bz = 2 * (size_t)k * sizeof(double), bd = (size_t)k * sizeof(double), bi = (size_t)k * sizeof(int32_t);
+    if ((rc = stage_fetch(g, fe.fr_out, c.opt ? L.out_bytes : L.na)) != GS_OK) return rc;                       // (the greedy assignment counts no admissible cones)
+    if (c.jc && (rc = stage_fetch(g, fe.ch_rec, c.loc ? sizeof(ChainRec) : offsetof(JcRec, index) + bi)) != GS_OK) return rc;
+    if ((rc = frame_finish(g, c.loc ? "frame localisation" : c.jc ? "joint compatibility" : "assignment (nn)")) != GS_OK) return rc;
+    const char *po = fe.fr_out.pin;
+    std::memcpy(a.zxy, po + L.z, bz); std::memcpy(a.gxy, po + L.g, bz); std::memcpy(a.d2, po + L.d2, bd);
+    if (a.na) std::memcpy(a.na, po + L.na, bi);
+    if (!c.jc) std::memcpy(a.idx, po + L.idx, bi);
+    else { const ChainRec *pr = (const ChainRec *)fe.ch_rec.pin;    // the joint test's pruned index in the assignment's place
+        std::memcpy(a.idx, pr->jc.index, bi); jc_store(jo, pr->jc);
+        if (c.loc) lo_store(lo, pr->lo); }
+    if (c.search) { const RelocRec *rr = (const RelocRec *)fe.rl_out.pin;
+        reloc_store(ro, *rr, k);
+        if (rr->status >= 2)                                        // the chain found an empty frame: it wrote nothing per observation
+            for (int i = 0; i < k; ++i) { a.zxy[2 * i] = a.zxy[2 * i + 1] = a.gxy[2 * i] = a.gxy[2 * i + 1] = 0.0; a.idx[i] = -1; a.d2[i] = INFINITY;
+                if (a.na) a.na[i] = 0; } }
+    return GS_OK;
+}
+extern "C" int gs_frame_frontend_assign(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
+                                        double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2) {
+    Chain c{}; const FrameIn f{pose, pose_cov, obs, k}; const AssignOut a{out_zxy, out_gxy, out_idx, out_d2, nullptr};
+    const int rc = chain_checks(g, f, a, params, nullptr, nullptr, c);
+    return rc != GS_OK ? rc : frame_chain_run(g, f, c, a, JcOut{}, LocOut{}, RelocOut{});
+}
+extern "C" int gs_frame_frontend_assign_opt(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
+                                            double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2, int32_t *out_na) {
+    Chain c{}; c.opt = true; const FrameIn f{pose, pose_cov, obs, k}; const AssignOut a{out_zxy, out_gxy, out_idx, out_d2, out_na};
+    const int rc = chain_checks(g, f, a, params, nullptr, nullptr, c);
+    return rc != GS_OK ? rc : frame_chain_run(g, f, c, a, JcOut{}, LocOut{}, RelocOut{});
+}
+extern "C" int gs_frame_frontend_jc(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
+                                    const gs_jc_params *jc, double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2, int32_t *out_na,
+                                    double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable, double *out_delta) {
+    Chain c{}; c.opt = c.jc = true; const FrameIn f{pose, pose_cov, obs, k}; const AssignOut a{out_zxy, out_gxy, out_idx, out_d2, out_na};
+    const int rc = chain_checks(g, f, a, params, jc, nullptr, c);
+    return rc != GS_OK ? rc : frame_chain_run(g, f, c, a, JcOut{out_j, out_kept, out_dropped, out_untestable, out_delta}, LocOut{}, RelocOut{});
+}
+extern "C" int gs_frame_frontend_localize(gs_graph *g, const double pose[3], const double *pose_cov, const double *obs, int32_t k, const gs_nn_params *params,
+                                          const gs_jc_params *jc, const gs_loc_params *loc, double *out_zxy, double *out_gxy, int32_t *out_idx, double *out_d2,
+                                          int32_t *out_na, double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable, double *out_delta,
+                                          double *out_pose, double *out_cov, double *out_chi2, int32_t *out_pairs, int32_t *out_iters, int32_t *out_status) {
+    Chain c{}; c.opt = c.jc = c.loc = true; const FrameIn f{pose, pose_cov, obs, k}; const AssignOut a{out_zxy, out_gxy, out_idx, out_d2, out_na};
+    const int rc = chain_checks(g, f, a, params, jc, loc, c);
+    return rc != GS_OK ? rc : frame_chain_run(g, f, c, a, JcOut{out_j, out_kept, out_dropped, out_untestable, out_delta},
+                                              LocOut{out_pose, out_cov, out_chi2, out_pairs, out_iters, out_status}, RelocOut{});
+}
+// the search, then the chain of gs_frame_frontend_localize from the found pose under the diagonal prior (the empty frame: at the pose zero)
 extern "C" int gs_frame_frontend_relocalize(gs_graph *g, const double *obs, int32_t k, const gs_reloc_params *reloc, double prior_sigma_xy, double prior_sigma_theta,
                                             const gs_nn_params *params, const gs_jc_params *jc, const gs_loc_params *loc, double *out_rl_pose, int32_t *out_rl_count,
                                             double *out_rl_cost, int32_t *out_rl_seed, int32_t *out_second_count, double *out_second_pose, int64_t *out_n_seeds,
@@ -1117,50 +1052,16 @@ extern "C" int gs_frame_frontend_relocalize(gs_graph *g, const double *obs, int3
                                             double *out_delta, double *out_pose, double *out_cov, double *out_chi2, int32_t *out_pairs, int32_t *out_iters,
                                             int32_t *out_status) {
     if (!g || k < 0 || (k > 0 && (!obs || !out_zxy || !out_gxy || !out_idx || !out_d2))) return fail(GS_ERR_INVALID, "bad argument");
-    RelocHook hook; int rc = reloc_params_check(reloc, hook.rd); if (rc != GS_OK) return rc;
+    RlDev rd; int rc = reloc_params_check(reloc, rd); if (rc != GS_OK) return rc;
     if (!std::isfinite(prior_sigma_xy) || prior_sigma_xy < 0.0 || !std::isfinite(prior_sigma_theta) || prior_sigma_theta < 0.0)
         return fail(GS_ERR_INVALID, "a prior sigma is not finite or negative");
-    NnDev nd; if ((rc = nn_params_check(params, nd)) != GS_OK) return rc;
-    JcGate gt; if ((rc = jc_params_check(jc, gt)) != GS_OK) return rc;
-    LoParams lp; if ((rc = loc_params_check(loc, lp)) != GS_OK) return rc;
-    if (k > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "a frame holds more than GS_NN_FRAME_MAX observations");
-    rc = ensure_device(g); if (rc != GS_OK) return rc;
     const double zero3[3] = {0.0, 0.0, 0.0};
     const double prior[9] = {prior_sigma_xy * prior_sigma_xy, 0.0, 0.0, 0.0, prior_sigma_xy * prior_sigma_xy, 0.0, 0.0, 0.0, prior_sigma_theta * prior_sigma_theta};
-    auto none = [&] {                                                // the record of "no seed"
-        if (out_rl_pose) std::memcpy(out_rl_pose, zero3, sizeof(zero3));
-        if (out_rl_count) *out_rl_count = 0;
-        if (out_rl_cost) *out_rl_cost = INFINITY;
-        if (out_rl_seed) out_rl_seed[0] = out_rl_seed[1] = out_rl_seed[2] = out_rl_seed[3] = -1;
-        if (out_second_count) *out_second_count = 0;
-        if (out_second_pose) std::memcpy(out_second_pose, zero3, sizeof(zero3));
-        if (out_n_seeds) *out_n_seeds = 0;
-        if (out_rl_status) *out_rl_status = 2; };
-    if (k == 0) {                                                    // nothing is launched: no seed, and the chain's empty frame at the pose zero
-        none();
-        return gs_frame_frontend_localize(g, zero3, prior, obs, 0, params, jc, loc, out_zxy, out_gxy, out_idx, out_d2, out_na, out_j, out_kept, out_dropped,
-                                          out_untestable, out_delta, out_pose, out_cov, out_chi2, out_pairs, out_iters, out_status); }
-    auto &fe = g->fe;
-    if (!fe.rl_dev_out) {                                            // once per handle: the size does not depend on k
-        HIP_TRY(hipHostMalloc((void **)&fe.rl_pin_out, RL_BYTES, hipHostMallocDefault)); HIP_TRY(hipMalloc((void **)&fe.rl_dev_out, RL_BYTES)); }
-    hook.k = k; hook.second = out_second_count || out_second_pose;
-    if ((rc = frame_localize_run(g, zero3, prior, obs, k, nd, gt, lp, &hook, out_zxy, out_gxy, out_idx, out_d2, out_na, out_j, out_kept, out_dropped, out_untestable,
-                                 out_delta, out_pose, out_cov, out_chi2, out_pairs, out_iters, out_status)) != GS_OK) return rc;
-    const char *pr = fe.rl_pin_out; int32_t status; std::memcpy(&status, pr + 88, sizeof(status));
-    if (out_rl_pose) std::memcpy(out_rl_pose, pr, 3 * sizeof(double));
-    if (out_second_pose) std::memcpy(out_second_pose, pr + 24, 3 * sizeof(double));
-    if (out_rl_cost) std::memcpy(out_rl_cost, pr + 48, sizeof(double));
-    if (out_n_seeds) std::memcpy(out_n_seeds, pr + 56, sizeof(int64_t));
-    if (out_rl_seed) std::memcpy(out_rl_seed, pr + 64, 4 * sizeof(int32_t));
-    if (out_rl_count) std::memcpy(out_rl_count, pr + 80, sizeof(int32_t));
-    if (out_second_count) std::memcpy(out_second_count, pr + 84, sizeof(int32_t));
-    if (out_rl_status) *out_rl_status = status;
-    if (out_rl_index) std::memcpy(out_rl_index, pr + RL_IDX, (size_t)k * sizeof(int32_t));
-    if (out_rl_e2) std::memcpy(out_rl_e2, pr + RL_E2, (size_t)k * sizeof(double));
-    if (status >= 2)                                                 // the chain found an empty frame: it wrote nothing per observation
-        for (int i = 0; i < k; ++i) { out_zxy[2 * i] = out_zxy[2 * i + 1] = out_gxy[2 * i] = out_gxy[2 * i + 1] = 0.0; out_idx[i] = -1; out_d2[i] = INFINITY;
-            if (out_na) out_na[i] = 0; }
-    return GS_OK;
+    Chain c{}; c.opt = c.jc = c.loc = true; c.search = &rd; c.second = out_second_count || out_second_pose;
+    const FrameIn f{zero3, prior, obs, k}; const AssignOut a{out_zxy, out_gxy, out_idx, out_d2, out_na};
+    if ((rc = chain_checks(g, f, a, params, jc, loc, c)) != GS_OK) return rc;
+    return frame_chain_run(g, f, c, a, JcOut{out_j, out_kept, out_dropped, out_untestable, out_delta}, LocOut{out_pose, out_cov, out_chi2, out_pairs, out_iters, out_status},
+                           RelocOut{out_rl_pose, out_rl_count, out_rl_cost, out_rl_seed, out_second_count, out_second_pose, out_n_seeds, out_rl_status, out_rl_index, out_rl_e2});
 }
 
 // ---- frame following (gs_follow.hip): pose hypotheses carried from frame to frame on the device — batch / resident / live frame calls ----
@@ -1210,6 +1111,19 @@ static int follow_reserve(gs_graph *g, int n_hyp, int cap, FollowLayout &L) {
         if (fe.fo_mem) hipFree(fe.fo_mem);
         fe.fo_mem = nullptr; fe.fo_bytes = 0;
         HIP_TRY(hipMalloc((void **)&fe.fo_mem, L.bytes)); fe.fo_bytes = L.bytes; }
+    return GS_OK;
+}
+// the map / grid part of a run: a batch call's uploaded map and carved grid (gb null: the tile kernel) ...
+static void follow_map(FollowRun &R, int n_map, const double *map_xy, const int32_t *map_type, const double *map_cov, const GridBufs *gb) {
+    R.n_map = n_map; R.map_xy = map_xy; R.map_type = map_type; R.map_cov = map_cov;
+    R.buckets = gb ? gb->buckets : 0; R.cell_start = gb ? gb->start : nullptr; R.cell_items = gb ? gb->items : nullptr;
+}
+// ... or the resident map, through its grid (built here if the map or the distance changed) where `grid`
+static int follow_map_resident(gs_graph *g, FollowRun &R, bool grid) {
+    auto &fe = g->fe; GridBufs gb{};
+    if (grid) { const int rc = resident_grid(g, R.nd.max_distance); if (rc != GS_OK) return rc;
+        gb = grid_carve(fe.grid_mem, fe.map_n, fe.grid_max_cells); }
+    follow_map(R, fe.map_n, fe.map_xy, fe.map_type, fe.map_cov, grid ? &gb : nullptr);
     return GS_OK;
 }
 static gs_follow_state *follow_state(gs_graph *g, bool live) { return (gs_follow_state *)g->fe.fo_state + (live ? 0 : GS_FOLLOW_HYP_MAX); }
@@ -1267,8 +1181,7 @@ extern "C" int gs_follow_batch(gs_graph *g, int32_t n_hyp, const double *poses, 
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     int cap = 0; for (int t = 0; t < n_steps; ++t) cap = std::max(cap, frame_start[t + 1] - frame_start[t]);
     FollowLayout L; if ((rc = follow_reserve(g, n_hyp, cap, L)) != GS_OK) return rc;
-    bool grid = n_map >= 2048;                                      // as gs_assign_opt_batch
-    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && n_map > 0;
+    const bool grid = grid_batch(g, n_map);
     long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
     std::vector<gs_follow_state> init((size_t)n_hyp); follow_init_host(n_hyp, poses, covs, init.data());
     const int32_t best0[2] = {0, n_hyp};
@@ -1283,8 +1196,7 @@ extern "C" int gs_follow_batch(gs_graph *g, int32_t n_hyp, const double *poses, 
         launch_grid_build(n_map, mx, R.nd.max_distance, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream); }
     R.n_hyp = n_hyp; R.n = n; R.cap = cap; R.obs = ob; R.fs = fs; R.motion = mo; R.motion_cov = motion_cov ? mq : nullptr;
     R.state = stt; R.best2 = b2; R.rec = rec; R.index = out_index ? oi : nullptr;
-    R.n_map = n_map; R.map_xy = mx; R.map_type = mt; R.map_cov = map_cov ? mc : nullptr; R.buckets = buckets;
-    R.cell_start = grid ? gb.start : nullptr; R.cell_items = grid ? gb.items : nullptr;
+    follow_map(R, n_map, mx, mt, map_cov ? mc : nullptr, grid ? &gb : nullptr);
     for (int t = 0; t < n_steps; ++t)                               // back to back: no host decision between the frames
         follow_step_enqueue(g, R, L, t, t, frame_start[t + 1] - frame_start[t], t - 1, nullptr, nullptr);
     sg.fetch(out_steps, rec, nrec * sizeof(gs_follow_step)); sg.fetch(out_index, oi, (size_t)n_hyp * n * sizeof(int32_t));
@@ -1301,16 +1213,10 @@ extern "C" int gs_follow_resident(gs_graph *g, int32_t n_hyp, const double *dev_
     if (frame_cap < 0 || frame_cap > GS_NN_FRAME_MAX) return fail(GS_ERR_INVALID, "frame_cap outside 0 .. GS_NN_FRAME_MAX");
     if ((rc = dev_obs_aligned(dev_obs)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
-    auto &fe = g->fe;
     FollowLayout L; if ((rc = follow_reserve(g, n_hyp, frame_cap, L)) != GS_OK) return rc;
-    const bool grid = fe.map_n > 0 && g->opt.assoc_grid != 0;        // as gs_assign_opt_resident
-    GridBufs gb{};
-    if (grid) { if ((rc = resident_grid(g, R.nd.max_distance)) != GS_OK) return rc;
-        gb = grid_carve(fe.grid_mem, fe.map_n, fe.grid_max_cells); }
+    if ((rc = follow_map_resident(g, R, grid_resident(g))) != GS_OK) return rc;
     R.n_hyp = n_hyp; R.n = n; R.cap = frame_cap; R.obs = dev_obs; R.fs = dev_frame_start; R.motion = dev_motion; R.motion_cov = dev_motion_cov;
     R.state = follow_state(g, false); R.best2 = follow_best(g, false); R.rec = dev_out_steps; R.index = dev_out_index;
-    R.n_map = fe.map_n; R.map_xy = fe.map_xy; R.map_type = fe.map_type; R.map_cov = fe.map_cov; R.buckets = gb.buckets;
-    R.cell_start = grid ? gb.start : nullptr; R.cell_items = grid ? gb.items : nullptr;
     launch_follow_init(n_hyp, dev_poses, dev_covs, R.state, R.best2, g->stream, g->ev_lin[0], n_steps == 0 ? g->ev_lin[1] : nullptr);
     for (int t = 0; t < n_steps; ++t) follow_step_enqueue(g, R, L, t, t, -1, t - 1, nullptr, t == n_steps - 1 ? g->ev_lin[1] : nullptr);
     if (dev_out_state) HIP_TRY(hipMemcpyAsync(dev_out_state, R.state, (size_t)n_hyp * sizeof(gs_follow_state), hipMemcpyDeviceToDevice, g->stream));
@@ -1370,39 +1276,29 @@ extern "C" int gs_frame_frontend_follow(gs_graph *g, const double *motion, const
     const int n_hyp = fe.fo_n_hyp;
     FollowLayout L; if ((rc = follow_reserve(g, n_hyp, k, L)) != GS_OK) return rc;
     using Io = FollowFrameIo;
-    if (!fe.fo_dev_in) {                                            // once per handle: fixed sizes
-        HIP_TRY(hipHostMalloc((void **)&fe.fo_pin_in, Io::IN_BYTES, hipHostMallocDefault)); HIP_TRY(hipHostMalloc((void **)&fe.fo_pin_out, Io::OUT_BYTES, hipHostMallocDefault));
-        HIP_TRY(hipMalloc((void **)&fe.fo_dev_in, Io::IN_BYTES)); HIP_TRY(hipMalloc((void **)&fe.fo_dev_out, Io::OUT_BYTES)); }
-    std::memset(fe.fo_pin_in, 0, Io::IN_OBS);
-    if (motion) std::memcpy(fe.fo_pin_in + Io::IN_MOTION, motion, 3 * sizeof(double));
-    if (motion_cov) std::memcpy(fe.fo_pin_in + Io::IN_COV, motion_cov, 9 * sizeof(double));
-    ((int32_t *)(fe.fo_pin_in + Io::IN_FS))[1] = k;
-    if (k > 0) std::memcpy(fe.fo_pin_in + Io::IN_OBS, obs, 4 * (size_t)k * sizeof(double));
-    HIP_TRY(hipMemcpyAsync(fe.fo_dev_in, fe.fo_pin_in, Io::in_bytes(k), hipMemcpyHostToDevice, g->stream));
-    bool grid = fe.map_n >= 2048;                                    // by the map's size, as gs_frame_frontend_localize
-    if (g->opt.assoc_grid >= 0) grid = g->opt.assoc_grid != 0 && fe.map_n > 0;
-    GridBufs gb{};
-    if (grid) { if ((rc = resident_grid(g, R.nd.max_distance)) != GS_OK) return rc;
-        gb = grid_carve(fe.grid_mem, fe.map_n, fe.grid_max_cells); }
-    R.n_hyp = n_hyp; R.n = k; R.cap = k; R.obs = (const double *)(fe.fo_dev_in + Io::IN_OBS); R.fs = (const int32_t *)(fe.fo_dev_in + Io::IN_FS);
-    R.motion = (const double *)(fe.fo_dev_in + Io::IN_MOTION); R.motion_cov = motion_cov ? (const double *)(fe.fo_dev_in + Io::IN_COV) : nullptr;
+    if ((rc = fe.fo_in.reserve(g, Io::IN_BYTES)) != GS_OK || (rc = fe.fo_out.reserve(g, Io::OUT_BYTES)) != GS_OK) return rc;    // once per handle: fixed sizes
+    char *pi = fe.fo_in.pin, *di = fe.fo_in.dev, *po = fe.fo_out.pin, *dv = fe.fo_out.dev;
+    std::memset(pi, 0, Io::IN_OBS);
+    if (motion) std::memcpy(pi + Io::IN_MOTION, motion, 3 * sizeof(double));
+    if (motion_cov) std::memcpy(pi + Io::IN_COV, motion_cov, 9 * sizeof(double));
+    ((int32_t *)(pi + Io::IN_FS))[1] = k;
+    if (k > 0) std::memcpy(pi + Io::IN_OBS, obs, 4 * (size_t)k * sizeof(double));
+    if ((rc = stage_send(g, fe.fo_in, Io::in_bytes(k))) != GS_OK) return rc;
+    if ((rc = follow_map_resident(g, R, grid_live(g))) != GS_OK) return rc;
+    R.n_hyp = n_hyp; R.n = k; R.cap = k; R.obs = (const double *)(di + Io::IN_OBS); R.fs = (const int32_t *)(di + Io::IN_FS);
+    R.motion = (const double *)(di + Io::IN_MOTION); R.motion_cov = motion_cov ? (const double *)(di + Io::IN_COV) : nullptr;
     R.state = follow_state(g, true); R.best2 = follow_best(g, true);
-    R.rec = (gs_follow_step *)(fe.fo_dev_out + Io::OUT_REC); R.index = out_index ? (int32_t *)(fe.fo_dev_out + Io::OUT_IDX) : nullptr;
-    R.n_map = fe.map_n; R.map_xy = fe.map_xy; R.map_type = fe.map_type; R.map_cov = fe.map_cov; R.buckets = gb.buckets;
-    R.cell_start = grid ? gb.start : nullptr; R.cell_items = grid ? gb.items : nullptr;
+    R.rec = (gs_follow_step *)(dv + Io::OUT_REC); R.index = out_index ? (int32_t *)(dv + Io::OUT_IDX) : nullptr;
     follow_step_enqueue(g, R, L, 0, fe.fo_t, k, motion ? 0 : -1, nullptr, nullptr);
     const size_t brec = (size_t)n_hyp * sizeof(gs_follow_step), bidx = (size_t)n_hyp * k * sizeof(int32_t);
-    HIP_TRY(hipMemcpyAsync(fe.fo_pin_out + Io::OUT_REC, fe.fo_dev_out + Io::OUT_REC, brec, hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipMemcpyAsync(fe.fo_pin_out + Io::OUT_BEST, R.best2, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    if (out_index && bidx) HIP_TRY(hipMemcpyAsync(fe.fo_pin_out + Io::OUT_IDX, fe.fo_dev_out + Io::OUT_IDX, bidx, hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));                       // the one wait of the frame
-    fe.pin_map_busy = false;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("frame following: ") + hipGetErrorString(e));
+    if ((rc = stage_fetch(g, fe.fo_out, brec, Io::OUT_REC)) != GS_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(po + Io::OUT_BEST, R.best2, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));     // (the pair lives with the state, not in the staging)
+    if (out_index && bidx && (rc = stage_fetch(g, fe.fo_out, bidx, Io::OUT_IDX)) != GS_OK) return rc;
+    if ((rc = frame_finish(g, "frame following")) != GS_OK) return rc;
     fe.fo_t += 1;
-    if (out_steps) std::memcpy(out_steps, fe.fo_pin_out + Io::OUT_REC, brec);
-    if (out_index && bidx) std::memcpy(out_index, fe.fo_pin_out + Io::OUT_IDX, bidx);
-    if (out_best) std::memcpy(out_best, fe.fo_pin_out + Io::OUT_BEST, sizeof(int32_t));
-    if (out_n_tracking) std::memcpy(out_n_tracking, fe.fo_pin_out + Io::OUT_BEST + 4, sizeof(int32_t));
+    if (out_steps) std::memcpy(out_steps, po + Io::OUT_REC, brec);
+    if (out_index && bidx) std::memcpy(out_index, po + Io::OUT_IDX, bidx);
+    if (out_best) std::memcpy(out_best, po + Io::OUT_BEST, sizeof(int32_t));
+    if (out_n_tracking) std::memcpy(out_n_tracking, po + Io::OUT_N_TRACKING, sizeof(int32_t));
     return GS_OK;
 }

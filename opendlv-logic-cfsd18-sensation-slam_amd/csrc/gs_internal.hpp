@@ -8,6 +8,7 @@
 
 #include "../../include/graphslam.h"
 #include "../../include/graphslam_debug.h"
+struct gs_graph;
 #include "gs_device.hpp"
 #include "gs_dogleg.hpp"
 #include "gs_edge_mask.hpp"
@@ -21,6 +22,9 @@ namespace gs {
 // One grow-only device allocation of the handle's own, holding the blocks of an ArenaLayout (gs_side_host.hpp); reserve / upload /
 // release: gs_private.hpp
 struct DevArena { void *mem = nullptr; size_t cap = 0; char *at(size_t off) const { return (char *)mem + off; } };
+// A live frame call's staging: pinned host memory and device memory of one size, grow-only — reserve waits for the stream before it frees the
+// smaller pair, which then holds nothing (gs_frontend.cpp; the layouts: gs_frame_host.hpp)
+struct FrameStage { char *pin = nullptr, *dev = nullptr; size_t bytes = 0; int reserve(gs_graph *g, size_t want); void release(); };
 }
 
 struct gs_graph {
@@ -59,8 +63,10 @@ struct gs_graph {
     // front end (A0 / A1): nothing is allocated or freed per call
     struct FrontEnd {
         char *arena = nullptr; size_t arena_bytes = 0;          // grow-only device scratch of the batch calls
-        double *pin_in = nullptr; char *pin_out = nullptr;      // per-frame path: pinned staging, device in / out, capacity in observations
-        double *dev_in = nullptr; char *dev_out = nullptr; int cap_obs = 0;
+        // the live frame calls' staging (each null until a call needs it): a frame in and its per-observation results out — one pair for
+        // gs_frame_frontend, gs_frame_frontend_nn and the assignment chain, whose calls each end in a wait —, the chain's records (ChainRec),
+        // the search's record of gs_frame_frontend_relocalize (RelocRec), and gs_frame_frontend_follow's in and out (FollowFrameIo)
+        gs::FrameStage fr_in, fr_out, ch_rec, rl_out, fo_in, fo_out;
         double *map_xy = nullptr; int32_t *map_type = nullptr;  // the resident association map (mirror of Slam::m_map), grow-only
         int map_n = 0, map_cap = 0;
         char *pin_map = nullptr; size_t pin_map_bytes = 0; bool pin_map_busy = false;   // pinned staging of map appends (busy: a copy out of it may be in flight)
@@ -68,29 +74,22 @@ struct gs_graph {
         bool grid_valid = false; int grid_map_n = 0; double grid_thr = 0.0; long long grid_max_cells = 0;
         double *pcs = nullptr; size_t pcs_bytes = 0;            // cos / sin of the poses of a batched association (scratch, grow-only)
         // covariance-gated association: the resident map's 2x2 blocks (map_cap x 4; null until a call needs them: every cone's block is
-        // zero then), the index table of gs_map_set_cov_from_marginals, and the frame path's own staging (capacity in observations)
+        // zero then) and the index table of gs_map_set_cov_from_marginals
         double *map_cov = nullptr;
         int64_t *cov_src = nullptr; size_t cov_src_n = 0;
-        double *nn_pin_in = nullptr, *nn_dev_in = nullptr; char *nn_pin_out = nullptr, *nn_dev_out = nullptr; int nn_cap_obs = 0;
-        // one-to-one association: the frame call's staging (null until gs_frame_frontend_assign is called), capacity in observations
-        char *as_pin_in = nullptr, *as_dev_in = nullptr, *as_pin_out = nullptr, *as_dev_out = nullptr; int as_cap_obs = 0;
-        // joint compatibility: the frame call's record and pruned index (null until gs_frame_frontend_jc is called; sized for GS_NN_FRAME_MAX)
-        char *jc_pin_out = nullptr, *jc_dev_out = nullptr;
-        // frame localisation: the frame call's record (null until gs_frame_frontend_localize is called; a fixed size); gs_debug_localize's
-        // kernel choice (-1: by the mean frame size) and step output (a device pointer of the caller's, or null)
-        char *lo_pin_out = nullptr, *lo_dev_out = nullptr; int lo_kernel = -1; double *lo_step = nullptr;
+        // frame localisation: gs_debug_localize's kernel choice (-1: by the mean frame size) and step output (a device pointer of the caller's, or null)
+        int lo_kernel = -1; double *lo_step = nullptr;
         // relocalisation (null until one of its calls is made): the seed kernel's records of the resident and the frame call (grow-only), a grid
-        // of its own beside the association's (cell edge from inlier_radius: the two edges must not evict each other), the frame call's
-        // record staging (a fixed size), gs_debug_relocalize's slice (0: the launcher's choice)
+        // of its own beside the association's (cell edge from inlier_radius: the two edges must not evict each other), gs_debug_relocalize's
+        // slice (0: the launcher's choice)
         char *rl_rec = nullptr; size_t rl_rec_bytes = 0;
         char *rl_grid_mem = nullptr; size_t rl_grid_bytes = 0; bool rl_grid_valid = false; int rl_grid_map_n = 0; double rl_grid_thr = 0.0; long long rl_grid_cells = 0;
-        char *rl_pin_out = nullptr, *rl_dev_out = nullptr; int rl_slice = 0;
+        int rl_slice = 0;
         // frame following (null until one of its calls is made): the per-step stage and chain buffers (gs_follow_host.hpp's FollowLayout,
         // grow-only), the hypotheses' state — 64 records that live between gs_frame_frontend_follow calls, 64 more that a batch or resident
-        // run works in — with {best, n_tracking} of either, the frame call's staging (fixed sizes), and the live run's size and step count
+        // run works in — with {best, n_tracking} of either, and the live run's size and step count
         char *fo_mem = nullptr; size_t fo_bytes = 0;
         char *fo_state = nullptr; int32_t *fo_best = nullptr;
-        char *fo_pin_in = nullptr, *fo_dev_in = nullptr, *fo_pin_out = nullptr, *fo_dev_out = nullptr;
         int fo_n_hyp = 0, fo_t = 0;
     } fe;
     bool tree_proven = false;               // a whole-tree launch sequence of the CURRENT plan has completed without a flag timeout (gs_optimize then sends all iterations of a call at once)
