@@ -1176,6 +1176,127 @@ int  gs_frame_frontend_follow(gs_graph *g, const double *motion_3, const double 
                               const gs_nn_params *params, const gs_jc_params *jc, const gs_loc_params *loc, const gs_follow_params *follow,
                               gs_follow_step *out_steps, int32_t *out_index, int32_t *out_best, int32_t *out_n_tracking);
 
+/* ---- cone candidates: unmatched observations tracked into new map cones --------------------------------------------------------------
+ * Every call above works against a finished map and returns -1 for an observation that no map cone explains.  These calls consume that -1:
+ * a table of GS_CAND_MAX tentative cones on the device, into which such observations are fused or spawn an entry; an entry is confirmed
+ * after enough sightings and retired after enough misses while it should have been visible; confirmed entries are handed to the caller,
+ * who appends them to the map and the graph.  The reference's addConesToMap (src/slam.cpp:608-623) makes a map cone and a vertex of an
+ * unmatched observation inside coneMappingThreshold on first sight, without a second look or a way back.  The rule is build-defined.  No
+ * contraction anywhere: every product and sum below is rounded once, in the order the parentheses give.
+ *
+ * Table.  GS_CAND_MAX slots, stored as a map is stored (xy [2], type, cov [4] per slot) so that the association takes it as one, and a
+ *      record (gs_cand) per slot that repeats those bits and adds: id (a serial number, unique over the table's life), state (0 free,
+ *      1 tentative, 2 confirmed), hits, misses (the current run of misses), first_step, last_step, confirm_step (-1 until confirmed).  A FREE
+ *      slot is xy = (NaN, NaN), type 0, cov 0, id -1, every counter 0, confirm_step -1: no admissibility test of the covariance-gated
+ *      association holds for it.  The table also holds next_id and the step counter t.  Loading n_in records (gs_cand_set, the initial table
+ *      of a batch or resident run) puts record s into slot s as it is — a record of state 0 becomes a free slot whatever else it holds — and
+ *      frees the rest; next_id = 1 + the largest id and t = 1 + the largest last_step over the loaded records that are not free, 0 without one.
+ * Step t.  One frame of k <= GS_NN_FRAME_MAX observations (collector layout 4 x k), a pose x = (tx, ty, theta), its covariance Sigma_p (NULL:
+ *      none) and in_idx[i], the map cone that explains observation i (-1: none; in_idx == NULL: nothing is explained).
+ *   1. Unexplained: U = { i : in_idx[i] < 0 }.
+ *   2. Association.  The minimum-cost association above over this one frame, with the table AS IT STOOD BEFORE THE STEP as the map
+ *      (n_map = GS_CAND_MAX, its cov array, brute force), the pose and Sigma_p of the step, and the azimuth of every observation outside U
+ *      replaced by NaN (an invalid query: -1).  slot[i] and n_admissible[i] are bitwise what gs_assign_opt_batch returns for those arrays.
+ *   3. Fusion, for every i with slot[i] = c >= 0.  g and A = Q + P are the query's of the covariance-gated association (Sigma_p NULL: A = Q);
+ *      l = the slot's xy, C00 C01 C11 = its cov [0] [1] [3]:
+ *            S00 = C00 + A00   S01 = C01 + A01   S11 = C11 + A11      det = (S00 S11) - (S01 S01)      n0 = gx - lx   n1 = gy - ly
+ *            K00 = ((C00 S11) - (C01 S01)) / det      K01 = ((C01 S00) - (C00 S01)) / det
+ *            K10 = ((C01 S11) - (C11 S01)) / det      K11 = ((C11 S00) - (C01 S01)) / det
+ *            lx+ = lx + ((K00 n0) + (K01 n1))         ly+ = ly + ((K10 n0) + (K11 n1))
+ *            C00+ = (K00 A00) + (K01 A01)             C01+ = (K00 A01) + (K01 A11)             C11+ = (K10 A01) + (K11 A11)
+ *      (K = C S^-1, C+ = K A = the parallel sum C S^-1 A: no C - K C cancellation); cov+ = (C00+, C01+, C01+, C11+), the 01 entry formed once.
+ *      hits += 1, misses = 0, last_step = t.  (An assigned pair is admissible, so det > 0 holds.)
+ *   4. Misses, for every slot that is not free and was not fused in this step.  (s, c) = sincos(theta), the device call the association's
+ *      query side makes;  ex = lx - tx,  ey = ly - ty;  dx = (c ex) + (s ey),  dy = (c ey) - (s ex);  r2 = (dx dx) + (dy dy).  The slot is
+ *      VISIBLE iff BOTH  r2 < view_range view_range  (the right side formed once, on the host)  and  dx >= view_cos sqrt(r2)  hold (positive
+ *      tests: a NaN fails).  Visible: misses += 1, and a TENTATIVE slot with misses >= max_misses becomes free.  A confirmed slot never
+ *      retires.  A slot that is not visible is left alone.
+ *   5. Confirmation.  A tentative slot (not retired in 4) with hits >= confirm_hits: state = 2, confirm_step = t.
+ *   6. Spawning.  i in U with a valid query, slot[i] = -1 and n_admissible[i] == 0 SPAWNS iff its distance column < spawn_range (the
+ *      reference's coneMappingThreshold test; positive: a NaN fails), else it is FAR.  Spawners are ranked in ascending observation index;
+ *      rank r takes the r-th slot, in ascending slot index, of those that were FREE AT THE START OF THE STEP (a slot retired in 4 is reusable
+ *      from the next step on).  The slot gets xy = g, cov = (A00, A01, A01, A11), type = (int) the observation's type (the C conversion of
+ *      gs_slam's addConesToMap), id = next_id + r, hits 1, misses 0, first_step = last_step = t, state 1 and confirm_step -1 — or state 2 and
+ *      confirm_step = t when confirm_hits == 1.  Spawners beyond the free slots are DROPPED.  next_id += the slots taken.
+ *      i in U with a valid query, slot[i] = -1 and n_admissible[i] > 0 is CONTESTED: it neither fuses nor spawns.  An invalid query (g not
+ *      finite, or r == 0) does nothing and is counted in none of fused, spawned, contested, far, dropped.
+ *   7. Outputs.  out_cand_id[i] / out_cand_slot[i]: the id and the slot fused with or spawned into, else -1 / -1.  gs_cand_step: step = t,
+ *      n_unexplained = |U|, n_fused, n_spawned (slots taken), n_contested, n_far, n_dropped, n_missed (visible slots of 4), n_retired,
+ *      n_confirmed (newly confirmed: in 5, or spawned confirmed), n_live (slots not free after the step).  Then t += 1.
+ *      An empty frame still runs 4 and 5.
+ *
+ * gs_cand_params_default fills the struct: confirm_hits 3, max_misses 3, view_cos 0.5 (the cosine of half the field of view, so that no host
+ *      cos enters a decision; -1 is all-round); spawn_range 67 m = the reference's coneMappingThreshold default (src/slam.hpp:116; the Slam
+ *      mirror's cone_mapping_threshold is compared with the same distance column); view_range 12 m = the forward bound of the lidar cone
+ *      detector's region of interest in the reference's usecase (usecase/docker-compose.yml, yBoundary=12).
+ *      Refused (GS_ERR_INVALID) before the device is touched, by every call below that takes the blocks: a wrong struct_size of either block
+ *      and whatever the association refuses of gs_nn_params; confirm_hits < 1; max_misses < 1; spawn_range or view_range not finite or <= 0;
+ *      view_cos outside [-1, 1] (a NaN included).  A host-only handle: GS_ERR_NO_DEVICE.
+ * gs_cand_batch: host arrays; n_steps frames through frame_start (as gs_assign_nn_batch checks it), a pose and (pose_cov != NULL) a 3x3
+ *      covariance per STEP, in_idx[n] (may be NULL), the initial table (n_in records, 0 .. GS_CAND_MAX; a record whose state is outside
+ *      0 .. 2: GS_ERR_INVALID).  Outputs, each may be NULL: out_steps[n_steps], out_cand_id[n], out_cand_slot[n], out_table[GS_CAND_MAX]
+ *      (slot s at [s]), out_n_live.  One upload, all steps enqueued back to back, one wait.
+ * gs_cand_resident: everything in DEVICE memory, asynchronous on the handle's stream, no wait.  dev_obs must be 32-byte aligned.
+ *      frame_cap (0 .. GS_NN_FRAME_MAX) sizes launches, never a result.  The kernels defend themselves: a step whose bounds are not
+ *      0 <= a <= b <= n, or whose frame is above frame_cap, is no step: nothing of it is read, the table and t stay, no output of it is
+ *      written.  Observations that no frame covers are not written.  dev_out_meta_4: {next_id, t, n_live, 0}.  A loaded record whose
+ *      state is neither 1 nor 2 becomes a free slot (the host cannot see it to refuse it).
+ *      A batch or resident run works in a table of its own and does not disturb the live one.
+ * gs_cand_clear / gs_cand_set / gs_frame_frontend_candidates / gs_cand_get / gs_cand_take_confirmed: the live table, empty until set.
+ *      gs_frame_frontend_candidates is one step on it, one wait.  gs_cand_get reads all GS_CAND_MAX records (slot s at [s]) and next_id,
+ *      t, n_live (each may be NULL).  gs_cand_take_confirmed returns the confirmed records in ascending id and frees their slots (more
+ *      than cap of them: GS_ERR_INVALID, nothing changes); it touches neither map nor graph: the caller runs gs_map_append,
+ *      gs_map_set_cov and gs_add_landmark.  Batch, resident and a sequence of live calls return identical bits.
+ * Per step: two dispatches of its own (gs_cand.hip: the masked frame laid out for the association; the update, one workgroup) around the
+ *      association's one or two.  Everything (two tables, the stage) is one allocation made at the first call; a handle that never calls
+ *      any of these allocates and launches nothing for them; the calls above are unchanged by them.
+ * NOT DONE: one wait for localisation plus candidates (the caller chains gs_frame_frontend_follow or gs_frame_frontend_localize and this
+ *      call); correlation of the pose error across frames (P is added afresh at every fusion, so the fused covariance is optimistic when
+ *      Sigma_p is given — the counterpart of the association ignoring cross-covariances); merging two candidates spawned for one cone;
+ *      observation edges for a candidate's earlier sightings (out_cand_id lets the caller keep that log); the Slam mirror and the shell;
+ *      sharded handles; frames above GS_NN_FRAME_MAX and more than GS_CAND_MAX candidates. */
+#define GS_CAND_MAX 1024
+typedef struct gs_cand_params {
+    int32_t struct_size;
+    int32_t confirm_hits;    /* 3; >= 1 */
+    int32_t max_misses;      /* 3; >= 1 */
+    int32_t reserved;
+    double spawn_range;      /* 67 m; finite, > 0 */
+    double view_range;       /* 12 m; finite, > 0 */
+    double view_cos;         /* 0.5; in [-1, 1] */
+} gs_cand_params;
+typedef struct gs_cand {
+    double xy[2];
+    double cov[4];
+    int32_t type;
+    int32_t id;              /* -1 in a free slot */
+    int32_t state;           /* 0 free, 1 tentative, 2 confirmed */
+    int32_t hits, misses;
+    int32_t first_step, last_step;
+    int32_t confirm_step;    /* -1 until confirmed */
+} gs_cand;
+typedef struct gs_cand_step {
+    int32_t step;
+    int32_t n_unexplained, n_fused, n_spawned, n_contested, n_far, n_dropped, n_missed, n_retired, n_confirmed, n_live;
+    int32_t reserved;
+} gs_cand_step;
+int  gs_cand_params_default(gs_cand_params *p);
+int  gs_cand_batch(gs_graph *g, int32_t n_steps, int32_t n, const double *obs_4xn, const int32_t *frame_start, const double *poses_xytheta,
+                   const double *pose_covs_3x3, const int32_t *in_idx, int32_t n_in, const gs_cand *in_table, const gs_nn_params *params,
+                   const gs_cand_params *cand, gs_cand_step *out_steps, int32_t *out_cand_id, int32_t *out_cand_slot, gs_cand *out_table,
+                   int32_t *out_n_live);
+int  gs_cand_resident(gs_graph *g, int32_t n_steps, int32_t n, const double *dev_obs_4xn, const int32_t *dev_frame_start, int32_t frame_cap,
+                      const double *dev_poses_xytheta, const double *dev_pose_covs_3x3, const int32_t *dev_in_idx, int32_t n_in,
+                      const gs_cand *dev_in_table, const gs_nn_params *params, const gs_cand_params *cand, gs_cand_step *dev_out_steps,
+                      int32_t *dev_out_cand_id, int32_t *dev_out_cand_slot, gs_cand *dev_out_table, int32_t *dev_out_meta_4);
+int  gs_cand_clear(gs_graph *g);
+int  gs_cand_set(gs_graph *g, int32_t n_in, const gs_cand *records);
+int  gs_cand_get(gs_graph *g, gs_cand *out_table, int32_t *out_next_id, int32_t *out_step, int32_t *out_n_live);
+int  gs_cand_take_confirmed(gs_graph *g, int32_t cap, gs_cand *out_records, int32_t *out_n);
+int  gs_frame_frontend_candidates(gs_graph *g, const double pose_xytheta[3], const double *pose_cov_3x3, const double *obs_4xk, int32_t k,
+                                  const int32_t *in_idx, const gs_nn_params *params, const gs_cand_params *cand, gs_cand_step *out_step,
+                                  int32_t *out_cand_id, int32_t *out_cand_slot);
+
 /* ---- multi-GPU: pose-window shards -----------------------------
  * Each rank owns a contiguous pose window and builds the SAME global plan; it linearises and
  * factorises only its own subtrees, exports the update contributions to the shared top of the

@@ -139,6 +139,13 @@ int gs_debug_time_follow_resident(gs_graph *g, int32_t n_hyp, const double *dev_
                                   const double *dev_motion_cov_3x3, const gs_nn_params *params, const gs_jc_params *jc, const gs_loc_params *loc,
                                   const gs_follow_params *follow, gs_follow_step *dev_out_steps, int32_t *dev_out_index, gs_follow_state *dev_out_state,
                                   int32_t *dev_out_best_2, int32_t reps, double *out_ms);
+/* Cone candidates.  gs_debug_time_cand_resident: `reps` calls of gs_cand_resident, events from the run's first dispatch (the kernel that sets
+ * the table up) to its last (the last step's update); mean milliseconds per run. */
+int gs_debug_time_cand_resident(gs_graph *g, int32_t n_steps, int32_t n, const double *dev_obs_4xn, const int32_t *dev_frame_start, int32_t frame_cap,
+                                const double *dev_poses_xytheta, const double *dev_pose_covs_3x3, const int32_t *dev_in_idx, int32_t n_in,
+                                const gs_cand *dev_in_table, const gs_nn_params *params, const gs_cand_params *cand, gs_cand_step *dev_out_steps,
+                                int32_t *dev_out_cand_id, int32_t *dev_out_cand_slot, gs_cand *dev_out_table, int32_t *dev_out_meta_4,
+                                int32_t reps, double *out_ms);
 /* Measurement hook of the sharded iteration (bench.py's `ms_exchange`): `reps` RCCL all-reduces of the exchange buffer back to back on the
  * handle's stream, HIP events around them; mean ms per all-reduce.  Collective: every rank of the communicator calls it. */
 int gs_debug_time_exchange(gs_graph *g, int32_t reps, double *out_ms);

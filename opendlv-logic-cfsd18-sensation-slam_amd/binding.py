@@ -241,6 +241,35 @@ FOLLOW_STEP = np.dtype([("prior_pose", "<f8", 3), ("prior_cov", "<f8", 9), ("pos
                         ("iterations", "<i4"), ("status", "<i4"), ("n_kept", "<i4"), ("accepted", "<i4"), ("state", "<i4")])
 
 
+CAND_MAX = 1024                                             # GS_CAND_MAX
+
+
+class CandParams(C.Structure):
+    """gs_cand_params (include/graphslam.h): when a candidate is confirmed, when it is retired, where one may spawn and what counts as visible"""
+    _fields_ = [("struct_size", C.c_int32), ("confirm_hits", C.c_int32), ("max_misses", C.c_int32), ("reserved", C.c_int32), ("spawn_range", C.c_double),
+                ("view_range", C.c_double), ("view_cos", C.c_double)]
+
+
+def cand_params(**kw):
+    """the library's gs_cand_params defaults, with the named fields changed"""
+    p = CandParams(); L = lib()
+    rc = L.gs_cand_params_default(C.byref(p))
+    if rc != GS_OK:
+        raise GsError(rc, (L.gs_last_error() or b"").decode())
+    for k, v in kw.items():
+        if k not in ("confirm_hits", "max_misses", "spawn_range", "view_range", "view_cos"):
+            raise AttributeError("gs_cand_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+# gs_cand and gs_cand_step as numpy records (80 and 48 bytes, no padding)
+CAND = np.dtype([("xy", "<f8", 2), ("cov", "<f8", 4), ("type", "<i4"), ("id", "<i4"), ("state", "<i4"), ("hits", "<i4"), ("misses", "<i4"),
+                 ("first_step", "<i4"), ("last_step", "<i4"), ("confirm_step", "<i4")])
+CAND_STEP = np.dtype([("step", "<i4"), ("n_unexplained", "<i4"), ("n_fused", "<i4"), ("n_spawned", "<i4"), ("n_contested", "<i4"), ("n_far", "<i4"),
+                      ("n_dropped", "<i4"), ("n_missed", "<i4"), ("n_retired", "<i4"), ("n_confirmed", "<i4"), ("n_live", "<i4"), ("reserved", "<i4")])
+
+
 class DoglegParams(C.Structure):
     """gs_dogleg_params (include/graphslam.h)"""
     _fields_ = [("struct_size", C.c_int32), ("max_trials_after_failure", C.c_int32), ("initial_delta", C.c_double)]
@@ -452,6 +481,17 @@ def lib():
         L.gs_follow_set.argtypes = [vp, C.c_int32, _dp, _dp]
         L.gs_follow_get.argtypes = [vp, vp, _ip, _ip, _ip]
         L.gs_frame_frontend_follow.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, jpp, lpp, fpp, vp, _ip, _ip, _ip]
+    if hasattr(L, "gs_cand_batch"):                        # (and for the cone candidates)
+        npp = C.POINTER(NnParams); cpp = C.POINTER(CandParams)
+        L.gs_cand_params_default.argtypes = [cpp]
+        L.gs_cand_batch.argtypes = [vp, C.c_int32, C.c_int32, _dp, _ip, _dp, _dp, _ip, C.c_int32, vp, npp, cpp, vp, _ip, _ip, vp, _ip]
+        L.gs_cand_resident.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, npp, cpp, vp, vp, vp, vp, vp]
+        L.gs_debug_time_cand_resident.argtypes = L.gs_cand_resident.argtypes + [C.c_int32, _dp]
+        L.gs_cand_clear.argtypes = [vp]
+        L.gs_cand_set.argtypes = [vp, C.c_int32, vp]
+        L.gs_cand_get.argtypes = [vp, vp, _ip, _ip, _ip]
+        L.gs_cand_take_confirmed.argtypes = [vp, C.c_int32, vp, _ip]
+        L.gs_frame_frontend_candidates.argtypes = [vp, _dp, _dp, _dp, C.c_int32, _ip, npp, cpp, vp, _ip, _ip]
     if hasattr(L, "gs_set_robust_kernel"):                # (a tuning build of an older tree loaded through GS_LIB may predate the robust kernels)
         L.gs_set_robust_kernel.argtypes = [vp, C.c_int32, C.c_int32, C.c_double]
         L.gs_get_robust_kernel.argtypes = [vp, C.c_int32, _ip, _dp]
@@ -1400,6 +1440,91 @@ class Graph:
         self._check(self.L.gs_frame_frontend_follow(self.h, None if mo is None else _d(mo), None if mq is None else _d(mq), _d(obs), k, C.byref(p), C.byref(j),
                                                     C.byref(l), C.byref(f), steps.ctypes.data_as(C.c_void_p), _i(idx), C.byref(best), C.byref(nt)))
         return steps[:nh].copy(), idx[:nh * k].reshape(nh, k).copy(), best.value, nt.value
+
+    # ---- cone candidates (include/graphslam.h): unmatched observations tracked into new map cones on the device.
+    # Records are numpy arrays of CAND [CAND_MAX] (slot s at [s]) and CAND_STEP [n_steps]
+    @staticmethod
+    def _cand_blocks(params, cand):
+        return nn_params() if params is None else params, cand_params() if cand is None else cand
+
+    @staticmethod
+    def _cand_records(table):
+        """a table to load: CAND records, slot s at [s] (None: none)"""
+        t = np.zeros(0, dtype=CAND) if table is None else np.ascontiguousarray(table, dtype=CAND).reshape(-1)
+        return t, (t.ctypes.data_as(C.c_void_p) if len(t) else None)
+
+    def cand(self, poses, obs, frame_start, in_idx=None, pose_covs=None, table=None, params=None, cand=None):
+        """gs_cand_batch: {"steps", "cand_id", "cand_slot", "table", "n_live"} of a run over all frames from the table given (None: empty)"""
+        poses = _f64(poses, (-1, 3)); obs = _f64(obs, (-1, 4)); fs = _i32(frame_start); n = len(obs); ns = len(fs) - 1
+        pc = None if pose_covs is None else _f64(pose_covs, (-1, 9)); ii = None if in_idx is None else _i32(in_idx)
+        assert len(fs) >= 1 and len(poses) >= ns and (pc is None or len(pc) >= ns) and (ii is None or len(ii) == n)
+        p, c = self._cand_blocks(params, cand); tab, tp = self._cand_records(table)
+        steps = np.zeros(max(ns, 0), dtype=CAND_STEP); cid = np.zeros(n, dtype=np.int32); slot = np.zeros(n, dtype=np.int32)
+        out = np.zeros(CAND_MAX, dtype=CAND); nl = C.c_int32(-2)
+        self._check(self.L.gs_cand_batch(self.h, ns, n, _d(obs), _i(fs), _d(poses), None if pc is None else _d(pc), None if ii is None else _i(ii), len(tab), tp,
+                                         C.byref(p), C.byref(c), steps.ctypes.data_as(C.c_void_p), _i(cid), _i(slot), out.ctypes.data_as(C.c_void_p), C.byref(nl)))
+        return {"steps": steps, "cand_id": cid, "cand_slot": slot, "table": out, "n_live": nl.value}
+
+    def _cand_resident_args(self, d_obs, n, n_steps, d_frame_start, frame_cap, d_poses, d_pose_covs, d_in_idx, n_in, d_table, d_steps, d_cand_id, d_cand_slot,
+                            d_out_table, d_meta, params, cand):
+        p, c = self._cand_blocks(params, cand)
+        opt = lambda a: None if a is None else a.ptr
+        return [self.h, int(n_steps), int(n), opt(d_obs), opt(d_frame_start), int(frame_cap), opt(d_poses), opt(d_pose_covs), opt(d_in_idx), int(n_in), opt(d_table),
+                C.byref(p), C.byref(c), opt(d_steps), opt(d_cand_id), opt(d_cand_slot), opt(d_out_table), opt(d_meta)]
+
+    def cand_resident(self, d_obs, n, n_steps, d_frame_start, frame_cap, d_poses, d_pose_covs=None, d_in_idx=None, n_in=0, d_table=None, d_steps=None,
+                      d_cand_id=None, d_cand_slot=None, d_out_table=None, d_meta=None, params=None, cand=None):
+        """gs_cand_resident: everything DeviceArray; asynchronous (synchronize() before reading)"""
+        self._check(self.L.gs_cand_resident(*self._cand_resident_args(d_obs, n, n_steps, d_frame_start, frame_cap, d_poses, d_pose_covs, d_in_idx, n_in, d_table,
+                                                                      d_steps, d_cand_id, d_cand_slot, d_out_table, d_meta, params, cand)))
+
+    def time_cand_resident(self, d_obs, n, n_steps, d_frame_start, frame_cap, d_poses, reps, d_pose_covs=None, d_in_idx=None, n_in=0, d_table=None, d_steps=None,
+                           d_cand_id=None, d_cand_slot=None, d_out_table=None, d_meta=None, params=None, cand=None):
+        """gs_debug_time_cand_resident: mean milliseconds per run, events from the run's first dispatch to its last"""
+        ms = C.c_double()
+        a = self._cand_resident_args(d_obs, n, n_steps, d_frame_start, frame_cap, d_poses, d_pose_covs, d_in_idx, n_in, d_table, d_steps, d_cand_id, d_cand_slot,
+                                     d_out_table, d_meta, params, cand)
+        self._check(self.L.gs_debug_time_cand_resident(*(a + [int(reps), C.byref(ms)])))
+        return ms.value
+
+    def cand_clear(self):
+        self._check(self.L.gs_cand_clear(self.h))
+
+    def cand_set(self, table):
+        """gs_cand_set: load CAND records into the live table, slot s from [s]"""
+        tab, tp = self._cand_records(table)
+        self._check(self.L.gs_cand_set(self.h, len(tab), tp))
+
+    def cand_get(self):
+        """gs_cand_get: (table [CAND_MAX], next_id, step, n_live) of the live table"""
+        out = np.zeros(CAND_MAX, dtype=CAND); ni = C.c_int32(-2); t = C.c_int32(-2); nl = C.c_int32(-2)
+        self._check(self.L.gs_cand_get(self.h, out.ctypes.data_as(C.c_void_p), C.byref(ni), C.byref(t), C.byref(nl)))
+        return out, ni.value, t.value, nl.value
+
+    def cand_take_confirmed(self):
+        """gs_cand_take_confirmed: the confirmed records in ascending id; their slots are free afterwards"""
+        out = np.zeros(CAND_MAX, dtype=CAND); n = C.c_int32(0)
+        self._check(self.L.gs_cand_take_confirmed(self.h, CAND_MAX, out.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return out[:n.value].copy()
+
+    def cand_promote(self):
+        """the confirmed candidates taken out of the table and appended to the resident map with their covariances (gs_map_append,
+        gs_map_set_cov); returns (records, the map index of the first) — adding the landmarks to the graph stays with the caller"""
+        rec = self.cand_take_confirmed(); first = self.map_size()
+        if len(rec):
+            self.map_append(rec["xy"], rec["type"]); self.map_set_cov(first, rec["cov"])
+        return rec, first
+
+    def frame_frontend_candidates(self, pose, obs, in_idx=None, pose_cov=None, params=None, cand=None):
+        """gs_frame_frontend_candidates: one step on the live table: (step record, cand_id [k], cand_slot [k])"""
+        pose = _f64(pose, (3,)); obs = _f64(obs, (-1, 4)); k = len(obs)
+        pc = None if pose_cov is None else _f64(pose_cov, (9,)); ii = None if in_idx is None else _i32(in_idx)
+        assert ii is None or len(ii) == k
+        p, c = self._cand_blocks(params, cand)
+        step = np.zeros(1, dtype=CAND_STEP); cid = np.zeros(max(k, 1), dtype=np.int32); slot = np.zeros(max(k, 1), dtype=np.int32)
+        self._check(self.L.gs_frame_frontend_candidates(self.h, _d(pose), None if pc is None else _d(pc), _d(obs), k, None if ii is None else _i(ii), C.byref(p),
+                                                        C.byref(c), step.ctypes.data_as(C.c_void_p), _i(cid), _i(slot)))
+        return step[0].copy(), cid[:k].copy(), slot[:k].copy()
 
     # ---- pose-window shards (one handle per rank / GPU)
     def dist_configure(self, rank, world):

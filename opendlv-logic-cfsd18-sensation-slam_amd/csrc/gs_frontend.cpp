@@ -152,6 +152,7 @@ void gs_frontend_release(gs_graph *g) {      // gs_destroy
     if (g->fe.fo_mem) hipFree(g->fe.fo_mem);
     if (g->fe.fo_state) hipFree(g->fe.fo_state);
     if (g->fe.fo_best) hipFree(g->fe.fo_best);
+    gs_cand_release(g);
     g->fe = gs_graph::FrontEnd();
 }
 
@@ -360,7 +361,7 @@ extern "C" int gs_nn_params_default(gs_nn_params *p) {
     return GS_OK;
 }
 // everything a caller can get wrong about the parameters, decided before the device is touched
-static int nn_params_check(const gs_nn_params *p, NnDev &d) {
+int nn_params_check(const gs_nn_params *p, NnDev &d) {
     if (!p) return fail(GS_ERR_INVALID, "null params");
     if (p->struct_size != (int32_t)sizeof(gs_nn_params)) return fail(GS_ERR_INVALID, "gs_nn_params: wrong struct_size");
     const double v[6] = {p->gate_chi2, p->max_distance, p->type_tol, p->sigma_range, p->sigma_bearing, p->sigma_xy};
@@ -507,7 +508,7 @@ extern "C" int gs_frame_frontend_nn(gs_graph *g, const double pose[3], const dou
 }
 
 // ---- one-to-one association inside a frame (gs_assoc_nn.hip, k_assign_nn): the batch / resident / frame calls -----------------------
-static int frame_start_check(int32_t n, int32_t n_frames, const int32_t *fs) {
+int frame_start_check(int32_t n, int32_t n_frames, const int32_t *fs) {
     if (n_frames < 0 || !fs) return fail(GS_ERR_INVALID, "bad argument");
     if (fs[0] != 0 || fs[n_frames] != n) return fail(GS_ERR_INVALID, "frame_start must begin at 0 and end at n");
     for (int f = 0; f < n_frames; ++f) {
@@ -1233,6 +1234,14 @@ extern "C" int gs_debug_time_follow_resident(gs_graph *g, int32_t n_hyp, const d
     return time_resident(g, reps, out_ms, [&] {
         return gs_follow_resident(g, n_hyp, dev_poses, dev_covs, n_steps, n, dev_obs, dev_frame_start, frame_cap, dev_motion, dev_motion_cov, params, jc, loc, follow,
                                   dev_out_steps, dev_out_index, dev_out_state, dev_out_best_2); });
+}
+extern "C" int gs_debug_time_cand_resident(gs_graph *g, int32_t n_steps, int32_t n, const double *dev_obs, const int32_t *dev_frame_start, int32_t frame_cap,
+                                           const double *dev_poses, const double *dev_pose_covs, const int32_t *dev_in_idx, int32_t n_in, const gs_cand *dev_in_table,
+                                           const gs_nn_params *params, const gs_cand_params *cand, gs_cand_step *dev_out_steps, int32_t *dev_out_cand_id,
+                                           int32_t *dev_out_cand_slot, gs_cand *dev_out_table, int32_t *dev_out_meta_4, int32_t reps, double *out_ms) {
+    return time_resident(g, reps, out_ms, [&] {
+        return gs_cand_resident(g, n_steps, n, dev_obs, dev_frame_start, frame_cap, dev_poses, dev_pose_covs, dev_in_idx, n_in, dev_in_table, params, cand,
+                                dev_out_steps, dev_out_cand_id, dev_out_cand_slot, dev_out_table, dev_out_meta_4); });
 }
 // the live run: the hypotheses stay on the handle between frames
 extern "C" int gs_follow_set(gs_graph *g, int32_t n_hyp, const double *poses, const double *covs) {

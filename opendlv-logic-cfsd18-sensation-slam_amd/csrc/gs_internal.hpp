@@ -91,6 +91,11 @@ struct gs_graph {
         char *fo_mem = nullptr; size_t fo_bytes = 0;
         char *fo_state = nullptr; int32_t *fo_best = nullptr;
         int fo_n_hyp = 0, fo_t = 0;
+        // cone candidates (empty until one of their calls is made): the two tables and the per-step stage in one allocation of a fixed size
+        // (gs_cand_host.hpp's CandLayout; live: the live table has been initialised), a batch call's uploads and outputs (CandBatch,
+        // grow-only), the frame call's staging (CandFrameIo)
+        gs::DevArena cd_mem, cd_batch; bool cd_live = false;
+        gs::FrameStage cd_io;
     } fe;
     bool tree_proven = false;               // a whole-tree launch sequence of the CURRENT plan has completed without a flag timeout (gs_optimize then sends all iterations of a call at once)
     bool fell_back = false;                 // a whole-tree launch gave up on a flag: this handle uses one launch per level — until the next plan, or until a retry (below) comes back clean
