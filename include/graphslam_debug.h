@@ -25,7 +25,9 @@ extern "C" {
  *     block_fronts    GS_BLOCK_FRONTS  plan  levels of at most this many fronts run a WORKGROUP per front (default 512)
  *     leaf_kernel     GS_LEAF_KERNEL   plan  0 never a separate leaf launch, 2 always, -1 by leaf_min
  *     leaf_min        GS_LEAF_MIN      plan  separate leaf launches only above this many leaves (default 2048)
- *     bs_wide         GS_BS_WIDE       plan  backward solve: levels wider than this get a light launch of their own (default 2048)
+ *     bs_wide         GS_BS_WIDE       plan  backward solve: levels wider than this leave the flagged launch for the light one(s) (default 1024)
+ *     bs_low          GS_BS_LOW        plan  backward solve: 1 (default) the wide levels below the flagged launch share ONE light launch whose fronts
+ *                                      poll their boundary rows; 0 one light launch per level (the launches before that one existed)
  *     leaf_nt3        GS_LEAF_NT3      plan  1 three-tile-row leaf instance when every leaf has <= 47 scalars (default), 0 off
  *     f3_lds_kb       GS_F3_LDS_KB     plan  occupancy experiments: LDS per workgroup of the per-level factor launches, KB (0 = need)
  *     subtree         GS_SUBTREE       plan  1: a level-1 front and the leaves below it run in ONE workgroup (k_factor3_sub: the leaves'
@@ -63,7 +65,7 @@ extern "C" {
  * Two process-wide variables remain outside the struct: GS_THREADS (host threads of the plan build) and, Python binding only, GS_LIB. */
 typedef struct gs_debug_options {
     int32_t struct_size;
-    int32_t tree, block_fronts, leaf_kernel, leaf_min, bs_wide, leaf_nt3, f3_lds_kb, reserved0;
+    int32_t tree, block_fronts, leaf_kernel, leaf_min, bs_wide, leaf_nt3, f3_lds_kb, bs_low;
     int32_t leaf_poses, cluster_ways, ell_lanes, big_cluster, grow_headroom, factor_variant;
     int32_t grow, grow_min_poses;
     int32_t assoc_grid;
@@ -171,7 +173,8 @@ int gs_debug_select_factor_variant(int32_t requested, int32_t max_front, int64_t
  *            the header says), 2 the leaf instance alone, 3 one factor launch over positions of one level (class = mode: 0 own, 1
  *            contributions, 2 shared top), 4 the shared top's flagged launch, 5 table-driven factor launch: entries [first, first + count)
  *            of `table` (0 .. 4 in the order above), 6 flagged backward-solve launch, 7 backward-solve launch of one level, 8 table-driven
- *            backward-solve launch.  A launch over no fronts (an empty level of a list) is none: left out. */
+ *            backward-solve launch.  A launch over no fronts (an empty level of a list) is none: left out.  The light polling launch
+ *            over the wide levels (bs_low) is recorded with kind 6 as well — its fronts order themselves — with its LDS bytes. */
 int gs_debug_schedule_export(gs_graph *g, int32_t *out, int64_t *out_len);
 
 #ifdef __cplusplus

@@ -113,6 +113,7 @@ void launch_factor_tree(const DevGraph &d, int n_leaf, int leaf_slot, int leaf_m
 size_t factor_sub_lds_bytes(int leaf_slot);                                  // LDS of one workgroup of k_factor3_sub
 void launch_factor_tree_top(const DevGraph &d, int first, int count, hipStream_t st);           // shared top of a sharded graph (mode TOP)
 void launch_backsolve_tree(const DevGraph &d, int first, int count, int max_npiv, int max_f, hipStream_t st);
+void launch_backsolve_low(const DevGraph &d, int first, int count, int n_up, int up_fronts, int up_slot, int slot, size_t lds_bytes, hipStream_t st);
 void launch_backsolve_level(const DevGraph &d, int level_off, int count, int max_npiv, int max_nbnd, hipStream_t st);
 void launch_update(const DevGraph &d, hipStream_t st);
 void launch_pose_trig(const DevGraph &d, hipStream_t st);       // pose_cs from pose_est (after every host -> device estimate copy)

@@ -2138,9 +2138,29 @@ __global__ void __launch_bounds__(256, LEAF ? (NT == 3 ? 5 : F3_LEAF4_WPS) : 2) 
     f3_wave_front<TREE, LEAF, NT, false, CAP>(d, level_off + fi, mode, leaf_slot, smem, wave, lane, ts_on, fi == 0);
 }
 
+// the boundary rows of a front belong to its ancestors: poll the values themselves until none holds the "not written yet" pattern
+// (lanes without a row: 0, their terms vanish).  Bounded: on expiry report through d.fail, carry on with 0, and the grid drains
+__device__ __forceinline__ double bs3_poll_boundary(const DevGraph &d, int row, int lane) {
+    double xb = 0.0;
+    bool got = false, failed_already = false;
+    for (int it = 0; it < (1 << 18); ++it) {
+        if (row >= 0) xb = ld_off_coh(d.xe, (uint32_t)row * 8u);
+        if (!__any(row >= 0 && f3_is_unset(xb))) { got = true; break; }
+        if ((it & 63) == 63 && __hip_atomic_load(d.fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) { failed_already = true; break; }   // some front reported: leave at once
+        __builtin_amdgcn_s_sleep(F3_POLL_SLEEP);
+    }
+    if (!got) { if (lane == 0 && !failed_already) atomicMax(d.fail, 2); if (f3_is_unset(xb)) xb = 0.0; }     // bounded: report, carry on, drain
+    return xb;
+}
 // backward solve of variant 3's LDL^T panels (unit diagonal): x_piv = L11^-T (y - L21^T x_bnd), one wave per front
-template <bool TREE>      // TREE: the front polls its boundary rows of the solution until its ancestors have written them
+// MODE  BS_PLAIN: every ancestor ran in an earlier launch.  BS_TREE: the front polls its boundary rows of the solution until its
+// ancestors have written them, everything else preloaded into registers (the chain of the upper levels; 2 waves per SIMD).
+// BS_LOW: the PLAIN path — panel in LDS, mat-vec and substitution out of LDS, the same arithmetic in the same order — that polls
+// like TREE and, above level 0, stores write-through for the children of its own launch: the wide levels in one light launch.
+enum { BS_PLAIN = 0, BS_TREE = 1, BS_LOW = 2 };
+template <int MODE>
 __device__ __forceinline__ void bs3_wave_front(const DevGraph &d, int pos, double *smem, int slot_doubles, int wave, int lane, bool ts_on) {
+    constexpr bool TREE = MODE == BS_TREE;
     F3_TS(32);
     const F3 fr = f3_load(d.f3_desc, pos, lane);
     const int npiv = fr.npiv, nbnd = fr.nbnd, f = npiv + nbnd, ldl = f + 1, lds = (f + 1) | 1;
@@ -2174,17 +2194,7 @@ __device__ __forceinline__ void bs3_wave_front(const DevGraph &d, int pos, doubl
         for (int cc = 1; cc < 32; ++cc) { lcol[cc] = S[min(min(lane, cc - 1), npiv - 1) * lds + min(cc, f)];
             lcol[cc] = lane < cc ? lcol[cc] : 0.0; }                  // the mask of the substitution step goes into the coefficient HERE, before the wait
         w = S[me * lds + f];
-        double xb = 0.0;                                             // 0 beyond the boundary: those terms vanish
-        if (nbnd > 0) {                                              // the boundary rows belong to the ancestors: poll the values themselves
-            bool got = false, failed_already = false;
-            for (int it = 0; it < (1 << 18); ++it) {
-                if (row >= 0) xb = ld_off_coh(d.xe, (uint32_t)row * 8u);
-                if (!__any(row >= 0 && f3_is_unset(xb))) { got = true; break; }
-                if ((it & 63) == 63 && __hip_atomic_load(d.fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) { failed_already = true; break; }   // some front reported: leave at once
-                __builtin_amdgcn_s_sleep(F3_POLL_SLEEP);
-            }
-            if (!got) { if (lane == 0 && !failed_already) atomicMax(d.fail, 2); if (f3_is_unset(xb)) xb = 0.0; }     // bounded: report, carry on, drain
-        }
+        const double xb = nbnd > 0 ? bs3_poll_boundary(d, row, lane) : 0.0;     // 0 beyond the boundary: those terms vanish
         F3_TS(35);
 #pragma unroll
         for (int r0 = 0; r0 < 64; r0 += 8) if (r0 < nbnd) {          // uniform; groups of 8: at most 7 terms beyond the boundary (their x is 0)
@@ -2198,7 +2208,8 @@ __device__ __forceinline__ void bs3_wave_front(const DevGraph &d, int pos, doubl
         for (int cc = 31; cc >= 1; --cc) if (cc < npiv) {            // uniform
             const double xcc = lane_bcast(w, cc); w -= lcol[cc] * xcc; }   // lanes >= cc: coefficient 0 (a select per step was half of the step's dependent chain)
     } else {
-        const double xb = (row >= 0) ? d.xe[row] : 0.0;
+        double xb;                                                   // LOW: rows whose owners ran in an earlier launch are never unset
+        if (MODE == BS_LOW) xb = nbnd > 0 ? bs3_poll_boundary(d, row, lane) : 0.0; else xb = (row >= 0) ? d.xe[row] : 0.0;
         wave_lds_sync();
         F3_TS(35);
         w = S[me * lds + f];
@@ -2220,22 +2231,33 @@ __device__ __forceinline__ void bs3_wave_front(const DevGraph &d, int pos, doubl
         }
     }
     F3_TS(37);
-    if (lane < npiv) { if (TREE) st_off_wt(d.xe, (uint32_t)(fr.piv0 + lane) * 8u, w); else d.xe[fr.piv0 + lane] = w; }
+    if (lane < npiv) { if (TREE || (MODE == BS_LOW && fr.level > 0)) st_off_wt(d.xe, (uint32_t)(fr.piv0 + lane) * 8u, w); else d.xe[fr.piv0 + lane] = w; }      // polled inside this launch: write through (a leaf has no children)
 #if F3_DONE_TS
     if (lane == 0) d.done_ts[d.n_fronts + fr.s] = wall_clock64();
 #endif
     F3_TS(38);
 }
-template <bool TREE>      // TREE: one launch, root first (wave w takes level position count - 1 - w), a front waits for its parent's flag
-__global__ void __launch_bounds__(256) k_backsolve3(DevGraph d, int level_off, int count, int slot_doubles) {
+// BS_TREE: one launch, root first (wave w takes level position count - 1 - w), a front polls its ancestors' rows.
+// BS_LOW: the same order over the wide levels at the bottom.  The launch's LDS is the leaves' (four slots of slot_doubles), so that the
+// leaf level keeps its resident waves; the first n_up fronts from the top — the levels above the leaves, whose panels may need a bigger
+// slot (up_slot) — run up_fronts to a workgroup instead of four (n_wave_fronts splits the factor launch the same way).  A front's
+// parent sits in an earlier workgroup either way: the forward-progress argument of the flagged launches.  (The leaves in ascending
+// position order — the order their panels were written in — measured the same: profiles/backsolve_low_ab.txt.)
+template <int MODE>
+__global__ void __launch_bounds__(256) k_backsolve3(DevGraph d, int level_off, int count, int slot_doubles, int n_up, int up_fronts, int up_slot) {
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int bid = TREE ? wg_ticket(d, smem) : (int)blockIdx.x;     // (TREE: a front polls its ancestors' values — they must belong to workgroups that have started)
-    const int fi = bid * 4 + wave;
+    const int bid = MODE != BS_PLAIN ? wg_ticket(d, smem) : (int)blockIdx.x;     // (a front polls its ancestors' values — they must belong to workgroups that have started)
+    int fi = bid * 4 + wave, slot = slot_doubles;
+    if constexpr (MODE == BS_LOW) {
+        const int up_wgs = (n_up + up_fronts - 1) / up_fronts;
+        if (bid < up_wgs) { fi = wave < up_fronts ? bid * up_fronts + wave : count; if (fi >= n_up) return; slot = up_slot; }
+        else fi = n_up + (bid - up_wgs) * 4 + wave;
+    }
     if (fi >= count) return;
-    const int pos = TREE ? level_off + (count - 1 - fi) : level_off + fi;
+    const int pos = MODE != BS_PLAIN ? level_off + (count - 1 - fi) : level_off + fi;
     const bool ts_on = ((d.dbg & 8) && count == (d.dbg >> 8) && fi == 0) || ((d.dbg & 16) && pos == (d.dbg >> 8));   // 16: probe the front at a level POSITION
-    bs3_wave_front<TREE>(d, pos, smem, slot_doubles, wave, lane, ts_on);
+    bs3_wave_front<MODE>(d, pos, smem, slot, wave, lane, ts_on);
 }
 
 // ------------------------------------------------------------------ fronts of 64 .. 159 scalars (round 3)
@@ -2553,7 +2575,7 @@ __global__ void __launch_bounds__(256, BIG ? 4 : 2) k_backsolve3_tab(DevGraph d,
     const int2 e = wgt[wg_ticket(d, smem)];
     const int pos = __builtin_amdgcn_readfirstlane(e.x), cnt = __builtin_amdgcn_readfirstlane(e.y) >> 8;
     if constexpr (BIG) bs3_big_front<true>(d, pos, smem);
-    else { if (wave < cnt) bs3_wave_front<true>(d, pos - wave, smem, slot_doubles, wave, lane, false); }     // root first: positions downwards
+    else { if (wave < cnt) bs3_wave_front<BS_TREE>(d, pos - wave, smem, slot_doubles, wave, lane, false); }     // root first: positions downwards
 }
 // the kernel's copy of the handle's device view for a ticketed launch of `grid` workgroups: the counter's value when its first workgroup starts
 static DevGraph ticketed(const DevGraph &d, unsigned grid) { DevGraph dd = d; if (d.tickets) d.ticket_base += grid; return dd; }
@@ -2805,8 +2827,16 @@ void launch_factor_tree_top(const DevGraph &d, int first, int count, hipStream_t
 void launch_backsolve_tree(const DevGraph &d, int first, int count, int max_npiv, int max_f, hipStream_t st) {
     if (count <= 0) return;                                          // positions [first, first + count), root first
     const int slot = ((((max_f + 1) | 1) * max_npiv) + 1) & ~1;
-    allow_max_lds((const void *)k_backsolve3<true>);
-    hipLaunchKernelGGL(k_backsolve3<true>, dim3((count + 3) / 4), dim3(256), (size_t)slot * 4 * sizeof(double), st, ticketed(d, (unsigned)((count + 3) / 4)), first, count, slot);
+    allow_max_lds((const void *)k_backsolve3<BS_TREE>);
+    hipLaunchKernelGGL(k_backsolve3<BS_TREE>, dim3((count + 3) / 4), dim3(256), (size_t)slot * 4 * sizeof(double), st, ticketed(d, (unsigned)((count + 3) / 4)), first, count, slot, 0, 4, 0);
+}
+// the wide levels below the flagged launch in one light launch (geometry: build_schedule): positions [first, first + count) from the top
+// down, the n_up positions above the leaves `up_fronts` to a workgroup on slots of up_slot doubles, the leaves four on slots of `slot`
+void launch_backsolve_low(const DevGraph &d, int first, int count, int n_up, int up_fronts, int up_slot, int slot, size_t lds_bytes, hipStream_t st) {
+    if (count <= 0) return;
+    const unsigned grid = (unsigned)((n_up + up_fronts - 1) / up_fronts + (count - n_up + 3) / 4);
+    allow_max_lds((const void *)k_backsolve3<BS_LOW>);
+    hipLaunchKernelGGL(k_backsolve3<BS_LOW>, dim3(grid), dim3(256), lds_bytes, st, ticketed(d, grid), first, count, slot, n_up, up_fronts, up_slot);
 }
 
 void launch_factor_level(const DevGraph &d, int level_off, int count, int max_f, int mode, hipStream_t st) {
@@ -2900,8 +2930,8 @@ void launch_backsolve_level(const DevGraph &d, int level_off, int count, int max
     if (count <= 0) return;
     if (d.factor_variant == 3) {                                     // LDL^T panels: unit-diagonal backward solve
         const int f = max_npiv + max_nbnd, slot = ((((f + 1) | 1) * max_npiv) + 1) & ~1;
-        allow_max_lds((const void *)k_backsolve3<false>);
-        hipLaunchKernelGGL(k_backsolve3<false>, dim3((count + 3) / 4), dim3(256), (size_t)slot * 4 * sizeof(double), st, d, level_off, count, slot);
+        allow_max_lds((const void *)k_backsolve3<BS_PLAIN>);
+        hipLaunchKernelGGL(k_backsolve3<BS_PLAIN>, dim3((count + 3) / 4), dim3(256), (size_t)slot * 4 * sizeof(double), st, d, level_off, count, slot, 0, 4, 0);
         return;
     }
     if (max_npiv + max_nbnd <= 63) {

@@ -127,7 +127,15 @@ Schedule build_schedule(const Plan &P, const std::vector<int32_t> &pos_of_front,
           int l0 = 0;
           if (S.leaf_n != 0) while (l0 + 1 < nlev && ls.start[l0 + 1] - ls.start[l0] > wide) ++l0;
           if (l0 == 0 && nlev > 1 && S.leaf_n != 0) l0 = 1;
-          S.bs_l0 = l0; }
+          S.bs_l0 = l0;
+          // ... and the one light launch below it: the LDS slot of a wave front is ((f + 1) | 1) * npiv doubles, even (launch_backsolve_level)
+          auto slot_of = [](int f, int npiv) { return ((((f + 1) | 1) * npiv) + 1) & ~1; };
+          S.bs_low = l0 > 0 ? opt.bs_low : 0;
+          if (S.bs_low != 0) { int mn = 0, mf = 0;
+              for (int l = 1; l < l0; ++l) { mn = std::max(mn, ls.max_npiv[l]); mf = std::max(mf, ls.max_f[l]); }
+              S.low_slot = slot_of(ls.max_npiv[0] + ls.max_nbnd[0], ls.max_npiv[0]); S.low_up_slot = slot_of(mf, mn); S.low_n_up = ls.start[l0] - ls.start[1];
+              S.low_up_fronts = S.low_n_up > 0 ? std::min(4, std::max(1, 4 * S.low_slot / std::max(S.low_up_slot, 1))) : 4;
+              S.low_lds = (size_t)std::max(4 * S.low_slot, S.low_n_up > 0 ? S.low_up_fronts * S.low_up_slot : 0) * sizeof(double); } }
     }
     if (S.big) build_big_tables(P, S);
     return S;
@@ -149,6 +157,7 @@ struct Recorder {
     void factor_tree_top(int first, int count) { rec(L_FACTOR_TOP, first, count, 0, 2, -1); }
     void factor_tab(int t, int first, int n_wg, int, size_t lds, int cls, int) { rec(L_FACTOR_TAB, first, n_wg, lds, cls, t); }
     void backsolve_tree(int first, int count, int, int) { rec(L_BACKSOLVE_TREE, first, count, 0, 0, -1); }
+    void backsolve_low(int first, int count, int, int, int, int, size_t lds) { rec(L_BACKSOLVE_TREE, first, count, lds, 0, -1); }     // the flagged kind: its fronts order themselves
     void backsolve_level(int off, int count, int, int) { rec(L_BACKSOLVE_LEVEL, off, count, 0, 0, -1); }
     void backsolve_tab(int t, int first, int n_wg, int, int, size_t lds, int cls) { rec(L_BACKSOLVE_TAB, first, n_wg, lds, cls, t); }
 };

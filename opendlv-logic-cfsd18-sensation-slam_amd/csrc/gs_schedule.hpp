@@ -30,7 +30,10 @@ struct Schedule {
     int leaf_n = 0, leaf_slot = 0, leaf_max_f = 0;  // level-0 fronts handled by the leaf instance of the factor kernel, its LDS slot (doubles per wave), largest leaf front (<= 47: the three-tile-row leaf instance)
     int sub_n = 0, sub_first = 0, sub_free = 0;     // bottom subtrees (k_factor3_sub): level-1 fronts [sub_first, sub_first + sub_n) each take the leaves below them; the leaf launch covers [0, sub_free)
     int block_n = 0;                        // trailing level positions of the whole-tree factor launch that get a workgroup each
-    int bs_l0 = 0;                          // whole-tree backward solve: levels >= bs_l0 in the flagged launch, the wide levels below one light launch each
+    int bs_l0 = 0;                          // whole-tree backward solve: levels >= bs_l0 in the flagged launch, the wide levels below in one light polling launch (bs_low) or one light launch each
+    // the light polling launch over levels bs_l0 - 1 .. 0 (gs_debug_options.bs_low; 0: off): LDS slots of the leaves (low_slot doubles, four
+    // to a workgroup) and of the low_n_up positions above them (low_up_slot, low_up_fronts to a workgroup: what fits the leaves' LDS, at least one)
+    int bs_low = 0, low_n_up = 0, low_up_fronts = 4, low_up_slot = 0, low_slot = 0; size_t low_lds = 0;
     int small_max_npiv = 0, small_max_f = 0;
     WgTable tab[N_TABS];
 };
@@ -89,11 +92,14 @@ template <class Sink> void walk_backsolve_levels(const Schedule &S, bool tree, c
         // parent is done, so it needs no flags, and its LDS slot is sized for the leaves alone (more resident waves)
         // The flagged launch is register-heavy (each lane preloads its L columns: 2 waves per SIMD) — right for the chain
         // of the upper levels (2.2 us per level), wrong for the wide levels at the bottom, which are bound by resident
-        // waves x bytes: levels of more than GS_BS_WIDE (2048) fronts run one light launch each, like the leaves
-        // (measured per-level completion times: scripts/level_times.py).
+        // waves x bytes: levels of more than GS_BS_WIDE (1024) fronts leave it for the light path, like the leaves
+        // (measured per-level completion times: scripts/level_times.py).  Those wide levels share ONE launch (bs_low): its fronts
+        // poll their boundary rows like the flagged launch's, so the levels need no boundary between them and the leaves' panels
+        // stream while the level above still computes; bs_low = 0 keeps a launch per level.
         const int l0 = S.bs_l0;
         int mn = 0, mf = 0; for (int l = l0; l < nlev; ++l) { mn = std::max(mn, ls.max_npiv[l]); mf = std::max(mf, ls.max_f[l]); }
         sink.backsolve_tree(ls.start[l0], ls.start[nlev] - ls.start[l0], mn, mf);
+        if (S.bs_low != 0 && l0 > 0) { sink.backsolve_low(0, ls.start[l0], S.low_n_up, S.low_up_fronts, S.low_up_slot, S.low_slot, S.low_lds); return; }
         for (int l = l0 - 1; l >= 0; --l) sink.backsolve_level(ls.start[l], ls.start[l + 1] - ls.start[l], ls.max_npiv[l], ls.max_nbnd[l]);
         return; }
     if (v3 && tree && base != 0 && nlev > 0 && ls.start[nlev] > 0) {      // shared top: one flagged launch, root first

@@ -28,6 +28,7 @@ struct Launcher {
     void factor_tree_top(int first, int count) { launch_factor_tree_top(g->d, first, count, g->stream); }
     void factor_tab(int t, int first, int n, int leaf_pre, size_t lds, int cls, int mode) { launch_factor_tab(g->d, g->d_wg[t] + first, n, leaf_pre, lds, cls, g->stream, mode); }
     void backsolve_tree(int first, int count, int max_npiv, int max_f) { launch_backsolve_tree(g->d, first, count, max_npiv, max_f, g->stream); }
+    void backsolve_low(int first, int count, int n_up, int up_fronts, int up_slot, int slot, size_t lds) { launch_backsolve_low(g->d, first, count, n_up, up_fronts, up_slot, slot, lds, g->stream); }
     void backsolve_level(int off, int count, int max_npiv, int max_nbnd) { launch_backsolve_level(g->d, off, count, max_npiv, max_nbnd, g->stream); }
     void backsolve_tab(int t, int first, int n, int max_npiv_small, int max_f_small, size_t lds, int cls) { launch_backsolve_tab(g->d, g->d_wg[t] + first, n, max_npiv_small, max_f_small, lds, cls, g->stream); }
 };
