@@ -1297,6 +1297,98 @@ int  gs_frame_frontend_candidates(gs_graph *g, const double pose_xytheta[3], con
                                   const int32_t *in_idx, const gs_nn_params *params, const gs_cand_params *cand, gs_cand_step *out_step,
                                   int32_t *out_cand_id, int32_t *out_cand_slot);
 
+/* ---- map twins: duplicate cones found, fused and merged in the graph -------------------------------------------------------------------
+ * Every call above assumes that one physical cone is one map entry.  The reference's addConesToMap (src/slam.cpp:570-623) makes a new cone
+ * whenever no map cone of the same type lies within m_newConeThreshold (1 m, src/slam.hpp:113), so drift at the end of a lap maps the first
+ * cones a second time beside themselves, and loopClosing only ever looks at cone 0; the cone candidates above can spawn two entries for one
+ * cone.  These calls find such twins among ALL cone pairs of a map, fuse each pair into one cone, compact the map, and merge the two
+ * landmark vertices in the graph (g2o's OptimizableGraph::mergeVertices).  The rule is build-defined.  No contraction anywhere: every
+ * product and sum below is rounded once, in the order the parentheses give.
+ *
+ * Map.  What the association calls take: xy [n][2], type [n] (int32) and cov [n][4] (row-major 2x2, entry [1] read; NULL or never set: zeros).
+ * Pair.  The quantities of cones i != j are ALWAYS formed from a = min(i, j) and b = max(i, j), so both ends of a pair see identical bits:
+ *            s2 = sigma_floor sigma_floor  (formed once, on the host)
+ *            A00 = Ca00 + s2   A01 = Ca01   A11 = Ca11 + s2         B00 = Cb00 + s2   B01 = Cb01   B11 = Cb11 + s2
+ *            S00 = A00 + B00   S01 = A01 + B01   S11 = A11 + B11     n0 = xb - xa   n1 = yb - ya
+ *            det = (S00 S11) - (S01 S01)
+ *            d2  = ((((S11 n0) n0) - (((2 S01) n0) n1)) + ((S00 n1) n1)) / det          (the covariance-gated association's order)
+ *      The pair is ADMISSIBLE iff ALL of   type_a == type_b (only when require_same_type),   sqrt((n0 n0) + (n1 n1)) < max_distance,
+ *      det > 0,   S00 > 0,   d2 < gate_chi2   hold.  Positive tests: any NaN skips the pair, so a cone whose xy is not finite is invisible
+ *      (as a free candidate slot is).  A cone is never its own partner.
+ * Per cone i.  twin[i] = the admissible j with the smallest d2, exact ties to the lowest j, -1 when there is none; d2[i] = that d2, +inf
+ *      when there is none; second_d2[i] = the smallest d2 among the OTHER admissible cones, +inf when there is none; n_admissible[i] = how
+ *      many cones are admissible.
+ * Twin pair.  (a, b), a < b, is a twin pair iff twin[a] == b and twin[b] == a — with `exclusive` also n_admissible == 1 at both ends.  Twin
+ *      pairs are disjoint by construction.  Of a triplet the closest two are a pair in one round and the third finds the fused cone in the
+ *      next: the caller repeats until n_pairs == 0.
+ * Fusion of a twin pair.  The keeper is a.  With A, B, S, det, n0, n1 of the pair as above:
+ *            K00 = ((A00 S11) - (A01 S01)) / det      K01 = ((A01 S00) - (A00 S01)) / det
+ *            K10 = ((A01 S11) - (A11 S01)) / det      K11 = ((A11 S00) - (A01 S01)) / det
+ *            x+ = xa + ((K00 n0) + (K01 n1))          y+ = ya + ((K10 n0) + (K11 n1))
+ *            C00+ = (K00 B00) + (K01 B01)             C01+ = (K00 B01) + (K01 B11)             C11+ = (K10 B01) + (K11 B11)
+ *      (K = A S^-1, C+ = K B = the parallel sum (A^-1 + B^-1)^-1: no C - K C cancellation); cov+ = (C00+, C01+, C01+, C11+), the 01 entry
+ *      formed once; the type is a's.  THE FLOOR IS PART OF C+: A and B carry s2, so two cones of zero covariance fuse to (s2 / 2) I and
+ *      every fused cone's covariance includes what the floor stood for.
+ * Consolidated map.  Every b of a twin pair is dropped; every other cone keeps its relative order; a cone in no pair keeps its bits (a NaN
+ *      cone included); a keeper takes x+, y+, cov+.  remap[old] = the new index, remap[b] = remap[a].  n_out = n_in - n_pairs.
+ *
+ * gs_dup_params_default fills the struct: require_same_type 1, exclusive 0, gate_chi2 5.991464547107979 (95 %, 2 dof, as gs_nn_params),
+ *      max_distance 1.0 m (the reference's m_newConeThreshold), sigma_floor 0.05 m (gs_nn_params.sigma_xy's default).
+ *      Refused (GS_ERR_INVALID) before the device is touched, by every call below that takes the block: a null block, a wrong struct_size,
+ *      a parameter that is not finite, gate_chi2 <= 0, max_distance <= 0, sigma_floor < 0, require_same_type or exclusive outside {0, 1};
+ *      a map of more than GS_DUP_MAP_MAX cones; a null array where one is required.  A host-only handle: GS_ERR_NO_DEVICE.
+ * gs_dup_info: n_in, n_out, n_pairs, n_ambiguous = the cones of the INPUT map with n_admissible > 1.
+ * gs_map_twins_batch: a query over host arrays; map_cov and every output but out_twin may be NULL.
+ * gs_map_twins_resident: the same over the resident map and its covariances; outputs in DEVICE memory ([map size] each, every one but
+ *      dev_out_twin may be NULL), asynchronous on the handle's stream.  Nothing is changed.
+ * gs_map_merge_twins_batch: host map in, consolidated host map out (each output array has room for n_map cones and is written whole: entries from n_out
+ *      on are free cones, xy = (NaN, NaN), type 0, zero covariance); out_cov is written when map_cov is given and may be NULL; out_remap [n_map] and out_info may be NULL.
+ * gs_map_merge_twins: consolidates the RESIDENT map in place, device to device (compacted into a second buffer and copied back), with the
+ *      one wait at its end that the new map size needs: a maintenance call, not a per-frame one.  It invalidates what gs_map_clear
+ *      invalidates (the grids of the resident searches).  out_remap is a host array of `capacity` entries, capacity >= the map size before
+ *      the call (else GS_ERR_CAPACITY, nothing changes), and may be NULL (capacity is then ignored).  A handle that never set a covariance
+ *      runs with Sigma = 0, stores no C+ and creates no covariance array.
+ * gs_map_get_xy: positions and types of the resident map's cones [first, first + n) back to the host (either output may be NULL): after a
+ *      consolidation the caller's own copy of the map is stale.
+ * All four twins calls return identical bits for identical maps.  Four dispatches for a consolidation (gs_dup.hip: the search, the mutual
+ *      test with the fusion and per-block counts, a one-workgroup scan of the block counts, the scatter), one for a query; no atomics, no
+ *      spin, no cross-workgroup wait.  A handle that never calls these allocates and launches nothing for them.
+ * gs_merge_landmarks(keep, drop) = g2o's mergeVertices(keep, drop, erase = true) on the handle's graph: every observation edge of `drop`
+ *      (polar edges are observation edges and follow) and every landmark prior of `drop` is re-attached to `keep`, activity flags stay with
+ *      their edge, `drop` is erased, later landmarks move down by one (in the graph, in the priors' and in the polar edges' tables alike).
+ *      The next optimisation runs a full structure phase; marginals become stale.  keep's estimate and fixed flag are untouched: the caller sets the fused position with gs_set_landmark_estimate.  Estimates
+ *      that are newer on the device are brought to the host first (as gs_add_landmark does).  Afterwards the handle is indistinguishable
+ *      from a fresh one given the same insertions without `drop` and with those edges pointing at `keep`.
+ *      Unknown id: GS_ERR_UNKNOWN_ID.  keep == drop, `drop` fixed while `keep` is free, a handle configured with
+ *      gs_dist_configure(world > 1): GS_ERR_INVALID.
+ * NOT DONE: twins inside the candidate table (the search kernel takes plain (xy, type, cov, n) pointers so that it can be handed the table);
+ *      a grid instead of the walk over all pairs; cone-cone cross-covariances (outside the factor's pattern, as the association ignores
+ *      them); chains merged in one round; sharded handles; the Slam mirror and the shell. */
+#define GS_DUP_MAP_MAX 262144
+typedef struct gs_dup_params {
+    int32_t struct_size;
+    int32_t require_same_type;  /* 1; 0 or 1 */
+    int32_t exclusive;          /* 0; 0 or 1 */
+    int32_t reserved;
+    double gate_chi2;           /* 5.991464547107979: 95 %, 2 dof */
+    double max_distance;        /* 1.0 m: Euclidean pre-gate */
+    double sigma_floor;         /* 0.05 m; >= 0 */
+} gs_dup_params;
+typedef struct gs_dup_info {
+    int32_t n_in, n_out, n_pairs, n_ambiguous;
+} gs_dup_info;
+int  gs_dup_params_default(gs_dup_params *p);
+int  gs_map_twins_batch(gs_graph *g, int32_t n_map, const double *map_xy, const int32_t *map_type, const double *map_cov_2x2,
+                        const gs_dup_params *params, int32_t *out_twin, double *out_d2, double *out_second_d2, int32_t *out_n_admissible);
+int  gs_map_twins_resident(gs_graph *g, const gs_dup_params *params, int32_t *dev_out_twin, double *dev_out_d2, double *dev_out_second_d2,
+                           int32_t *dev_out_n_admissible);
+int  gs_map_merge_twins_batch(gs_graph *g, int32_t n_map, const double *map_xy, const int32_t *map_type, const double *map_cov_2x2,
+                              const gs_dup_params *params, double *out_xy, int32_t *out_type, double *out_cov_2x2, int32_t *out_remap,
+                              gs_dup_info *out_info);
+int  gs_map_merge_twins(gs_graph *g, const gs_dup_params *params, int32_t capacity, int32_t *out_remap, gs_dup_info *out_info);
+int  gs_map_get_xy(gs_graph *g, int32_t first, int32_t n, double *out_xy, int32_t *out_type);
+int  gs_merge_landmarks(gs_graph *g, int32_t keep_id, int32_t drop_id);
+
 /* ---- multi-GPU: pose-window shards -----------------------------
  * Each rank owns a contiguous pose window and builds the SAME global plan; it linearises and
  * factorises only its own subtrees, exports the update contributions to the shared top of the

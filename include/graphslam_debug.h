@@ -148,6 +148,12 @@ int gs_debug_time_cand_resident(gs_graph *g, int32_t n_steps, int32_t n, const d
                                 const gs_cand *dev_in_table, const gs_nn_params *params, const gs_cand_params *cand, gs_cand_step *dev_out_steps,
                                 int32_t *dev_out_cand_id, int32_t *dev_out_cand_slot, gs_cand *dev_out_table, int32_t *dev_out_meta_4,
                                 int32_t reps, double *out_ms);
+/* Map twins.  gs_debug_time_map_twins_resident: `reps` calls of gs_map_twins_resident, events on its one dispatch.
+ * gs_debug_time_map_merge_twins: `reps` times the four dispatches of gs_map_merge_twins over the resident map into the second buffer, events
+ * from the first to the last; the map itself is left as it is, so every run sees the same twins.  Mean milliseconds per run. */
+int gs_debug_time_map_twins_resident(gs_graph *g, const gs_dup_params *params, int32_t *dev_out_twin, double *dev_out_d2, double *dev_out_second_d2,
+                                     int32_t *dev_out_n_admissible, int32_t reps, double *out_ms);
+int gs_debug_time_map_merge_twins(gs_graph *g, const gs_dup_params *params, int32_t reps, double *out_ms);
 /* Measurement hook of the sharded iteration (bench.py's `ms_exchange`): `reps` RCCL all-reduces of the exchange buffer back to back on the
  * handle's stream, HIP events around them; mean ms per all-reduce.  Collective: every rank of the communicator calls it. */
 int gs_debug_time_exchange(gs_graph *g, int32_t reps, double *out_ms);

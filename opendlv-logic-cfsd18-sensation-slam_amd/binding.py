@@ -270,6 +270,31 @@ CAND_STEP = np.dtype([("step", "<i4"), ("n_unexplained", "<i4"), ("n_fused", "<i
                       ("n_dropped", "<i4"), ("n_missed", "<i4"), ("n_retired", "<i4"), ("n_confirmed", "<i4"), ("n_live", "<i4"), ("reserved", "<i4")])
 
 
+DUP_MAP_MAX = 262144                                        # GS_DUP_MAP_MAX
+
+
+class DupParams(C.Structure):
+    """gs_dup_params (include/graphslam.h): which cone pairs of a map count as twins"""
+    _fields_ = [("struct_size", C.c_int32), ("require_same_type", C.c_int32), ("exclusive", C.c_int32), ("reserved", C.c_int32), ("gate_chi2", C.c_double),
+                ("max_distance", C.c_double), ("sigma_floor", C.c_double)]
+
+
+def dup_params(**kw):
+    """the library's gs_dup_params defaults, with the named fields changed"""
+    p = DupParams(); L = lib()
+    rc = L.gs_dup_params_default(C.byref(p))
+    if rc != GS_OK:
+        raise GsError(rc, (L.gs_last_error() or b"").decode())
+    for k, v in kw.items():
+        if k not in ("require_same_type", "exclusive", "gate_chi2", "max_distance", "sigma_floor"):
+            raise AttributeError("gs_dup_params has no field %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+DUP_INFO = np.dtype([("n_in", "<i4"), ("n_out", "<i4"), ("n_pairs", "<i4"), ("n_ambiguous", "<i4")])      # gs_dup_info
+
+
 class DoglegParams(C.Structure):
     """gs_dogleg_params (include/graphslam.h)"""
     _fields_ = [("struct_size", C.c_int32), ("max_trials_after_failure", C.c_int32), ("initial_delta", C.c_double)]
@@ -492,6 +517,17 @@ def lib():
         L.gs_cand_get.argtypes = [vp, vp, _ip, _ip, _ip]
         L.gs_cand_take_confirmed.argtypes = [vp, C.c_int32, vp, _ip]
         L.gs_frame_frontend_candidates.argtypes = [vp, _dp, _dp, _dp, C.c_int32, _ip, npp, cpp, vp, _ip, _ip]
+    if hasattr(L, "gs_map_twins_batch"):                   # (and for the map twins)
+        upp = C.POINTER(DupParams)
+        L.gs_dup_params_default.argtypes = [upp]
+        L.gs_map_twins_batch.argtypes = [vp, C.c_int32, _dp, _ip, _dp, upp, _ip, _dp, _dp, _ip]
+        L.gs_map_twins_resident.argtypes = [vp, upp, vp, vp, vp, vp]
+        L.gs_debug_time_map_twins_resident.argtypes = [vp, upp, vp, vp, vp, vp, C.c_int32, _dp]
+        L.gs_debug_time_map_merge_twins.argtypes = [vp, upp, C.c_int32, _dp]
+        L.gs_map_merge_twins_batch.argtypes = [vp, C.c_int32, _dp, _ip, _dp, upp, _dp, _ip, _dp, _ip, vp]
+        L.gs_map_merge_twins.argtypes = [vp, upp, C.c_int32, _ip, vp]
+        L.gs_map_get_xy.argtypes = [vp, C.c_int32, C.c_int32, _dp, _ip]
+        L.gs_merge_landmarks.argtypes = [vp, C.c_int32, C.c_int32]
     if hasattr(L, "gs_set_robust_kernel"):                # (a tuning build of an older tree loaded through GS_LIB may predate the robust kernels)
         L.gs_set_robust_kernel.argtypes = [vp, C.c_int32, C.c_int32, C.c_double]
         L.gs_get_robust_kernel.argtypes = [vp, C.c_int32, _ip, _dp]
@@ -1525,6 +1561,91 @@ class Graph:
         self._check(self.L.gs_frame_frontend_candidates(self.h, _d(pose), None if pc is None else _d(pc), _d(obs), k, None if ii is None else _i(ii), C.byref(p),
                                                         C.byref(c), step.ctypes.data_as(C.c_void_p), _i(cid), _i(slot)))
         return step[0].copy(), cid[:k].copy(), slot[:k].copy()
+
+    # ---- map twins (include/graphslam.h): duplicate cones found, fused and merged in the graph.  params = DupParams (None: the defaults)
+    def map_twins(self, map_xy, map_type, map_cov=None, params=None):
+        """gs_map_twins_batch: (twin [n] int32, d2 [n], second_d2 [n], n_admissible [n] int32) of a host map"""
+        xy = _f64(map_xy, (-1, 2)); ty = _i32(map_type); n = len(ty); mc = None if map_cov is None else _f64(map_cov, (-1, 4))
+        assert len(xy) == n and (mc is None or len(mc) == n)
+        p = dup_params() if params is None else params
+        tw = np.zeros(max(n, 1), dtype=np.int32); d2 = np.zeros(max(n, 1)); sec = np.zeros(max(n, 1)); na = np.zeros(max(n, 1), dtype=np.int32)
+        self._check(self.L.gs_map_twins_batch(self.h, n, _d(xy), _i(ty), None if mc is None else _d(mc), C.byref(p), _i(tw), _d(d2), _d(sec), _i(na)))
+        return tw[:n].copy(), d2[:n].copy(), sec[:n].copy(), na[:n].copy()
+
+    def map_twins_resident(self, d_twin, d_d2=None, d_second=None, d_n_admissible=None, params=None):
+        """gs_map_twins_resident: the resident map and its covariances, outputs DeviceArray; asynchronous (synchronize() before reading)"""
+        p = dup_params() if params is None else params
+        opt = lambda a: None if a is None else a.ptr
+        self._check(self.L.gs_map_twins_resident(self.h, C.byref(p), opt(d_twin), opt(d_d2), opt(d_second), opt(d_n_admissible)))
+
+    def time_map_twins_resident(self, d_twin, reps, d_d2=None, d_second=None, d_n_admissible=None, params=None):
+        """gs_debug_time_map_twins_resident: mean milliseconds per call, events on the search's dispatch"""
+        p = dup_params() if params is None else params
+        opt = lambda a: None if a is None else a.ptr
+        ms = C.c_double()
+        self._check(self.L.gs_debug_time_map_twins_resident(self.h, C.byref(p), opt(d_twin), opt(d_d2), opt(d_second), opt(d_n_admissible), int(reps), C.byref(ms)))
+        return ms.value
+
+    def time_map_merge_twins(self, reps, params=None):
+        """gs_debug_time_map_merge_twins: mean milliseconds of the consolidation's four dispatches over the resident map, which stays as it is"""
+        p = dup_params() if params is None else params
+        ms = C.c_double()
+        self._check(self.L.gs_debug_time_map_merge_twins(self.h, C.byref(p), int(reps), C.byref(ms)))
+        return ms.value
+
+    def map_merge_twins_batch(self, map_xy, map_type, map_cov=None, params=None):
+        """gs_map_merge_twins_batch: (xy [n_out,2], type [n_out], cov [n_out,2,2] or None, remap [n], info) of a host map"""
+        xy = _f64(map_xy, (-1, 2)); ty = _i32(map_type); n = len(ty); mc = None if map_cov is None else _f64(map_cov, (-1, 4))
+        assert len(xy) == n and (mc is None or len(mc) == n)
+        p = dup_params() if params is None else params
+        m = max(n, 1)
+        oxy = np.zeros((m, 2)); oty = np.zeros(m, dtype=np.int32); ocv = None if mc is None else np.zeros((m, 2, 2)); rm = np.zeros(m, dtype=np.int32)
+        info = np.zeros(1, dtype=DUP_INFO)
+        self._check(self.L.gs_map_merge_twins_batch(self.h, n, _d(xy), _i(ty), None if mc is None else _d(mc), C.byref(p), _d(oxy), _i(oty),
+                                                    None if ocv is None else _d(ocv), _i(rm), info.ctypes.data_as(C.c_void_p)))
+        k = int(info[0]["n_out"])
+        return oxy[:k].copy(), oty[:k].copy(), None if ocv is None else ocv[:k].copy(), rm[:n].copy(), info[0].copy()
+
+    def map_merge_twins(self, params=None):
+        """gs_map_merge_twins: the resident map consolidated in place; (remap [map size before], info)"""
+        p = dup_params() if params is None else params
+        n = self.map_size(); rm = np.zeros(max(n, 1), dtype=np.int32); info = np.zeros(1, dtype=DUP_INFO)
+        self._check(self.L.gs_map_merge_twins(self.h, C.byref(p), len(rm), _i(rm), info.ctypes.data_as(C.c_void_p)))
+        return rm[:n].copy(), info[0].copy()
+
+    def map_xy(self, first=0, n=None):
+        """gs_map_get_xy: (xy [n,2], type [n]) of the resident map's cones [first, first + n) (n = None: to the end)"""
+        n = self.map_size() - int(first) if n is None else int(n)
+        xy = np.zeros((max(n, 1), 2)); ty = np.zeros(max(n, 1), dtype=np.int32)
+        self._check(self.L.gs_map_get_xy(self.h, int(first), n, _d(xy), _i(ty)))
+        return xy[:max(n, 0)].copy(), ty[:max(n, 0)].copy()
+
+    def merge_landmarks(self, keep_id, drop_id):
+        """gs_merge_landmarks: drop's observation edges and priors re-attached to keep, drop erased"""
+        self._check(self.L.gs_merge_landmarks(self.h, int(keep_id), int(drop_id)))
+
+    def map_consolidate(self, lm_ids, params=None):
+        """The resident map consolidated (gs_map_merge_twins) and the graph with it: lm_ids[j] is the graph id of map cone j (-1: not in the
+        graph).  For every twin pair whose two cones are in the graph the dropped cone's landmark is merged into the keeper's
+        (gs_merge_landmarks) and the keeper's estimate set to the fused position.  Returns (remap, new_lm_ids, info): new_lm_ids[k] is the graph
+        id of cone k of the consolidated map — of a pair the keeper's, or the dropped cone's where only that one was in the graph."""
+        ids = _i32(lm_ids); n = self.map_size()
+        assert len(ids) == n
+        remap, info = self.map_merge_twins(params)
+        new_ids = np.full(int(info["n_out"]), -1, dtype=np.int32)
+        xy, _ = self.map_xy()
+        seen = {}
+        for old in range(n):
+            k = int(remap[old])
+            if k not in seen:
+                seen[k] = old; new_ids[k] = ids[old]
+                continue
+            a, b = seen[k], old                             # a twin pair: a < b, a the keeper
+            if ids[a] >= 0 and ids[b] >= 0:
+                self.merge_landmarks(int(ids[a]), int(ids[b])); self.set_landmark_estimate(int(ids[a]), xy[k])
+            elif ids[b] >= 0:
+                new_ids[k] = ids[b]
+        return remap, new_ids, info
 
     # ---- pose-window shards (one handle per rank / GPU)
     def dist_configure(self, rank, world):

@@ -153,6 +153,7 @@ void gs_frontend_release(gs_graph *g) {      // gs_destroy
     if (g->fe.fo_state) hipFree(g->fe.fo_state);
     if (g->fe.fo_best) hipFree(g->fe.fo_best);
     gs_cand_release(g);
+    gs_dup_release(g);
     g->fe = gs_graph::FrontEnd();
 }
 

@@ -96,6 +96,9 @@ struct gs_graph {
         // grow-only), the frame call's staging (CandFrameIo)
         gs::DevArena cd_mem, cd_batch; bool cd_live = false;
         gs::FrameStage cd_io;
+        // map twins (empty until one of their calls is made): a call's uploads, search outputs, second buffer and counters (gs_dup_host.hpp's
+        // DupLayout, grow-only)
+        gs::DevArena dp_mem;
     } fe;
     bool tree_proven = false;               // a whole-tree launch sequence of the CURRENT plan has completed without a flag timeout (gs_optimize then sends all iterations of a call at once)
     bool fell_back = false;                 // a whole-tree launch gave up on a flag: this handle uses one launch per level — until the next plan, or until a retry (below) comes back clean

@@ -131,4 +131,5 @@ namespace gs { struct NnDev; }
 int nn_params_check(const gs_nn_params *p, gs::NnDev &d);                      // gs_frontend.cpp: what every call refuses of gs_nn_params, before the device is touched
 int frame_start_check(int32_t n, int32_t n_frames, const int32_t *fs);         // gs_frontend.cpp: a batch call's frame bounds
 void gs_cand_release(gs_graph *g);           // gs_cand_api.cpp: the cone candidates' buffers (gs_frontend_release)
+void gs_dup_release(gs_graph *g);            // gs_dup_api.cpp: the map twins' buffers (gs_frontend_release)
 void gs_dist_comm_release(gs_graph *g);      // gs_dist.cpp: the handle's own RCCL communicator
