@@ -18,6 +18,7 @@
 // once per inlining context), heading cos / sin come from sincos everywhere, and the winner is a minimum over (d2, index) — which does
 // not depend on the order the candidates arrive in; the frame kernel reduces it in a fixed order all the same.
 #include "gs_assoc_dev.hpp"
+#include "gs_edge_dev.hpp"      // normalize_theta
 #include <hip/hip_ext.h>
 
 namespace gs {
@@ -619,16 +620,6 @@ struct LoArgs : FrameArgs {
     const int32_t *in_idx; int max_it; double tol_xy, tol_th;
     double *out_pose, *out_cov, *out_chi2; int32_t *out_pairs, *out_iters, *out_status; double *out_step;
 };
-__device__ __forceinline__ double lo_normalize_theta(double th) {             // g2o normalize_theta, as in gs_kernels.hip (k_update)
-#pragma clang fp contract(off)
-    constexpr double pi = 3.14159265358979323846;
-    if (th >= -pi && th < pi) return th;
-    const double m = floor(th / (2.0 * pi));
-    th = th - m * 2.0 * pi;
-    if (th >= pi) th -= 2.0 * pi;
-    if (th < -pi) th += 2.0 * pi;
-    return th;
-}
 // one row's terms at the pose (sn, cs: its heading's sin / cos) ADDED to S (a, c[3], M[6]: jc_solve's layout) when the pair counts; FINAL: a
 // and M, else c and M (the terms not added are never computed: everything here is inlined)
 template <bool FINAL>
@@ -752,7 +743,7 @@ __device__ __forceinline__ void lo_pass(LoRows<SLOTS> &R, const LoArgs &A, int f
         chi2 = S[0] + ((x[0] * d[0] + x[1] * d[1]) + x[2] * d[2]);
     }
     if (status == 3) { lo_write(A, fw, x0, P, __builtin_inf(), 0, iters, 3, zero3); return; }
-    xf[2] = lo_normalize_theta(xf[2]);                                         // k_update's addition and normalisation
+    xf[2] = normalize_theta(xf[2]);                                         // k_update's addition and normalisation
     lo_write(A, fw, xf, cv, chi2, pairs, iters, status, d);
 }
 __global__ void __launch_bounds__(256) k_localize(LoArgs A) {

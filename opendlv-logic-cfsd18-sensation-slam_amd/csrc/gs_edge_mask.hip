@@ -9,38 +9,13 @@
 //                     the three entries of t_pl_w, or the six entries of pp_info.  Every index is checked against the plan's counts on
 //                     the device; plain vector stores, one writer per address (an edge is listed once).
 // k_edge_select       a thread per edge of one kind: s = e^T Omega e with the edge's OWN information at the current estimates — the
-//                     residual expressions of edge_pl / pp_incidence (GS_G2O_ORDER: inverse, then compose, every product rounded on its
-//                     own), the poses' cached cos / sin —, the weight of the kind's robust kernel (0 for an inactive edge), a candidate
+//                     residuals and squared errors of the linearisation (pl_sq_error / pp_sq_error, gs_edge_dev.hpp), the poses' cached cos / sin —, the weight of the kind's robust kernel (0 for an inactive edge), a candidate
 //                     byte (active and s > threshold) and the candidates per workgroup (waves by ballot, then the four waves' counts
 //                     in index order: integers, no floating-point atomics, nothing order-dependent).
 #include "gs_edge_mask.hpp"
 #include "gs_side_dev.hpp"
 
 namespace gs {
-
-// EdgeSE2PointXY: e = (x_p^-1 * l) - z, s = e^T W e (edge_pl + the first lines of quad_pl)
-__device__ __forceinline__ double mask_s_pl(double px, double py, double c, double s, double lx, double ly, double zx, double zy, double w00, double w01, double w11) {
-    double dx, dy;
-    side_lm_in_pose_frame(px, py, c, s, lx, ly, dx, dy);
-    const double ex = dx - zx, ey = dy - zy;
-    const double We0 = w00 * ex + w01 * ey, We1 = w01 * ex + w11 * ey;
-    return ex * We0 + ey * We1;
-}
-// EdgeSE2: e = vec(z^-1 * (x_i^-1 * x_j)), s = e^T W e (the residual of pp_incidence)
-__device__ __forceinline__ double mask_s_pp(const double xi[3], const double xj[3], double ci, double si, const double zinv5[5], const double w[6]) {
-    const double rth = side_normalize_theta(side_normalize_theta(-xi[2]) + xj[2]);
-    const double cz = zinv5[3], sz = zinv5[4];
-    double e0, e1;
-    {
-#pragma clang fp contract(off)
-        const double ix = -(ci * xi[0] + si * xi[1]), iy = si * xi[0] - ci * xi[1];
-        const double qx = ix + (ci * xj[0] + si * xj[1]), qy = iy + (ci * xj[1] - si * xj[0]);
-        e0 = zinv5[0] + (cz * qx - sz * qy); e1 = zinv5[1] + (sz * qx + cz * qy);
-    }
-    const double e2 = side_normalize_theta(zinv5[2] + rth);
-    const double We0 = w[0] * e0 + w[1] * e1 + w[2] * e2, We1 = w[1] * e0 + w[3] * e1 + w[4] * e2, We2 = w[2] * e0 + w[4] * e1 + w[5] * e2;
-    return e0 * We0 + e1 * We1 + e2 * We2;
-}
 
 __global__ void __launch_bounds__(256) k_edge_mask_apply(DevGraph d, int kind, int n, const int32_t *__restrict__ loc, const double *__restrict__ orig,
                                                          const uint8_t *__restrict__ act) {
@@ -87,8 +62,8 @@ __global__ void __launch_bounds__(256) k_edge_select(DevGraph d, int kind, int n
 #pragma unroll
                 for (int c = 0; c < 6; ++c) wi[c] = info[6 * (int64_t)k + c];
                 const double2 ci = reinterpret_cast<const double2 *>(d.pose_cs)[i];
-                s = mask_s_pp(xi, xj, ci.x, ci.y, z5, wi);
-                if (on) side_robust_rho(d.rk_pp, d.rd_pp, s, w);
+                s = pp_sq_error(xi, xj, ci.x, ci.y, z5, wi);
+                if (on) robust_rho(d.rk_pp, d.rd_pp, s, w);
                 ok = true; }
         } else {
             const int p = tab[3 * (int64_t)k], l = tab[3 * (int64_t)k + 1], src = tab[3 * (int64_t)k + 2];
@@ -97,9 +72,9 @@ __global__ void __launch_bounds__(256) k_edge_select(DevGraph d, int kind, int n
             else if (side_pl_in_tail(d, src, e) && d.t_pl_z) { zx = d.t_pl_z[2 * e]; zy = d.t_pl_z[2 * e + 1]; have = true; }
             if (have && p >= 0 && p < NP && l >= 0 && l < NL) {
                 const double2 cs = reinterpret_cast<const double2 *>(d.pose_cs)[p];
-                s = mask_s_pl(d.pose_est[3 * (int64_t)p], d.pose_est[3 * (int64_t)p + 1], cs.x, cs.y, d.lm_est[2 * (int64_t)l], d.lm_est[2 * (int64_t)l + 1],
-                              zx, zy, info[3 * (int64_t)k], info[3 * (int64_t)k + 1], info[3 * (int64_t)k + 2]);
-                if (on) side_robust_rho(d.rk_pl, d.rd_pl, s, w);
+                s = pl_sq_error(d.pose_est[3 * (int64_t)p], d.pose_est[3 * (int64_t)p + 1], cs.x, cs.y, d.lm_est[2 * (int64_t)l], d.lm_est[2 * (int64_t)l + 1],
+                                zx, zy, info[3 * (int64_t)k], info[3 * (int64_t)k + 1], info[3 * (int64_t)k + 2]);
+                if (on) robust_rho(d.rk_pl, d.rd_pl, s, w);
                 ok = true; }
         }
     }

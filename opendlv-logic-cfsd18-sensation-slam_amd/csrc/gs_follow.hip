@@ -6,6 +6,7 @@
 //                     ballots, best by a scan of broadcasts; then the workgroup's 256 threads copy the pruned index
 // No atomics, no spin, no cross-workgroup wait.  Every floating-point expression is under contract(off): the header's order of operations.
 #include "gs_follow.hpp"
+#include "gs_edge_dev.hpp"      // normalize_theta
 #include <hip/hip_ext.h>
 
 #include <algorithm>
@@ -14,16 +15,6 @@ namespace gs {
 
 namespace {
 
-__device__ __forceinline__ double fo_normalize_theta(double th) {             // g2o normalize_theta, as in gs_kernels.hip (k_update)
-#pragma clang fp contract(off)
-    constexpr double pi = 3.14159265358979323846;
-    if (th >= -pi && th < pi) return th;
-    const double m = floor(th / (2.0 * pi));
-    th = th - m * 2.0 * pi;
-    if (th >= pi) th -= 2.0 * pi;
-    if (th < -pi) th += 2.0 * pi;
-    return th;
-}
 // lane `src`'s value in every lane; src is wave-uniform (a loop counter): two v_readlane, no LDS traffic
 __device__ __forceinline__ int fo_bcast(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
 __device__ __forceinline__ double fo_bcast(double v, int src) {
@@ -41,7 +32,7 @@ __device__ __forceinline__ void fo_predict(const double *u, const double *qu, do
 #pragma clang fp contract(off)
     double s, c; sincos(x[2], &s, &c);
     const double p = (c * u[0]) - (s * u[1]), q = (s * u[0]) + (c * u[1]);
-    x[0] = x[0] + p; x[1] = x[1] + q; x[2] = fo_normalize_theta(x[2] + u[2]);
+    x[0] = x[0] + p; x[1] = x[1] + q; x[2] = normalize_theta(x[2] + u[2]);
     const double a = -q, b = p;
     const double P00 = P[0], P01 = P[1], P02 = P[2], P11 = P[3], P12 = P[4], P22 = P[5];
     double S[6];
@@ -158,7 +149,7 @@ __global__ void __launch_bounds__(256) k_follow_update(FoUpdateArgs U) {
             const int alive_h = fo_bcast(alive, hh);
             if (!alive_h) continue;                                            // (wave-uniform) a retired hypothesis is compared with nobody
             const double xh = fo_bcast(s.pose[0], hh), yh = fo_bcast(s.pose[1], hh), th = fo_bcast(s.pose[2], hh);
-            const double dx = xh - s.pose[0], dy = yh - s.pose[1], dth = fo_normalize_theta(th - s.pose[2]);
+            const double dx = xh - s.pose[0], dy = yh - s.pose[1], dth = normalize_theta(th - s.pose[2]);
             const bool near = alive && h < hh && ((dx * dx) + (dy * dy)) < A.merge2 && fabs(dth) < A.merge_theta;
             const unsigned long long m = __ballot(near);
             if (m != 0ull && h == hh) { alive = 0; s.state = 2; s.duplicate_of = __builtin_ctzll(m); s.state_step = A.t; }

@@ -15,6 +15,7 @@
 //
 // All fp64; every sum has a fixed order (no floating-point atomics) so results are bitwise reproducible.
 #include "gs_device.hpp"
+#include "gs_edge_dev.hpp"
 #include "gs_frontend_dev.hpp"
 #include <hip/hip_ext.h>
 #include <algorithm>
@@ -26,26 +27,7 @@
 namespace gs {
 
 static constexpr int WAVE = 64;
-static constexpr int LM_REC = 8;       // doubles per (wave tile, landmark) partial-sum record: {H00, H01, H11, b0, b1, -, -, -} = one 64-byte line (gs_device.hpp: lm_part)
-// GS_G2O_ORDER (default 1): the edge residuals in g2o's operation order (inverse, then compose) without fused
-// multiply-adds; 0 = differences first (fewer rounding errors, but not the reference's numbers) — A/B builds only
-#ifndef GS_G2O_ORDER
-#define GS_G2O_ORDER 1
-#endif
-
-// (kDeg2Rad, kRad2Deg, kPiF: gs_frontend_dev.hpp)
-__device__ static constexpr double kPi = 3.14159265358979323846;
-
-// g2o normalize_theta
-__device__ __forceinline__ double normalize_theta(double th) {
-#pragma clang fp contract(off)                                      // m * 2 pi is rounded before the subtraction, as on the CPU path
-    if (th >= -kPi && th < kPi) return th;
-    double m = floor(th / (2.0 * kPi));
-    th = th - m * 2.0 * kPi;
-    if (th >= kPi) th -= 2.0 * kPi;
-    if (th < -kPi) th += 2.0 * kPi;
-    return th;
-}
+// (kPi, normalize_theta: gs_edge_dev.hpp; LM_REC: gs_layout.hpp)
 
 // ------------------------------------------------------------------ A0  (polar_to_xy, cone_to_global_cs: gs_frontend_dev.hpp)
 
@@ -232,59 +214,12 @@ void launch_frame_frontend(int k, const double *in, double lidar, int n_map, con
 }
 
 // ------------------------------------------------------------------ A5-A7
-// EdgeSE2PointXY with the pose's cos/sin already known: error, Jacobian rows A0/A1 (2x3); B = R(theta)^T
-__device__ __forceinline__ void edge_pl(double px, double py, double c, double s, double lx, double ly, double zx, double zy,
-                                        double &ex, double &ey, double A0[3], double A1[3]) {
-#if !GS_G2O_ORDER
-    double dx = lx - px, dy = ly - py;
-#endif
-#if GS_G2O_ORDER
-    {   // g2o EdgeSE2PointXY::computeError: (x_p^-1 * l) - z with SE2::inverse() = (R^T (-t), -theta) and SE2 * point =
-        // R p + t, in g2o's operation order and without fused multiply-adds: at kilometre coordinates the two products
-        // cancel to the metre-sized residual and HOW they are rounded is 1e-12 m of it — the CPU path's rounding is the bar
-#pragma clang fp contract(off)
-        const double ix = -(c * px + s * py), iy = s * px - c * py;
-        ex = ((c * lx + s * ly) + ix) - zx;
-        ey = ((c * ly - s * lx) + iy) - zy;
-    }
-#else
-    ex = (c * dx + s * dy) - zx;
-    ey = (-s * dx + c * dy) - zy;
-#endif
-    A0[0] = -c; A0[1] = -s; A1[0] = s;  A1[1] = -c;
-#if GS_G2O_ORDER
-    {   // g2o EdgeSE2PointXY::linearizeOplus writes the lever-arm entries as  a1 y2 - a1 y1 - a3 x2 + a3 x1  and
-        // -a3 y2 + a3 y1 - a1 x2 + a1 x1  (a1 = cos, a3 = sin; left to right, every product rounded): at kilometre coordinates that
-        // is 1e-13 of relative rounding in H_pp and H_pl which "differences first" does not have — and cond(H) ~ 1e13 on a 25 km lap
-        // turns exactly that 1e-13 into the per-cent of the first increment by which the GPU path stood apart from every CPU path
-        // (measured: profiles/r03_parity_spread_cfg4*.json).  The reference's numbers are the bar: same order, no contraction.
-#pragma clang fp contract(off)
-        A0[2] = ((c * ly - c * py) - s * lx) + s * px;
-        A1[2] = (((-s) * ly + s * py) - c * lx) + c * px;
-    }
-#else
-    A0[2] = c * dy - s * dx;
-    A1[2] = -s * dy - c * dx;
-#endif
-}
+// (edge_pl, pp_error, W e and the squared errors, robust_rho: gs_edge_dev.hpp)
 
 // One observation edge: everything constructQuadraticForm produces, packed symmetric.
 //   Hp[6] = A^T W A (xx xy xt yy yt tt), bp[3] = -A^T W e, W6 = A^T W B (3x2 row-major),
 //   Hl[3] = B^T W B (00 01 11), bl[2] = -B^T W e, chi = e^T W e
 struct PlQuad { double Hp[6], bp[3], W6[6], Hl[3], bl[2], chi; };
-// Robust kernels (g2o RobustKernelHuber / RobustKernelCauchy, restated): for the squared error s = e^T W e of an edge returns rho(s)
-// and sets w = rho'(s).  kernel: GS_ROBUST_* of include/graphslam.h (0 none, 1 Huber, 2 Cauchy).  IEEE sqrt / log / division, every
-// product rounded on its own, so that a weight is a function of s alone wherever it is computed.  w is EXACTLY 1.0 where the kernel
-// does not act (none; Huber with s <= delta^2): scaling by it changes no bit.
-__device__ __forceinline__ double robust_rho(int kernel, double delta, double s, double &w) {
-#pragma clang fp contract(off)
-    w = 1.0;
-    if (kernel == 1) { const double d2 = delta * delta;
-        if (s > d2) { const double r = sqrt(s); w = delta / r; return 2.0 * r * delta - d2; }
-        return s; }
-    if (kernel == 2) { const double d2 = delta * delta, aux = 1.0 + s / d2; w = 1.0 / aux; return d2 * log(aux); }
-    return s;
-}
 // The scaled information enters the products below as an opaque value, like the loaded one it replaces: the compiler then forms the
 // same multiply-adds in the ROBUST instance as in the plain one, and a weight of exactly 1.0 gives the plain instance's bits
 // (tests: Huber with delta = 1e150 against none).  Without it the contraction of a * (w * wr) + ... is free to differ.
@@ -297,8 +232,9 @@ __device__ __forceinline__ void quad_pl(double px, double py, double c, double s
                                         double w00, double w01, double w11, PlQuad &q, int rk = 0, double rd = 1.0) {
     double ex, ey, A0[3], A1[3];
     edge_pl(px, py, c, s, lx, ly, zx, zy, ex, ey, A0, A1);
-    double We0 = w00 * ex + w01 * ey, We1 = w01 * ex + w11 * ey;
-    q.chi = ex * We0 + ey * We1;
+    double We0, We1;
+    pl_info_error(ex, ey, w00, w01, w11, We0, We1);
+    q.chi = pl_sq_error(ex, ey, We0, We1);
     if (ROBUST) { double wr; q.chi = robust_rho(rk, rd, q.chi, wr);
         w00 = opaque(w00 * wr); w01 = opaque(w01 * wr); w11 = opaque(w11 * wr); We0 = opaque(We0 * wr); We1 = opaque(We1 * wr); }
     double WA0[3], WA1[3];
@@ -344,29 +280,17 @@ __device__ __forceinline__ double pp_incidence(const DevGraph &d, int k, int rol
     double chi = 0.0;
     const double dx = xj[0] - xi[0], dy = xj[1] - xi[1];
     const double rx = ci * dx + si * dy, ry = -si * dx + ci * dy;     // rel = xi^-1 * xj
-    const double rth = normalize_theta(normalize_theta(-xi[2]) + xj[2]);
     const double cz = zinv5[3], sz = zinv5[4];
-#if GS_G2O_ORDER
-    double e0, e1;
-    {   // g2o EdgeSE2::computeError: z^-1 * (x_i^-1 * x_j) as inverse-then-compose (SE2::inverse = (R^T (-t), -theta), SE2 * SE2 =
-        // (R_a t_b + t_a, theta_a + theta_b)), every product rounded on its own (no fused multiply-add): at the reference's
-        // initial point these residuals are zero in exact arithmetic and what is computed IS the rounding — follow the CPU path's
-#pragma clang fp contract(off)
-        const double ix = -(ci * xi[0] + si * xi[1]), iy = si * xi[0] - ci * xi[1];
-        const double qx = ix + (ci * xj[0] + si * xj[1]), qy = iy + (ci * xj[1] - si * xj[0]);
-        e0 = zinv5[0] + (cz * qx - sz * qy); e1 = zinv5[1] + (sz * qx + cz * qy);
-    }
-    const double e2 = normalize_theta(zinv5[2] + rth);
-#else
-    const double e0 = zinv5[0] + (cz * rx - sz * ry), e1 = zinv5[1] + (sz * rx + cz * ry), e2 = normalize_theta(zinv5[2] + rth);
-#endif
+    double e0, e1, e2;
+    pp_error(xi, xj, ci, si, zinv5, e0, e1, e2);
     double w00 = w[0], w01 = w[1], w02 = w[2], w11 = w[3], w12 = w[4], w22 = w[5];
-    double We0 = w00 * e0 + w01 * e1 + w02 * e2, We1 = w01 * e0 + w11 * e1 + w12 * e2, We2 = w02 * e0 + w12 * e1 + w22 * e2;
-    if (ROBUST) { double wr; const double rho = robust_rho(d.rk_pp, d.rd_pp, e0 * We0 + e1 * We1 + e2 * We2, wr);
+    double We0, We1, We2;
+    pp_info_error(e0, e1, e2, w, We0, We1, We2);
+    if (ROBUST) { double wr; const double rho = robust_rho(d.rk_pp, d.rd_pp, pp_sq_error(e0, e1, e2, We0, We1, We2), wr);
         if (role == 0 && !(fi && fj)) chi = rho;
         w00 = opaque(w00 * wr); w01 = opaque(w01 * wr); w02 = opaque(w02 * wr); w11 = opaque(w11 * wr); w12 = opaque(w12 * wr); w22 = opaque(w22 * wr);
         We0 = opaque(We0 * wr); We1 = opaque(We1 * wr); We2 = opaque(We2 * wr); }
-    else if (role == 0 && !(fi && fj)) chi = e0 * We0 + e1 * We1 + e2 * We2;
+    else if (role == 0 && !(fi && fj)) chi = pp_sq_error(e0, e1, e2, We0, We1, We2);
     if (WRITE_H) {
         const double m0 = cz * ci + sz * si, m1 = cz * si - sz * ci;
         const double bw0 = m0 * We0 - m1 * We1, bw1 = m1 * We0 + m0 * We1;      // b0.We, b1.We

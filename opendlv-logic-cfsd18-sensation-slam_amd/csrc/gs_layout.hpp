@@ -19,6 +19,7 @@ struct DevFront {
 enum ArenaPart : int { ARENA_Hpp_diag, ARENA_b_pose, ARENA_Hpp_off, ARENA_Hpl, ARENA_lm_part, ARENA_Hll_diag, ARENA_b_lm,
                        ARENA_t_Hpp_diag, ARENA_t_b_pose, ARENA_t_Hpp_off, ARENA_t_Hpl, ARENA_t_Hll_diag, ARENA_t_b_lm, ARENA_PARTS };
 constexpr int ARENA_TAIL = ARENA_t_Hpp_diag;                    // the first tail part: Sc3Args::toff[part - ARENA_TAIL]
+constexpr int LM_REC = 8;       // doubles per (wave tile, landmark) partial-sum record of lm_part: {H00, H01, H11, b0, b1, -, -, -} = one 64-byte line
 struct ArenaCounts { int64_t N, Epp, ell_len, n_groups, M, tcapN, tcapEpp, tcapEpl, tcapM; };     // base counts, then the tail capacities
 struct ArenaOffsets { int64_t at[ARENA_PARTS + 1];             // in doubles; at[ARENA_PARTS] = the whole arena
                       int64_t doubles() const { return at[ARENA_PARTS]; } };
@@ -26,7 +27,7 @@ struct ArenaOffsets { int64_t at[ARENA_PARTS + 1];             // in doubles; at
 // 6 N is even, no padding between), the partial-sum records of lm_part on a 64-byte line.  false: beyond the 32-bit offsets the
 // front assembly names every scalar by.
 inline bool arena_layout(const ArenaCounts &c, ArenaOffsets &o) {
-    const int64_t sizes[ARENA_PARTS] = {c.N * 6, c.N * 3, c.Epp * 9, c.ell_len * 6, c.n_groups * 8, c.M * 3, c.M * 2,
+    const int64_t sizes[ARENA_PARTS] = {c.N * 6, c.N * 3, c.Epp * 9, c.ell_len * 6, c.n_groups * LM_REC, c.M * 3, c.M * 2,
                                         c.tcapN * 6, c.tcapN * 3, c.tcapEpp * 9, c.tcapEpl * 6, c.tcapM * 3, c.tcapM * 2};
     o.at[0] = 0;
     for (int k = 0; k < ARENA_PARTS; ++k) { o.at[k + 1] = o.at[k] + ((sizes[k] + 1) & ~(int64_t)1);

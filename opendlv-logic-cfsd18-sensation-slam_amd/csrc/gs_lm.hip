@@ -62,7 +62,7 @@ __global__ void __launch_bounds__(256) k_lm_damp(DevGraph d, LmDev lm, int par, 
             // would read a lambda from: its diagonal is assembled as 0, H + lambda I stays singular there, and the zero pivot makes every
             // trial a rejected one — the call terminates instead of moving a vertex no measurement holds.  The guard keeps the store in bounds.)
             else if (d.n_wtiles > 0) { const int q = d.lm_grp_start[l];
-                if (q < d.lm_grp_start[l + 1]) { d.lm_part[(int64_t)q * LM_PART_REC] += lam; d.lm_part[(int64_t)q * LM_PART_REC + 2] += lam; } }
+                if (q < d.lm_grp_start[l + 1]) { d.lm_part[(int64_t)q * LM_REC] += lam; d.lm_part[(int64_t)q * LM_REC + 2] += lam; } }
             else { d.Hll_diag[l] += lam; d.Hll_diag[2 * (int64_t)d.M + l] += lam; } } }
     if (blockIdx.x == 0 && threadIdx.x == 0 && !done) {             // (fields no other workgroup of this launch reads)
         S.lambda_last = lam;

@@ -2,8 +2,8 @@
 // gs_polar_host.hpp for the tables.  A translation unit of its own, like gs_prior.hip: the kernels of gs_kernels.hip are not touched and
 // DevGraph is what it was.
 //
-// Semantics.  d = x_p^-1 * l, the landmark in the pose frame, by the expressions of edge_pl (GS_G2O_ORDER: inverse, then compose, every
-// product rounded on its own, the pose's cached cos / sin); r = sqrt(dx^2 + dy^2), beta = atan2(dy, dx).
+// Semantics.  d = x_p^-1 * l, the landmark in the pose frame, by lm_in_pose_frame (gs_edge_dev.hpp: inverse, then compose, every
+// product rounded on its own; the pose's cached cos / sin); r = sqrt(dx^2 + dy^2), beta = atan2(dy, dx).
 //   range-bearing   e = (r - z_r, normalize_theta(beta - z_beta)), Omega 2 x 2 in (range, bearing)
 //   bearing-only    the range-bearing edge with z_r = 0 and Omega = [[0, 0], [0, w]], stored as such
 // g2o's EdgeSE2PointXYBearing takes z - beta: the sign changes neither H, b nor chi2.  (g2o is not part of this project's checkers:
@@ -36,19 +36,19 @@ struct PolarQuad { double Hp[6], bp[3], W6[6], Hl[3], bl[2], s, chi, wr; };
 __device__ __forceinline__ bool polar_quad(double px, double py, double c, double s, double lx, double ly, double zr, double zb,
                                            double w00, double w01, double w11, int rk, double rd, PolarQuad &q) {
     double dx, dy;
-    side_lm_in_pose_frame(px, py, c, s, lx, ly, dx, dy);
+    lm_in_pose_frame(px, py, c, s, lx, ly, dx, dy);
     const double r2 = dx * dx + dy * dy;
     q.s = 0.0; q.chi = 0.0; q.wr = 1.0;
     if (!(r2 > 0.0)) return false;
     const double r = sqrt(r2), beta = atan2(dy, dx);
-    const double e0 = r - zr, e1 = side_normalize_theta(beta - zb);
+    const double e0 = r - zr, e1 = normalize_theta(beta - zb);
     const double j00 = dx / r, j01 = dy / r, j10 = -dy / r2, j11 = dx / r2;
     // B = Jd R^T, R^T rows (c, s), (-s, c)
     const double B0[2] = {j00 * c - j01 * s, j00 * s + j01 * c}, B1[2] = {j10 * c - j11 * s, j10 * s + j11 * c};
     const double A0[3] = {-B0[0], -B0[1], 0.0}, A1[3] = {-B1[0], -B1[1], -1.0};
     double We0 = w00 * e0 + w01 * e1, We1 = w01 * e0 + w11 * e1;
     q.s = e0 * We0 + e1 * We1;
-    q.chi = side_robust_rho(rk, rd, q.s, q.wr);
+    q.chi = robust_rho(rk, rd, q.s, q.wr);
     w00 *= q.wr; w01 *= q.wr; w11 *= q.wr; We0 *= q.wr; We1 *= q.wr;
     double WA0[3], WA1[3];
 #pragma unroll

@@ -5,7 +5,7 @@
 //   pose prior (EdgeSE2Prior)       e = vec(z^-1 o x): e_t = R_z^T (t - t_z), e_theta = normalize(theta - z_theta);  J = diag(R_z^T, 1)
 //   pose XY prior (EdgeSE2XYPrior)  e = t - z: the pose prior with z_theta = 0 and Omega in the upper-left 2 x 2, stored as such
 //   landmark prior (EdgeXYPrior)    e = l - z;  J = I
-// with the additive update of k_update.  The error is formed the way the odometry residual is (pp_incidence, GS_G2O_ORDER): the stored
+// with the additive update of k_update.  The error is formed the way the odometry residual is (pp_error, gs_edge_dev.hpp): the stored
 // inverse measurement composed with the estimate, every product rounded on its own.
 //
 // k_prior_pass: thread v < n_pv is listed pose v, thread n_pv + j listed landmark j; 256 threads per workgroup.  The thread walks its
@@ -27,7 +27,7 @@ __device__ __forceinline__ double prior_pose_record(const double *__restrict__ r
     for (int k = 0; k < PRIOR_POSE_REC; ++k) v[k] = rec[(int64_t)k * S + r];
     const double cz = v[3], sz = v[4];
     const double e0 = v[0] + (cz * x[0] - sz * x[1]), e1 = v[1] + (sz * x[0] + cz * x[1]);
-    const double e2 = side_normalize_theta(v[2] + side_normalize_theta(x[2]));
+    const double e2 = normalize_theta(v[2] + normalize_theta(x[2]));
     const double w00 = v[5], w01 = v[6], w02 = v[7], w11 = v[8], w12 = v[9], w22 = v[10];
     const double We0 = w00 * e0 + w01 * e1 + w02 * e2, We1 = w01 * e0 + w11 * e1 + w12 * e2, We2 = w02 * e0 + w12 * e1 + w22 * e2;
     if (APPLY) {

@@ -1,41 +1,11 @@
 // gs_side_dev.hpp — device functions the three side passes share (gs_prior.hip, gs_edge_mask.hip, gs_polar.hip; gfx950, wave64).
-// Included by those three files only: gs_kernels.hip and gs_lm.hip keep their own copies of the expressions restated here, so the main
-// path's code objects do not depend on this header.  Every workgroup of a side pass has 256 threads.
+// Residuals, squared errors, robust weight and angle normalisation are those of the main path: gs_edge_dev.hpp.  Every workgroup of a
+// side pass has 256 threads.
 #pragma once
 #include "gs_device.hpp"
+#include "gs_edge_dev.hpp"
 
 namespace gs {
-
-static constexpr int SIDE_LM_PART = 8;       // doubles per lm_part record (gs_kernels.hip)
-static constexpr double kSidePi = 3.14159265358979323846;
-
-__device__ __forceinline__ double side_normalize_theta(double th) {      // g2o normalize_theta, as in gs_kernels.hip
-#pragma clang fp contract(off)
-    if (th >= -kSidePi && th < kSidePi) return th;
-    const double m = floor(th / (2.0 * kSidePi));
-    th = th - m * 2.0 * kSidePi;
-    if (th >= kSidePi) th -= 2.0 * kSidePi;
-    if (th < -kSidePi) th += 2.0 * kSidePi;
-    return th;
-}
-// rho(s) and w = rho'(s) of robust_rho (gs_kernels.hip): w exactly 1 where the kernel does not act
-__device__ __forceinline__ double side_robust_rho(int kernel, double delta, double s, double &w) {
-#pragma clang fp contract(off)
-    w = 1.0;
-    if (kernel == 1) { const double d2 = delta * delta;
-        if (s > d2) { const double r = sqrt(s); w = delta / r; return 2.0 * r * delta - d2; }
-        return s; }
-    if (kernel == 2) { const double d2 = delta * delta, aux = 1.0 + s / d2; w = 1.0 / aux; return d2 * log(aux); }
-    return s;
-}
-// d = x_p^-1 * l, the landmark in the pose frame, by the expressions of edge_pl (GS_G2O_ORDER: inverse, then compose, every product
-// rounded on its own); c, s: the pose's cached cos / sin
-__device__ __forceinline__ void side_lm_in_pose_frame(double px, double py, double c, double s, double lx, double ly, double &dx, double &dy) {
-#pragma clang fp contract(off)
-    const double ix = -(c * px + s * py), iy = s * px - c * py;
-    dx = (c * lx + s * ly) + ix;
-    dy = (c * ly - s * lx) + iy;
-}
 
 // fixed-order sum over the 256 threads, the result in thread 0 (red: 4 doubles of LDS)
 __device__ __forceinline__ double side_block_sum(double v, double *red) {
@@ -85,7 +55,7 @@ __device__ __forceinline__ void side_add_lm(const DevGraph &d, int l, const doub
         if (o < d.tcapM && d.t_Hll_diag) {
             d.t_Hll_diag[o] += H[0]; d.t_Hll_diag[St + o] += H[1]; d.t_Hll_diag[2 * St + o] += H[2]; d.t_b_lm[o] += b[0]; d.t_b_lm[St + o] += b[1]; } }
     else if (d.n_wtiles > 0) { const int q0 = d.lm_grp_start[l];
-        if (q0 >= 0 && q0 < d.lm_grp_start[l + 1] && q0 < d.n_groups) { double *s = d.lm_part + (int64_t)q0 * SIDE_LM_PART;
+        if (q0 >= 0 && q0 < d.lm_grp_start[l + 1] && q0 < d.n_groups) { double *s = d.lm_part + (int64_t)q0 * LM_REC;
             s[0] += H[0]; s[1] += H[1]; s[2] += H[2]; s[3] += b[0]; s[4] += b[1]; } }
     else { const int64_t St = d.M;
         d.Hll_diag[l] += H[0]; d.Hll_diag[St + l] += H[1]; d.Hll_diag[2 * St + l] += H[2]; d.b_lm[l] += b[0]; d.b_lm[St + l] += b[1]; }

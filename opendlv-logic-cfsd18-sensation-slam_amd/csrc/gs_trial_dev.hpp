@@ -10,8 +10,6 @@
 
 namespace gs {
 
-static constexpr int LM_PART_REC = 8;   // doubles per lm_part record (gs_kernels.hip)
-
 // fixed-order sum / max over the 256 threads, the result in EVERY thread (red: 5 doubles of LDS)
 template <bool MAX> __device__ __forceinline__ double lm_block_reduce(double v, double *red) {
 #pragma unroll
@@ -43,7 +41,7 @@ template <class T> __device__ __forceinline__ T *pose_plane(const DevGraph &d, T
 template <int K> __device__ __forceinline__ void lm_slot_sum(const DevGraph &d, int l, const int (&e)[K], double (&s)[K]) {
 #pragma unroll
     for (int k = 0; k < K; ++k) s[k] = 0.0;
-    for (int q = d.lm_grp_start[l]; q < d.lm_grp_start[l + 1]; ++q) { const double *r = d.lm_part + (int64_t)q * LM_PART_REC;
+    for (int q = d.lm_grp_start[l]; q < d.lm_grp_start[l + 1]; ++q) { const double *r = d.lm_part + (int64_t)q * LM_REC;
 #pragma unroll
         for (int k = 0; k < K; ++k) s[k] += r[e[k]]; }
 }

@@ -8,7 +8,11 @@ more per tree with -Rpass-analysis=kernel-resource-usage and the Makefile's flag
     make -C <tree A>/csrc variant NAME=a && make -C <tree B>/csrc variant NAME=b
     scripts/codeobj_compare.py <tree A>/csrc/build/var_a <tree B>/csrc/build/var_b [LABEL_A LABEL_B] > profiles/<name>.txt
 
-Exit status 1 when anything differs."""
+A kernel of equal length whose differing lines each keep opcode, destination and the multiset of source operands reads COMM and counts
+as same: the compiler wrote the sources of an instruction in another order (the report names the opcodes, so that the reader sees they
+commute).  Any other difference in the code reads CODE, with the number of differing lines and whether the opcode histograms agree.
+
+Exit status 1 when anything differs beyond COMM."""
 import os
 import re
 import subprocess
@@ -36,6 +40,23 @@ def disassembly(obj, tmp):
         elif name and line.strip():
             out[name].append(line.strip())
     return out
+
+
+def parse(line):
+    """(opcode, destination, sorted source operands) of a disassembly line"""
+    op, _, rest = line.split("//")[0].strip().partition(" ")
+    args = [a.strip() for a in rest.split(",")] if rest.strip() else []
+    return op, args[:1], sorted(args[1:])
+
+
+def code_diff(a, b):
+    """how two kernels' instruction lines differ: (number of differing lines or None when the lengths differ, the opcodes of the differing
+    lines when every one of them is the same instruction with its sources in another order, else None, opcode histograms equal)"""
+    hist = sorted(parse(x)[0] for x in a) == sorted(parse(x)[0] for x in b)
+    if len(a) != len(b):
+        return None, None, hist
+    pairs = [(parse(x), parse(y)) for x, y in zip(a, b) if x != y]
+    return len(pairs), sorted({x[0] for x, _ in pairs}) if all(x == y for x, y in pairs) else None, hist
 
 
 def resources(src, include):
@@ -70,7 +91,7 @@ def main():
     with ThreadPoolExecutor(max_workers=8) as pool:
         res = dict(zip(jobs, pool.map(lambda j: resources(os.path.join(csrc[j[1]], j[0] + ".hip"), os.path.join(csrc[j[1]], "..", "..", "include")), jobs)))
     print("device code objects, gfx950: A = %s\n                             B = %s" % tuple(labels))
-    differ = 0
+    differ = n_comm = 0
     for u in units:
         with tempfile.TemporaryDirectory() as ta, tempfile.TemporaryDirectory() as tb:
             da, db = disassembly(os.path.join(dirs[0], u + ".o"), ta), disassembly(os.path.join(dirs[1], u + ".o"), tb)
@@ -82,13 +103,20 @@ def main():
             # (a device function that is called, not inlined, is a symbol of the code object without remarks of its own: its code alone is compared)
             same_res = ra.get(name) == rb.get(name) and (len(ra.get(name, {})) == len(FIELDS) or (name not in ra and name not in rb))
             r = rb.get(name) or ra.get(name) or {}
-            verdict = "same" if same_code and same_res else ("CODE" if not same_code else "RES")
-            differ += verdict != "same"
+            n_lines, comm, hist = (0, None, True) if same_code else code_diff(da.get(name, []), db.get(name, []))
+            verdict = "same" if same_code and same_res else ("RES" if same_code else "COMM" if comm and same_res else "CODE")
+            differ += verdict not in ("same", "COMM")
             print("  %-7s %6d %5s %5s %5s %7s %6s %4s  %s" % ((verdict, len(db.get(name, da.get(name, [])))) + tuple(r.get(f, "-") for f in FIELDS[:4]) +
                                                                  (r.get(FIELDS[5], "-"), r.get(FIELDS[4], "-"), name)))
-            if verdict != "same":
+            if verdict == "COMM":
+                print("          %d lines with their sources in another order: %s" % (n_lines, " ".join(comm)))
+                n_comm += 1
+            elif verdict != "same":
                 print("          A: %d instr, %s\n          B: %d instr, %s" % (len(da.get(name, [])), ra.get(name), len(db.get(name, [])), rb.get(name)))
-    print("\nverdict: %s" % ("every kernel's disassembly and resource lines are identical" if not differ else "%d kernels differ" % differ))
+                if not same_code:
+                    print("          %s lines differ, opcode histograms %s" % ("-" if n_lines is None else n_lines, "equal" if hist else "DIFFER"))
+    same_txt = "every kernel's disassembly and resource lines are identical" + (", but for %d with commuted sources (COMM)" % n_comm if n_comm else "")
+    print("\nverdict: %s" % (same_txt if not differ else "%d kernels differ" % differ))
     return 1 if differ else 0
 
 

@@ -2,7 +2,7 @@
 For one configuration (cfg4 by default): (1) the linearised system at the initial point, GPU vs oracle, block by block;
 (2) the first Gauss-Newton increment and (3) the estimates after the reference's 10 iterations (src/slam.cpp:481), pairwise
 between the GPU, the oracle's own LDL^T (track order; natural order where its fill-in fits), and the reference's vendored
-Eigen SimplicialLDLT + AMD (oracle/_ref).  GS_LIB selects an A/B build of the library (e.g. -DGS_G2O_ORDER=0).
+Eigen SimplicialLDLT + AMD (oracle/_ref).  GS_LIB selects an A/B build of the library (make variant).
 Writes gpurun_out/parity_spread_<cfg>_<tag>.json."""
 import importlib, json, os, sys, time
 import numpy as np

@@ -43,7 +43,7 @@ RB, BO = plr.RANGE_BEARING, plr.BEARING
 
 
 def device_d(px, py, th, lx, ly):
-    """d = x_p^-1 . l in the device's operation order (side_lm_in_pose_frame), in numpy: signs of zeros included"""
+    """d = x_p^-1 . l in the device's operation order (lm_in_pose_frame, gs_edge_dev.hpp), in numpy: signs of zeros included"""
     c, s = np.cos(th), np.sin(th)
     ix = -(c * px + s * py); iy = s * px - c * py
     return (c * lx + s * ly) + ix, (c * ly - s * lx) + iy

@@ -152,7 +152,7 @@ def test_census_wrap():
     for want in (6.0, -6.0, np.pi - 1e-5, -(np.pi - 1e-5), np.pi + 1e-5, -(np.pi + 1e-5), 0.0, 2 * np.pi):
         assert (np.abs(a - want) < 1e-9).any(), want
     assert ((a > np.pi) & (a < 2 * np.pi)).sum() >= 2 and ((a < -np.pi) & (a > -2 * np.pi)).sum() >= 2
-    # the device's own expression, in numpy: both branches of side_normalize_theta are taken, and the 2 pi edge gives exactly 0
+    # the device's own expression, in numpy: both branches of normalize_theta (gs_edge_dev.hpp) are taken, and the 2 pi edge gives exactly 0
     t = plr.terms(g, pol, g["pose_est"], g["lm_est"])
     raw = np.arctan2(t["d"][:, 1], t["d"][:, 0]) - pol["z"][:, 1]
     mine = np.array([at[e] for e in c["notes"]["wrap_edges"]])
