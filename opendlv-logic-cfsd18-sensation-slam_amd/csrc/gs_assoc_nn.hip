@@ -760,69 +760,58 @@ __global__ void __launch_bounds__(64) k_localize_big(LoArgs A) {
                [&](int f, int a, int b, const FrameLanes &l, int lane) __attribute__((always_inline)) { lo_pass<4>(R, A, f, a, b, l.W, l.lg, lane); });
 }
 
-void launch_assoc_nn(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, double lidar, int n_map,
-                     const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
-                     int32_t *out_idx, double *out_d2, double *out_second, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
-    if (n <= 0) return;
-    hipExtLaunchKernelGGL(k_assoc_nn, dim3((n + 255) / 256), dim3(256), 0, st, start, stop, 0, n, poses, n_poses, pose_of_obs, obs, lidar, n_map,
-                          map_xy, map_type, map_cov, pose_cov, p, out_idx, out_d2, out_second);
+void launch_assoc_nn(const ObsRef &o, const MapRef &m, double lidar, NnDev p, int32_t *out_idx, double *out_d2, double *out_second, Launch L) {
+    if (o.n <= 0) return;
+    const dim3 grid((o.n + 255) / 256), block(256);
+    if (m.cell_start) hipExtLaunchKernelGGL(k_assoc_nn_grid, grid, block, 0, L.st, L.start, L.stop, 0, o.n, o.poses, o.n_poses, o.pose_of_obs, o.obs, lidar,
+                                            m.xy, m.type, m.cov, o.pose_cov, p, grid_params_of(p.max_distance, m.buckets), m.cell_start, m.cell_items,
+                                            out_idx, out_d2, out_second);
+    else hipExtLaunchKernelGGL(k_assoc_nn, grid, block, 0, L.st, L.start, L.stop, 0, o.n, o.poses, o.n_poses, o.pose_of_obs, o.obs, lidar, m.n,
+                               m.xy, m.type, m.cov, o.pose_cov, p, out_idx, out_d2, out_second);
 }
-void launch_assoc_nn_grid(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, double lidar,
-                          const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
-                          long long buckets, const int32_t *cell_start, const int32_t *cell_items,
-                          int32_t *out_idx, double *out_d2, double *out_second, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
-    if (n <= 0) return;
-    hipExtLaunchKernelGGL(k_assoc_nn_grid, dim3((n + 255) / 256), dim3(256), 0, st, start, stop, 0, n, poses, n_poses, pose_of_obs, obs, lidar,
-                          map_xy, map_type, map_cov, pose_cov, p, grid_params_of(p.max_distance, buckets), cell_start, cell_items, out_idx, out_d2, out_second);
-}
-void launch_frame_nn(int k, const double *in, int has_pose_cov, double lidar, int n_map, const double *map_xy, const int32_t *map_type,
-                     const double *map_cov, NnDev p, double *out_z, double *out_g, int32_t *out_idx, double *out_d2, double *out_second, hipStream_t st) {
-    if (k > 0) hipLaunchKernelGGL(k_frame_nn, dim3(k), dim3(256), 0, st, k, in, has_pose_cov, lidar, n_map, map_xy, map_type, map_cov, p,
+void launch_frame_nn(int k, const double *in, int has_pose_cov, const MapRef &m, double lidar, NnDev p, double *out_z, double *out_g, int32_t *out_idx,
+                     double *out_d2, double *out_second, hipStream_t st) {
+    if (k > 0) hipLaunchKernelGGL(k_frame_nn, dim3(k), dim3(256), 0, st, k, in, has_pose_cov, lidar, m.n, m.xy, m.type, m.cov, p,
                                   out_z, out_g, out_idx, out_d2, out_second);
 }
 void launch_map_cov_gather(int n, const int64_t *src, const double *values, double *map_cov_first, hipStream_t st) {
     if (n > 0) hipLaunchKernelGGL(k_map_cov_gather, dim3((n + 255) / 256), dim3(256), 0, st, n, src, values, map_cov_first);
 }
-void launch_assign_nn(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, int n_frames, const int32_t *frame_start,
-                      double lidar, int n_map, const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
-                      long long buckets, const int32_t *cell_start, const int32_t *cell_items, int32_t *out_idx, double *out_d2, double *out_z, double *out_g,
-                      hipStream_t st, hipEvent_t start, hipEvent_t stop) {
-    if (n <= 0 || n_frames <= 0) return;
-    const int fpw = frames_per_wave(mean_frame(n, n_frames));
-    const dim3 grid((n_frames + 4 * fpw - 1) / (4 * fpw)), block(256);
-    if (cell_start) hipExtLaunchKernelGGL(k_assign_nn<true>, grid, block, 0, st, start, stop, 0, n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, fpw, lidar,
-                                          n_map, map_xy, map_type, map_cov, pose_cov, p, grid_params_of(p.max_distance, buckets), cell_start, cell_items,
-                                          out_idx, out_d2, out_z, out_g);
-    else hipExtLaunchKernelGGL(k_assign_nn<false>, grid, block, 0, st, start, stop, 0, n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, fpw, lidar,
-                               n_map, map_xy, map_type, map_cov, pose_cov, p, GridParams{}, cell_start, cell_items, out_idx, out_d2, out_z, out_g);
+void launch_assign_nn(const ObsRef &o, const MapRef &m, double lidar, NnDev p, int32_t *out_idx, double *out_d2, double *out_z, double *out_g, Launch L) {
+    if (o.n <= 0 || o.n_frames <= 0) return;
+    const int fpw = frames_per_wave(mean_frame(o.n, o.n_frames));
+    const dim3 grid((o.n_frames + 4 * fpw - 1) / (4 * fpw)), block(256);
+    if (m.cell_start) hipExtLaunchKernelGGL(k_assign_nn<true>, grid, block, 0, L.st, L.start, L.stop, 0, o.n, o.poses, o.n_poses, o.pose_of_obs, o.obs, o.n_frames,
+                                            o.frame_start, fpw, lidar, m.n, m.xy, m.type, m.cov, o.pose_cov, p, grid_params_of(p.max_distance, m.buckets),
+                                            m.cell_start, m.cell_items, out_idx, out_d2, out_z, out_g);
+    else hipExtLaunchKernelGGL(k_assign_nn<false>, grid, block, 0, L.st, L.start, L.stop, 0, o.n, o.poses, o.n_poses, o.pose_of_obs, o.obs, o.n_frames,
+                               o.frame_start, fpw, lidar, m.n, m.xy, m.type, m.cov, o.pose_cov, p, GridParams{}, m.cell_start, m.cell_items,
+                               out_idx, out_d2, out_z, out_g);
 }
-void launch_assign_opt(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, int n_frames, const int32_t *frame_start,
-                       double lidar, int n_map, const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov, NnDev p,
-                       long long buckets, const int32_t *cell_start, const int32_t *cell_items, int32_t *out_idx, double *out_d2, int32_t *out_na,
-                       double *out_z, double *out_g, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
-    if (n <= 0 || n_frames <= 0) return;
-    const AoArgs A{{n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, 1, 0, lidar, n_map, map_xy, map_cov, pose_cov, p}, map_type,
-                   cell_start ? grid_params_of(p.max_distance, buckets) : GridParams{}, cell_start, cell_items, out_idx, out_d2, out_na, out_z, out_g};
-    if (cell_start) launch_small_then_big(A, -1, k_assign_opt<true>, k_assign_opt_big<true>, st, start, stop);
-    else launch_small_then_big(A, -1, k_assign_opt<false>, k_assign_opt_big<false>, st, start, stop);
+// what the three two-kernel launchers put first in their argument block (fpw and only_large: launch_small_then_big's to set)
+static FrameArgs frame_args(const ObsRef &o, const MapRef &m, double lidar, NnDev p) {
+    return FrameArgs{o.n, o.poses, o.n_poses, o.pose_of_obs, o.obs, o.n_frames, o.frame_start, 1, 0, lidar, m.n, m.xy, m.cov, o.pose_cov, p};
 }
-void launch_joint_compat(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, int n_frames, const int32_t *frame_start,
-                         double lidar, int n_map, const double *map_xy, const double *map_cov, const double *pose_cov, NnDev p, const JcGate &gate,
-                         const int32_t *in_idx, int32_t *out_idx, double *out_j, int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable,
-                         double *out_delta, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
-    if (n_frames <= 0) return;
-    const JcArgs A{{n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, 1, 0, lidar, n_map, map_xy, map_cov, pose_cov, p}, in_idx,
-                   out_idx, out_j, out_kept, out_dropped, out_untestable, out_delta, gate};
-    launch_small_then_big(A, -1, k_joint_compat, k_joint_compat_big, st, start, stop);
+void launch_assign_opt(const ObsRef &o, const MapRef &m, double lidar, NnDev p, int32_t *out_idx, double *out_d2, int32_t *out_na, double *out_z, double *out_g,
+                       Launch L) {
+    if (o.n <= 0 || o.n_frames <= 0) return;
+    const AoArgs A{frame_args(o, m, lidar, p), m.type, m.cell_start ? grid_params_of(p.max_distance, m.buckets) : GridParams{}, m.cell_start, m.cell_items,
+                   out_idx, out_d2, out_na, out_z, out_g};
+    if (m.cell_start) launch_small_then_big(A, -1, k_assign_opt<true>, k_assign_opt_big<true>, L.st, L.start, L.stop);
+    else launch_small_then_big(A, -1, k_assign_opt<false>, k_assign_opt_big<false>, L.st, L.start, L.stop);
+}
+void launch_joint_compat(const ObsRef &o, const MapRef &m, double lidar, NnDev p, const JcGate &gate, const int32_t *in_idx, int32_t *out_idx, double *out_j,
+                         int32_t *out_kept, int32_t *out_dropped, int32_t *out_untestable, double *out_delta, Launch L) {
+    if (o.n_frames <= 0) return;
+    const JcArgs A{frame_args(o, m, lidar, p), in_idx, out_idx, out_j, out_kept, out_dropped, out_untestable, out_delta, gate};
+    launch_small_then_big(A, -1, k_joint_compat, k_joint_compat_big, L.st, L.start, L.stop);
 }
 // kernel 0 / 1 (gs_debug_localize) forces k_localize (with k_localize_big behind it for the frames above 64) / k_localize_big alone
-void launch_localize(int n, const double *poses, int n_poses, const int32_t *pose_of_obs, const double *obs, int n_frames, const int32_t *frame_start,
-                     double lidar, int n_map, const double *map_xy, const double *map_cov, const double *pose_cov, NnDev p, const LoParams &lp,
-                     const int32_t *in_idx, const LoOut &o, int kernel, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
-    if (n_frames <= 0) return;
-    const LoArgs A{{n, poses, n_poses, pose_of_obs, obs, n_frames, frame_start, 1, 0, lidar, n_map, map_xy, map_cov, pose_cov, p}, in_idx,
-                   lp.max_iterations, lp.tol_xy, lp.tol_theta, o.pose, o.cov, o.chi2, o.n_pairs, o.iterations, o.status, o.step};
-    launch_small_then_big(A, kernel, k_localize, k_localize_big, st, start, stop);
+void launch_localize(const ObsRef &o, const MapRef &m, double lidar, NnDev p, const LoParams &lp, const int32_t *in_idx, const LoOut &out, int kernel, Launch L) {
+    if (o.n_frames <= 0) return;
+    const LoArgs A{frame_args(o, m, lidar, p), in_idx, lp.max_iterations, lp.tol_xy, lp.tol_theta, out.pose, out.cov, out.chi2, out.n_pairs, out.iterations,
+                   out.status, out.step};
+    launch_small_then_big(A, kernel, k_localize, k_localize_big, L.st, L.start, L.stop);
 }
 
 }  // namespace gs

@@ -88,8 +88,8 @@ static void cand_step_enqueue(gs_graph *g, const CandRun &R, const CandLayout &L
     const int kk = k >= 0 ? k : R.cap;
     launch_cand_stage(A, g->stream, start, nullptr);
     if (kk > 0)
-        launch_assign_opt(kk, A.pose, 1, A.st_pose_of_obs, A.st_obs, 1, A.st_fs, A.lidar, GS_CAND_MAX, R.tab.xy, R.tab.type, R.tab.cov, A.pose_cov, R.nd,
-                          0, nullptr, nullptr, as_idx, as_d2, as_na, nullptr, nullptr, g->stream);
+        launch_assign_opt(ObsRef{kk, A.pose, 1, A.st_pose_of_obs, A.st_obs, 1, A.st_fs, A.pose_cov}, MapRef{GS_CAND_MAX, R.tab.xy, R.tab.type, R.tab.cov, 0, nullptr, nullptr},
+                          A.lidar, R.nd, as_idx, as_d2, as_na, nullptr, nullptr, Launch{g->stream});
     launch_cand_update(A, g->stream, nullptr, stop);
 }
 

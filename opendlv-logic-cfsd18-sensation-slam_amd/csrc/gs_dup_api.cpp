@@ -163,7 +163,7 @@ extern "C" int gs_map_merge_twins(gs_graph *g, const gs_dup_params *params, int3
     if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("map twins: ") + hipGetErrorString(e));
     if ((rc = dup_launch_error("map twins")) != GS_OK) return rc;
     if (info.n_in != n_map || info.n_out < 0 || info.n_out > n_map) return fail(GS_ERR_HIP, "map twins: the device's counters do not describe the map");
-    fe.map_n = info.n_out; fe.grid_valid = false; fe.rl_grid_valid = false;
+    fe.map_n = info.n_out; map_changed(g);
     if (out_info) *out_info = info;
     return GS_OK;
 }

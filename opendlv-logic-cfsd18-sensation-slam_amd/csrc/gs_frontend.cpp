@@ -22,35 +22,27 @@ using namespace gs;
 // Device memory of the front end lives on the handle and only ever grows: the batch calls carve a scratch arena, the
 // per-frame path has pinned staging buffers and a device-resident copy of the map.  Nothing is allocated, freed or
 // synchronised beyond the one wait for the results per call.
-namespace {
-struct Carver {   // carves the handle's grow-only arena (256-byte aligned pieces), valid until the next front-end call
-    gs_graph *g; size_t off = 0;
-    template <class T> T *get(size_t n) { T *p = (T *)(g->fe.arena + off); off += (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255; return p; }
-};
-}
-static int arena_reserve(gs_graph *g, size_t bytes) {
-    if (bytes <= g->fe.arena_bytes) return GS_OK;
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    if (g->fe.arena) { hipFree(g->fe.arena); g->fe.arena = nullptr; g->fe.arena_bytes = 0; }
-    const size_t want = bytes + bytes / 2 + 4096;
-    HIP_TRY(hipMalloc((void **)&g->fe.arena, want));
-    g->fe.arena_bytes = want;
-    return GS_OK;
-}
 static size_t padded(size_t n, size_t elem) { return (std::max<size_t>(n, 1) * elem + 255) & ~(size_t)255; }
+// what the launches left behind: a resident call's whole tail, and the end of a batch and a live call behind their one wait
+static int resident_done(gs_graph *, const char *what) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? GS_OK : fail(GS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
 namespace {
 // a batch call's device memory: the pieces it names, in the order it names them, carved from the handle's arena — whose size is the sum over
 // the same list, so the two cannot drift — and uploaded where a host array is given.  Valid until the next front-end call
 struct Staging {
     struct Piece { void **dev; const void *host; size_t bytes; };
     gs_graph *g; std::vector<Piece> pieces{};
-    // `count` elements at dev once commit() has run; host null: not uploaded (an output, scratch, or an optional input that is absent)
+    // `count` elements at dev once commit() has run; host null: not uploaded (an output or scratch)
     template <class T> void add(T *&dev, size_t count, const T *host = nullptr) { pieces.push_back(Piece{(void **)&dev, host, count * sizeof(T)}); }
+    // an input array of a view: as add, but an array the caller did not give is no piece, and dev null
+    template <class T> void input(const T *&dev, size_t count, const T *host) { dev = nullptr; if (host) pieces.push_back(Piece{(void **)&dev, host, count * sizeof(T)}); }
     int commit() {
         size_t total = 0; for (const Piece &p : pieces) total += padded(p.bytes, 1);
-        const int rc = arena_reserve(g, total); if (rc != GS_OK) return rc;
+        const int rc = arena_reserve(g, g->fe.arena, total); if (rc != GS_OK) return rc;
         size_t off = 0;
-        for (const Piece &p : pieces) { *p.dev = g->fe.arena + off; off += padded(p.bytes, 1);
+        for (const Piece &p : pieces) { *p.dev = g->fe.arena.at(off); off += padded(p.bytes, 1);
             if (p.host && p.bytes) HIP_TRY(hipMemcpyAsync(*p.dev, p.host, p.bytes, hipMemcpyHostToDevice, g->stream)); }
         return GS_OK;
     }
@@ -65,8 +57,7 @@ struct Staging {
     int finish(const char *what) {
         if (err != GS_OK) return err;
         HIP_TRY(hipStreamSynchronize(g->stream));
-        const hipError_t e = hipGetLastError();
-        return e == hipSuccess ? GS_OK : fail(GS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+        return resident_done(g, what);
     }
 };
 }
@@ -102,6 +93,57 @@ static bool grid_batch(const gs_graph *g, int n_map, bool usable = true) {
 }
 static bool grid_resident(const gs_graph *g, bool usable = true) { return usable && g->fe.map_n > 0 && g->opt.assoc_grid != 0; }
 static bool grid_live(const gs_graph *g) { return grid_batch(g, g->fe.map_n); }
+// the hashed grid of a map that is in device memory: built on the device (launch_grid_build), nothing crosses PCIe, nothing waits
+struct GridBufs { int32_t *count, *start, *cursor, *items; long long buckets; };
+static size_t grid_bytes(int n_map, long long &buckets) {
+    buckets = 4096; while (buckets < 4 * (long long)n_map) buckets <<= 1;      // a power of two >= 4 n_map: mostly empty buckets, L2-resident
+    return 3 * padded((size_t)buckets + 1, 4) + padded((size_t)n_map, 4) + 5 * 256;
+}
+static GridBufs grid_carve(char *base, int n_map, long long buckets) {
+    GridBufs b; size_t off = 0; auto take = [&](size_t bytes) { char *p = base + off; off += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return p; };
+    b.count = (int32_t *)take(((size_t)buckets + 1) * 4); b.start = (int32_t *)take(((size_t)buckets + 1) * 4);
+    b.cursor = (int32_t *)take(((size_t)buckets + 1) * 4); b.items = (int32_t *)take((size_t)n_map * 4); b.buckets = buckets;
+    return b;
+}
+// the resident map as the launchers take it: walked whole (what a launcher that searches nothing is given, too) ...
+static MapRef resident_map_whole(const gs_graph *g) { return MapRef{g->fe.map_n, g->fe.map_xy, g->fe.map_type, g->fe.map_cov, 0, nullptr, nullptr}; }
+// ... or, where `grid`, through rg — which is built here, on the device and ahead of the caller's query on the stream, when the map, its
+// size or thr (the distance its cell edge comes from) differ from what rg was last built for
+static int resident_map(gs_graph *g, gs_graph::FrontEnd::ResidentGrid &rg, bool grid, double thr, MapRef &out) {
+    const auto &fe = g->fe;
+    out = resident_map_whole(g);
+    if (!grid) return GS_OK;
+    const bool fresh = rg.valid && rg.map_n == fe.map_n && rg.thr == thr;
+    if (!fresh) { const int rc = arena_reserve(g, rg.mem, grid_bytes(fe.map_n, rg.cells)); rg.valid = false; if (rc != GS_OK) return rc; }
+    const GridBufs gb = grid_carve(rg.mem.at(0), fe.map_n, rg.cells);
+    if (!fresh) { launch_grid_build(fe.map_n, fe.map_xy, thr, rg.cells, gb.count, gb.start, gb.cursor, gb.items, g->stream);
+        rg.valid = true; rg.map_n = fe.map_n; rg.thr = thr; }
+    out.buckets = rg.cells; out.cell_start = gb.start; out.cell_items = gb.items;
+    return GS_OK;
+}
+// the resident map's cones moved or their number changed: every grid of it is stale
+void map_changed(gs_graph *g) { g->fe.grid.valid = g->fe.rl_grid.valid = false; }
+namespace {
+// a batch call's observations and map, staged beside its own pieces: add() before commit() names the host arrays the call was given (views
+// of host pointers; an array that is null there stays null on the device) and, where `grid`, the grid's memory; after commit() o and m are
+// the device views, and build_grid() enqueues the grid's build (cell edge from thr) ahead of the query
+struct BatchIo {
+    ObsRef o{}; MapRef m{}; char *grid_mem = nullptr;
+    void add(Staging &sg, const ObsRef &ho, const MapRef &hm, bool grid) {
+        o = ho; m = hm; m.buckets = 0; m.cell_start = m.cell_items = nullptr;
+        sg.input(o.poses, 3 * (size_t)o.n_poses, ho.poses); sg.input(o.pose_cov, 9 * (size_t)o.n_poses, ho.pose_cov);
+        sg.input(o.pose_of_obs, (size_t)o.n, ho.pose_of_obs); sg.input(o.obs, 4 * (size_t)o.n, ho.obs); sg.input(o.frame_start, (size_t)o.n_frames + 1, ho.frame_start);
+        sg.input(m.xy, 2 * (size_t)m.n, hm.xy); sg.input(m.type, (size_t)m.n, hm.type); sg.input(m.cov, 4 * (size_t)m.n, hm.cov);
+        if (grid) sg.add(grid_mem, grid_bytes(m.n, m.buckets));
+    }
+    void build_grid(gs_graph *g, double thr) {
+        if (!grid_mem) return;
+        const GridBufs gb = grid_carve(grid_mem, m.n, m.buckets);
+        launch_grid_build(m.n, m.xy, thr, m.buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream);
+        m.cell_start = gb.start; m.cell_items = gb.items;
+    }
+};
+}
 
 // ---- the live frame calls' staging (gs::FrameStage, layouts: gs_frame_host.hpp) ----
 static_assert(FRAME_MAX == GS_NN_FRAME_MAX, "gs_frame_host.hpp restates the frame size");
@@ -134,22 +176,16 @@ static int stage_fetch(gs_graph *g, const FrameStage &s, size_t bytes, size_t of
 static int frame_finish(gs_graph *g, const char *what) {
     HIP_TRY(hipStreamSynchronize(g->stream));
     g->fe.pin_map_busy = false;
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? GS_OK : fail(GS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    return resident_done(g, what);
 }
 void gs_frontend_release(gs_graph *g) {      // gs_destroy
     for (FrameStage *s : {&g->fe.fr_in, &g->fe.fr_out, &g->fe.ch_rec, &g->fe.rl_out, &g->fe.fo_in, &g->fe.fo_out}) s->release();
-    if (g->fe.arena) hipFree(g->fe.arena);
+    for (DevArena *a : {&g->fe.arena, &g->fe.grid.mem, &g->fe.rl_grid.mem, &g->fe.pcs, &g->fe.rl_rec, &g->fe.fo_mem}) arena_release(*a);
     if (g->fe.map_xy) hipFree(g->fe.map_xy);
     if (g->fe.map_type) hipFree(g->fe.map_type);
     if (g->fe.pin_map) hipHostFree(g->fe.pin_map);
-    if (g->fe.grid_mem) hipFree(g->fe.grid_mem);
-    if (g->fe.pcs) hipFree(g->fe.pcs);
     if (g->fe.map_cov) hipFree(g->fe.map_cov);
     if (g->fe.cov_src) hipFree(g->fe.cov_src);
-    if (g->fe.rl_rec) hipFree(g->fe.rl_rec);
-    if (g->fe.rl_grid_mem) hipFree(g->fe.rl_grid_mem);
-    if (g->fe.fo_mem) hipFree(g->fe.fo_mem);
     if (g->fe.fo_state) hipFree(g->fe.fo_state);
     if (g->fe.fo_best) hipFree(g->fe.fo_best);
     gs_cand_release(g);
@@ -161,15 +197,12 @@ extern "C" int gs_polar_to_xy_batch(gs_graph *g, int32_t n, const double *az, co
     if (!g || n < 0 || (n > 0 && (!az || !zen || !dist || !out))) return fail(GS_ERR_INVALID, "bad argument");
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n == 0) return GS_OK;
-    if ((rc = arena_reserve(g, 3 * padded(n, 8) + padded(2 * (size_t)n, 8))) != GS_OK) return rc;
-    Carver c{g}; double *a = c.get<double>(n), *z = c.get<double>(n), *d = c.get<double>(n), *o = c.get<double>(2 * (size_t)n);
-    HIP_TRY(hipMemcpyAsync(a, az, (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(z, zen, (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(d, dist, (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
+    Staging sg{g}; double *a, *z, *d, *o;
+    sg.add(a, n, az); sg.add(z, n, zen); sg.add(d, n, dist); sg.add(o, 2 * (size_t)n);
+    if ((rc = sg.commit()) != GS_OK) return rc;
     launch_polar_to_xy(n, a, z, d, g->cfg.lidar_to_cog, o, g->stream);
-    HIP_TRY(hipMemcpyAsync(out, o, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    return GS_OK;
+    sg.fetch(out, o, 2 * (size_t)n * sizeof(double));
+    return sg.finish("polar to XY");
 }
 extern "C" int gs_cone_to_global_batch(gs_graph *g, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs,
                                        const double *obs, double *out) {
@@ -177,28 +210,12 @@ extern "C" int gs_cone_to_global_batch(gs_graph *g, int32_t n, const double *pos
     for (int i = 0; i < n; ++i) if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n == 0) return GS_OK;
-    if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded(2 * (size_t)n, 8))) != GS_OK) return rc;
-    Carver c{g}; double *p = c.get<double>(3 * (size_t)npose); int32_t *po = c.get<int32_t>(n);
-    double *ob = c.get<double>(4 * (size_t)n), *o = c.get<double>(2 * (size_t)n);
-    HIP_TRY(hipMemcpyAsync(p, poses, 3 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(po, pose_of_obs, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
+    Staging sg{g}; double *p, *ob, *o; int32_t *po;
+    sg.add(p, 3 * (size_t)npose, poses); sg.add(po, n, pose_of_obs); sg.add(ob, 4 * (size_t)n, obs); sg.add(o, 2 * (size_t)n);
+    if ((rc = sg.commit()) != GS_OK) return rc;
     launch_cone_to_global(n, p, po, ob, g->cfg.lidar_to_cog, o, g->stream);
-    HIP_TRY(hipMemcpyAsync(out, o, 2 * (size_t)n * sizeof(double), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));
-    return GS_OK;
-}
-// the hashed grid of a map that is in device memory: built on the device (launch_grid_build), nothing crosses PCIe, nothing waits
-struct GridBufs { int32_t *count, *start, *cursor, *items; long long buckets; };
-static size_t grid_bytes(int n_map, long long &buckets) {
-    buckets = 4096; while (buckets < 4 * (long long)n_map) buckets <<= 1;      // a power of two >= 4 n_map: mostly empty buckets, L2-resident
-    return 3 * padded((size_t)buckets + 1, 4) + padded((size_t)n_map, 4);
-}
-static GridBufs grid_carve(char *base, int n_map, long long buckets) {
-    GridBufs b; size_t off = 0; auto take = [&](size_t bytes) { char *p = base + off; off += (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255; return p; };
-    b.count = (int32_t *)take(((size_t)buckets + 1) * 4); b.start = (int32_t *)take(((size_t)buckets + 1) * 4);
-    b.cursor = (int32_t *)take(((size_t)buckets + 1) * 4); b.items = (int32_t *)take((size_t)n_map * 4); b.buckets = buckets;
-    return b;
+    sg.fetch(out, o, 2 * (size_t)n * sizeof(double));
+    return sg.finish("cone to global");
 }
 extern "C" int gs_associate_batch(gs_graph *g, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs, const double *obs,
                                   int32_t n_map, const double *map_xy, const int32_t *map_type, double thr, double type_tol, int32_t *out) {
@@ -210,63 +227,32 @@ extern "C" int gs_associate_batch(gs_graph *g, int32_t n, const double *poses, i
     // maps beyond a few LDS tiles go through a hashed uniform grid (cell edge a hair above the threshold, so that every cone
     // within the threshold sits in the 3 x 3 cells around the query) that is BUILT ON THE DEVICE from the uploaded map; the brute-force
     // kernel stays for small maps and non-positive thresholds (grid_batch).
-    const bool grid = grid_batch(g, n_map, thr > 0.0);
-    long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
-    if ((rc = arena_reserve(g, padded(3 * (size_t)npose, 8) + padded(n, 4) + padded(4 * (size_t)n, 8) + padded(2 * (size_t)n_map, 8) +
-                               padded(n_map, 4) + padded(n, 4) + gbytes + padded(2 * (size_t)npose, 8))) != GS_OK) return rc;
-    Carver c{g}; double *p = c.get<double>(3 * (size_t)npose); int32_t *po = c.get<int32_t>(n); double *pcs = c.get<double>(2 * (size_t)npose);
-    double *ob = c.get<double>(4 * (size_t)n), *mx = c.get<double>(2 * (size_t)n_map);
-    int32_t *mt = c.get<int32_t>(n_map), *o = c.get<int32_t>(n);
-    HIP_TRY(hipMemcpyAsync(p, poses, 3 * (size_t)npose * 8, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(po, pose_of_obs, (size_t)n * 4, hipMemcpyHostToDevice, g->stream));
-    HIP_TRY(hipMemcpyAsync(ob, obs, 4 * (size_t)n * 8, hipMemcpyHostToDevice, g->stream));
-    if (n_map > 0) { HIP_TRY(hipMemcpyAsync(mx, map_xy, 2 * (size_t)n_map * 8, hipMemcpyHostToDevice, g->stream));
-                     HIP_TRY(hipMemcpyAsync(mt, map_type, (size_t)n_map * 4, hipMemcpyHostToDevice, g->stream)); }
-    if (grid) { const GridBufs gb = grid_carve(c.get<char>(gbytes), n_map, buckets);
-        launch_grid_build(n_map, mx, thr, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream);
-        launch_associate_grid_dev(n, p, po, ob, g->cfg.lidar_to_cog, mx, mt, thr, type_tol, buckets, gb.start, gb.items, o, npose, pcs, g->stream);
-    } else launch_associate(n, p, po, ob, g->cfg.lidar_to_cog, n_map, mx, mt, thr, type_tol, o, g->stream);
-    HIP_TRY(hipMemcpyAsync(out, o, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, g->stream));
-    HIP_TRY(hipStreamSynchronize(g->stream));        // the one wait of the call: the result copy
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("association: ") + hipGetErrorString(e));
-    return GS_OK;
+    Staging sg{g}; BatchIo io; double *pcs; int32_t *o;
+    io.add(sg, ObsRef{n, poses, npose, pose_of_obs, obs, 0, nullptr, nullptr}, MapRef{n_map, map_xy, map_type, nullptr, 0, nullptr, nullptr}, grid_batch(g, n_map, thr > 0.0));
+    sg.add(pcs, 2 * (size_t)npose); sg.add(o, n);
+    if ((rc = sg.commit()) != GS_OK) return rc;
+    io.build_grid(g, thr);
+    const ObsRef &ob = io.o; const MapRef &m = io.m;
+    if (m.cell_start) launch_associate_grid_dev(n, ob.poses, ob.pose_of_obs, ob.obs, g->cfg.lidar_to_cog, m.xy, m.type, thr, type_tol, m.buckets, m.cell_start, m.cell_items, o,
+                                                npose, pcs, g->stream);
+    else launch_associate(n, ob.poses, ob.pose_of_obs, ob.obs, g->cfg.lidar_to_cog, n_map, m.xy, m.type, thr, type_tol, o, g->stream);
+    sg.fetch(out, o, (size_t)n * sizeof(int32_t));
+    return sg.finish("association");                 // the one wait of the call: the result copy
 }
 // A1 batched with EVERYTHING resident: the map of gs_map_append (its grid is built on the device, once per map change or threshold),
 // poses / observations / result in device memory, asynchronous on the handle's stream (the caller waits: gs_stream_synchronize).
-static int resident_grid(gs_graph *g, double thr) {
-    auto &fe = g->fe;
-    if (fe.grid_valid && fe.grid_map_n == fe.map_n && fe.grid_thr == thr) return GS_OK;
-    long long buckets = 0; const size_t bytes = grid_bytes(fe.map_n, buckets) + 5 * 256;
-    if (bytes > fe.grid_bytes) { HIP_TRY(hipStreamSynchronize(g->stream));
-        if (fe.grid_mem) hipFree(fe.grid_mem);
-        fe.grid_mem = nullptr; fe.grid_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&fe.grid_mem, bytes + bytes / 2)); fe.grid_bytes = bytes + bytes / 2; }
-    const GridBufs gb = grid_carve(fe.grid_mem, fe.map_n, buckets);
-    launch_grid_build(fe.map_n, fe.map_xy, thr, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream);
-    fe.grid_valid = true; fe.grid_map_n = fe.map_n; fe.grid_thr = thr; fe.grid_max_cells = buckets;
-    return GS_OK;
-}
 extern "C" int gs_associate_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
                                      double thr, double type_tol, int32_t *dev_out) {
     if (!g || n < 0 || npose < 0 || (n > 0 && (!dev_poses || !dev_pose_of_obs || !dev_obs || !dev_out))) return fail(GS_ERR_INVALID, "bad argument");
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n == 0) return GS_OK;
-    auto &fe = g->fe;
-    const bool grid = grid_resident(g, thr > 0.0);
-    if (grid) { if ((rc = resident_grid(g, thr)) != GS_OK) return rc;
-        if ((size_t)npose * 2 * sizeof(double) > fe.pcs_bytes) { HIP_TRY(hipStreamSynchronize(g->stream));      // scratch for the poses' cos / sin, grow-only
-            if (fe.pcs) hipFree(fe.pcs);
-            fe.pcs = nullptr; fe.pcs_bytes = 0;
-            const size_t want = (size_t)npose * 2 * sizeof(double) * 3 / 2 + 4096;
-            HIP_TRY(hipMalloc((void **)&fe.pcs, want)); fe.pcs_bytes = want; }
-        const GridBufs gb = grid_carve(fe.grid_mem, fe.map_n, fe.grid_max_cells);
-        launch_associate_grid_dev(n, dev_poses, dev_pose_of_obs, dev_obs, g->cfg.lidar_to_cog, fe.map_xy, fe.map_type, thr, type_tol, gb.buckets, gb.start, gb.items, dev_out,
-                                  npose, fe.pcs, g->stream, g->ev_lin[0], g->ev_lin[1]);
-    } else launch_associate(n, dev_poses, dev_pose_of_obs, dev_obs, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, thr, type_tol, dev_out, g->stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("association: ") + hipGetErrorString(e));
-    return GS_OK;
+    auto &fe = g->fe; MapRef m;
+    if ((rc = resident_map(g, fe.grid, grid_resident(g, thr > 0.0), thr, m)) != GS_OK) return rc;
+    if (m.cell_start) { if ((rc = arena_reserve(g, fe.pcs, (size_t)npose * 2 * sizeof(double))) != GS_OK) return rc;      // scratch for the poses' cos / sin
+        launch_associate_grid_dev(n, dev_poses, dev_pose_of_obs, dev_obs, g->cfg.lidar_to_cog, m.xy, m.type, thr, type_tol, m.buckets, m.cell_start, m.cell_items, dev_out,
+                                  npose, (double *)fe.pcs.mem, g->stream, g->ev_lin[0], g->ev_lin[1]);
+    } else launch_associate(n, dev_poses, dev_pose_of_obs, dev_obs, g->cfg.lidar_to_cog, m.n, m.xy, m.type, thr, type_tol, dev_out, g->stream);
+    return resident_done(g, "association");
 }
 extern "C" int gs_debug_time_associate_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
                                                 const double *dev_obs, double thr, double type_tol, int32_t *dev_out, int32_t reps, double *out_ms) {
@@ -304,7 +290,7 @@ static int pin_map_reserve(gs_graph *g, size_t bytes) {
     return GS_OK;
 }
 extern "C" int gs_map_size(gs_graph *g) { return g ? g->fe.map_n : fail(GS_ERR_INVALID, "null graph"); }
-extern "C" int gs_map_clear(gs_graph *g) { if (!g) return fail(GS_ERR_INVALID, "null graph"); g->fe.map_n = 0; g->fe.grid_valid = false; g->fe.rl_grid_valid = false; return GS_OK; }
+extern "C" int gs_map_clear(gs_graph *g) { if (!g) return fail(GS_ERR_INVALID, "null graph"); g->fe.map_n = 0; map_changed(g); return GS_OK; }
 extern "C" int gs_map_append(gs_graph *g, int32_t n, const double *xy, const int32_t *type) {
     if (!g || n < 0 || (n > 0 && (!xy || !type))) return fail(GS_ERR_INVALID, "bad argument");
     int rc = ensure_device(g); if (rc != GS_OK) return rc;
@@ -320,7 +306,7 @@ extern "C" int gs_map_append(gs_graph *g, int32_t n, const double *xy, const int
     HIP_TRY(hipMemcpyAsync(g->fe.map_type + g->fe.map_n, g->fe.pin_map + bx, bt, hipMemcpyHostToDevice, g->stream));
     g->fe.pin_map_busy = true;                                      // no wait here: the next frame's launch is ordered behind the copies
     if (g->fe.map_cov) HIP_TRY(hipMemsetAsync(g->fe.map_cov + 4 * (size_t)g->fe.map_n, 0, (size_t)n * 4 * sizeof(double), g->stream));   // (also what gs_map_clear's "drops covariances" rests on)
-    g->fe.map_n += n; g->fe.grid_valid = false; g->fe.rl_grid_valid = false;
+    g->fe.map_n += n; map_changed(g);
     return GS_OK;
 }
 extern "C" int gs_map_set_xy(gs_graph *g, int32_t first, int32_t n, const double *xy) {
@@ -330,7 +316,7 @@ extern "C" int gs_map_set_xy(gs_graph *g, int32_t first, int32_t n, const double
     if (n == 0) return GS_OK;
     HIP_TRY(hipMemcpyAsync(g->fe.map_xy + 2 * (size_t)first, xy, (size_t)n * 2 * sizeof(double), hipMemcpyHostToDevice, g->stream));
     HIP_TRY(hipStreamSynchronize(g->stream));                       // pageable source: the caller's buffer is free on return
-    g->fe.pin_map_busy = false; g->fe.grid_valid = false; g->fe.rl_grid_valid = false;
+    g->fe.pin_map_busy = false; map_changed(g);
     return GS_OK;
 }
 extern "C" int gs_frame_frontend(gs_graph *g, const double pose[3], const double *obs, int32_t k, double thr, double type_tol,
@@ -431,9 +417,7 @@ extern "C" int gs_map_set_cov_from_marginals(gs_graph *g, int32_t first, int32_t
     launch_map_cov_gather(n, fe.cov_src, g->marg.d_out, fe.map_cov + 4 * (size_t)first, g->stream);      // device to device: the values never visit the host
     HIP_TRY(hipStreamSynchronize(g->stream));                       // (src is a host temporary)
     g->fe.pin_map_busy = false;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("map covariances from marginals: ") + hipGetErrorString(e));
-    return GS_OK;
+    return resident_done(g, "map covariances from marginals");
 }
 extern "C" int gs_associate_nn_batch(gs_graph *g, int32_t n, const double *poses, int32_t npose, const int32_t *pose_of_obs, const double *obs,
                                      int32_t n_map, const double *map_xy, const int32_t *map_type, const double *map_cov, const double *pose_cov,
@@ -444,18 +428,12 @@ extern "C" int gs_associate_nn_batch(gs_graph *g, int32_t n, const double *poses
     for (int i = 0; i < n; ++i) if (pose_of_obs[i] < 0 || pose_of_obs[i] >= npose) return fail(GS_ERR_INVALID, "pose_of_obs out of range");
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n == 0) return GS_OK;
-    const bool grid = grid_batch(g, n_map);
-    long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
-    Staging sg{g}; double *p, *pcv, *ob, *mx, *mc, *od, *os; int32_t *po, *mt, *o; char *gm;
-    sg.add(p, 3 * (size_t)npose, poses); sg.add(pcv, 9 * (size_t)npose, pose_cov); sg.add(po, n, pose_of_obs); sg.add(ob, 4 * (size_t)n, obs);
-    sg.add(mx, 2 * (size_t)n_map, map_xy); sg.add(mt, n_map, map_type); sg.add(mc, 4 * (size_t)n_map, map_cov);
-    sg.add(o, n); sg.add(od, n); sg.add(os, n); sg.add(gm, gbytes);
+    Staging sg{g}; BatchIo io; double *od, *os; int32_t *o;
+    io.add(sg, ObsRef{n, poses, npose, pose_of_obs, obs, 0, nullptr, pose_cov}, MapRef{n_map, map_xy, map_type, map_cov, 0, nullptr, nullptr}, grid_batch(g, n_map));
+    sg.add(o, n); sg.add(od, n); sg.add(os, n);
     if ((rc = sg.commit()) != GS_OK) return rc;
-    const double *dmc = map_cov ? mc : nullptr, *dpc = pose_cov ? pcv : nullptr;
-    if (grid) { const GridBufs gb = grid_carve(gm, n_map, buckets);
-        launch_grid_build(n_map, mx, nd.max_distance, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream);
-        launch_assoc_nn_grid(n, p, npose, po, ob, g->cfg.lidar_to_cog, mx, mt, dmc, dpc, nd, buckets, gb.start, gb.items, o, od, os, g->stream);
-    } else launch_assoc_nn(n, p, npose, po, ob, g->cfg.lidar_to_cog, n_map, mx, mt, dmc, dpc, nd, o, od, os, g->stream);
+    io.build_grid(g, nd.max_distance);
+    launch_assoc_nn(io.o, io.m, g->cfg.lidar_to_cog, nd, o, od, os, Launch{g->stream});
     sg.fetch(out, o, (size_t)n * sizeof(int32_t)); sg.fetch(out_d2, od, (size_t)n * sizeof(double)); sg.fetch(out_second, os, (size_t)n * sizeof(double));
     return sg.finish("association (nn)");
 }
@@ -466,17 +444,10 @@ extern "C" int gs_associate_nn_resident(gs_graph *g, int32_t n, const double *de
     if ((rc = dev_obs_aligned(dev_obs)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n == 0) return GS_OK;
-    auto &fe = g->fe;
-    const bool grid = grid_resident(g);
-    if (grid) { if ((rc = resident_grid(g, nd.max_distance)) != GS_OK) return rc;
-        const GridBufs gb = grid_carve(fe.grid_mem, fe.map_n, fe.grid_max_cells);
-        launch_assoc_nn_grid(n, dev_poses, npose, dev_pose_of_obs, dev_obs, g->cfg.lidar_to_cog, fe.map_xy, fe.map_type, fe.map_cov, dev_pose_cov, nd,
-                             gb.buckets, gb.start, gb.items, dev_out, dev_out_d2, dev_out_second, g->stream, g->ev_lin[0], g->ev_lin[1]);
-    } else launch_assoc_nn(n, dev_poses, npose, dev_pose_of_obs, dev_obs, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, fe.map_cov, dev_pose_cov, nd,
-                           dev_out, dev_out_d2, dev_out_second, g->stream, g->ev_lin[0], g->ev_lin[1]);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("association (nn): ") + hipGetErrorString(e));
-    return GS_OK;
+    MapRef m; if ((rc = resident_map(g, g->fe.grid, grid_resident(g), nd.max_distance, m)) != GS_OK) return rc;
+    launch_assoc_nn(ObsRef{n, dev_poses, npose, dev_pose_of_obs, dev_obs, 0, nullptr, dev_pose_cov}, m, g->cfg.lidar_to_cog, nd, dev_out, dev_out_d2, dev_out_second,
+                    Launch{g->stream, g->ev_lin[0], g->ev_lin[1]});
+    return resident_done(g, "association (nn)");
 }
 extern "C" int gs_debug_time_associate_nn_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
                                                    const double *dev_obs, const double *dev_pose_cov, const gs_nn_params *params, int32_t *dev_out,
@@ -498,8 +469,8 @@ extern "C" int gs_frame_frontend_nn(gs_graph *g, const double pose[3], const dou
     if (pose_cov) std::memcpy(pi + L.cov, pose_cov, 9 * sizeof(double)); else std::memset(pi + L.cov, 0, 9 * sizeof(double));
     std::memcpy(pi + L.obs, obs, 4 * (size_t)k * sizeof(double));
     if ((rc = stage_send(g, fe.fr_in, L.in_bytes)) != GS_OK) return rc;
-    launch_frame_nn(k, (const double *)fe.fr_in.dev, pose_cov ? 1 : 0, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, fe.map_cov, nd, (double *)(d + L.z),
-                    (double *)(d + L.g), (int32_t *)(d + L.idx), (double *)(d + L.d2), (double *)(d + L.second), g->stream);
+    launch_frame_nn(k, (const double *)fe.fr_in.dev, pose_cov ? 1 : 0, resident_map_whole(g), g->cfg.lidar_to_cog, nd,
+                    (double *)(d + L.z), (double *)(d + L.g), (int32_t *)(d + L.idx), (double *)(d + L.d2), (double *)(d + L.second), g->stream);
     if ((rc = stage_fetch(g, fe.fr_out, L.out_bytes)) != GS_OK) return rc;
     if ((rc = frame_finish(g, "association (nn)")) != GS_OK) return rc;
     const char *po = fe.fr_out.pin; const size_t bz = 2 * (size_t)k * sizeof(double), bd = (size_t)k * sizeof(double);
@@ -541,23 +512,13 @@ static int assign_batch(gs_graph *g, bool opt, int32_t n, const double *poses, i
     if ((rc = frame_inputs_check(n, npose, pose_of_obs, n_frames, frame_start, nullptr, n_map, false)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n == 0) return GS_OK;
-    const bool grid = grid_batch(g, n_map);
-    long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
-    Staging sg{g}; double *p, *pcv, *ob, *mx, *mc, *od; int32_t *po, *fs, *mt, *o, *ona = nullptr; char *gm;
-    sg.add(p, 3 * (size_t)npose, poses); sg.add(pcv, 9 * (size_t)npose, pose_cov); sg.add(po, n, pose_of_obs); sg.add(ob, 4 * (size_t)n, obs);
-    sg.add(fs, (size_t)n_frames + 1, frame_start);
-    sg.add(mx, 2 * (size_t)n_map, map_xy); sg.add(mt, n_map, map_type); sg.add(mc, 4 * (size_t)n_map, map_cov);
+    Staging sg{g}; BatchIo io; double *od; int32_t *o, *ona = nullptr;
+    io.add(sg, ObsRef{n, poses, npose, pose_of_obs, obs, n_frames, frame_start, pose_cov}, MapRef{n_map, map_xy, map_type, map_cov, 0, nullptr, nullptr}, grid_batch(g, n_map));
     sg.add(o, n); sg.add(od, n); if (opt) sg.add(ona, n);
-    sg.add(gm, gbytes);
     if ((rc = sg.commit()) != GS_OK) return rc;
-    const double *dmc = map_cov ? mc : nullptr, *dpc = pose_cov ? pcv : nullptr;
-    GridBufs gb{};
-    if (grid) { gb = grid_carve(gm, n_map, buckets);
-        launch_grid_build(n_map, mx, nd.max_distance, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream); }
-    if (opt) launch_assign_opt(n, p, npose, po, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, mt, dmc, dpc, nd, buckets, grid ? gb.start : nullptr,
-                               grid ? gb.items : nullptr, o, od, ona, nullptr, nullptr, g->stream);
-    else launch_assign_nn(n, p, npose, po, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, mt, dmc, dpc, nd, buckets, grid ? gb.start : nullptr, grid ? gb.items : nullptr,
-                          o, od, nullptr, nullptr, g->stream);
+    io.build_grid(g, nd.max_distance);
+    if (opt) launch_assign_opt(io.o, io.m, g->cfg.lidar_to_cog, nd, o, od, ona, nullptr, nullptr, Launch{g->stream});
+    else launch_assign_nn(io.o, io.m, g->cfg.lidar_to_cog, nd, o, od, nullptr, nullptr, Launch{g->stream});
     sg.fetch(out, o, (size_t)n * sizeof(int32_t)); sg.fetch(out_d2, od, (size_t)n * sizeof(double)); sg.fetch(out_na, ona, (size_t)n * sizeof(int32_t));
     return sg.finish("assignment (nn)");
 }
@@ -571,18 +532,13 @@ extern "C" int gs_assign_opt_batch(gs_graph *g, int32_t n, const double *poses, 
                                    const double *map_cov, const double *pose_cov, const gs_nn_params *params, int32_t *out, double *out_d2, int32_t *out_na) {
     return assign_batch(g, true, n, poses, npose, pose_of_obs, obs, n_frames, frame_start, n_map, map_xy, map_type, map_cov, pose_cov, params, out, out_d2, out_na);
 }
-// the resident map through either search: the launch both the resident and the frame call end in
-static int assign_resident_launch(gs_graph *g, bool opt, bool grid, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
-                                  int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov, const NnDev &nd, int32_t *dev_out, double *dev_out_d2,
-                                  int32_t *dev_out_na, double *dev_z, double *dev_g) {
-    auto &fe = g->fe; GridBufs gb{}; int rc;
-    if (grid) { if ((rc = resident_grid(g, nd.max_distance)) != GS_OK) return rc;
-        gb = grid_carve(fe.grid_mem, fe.map_n, fe.grid_max_cells); }
-    if (opt) launch_assign_opt(n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, fe.map_cov,
-                               dev_pose_cov, nd, gb.buckets, grid ? gb.start : nullptr, grid ? gb.items : nullptr, dev_out, dev_out_d2, dev_out_na, dev_z, dev_g,
-                               g->stream, g->ev_lin[0], g->ev_lin[1]);
-    else launch_assign_nn(n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, fe.map_cov,
-                          dev_pose_cov, nd, gb.buckets, grid ? gb.start : nullptr, grid ? gb.items : nullptr, dev_out, dev_out_d2, dev_z, dev_g, g->stream, g->ev_lin[0], g->ev_lin[1]);
+// the resident map through either search (its grid built first where it is stale): the launch both the resident and the frame call end in
+static int assign_resident_launch(gs_graph *g, bool opt, bool grid, const ObsRef &o, const NnDev &nd, int32_t *dev_out, double *dev_out_d2, int32_t *dev_out_na,
+                                  double *dev_z, double *dev_g) {
+    MapRef m; const int rc = resident_map(g, g->fe.grid, grid, nd.max_distance, m); if (rc != GS_OK) return rc;
+    const Launch L{g->stream, g->ev_lin[0], g->ev_lin[1]};
+    if (opt) launch_assign_opt(o, m, g->cfg.lidar_to_cog, nd, dev_out, dev_out_d2, dev_out_na, dev_z, dev_g, L);
+    else launch_assign_nn(o, m, g->cfg.lidar_to_cog, nd, dev_out, dev_out_d2, dev_z, dev_g, L);
     return GS_OK;
 }
 static int assign_resident(gs_graph *g, bool opt, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
@@ -594,11 +550,9 @@ static int assign_resident(gs_graph *g, bool opt, int32_t n, const double *dev_p
     if ((rc = dev_obs_aligned(dev_obs)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n == 0 || n_frames == 0) return GS_OK;
-    if ((rc = assign_resident_launch(g, opt, grid_resident(g), n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov, nd, dev_out, dev_out_d2,
-                                     dev_out_na, nullptr, nullptr)) != GS_OK) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("assignment (nn): ") + hipGetErrorString(e));
-    return GS_OK;
+    if ((rc = assign_resident_launch(g, opt, grid_resident(g), ObsRef{n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov}, nd,
+                                     dev_out, dev_out_d2, dev_out_na, nullptr, nullptr)) != GS_OK) return rc;
+    return resident_done(g, "assignment (nn)");
 }
 extern "C" int gs_assign_nn_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs, const double *dev_obs,
                                      int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov, const gs_nn_params *params,
@@ -677,13 +631,11 @@ extern "C" int gs_joint_compat_batch(gs_graph *g, int32_t n, const double *poses
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n_frames == 0) return GS_OK;
     const size_t nf = (size_t)n_frames;
-    Staging sg{g}; double *p, *pcv, *ob, *mx, *mc, *oj, *odl; int32_t *po, *ii, *fs, *o, *ok, *od, *ou;
-    sg.add(p, 3 * (size_t)npose, poses); sg.add(pcv, 9 * (size_t)npose, pose_cov); sg.add(po, n, pose_of_obs); sg.add(ob, 4 * (size_t)n, obs);
-    sg.add(ii, n, in_index); sg.add(fs, nf + 1, frame_start); sg.add(mx, 2 * (size_t)n_map, map_xy); sg.add(mc, 4 * (size_t)n_map, map_cov);
-    sg.add(o, n); sg.add(oj, nf); sg.add(odl, 3 * nf); sg.add(ok, nf); sg.add(od, nf); sg.add(ou, nf);
+    Staging sg{g}; BatchIo io; double *oj, *odl; int32_t *ii, *o, *ok, *od, *ou;
+    io.add(sg, ObsRef{n, poses, npose, pose_of_obs, obs, n_frames, frame_start, pose_cov}, MapRef{n_map, map_xy, nullptr, map_cov, 0, nullptr, nullptr}, false);
+    sg.add(ii, n, in_index); sg.add(o, n); sg.add(oj, nf); sg.add(odl, 3 * nf); sg.add(ok, nf); sg.add(od, nf); sg.add(ou, nf);
     if ((rc = sg.commit()) != GS_OK) return rc;
-    launch_joint_compat(n, p, npose, po, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, map_cov ? mc : nullptr, pose_cov ? pcv : nullptr, nd, gt,
-                        ii, o, oj, ok, od, ou, odl, g->stream);
+    launch_joint_compat(io.o, io.m, g->cfg.lidar_to_cog, nd, gt, ii, o, oj, ok, od, ou, odl, Launch{g->stream});
     sg.fetch(out, o, (size_t)n * sizeof(int32_t)); sg.fetch(out_j, oj, nf * sizeof(double)); sg.fetch(out_kept, ok, nf * sizeof(int32_t));
     sg.fetch(out_dropped, od, nf * sizeof(int32_t)); sg.fetch(out_untestable, ou, nf * sizeof(int32_t)); sg.fetch(out_delta, odl, 3 * nf * sizeof(double));
     return sg.finish("joint compatibility");
@@ -699,12 +651,9 @@ extern "C" int gs_joint_compat_resident(gs_graph *g, int32_t n, const double *de
     if ((rc = dev_obs_aligned(dev_obs)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n_frames == 0) return GS_OK;
-    auto &fe = g->fe;
-    launch_joint_compat(n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_cov, dev_pose_cov,
-                        nd, gt, dev_in_index, dev_out, dev_out_j, dev_out_kept, dev_out_dropped, dev_out_untestable, dev_out_delta, g->stream, g->ev_lin[0], g->ev_lin[1]);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("joint compatibility: ") + hipGetErrorString(e));
-    return GS_OK;
+    launch_joint_compat(ObsRef{n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov}, resident_map_whole(g), g->cfg.lidar_to_cog, nd, gt, dev_in_index,
+                        dev_out, dev_out_j, dev_out_kept, dev_out_dropped, dev_out_untestable, dev_out_delta, Launch{g->stream, g->ev_lin[0], g->ev_lin[1]});
+    return resident_done(g, "joint compatibility");
 }
 extern "C" int gs_debug_time_joint_compat_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
                                                    const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov,
@@ -749,13 +698,11 @@ extern "C" int gs_localize_batch(gs_graph *g, int32_t n, const double *poses, in
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n_frames == 0) return GS_OK;
     const size_t nf = (size_t)n_frames;
-    Staging sg{g}; double *p, *pcv, *ob, *mx, *mc, *op, *oc, *ox; int32_t *po, *ii, *fs, *on, *oi, *os;
-    sg.add(p, 3 * (size_t)npose, poses); sg.add(pcv, 9 * (size_t)npose, pose_cov); sg.add(po, n, pose_of_obs); sg.add(ob, 4 * (size_t)n, obs);
-    sg.add(ii, n, in_index); sg.add(fs, nf + 1, frame_start); sg.add(mx, 2 * (size_t)n_map, map_xy); sg.add(mc, 4 * (size_t)n_map, map_cov);
-    sg.add(op, 3 * nf); sg.add(oc, 9 * nf); sg.add(ox, nf); sg.add(on, nf); sg.add(oi, nf); sg.add(os, nf);
+    Staging sg{g}; BatchIo io; double *op, *oc, *ox; int32_t *ii, *on, *oi, *os;
+    io.add(sg, ObsRef{n, poses, npose, pose_of_obs, obs, n_frames, frame_start, pose_cov}, MapRef{n_map, map_xy, nullptr, map_cov, 0, nullptr, nullptr}, false);
+    sg.add(ii, n, in_index); sg.add(op, 3 * nf); sg.add(oc, 9 * nf); sg.add(ox, nf); sg.add(on, nf); sg.add(oi, nf); sg.add(os, nf);
     if ((rc = sg.commit()) != GS_OK) return rc;
-    launch_localize(n, p, npose, po, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, map_cov ? mc : nullptr, pose_cov ? pcv : nullptr, nd, lp, ii,
-                    LoOut{op, oc, ox, on, oi, os, nullptr}, g->fe.lo_kernel, g->stream);
+    launch_localize(io.o, io.m, g->cfg.lidar_to_cog, nd, lp, ii, LoOut{op, oc, ox, on, oi, os, nullptr}, g->fe.lo_kernel, Launch{g->stream});
     sg.fetch(out_pose, op, 3 * nf * sizeof(double)); sg.fetch(out_cov, oc, 9 * nf * sizeof(double)); sg.fetch(out_chi2, ox, nf * sizeof(double));
     sg.fetch(out_pairs, on, nf * sizeof(int32_t)); sg.fetch(out_iters, oi, nf * sizeof(int32_t)); sg.fetch(out_status, os, nf * sizeof(int32_t));
     return sg.finish("frame localisation");
@@ -772,12 +719,10 @@ extern "C" int gs_localize_resident(gs_graph *g, int32_t n, const double *dev_po
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n_frames == 0) return GS_OK;
     auto &fe = g->fe;
-    launch_localize(n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_cov, dev_pose_cov,
-                    nd, lp, dev_in_index, LoOut{dev_out_pose, dev_out_cov, dev_out_chi2, dev_out_pairs, dev_out_iters, dev_out_status, fe.lo_step}, fe.lo_kernel,
-                    g->stream, g->ev_lin[0], g->ev_lin[1]);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("frame localisation: ") + hipGetErrorString(e));
-    return GS_OK;
+    launch_localize(ObsRef{n, dev_poses, npose, dev_pose_of_obs, dev_obs, n_frames, dev_frame_start, dev_pose_cov}, resident_map_whole(g), g->cfg.lidar_to_cog, nd, lp, dev_in_index,
+                    LoOut{dev_out_pose, dev_out_cov, dev_out_chi2, dev_out_pairs, dev_out_iters, dev_out_status, fe.lo_step}, fe.lo_kernel,
+                    Launch{g->stream, g->ev_lin[0], g->ev_lin[1]});
+    return resident_done(g, "frame localisation");
 }
 extern "C" int gs_debug_time_localize_resident(gs_graph *g, int32_t n, const double *dev_poses, int32_t npose, const int32_t *dev_pose_of_obs,
                                                const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const double *dev_pose_cov,
@@ -824,55 +769,31 @@ extern "C" int gs_relocalize_batch(gs_graph *g, int32_t n, const double *obs, in
     if ((rc = frame_start_check(n, n_frames, frame_start)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n_frames == 0) return GS_OK;
-    const bool grid = grid_batch(g, n_map);
     const size_t nf = (size_t)n_frames;
     int slice = 0; const int n_slices = reloc_slices(n_frames, n_map, g->fe.rl_slice, slice);
-    long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
-    Staging sg{g}; double *ob, *mx, *op, *osp, *oc, *oe; int32_t *fs, *mt, *osd, *ocn, *osc, *ost, *oi; long long *ons; char *rec, *gm;
-    sg.add(ob, 4 * (size_t)n, obs); sg.add(fs, nf + 1, frame_start); sg.add(mx, 2 * (size_t)n_map, map_xy); sg.add(mt, n_map, map_type);
+    Staging sg{g}; BatchIo io; double *op, *osp, *oc, *oe; int32_t *osd, *ocn, *osc, *ost, *oi; long long *ons; char *rec;
+    io.add(sg, ObsRef{n, nullptr, 0, nullptr, obs, n_frames, frame_start, nullptr}, MapRef{n_map, map_xy, map_type, nullptr, 0, nullptr, nullptr}, grid_batch(g, n_map));
     sg.add(rec, reloc_rec_bytes(n_frames, n_slices)); sg.add(op, 3 * nf); sg.add(osp, 3 * nf); sg.add(oc, nf); sg.add(ons, nf);
-    sg.add(osd, 4 * nf); sg.add(ocn, nf); sg.add(osc, nf); sg.add(ost, nf); sg.add(oi, n); sg.add(oe, n); sg.add(gm, gbytes);
+    sg.add(osd, 4 * nf); sg.add(ocn, nf); sg.add(osc, nf); sg.add(ost, nf); sg.add(oi, n); sg.add(oe, n);
     if ((rc = sg.commit()) != GS_OK) return rc;
-    GridBufs gb{};
-    if (grid) { gb = grid_carve(gm, n_map, buckets);
-        launch_grid_build(n_map, mx, rd.inlier_radius, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream); }
+    io.build_grid(g, rd.inlier_radius);
     const bool second = out_second_count || out_second_pose;
-    launch_relocalize(n, ob, n_frames, fs, g->cfg.lidar_to_cog, n_map, mx, mt, rd, buckets, grid ? gb.start : nullptr, grid ? gb.items : nullptr, slice, n_slices,
-                      (RlRec *)rec, RlOut{op, oc, ocn, osd, second ? osc : nullptr, second ? osp : nullptr, ons, ost, oi, oe}, nullptr, nullptr, g->stream);
+    launch_relocalize(io.o, io.m, g->cfg.lidar_to_cog, rd, slice, n_slices, (RlRec *)rec, RlOut{op, oc, ocn, osd, second ? osc : nullptr, second ? osp : nullptr, ons, ost, oi, oe},
+                      nullptr, nullptr, Launch{g->stream});
     sg.fetch(out_pose, op, 3 * nf * sizeof(double)); sg.fetch(out_count, ocn, nf * sizeof(int32_t)); sg.fetch(out_cost, oc, nf * sizeof(double));
     sg.fetch(out_seed, osd, 4 * nf * sizeof(int32_t)); sg.fetch(out_second_count, osc, nf * sizeof(int32_t)); sg.fetch(out_second_pose, osp, 3 * nf * sizeof(double));
     sg.fetch(out_n_seeds, ons, nf * sizeof(int64_t)); sg.fetch(out_status, ost, nf * sizeof(int32_t)); sg.fetch(out_index, oi, (size_t)n * sizeof(int32_t));
     sg.fetch(out_e2, oe, (size_t)n * sizeof(double));
     return sg.finish("relocalisation");
 }
-// the resident map's second grid (cell edge from inlier_radius), built on the device once per map change or radius: resident_grid's twin
-static int reloc_grid(gs_graph *g, double thr) {
+// the search against the resident map through either scoring search (relocalisation's own grid, built first where it is stale): what the
+// resident and the frame call end in.  o's pose fields are not read
+static int reloc_resident_launch(gs_graph *g, bool grid, const ObsRef &o, const RlDev &rd, const RlOut &out, double *chain_pose, int32_t *chain_frame_end) {
     auto &fe = g->fe;
-    if (fe.rl_grid_valid && fe.rl_grid_map_n == fe.map_n && fe.rl_grid_thr == thr) return GS_OK;
-    long long buckets = 0; const size_t bytes = grid_bytes(fe.map_n, buckets) + 5 * 256;
-    if (bytes > fe.rl_grid_bytes) { HIP_TRY(hipStreamSynchronize(g->stream));
-        if (fe.rl_grid_mem) hipFree(fe.rl_grid_mem);
-        fe.rl_grid_mem = nullptr; fe.rl_grid_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&fe.rl_grid_mem, bytes + bytes / 2)); fe.rl_grid_bytes = bytes + bytes / 2; }
-    const GridBufs gb = grid_carve(fe.rl_grid_mem, fe.map_n, buckets);
-    launch_grid_build(fe.map_n, fe.map_xy, thr, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream);
-    fe.rl_grid_valid = true; fe.rl_grid_map_n = fe.map_n; fe.rl_grid_thr = thr; fe.rl_grid_cells = buckets;
-    return GS_OK;
-}
-// the search against the resident map through either scoring search: what the resident and the frame call end in
-static int reloc_resident_launch(gs_graph *g, bool grid, int32_t n, const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start, const RlDev &rd,
-                                 const RlOut &o, double *chain_pose, int32_t *chain_frame_end) {
-    auto &fe = g->fe; int rc; GridBufs gb{};
-    int slice = 0; const int n_slices = reloc_slices(n_frames, fe.map_n, fe.rl_slice, slice);
-    const size_t bytes = reloc_rec_bytes(n_frames, n_slices);
-    if (bytes > fe.rl_rec_bytes) { HIP_TRY(hipStreamSynchronize(g->stream));   // grow-only
-        if (fe.rl_rec) hipFree(fe.rl_rec);
-        fe.rl_rec = nullptr; fe.rl_rec_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&fe.rl_rec, bytes + bytes / 2)); fe.rl_rec_bytes = bytes + bytes / 2; }
-    if (grid) { if ((rc = reloc_grid(g, rd.inlier_radius)) != GS_OK) return rc;
-        gb = grid_carve(fe.rl_grid_mem, fe.map_n, fe.rl_grid_cells); }
-    launch_relocalize(n, dev_obs, n_frames, dev_frame_start, g->cfg.lidar_to_cog, fe.map_n, fe.map_xy, fe.map_type, rd, gb.buckets, grid ? gb.start : nullptr,
-                      grid ? gb.items : nullptr, slice, n_slices, (RlRec *)fe.rl_rec, o, chain_pose, chain_frame_end, g->stream, g->ev_lin[0], g->ev_lin[1]);
+    int slice = 0; const int n_slices = reloc_slices(o.n_frames, fe.map_n, fe.rl_slice, slice);
+    int rc = arena_reserve(g, fe.rl_rec, reloc_rec_bytes(o.n_frames, n_slices)); if (rc != GS_OK) return rc;
+    MapRef m; if ((rc = resident_map(g, fe.rl_grid, grid, rd.inlier_radius, m)) != GS_OK) return rc;
+    launch_relocalize(o, m, g->cfg.lidar_to_cog, rd, slice, n_slices, (RlRec *)fe.rl_rec.mem, out, chain_pose, chain_frame_end, Launch{g->stream, g->ev_lin[0], g->ev_lin[1]});
     return GS_OK;
 }
 extern "C" int gs_relocalize_resident(gs_graph *g, int32_t n, const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start,
@@ -884,12 +805,10 @@ extern "C" int gs_relocalize_resident(gs_graph *g, int32_t n, const double *dev_
     if ((rc = dev_obs_aligned(dev_obs)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     if (n_frames == 0) return GS_OK;
-    if ((rc = reloc_resident_launch(g, grid_resident(g), n, dev_obs, n_frames, dev_frame_start, rd,
+    if ((rc = reloc_resident_launch(g, grid_resident(g), ObsRef{n, nullptr, 0, nullptr, dev_obs, n_frames, dev_frame_start, nullptr}, rd,
                                     RlOut{dev_out_pose, dev_out_cost, dev_out_count, dev_out_seed, dev_out_second_count, dev_out_second_pose, (long long *)dev_out_n_seeds,
                                           dev_out_status, dev_out_index, dev_out_e2}, nullptr, nullptr)) != GS_OK) return rc;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("relocalisation: ") + hipGetErrorString(e));
-    return GS_OK;
+    return resident_done(g, "relocalisation");
 }
 extern "C" int gs_debug_time_relocalize_resident(gs_graph *g, int32_t n, const double *dev_obs, int32_t n_frames, const int32_t *dev_frame_start,
                                                  const gs_reloc_params *params, double *dev_out_pose, int32_t *dev_out_count, double *dev_out_cost,
@@ -987,18 +906,19 @@ static int frame_chain_run(gs_graph *g, const FrameIn &f, const Chain &c, const 
     double *d_pose = (double *)(di + L.pose); const double *d_cov = f.pose_cov ? (const double *)(di + L.cov) : nullptr, *d_obs = (const double *)(di + L.obs);
     int32_t *d_fs = (int32_t *)(di + L.frame_start), *d_idx = (int32_t *)(dv + L.idx); const int32_t *d_po = (const int32_t *)(di + L.pose_of_obs);
     const bool grid = grid_live(g); const double lidar = g->cfg.lidar_to_cog;
+    const ObsRef o{k, d_pose, 1, d_po, d_obs, 1, d_fs, d_cov};       // the frame as every launcher of the chain takes it
     if (c.search) { RelocRec *r = (RelocRec *)fe.rl_out.dev;
-        if ((rc = reloc_resident_launch(g, grid, k, d_obs, 1, d_fs, *c.search,
+        if ((rc = reloc_resident_launch(g, grid, o, *c.search,
                                         RlOut{r->pose, &r->cost, &r->count, r->seed, c.second ? &r->second_count : nullptr, c.second ? r->second_pose : nullptr,
                                               &r->n_seeds, &r->status, r->index, r->e2}, d_pose, d_fs + 1)) != GS_OK) return rc;
         if ((rc = stage_fetch(g, fe.rl_out, sizeof(RelocRec))) != GS_OK) return rc; }
-    if ((rc = assign_resident_launch(g, c.opt, grid, k, d_pose, 1, d_po, d_obs, 1, d_fs, d_cov, c.nd, d_idx, (double *)(dv + L.d2),
-                                     c.opt ? (int32_t *)(dv + L.na) : nullptr, (double *)(dv + L.z), (double *)(dv + L.g))) != GS_OK) return rc;
+    if ((rc = assign_resident_launch(g, c.opt, grid, o, c.nd, d_idx, (double *)(dv + L.d2), c.opt ? (int32_t *)(dv + L.na) : nullptr, (double *)(dv + L.z),
+                                     (double *)(dv + L.g))) != GS_OK) return rc;
     if (c.jc) { ChainRec *cr = (ChainRec *)fe.ch_rec.dev;           // (the localisation is asked for only behind the joint test)
-        launch_joint_compat(k, d_pose, 1, d_po, d_obs, 1, d_fs, lidar, fe.map_n, fe.map_xy, fe.map_cov, d_cov, c.nd, c.gt, d_idx, cr->jc.index, &cr->jc.j,
-                            &cr->jc.kept, &cr->jc.dropped, &cr->jc.untestable, cr->jc.delta, g->stream);
-        if (c.loc) launch_localize(k, d_pose, 1, d_po, d_obs, 1, d_fs, lidar, fe.map_n, fe.map_xy, fe.map_cov, d_cov, c.nd, c.lp, cr->jc.index,
-                                   LoOut{cr->lo.pose, cr->lo.cov, &cr->lo.chi2, &cr->lo.pairs, &cr->lo.iterations, &cr->lo.status, nullptr}, fe.lo_kernel, g->stream); }
+        const MapRef m = resident_map_whole(g);                     // (neither searches the map)
+        launch_joint_compat(o, m, lidar, c.nd, c.gt, d_idx, cr->jc.index, &cr->jc.j, &cr->jc.kept, &cr->jc.dropped, &cr->jc.untestable, cr->jc.delta, Launch{g->stream});
+        if (c.loc) launch_localize(o, m, lidar, c.nd, c.lp, cr->jc.index, LoOut{cr->lo.pose, cr->lo.cov, &cr->lo.chi2, &cr->lo.pairs, &cr->lo.iterations, &cr->lo.status, nullptr},
+                                   fe.lo_kernel, Launch{g->stream}); }
     const size_t bz = 2 * (size_t)k * sizeof(double), bd = (size_t)k * sizeof(double), bi = (size_t)k * sizeof(int32_t);
     if ((rc = stage_fetch(g, fe.fr_out, c.opt ? L.out_bytes : L.na)) != GS_OK) return rc;                       // (the greedy assignment counts no admissible cones)
     if (c.jc && (rc = stage_fetch(g, fe.ch_rec, c.loc ? sizeof(ChainRec) : offsetof(JcRec, index) + bi)) != GS_OK) return rc;
@@ -1080,7 +1000,7 @@ struct FoParams { int min_pairs, max_misses; double merge2, merge_theta; };
 struct FollowRun {
     int n_hyp, n, cap; const double *obs; const int32_t *fs; const double *motion, *motion_cov;
     gs_follow_state *state; int32_t *best2; gs_follow_step *rec; int32_t *index;
-    int n_map; const double *map_xy; const int32_t *map_type; const double *map_cov; long long buckets; const int32_t *cell_start, *cell_items;
+    MapRef map;
     NnDev nd; JcGate gt; LoParams lp; FoParams fp;
 };
 }
@@ -1109,24 +1029,7 @@ static int follow_reserve(gs_graph *g, int n_hyp, int cap, FollowLayout &L) {
     if (!follow_layout(n_hyp, cap, L)) return fail(GS_ERR_INVALID, "frame following: bad sizes");
     if (!fe.fo_state) { HIP_TRY(hipMalloc((void **)&fe.fo_state, 2 * (size_t)GS_FOLLOW_HYP_MAX * sizeof(gs_follow_state)));
         HIP_TRY(hipMalloc((void **)&fe.fo_best, 4 * sizeof(int32_t))); }
-    if (L.bytes > fe.fo_bytes) { HIP_TRY(hipStreamSynchronize(g->stream));       // grow-only
-        if (fe.fo_mem) hipFree(fe.fo_mem);
-        fe.fo_mem = nullptr; fe.fo_bytes = 0;
-        HIP_TRY(hipMalloc((void **)&fe.fo_mem, L.bytes)); fe.fo_bytes = L.bytes; }
-    return GS_OK;
-}
-// the map / grid part of a run: a batch call's uploaded map and carved grid (gb null: the tile kernel) ...
-static void follow_map(FollowRun &R, int n_map, const double *map_xy, const int32_t *map_type, const double *map_cov, const GridBufs *gb) {
-    R.n_map = n_map; R.map_xy = map_xy; R.map_type = map_type; R.map_cov = map_cov;
-    R.buckets = gb ? gb->buckets : 0; R.cell_start = gb ? gb->start : nullptr; R.cell_items = gb ? gb->items : nullptr;
-}
-// ... or the resident map, through its grid (built here if the map or the distance changed) where `grid`
-static int follow_map_resident(gs_graph *g, FollowRun &R, bool grid) {
-    auto &fe = g->fe; GridBufs gb{};
-    if (grid) { const int rc = resident_grid(g, R.nd.max_distance); if (rc != GS_OK) return rc;
-        gb = grid_carve(fe.grid_mem, fe.map_n, fe.grid_max_cells); }
-    follow_map(R, fe.map_n, fe.map_xy, fe.map_type, fe.map_cov, grid ? &gb : nullptr);
-    return GS_OK;
+    return arena_reserve(g, fe.fo_mem, L.bytes);
 }
 static gs_follow_state *follow_state(gs_graph *g, bool live) { return (gs_follow_state *)g->fe.fo_state + (live ? 0 : GS_FOLLOW_HYP_MAX); }
 static int32_t *follow_best(gs_graph *g, bool live) { return g->fe.fo_best + (live ? 0 : 2); }
@@ -1143,7 +1046,7 @@ static void follow_init_host(int n_hyp, const double *poses, const double *covs,
 // step: its place in the run's frame bounds and records; t: its number (state_step); k: the frame's size, or -1 where only the device knows
 // it; mrec: its motion record's place, -1 for none (no prediction)
 static void follow_step_enqueue(gs_graph *g, const FollowRun &R, const FollowLayout &L, int step, int t, int k, int mrec, hipEvent_t start, hipEvent_t stop) {
-    auto &fe = g->fe; char *m = fe.fo_mem;
+    auto &fe = g->fe; char *m = fe.fo_mem.at(0);
     FoArgs A{};
     A.n_hyp = R.n_hyp; A.t = t; A.n = R.n; A.cap = R.cap; A.fs = R.fs + step; A.obs = R.obs;
     A.motion = mrec >= 0 ? R.motion + 3 * (size_t)mrec : nullptr;
@@ -1160,13 +1063,11 @@ static void follow_step_enqueue(gs_graph *g, const FollowRun &R, const FollowLay
     const int kk = k >= 0 ? k : R.cap;
     launch_follow_stage(A, kk, g->stream, start, nullptr);
     if (kk > 0) {
-        const int nc = R.n_hyp * kk; const double lidar = g->cfg.lidar_to_cog;
-        launch_assign_opt(nc, A.st_pose, R.n_hyp, A.st_pose_of_obs, A.st_obs, R.n_hyp, A.st_frame_start, lidar, R.n_map, R.map_xy, R.map_type, R.map_cov, A.st_cov, R.nd,
-                          R.buckets, R.cell_start, R.cell_items, as_idx, as_d2, nullptr, nullptr, nullptr, g->stream);
-        launch_joint_compat(nc, A.st_pose, R.n_hyp, A.st_pose_of_obs, A.st_obs, R.n_hyp, A.st_frame_start, lidar, R.n_map, R.map_xy, R.map_cov, A.st_cov, R.nd, R.gt,
-                            as_idx, jc_idx, nullptr, jc_kept, nullptr, nullptr, nullptr, g->stream);
-        launch_localize(nc, A.st_pose, R.n_hyp, A.st_pose_of_obs, A.st_obs, R.n_hyp, A.st_frame_start, lidar, R.n_map, R.map_xy, R.map_cov, A.st_cov, R.nd, R.lp,
-                        jc_idx, LoOut{lo_pose, lo_cov, lo_chi2, lo_pairs, lo_iters, lo_status, nullptr}, fe.lo_kernel, g->stream);
+        const double lidar = g->cfg.lidar_to_cog; const Launch S{g->stream};
+        const ObsRef o{R.n_hyp * kk, A.st_pose, R.n_hyp, A.st_pose_of_obs, A.st_obs, R.n_hyp, A.st_frame_start, A.st_cov};    // the stage: every hypothesis a frame
+        launch_assign_opt(o, R.map, lidar, R.nd, as_idx, as_d2, nullptr, nullptr, nullptr, S);
+        launch_joint_compat(o, R.map, lidar, R.nd, R.gt, as_idx, jc_idx, nullptr, jc_kept, nullptr, nullptr, nullptr, S);
+        launch_localize(o, R.map, lidar, R.nd, R.lp, jc_idx, LoOut{lo_pose, lo_cov, lo_chi2, lo_pairs, lo_iters, lo_status, nullptr}, fe.lo_kernel, S);
     }
     launch_follow_update(A, R.gt, g->stream, nullptr, stop);
 }
@@ -1183,22 +1084,17 @@ extern "C" int gs_follow_batch(gs_graph *g, int32_t n_hyp, const double *poses, 
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     int cap = 0; for (int t = 0; t < n_steps; ++t) cap = std::max(cap, frame_start[t + 1] - frame_start[t]);
     FollowLayout L; if ((rc = follow_reserve(g, n_hyp, cap, L)) != GS_OK) return rc;
-    const bool grid = grid_batch(g, n_map);
-    long long buckets = 0; const size_t gbytes = grid ? grid_bytes(n_map, buckets) + 5 * 256 : 0;
     std::vector<gs_follow_state> init((size_t)n_hyp); follow_init_host(n_hyp, poses, covs, init.data());
     const int32_t best0[2] = {0, n_hyp};
     const size_t nm = n_steps > 1 ? (size_t)n_steps - 1 : 0, nrec = (size_t)n_steps * n_hyp;
-    Staging sg{g}; double *ob, *mo, *mq, *mx, *mc; int32_t *fs, *mt, *b2, *oi; gs_follow_state *stt; gs_follow_step *rec; char *gm;
-    sg.add(stt, (size_t)n_hyp, (const gs_follow_state *)init.data()); sg.add(b2, 2, best0); sg.add(ob, 4 * (size_t)n, obs); sg.add(fs, (size_t)n_steps + 1, frame_start);
-    sg.add(mo, 3 * nm, motion); sg.add(mq, 9 * nm, motion_cov); sg.add(mx, 2 * (size_t)n_map, map_xy); sg.add(mt, n_map, map_type); sg.add(mc, 4 * (size_t)n_map, map_cov);
-    sg.add(rec, nrec); sg.add(oi, out_index ? (size_t)n_hyp * n : 0); sg.add(gm, gbytes);
+    Staging sg{g}; BatchIo io; double *mo, *mq; int32_t *b2, *oi; gs_follow_state *stt; gs_follow_step *rec;
+    sg.add(stt, (size_t)n_hyp, (const gs_follow_state *)init.data()); sg.add(b2, 2, best0);
+    io.add(sg, ObsRef{n, nullptr, 0, nullptr, obs, n_steps, frame_start, nullptr}, MapRef{n_map, map_xy, map_type, map_cov, 0, nullptr, nullptr}, grid_batch(g, n_map));
+    sg.add(mo, 3 * nm, motion); sg.add(mq, 9 * nm, motion_cov); sg.add(rec, nrec); sg.add(oi, out_index ? (size_t)n_hyp * n : 0);
     if ((rc = sg.commit()) != GS_OK) return rc;
-    GridBufs gb{};
-    if (grid) { gb = grid_carve(gm, n_map, buckets);
-        launch_grid_build(n_map, mx, R.nd.max_distance, buckets, gb.count, gb.start, gb.cursor, gb.items, g->stream); }
-    R.n_hyp = n_hyp; R.n = n; R.cap = cap; R.obs = ob; R.fs = fs; R.motion = mo; R.motion_cov = motion_cov ? mq : nullptr;
-    R.state = stt; R.best2 = b2; R.rec = rec; R.index = out_index ? oi : nullptr;
-    follow_map(R, n_map, mx, mt, map_cov ? mc : nullptr, grid ? &gb : nullptr);
+    io.build_grid(g, R.nd.max_distance);
+    R.n_hyp = n_hyp; R.n = n; R.cap = cap; R.obs = io.o.obs; R.fs = io.o.frame_start; R.motion = mo; R.motion_cov = motion_cov ? mq : nullptr;
+    R.state = stt; R.best2 = b2; R.rec = rec; R.index = out_index ? oi : nullptr; R.map = io.m;
     for (int t = 0; t < n_steps; ++t)                               // back to back: no host decision between the frames
         follow_step_enqueue(g, R, L, t, t, frame_start[t + 1] - frame_start[t], t - 1, nullptr, nullptr);
     sg.fetch(out_steps, rec, nrec * sizeof(gs_follow_step)); sg.fetch(out_index, oi, (size_t)n_hyp * n * sizeof(int32_t));
@@ -1216,16 +1112,14 @@ extern "C" int gs_follow_resident(gs_graph *g, int32_t n_hyp, const double *dev_
     if ((rc = dev_obs_aligned(dev_obs)) != GS_OK) return rc;
     rc = ensure_device(g); if (rc != GS_OK) return rc;
     FollowLayout L; if ((rc = follow_reserve(g, n_hyp, frame_cap, L)) != GS_OK) return rc;
-    if ((rc = follow_map_resident(g, R, grid_resident(g))) != GS_OK) return rc;
+    if ((rc = resident_map(g, g->fe.grid, grid_resident(g), R.nd.max_distance, R.map)) != GS_OK) return rc;
     R.n_hyp = n_hyp; R.n = n; R.cap = frame_cap; R.obs = dev_obs; R.fs = dev_frame_start; R.motion = dev_motion; R.motion_cov = dev_motion_cov;
     R.state = follow_state(g, false); R.best2 = follow_best(g, false); R.rec = dev_out_steps; R.index = dev_out_index;
     launch_follow_init(n_hyp, dev_poses, dev_covs, R.state, R.best2, g->stream, g->ev_lin[0], n_steps == 0 ? g->ev_lin[1] : nullptr);
     for (int t = 0; t < n_steps; ++t) follow_step_enqueue(g, R, L, t, t, -1, t - 1, nullptr, t == n_steps - 1 ? g->ev_lin[1] : nullptr);
     if (dev_out_state) HIP_TRY(hipMemcpyAsync(dev_out_state, R.state, (size_t)n_hyp * sizeof(gs_follow_state), hipMemcpyDeviceToDevice, g->stream));
     if (dev_out_best_2) HIP_TRY(hipMemcpyAsync(dev_out_best_2, R.best2, 2 * sizeof(int32_t), hipMemcpyDeviceToDevice, g->stream));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GS_ERR_HIP, std::string("frame following: ") + hipGetErrorString(e));
-    return GS_OK;
+    return resident_done(g, "frame following");
 }
 extern "C" int gs_debug_time_follow_resident(gs_graph *g, int32_t n_hyp, const double *dev_poses, const double *dev_covs, int32_t n_steps, int32_t n,
                                              const double *dev_obs, const int32_t *dev_frame_start, int32_t frame_cap, const double *dev_motion,
@@ -1294,7 +1188,7 @@ extern "C" int gs_frame_frontend_follow(gs_graph *g, const double *motion, const
     ((int32_t *)(pi + Io::IN_FS))[1] = k;
     if (k > 0) std::memcpy(pi + Io::IN_OBS, obs, 4 * (size_t)k * sizeof(double));
     if ((rc = stage_send(g, fe.fo_in, Io::in_bytes(k))) != GS_OK) return rc;
-    if ((rc = follow_map_resident(g, R, grid_live(g))) != GS_OK) return rc;
+    if ((rc = resident_map(g, fe.grid, grid_live(g), R.nd.max_distance, R.map)) != GS_OK) return rc;
     R.n_hyp = n_hyp; R.n = k; R.cap = k; R.obs = (const double *)(di + Io::IN_OBS); R.fs = (const int32_t *)(di + Io::IN_FS);
     R.motion = (const double *)(di + Io::IN_MOTION); R.motion_cov = motion_cov ? (const double *)(di + Io::IN_COV) : nullptr;
     R.state = follow_state(g, true); R.best2 = follow_best(g, true);

@@ -62,7 +62,7 @@ struct gs_graph {
     bool force_gather = false;              // cfg.linearize_gather
     // front end (A0 / A1): nothing is allocated or freed per call
     struct FrontEnd {
-        char *arena = nullptr; size_t arena_bytes = 0;          // grow-only device scratch of the batch calls
+        gs::DevArena arena;                                     // grow-only device scratch of the batch calls (Staging)
         // the live frame calls' staging (each null until a call needs it): a frame in and its per-observation results out — one pair for
         // gs_frame_frontend, gs_frame_frontend_nn and the assignment chain, whose calls each end in a wait —, the chain's records (ChainRec),
         // the search's record of gs_frame_frontend_relocalize (RelocRec), and gs_frame_frontend_follow's in and out (FollowFrameIo)
@@ -70,25 +70,27 @@ struct gs_graph {
         double *map_xy = nullptr; int32_t *map_type = nullptr;  // the resident association map (mirror of Slam::m_map), grow-only
         int map_n = 0, map_cap = 0;
         char *pin_map = nullptr; size_t pin_map_bytes = 0; bool pin_map_busy = false;   // pinned staging of map appends (busy: a copy out of it may be in flight)
-        char *grid_mem = nullptr; size_t grid_bytes = 0;        // the resident map's uniform grid, built on the device (gs_associate_resident): parameters, cell starts, items
-        bool grid_valid = false; int grid_map_n = 0; double grid_thr = 0.0; long long grid_max_cells = 0;
-        double *pcs = nullptr; size_t pcs_bytes = 0;            // cos / sin of the poses of a batched association (scratch, grow-only)
+        // a hashed grid of the resident map, built on the device (resident_map): counts, cell starts, cursors and items in mem (grow-only), and
+        // what it was built for — a map of map_n cones, a cell edge from thr, `cells` buckets; valid: the map has not changed since (map_changed).
+        // Two of them: the association's (cell edge from max_distance / the threshold) and relocalisation's (from inlier_radius) — two edges in
+        // one grid would evict each other on every frame that runs both
+        struct ResidentGrid { gs::DevArena mem; bool valid = false; int map_n = 0; double thr = 0.0; long long cells = 0; };
+        ResidentGrid grid, rl_grid;
+        gs::DevArena pcs;                                       // cos / sin of the poses of a batched association (scratch, grow-only)
         // covariance-gated association: the resident map's 2x2 blocks (map_cap x 4; null until a call needs them: every cone's block is
         // zero then) and the index table of gs_map_set_cov_from_marginals
         double *map_cov = nullptr;
         int64_t *cov_src = nullptr; size_t cov_src_n = 0;
         // frame localisation: gs_debug_localize's kernel choice (-1: by the mean frame size) and step output (a device pointer of the caller's, or null)
         int lo_kernel = -1; double *lo_step = nullptr;
-        // relocalisation (null until one of its calls is made): the seed kernel's records of the resident and the frame call (grow-only), a grid
-        // of its own beside the association's (cell edge from inlier_radius: the two edges must not evict each other), gs_debug_relocalize's
-        // slice (0: the launcher's choice)
-        char *rl_rec = nullptr; size_t rl_rec_bytes = 0;
-        char *rl_grid_mem = nullptr; size_t rl_grid_bytes = 0; bool rl_grid_valid = false; int rl_grid_map_n = 0; double rl_grid_thr = 0.0; long long rl_grid_cells = 0;
+        // relocalisation: the seed kernel's records of the resident and the frame call (empty until one of them is made, grow-only; its grid:
+        // rl_grid above), gs_debug_relocalize's slice (0: the launcher's choice)
+        gs::DevArena rl_rec;
         int rl_slice = 0;
-        // frame following (null until one of its calls is made): the per-step stage and chain buffers (gs_follow_host.hpp's FollowLayout,
+        // frame following (empty / null until one of its calls is made): the per-step stage and chain buffers (gs_follow_host.hpp's FollowLayout,
         // grow-only), the hypotheses' state — 64 records that live between gs_frame_frontend_follow calls, 64 more that a batch or resident
         // run works in — with {best, n_tracking} of either, and the live run's size and step count
-        char *fo_mem = nullptr; size_t fo_bytes = 0;
+        gs::DevArena fo_mem;
         char *fo_state = nullptr; int32_t *fo_best = nullptr;
         int fo_n_hyp = 0, fo_t = 0;
         // cone candidates (empty until one of their calls is made): the two tables and the per-step stage in one allocation of a fixed size

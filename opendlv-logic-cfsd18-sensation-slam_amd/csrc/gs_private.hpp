@@ -127,6 +127,7 @@ int run_check(gs_graph *g, const char *what, float *ms);
 void run_stats(gs_graph *g, gs_stats *stats, int32_t iterations, int32_t failure, int first_failure, double chi2_initial, double chi2_final, float ms);
 int marg_ready(gs_graph *g);                  // gs_marginals.cpp: GS_OK when the last gs_compute_marginals still describes the graph and its estimates (the getters' test)
 void gs_frontend_release(gs_graph *g);       // gs_frontend.cpp: front-end buffers of the handle
+void map_changed(gs_graph *g);               // gs_frontend.cpp: what every call that moves, adds or removes cones of the resident map ends in (its grids are stale)
 namespace gs { struct NnDev; }
 int nn_params_check(const gs_nn_params *p, gs::NnDev &d);                      // gs_frontend.cpp: what every call refuses of gs_nn_params, before the device is touched
 int frame_start_check(int32_t n, int32_t n_frames, const int32_t *fs);         // gs_frontend.cpp: a batch call's frame bounds

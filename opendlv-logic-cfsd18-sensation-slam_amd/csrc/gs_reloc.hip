@@ -301,22 +301,20 @@ int reloc_slices(int n_frames, int n_map, int forced, int &slice) {
     return std::max(1, (n_map + slice - 1) / slice);
 }
 
-void launch_relocalize(int n, const double *obs, int n_frames, const int32_t *frame_start, double lidar, int n_map, const double *map_xy,
-                       const int32_t *map_type, RlDev p, long long buckets, const int32_t *cell_start, const int32_t *cell_items, int slice,
-                       int n_slices, RlRec *rec, const RlOut &o, double *chain_pose, int32_t *chain_frame_end, hipStream_t st,
-                       hipEvent_t start, hipEvent_t stop) {
-    if (n_frames <= 0) return;
-    RlArgs A{n, obs, n_frames, frame_start, lidar, RlMap{n_map, map_xy, map_type, cell_start ? grid_params_of(p.inlier_radius, buckets) : GridParams{}, cell_start, cell_items},
-             p, slice, n_slices, rec, 0};
-    const dim3 sg((unsigned)n_frames * (unsigned)n_slices), pg(n_frames), blk(256);
-    const bool second = o.second_count || o.second_pose;
+void launch_relocalize(const ObsRef &o, const MapRef &m, double lidar, RlDev p, int slice, int n_slices, RlRec *rec, const RlOut &out, double *chain_pose,
+                       int32_t *chain_frame_end, Launch L) {
+    if (o.n_frames <= 0) return;
+    RlArgs A{o.n, o.obs, o.n_frames, o.frame_start, lidar,
+             RlMap{m.n, m.xy, m.type, m.cell_start ? grid_params_of(p.inlier_radius, m.buckets) : GridParams{}, m.cell_start, m.cell_items}, p, slice, n_slices, rec, 0};
+    const dim3 sg((unsigned)o.n_frames * (unsigned)n_slices), pg(o.n_frames), blk(256);
+    const bool second = out.second_count || out.second_pose;
     for (int pass = 0; pass < (second ? 2 : 1); ++pass) {                      // start on the first dispatch, stop on the last
         A.excl = pass;
-        hipEvent_t e0 = pass == 0 ? start : nullptr, e1 = pass == (second ? 1 : 0) ? stop : nullptr;
-        if (cell_start) { hipExtLaunchKernelGGL(k_reloc_seed<true>, sg, blk, 0, st, e0, nullptr, 0, A);
-                          hipExtLaunchKernelGGL(k_reloc_pick<true>, pg, blk, 0, st, nullptr, e1, 0, A, o, pass == 0 ? chain_pose : nullptr, pass == 0 ? chain_frame_end : nullptr); }
-        else { hipExtLaunchKernelGGL(k_reloc_seed<false>, sg, blk, 0, st, e0, nullptr, 0, A);
-               hipExtLaunchKernelGGL(k_reloc_pick<false>, pg, blk, 0, st, nullptr, e1, 0, A, o, pass == 0 ? chain_pose : nullptr, pass == 0 ? chain_frame_end : nullptr); }
+        hipEvent_t e0 = pass == 0 ? L.start : nullptr, e1 = pass == (second ? 1 : 0) ? L.stop : nullptr;
+        if (m.cell_start) { hipExtLaunchKernelGGL(k_reloc_seed<true>, sg, blk, 0, L.st, e0, nullptr, 0, A);
+                            hipExtLaunchKernelGGL(k_reloc_pick<true>, pg, blk, 0, L.st, nullptr, e1, 0, A, out, pass == 0 ? chain_pose : nullptr, pass == 0 ? chain_frame_end : nullptr); }
+        else { hipExtLaunchKernelGGL(k_reloc_seed<false>, sg, blk, 0, L.st, e0, nullptr, 0, A);
+               hipExtLaunchKernelGGL(k_reloc_pick<false>, pg, blk, 0, L.st, nullptr, e1, 0, A, out, pass == 0 ? chain_pose : nullptr, pass == 0 ? chain_frame_end : nullptr); }
     }
 }
 
