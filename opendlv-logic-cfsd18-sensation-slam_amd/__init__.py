@@ -6,7 +6,7 @@ This package only holds the ctypes plumbing above that C-ABI and the synthetic t
 The directory name contains hyphens, import it with
     importlib.import_module("opendlv-logic-cfsd18-sensation-slam_amd")
 """
-from . import binding, track  # noqa: F401
+from . import binding, cheader, track  # noqa: F401
 from .binding import Config, Graph, GsError, Shell, Slam, Stats, cone_encode, default_config, device_count, wgs84_from_cartesian, wgs84_to_cartesian  # noqa: F401
 
 

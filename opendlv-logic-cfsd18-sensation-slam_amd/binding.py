@@ -5,10 +5,11 @@ shared library is missing or no gfx950 device is usable, calls raise.
 """
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
+
+from . import cheader
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -16,13 +17,29 @@ LIB_PATH = os.environ.get("GS_LIB") or os.path.join(CSRC, "libgraphslam_hip.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "graphslam.h")
 DEBUG_HEADER = os.path.join(os.path.dirname(HERE), "include", "graphslam_debug.h")     # tuning / fault injection / timestamps: not the drop-in boundary
 
+# The headers are the one statement of the ABI on this side too: every constant, struct and prototype below is read from them (cheader.py)
+ABI = cheader.Abi()
+for _h in (HEADER, DEBUG_HEADER):
+    with open(_h) as _f:
+        ABI.read(_f.read(), _h)
+
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
+_lp = C.POINTER(C.c_int64)
 
-GS_OK = 0
-ERRORS = {-1: "GS_ERR_INVALID", -2: "GS_ERR_DUPLICATE_ID", -3: "GS_ERR_UNKNOWN_ID", -4: "GS_ERR_NO_DEVICE",
-          -5: "GS_ERR_HIP", -6: "GS_ERR_NOT_INITIALIZED", -7: "GS_ERR_EMPTY", -8: "GS_ERR_NUMERIC",
-          -9: "GS_ERR_CAPACITY", -10: "GS_ERR_TIMEOUT", -11: "GS_ERR_OUT_OF_PATTERN"}
+
+def _defines(prefix):
+    """the header's #define <prefix>* integers by lower-case name, in the header's order"""
+    return {k[len(prefix):].lower(): v for k, v in ABI.defines.items() if k.startswith(prefix)}
+
+
+GS_OK = ABI.defines["GS_OK"]
+ERRORS = {v: "GS_ERR_" + k.upper() for k, v in _defines("GS_ERR_").items()}
+ROBUST_KERNELS = _defines("GS_ROBUST_")                     # gs_set_robust_kernel: GS_ROBUST_* / GS_EDGE_* by name
+EDGE_KINDS = _defines("GS_EDGE_")
+DOGLEG_KINDS = tuple(k.upper() for k in sorted(_defines("GS_DOGLEG_"), key=_defines("GS_DOGLEG_").get))    # ("GN", "SD", "DL")
+NN_FRAME_MAX, LOC_ITER_MAX, RELOC_SEED_MAX, FOLLOW_HYP_MAX, CAND_MAX, DUP_MAP_MAX = (
+    ABI.defines["GS_" + k] for k in ("NN_FRAME_MAX", "LOC_ITER_MAX", "RELOC_SEED_MAX", "FOLLOW_HYP_MAX", "CAND_MAX", "DUP_MAP_MAX"))
 
 
 class GsError(RuntimeError):
@@ -31,117 +48,99 @@ class GsError(RuntimeError):
         self.code = code
 
 
-class Config(C.Structure):
-    _fields_ = [("struct_size", C.c_int32), ("device", C.c_int32), ("verbose", C.c_int32),
-                ("leaf_poses", C.c_int32), ("factor_variant", C.c_int32), ("linearize_gather", C.c_int32),
-                ("odometry_information", C.c_double), ("cone_information", C.c_double),
-                ("same_cone_threshold", C.c_double), ("cone_mapping_threshold", C.c_double),
-                ("lidar_to_cog", C.c_double), ("loop_closing_radius", C.c_double),
-                ("loop_closing_min_index", C.c_int32), ("optimize_iterations", C.c_int32),
-                ("reference_quirks", C.c_int32), ("optimize_every_keyframe", C.c_int32),
-                ("odometry_robust_kernel", C.c_int32), ("odometry_robust_delta", C.c_double),
-                ("observation_robust_kernel", C.c_int32), ("observation_robust_delta", C.c_double)]
-
-
-# gs_set_robust_kernel: GS_ROBUST_* / GS_EDGE_* of include/graphslam.h by name
-ROBUST_KERNELS = {"none": 0, "huber": 1, "cauchy": 2}
-EDGE_KINDS = {"odometry": 0, "observation": 1}
-
-
-class Stats(C.Structure):
-    _fields_ = [("struct_size", C.c_int32), ("iterations", C.c_int32),
-                ("n_free_poses", C.c_int32), ("n_free_landmarks", C.c_int32),
-                ("n_odometry_edges", C.c_int32), ("n_observation_edges", C.c_int32),
-                ("n_fronts", C.c_int32), ("n_levels", C.c_int32), ("max_front", C.c_int32),
-                ("numeric_failure", C.c_int32),
-                ("chi2_initial", C.c_double), ("chi2_final", C.c_double),
-                ("ms_structure", C.c_double), ("ms_linearize", C.c_double), ("ms_factor", C.c_double),
-                ("ms_backsolve", C.c_double), ("ms_update", C.c_double), ("ms_total", C.c_double),
-                ("factor_flops", C.c_int64), ("factor_bytes", C.c_int64), ("ms_event_overhead", C.c_double),
-                ("fell_back", C.c_int32), ("first_failure", C.c_int32), ("factor_variant", C.c_int32), ("n_big_fronts", C.c_int32),
-                ("device_bytes", C.c_int64), ("n_own_fronts", C.c_int32), ("n_shared_fronts", C.c_int32), ("ms_plan_host", C.c_double),
-                ("ms_linearize_kernel", C.c_double), ("n_growths", C.c_int32), ("n_subtrees", C.c_int32),
-                ("n_pose_priors", C.c_int32), ("n_landmark_priors", C.c_int32)]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
-
-
-class ShellMsg(C.Structure):
-    _fields_ = [("data_type", C.c_int32), ("sender_stamp", C.c_uint32), ("sample_time_us", C.c_int64),
-                ("object_id", C.c_uint32), ("reserved", C.c_uint32), ("v", C.c_double * 3)]
-
-
-class DebugOptions(C.Structure):
-    """gs_debug_options (include/graphslam_debug.h): every tuning switch of a handle."""
-    _fields_ = [("struct_size", C.c_int32)] + [(k, C.c_int32) for k in (
-        "tree", "block_fronts", "leaf_kernel", "leaf_min", "bs_wide", "leaf_nt3", "f3_lds_kb", "bs_low",
-        "leaf_poses", "cluster_ways", "ell_lanes", "big_cluster", "grow_headroom", "factor_variant",
-        "grow", "grow_min_poses", "assoc_grid", "force_shared_top", "host_trig", "pool_poison", "plan_timing", "dbg", "subtree", "tickets", "shard_by_window")] + [("reserved", C.c_int32 * 5)]
-
+# ---- the structs: ctypes mirrors for the ones passed by pointer, numpy records for the ones that come in arrays
+Config = ABI.structure("Config", "gs_config")
+ShellMsg = ABI.structure("ShellMsg", "gs_shell_msg")
+DebugOptions = ABI.structure("DebugOptions", "gs_debug_options")    # every tuning switch of a handle (include/graphslam_debug.h)
+PlanInfo = ABI.structure("PlanInfo", "gs_plan_info")
+LmParams = ABI.structure("LmParams", "gs_lm_params")
+DoglegParams = ABI.structure("DoglegParams", "gs_dogleg_params")
+NnParams = ABI.structure("NnParams", "gs_nn_params")                # the gate and the noise model of the covariance-gated association
+JcParams = ABI.structure("JcParams", "gs_jc_params")                # the joint compatibility test's gate per number of kept pairs
+LocParams = ABI.structure("LocParams", "gs_loc_params")             # the iteration limit and the stop tolerances of frame localisation
+RelocParams = ABI.structure("RelocParams", "gs_reloc_params")       # the seeds, the tolerances and what counts as a different pose
+FollowParams = ABI.structure("FollowParams", "gs_follow_params")    # when a fit is accepted, a hypothesis lost, two have become one
+CandParams = ABI.structure("CandParams", "gs_cand_params")          # when a candidate is confirmed or retired, where one may spawn
+DupParams = ABI.structure("DupParams", "gs_dup_params")             # which cone pairs of a map count as twins
+FOLLOW_STATE, FOLLOW_STEP = ABI.dtype("gs_follow_state"), ABI.dtype("gs_follow_step")
+CAND, CAND_STEP, DUP_INFO = ABI.dtype("gs_cand"), ABI.dtype("gs_cand_step"), ABI.dtype("gs_dup_info")
 
 # switches applied to every handle this process creates through the binding (tests: conftest sets grow_min_poses = 0)
 DEFAULT_DEBUG = {}
 
 
-class PlanInfo(C.Structure):
-    _fields_ = [("n_scalar", C.c_int32), ("n_fronts", C.c_int32), ("n_levels", C.c_int32),
-                ("max_front", C.c_int32), ("l_doubles", C.c_int64), ("u_doubles", C.c_int64),
-                ("n_asm_blocks", C.c_int64), ("n_child_map", C.c_int64)]
-
-
-class MarginalsInfo(C.Structure):
-    _fields_ = [("struct_size", C.c_int32), ("numeric_failure", C.c_int32), ("n_fronts", C.c_int32), ("n_levels", C.c_int32),
-                ("sigma_bytes", C.c_int64), ("ms_linearize_factor", C.c_double), ("ms_selinv", C.c_double),
-                ("ms_extract", C.c_double), ("ms_total", C.c_double)]
-
+@ABI.mirror("gs_stats")
+class Stats(C.Structure):
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
-class LmParams(C.Structure):
-    """gs_lm_params (include/graphslam.h)"""
-    _fields_ = [("struct_size", C.c_int32), ("max_trials_after_failure", C.c_int32), ("initial_lambda", C.c_double), ("tau", C.c_double)]
+@ABI.mirror("gs_marginals_info")
+class MarginalsInfo(C.Structure):
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+@ABI.mirror("gs_lm_info", rename={"lambda": "lambda_"})          # (a Python keyword: the one field not under its header name)
 class LmInfo(C.Structure):
-    """gs_lm_info: counters of a gs_optimize_lm call and its per-iteration history (the first 64 iterations)"""
-    _fields_ = [("struct_size", C.c_int32), ("iterations", C.c_int32), ("trials", C.c_int32), ("rejected", C.c_int32),
-                ("terminated", C.c_int32), ("reserved", C.c_int32), ("lambda_initial", C.c_double), ("lambda_final", C.c_double),
-                ("chi2", C.c_double * 64), ("lambda_", C.c_double * 64), ("n_trials", C.c_int32 * 64)]
+    """gs_lm_info: counters of a gs_optimize_lm call and its per-iteration history (the first iterations only)"""
 
     def as_dict(self):
         """scalars as they are; the histories as arrays cut to the iterations that ran (one more than accepted after a terminate)"""
-        n = min(self.iterations + (1 if self.terminated else 0), 64)
+        n = min(self.iterations + (1 if self.terminated else 0), len(self.chi2))
         o = {k: getattr(self, k) for k in ("iterations", "trials", "rejected", "terminated", "lambda_initial", "lambda_final")}
         o["chi2"] = np.array(self.chi2[:n]); o["lambda"] = np.array(self.lambda_[:n]); o["n_trials"] = np.array(self.n_trials[:n], dtype=np.int32)
         return o
 
 
-class NnParams(C.Structure):
-    """gs_nn_params (include/graphslam.h): the gate and the noise model of the covariance-gated association"""
-    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("gate_chi2", C.c_double), ("max_distance", C.c_double),
-                ("type_tol", C.c_double), ("sigma_range", C.c_double), ("sigma_bearing", C.c_double), ("sigma_xy", C.c_double)]
+@ABI.mirror("gs_dogleg_info")
+class DoglegInfo(C.Structure):
+    """gs_dogleg_info: counters of a gs_optimize_dogleg call and its per-iteration history (the first iterations only)"""
+
+    def as_dict(self):
+        """scalars as they are; the histories as arrays cut to the iterations that ran (one more than accepted after a terminate)"""
+        n = min(self.iterations + (1 if self.terminated else 0), len(self.chi2))
+        o = {k: getattr(self, k) for k in ("iterations", "trials", "rejected", "terminated", "n_gn", "n_sd", "n_dl", "delta_initial", "delta_final")}
+        o["chi2"] = np.array(self.chi2[:n]); o["delta"] = np.array(self.delta[:n])
+        o["n_trials"] = np.array(self.n_trials[:n], dtype=np.int32); o["step_kind"] = np.array(self.step_kind[:n], dtype=np.int32)
+        return o
 
 
-def nn_params(**kw):
-    """the library's gs_nn_params defaults with the given fields replaced"""
-    p = NnParams(); rc = lib().gs_nn_params_default(C.byref(p))
+# A struct of parameters is the library's defaults with the named fields replaced.  Per struct: the fields that may NOT be named (every
+# other field of the header's struct may), and what naming one of those or an unknown one raises.
+_PARAMS = {"gs_nn_params": ((), KeyError),
+           "gs_loc_params": (("struct_size",), AttributeError),
+           "gs_reloc_params": (("reserved",), AttributeError),
+           "gs_follow_params": (("struct_size", "reserved"), AttributeError),
+           "gs_cand_params": (("struct_size", "reserved"), AttributeError),
+           "gs_dup_params": (("struct_size", "reserved"), AttributeError),
+           "gs_lm_params": (("struct_size",), AttributeError),
+           "gs_dogleg_params": (("struct_size",), AttributeError)}
+
+
+def _params(cname, kw):
+    fixed, error = _PARAMS[cname]
+    p = ABI.mirrors[cname](); L = lib()
+    rc = getattr(L, cname + "_default")(C.byref(p))
     if rc != GS_OK:
-        raise GsError(rc, "gs_nn_params_default")
+        raise GsError(rc, (L.gs_last_error() or b"").decode())
     for k, v in kw.items():
-        if k not in dict(NnParams._fields_):
-            raise KeyError(k)
+        if k == "max_trials":                               # short for max_trials_after_failure (gs_lm_params, gs_dogleg_params)
+            k = "max_trials_after_failure"
+        if k in fixed or k not in dict(p._fields_):
+            raise error("%s has no field %r" % (cname, k))
         setattr(p, k, v)
     return p
 
 
-NN_FRAME_MAX = 256                                          # GS_NN_FRAME_MAX
-
-
-class JcParams(C.Structure):
-    """gs_jc_params (include/graphslam.h): the joint compatibility test's gate per number of kept pairs"""
-    _fields_ = [("struct_size", C.c_int32), ("reserved", C.c_int32), ("confidence", C.c_double), ("gate", C.c_double * (NN_FRAME_MAX + 1))]
+def nn_params(**kw): return _params("gs_nn_params", kw)
+def loc_params(**kw): return _params("gs_loc_params", kw)
+def reloc_params(**kw): return _params("gs_reloc_params", kw)
+def follow_params(**kw): return _params("gs_follow_params", kw)
+def cand_params(**kw): return _params("gs_cand_params", kw)
+def dup_params(**kw): return _params("gs_dup_params", kw)
+def lm_params(**kw): return _params("gs_lm_params", kw)             # max_trials: short for max_trials_after_failure
+def dogleg_params(**kw): return _params("gs_dogleg_params", kw)     # the same
 
 
 def jc_params(confidence=None):
@@ -153,57 +152,17 @@ def jc_params(confidence=None):
     return p
 
 
+# The per-frame records of the joint test and of localisation: (the record as a dict of arrays, its C arguments in the header's order)
 def _jc_record(n_frames):
-    return {"joint_d2": np.zeros(n_frames), "n_kept": np.zeros(n_frames, dtype=np.int32), "n_dropped": np.zeros(n_frames, dtype=np.int32),
-            "n_untestable": np.zeros(n_frames, dtype=np.int32), "delta": np.zeros((n_frames, 3))}
-
-
-LOC_ITER_MAX = 16                                           # GS_LOC_ITER_MAX
-
-
-class LocParams(C.Structure):
-    """gs_loc_params (include/graphslam.h): the iteration limit and the stop tolerances of frame localisation"""
-    _fields_ = [("struct_size", C.c_int32), ("max_iterations", C.c_int32), ("tol_xy", C.c_double), ("tol_theta", C.c_double)]
-
-
-def loc_params(**kw):
-    """the library's gs_loc_params defaults, with the named fields changed"""
-    p = LocParams(); L = lib()
-    rc = L.gs_loc_params_default(C.byref(p))
-    if rc != GS_OK:
-        raise GsError(rc, (L.gs_last_error() or b"").decode())
-    for k, v in kw.items():
-        if k not in ("max_iterations", "tol_xy", "tol_theta"):
-            raise AttributeError("gs_loc_params has no field %r" % k)
-        setattr(p, k, v)
-    return p
+    r = {"joint_d2": np.zeros(n_frames), "n_kept": np.zeros(n_frames, dtype=np.int32), "n_dropped": np.zeros(n_frames, dtype=np.int32),
+         "n_untestable": np.zeros(n_frames, dtype=np.int32), "delta": np.zeros((n_frames, 3))}
+    return r, (_d(r["joint_d2"]), _i(r["n_kept"]), _i(r["n_dropped"]), _i(r["n_untestable"]), _d(r["delta"]))
 
 
 def _loc_record(n_frames):
-    return {"pose": np.zeros((n_frames, 3)), "cov": np.zeros((n_frames, 9)), "chi2": np.zeros(n_frames), "n_pairs": np.zeros(n_frames, dtype=np.int32),
-            "iterations": np.zeros(n_frames, dtype=np.int32), "status": np.zeros(n_frames, dtype=np.int32)}
-
-
-RELOC_SEED_MAX = 16                                         # GS_RELOC_SEED_MAX
-
-
-class RelocParams(C.Structure):
-    """gs_reloc_params (include/graphslam.h): the seeds, the tolerances and what counts as a different pose in relocalisation"""
-    _fields_ = [("struct_size", C.c_int32), ("seed_obs", C.c_int32), ("min_inliers", C.c_int32), ("reserved", C.c_int32), ("min_baseline", C.c_double),
-                ("length_tol", C.c_double), ("inlier_radius", C.c_double), ("type_tol", C.c_double), ("distinct_xy", C.c_double), ("distinct_cos", C.c_double)]
-
-
-def reloc_params(**kw):
-    """the library's gs_reloc_params defaults, with the named fields changed"""
-    p = RelocParams(); L = lib()
-    rc = L.gs_reloc_params_default(C.byref(p))
-    if rc != GS_OK:
-        raise GsError(rc, (L.gs_last_error() or b"").decode())
-    for k, v in kw.items():
-        if k not in dict(RelocParams._fields_) or k == "reserved":
-            raise AttributeError("gs_reloc_params has no field %r" % k)
-        setattr(p, k, v)
-    return p
+    r = {"pose": np.zeros((n_frames, 3)), "cov": np.zeros((n_frames, 9)), "chi2": np.zeros(n_frames), "n_pairs": np.zeros(n_frames, dtype=np.int32),
+         "iterations": np.zeros(n_frames, dtype=np.int32), "status": np.zeros(n_frames, dtype=np.int32)}
+    return r, (_d(r["pose"]), _d(r["cov"]), _d(r["chi2"]), _i(r["n_pairs"]), _i(r["iterations"]), _i(r["status"]))
 
 
 def _reloc_record(n_frames):
@@ -212,121 +171,21 @@ def _reloc_record(n_frames):
             "status": np.zeros(n_frames, dtype=np.int32)}
 
 
-FOLLOW_HYP_MAX = 64                                         # GS_FOLLOW_HYP_MAX
+def _reloc_record_args(r, second):
+    """the C arguments of a search record; second=False: NULL for the runner-up's fields, which skips its pass"""
+    return (_d(r["pose"]), _i(r["count"]), _d(r["cost"]), _i(r["seed"]), _i(r["second_count"]) if second else None, _d(r["second_pose"]) if second else None,
+            r["n_seeds"].ctypes.data_as(_lp), _i(r["status"]))
 
 
-class FollowParams(C.Structure):
-    """gs_follow_params (include/graphslam.h): when a fit is accepted, when a hypothesis is lost, when two have become one"""
-    _fields_ = [("struct_size", C.c_int32), ("min_pairs", C.c_int32), ("max_misses", C.c_int32), ("reserved", C.c_int32), ("merge_xy", C.c_double),
-                ("merge_theta", C.c_double)]
-
-
-def follow_params(**kw):
-    """the library's gs_follow_params defaults, with the named fields changed"""
-    p = FollowParams(); L = lib()
-    rc = L.gs_follow_params_default(C.byref(p))
-    if rc != GS_OK:
-        raise GsError(rc, (L.gs_last_error() or b"").decode())
-    for k, v in kw.items():
-        if k not in ("min_pairs", "max_misses", "merge_xy", "merge_theta"):
-            raise AttributeError("gs_follow_params has no field %r" % k)
-        setattr(p, k, v)
-    return p
-
-
-# gs_follow_state and gs_follow_step as numpy records (136 and 224 bytes, no padding)
-FOLLOW_STATE = np.dtype([("pose", "<f8", 3), ("cov", "<f8", 9), ("sum_chi2", "<f8"), ("hits", "<i4"), ("frames_hit", "<i4"), ("frames_missed", "<i4"),
-                         ("misses", "<i4"), ("state", "<i4"), ("state_step", "<i4"), ("duplicate_of", "<i4"), ("reserved", "<i4")])
-FOLLOW_STEP = np.dtype([("prior_pose", "<f8", 3), ("prior_cov", "<f8", 9), ("pose", "<f8", 3), ("cov", "<f8", 9), ("chi2", "<f8"), ("n_pairs", "<i4"),
-                        ("iterations", "<i4"), ("status", "<i4"), ("n_kept", "<i4"), ("accepted", "<i4"), ("state", "<i4")])
-
-
-CAND_MAX = 1024                                             # GS_CAND_MAX
-
-
-class CandParams(C.Structure):
-    """gs_cand_params (include/graphslam.h): when a candidate is confirmed, when it is retired, where one may spawn and what counts as visible"""
-    _fields_ = [("struct_size", C.c_int32), ("confirm_hits", C.c_int32), ("max_misses", C.c_int32), ("reserved", C.c_int32), ("spawn_range", C.c_double),
-                ("view_range", C.c_double), ("view_cos", C.c_double)]
-
-
-def cand_params(**kw):
-    """the library's gs_cand_params defaults, with the named fields changed"""
-    p = CandParams(); L = lib()
-    rc = L.gs_cand_params_default(C.byref(p))
-    if rc != GS_OK:
-        raise GsError(rc, (L.gs_last_error() or b"").decode())
-    for k, v in kw.items():
-        if k not in ("confirm_hits", "max_misses", "spawn_range", "view_range", "view_cos"):
-            raise AttributeError("gs_cand_params has no field %r" % k)
-        setattr(p, k, v)
-    return p
-
-
-# gs_cand and gs_cand_step as numpy records (80 and 48 bytes, no padding)
-CAND = np.dtype([("xy", "<f8", 2), ("cov", "<f8", 4), ("type", "<i4"), ("id", "<i4"), ("state", "<i4"), ("hits", "<i4"), ("misses", "<i4"),
-                 ("first_step", "<i4"), ("last_step", "<i4"), ("confirm_step", "<i4")])
-CAND_STEP = np.dtype([("step", "<i4"), ("n_unexplained", "<i4"), ("n_fused", "<i4"), ("n_spawned", "<i4"), ("n_contested", "<i4"), ("n_far", "<i4"),
-                      ("n_dropped", "<i4"), ("n_missed", "<i4"), ("n_retired", "<i4"), ("n_confirmed", "<i4"), ("n_live", "<i4"), ("reserved", "<i4")])
-
-
-DUP_MAP_MAX = 262144                                        # GS_DUP_MAP_MAX
-
-
-class DupParams(C.Structure):
-    """gs_dup_params (include/graphslam.h): which cone pairs of a map count as twins"""
-    _fields_ = [("struct_size", C.c_int32), ("require_same_type", C.c_int32), ("exclusive", C.c_int32), ("reserved", C.c_int32), ("gate_chi2", C.c_double),
-                ("max_distance", C.c_double), ("sigma_floor", C.c_double)]
-
-
-def dup_params(**kw):
-    """the library's gs_dup_params defaults, with the named fields changed"""
-    p = DupParams(); L = lib()
-    rc = L.gs_dup_params_default(C.byref(p))
-    if rc != GS_OK:
-        raise GsError(rc, (L.gs_last_error() or b"").decode())
-    for k, v in kw.items():
-        if k not in ("require_same_type", "exclusive", "gate_chi2", "max_distance", "sigma_floor"):
-            raise AttributeError("gs_dup_params has no field %r" % k)
-        setattr(p, k, v)
-    return p
-
-
-DUP_INFO = np.dtype([("n_in", "<i4"), ("n_out", "<i4"), ("n_pairs", "<i4"), ("n_ambiguous", "<i4")])      # gs_dup_info
-
-
-class DoglegParams(C.Structure):
-    """gs_dogleg_params (include/graphslam.h)"""
-    _fields_ = [("struct_size", C.c_int32), ("max_trials_after_failure", C.c_int32), ("initial_delta", C.c_double)]
-
-
-DOGLEG_KINDS = ("GN", "SD", "DL")                           # GS_DOGLEG_GN / _SD / _DL
-
-
-class DoglegInfo(C.Structure):
-    """gs_dogleg_info: counters of a gs_optimize_dogleg call and its per-iteration history (the first 64 iterations)"""
-    _fields_ = [("struct_size", C.c_int32), ("iterations", C.c_int32), ("trials", C.c_int32), ("rejected", C.c_int32),
-                ("terminated", C.c_int32), ("reserved", C.c_int32), ("n_gn", C.c_int32), ("n_sd", C.c_int32), ("n_dl", C.c_int32),
-                ("delta_initial", C.c_double), ("delta_final", C.c_double),
-                ("chi2", C.c_double * 64), ("delta", C.c_double * 64), ("n_trials", C.c_int32 * 64), ("step_kind", C.c_int32 * 64)]
-
-    def as_dict(self):
-        """scalars as they are; the histories as arrays cut to the iterations that ran (one more than accepted after a terminate)"""
-        n = min(self.iterations + (1 if self.terminated else 0), 64)
-        o = {k: getattr(self, k) for k in ("iterations", "trials", "rejected", "terminated", "n_gn", "n_sd", "n_dl", "delta_initial", "delta_final")}
-        o["chi2"] = np.array(self.chi2[:n]); o["delta"] = np.array(self.delta[:n])
-        o["n_trials"] = np.array(self.n_trials[:n], dtype=np.int32); o["step_kind"] = np.array(self.step_kind[:n], dtype=np.int32)
-        return o
+# The prototypes of the headers under the rules of cheader.py, except two parameters: the 128-byte unique id of RCCL is declared void * and
+# passed as a Python bytes object / string buffer
+PROTOTYPE_OVERRIDES = {("gs_dist_unique_id", "out_128_bytes"): C.c_char_p, ("gs_dist_comm_init", "unique_id_128_bytes"): C.c_char_p}
+PROTOTYPES = {fn: ABI.prototype(fn, PROTOTYPE_OVERRIDES) for fn in ABI.protos}
 
 
 def declared_symbols(debug=True):
     """Every function name include/graphslam.h (and, debug=True, include/graphslam_debug.h) declares."""
-    names = set()
-    for h in (HEADER, DEBUG_HEADER) if debug else (HEADER,):
-        txt = open(h).read()
-        txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-        names |= set(re.findall(r"\b(gs_[a-z0-9_]+)\s*\(", txt))
-    return sorted(names)
+    return sorted(fn for fn, (origin, _, _) in ABI.protos.items() if debug or origin == HEADER)
 
 
 def build(force=False):
@@ -341,247 +200,20 @@ _lib = None
 
 
 def lib():
-    """Load the HIP library.  Raises if it has not been built: there is no fallback path."""
+    """Load the HIP library and give every declared function it exports the header's prototype (a library loaded through GS_LIB may be an
+    older build that lacks some).  Raises if it has not been built: there is no fallback path."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError("libgraphslam_hip.so is missing (run __graft_entry__.build()); "
-                           "the GraphSLAM back-end has no CPU fallback")
-    L = C.CDLL(LIB_PATH)
-    L.gs_last_error.restype = C.c_char_p
-    L.gs_linearize_bytes.restype = C.c_int64
-    L.gs_dist_exchange_doubles.restype = C.c_int64
-    L.gs_slam_graph.restype = C.c_void_p
-    vp = C.c_void_p
-    L.gs_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
-    L.gs_slam_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]
-    for name in ("gs_destroy", "gs_clear", "gs_initialize_optimization", "gs_iterate", "gs_sync_estimates",
-                 "gs_stream_synchronize", "gs_linearize", "gs_num_poses", "gs_num_landmarks",
-                 "gs_num_odometry_edges", "gs_num_observation_edges", "gs_dist_iterate_local",
-                 "gs_dist_iterate_finish", "gs_slam_destroy", "gs_slam_map_size", "gs_slam_loop_closed",
-                 "gs_slam_current_cone_index"):
-        getattr(L, name).argtypes = [vp]
-    L.gs_linearize_bytes.argtypes = [vp]
-    L.gs_debug_timestamps.argtypes = [vp, C.POINTER(C.c_int64)]
-    L.gs_debug_front_times.argtypes = [vp, C.POINTER(C.c_int64), C.c_int64]
-    L.gs_dist_exchange_doubles.argtypes = [vp]
-    L.gs_slam_graph.argtypes = [vp]
-    L.gs_set_stream.argtypes = [vp, vp]
-    L.gs_dist_set_exchange_buffer.argtypes = [vp, vp]
-    L.gs_dist_configure.argtypes = [vp, C.c_int32, C.c_int32]
-    if hasattr(L, "gs_dist_window_starts"):               # (a tuning build of an older tree loaded through GS_LIB may predate rank-local ingestion)
-        L.gs_dist_window_starts.argtypes = [vp, C.POINTER(C.c_int32), C.c_int32]
-        L.gs_dist_local_landmark_windows.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32]
-        L.gs_dist_set_landmark_windows.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_int32]
-        L.gs_dist_share_landmark_windows.argtypes = [vp]
-    L.gs_add_pose.argtypes = [vp, C.c_int32, _dp]
-    L.gs_add_landmark.argtypes = [vp, C.c_int32, _dp]
-    L.gs_add_odometry_edge.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp]
-    L.gs_add_observation_edge.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp]
-    L.gs_add_poses.argtypes = [vp, C.c_int32, _ip, _dp]
-    L.gs_add_landmarks.argtypes = [vp, C.c_int32, _ip, _dp]
-    L.gs_add_odometry_edges.argtypes = [vp, C.c_int32, _ip, _ip, _dp, _dp]
-    L.gs_add_observation_edges.argtypes = [vp, C.c_int32, _ip, _ip, _dp, _dp]
-    L.gs_set_fixed_pose.argtypes = [vp, C.c_int32, C.c_int32]
-    L.gs_set_fixed_landmark.argtypes = [vp, C.c_int32, C.c_int32]
-    L.gs_set_pose_estimate.argtypes = [vp, C.c_int32, _dp]
-    L.gs_set_landmark_estimate.argtypes = [vp, C.c_int32, _dp]
-    L.gs_get_pose.argtypes = [vp, C.c_int32, _dp]
-    L.gs_get_landmark.argtypes = [vp, C.c_int32, _dp]
-    L.gs_get_poses.argtypes = [vp, C.c_int32, _ip, _dp]
-    L.gs_get_landmarks.argtypes = [vp, C.c_int32, _ip, _dp]
-    L.gs_optimize.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
-    L.gs_optimize_until.argtypes = [vp, C.c_int32, C.c_double, C.POINTER(Stats)]
-    L.gs_debug_fail_at_iteration.argtypes = [vp, C.c_int32, C.c_int32]
-    L.gs_debug_select_factor_variant.argtypes = [C.c_int32, C.c_int32, C.c_int64]
-    L.gs_debug_options_default.argtypes = [C.POINTER(DebugOptions)]
-    L.gs_debug_get_options.argtypes = [vp, C.POINTER(DebugOptions)]
-    L.gs_debug_set_options.argtypes = [vp, C.POINTER(DebugOptions)]
-    L.gs_chi2.argtypes = [vp, _dp]
-    L.gs_get_stats.argtypes = [vp, C.POINTER(Stats)]
-    L.gs_time_linearize.argtypes = [vp, C.c_int32, _dp]
-    L.gs_export_system.argtypes = [vp, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip]
-    L.gs_export_delta.argtypes = [vp, _dp, _dp]
-    L.gs_time_iterations.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
-    L.gs_plan_build_host.argtypes = [vp, C.POINTER(PlanInfo)]
-    L.gs_plan_export.argtypes = [vp, _ip, C.POINTER(C.c_int64)]
-    if hasattr(L, "gs_debug_schedule_export"):             # (a tuning build of an older tree loaded through GS_LIB may predate the schedule)
-        L.gs_debug_schedule_export.argtypes = [vp, _ip, C.POINTER(C.c_int64)]
-    L.gs_reserve_device.argtypes = [vp, C.c_int64]
-    L.gs_plan_growths.argtypes = [vp]; L.gs_growth_refusal.argtypes = [vp]; L.gs_growth_refusal.restype = C.c_char_p
-    L.gs_polar_to_xy_batch.argtypes = [vp, C.c_int32, _dp, _dp, _dp, _dp]
-    L.gs_cone_to_global_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _ip, _dp, _dp]
-    L.gs_associate_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32, _dp, _ip,
-                                     C.c_double, C.c_double, _ip]
-    L.gs_associate_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_double, C.c_double, vp]
-    L.gs_debug_time_associate_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_double, C.c_double, vp, C.c_int32, _dp]
-    L.gs_map_clear.argtypes = [vp]; L.gs_map_size.argtypes = [vp]
-    L.gs_map_append.argtypes = [vp, C.c_int32, _dp, _ip]
-    L.gs_map_set_xy.argtypes = [vp, C.c_int32, C.c_int32, _dp]
-    L.gs_frame_frontend.argtypes = [vp, _dp, _dp, C.c_int32, C.c_double, C.c_double, C.c_int32, _dp, _dp, _ip]
-    L.gs_dist_unique_id.argtypes = [C.c_char_p]
-    L.gs_dist_comm_init.argtypes = [vp, C.c_char_p, C.c_int32, C.c_int32]
-    L.gs_dist_set_communicator.argtypes = [vp, vp]
-    L.gs_dist_iterate.argtypes = [vp]
-    L.gs_dist_optimize.argtypes = [vp, C.c_int32, C.POINTER(Stats)]
-    L.gs_debug_time_exchange.argtypes = [vp, C.c_int32, _dp]
-    L.gs_dist_read_exchange.argtypes = [vp, _dp]
-    L.gs_dist_write_exchange.argtypes = [vp, _dp]
-    u8 = C.POINTER(C.c_uint8)
-    L.gs_dist_known.argtypes = [vp, u8, u8, u8, u8]
-    L.gs_slam_collect_extract.argtypes = [vp, C.POINTER(C.c_int32), _dp]
-    L.gs_shell_create.argtypes = [C.c_int32, C.POINTER(C.c_char_p), C.c_int32, C.POINTER(vp)]
-    L.gs_shell_destroy.argtypes = [vp]
-    L.gs_shell_on_message.argtypes = [vp, C.POINTER(ShellMsg), C.c_int64]
-    L.gs_shell_poll.argtypes = [vp, C.c_int64]
-    L.gs_shell_pending_output.argtypes = [vp]
-    L.gs_shell_take_output.argtypes = [vp, C.c_int32, C.POINTER(ShellMsg)]
-    L.gs_shell_counters.argtypes = [vp, C.POINTER(C.c_int64)]
-    L.gs_shell_cid.argtypes = [vp]
-    L.gs_shell_slam.argtypes = [vp]; L.gs_shell_slam.restype = vp
-    L.gs_slam_perform.argtypes = [vp, _dp, _dp, C.c_int32]
-    L.gs_slam_get_map.argtypes = [vp, C.c_int32, _dp, _ip]
-    if hasattr(L, "gs_compute_marginals"):                 # (a tuning build of an older tree loaded through GS_LIB may predate the marginals)
-        L.gs_slam_get_map_covariances.argtypes = [vp, C.c_int32, _dp]
-        L.gs_compute_marginals.argtypes = [vp, C.POINTER(MarginalsInfo)]
-        L.gs_get_pose_covariances.argtypes = [vp, C.c_int32, _ip, _dp]
-        L.gs_get_landmark_covariances.argtypes = [vp, C.c_int32, _ip, _dp]
-        L.gs_get_odometry_edge_covariances.argtypes = [vp, C.c_int32, _dp]
-        L.gs_get_observation_edge_covariances.argtypes = [vp, C.c_int32, _dp]
-        L.gs_get_covariance_block.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp]
-    if hasattr(L, "gs_associate_nn_batch"):                # (the same for the covariance-gated association)
-        npp = C.POINTER(NnParams)
-        L.gs_nn_params_default.argtypes = [npp]
-        L.gs_map_set_cov.argtypes = [vp, C.c_int32, C.c_int32, _dp]
-        L.gs_map_get_cov.argtypes = [vp, C.c_int32, C.c_int32, _dp]
-        L.gs_map_set_cov_from_marginals.argtypes = [vp, C.c_int32, C.c_int32, _ip]
-        L.gs_associate_nn_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32, _dp, _ip, _dp, _dp, npp, _ip, _dp, _dp]
-        L.gs_associate_nn_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, npp, vp, vp, vp]
-        L.gs_debug_time_associate_nn_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp, npp, vp, vp, vp, C.c_int32, _dp]
-        L.gs_frame_frontend_nn.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, _dp, _dp, _ip, _dp, _dp]
-    if hasattr(L, "gs_assign_nn_batch"):                   # (and for the one-to-one association)
-        npp = C.POINTER(NnParams)
-        L.gs_assign_nn_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32, _ip, C.c_int32, _dp, _ip, _dp, _dp, npp, _ip, _dp]
-        L.gs_assign_nn_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, vp, vp]
-        L.gs_debug_time_assign_nn_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, vp, vp, C.c_int32, _dp]
-        L.gs_frame_frontend_assign.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, _dp, _dp, _ip, _dp]
-    if hasattr(L, "gs_assign_opt_batch"):                  # (and for the minimum-cost association)
-        npp = C.POINTER(NnParams)
-        L.gs_assign_opt_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32, _ip, C.c_int32, _dp, _ip, _dp, _dp, npp, _ip, _dp, _ip]
-        L.gs_assign_opt_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, vp, vp, vp]
-        L.gs_debug_time_assign_opt_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, vp, vp, vp, C.c_int32, _dp]
-        L.gs_frame_frontend_assign_opt.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, _dp, _dp, _ip, _dp, _ip]
-    if hasattr(L, "gs_joint_compat_batch"):                # (and for the joint compatibility test)
-        npp = C.POINTER(NnParams); jpp = C.POINTER(JcParams)
-        L.gs_jc_params_default.argtypes = [jpp]
-        L.gs_jc_params_set_confidence.argtypes = [jpp, C.c_double]
-        L.gs_joint_compat_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32, _ip, C.c_int32, _dp, _dp, _dp, npp, jpp, _ip, _ip, _dp, _ip, _ip, _ip, _dp]
-        L.gs_joint_compat_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, jpp, vp, vp, vp, vp, vp, vp, vp]
-        L.gs_debug_time_joint_compat_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, jpp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, _dp]
-        L.gs_frame_frontend_jc.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, jpp, _dp, _dp, _ip, _dp, _ip, _dp, _ip, _ip, _ip, _dp]
-    if hasattr(L, "gs_localize_batch"):                    # (and for frame localisation)
-        npp = C.POINTER(NnParams); jpp = C.POINTER(JcParams); lpp = C.POINTER(LocParams)
-        L.gs_loc_params_default.argtypes = [lpp]
-        L.gs_debug_localize.argtypes = [vp, C.c_int32, vp]
-        L.gs_localize_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _ip, _dp, C.c_int32, _ip, C.c_int32, _dp, _dp, _dp, npp, lpp, _ip, _dp, _dp, _dp, _ip, _ip, _ip]
-        L.gs_localize_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, lpp, vp, vp, vp, vp, vp, vp, vp]
-        L.gs_debug_time_localize_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, lpp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, _dp]
-        L.gs_frame_frontend_localize.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, jpp, lpp, _dp, _dp, _ip, _dp, _ip, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
-    if hasattr(L, "gs_relocalize_batch"):                  # (and for relocalisation)
-        npp = C.POINTER(NnParams); jpp = C.POINTER(JcParams); lpp = C.POINTER(LocParams); rpp = C.POINTER(RelocParams); _lp = C.POINTER(C.c_int64)
-        L.gs_reloc_params_default.argtypes = [rpp]
-        L.gs_debug_relocalize.argtypes = [vp, C.c_int32]
-        L.gs_relocalize_batch.argtypes = [vp, C.c_int32, _dp, C.c_int32, _ip, C.c_int32, _dp, _ip, rpp, _dp, _ip, _dp, _ip, _ip, _dp, _lp, _ip, _ip, _dp]
-        L.gs_relocalize_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, rpp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.gs_debug_time_relocalize_resident.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, rpp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int32, _dp]
-        L.gs_frame_frontend_relocalize.argtypes = [vp, _dp, C.c_int32, rpp, C.c_double, C.c_double, npp, jpp, lpp, _dp, _ip, _dp, _ip, _ip, _dp, _lp, _ip, _ip, _dp,
-                                                   _dp, _dp, _ip, _dp, _ip, _dp, _ip, _ip, _ip, _dp, _dp, _dp, _dp, _ip, _ip, _ip]
-    if hasattr(L, "gs_follow_batch"):                      # (and for frame following)
-        npp = C.POINTER(NnParams); jpp = C.POINTER(JcParams); lpp = C.POINTER(LocParams); fpp = C.POINTER(FollowParams)
-        L.gs_follow_params_default.argtypes = [fpp]
-        L.gs_follow_batch.argtypes = [vp, C.c_int32, _dp, _dp, C.c_int32, C.c_int32, _dp, _ip, _dp, _dp, C.c_int32, _dp, _ip, _dp, npp, jpp, lpp, fpp, vp, _ip, vp, _ip, _ip]
-        L.gs_follow_resident.argtypes = [vp, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, npp, jpp, lpp, fpp, vp, vp, vp, vp]
-        L.gs_debug_time_follow_resident.argtypes = L.gs_follow_resident.argtypes + [C.c_int32, _dp]
-        L.gs_follow_set.argtypes = [vp, C.c_int32, _dp, _dp]
-        L.gs_follow_get.argtypes = [vp, vp, _ip, _ip, _ip]
-        L.gs_frame_frontend_follow.argtypes = [vp, _dp, _dp, _dp, C.c_int32, npp, jpp, lpp, fpp, vp, _ip, _ip, _ip]
-    if hasattr(L, "gs_cand_batch"):                        # (and for the cone candidates)
-        npp = C.POINTER(NnParams); cpp = C.POINTER(CandParams)
-        L.gs_cand_params_default.argtypes = [cpp]
-        L.gs_cand_batch.argtypes = [vp, C.c_int32, C.c_int32, _dp, _ip, _dp, _dp, _ip, C.c_int32, vp, npp, cpp, vp, _ip, _ip, vp, _ip]
-        L.gs_cand_resident.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.c_int32, vp, vp, vp, C.c_int32, vp, npp, cpp, vp, vp, vp, vp, vp]
-        L.gs_debug_time_cand_resident.argtypes = L.gs_cand_resident.argtypes + [C.c_int32, _dp]
-        L.gs_cand_clear.argtypes = [vp]
-        L.gs_cand_set.argtypes = [vp, C.c_int32, vp]
-        L.gs_cand_get.argtypes = [vp, vp, _ip, _ip, _ip]
-        L.gs_cand_take_confirmed.argtypes = [vp, C.c_int32, vp, _ip]
-        L.gs_frame_frontend_candidates.argtypes = [vp, _dp, _dp, _dp, C.c_int32, _ip, npp, cpp, vp, _ip, _ip]
-    if hasattr(L, "gs_map_twins_batch"):                   # (and for the map twins)
-        upp = C.POINTER(DupParams)
-        L.gs_dup_params_default.argtypes = [upp]
-        L.gs_map_twins_batch.argtypes = [vp, C.c_int32, _dp, _ip, _dp, upp, _ip, _dp, _dp, _ip]
-        L.gs_map_twins_resident.argtypes = [vp, upp, vp, vp, vp, vp]
-        L.gs_debug_time_map_twins_resident.argtypes = [vp, upp, vp, vp, vp, vp, C.c_int32, _dp]
-        L.gs_debug_time_map_merge_twins.argtypes = [vp, upp, C.c_int32, _dp]
-        L.gs_map_merge_twins_batch.argtypes = [vp, C.c_int32, _dp, _ip, _dp, upp, _dp, _ip, _dp, _ip, vp]
-        L.gs_map_merge_twins.argtypes = [vp, upp, C.c_int32, _ip, vp]
-        L.gs_map_get_xy.argtypes = [vp, C.c_int32, C.c_int32, _dp, _ip]
-        L.gs_merge_landmarks.argtypes = [vp, C.c_int32, C.c_int32]
-    if hasattr(L, "gs_set_robust_kernel"):                # (a tuning build of an older tree loaded through GS_LIB may predate the robust kernels)
-        L.gs_set_robust_kernel.argtypes = [vp, C.c_int32, C.c_int32, C.c_double]
-        L.gs_get_robust_kernel.argtypes = [vp, C.c_int32, _ip, _dp]
-        L.gs_get_edge_chi2.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp]
-    if hasattr(L, "gs_optimize_lm"):                       # (a tuning build of an older tree loaded through GS_LIB may predate Levenberg-Marquardt)
-        L.gs_lm_params_default.argtypes = [C.POINTER(LmParams)]
-        L.gs_optimize_lm.argtypes = [vp, C.c_int32, C.POINTER(LmParams), C.POINTER(Stats), C.POINTER(LmInfo)]
-    if hasattr(L, "gs_optimize_dogleg"):                   # (the same for the dogleg and the Hessian-vector product)
-        L.gs_dogleg_params_default.argtypes = [C.POINTER(DoglegParams)]
-        L.gs_optimize_dogleg.argtypes = [vp, C.c_int32, C.POINTER(DoglegParams), C.POINTER(Stats), C.POINTER(DoglegInfo)]
-        L.gs_multiply_hessian.argtypes = [vp, _dp, _dp, _dp, _dp]
-    if hasattr(L, "gs_add_pose_prior"):                    # (a tuning build of an older tree loaded through GS_LIB may predate the prior edges)
-        for name in ("gs_add_pose_prior", "gs_add_pose_xy_prior", "gs_add_landmark_prior"):
-            getattr(L, name).argtypes = [vp, C.c_int32, _dp, _dp]
-        for name in ("gs_add_pose_priors", "gs_add_pose_xy_priors", "gs_add_landmark_priors"):
-            getattr(L, name).argtypes = [vp, C.c_int32, _ip, _dp, _dp]
-        for name in ("gs_num_pose_priors", "gs_num_landmark_priors", "gs_clear_priors"):
-            getattr(L, name).argtypes = [vp]
-        L.gs_get_prior_chi2.argtypes = [vp, C.c_int32, C.c_int32, _dp]
-    if hasattr(L, "gs_set_edge_active"):                   # (the same for edge deactivation)
-        u8p = C.POINTER(C.c_uint8)
-        L.gs_set_edge_active.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32]
-        L.gs_set_edges_active.argtypes = [vp, C.c_int32, C.c_int32, _ip, u8p]
-        L.gs_get_edges_active.argtypes = [vp, C.c_int32, C.c_int32, u8p]
-        L.gs_activate_all_edges.argtypes = [vp]
-        L.gs_num_inactive_edges.argtypes = [vp, C.c_int32]
-        L.gs_find_isolated_vertex.argtypes = [vp, _ip, _ip]
-        L.gs_deactivate_edges_above.argtypes = [vp, C.c_int32, C.c_double, C.c_int32, _ip]
-    if hasattr(L, "gs_add_range_bearing_edge"):            # (the same for the polar observation edges)
-        L.gs_add_range_bearing_edge.argtypes = [vp, C.c_int32, C.c_int32, _dp, _dp]
-        L.gs_add_bearing_edge.argtypes = [vp, C.c_int32, C.c_int32, C.c_double, C.c_double]
-        L.gs_add_range_bearing_edges.argtypes = [vp, C.c_int32, _ip, _ip, _dp, _dp]
-        L.gs_add_bearing_edges.argtypes = [vp, C.c_int32, _ip, _ip, _dp, _dp]
-        L.gs_num_polar_edges.argtypes = [vp]
-        L.gs_get_polar_edges.argtypes = [vp, C.c_int32, _ip, _ip]
-    L.gs_slam_get_send_pose.argtypes = [vp, _dp]
-    L.gs_slam_collect_direction.argtypes = [vp, C.c_uint32, C.c_double, C.c_double]
-    L.gs_slam_collect_distance.argtypes = [vp, C.c_uint32, C.c_double]
-    L.gs_slam_collect_type.argtypes = [vp, C.c_uint32, C.c_uint32]
-    L.gs_slam_collect_flush.argtypes = [vp, _dp, C.POINTER(C.c_int32), _dp]
-    L.gs_slam_encode_cones.argtypes = [vp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_int32)]
-    L.gs_cone_encode.argtypes = [_dp, _dp, C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.gs_wgs84_to_cartesian.argtypes = [_dp, _dp, _dp]
-    L.gs_wgs84_from_cartesian.argtypes = [_dp, _dp, _dp]
-    L.gs_slam_set_gps_reference.argtypes = [vp, C.c_double, C.c_double]
-    L.gs_slam_next_wgs84.argtypes = [vp, C.c_double, C.c_double]
-    L.gs_slam_next_heading.argtypes = [vp, C.c_double]
-    L.gs_slam_next_geolocation.argtypes = [vp, C.c_double, C.c_double, C.c_double]
-    L.gs_slam_next_yaw_rate.argtypes = [vp, C.c_double]
-    L.gs_slam_get_odometry.argtypes = [vp, _dp]
-    L.gs_slam_set_sample_times.argtypes = [vp, C.c_int64, C.c_int64]
-    L.gs_slam_encode_pose.argtypes = [vp, C.POINTER(C.c_float)]
-    _lib = L
-    return L
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError("libgraphslam_hip.so is missing (run __graft_entry__.build()); "
+                               "the GraphSLAM back-end has no CPU fallback")
+        L = C.CDLL(LIB_PATH)
+        for fn, (restype, argtypes) in PROTOTYPES.items():
+            f = getattr(L, fn, None)
+            if f is not None:
+                f.restype = restype; f.argtypes = argtypes
+        _lib = L
+    return _lib
 
 
 def _f64(a, shape=None):
@@ -599,6 +231,16 @@ def _d(a):
 
 def _i(a):
     return a.ctypes.data_as(_ip)
+
+
+def _vp(a):
+    """an array of records, for a parameter declared as a pointer to the record struct"""
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _ptr(a):
+    """the address of an optional DeviceArray"""
+    return None if a is None else a.ptr
 
 
 def default_config(**kw):
@@ -666,31 +308,6 @@ def dist_unique_id():
     if rc < 0:
         raise GsError(rc, (lib().gs_last_error() or b"").decode())
     return buf.raw
-
-
-def _step_params(cls, default, name, fields, kw):
-    """a step-control method's parameter struct: its defaults with the named fields replaced (max_trials: short for max_trials_after_failure)"""
-    p = cls()
-    rc = default(C.byref(p))
-    if rc < 0:
-        raise GsError(rc, (lib().gs_last_error() or b"").decode())
-    if "max_trials" in kw:
-        kw["max_trials_after_failure"] = kw.pop("max_trials")
-    for k, v in kw.items():
-        if k not in ("max_trials_after_failure",) + fields:
-            raise AttributeError("%s has no field %r" % (name, k))
-        setattr(p, k, v)
-    return p
-
-
-def lm_params(**kw):
-    """gs_lm_params_default with the named fields replaced (max_trials: short for max_trials_after_failure)"""
-    return _step_params(LmParams, lib().gs_lm_params_default, "gs_lm_params", ("initial_lambda", "tau"), kw)
-
-
-def dogleg_params(**kw):
-    """gs_dogleg_params_default with the named fields replaced (max_trials: short for max_trials_after_failure)"""
-    return _step_params(DoglegParams, lib().gs_dogleg_params_default, "gs_dogleg_params", ("initial_delta",), kw)
 
 
 def device_count():
@@ -871,7 +488,7 @@ class Graph:
         self._check(self.L.gs_linearize(self.h))
 
     def time_linearize(self, reps):
-        o = C.c_double(); self._check(self.L.gs_time_linearize(self.h, int(reps), C.byref(o))); return o.value
+        return self._timed(self.L.gs_time_linearize, [self.h], reps)
 
     def linearize_bytes(self):
         return int(self.L.gs_linearize_bytes(self.h))
@@ -1114,16 +731,48 @@ class Graph:
                                               _d(map_xy), _i(map_type), float(thr), float(type_tol), _i(out)))
         return out
 
+    # ---- what the call families below share.  A family's C argument list is built in one place: _<family>_resident_args serves the resident
+    # call and, through _timed, its time_* twin; _batch_args makes the host inputs of a batch call.  The frame_frontend_* calls keep their
+    # prologue inline: a helper there measured 3 to 5 % on a 30 microsecond call.  A numpy array lives as long as the pointer made
+    # from it, a parameter struct as long as its byref: the lists keep both.
+    def _timed(self, fn, args, reps):
+        """a gs_*time_* entry point: the arguments of the call it repeats, then (reps, out_ms); mean milliseconds per call"""
+        ms = C.c_double(); self._check(fn(*args, int(reps), C.byref(ms))); return ms.value
+
+    def _batch_args(self, poses, pose_of_obs, obs, map_xy, map_type, map_cov, pose_cov, frame_start=None, typed=True):
+        """the host inputs of a batch call, converted and checked: (n, n_frames or None, the C arguments from the handle to the covariances);
+        frame_start: the call takes frames; typed=False: it takes no map types"""
+        poses = _f64(poses, (-1, 3)); obs = _f64(obs, (-1, 4)); po = _i32(pose_of_obs); map_xy = _f64(map_xy, (-1, 2)); nf = None
+        mc = None if map_cov is None else _f64(map_cov, (-1, 4)); pc = None if pose_cov is None else _f64(pose_cov, (-1, 9))
+        assert mc is None or len(mc) == len(map_xy); assert pc is None or len(pc) == len(poses)
+        a = [self.h, len(obs), _d(poses), len(poses), _i(po), _d(obs)]
+        if frame_start is not None:
+            fs = _i32(frame_start); nf = len(fs) - 1
+            assert len(fs) >= 1
+            a += [nf, _i(fs)]
+        a += [len(map_xy), _d(map_xy)]
+        if typed:
+            a.append(_i(_i32(map_type)))
+        return len(obs), nf, a + [None if mc is None else _d(mc), None if pc is None else _d(pc)]
+
+    def _resident_head(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, d_pose_cov, params, n_frames=None, d_frame_start=None):
+        """what a resident call against the map's covariances begins with: the handle, the observations and their poses, the frames where the
+        call takes them, the pose covariances, the gs_nn_params"""
+        a = [self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr]
+        if d_frame_start is not None:
+            a += [int(n_frames), d_frame_start.ptr]
+        return a + [_ptr(d_pose_cov), C.byref(nn_params() if params is None else params)]
+
     # ---- per-keyframe front end against the resident map
+    def _associate_resident_args(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, thr, d_out, type_tol):
+        return [self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, float(thr), float(type_tol), d_out.ptr]
+
     def associate_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, thr, d_out, type_tol=1e-4):
         """gs_associate_resident: the resident map (map_append), everything else DeviceArray; asynchronous (synchronize() before reading d_out)."""
-        self._check(self.L.gs_associate_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, float(thr), float(type_tol), d_out.ptr))
+        self._check(self.L.gs_associate_resident(*self._associate_resident_args(d_poses, n_poses, d_pose_of_obs, d_obs, n, thr, d_out, type_tol)))
 
     def time_associate_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, thr, d_out, reps, type_tol=1e-4):
-        ms = C.c_double()
-        self._check(self.L.gs_debug_time_associate_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, float(thr), float(type_tol), d_out.ptr,
-                                                             int(reps), C.byref(ms)))
-        return ms.value
+        return self._timed(self.L.gs_debug_time_associate_resident, self._associate_resident_args(d_poses, n_poses, d_pose_of_obs, d_obs, n, thr, d_out, type_tol), reps)
 
     def map_clear(self): self._check(self.L.gs_map_clear(self.h))
     def map_size(self): return self._check(self.L.gs_map_size(self.h))
@@ -1155,30 +804,23 @@ class Graph:
 
     def associate_nn(self, poses, pose_of_obs, obs, map_xy, map_type, map_cov=None, pose_cov=None, params=None):
         """gs_associate_nn_batch: (index [n] int32, d2 [n], second_d2 [n])"""
-        poses = _f64(poses, (-1, 3)); obs = _f64(obs, (-1, 4)); po = _i32(pose_of_obs)
-        map_xy = _f64(map_xy, (-1, 2)); map_type = _i32(map_type); n = len(obs)
-        mc = None if map_cov is None else _f64(map_cov, (-1, 4)); pc = None if pose_cov is None else _f64(pose_cov, (-1, 9))
-        assert mc is None or len(mc) == len(map_xy); assert pc is None or len(pc) == len(poses)
+        n, _, a = self._batch_args(poses, pose_of_obs, obs, map_xy, map_type, map_cov, pose_cov)
         p = nn_params() if params is None else params
         idx = np.zeros(n, dtype=np.int32); d2 = np.zeros(n); sec = np.zeros(n)
-        self._check(self.L.gs_associate_nn_batch(self.h, n, _d(poses), len(poses), _i(po), _d(obs), len(map_xy), _d(map_xy), _i(map_type),
-                                                 None if mc is None else _d(mc), None if pc is None else _d(pc), C.byref(p), _i(idx), _d(d2), _d(sec)))
+        self._check(self.L.gs_associate_nn_batch(*a, C.byref(p), _i(idx), _d(d2), _d(sec)))
         return idx, d2, sec
+
+    def _associate_nn_resident_args(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, d_out, d_out_d2, d_out_second, d_pose_cov, params):
+        return self._resident_head(d_poses, n_poses, d_pose_of_obs, d_obs, n, d_pose_cov, params) + [d_out.ptr, _ptr(d_out_d2), _ptr(d_out_second)]
 
     def associate_nn_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, d_out, d_out_d2=None, d_out_second=None, d_pose_cov=None, params=None):
         """gs_associate_nn_resident: the resident map and its covariances, everything else DeviceArray; asynchronous (synchronize() before reading)"""
-        p = nn_params() if params is None else params
-        opt = lambda a: None if a is None else a.ptr
-        self._check(self.L.gs_associate_nn_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, opt(d_pose_cov), C.byref(p),
-                                                    d_out.ptr, opt(d_out_d2), opt(d_out_second)))
+        self._check(self.L.gs_associate_nn_resident(*self._associate_nn_resident_args(d_poses, n_poses, d_pose_of_obs, d_obs, n, d_out, d_out_d2, d_out_second,
+                                                                                      d_pose_cov, params)))
 
     def time_associate_nn_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, d_out, reps, d_out_d2=None, d_out_second=None, d_pose_cov=None, params=None):
-        p = nn_params() if params is None else params
-        opt = lambda a: None if a is None else a.ptr
-        ms = C.c_double()
-        self._check(self.L.gs_debug_time_associate_nn_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, opt(d_pose_cov), C.byref(p),
-                                                               d_out.ptr, opt(d_out_d2), opt(d_out_second), int(reps), C.byref(ms)))
-        return ms.value
+        return self._timed(self.L.gs_debug_time_associate_nn_resident,
+                           self._associate_nn_resident_args(d_poses, n_poses, d_pose_of_obs, d_obs, n, d_out, d_out_d2, d_out_second, d_pose_cov, params), reps)
 
     def frame_frontend_nn(self, pose, obs, pose_cov=None, params=None):
         """(zxy [k,2], gxy [k,2], idx [k], d2 [k], second_d2 [k]) of one frame's observations [k,4] against the resident map and its covariances"""
@@ -1191,30 +833,23 @@ class Graph:
     # ---- one-to-one association (include/graphslam.h): frame f is the observations [frame_start[f], frame_start[f + 1])
     def assign_nn(self, poses, pose_of_obs, obs, frame_start, map_xy, map_type, map_cov=None, pose_cov=None, params=None):
         """gs_assign_nn_batch: (index [n] int32, d2 [n])"""
-        poses = _f64(poses, (-1, 3)); obs = _f64(obs, (-1, 4)); po = _i32(pose_of_obs); fs = _i32(frame_start)
-        map_xy = _f64(map_xy, (-1, 2)); map_type = _i32(map_type); n = len(obs)
-        mc = None if map_cov is None else _f64(map_cov, (-1, 4)); pc = None if pose_cov is None else _f64(pose_cov, (-1, 9))
-        assert mc is None or len(mc) == len(map_xy); assert pc is None or len(pc) == len(poses); assert len(fs) >= 1
+        n, _, a = self._batch_args(poses, pose_of_obs, obs, map_xy, map_type, map_cov, pose_cov, frame_start)
         p = nn_params() if params is None else params
         idx = np.zeros(n, dtype=np.int32); d2 = np.zeros(n)
-        self._check(self.L.gs_assign_nn_batch(self.h, n, _d(poses), len(poses), _i(po), _d(obs), len(fs) - 1, _i(fs), len(map_xy), _d(map_xy), _i(map_type),
-                                              None if mc is None else _d(mc), None if pc is None else _d(pc), C.byref(p), _i(idx), _d(d2)))
+        self._check(self.L.gs_assign_nn_batch(*a, C.byref(p), _i(idx), _d(d2)))
         return idx, d2
+
+    def _assign_nn_resident_args(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_out, d_out_d2, d_pose_cov, params):
+        return self._resident_head(d_poses, n_poses, d_pose_of_obs, d_obs, n, d_pose_cov, params, n_frames, d_frame_start) + [d_out.ptr, _ptr(d_out_d2)]
 
     def assign_nn_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_out, d_out_d2=None, d_pose_cov=None, params=None):
         """gs_assign_nn_resident: the resident map and its covariances, everything else DeviceArray; asynchronous (synchronize() before reading)"""
-        p = nn_params() if params is None else params
-        opt = lambda a: None if a is None else a.ptr
-        self._check(self.L.gs_assign_nn_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, int(n_frames), d_frame_start.ptr,
-                                                 opt(d_pose_cov), C.byref(p), d_out.ptr, opt(d_out_d2)))
+        self._check(self.L.gs_assign_nn_resident(*self._assign_nn_resident_args(d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_out, d_out_d2,
+                                                                                d_pose_cov, params)))
 
     def time_assign_nn_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_out, reps, d_out_d2=None, d_pose_cov=None, params=None):
-        p = nn_params() if params is None else params
-        opt = lambda a: None if a is None else a.ptr
-        ms = C.c_double()
-        self._check(self.L.gs_debug_time_assign_nn_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, int(n_frames), d_frame_start.ptr,
-                                                            opt(d_pose_cov), C.byref(p), d_out.ptr, opt(d_out_d2), int(reps), C.byref(ms)))
-        return ms.value
+        return self._timed(self.L.gs_debug_time_assign_nn_resident,
+                           self._assign_nn_resident_args(d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_out, d_out_d2, d_pose_cov, params), reps)
 
     def frame_frontend_assign(self, pose, obs, pose_cov=None, params=None):
         """(zxy [k,2], gxy [k,2], idx [k], d2 [k]) of one frame's observations [k,4], each cone given to at most one of them"""
@@ -1227,30 +862,25 @@ class Graph:
     # ---- minimum-cost association (include/graphslam.h): the same frames, the matching of largest total gain over each observation's 8 best cones
     def assign_opt(self, poses, pose_of_obs, obs, frame_start, map_xy, map_type, map_cov=None, pose_cov=None, params=None):
         """gs_assign_opt_batch: (index [n] int32, d2 [n], n_admissible [n] int32)"""
-        poses = _f64(poses, (-1, 3)); obs = _f64(obs, (-1, 4)); po = _i32(pose_of_obs); fs = _i32(frame_start)
-        map_xy = _f64(map_xy, (-1, 2)); map_type = _i32(map_type); n = len(obs)
-        mc = None if map_cov is None else _f64(map_cov, (-1, 4)); pc = None if pose_cov is None else _f64(pose_cov, (-1, 9))
-        assert mc is None or len(mc) == len(map_xy); assert pc is None or len(pc) == len(poses); assert len(fs) >= 1
+        n, _, a = self._batch_args(poses, pose_of_obs, obs, map_xy, map_type, map_cov, pose_cov, frame_start)
         p = nn_params() if params is None else params
         idx = np.zeros(n, dtype=np.int32); d2 = np.zeros(n); na = np.zeros(n, dtype=np.int32)
-        self._check(self.L.gs_assign_opt_batch(self.h, n, _d(poses), len(poses), _i(po), _d(obs), len(fs) - 1, _i(fs), len(map_xy), _d(map_xy), _i(map_type),
-                                               None if mc is None else _d(mc), None if pc is None else _d(pc), C.byref(p), _i(idx), _d(d2), _i(na)))
+        self._check(self.L.gs_assign_opt_batch(*a, C.byref(p), _i(idx), _d(d2), _i(na)))
         return idx, d2, na
+
+    def _assign_opt_resident_args(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_out, d_out_d2, d_out_na, d_pose_cov, params):
+        return (self._resident_head(d_poses, n_poses, d_pose_of_obs, d_obs, n, d_pose_cov, params, n_frames, d_frame_start)
+                + [d_out.ptr, _ptr(d_out_d2), _ptr(d_out_na)])
 
     def assign_opt_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_out, d_out_d2=None, d_out_na=None, d_pose_cov=None, params=None):
         """gs_assign_opt_resident: the resident map and its covariances, everything else DeviceArray; asynchronous (synchronize() before reading)"""
-        p = nn_params() if params is None else params
-        opt = lambda a: None if a is None else a.ptr
-        self._check(self.L.gs_assign_opt_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, int(n_frames), d_frame_start.ptr,
-                                                  opt(d_pose_cov), C.byref(p), d_out.ptr, opt(d_out_d2), opt(d_out_na)))
+        self._check(self.L.gs_assign_opt_resident(*self._assign_opt_resident_args(d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_out, d_out_d2,
+                                                                                  d_out_na, d_pose_cov, params)))
 
     def time_assign_opt_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_out, reps, d_out_d2=None, d_out_na=None, d_pose_cov=None, params=None):
-        p = nn_params() if params is None else params
-        opt = lambda a: None if a is None else a.ptr
-        ms = C.c_double()
-        self._check(self.L.gs_debug_time_assign_opt_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, int(n_frames), d_frame_start.ptr,
-                                                             opt(d_pose_cov), C.byref(p), d_out.ptr, opt(d_out_d2), opt(d_out_na), int(reps), C.byref(ms)))
-        return ms.value
+        return self._timed(self.L.gs_debug_time_assign_opt_resident,
+                           self._assign_opt_resident_args(d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_out, d_out_d2, d_out_na, d_pose_cov,
+                                                          params), reps)
 
     def frame_frontend_assign_opt(self, pose, obs, pose_cov=None, params=None):
         """(zxy [k,2], gxy [k,2], idx [k], d2 [k], n_admissible [k]) of one frame's observations [k,4], matched at least total d2"""
@@ -1264,95 +894,85 @@ class Graph:
     # A frame's record is a dict: joint_d2 [f], n_kept / n_dropped / n_untestable [f] int32, delta [f,3]
     def joint_compat(self, poses, pose_of_obs, obs, frame_start, map_xy, in_index, map_cov=None, pose_cov=None, params=None, jc=None):
         """gs_joint_compat_batch: (index [n] int32, record)"""
-        poses = _f64(poses, (-1, 3)); obs = _f64(obs, (-1, 4)); po = _i32(pose_of_obs); fs = _i32(frame_start); ii = _i32(in_index)
-        map_xy = _f64(map_xy, (-1, 2)); n = len(obs); nf = len(fs) - 1
-        mc = None if map_cov is None else _f64(map_cov, (-1, 4)); pc = None if pose_cov is None else _f64(pose_cov, (-1, 9))
-        assert mc is None or len(mc) == len(map_xy); assert pc is None or len(pc) == len(poses); assert len(fs) >= 1 and len(ii) == n
+        n, nf, a = self._batch_args(poses, pose_of_obs, obs, map_xy, None, map_cov, pose_cov, frame_start, typed=False)
+        ii = _i32(in_index)
+        assert len(ii) == n
         p = nn_params() if params is None else params; j = jc_params() if jc is None else jc
-        idx = np.zeros(n, dtype=np.int32); rec = _jc_record(nf)
-        self._check(self.L.gs_joint_compat_batch(self.h, n, _d(poses), len(poses), _i(po), _d(obs), nf, _i(fs), len(map_xy), _d(map_xy),
-                                                 None if mc is None else _d(mc), None if pc is None else _d(pc), C.byref(p), C.byref(j), _i(ii), _i(idx),
-                                                 _d(rec["joint_d2"]), _i(rec["n_kept"]), _i(rec["n_dropped"]), _i(rec["n_untestable"]), _d(rec["delta"])))
+        idx = np.zeros(n, dtype=np.int32); rec, ra = _jc_record(nf)
+        self._check(self.L.gs_joint_compat_batch(*a, C.byref(p), C.byref(j), _i(ii), _i(idx), *ra))
         return idx, rec
+
+    def _joint_compat_resident_args(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_in_index, d_out, d_joint_d2, d_n_kept, d_n_dropped,
+                                    d_n_untestable, d_delta, d_pose_cov, params, jc):
+        return (self._resident_head(d_poses, n_poses, d_pose_of_obs, d_obs, n, d_pose_cov, params, n_frames, d_frame_start)
+                + [C.byref(jc_params() if jc is None else jc), d_in_index.ptr, d_out.ptr, _ptr(d_joint_d2), _ptr(d_n_kept), _ptr(d_n_dropped), _ptr(d_n_untestable),
+                   _ptr(d_delta)])
 
     def joint_compat_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_in_index, d_out, d_joint_d2=None, d_n_kept=None,
                               d_n_dropped=None, d_n_untestable=None, d_delta=None, d_pose_cov=None, params=None, jc=None):
         """gs_joint_compat_resident: the resident map and its covariances, everything else DeviceArray; asynchronous (synchronize() before reading)"""
-        p = nn_params() if params is None else params; j = jc_params() if jc is None else jc
-        opt = lambda a: None if a is None else a.ptr
-        self._check(self.L.gs_joint_compat_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, int(n_frames), d_frame_start.ptr,
-                                                    opt(d_pose_cov), C.byref(p), C.byref(j), d_in_index.ptr, d_out.ptr, opt(d_joint_d2), opt(d_n_kept),
-                                                    opt(d_n_dropped), opt(d_n_untestable), opt(d_delta)))
+        self._check(self.L.gs_joint_compat_resident(*self._joint_compat_resident_args(d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_in_index, d_out,
+                                                                                      d_joint_d2, d_n_kept, d_n_dropped, d_n_untestable, d_delta, d_pose_cov, params, jc)))
 
     def time_joint_compat_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_in_index, d_out, reps, d_joint_d2=None,
                                    d_n_kept=None, d_n_dropped=None, d_n_untestable=None, d_delta=None, d_pose_cov=None, params=None, jc=None):
-        p = nn_params() if params is None else params; j = jc_params() if jc is None else jc
-        opt = lambda a: None if a is None else a.ptr
-        ms = C.c_double()
-        self._check(self.L.gs_debug_time_joint_compat_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, int(n_frames), d_frame_start.ptr,
-                                                               opt(d_pose_cov), C.byref(p), C.byref(j), d_in_index.ptr, d_out.ptr, opt(d_joint_d2), opt(d_n_kept),
-                                                               opt(d_n_dropped), opt(d_n_untestable), opt(d_delta), int(reps), C.byref(ms)))
-        return ms.value
+        return self._timed(self.L.gs_debug_time_joint_compat_resident,
+                           self._joint_compat_resident_args(d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_in_index, d_out, d_joint_d2, d_n_kept,
+                                                            d_n_dropped, d_n_untestable, d_delta, d_pose_cov, params, jc), reps)
 
     def frame_frontend_jc(self, pose, obs, pose_cov=None, params=None, jc=None):
         """(zxy [k,2], gxy [k,2], pruned idx [k], the assignment's d2 [k] and n_admissible [k], record of the one frame) — gs_frame_frontend_assign_opt
         followed by the joint test of its result"""
         pose = _f64(pose); obs = _f64(obs, (-1, 4)); k = len(obs); pc = None if pose_cov is None else _f64(pose_cov, (9,))
         p = nn_params() if params is None else params; j = jc_params() if jc is None else jc
-        z = np.zeros((k, 2)); gx = np.zeros((k, 2)); idx = np.zeros(k, dtype=np.int32); d2 = np.zeros(k); na = np.zeros(k, dtype=np.int32); rec = _jc_record(1)
+        z = np.zeros((k, 2)); gx = np.zeros((k, 2)); idx = np.zeros(k, dtype=np.int32); d2 = np.zeros(k); na = np.zeros(k, dtype=np.int32); rec, ra = _jc_record(1)
         self._check(self.L.gs_frame_frontend_jc(self.h, _d(pose), None if pc is None else _d(pc), _d(obs), k, C.byref(p), C.byref(j), _d(z), _d(gx), _i(idx), _d(d2), _i(na),
-                                                _d(rec["joint_d2"]), _i(rec["n_kept"]), _i(rec["n_dropped"]), _i(rec["n_untestable"]), _d(rec["delta"])))
+                                                *ra))
         return z, gx, idx, d2, na, rec
 
     # ---- frame localisation (include/graphslam.h): the iterated pose refinement of a frame under its hypothesis.
     # A frame's record is a dict: pose [f,3], cov [f,9], chi2 [f], n_pairs / iterations / status [f] int32
     def localize(self, poses, pose_of_obs, obs, frame_start, map_xy, in_index, map_cov=None, pose_cov=None, params=None, loc=None):
         """gs_localize_batch: the record of every frame"""
-        poses = _f64(poses, (-1, 3)); obs = _f64(obs, (-1, 4)); po = _i32(pose_of_obs); fs = _i32(frame_start); ii = _i32(in_index)
-        map_xy = _f64(map_xy, (-1, 2)); n = len(obs); nf = len(fs) - 1
-        mc = None if map_cov is None else _f64(map_cov, (-1, 4)); pc = None if pose_cov is None else _f64(pose_cov, (-1, 9))
-        assert mc is None or len(mc) == len(map_xy); assert pc is None or len(pc) == len(poses); assert len(fs) >= 1 and len(ii) == n
+        n, nf, a = self._batch_args(poses, pose_of_obs, obs, map_xy, None, map_cov, pose_cov, frame_start, typed=False)
+        ii = _i32(in_index)
+        assert len(ii) == n
         p = nn_params() if params is None else params; l = loc_params() if loc is None else loc
-        rec = _loc_record(nf)
-        self._check(self.L.gs_localize_batch(self.h, n, _d(poses), len(poses), _i(po), _d(obs), nf, _i(fs), len(map_xy), _d(map_xy),
-                                             None if mc is None else _d(mc), None if pc is None else _d(pc), C.byref(p), C.byref(l), _i(ii),
-                                             _d(rec["pose"]), _d(rec["cov"]), _d(rec["chi2"]), _i(rec["n_pairs"]), _i(rec["iterations"]), _i(rec["status"])))
+        rec, ra = _loc_record(nf)
+        self._check(self.L.gs_localize_batch(*a, C.byref(p), C.byref(l), _i(ii), *ra))
         return rec
+
+    def _localize_resident_args(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_in_index, d_pose, d_cov, d_chi2, d_n_pairs, d_iterations,
+                                d_status, d_pose_cov, params, loc):
+        return (self._resident_head(d_poses, n_poses, d_pose_of_obs, d_obs, n, d_pose_cov, params, n_frames, d_frame_start)
+                + [C.byref(loc_params() if loc is None else loc), d_in_index.ptr, _ptr(d_pose), _ptr(d_cov), _ptr(d_chi2), _ptr(d_n_pairs), _ptr(d_iterations),
+                   _ptr(d_status)])
 
     def localize_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_in_index, d_pose=None, d_cov=None, d_chi2=None,
                           d_n_pairs=None, d_iterations=None, d_status=None, d_pose_cov=None, params=None, loc=None):
         """gs_localize_resident: the resident map and its covariances, everything else DeviceArray; asynchronous (synchronize() before reading)"""
-        p = nn_params() if params is None else params; l = loc_params() if loc is None else loc
-        opt = lambda a: None if a is None else a.ptr
-        self._check(self.L.gs_localize_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, int(n_frames), d_frame_start.ptr,
-                                                opt(d_pose_cov), C.byref(p), C.byref(l), d_in_index.ptr, opt(d_pose), opt(d_cov), opt(d_chi2),
-                                                opt(d_n_pairs), opt(d_iterations), opt(d_status)))
+        self._check(self.L.gs_localize_resident(*self._localize_resident_args(d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_in_index, d_pose, d_cov,
+                                                                              d_chi2, d_n_pairs, d_iterations, d_status, d_pose_cov, params, loc)))
 
     def time_localize_resident(self, d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_in_index, reps, d_pose=None, d_cov=None,
                                d_chi2=None, d_n_pairs=None, d_iterations=None, d_status=None, d_pose_cov=None, params=None, loc=None):
-        p = nn_params() if params is None else params; l = loc_params() if loc is None else loc
-        opt = lambda a: None if a is None else a.ptr
-        ms = C.c_double()
-        self._check(self.L.gs_debug_time_localize_resident(self.h, int(n), d_poses.ptr, int(n_poses), d_pose_of_obs.ptr, d_obs.ptr, int(n_frames), d_frame_start.ptr,
-                                                           opt(d_pose_cov), C.byref(p), C.byref(l), d_in_index.ptr, opt(d_pose), opt(d_cov), opt(d_chi2),
-                                                           opt(d_n_pairs), opt(d_iterations), opt(d_status), int(reps), C.byref(ms)))
-        return ms.value
+        return self._timed(self.L.gs_debug_time_localize_resident,
+                           self._localize_resident_args(d_poses, n_poses, d_pose_of_obs, d_obs, n, n_frames, d_frame_start, d_in_index, d_pose, d_cov, d_chi2, d_n_pairs,
+                                                        d_iterations, d_status, d_pose_cov, params, loc), reps)
 
     def debug_localize(self, kernel=-1, d_step=None):
         """gs_debug_localize: force k_localize (0) or k_localize_big (1), -1 by the mean frame size; d_step: a DeviceArray of 3 doubles per frame that
         later localize_resident calls fill with d_f, None to stop"""
-        self._check(self.L.gs_debug_localize(self.h, int(kernel), None if d_step is None else d_step.ptr))
+        self._check(self.L.gs_debug_localize(self.h, int(kernel), _ptr(d_step)))
 
     def frame_frontend_localize(self, pose, obs, pose_cov=None, params=None, jc=None, loc=None):
         """frame_frontend_jc's tuple (zxy, gxy, pruned idx, d2, n_admissible, joint record) + the localisation record of the one frame"""
         pose = _f64(pose); obs = _f64(obs, (-1, 4)); k = len(obs); pc = None if pose_cov is None else _f64(pose_cov, (9,))
         p = nn_params() if params is None else params; j = jc_params() if jc is None else jc; l = loc_params() if loc is None else loc
         z = np.zeros((k, 2)); gx = np.zeros((k, 2)); idx = np.zeros(k, dtype=np.int32); d2 = np.zeros(k); na = np.zeros(k, dtype=np.int32)
-        rec = _jc_record(1); lr = _loc_record(1)
+        (rec, ra), (lr, la) = _jc_record(1), _loc_record(1)
         self._check(self.L.gs_frame_frontend_localize(self.h, _d(pose), None if pc is None else _d(pc), _d(obs), k, C.byref(p), C.byref(j), C.byref(l), _d(z), _d(gx),
-                                                      _i(idx), _d(d2), _i(na), _d(rec["joint_d2"]), _i(rec["n_kept"]), _i(rec["n_dropped"]), _i(rec["n_untestable"]),
-                                                      _d(rec["delta"]), _d(lr["pose"]), _d(lr["cov"]), _d(lr["chi2"]), _i(lr["n_pairs"]), _i(lr["iterations"]),
-                                                      _i(lr["status"])))
+                                                      _i(idx), _d(d2), _i(na), *ra, *la))
         return z, gx, idx, d2, na, rec, lr
 
     # ---- relocalisation (include/graphslam.h): a frame's pose found on the map without a prior.
@@ -1362,29 +982,27 @@ class Graph:
         obs = _f64(obs, (-1, 4)); fs = _i32(frame_start); map_xy = _f64(map_xy, (-1, 2)); mt = _i32(map_type); n = len(obs); nf = len(fs) - 1
         assert len(fs) >= 1 and len(mt) == len(map_xy)
         p = reloc_params() if params is None else params
-        rec = _reloc_record(nf); idx = np.zeros(n, dtype=np.int32); e2 = np.zeros(n); lp = C.POINTER(C.c_int64)
-        self._check(self.L.gs_relocalize_batch(self.h, n, _d(obs), nf, _i(fs), len(map_xy), _d(map_xy), _i(mt), C.byref(p), _d(rec["pose"]), _i(rec["count"]),
-                                               _d(rec["cost"]), _i(rec["seed"]), _i(rec["second_count"]) if second else None,
-                                               _d(rec["second_pose"]) if second else None, rec["n_seeds"].ctypes.data_as(lp), _i(rec["status"]), _i(idx), _d(e2)))
+        rec = _reloc_record(nf); ra = _reloc_record_args(rec, second); idx = np.zeros(n, dtype=np.int32); e2 = np.zeros(n)
+        self._check(self.L.gs_relocalize_batch(self.h, n, _d(obs), nf, _i(fs), len(map_xy), _d(map_xy), _i(mt), C.byref(p), *ra,
+                                               _i(idx), _d(e2)))
         return rec, idx, e2
+
+    def _relocalize_resident_args(self, d_obs, n, n_frames, d_frame_start, d_pose, d_count, d_cost, d_seed, d_second_count, d_second_pose, d_n_seeds, d_status,
+                                  d_index, d_e2, params):
+        return [self.h, int(n), d_obs.ptr, int(n_frames), d_frame_start.ptr, C.byref(reloc_params() if params is None else params), _ptr(d_pose), _ptr(d_count),
+                _ptr(d_cost), _ptr(d_seed), _ptr(d_second_count), _ptr(d_second_pose), _ptr(d_n_seeds), _ptr(d_status), _ptr(d_index), _ptr(d_e2)]
 
     def relocalize_resident(self, d_obs, n, n_frames, d_frame_start, d_pose=None, d_count=None, d_cost=None, d_seed=None, d_second_count=None,
                             d_second_pose=None, d_n_seeds=None, d_status=None, d_index=None, d_e2=None, params=None):
         """gs_relocalize_resident: the resident map, everything else DeviceArray; asynchronous (synchronize() before reading)"""
-        p = reloc_params() if params is None else params
-        opt = lambda a: None if a is None else a.ptr
-        self._check(self.L.gs_relocalize_resident(self.h, int(n), d_obs.ptr, int(n_frames), d_frame_start.ptr, C.byref(p), opt(d_pose), opt(d_count), opt(d_cost),
-                                                  opt(d_seed), opt(d_second_count), opt(d_second_pose), opt(d_n_seeds), opt(d_status), opt(d_index), opt(d_e2)))
+        self._check(self.L.gs_relocalize_resident(*self._relocalize_resident_args(d_obs, n, n_frames, d_frame_start, d_pose, d_count, d_cost, d_seed, d_second_count,
+                                                                                  d_second_pose, d_n_seeds, d_status, d_index, d_e2, params)))
 
     def time_relocalize_resident(self, d_obs, n, n_frames, d_frame_start, reps, d_pose=None, d_count=None, d_cost=None, d_seed=None, d_second_count=None,
                                  d_second_pose=None, d_n_seeds=None, d_status=None, d_index=None, d_e2=None, params=None):
-        p = reloc_params() if params is None else params
-        opt = lambda a: None if a is None else a.ptr
-        ms = C.c_double()
-        self._check(self.L.gs_debug_time_relocalize_resident(self.h, int(n), d_obs.ptr, int(n_frames), d_frame_start.ptr, C.byref(p), opt(d_pose), opt(d_count),
-                                                             opt(d_cost), opt(d_seed), opt(d_second_count), opt(d_second_pose), opt(d_n_seeds), opt(d_status),
-                                                             opt(d_index), opt(d_e2), int(reps), C.byref(ms)))
-        return ms.value
+        return self._timed(self.L.gs_debug_time_relocalize_resident,
+                           self._relocalize_resident_args(d_obs, n, n_frames, d_frame_start, d_pose, d_count, d_cost, d_seed, d_second_count, d_second_pose, d_n_seeds,
+                                                          d_status, d_index, d_e2, params), reps)
 
     def debug_relocalize(self, slice_cones=0):
         """gs_debug_relocalize: the cones p a workgroup of the seed kernel enumerates (0: the launcher's choice); results do not depend on it"""
@@ -1395,15 +1013,11 @@ class Graph:
         obs = _f64(obs, (-1, 4)); k = len(obs)
         r = reloc_params() if reloc is None else reloc
         p = nn_params() if params is None else params; j = jc_params() if jc is None else jc; l = loc_params() if loc is None else loc
-        sr = _reloc_record(1); si = np.zeros(k, dtype=np.int32); se = np.zeros(k); lp = C.POINTER(C.c_int64)
+        sr = _reloc_record(1); sa = _reloc_record_args(sr, second); si = np.zeros(k, dtype=np.int32); se = np.zeros(k)
         z = np.zeros((k, 2)); gx = np.zeros((k, 2)); idx = np.zeros(k, dtype=np.int32); d2 = np.zeros(k); na = np.zeros(k, dtype=np.int32)
-        rec = _jc_record(1); lr = _loc_record(1)
+        (rec, ra), (lr, la) = _jc_record(1), _loc_record(1)
         self._check(self.L.gs_frame_frontend_relocalize(self.h, _d(obs), k, C.byref(r), float(prior_sigma_xy), float(prior_sigma_theta), C.byref(p), C.byref(j), C.byref(l),
-                                                        _d(sr["pose"]), _i(sr["count"]), _d(sr["cost"]), _i(sr["seed"]), _i(sr["second_count"]) if second else None,
-                                                        _d(sr["second_pose"]) if second else None, sr["n_seeds"].ctypes.data_as(lp), _i(sr["status"]), _i(si), _d(se),
-                                                        _d(z), _d(gx), _i(idx), _d(d2), _i(na), _d(rec["joint_d2"]), _i(rec["n_kept"]), _i(rec["n_dropped"]),
-                                                        _i(rec["n_untestable"]), _d(rec["delta"]), _d(lr["pose"]), _d(lr["cov"]), _d(lr["chi2"]), _i(lr["n_pairs"]),
-                                                        _i(lr["iterations"]), _i(lr["status"])))
+                                                        *sa, _i(si), _d(se), _d(z), _d(gx), _i(idx), _d(d2), _i(na), *ra, *la))
         return sr, si, se, z, gx, idx, d2, na, rec, lr
 
     # ---- frame following (include/graphslam.h): pose hypotheses carried from frame to frame on the device.
@@ -1427,16 +1041,15 @@ class Graph:
         state = np.zeros(nh, dtype=FOLLOW_STATE); best = C.c_int32(-2); nt = C.c_int32(-2)
         o = lambda a: None if a is None else _d(a)
         self._check(self.L.gs_follow_batch(self.h, nh, _d(poses), o(cv), ns, n, _d(obs), _i(fs), o(mo), o(mq), len(map_xy), _d(map_xy), _i(mt), o(mc),
-                                           C.byref(p), C.byref(j), C.byref(l), C.byref(f), steps.ctypes.data_as(C.c_void_p), None if idx is None else _i(idx),
-                                           state.ctypes.data_as(C.c_void_p), C.byref(best), C.byref(nt)))
+                                           C.byref(p), C.byref(j), C.byref(l), C.byref(f), _vp(steps), None if idx is None else _i(idx),
+                                           _vp(state), C.byref(best), C.byref(nt)))
         return {"steps": steps, "index": idx, "state": state, "best": best.value, "n_tracking": nt.value}
 
     def _follow_resident_args(self, d_poses, n_hyp, d_obs, n, n_steps, d_frame_start, frame_cap, d_motion, d_covs, d_motion_cov, d_steps, d_index, d_state,
                               d_best, params, jc, loc, follow):
         p, j, l, f = self._follow_blocks(params, jc, loc, follow)
-        opt = lambda a: None if a is None else a.ptr
-        return [self.h, int(n_hyp), opt(d_poses), opt(d_covs), int(n_steps), int(n), opt(d_obs), opt(d_frame_start), int(frame_cap), opt(d_motion),
-                opt(d_motion_cov), C.byref(p), C.byref(j), C.byref(l), C.byref(f), opt(d_steps), opt(d_index), opt(d_state), opt(d_best)]
+        return [self.h, int(n_hyp), _ptr(d_poses), _ptr(d_covs), int(n_steps), int(n), _ptr(d_obs), _ptr(d_frame_start), int(frame_cap), _ptr(d_motion),
+                _ptr(d_motion_cov), C.byref(p), C.byref(j), C.byref(l), C.byref(f), _ptr(d_steps), _ptr(d_index), _ptr(d_state), _ptr(d_best)]
 
     def follow_resident(self, d_poses, n_hyp, d_obs, n, n_steps, d_frame_start, frame_cap, d_motion=None, d_covs=None, d_motion_cov=None, d_steps=None,
                         d_index=None, d_state=None, d_best=None, params=None, jc=None, loc=None, follow=None):
@@ -1447,11 +1060,9 @@ class Graph:
     def time_follow_resident(self, d_poses, n_hyp, d_obs, n, n_steps, d_frame_start, frame_cap, reps, d_motion=None, d_covs=None, d_motion_cov=None,
                              d_steps=None, d_index=None, d_state=None, d_best=None, params=None, jc=None, loc=None, follow=None):
         """gs_debug_time_follow_resident: mean milliseconds per run, events from the run's first dispatch to its last"""
-        ms = C.c_double()
-        a = self._follow_resident_args(d_poses, n_hyp, d_obs, n, n_steps, d_frame_start, frame_cap, d_motion, d_covs, d_motion_cov, d_steps, d_index,
-                                       d_state, d_best, params, jc, loc, follow)
-        self._check(self.L.gs_debug_time_follow_resident(*(a + [int(reps), C.byref(ms)])))
-        return ms.value
+        return self._timed(self.L.gs_debug_time_follow_resident,
+                           self._follow_resident_args(d_poses, n_hyp, d_obs, n, n_steps, d_frame_start, frame_cap, d_motion, d_covs, d_motion_cov, d_steps, d_index,
+                                                      d_state, d_best, params, jc, loc, follow), reps)
 
     def follow_set(self, poses, covs=None):
         """gs_follow_set: put the hypotheses on the handle; the next frame_frontend_follow takes no motion"""
@@ -1463,7 +1074,7 @@ class Graph:
     def follow_get(self):
         """gs_follow_get: (state [n_hyp], best, n_tracking) of the live run"""
         state = np.zeros(FOLLOW_HYP_MAX, dtype=FOLLOW_STATE); nh = C.c_int32(0); best = C.c_int32(-2); nt = C.c_int32(-2)
-        self._check(self.L.gs_follow_get(self.h, state.ctypes.data_as(C.c_void_p), C.byref(nh), C.byref(best), C.byref(nt)))
+        self._check(self.L.gs_follow_get(self.h, _vp(state), C.byref(nh), C.byref(best), C.byref(nt)))
         return state[:nh.value].copy(), best.value, nt.value
 
     def frame_frontend_follow(self, obs, motion=None, motion_cov=None, params=None, jc=None, loc=None, follow=None):
@@ -1474,7 +1085,7 @@ class Graph:
         steps = np.zeros(FOLLOW_HYP_MAX, dtype=FOLLOW_STEP); idx = np.zeros(FOLLOW_HYP_MAX * max(k, 1), dtype=np.int32)
         nh = getattr(self, "_follow_n_hyp", 0); best = C.c_int32(-2); nt = C.c_int32(-2)
         self._check(self.L.gs_frame_frontend_follow(self.h, None if mo is None else _d(mo), None if mq is None else _d(mq), _d(obs), k, C.byref(p), C.byref(j),
-                                                    C.byref(l), C.byref(f), steps.ctypes.data_as(C.c_void_p), _i(idx), C.byref(best), C.byref(nt)))
+                                                    C.byref(l), C.byref(f), _vp(steps), _i(idx), C.byref(best), C.byref(nt)))
         return steps[:nh].copy(), idx[:nh * k].reshape(nh, k).copy(), best.value, nt.value
 
     # ---- cone candidates (include/graphslam.h): unmatched observations tracked into new map cones on the device.
@@ -1487,7 +1098,7 @@ class Graph:
     def _cand_records(table):
         """a table to load: CAND records, slot s at [s] (None: none)"""
         t = np.zeros(0, dtype=CAND) if table is None else np.ascontiguousarray(table, dtype=CAND).reshape(-1)
-        return t, (t.ctypes.data_as(C.c_void_p) if len(t) else None)
+        return t, (_vp(t) if len(t) else None)
 
     def cand(self, poses, obs, frame_start, in_idx=None, pose_covs=None, table=None, params=None, cand=None):
         """gs_cand_batch: {"steps", "cand_id", "cand_slot", "table", "n_live"} of a run over all frames from the table given (None: empty)"""
@@ -1498,15 +1109,14 @@ class Graph:
         steps = np.zeros(max(ns, 0), dtype=CAND_STEP); cid = np.zeros(n, dtype=np.int32); slot = np.zeros(n, dtype=np.int32)
         out = np.zeros(CAND_MAX, dtype=CAND); nl = C.c_int32(-2)
         self._check(self.L.gs_cand_batch(self.h, ns, n, _d(obs), _i(fs), _d(poses), None if pc is None else _d(pc), None if ii is None else _i(ii), len(tab), tp,
-                                         C.byref(p), C.byref(c), steps.ctypes.data_as(C.c_void_p), _i(cid), _i(slot), out.ctypes.data_as(C.c_void_p), C.byref(nl)))
+                                         C.byref(p), C.byref(c), _vp(steps), _i(cid), _i(slot), _vp(out), C.byref(nl)))
         return {"steps": steps, "cand_id": cid, "cand_slot": slot, "table": out, "n_live": nl.value}
 
     def _cand_resident_args(self, d_obs, n, n_steps, d_frame_start, frame_cap, d_poses, d_pose_covs, d_in_idx, n_in, d_table, d_steps, d_cand_id, d_cand_slot,
                             d_out_table, d_meta, params, cand):
         p, c = self._cand_blocks(params, cand)
-        opt = lambda a: None if a is None else a.ptr
-        return [self.h, int(n_steps), int(n), opt(d_obs), opt(d_frame_start), int(frame_cap), opt(d_poses), opt(d_pose_covs), opt(d_in_idx), int(n_in), opt(d_table),
-                C.byref(p), C.byref(c), opt(d_steps), opt(d_cand_id), opt(d_cand_slot), opt(d_out_table), opt(d_meta)]
+        return [self.h, int(n_steps), int(n), _ptr(d_obs), _ptr(d_frame_start), int(frame_cap), _ptr(d_poses), _ptr(d_pose_covs), _ptr(d_in_idx), int(n_in),
+                _ptr(d_table), C.byref(p), C.byref(c), _ptr(d_steps), _ptr(d_cand_id), _ptr(d_cand_slot), _ptr(d_out_table), _ptr(d_meta)]
 
     def cand_resident(self, d_obs, n, n_steps, d_frame_start, frame_cap, d_poses, d_pose_covs=None, d_in_idx=None, n_in=0, d_table=None, d_steps=None,
                       d_cand_id=None, d_cand_slot=None, d_out_table=None, d_meta=None, params=None, cand=None):
@@ -1517,11 +1127,9 @@ class Graph:
     def time_cand_resident(self, d_obs, n, n_steps, d_frame_start, frame_cap, d_poses, reps, d_pose_covs=None, d_in_idx=None, n_in=0, d_table=None, d_steps=None,
                            d_cand_id=None, d_cand_slot=None, d_out_table=None, d_meta=None, params=None, cand=None):
         """gs_debug_time_cand_resident: mean milliseconds per run, events from the run's first dispatch to its last"""
-        ms = C.c_double()
-        a = self._cand_resident_args(d_obs, n, n_steps, d_frame_start, frame_cap, d_poses, d_pose_covs, d_in_idx, n_in, d_table, d_steps, d_cand_id, d_cand_slot,
-                                     d_out_table, d_meta, params, cand)
-        self._check(self.L.gs_debug_time_cand_resident(*(a + [int(reps), C.byref(ms)])))
-        return ms.value
+        return self._timed(self.L.gs_debug_time_cand_resident,
+                           self._cand_resident_args(d_obs, n, n_steps, d_frame_start, frame_cap, d_poses, d_pose_covs, d_in_idx, n_in, d_table, d_steps, d_cand_id,
+                                                    d_cand_slot, d_out_table, d_meta, params, cand), reps)
 
     def cand_clear(self):
         self._check(self.L.gs_cand_clear(self.h))
@@ -1534,13 +1142,13 @@ class Graph:
     def cand_get(self):
         """gs_cand_get: (table [CAND_MAX], next_id, step, n_live) of the live table"""
         out = np.zeros(CAND_MAX, dtype=CAND); ni = C.c_int32(-2); t = C.c_int32(-2); nl = C.c_int32(-2)
-        self._check(self.L.gs_cand_get(self.h, out.ctypes.data_as(C.c_void_p), C.byref(ni), C.byref(t), C.byref(nl)))
+        self._check(self.L.gs_cand_get(self.h, _vp(out), C.byref(ni), C.byref(t), C.byref(nl)))
         return out, ni.value, t.value, nl.value
 
     def cand_take_confirmed(self):
         """gs_cand_take_confirmed: the confirmed records in ascending id; their slots are free afterwards"""
         out = np.zeros(CAND_MAX, dtype=CAND); n = C.c_int32(0)
-        self._check(self.L.gs_cand_take_confirmed(self.h, CAND_MAX, out.ctypes.data_as(C.c_void_p), C.byref(n)))
+        self._check(self.L.gs_cand_take_confirmed(self.h, CAND_MAX, _vp(out), C.byref(n)))
         return out[:n.value].copy()
 
     def cand_promote(self):
@@ -1559,50 +1167,48 @@ class Graph:
         p, c = self._cand_blocks(params, cand)
         step = np.zeros(1, dtype=CAND_STEP); cid = np.zeros(max(k, 1), dtype=np.int32); slot = np.zeros(max(k, 1), dtype=np.int32)
         self._check(self.L.gs_frame_frontend_candidates(self.h, _d(pose), None if pc is None else _d(pc), _d(obs), k, None if ii is None else _i(ii), C.byref(p),
-                                                        C.byref(c), step.ctypes.data_as(C.c_void_p), _i(cid), _i(slot)))
+                                                        C.byref(c), _vp(step), _i(cid), _i(slot)))
         return step[0].copy(), cid[:k].copy(), slot[:k].copy()
 
     # ---- map twins (include/graphslam.h): duplicate cones found, fused and merged in the graph.  params = DupParams (None: the defaults)
-    def map_twins(self, map_xy, map_type, map_cov=None, params=None):
-        """gs_map_twins_batch: (twin [n] int32, d2 [n], second_d2 [n], n_admissible [n] int32) of a host map"""
+    @staticmethod
+    def _host_map(map_xy, map_type, map_cov):
+        """a host map, converted and checked: (n, the C arguments n, xy, type, covariances or NULL)"""
         xy = _f64(map_xy, (-1, 2)); ty = _i32(map_type); n = len(ty); mc = None if map_cov is None else _f64(map_cov, (-1, 4))
         assert len(xy) == n and (mc is None or len(mc) == n)
+        return n, [n, _d(xy), _i(ty), None if mc is None else _d(mc)]
+
+    def map_twins(self, map_xy, map_type, map_cov=None, params=None):
+        """gs_map_twins_batch: (twin [n] int32, d2 [n], second_d2 [n], n_admissible [n] int32) of a host map"""
+        n, a = self._host_map(map_xy, map_type, map_cov)
         p = dup_params() if params is None else params
         tw = np.zeros(max(n, 1), dtype=np.int32); d2 = np.zeros(max(n, 1)); sec = np.zeros(max(n, 1)); na = np.zeros(max(n, 1), dtype=np.int32)
-        self._check(self.L.gs_map_twins_batch(self.h, n, _d(xy), _i(ty), None if mc is None else _d(mc), C.byref(p), _i(tw), _d(d2), _d(sec), _i(na)))
+        self._check(self.L.gs_map_twins_batch(self.h, *a, C.byref(p), _i(tw), _d(d2), _d(sec), _i(na)))
         return tw[:n].copy(), d2[:n].copy(), sec[:n].copy(), na[:n].copy()
+
+    def _map_twins_resident_args(self, d_twin, d_d2, d_second, d_n_admissible, params):
+        return [self.h, C.byref(dup_params() if params is None else params), _ptr(d_twin), _ptr(d_d2), _ptr(d_second), _ptr(d_n_admissible)]
 
     def map_twins_resident(self, d_twin, d_d2=None, d_second=None, d_n_admissible=None, params=None):
         """gs_map_twins_resident: the resident map and its covariances, outputs DeviceArray; asynchronous (synchronize() before reading)"""
-        p = dup_params() if params is None else params
-        opt = lambda a: None if a is None else a.ptr
-        self._check(self.L.gs_map_twins_resident(self.h, C.byref(p), opt(d_twin), opt(d_d2), opt(d_second), opt(d_n_admissible)))
+        self._check(self.L.gs_map_twins_resident(*self._map_twins_resident_args(d_twin, d_d2, d_second, d_n_admissible, params)))
 
     def time_map_twins_resident(self, d_twin, reps, d_d2=None, d_second=None, d_n_admissible=None, params=None):
         """gs_debug_time_map_twins_resident: mean milliseconds per call, events on the search's dispatch"""
-        p = dup_params() if params is None else params
-        opt = lambda a: None if a is None else a.ptr
-        ms = C.c_double()
-        self._check(self.L.gs_debug_time_map_twins_resident(self.h, C.byref(p), opt(d_twin), opt(d_d2), opt(d_second), opt(d_n_admissible), int(reps), C.byref(ms)))
-        return ms.value
+        return self._timed(self.L.gs_debug_time_map_twins_resident, self._map_twins_resident_args(d_twin, d_d2, d_second, d_n_admissible, params), reps)
 
     def time_map_merge_twins(self, reps, params=None):
         """gs_debug_time_map_merge_twins: mean milliseconds of the consolidation's four dispatches over the resident map, which stays as it is"""
-        p = dup_params() if params is None else params
-        ms = C.c_double()
-        self._check(self.L.gs_debug_time_map_merge_twins(self.h, C.byref(p), int(reps), C.byref(ms)))
-        return ms.value
+        return self._timed(self.L.gs_debug_time_map_merge_twins, [self.h, C.byref(dup_params() if params is None else params)], reps)
 
     def map_merge_twins_batch(self, map_xy, map_type, map_cov=None, params=None):
         """gs_map_merge_twins_batch: (xy [n_out,2], type [n_out], cov [n_out,2,2] or None, remap [n], info) of a host map"""
-        xy = _f64(map_xy, (-1, 2)); ty = _i32(map_type); n = len(ty); mc = None if map_cov is None else _f64(map_cov, (-1, 4))
-        assert len(xy) == n and (mc is None or len(mc) == n)
+        n, a = self._host_map(map_xy, map_type, map_cov)
         p = dup_params() if params is None else params
         m = max(n, 1)
-        oxy = np.zeros((m, 2)); oty = np.zeros(m, dtype=np.int32); ocv = None if mc is None else np.zeros((m, 2, 2)); rm = np.zeros(m, dtype=np.int32)
+        oxy = np.zeros((m, 2)); oty = np.zeros(m, dtype=np.int32); ocv = None if map_cov is None else np.zeros((m, 2, 2)); rm = np.zeros(m, dtype=np.int32)
         info = np.zeros(1, dtype=DUP_INFO)
-        self._check(self.L.gs_map_merge_twins_batch(self.h, n, _d(xy), _i(ty), None if mc is None else _d(mc), C.byref(p), _d(oxy), _i(oty),
-                                                    None if ocv is None else _d(ocv), _i(rm), info.ctypes.data_as(C.c_void_p)))
+        self._check(self.L.gs_map_merge_twins_batch(self.h, *a, C.byref(p), _d(oxy), _i(oty), None if ocv is None else _d(ocv), _i(rm), _vp(info)))
         k = int(info[0]["n_out"])
         return oxy[:k].copy(), oty[:k].copy(), None if ocv is None else ocv[:k].copy(), rm[:n].copy(), info[0].copy()
 
@@ -1610,7 +1216,7 @@ class Graph:
         """gs_map_merge_twins: the resident map consolidated in place; (remap [map size before], info)"""
         p = dup_params() if params is None else params
         n = self.map_size(); rm = np.zeros(max(n, 1), dtype=np.int32); info = np.zeros(1, dtype=DUP_INFO)
-        self._check(self.L.gs_map_merge_twins(self.h, C.byref(p), len(rm), _i(rm), info.ctypes.data_as(C.c_void_p)))
+        self._check(self.L.gs_map_merge_twins(self.h, C.byref(p), len(rm), _i(rm), _vp(info)))
         return rm[:n].copy(), info[0].copy()
 
     def map_xy(self, first=0, n=None):
@@ -1715,7 +1321,7 @@ class Graph:
         return done, st
 
     def time_exchange(self, reps):
-        ms = C.c_double(); self._check(self.L.gs_debug_time_exchange(self.h, int(reps), C.byref(ms))); return ms.value
+        return self._timed(self.L.gs_debug_time_exchange, [self.h], reps)
 
     def dist_iterate_local(self):
         self._check(self.L.gs_dist_iterate_local(self.h))
